@@ -10,6 +10,7 @@ own chunks back to RGB.  Chunks are independent bitstreams, so ranks share no da
 batch from the free HBM: one rANS chain is one wavefront, and what bounds the chains in flight is memory.
 
     python bench.py --gpus 1 --steps 2 --warmup 1
+    python bench.py --gpus 1 --steps 2 --warmup 1 --dump-outputs DIR   # + a fixed sample of the last step's outputs as .npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -79,6 +80,77 @@ def synth_chunk(dev, idx: int):
     base = 128 + 90 * torch.sin((x + 2 * t + 5 * idx) / s + ph) * torch.cos((y - t) / (0.7 * s))
     noise = torch.randint(-4, 5, (F, H, W, 3), device=dev, generator=g)
     return (base + noise).round().clamp(0, 255).to(torch.uint8)
+
+
+# ---- --dump-outputs: what the timed path handed back in its last step, as .npy files ---------------------------------
+# The batch is far larger than the 64 MB the dump may take (337 chunks x 398 MB of decoded RGB), so a fixed set of chunks is
+# written: each one's .alc size and byte sum, its first DUMP_ALC_HEAD bytes (header and tables), a seeded sample of its
+# .alc bytes, and the sum and a seeded sample of its decoded RGB.  The chunk indices and sample positions depend on
+# nothing but the chunk count, and the inputs on nothing but the chunk index, so two builds compare array for array.
+DUMP_CHUNKS = (0, 1, 2, 3, 11, 47, 101, 199)   # those below the batch's chunk count
+DUMP_ALC_HEAD = 4096
+DUMP_ALC_SAMPLES = 1 << 18
+DUMP_RGB_SAMPLES = 1 << 20
+DUMP_SEED = 20251015
+DUMP_MAX_BYTES = 64 << 20
+_SUM_SLICE = 8 << 20   # elements per int64 reduction: HBM is nearly full after the timed steps
+
+
+def dump_plan(n_chunks: int, rgb_elems: int = W * H * F * 3):
+    """(chunk indices, .alc sample fractions in [0, 1), decoded RGB sample positions).  Pure, numpy only."""
+    import numpy as _np
+    rng = _np.random.default_rng(DUMP_SEED)
+    chunks = [c for c in DUMP_CHUNKS if c < n_chunks]
+    alc_frac = _np.sort(rng.random(DUMP_ALC_SAMPLES))
+    rgb_pos = _np.sort(rng.integers(0, rgb_elems, DUMP_RGB_SAMPLES, dtype=_np.int64))
+    return chunks, alc_frac, rgb_pos
+
+
+def dump_nbytes(n_chunks: int) -> int:
+    """Bytes the .npy payloads of dump_outputs() take for a batch of n_chunks (float32 samples, float64 per-chunk values)."""
+    n = len([c for c in DUMP_CHUNKS if c < n_chunks])
+    return n * (4 * (DUMP_ALC_HEAD + DUMP_ALC_SAMPLES + DUMP_RGB_SAMPLES) + 8 * 3)
+
+
+def _exact_sum(t) -> int:
+    """Sum of a uint8 device tensor, in int64 slices (each slice's temporary stays small)."""
+    s = 0
+    for i in range(0, t.numel(), _SUM_SLICE):
+        s += int(t[i:i + _SUM_SLICE].sum(dtype=torch.int64).item())
+    return s
+
+
+def dump_outputs(path: str, n_chunks: int, sizes, alc_view, rgb_view, dev) -> dict:
+    """Write the sampled outputs of the last timed step to path/<name>.npy.  alc_view(i, nbytes) / rgb_view(i): uint8
+    device tensors of chunk i's .alc bytes and decoded RGB."""
+    chunks, alc_frac, rgb_pos = dump_plan(n_chunks)
+    rgb_idx = torch.from_numpy(rgb_pos).to(dev)
+    alc_sizes, alc_sums, alc_sample, rgb_sums, rgb_sample = [], [], [], [], []
+    for c in chunks:
+        n = int(sizes[c])
+        alc = alc_view(c, n)
+        head = torch.zeros(DUMP_ALC_HEAD, dtype=torch.float32)
+        head[:min(n, DUMP_ALC_HEAD)] = alc[:DUMP_ALC_HEAD].float().cpu()
+        pos = torch.from_numpy(np.minimum((alc_frac * n).astype(np.int64), max(n - 1, 0))).to(dev)
+        alc_sizes.append(n)
+        alc_sums.append(_exact_sum(alc))
+        alc_sample.append(torch.cat([head, alc[pos].float().cpu()]).numpy())
+        rgb = rgb_view(c)
+        rgb_sums.append(_exact_sum(rgb))
+        rgb_sample.append(rgb[rgb_idx].float().cpu().numpy())
+    arrays = {
+        "alc_sizes": np.asarray(alc_sizes, dtype=np.float64),
+        "alc_byte_sums": np.asarray(alc_sums, dtype=np.float64),
+        "alc_bytes_sample": np.asarray(alc_sample, dtype=np.float32).reshape(len(chunks), DUMP_ALC_HEAD + DUMP_ALC_SAMPLES),
+        "decoded_rgb_sums": np.asarray(rgb_sums, dtype=np.float64),
+        "decoded_rgb_sample": np.asarray(rgb_sample, dtype=np.float32).reshape(len(chunks), DUMP_RGB_SAMPLES),
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, total
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {"dir": os.path.abspath(path), "chunks": chunks, "files": sorted(n + ".npy" for n in arrays), "bytes": int(total)}
 
 
 def native_oracle():
@@ -211,7 +283,15 @@ def parse_args(argv=None):
                          "on to pinned host memory (8 GPUs x 337 chunks x 0.11 GB = 296 GB per step over rank 0's one PCIe link)")
     ap.add_argument("--no-host-api", action="store_true",
                     help="skip the drop-in host-call measurement (T host threads through alice_codec_encode64 / decode64)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed seeded sample of what the last step computed (.alc bytes and "
+                         "decoded RGB of rank 0's chunks) as DIR/<name>.npy, float32 / float64, at most 64 MB")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error(f"--steps {args.steps}: at least one timed step")
+    if args.warmup < 0:
+        ap.error(f"--warmup {args.warmup}: must not be negative")
+    return args
 
 
 # ---- N ranks from one command ------------------------------------------------------------------------------------
@@ -464,6 +544,16 @@ def main(argv=None) -> None:
     print(f"[bench] rank {rank}: {B} chunks, HBM free {free_b / 1e9:.1f} GB of {total_b / 1e9:.1f} GB "
           f"({100.0 * free_b / total_b:.1f} %) after the timed steps", file=sys.stderr)
 
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(
+            args.dump_outputs, B, sizes,
+            lambda i, n: multi.DeviceView(batch.alc_ptr(i), n).tensor(dev),
+            lambda i: out[i].reshape(-1) if out is not None else multi.DeviceView(batch.rgb_ptr(i), px_chunk * 3).tensor(dev),
+            dev)
+        print(f"[bench] wrote {len(dumped['files'])} arrays ({dumped['bytes'] / 1e6:.1f} MB) of chunks {dumped['chunks']} "
+              f"to {dumped['dir']}", file=sys.stderr)
+
     # ---- what the timed steps left in the batch, against the oracle: first and last chunk, all 64 frames, every rank
     verdict = None
     bit_exact = None
@@ -565,6 +655,8 @@ def main(argv=None) -> None:
             result["cpu_baseline"] = verdict
         if host_api is not None:
             result["host_api"] = host_api
+        if dumped is not None:
+            result["dump_outputs"] = dumped
         _RESULT_OUT.write(json.dumps(result) + "\n")
         _RESULT_OUT.flush()
     if use_dist:

@@ -73,3 +73,31 @@ def test_spawn_dry_run_shows_two_children():
     assert [p["env"]["RANK"] for p in plan] == ["0", "1"]
     assert all(p["env"]["WORLD_SIZE"] == "2" and p["cmd"][1:] == [BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1"] for p in plan)
     assert len({p["env"]["MASTER_PORT"] for p in plan}) == 1
+
+
+def test_dump_plan_is_fixed_and_within_bounds():
+    """--dump-outputs: the same chunk count gives the same chunks and sample positions, inside the buffers, under 64 MB."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    px3 = bench.W * bench.H * bench.F * 3
+    c1, a1, r1 = bench.dump_plan(337)
+    c2, a2, r2 = bench.dump_plan(337)
+    assert c1 == c2 and np.array_equal(a1, a2) and np.array_equal(r1, r2)
+    assert c1 == list(bench.DUMP_CHUNKS)
+    assert bench.dump_plan(3)[0] == [0, 1, 2] and bench.dump_plan(1)[0] == [0]
+    assert a1.min() >= 0.0 and a1.max() < 1.0
+    assert r1.dtype == np.int64 and r1.min() >= 0 and r1.max() < px3
+    assert 0 < bench.dump_nbytes(337) <= 64 << 20
+    assert bench.dump_nbytes(1) < bench.dump_nbytes(337)
+
+
+def test_steps_and_warmup_are_checked():
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--steps", "7", "--warmup", "0", "--dump-outputs", "d"])
+    assert (a.steps, a.warmup, a.dump_outputs) == (7, 0, "d")
+    assert bench.parse_args([]).dump_outputs is None
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        out = subprocess.run([sys.executable, BENCH, "--gpus", "1"] + bad, capture_output=True, text=True, env=_env(), timeout=120)
+        assert out.returncode != 0 and out.stdout.strip() == ""
