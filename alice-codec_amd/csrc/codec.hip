@@ -53,6 +53,13 @@ int fail(int code, const std::string& msg) {
 }
 void clear_error() { tl_err = kOk; tl_msg.clear(); }
 
+// ALICE_CODEC_DEBUG set: the hub's launches and every chain's result go to stderr.  Read once: the library calls setenv
+// (widen_hw_queues_once), and getenv concurrent with setenv is not thread-safe.
+bool debug_on() {
+    static const bool on = getenv("ALICE_CODEC_DEBUG") != nullptr;
+    return on;
+}
+
 #define HIP_TRY(expr)                                                                          \
     do {                                                                                       \
         hipError_t e__ = (expr);                                                               \
@@ -334,7 +341,7 @@ public:
         in_flight_ += bytes;
         ++serving_;
         adm_cv_.notify_all();
-        if (getenv("ALICE_CODEC_DEBUG"))
+        if (debug_on())
             fprintf(stderr, "[alice] hub: admitted %.2f GB, %.2f GB in flight of a budget of %.2f GB\n", bytes / 1e9, in_flight_ / 1e9, budget_ / 1e9);
     }
     void leave(size_t bytes) { { std::lock_guard<std::mutex> g(adm_mu_); in_flight_ -= std::min(in_flight_, bytes); } adm_cv_.notify_all(); }
@@ -381,7 +388,7 @@ public:
             } catch (const std::exception& e) {   // host allocation failure while merging the descriptors
                 L->rc = kOutOfMemory; L->msg = std::string("merged chain launch: ") + e.what();
             }
-            if (getenv("ALICE_CODEC_DEBUG")) {
+            if (debug_on()) {
                 static const auto t0 = std::chrono::steady_clock::now();
                 fprintf(stderr, "[alice] hub: t=%.3f s, %s launch of %zu calls, %zu chains, lane %d\n",
                         std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), job.encode ? "encode" : "decode",
@@ -456,15 +463,12 @@ struct HubTicket {
     size_t admitted = 0;
     // device_bytes: what the call is about to allocate on the device, roughly (see ChainHub::admit)
     int open(size_t device_bytes) {
-        TRY(ensure_device());
+        TRY(get_stream(&st));
         hub = ChainHub::of_device(tl_device);
-        if (!hub->ok()) return fail(kDeviceError, "the streams of the chain hub could not be created");
         hub->admit(device_bytes);
         admitted = device_bytes;
         hub->announce();
         counted = true;
-        st = hub->short_stream();
-        tl_scope_stream = st;
         return kOk;
     }
     void arrived() { if (counted) { counted = false; hub->arrived_or_gone(); } }
@@ -528,50 +532,44 @@ int copy_to_host(void* dst, const void* d_src, size_t bytes, hipStream_t st) {
     return kOk;
 }
 
-// fn(i) for i in [0, n) on up to `width` helper threads bound to the calling thread's device (the copies of a many-chunk
-// call: every helper moves its chunks through pinned pieces of its own, so the CPU side of the copies runs side by side).
+// fn(t) on T new threads, thread t with a clean error state and device_of(t) as its device (fn calls ensure_device).
 // Returns the first failure, with its message, as this thread's error.
-template <typename Fn>
-int parallel_chunks(uint32_t n, uint32_t width, Fn fn) {
-    if (n <= 1 || width <= 1) {
-        for (uint32_t i = 0; i < n; ++i) TRY(fn(i));
-        return kOk;
-    }
-    const uint32_t T = std::min(width, n);
-    const int device = tl_device;
+template <typename Dev, typename Fn>
+int on_threads(uint32_t T, Dev device_of, Fn fn) {
     std::vector<int> code(T, kOk);
     std::vector<std::string> msg(T);
-    std::atomic<uint32_t> next{0};
     std::vector<std::thread> th;
     th.reserve(T);
     for (uint32_t t = 0; t < T; ++t)
         th.emplace_back([&, t] {
             clear_error();
-            tl_device = device;
-            int rc = ensure_device();
-            for (uint32_t i; rc == kOk && (i = next.fetch_add(1u)) < n;) rc = fn(i);
-            code[t] = rc;
-            if (rc != kOk) msg[t] = tl_msg;
+            tl_device = device_of(t);
+            code[t] = fn(t);
+            if (code[t] != kOk) msg[t] = tl_msg;
         });
     for (auto& t : th) t.join();
     for (uint32_t t = 0; t < T; ++t)
         if (code[t] != kOk) return fail(code[t], msg[t]);
     return kOk;
 }
-constexpr uint32_t kCopyThreads = 8;
 
-// records `ready` on st, runs the job through the hub, destroys the event
-int hub_run(ChainHub* hub, HubTicket* t, HubJob& job, hipStream_t st) {
-    HIP_TRY(hipEventCreateWithFlags(&job.ready, hipEventDisableTiming));
-    int rc = kOk;
-    if (hipEventRecord(job.ready, st) != hipSuccess) rc = fail(kDeviceError, "hipEventRecord failed");
-    if (t) t->arrived();
-    if (rc == kOk) rc = hub->run(job);
-    (void)hipEventDestroy(job.ready);
-    job.ready = nullptr;
-    return rc;
+// fn(i) for i in [0, n) on up to `width` helper threads bound to the calling thread's device (the copies of a many-chunk
+// call: every helper moves its chunks through pinned pieces of its own, so the CPU side of the copies runs side by side).
+template <typename Fn>
+int parallel_chunks(uint32_t n, uint32_t width, Fn fn) {
+    if (n <= 1 || width <= 1) {
+        for (uint32_t i = 0; i < n; ++i) TRY(fn(i));
+        return kOk;
+    }
+    const int device = tl_device;
+    std::atomic<uint32_t> next{0};
+    return on_threads(std::min(width, n), [&](uint32_t) { return device; }, [&](uint32_t) {
+        TRY(ensure_device());
+        for (uint32_t i; (i = next.fetch_add(1u)) < n;) TRY(fn(i));
+        return (int)kOk;
+    });
 }
-int hub_run(HubTicket& t, HubJob& job, hipStream_t st) { return hub_run(t.hub, &t, job, st); }
+constexpr uint32_t kCopyThreads = 8;
 
 // Every host entry point works on a short stream of its device's hub: the library owns kHubShort + kHubLanes streams per
 // device and none per calling thread.
@@ -584,16 +582,23 @@ int get_stream(hipStream_t* out) {
     return kOk;
 }
 
-// The chains of a stage-level call (RansEncoder / RansDecoder objects, the one-shot and the interleaved calls): they may run
-// for seconds, so they too leave with the hub's merged launches instead of sitting on a short stream.  `st`: the short
-// stream the call's other work is on (the chains' inputs are complete at this point of it).
-int stage_chains(hipStream_t st, std::vector<RansEncodeDesc>&& enc, std::vector<RansDecodeDesc>&& dec, uint64_t symbols_per_chain) {
+// Hands a call's chains to the hub's next merged launch and returns when they have run; `st`: the short stream the call's
+// other work is on (the chains' inputs are complete at this point of it).  Whole-chunk calls pass their ticket; the chains
+// of the stage-level calls may run for seconds too, so they also leave with the merged launches instead of sitting on `st`.
+int hub_chains(hipStream_t st, std::vector<RansEncodeDesc>&& enc, std::vector<RansDecodeDesc>&& dec, uint64_t symbols_per_chain,
+               HubTicket* t = nullptr) {
     HubJob job;
     job.encode = !enc.empty();
     job.enc = std::move(enc);
     job.dec = std::move(dec);
     job.seconds = (double)symbols_per_chain * (job.encode ? 21e-9 : 39e-9);
-    return hub_run(ChainHub::of_device(tl_device), nullptr, job, st);
+    HIP_TRY(hipEventCreateWithFlags(&job.ready, hipEventDisableTiming));
+    int rc = kOk;
+    if (hipEventRecord(job.ready, st) != hipSuccess) rc = fail(kDeviceError, "hipEventRecord failed");
+    if (t) t->arrived();
+    if (rc == kOk) rc = (t ? t->hub : ChainHub::of_device(tl_device))->run(job);
+    (void)hipEventDestroy(job.ready);
+    return rc;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -691,6 +696,17 @@ int checked_pixel_count(uint64_t w, uint64_t h, uint64_t f, uint64_t* out) {
     return kOk;
 }
 
+// The shape checks of the calls outside the reference: a pixel count that fits, a non-empty chunk (and `count` chunks of
+// it: a batch of none is empty too), a padded volume the header's u32 num_symbols can count.
+int chunk_dims(uint32_t w, uint32_t h, uint32_t f, ChunkDims* d, uint32_t count = 1) {
+    uint64_t n_pixels = 0;
+    TRY(checked_pixel_count(w, h, f, &n_pixels));
+    if (n_pixels == 0 || count == 0) return fail(kInvalidDimensions, count ? "invalid dimensions" : "empty batch");
+    *d = make_dims(w, h, f);
+    if (d->padded > 0xFFFFFFFFull) return fail(kDimensionOverflow, "padded pixel count does not fit the header's u32 num_symbols");
+    return kOk;
+}
+
 // ------------------------------------------------------------------------------------------
 // encode / decode on device buffers
 // ------------------------------------------------------------------------------------------
@@ -699,9 +715,9 @@ inline uint64_t round_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
 
 // Rigorous magnitude bound through the inverse 3-D lifting.  Symbols are u8, so |q| <= 128 and every
 // dequantised sample is at most 128 * |step|; each lifting step adds at most (2 * other * |c| + 4096) / 8192 + 1.
-// fast: 32-bit (24 x 24-bit) products are exact everywhere.  mid16: additionally every value after the
-// temporal pass fits i16, so the intermediate can be stored in 16 bits.
-struct InverseBounds { bool fast; bool mid16; bool lds16; };
+// The flags of launch_inverse_transform: exact unless 32-bit (24 x 24-bit) products are exact everywhere; mid16 (never with
+// exact): every value after the temporal pass fits i16, so it can be stored in 16 bits; lds16: also after the column pass.
+struct InverseBounds { bool exact; bool mid16; bool lds16; };
 InverseBounds inverse_bounds(int wavelet, const int32_t step[3]) {
     const LiftSteps ls = lift_steps(wavelet);
     long double worst = 0;
@@ -709,7 +725,8 @@ InverseBounds inverse_bounds(int wavelet, const int32_t step[3]) {
         long double a = 128.0L * fabsl((long double)step[c]);
         if (a > worst) worst = a;
     }
-    InverseBounds r{true, false, false};
+    const InverseBounds exact{true, false, false};
+    InverseBounds r{false, false, false};
     long double m = worst;  // bound on every sample
     for (int pass = 0; pass < 3; ++pass) {
         long double me = m, mo = m;
@@ -718,21 +735,15 @@ InverseBounds inverse_bounds(int wavelet, const int32_t step[3]) {
             long double& target = (k & 1) == 0 ? mo : me;
             const long double other = (k & 1) == 0 ? me : mo;
             // v_mul_i24 operands: |a + b| < 2^23; product + rounding below 2^31
-            if (2 * other >= 8388607.0L || 2 * other * cabs + 4096 >= 2147483647.0L) { r.fast = false; return r; }
+            if (2 * other >= 8388607.0L || 2 * other * cabs + 4096 >= 2147483647.0L) return exact;
             target = target + (2 * other * cabs + 4096) / 8192 + 1;
-            if (target >= 1073741824.0L) { r.fast = false; return r; }
+            if (target >= 1073741824.0L) return exact;
         }
         m = me > mo ? me : mo;
         if (pass == 0) r.mid16 = m <= 32767.0L;
         if (pass == 1) r.lds16 = r.mid16 && m <= 32767.0L;
     }
     return r;
-}
-
-// (re)allocates only when the buffer is too small; the caller guarantees nothing in flight still uses it
-int ensure_bytes(DevBuf& b, size_t bytes) {
-    if (b.p && b.n >= bytes) return kOk;
-    return b.alloc(bytes);
 }
 
 struct EncodeWork {
@@ -795,9 +806,11 @@ uint64_t estimate_stream_cap(const uint32_t* hist, uint64_t n) {
 
 uint64_t worst_cap(const ChunkDims& d) { return round_up(2 * d.padded + 4 + 64 + 64, 256); }  // +64: dummy-store guard band
 
-// Exact reference arithmetic on caller-shaped data for chunks of more than 64 padded frames.
-int forward_generic(const uint8_t* d_rgb, const ChunkDims& d, int wavelet, int32_t step, EncodeWork& w,
-                    uint8_t* d_sym, uint32_t* d_hist, hipStream_t st) {
+// The forward transform of one chunk: the tile kernels where they cover the shape (w.scratch holds their band slots), else
+// exact reference arithmetic on caller-shaped data (chunks of more than 64 padded frames, say).
+int forward_chunk(const uint8_t* d_rgb, const ChunkDims& d, int wavelet, int32_t step, EncodeWork& w,
+                  uint8_t* d_sym, uint32_t* d_hist, hipStream_t st) {
+    if (w.scratch.p && launch_forward_transform(d_rgb, d, wavelet, step, w.scratch.p, d_sym, d_hist, st)) return kOk;
     if (!w.planes.p) TRY(w.planes.alloc(3 * d.n_pixels * sizeof(int16_t)));
     if (!w.tmp.p) TRY(w.tmp.alloc(d.padded * sizeof(int32_t)));
     if (!w.gen.p) TRY(w.gen.alloc(2 * d.padded * sizeof(int32_t)));
@@ -855,9 +868,7 @@ int encode_launch(const uint8_t* d_rgb, EncodeWork& w, uint8_t quality, int wave
     for (int b = 0; b < B; ++b) {
         const uint8_t* rgb = d_rgb + (size_t)b * d.n_pixels * 3;
         uint8_t* sym = w.sym.as<uint8_t>() + (size_t)b * 3 * d.padded;
-        uint32_t* hist = w.hist.as<uint32_t>() + (size_t)b * 3 * 256;
-        if (!w.scratch.p || !launch_forward_transform(rgb, d, wavelet, step, w.scratch.p, sym, hist, st))
-            TRY(forward_generic(rgb, d, wavelet, step, w, sym, hist, st));
+        TRY(forward_chunk(rgb, d, wavelet, step, w, sym, w.hist.as<uint32_t>() + (size_t)b * 3 * 256, st));
     }
     if (evs) HIP_TRY(hipEventRecord(evs->ev[1], st));
     const bool had_alc = w.alc.p != nullptr;
@@ -883,11 +894,9 @@ int encode_launch(const uint8_t* d_rgb, EncodeWork& w, uint8_t quality, int wave
     if (hub) {
         // host call: the chains leave with the hub's next merged launch (same regions as the grouped layout below); this
         // thread sleeps until they have run and then queues the tail on its short stream
-        HubJob job;
-        job.encode = true;
-        job.enc.resize((size_t)3 * B);
+        std::vector<RansEncodeDesc> enc((size_t)3 * B);
         for (int c = 0; c < 3 * B; ++c) {
-            RansEncodeDesc& e = job.enc[(size_t)c];
+            RansEncodeDesc& e = enc[(size_t)c];
             const int g = c % 3;
             e.sym = w.sym.as<uint8_t>() + (size_t)c * d.padded;
             e.n = d.padded;
@@ -898,8 +907,7 @@ int encode_launch(const uint8_t* d_rgb, EncodeWork& w, uint8_t quality, int wave
             e.x_init = kRansL;
             e.keep_open = 0u;
         }
-        job.seconds = (double)d.padded * 21e-9;
-        TRY(hub_run(*hub, job, st));
+        TRY(hub_chains(st, std::move(enc), {}, d.padded, hub));
     } else {
         launch_rans_encode(w.sym.as<uint8_t>(), d.padded, d.padded, w.tables.as<RansTable>(), w.alc.as<uint8_t>(),
                            w.cap[0], w.results.as<RansResult>(), 3 * B, st, w.alc_stride, kStreamHead, 0xFFFFFFFFu, w.cap[1], w.cap[2]);
@@ -913,25 +921,43 @@ int encode_launch(const uint8_t* d_rgb, EncodeWork& w, uint8_t quality, int wave
     return kOk;
 }
 
+// The error an encode chain's flags report, overflow aside: what that means is the caller's.
+int encode_flags_error(uint32_t flags) {
+    if (flags & kTableDiverges)
+        return fail(kReferenceDiverges, "a symbol whose table frequency wrapped to 0 is present: the reference encoder does not terminate on this input");
+    if (flags & kRansInternal) return fail(kInternal, "rANS kernel invariant violated");
+    return kOk;
+}
+
+constexpr int kOverflowed = -1;   // encode_collect: a chain outgrew its stream region, encode again with more room
+
 // After the stream has drained: fetch per-chain results, map flags to errors.
 int encode_collect(EncodeWork& w, hipStream_t st, std::vector<RansResult>& res) {
     res.resize((size_t)w.n_chunks * 3);
     HIP_TRY(hipMemcpyAsync(res.data(), w.results.p, res.size() * sizeof(RansResult), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    for (auto& r : res) {
-        if (r.flags & kTableDiverges)
-            return fail(kReferenceDiverges, "a symbol whose table frequency wrapped to 0 is present: the reference encoder does not terminate on this input");
-        if (r.flags & kRansInternal) return fail(kInternal, "rANS kernel invariant violated");
-    }
-    if (getenv("ALICE_CODEC_DEBUG"))
+    for (auto& r : res) TRY(encode_flags_error(r.flags));
+    if (debug_on())
         for (size_t i = 0; i < res.size(); ++i)
             fprintf(stderr, "[alice] encode chain %zu: %llu bytes, %.1f Mcycles, %.1f ms of 100 MHz ticks => %.2f GHz, xcc %u se %u cu %u simd %u\n", i, res[i].len,
                     res[i].cycles_k * 1024.0 / 1e6, res[i].ticks_k * 1024.0 / 1e5,
                     res[i].ticks_k ? (res[i].cycles_k / (double)res[i].ticks_k) * 0.1 : 0.0,
                     res[i].xcc_id & 15u, (res[i].hw_id >> 13) & 7u, (res[i].hw_id >> 8) & 15u, (res[i].hw_id >> 4) & 3u);
     for (auto& r : res)
-        if (r.flags & kRansOverflow) return -1;  // caller retries with the worst-case capacity
+        if (r.flags & kRansOverflow) return kOverflowed;
     return kOk;
+}
+
+// The capacity ladder: encodes from `mode` on, one CapMode further after every overflow.  kCapWorst is the format's bound,
+// so a chain that overflows even there is an internal error.
+int encode_with_retry(const uint8_t* d_rgb, EncodeWork& w, uint8_t quality, int wavelet, hipStream_t st, StageEvents* evs,
+                      CapMode mode, HubTicket* hub, std::vector<RansResult>& res) {
+    for (int m = mode; m <= kCapWorst; ++m) {
+        TRY(encode_launch(d_rgb, w, quality, wavelet, st, evs, (CapMode)m, hub));
+        const int rc = encode_collect(w, st, res);
+        if (rc != kOverflowed) return rc;
+    }
+    return fail(kInternal, "rANS output exceeded the worst-case capacity");
 }
 
 struct DecodeWork {
@@ -956,8 +982,12 @@ int decode_work_alloc(DecodeWork& w, const ChunkDims& d, int n_chunks, uint8_t* 
     return kOk;
 }
 
-int inverse_generic(const uint8_t* d_sym, const ChunkDims& d, int wavelet, const int32_t step[3], DecodeWork& w,
-                    uint8_t* d_rgb, hipStream_t st) {
+// The inverse transform of one chunk: the tile kernels where they cover the shape (d_scratch: their band slots, null when
+// they do not), else exact reference arithmetic.
+int inverse_chunk(const uint8_t* d_sym, const ChunkDims& d, int wavelet, const int32_t step[3], void* d_scratch, DecodeWork& w,
+                  uint8_t* d_rgb, hipStream_t st) {
+    const InverseBounds ib = inverse_bounds(wavelet, step);
+    if (d_scratch && launch_inverse_transform(d_sym, d, wavelet, step, ib.exact, ib.mid16, ib.lds16, d_scratch, d_rgb, st)) return kOk;
     if (!w.planes.p) TRY(w.planes.alloc(3 * d.n_pixels * sizeof(int16_t)));
     if (!w.tmp.p) TRY(w.tmp.alloc(d.padded * sizeof(int32_t)));
     if (!w.gen.p) TRY(w.gen.alloc(2 * d.padded * sizeof(int32_t)));
@@ -979,7 +1009,7 @@ int inverse_generic(const uint8_t* d_sym, const ChunkDims& d, int wavelet, const
 
 // headers[b]: parsed chunk headers (validated); d_payload[b]: device pointer to chunk b's payload;
 // d_rgb[b]: where chunk b's pixels go
-int decode_launch(const std::vector<EncodedChunk>& headers, const std::vector<const uint8_t*>& d_payload,
+int decode_launch(const EncodedChunk* const* headers, const std::vector<const uint8_t*>& d_payload,
                   DecodeWork& w, const std::vector<uint8_t*>& d_rgb, hipStream_t st, StageEvents* evs, HubTicket* hub = nullptr) {
     const ChunkDims& d = w.d;
     const int B = w.n_chunks;
@@ -988,14 +1018,13 @@ int decode_launch(const std::vector<EncodedChunk>& headers, const std::vector<co
         // a batch share the ring, and growing it must not wait for the chains)
         bool all16 = true;
         for (int b = 0; b < B; ++b) {
-            int32_t step[3] = {headers[b].ch[0].quant_step, headers[b].ch[1].quant_step, headers[b].ch[2].quant_step};
-            const InverseBounds ib = inverse_bounds(headers[b].wavelet, step);
-            all16 = all16 && ib.fast && ib.mid16;
+            const int32_t step[3] = {headers[b]->ch[0].quant_step, headers[b]->ch[1].quant_step, headers[b]->ch[2].quant_step};
+            all16 = all16 && inverse_bounds(headers[b]->wavelet, step).mid16;
         }
         const size_t need = inverse_scratch_bytes(d, all16);
         if (!w.scratch->p || w.scratch->n < need) {
             HIP_TRY(hipStreamSynchronize(st));   // an earlier call's tail may still use the old ring
-            TRY(ensure_bytes(*w.scratch, need));
+            TRY(w.scratch->alloc(need));
         }
     }
     std::vector<uint32_t> hist((size_t)B * 3 * 256);
@@ -1003,7 +1032,7 @@ int decode_launch(const std::vector<EncodedChunk>& headers, const std::vector<co
     for (int b = 0; b < B; ++b) {
         uint64_t off = 0;
         for (int c = 0; c < 3; ++c) {
-            const ChannelHeader& h = headers[b].ch[c];
+            const ChannelHeader& h = headers[b]->ch[c];
             memcpy(&hist[((size_t)b * 3 + c) * 256], h.histogram, 256 * sizeof(uint32_t));
             RansDecodeDesc& ds = descs[(size_t)b * 3 + c];
             ds.in = d_payload[b] + off;
@@ -1020,25 +1049,15 @@ int decode_launch(const std::vector<EncodedChunk>& headers, const std::vector<co
     if (evs) HIP_TRY(hipEventRecord(evs->ev[5], st));
     launch_rans_table(w.hist.as<uint32_t>(), w.tables.as<RansTable>(), 3 * B, st);
     if (hub) {   // host call: see encode_launch
-        HubJob job;
-        job.encode = false;
-        job.dec = std::move(descs);
-        for (size_t c = 0; c < job.dec.size(); ++c) job.dec[c].result = w.results.as<RansResult>() + c;
-        job.seconds = (double)d.padded * 39e-9;
-        TRY(hub_run(*hub, job, st));
+        for (size_t c = 0; c < descs.size(); ++c) descs[c].result = w.results.as<RansResult>() + c;
+        TRY(hub_chains(st, {}, std::move(descs), d.padded, hub));
     } else {
         launch_rans_decode(w.descs.as<RansDecodeDesc>(), w.results.as<RansResult>(), 3 * B, st);
     }
     if (evs) HIP_TRY(hipEventRecord(evs->ev[6], st));
-    {
-        const bool tiles = transform_tiles_eligible(d) && w.scratch->p;
-        for (int b = 0; b < B; ++b) {
-            int32_t step[3] = {headers[b].ch[0].quant_step, headers[b].ch[1].quant_step, headers[b].ch[2].quant_step};
-            const InverseBounds ib = inverse_bounds(headers[b].wavelet, step);
-            const uint8_t* sym = w.sym_ptr + (size_t)b * 3 * d.padded;
-            if (!tiles || !launch_inverse_transform(sym, d, headers[b].wavelet, step, !ib.fast, ib.fast && ib.mid16, ib.fast && ib.lds16, w.scratch->p, d_rgb[b], st))
-                TRY(inverse_generic(sym, d, headers[b].wavelet, step, w, d_rgb[b], st));
-        }
+    for (int b = 0; b < B; ++b) {
+        const int32_t step[3] = {headers[b]->ch[0].quant_step, headers[b]->ch[1].quant_step, headers[b]->ch[2].quant_step};
+        TRY(inverse_chunk(w.sym_ptr + (size_t)b * 3 * d.padded, d, headers[b]->wavelet, step, w.scratch->p, w, d_rgb[b], st));
     }
     if (evs) HIP_TRY(hipEventRecord(evs->ev[7], st));
     HIP_TRY(hipGetLastError());
@@ -1051,7 +1070,7 @@ int decode_collect(DecodeWork& w, hipStream_t st) {
     HIP_TRY(hipStreamSynchronize(st));
     for (auto& r : res)
         if (r.flags & kRansInternal) return fail(kInternal, "rANS decode table invariant violated");
-    if (getenv("ALICE_CODEC_DEBUG"))
+    if (debug_on())
         for (size_t i = 0; i < res.size(); ++i)
             fprintf(stderr, "[alice] decode chain %zu: consumed %llu bytes, fast tiles %u, slow tiles %u, %.1f Mcycles, xcc %u se %u cu %u simd %u\n", i, res[i].len,
                     res[i].fast_tiles, res[i].slow_tiles, res[i].cycles_k * 1024.0 / 1e6,
@@ -1077,54 +1096,145 @@ int validate_for_decode(const EncodedChunk& c, ChunkDims* dims, uint64_t payload
     return kOk;
 }
 
-// FrameEncoder::encode on host buffers (src/pipeline.rs:377-507)
-int encode_host(const FrameEncoder& enc, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
-                uint32_t frames, EncodedChunk& out) {
-    uint64_t n_pixels = 0;
-    TRY(checked_pixel_count(width, height, frames, &n_pixels));                 // :388
-    out.width = width; out.height = height; out.frames = frames; out.wavelet = enc.wavelet;
-    for (auto& h : out.ch) h = ChannelHeader();
-    out.data.clear();
-    if (n_pixels == 0) {                                                         // :391-412
-        if (rgb_len != 0) return fail(kInvalidBufferSize, "buffer size mismatch: expected 0, got " + std::to_string(rgb_len));
-        return kOk;
-    }
-    if (width == 0 || height == 0) return fail(kInvalidDimensions, "invalid dimensions");  // :415-417
-    if (n_pixels > UINT64_MAX / 3) return fail(kDimensionOverflow, "dimensions overflow usize");
-    if (rgb_len != n_pixels * 3)                                                // :422-427
-        return fail(kInvalidBufferSize, "buffer size mismatch: expected " + std::to_string(n_pixels * 3) + ", got " + std::to_string(rgb_len));
-    const ChunkDims d = make_dims(width, height, frames);
-    if (d.padded > 0xFFFFFFFFull) return fail(kDimensionOverflow, "padded pixel count does not fit the header's u32 num_symbols");
+// How many chunks of this shape the calling thread's device can hold at once (inputs or outputs, symbols, .alc
+// buffers with the worst observed payload of 1 byte per pixel sample, tables), leaving a fifth of the free memory alone.
+uint32_t chunks_that_fit(const ChunkDims& d, uint32_t want) {
+    if (want <= 1) return want;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return want; }
+    const long double per_chunk = (long double)d.n_pixels * 3 + (long double)d.padded * 3 * 2 + 3.0L * sizeof(RansTable) * 2 + 65536;
+    const long double fixed = (long double)std::max(forward_scratch_bytes(d), inverse_scratch_bytes(d, false)) + (64u << 20);
+    const long double room = (long double)free_b * 0.8L - fixed;
+    if (room < per_chunk) return 1;
+    const long double n = room / per_chunk;
+    return n >= (long double)want ? want : (uint32_t)n;
+}
 
+// Every whole-chunk encode from host memory: chunks k = slot, slot + step, ... below n_chunks of rgb (n_pixels * 3 bytes
+// each) on the calling thread's device, as many at a time as its memory holds, into out[k].  On error nothing is left in
+// out.  One chunk is the case n = 1 (parallel_chunks then runs its copies inline).
+int encode_chunks_on_device(const FrameEncoder& enc, const uint8_t* rgb, const ChunkDims& d, EncodedChunk** out, uint32_t n_chunks,
+                            uint32_t slot = 0, uint32_t step = 1) {
+    const uint32_t n = slot < n_chunks ? (n_chunks - slot + step - 1) / step : 0;
+    auto at = [&](uint32_t i) { return slot + (size_t)i * step; };   // this call's i-th chunk
+    for (uint32_t i = 0; i < n; ++i) out[at(i)] = nullptr;
+    if (!n) return kOk;
+    TRY(ensure_device());
+    const uint32_t per_pass = chunks_that_fit(d, n);
     HubTicket ticket;
-    TRY(ticket.open(encode_device_bytes(d, 1)));
+    TRY(ticket.open(encode_device_bytes(d, per_pass)));
     const hipStream_t st = ticket.st;
-    DevBuf d_rgb;
-    TRY(d_rgb.alloc(rgb_len));
-    HIP_TRY(hipMemcpyAsync(d_rgb.p, rgb, rgb_len, hipMemcpyHostToDevice, st));
-    EncodeWork w;
-    std::vector<RansResult> res;
-    TRY(encode_work_alloc(w, d, 1));
-    for (int attempt = 0;; ++attempt) {
-        TRY(encode_launch(d_rgb.as<uint8_t>(), w, enc.quality, enc.wavelet, st, nullptr, (CapMode)attempt, &ticket));
-        int rc = encode_collect(w, st, res);
-        if (rc == kOk) break;
-        if (rc != -1 || attempt >= 2) return rc == -1 ? fail(kInternal, "rANS output exceeded the worst-case bound") : rc;
+    auto undo = [&](int rc) { for (uint32_t i = 0; i < n; ++i) { delete out[at(i)]; out[at(i)] = nullptr; } return rc; };
+    const uint64_t chunk_bytes = d.n_pixels * 3;
+    for (uint32_t first = 0; first < n; first += per_pass) {
+        const uint32_t B = std::min(per_pass, n - first);
+        DevBuf d_rgb;
+        EncodeWork w;
+        std::vector<RansResult> res;
+        int rc = d_rgb.alloc(chunk_bytes * B);
+        if (rc == kOk) rc = encode_work_alloc(w, d, (int)B);
+        if (rc == kOk)
+            rc = parallel_chunks(B, chunk_bytes >= (4u << 20) ? kCopyThreads : 1u, [&](uint32_t i) {
+                HIP_TRY(hipMemcpyAsync(d_rgb.as<uint8_t>() + (size_t)i * chunk_bytes, rgb + at(first + i) * chunk_bytes, chunk_bytes, hipMemcpyHostToDevice, st));
+                return (int)kOk;
+            });
+        if (rc == kOk) rc = encode_with_retry(d_rgb.as<uint8_t>(), w, enc.quality, enc.wavelet, st, nullptr, kCapReuse, &ticket, res);
+        if (rc != kOk) return undo(rc);
+        // all headers with one strided copy, then the payloads straight into the chunk objects, several at a time
+        std::vector<uint8_t> hdr((size_t)B * kAlcHeaderBytes);
+        if (hipMemcpy2DAsync(hdr.data(), kAlcHeaderBytes, w.alc.p, w.alc_stride, kAlcHeaderBytes, B, hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess)
+            return undo(fail(kDeviceError, "device to host copy failed"));
+        rc = parallel_chunks(B, w.alc_stride >= (4u << 20) ? kCopyThreads : 1u, [&](uint32_t i) {
+            const uint64_t payload = res[3 * i].len + res[3 * i + 1].len + res[3 * i + 2].len;
+            EncodedChunk* c = out[at(first + i)] = new (std::nothrow) EncodedChunk();   // (undo() deletes it)
+            if (!c) return fail(kOutOfMemory, "out of host memory");
+            uint64_t tot = 0;
+            if (parse_alc_header(hdr.data() + (size_t)i * kAlcHeaderBytes, kAlcHeaderBytes + payload, *c, &tot) != kOk || tot != payload)
+                return fail(kInternal, "device header/payload length mismatch");
+            c->data.resize((size_t)payload);
+            return copy_to_host(c->data.data(), w.alc.as<uint8_t>() + (size_t)i * w.alc_stride + kAlcHeaderBytes, (size_t)payload, st);
+        });
+        if (rc != kOk) return undo(rc);
     }
-    uint64_t payload = res[0].len + res[1].len + res[2].len;
-    // the header into a small buffer, the payload straight into the chunk object (one allocation, one pass over it)
-    std::vector<uint8_t> hdr((size_t)kAlcHeaderBytes);
-    HIP_TRY(hipMemcpyAsync(hdr.data(), w.alc.p, hdr.size(), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    uint64_t tot = 0;
-    TRY(parse_alc_header(hdr.data(), hdr.size() + payload, out, &tot));
-    if (tot != payload) return fail(kInternal, "device header/payload length mismatch");
-    out.data.resize((size_t)payload);
-    TRY(copy_to_host(out.data.data(), w.alc.as<uint8_t>() + kAlcHeaderBytes, (size_t)payload, st));
     return kOk;
 }
 
-// FrameDecoder::decode on a host chunk (src/pipeline.rs:537-624)
+// Every whole-chunk decode into host memory, chunks chosen as by encode_chunks_on_device (all of one shape, validated by the
+// caller): chunk k's pixels go to rgb_out + k * n_pixels * 3.  Empty chunks return before any device is touched.
+int decode_chunks_on_device(const EncodedChunk* const* chunks, const ChunkDims& d, uint8_t* rgb_out, uint32_t n_chunks,
+                            uint32_t slot = 0, uint32_t step = 1) {
+    const uint32_t n = slot < n_chunks ? (n_chunks - slot + step - 1) / step : 0;
+    auto at = [&](uint32_t i) { return slot + (size_t)i * step; };
+    if (!n || d.n_pixels == 0) return kOk;
+    TRY(ensure_device());
+    const uint32_t per_pass = chunks_that_fit(d, n);
+    uint64_t max_payload = 0;
+    for (uint32_t i = 0; i < n; ++i) max_payload = std::max<uint64_t>(max_payload, chunks[at(i)]->data.size());
+    HubTicket ticket;
+    TRY(ticket.open(decode_device_bytes(d, per_pass, (uint64_t)per_pass * (max_payload + 512))));
+    const hipStream_t st = ticket.st;
+    const uint64_t chunk_bytes = d.n_pixels * 3;
+    for (uint32_t first = 0; first < n; first += per_pass) {
+        const uint32_t B = std::min(per_pass, n - first);
+        std::vector<const EncodedChunk*> hdrs(B);
+        uint64_t total_payload = 0;
+        for (uint32_t i = 0; i < B; ++i) { hdrs[i] = chunks[at(first + i)]; total_payload += round_up(hdrs[i]->data.size() + 16, 256); }
+        DevBuf d_payload, d_rgb;
+        TRY(d_payload.alloc(total_payload + 256));
+        TRY(d_rgb.alloc(chunk_bytes * B));
+        std::vector<const uint8_t*> pay(B);
+        std::vector<uint8_t*> dst(B);
+        uint64_t off = 0;
+        for (uint32_t i = 0; i < B; ++i) {
+            const EncodedChunk& c = *hdrs[i];
+            pay[i] = d_payload.as<uint8_t>() + off;
+            dst[i] = d_rgb.as<uint8_t>() + (size_t)i * chunk_bytes;
+            if (!c.data.empty())
+                HIP_TRY(hipMemcpyAsync(d_payload.as<uint8_t>() + off, c.data.data(), c.data.size(), hipMemcpyHostToDevice, st));
+            off += round_up(c.data.size() + 16, 256);
+        }
+        DecodeWork w;
+        TRY(decode_work_alloc(w, d, (int)B));
+        TRY(decode_launch(hdrs.data(), pay, w, dst, st, nullptr, &ticket));
+        TRY(decode_collect(w, st));
+        TRY(parallel_chunks(B, chunk_bytes >= (4u << 20) ? kCopyThreads : 1u,
+                            [&](uint32_t i) { return copy_to_host(rgb_out + at(first + i) * chunk_bytes, dst[i], chunk_bytes, st); }));
+    }
+    return kOk;
+}
+
+// FrameEncoder::encode's validation (src/pipeline.rs:388-427, in its order) of n_chunks chunks in one buffer: the checks of
+// one chunk, with the buffer n_chunks times as long.  The calls of one chunk answer the empty chunk (:391-412) before.
+int validate_encode_many(const FrameEncoder* encoder, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
+                         uint32_t frames, uint32_t n_chunks, EncodedChunk** out_chunks, ChunkDims* d) {
+    if (!encoder || !out_chunks || (!rgb && rgb_len)) return fail(kNullArgument, "null argument");
+    for (uint32_t i = 0; i < n_chunks; ++i) out_chunks[i] = nullptr;
+    if (n_chunks == 0) return kOk;
+    uint64_t n_pixels = 0;
+    TRY(checked_pixel_count(width, height, frames, &n_pixels));                             // :388
+    if (n_pixels == 0 || width == 0 || height == 0) return fail(kInvalidDimensions, "invalid dimensions");   // :415-417
+    if (n_pixels > UINT64_MAX / 3 / n_chunks) return fail(kDimensionOverflow, "dimensions overflow usize");
+    if (rgb_len != n_pixels * 3 * n_chunks)                                                 // :422-427
+        return fail(kInvalidBufferSize, "buffer size mismatch: expected " + std::to_string(n_pixels * 3 * n_chunks) + ", got " + std::to_string(rgb_len));
+    return chunk_dims(width, height, frames, d);
+}
+
+// FrameEncoder::encode on host buffers (src/pipeline.rs:377-507); *out: the chunk object
+int encode_host(const FrameEncoder& enc, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
+                uint32_t frames, EncodedChunk** out) {
+    uint64_t n_pixels = 0;
+    TRY(checked_pixel_count(width, height, frames, &n_pixels));                 // :388
+    if (n_pixels == 0) {                                                         // :391-412
+        if (rgb_len != 0) return fail(kInvalidBufferSize, "buffer size mismatch: expected 0, got " + std::to_string(rgb_len));
+        *out = new (std::nothrow) EncodedChunk{width, height, frames, enc.wavelet};
+        return *out ? kOk : fail(kOutOfMemory, "out of host memory");
+    }
+    ChunkDims d{};
+    TRY(validate_encode_many(&enc, rgb, rgb_len, width, height, frames, 1, out, &d));
+    return encode_chunks_on_device(enc, rgb, d, out, 1);
+}
+
 // A buffer the C ABI hands to the caller (released with free(): alice_codec_data_free64).  Large ones are 2 MiB aligned and
 // marked for huge pages: 64 threads that each fault a fresh 398 MB result in 4 KiB pages spend more time in the kernel's
 // page-fault path than the GPU spends on their chains.
@@ -1137,31 +1247,15 @@ uint8_t* host_result_alloc(uint64_t bytes) {
     return (uint8_t*)p;
 }
 
-// *out: malloc'ed pixels (nullptr for an empty chunk), *out_len their count
+// FrameDecoder::decode on a host chunk (src/pipeline.rs:537-624): *out receives malloc'ed pixels, *out_len their count
 int decode_host(const EncodedChunk& c, uint8_t** out, uint64_t* out_len) {
     ChunkDims d;
     TRY(validate_for_decode(c, &d, c.data.size()));
     *out = nullptr; *out_len = 0;
-    if (d.n_pixels == 0) { *out = host_result_alloc(0); return *out ? kOk : fail(kOutOfMemory, "out of host memory"); }
-    HubTicket ticket;
-    TRY(ticket.open(decode_device_bytes(d, 1, c.data.size())));
-    const hipStream_t st = ticket.st;
-    DevBuf d_payload, d_rgb;
-    TRY(d_payload.alloc(c.data.size() + 16));
-    TRY(d_rgb.alloc(d.n_pixels * 3));
-    if (!c.data.empty())
-        HIP_TRY(hipMemcpyAsync(d_payload.p, c.data.data(), c.data.size(), hipMemcpyHostToDevice, st));
-    DecodeWork w;
-    TRY(decode_work_alloc(w, d, 1));
-    std::vector<EncodedChunk> hdrs(1);
-    hdrs[0].width = c.width; hdrs[0].height = c.height; hdrs[0].frames = c.frames; hdrs[0].wavelet = c.wavelet;
-    for (int k = 0; k < 3; ++k) hdrs[0].ch[k] = c.ch[k];
-    std::vector<const uint8_t*> pay(1, d_payload.as<uint8_t>());
-    TRY(decode_launch(hdrs, pay, w, std::vector<uint8_t*>(1, d_rgb.as<uint8_t>()), st, nullptr, &ticket));
-    TRY(decode_collect(w, st));
     uint8_t* rgb = host_result_alloc(d.n_pixels * 3);
     if (!rgb) return fail(kOutOfMemory, "out of host memory");
-    const int rc = copy_to_host(rgb, d_rgb.p, d.n_pixels * 3, st);
+    const EncodedChunk* one = &c;
+    const int rc = decode_chunks_on_device(&one, d, rgb, 1);
     if (rc != kOk) { free(rgb); return rc; }
     *out = rgb; *out_len = d.n_pixels * 3;
     return kOk;
@@ -1225,6 +1319,63 @@ int wavelet_nd(int kind, int32_t* data, uint64_t W, uint64_t H, uint64_t D, int 
     return kOk;
 }
 
+// ---- the stage-level rANS calls: a frequency table of the caller's, one chain or the four of the interleaved format ----
+
+// The caller's (cum_freq, freq) pair built into k identical tables on the device; buf holds the pair, then the tables.
+int stage_tables(const uint16_t* cum_freq, const uint16_t* freq, int k, DevBuf& buf, hipStream_t st, RansTable** tables) {
+    TRY(buf.alloc(1024 + (size_t)k * sizeof(RansTable)));
+    uint16_t* arrays = buf.as<uint16_t>();
+    HIP_TRY(hipMemcpyAsync(arrays, cum_freq, 512, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(arrays + 256, freq, 512, hipMemcpyHostToDevice, st));
+    *tables = (RansTable*)(buf.as<uint8_t>() + 1024);
+    for (int j = 0; j < k; ++j) launch_rans_table_from_arrays(arrays, arrays + 256, *tables + j, st);
+    return kOk;
+}
+
+// One encode chain from state x_init (keep_open: an encoder object carries the state on, its four bytes stay unwritten);
+// the stream, res.len bytes, is copied to dst(res.len), a host buffer of the caller's (null: out of memory, or 0 bytes).
+template <typename Dst>
+int stage_encode_chain(const uint8_t* symbols, uint64_t n, const uint16_t* cum_freq, const uint16_t* freq, uint32_t x_init,
+                       uint32_t keep_open, RansResult& res, Dst dst) {
+    hipStream_t st;
+    TRY(get_stream(&st));
+    const uint64_t cap = round_up(2 * n + 4 + 64 + 64, 256);
+    DevBuf ds, dt, dout, dres;
+    RansTable* table = nullptr;
+    TRY(ds.alloc(n)); TRY(dout.alloc(cap)); TRY(dres.alloc(sizeof(RansResult)));
+    if (n) HIP_TRY(hipMemcpyAsync(ds.p, symbols, n, hipMemcpyHostToDevice, st));
+    TRY(stage_tables(cum_freq, freq, 1, dt, st, &table));
+    TRY(hub_chains(st, {RansEncodeDesc{ds.as<uint8_t>(), n, table, dout.as<uint8_t>(), cap, dres.as<RansResult>(), x_init, keep_open}}, {}, n));
+    HIP_TRY(hipMemcpyAsync(&res, dres.p, sizeof(res), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    TRY(encode_flags_error(res.flags));
+    if (res.flags & kRansOverflow) return fail(kInternal, "rANS output exceeded the worst-case capacity");
+    uint8_t* p = dst(res.len);
+    if (!p && res.len) return fail(kOutOfMemory, "out of host memory");
+    if (res.len) {
+        HIP_TRY(hipMemcpyAsync(p, dout.as<uint8_t>() + (cap - res.len), res.len, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return kOk;
+}
+
+// One decode chain on `st`: n symbols of the stream at d_in (len bytes) into symbols[] on the host; resume: continue from
+// state x0 at byte pos0, where a decoder object stopped, instead of from the stream's four head bytes.
+int stage_decode_chain(hipStream_t st, const uint8_t* d_in, uint64_t len, const uint16_t* cum_freq, const uint16_t* freq, uint64_t n,
+                       uint32_t resume, uint32_t x0, uint64_t pos0, uint8_t* symbols, RansResult& res) {
+    DevBuf dt, dout, dres;
+    RansTable* table = nullptr;
+    TRY(dout.alloc(n)); TRY(dres.alloc(sizeof(RansResult)));
+    TRY(stage_tables(cum_freq, freq, 1, dt, st, &table));
+    TRY(hub_chains(st, {}, {RansDecodeDesc{d_in, len, dout.as<uint8_t>(), n, table, resume, x0, pos0, dres.as<RansResult>()}}, n));
+    HIP_TRY(hipMemcpyAsync(&res, dres.p, sizeof(res), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(symbols, dout.p, n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    note_decode_stats(res);
+    if (res.flags & kRansInternal) return fail(kInternal, "rANS decode kernel invariant violated");
+    return kOk;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
@@ -1279,10 +1430,8 @@ EncodedChunk* alice_codec_encode64(const FrameEncoder* encoder, const uint8_t* r
                                    uint32_t height, uint32_t frames) {
     clear_error();
     if (!encoder || !rgb) { fail(kNullArgument, "null argument"); return nullptr; }
-    EncodedChunk* c = new (std::nothrow) EncodedChunk();
-    if (!c) { fail(kOutOfMemory, "out of host memory"); return nullptr; }
-    if (encode_host(*encoder, rgb, rgb_len, width, height, frames, *c) != kOk) { delete c; return nullptr; }
-    return c;
+    EncodedChunk* c = nullptr;
+    return encode_host(*encoder, rgb, rgb_len, width, height, frames, &c) == kOk ? c : nullptr;
 }
 EncodedChunk* alice_codec_encode(const FrameEncoder* encoder, const uint8_t* rgb, uint32_t rgb_len, uint32_t width,
                                  uint32_t height, uint32_t frames) {
@@ -1408,12 +1557,8 @@ AliceBatch* alice_codec_batch_create(uint32_t width, uint32_t height, uint32_t f
                                      uint8_t wavelet_type) {
     clear_error();
     if (wavelet_type > 2) { fail(kInvalidBitstream, "unknown wavelet type"); return nullptr; }
-    uint64_t n_pixels = 0;
-    if (checked_pixel_count(width, height, frames, &n_pixels)) return nullptr;
-    if (n_pixels == 0 || n_chunks == 0) { fail(kInvalidDimensions, "empty batch"); return nullptr; }
-    const ChunkDims d = make_dims(width, height, frames);
-    if (d.padded > 0xFFFFFFFFull) { fail(kDimensionOverflow, "padded pixel count exceeds u32"); return nullptr; }
-    if (ensure_device()) return nullptr;
+    ChunkDims d{};
+    if (chunk_dims(width, height, frames, &d, n_chunks) || ensure_device()) return nullptr;
     tl_scope_stream = nullptr;   // the batch's buffers outlive every call: no stream of this thread's past belongs on them
     AliceBatch* b = new (std::nothrow) AliceBatch();
     if (!b) { fail(kOutOfMemory, "out of host memory"); return nullptr; }
@@ -1455,11 +1600,9 @@ int alice_codec_batch_encode_finish(AliceBatch* b, uint64_t* sizes) {
     int rc = encode_collect(b->enc, b->enc_stream, res);
     // a chain outgrew its region: the capacities came from an earlier encode of other content (kCapReuse) -- size them
     // from this content's histograms and run again; should even that fall short (never observed), take the format's bound
-    for (int mode = kCapEstimate; rc == -1 && b->last_rgb && mode <= kCapWorst; ++mode) {
-        TRY(encode_launch(b->last_rgb, b->enc, b->quality, b->wavelet, b->enc_stream, &b->evs, (CapMode)mode));
-        rc = encode_collect(b->enc, b->enc_stream, res);
-    }
-    if (rc == -1) return fail(kInternal, "rANS output exceeded the worst-case capacity");
+    if (rc == kOverflowed && b->last_rgb)
+        rc = encode_with_retry(b->last_rgb, b->enc, b->quality, b->wavelet, b->enc_stream, &b->evs, kCapEstimate, nullptr, res);
+    if (rc == kOverflowed) return fail(kInternal, "rANS output exceeded the worst-case capacity");   // (no encode to repeat)
     if (rc) return rc;
     for (int i = 0; i < 4; ++i) (void)hipEventElapsedTime(&b->stage_ms[i], b->evs.ev[i], b->evs.ev[i + 1]);
     b->enc_timed = true;
@@ -1523,6 +1666,7 @@ int alice_codec_batch_decode(AliceBatch* b, const void* d_alc, uint64_t alc_stri
     HIP_TRY(hipMemcpy2DAsync(hdr.data(), kAlcHeaderBytes, d_alc, alc_stride, kAlcHeaderBytes, b->n_chunks, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     std::vector<EncodedChunk> headers(b->n_chunks);
+    std::vector<const EncodedChunk*> hp(b->n_chunks);
     std::vector<const uint8_t*> pay(b->n_chunks);
     for (uint32_t i = 0; i < b->n_chunks; ++i) {
         uint64_t payload = 0;
@@ -1533,6 +1677,7 @@ int alice_codec_batch_decode(AliceBatch* b, const void* d_alc, uint64_t alc_stri
         ChunkDims dd;
         TRY(validate_for_decode(headers[i], &dd, payload));
         pay[i] = (const uint8_t*)d_alc + (size_t)i * alc_stride + kAlcHeaderBytes;
+        hp[i] = &headers[i];
     }
     // d_rgb_out == NULL: the batch keeps the pixels in its own storage (alice_codec_batch_rgb_ptr).  An uncut chunk is
     // reconstructed over its own (by then consumed) symbols: its temporal pass is the last reader of those symbols and
@@ -1549,7 +1694,7 @@ int alice_codec_batch_decode(AliceBatch* b, const void* d_alc, uint64_t alc_stri
     } else {
         for (uint32_t i = 0; i < b->n_chunks; ++i) b->rgb_dst[i] = (uint8_t*)d_rgb_out + (size_t)i * b->d.n_pixels * 3;
     }
-    return decode_launch(headers, pay, b->dec, b->rgb_dst, st, &b->evs);
+    return decode_launch(hp.data(), pay, b->dec, b->rgb_dst, st, &b->evs);
 }
 const void* alice_codec_batch_rgb_ptr(const AliceBatch* b, uint32_t chunk) {
     if (!b || chunk >= b->n_chunks || chunk >= b->rgb_dst.size()) return nullptr;
@@ -1680,24 +1825,12 @@ uint8_t* alice_codec_rans_encode(const uint8_t* symbols, uint64_t n, const uint1
                                  uint64_t* out_len) {
     clear_error();
     if ((!symbols && n) || !cum_freq || !freq || !out_len) { fail(kNullArgument, "null argument"); return nullptr; }
-    hipStream_t st;
-    if (get_stream(&st)) return nullptr;
-    const uint64_t cap = round_up(2 * n + 4 + 64 + 64, 256);
-    DevBuf ds, dc, df, dt, dout, dres;
-    if (ds.alloc(n) || dc.alloc(512) || df.alloc(512) || dt.alloc(sizeof(RansTable)) || dout.alloc(cap) || dres.alloc(sizeof(RansResult))) return nullptr;
+    uint8_t* p = nullptr;
     RansResult res{};
-    auto ok = [&](hipError_t e) { if (e != hipSuccess) { fail(kDeviceError, hipGetErrorString(e)); return false; } return true; };
-    if (n && !ok(hipMemcpyAsync(ds.p, symbols, n, hipMemcpyHostToDevice, st))) return nullptr;
-    if (!ok(hipMemcpyAsync(dc.p, cum_freq, 512, hipMemcpyHostToDevice, st)) || !ok(hipMemcpyAsync(df.p, freq, 512, hipMemcpyHostToDevice, st))) return nullptr;
-    launch_rans_table_from_arrays(dc.as<uint16_t>(), df.as<uint16_t>(), dt.as<RansTable>(), st);
-    if (stage_chains(st, {RansEncodeDesc{ds.as<uint8_t>(), n, dt.as<RansTable>(), dout.as<uint8_t>(), cap, dres.as<RansResult>(), kRansL, 0u}}, {}, n) != kOk)
+    if (stage_encode_chain(symbols, n, cum_freq, freq, kRansL, 0u, res, [&](uint64_t len) { return p = (uint8_t*)malloc(len ? len : 1); }) != kOk) {
+        free(p);
         return nullptr;
-    if (!ok(hipMemcpyAsync(&res, dres.p, sizeof(res), hipMemcpyDeviceToHost, st)) || !ok(hipStreamSynchronize(st))) return nullptr;
-    if (res.flags & kTableDiverges) { fail(kReferenceDiverges, "symbol with table frequency 0 encoded"); return nullptr; }
-    if (res.flags & (kRansOverflow | kRansInternal)) { fail(kInternal, "rANS encode failed"); return nullptr; }
-    uint8_t* p = (uint8_t*)malloc(res.len ? res.len : 1);
-    if (!p) { fail(kOutOfMemory, "out of host memory"); return nullptr; }
-    if (!ok(hipMemcpyAsync(p, dout.as<uint8_t>() + (cap - res.len), res.len, hipMemcpyDeviceToHost, st)) || !ok(hipStreamSynchronize(st))) { free(p); return nullptr; }
+    }
     *out_len = res.len;
     return p;
 }
@@ -1709,23 +1842,11 @@ int alice_codec_rans_decode(const uint8_t* bytes, uint64_t len, const uint16_t c
     if (!n) return kOk;
     hipStream_t st;
     TRY(get_stream(&st));
-    DevBuf din, dc, df, dt, dout, ddesc, dres;
-    TRY(din.alloc(len + 16)); TRY(dc.alloc(512)); TRY(df.alloc(512)); TRY(dt.alloc(sizeof(RansTable)));
-    TRY(dout.alloc(n)); TRY(ddesc.alloc(sizeof(RansDecodeDesc))); TRY(dres.alloc(sizeof(RansResult)));
+    DevBuf din;
+    TRY(din.alloc(len + 16));
     if (len) HIP_TRY(hipMemcpyAsync(din.p, bytes, len, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(dc.p, cum_freq, 512, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(df.p, freq, 512, hipMemcpyHostToDevice, st));
-    RansDecodeDesc desc{din.as<uint8_t>(), len, dout.as<uint8_t>(), n, dt.as<RansTable>()};
-    desc.result = dres.as<RansResult>();
-    launch_rans_table_from_arrays(dc.as<uint16_t>(), df.as<uint16_t>(), dt.as<RansTable>(), st);
-    TRY(stage_chains(st, {}, {desc}, n));
     RansResult res{};
-    HIP_TRY(hipMemcpyAsync(&res, dres.p, sizeof(res), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(symbols, dout.p, n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    note_decode_stats(res);
-    if (res.flags & kRansInternal) return fail(kInternal, "rANS decode kernel invariant violated");
-    return kOk;
+    return stage_decode_chain(st, din.as<uint8_t>(), len, cum_freq, freq, n, 0u, 0u, 0, symbols, res);
 }
 void alice_codec_test_last_decode_stats(uint32_t out[4]) { if (out) for (int i = 0; i < 4; ++i) out[i] = tl_dec_stats[i]; }
 
@@ -1742,26 +1863,9 @@ int alice_codec_rans_encoder_encode_symbols(AliceRansEncoder* e, const uint8_t* 
     clear_error();
     if (!e || (!symbols && n) || !cum_freq || !freq) return fail(kNullArgument, "null argument");
     if (!n) return kOk;
-    hipStream_t st;
-    TRY(get_stream(&st));
-    const uint64_t cap = round_up(2 * n + 4 + 64 + 64, 256);
-    DevBuf ds, dc, df, dt, dout, dres;
-    TRY(ds.alloc(n)); TRY(dc.alloc(512)); TRY(df.alloc(512)); TRY(dt.alloc(sizeof(RansTable))); TRY(dout.alloc(cap)); TRY(dres.alloc(sizeof(RansResult)));
-    HIP_TRY(hipMemcpyAsync(ds.p, symbols, n, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(dc.p, cum_freq, 512, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(df.p, freq, 512, hipMemcpyHostToDevice, st));
-    launch_rans_table_from_arrays(dc.as<uint16_t>(), df.as<uint16_t>(), dt.as<RansTable>(), st);
-    TRY(stage_chains(st, {RansEncodeDesc{ds.as<uint8_t>(), n, dt.as<RansTable>(), dout.as<uint8_t>(), cap, dres.as<RansResult>(), e->state, 1u}}, {}, n));
     RansResult res{};
-    HIP_TRY(hipMemcpyAsync(&res, dres.p, sizeof(res), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (res.flags & kTableDiverges) return fail(kReferenceDiverges, "symbol with table frequency 0 encoded (the reference does not terminate / indexes out of bounds)");
-    if (res.flags & (kRansOverflow | kRansInternal)) return fail(kInternal, "rANS encode failed");
-    std::vector<uint8_t> seg((size_t)res.len);
-    if (res.len) {
-        HIP_TRY(hipMemcpyAsync(seg.data(), dout.as<uint8_t>() + (cap - res.len), res.len, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
+    std::vector<uint8_t> seg;
+    TRY(stage_encode_chain(symbols, n, cum_freq, freq, e->state, 1u, res, [&](uint64_t len) { seg.resize((size_t)len); return seg.data(); }));
     e->state = res.final_state;
     e->bytes += res.len;
     e->segments.push_back(std::move(seg));
@@ -1827,21 +1931,8 @@ int alice_codec_rans_decoder_decode_n(AliceRansDecoder* d, uint64_t n, const uin
         d->device = tl_device;
         if (len) HIP_TRY(hipMemcpyAsync(d->d_input.p, d->input.data(), len, hipMemcpyHostToDevice, st));
     }
-    DevBuf dc, df, dt, dout, ddesc, dres;
-    TRY(dc.alloc(512)); TRY(df.alloc(512)); TRY(dt.alloc(sizeof(RansTable)));
-    TRY(dout.alloc(n)); TRY(ddesc.alloc(sizeof(RansDecodeDesc))); TRY(dres.alloc(sizeof(RansResult)));
-    HIP_TRY(hipMemcpyAsync(dc.p, cum_freq, 512, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(df.p, freq, 512, hipMemcpyHostToDevice, st));
-    RansDecodeDesc desc{d->d_input.as<uint8_t>(), len, dout.as<uint8_t>(), n, dt.as<RansTable>(), 1u, d->state, d->pos};
-    desc.result = dres.as<RansResult>();
-    launch_rans_table_from_arrays(dc.as<uint16_t>(), df.as<uint16_t>(), dt.as<RansTable>(), st);
-    TRY(stage_chains(st, {}, {desc}, n));
     RansResult res{};
-    HIP_TRY(hipMemcpyAsync(&res, dres.p, sizeof(res), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(symbols, dout.p, n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    note_decode_stats(res);
-    if (res.flags & kRansInternal) return fail(kInternal, "rANS decode kernel invariant violated");
+    TRY(stage_decode_chain(st, d->d_input.as<uint8_t>(), len, cum_freq, freq, n, 1u, d->state, d->pos, symbols, res));
     d->state = res.final_state;
     d->pos = res.len;
     d->started = true;
@@ -1972,54 +2063,58 @@ int alice_codec_rdo_compute_quantizer(double target_bpp, const int32_t* coeffs, 
 // InterleavedRansEncoder::{encode, finish} (src/rans.rs:393-456): four independent single-stream coders over the
 // sub-sequences i = j mod 4, behind a 32-byte header (4 stream lengths, 4 symbol counts, u32 LE).  On the GPU
 // that is four chains of the same encode kernel running side by side.
-uint8_t* alice_codec_rans_encode_interleaved(const uint8_t* symbols, uint64_t n, const uint16_t cum_freq[256],
-                                             const uint16_t freq[256], uint64_t* out_len) {
-    clear_error();
-    if ((!symbols && n) || !cum_freq || !freq || !out_len) { fail(kNullArgument, "null argument"); return nullptr; }
+static int rans_encode_interleaved_impl(const uint8_t* symbols, uint64_t n, const uint16_t cum_freq[256], const uint16_t freq[256],
+                                        uint8_t** out, uint64_t* out_len) {
+    if ((!symbols && n) || !cum_freq || !freq || !out_len) return fail(kNullArgument, "null argument");
     hipStream_t st;
-    if (get_stream(&st)) return nullptr;
+    TRY(get_stream(&st));
     uint64_t cnt[4];
     for (int j = 0; j < 4; ++j) cnt[j] = (n + 3 - j) / 4;        // :423-425
-    if (cnt[0] > 0xFFFFFFFFull) { fail(kDimensionOverflow, "symbol count does not fit the u32 header field"); return nullptr; }
+    if (cnt[0] > 0xFFFFFFFFull) return fail(kDimensionOverflow, "symbol count does not fit the u32 header field");
     const uint64_t stride = round_up(cnt[0] + 16, 256);
     const uint64_t cap = round_up(2 * cnt[0] + 4 + 64 + 64, 256);
-    DevBuf ds, d4, dc, df, dt, dout, dres;
-    if (ds.alloc(n) || d4.alloc(4 * stride) || dc.alloc(512) || df.alloc(512) || dt.alloc(4 * sizeof(RansTable)) ||
-        dout.alloc(4 * cap) || dres.alloc(4 * sizeof(RansResult))) return nullptr;
-    auto ok = [&](hipError_t e) { if (e != hipSuccess) { fail(kDeviceError, hipGetErrorString(e)); return false; } return true; };
-    if (n && !ok(hipMemcpyAsync(ds.p, symbols, n, hipMemcpyHostToDevice, st))) return nullptr;
-    if (!ok(hipMemcpyAsync(dc.p, cum_freq, 512, hipMemcpyHostToDevice, st)) || !ok(hipMemcpyAsync(df.p, freq, 512, hipMemcpyHostToDevice, st))) return nullptr;
+    DevBuf ds, d4, dt, dout, dres;
+    RansTable* tables = nullptr;
+    TRY(ds.alloc(n)); TRY(d4.alloc(4 * stride)); TRY(dout.alloc(4 * cap)); TRY(dres.alloc(4 * sizeof(RansResult)));
+    if (n) HIP_TRY(hipMemcpyAsync(ds.p, symbols, n, hipMemcpyHostToDevice, st));
     launch_split4(ds.as<uint8_t>(), n, d4.as<uint8_t>(), stride, st);
-    for (int j = 0; j < 4; ++j) launch_rans_table_from_arrays(dc.as<uint16_t>(), df.as<uint16_t>(), dt.as<RansTable>() + j, st);
-    {
-        std::vector<RansEncodeDesc> enc(4);
-        for (int j = 0; j < 4; ++j)
-            enc[j] = RansEncodeDesc{d4.as<uint8_t>() + (size_t)j * stride, cnt[j], dt.as<RansTable>() + j, dout.as<uint8_t>() + (size_t)j * cap, cap,
-                                    dres.as<RansResult>() + j, kRansL, 0u};
-        if (stage_chains(st, std::move(enc), {}, cnt[0]) != kOk) return nullptr;
-    }
+    TRY(stage_tables(cum_freq, freq, 4, dt, st, &tables));
+    std::vector<RansEncodeDesc> enc(4);
+    for (int j = 0; j < 4; ++j)
+        enc[j] = RansEncodeDesc{d4.as<uint8_t>() + (size_t)j * stride, cnt[j], tables + j, dout.as<uint8_t>() + (size_t)j * cap, cap,
+                                dres.as<RansResult>() + j, kRansL, 0u};
+    TRY(hub_chains(st, std::move(enc), {}, cnt[0]));
     RansResult res[4];
-    if (!ok(hipMemcpyAsync(res, dres.p, sizeof(res), hipMemcpyDeviceToHost, st)) || !ok(hipStreamSynchronize(st))) return nullptr;
+    HIP_TRY(hipMemcpyAsync(res, dres.p, sizeof(res), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     uint64_t total = 32;
     for (int j = 0; j < 4; ++j) {
-        if (res[j].flags & kTableDiverges) { fail(kReferenceDiverges, "symbol with table frequency 0 encoded"); return nullptr; }
-        if (res[j].flags & (kRansOverflow | kRansInternal)) { fail(kInternal, "rANS encode failed"); return nullptr; }
-        if (res[j].len > 0xFFFFFFFFull) { fail(kDimensionOverflow, "stream length does not fit the u32 header field"); return nullptr; }
+        TRY(encode_flags_error(res[j].flags));
+        if (res[j].flags & kRansOverflow) return fail(kInternal, "rANS output exceeded the worst-case capacity");
+        if (res[j].len > 0xFFFFFFFFull) return fail(kDimensionOverflow, "stream length does not fit the u32 header field");
         total += res[j].len;
     }
-    uint8_t* p = (uint8_t*)malloc(total);
-    if (!p) { fail(kOutOfMemory, "out of host memory"); return nullptr; }
+    uint8_t* p = *out = (uint8_t*)malloc(total);   // (the caller frees it on failure)
+    if (!p) return fail(kOutOfMemory, "out of host memory");
     uint64_t off = 32;
     for (int j = 0; j < 4; ++j) {
         const uint32_t l = (uint32_t)res[j].len, c = (uint32_t)cnt[j];
         memcpy(p + 4 * j, &l, 4);
         memcpy(p + 16 + 4 * j, &c, 4);
-        if (!ok(hipMemcpyAsync(p + off, dout.as<uint8_t>() + (size_t)j * cap + (cap - res[j].len), res[j].len, hipMemcpyDeviceToHost, st))) { free(p); return nullptr; }
+        HIP_TRY(hipMemcpyAsync(p + off, dout.as<uint8_t>() + (size_t)j * cap + (cap - res[j].len), res[j].len, hipMemcpyDeviceToHost, st));
         off += res[j].len;
     }
-    if (!ok(hipStreamSynchronize(st))) { free(p); return nullptr; }
+    HIP_TRY(hipStreamSynchronize(st));
     *out_len = total;
-    return p;
+    return kOk;
+}
+uint8_t* alice_codec_rans_encode_interleaved(const uint8_t* symbols, uint64_t n, const uint16_t cum_freq[256],
+                                             const uint16_t freq[256], uint64_t* out_len) {
+    clear_error();
+    uint8_t* p = nullptr;
+    if (rans_encode_interleaved_impl(symbols, n, cum_freq, freq, &p, out_len) == kOk) return p;
+    free(p);
+    return nullptr;
 }
 
 // InterleavedRansDecoder::{new, decode_n} (src/rans.rs:468-519; SimdRansDecoder reads the same format): the four
@@ -2054,21 +2149,18 @@ int alice_codec_rans_decode_interleaved(const uint8_t* bytes, uint64_t len, cons
     hipStream_t st;
     TRY(get_stream(&st));
     const uint64_t stride = round_up(mx + 16, 256);
-    DevBuf din, dc, df, dt, d4, dout, ddesc, dres;
-    TRY(din.alloc(len + 16)); TRY(dc.alloc(512)); TRY(df.alloc(512)); TRY(dt.alloc(sizeof(RansTable)));
-    TRY(d4.alloc(4 * stride)); TRY(dout.alloc(n)); TRY(ddesc.alloc(4 * sizeof(RansDecodeDesc))); TRY(dres.alloc(4 * sizeof(RansResult)));
+    DevBuf din, dt, d4, dout, dres;
+    RansTable* table = nullptr;
+    TRY(din.alloc(len + 16)); TRY(d4.alloc(4 * stride)); TRY(dout.alloc(n)); TRY(dres.alloc(4 * sizeof(RansResult)));
     HIP_TRY(hipMemcpyAsync(din.p, bytes, len, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(dc.p, cum_freq, 512, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(df.p, freq, 512, hipMemcpyHostToDevice, st));
+    TRY(stage_tables(cum_freq, freq, 1, dt, st, &table));
     std::vector<RansDecodeDesc> desc(4);
     uint64_t off = 32;
     for (int j = 0; j < 4; ++j) {
-        desc[j] = RansDecodeDesc{din.as<uint8_t>() + off, slen[j], d4.as<uint8_t>() + (size_t)j * stride, need[j], dt.as<RansTable>()};
-        desc[j].result = dres.as<RansResult>() + j;
+        desc[j] = RansDecodeDesc{din.as<uint8_t>() + off, slen[j], d4.as<uint8_t>() + (size_t)j * stride, need[j], table, 0u, 0u, 0, dres.as<RansResult>() + j};
         off += slen[j];
     }
-    launch_rans_table_from_arrays(dc.as<uint16_t>(), df.as<uint16_t>(), dt.as<RansTable>(), st);
-    TRY(stage_chains(st, {}, std::move(desc), mx));
+    TRY(hub_chains(st, {}, std::move(desc), mx));
     launch_merge4(d4.as<uint8_t>(), stride, need, cnt, dout.as<uint8_t>(), n, st);
     RansResult res[4];
     HIP_TRY(hipMemcpyAsync(res, dres.p, sizeof(res), hipMemcpyDeviceToHost, st));
@@ -2121,141 +2213,6 @@ int alice_codec_ycocg_r_to_rgb(const int16_t* y, const int16_t* co, const int16_
 // ---- many chunks from host memory in one call: the chunk driver's fast path (the chains of all chunks run side
 // by side; a single chunk is bound by its three serial chains) ----
 
-// How many chunks of this shape the calling thread's device can hold at once (inputs or outputs, symbols, .alc
-// buffers with the worst observed payload of 1 byte per pixel sample, tables), leaving a fifth of the free memory alone.
-static uint32_t chunks_that_fit(const ChunkDims& d, uint32_t want) {
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return want; }
-    const long double per_chunk = (long double)d.n_pixels * 3 + (long double)d.padded * 3 * 2 + 3.0L * sizeof(RansTable) * 2 + 65536;
-    const long double fixed = (long double)std::max(forward_scratch_bytes(d), inverse_scratch_bytes(d, false)) + (64u << 20);
-    const long double room = (long double)free_b * 0.8L - fixed;
-    if (room < per_chunk) return 1;
-    const long double n = room / per_chunk;
-    return n >= (long double)want ? want : (uint32_t)n;
-}
-
-// Encodes the chunks at rgb[i] (host pointers, n_pixels * 3 bytes each) on the calling thread's device, as many at a
-// time as its memory holds; out[i] receives the chunk objects.  On error nothing is left in out.
-static int encode_chunks_on_device(const FrameEncoder& enc, const std::vector<const uint8_t*>& rgb, const ChunkDims& d,
-                                   const std::vector<EncodedChunk**>& out) {
-    const uint32_t n = (uint32_t)rgb.size();
-    for (uint32_t i = 0; i < n; ++i) *out[i] = nullptr;
-    if (!n) return kOk;
-    TRY(ensure_device());
-    const uint32_t per_pass = chunks_that_fit(d, n);
-    HubTicket ticket;
-    TRY(ticket.open(encode_device_bytes(d, per_pass)));
-    const hipStream_t st = ticket.st;
-    auto undo = [&](int rc) { for (uint32_t k = 0; k < n; ++k) { delete *out[k]; *out[k] = nullptr; } return rc; };
-    const uint64_t chunk_bytes = d.n_pixels * 3;
-    for (uint32_t first = 0; first < n; first += per_pass) {
-        const uint32_t B = std::min(per_pass, n - first);
-        DevBuf d_rgb;
-        EncodeWork w;
-        std::vector<RansResult> res;
-        int rc = d_rgb.alloc(chunk_bytes * B);
-        if (rc == kOk) rc = encode_work_alloc(w, d, (int)B);
-        if (rc != kOk) return undo(rc);
-        rc = parallel_chunks(B, chunk_bytes >= (4u << 20) ? kCopyThreads : 1u, [&](uint32_t i) {
-            HIP_TRY(hipMemcpyAsync(d_rgb.as<uint8_t>() + (size_t)i * chunk_bytes, rgb[first + i], chunk_bytes, hipMemcpyHostToDevice, st));
-            return (int)kOk;
-        });
-        if (rc != kOk) return undo(rc);
-        for (int attempt = 0;; ++attempt) {
-            rc = encode_launch(d_rgb.as<uint8_t>(), w, enc.quality, enc.wavelet, st, nullptr, (CapMode)attempt, &ticket);
-            if (rc != kOk) return undo(rc);
-            rc = encode_collect(w, st, res);
-            if (rc == kOk) break;
-            if (rc != -1 || attempt >= 2) return undo(rc == -1 ? fail(kInternal, "rANS output exceeded the worst-case bound") : rc);
-        }
-        // all headers with one strided copy, then the payloads straight into the chunk objects, several at a time
-        std::vector<uint8_t> hdr((size_t)B * kAlcHeaderBytes);
-        if (hipMemcpy2DAsync(hdr.data(), kAlcHeaderBytes, w.alc.p, w.alc_stride, kAlcHeaderBytes, B, hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess)
-            return undo(fail(kDeviceError, "device to host copy failed"));
-        for (uint32_t i = 0; i < B; ++i) {
-            const uint64_t payload = res[3 * i].len + res[3 * i + 1].len + res[3 * i + 2].len;
-            EncodedChunk* c = new (std::nothrow) EncodedChunk();
-            uint64_t tot = 0;
-            if (!c || parse_alc_header(hdr.data() + (size_t)i * kAlcHeaderBytes, kAlcHeaderBytes + payload, *c, &tot) != kOk || tot != payload) {
-                delete c;
-                return undo(fail(kInternal, "device header/payload length mismatch"));
-            }
-            *out[first + i] = c;   // (undo() deletes it from here on)
-        }
-        rc = parallel_chunks(B, w.alc_stride >= (4u << 20) ? kCopyThreads : 1u, [&](uint32_t i) {
-            EncodedChunk* c = *out[first + i];
-            const uint64_t payload = res[3 * i].len + res[3 * i + 1].len + res[3 * i + 2].len;
-            c->data.resize((size_t)payload);
-            return copy_to_host(c->data.data(), w.alc.as<uint8_t>() + (size_t)i * w.alc_stride + kAlcHeaderBytes, (size_t)payload, st);
-        });
-        if (rc != kOk) return undo(rc);
-    }
-    return kOk;
-}
-
-// Decodes chunks (all of one shape, validated by the caller) on the calling thread's device into rgb_out[i].
-static int decode_chunks_on_device(const std::vector<const EncodedChunk*>& chunks, const ChunkDims& d, const std::vector<uint8_t*>& rgb_out) {
-    const uint32_t n = (uint32_t)chunks.size();
-    if (!n || d.n_pixels == 0) return kOk;
-    TRY(ensure_device());
-    const uint32_t per_pass = chunks_that_fit(d, n);
-    uint64_t max_payload = 0;
-    for (const EncodedChunk* c : chunks) max_payload = std::max<uint64_t>(max_payload, c->data.size());
-    HubTicket ticket;
-    TRY(ticket.open(decode_device_bytes(d, per_pass, (uint64_t)per_pass * (max_payload + 512))));
-    const hipStream_t st = ticket.st;
-    const uint64_t chunk_bytes = d.n_pixels * 3;
-    for (uint32_t first = 0; first < n; first += per_pass) {
-        const uint32_t B = std::min(per_pass, n - first);
-        std::vector<EncodedChunk> hdrs(B);
-        uint64_t total_payload = 0;
-        for (uint32_t i = 0; i < B; ++i) {
-            const EncodedChunk& c = *chunks[first + i];
-            hdrs[i].width = c.width; hdrs[i].height = c.height; hdrs[i].frames = c.frames; hdrs[i].wavelet = c.wavelet;
-            for (int k = 0; k < 3; ++k) hdrs[i].ch[k] = c.ch[k];
-            total_payload += round_up(c.data.size() + 16, 256);
-        }
-        DevBuf d_payload, d_rgb;
-        TRY(d_payload.alloc(total_payload + 256));
-        TRY(d_rgb.alloc(chunk_bytes * B));
-        std::vector<const uint8_t*> pay(B);
-        std::vector<uint8_t*> dst(B);
-        uint64_t off = 0;
-        for (uint32_t i = 0; i < B; ++i) {
-            const EncodedChunk& c = *chunks[first + i];
-            pay[i] = d_payload.as<uint8_t>() + off;
-            dst[i] = d_rgb.as<uint8_t>() + (size_t)i * chunk_bytes;
-            if (!c.data.empty())
-                HIP_TRY(hipMemcpyAsync(d_payload.as<uint8_t>() + off, c.data.data(), c.data.size(), hipMemcpyHostToDevice, st));
-            off += round_up(c.data.size() + 16, 256);
-        }
-        DecodeWork w;
-        TRY(decode_work_alloc(w, d, (int)B));
-        TRY(decode_launch(hdrs, pay, w, dst, st, nullptr, &ticket));
-        TRY(decode_collect(w, st));
-        TRY(parallel_chunks(B, chunk_bytes >= (4u << 20) ? kCopyThreads : 1u,
-                            [&](uint32_t i) { return copy_to_host(rgb_out[first + i], dst[i], chunk_bytes, st); }));
-    }
-    return kOk;
-}
-
-// validation shared by the many-chunk encode entry points (FrameEncoder::encode's, src/pipeline.rs:388-427, per chunk)
-static int validate_encode_many(const FrameEncoder* encoder, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
-                                uint32_t frames, uint32_t n_chunks, EncodedChunk** out_chunks, ChunkDims* d) {
-    if (!encoder || !out_chunks || (!rgb && rgb_len)) return fail(kNullArgument, "null argument");
-    for (uint32_t i = 0; i < n_chunks; ++i) out_chunks[i] = nullptr;
-    if (n_chunks == 0) return kOk;
-    uint64_t n_pixels = 0;
-    TRY(checked_pixel_count(width, height, frames, &n_pixels));
-    if (n_pixels == 0 || width == 0 || height == 0) return fail(kInvalidDimensions, "invalid dimensions");
-    if (n_pixels > UINT64_MAX / 3 / n_chunks) return fail(kDimensionOverflow, "dimensions overflow usize");
-    if (rgb_len != n_pixels * 3 * n_chunks)
-        return fail(kInvalidBufferSize, "buffer size mismatch: expected " + std::to_string(n_pixels * 3 * n_chunks) + ", got " + std::to_string(rgb_len));
-    *d = make_dims(width, height, frames);
-    if (d->padded > 0xFFFFFFFFull) return fail(kDimensionOverflow, "padded pixel count does not fit the header's u32 num_symbols");
-    return kOk;
-}
 static int validate_decode_many(const EncodedChunk* const* chunks, uint32_t n_chunks, uint8_t* rgb_out, uint64_t rgb_out_len, ChunkDims* d) {
     if (!chunks || (!rgb_out && rgb_out_len)) return fail(kNullArgument, "null argument");
     if (n_chunks == 0) return kOk;
@@ -2276,22 +2233,14 @@ int alice_codec_encode_many(const FrameEncoder* encoder, const uint8_t* rgb, uin
     clear_error();
     ChunkDims d{};
     TRY(validate_encode_many(encoder, rgb, rgb_len, width, height, frames, n_chunks, out_chunks, &d));
-    if (n_chunks == 0) return kOk;
-    std::vector<const uint8_t*> src(n_chunks);
-    std::vector<EncodedChunk**> dst(n_chunks);
-    for (uint32_t i = 0; i < n_chunks; ++i) { src[i] = rgb + (size_t)i * d.n_pixels * 3; dst[i] = &out_chunks[i]; }
-    return encode_chunks_on_device(*encoder, src, d, dst);
+    return encode_chunks_on_device(*encoder, rgb, d, out_chunks, n_chunks);
 }
 
 int alice_codec_decode_many(const EncodedChunk* const* chunks, uint32_t n_chunks, uint8_t* rgb_out, uint64_t rgb_out_len) {
     clear_error();
     ChunkDims d{};
     TRY(validate_decode_many(chunks, n_chunks, rgb_out, rgb_out_len, &d));
-    if (n_chunks == 0 || d.n_pixels == 0) return kOk;
-    std::vector<const EncodedChunk*> src(chunks, chunks + n_chunks);
-    std::vector<uint8_t*> dst(n_chunks);
-    for (uint32_t i = 0; i < n_chunks; ++i) dst[i] = rgb_out + (size_t)i * d.n_pixels * 3;
-    return decode_chunks_on_device(src, d, dst);
+    return decode_chunks_on_device(chunks, d, rgb_out, n_chunks);
 }
 
 // ---- the same over several GPUs of the node: chunk k goes to devices[k mod n_devices] (64-frame chunks are independent
@@ -2310,29 +2259,17 @@ int alice_codec_many_devices_plan(uint32_t n_chunks, const int* devices, uint32_
 
 }  // extern "C"
 namespace {
-struct WorkerResult { int code = kOk; std::string msg; };
 // runs fn(slot) on one thread per slot of the device list, each bound to its device; returns the first failure
 template <typename Fn>
 int run_on_devices(const int* devices, uint32_t n_devices, Fn fn) {
     const int count = alice_codec_device_count();
     for (uint32_t i = 0; i < n_devices; ++i)
         if (devices[i] >= count) return fail(kDeviceError, "device index " + std::to_string(devices[i]) + " out of range (" + std::to_string(count) + " visible)");
-    std::vector<WorkerResult> res(n_devices);
-    std::vector<std::thread> th;
-    th.reserve(n_devices);
-    for (uint32_t s = 0; s < n_devices; ++s)
-        th.emplace_back([&, s] {
-            clear_error();
-            tl_device = devices[s];
-            int rc = ensure_device();
-            if (rc == kOk) rc = fn(s);
-            res[s].code = rc;
-            if (rc != kOk) res[s].msg = tl_msg;
-        });
-    for (auto& t : th) t.join();
-    for (uint32_t s = 0; s < n_devices; ++s)
-        if (res[s].code != kOk) return fail(res[s].code, "device " + std::to_string(devices[s]) + ": " + res[s].msg);
-    return kOk;
+    return on_threads(n_devices, [&](uint32_t s) { return devices[s]; }, [&](uint32_t s) {
+        int rc = ensure_device();
+        if (rc == kOk) rc = fn(s);
+        return rc == kOk ? rc : fail(rc, "device " + std::to_string(devices[s]) + ": " + tl_msg);
+    });
 }
 }  // namespace
 extern "C" {
@@ -2346,10 +2283,7 @@ int alice_codec_encode_many_devices(const FrameEncoder* encoder, const uint8_t* 
     TRY(alice_codec_many_devices_plan(n_chunks, devices, n_devices, plan.data()));
     if (n_chunks == 0) return kOk;
     const int rc = run_on_devices(devices, n_devices, [&](uint32_t slot) {
-        std::vector<const uint8_t*> src;
-        std::vector<EncodedChunk**> dst;
-        for (uint32_t k = slot; k < n_chunks; k += n_devices) { src.push_back(rgb + (size_t)k * d.n_pixels * 3); dst.push_back(&out_chunks[k]); }
-        return encode_chunks_on_device(*encoder, src, d, dst);
+        return encode_chunks_on_device(*encoder, rgb, d, out_chunks, n_chunks, slot, n_devices);
     });
     if (rc != kOk)
         for (uint32_t k = 0; k < n_chunks; ++k) { delete out_chunks[k]; out_chunks[k] = nullptr; }
@@ -2365,10 +2299,7 @@ int alice_codec_decode_many_devices(const EncodedChunk* const* chunks, uint32_t 
     TRY(alice_codec_many_devices_plan(n_chunks, devices, n_devices, plan.data()));
     if (n_chunks == 0 || d.n_pixels == 0) return kOk;
     return run_on_devices(devices, n_devices, [&](uint32_t slot) {
-        std::vector<const EncodedChunk*> src;
-        std::vector<uint8_t*> dst;
-        for (uint32_t k = slot; k < n_chunks; k += n_devices) { src.push_back(chunks[k]); dst.push_back(rgb_out + (size_t)k * d.n_pixels * 3); }
-        return decode_chunks_on_device(src, d, dst);
+        return decode_chunks_on_device(chunks, d, rgb_out, n_chunks, slot, n_devices);
     });
 }
 
@@ -2381,24 +2312,18 @@ int alice_codec_dev_forward_symbols(const void* d_rgb, uint32_t width, uint32_t 
     clear_error();
     if (!d_rgb || !d_symbols) return fail(kNullArgument, "null argument");
     if (wavelet_type > 2) return fail(kInvalidBitstream, "unknown wavelet type");
-    uint64_t n_pixels = 0;
-    TRY(checked_pixel_count(width, height, frames, &n_pixels));
-    if (n_pixels == 0) return fail(kInvalidDimensions, "invalid dimensions");
-    const ChunkDims d = make_dims(width, height, frames);
-    if (d.padded > 0xFFFFFFFFull) return fail(kDimensionOverflow, "padded pixel count exceeds u32");
+    ChunkDims d{};
+    TRY(chunk_dims(width, height, frames, &d));
     TRY(ensure_device());
     hipStream_t st = (hipStream_t)hip_stream;
     ScopeStream scope(st);   // temporaries drain the caller's stream before they return to the pool
     EncodeWork w;
     w.d = d; w.n_chunks = 1;
-    const bool tiles = transform_tiles_eligible(d);
-    if (tiles) TRY(w.scratch.alloc(forward_scratch_bytes(d)));
+    if (transform_tiles_eligible(d)) TRY(w.scratch.alloc(forward_scratch_bytes(d)));
     TRY(w.hist.alloc(3 * 256 * sizeof(uint32_t)));
     uint32_t* hist = d_hist ? (uint32_t*)d_hist : w.hist.as<uint32_t>();
     HIP_TRY(hipMemsetAsync(hist, 0, 3 * 256 * sizeof(uint32_t), st));
-    const int32_t step = quality_to_step(quality);
-    if (!tiles || !launch_forward_transform((const uint8_t*)d_rgb, d, wavelet_type, step, w.scratch.p, (uint8_t*)d_symbols, hist, st))
-        TRY(forward_generic((const uint8_t*)d_rgb, d, wavelet_type, step, w, (uint8_t*)d_symbols, hist, st));
+    TRY(forward_chunk((const uint8_t*)d_rgb, d, wavelet_type, quality_to_step(quality), w, (uint8_t*)d_symbols, hist, st));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
     return kOk;
@@ -2409,21 +2334,15 @@ int alice_codec_dev_inverse_symbols(const void* d_symbols, uint32_t width, uint3
     clear_error();
     if (!d_rgb || !d_symbols || !step) return fail(kNullArgument, "null argument");
     if (wavelet_type > 2) return fail(kInvalidBitstream, "unknown wavelet type");
-    uint64_t n_pixels = 0;
-    TRY(checked_pixel_count(width, height, frames, &n_pixels));
-    if (n_pixels == 0) return fail(kInvalidDimensions, "invalid dimensions");
-    const ChunkDims d = make_dims(width, height, frames);
-    if (d.padded > 0xFFFFFFFFull) return fail(kDimensionOverflow, "padded pixel count exceeds u32");
+    ChunkDims d{};
+    TRY(chunk_dims(width, height, frames, &d));
     TRY(ensure_device());
     hipStream_t st = (hipStream_t)hip_stream;
     ScopeStream scope(st);   // temporaries drain the caller's stream before they return to the pool
     DecodeWork w;
     w.d = d; w.n_chunks = 1;
-    const InverseBounds ib = inverse_bounds(wavelet_type, step);
-    const bool tiles = transform_tiles_eligible(d);
-    if (tiles) TRY(w.scratch_own.alloc(inverse_scratch_bytes(d, ib.fast && ib.mid16)));
-    if (!tiles || !launch_inverse_transform((const uint8_t*)d_symbols, d, wavelet_type, step, !ib.fast, ib.fast && ib.mid16, ib.fast && ib.lds16, w.scratch_own.p, (uint8_t*)d_rgb, st))
-        TRY(inverse_generic((const uint8_t*)d_symbols, d, wavelet_type, step, w, (uint8_t*)d_rgb, st));
+    if (transform_tiles_eligible(d)) TRY(w.scratch_own.alloc(inverse_scratch_bytes(d, inverse_bounds(wavelet_type, step).mid16)));
+    TRY(inverse_chunk((const uint8_t*)d_symbols, d, wavelet_type, step, w.scratch_own.p, w, (uint8_t*)d_rgb, st));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
     return kOk;
@@ -2486,9 +2405,7 @@ int alice_codec_dev_rans_encode(const void* d_symbols, uint64_t n, const uint32_
     RansResult res{};
     HIP_TRY(hipMemcpyAsync(&res, dres.p, sizeof(res), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (res.flags & kTableDiverges)
-        return fail(kReferenceDiverges, "a symbol whose table frequency wrapped to 0 is present: the reference encoder does not terminate on this input");
-    if (res.flags & kRansInternal) return fail(kInternal, "rANS kernel invariant violated");
+    TRY(encode_flags_error(res.flags));
     if (res.flags & kRansOverflow) return fail(kInvalidBufferSize, "stream region too small for this chain (use alice_codec_rans_stream_bound(NULL, n))");
     *out_len = res.len;
     *out_offset = cap - res.len;
@@ -2556,7 +2473,7 @@ int alice_codec_test_transform_ms(const void* d_rgb, void* d_sym, void* d_rgb_ou
     const int32_t steps[3] = {step, step, step};
     const InverseBounds ib = inverse_bounds(wavelet_type, steps);
     DevBuf scratch, hist;
-    TRY(scratch.alloc(std::max(forward_scratch_bytes(d), inverse_scratch_bytes(d, ib.fast && ib.mid16))));
+    TRY(scratch.alloc(std::max(forward_scratch_bytes(d), inverse_scratch_bytes(d, ib.mid16))));
     TRY(hist.alloc(3 * 256 * sizeof(uint32_t)));
     HIP_TRY(hipMemsetAsync(hist.p, 0, 3 * 256 * sizeof(uint32_t), st));
     StageEvents ev;
@@ -2572,8 +2489,8 @@ int alice_codec_test_transform_ms(const void* d_rgb, void* d_sym, void* d_rgb_ou
     auto inv = [&]() {
         for (uint32_t c = 0; c < n_chunks; ++c) {
             const uint32_t k = c % n_buffers;
-            launch_inverse_transform((const uint8_t*)d_sym + (size_t)k * 3 * d.padded, d, wavelet_type, steps, !ib.fast, ib.fast && ib.mid16,
-                                     ib.fast && ib.lds16, scratch.p, (uint8_t*)d_rgb_out + (size_t)k * d.n_pixels * 3, st);
+            launch_inverse_transform((const uint8_t*)d_sym + (size_t)k * 3 * d.padded, d, wavelet_type, steps, ib.exact, ib.mid16,
+                                     ib.lds16, scratch.p, (uint8_t*)d_rgb_out + (size_t)k * d.n_pixels * 3, st);
         }
     };
     fwd();   // warm-up; also leaves real symbols for the inverse

@@ -562,6 +562,30 @@ def test_batch_in_place_decode_odd_shape(gpu_codec, oracle_mod):
         assert np.array_equal(t.cpu().numpy(), want), i
 
 
+def test_batch_stream_capacity_overflow_is_retried(gpu_codec, oracle_mod):
+    """A batch's first encode sizes its stream regions from the histograms; the test hook shrinks them to 4352 bytes, so
+    every chain overflows and encode_finish must climb the capacity ladder (estimate, then the worst case) itself."""
+    import torch
+    w, h, f, B = 96, 64, 16, 2
+    chunks = [np.random.default_rng(31 + i).integers(0, 256, w * h * f * 3, dtype=np.uint8) for i in range(B)]
+    refs = [oracle_mod.encode(c, w, h, f, 90, 1) for c in chunks]
+    assert all(len(r) > 3138 + 3 * 4352 for r in refs)
+    rgb = torch.from_numpy(np.stack(chunks)).cuda()
+    st = torch.cuda.current_stream().cuda_stream
+    lib = gpu_codec.load_library()
+    lib.alice_codec_test_force_first_cap(4352)
+    try:
+        bt = gpu_codec.Batch(w, h, f, B, 90, gpu_codec.WaveletType.Cdf97)
+        bt.encode(rgb.data_ptr(), st)
+        sizes = bt.encode_finish()
+    finally:
+        lib.alice_codec_test_force_first_cap(0)
+    for i in range(B):
+        t = torch.empty(int(sizes[i]), dtype=torch.uint8, device="cuda")
+        gpu_hip_memcpy(t.data_ptr(), bt.alc_ptr(i), int(sizes[i]))
+        assert bytes(t.cpu().numpy()) == refs[i], i
+
+
 def gpu_hip_memcpy(dst, src, n):
     hip = C.CDLL("libamdhip64.so")
     hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
