@@ -217,6 +217,19 @@ def load_library() -> C.CDLL:
         "alice_codec_rans_stream_bound": (C.c_uint64, [_u32p, C.c_uint64]),
         "alice_codec_dev_rans_encode": (C.c_int, [vp, C.c_uint64, _u32p, vp, C.c_uint64, _u64p, _u64p, vp]),
         "alice_codec_dev_rans_decode": (C.c_int, [vp, C.c_uint64, _u32p, vp, C.c_uint64, vp]),
+        "alice_codec_segment_by_motion": (C.c_int, [_u8p, C.c_uint64, _u8p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint8,
+                                                    C.c_uint32, C.c_uint32, _u8p, C.c_uint64, _u32p, _u32p]),
+        "alice_codec_segment_by_chroma": (C.c_int, [_i16p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int16, _u8p, C.c_uint64,
+                                                    _u32p, _u32p]),
+        "alice_codec_rle_encode_mask": (vp, [_u8p, C.c_uint64, _u64p]),
+        "alice_codec_extract_person_rgb": (C.c_int, [_u8p, C.c_uint64, C.c_uint32, _u32p, _u8p, C.c_uint64, _u8p, C.c_uint64,
+                                                     _u64p]),
+        "alice_codec_dev_segment_motion": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint8,
+                                                     C.c_uint32, C.c_uint32, vp, vp, vp]),
+        "alice_codec_dev_segment_chroma_rgb": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int16, vp, vp, vp]),
+        "alice_codec_rle_bound": (C.c_uint64, [C.c_uint64]),
+        "alice_codec_dev_rle_encode_mask": (C.c_int, [vp, C.c_uint64, vp, C.c_uint64, _u64p, vp]),
+        "alice_codec_dev_extract_person_rgb": (C.c_int, [vp, C.c_uint32, C.c_uint32, _u32p, vp, vp, C.c_uint64, _u64p, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
@@ -985,3 +998,245 @@ class Batch:
     def fixed_bytes(self) -> int:
         """device bytes the batch holds whatever its chunk count (transform scratch)"""
         return load_library().alice_codec_batch_fixed_bytes(self._h)
+
+
+# ---------------------------------------------------------------------------------------------
+# person segmentation (reference src/segment.rs; kernels in csrc/segment.hip)
+# ---------------------------------------------------------------------------------------------
+
+_U32 = 0xFFFFFFFF
+
+
+def _nz(a: np.ndarray, t):
+    return _p(a, t) if a.size else C.cast(C.c_char_p(b"\0\0\0\0"), t)
+
+
+def _u32_arg(v, what: str) -> int:
+    v = int(v)
+    if not 0 <= v <= _U32:
+        raise CodecError(3, f"{what} out of u32 range")
+    return v
+
+
+class SegmentConfig:
+    """reference src/segment.rs:42-63.  min_region_size is carried and, as in the reference, not used."""
+
+    def __init__(self, motion_threshold: int = 25, min_region_size: int = 100, dilate_radius: int = 2, erode_radius: int = 1):
+        self.motion_threshold = int(motion_threshold)
+        self.min_region_size = int(min_region_size)
+        self.dilate_radius = int(dilate_radius)
+        self.erode_radius = int(erode_radius)
+
+    def __repr__(self):
+        return (f"SegmentConfig(motion_threshold={self.motion_threshold}, min_region_size={self.min_region_size}, "
+                f"dilate_radius={self.dilate_radius}, erode_radius={self.erode_radius})")
+
+
+class SegmentResult:
+    """reference src/segment.rs:78-154: mask (u8, 1 = person), bbox [x, y, w, h], foreground_count, width, height."""
+
+    def __init__(self, mask, bbox, foreground_count: int, width: int, height: int):
+        self.mask = _as_u8(mask)
+        self.bbox = [int(v) for v in bbox]
+        self.foreground_count = int(foreground_count)
+        self.width = int(width)
+        self.height = int(height)
+
+    def coverage(self) -> float:
+        """f32 arithmetic as in :94-101 (count * (1 / total)); 0.0 for an empty frame."""
+        total = self.width * self.height
+        if total > _U32:
+            raise CodecError(3, "width * height does not fit u32")
+        if total == 0:
+            return 0.0
+        inv = np.float32(1.0) / np.float32(total)
+        return float(np.float32(self.foreground_count) * inv)
+
+    def extract_person_rgb(self, frame_rgb) -> bytes:
+        """:107-125 -- the bbox pixels whose mask byte is exactly 1."""
+        return extract_person_rgb(self.mask, self.width, self.bbox, frame_rgb)
+
+    def rle_encode_mask(self) -> bytes:
+        """:131-154 -- [len u16 LE, value u8] per run of (mask & 1)."""
+        return rle_encode_mask(self.mask)
+
+
+def _seg_out(rc: int, mask: np.ndarray, bbox: np.ndarray, count, width: int, height: int) -> SegmentResult:
+    _check(rc)
+    return SegmentResult(mask, [int(v) for v in bbox], int(count.value), width, height)
+
+
+def segment_by_motion(current, reference, width: int, height: int, config: SegmentConfig | None = None) -> SegmentResult:
+    """reference src/segment.rs:172-230 on the GPU."""
+    cfg = config or SegmentConfig()
+    w, h = _u32_arg(width, "width"), _u32_arg(height, "height")
+    cur, ref = _as_u8(current), _as_u8(reference)
+    total = w * h
+    mask = np.zeros(total if total <= _U32 else 0, np.uint8)
+    bbox = np.zeros(4, np.uint32)
+    cnt = C.c_uint32()
+    rc = load_library().alice_codec_segment_by_motion(_nz(cur, _u8p), cur.size, _nz(ref, _u8p), ref.size, w, h,
+                                                      int(cfg.motion_threshold) & 0xFF, _u32_arg(cfg.dilate_radius, "dilate_radius"),
+                                                      _u32_arg(cfg.erode_radius, "erode_radius"), _nz(mask, _u8p), mask.size,
+                                                      _p(bbox, _u32p), C.byref(cnt))
+    return _seg_out(rc, mask, bbox, cnt, w, h)
+
+
+def segment_by_chroma(y, co, cg, width: int, height: int, green_threshold: int) -> SegmentResult:
+    """reference src/segment.rs:234-265 on the GPU (y and co are accepted and ignored, as there).  A cg shorter than
+    width*height raises InvalidBufferSize where the reference panics."""
+    del y, co
+    w, h = _u32_arg(width, "width"), _u32_arg(height, "height")
+    c = np.ascontiguousarray(cg, np.int16).reshape(-1)
+    total = w * h
+    mask = np.zeros(total if total <= _U32 else 0, np.uint8)
+    bbox = np.zeros(4, np.uint32)
+    cnt = C.c_uint32()
+    rc = load_library().alice_codec_segment_by_chroma(_nz(c, _i16p), c.size, w, h, int(green_threshold), _nz(mask, _u8p), mask.size,
+                                                      _p(bbox, _u32p), C.byref(cnt))
+    return _seg_out(rc, mask, bbox, cnt, w, h)
+
+
+def rle_encode_mask(mask) -> bytes:
+    """SegmentResult::rle_encode_mask (src/segment.rs:131-154) of any byte mask, on the GPU."""
+    m = _as_u8(mask)
+    lib = load_library()
+    n = C.c_uint64()
+    p = lib.alice_codec_rle_encode_mask(_nz(m, _u8p), m.size, C.byref(n))
+    if not p:
+        _raise_last()
+    try:
+        return _copy_out(p, n.value).tobytes()
+    finally:
+        lib.alice_codec_data_free64(p, n.value)
+
+
+def extract_person_rgb(mask, width: int, bbox, frame_rgb) -> bytes:
+    """SegmentResult::extract_person_rgb (src/segment.rs:107-125) on the GPU."""
+    m, rgb = _as_u8(mask), _as_u8(frame_rgb)
+    b = np.array([_u32_arg(v, "bbox") for v in bbox], np.uint32)
+    out = np.zeros(3 * int(b[2]) * int(b[3]), np.uint8)
+    n = C.c_uint64()
+    _check(load_library().alice_codec_extract_person_rgb(_nz(m, _u8p), m.size, _u32_arg(width, "width"), _p(b, _u32p), _nz(rgb, _u8p),
+                                                          rgb.size, _nz(out, _u8p), out.size, C.byref(n)))
+    return out[:n.value].tobytes()
+
+
+def _bbox_rows(frame_width: int, bbox):
+    """rows of crop_to_bbox / paste_from_bbox (src/segment.rs:269-298): (start, end) per row; u32 row * frame_width + bx"""
+    bx, by, bw, bh = (_u32_arg(v, "bbox") for v in bbox)
+    fw = _u32_arg(frame_width, "frame_width")
+    if by + bh > _U32:
+        raise CodecError(3, "bbox y + h does not fit u32")
+    for row in range(by, by + bh):
+        start = row * fw + bx
+        if start > _U32:
+            raise CodecError(3, "row * frame_width + x does not fit u32")
+        yield start, start + bw
+
+
+def crop_to_bbox(frame, frame_width: int, bbox) -> bytes:
+    """reference src/segment.rs:269-281 (host byte copy): a row whose end falls past the frame is skipped."""
+    f = _as_u8(frame)
+    bw = int(bbox[2])
+    parts = [f[s:e] for s, e in _bbox_rows(frame_width, bbox) if e <= f.size]
+    return np.concatenate(parts).tobytes() if parts and bw else b""
+
+
+def paste_from_bbox(frame: np.ndarray, frame_width: int, person_data, bbox) -> np.ndarray:
+    """reference src/segment.rs:284-298 (host byte copy) into `frame` (a writable uint8 array), which is returned."""
+    if not (isinstance(frame, np.ndarray) and frame.dtype == np.uint8 and frame.flags.c_contiguous):
+        raise TypeError("frame must be a C-contiguous uint8 numpy array")
+    dst = frame.reshape(-1)
+    src = _as_u8(person_data)
+    bw = int(bbox[2])
+    off = 0
+    for s, e in _bbox_rows(frame_width, bbox):
+        if e <= dst.size and off + bw <= src.size:
+            dst[s:e] = src[off:off + bw]
+        off += bw
+    return frame
+
+
+# the reference's own Python functions (src/python.rs:80-267): same names, arguments, defaults and return shapes;
+# frames are 2-D [H, W] arrays
+
+def _plane(a, dtype) -> np.ndarray:
+    a = np.asarray(a)
+    if a.ndim != 2:
+        raise ValueError("expected a 2-D [H, W] array")
+    return np.ascontiguousarray(a, dtype)
+
+
+def segment_motion_numpy(current, reference, motion_threshold: int = 25, dilate_radius: int = 2, erode_radius: int = 1):
+    """-> (mask [H, W] uint8, [x, y, w, h], foreground_count)  (src/python.rs:80-129)"""
+    cur, ref = _plane(current, np.uint8), _plane(reference, np.uint8)
+    h, w = cur.shape
+    r = segment_by_motion(cur, ref, w, h, SegmentConfig(motion_threshold, 100, dilate_radius, erode_radius))
+    return r.mask.reshape(h, w), r.bbox, r.foreground_count
+
+
+def segment_chroma_numpy(y_channel, co_channel, cg_channel, green_threshold: int = 30):
+    """-> (mask [H, W] uint8, [x, y, w, h], foreground_count)  (src/python.rs:141-184; shape from the Y plane)"""
+    h, w = _plane(y_channel, np.int16).shape
+    r = segment_by_chroma(None, None, _plane(cg_channel, np.int16), w, h, green_threshold)
+    return r.mask.reshape(h, w), r.bbox, r.foreground_count
+
+
+def crop_bbox_numpy(frame, bbox) -> np.ndarray:
+    """-> [bh, bw] uint8  (src/python.rs:195-217)"""
+    if len(bbox) != 4:
+        raise ValueError("bbox must have 4 elements")
+    f = _plane(frame, np.uint8)
+    out = np.frombuffer(crop_to_bbox(f, f.shape[1], bbox), np.uint8).copy()
+    return out.reshape(int(bbox[3]), int(bbox[2]))
+
+
+def paste_bbox_numpy(frame: np.ndarray, person_data, bbox) -> None:
+    """in place into a C-contiguous [H, W] uint8 frame  (src/python.rs:227-248)"""
+    if len(bbox) != 4:
+        raise ValueError("bbox must have 4 elements")
+    if not (isinstance(frame, np.ndarray) and frame.ndim == 2):
+        raise ValueError("expected a 2-D [H, W] array")
+    paste_from_bbox(frame, frame.shape[1], person_data, bbox)
+
+
+def rle_encode_numpy(mask) -> list:
+    """-> list of byte values, as PyO3 returns a Vec<u8>  (src/python.rs:257-271)"""
+    return list(rle_encode_mask(_plane(mask, np.uint8)))
+
+
+# device-resident (data_ptr() integers, like Batch); stats = n_frames x {x, y, w, h, count} uint32
+
+def segment_motion_device(d_current: int, d_reference: int, reference_stride: int, width: int, height: int, n_frames: int,
+                          d_stats: int, d_mask: int | None = None, config: SegmentConfig | None = None, stream: int = 0) -> None:
+    cfg = config or SegmentConfig()
+    _check(load_library().alice_codec_dev_segment_motion(d_current, d_reference, reference_stride, width, height, n_frames,
+                                                         int(cfg.motion_threshold) & 0xFF, cfg.dilate_radius, cfg.erode_radius,
+                                                         d_mask, d_stats, stream))
+
+
+def segment_chroma_rgb_device(d_rgb: int, width: int, height: int, n_frames: int, green_threshold: int, d_stats: int,
+                              d_mask: int | None = None, stream: int = 0) -> None:
+    _check(load_library().alice_codec_dev_segment_chroma_rgb(d_rgb, width, height, n_frames, int(green_threshold), d_mask, d_stats,
+                                                             stream))
+
+
+def rle_bound(n: int) -> int:
+    return int(load_library().alice_codec_rle_bound(n))
+
+
+def rle_encode_mask_device(d_mask: int, n: int, d_out: int, cap: int, stream: int = 0) -> int:
+    """-> bytes written at d_out (cap >= rle_bound(n))"""
+    out = C.c_uint64()
+    _check(load_library().alice_codec_dev_rle_encode_mask(d_mask, n, d_out, cap, C.byref(out), stream))
+    return out.value
+
+
+def extract_person_rgb_device(d_mask: int, width: int, height: int, bbox, d_rgb: int, d_out: int, cap: int, stream: int = 0) -> int:
+    """-> bytes written at d_out (cap >= 3 * bbox w * h)"""
+    b = np.array([_u32_arg(v, "bbox") for v in bbox], np.uint32)
+    out = C.c_uint64()
+    _check(load_library().alice_codec_dev_extract_person_rgb(d_mask, width, height, _p(b, _u32p), d_rgb, d_out, cap, C.byref(out),
+                                                             stream))
+    return out.value

@@ -2514,3 +2514,271 @@ int alice_codec_test_transform_ms(const void* d_rgb, void* d_sym, void* d_rgb_ou
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// segmentation (src/segment.rs; kernels in segment.hip)
+// ------------------------------------------------------------------------------------------
+namespace {
+
+// width * height as the reference's u32 `total` (src/segment.rs:179, :242): a product past u32 wraps in a release build
+// and panics in a debug one, here it is an error before any device work
+int segment_total(uint32_t w, uint32_t h, uint64_t* total) {
+    const uint64_t t = (uint64_t)w * h;
+    if (t > 0xFFFFFFFFull) return fail(kDimensionOverflow, "width * height does not fit u32");
+    *total = t;
+    return kOk;
+}
+
+// extract_person_rgb indexes the mask with u32 arithmetic (src/segment.rs:111-113): every index of the bbox walk must fit
+int bbox_indices_fit(uint32_t width, const uint32_t bbox[4]) {
+    const uint64_t bx = bbox[0], by = bbox[1], bw = bbox[2], bh = bbox[3];
+    if (by + bh > 0xFFFFFFFFull || bx + bw > 0xFFFFFFFFull) return fail(kDimensionOverflow, "bbox end does not fit u32");
+    if (bw && bh && (by + bh - 1) * width + bx + bw - 1 > 0xFFFFFFFFull)
+        return fail(kDimensionOverflow, "bbox index row * width + col does not fit u32");
+    return kOk;
+}
+
+// one segmentation on device buffers; d_mask may be null; total > 0
+int segment_on_device(const SegSource& src, uint32_t w, uint32_t h, uint32_t n_frames, uint32_t rd, uint32_t re, uint8_t* d_mask,
+                      uint32_t* d_stats, hipStream_t st) {
+    DevBuf scratch;
+    const uint64_t sb = segment_scratch_bytes(w, h, n_frames, rd, re);
+    if (sb) TRY(scratch.alloc(sb));
+    launch_segment(src, w, h, n_frames, rd, re, scratch.p, d_mask, d_stats, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    return kOk;
+}
+
+// host planes in, host mask / bbox / count out (the shared tail of segment_by_motion and segment_by_chroma)
+int segment_host(SegSource src, const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes, uint32_t w, uint32_t h,
+                 uint32_t rd, uint32_t re, uint8_t* mask, uint32_t bbox[4], uint32_t* count) {
+    const uint64_t total = (uint64_t)w * h;
+    TRY(ensure_device());
+    hipStream_t st;
+    TRY(get_stream(&st));
+    DevBuf da, db, dm, ds;
+    TRY(da.alloc(a_bytes));
+    if (b) TRY(db.alloc(b_bytes));
+    TRY(dm.alloc(total));
+    TRY(ds.alloc(5 * sizeof(uint32_t)));
+    HIP_TRY(hipMemcpyAsync(da.p, a, a_bytes, hipMemcpyHostToDevice, st));
+    if (b) HIP_TRY(hipMemcpyAsync(db.p, b, b_bytes, hipMemcpyHostToDevice, st));
+    if (src.kind == kSegMotion) { src.cur = da.as<uint8_t>(); src.ref = db.as<uint8_t>(); }
+    else src.cg = da.as<int16_t>();
+    TRY(segment_on_device(src, w, h, 1, rd, re, dm.as<uint8_t>(), ds.as<uint32_t>(), st));
+    uint32_t stats[5];
+    HIP_TRY(hipMemcpyAsync(mask, dm.p, total, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(stats, ds.p, sizeof(stats), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    memcpy(bbox, stats, 4 * sizeof(uint32_t));
+    *count = stats[4];
+    return kOk;
+}
+
+int empty_segment(uint32_t bbox[4], uint32_t* count) {
+    bbox[0] = bbox[1] = bbox[2] = bbox[3] = 0;
+    *count = 0;
+    return kOk;
+}
+
+// RLE of n > 0 device bytes into d_out (>= 3n); *out_len = bytes written
+int rle_on_device(const uint8_t* d_mask, uint64_t n, uint8_t* d_out, uint64_t* out_len, hipStream_t st) {
+    DevBuf scratch, dn;
+    TRY(scratch.alloc(rle_scratch_bytes(n)));
+    TRY(dn.alloc(sizeof(unsigned long long)));
+    launch_rle(d_mask, n, d_out, scratch.p, dn.as<unsigned long long>(), st);
+    HIP_TRY(hipGetLastError());
+    unsigned long long pieces = 0;
+    HIP_TRY(hipMemcpyAsync(&pieces, dn.p, sizeof(pieces), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *out_len = pieces * 3;
+    return kOk;
+}
+
+int extract_on_device(const uint8_t* d_mask, uint64_t mask_len, const uint8_t* d_rgb, uint64_t rgb_len, uint32_t width,
+                      const uint32_t bbox[4], uint8_t* d_out, uint64_t* out_len, hipStream_t st) {
+    DevBuf scratch, dn;
+    TRY(scratch.alloc(compact_scratch_bytes((uint64_t)bbox[2] * bbox[3])));
+    TRY(dn.alloc(sizeof(unsigned long long)));
+    launch_extract_person(d_mask, mask_len, d_rgb, rgb_len, width, bbox, d_out, scratch.p, dn.as<unsigned long long>(), st);
+    HIP_TRY(hipGetLastError());
+    unsigned long long px = 0;
+    HIP_TRY(hipMemcpyAsync(&px, dn.p, sizeof(px), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *out_len = px * 3;
+    return kOk;
+}
+
+}  // namespace
+extern "C" {
+
+int alice_codec_segment_by_motion(const uint8_t* current, uint64_t current_len, const uint8_t* reference, uint64_t reference_len,
+                                  uint32_t width, uint32_t height, uint8_t motion_threshold, uint32_t dilate_radius,
+                                  uint32_t erode_radius, uint8_t* mask, uint64_t mask_len, uint32_t bbox[4],
+                                  uint32_t* foreground_count) {
+    clear_error();
+    if (!bbox || !foreground_count || (!current && current_len) || (!reference && reference_len) || (!mask && mask_len))
+        return fail(kNullArgument, "null argument");
+    uint64_t total = 0;
+    TRY(segment_total(width, height, &total));
+    if (current_len < total)   // src/segment.rs:180-185
+        return fail(kInvalidBufferSize, "buffer size mismatch: expected " + std::to_string(total) + ", got " + std::to_string(current_len));
+    if (reference_len < total)   // :186-191
+        return fail(kInvalidBufferSize, "buffer size mismatch: expected " + std::to_string(total) + ", got " + std::to_string(reference_len));
+    if (mask_len < total) return fail(kInvalidBufferSize, "mask buffer too small: need " + std::to_string(total));
+    if (!total) return empty_segment(bbox, foreground_count);
+    SegSource src{};
+    src.kind = kSegMotion; src.motion_threshold = motion_threshold;
+    return segment_host(src, current, total, reference, total, width, height, dilate_radius, erode_radius, mask, bbox, foreground_count);
+}
+
+int alice_codec_segment_by_chroma(const int16_t* cg, uint64_t cg_len, uint32_t width, uint32_t height, int16_t green_threshold,
+                                  uint8_t* mask, uint64_t mask_len, uint32_t bbox[4], uint32_t* foreground_count) {
+    clear_error();
+    if (!bbox || !foreground_count || (!cg && cg_len) || (!mask && mask_len)) return fail(kNullArgument, "null argument");
+    uint64_t total = 0;
+    TRY(segment_total(width, height, &total));
+    // the reference indexes past a short cg and panics (src/segment.rs:245-253)
+    if (cg_len < total)
+        return fail(kInvalidBufferSize, "buffer size mismatch: expected " + std::to_string(total) + ", got " + std::to_string(cg_len));
+    if (mask_len < total) return fail(kInvalidBufferSize, "mask buffer too small: need " + std::to_string(total));
+    if (!total) return empty_segment(bbox, foreground_count);
+    SegSource src{};
+    src.kind = kSegCg; src.green_threshold = green_threshold;
+    return segment_host(src, cg, total * sizeof(int16_t), nullptr, 0, width, height, 2, 1, mask, bbox, foreground_count);   // :253-254
+}
+
+uint64_t alice_codec_rle_bound(uint64_t n) { return n > UINT64_MAX / 3 ? UINT64_MAX : 3 * n; }
+
+uint8_t* alice_codec_rle_encode_mask(const uint8_t* mask, uint64_t n, uint64_t* out_len) {
+    clear_error();
+    if (!out_len || (!mask && n)) { fail(kNullArgument, "null argument"); return nullptr; }
+    if (n > UINT64_MAX / 3) { fail(kDimensionOverflow, "mask too long"); return nullptr; }
+    if (!n) {   // an empty mask encodes to nothing (src/segment.rs:132-134)
+        uint8_t* p = (uint8_t*)malloc(1);
+        if (!p) { fail(kOutOfMemory, "out of host memory"); return nullptr; }
+        *out_len = 0;
+        return p;
+    }
+    if (ensure_device() != kOk) return nullptr;
+    hipStream_t st;
+    if (get_stream(&st) != kOk) return nullptr;
+    DevBuf dm, dout;
+    uint64_t len = 0;
+    int rc = dm.alloc(n);
+    if (rc == kOk) rc = dout.alloc(3 * n);
+    if (rc == kOk && hipMemcpyAsync(dm.p, mask, n, hipMemcpyHostToDevice, st) != hipSuccess) rc = fail(kDeviceError, "copy failed");
+    if (rc == kOk) rc = rle_on_device(dm.as<uint8_t>(), n, dout.as<uint8_t>(), &len, st);
+    if (rc != kOk) return nullptr;
+    uint8_t* p = (uint8_t*)malloc(len ? len : 1);
+    if (!p) { fail(kOutOfMemory, "out of host memory"); return nullptr; }
+    if (hipMemcpyAsync(p, dout.p, len, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+        free(p);
+        fail(kDeviceError, "copy failed");
+        return nullptr;
+    }
+    *out_len = len;
+    return p;
+}
+
+int alice_codec_extract_person_rgb(const uint8_t* mask, uint64_t mask_len, uint32_t width, const uint32_t bbox[4],
+                                   const uint8_t* rgb, uint64_t rgb_len, uint8_t* out, uint64_t out_cap, uint64_t* out_len) {
+    clear_error();
+    if (!bbox || !out_len || (!mask && mask_len) || (!rgb && rgb_len) || (!out && out_cap)) return fail(kNullArgument, "null argument");
+    TRY(bbox_indices_fit(width, bbox));
+    const uint64_t items = (uint64_t)bbox[2] * bbox[3];
+    if (out_cap < 3 * (unsigned __int128)items)
+        return fail(kInvalidBufferSize, "output buffer too small: need 3 * bbox w * h = " + std::to_string(3 * (unsigned __int128)items > UINT64_MAX ? UINT64_MAX : 3 * items));
+    *out_len = 0;
+    if (!items || !mask_len || rgb_len < 3) return kOk;   // nothing passes the guards of src/segment.rs:114-116
+    TRY(ensure_device());
+    hipStream_t st;
+    TRY(get_stream(&st));
+    DevBuf dm, dr, dout;
+    TRY(dm.alloc(mask_len));
+    TRY(dr.alloc(rgb_len));
+    TRY(dout.alloc(3 * items));
+    HIP_TRY(hipMemcpyAsync(dm.p, mask, mask_len, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dr.p, rgb, rgb_len, hipMemcpyHostToDevice, st));
+    uint64_t len = 0;
+    TRY(extract_on_device(dm.as<uint8_t>(), mask_len, dr.as<uint8_t>(), rgb_len, width, bbox, dout.as<uint8_t>(), &len, st));
+    HIP_TRY(hipMemcpyAsync(out, dout.p, len, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *out_len = len;
+    return kOk;
+}
+
+int alice_codec_dev_segment_motion(const void* d_current, const void* d_reference, uint64_t reference_stride, uint32_t width,
+                                   uint32_t height, uint32_t n_frames, uint8_t motion_threshold, uint32_t dilate_radius,
+                                   uint32_t erode_radius, void* d_mask, void* d_stats, void* hip_stream) {
+    clear_error();
+    if (!d_current || !d_reference || !d_stats) return fail(kNullArgument, "null argument");
+    uint64_t total = 0;
+    TRY(segment_total(width, height, &total));
+    if (!n_frames) return kOk;
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);   // temporaries drain the caller's stream before they return to the pool
+    if (!total) {
+        HIP_TRY(hipMemsetAsync(d_stats, 0, (size_t)n_frames * 5 * sizeof(uint32_t), st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return kOk;
+    }
+    SegSource src{};
+    src.kind = kSegMotion; src.cur = (const uint8_t*)d_current; src.ref = (const uint8_t*)d_reference;
+    src.ref_stride = reference_stride; src.motion_threshold = motion_threshold;
+    return segment_on_device(src, width, height, n_frames, dilate_radius, erode_radius, (uint8_t*)d_mask, (uint32_t*)d_stats, st);
+}
+
+int alice_codec_dev_segment_chroma_rgb(const void* d_rgb, uint32_t width, uint32_t height, uint32_t n_frames, int16_t green_threshold,
+                                       void* d_mask, void* d_stats, void* hip_stream) {
+    clear_error();
+    if (!d_rgb || !d_stats) return fail(kNullArgument, "null argument");
+    uint64_t total = 0;
+    TRY(segment_total(width, height, &total));
+    if (!n_frames) return kOk;
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);
+    if (!total) {
+        HIP_TRY(hipMemsetAsync(d_stats, 0, (size_t)n_frames * 5 * sizeof(uint32_t), st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return kOk;
+    }
+    SegSource src{};
+    src.kind = kSegRgb; src.rgb = (const uint8_t*)d_rgb; src.green_threshold = green_threshold;
+    return segment_on_device(src, width, height, n_frames, 2, 1, (uint8_t*)d_mask, (uint32_t*)d_stats, st);
+}
+
+int alice_codec_dev_rle_encode_mask(const void* d_mask, uint64_t n, void* d_out, uint64_t cap, uint64_t* out_len, void* hip_stream) {
+    clear_error();
+    if (!out_len || ((!d_mask || !d_out) && n)) return fail(kNullArgument, "null argument");
+    if (cap < alice_codec_rle_bound(n)) return fail(kInvalidBufferSize, "output capacity below alice_codec_rle_bound(n)");
+    *out_len = 0;
+    if (!n) return kOk;
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);
+    return rle_on_device((const uint8_t*)d_mask, n, (uint8_t*)d_out, out_len, st);
+}
+
+int alice_codec_dev_extract_person_rgb(const void* d_mask, uint32_t width, uint32_t height, const uint32_t bbox[4], const void* d_rgb,
+                                       void* d_out, uint64_t cap, uint64_t* out_len, void* hip_stream) {
+    clear_error();
+    if (!bbox || !out_len || !d_mask || !d_rgb) return fail(kNullArgument, "null argument");
+    uint64_t total = 0;
+    TRY(segment_total(width, height, &total));
+    TRY(bbox_indices_fit(width, bbox));
+    const uint64_t items = (uint64_t)bbox[2] * bbox[3];
+    if (cap < 3 * (unsigned __int128)items) return fail(kInvalidBufferSize, "output capacity below 3 * bbox w * h");
+    if (!d_out && items) return fail(kNullArgument, "null argument");
+    *out_len = 0;
+    if (!items || !total) return kOk;
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);
+    return extract_on_device((const uint8_t*)d_mask, total, (const uint8_t*)d_rgb, 3 * total, width, bbox, (uint8_t*)d_out, out_len, st);
+}
+
+}  // extern "C"

@@ -171,4 +171,32 @@ void launch_write_headers(uint8_t* d_alc, uint64_t alc_stride, const ChunkDims& 
                           const uint32_t* d_hist, const RansResult* d_results, unsigned long long* d_sizes,
                           int n_chunks, hipStream_t st);
 
+// ---- segment.hip: person segmentation (reference src/segment.rs) ----
+enum SegSourceKind : int { kSegMotion = 0, kSegCg = 1, kSegRgb = 2, kSegPacked = 3 };
+// the first stage's pixels: frames [f][h][w] back to back
+struct SegSource {
+    int kind;                 // kSegMotion, kSegCg (planar i16 Cg) or kSegRgb (interleaved RGB, Cg computed on load)
+    const uint8_t* cur;       // motion: current frames
+    const uint8_t* ref;       // motion: reference frame(s); frame f at ref + f * ref_stride
+    uint64_t ref_stride;
+    uint8_t motion_threshold;
+    const int16_t* cg;
+    const uint8_t* rgb;
+    int16_t green_threshold;
+};
+// device scratch launch_segment needs (0 when both radii are 0)
+uint64_t segment_scratch_bytes(uint32_t w, uint32_t h, uint32_t n_frames, uint32_t dilate_radius, uint32_t erode_radius);
+// threshold, dilate, erode, then d_mask (u8, may be null) and d_stats (n_frames x {x, y, w, h, count}); w*h > 0
+void launch_segment(const SegSource& src, uint32_t w, uint32_t h, uint32_t n_frames, uint32_t dilate_radius,
+                    uint32_t erode_radius, void* d_scratch, uint8_t* d_mask, uint32_t* d_stats, hipStream_t st);
+// rle_encode_mask of n > 0 bytes into d_out (>= 3n bytes); *d_pieces = number of 3-byte triples written
+uint64_t rle_scratch_bytes(uint64_t n);
+void launch_rle(const uint8_t* d_mask, uint64_t n, uint8_t* d_out, void* d_scratch, unsigned long long* d_pieces, hipStream_t st);
+// extract_person_rgb over bbox = {x, y, w, h} with w*h > 0 into d_out (>= 3*w*h bytes); *d_count = pixels written.
+// Every mask index (y+h-1)*width + x+w-1 must fit u32 (checked by the caller).
+uint64_t compact_scratch_bytes(uint64_t n_items);
+void launch_extract_person(const uint8_t* d_mask, uint64_t mask_len, const uint8_t* d_rgb, uint64_t rgb_len, uint32_t width,
+                           const uint32_t bbox[4], uint8_t* d_out, void* d_scratch, unsigned long long* d_count,
+                           hipStream_t st);
+
 }  // namespace alice

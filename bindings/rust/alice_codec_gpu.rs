@@ -459,3 +459,118 @@ pub fn decode_many(chunks: &[EncodedChunk], devices: &[i32]) -> Result<Vec<u8>, 
     check(rc, 0, 0)?;
     Ok(out)
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// person segmentation: src/segment.rs (GPU; crop / paste are byte copies on the host)
+// ---------------------------------------------------------------------------------------------------------------
+
+#[link(name = "alice_codec")]
+extern "C" {
+    fn alice_codec_segment_by_motion(current: *const u8, current_len: u64, reference: *const u8, reference_len: u64, width: u32,
+                                     height: u32, motion_threshold: u8, dilate_radius: u32, erode_radius: u32, mask: *mut u8,
+                                     mask_len: u64, bbox: *mut u32, foreground_count: *mut u32) -> c_int;
+    fn alice_codec_segment_by_chroma(cg: *const i16, cg_len: u64, width: u32, height: u32, green_threshold: i16, mask: *mut u8,
+                                     mask_len: u64, bbox: *mut u32, foreground_count: *mut u32) -> c_int;
+    fn alice_codec_rle_encode_mask(mask: *const u8, n: u64, out_len: *mut u64) -> *mut u8;
+    fn alice_codec_extract_person_rgb(mask: *const u8, mask_len: u64, width: u32, bbox: *const u32, rgb: *const u8, rgb_len: u64,
+                                      out: *mut u8, out_cap: u64, out_len: *mut u64) -> c_int;
+}
+
+/// src/segment.rs:42-63 (`min_region_size` is carried and, as in the reference, unused)
+#[derive(Debug, Clone)]
+pub struct SegmentConfig { pub motion_threshold: u8, pub min_region_size: u32, pub dilate_radius: u32, pub erode_radius: u32 }
+impl Default for SegmentConfig {
+    fn default() -> Self { Self { motion_threshold: 25, min_region_size: 100, dilate_radius: 2, erode_radius: 1 } }
+}
+
+/// src/segment.rs:78-89
+#[derive(Debug, Clone)]
+pub struct SegmentResult { pub mask: Vec<u8>, pub bbox: [u32; 4], pub foreground_count: u32, pub width: u32, pub height: u32 }
+
+impl SegmentResult {
+    /// src/segment.rs:94-101
+    pub fn coverage(&self) -> f32 {
+        let total = self.width.wrapping_mul(self.height);
+        if total == 0 { return 0.0; }
+        let inv_total = 1.0 / total as f32;
+        self.foreground_count as f32 * inv_total
+    }
+    /// src/segment.rs:107-125 (on the GPU)
+    pub fn extract_person_rgb(&self, frame_rgb: &[u8]) -> Result<Vec<u8>, CodecError> {
+        let [_, _, bw, bh] = self.bbox;
+        let mut out = vec![0u8; 3 * bw as usize * bh as usize];
+        let mut n = 0u64;
+        let rc = unsafe {
+            alice_codec_extract_person_rgb(self.mask.as_ptr(), self.mask.len() as u64, self.width, self.bbox.as_ptr(), frame_rgb.as_ptr(),
+                                           frame_rgb.len() as u64, out.as_mut_ptr(), out.len() as u64, &mut n)
+        };
+        check(rc, 0, 0)?;
+        out.truncate(n as usize);
+        Ok(out)
+    }
+    /// src/segment.rs:131-154 (on the GPU)
+    pub fn rle_encode_mask(&self) -> Result<Vec<u8>, CodecError> {
+        let mut n = 0u64;
+        unsafe {
+            let p = alice_codec_rle_encode_mask(self.mask.as_ptr(), self.mask.len() as u64, &mut n);
+            if p.is_null() { Err(last_error(0, 0, 0, 0, 0)) } else { Ok(take(p, n)) }
+        }
+    }
+}
+
+/// src/segment.rs:172-230.  width * height past u32 is `DimensionOverflow` (the reference wraps or panics).
+pub fn segment_by_motion(current: &[u8], reference: &[u8], width: u32, height: u32, config: &SegmentConfig)
+    -> Result<SegmentResult, CodecError> {
+    let total = (width as u64 * height as u64).min(u32::MAX as u64 + 1) as usize;
+    let mut r = SegmentResult { mask: vec![0u8; if total > u32::MAX as usize { 0 } else { total }], bbox: [0; 4], foreground_count: 0, width, height };
+    let rc = unsafe {
+        alice_codec_segment_by_motion(current.as_ptr(), current.len() as u64, reference.as_ptr(), reference.len() as u64, width, height,
+                                      config.motion_threshold, config.dilate_radius, config.erode_radius, r.mask.as_mut_ptr(),
+                                      r.mask.len() as u64, r.bbox.as_mut_ptr(), &mut r.foreground_count)
+    };
+    check(rc, total, current.len().min(reference.len()))?;
+    Ok(r)
+}
+
+/// src/segment.rs:234-265.  Returns a `Result` where the reference panics on a short `cg`.
+pub fn segment_by_chroma(_y: &[i16], _co: &[i16], cg: &[i16], width: u32, height: u32, green_threshold: i16)
+    -> Result<SegmentResult, CodecError> {
+    let total = (width as u64 * height as u64).min(u32::MAX as u64 + 1) as usize;
+    let mut r = SegmentResult { mask: vec![0u8; if total > u32::MAX as usize { 0 } else { total }], bbox: [0; 4], foreground_count: 0, width, height };
+    let rc = unsafe {
+        alice_codec_segment_by_chroma(cg.as_ptr(), cg.len() as u64, width, height, green_threshold, r.mask.as_mut_ptr(),
+                                      r.mask.len() as u64, r.bbox.as_mut_ptr(), &mut r.foreground_count)
+    };
+    check(rc, total, cg.len())?;
+    Ok(r)
+}
+
+/// u32 `row * frame_width + bx` of crop / paste (src/segment.rs:273-274, :288-289); overflow is `DimensionOverflow`
+fn bbox_row_start(row: u32, frame_width: u32, bx: u32) -> Result<usize, CodecError> {
+    row.checked_mul(frame_width).and_then(|v| v.checked_add(bx)).map(|v| v as usize).ok_or(CodecError::DimensionOverflow)
+}
+
+/// src/segment.rs:269-281 (host): a row whose end falls past the frame is skipped
+pub fn crop_to_bbox(frame: &[u8], frame_width: u32, bbox: &[u32; 4]) -> Result<Vec<u8>, CodecError> {
+    let [bx, by, bw, bh] = *bbox;
+    let mut cropped = Vec::new();
+    for row in by..by.checked_add(bh).ok_or(CodecError::DimensionOverflow)? {
+        let start = bbox_row_start(row, frame_width, bx)?;
+        let end = start + bw as usize;
+        if end <= frame.len() { cropped.extend_from_slice(&frame[start..end]); }
+    }
+    Ok(cropped)
+}
+
+/// src/segment.rs:284-298 (host)
+pub fn paste_from_bbox(frame: &mut [u8], frame_width: u32, person_data: &[u8], bbox: &[u32; 4]) -> Result<(), CodecError> {
+    let [bx, by, bw, bh] = *bbox;
+    let mut src = 0usize;
+    for row in by..by.checked_add(bh).ok_or(CodecError::DimensionOverflow)? {
+        let d0 = bbox_row_start(row, frame_width, bx)?;
+        let d1 = d0 + bw as usize;
+        if d1 <= frame.len() && src + bw as usize <= person_data.len() { frame[d0..d1].copy_from_slice(&person_data[src..src + bw as usize]); }
+        src += bw as usize;
+    }
+    Ok(())
+}

@@ -288,6 +288,48 @@ int alice_codec_dev_rans_encode(const void *d_symbols, uint64_t n, const uint32_
 int alice_codec_dev_rans_decode(const void *d_stream, uint64_t len, const uint32_t hist[256], void *d_symbols,
                                 uint64_t n, void *hip_stream);
 
+/* ---- segmentation ----
+ * Person segmentation of the reference (src/segment.rs), bit-exact: a motion mask (|current - reference| > threshold,
+ * :172-230) or a chroma-key mask (cg <= green_threshold, :234-265), then a box dilation of dilate_radius and a box erosion
+ * of erode_radius (a radius of 0 skips its step; pixels outside the frame count as background for the dilation and as
+ * foreground for the erosion, :313-390), then the bounding box [x, y, w, h] and the foreground count (:400-441; an empty
+ * mask gives [0,0,0,0] and 0).  Radii are any u32.  Where the reference panics or wraps these return an error: a cg
+ * shorter than width*height is ALICE_ERR_INVALID_BUFFER_SIZE, width*height past u32 is ALICE_ERR_DIMENSION_OVERFLOW. */
+/* segment_by_motion on host buffers; mask_len >= width*height; a short current, then a short reference, is
+ * ALICE_ERR_INVALID_BUFFER_SIZE (:180-191) */
+int alice_codec_segment_by_motion(const uint8_t *current, uint64_t current_len, const uint8_t *reference, uint64_t reference_len,
+                                  uint32_t width, uint32_t height, uint8_t motion_threshold, uint32_t dilate_radius,
+                                  uint32_t erode_radius, uint8_t *mask, uint64_t mask_len, uint32_t bbox[4],
+                                  uint32_t *foreground_count);
+/* segment_by_chroma (dilate 2, erode 1); the reference's y and co planes are accepted and ignored there, so only cg is taken */
+int alice_codec_segment_by_chroma(const int16_t *cg, uint64_t cg_len, uint32_t width, uint32_t height, int16_t green_threshold,
+                                  uint8_t *mask, uint64_t mask_len, uint32_t bbox[4], uint32_t *foreground_count);
+/* SegmentResult::rle_encode_mask (:131-154): runs of (mask[i] & 1) as [len u16 LE, value u8], a run cut after 65535
+ * elements.  Buffer freed with alice_codec_data_free64; an empty mask gives *out_len = 0. */
+uint8_t *alice_codec_rle_encode_mask(const uint8_t *mask, uint64_t n, uint64_t *out_len);
+/* SegmentResult::extract_person_rgb (:107-125): RGB of the bbox pixels whose mask byte is exactly 1, row-major, with the
+ * reference's mask_idx < mask_len and rgb_idx + 2 < rgb_len guards.  out_cap >= 3 * bbox[2] * bbox[3]; every index
+ * (y+h-1)*width + x+w-1 must fit u32 (ALICE_ERR_DIMENSION_OVERFLOW otherwise). */
+int alice_codec_extract_person_rgb(const uint8_t *mask, uint64_t mask_len, uint32_t width, const uint32_t bbox[4],
+                                   const uint8_t *rgb, uint64_t rgb_len, uint8_t *out, uint64_t out_cap, uint64_t *out_len);
+/* Device-resident, n_frames frames [f][height][width] in one launch sequence.  Frame f's reference is at
+ * d_reference + f * reference_stride (0: one shared background, width*height: one per frame).  d_stats receives
+ * n_frames x {x, y, w, h, count} u32; d_mask (n_frames * width*height u8) may be NULL: then only the stats are made.
+ * Finished on return, like PART 3. */
+int alice_codec_dev_segment_motion(const void *d_current, const void *d_reference, uint64_t reference_stride, uint32_t width,
+                                   uint32_t height, uint32_t n_frames, uint8_t motion_threshold, uint32_t dilate_radius,
+                                   uint32_t erode_radius, void *d_mask, void *d_stats, void *hip_stream);
+/* segment_by_chroma of interleaved RGB frames: Cg is computed on load as alice_codec_rgb_to_ycocg_r does */
+int alice_codec_dev_segment_chroma_rgb(const void *d_rgb, uint32_t width, uint32_t height, uint32_t n_frames,
+                                       int16_t green_threshold, void *d_mask, void *d_stats, void *hip_stream);
+/* the most bytes rle_encode_mask writes for n mask bytes: 3n (the capacity alice_codec_dev_rle_encode_mask requires) */
+uint64_t alice_codec_rle_bound(uint64_t n);
+int alice_codec_dev_rle_encode_mask(const void *d_mask, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len,
+                                    void *hip_stream);
+/* extract_person_rgb of one device frame (mask width*height bytes, rgb 3*width*height); cap >= 3 * bbox[2] * bbox[3] */
+int alice_codec_dev_extract_person_rgb(const void *d_mask, uint32_t width, uint32_t height, const uint32_t bbox[4],
+                                       const void *d_rgb, void *d_out, uint64_t cap, uint64_t *out_len, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

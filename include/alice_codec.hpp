@@ -13,6 +13,7 @@
 // Everything executes on the GPU through libalice_codec.so; there is no CPU fallback.
 #pragma once
 
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <stdexcept>
@@ -388,6 +389,108 @@ inline double ms_ssim(const std::vector<uint8_t>& a, const std::vector<uint8_t>&
     const double v = alice_codec_ms_ssim(a.empty() ? &empty : a.data(), a.size(), b.empty() ? &empty : b.data(), b.size(), width, height);
     if (v == -1.0 && alice_codec_last_error() != 0) detail::raise();
     return v;
+}
+
+// ---- person segmentation, src/segment.rs (GPU; crop / paste are host byte copies) ----
+struct SegmentConfig {  // :42-63 (min_region_size is carried and, as in the reference, unused)
+    uint8_t motion_threshold = 25;
+    uint32_t min_region_size = 100;
+    uint32_t dilate_radius = 2;
+    uint32_t erode_radius = 1;
+};
+
+inline std::vector<uint8_t> rle_encode_mask(const std::vector<uint8_t>& mask) {  // :131-154
+    static const uint8_t empty = 0;
+    uint64_t n = 0;
+    uint8_t* p = alice_codec_rle_encode_mask(mask.empty() ? &empty : mask.data(), mask.size(), &n);
+    if (!p) detail::raise();
+    return detail::take(p, n);
+}
+
+struct SegmentResult {  // :78-154
+    std::vector<uint8_t> mask;
+    uint32_t bbox[4] = {0, 0, 0, 0};
+    uint32_t foreground_count = 0;
+    uint32_t width = 0, height = 0;
+    float coverage() const {  // :94-101, f32 arithmetic
+        const uint64_t total = (uint64_t)width * height;
+        if (total > 0xFFFFFFFFull) throw CodecError(ALICE_ERR_DIMENSION_OVERFLOW, "width * height does not fit u32");
+        if (total == 0) return 0.0f;
+        const float inv = 1.0f / (float)total;
+        return (float)foreground_count * inv;
+    }
+    std::vector<uint8_t> extract_person_rgb(const std::vector<uint8_t>& frame_rgb) const {  // :107-125
+        static const uint8_t empty = 0;
+        std::vector<uint8_t> out((size_t)3 * bbox[2] * bbox[3]);
+        uint64_t n = 0;
+        detail::check(alice_codec_extract_person_rgb(mask.empty() ? &empty : mask.data(), mask.size(), width, bbox,
+                                                     frame_rgb.empty() ? &empty : frame_rgb.data(), frame_rgb.size(),
+                                                     out.empty() ? nullptr : out.data(), out.size(), &n));
+        out.resize(n);
+        return out;
+    }
+    std::vector<uint8_t> rle_encode_mask() const { return alice_codec::rle_encode_mask(mask); }
+};
+
+inline SegmentResult segment_by_motion(const std::vector<uint8_t>& current, const std::vector<uint8_t>& reference, uint32_t width,
+                                       uint32_t height, const SegmentConfig& config = SegmentConfig()) {  // :172-230
+    static const uint8_t empty = 0;
+    SegmentResult r;
+    r.width = width; r.height = height;
+    const uint64_t total = (uint64_t)width * height;
+    if (total <= 0xFFFFFFFFull) r.mask.resize(total);
+    detail::check(alice_codec_segment_by_motion(current.empty() ? &empty : current.data(), current.size(),
+                                                reference.empty() ? &empty : reference.data(), reference.size(), width, height,
+                                                config.motion_threshold, config.dilate_radius, config.erode_radius,
+                                                r.mask.empty() ? nullptr : r.mask.data(), r.mask.size(), r.bbox, &r.foreground_count));
+    return r;
+}
+
+// :234-265; y and co are accepted and ignored, as there
+inline SegmentResult segment_by_chroma(const std::vector<int16_t>& /*y*/, const std::vector<int16_t>& /*co*/, const std::vector<int16_t>& cg,
+                                       uint32_t width, uint32_t height, int16_t green_threshold) {
+    static const int16_t empty = 0;
+    SegmentResult r;
+    r.width = width; r.height = height;
+    const uint64_t total = (uint64_t)width * height;
+    if (total <= 0xFFFFFFFFull) r.mask.resize(total);
+    detail::check(alice_codec_segment_by_chroma(cg.empty() ? &empty : cg.data(), cg.size(), width, height, green_threshold,
+                                                r.mask.empty() ? nullptr : r.mask.data(), r.mask.size(), r.bbox, &r.foreground_count));
+    return r;
+}
+
+namespace detail {
+// row starts of crop_to_bbox / paste_from_bbox (:273-274, :288-289): u32 arithmetic, overflow is DimensionOverflow
+inline uint64_t bbox_row_start(uint32_t frame_width, const uint32_t bbox[4], uint64_t row) {
+    const uint64_t s = row * frame_width + bbox[0];
+    if (s > 0xFFFFFFFFull) throw CodecError(ALICE_ERR_DIMENSION_OVERFLOW, "row * frame_width + x does not fit u32");
+    return s;
+}
+inline void bbox_rows_fit(const uint32_t bbox[4]) {
+    if ((uint64_t)bbox[1] + bbox[3] > 0xFFFFFFFFull) throw CodecError(ALICE_ERR_DIMENSION_OVERFLOW, "bbox y + h does not fit u32");
+}
+}  // namespace detail
+
+inline std::vector<uint8_t> crop_to_bbox(const std::vector<uint8_t>& frame, uint32_t frame_width, const uint32_t bbox[4]) {  // :269-281
+    detail::bbox_rows_fit(bbox);
+    std::vector<uint8_t> out;
+    for (uint64_t row = bbox[1]; row < (uint64_t)bbox[1] + bbox[3]; ++row) {
+        const uint64_t start = detail::bbox_row_start(frame_width, bbox, row), end = start + bbox[2];
+        if (end <= frame.size()) out.insert(out.end(), frame.begin() + start, frame.begin() + end);   // a partial row is skipped
+    }
+    return out;
+}
+
+inline void paste_from_bbox(std::vector<uint8_t>& frame, uint32_t frame_width, const std::vector<uint8_t>& person,
+                            const uint32_t bbox[4]) {  // :284-298
+    detail::bbox_rows_fit(bbox);
+    uint64_t src = 0;
+    for (uint64_t row = bbox[1]; row < (uint64_t)bbox[1] + bbox[3]; ++row) {
+        const uint64_t d0 = detail::bbox_row_start(frame_width, bbox, row), d1 = d0 + bbox[2];
+        if (d1 <= frame.size() && src + bbox[2] <= person.size())
+            std::copy(person.begin() + src, person.begin() + src + bbox[2], frame.begin() + d0);
+        src += bbox[2];
+    }
 }
 
 }  // namespace alice_codec
