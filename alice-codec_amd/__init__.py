@@ -174,6 +174,8 @@ def load_library() -> C.CDLL:
         "alice_codec_batch_alc_stride": (C.c_uint64, [vp]),
         "alice_codec_batch_pack_alc": (C.c_int, [vp, _u64p, vp, C.c_uint64, vp]),
         "alice_codec_batch_decode": (C.c_int, [vp, vp, C.c_uint64, vp, vp]),
+        "alice_codec_batch_encode_regions": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, _u32p, vp]),
+        "alice_codec_batch_decode_regions": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint32, _u32p, vp]),
         "alice_codec_batch_decode_finish": (C.c_int, [vp]),
         "alice_codec_batch_stage_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
         "alice_codec_batch_symbols_ptr": (vp, [vp]),
@@ -973,6 +975,27 @@ class Batch:
     def decode_finish(self) -> None:
         _check(load_library().alice_codec_batch_decode_finish(self._h))
 
+    def _origins(self, origins) -> np.ndarray:
+        o = [[_u32_arg(v, "origin") for v in xy] for xy in origins]
+        if len(o) != self.n_chunks or any(len(xy) != 2 for xy in o):
+            raise CodecError(1, f"origins: expected {self.n_chunks} (x, y) pairs")
+        return np.array(o, np.uint32).reshape(-1)
+
+    def encode_regions(self, d_frames_ptr: int, frame_width: int, frame_height: int, origins, stream: int = 0) -> None:
+        """chunk i = frames [i*frames, (i+1)*frames) of d_frames (frame_width x frame_height RGB), cropped to the batch's
+        width x height at origins[i] = (x, y) in pixels; the .alc equals FrameEncoder.encode of that crop."""
+        o = self._origins(origins)
+        _check(load_library().alice_codec_batch_encode_regions(self._h, d_frames_ptr, _u32_arg(frame_width, "frame_width"),
+                                                               _u32_arg(frame_height, "frame_height"), _p(o, _u32p), stream))
+
+    def decode_regions(self, d_alc_ptr: int, alc_stride: int, d_frames_out_ptr: int, frame_width: int, frame_height: int,
+                       origins, stream: int = 0) -> None:
+        """decodes chunk i into its rectangle of d_frames_out; bytes outside the rectangles are not written"""
+        o = self._origins(origins)
+        _check(load_library().alice_codec_batch_decode_regions(self._h, d_alc_ptr, alc_stride, d_frames_out_ptr,
+                                                               _u32_arg(frame_width, "frame_width"),
+                                                               _u32_arg(frame_height, "frame_height"), _p(o, _u32p), stream))
+
     def stage_ms(self) -> dict:
         out = (C.c_float * 6)()
         load_library().alice_codec_batch_stage_ms(self._h, out)
@@ -1240,3 +1263,178 @@ def extract_person_rgb_device(d_mask: int, width: int, height: int, bbox, d_rgb:
     _check(load_library().alice_codec_dev_extract_person_rgb(d_mask, width, height, _p(b, _u32p), d_rgb, d_out, cap, C.byref(out),
                                                              stream))
     return out.value
+
+
+# ---------------------------------------------------------------------------------------------
+# hybrid streaming (reference src/segment.rs:1-8, README "Person Segmentation"): only the person's box is coded, and the
+# decoder pastes it back over a background.  Segmentation, crop, encode, decode and paste all run in HBM: the region calls
+# of Batch read and write the boxes of the full frames in place, and only the 20 B/frame stats come to the host.
+# ---------------------------------------------------------------------------------------------
+
+def _dptr(x) -> int:
+    """a device pointer: an int, or anything with data_ptr() (a torch tensor)"""
+    return int(x) if isinstance(x, int) else int(x.data_ptr())
+
+
+def _positive_u32(v, what: str) -> int:
+    v = _u32_arg(v, what)
+    if v == 0:
+        raise CodecError(2, f"{what} must be positive")
+    return v
+
+
+def person_chunk_boxes(stats, width: int, height: int, frames: int) -> list:
+    """The box policy of encode_person_chunks: [x, y, w, h] in pixels per chunk, from the per-frame segmentation stats
+    (n_chunks * frames rows of {x, y, w, h, count}, pixel units).  A chunk whose frames have no foreground gets
+    [0, 0, 0, 0].  All others share one w x h, and each box contains its chunk's union box and lies inside the frame.
+    Where width % 4 == 0 every x is a multiple of 4 (the tile kernels' dword path) and so is the common width, which keeps
+    a box pushed against the right edge on a multiple of 4: the common width is the widest span from a union box's
+    4-aligned left edge to its right edge, rounded up to 4 (at most 6 more than the widest union box), clamped to the
+    frame width."""
+    W, H, f = _positive_u32(width, "width"), _positive_u32(height, "height"), _positive_u32(frames, "frames")
+    st = np.asarray(stats, dtype=np.int64)
+    if st.ndim != 2 or st.shape[1] != 5 or st.shape[0] % f:
+        raise CodecError(1, f"stats: expected n_chunks * {f} rows of {{x, y, w, h, count}}, got shape {st.shape}")
+    unions = []
+    for c in range(st.shape[0] // f):
+        s = st[c * f:(c + 1) * f]
+        s = s[s[:, 4] > 0]
+        if not len(s):
+            unions.append(None)
+            continue
+        u = (int(s[:, 0].min()), int(s[:, 1].min()), int((s[:, 0] + s[:, 2]).max()), int((s[:, 1] + s[:, 3]).max()))
+        if u[0] < 0 or u[1] < 0 or u[2] > W or u[3] > H:
+            raise CodecError(2, f"chunk {c}: foreground box {u} does not lie inside the {W}x{H} frame")
+        unions.append(u)
+    fg = [u for u in unions if u is not None]
+    if not fg:
+        return [[0, 0, 0, 0] for _ in unions]
+    align = W % 4 == 0
+    if align:
+        cw = min(W, (max(x1 - (x0 & ~3) for x0, _, x1, _ in fg) + 3) & ~3)
+    else:
+        cw = max(x1 - x0 for x0, _, x1, _ in fg)
+    ch = max(y1 - y0 for _, y0, _, y1 in fg)
+    boxes = []
+    for u in unions:
+        if u is None:
+            boxes.append([0, 0, 0, 0])
+            continue
+        x = min(u[0], W - cw)
+        boxes.append([x & ~3 if align else x, min(u[1], H - ch), cw, ch])
+    return boxes
+
+
+def _runs(boxes) -> list:
+    """maximal runs [start, end) of consecutive chunks with the same non-empty box size: one Batch call each"""
+    out, i = [], 0
+    while i < len(boxes):
+        if boxes[i][2] * boxes[i][3] == 0:
+            i += 1
+            continue
+        j = i + 1
+        while j < len(boxes) and boxes[j][2:] == boxes[i][2:]:
+            j += 1
+        out.append((i, j))
+        i = j
+    return out
+
+
+def encode_person_chunks(d_frames, d_background, width: int, height: int, frames: int, n_chunks: int, quality: int,
+                         wavelet: WaveletType = WaveletType.Cdf53, config: SegmentConfig | None = None,
+                         green_threshold: int | None = None) -> list:
+    """Hybrid encode of n_chunks chunks of `frames` frames each (d_frames: n_chunks * frames frames of width x height
+    interleaved RGB in HBM) -> list of (bbox [x, y, w, h] in pixels, .alc bytes), one per chunk.
+
+    1. Segmentation of all frames in one call.  Motion (default): against the one background frame d_background (RGB of
+       the same shape), on the interleaved bytes as a (3 * width)-sample row, so a pixel is foreground when any of its
+       channels moved; config's radii then count bytes along a row and rows down a column.  green_threshold given:
+       chroma keying of the RGB frames instead (segment_chroma_rgb_device), d_background unused.
+    2. Per chunk the union of its frames' boxes (only the stats come to the host), 3. person_chunk_boxes, 4. Batch region
+       encodes of the chunks with foreground (one per run of consecutive such chunks).  A chunk without foreground gets
+       bbox [0, 0, 0, 0] and the reference's empty chunk, FrameEncoder.encode(b"", 0, 0, frames)."""
+    W, H, f = _positive_u32(width, "width"), _positive_u32(height, "height"), _positive_u32(frames, "frames")
+    n = _positive_u32(n_chunks, "n_chunks")
+    if not 0 <= int(quality) <= 255:
+        raise CodecError(5, f"quality must fit a u8, got {quality}")
+    wavelet = WaveletType(wavelet)
+    cfg = config or SegmentConfig()
+    if n * f > _U32 or 3 * W > _U32:
+        raise CodecError(3, "n_chunks * frames and 3 * width must fit u32")
+    if green_threshold is None and d_background is None:
+        raise CodecError(9, "motion segmentation needs d_background")
+    import torch
+    frames_ptr = _dptr(d_frames)
+    stats = torch.zeros(n * f * 5, dtype=torch.int32, device="cuda")
+    if green_threshold is None:
+        segment_motion_device(frames_ptr, _dptr(d_background), 0, 3 * W, H, n * f, stats.data_ptr(), config=cfg)
+        torch.cuda.synchronize()
+        st = stats.cpu().numpy().view(np.uint32).reshape(-1, 5).astype(np.int64)
+        x0, x1 = st[:, 0] // 3, -(-(st[:, 0] + st[:, 2]) // 3)          # byte columns -> the pixels they belong to
+        st[:, 0], st[:, 2] = x0, x1 - x0
+    else:
+        segment_chroma_rgb_device(frames_ptr, W, H, n * f, int(green_threshold), stats.data_ptr())
+        torch.cuda.synchronize()
+        st = stats.cpu().numpy().view(np.uint32).reshape(-1, 5).astype(np.int64)
+    boxes = person_chunk_boxes(st, W, H, f)
+    empty = FrameEncoder(int(quality), wavelet).encode(b"", 0, 0, f).to_bytes()
+    out = [(b, empty) for b in boxes]
+    frame_bytes = W * H * 3
+    batches = {}
+    for i, j in _runs(boxes):
+        bw, bh = boxes[i][2], boxes[i][3]
+        key = (bw, bh, j - i)
+        if key not in batches:
+            batches[key] = Batch(bw, bh, f, j - i, int(quality), wavelet)
+        batch = batches[key]
+        batch.encode_regions(frames_ptr + i * f * frame_bytes, W, H, [b[:2] for b in boxes[i:j]])
+        sizes = batch.encode_finish()
+        packed = torch.empty(int(sizes.sum()), dtype=torch.uint8, device="cuda")
+        batch.pack_alc(sizes, packed.data_ptr(), packed.numel())
+        torch.cuda.synchronize()
+        host = packed.cpu().numpy()
+        ends = np.cumsum(sizes.astype(np.int64))
+        for k in range(j - i):
+            out[i + k] = (boxes[i + k], host[ends[k] - int(sizes[k]):ends[k]].tobytes())
+    return out
+
+
+def decode_person_chunks(chunks, d_frames_out, width: int, height: int, frames: int) -> None:
+    """Hybrid decode: chunk k of `chunks` (encode_person_chunks' list of (bbox, .alc bytes)) is decoded and pasted into
+    its bbox of frames [k * frames, (k + 1) * frames) of d_frames_out (width x height RGB in HBM, typically holding the
+    background).  Empty chunks paste nothing; no byte outside the boxes is written."""
+    W, H, f = _positive_u32(width, "width"), _positive_u32(height, "height"), _positive_u32(frames, "frames")
+    boxes, alcs = [], []
+    for k, (bbox, alc) in enumerate(chunks):
+        b = [_u32_arg(v, "bbox") for v in bbox]
+        if len(b) != 4:
+            raise CodecError(2, f"chunk {k}: bbox must have 4 elements")
+        if b[2] * b[3] and (b[0] + b[2] > W or b[1] + b[3] > H):
+            raise CodecError(2, f"chunk {k}: bbox {b} does not lie inside the {W}x{H} frame")
+        data = bytes(alc)
+        if b[2] * b[3]:
+            c = EncodedChunk.from_bytes(data)
+            if (c.width, c.height, c.frames) != (b[2], b[3], f):
+                raise CodecError(2, f"chunk {k}: .alc is {c.width}x{c.height}x{c.frames}, bbox says {b[2]}x{b[3]}x{f}")
+        boxes.append(b)
+        alcs.append(data)
+    runs = _runs(boxes)
+    if not runs:
+        return
+    import torch
+    out_ptr = _dptr(d_frames_out)
+    frame_bytes = W * H * 3
+    batches = {}
+    for i, j in runs:
+        bw, bh = boxes[i][2], boxes[i][3]
+        stride = (max(len(a) for a in alcs[i:j]) + 255) & ~255
+        host = np.zeros((j - i, stride), np.uint8)
+        for k in range(i, j):
+            host[k - i, :len(alcs[k])] = np.frombuffer(alcs[k], np.uint8)
+        d_alc = torch.from_numpy(host).to("cuda")
+        key = (bw, bh, j - i)
+        if key not in batches:
+            batches[key] = Batch(bw, bh, f, j - i, 90)
+        batch = batches[key]
+        batch.decode_regions(d_alc.data_ptr(), stride, out_ptr + i * f * frame_bytes, W, H, [b[:2] for b in boxes[i:j]])
+        batch.decode_finish()

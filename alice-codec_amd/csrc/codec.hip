@@ -808,14 +808,14 @@ uint64_t worst_cap(const ChunkDims& d) { return round_up(2 * d.padded + 4 + 64 +
 
 // The forward transform of one chunk: the tile kernels where they cover the shape (w.scratch holds their band slots), else
 // exact reference arithmetic on caller-shaped data (chunks of more than 64 padded frames, say).
-int forward_chunk(const uint8_t* d_rgb, const ChunkDims& d, int wavelet, int32_t step, EncodeWork& w,
+int forward_chunk(const RgbLayout& rgb, const ChunkDims& d, int wavelet, int32_t step, EncodeWork& w,
                   uint8_t* d_sym, uint32_t* d_hist, hipStream_t st) {
-    if (w.scratch.p && launch_forward_transform(d_rgb, d, wavelet, step, w.scratch.p, d_sym, d_hist, st)) return kOk;
+    if (w.scratch.p && launch_forward_transform(rgb, d, wavelet, step, w.scratch.p, d_sym, d_hist, st)) return kOk;
     if (!w.planes.p) TRY(w.planes.alloc(3 * d.n_pixels * sizeof(int16_t)));
     if (!w.tmp.p) TRY(w.tmp.alloc(d.padded * sizeof(int32_t)));
     if (!w.gen.p) TRY(w.gen.alloc(2 * d.padded * sizeof(int32_t)));
     int16_t* pl = w.planes.as<int16_t>();
-    launch_rgb_to_ycocg(d_rgb, d.n_pixels, pl, pl + d.n_pixels, pl + 2 * d.n_pixels, st);
+    launch_rgb_to_ycocg(rgb, d, pl, pl + d.n_pixels, pl + 2 * d.n_pixels, st);
     int32_t* vol = w.gen.as<int32_t>();
     int32_t* qb = vol + d.padded;
     const uint64_t W = d.pw, H = d.ph, D = d.pf;
@@ -858,7 +858,8 @@ struct StageEvents {
 //                per channel (estimate_stream_cap); also what kCapReuse falls back to when there are no buffers yet;
 //   kCapWorst    2 bytes per symbol, the bound of the format (the last resort: 3 x 2 x padded bytes per chunk).
 enum CapMode { kCapReuse = 0, kCapEstimate = 1, kCapWorst = 2 };
-int encode_launch(const uint8_t* d_rgb, EncodeWork& w, uint8_t quality, int wavelet, hipStream_t st,
+// rgb[b]: where chunk b's pixels are (w.n_chunks layouts)
+int encode_launch(const RgbLayout* rgb, EncodeWork& w, uint8_t quality, int wavelet, hipStream_t st,
                   StageEvents* evs, CapMode mode = kCapReuse, HubTicket* hub = nullptr) {
     const ChunkDims& d = w.d;
     const int32_t step = quality_to_step(quality);
@@ -866,9 +867,8 @@ int encode_launch(const uint8_t* d_rgb, EncodeWork& w, uint8_t quality, int wave
     HIP_TRY(hipMemsetAsync(w.hist.p, 0, (size_t)B * 3 * 256 * sizeof(uint32_t), st));
     if (evs) HIP_TRY(hipEventRecord(evs->ev[0], st));
     for (int b = 0; b < B; ++b) {
-        const uint8_t* rgb = d_rgb + (size_t)b * d.n_pixels * 3;
         uint8_t* sym = w.sym.as<uint8_t>() + (size_t)b * 3 * d.padded;
-        TRY(forward_chunk(rgb, d, wavelet, step, w, sym, w.hist.as<uint32_t>() + (size_t)b * 3 * 256, st));
+        TRY(forward_chunk(rgb[b], d, wavelet, step, w, sym, w.hist.as<uint32_t>() + (size_t)b * 3 * 256, st));
     }
     if (evs) HIP_TRY(hipEventRecord(evs->ev[1], st));
     const bool had_alc = w.alc.p != nullptr;
@@ -950,10 +950,10 @@ int encode_collect(EncodeWork& w, hipStream_t st, std::vector<RansResult>& res) 
 
 // The capacity ladder: encodes from `mode` on, one CapMode further after every overflow.  kCapWorst is the format's bound,
 // so a chain that overflows even there is an internal error.
-int encode_with_retry(const uint8_t* d_rgb, EncodeWork& w, uint8_t quality, int wavelet, hipStream_t st, StageEvents* evs,
+int encode_with_retry(const RgbLayout* rgb, EncodeWork& w, uint8_t quality, int wavelet, hipStream_t st, StageEvents* evs,
                       CapMode mode, HubTicket* hub, std::vector<RansResult>& res) {
     for (int m = mode; m <= kCapWorst; ++m) {
-        TRY(encode_launch(d_rgb, w, quality, wavelet, st, evs, (CapMode)m, hub));
+        TRY(encode_launch(rgb, w, quality, wavelet, st, evs, (CapMode)m, hub));
         const int rc = encode_collect(w, st, res);
         if (rc != kOverflowed) return rc;
     }
@@ -985,9 +985,9 @@ int decode_work_alloc(DecodeWork& w, const ChunkDims& d, int n_chunks, uint8_t* 
 // The inverse transform of one chunk: the tile kernels where they cover the shape (d_scratch: their band slots, null when
 // they do not), else exact reference arithmetic.
 int inverse_chunk(const uint8_t* d_sym, const ChunkDims& d, int wavelet, const int32_t step[3], void* d_scratch, DecodeWork& w,
-                  uint8_t* d_rgb, hipStream_t st) {
+                  const RgbLayout& rgb, hipStream_t st) {
     const InverseBounds ib = inverse_bounds(wavelet, step);
-    if (d_scratch && launch_inverse_transform(d_sym, d, wavelet, step, ib.exact, ib.mid16, ib.lds16, d_scratch, d_rgb, st)) return kOk;
+    if (d_scratch && launch_inverse_transform(d_sym, d, wavelet, step, ib.exact, ib.mid16, ib.lds16, d_scratch, rgb, st)) return kOk;
     if (!w.planes.p) TRY(w.planes.alloc(3 * d.n_pixels * sizeof(int16_t)));
     if (!w.tmp.p) TRY(w.tmp.alloc(d.padded * sizeof(int32_t)));
     if (!w.gen.p) TRY(w.gen.alloc(2 * d.padded * sizeof(int32_t)));
@@ -1003,14 +1003,14 @@ int inverse_chunk(const uint8_t* d_sym, const ChunkDims& d, int wavelet, const i
         launch_wavelet_axis(vol, w.tmp.as<int32_t>(), W, 1, D * H, W, 1, 0, wavelet, true, st);
         launch_strip_channel(vol, d, pl + (size_t)c * d.n_pixels, st);
     }
-    launch_ycocg_to_rgb(pl, pl + d.n_pixels, pl + 2 * d.n_pixels, d.n_pixels, d_rgb, st);
+    launch_ycocg_to_rgb(pl, pl + d.n_pixels, pl + 2 * d.n_pixels, d, rgb, st);
     return kOk;
 }
 
 // headers[b]: parsed chunk headers (validated); d_payload[b]: device pointer to chunk b's payload;
-// d_rgb[b]: where chunk b's pixels go
+// rgb[b]: where chunk b's pixels go
 int decode_launch(const EncodedChunk* const* headers, const std::vector<const uint8_t*>& d_payload,
-                  DecodeWork& w, const std::vector<uint8_t*>& d_rgb, hipStream_t st, StageEvents* evs, HubTicket* hub = nullptr) {
+                  DecodeWork& w, const std::vector<RgbLayout>& rgb, hipStream_t st, StageEvents* evs, HubTicket* hub = nullptr) {
     const ChunkDims& d = w.d;
     const int B = w.n_chunks;
     if (transform_tiles_eligible(d)) {
@@ -1057,7 +1057,7 @@ int decode_launch(const EncodedChunk* const* headers, const std::vector<const ui
     if (evs) HIP_TRY(hipEventRecord(evs->ev[6], st));
     for (int b = 0; b < B; ++b) {
         const int32_t step[3] = {headers[b]->ch[0].quant_step, headers[b]->ch[1].quant_step, headers[b]->ch[2].quant_step};
-        TRY(inverse_chunk(w.sym_ptr + (size_t)b * 3 * d.padded, d, headers[b]->wavelet, step, w.scratch->p, w, d_rgb[b], st));
+        TRY(inverse_chunk(w.sym_ptr + (size_t)b * 3 * d.padded, d, headers[b]->wavelet, step, w.scratch->p, w, rgb[b], st));
     }
     if (evs) HIP_TRY(hipEventRecord(evs->ev[7], st));
     HIP_TRY(hipGetLastError());
@@ -1138,7 +1138,9 @@ int encode_chunks_on_device(const FrameEncoder& enc, const uint8_t* rgb, const C
                 HIP_TRY(hipMemcpyAsync(d_rgb.as<uint8_t>() + (size_t)i * chunk_bytes, rgb + at(first + i) * chunk_bytes, chunk_bytes, hipMemcpyHostToDevice, st));
                 return (int)kOk;
             });
-        if (rc == kOk) rc = encode_with_retry(d_rgb.as<uint8_t>(), w, enc.quality, enc.wavelet, st, nullptr, kCapReuse, &ticket, res);
+        std::vector<RgbLayout> layouts(B);
+        for (uint32_t i = 0; i < B; ++i) layouts[i] = packed_rgb(d_rgb.as<uint8_t>() + (size_t)i * chunk_bytes, d);
+        if (rc == kOk) rc = encode_with_retry(layouts.data(), w, enc.quality, enc.wavelet, st, nullptr, kCapReuse, &ticket, res);
         if (rc != kOk) return undo(rc);
         // all headers with one strided copy, then the payloads straight into the chunk objects, several at a time
         std::vector<uint8_t> hdr((size_t)B * kAlcHeaderBytes);
@@ -1184,12 +1186,12 @@ int decode_chunks_on_device(const EncodedChunk* const* chunks, const ChunkDims& 
         TRY(d_payload.alloc(total_payload + 256));
         TRY(d_rgb.alloc(chunk_bytes * B));
         std::vector<const uint8_t*> pay(B);
-        std::vector<uint8_t*> dst(B);
+        std::vector<RgbLayout> dst(B);
         uint64_t off = 0;
         for (uint32_t i = 0; i < B; ++i) {
             const EncodedChunk& c = *hdrs[i];
             pay[i] = d_payload.as<uint8_t>() + off;
-            dst[i] = d_rgb.as<uint8_t>() + (size_t)i * chunk_bytes;
+            dst[i] = packed_rgb(d_rgb.as<uint8_t>() + (size_t)i * chunk_bytes, d);
             if (!c.data.empty())
                 HIP_TRY(hipMemcpyAsync(d_payload.as<uint8_t>() + off, c.data.data(), c.data.size(), hipMemcpyHostToDevice, st));
             off += round_up(c.data.size() + 16, 256);
@@ -1199,7 +1201,7 @@ int decode_chunks_on_device(const EncodedChunk* const* chunks, const ChunkDims& 
         TRY(decode_launch(hdrs.data(), pay, w, dst, st, nullptr, &ticket));
         TRY(decode_collect(w, st));
         TRY(parallel_chunks(B, chunk_bytes >= (4u << 20) ? kCopyThreads : 1u,
-                            [&](uint32_t i) { return copy_to_host(rgb_out + at(first + i) * chunk_bytes, dst[i], chunk_bytes, st); }));
+                            [&](uint32_t i) { return copy_to_host(rgb_out + at(first + i) * chunk_bytes, dst[i].base, chunk_bytes, st); }));
     }
     return kOk;
 }
@@ -1390,14 +1392,97 @@ struct AliceBatch {
     EncodeWork enc;
     DecodeWork dec;
     DevBuf spare;             // in-place decode: the pixels of chunk 0 (chunk i > 0 lands on the symbols of chunk i - 1)
-    std::vector<uint8_t*> rgb_dst;   // where the last decode put each chunk's pixels
+    std::vector<RgbLayout> rgb_dst;  // where the last decode put each chunk's pixels
     bool dec_ready = false;
     StageEvents evs;
     hipStream_t enc_stream = nullptr, dec_stream = nullptr;
-    const uint8_t* last_rgb = nullptr;
+    std::vector<RgbLayout> last_rgb;   // where the last encode read each chunk (packed or a region): what a retry re-reads
     bool enc_timed = false, dec_timed = false;
     float stage_ms[6] = {0, 0, 0, 0, 0, 0};
 };
+
+namespace {
+
+// Chunk i of a region call: frames [i * f, (i + 1) * f) of the frame_width x frame_height frames at d_frames (packed RGB),
+// cropped to the batch's w x h at origins[2i], origins[2i + 1].  Every rectangle must lie inside the frame: where the
+// reference's crop_to_bbox / paste_from_bbox skip rows that fall outside (src/segment.rs:275-276, 293), this is an error
+// before anything is queued.
+int region_layouts(const AliceBatch* b, const void* d_frames, uint32_t frame_width, uint32_t frame_height, const uint32_t* origins,
+                   std::vector<RgbLayout>& out) {
+    if (!b || !d_frames || !origins) return fail(kNullArgument, "null argument");
+    uint64_t frame_px = 0;
+    TRY(checked_pixel_count(frame_width, frame_height, (uint64_t)b->d.f * b->n_chunks, &frame_px));
+    if (frame_px > UINT64_MAX / 3) return fail(kDimensionOverflow, "dimensions overflow usize");
+    const uint64_t row_pitch = 3ull * frame_width, frame_pitch = row_pitch * frame_height;
+    out.resize(b->n_chunks);
+    for (uint32_t i = 0; i < b->n_chunks; ++i) {
+        const uint64_t x0 = origins[2 * i], y0 = origins[2 * i + 1];
+        if (x0 + b->d.w > frame_width || y0 + b->d.h > frame_height)
+            return fail(kInvalidDimensions, "region " + std::to_string(i) + " at (" + std::to_string(x0) + ", " + std::to_string(y0) +
+                                                ") does not lie inside the " + std::to_string(frame_width) + "x" + std::to_string(frame_height) + " frame");
+        out[i] = RgbLayout{(uint8_t*)d_frames + (size_t)i * b->d.f * frame_pitch + y0 * row_pitch + x0 * 3, row_pitch, frame_pitch};
+    }
+    return kOk;
+}
+
+// rgb: one layout per chunk, kept for encode_finish's retry
+int batch_encode_layouts(AliceBatch* b, std::vector<RgbLayout>&& rgb, hipStream_t st) {
+    DeviceScope ds(b->device);
+    if (!ds.ok) return tl_err;
+    tl_scope_stream = nullptr;   // batch buffers outlive the call; alice_codec_batch_destroy drains the device
+    b->enc_stream = st;
+    b->enc_timed = false;
+    b->last_rgb = std::move(rgb);
+    return encode_launch(b->last_rgb.data(), b->enc, b->quality, b->wavelet, b->enc_stream, &b->evs);
+}
+
+// rgb: one layout per chunk, or empty for the batch's own storage
+int batch_decode_layouts(AliceBatch* b, const void* d_alc, uint64_t alc_stride, std::vector<RgbLayout>&& rgb, hipStream_t st) {
+    DeviceScope ds(b->device);
+    if (!ds.ok) return tl_err;
+    tl_scope_stream = nullptr;
+    b->dec_stream = st;
+    b->dec_timed = false;
+    if (!b->dec_ready) {
+        TRY(decode_work_alloc(b->dec, b->d, (int)b->n_chunks, b->enc.sym.as<uint8_t>(), &b->enc.scratch));
+        b->dec_ready = true;
+    }
+    // headers: one strided device-to-host copy, then validation on the host
+    std::vector<uint8_t> hdr((size_t)b->n_chunks * kAlcHeaderBytes);
+    HIP_TRY(hipMemcpy2DAsync(hdr.data(), kAlcHeaderBytes, d_alc, alc_stride, kAlcHeaderBytes, b->n_chunks, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    std::vector<EncodedChunk> headers(b->n_chunks);
+    std::vector<const EncodedChunk*> hp(b->n_chunks);
+    std::vector<const uint8_t*> pay(b->n_chunks);
+    for (uint32_t i = 0; i < b->n_chunks; ++i) {
+        uint64_t payload = 0;
+        TRY(parse_alc_header(hdr.data() + (size_t)i * kAlcHeaderBytes, kAlcHeaderBytes, headers[i], &payload));
+        if (headers[i].width != b->d.w || headers[i].height != b->d.h || headers[i].frames != b->d.f)
+            return fail(kInvalidDimensions, "chunk dimensions differ from the batch shape");
+        if ((uint64_t)kAlcHeaderBytes + payload > alc_stride) return fail(kInvalidBitstream, "truncated payload");
+        ChunkDims dd;
+        TRY(validate_for_decode(headers[i], &dd, payload));
+        pay[i] = (const uint8_t*)d_alc + (size_t)i * alc_stride + kAlcHeaderBytes;
+        hp[i] = &headers[i];
+    }
+    // no layouts: the batch keeps the pixels in its own storage (alice_codec_batch_rgb_ptr).  An uncut chunk is
+    // reconstructed over its own (by then consumed) symbols: its temporal pass is the last reader of those symbols and
+    // runs before the tile pass that writes the pixels.  A chunk that is cut into bands writes the pixels of its first
+    // band while the temporal pass of its later bands still reads symbols: the pixels of chunk i then land on the symbols
+    // of chunk i - 1, whose last reader finished launches ago, and chunk 0 gets a buffer of its own.
+    if (rgb.empty()) {
+        const bool cut = inverse_cuts_chunk(b->d);
+        if (cut && !b->spare.p) TRY(b->spare.alloc(b->d.n_pixels * 3));
+        rgb.resize(b->n_chunks);
+        for (uint32_t i = 0; i < b->n_chunks; ++i)
+            rgb[i] = packed_rgb(!cut ? b->dec.sym_ptr + (size_t)i * 3 * b->d.padded
+                                     : (i == 0 ? b->spare.as<uint8_t>() : b->dec.sym_ptr + (size_t)(i - 1) * 3 * b->d.padded), b->d);
+    }
+    b->rgb_dst = std::move(rgb);
+    return decode_launch(hp.data(), pay, b->dec, b->rgb_dst, st, &b->evs);
+}
+
+}  // namespace
 
 // ------------------------------------------------------------------------------------------
 // C ABI
@@ -1582,13 +1667,16 @@ void alice_codec_batch_destroy(AliceBatch* b) {
 int alice_codec_batch_encode(AliceBatch* b, const void* d_rgb, void* hip_stream) {
     clear_error();
     if (!b || !d_rgb) return fail(kNullArgument, "null argument");
-    DeviceScope ds(b->device);
-    if (!ds.ok) return tl_err;
-    tl_scope_stream = nullptr;   // batch buffers outlive the call; alice_codec_batch_destroy drains the device
-    b->enc_stream = (hipStream_t)hip_stream;
-    b->enc_timed = false;
-    b->last_rgb = (const uint8_t*)d_rgb;
-    return encode_launch((const uint8_t*)d_rgb, b->enc, b->quality, b->wavelet, b->enc_stream, &b->evs);
+    std::vector<RgbLayout> rgb(b->n_chunks);
+    for (uint32_t i = 0; i < b->n_chunks; ++i) rgb[i] = packed_rgb((const uint8_t*)d_rgb + (size_t)i * b->d.n_pixels * 3, b->d);
+    return batch_encode_layouts(b, std::move(rgb), (hipStream_t)hip_stream);
+}
+int alice_codec_batch_encode_regions(AliceBatch* b, const void* d_frames, uint32_t frame_width, uint32_t frame_height,
+                                     const uint32_t* origins, void* hip_stream) {
+    clear_error();
+    std::vector<RgbLayout> rgb;
+    TRY(region_layouts(b, d_frames, frame_width, frame_height, origins, rgb));
+    return batch_encode_layouts(b, std::move(rgb), (hipStream_t)hip_stream);
 }
 int alice_codec_batch_encode_finish(AliceBatch* b, uint64_t* sizes) {
     clear_error();
@@ -1600,8 +1688,8 @@ int alice_codec_batch_encode_finish(AliceBatch* b, uint64_t* sizes) {
     int rc = encode_collect(b->enc, b->enc_stream, res);
     // a chain outgrew its region: the capacities came from an earlier encode of other content (kCapReuse) -- size them
     // from this content's histograms and run again; should even that fall short (never observed), take the format's bound
-    if (rc == kOverflowed && b->last_rgb)
-        rc = encode_with_retry(b->last_rgb, b->enc, b->quality, b->wavelet, b->enc_stream, &b->evs, kCapEstimate, nullptr, res);
+    if (rc == kOverflowed && !b->last_rgb.empty())
+        rc = encode_with_retry(b->last_rgb.data(), b->enc, b->quality, b->wavelet, b->enc_stream, &b->evs, kCapEstimate, nullptr, res);
     if (rc == kOverflowed) return fail(kInternal, "rANS output exceeded the worst-case capacity");   // (no encode to repeat)
     if (rc) return rc;
     for (int i = 0; i < 4; ++i) (void)hipEventElapsedTime(&b->stage_ms[i], b->evs.ev[i], b->evs.ev[i + 1]);
@@ -1651,54 +1739,24 @@ int alice_codec_batch_pack_alc(AliceBatch* b, const uint64_t* sizes, void* d_dst
 int alice_codec_batch_decode(AliceBatch* b, const void* d_alc, uint64_t alc_stride, void* d_rgb_out, void* hip_stream) {
     clear_error();
     if (!b || !d_alc) return fail(kNullArgument, "null argument");
-    DeviceScope ds(b->device);
-    if (!ds.ok) return tl_err;
-    tl_scope_stream = nullptr;
-    hipStream_t st = (hipStream_t)hip_stream;
-    b->dec_stream = st;
-    b->dec_timed = false;
-    if (!b->dec_ready) {
-        TRY(decode_work_alloc(b->dec, b->d, (int)b->n_chunks, b->enc.sym.as<uint8_t>(), &b->enc.scratch));
-        b->dec_ready = true;
+    std::vector<RgbLayout> rgb;
+    if (d_rgb_out) {
+        rgb.resize(b->n_chunks);
+        for (uint32_t i = 0; i < b->n_chunks; ++i) rgb[i] = packed_rgb((uint8_t*)d_rgb_out + (size_t)i * b->d.n_pixels * 3, b->d);
     }
-    // headers: one strided device-to-host copy, then validation on the host
-    std::vector<uint8_t> hdr((size_t)b->n_chunks * kAlcHeaderBytes);
-    HIP_TRY(hipMemcpy2DAsync(hdr.data(), kAlcHeaderBytes, d_alc, alc_stride, kAlcHeaderBytes, b->n_chunks, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    std::vector<EncodedChunk> headers(b->n_chunks);
-    std::vector<const EncodedChunk*> hp(b->n_chunks);
-    std::vector<const uint8_t*> pay(b->n_chunks);
-    for (uint32_t i = 0; i < b->n_chunks; ++i) {
-        uint64_t payload = 0;
-        TRY(parse_alc_header(hdr.data() + (size_t)i * kAlcHeaderBytes, kAlcHeaderBytes, headers[i], &payload));
-        if (headers[i].width != b->d.w || headers[i].height != b->d.h || headers[i].frames != b->d.f)
-            return fail(kInvalidDimensions, "chunk dimensions differ from the batch shape");
-        if ((uint64_t)kAlcHeaderBytes + payload > alc_stride) return fail(kInvalidBitstream, "truncated payload");
-        ChunkDims dd;
-        TRY(validate_for_decode(headers[i], &dd, payload));
-        pay[i] = (const uint8_t*)d_alc + (size_t)i * alc_stride + kAlcHeaderBytes;
-        hp[i] = &headers[i];
-    }
-    // d_rgb_out == NULL: the batch keeps the pixels in its own storage (alice_codec_batch_rgb_ptr).  An uncut chunk is
-    // reconstructed over its own (by then consumed) symbols: its temporal pass is the last reader of those symbols and
-    // runs before the tile pass that writes the pixels.  A chunk that is cut into bands writes the pixels of its first
-    // band while the temporal pass of its later bands still reads symbols: the pixels of chunk i then land on the symbols
-    // of chunk i - 1, whose last reader finished launches ago, and chunk 0 gets a buffer of its own.
-    b->rgb_dst.assign(b->n_chunks, nullptr);
-    if (!d_rgb_out) {
-        const bool cut = inverse_cuts_chunk(b->d);
-        if (cut && !b->spare.p) TRY(b->spare.alloc(b->d.n_pixels * 3));
-        for (uint32_t i = 0; i < b->n_chunks; ++i)
-            b->rgb_dst[i] = !cut ? b->dec.sym_ptr + (size_t)i * 3 * b->d.padded
-                                 : (i == 0 ? b->spare.as<uint8_t>() : b->dec.sym_ptr + (size_t)(i - 1) * 3 * b->d.padded);
-    } else {
-        for (uint32_t i = 0; i < b->n_chunks; ++i) b->rgb_dst[i] = (uint8_t*)d_rgb_out + (size_t)i * b->d.n_pixels * 3;
-    }
-    return decode_launch(hp.data(), pay, b->dec, b->rgb_dst, st, &b->evs);
+    return batch_decode_layouts(b, d_alc, alc_stride, std::move(rgb), (hipStream_t)hip_stream);
+}
+int alice_codec_batch_decode_regions(AliceBatch* b, const void* d_alc, uint64_t alc_stride, void* d_frames_out, uint32_t frame_width,
+                                     uint32_t frame_height, const uint32_t* origins, void* hip_stream) {
+    clear_error();
+    if (!d_alc) return fail(kNullArgument, "null argument");
+    std::vector<RgbLayout> rgb;
+    TRY(region_layouts(b, d_frames_out, frame_width, frame_height, origins, rgb));
+    return batch_decode_layouts(b, d_alc, alc_stride, std::move(rgb), (hipStream_t)hip_stream);
 }
 const void* alice_codec_batch_rgb_ptr(const AliceBatch* b, uint32_t chunk) {
     if (!b || chunk >= b->n_chunks || chunk >= b->rgb_dst.size()) return nullptr;
-    return b->rgb_dst[chunk];
+    return b->rgb_dst[chunk].base;
 }
 int alice_codec_batch_decode_finish(AliceBatch* b) {
     clear_error();
@@ -2323,7 +2381,7 @@ int alice_codec_dev_forward_symbols(const void* d_rgb, uint32_t width, uint32_t 
     TRY(w.hist.alloc(3 * 256 * sizeof(uint32_t)));
     uint32_t* hist = d_hist ? (uint32_t*)d_hist : w.hist.as<uint32_t>();
     HIP_TRY(hipMemsetAsync(hist, 0, 3 * 256 * sizeof(uint32_t), st));
-    TRY(forward_chunk((const uint8_t*)d_rgb, d, wavelet_type, quality_to_step(quality), w, (uint8_t*)d_symbols, hist, st));
+    TRY(forward_chunk(packed_rgb(d_rgb, d), d, wavelet_type, quality_to_step(quality), w, (uint8_t*)d_symbols, hist, st));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
     return kOk;
@@ -2342,7 +2400,7 @@ int alice_codec_dev_inverse_symbols(const void* d_symbols, uint32_t width, uint3
     DecodeWork w;
     w.d = d; w.n_chunks = 1;
     if (transform_tiles_eligible(d)) TRY(w.scratch_own.alloc(inverse_scratch_bytes(d, inverse_bounds(wavelet_type, step).mid16)));
-    TRY(inverse_chunk((const uint8_t*)d_symbols, d, wavelet_type, step, w.scratch_own.p, w, (uint8_t*)d_rgb, st));
+    TRY(inverse_chunk((const uint8_t*)d_symbols, d, wavelet_type, step, w.scratch_own.p, w, packed_rgb(d_rgb, d), st));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
     return kOk;
@@ -2482,7 +2540,7 @@ int alice_codec_test_transform_ms(const void* d_rgb, void* d_sym, void* d_rgb_ou
     auto fwd = [&]() {
         for (uint32_t c = 0; c < n_chunks; ++c) {
             const uint32_t k = c % n_buffers;
-            launch_forward_transform((const uint8_t*)d_rgb + (size_t)k * d.n_pixels * 3, d, wavelet_type, step, scratch.p,
+            launch_forward_transform(packed_rgb((const uint8_t*)d_rgb + (size_t)k * d.n_pixels * 3, d), d, wavelet_type, step, scratch.p,
                                      (uint8_t*)d_sym + (size_t)k * 3 * d.padded, hist.as<uint32_t>(), st);
         }
     };
@@ -2490,7 +2548,7 @@ int alice_codec_test_transform_ms(const void* d_rgb, void* d_sym, void* d_rgb_ou
         for (uint32_t c = 0; c < n_chunks; ++c) {
             const uint32_t k = c % n_buffers;
             launch_inverse_transform((const uint8_t*)d_sym + (size_t)k * 3 * d.padded, d, wavelet_type, steps, ib.exact, ib.mid16,
-                                     ib.lds16, scratch.p, (uint8_t*)d_rgb_out + (size_t)k * d.n_pixels * 3, st);
+                                     ib.lds16, scratch.p, packed_rgb((uint8_t*)d_rgb_out + (size_t)k * d.n_pixels * 3, d), st);
         }
     };
     fwd();   // warm-up; also leaves real symbols for the inverse

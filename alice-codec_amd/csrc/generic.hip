@@ -3,6 +3,8 @@
 // that assemble `.alc` buffers on the device.  These back the public Wavelet1D/2D/3D,
 // Quantizer/FastQuantizer, to_symbols/from_symbols/build_histogram and colour entry points,
 // and the pipeline when a chunk has more than 64 (padded) frames.
+#include <algorithm>
+
 #include "common.h"
 #include "kernels.h"
 
@@ -163,6 +165,61 @@ void launch_ycocg_to_rgb(const int16_t* y, const int16_t* co, const int16_t* cg,
     if (!n_pixels) return;
     hipLaunchKernelGGL(ycocg_to_rgb_kernel, dim3(grid_for(n_pixels)), dim3(256), 0, st, y, co, cg,
                        (unsigned long long)n_pixels, d_rgb);
+}
+
+// The same conversions for a chunk at any RgbLayout (a region of larger frames): planes [f][h][w] on one side, the rectangle
+// on the other, nothing outside it read or written.  A workgroup takes whole rows (t, y), its threads the pixels of a row,
+// so the only division is one per row.
+__global__ __launch_bounds__(256) void rgb_region_to_ycocg_kernel(RgbLayout src, uint32_t w, uint32_t h, unsigned long long rows,
+                                                                  int16_t* __restrict__ y, int16_t* __restrict__ co,
+                                                                  int16_t* __restrict__ cg) {
+    for (unsigned long long row = blockIdx.x; row < rows; row += gridDim.x) {
+        const uint8_t* p = src.base + (row / h) * src.frame_pitch + (row % h) * src.row_pitch;
+        const unsigned long long o = row * w;
+        for (uint32_t x = threadIdx.x; x < w; x += 256) {
+            const int r = p[3ull * x], g = p[3ull * x + 1], b = p[3ull * x + 2];  // src/color.rs:221-228
+            const int c_o = r - b;
+            const int t = b + (c_o >> 1);
+            const int c_g = g - t;
+            y[o + x] = (int16_t)(t + (c_g >> 1));
+            co[o + x] = (int16_t)c_o;
+            cg[o + x] = (int16_t)c_g;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void ycocg_to_rgb_region_kernel(const int16_t* __restrict__ y, const int16_t* __restrict__ co,
+                                                                  const int16_t* __restrict__ cg, RgbLayout dst, uint32_t w,
+                                                                  uint32_t h, unsigned long long rows) {
+    for (unsigned long long row = blockIdx.x; row < rows; row += gridDim.x) {
+        uint8_t* p = dst.base + (row / h) * dst.frame_pitch + (row % h) * dst.row_pitch;
+        const unsigned long long o = row * w;
+        for (uint32_t x = threadIdx.x; x < w; x += 256) {
+            const short yv = y[o + x], c_o = co[o + x], c_g = cg[o + x];  // src/color.rs:266-273, i16 wrapping
+            const short t = (short)(yv - (short)(c_g >> 1));
+            const short g = (short)(c_g + t);
+            const short b = (short)(t - (short)(c_o >> 1));
+            const short r = (short)(c_o + b);
+            p[3ull * x] = (uint8_t)min(max((int)r, 0), 255);
+            p[3ull * x + 1] = (uint8_t)min(max((int)g, 0), 255);
+            p[3ull * x + 2] = (uint8_t)min(max((int)b, 0), 255);
+        }
+    }
+}
+
+void launch_rgb_to_ycocg(const RgbLayout& rgb, const ChunkDims& d, int16_t* y, int16_t* co, int16_t* cg, hipStream_t st) {
+    if (rgb_is_packed(rgb, d)) return launch_rgb_to_ycocg(rgb.base, d.n_pixels, y, co, cg, st);
+    const unsigned long long rows = (unsigned long long)d.h * d.f;
+    if (!rows || !d.w) return;
+    hipLaunchKernelGGL(rgb_region_to_ycocg_kernel, dim3((unsigned)std::min<unsigned long long>(rows, 65536)), dim3(256), 0, st, rgb,
+                       d.w, d.h, rows, y, co, cg);
+}
+void launch_ycocg_to_rgb(const int16_t* y, const int16_t* co, const int16_t* cg, const ChunkDims& d, const RgbLayout& rgb, hipStream_t st) {
+    if (rgb_is_packed(rgb, d)) return launch_ycocg_to_rgb(y, co, cg, d.n_pixels, rgb.base, st);
+    const unsigned long long rows = (unsigned long long)d.h * d.f;
+    if (!rows || !d.w) return;
+    hipLaunchKernelGGL(ycocg_to_rgb_region_kernel, dim3((unsigned)std::min<unsigned long long>(rows, 65536)), dim3(256), 0, st, y, co,
+                       cg, rgb, d.w, d.h, rows);
 }
 
 // ---- pad / strip (src/pipeline.rs:77-114, 603-611) ---------------------------------------

@@ -94,6 +94,19 @@ void launch_rans_encode_descs(const RansEncodeDesc* d_descs, int n_chains, hipSt
 // static LDS bytes, workgroups per CU it would co-schedule; out[3..5] = decoder.  False when a query failed.
 bool chain_kernel_occupancy(uint32_t out[6]);
 
+// Where a chunk's interleaved RGB pixels live: pixel x of row y of frame t at base + t * frame_pitch + y * row_pitch + 3 * x,
+// for x < w, y < h, t < f of the chunk.  A chunk stored on its own is packed (row_pitch 3w, frame_pitch 3wh); a region of
+// larger frames points base at its origin pixel and keeps the frames' pitches.  All offsets are 64-bit.
+struct RgbLayout {
+    uint8_t* base;
+    uint64_t row_pitch, frame_pitch;
+};
+inline RgbLayout packed_rgb(const void* p, const ChunkDims& d) { return RgbLayout{(uint8_t*)p, 3ull * d.w, 3ull * d.w * d.h}; }
+inline bool rgb_is_packed(const RgbLayout& l, const ChunkDims& d) { return l.row_pitch == 3ull * d.w && l.frame_pitch == 3ull * d.w * d.h; }
+// the tile kernels' dword loads / stores: every row start 4-byte aligned (a 16-pixel segment starts at a multiple of 48
+// bytes into its row), and a region of 4-aligned width-W frames qualifies when W % 4 == 0 and x0 % 4 == 0
+inline bool rgb_dword_aligned(const RgbLayout& l) { return (((uintptr_t)l.base) & 3u) == 0 && l.row_pitch % 4 == 0 && l.frame_pitch % 4 == 0; }
+
 // ---- transform.hip (pipeline-specialised: RGB <-> u8 symbols) ----
 // A chunk is processed in BANDS of whole tile rows so that a band's intermediate (i16 after the spatial pass, i16 / i32
 // after the inverse temporal pass) stays in the Infinity Cache between the two passes, and every launch runs the
@@ -120,14 +133,15 @@ void set_transform_tuning(long band_kb);
 void set_value_table_radius(int r);
 // Launches of one chunk on `st`, band after band (tile pass then temporal pass; the inverse the other way round).
 // hist: uint32 [3][256], zeroed by the caller.  Returns false (nothing launched) when the shape needs the generic path.
-bool launch_forward_transform(const uint8_t* d_rgb, const ChunkDims& d, int wavelet, int32_t step,
+bool launch_forward_transform(const RgbLayout& rgb, const ChunkDims& d, int wavelet, int32_t step,
                               void* d_scratch, uint8_t* d_sym, uint32_t* d_hist, hipStream_t st);
 // steps per channel come from the chunk header.  exact = 64-bit lifting products.  mid16 = the intermediate after the
 // temporal pass provably fits i16 (halves its traffic); lds16 = so does everything after the column pass (packed tile).
 // When the chunk is cut into bands the pixels of the first band are written while the symbols of later bands are still
-// unread: d_rgb must not overlap d_sym then (an uncut chunk may decode over its own symbols).
+// unread: the pixels must not overlap d_sym then (an uncut chunk may decode over its own symbols).  Only the w x h x f
+// pixels of `rgb` are written: no byte between or beside the rows of a region.
 bool launch_inverse_transform(const uint8_t* d_sym, const ChunkDims& d, int wavelet, const int32_t step[3],
-                              bool exact, bool mid16, bool lds16, void* d_scratch, uint8_t* d_rgb, hipStream_t st);
+                              bool exact, bool mid16, bool lds16, void* d_scratch, const RgbLayout& rgb, hipStream_t st);
 
 // ---- transform.hip, stage level: Wavelet2D / Wavelet3D of caller-shaped i32 data on the tile kernels' exact instances ----
 // eligible: even width and height >= 6, even depth (or depth 1); otherwise the caller uses launch_wavelet_axis.
@@ -144,6 +158,9 @@ void launch_wavelet_axis(int32_t* d_data, int32_t* d_tmp, uint64_t n, uint64_t s
                          hipStream_t st);
 void launch_rgb_to_ycocg(const uint8_t* d_rgb, uint64_t n_pixels, int16_t* y, int16_t* co, int16_t* cg, hipStream_t st);
 void launch_ycocg_to_rgb(const int16_t* y, const int16_t* co, const int16_t* cg, uint64_t n_pixels, uint8_t* d_rgb, hipStream_t st);
+// the same for the w x h x f pixels of a chunk at any layout (planes packed [f][h][w]; a packed layout takes the calls above)
+void launch_rgb_to_ycocg(const RgbLayout& rgb, const ChunkDims& d, int16_t* y, int16_t* co, int16_t* cg, hipStream_t st);
+void launch_ycocg_to_rgb(const int16_t* y, const int16_t* co, const int16_t* cg, const ChunkDims& d, const RgbLayout& rgb, hipStream_t st);
 void launch_pad_channel(const int16_t* ch, const ChunkDims& d, int32_t* out, hipStream_t st);
 void launch_strip_channel(const int32_t* in, const ChunkDims& d, int16_t* ch, hipStream_t st);
 void launch_quantize(const int32_t* in, int32_t* out, uint64_t n, int32_t step, int32_t dead_zone, hipStream_t st);

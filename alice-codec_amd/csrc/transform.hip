@@ -155,11 +155,11 @@ constexpr int F_TW = 128, F_TH = 40, F_SEG = 16, F_NSEG = 8, F_THREADS = 384;
 constexpr int F_LP = F_TW / 2 + 1;  // LDS row pitch in dwords (packed i16 pairs); odd pitch keeps stage-A stores at <= 2-way conflicts
 
 struct FwdXy {
-    const uint8_t* rgb;
+    RgbLayout rgb;               // the chunk's pixels (read only)
     int16_t* mid;                // the band's slot: i16 [ch][t][band row][pw], band rows = [low rows | high rows]
     ChunkDims d;
     Coeffs cf;
-    int aligned;
+    int aligned;                 // rgb_dword_aligned(rgb): dword loads for segments inside the frame
     BandTiles bt;
     int y0, rows;                // the band: first padded row (even) and number of padded rows (even)
 };
@@ -188,7 +188,7 @@ __device__ __forceinline__ void fwd_xy_tile(const FwdXy& a, int bx, int by, int 
             // of an odd size (src/pipeline.rs:77-114: edge replicate) clamps to the last real one
             const int sy = EDGE ? min(reflect_idx(gy, ph), (int)d.h - 1) : gy;
             const int gxs = gx0 - 4 + s * F_SEG;
-            const uint8_t* row = a.rgb + ((size_t)st * d.h + sy) * d.w * 3;
+            const uint8_t* row = a.rgb.base + (size_t)st * a.rgb.frame_pitch + (size_t)sy * a.rgb.row_pitch;
             int y[SE], co[SE], cg[SE];
             if ((PROBE & 1) || (a.aligned && (!EDGE || (gxs >= 0 && gxs + SE <= (int)d.w)))) {
                 const uint32_t* p4 = (const uint32_t*)(row + (ptrdiff_t)gxs * 3);
@@ -735,10 +735,10 @@ constexpr int I_LW = 112;   // LDS row pitch in dwords.  Every 8-sample run stag
 
 struct InvXy {
     const void* mid;             // the band's slot (see InvTm)
-    uint8_t* rgb;
+    RgbLayout rgb;               // where the chunk's w x h x f pixels go; nothing else is written
     ChunkDims d;
     Coeffs cf;
-    int aligned;
+    int aligned;                 // rgb_dword_aligned(rgb): dword stores for segments inside the frame
     BandTiles bt;
     int L0, rows_l;              // slot rows: low-band rows [L0, L0 + rows_l), then the same rows of the high band
 };
@@ -790,13 +790,13 @@ __device__ __forceinline__ void store_rgb8(const InvXy& a, bool edge, const int*
         out[3 * kk + 1] = (uint8_t)min(max((int)g, 0), 255);
         out[3 * kk + 2] = (uint8_t)min(max((int)b, 0), 255);
     }
-    uint8_t* p = a.rgb + (((size_t)t * d.h + gy) * d.w + gxs) * 3;
+    uint8_t* p = a.rgb.base + (size_t)t * a.rgb.frame_pitch + (size_t)gy * a.rgb.row_pitch + (size_t)gxs * 3;
     if (PROBE & 2) {
         uint32_t acc = 0u;
 #pragma unroll
         for (int i = 0; i < 6; ++i)
             acc ^= ((uint32_t)out[4 * i] | ((uint32_t)out[4 * i + 1] << 8) | ((uint32_t)out[4 * i + 2] << 16) | ((uint32_t)out[4 * i + 3] << 24)) + (uint32_t)i;
-        if (acc == 0x5EEDF00Du) *a.rgb = (uint8_t)acc;   // (keeps the checksum alive; a valid address whatever the tile)
+        if (acc == 0x5EEDF00Du) *a.rgb.base = (uint8_t)acc;   // (keeps the checksum alive; a valid address whatever the tile)
     } else if (a.aligned && (!edge || gxs + 8 <= (int)d.w)) {
         uint32_t* p4 = (uint32_t*)p;
 #pragma unroll
@@ -1207,7 +1207,9 @@ static thread_local int tl_valu_probe = 0;
 void set_transform_probe(int mode) { tl_valu_probe = mode; }
 
 bool transform_tiles_eligible(const ChunkDims& d) {
-    if ((unsigned long long)d.pw * d.ph > (1ull << 30)) return false;   // 32-bit byte offsets inside one frame
+    // 32-bit offsets inside one padded frame of the chunk's own planes (band slots, symbols).  RGB addresses are 64-bit
+    // (RgbLayout), so a small region of a frame of any size qualifies on its own shape.
+    if ((unsigned long long)d.pw * d.ph > (1ull << 30)) return false;
     if (d.pw < 6 || d.ph < 6) return false;                             // reflect_idx: one reflection must cover the halo
     if ((unsigned long long)((d.pw + I_TW - 1) / I_TW) * ((d.ph + I_TH - 1) / I_TH) * d.pf > 0x7FFFFFF0ull) return false;
     return true;
@@ -1269,7 +1271,7 @@ static void fwd_t_launch(const FwdTm& ta, hipStream_t st) {
     hipLaunchKernelGGL((fwd_t_kernel<NS, STEP1, PROBE>), dim3(3u * ta.b.units_per_ch), dim3(256), 0, st, ta);
 }
 
-bool launch_forward_transform(const uint8_t* d_rgb, const ChunkDims& d, int wavelet, int32_t step,
+bool launch_forward_transform(const RgbLayout& rgb, const ChunkDims& d, int wavelet, int32_t step,
                               void* d_scratch, uint8_t* d_sym, uint32_t* d_hist, hipStream_t st) {
     if (step < 1 || step > 64) return false;
     if (!transform_tiles_eligible(d)) return false;
@@ -1290,8 +1292,8 @@ bool launch_forward_transform(const uint8_t* d_rgb, const ChunkDims& d, int wave
         const int by0 = band * bp.tpb, nby = std::min(bp.tpb, bp.tiles_y - by0);
         const int y0 = by0 * F_TH, rows = (int)std::min<uint64_t>((uint64_t)(by0 + nby) * F_TH, d.ph) - y0;
         FwdXy xa{};
-        xa.rgb = d_rgb; xa.mid = (int16_t*)d_scratch; xa.d = d; xa.cf = cf;
-        xa.aligned = (d.w % 4 == 0) && ((((uintptr_t)d_rgb) & 3u) == 0u);
+        xa.rgb = rgb; xa.mid = (int16_t*)d_scratch; xa.d = d; xa.cf = cf;
+        xa.aligned = rgb_dword_aligned(rgb);
         xa.bt = BandTiles{(int)nx, by0, nby, 1, (int)ix1, 1, (int)iy1};
         xa.y0 = y0; xa.rows = rows;
         FwdTm ta{};
@@ -1322,7 +1324,7 @@ static void inv_band_launch(const InvTm& ta, const InvXy& xa, hipStream_t st) {
 }
 
 bool launch_inverse_transform(const uint8_t* d_sym, const ChunkDims& d, int wavelet, const int32_t step[3],
-                              bool exact, bool mid16, bool lds16, void* d_scratch, uint8_t* d_rgb, hipStream_t st) {
+                              bool exact, bool mid16, bool lds16, void* d_scratch, const RgbLayout& rgb, hipStream_t st) {
     if (!transform_tiles_eligible(d)) return false;
     const LiftSteps ls = lift_steps(wavelet);
     // mid16: the host proved every value after the inverse temporal pass fits i16 (then exact is false too);
@@ -1356,8 +1358,8 @@ bool launch_inverse_transform(const uint8_t* d_sym, const ChunkDims& d, int wave
         ta.sym = d_sym; ta.mid = d_scratch; ta.cf = cf; ta.step[0] = step[0]; ta.step[1] = step[1]; ta.step[2] = step[2]; ta.nf = d.f;
         ta.b = make_band_t(d, 2u * (uint32_t)rows_l * pw, (uint32_t)rows_l * pw, (uint32_t)L0 * pw, (uint32_t)(hh + L0) * pw);
         InvXy xa{};
-        xa.mid = d_scratch; xa.rgb = d_rgb; xa.d = d; xa.cf = cf;
-        xa.aligned = (d.w % 4 == 0) && ((((uintptr_t)d_rgb) & 3u) == 0u);
+        xa.mid = d_scratch; xa.rgb = rgb; xa.d = d; xa.cf = cf;
+        xa.aligned = rgb_dword_aligned(rgb);
         xa.bt = BandTiles{(int)nx, by0, nby, 1, (int)ix1, 1, (int)iy1};
         xa.L0 = L0; xa.rows_l = rows_l;
         if (probe) {

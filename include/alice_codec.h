@@ -155,6 +155,20 @@ int alice_codec_batch_pack_alc(AliceBatch *batch, const uint64_t *sizes, void *d
  * RGB-sized buffer per chunk in flight.  Synchronises once to read headers. */
 int alice_codec_batch_decode(AliceBatch *batch, const void *d_alc, uint64_t alc_stride, void *d_rgb_out,
                              void *hip_stream);
+/* Region encode / decode (the hybrid flow of src/segment.rs: only the person's box is coded).
+ * Chunk i of the batch is frames [i*frames, (i+1)*frames) of d_frames (frame_width x frame_height interleaved RGB,
+ * tightly packed), cropped to the batch's width x height at origin (origins[2i], origins[2i+1]) in pixels.  The .alc of
+ * chunk i is byte-identical to alice_codec_encode64 of crop_to_bbox of those frames (src/segment.rs:269-281).
+ * origins: host array of 2*n_chunks u32, copied before return.  A region not inside the frame is
+ * ALICE_ERR_INVALID_DIMENSIONS and nothing is queued (the reference's crop skips such rows instead).
+ * The transforms read the rectangles in place; d_frames must stay valid until alice_codec_batch_encode_finish. */
+int alice_codec_batch_encode_regions(AliceBatch *batch, const void *d_frames, uint32_t frame_width,
+                                     uint32_t frame_height, const uint32_t *origins, void *hip_stream);
+/* Decodes chunk i and writes its pixels into that rectangle of d_frames_out (paste_from_bbox, :284-297).
+ * Bytes outside the rectangles are not written.  alice_codec_batch_rgb_ptr then gives each rectangle's first pixel. */
+int alice_codec_batch_decode_regions(AliceBatch *batch, const void *d_alc, uint64_t alc_stride, void *d_frames_out,
+                                     uint32_t frame_width, uint32_t frame_height, const uint32_t *origins,
+                                     void *hip_stream);
 const void *alice_codec_batch_rgb_ptr(const AliceBatch *batch, uint32_t chunk); /* device pointer, see above */
 int alice_codec_batch_decode_finish(AliceBatch *batch);
 /* per-stage device times of the last encode+finish / decode+finish, measured with HIP events on the
