@@ -11,6 +11,7 @@ batch from the free HBM: one rANS chain is one wavefront, and what bounds the ch
 
     python bench.py --gpus 1 --steps 2 --warmup 1
     python bench.py --gpus 1 --steps 2 --warmup 1 --dump-outputs DIR   # + a fixed sample of the last step's outputs as .npy
+    python bench.py --gpus 1 --steps 2 --warmup 1 --full               # + the oracle check, CPU baseline and host-call rates
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -18,8 +19,13 @@ Prints ONE JSON line on rank 0.  `value` = 2 * pixels / time (each pixel is enco
 once per step), whole job.  `roofline` describes the HBM-bound kernels of the path (the forward
 transform, RGB -> u8 symbols, 6 algorithmic bytes per pixel); the serial single-stream rANS chains
 that dominate wall time are latency-bound and are reported separately under `entropy_chain`.
-`cpu_baseline` is the CPU oracle (a scalar port of the single-threaded reference; the Rust crate
-cannot be built here) timed on this host on a bounded sample of the same input."""
+
+A plain run does only what the headline needs: set up, warm up, time the steps, dump if asked, print.
+`--full` adds what takes a minute or more of its own after the timed steps: the check of the batch
+against the CPU oracle with `cpu_baseline` (the oracle, a scalar port of the single-threaded
+reference, timed on this host on chunk 0 of the same input) and `host_api` (the drop-in host calls
+from 1, 8 and 64 threads).  The metric string is the same in every run that passes; `batch_bit_exact` says
+whether this run checked the batch (null: it did not)."""
 from __future__ import annotations
 
 import argparse
@@ -275,14 +281,17 @@ def parse_args(argv=None):
     ap.add_argument("--quality", type=int, default=80)
     ap.add_argument("--separate-output", action="store_true",
                     help="decode into a caller-owned RGB buffer instead of the batch's own storage (one more RGB-sized buffer per chunk)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also check the batch against the CPU oracle and time the CPU baseline "
+                         "(cpu_baseline), and measure the drop-in host calls (host_api); a plain run does neither")
     ap.add_argument("--no-verify", action="store_true",
-                    help="skip the oracle check of the batch and the CPU baseline (the line then does not say bit-exact)")
+                    help="with --full: skip the oracle check of the batch and the CPU baseline (batch_bit_exact is then null)")
     ap.add_argument("--gather-sink", choices=["device", "host"], default="device",
                     help="N > 1: what rank 0 does with the .alc bytes the gather delivers: 'device' adds them to a checksum on the "
                          "GPU (outputs stay in HBM, as the inputs are: no PCIe inside `value`); 'host' also copies every chunk "
                          "on to pinned host memory (8 GPUs x 337 chunks x 0.11 GB = 296 GB per step over rank 0's one PCIe link)")
     ap.add_argument("--no-host-api", action="store_true",
-                    help="skip the drop-in host-call measurement (T host threads through alice_codec_encode64 / decode64)")
+                    help="with --full: skip the drop-in host-call measurement (T host threads through alice_codec_encode64 / decode64)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write a fixed seeded sample of what the last step computed (.alc bytes and "
                          "decoded RGB of rank 0's chunks) as DIR/<name>.npy, float32 / float64, at most 64 MB")
@@ -292,6 +301,21 @@ def parse_args(argv=None):
     if args.warmup < 0:
         ap.error(f"--warmup {args.warmup}: must not be negative")
     return args
+
+
+def extras(args, rank: int, world: int) -> tuple:
+    """(check the batch against the CPU oracle and time cpu_baseline, measure host_api) after the timed steps: only with
+    --full.  The host calls need the device memory the batch holds, so they run on rank 0 of a one-GPU run only.  Pure."""
+    return (args.full and not args.no_verify,
+            args.full and not args.no_host_api and rank == 0 and world == 1)
+
+
+def metric_name(wavelet: str, quality: int, bit_exact) -> str:
+    """The result line's `metric`, named as BASELINE.json names it and the same in every run that passes, plain or
+    --full.  Whether this run checked the batch is `batch_bit_exact` (None: not checked here); a check that found a
+    difference (bit_exact False) renames the metric, and the process then exits non-zero.  Pure."""
+    what = "CDF9/7 q=80" if (wavelet, quality) == ("cdf97", 80) else f"{wavelet} q={quality}"
+    return f"Mpixels/s encode+decode, 1080p x 64 {what}" + ("; NOT bit-exact vs CPU" if bit_exact is False else "; bit-exact vs CPU")
 
 
 # ---- N ranks from one command ------------------------------------------------------------------------------------
@@ -555,9 +579,10 @@ def main(argv=None) -> None:
               f"to {dumped['dir']}", file=sys.stderr)
 
     # ---- what the timed steps left in the batch, against the oracle: first and last chunk, all 64 frames, every rank
+    verify, measure_host_api = extras(args, rank, world)
     verdict = None
     bit_exact = None
-    if not args.no_verify:
+    if verify:
         def fetch(i):
             alc = multi.DeviceView(batch.alc_ptr(i), int(sizes[i])).tensor(dev).cpu().numpy().tobytes()
             if out is not None:
@@ -574,7 +599,7 @@ def main(argv=None) -> None:
     # ---- the drop-in host calls, measured the way a caller of the reference would use them (rank 0 of a one-GPU run
     # only; the batch goes first: the calls need the device memory)
     host_api = None
-    if rank == 0 and world == 1 and not args.no_host_api:
+    if measure_host_api:
         chunks_per_gpu_used = B
         del batch
         del rgb
@@ -595,10 +620,8 @@ def main(argv=None) -> None:
         dec_chain_s = ms["rans_decode"] / 1e3
         payload_bpp = float(sizes.sum() - 3138 * B) / (B * px_chunk)
         headline = (args.wavelet, QUALITY) == ("cdf97", 80)
-        tail = "; bit-exact vs CPU" if bit_exact else ("; NOT bit-exact vs CPU" if bit_exact is False else "; not checked against the CPU in this run")
         result = {
-            "metric": ("Mpixels/s encode+decode, 1080p x 64 CDF9/7 q=80" if headline
-                       else f"Mpixels/s encode+decode, 1080p x 64 {args.wavelet} q={QUALITY}") + tail,
+            "metric": metric_name(args.wavelet, QUALITY, bit_exact),
             "value": round(value, 2), "unit": "Mpix/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(elapsed / args.steps * 1e3, 2), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "int32", "data": "synthetic",

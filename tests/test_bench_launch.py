@@ -92,6 +92,31 @@ def test_dump_plan_is_fixed_and_within_bounds():
     assert bench.dump_nbytes(1) < bench.dump_nbytes(337)
 
 
+def test_plain_run_does_only_the_headline():
+    """The oracle check, the CPU baseline and the host-call measurement run after the timed steps only with --full."""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse_args([]).full is False
+    assert bench.extras(bench.parse_args(["--steps", "20", "--warmup", "5"]), 0, 1) == (False, False)
+    assert bench.extras(bench.parse_args(["--dump-outputs", "d"]), 0, 1) == (False, False)
+    assert bench.extras(bench.parse_args(["--full"]), 0, 1) == (True, True)
+    assert bench.extras(bench.parse_args(["--full", "--no-verify"]), 0, 1) == (False, True)
+    assert bench.extras(bench.parse_args(["--full", "--no-host-api"]), 0, 1) == (True, False)
+    assert bench.extras(bench.parse_args(["--full"]), 1, 2) == (True, False)   # every rank checks; host calls on 1 GPU only
+    assert bench.extras(bench.parse_args(["--full"]), 0, 2) == (True, False)
+
+
+def test_metric_is_the_same_in_plain_and_full_runs():
+    """A plain run (not checked) and a --full run that checked the batch report the same metric; a failed check does not."""
+    sys.path.insert(0, ROOT)
+    import bench
+    name = "Mpixels/s encode+decode, 1080p x 64 CDF9/7 q=80; bit-exact vs CPU"
+    assert bench.metric_name("cdf97", 80, None) == bench.metric_name("cdf97", 80, True) == name
+    assert bench.metric_name("cdf97", 80, False) == "Mpixels/s encode+decode, 1080p x 64 CDF9/7 q=80; NOT bit-exact vs CPU"
+    assert bench.metric_name("cdf53", 80, None) == bench.metric_name("cdf53", 80, True) == \
+        "Mpixels/s encode+decode, 1080p x 64 cdf53 q=80; bit-exact vs CPU"
+
+
 def test_steps_and_warmup_are_checked():
     sys.path.insert(0, ROOT)
     import bench
