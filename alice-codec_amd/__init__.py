@@ -232,6 +232,15 @@ def load_library() -> C.CDLL:
         "alice_codec_rle_bound": (C.c_uint64, [C.c_uint64]),
         "alice_codec_dev_rle_encode_mask": (C.c_int, [vp, C.c_uint64, vp, C.c_uint64, _u64p, vp]),
         "alice_codec_dev_extract_person_rgb": (C.c_int, [vp, C.c_uint32, C.c_uint32, _u32p, vp, vp, C.c_uint64, _u64p, vp]),
+        "alice_codec_predict_sizes": (C.c_int, [C.c_uint8, _u8p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _u64p, _u64p, _u8p]),
+        "alice_codec_encode_to_size": (vp, [C.c_uint8, _u8p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                            C.c_uint8, C.c_uint8, _u8p, _u8p]),
+        "alice_codec_dev_predict_sizes": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint8, _u64p, _u64p,
+                                                    _u8p, vp, vp]),
+        "alice_codec_test_rate_log_table": (None, [_u32p, _u32p, _u32p]),
+        "alice_codec_batch_predict_sizes": (C.c_int, [vp, vp, _u64p, _u64p, _u8p, vp]),
+        "alice_codec_batch_set_qualities": (C.c_int, [vp, _u8p]),
+        "alice_codec_batch_encode_to_budget": (C.c_int, [vp, vp, _u64p, C.c_uint8, C.c_uint8, _u8p, _u8p, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
@@ -403,6 +412,91 @@ class FrameEncoder:
         if not h:
             _raise_last()
         return EncodedChunk(h)
+
+
+# ---------------------------------------------------------------------------------------------
+# rate control: sizes at every quality before encoding, encodes to a byte budget
+# ---------------------------------------------------------------------------------------------
+
+from .rate_control import RateControlConfig, RateController, estimate_quality, budget_bytes_per_chunk  # noqa: E402
+
+RATE_BOUNDED, RATE_UNBOUNDED, RATE_DIVERGES = 0, 1, 2
+
+
+class SizePrediction:
+    """Predicted .alc lengths of a chunk at the 101 qualities: ``lo[q] <= len(chunk.to_bytes()) <= hi[q]`` wherever
+    ``status[q] == RATE_BOUNDED`` (otherwise lo = 0 and hi = 2^64 - 1).  Arrays of 101 entries, or (n_chunks, 101)."""
+
+    def __init__(self, lo: np.ndarray, hi: np.ndarray, status: np.ndarray):
+        self.lo, self.hi, self.status = lo, hi, status
+
+    def choose(self, budget: int, min_quality: int = 10, max_quality: int = 95) -> tuple:
+        """The budget rule of encode_to_size for one chunk: (quality, fits)."""
+        lo_q, hi_q = min(int(min_quality), 100), min(int(max_quality), 100)
+        for q in range(hi_q, lo_q - 1, -1):
+            if self.status[q] == RATE_BOUNDED and int(self.hi[q]) <= budget:
+                return q, True
+        return lo_q, False
+
+
+def _check_budget_args(budgets, min_quality, max_quality):
+    for q in (min_quality, max_quality):
+        if not 0 <= int(q) <= 255:
+            raise ValueError(f"quality must fit a u8 (0..255), got {q}")
+    for b in budgets:
+        if not 0 <= int(b) < (1 << 64):
+            raise ValueError(f"a byte budget must fit a u64 (0 .. 2^64 - 1), got {b}")
+
+
+def _dims_u32(*vals):
+    for v in vals:
+        if not 0 <= v <= 0xFFFFFFFF:
+            raise CodecError(3, "dimension out of u32 range")
+
+
+def predict_sizes(rgb_frames, width: int, height: int, frames: int,
+                  wavelet_type: WaveletType = WaveletType.Cdf53) -> SizePrediction:
+    """The size bracket of FrameEncoder.with_wavelet(q, wavelet_type).encode(...) at every quality q, from one forward
+    transform on the GPU (no entropy coding)."""
+    lib = load_library()
+    r = _as_u8(rgb_frames)
+    _dims_u32(width, height, frames)
+    lo = np.zeros(101, np.uint64); hi = np.zeros(101, np.uint64); st = np.zeros(101, np.uint8)
+    ptr = _p(r, _u8p) if r.size else C.cast(C.c_char_p(b""), _u8p)
+    _check(lib.alice_codec_predict_sizes(int(wavelet_type), ptr, r.size, width, height, frames,
+                                         _p(lo, _u64p), _p(hi, _u64p), _p(st, _u8p)))
+    return SizePrediction(lo, hi, st)
+
+
+def predict_sizes_device(d_rgb_ptr: int, width: int, height: int, frames: int, n_chunks: int,
+                         wavelet_type: WaveletType = WaveletType.Cdf53, d_step_hist_ptr: int | None = None,
+                         stream: int = 0) -> SizePrediction:
+    """n_chunks packed chunks at a device pointer: arrays of shape (n_chunks, 101).  d_step_hist_ptr (optional, device,
+    n_chunks * 64 * 3 * 256 u32) receives the symbol histograms at every quantiser step."""
+    lib = load_library()
+    _dims_u32(width, height, frames, n_chunks)
+    lo = np.zeros((max(n_chunks, 1), 101), np.uint64); hi = np.zeros_like(lo); st = np.zeros(lo.shape, np.uint8)
+    _check(lib.alice_codec_dev_predict_sizes(d_rgb_ptr, width, height, frames, n_chunks, int(wavelet_type), _p(lo, _u64p),
+                                             _p(hi, _u64p), _p(st, _u8p), d_step_hist_ptr, stream))
+    return SizePrediction(lo[:n_chunks], hi[:n_chunks], st[:n_chunks])
+
+
+def encode_to_size(rgb_frames, width: int, height: int, frames: int, max_bytes: int,
+                   wavelet_type: WaveletType = WaveletType.Cdf53, min_quality: int = 10, max_quality: int = 95) -> tuple:
+    """Encodes one chunk once, at the highest quality in [min_quality, max_quality] whose predicted .alc length is
+    guaranteed to fit max_bytes.  Returns (EncodedChunk, quality, fits); fits is False when not even min_quality is
+    guaranteed to fit (the chunk is then encoded at min_quality)."""
+    lib = load_library()
+    r = _as_u8(rgb_frames)
+    _dims_u32(width, height, frames)
+    _check_budget_args([max_bytes], min_quality, max_quality)
+    chosen = C.c_uint8(0); fits = C.c_uint8(0)
+    ptr = _p(r, _u8p) if r.size else C.cast(C.c_char_p(b""), _u8p)
+    h = lib.alice_codec_encode_to_size(int(wavelet_type), ptr, r.size, width, height, frames, int(max_bytes),
+                                       int(min_quality), int(max_quality), C.byref(chosen), C.byref(fits))
+    if not h:
+        _raise_last()
+    return EncodedChunk(h), int(chosen.value), bool(fits.value)
 
 
 def plan_devices(n_chunks: int, devices) -> list:
@@ -951,6 +1045,37 @@ class Batch:
 
     def encode(self, d_rgb_ptr: int, stream: int = 0) -> None:
         _check(load_library().alice_codec_batch_encode(self._h, d_rgb_ptr, stream))
+
+    def predict_sizes(self, d_rgb_ptr: int, stream: int = 0) -> "SizePrediction":
+        """The size bracket of every chunk at every quality: arrays of shape (n_chunks, 101) (see predict_sizes)."""
+        n = self.n_chunks
+        lo = np.zeros((n, 101), np.uint64); hi = np.zeros_like(lo); st = np.zeros(lo.shape, np.uint8)
+        _check(load_library().alice_codec_batch_predict_sizes(self._h, d_rgb_ptr, _p(lo, _u64p), _p(hi, _u64p), _p(st, _u8p), stream))
+        return SizePrediction(lo, hi, st)
+
+    def set_qualities(self, qualities=None) -> None:
+        """One quality per chunk for the next encodes; None: the batch's own quality for every chunk again."""
+        if qualities is None:
+            _check(load_library().alice_codec_batch_set_qualities(self._h, None))
+            return
+        q = np.ascontiguousarray(qualities, np.int64).reshape(-1)
+        if q.size != self.n_chunks or q.min() < 0 or q.max() > 255:
+            raise ValueError(f"need {self.n_chunks} qualities in 0..255")
+        q8 = q.astype(np.uint8)
+        _check(load_library().alice_codec_batch_set_qualities(self._h, _p(q8, _u8p)))
+
+    def encode_to_budget(self, d_rgb_ptr: int, budgets, min_quality: int = 10, max_quality: int = 95, stream: int = 0) -> tuple:
+        """Each chunk once, at the highest quality whose predicted .alc length fits its budget (finish with
+        encode_finish).  Returns (chosen qualities, fits) as numpy arrays; the chosen qualities stay set."""
+        b = [int(x) for x in np.asarray(budgets, dtype=object).reshape(-1)]
+        if len(b) != self.n_chunks:
+            raise ValueError(f"need {self.n_chunks} budgets")
+        _check_budget_args(b, min_quality, max_quality)
+        bb = np.array(b, np.uint64)
+        chosen = np.zeros(self.n_chunks, np.uint8); fits = np.zeros(self.n_chunks, np.uint8)
+        _check(load_library().alice_codec_batch_encode_to_budget(self._h, d_rgb_ptr, _p(bb, _u64p), int(min_quality),
+                                                                 int(max_quality), _p(chosen, _u8p), _p(fits, _u8p), stream))
+        return chosen, fits.astype(bool)
 
     def encode_finish(self) -> np.ndarray:
         sizes = np.zeros(self.n_chunks, np.uint64)

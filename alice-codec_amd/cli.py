@@ -12,7 +12,8 @@ import sys
 
 import numpy as np
 
-from . import DEFAULT_CHUNK_SIZE, CodecError, EncodedChunk, FrameDecoder, FrameEncoder, WaveletType, encode_many
+from . import (DEFAULT_CHUNK_SIZE, CodecError, EncodedChunk, FrameDecoder, FrameEncoder, WaveletType, budget_bytes_per_chunk,
+               encode_many, encode_to_size)
 
 WAVELETS = {"cdf53": WaveletType.Cdf53, "cdf97": WaveletType.Cdf97, "haar": WaveletType.Haar}
 WAVELET_NAMES = {WaveletType.Cdf53: "CDF 5/3", WaveletType.Cdf97: "CDF 9/7", WaveletType.Haar: "Haar"}
@@ -27,13 +28,21 @@ def parse_wavelet(s: str) -> WaveletType:
 def cmd_encode(a) -> None:
     wt = parse_wavelet(a.wavelet)
     rgb = np.fromfile(a.input, dtype=np.uint8)
-    chunk = FrameEncoder.with_wavelet(a.quality, wt).encode(rgb, a.width, a.height, a.frames)
+    quality = a.quality
+    if a.max_bytes is not None:
+        chunk, quality, fits = encode_to_size(rgb, a.width, a.height, a.frames, a.max_bytes, wt, a.min_quality, a.max_quality)
+        print(f"chosen quality: {quality}", file=sys.stderr)
+        if not fits:
+            print(f"warning: not even --min-quality {a.min_quality} is guaranteed to fit {a.max_bytes} bytes; "
+                  f"encoded at {quality}", file=sys.stderr)
+    else:
+        chunk = FrameEncoder.with_wavelet(a.quality, wt).encode(rgb, a.width, a.height, a.frames)
     data = chunk.to_bytes()
     with open(a.output, "wb") as f:
         f.write(data)
     ratio = 0.0 if rgb.size == 0 else len(data) / rgb.size
     print(f"encoded {a.width}x{a.height}x{a.frames} ({rgb.size} bytes) -> {len(data)} bytes "
-          f"({ratio * 100:.1f}% ratio, quality={a.quality}, wavelet={a.wavelet})", file=sys.stderr)
+          f"({ratio * 100:.1f}% ratio, quality={quality}, wavelet={a.wavelet})", file=sys.stderr)
 
 
 def cmd_encode_chunks(a) -> None:
@@ -43,6 +52,9 @@ def cmd_encode_chunks(a) -> None:
     if frame_bytes == 0 or rgb.size % frame_bytes:
         raise ValueError("input size is not a whole number of frames")
     n_frames = rgb.size // frame_bytes
+    if a.kbps is not None:
+        _encode_chunks_to_rate(a, wt, rgb, frame_bytes, n_frames)
+        return
     enc = FrameEncoder.with_wavelet(a.quality, wt)
     starts = list(range(0, n_frames, a.chunk))
     k = 0
@@ -59,6 +71,31 @@ def cmd_encode_chunks(a) -> None:
             print(f"chunk {k}: frames {start}..{start + f - 1} -> {len(data)} bytes", file=sys.stderr)
             k += 1
         i += len(group)
+
+
+def _encode_chunks_to_rate(a, wt, rgb, frame_bytes, n_frames) -> None:
+    """--kbps / --fps: every chunk gets floor(target_bits_per_frame * frames / 8) bytes (RateController's per-frame target),
+    encoded by encode_to_size on --in-flight host threads, whose chains merge on the device."""
+    from concurrent.futures import ThreadPoolExecutor
+    starts = list(range(0, n_frames, a.chunk))
+
+    def one(k):
+        s0 = starts[k]
+        f = min(a.chunk, n_frames - s0)
+        budget = budget_bytes_per_chunk(a.kbps, a.fps, f)
+        part = np.ascontiguousarray(rgb[s0 * frame_bytes:(s0 + f) * frame_bytes])
+        chunk, q, fits = encode_to_size(part, a.width, a.height, f, budget, wt, a.min_quality, a.max_quality)
+        data = chunk.to_bytes()
+        with open(f"{a.output}.{k:05d}.alc", "wb") as out:
+            out.write(data)
+        return s0, f, budget, q, fits, len(data)
+
+    with ThreadPoolExecutor(max_workers=max(1, a.in_flight)) as ex:
+        for k, (s0, f, budget, q, fits, n) in enumerate(ex.map(one, range(len(starts)))):
+            print(f"chunk {k}: frames {s0}..{s0 + f - 1} -> {n} bytes (budget {budget}), chosen quality: {q}", file=sys.stderr)
+            if not fits:
+                print(f"warning: chunk {k}: not even --min-quality {a.min_quality} is guaranteed to fit {budget} bytes",
+                      file=sys.stderr)
 
 
 def cmd_decode(a) -> None:
@@ -110,6 +147,13 @@ def main(argv=None) -> int:
             e.add_argument("--in-flight", type=int, default=16, help="chunks encoded per call (GPU memory: about 2.4x the raw size of a chunk each)")
         e.add_argument("-q", "--quality", type=_u8, default=90)
         e.add_argument("-w", "--wavelet", default="cdf53")
+        if name == "encode":
+            e.add_argument("--max-bytes", type=int, default=None, help="encode at the highest quality that fits this many bytes")
+        else:
+            e.add_argument("--kbps", type=int, default=None, help="target bitrate: a byte budget per chunk (with --fps)")
+            e.add_argument("--fps", type=float, default=30.0)
+        e.add_argument("--min-quality", type=_u8, default=10)
+        e.add_argument("--max-quality", type=_u8, default=95)
     d = sub.add_parser("decode")
     d.add_argument("input")
     d.add_argument("-o", "--output", required=True)

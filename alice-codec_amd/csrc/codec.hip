@@ -806,29 +806,117 @@ uint64_t estimate_stream_cap(const uint32_t* hist, uint64_t n) {
 
 uint64_t worst_cap(const ChunkDims& d) { return round_up(2 * d.padded + 4 + 64 + 64, 256); }  // +64: dummy-store guard band
 
-// The forward transform of one chunk: the tile kernels where they cover the shape (w.scratch holds their band slots), else
-// exact reference arithmetic on caller-shaped data (chunks of more than 64 padded frames, say).
-int forward_chunk(const RgbLayout& rgb, const ChunkDims& d, int wavelet, int32_t step, EncodeWork& w,
-                  uint8_t* d_sym, uint32_t* d_hist, hipStream_t st) {
-    if (w.scratch.p && launch_forward_transform(rgb, d, wavelet, step, w.scratch.p, d_sym, d_hist, st)) return kOk;
+// The generic path's forward transform of one chunk: exact reference arithmetic on caller-shaped data (chunks of more than 64
+// padded frames, say); per_channel(c, vol) gets each channel's coefficient volume (d.padded i32, followed by as much room).
+template <typename Fn>
+int generic_forward(const RgbLayout& rgb, const ChunkDims& d, int wavelet, EncodeWork& w, hipStream_t st, Fn per_channel) {
     if (!w.planes.p) TRY(w.planes.alloc(3 * d.n_pixels * sizeof(int16_t)));
     if (!w.tmp.p) TRY(w.tmp.alloc(d.padded * sizeof(int32_t)));
     if (!w.gen.p) TRY(w.gen.alloc(2 * d.padded * sizeof(int32_t)));
     int16_t* pl = w.planes.as<int16_t>();
     launch_rgb_to_ycocg(rgb, d, pl, pl + d.n_pixels, pl + 2 * d.n_pixels, st);
     int32_t* vol = w.gen.as<int32_t>();
-    int32_t* qb = vol + d.padded;
     const uint64_t W = d.pw, H = d.ph, D = d.pf;
     for (int c = 0; c < 3; ++c) {
         launch_pad_channel(pl + (size_t)c * d.n_pixels, d, vol, st);
         launch_wavelet_axis(vol, w.tmp.as<int32_t>(), W, 1, D * H, W, 1, 0, wavelet, false, st);
         launch_wavelet_axis(vol, w.tmp.as<int32_t>(), H, W, D, W * H, W, 1, wavelet, false, st);
         launch_wavelet_axis(vol, w.tmp.as<int32_t>(), D, W * H, 1, 0, W * H, 1, wavelet, false, st);
+        per_channel(c, vol);
+    }
+    return kOk;
+}
+
+// The forward transform of one chunk: the tile kernels where they cover the shape (w.scratch holds their band slots), else
+// the generic path.
+int forward_chunk(const RgbLayout& rgb, const ChunkDims& d, int wavelet, int32_t step, EncodeWork& w,
+                  uint8_t* d_sym, uint32_t* d_hist, hipStream_t st) {
+    if (w.scratch.p && launch_forward_transform(rgb, d, wavelet, step, w.scratch.p, d_sym, d_hist, st)) return kOk;
+    return generic_forward(rgb, d, wavelet, w, st, [&](int c, int32_t* vol) {
+        int32_t* qb = vol + d.padded;
         launch_quantize(vol, qb, d.padded, step, step, st);
         launch_to_symbols(qb, d_sym + (size_t)c * d.padded, d.padded, st);
         launch_histogram(d_sym + (size_t)c * d.padded, d.padded, d_hist + c * 256, st);
+    });
+}
+
+// ---- rate prediction (rate.hip) ----
+constexpr int kQualities = 101;
+
+// Coefficient bins of one chunk (bins: [3][4096], zeroed; oor: the chunk's out-of-range counter, zeroed).
+int coef_hist_chunk(const RgbLayout& rgb, const ChunkDims& d, int wavelet, EncodeWork& w, uint32_t* d_bins, uint32_t* d_oor,
+                    hipStream_t st) {
+    if (w.scratch.p && launch_forward_coef_hist(rgb, d, wavelet, w.scratch.p, d_bins, d_oor, st)) return kOk;
+    return generic_forward(rgb, d, wavelet, w, st, [&](int c, int32_t* vol) { launch_coef_hist(vol, d.padded, d_bins + (size_t)c * 4096, d_oor, st); });
+}
+
+// Stream-length brackets of n chunks at every step: out[(chunk * 64 + step - 1) * 3 + channel].  w: the chunk shape's
+// forward scratch (EncodeWork of one chunk).  d_step_hist: [chunk][step - 1][channel][256] u32 on the device, or null.
+// A chunk with coefficients outside the value table's range (never for 8-bit RGB at the default radius) gets its step
+// histograms from the real forward pass at each of the 64 steps instead of the fold.  Returns after the stream has drained.
+int predict_chunks(const RgbLayout* rgb, uint32_t n, const ChunkDims& d, int wavelet, EncodeWork& w, hipStream_t st,
+                   uint32_t* d_step_hist, std::vector<RateChannel>& out) {
+    const size_t per_chunk = (size_t)64 * 3;
+    DevBuf bins, oor, own_hist, res, logt, fsym;
+    TRY(bins.alloc((size_t)n * 3 * 4096 * sizeof(uint32_t)));
+    TRY(oor.alloc((size_t)n * sizeof(uint32_t)));
+    TRY(res.alloc((size_t)n * per_chunk * sizeof(RateChannel)));
+    TRY(logt.alloc(2 * (kProbScale + 1) * sizeof(uint32_t)));
+    if (!d_step_hist) { TRY(own_hist.alloc((size_t)n * per_chunk * 256 * sizeof(uint32_t))); d_step_hist = own_hist.as<uint32_t>(); }
+    const RateLogTable& t = rate_log_table();
+    HIP_TRY(hipMemcpyAsync(logt.p, t.lo, sizeof(t.lo), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(logt.as<uint32_t>() + (kProbScale + 1), t.hi, sizeof(t.hi), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(bins.p, 0, (size_t)n * 3 * 4096 * sizeof(uint32_t), st));
+    HIP_TRY(hipMemsetAsync(oor.p, 0, (size_t)n * sizeof(uint32_t), st));
+    for (uint32_t b = 0; b < n; ++b)
+        TRY(coef_hist_chunk(rgb[b], d, wavelet, w, bins.as<uint32_t>() + (size_t)b * 3 * 4096, oor.as<uint32_t>() + b, st));
+    launch_rate_fold(bins.as<uint32_t>(), oor.as<uint32_t>(), n, d_step_hist, st);
+    std::vector<uint32_t> h_oor(n);
+    HIP_TRY(hipMemcpyAsync(h_oor.data(), oor.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (uint32_t b = 0; b < n; ++b) {
+        if (!h_oor[b]) continue;
+        if (!fsym.p) TRY(fsym.alloc(3 * d.padded));   // (not w.sym: a batch keeps its decoded pixels there)
+        for (int32_t step = 1; step <= 64; ++step) {
+            uint32_t* h = d_step_hist + ((size_t)b * 64 + (size_t)(step - 1)) * 3 * 256;
+            HIP_TRY(hipMemsetAsync(h, 0, 3 * 256 * sizeof(uint32_t), st));
+            TRY(forward_chunk(rgb[b], d, wavelet, step, w, fsym.as<uint8_t>(), h, st));
+        }
     }
+    launch_rate_cost(d_step_hist, logt.as<uint32_t>(), n, res.as<RateChannel>(), st);
+    HIP_TRY(hipGetLastError());
+    out.resize((size_t)n * per_chunk);
+    HIP_TRY(hipMemcpyAsync(out.data(), res.p, out.size() * sizeof(RateChannel), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return kOk;
+}
+
+// Whole-.alc brackets of one chunk at the 101 qualities from its 64 x 3 channel brackets: 3138 + the three streams, or
+// lo = 0, hi = UINT64_MAX and the worst channel status when a channel's table is not bounded.
+void rate_by_quality(const RateChannel* rc, uint64_t* lo, uint64_t* hi, uint8_t* status) {
+    for (int q = 0; q < kQualities; ++q) {
+        const RateChannel* c = rc + (size_t)(quality_to_step((uint8_t)q) - 1) * 3;
+        const uint32_t worst = std::max(c[0].status, std::max(c[1].status, c[2].status));
+        status[q] = (uint8_t)worst;
+        lo[q] = worst == kRateBounded ? kAlcHeaderBytes + c[0].lo + c[1].lo + c[2].lo : 0;
+        hi[q] = worst == kRateBounded ? kAlcHeaderBytes + c[0].hi + c[1].hi + c[2].hi : UINT64_MAX;
+    }
+}
+
+// An empty chunk (no pixels) is its header alone at every quality.
+void rate_of_empty_chunk(uint64_t* lo, uint64_t* hi, uint8_t* status) {
+    for (int q = 0; q < kQualities; ++q) { lo[q] = hi[q] = kAlcHeaderBytes; status[q] = (uint8_t)kRateBounded; }
+}
+
+// The budget rule: the largest quality in [min_q, max_q] whose prediction is bounded and whose upper bound fits the budget
+// (every quality is looked at: size need not fall with quality); min_q with *fits = 0 when none does.  Qualities above 100
+// act as 100.
+uint8_t choose_quality(const uint64_t* hi, const uint8_t* status, uint64_t budget, uint8_t min_q, uint8_t max_q, uint8_t* fits) {
+    min_q = std::min<uint8_t>(min_q, 100); max_q = std::min<uint8_t>(max_q, 100);
+    for (int q = max_q; q >= min_q; --q)
+        if (status[q] == kRateBounded && hi[q] <= budget) { *fits = 1; return (uint8_t)q; }
+    *fits = 0;
+    return min_q;
 }
 
 thread_local uint64_t tl_test_first_cap = 0;   // alice_codec_test_force_first_cap
@@ -859,8 +947,9 @@ struct StageEvents {
 //   kCapWorst    2 bytes per symbol, the bound of the format (the last resort: 3 x 2 x padded bytes per chunk).
 enum CapMode { kCapReuse = 0, kCapEstimate = 1, kCapWorst = 2 };
 // rgb[b]: where chunk b's pixels are (w.n_chunks layouts)
+// qualities: one per chunk (alice_codec_batch_set_qualities), or null for `quality` everywhere
 int encode_launch(const RgbLayout* rgb, EncodeWork& w, uint8_t quality, int wavelet, hipStream_t st,
-                  StageEvents* evs, CapMode mode = kCapReuse, HubTicket* hub = nullptr) {
+                  StageEvents* evs, CapMode mode = kCapReuse, HubTicket* hub = nullptr, const uint8_t* qualities = nullptr) {
     const ChunkDims& d = w.d;
     const int32_t step = quality_to_step(quality);
     const int B = w.n_chunks;
@@ -868,7 +957,8 @@ int encode_launch(const RgbLayout* rgb, EncodeWork& w, uint8_t quality, int wave
     if (evs) HIP_TRY(hipEventRecord(evs->ev[0], st));
     for (int b = 0; b < B; ++b) {
         uint8_t* sym = w.sym.as<uint8_t>() + (size_t)b * 3 * d.padded;
-        TRY(forward_chunk(rgb[b], d, wavelet, step, w, sym, w.hist.as<uint32_t>() + (size_t)b * 3 * 256, st));
+        TRY(forward_chunk(rgb[b], d, wavelet, qualities ? quality_to_step(qualities[b]) : step, w, sym,
+                          w.hist.as<uint32_t>() + (size_t)b * 3 * 256, st));
     }
     if (evs) HIP_TRY(hipEventRecord(evs->ev[1], st));
     const bool had_alc = w.alc.p != nullptr;
@@ -913,8 +1003,14 @@ int encode_launch(const RgbLayout* rgb, EncodeWork& w, uint8_t quality, int wave
                            w.cap[0], w.results.as<RansResult>(), 3 * B, st, w.alc_stride, kStreamHead, 0xFFFFFFFFu, w.cap[1], w.cap[2]);
     }
     if (evs) HIP_TRY(hipEventRecord(evs->ev[3], st));
-    launch_write_headers(w.alc.as<uint8_t>(), w.alc_stride, d, wavelet, step, w.hist.as<uint32_t>(),
-                         w.results.as<RansResult>(), w.sizes.as<unsigned long long>(), B, st);
+    if (!qualities)
+        launch_write_headers(w.alc.as<uint8_t>(), w.alc_stride, d, wavelet, step, w.hist.as<uint32_t>(),
+                             w.results.as<RansResult>(), w.sizes.as<unsigned long long>(), B, st);
+    else   // each chunk's header carries its own step
+        for (int b = 0; b < B; ++b)
+            launch_write_headers(w.alc.as<uint8_t>() + (size_t)b * w.alc_stride, w.alc_stride, d, wavelet, quality_to_step(qualities[b]),
+                                 w.hist.as<uint32_t>() + (size_t)b * 3 * 256, w.results.as<RansResult>() + 3 * b,
+                                 w.sizes.as<unsigned long long>() + b, 1, st);
     launch_compact_streams(w.alc.as<uint8_t>(), w.alc_stride, kStreamHead, w.cap, w.results.as<RansResult>(), B, st);
     if (evs) HIP_TRY(hipEventRecord(evs->ev[4], st));
     HIP_TRY(hipGetLastError());
@@ -951,9 +1047,9 @@ int encode_collect(EncodeWork& w, hipStream_t st, std::vector<RansResult>& res) 
 // The capacity ladder: encodes from `mode` on, one CapMode further after every overflow.  kCapWorst is the format's bound,
 // so a chain that overflows even there is an internal error.
 int encode_with_retry(const RgbLayout* rgb, EncodeWork& w, uint8_t quality, int wavelet, hipStream_t st, StageEvents* evs,
-                      CapMode mode, HubTicket* hub, std::vector<RansResult>& res) {
+                      CapMode mode, HubTicket* hub, std::vector<RansResult>& res, const uint8_t* qualities = nullptr) {
     for (int m = mode; m <= kCapWorst; ++m) {
-        TRY(encode_launch(rgb, w, quality, wavelet, st, evs, (CapMode)m, hub));
+        TRY(encode_launch(rgb, w, quality, wavelet, st, evs, (CapMode)m, hub, qualities));
         const int rc = encode_collect(w, st, res);
         if (rc != kOverflowed) return rc;
     }
@@ -1110,6 +1206,34 @@ uint32_t chunks_that_fit(const ChunkDims& d, uint32_t want) {
     return n >= (long double)want ? want : (uint32_t)n;
 }
 
+// The n_chunks encoded chunks of w (chain results res) as chunk objects: chunk i's object goes to slot(i) (left for the
+// caller to delete on error).  All headers with one strided copy, then the payloads straight into the objects, several at
+// a time.
+template <typename Slot>
+int chunks_to_host(EncodeWork& w, const std::vector<RansResult>& res, hipStream_t st, Slot slot) {
+    const uint32_t B = (uint32_t)w.n_chunks;
+    std::vector<uint8_t> hdr((size_t)B * kAlcHeaderBytes);
+    if (hipMemcpy2DAsync(hdr.data(), kAlcHeaderBytes, w.alc.p, w.alc_stride, kAlcHeaderBytes, B, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return fail(kDeviceError, "device to host copy failed");
+    return parallel_chunks(B, w.alc_stride >= (4u << 20) ? kCopyThreads : 1u, [&](uint32_t i) {
+        const uint64_t payload = res[3 * i].len + res[3 * i + 1].len + res[3 * i + 2].len;
+        EncodedChunk* c = slot(i) = new (std::nothrow) EncodedChunk();
+        if (!c) return fail(kOutOfMemory, "out of host memory");
+        uint64_t tot = 0;
+        if (parse_alc_header(hdr.data() + (size_t)i * kAlcHeaderBytes, kAlcHeaderBytes + payload, *c, &tot) != kOk || tot != payload)
+            return fail(kInternal, "device header/payload length mismatch");
+        c->data.resize((size_t)payload);
+        return copy_to_host(c->data.data(), w.alc.as<uint8_t>() + (size_t)i * w.alc_stride + kAlcHeaderBytes, (size_t)payload, st);
+    });
+}
+
+// The quality range of a budget call, after qualities above 100 have become 100.
+int check_quality_range(uint8_t min_q, uint8_t max_q) {
+    if (std::min<uint8_t>(min_q, 100) > std::min<uint8_t>(max_q, 100)) return fail(kInvalidDimensions, "min_quality > max_quality");
+    return kOk;
+}
+
 // Every whole-chunk encode from host memory: chunks k = slot, slot + step, ... below n_chunks of rgb (n_pixels * 3 bytes
 // each) on the calling thread's device, as many at a time as its memory holds, into out[k].  On error nothing is left in
 // out.  One chunk is the case n = 1 (parallel_chunks then runs its copies inline).
@@ -1141,22 +1265,7 @@ int encode_chunks_on_device(const FrameEncoder& enc, const uint8_t* rgb, const C
         std::vector<RgbLayout> layouts(B);
         for (uint32_t i = 0; i < B; ++i) layouts[i] = packed_rgb(d_rgb.as<uint8_t>() + (size_t)i * chunk_bytes, d);
         if (rc == kOk) rc = encode_with_retry(layouts.data(), w, enc.quality, enc.wavelet, st, nullptr, kCapReuse, &ticket, res);
-        if (rc != kOk) return undo(rc);
-        // all headers with one strided copy, then the payloads straight into the chunk objects, several at a time
-        std::vector<uint8_t> hdr((size_t)B * kAlcHeaderBytes);
-        if (hipMemcpy2DAsync(hdr.data(), kAlcHeaderBytes, w.alc.p, w.alc_stride, kAlcHeaderBytes, B, hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess)
-            return undo(fail(kDeviceError, "device to host copy failed"));
-        rc = parallel_chunks(B, w.alc_stride >= (4u << 20) ? kCopyThreads : 1u, [&](uint32_t i) {
-            const uint64_t payload = res[3 * i].len + res[3 * i + 1].len + res[3 * i + 2].len;
-            EncodedChunk* c = out[at(first + i)] = new (std::nothrow) EncodedChunk();   // (undo() deletes it)
-            if (!c) return fail(kOutOfMemory, "out of host memory");
-            uint64_t tot = 0;
-            if (parse_alc_header(hdr.data() + (size_t)i * kAlcHeaderBytes, kAlcHeaderBytes + payload, *c, &tot) != kOk || tot != payload)
-                return fail(kInternal, "device header/payload length mismatch");
-            c->data.resize((size_t)payload);
-            return copy_to_host(c->data.data(), w.alc.as<uint8_t>() + (size_t)i * w.alc_stride + kAlcHeaderBytes, (size_t)payload, st);
-        });
+        if (rc == kOk) rc = chunks_to_host(w, res, st, [&](uint32_t i) -> EncodedChunk*& { return out[at(first + i)]; });
         if (rc != kOk) return undo(rc);
     }
     return kOk;
@@ -1235,6 +1344,79 @@ int encode_host(const FrameEncoder& enc, const uint8_t* rgb, uint64_t rgb_len, u
     ChunkDims d{};
     TRY(validate_encode_many(&enc, rgb, rgb_len, width, height, frames, 1, out, &d));
     return encode_chunks_on_device(enc, rgb, d, out, 1);
+}
+
+// FrameEncoder::encode of one host chunk at the highest quality in [min_q, max_q] whose predicted size fits max_bytes (see
+// choose_quality): one upload, the prediction, one encode, on the hub's path like every whole-chunk host call.
+int encode_to_size_host(uint8_t wavelet, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height, uint32_t frames,
+                        uint64_t max_bytes, uint8_t min_q, uint8_t max_q, uint8_t* chosen, uint8_t* fits, EncodedChunk** out) {
+    uint64_t lo[kQualities], hi[kQualities];
+    uint8_t status[kQualities];
+    uint64_t n_pixels = 0;
+    TRY(checked_pixel_count(width, height, frames, &n_pixels));                 // src/pipeline.rs:388
+    if (n_pixels == 0) {                                                         // :391-412
+        if (rgb_len != 0) return fail(kInvalidBufferSize, "buffer size mismatch: expected 0, got " + std::to_string(rgb_len));
+        TRY(check_quality_range(min_q, max_q));
+        rate_of_empty_chunk(lo, hi, status);
+        *chosen = choose_quality(hi, status, max_bytes, min_q, max_q, fits);
+        *out = new (std::nothrow) EncodedChunk{width, height, frames, wavelet};
+        return *out ? kOk : fail(kOutOfMemory, "out of host memory");
+    }
+    const FrameEncoder enc{0, wavelet};
+    ChunkDims d{};
+    TRY(validate_encode_many(&enc, rgb, rgb_len, width, height, frames, 1, out, &d));
+    TRY(check_quality_range(min_q, max_q));
+    TRY(ensure_device());
+    HubTicket ticket;
+    TRY(ticket.open(encode_device_bytes(d, 1)));
+    const hipStream_t st = ticket.st;
+    DevBuf d_rgb;
+    EncodeWork w;
+    TRY(d_rgb.alloc(n_pixels * 3));
+    TRY(encode_work_alloc(w, d, 1));
+    HIP_TRY(hipMemcpyAsync(d_rgb.p, rgb, n_pixels * 3, hipMemcpyHostToDevice, st));
+    const RgbLayout layout = packed_rgb(d_rgb.as<uint8_t>(), d);
+    std::vector<RateChannel> rc;
+    TRY(predict_chunks(&layout, 1, d, wavelet, w, st, nullptr, rc));
+    rate_by_quality(rc.data(), lo, hi, status);
+    *chosen = choose_quality(hi, status, max_bytes, min_q, max_q, fits);
+    std::vector<RansResult> res;
+    TRY(encode_with_retry(&layout, w, *chosen, wavelet, st, nullptr, kCapReuse, &ticket, res));
+    const int r = chunks_to_host(w, res, st, [&](uint32_t) -> EncodedChunk*& { return *out; });
+    if (r != kOk) { delete *out; *out = nullptr; }
+    return r;
+}
+
+// The prediction of one host chunk (alice_codec_predict_sizes): one upload on a short stream of the hub; no chains, so the
+// call leaves the hub's gathering at once.
+int predict_sizes_host(uint8_t wavelet, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height, uint32_t frames,
+                       uint64_t* lo, uint64_t* hi, uint8_t* status) {
+    uint64_t n_pixels = 0;
+    TRY(checked_pixel_count(width, height, frames, &n_pixels));                 // src/pipeline.rs:388
+    if (n_pixels == 0) {                                                         // :391-412
+        if (rgb_len != 0) return fail(kInvalidBufferSize, "buffer size mismatch: expected 0, got " + std::to_string(rgb_len));
+        rate_of_empty_chunk(lo, hi, status);
+        return kOk;
+    }
+    const FrameEncoder enc{0, wavelet};
+    EncodedChunk* none = nullptr;
+    ChunkDims d{};
+    TRY(validate_encode_many(&enc, rgb, rgb_len, width, height, frames, 1, &none, &d));
+    TRY(ensure_device());
+    HubTicket ticket;
+    TRY(ticket.open(encode_device_bytes(d, 1)));
+    ticket.arrived();
+    DevBuf d_rgb;
+    EncodeWork w;
+    w.d = d; w.n_chunks = 1;
+    if (transform_tiles_eligible(d)) TRY(w.scratch.alloc(forward_scratch_bytes(d)));
+    TRY(d_rgb.alloc(n_pixels * 3));
+    HIP_TRY(hipMemcpyAsync(d_rgb.p, rgb, n_pixels * 3, hipMemcpyHostToDevice, ticket.st));
+    const RgbLayout layout = packed_rgb(d_rgb.as<uint8_t>(), d);
+    std::vector<RateChannel> rc;
+    TRY(predict_chunks(&layout, 1, d, wavelet, w, ticket.st, nullptr, rc));
+    rate_by_quality(rc.data(), lo, hi, status);
+    return kOk;
 }
 
 // A buffer the C ABI hands to the caller (released with free(): alice_codec_data_free64).  Large ones are 2 MiB aligned and
@@ -1397,6 +1579,8 @@ struct AliceBatch {
     StageEvents evs;
     hipStream_t enc_stream = nullptr, dec_stream = nullptr;
     std::vector<RgbLayout> last_rgb;   // where the last encode read each chunk (packed or a region): what a retry re-reads
+    std::vector<uint8_t> qualities;    // one per chunk (alice_codec_batch_set_qualities); empty: `quality` for every chunk
+    const uint8_t* chunk_qualities() const { return qualities.empty() ? nullptr : qualities.data(); }
     bool enc_timed = false, dec_timed = false;
     float stage_ms[6] = {0, 0, 0, 0, 0, 0};
 };
@@ -1433,7 +1617,8 @@ int batch_encode_layouts(AliceBatch* b, std::vector<RgbLayout>&& rgb, hipStream_
     b->enc_stream = st;
     b->enc_timed = false;
     b->last_rgb = std::move(rgb);
-    return encode_launch(b->last_rgb.data(), b->enc, b->quality, b->wavelet, b->enc_stream, &b->evs);
+    return encode_launch(b->last_rgb.data(), b->enc, b->quality, b->wavelet, b->enc_stream, &b->evs, kCapReuse, nullptr,
+                         b->chunk_qualities());
 }
 
 // rgb: one layout per chunk, or empty for the batch's own storage
@@ -1689,7 +1874,8 @@ int alice_codec_batch_encode_finish(AliceBatch* b, uint64_t* sizes) {
     // a chain outgrew its region: the capacities came from an earlier encode of other content (kCapReuse) -- size them
     // from this content's histograms and run again; should even that fall short (never observed), take the format's bound
     if (rc == kOverflowed && !b->last_rgb.empty())
-        rc = encode_with_retry(b->last_rgb.data(), b->enc, b->quality, b->wavelet, b->enc_stream, &b->evs, kCapEstimate, nullptr, res);
+        rc = encode_with_retry(b->last_rgb.data(), b->enc, b->quality, b->wavelet, b->enc_stream, &b->evs, kCapEstimate, nullptr, res,
+                               b->chunk_qualities());
     if (rc == kOverflowed) return fail(kInternal, "rANS output exceeded the worst-case capacity");   // (no encode to repeat)
     if (rc) return rc;
     for (int i = 0; i < 4; ++i) (void)hipEventElapsedTime(&b->stage_ms[i], b->evs.ev[i], b->evs.ev[i + 1]);
@@ -1698,6 +1884,42 @@ int alice_codec_batch_encode_finish(AliceBatch* b, uint64_t* sizes) {
         for (uint32_t i = 0; i < b->n_chunks; ++i)
             sizes[i] = (uint64_t)kAlcHeaderBytes + res[3 * i].len + res[3 * i + 1].len + res[3 * i + 2].len;
     return kOk;
+}
+int alice_codec_batch_predict_sizes(AliceBatch* b, const void* d_rgb, uint64_t* lo, uint64_t* hi, uint8_t* status, void* hip_stream) {
+    clear_error();
+    if (!b || !d_rgb || !lo || !hi || !status) return fail(kNullArgument, "null argument");
+    DeviceScope ds(b->device);
+    if (!ds.ok) return tl_err;
+    tl_scope_stream = nullptr;
+    std::vector<RgbLayout> rgb(b->n_chunks);
+    for (uint32_t i = 0; i < b->n_chunks; ++i) rgb[i] = packed_rgb((const uint8_t*)d_rgb + (size_t)i * b->d.n_pixels * 3, b->d);
+    std::vector<RateChannel> rc;
+    TRY(predict_chunks(rgb.data(), b->n_chunks, b->d, b->wavelet, b->enc, (hipStream_t)hip_stream, nullptr, rc));
+    for (uint32_t i = 0; i < b->n_chunks; ++i)
+        rate_by_quality(rc.data() + (size_t)i * 192, lo + (size_t)i * kQualities, hi + (size_t)i * kQualities, status + (size_t)i * kQualities);
+    return kOk;
+}
+int alice_codec_batch_set_qualities(AliceBatch* b, const uint8_t* qualities) {
+    clear_error();
+    if (!b) return fail(kNullArgument, "null argument");
+    if (qualities) b->qualities.assign(qualities, qualities + b->n_chunks);
+    else b->qualities.clear();
+    return kOk;
+}
+int alice_codec_batch_encode_to_budget(AliceBatch* b, const void* d_rgb, const uint64_t* budgets, uint8_t min_q, uint8_t max_q,
+                                       uint8_t* chosen, uint8_t* fits, void* hip_stream) {
+    clear_error();
+    if (!b || !d_rgb || !budgets || !chosen || !fits) return fail(kNullArgument, "null argument");
+    TRY(check_quality_range(min_q, max_q));
+    std::vector<uint64_t> lo((size_t)b->n_chunks * kQualities), hi(lo.size());
+    std::vector<uint8_t> status(lo.size());
+    TRY(alice_codec_batch_predict_sizes(b, d_rgb, lo.data(), hi.data(), status.data(), hip_stream));
+    std::vector<uint8_t> q(b->n_chunks);
+    for (uint32_t i = 0; i < b->n_chunks; ++i)
+        q[i] = chosen[i] = choose_quality(hi.data() + (size_t)i * kQualities, status.data() + (size_t)i * kQualities, budgets[i],
+                                          min_q, max_q, fits + i);
+    TRY(alice_codec_batch_set_qualities(b, q.data()));
+    return alice_codec_batch_encode(b, d_rgb, hip_stream);
 }
 const void* alice_codec_batch_alc_ptr(const AliceBatch* b, uint32_t chunk) {
     if (!b || chunk >= b->n_chunks) return nullptr;
@@ -2361,6 +2583,49 @@ int alice_codec_decode_many_devices(const EncodedChunk* const* chunks, uint32_t 
     });
 }
 
+// ---- PART 2: rate control ----
+
+int alice_codec_predict_sizes(uint8_t wavelet_type, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
+                              uint32_t frames, uint64_t lo[101], uint64_t hi[101], uint8_t status[101]) {
+    clear_error();
+    if (!lo || !hi || !status || (!rgb && rgb_len)) return fail(kNullArgument, "null argument");
+    if (wavelet_type > 2) return fail(kInvalidBitstream, "unknown wavelet type");
+    return predict_sizes_host(wavelet_type, rgb, rgb_len, width, height, frames, lo, hi, status);
+}
+
+EncodedChunk* alice_codec_encode_to_size(uint8_t wavelet_type, const uint8_t* rgb, uint64_t rgb_len, uint32_t width,
+                                         uint32_t height, uint32_t frames, uint64_t max_bytes, uint8_t min_q, uint8_t max_q,
+                                         uint8_t* chosen_q, uint8_t* fits) {
+    clear_error();
+    if (!chosen_q || !fits || (!rgb && rgb_len)) { fail(kNullArgument, "null argument"); return nullptr; }
+    if (wavelet_type > 2) { fail(kInvalidBitstream, "unknown wavelet type"); return nullptr; }
+    EncodedChunk* c = nullptr;
+    return encode_to_size_host(wavelet_type, rgb, rgb_len, width, height, frames, max_bytes, min_q, max_q, chosen_q, fits, &c) == kOk ? c : nullptr;
+}
+
+int alice_codec_dev_predict_sizes(const void* d_rgb, uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks,
+                                  uint8_t wavelet_type, uint64_t* lo, uint64_t* hi, uint8_t* status, void* d_step_hist,
+                                  void* hip_stream) {
+    clear_error();
+    if (!d_rgb || !lo || !hi || !status) return fail(kNullArgument, "null argument");
+    if (wavelet_type > 2) return fail(kInvalidBitstream, "unknown wavelet type");
+    ChunkDims d{};
+    TRY(chunk_dims(width, height, frames, &d, n_chunks));
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);   // temporaries drain the caller's stream before they return to the pool
+    EncodeWork w;
+    w.d = d; w.n_chunks = 1;
+    if (transform_tiles_eligible(d)) TRY(w.scratch.alloc(forward_scratch_bytes(d)));
+    std::vector<RgbLayout> layouts(n_chunks);
+    for (uint32_t i = 0; i < n_chunks; ++i) layouts[i] = packed_rgb((const uint8_t*)d_rgb + (size_t)i * d.n_pixels * 3, d);
+    std::vector<RateChannel> rc;
+    TRY(predict_chunks(layouts.data(), n_chunks, d, wavelet_type, w, st, (uint32_t*)d_step_hist, rc));
+    for (uint32_t i = 0; i < n_chunks; ++i)
+        rate_by_quality(rc.data() + (size_t)i * 192, lo + (size_t)i * kQualities, hi + (size_t)i * kQualities, status + (size_t)i * kQualities);
+    return kOk;
+}
+
 // ---- PART 3: device-resident stage calls (building blocks of the row-slab sharded path) ----
 // Every pointer named d_* is a device pointer; launches go on `hip_stream` and the call returns after the
 // stream has drained (the rANS calls need their result on the host anyway).
@@ -2498,6 +2763,12 @@ int alice_codec_dev_rans_decode(const void* d_stream, uint64_t len, const uint32
 
 void alice_codec_test_set_tuning(long band_kb) { set_transform_tuning(band_kb); }
 void alice_codec_test_set_value_table_radius(int r) { set_value_table_radius(r); }
+void alice_codec_test_rate_log_table(uint32_t lo[4097], uint32_t hi[4097], uint32_t g[2]) {
+    const RateLogTable& t = rate_log_table();
+    if (lo) memcpy(lo, t.lo, sizeof(t.lo));
+    if (hi) memcpy(hi, t.hi, sizeof(t.hi));
+    if (g) { g[0] = t.g_up; g[1] = t.g_dn; }
+}
 int alice_codec_test_set_admission_budget(uint64_t bytes) {
     clear_error();
     TRY(ensure_device());

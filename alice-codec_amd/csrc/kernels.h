@@ -131,10 +131,16 @@ void set_transform_probe(int mode);
 void set_transform_tuning(long band_kb);
 // radius of the forward temporal kernel's value -> symbol table (clamped to 1 .. 2048, the default).  Process-wide; tests only.
 void set_value_table_radius(int r);
+int value_table_radius();
 // Launches of one chunk on `st`, band after band (tile pass then temporal pass; the inverse the other way round).
 // hist: uint32 [3][256], zeroed by the caller.  Returns false (nothing launched) when the shape needs the generic path.
 bool launch_forward_transform(const RgbLayout& rgb, const ChunkDims& d, int wavelet, int32_t step,
                               void* d_scratch, uint8_t* d_sym, uint32_t* d_hist, hipStream_t st);
+// The same band loop for the rate prediction: the temporal pass counts the unquantised coefficients of each channel into
+// bins[c * 4096 + value + r] (r = value_table_radius(); zeroed by the caller) and values outside [-r, r) into *oor.
+// Returns false (nothing launched) when the shape needs the generic path.
+bool launch_forward_coef_hist(const RgbLayout& rgb, const ChunkDims& d, int wavelet, void* d_scratch, uint32_t* d_bins,
+                              uint32_t* d_oor, hipStream_t st);
 // steps per channel come from the chunk header.  exact = 64-bit lifting products.  mid16 = the intermediate after the
 // temporal pass provably fits i16 (halves its traffic); lds16 = so does everything after the column pass (packed tile).
 // When the chunk is cut into bands the pixels of the first band are written while the symbols of later bands are still
@@ -215,5 +221,24 @@ uint64_t compact_scratch_bytes(uint64_t n_items);
 void launch_extract_person(const uint8_t* d_mask, uint64_t mask_len, const uint8_t* d_rgb, uint64_t rgb_len, uint32_t width,
                            const uint32_t bbox[4], uint8_t* d_out, void* d_scratch, unsigned long long* d_count,
                            hipStream_t st);
+
+// ---- rate.hip: size prediction (see the derivation at the top of rate.hip) ----
+enum RateStatus : uint32_t { kRateBounded = 0, kRateUnbounded = 1, kRateDiverges = 2 };
+constexpr int kRateFracBits = 24;
+struct RateChannel {          // one (chunk, step, channel): stream bytes lo <= len <= hi when status == kRateBounded
+    unsigned long long lo, hi;
+    uint32_t status, pad_;
+};
+struct RateLogTable {
+    uint32_t lo[kProbScale + 1], hi[kProbScale + 1];   // floor / ceil of log2(4096 / f) * 2^24
+    uint32_t g_up, g_dn;                               // ceil(log2(1 + 2^-11) * 2^24), ceil(-log2(1 - 2^-11) * 2^24)
+};
+const RateLogTable& rate_log_table();
+// generic path: bins of one channel's coefficient volume (n values), same layout and counter as launch_forward_coef_hist
+void launch_coef_hist(const int32_t* d_vol, uint64_t n, uint32_t* d_bins, uint32_t* d_oor, hipStream_t st);
+// step_hist: [chunk][step - 1][channel][256]; chunks with a non-zero out-of-range counter are left alone
+void launch_rate_fold(const uint32_t* d_bins, const uint32_t* d_oor, uint32_t n_chunks, uint32_t* d_step_hist, hipStream_t st);
+// d_log: the lo and hi arrays of rate_log_table() back to back on the device; out: [chunk][step - 1][channel]
+void launch_rate_cost(const uint32_t* d_step_hist, const uint32_t* d_log, uint32_t n_chunks, RateChannel* d_out, hipStream_t st);
 
 }  // namespace alice

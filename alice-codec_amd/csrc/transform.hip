@@ -31,6 +31,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "symbols.h"
 
 namespace alice {
 
@@ -305,7 +306,6 @@ __device__ __forceinline__ I4 lift4(const I4& base, const I4& a, const I4& b, in
 constexpr int kHistReplicas = ALICE_HIST_REPLICAS;
 constexpr int kHistWords = kHistReplicas * 256;
 
-__device__ __forceinline__ uint32_t sat_sub_u32(uint32_t a, uint32_t b) { return __builtin_elementwise_sub_sat(a, b); }
 
 // Quantizer::quantize (src/quant.rs:89-97, dead zone = step) followed by to_symbols (:555-560), branch-free:
 //   q = (|v| - step/2) / step for |v| >= step, else 0.  For |v| < step the quotient of the saturating
@@ -330,14 +330,8 @@ __device__ __forceinline__ uint32_t quant_sym4(const I4& x, uint32_t hdz, uint32
     return s[0] | (s[1] << 8) | (s[2] << 16) | (s[3] << 24);
 }
 
-// The same map for one value (the table below is filled with it, so table and arithmetic cannot disagree)
-template <bool STEP1>
-__device__ __forceinline__ uint32_t quant_sym1(int val, uint32_t hdz, uint32_t magic) {
-    const uint32_t mag = (uint32_t)max(val, -val);
-    const uint32_t adj = sat_sub_u32(mag, hdz);
-    const uint32_t q = STEP1 ? adj : __umulhi(adj, magic);
-    return sat_sub_u32((q << 1) + ((uint32_t)val >> 31), 1u) & 0xFFu;
-}
+// quant_sym1 (symbols.h) is the same map for one value: the table below is filled with it, so table and arithmetic
+// cannot disagree.
 
 // Value -> symbol table in LDS for coefficients in [-r, r), r <= kQLutR: one add and one ds_read_u8 per sample instead of
 // the eight VALU operations above (one of them a quarter-rate multiply).  A wave in which any of a tick's eight values
@@ -363,7 +357,17 @@ __device__ __forceinline__ I4 unpack4_i16(const uint2 w) {
 // between ticks is O1[k], E1[k], O2[k-1] plus the raw pairs in flight: five values per pixel.
 // The tick is instantiated per position in a 4-tick block so that every register role is static: no window
 // shuffling moves, no per-tick selects except the end-of-signal mirror.
-template <int NS, bool STEP1, bool HIST, int PROBE = 0>
+// Coefficient bins of the rate prediction (BINS instance of FwdT, fwd_t_bins_kernel): kBinReplicas copies of the 2r bins,
+// word index = (value + r) * kBinReplicas + (lane & (kBinReplicas - 1)).  Zero, the most frequent coefficient of the high-pass
+// bands, is counted per wave (ballot + popcount, one add per wave); every other value goes to the bins.  Measured on
+// 1080p x 64 CDF 9/7 chunks (scripts/rate_probe.py --predict-only against builds with -DALICE_BIN_REPLICAS=R): 1, 2 and 4
+// replicas all give 0.92 ms per predicted chunk, 8 (128 KB, one workgroup per CU) 1.34 ms; one copy (16 KB) it is.
+#ifndef ALICE_BIN_REPLICAS
+#define ALICE_BIN_REPLICAS 1
+#endif
+constexpr int kBinReplicas = ALICE_BIN_REPLICAS;
+
+template <int NS, bool STEP1, bool HIST, int PROBE = 0, bool BINS = false>
 struct FwdT {
     const char* src;     // channel base inside the band slot (uniform)
     char* dst;           // channel base of the symbol volume (uniform)
@@ -378,6 +382,23 @@ struct FwdT {
     uint32_t qr;
     I4 o1p, e1p, o2pp;
     uint32_t acc;        // PROBE only
+    uint32_t* lb;        // BINS only: coefficient bins in LDS
+    uint32_t lane, oor;  // BINS only: lane in the wave, values outside [-qr, qr) seen by this thread
+
+    __device__ __forceinline__ void bin4(const I4& x) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int v = x.v[i];
+            const unsigned long long z = __builtin_amdgcn_ballot_w64(v == 0);
+            if (v == 0) {
+                if ((uint32_t)__builtin_ctzll(z) == lane) atomicAdd(&lb[qr * kBinReplicas], (uint32_t)__builtin_popcountll(z));
+            } else {
+                const uint32_t u = (uint32_t)v + qr;
+                if (u < 2u * qr) atomicAdd(&lb[u * kBinReplicas + (lane & (kBinReplicas - 1))], 1u);
+                else ++oor;
+            }
+        }
+    }
 
     __device__ __forceinline__ void load_pair(int pair, uint2& e, uint2& o) const {
         if (PROBE & 1) {     // small 16-bit pairs made of the pair index and the pixel offset: no memory
@@ -390,6 +411,7 @@ struct FwdT {
         o = *(const uint2*)(fe + plane_s * 2 + off16);
     }
     __device__ __forceinline__ void emit(int frame, const I4& lo, const I4& hi) {
+        if constexpr (BINS) { bin4(lo); bin4(hi); return; }
         uint32_t a, b;
         uint32_t ix[8], any = 0u;
 #pragma unroll
@@ -552,6 +574,53 @@ __global__ __launch_bounds__(256) void fwd_t_kernel(FwdTm a) {
 #pragma unroll 8
     for (int r = 0; r < kHistReplicas; ++r) cnt += lh[tid * kHistReplicas + ((r + tid) & (kHistReplicas - 1))];
     if (cnt) atomicAdd(&a.hist[ch * 256 + tid], cnt);
+}
+
+// The temporal pass of the rate prediction: the same lifting, but every coefficient is counted into 4096 bins per channel
+// (value + qr for values in [-qr, qr), the radius of the value table) instead of being quantised; values outside go to the
+// chunk's out-of-range counter.  No symbol stores.  A workgroup walks several units of its channel so that the 2 * qr bins
+// are folded into bins[ch * 4096 + ...] with few global atomics.
+struct FwdBm {
+    const int16_t* mid;
+    uint32_t* bins;              // [3][4096] of the chunk
+    uint32_t* oor;               // the chunk's out-of-range counter
+    Coeffs cf;
+    uint32_t qr;
+    uint32_t wgs_per_ch;
+    BandT b;
+};
+
+template <int NS>
+__global__ __launch_bounds__(256) void fwd_t_bins_kernel(FwdBm a) {
+    __shared__ uint32_t lb[kBinReplicas * 2 * kQLutR];
+    const int tid = threadIdx.x;
+    const uint32_t nw = 2u * a.qr * kBinReplicas;
+    for (uint32_t i = (uint32_t)tid; i < nw; i += 256u) lb[i] = 0u;
+    __syncthreads();
+    const int ch = (int)(blockIdx.x / a.wgs_per_ch);
+    uint32_t oor = 0u;
+    for (uint32_t blk = blockIdx.x % a.wgs_per_ch; blk < a.b.units_per_ch; blk += a.wgs_per_ch) {
+        const uint32_t idx = (blk * 256u + (uint32_t)tid) * 4u;
+        if (idx < a.b.band_px) {
+            FwdT<NS, false, false, 0, true> f;
+            f.src = (const char*)(a.mid + (size_t)ch * a.b.pf * a.b.band_px);
+            f.dst = nullptr;
+            f.plane_s = a.b.band_px; f.plane_d = 0;
+            f.off16 = idx * 2u; f.off8 = 0u;
+            f.half = (int)a.b.pf / 2; f.cf = a.cf; f.hdz = 0u; f.magic = 0u; f.lane_rep = 0u; f.lh = nullptr; f.qlut = nullptr;
+            f.qr = a.qr; f.lb = lb; f.lane = (uint32_t)tid & 63u; f.oor = 0u;
+            f.run();
+            oor += f.oor;
+        }
+    }
+    __syncthreads();
+    for (uint32_t v = (uint32_t)tid; v < 2u * a.qr; v += 256u) {
+        uint32_t cnt = 0u;
+#pragma unroll
+        for (int r = 0; r < kBinReplicas; ++r) cnt += lb[v * kBinReplicas + r];
+        if (cnt) atomicAdd(&a.bins[ch * 4096 + v], cnt);
+    }
+    if (oor) atomicAdd(a.oor, oor);
 }
 
 // (probe twins: border tiles need the clamping index map while the loads are real and the bounds tests while the stores
@@ -1202,6 +1271,7 @@ static long& band_target_kb() {
 void set_transform_tuning(long band_kb) { if (band_kb >= 0) band_target_kb() = band_kb; }
 static int g_value_table_radius = kQLutR;
 void set_value_table_radius(int r) { g_value_table_radius = r < 1 ? 1 : (r > kQLutR ? kQLutR : r); }
+int value_table_radius() { return g_value_table_radius; }
 // alice_codec_test_transform_ms(probe != 0): the CDF 9/7, step > 1, i16 lane-exchange instances run their probe twins
 static thread_local int tl_valu_probe = 0;
 void set_transform_probe(int mode) { tl_valu_probe = mode; }
@@ -1271,9 +1341,10 @@ static void fwd_t_launch(const FwdTm& ta, hipStream_t st) {
     hipLaunchKernelGGL((fwd_t_kernel<NS, STEP1, PROBE>), dim3(3u * ta.b.units_per_ch), dim3(256), 0, st, ta);
 }
 
-bool launch_forward_transform(const RgbLayout& rgb, const ChunkDims& d, int wavelet, int32_t step,
-                              void* d_scratch, uint8_t* d_sym, uint32_t* d_hist, hipStream_t st) {
-    if (step < 1 || step > 64) return false;
+// The band loop of the forward launches: the tile pass of every band, each followed by `temporal(BandT)` on its slot.
+template <typename Fn>
+static bool forward_bands(const RgbLayout& rgb, const ChunkDims& d, int wavelet, void* d_scratch, int probe, hipStream_t st,
+                          Fn temporal) {
     if (!transform_tiles_eligible(d)) return false;
     const LiftSteps ls = lift_steps(wavelet);
     const BandPlan bp = plan_bands(d, F_TH, sizeof(int16_t), 0);
@@ -1285,9 +1356,7 @@ bool launch_forward_transform(const RgbLayout& rgb, const ChunkDims& d, int wave
     unsigned ix1 = 1, iy1 = 1;
     while (ix1 < nx && interior_x(ix1)) ++ix1;
     while (iy1 < ny && interior_y(iy1)) ++iy1;
-    const uint32_t magic = step == 1 ? 0u : (uint32_t)(((1ull << 32) + (uint32_t)step - 1u) / (uint32_t)step);
     const uint32_t hh = (uint32_t)(d.ph / 2), pw = (uint32_t)d.pw;
-    const int probe = (ls.n == 4 && step != 1) ? tl_valu_probe : 0;
     for (int band = 0; band < bp.n_bands; ++band) {
         const int by0 = band * bp.tpb, nby = std::min(bp.tpb, bp.tiles_y - by0);
         const int y0 = by0 * F_TH, rows = (int)std::min<uint64_t>((uint64_t)(by0 + nby) * F_TH, d.ph) - y0;
@@ -1296,22 +1365,48 @@ bool launch_forward_transform(const RgbLayout& rgb, const ChunkDims& d, int wave
         xa.aligned = rgb_dword_aligned(rgb);
         xa.bt = BandTiles{(int)nx, by0, nby, 1, (int)ix1, 1, (int)iy1};
         xa.y0 = y0; xa.rows = rows;
-        FwdTm ta{};
-        ta.mid = (const int16_t*)d_scratch; ta.sym = d_sym; ta.hist = d_hist; ta.cf = cf; ta.hdz = (uint32_t)step / 2u; ta.magic = magic; ta.qr = (uint32_t)g_value_table_radius;
-        ta.b = make_band_t(d, (uint32_t)rows * pw, (uint32_t)(rows / 2) * pw, (uint32_t)(y0 / 2) * pw, (hh + (uint32_t)(y0 / 2)) * pw);
-        if (probe) {   // loads and stores replaced / loads only / stores only
-            if (probe == 1) { fwd_xy_launch<4, 3>(xa, st); fwd_t_launch<4, false, 3>(ta, st); }
-            else if (probe == 2) { fwd_xy_launch<4, 1>(xa, st); fwd_t_launch<4, false, 1>(ta, st); }
-            else { fwd_xy_launch<4, 2>(xa, st); fwd_t_launch<4, false, 2>(ta, st); }
-        } else if (ls.n == 4) {
-            fwd_xy_launch<4>(xa, st);
-            if (step == 1) fwd_t_launch<4, true>(ta, st); else fwd_t_launch<4, false>(ta, st);
-        } else {
-            fwd_xy_launch<2>(xa, st);
-            if (step == 1) fwd_t_launch<2, true>(ta, st); else fwd_t_launch<2, false>(ta, st);
-        }
+        const BandT b = make_band_t(d, (uint32_t)rows * pw, (uint32_t)(rows / 2) * pw, (uint32_t)(y0 / 2) * pw, (hh + (uint32_t)(y0 / 2)) * pw);
+        if (probe == 1) fwd_xy_launch<4, 3>(xa, st);
+        else if (probe == 2) fwd_xy_launch<4, 1>(xa, st);
+        else if (probe) fwd_xy_launch<4, 2>(xa, st);
+        else if (ls.n == 4) fwd_xy_launch<4>(xa, st);
+        else fwd_xy_launch<2>(xa, st);
+        temporal(b, cf, ls.n);
     }
     return true;
+}
+
+bool launch_forward_transform(const RgbLayout& rgb, const ChunkDims& d, int wavelet, int32_t step,
+                              void* d_scratch, uint8_t* d_sym, uint32_t* d_hist, hipStream_t st) {
+    if (step < 1 || step > 64) return false;
+    const uint32_t magic = step == 1 ? 0u : (uint32_t)(((1ull << 32) + (uint32_t)step - 1u) / (uint32_t)step);
+    const int probe = (lift_steps(wavelet).n == 4 && step != 1) ? tl_valu_probe : 0;
+    return forward_bands(rgb, d, wavelet, d_scratch, probe, st, [&](const BandT& b, const Coeffs& cf, int ns) {
+        FwdTm ta{};
+        ta.mid = (const int16_t*)d_scratch; ta.sym = d_sym; ta.hist = d_hist; ta.cf = cf; ta.hdz = (uint32_t)step / 2u; ta.magic = magic; ta.qr = (uint32_t)g_value_table_radius;
+        ta.b = b;
+        if (probe) {   // loads and stores replaced / loads only / stores only
+            if (probe == 1) fwd_t_launch<4, false, 3>(ta, st);
+            else if (probe == 2) fwd_t_launch<4, false, 1>(ta, st);
+            else fwd_t_launch<4, false, 2>(ta, st);
+        } else if (ns == 4) {
+            if (step == 1) fwd_t_launch<4, true>(ta, st); else fwd_t_launch<4, false>(ta, st);
+        } else {
+            if (step == 1) fwd_t_launch<2, true>(ta, st); else fwd_t_launch<2, false>(ta, st);
+        }
+    });
+}
+
+bool launch_forward_coef_hist(const RgbLayout& rgb, const ChunkDims& d, int wavelet, void* d_scratch, uint32_t* d_bins,
+                              uint32_t* d_oor, hipStream_t st) {
+    return forward_bands(rgb, d, wavelet, d_scratch, 0, st, [&](const BandT& b, const Coeffs& cf, int ns) {
+        FwdBm ba{};
+        ba.mid = (const int16_t*)d_scratch; ba.bins = d_bins; ba.oor = d_oor; ba.cf = cf; ba.qr = (uint32_t)g_value_table_radius;
+        ba.b = b;
+        ba.wgs_per_ch = std::min<uint32_t>(b.units_per_ch, 170u);   // 3 x 170 workgroups: about two per CU
+        if (ns == 4) hipLaunchKernelGGL(fwd_t_bins_kernel<4>, dim3(3u * ba.wgs_per_ch), dim3(256), 0, st, ba);
+        else hipLaunchKernelGGL(fwd_t_bins_kernel<2>, dim3(3u * ba.wgs_per_ch), dim3(256), 0, st, ba);
+    });
 }
 
 // ---- inverse ----

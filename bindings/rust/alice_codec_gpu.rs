@@ -93,6 +93,10 @@ extern "C" {
                                        devices: *const c_int, n_devices: u32, out: *mut *mut RawChunk) -> c_int;
     fn alice_codec_decode_many_devices(chunks: *const *const RawChunk, n_chunks: u32, devices: *const c_int, n_devices: u32,
                                        rgb_out: *mut u8, rgb_out_len: u64) -> c_int;
+    fn alice_codec_predict_sizes(wavelet: u8, rgb: *const u8, rgb_len: u64, w: u32, h: u32, f: u32, lo: *mut u64, hi: *mut u64,
+                                 status: *mut u8) -> c_int;
+    fn alice_codec_encode_to_size(wavelet: u8, rgb: *const u8, rgb_len: u64, w: u32, h: u32, f: u32, max_bytes: u64, min_q: u8,
+                                  max_q: u8, chosen_q: *mut u8, fits: *mut u8) -> *mut RawChunk;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -175,6 +179,46 @@ impl EncodedChunk {
     }
 }
 impl Drop for EncodedChunk { fn drop(&mut self) { unsafe { alice_codec_chunk_destroy(self.raw) } } }
+
+// ---------------------------------------------------------------------------------------------------------------
+// rate control on the GPU (an extension: the reference's own RateController / estimate_quality stay the reference's)
+// ---------------------------------------------------------------------------------------------------------------
+
+/// status of a quality's prediction (ALICE_RATE_*)
+pub const RATE_BOUNDED: u8 = 0;
+pub const RATE_UNBOUNDED: u8 = 1;
+pub const RATE_DIVERGES: u8 = 2;
+
+/// The guaranteed .alc length bracket `lo[q] <= len <= hi[q]` of a chunk at every quality q = 0..=100 (where
+/// `status[q] == RATE_BOUNDED`), from one forward transform on the GPU.
+pub struct SizePrediction { pub lo: [u64; 101], pub hi: [u64; 101], pub status: [u8; 101] }
+
+pub fn predict_sizes(rgb_frames: &[u8], width: u32, height: u32, frames: u32, wavelet_type: WaveletType)
+    -> Result<SizePrediction, CodecError> {
+    let mut p = SizePrediction { lo: [0; 101], hi: [0; 101], status: [0; 101] };
+    let rc = unsafe {
+        alice_codec_predict_sizes(wavelet_type as u8, rgb_frames.as_ptr(), rgb_frames.len() as u64, width, height, frames,
+                                  p.lo.as_mut_ptr(), p.hi.as_mut_ptr(), p.status.as_mut_ptr())
+    };
+    let expected = (width as usize).saturating_mul(height as usize).saturating_mul(frames as usize).saturating_mul(3);
+    check(rc, expected, rgb_frames.len()).map(|_| p)
+}
+
+/// Encodes once, at the highest quality in `min_quality..=max_quality` whose predicted length fits `max_bytes`:
+/// (chunk, chosen quality, fits).  When none fits, the chunk is encoded at `min_quality` and `fits` is false.
+pub fn encode_to_size(rgb_frames: &[u8], width: u32, height: u32, frames: u32, max_bytes: u64, wavelet_type: WaveletType,
+                      min_quality: u8, max_quality: u8) -> Result<(EncodedChunk, u8, bool), CodecError> {
+    let (mut q, mut fits) = (0u8, 0u8);
+    let raw = unsafe {
+        alice_codec_encode_to_size(wavelet_type as u8, rgb_frames.as_ptr(), rgb_frames.len() as u64, width, height, frames, max_bytes,
+                                   min_quality, max_quality, &mut q, &mut fits)
+    };
+    if raw.is_null() {
+        let expected = (width as usize).saturating_mul(height as usize).saturating_mul(frames as usize).saturating_mul(3);
+        return Err(last_error(expected, rgb_frames.len(), width, height, 0));
+    }
+    Ok((EncodedChunk { raw }, q, fits != 0))
+}
 
 /// src/pipeline.rs:335-340
 pub struct FrameEncoder { quality: u8, wavelet_type: WaveletType }

@@ -109,6 +109,38 @@ uint8_t *alice_codec_chunk_to_bytes64(const EncodedChunk *chunk, uint64_t *out_l
 EncodedChunk *alice_codec_chunk_from_bytes64(const uint8_t *data, uint64_t len);
 void alice_codec_data_free64(uint8_t *ptr, uint64_t len);
 
+/* ---- rate control: the size of a chunk at every quality before it is encoded, and encodes to a byte budget ----
+ * From one forward transform per chunk the library derives, for every quality q = 0..100, the exact symbol histograms the
+ * encoder would write and from them a guaranteed bracket lo[q] <= length of the .alc (to_bytes) <= hi[q], before any rANS
+ * chain runs (derivation: csrc/rate.hip).  status[q]: ALICE_RATE_BOUNDED when every channel's table is one the bracket
+ * covers (every present symbol has a frequency in 1..4096).  NOTE, a deliberate choice: a table whose cum + freq runs
+ * past 4096 -- the reference's freq-1 floor for empty bins makes that most tables of real chunks -- is BOUNDED here, the
+ * excess carried into the bracket; classing it UNBOUNDED would leave almost no quality of real content predictable.
+ * ALICE_RATE_UNBOUNDED when a present symbol's frequency is above 4096 (lo = 0, hi = UINT64_MAX); ALICE_RATE_DIVERGES when a present symbol's frequency wrapped to 0 (an encode at that quality
+ * fails with ALICE_ERR_REFERENCE_DIVERGES; lo = 0, hi = UINT64_MAX).  A chunk without pixels is its 3138-byte header at
+ * every quality.  Validation is that of alice_codec_encode64 (dimensions, then the buffer size); wavelet_type > 2 is
+ * ALICE_ERR_INVALID_BITSTREAM.  Budget calls: qualities above 100 act as 100, and min_q > max_q (after that) is
+ * ALICE_ERR_INVALID_DIMENSIONS.  The chosen quality is the largest q in [min_q, max_q] with status BOUNDED and
+ * hi[q] <= budget (every q is looked at; size need not fall with quality); when none fits, min_q with *fits = 0. */
+enum { ALICE_RATE_BOUNDED = 0, ALICE_RATE_UNBOUNDED = 1, ALICE_RATE_DIVERGES = 2 };
+/* one host chunk: lo / hi / status at the 101 qualities */
+int alice_codec_predict_sizes(uint8_t wavelet_type, const uint8_t *rgb, uint64_t rgb_len, uint32_t width,
+                              uint32_t height, uint32_t frames, uint64_t lo[101], uint64_t hi[101], uint8_t status[101]);
+/* FrameEncoder::with_wavelet(q, wavelet_type).encode(...) at the chosen q for the budget max_bytes (whole .alc bytes);
+ * *chosen_q and *fits out.  NULL on error (alice_codec_last_error). */
+EncodedChunk *alice_codec_encode_to_size(uint8_t wavelet_type, const uint8_t *rgb, uint64_t rgb_len, uint32_t width,
+                                         uint32_t height, uint32_t frames, uint64_t max_bytes, uint8_t min_q,
+                                         uint8_t max_q, uint8_t *chosen_q, uint8_t *fits);
+/* n_chunks equal-shaped packed chunks on the device, back to back: lo / hi / status of n_chunks * 101 entries, index
+ * chunk * 101 + quality.  Like every device call, a chunk without pixels is ALICE_ERR_INVALID_DIMENSIONS here (the host
+ * calls above answer it with its header size).  d_step_hist: device, n_chunks * 64 * 3 * 256 u32 (index [chunk][step - 1][channel][symbol]:
+ * the channel histograms the .alc header would hold at that quantiser step), or NULL.  Launches on hip_stream; finished
+ * on return. */
+int alice_codec_dev_predict_sizes(const void *d_rgb, uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks,
+                                  uint8_t wavelet_type, uint64_t *lo, uint64_t *hi, uint8_t *status, void *d_step_hist,
+                                  void *hip_stream);
+/* (the same for a device batch: alice_codec_batch_predict_sizes / _set_qualities / _encode_to_budget, below) */
+
 /* ---- many equal-shaped chunks from host memory in one call (what a 64-frame chunk driver wants: the serial
  * entropy chains of all chunks run side by side).  rgb = n_chunks chunks back to back; out_chunks[n_chunks] receives
  * handles to free with alice_codec_chunk_destroy.  Same results as n_chunks calls of alice_codec_encode64. ---- */
@@ -135,6 +167,17 @@ typedef struct AliceBatch AliceBatch;
 AliceBatch *alice_codec_batch_create(uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks,
                                      uint8_t quality, uint8_t wavelet_type);
 void alice_codec_batch_destroy(AliceBatch *batch);
+/* Rate control of a batch (the rules of the rate-control calls above).  predict_sizes: lo / hi / status of
+ * n_chunks * 101 entries for the chunks at d_rgb (as for alice_codec_batch_encode); finished on return. */
+int alice_codec_batch_predict_sizes(AliceBatch *batch, const void *d_rgb, uint64_t *lo, uint64_t *hi, uint8_t *status,
+                                    void *hip_stream);
+/* qualities: n_chunks entries, copied; the batch's next encodes (alice_codec_batch_encode, _encode_regions) encode chunk i
+ * at qualities[i], each header carrying its own step.  NULL: every chunk at the batch's quality again. */
+int alice_codec_batch_set_qualities(AliceBatch *batch, const uint8_t *qualities);
+/* budgets: n_chunks whole-.alc byte budgets.  Predicts, chooses each chunk's quality (chosen[n_chunks], fits[n_chunks]
+ * out), sets those qualities and queues the encode: finish with alice_codec_batch_encode_finish. */
+int alice_codec_batch_encode_to_budget(AliceBatch *batch, const void *d_rgb, const uint64_t *budgets, uint8_t min_q,
+                                       uint8_t max_q, uint8_t *chosen, uint8_t *fits, void *hip_stream);
 /* d_rgb: device pointer to n_chunks * width*height*frames*3 bytes.  hip_stream: hipStream_t (NULL = default).
  * Runs the transforms, waits for them once to size the stream regions from the histograms, then queues the
  * entropy coding and the .alc assembly asynchronously; the .alc buffers stay on the device.

@@ -493,4 +493,117 @@ inline void paste_from_bbox(std::vector<uint8_t>& frame, uint32_t frame_width, c
     }
 }
 
+// ---- rate control ----
+// On the GPU: the guaranteed size bracket of a chunk at the 101 qualities (alice_codec_predict_sizes) and one encode at the
+// highest quality that fits a byte budget (alice_codec_encode_to_size).
+struct SizePrediction {
+    std::array<uint64_t, 101> lo{}, hi{};
+    std::array<uint8_t, 101> status{};   // ALICE_RATE_BOUNDED / _UNBOUNDED / _DIVERGES
+};
+inline SizePrediction predict_sizes(const std::vector<uint8_t>& rgb, uint32_t w, uint32_t h, uint32_t f,
+                                     WaveletType wt = WaveletType::Cdf53) {
+    static const uint8_t empty = 0;
+    SizePrediction p;
+    detail::check(alice_codec_predict_sizes(static_cast<uint8_t>(wt), rgb.empty() ? &empty : rgb.data(), rgb.size(), w, h, f,
+                                            p.lo.data(), p.hi.data(), p.status.data()));
+    return p;
+}
+struct SizedChunk { EncodedChunk chunk; uint8_t quality; bool fits; };
+inline SizedChunk encode_to_size(const std::vector<uint8_t>& rgb, uint32_t w, uint32_t h, uint32_t f, uint64_t max_bytes,
+                                 WaveletType wt = WaveletType::Cdf53, uint8_t min_quality = 10, uint8_t max_quality = 95) {
+    static const uint8_t empty = 0;
+    uint8_t q = 0, fits = 0;
+    ::EncodedChunk* c = alice_codec_encode_to_size(static_cast<uint8_t>(wt), rgb.empty() ? &empty : rgb.data(), rgb.size(), w, h, f,
+                                                   max_bytes, min_quality, max_quality, &q, &fits);
+    if (!c) detail::raise();
+    return SizedChunk{EncodedChunk::adopt(c), q, fits != 0};
+}
+
+// The reference's buffer-model rate control (src/rate_control.rs:7-219), host only, with the Rust integer behaviour:
+// u32::midpoint start, buffer half full, 30-entry history, +-0.3 thresholds with +1 / -2 steps, saturating f64 casts
+// (NaN -> 0), wrapping integer casts.
+struct RateControlConfig {            // :7-31
+    uint32_t target_bitrate_kbps = 5000;
+    double framerate = 30.0;
+    uint32_t min_quality = 10, max_quality = 95;
+    uint64_t buffer_size_bits = 5000ull * 1000ull * 2ull;
+};
+namespace detail {
+inline uint64_t f64_as_u64(double x) {   // Rust `as u64`: saturating, NaN -> 0
+    if (!(x > 0.0)) return 0;
+    if (x >= 18446744073709551616.0) return UINT64_MAX;
+    return static_cast<uint64_t>(x);
+}
+inline uint32_t f64_as_u32(double x) {
+    if (!(x > 0.0)) return 0;
+    if (x >= 4294967296.0) return UINT32_MAX;
+    return static_cast<uint32_t>(x);
+}
+template <typename T> T clamp_or_throw(T v, T lo, T hi) {   // Ord::clamp panics on an inverted range
+    if (lo > hi) throw std::invalid_argument("clamp: min > max");
+    return v < lo ? lo : (v > hi ? hi : v);
+}
+}  // namespace detail
+class RateController {                // :34-190
+public:
+    explicit RateController(const RateControlConfig& c)
+        : config_(c), fullness_(static_cast<int64_t>(c.buffer_size_bits) / 2),
+          quality_(static_cast<uint32_t>(((uint64_t)c.min_quality + c.max_quality) >> 1)) {}
+    static RateController with_defaults() { return RateController(RateControlConfig{}); }
+    uint64_t target_bits_per_frame() const {
+        if (config_.framerate <= 0.0) return 0;
+        return detail::f64_as_u64(static_cast<double>(config_.target_bitrate_kbps) * 1000.0 / config_.framerate);
+    }
+    uint32_t recommended_quality() const { return quality_; }
+    void update(uint64_t frame_size_bits) {
+        const int64_t target = static_cast<int64_t>(target_bits_per_frame());
+        const int64_t buf = static_cast<int64_t>(config_.buffer_size_bits);
+        fullness_ = static_cast<int64_t>(static_cast<uint64_t>(fullness_) +
+                                         (static_cast<uint64_t>(target) - frame_size_bits));   // wrapping, as release Rust
+        fullness_ = detail::clamp_or_throw<int64_t>(fullness_, static_cast<int64_t>(0ull - static_cast<uint64_t>(buf)), buf);
+        history_.push_back(frame_size_bits);
+        if (history_.size() > 30) history_.erase(history_.begin());
+        ++frames_;
+        const double ratio = static_cast<double>(fullness_) / static_cast<double>(config_.buffer_size_bits);
+        const int32_t adj = ratio > 0.3 ? 1 : (ratio < -0.3 ? -2 : 0);
+        quality_ = static_cast<uint32_t>(detail::clamp_or_throw<int32_t>(
+            static_cast<int32_t>(quality_ + static_cast<uint32_t>(adj)), static_cast<int32_t>(config_.min_quality),
+            static_cast<int32_t>(config_.max_quality)));
+    }
+    double buffer_ratio() const {
+        if (config_.buffer_size_bits == 0) return 0.0;
+        return static_cast<double>(fullness_) / static_cast<double>(config_.buffer_size_bits);
+    }
+    uint64_t average_frame_size() const {
+        if (history_.empty()) return 0;
+        uint64_t s = 0;
+        for (uint64_t v : history_) s += v;
+        return s / history_.size();
+    }
+    uint64_t frame_count() const { return frames_; }
+    uint32_t current_quality() const { return quality_; }
+    double actual_to_target_ratio() const {
+        const uint64_t t = target_bits_per_frame();
+        if (t == 0) return 0.0;
+        return static_cast<double>(average_frame_size()) / static_cast<double>(t);
+    }
+private:
+    RateControlConfig config_;
+    int64_t fullness_;
+    uint32_t quality_;
+    std::vector<uint64_t> history_;
+    uint64_t frames_ = 0;
+};
+inline uint32_t estimate_quality(uint32_t target_bitrate_kbps, uint32_t width, uint32_t height, double fps) {   // :196-219
+    if (fps <= 0.0 || width == 0 || height == 0) return 50;
+    const double pps = static_cast<double>(width) * static_cast<double>(height) * fps;
+    const double bpp = static_cast<double>(target_bitrate_kbps) * 1000.0 / pps;
+    double q;
+    if (bpp > 2.0) q = 95.0;
+    else if (bpp > 0.5) q = __builtin_fma(bpp, 30.0, 35.0);
+    else if (bpp > 0.1) q = __builtin_fma(bpp, 75.0, 12.5);
+    else q = bpp * 100.0 + 5.0;
+    return detail::clamp_or_throw<uint32_t>(detail::f64_as_u32(q), 5u, 100u);
+}
+
 }  // namespace alice_codec

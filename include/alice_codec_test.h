@@ -55,6 +55,11 @@ int alice_codec_test_set_admission_budget(uint64_t bytes);
  * per CU (one wave per SIMD). */
 int alice_codec_test_chain_occupancy(uint32_t out[6]);
 
+/* The fixed-point table of the rate prediction (csrc/rate.hip): lo[f] / hi[f] = floor / ceil of log2(4096 / f) * 2^24 for
+ * f = 1 .. 4096 (entry 0 unused), g[0] = ceil(log2(1 + 2^-11) * 2^24), g[1] = ceil(-log2(1 - 2^-11) * 2^24).  Any pointer may
+ * be NULL.  No device needed. */
+void alice_codec_test_rate_log_table(uint32_t lo[4097], uint32_t hi[4097], uint32_t g[2]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,90 @@
+"""Rate prediction on 1920x1080x64 chunks (CDF 9/7, the benchmark's synthetic content): what it costs and how tight it is.
+
+* prediction ms per chunk: HIP events around alice_codec_dev_predict_sizes on a batch of chunks after warm-up (the call
+  returns after its work has drained, so this includes its host side and its one small device-to-host copy), next to
+  the forward transform pair of an encode (alice_codec_test_transform_ms);
+* the relative bracket width (hi - lo) / hi at q = 50, 80, 95;
+* the bracket against the actual .alc lengths of GPU encodes at those qualities;
+* encode_to_size of one chunk for a few budgets: chosen quality, size, budget.
+
+  python scripts/rate_probe.py --out profiles/r06_rate_probe_1080p64.json
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import alice_codec_amd as a  # noqa: E402
+import bench  # noqa: E402
+
+W, H, F = 1920, 1080, 64
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r06_rate_probe_1080p64.json"))
+    ap.add_argument("--chunks", type=int, default=4)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--predict-only", action="store_true", help="time the prediction only (replica sweeps of the bin layout)")
+    args = ap.parse_args()
+    a.set_device(0)
+    lib = a.load_library()
+    dev = torch.device("cuda:0")
+    px = W * H * F
+    rgb = torch.stack([bench.synth_chunk(dev, i).reshape(-1) for i in range(args.chunks)]).contiguous()
+    wt = a.WaveletType.Cdf97
+    a.predict_sizes_device(rgb.data_ptr(), W, H, F, args.chunks, wt)   # warm-up
+    torch.cuda.synchronize()
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(args.reps):
+        p = a.predict_sizes_device(rgb.data_ptr(), W, H, F, args.chunks, wt)
+    t1.record()
+    torch.cuda.synchronize()
+    predict_ms = t0.elapsed_time(t1) / (args.reps * args.chunks)
+    if args.predict_only:
+        print(json.dumps({"predict_ms_per_chunk": round(predict_ms, 3), "chunks_per_call": args.chunks, "reps": args.reps}))
+        return
+
+    sym = torch.empty((args.chunks, 3 * px), dtype=torch.uint8, device=dev)
+    out = torch.empty_like(rgb)
+    ms = (C.c_float * 2)()
+    st = torch.cuda.current_stream().cuda_stream
+    assert lib.alice_codec_test_transform_ms(rgb.data_ptr(), sym.data_ptr(), out.data_ptr(), args.chunks, W, H, F, int(wt), 80,
+                                             args.chunks, args.reps, 0, ms, st) == 0
+    forward_ms = float(ms[0])
+
+    host = rgb[0].cpu().numpy()
+    actual = {}
+    for q in (50, 80, 95):
+        n = len(a.FrameEncoder.with_wavelet(q, wt).encode(host, W, H, F).to_bytes())
+        actual[q] = {"lo": int(p.lo[0][q]), "actual": n, "hi": int(p.hi[0][q]), "status": int(p.status[0][q]),
+                     "rel_width": (int(p.hi[0][q]) - int(p.lo[0][q])) / int(p.hi[0][q]),
+                     "inside": int(p.lo[0][q]) <= n <= int(p.hi[0][q])}
+    budget_rows = []
+    for budget in (actual[50]["hi"] // 2, actual[80]["hi"], actual[95]["hi"] + 1):
+        chunk, q, fits = a.encode_to_size(host, W, H, F, budget, wt, 10, 95)
+        budget_rows.append({"budget": budget, "chosen_quality": q, "fits": fits, "bytes": len(chunk.to_bytes())})
+    res = {
+        "what": "rate prediction of 1920x1080x64 CDF 9/7 chunks (bench.synth_chunk content), MI355X",
+        "predict_ms_per_chunk": round(predict_ms, 3),
+        "forward_transform_pair_ms_per_chunk": round(forward_ms, 3),
+        "chunks_per_call": args.chunks, "reps": args.reps,
+        "bracket_vs_actual": {str(k): v for k, v in actual.items()},
+        "status_counts": {s: int((p.status == i).sum()) for i, s in enumerate(("bounded", "unbounded", "diverges"))},
+        "encode_to_size": budget_rows,
+    }
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as fh:
+        json.dump(res, fh, indent=1)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
