@@ -241,6 +241,16 @@ def load_library() -> C.CDLL:
         "alice_codec_batch_predict_sizes": (C.c_int, [vp, vp, _u64p, _u64p, _u8p, vp]),
         "alice_codec_batch_set_qualities": (C.c_int, [vp, _u8p]),
         "alice_codec_batch_encode_to_budget": (C.c_int, [vp, vp, _u64p, C.c_uint8, C.c_uint8, _u8p, _u8p, vp]),
+        "alice_codec_split_stream_bound": (C.c_uint64, [C.c_uint64, C.c_uint32]),
+        "alice_codec_split_normalize": (C.c_int, [_u32p, _u16p]),
+        "alice_codec_dev_split_encode": (C.c_int, [vp, C.c_uint64, _u32p, C.c_uint32, vp, C.c_uint64, _u64p, vp]),
+        "alice_codec_dev_split_decode": (C.c_int, [vp, C.c_uint64, _u16p, C.c_uint32, vp, C.c_uint64, vp]),
+        "alice_codec_encode_split": (vp, [vp, _u8p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _u64p]),
+        "alice_codec_decode_split": (vp, [_u8p, C.c_uint64, _u64p]),
+        "alice_codec_split_info": (C.c_int, [_u8p, C.c_uint64, vp]),
+        "alice_codec_dev_encode_split": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint8, _u8p,
+                                                   C.c_uint32, vp, C.c_uint64, _u64p, vp]),
+        "alice_codec_dev_decode_split": (C.c_int, [vp, C.c_uint64, _u64p, C.c_uint32, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
@@ -1563,3 +1573,109 @@ def decode_person_chunks(chunks, d_frames_out, width: int, height: int, frames: 
         batch = batches[key]
         batch.decode_regions(d_alc.data_ptr(), stride, out_ptr + i * f * frame_bytes, W, H, [b[:2] for b in boxes[i:j]])
         batch.decode_finish()
+
+
+# ---- split-stream format (.alc version 2) ----
+# v1 is the format for byte compatibility with the reference; v2 is for video that comes back and for the latency of one chunk.
+
+SPLIT_DEFAULT_LANE_SYMBOLS = 512
+SPLIT_HEADER_BYTES = 1630
+
+
+class _CSplitInfo(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("frames", C.c_uint32), ("lane_symbols", C.c_uint32),
+                ("wavelet", C.c_uint8), ("reserved", C.c_uint8 * 3),
+                ("quant_step", C.c_int32 * 3), ("dead_zone", C.c_int32 * 3),
+                ("num_symbols", C.c_uint32 * 3), ("n_blocks", C.c_uint32 * 3), ("payload_len", C.c_uint64 * 3)]
+
+
+class SplitInfo:
+    """The header fields of a version 2 container (alice_codec_split_info: validated, no device needed)."""
+
+    def __init__(self, c: _CSplitInfo):
+        self.width, self.height, self.frames = int(c.width), int(c.height), int(c.frames)
+        self.lane_symbols = int(c.lane_symbols)
+        self.wavelet_type = WaveletType(int(c.wavelet))
+        self.quant_step = [int(v) for v in c.quant_step]
+        self.dead_zone = [int(v) for v in c.dead_zone]
+        self.num_symbols = [int(v) for v in c.num_symbols]
+        self.n_blocks = [int(v) for v in c.n_blocks]
+        self.payload_len = [int(v) for v in c.payload_len]
+
+    def __repr__(self):
+        return (f"SplitInfo({self.width}x{self.height}x{self.frames}, {self.wavelet_type.name}, lane_symbols={self.lane_symbols}, "
+                f"steps={self.quant_step}, blocks={self.n_blocks}, payload={self.payload_len})")
+
+
+def split_info(data) -> SplitInfo:
+    buf = _as_u8(data)
+    c = _CSplitInfo()
+    _check(load_library().alice_codec_split_info(_p(buf, _u8p), buf.size, C.byref(c)))
+    return SplitInfo(c)
+
+
+def alc_version(data) -> int:
+    """The version byte of a container (0 when the data is too short to have one)."""
+    buf = _as_u8(data)
+    return int(buf[4]) if buf.size > 4 else 0
+
+
+def encode_split(encoder: "FrameEncoder", rgb_frames, width: int, height: int, frames: int, lane_symbols: int = 0) -> bytes:
+    """One chunk as version 2 bytes, with the encoder's wavelet and quality (lane_symbols 0: the default)."""
+    lib = load_library()
+    buf = _as_u8(rgb_frames)
+    _dims_u32(width, height, frames, lane_symbols)
+    n = C.c_uint64(0)
+    src = _p(buf, _u8p) if buf.size else C.cast(C.c_char_p(b""), _u8p)
+    ptr = lib.alice_codec_encode_split(encoder._h, src, buf.size, width, height, frames, lane_symbols, C.byref(n))
+    if not ptr:
+        _raise_last()
+    try:
+        return _copy_out(ptr, n.value).tobytes()
+    finally:
+        lib.alice_codec_data_free64(ptr, n.value)
+
+
+def decode_split(data) -> np.ndarray:
+    """The RGB bytes of a version 2 container."""
+    lib = load_library()
+    buf = _as_u8(data)
+    n = C.c_uint64(0)
+    ptr = lib.alice_codec_decode_split(_p(buf, _u8p), buf.size, C.byref(n))
+    if not ptr:
+        _raise_last()
+    return _adopt(ptr, n.value, lib.alice_codec_data_free64)
+
+
+def normalized_frequencies(histogram) -> np.ndarray:
+    """The 256 frequencies a version 2 header stores for this histogram (sum 4096), from the table kernel."""
+    h = np.ascontiguousarray(histogram, dtype=np.uint32).reshape(-1)
+    if h.size != 256:
+        raise ValueError("histogram must have 256 bins")
+    f = np.zeros(256, np.uint16)
+    _check(load_library().alice_codec_split_normalize(_p(h, _u32p), _p(f, _u16p)))
+    return f
+
+
+def split_stream_bound(n: int, lane_symbols: int = SPLIT_DEFAULT_LANE_SYMBOLS) -> int:
+    return int(load_library().alice_codec_split_stream_bound(n, lane_symbols))
+
+
+def split_encode_device(d_rgb_ptr: int, width: int, height: int, frames: int, n_chunks: int, wavelet_type: WaveletType,
+                        quality: int, d_out_ptr: int, out_stride: int, qualities=None, lane_symbols: int = 0,
+                        stream: int = 0) -> np.ndarray:
+    """n_chunks packed device chunks -> version 2 bytes at d_out_ptr + i * out_stride; returns the sizes."""
+    sizes = np.zeros(n_chunks, np.uint64)
+    q = None if qualities is None else np.ascontiguousarray(qualities, dtype=np.uint8).reshape(-1)
+    if q is not None and q.size != n_chunks:
+        raise ValueError("one quality per chunk")
+    _dims_u32(width, height, frames, n_chunks, lane_symbols)
+    _check(load_library().alice_codec_dev_encode_split(d_rgb_ptr, width, height, frames, n_chunks, int(wavelet_type), quality,
+                                                       None if q is None else _p(q, _u8p), lane_symbols, d_out_ptr, out_stride,
+                                                       _p(sizes, _u64p), stream or None))
+    return sizes
+
+
+def split_decode_device(d_alc_ptr: int, alc_stride: int, sizes, d_rgb_out_ptr: int, stream: int = 0) -> None:
+    s = np.ascontiguousarray(sizes, dtype=np.uint64).reshape(-1)
+    _check(load_library().alice_codec_dev_decode_split(d_alc_ptr, alc_stride, _p(s, _u64p), s.size, d_rgb_out_ptr, stream or None))

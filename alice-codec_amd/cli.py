@@ -2,6 +2,8 @@
     python -m alice_codec_amd.cli encode INPUT -o OUT.alc -W 1920 -H 1080 -f 64 [-q 90] [-w cdf53|cdf97|haar]
     python -m alice_codec_amd.cli decode INPUT.alc -o OUT.rgb
     python -m alice_codec_amd.cli info INPUT.alc
+`encode --format split [--lane-symbols N]` writes the split-stream container (.alc version 2, DESIGN.md section 10);
+`decode` and `info` pick the format from the version byte.  The default of every subcommand is version 1.
 Like the reference it treats the whole input file as ONE chunk (src/bin/main.rs:117-122).  `encode-chunks`
 is the extension SURVEY.md section 8f asks for: it cuts a long raw-RGB file into 64-frame chunks
 (DEFAULT_CHUNK_SIZE, src/lib.rs:110) and writes one .alc per chunk."""
@@ -13,7 +15,7 @@ import sys
 import numpy as np
 
 from . import (DEFAULT_CHUNK_SIZE, CodecError, EncodedChunk, FrameDecoder, FrameEncoder, WaveletType, budget_bytes_per_chunk,
-               encode_many, encode_to_size)
+               alc_version, decode_split, encode_many, encode_split, encode_to_size, split_info)
 
 WAVELETS = {"cdf53": WaveletType.Cdf53, "cdf97": WaveletType.Cdf97, "haar": WaveletType.Haar}
 WAVELET_NAMES = {WaveletType.Cdf53: "CDF 5/3", WaveletType.Cdf97: "CDF 9/7", WaveletType.Haar: "Haar"}
@@ -29,6 +31,16 @@ def cmd_encode(a) -> None:
     wt = parse_wavelet(a.wavelet)
     rgb = np.fromfile(a.input, dtype=np.uint8)
     quality = a.quality
+    if a.format == "split":
+        if a.max_bytes is not None:
+            raise ValueError("--max-bytes predicts version 1 sizes; it cannot be combined with --format split")
+        data = encode_split(FrameEncoder.with_wavelet(a.quality, wt), rgb, a.width, a.height, a.frames, a.lane_symbols)
+        with open(a.output, "wb") as f:
+            f.write(data)
+        ratio = 0.0 if rgb.size == 0 else len(data) / rgb.size
+        print(f"encoded {a.width}x{a.height}x{a.frames} ({rgb.size} bytes) -> {len(data)} bytes "
+              f"({ratio * 100:.1f}% ratio, quality={quality}, wavelet={a.wavelet}, format=split)", file=sys.stderr)
+        return
     if a.max_bytes is not None:
         chunk, quality, fits = encode_to_size(rgb, a.width, a.height, a.frames, a.max_bytes, wt, a.min_quality, a.max_quality)
         print(f"chosen quality: {quality}", file=sys.stderr)
@@ -53,10 +65,21 @@ def cmd_encode_chunks(a) -> None:
         raise ValueError("input size is not a whole number of frames")
     n_frames = rgb.size // frame_bytes
     if a.kbps is not None:
+        if a.format == "split":
+            raise ValueError("--kbps predicts version 1 sizes; it cannot be combined with --format split")
         _encode_chunks_to_rate(a, wt, rgb, frame_bytes, n_frames)
         return
     enc = FrameEncoder.with_wavelet(a.quality, wt)
     starts = list(range(0, n_frames, a.chunk))
+    if a.format == "split":   # one chunk uses the whole device: chunk after chunk
+        for k, s0 in enumerate(starts):
+            f = min(a.chunk, n_frames - s0)
+            data = encode_split(enc, np.ascontiguousarray(rgb[s0 * frame_bytes:(s0 + f) * frame_bytes]), a.width, a.height, f,
+                                a.lane_symbols)
+            with open(f"{a.output}.{k:05d}.alc", "wb") as out:
+                out.write(data)
+            print(f"chunk {k}: frames {s0}..{s0 + f - 1} -> {len(data)} bytes", file=sys.stderr)
+        return
     k = 0
     i = 0
     while i < len(starts):
@@ -100,6 +123,12 @@ def _encode_chunks_to_rate(a, wt, rgb, frame_bytes, n_frames) -> None:
 
 def cmd_decode(a) -> None:
     data = np.fromfile(a.input, dtype=np.uint8)
+    if alc_version(data) == 2:
+        i = split_info(data)
+        rgb = decode_split(data)
+        rgb.tofile(a.output)
+        print(f"decoded {i.width}x{i.height}x{i.frames} -> {rgb.size} bytes (raw RGB)", file=sys.stderr)
+        return
     chunk = EncodedChunk.from_bytes(data)
     rgb = FrameDecoder().decode(chunk)
     rgb.tofile(a.output)
@@ -108,6 +137,23 @@ def cmd_decode(a) -> None:
 
 def cmd_info(a) -> None:
     data = np.fromfile(a.input, dtype=np.uint8)
+    if alc_version(data) == 2:
+        i = split_info(data)
+        raw = i.width * i.height * i.frames * 3
+        payload = sum(i.payload_len)
+        print("ALICE-Codec Bitstream Info")
+        print(f"  File:        {a.input}")
+        print(f"  File size:   {data.size} bytes")
+        print("  Format:      split-stream (version 2)")
+        print(f"  Width:       {i.width}")
+        print(f"  Height:      {i.height}")
+        print(f"  Frames:      {i.frames}")
+        print(f"  Wavelet:     {WAVELET_NAMES[i.wavelet_type]}")
+        print(f"  Lane length: {i.lane_symbols} symbols, {sum(i.n_blocks)} blocks")
+        print(f"  Payload:     {payload} bytes")
+        print(f"  Raw size:    {raw} bytes (uncompressed RGB)")
+        print(f"  Ratio:       {0.0 if raw == 0 else payload / raw * 100:.1f}%")
+        return
     chunk = EncodedChunk.from_bytes(data)
     raw = chunk.width * chunk.height * chunk.frames * 3
     ratio = 0.0 if raw == 0 else chunk.compressed_size() / raw
@@ -152,6 +198,8 @@ def main(argv=None) -> int:
         else:
             e.add_argument("--kbps", type=int, default=None, help="target bitrate: a byte budget per chunk (with --fps)")
             e.add_argument("--fps", type=float, default=30.0)
+        e.add_argument("--format", choices=("v1", "split"), default="v1", help="v1: the reference's bitstream; split: .alc version 2")
+        e.add_argument("--lane-symbols", type=int, default=0, help="--format split: symbols per lane (power of two in 64..16384; 0 = default)")
         e.add_argument("--min-quality", type=_u8, default=10)
         e.add_argument("--max-quality", type=_u8, default=95)
     d = sub.add_parser("decode")

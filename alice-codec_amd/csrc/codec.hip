@@ -3111,3 +3111,556 @@ int alice_codec_dev_extract_person_rgb(const void* d_mask, uint32_t width, uint3
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// PART 4: split-stream format (.alc v2; kernels: split.hip)
+//
+// The front end is v1's (forward_chunk / inverse_chunk: the same symbols); only the entropy stage differs.  Nothing here
+// goes through the chain hub: every kernel of this part runs for well under a millisecond per chunk.
+// ------------------------------------------------------------------------------------------
+
+namespace {
+
+bool split_lane_ok(uint32_t L) { return L >= kSplitMinLane && L <= kSplitMaxLane && (L & (L - 1u)) == 0u; }
+uint32_t split_blocks(uint64_t n, uint32_t L) { return (uint32_t)((n + 64ull * L - 1) / (64ull * L)); }   // n <= 2^32: at most 2^20
+
+inline void put_u64(uint8_t* p, uint64_t v) { put_u32(p, (uint32_t)v); put_u32(p + 4, (uint32_t)(v >> 32)); }
+inline uint64_t get_u64(const uint8_t* p) { return (uint64_t)get_u32(p) | ((uint64_t)get_u32(p + 4) << 32); }
+
+struct SplitHeader {
+    uint32_t width = 0, height = 0, frames = 0, lane_symbols = 0;
+    uint8_t wavelet = 0;
+    int32_t step[3] = {1, 1, 1}, dead_zone[3] = {1, 1, 1};
+    uint32_t num_symbols[3] = {0, 0, 0}, n_blocks[3] = {0, 0, 0};
+    uint64_t payload_len[3] = {0, 0, 0};
+    uint16_t freq[3][256] = {};
+};
+
+// Header checks in their fixed order; data: at least min(total_len, kSplitHeaderBytes) readable bytes of a
+// container of total_len bytes.
+int parse_split_header(const uint8_t* data, uint64_t total_len, SplitHeader& h, ChunkDims* d) {
+    if (total_len < kSplitFixedHeaderBytes)
+        return fail(kInvalidBitstream, "data too short for the fixed fields: " + std::to_string(total_len) + " bytes (they take " +
+                                           std::to_string(kSplitFixedHeaderBytes) + ")");
+    if (memcmp(data, "ALCC", 4) != 0) return fail(kInvalidBitstream, "bad magic (expected ALCC)");
+    if (data[4] != 2) return fail(kInvalidBitstream, "unsupported version: " + std::to_string((int)data[4]) + " (expected 2)");
+    if (data[5] > 2) return fail(kInvalidBitstream, "unknown wavelet type byte: " + std::to_string((int)data[5]));
+    h.wavelet = data[5];
+    h.width = get_u32(data + 6); h.height = get_u32(data + 10); h.frames = get_u32(data + 14);
+    h.lane_symbols = get_u32(data + 18);
+    if (!split_lane_ok(h.lane_symbols))
+        return fail(kInvalidBitstream, "lane_symbols " + std::to_string(h.lane_symbols) + " is not a power of two in [64, 16384]");
+    if (total_len < kSplitHeaderBytes)
+        return fail(kInvalidBitstream, "data too short for the header: " + std::to_string(total_len) + " bytes (minimum " + std::to_string(kSplitHeaderBytes) + ")");
+    *d = make_dims(h.width, h.height, h.frames);
+    const unsigned __int128 pix = (unsigned __int128)h.width * h.height * h.frames;
+    if (pix > UINT64_MAX / 3) return fail(kInvalidBitstream, "dimensions overflow");
+    const uint64_t padded = pix == 0 ? 0 : d->padded;
+    uint64_t total = kSplitHeaderBytes;
+    for (int c = 0; c < 3; ++c) {
+        const uint8_t* q = data + kSplitFixedHeaderBytes + (size_t)c * kSplitChannelHeaderBytes;
+        const std::string ch = "channel " + std::to_string(c) + ": ";
+        h.step[c] = (int32_t)get_u32(q); h.dead_zone[c] = (int32_t)get_u32(q + 4);
+        h.num_symbols[c] = get_u32(q + 8); h.n_blocks[c] = get_u32(q + 12);
+        h.payload_len[c] = get_u64(q + 16);
+        // the encoder writes step = quality_to_step(q) in 1..64 and dead zone = step; a decoder multiplies by the step, so
+        // only a step below 1 (no quantiser has one) and a negative dead zone are refused
+        if (h.step[c] < 1 || h.dead_zone[c] < 0)
+            return fail(kInvalidBitstream, ch + "quantiser step " + std::to_string(h.step[c]) + " / dead zone " + std::to_string(h.dead_zone[c]) +
+                                               " (a step is at least 1, a dead zone at least 0)");
+        if ((uint64_t)h.num_symbols[c] != padded)
+            return fail(kInvalidBitstream, ch + "num_symbols " + std::to_string(h.num_symbols[c]) + " != padded_pixels " + std::to_string(padded));
+        if (h.n_blocks[c] != split_blocks(padded, h.lane_symbols))
+            return fail(kInvalidBitstream, ch + "n_blocks " + std::to_string(h.n_blocks[c]) + " does not match num_symbols and lane_symbols");
+        uint32_t sum = 0;
+        for (int i = 0; i < 256; ++i) { h.freq[c][i] = (uint16_t)(q[24 + 2 * i] | (q[25 + 2 * i] << 8)); sum += h.freq[c][i]; }
+        if (sum != (padded ? kProbScale : 0u))
+            return fail(kInvalidBitstream, ch + "frequencies sum to " + std::to_string(sum) + ", not " + std::to_string(padded ? kProbScale : 0u));
+        if (h.payload_len[c] < 132ull * h.n_blocks[c] || h.payload_len[c] > UINT64_MAX / 4)
+            return fail(kInvalidBitstream, ch + "payload_len " + std::to_string(h.payload_len[c]) + " cannot hold its directories");
+        total += h.payload_len[c];
+    }
+    if (total != total_len)
+        return fail(kInvalidBitstream, "length mismatch: header and payloads are " + std::to_string(total) + " bytes, data is " + std::to_string(total_len));
+    return kOk;
+}
+
+// the block tables of a whole container in host memory: every block holds its lane directory and the blocks fill the payload
+int check_split_directories(const uint8_t* data, const SplitHeader& h) {
+    const uint8_t* p = data + kSplitHeaderBytes;
+    for (int c = 0; c < 3; ++c) {
+        uint64_t sum = 4ull * h.n_blocks[c];
+        for (uint32_t b = 0; b < h.n_blocks[c]; ++b) {
+            const uint32_t v = get_u32(p + 4ull * b);
+            if (v < 128u) return fail(kInvalidBitstream, "channel " + std::to_string(c) + ": block " + std::to_string(b) + " is shorter than its lane directory");
+            sum += v;
+        }
+        if (sum != h.payload_len[c])
+            return fail(kInvalidBitstream, "channel " + std::to_string(c) + ": block lengths sum to " + std::to_string(sum) + ", payload_len is " + std::to_string(h.payload_len[c]));
+        p += h.payload_len[c];
+    }
+    return kOk;
+}
+
+// device scratch of n_jobs channel jobs of the same symbol count
+struct SplitWork {
+    int n_jobs = 0;
+    uint32_t n_blocks = 0;
+    DevBuf jobs, tables, freq, cum, blk_len, blk_off, lane_len, totals, flags;
+    std::vector<SplitJob> h;          // edited by the caller between the passes
+    // what the asynchronous uploads read: every upload gets a vector of its own that is never touched again, and the
+    // destructor drains the stream before they (and the device buffers above, on a caller's NULL stream) are released --
+    // also on an error return with kernels still queued
+    std::vector<std::vector<SplitJob>> sent;
+    std::vector<uint16_t> h_cum, h_freq;
+    hipStream_t st = nullptr;
+    bool armed = false;
+    ~SplitWork() { if (armed) (void)hipStreamSynchronize(st); }
+};
+
+int split_work_alloc(SplitWork& w, int n_jobs, uint64_t n, uint32_t L, bool encode) {
+    w.n_jobs = n_jobs;
+    w.n_blocks = split_blocks(n, L);
+    const size_t nb = w.n_blocks;
+    TRY(w.jobs.alloc((size_t)n_jobs * sizeof(SplitJob)));
+    TRY(w.tables.alloc((size_t)n_jobs * sizeof(RansTable)));
+    TRY(w.freq.alloc((size_t)n_jobs * 256 * sizeof(uint16_t)));
+    TRY(w.cum.alloc((size_t)n_jobs * 256 * sizeof(uint16_t)));
+    TRY(w.blk_len.alloc((size_t)n_jobs * nb * sizeof(uint32_t)));
+    TRY(w.blk_off.alloc((size_t)n_jobs * (nb + 1) * sizeof(unsigned long long)));
+    if (encode) TRY(w.lane_len.alloc((size_t)n_jobs * nb * 64 * sizeof(uint16_t)));
+    TRY(w.totals.alloc((size_t)n_jobs * sizeof(unsigned long long)));
+    TRY(w.flags.alloc((size_t)n_jobs * sizeof(uint32_t)));
+    w.h.assign((size_t)n_jobs, SplitJob{});
+    for (int j = 0; j < n_jobs; ++j) {
+        SplitJob& s = w.h[(size_t)j];
+        s.n = n; s.n_blocks = w.n_blocks; s.lane_symbols = L;
+        s.table = w.tables.as<RansTable>() + j;
+        s.blk_len = w.blk_len.as<uint32_t>() + (size_t)j * nb;
+        s.blk_off = w.blk_off.as<unsigned long long>() + (size_t)j * (nb + 1);
+        s.lane_len = encode ? w.lane_len.as<uint16_t>() + (size_t)j * nb * 64 : nullptr;
+        s.flags = w.flags.as<uint32_t>() + j;
+    }
+    return kOk;
+}
+
+int split_upload_jobs(SplitWork& w, hipStream_t st) {
+    w.st = st; w.armed = true;
+    w.sent.push_back(w.h);
+    HIP_TRY(hipMemcpyAsync(w.jobs.p, w.sent.back().data(), w.h.size() * sizeof(SplitJob), hipMemcpyHostToDevice, st));
+    return kOk;
+}
+
+// Tables from the jobs' histograms (device, n_jobs x 256) and the count pass: totals[j] = payload length of job j.  The
+// jobs' symbols (h[j].sym) are set by the caller.  Returns after the stream has drained.
+int split_count(SplitWork& w, const uint32_t* d_hist, hipStream_t st, std::vector<uint64_t>& totals, std::vector<uint16_t>* freq_out) {
+    launch_split_table(d_hist, w.freq.as<uint16_t>(), w.cum.as<uint16_t>(), w.n_jobs, st);
+    for (int j = 0; j < w.n_jobs; ++j)
+        launch_rans_table_from_arrays(w.cum.as<uint16_t>() + (size_t)j * 256, w.freq.as<uint16_t>() + (size_t)j * 256, w.tables.as<RansTable>() + j, st);
+    TRY(split_upload_jobs(w, st));
+    launch_split_count(w.jobs.as<SplitJob>(), w.n_jobs, w.n_blocks, st);
+    launch_split_scan(w.jobs.as<SplitJob>(), w.n_jobs, false, w.totals.as<unsigned long long>(), st);
+    HIP_TRY(hipGetLastError());
+    totals.resize((size_t)w.n_jobs);
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "totals");
+    HIP_TRY(hipMemcpyAsync(totals.data(), w.totals.p, totals.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (freq_out) {
+        freq_out->resize((size_t)w.n_jobs * 256);
+        HIP_TRY(hipMemcpyAsync(freq_out->data(), w.freq.p, freq_out->size() * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return kOk;
+}
+
+// the write pass, after the caller has pointed every h[j].stream at totals[j] writable bytes
+int split_write(SplitWork& w, hipStream_t st) {
+    TRY(split_upload_jobs(w, st));
+    launch_split_write(w.jobs.as<SplitJob>(), w.n_jobs, w.n_blocks, st);
+    HIP_TRY(hipGetLastError());
+    return kOk;
+}
+
+// Decode of the jobs' payloads (h[j].stream / len / sym set by the caller) with the tables of freq (n_jobs x 256, each
+// summing to 4096).  Queues the directory scan and the lane decode; split_decode_verdict reads the flags.
+int split_decode_launch(SplitWork& w, const uint16_t* freq, hipStream_t st) {
+    w.st = st; w.armed = true;
+    w.h_freq.assign(freq, freq + (size_t)w.n_jobs * 256);
+    freq = w.h_freq.data();
+    std::vector<uint16_t>& cum = w.h_cum;
+    cum.assign((size_t)w.n_jobs * 256, 0);
+    for (int j = 0; j < w.n_jobs; ++j) {
+        uint32_t run = 0;
+        for (int i = 0; i < 256; ++i) { cum[(size_t)j * 256 + i] = (uint16_t)run; run += freq[(size_t)j * 256 + i]; }
+    }
+    HIP_TRY(hipMemcpyAsync(w.freq.p, freq, (size_t)w.n_jobs * 256 * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(w.cum.p, cum.data(), cum.size() * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(w.flags.p, 0, (size_t)w.n_jobs * sizeof(uint32_t), st));
+    TRY(split_upload_jobs(w, st));
+    for (int j = 0; j < w.n_jobs; ++j)
+        launch_rans_table_from_arrays(w.cum.as<uint16_t>() + (size_t)j * 256, w.freq.as<uint16_t>() + (size_t)j * 256, w.tables.as<RansTable>() + j, st);
+    launch_split_scan(w.jobs.as<SplitJob>(), w.n_jobs, true, nullptr, st);
+    launch_split_decode(w.jobs.as<SplitJob>(), w.n_jobs, w.n_blocks, st);
+    HIP_TRY(hipGetLastError());
+    return kOk;
+}
+
+int split_decode_verdict(SplitWork& w, hipStream_t st) {
+    std::vector<uint32_t> flags((size_t)w.n_jobs);
+    HIP_TRY(hipMemcpyAsync(flags.data(), w.flags.p, flags.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (size_t j = 0; j < flags.size(); ++j) {
+        if (flags[j] & kSplitBadDirectory) return fail(kInvalidBitstream, "stream " + std::to_string(j) + ": block or lane directory does not add up");
+        if (flags[j]) return fail(kInvalidBitstream, "stream " + std::to_string(j) + ": a lane failed its end check");
+    }
+    return kOk;
+}
+
+// Whole chunks: B equal-shaped chunks at rgb[i] on the device, chunk i at quality q[i].  place(sizes, outs) is called once
+// the sizes are known and names where each chunk's bytes go (device).  Returns after the stream has drained.
+template <typename Place>
+int split_encode_chunks(const RgbLayout* rgb, uint32_t B, const ChunkDims& d, uint8_t wavelet, const uint8_t* q, uint32_t L,
+                        hipStream_t st, std::vector<uint64_t>& sizes, Place place) {
+    EncodeWork ew;
+    ew.d = d; ew.n_chunks = (int)B;
+    if (transform_tiles_eligible(d)) TRY(ew.scratch.alloc(forward_scratch_bytes(d)));
+    TRY(ew.sym.alloc((size_t)B * 3 * d.padded));
+    TRY(ew.hist.alloc((size_t)B * 3 * 256 * sizeof(uint32_t)));
+    HIP_TRY(hipMemsetAsync(ew.hist.p, 0, (size_t)B * 3 * 256 * sizeof(uint32_t), st));
+    for (uint32_t i = 0; i < B; ++i)
+        TRY(forward_chunk(rgb[i], d, wavelet, quality_to_step(q[i]), ew, ew.sym.as<uint8_t>() + (size_t)i * 3 * d.padded,
+                          ew.hist.as<uint32_t>() + (size_t)i * 3 * 256, st));
+    std::vector<SplitHeaderDesc> hd(B);   // (declared before w: w's destructor drains the stream that reads them)
+    DevBuf d_hd;
+    SplitWork w;
+    TRY(split_work_alloc(w, (int)(3 * B), d.padded, L, true));
+    for (size_t j = 0; j < 3 * (size_t)B; ++j) w.h[j].sym = ew.sym.as<uint8_t>() + j * d.padded;
+    std::vector<uint64_t> totals;
+    TRY(split_count(w, ew.hist.as<uint32_t>(), st, totals, nullptr));
+    sizes.resize(B);
+    for (uint32_t i = 0; i < B; ++i) sizes[i] = kSplitHeaderBytes + totals[3 * i] + totals[3 * i + 1] + totals[3 * i + 2];
+    std::vector<uint8_t*> outs(B, nullptr);
+    TRY(place(sizes, outs));
+    TRY(d_hd.alloc((size_t)B * sizeof(SplitHeaderDesc)));
+    for (uint32_t i = 0; i < B; ++i) {
+        SplitHeaderDesc& h = hd[i];
+        h.out = outs[i];
+        h.width = d.w; h.height = d.h; h.frames = d.f; h.lane_symbols = L;
+        h.num_symbols = (uint32_t)d.padded; h.n_blocks = w.n_blocks; h.wavelet = wavelet;
+        h.freq = w.freq.as<uint16_t>() + (size_t)i * 3 * 256;
+        uint64_t off = kSplitHeaderBytes;
+        for (int c = 0; c < 3; ++c) {
+            h.step[c] = h.dead_zone[c] = quality_to_step(q[i]);
+            h.payload_len[c] = totals[3 * i + c];
+            w.h[3 * (size_t)i + c].stream = outs[i] + off;
+            off += totals[3 * i + c];
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(d_hd.p, hd.data(), hd.size() * sizeof(SplitHeaderDesc), hipMemcpyHostToDevice, st));
+    TRY(split_write(w, st));
+    launch_split_headers(d_hd.as<SplitHeaderDesc>(), (int)B, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    return kOk;
+}
+
+// Decode of B equal-shaped chunks: hdr[i] validated, d_alc[i] the chunk's first byte on the device, pixels to rgb[i].
+// Returns after the stream has drained, with the verdict of the end checks.
+int split_decode_chunks(const SplitHeader* hdr, const uint8_t* const* d_alc, uint32_t B, const ChunkDims& d, const RgbLayout* rgb,
+                        hipStream_t st) {
+    DecodeWork dw;
+    dw.d = d; dw.n_chunks = (int)B;
+    TRY(dw.sym.alloc((size_t)B * 3 * d.padded));
+    SplitWork w;
+    TRY(split_work_alloc(w, (int)(3 * B), d.padded, hdr[0].lane_symbols, false));
+    std::vector<uint16_t> freq((size_t)B * 3 * 256);
+    bool all16 = true;
+    for (uint32_t i = 0; i < B; ++i) {
+        uint64_t off = kSplitHeaderBytes;
+        for (int c = 0; c < 3; ++c) {
+            SplitJob& s = w.h[3 * (size_t)i + c];
+            s.sym = dw.sym.as<uint8_t>() + (3 * (size_t)i + c) * d.padded;
+            s.stream = (uint8_t*)d_alc[i] + off;
+            s.len = hdr[i].payload_len[c];
+            off += s.len;
+            memcpy(&freq[(3 * (size_t)i + c) * 256], hdr[i].freq[c], 256 * sizeof(uint16_t));
+        }
+        all16 = all16 && inverse_bounds(hdr[i].wavelet, hdr[i].step).mid16;
+    }
+    if (transform_tiles_eligible(d)) TRY(dw.scratch_own.alloc(inverse_scratch_bytes(d, all16)));
+    TRY(split_decode_launch(w, freq.data(), st));
+    for (uint32_t i = 0; i < B; ++i)
+        TRY(inverse_chunk(dw.sym.as<uint8_t>() + (size_t)i * 3 * d.padded, d, hdr[i].wavelet, hdr[i].step, dw.scratch_own.p, dw, rgb[i], st));
+    HIP_TRY(hipGetLastError());
+    return split_decode_verdict(w, st);
+}
+
+// Chunks a device-resident call works on at a time: as many as keep its symbol buffer at or below 4 GiB (ten 1080p x 64
+// chunks).  Every chunk already fills the device on its own, so larger groups gain nothing, and a 32-chunk group (12.7 GB
+// of symbols) was measured to DEcode eleven times slower per chunk than groups of eight.
+uint32_t split_group(const ChunkDims& d) {
+    const uint64_t per_chunk = 3 * d.padded;
+    const uint64_t g = (uint64_t(4) << 30) / (per_chunk ? per_chunk : 1);
+    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(g, 1), 21845);
+}
+
+void write_empty_split(uint8_t* p, uint8_t wavelet, uint32_t w, uint32_t h, uint32_t f, uint32_t L, int32_t step) {
+    memset(p, 0, kSplitHeaderBytes);
+    memcpy(p, "ALCC", 4);
+    p[4] = 2; p[5] = wavelet;
+    put_u32(p + 6, w); put_u32(p + 10, h); put_u32(p + 14, f); put_u32(p + 18, L);
+    for (int c = 0; c < 3; ++c) {
+        uint8_t* q = p + kSplitFixedHeaderBytes + (size_t)c * kSplitChannelHeaderBytes;
+        put_u32(q, (uint32_t)step); put_u32(q + 4, (uint32_t)step);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t alice_codec_split_stream_bound(uint64_t n, uint32_t lane_symbols) {
+    if (!split_lane_ok(lane_symbols) || n > 0xFFFFFFFFull) return 0;
+    return (uint64_t)split_blocks(n, lane_symbols) * (4 + 128 + 64 * 4) + 2 * n;
+}
+
+int alice_codec_split_normalize(const uint32_t hist[256], uint16_t freq[256]) {
+    clear_error();
+    if (!hist || !freq) return fail(kNullArgument, "null argument");
+    hipStream_t st;
+    TRY(get_stream(&st));
+    DevBuf dh, df, dc;
+    TRY(dh.alloc(256 * 4)); TRY(df.alloc(256 * 2)); TRY(dc.alloc(256 * 2));
+    HIP_TRY(hipMemcpyAsync(dh.p, hist, 256 * 4, hipMemcpyHostToDevice, st));
+    launch_split_table(dh.as<uint32_t>(), df.as<uint16_t>(), dc.as<uint16_t>(), 1, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(freq, df.p, 256 * 2, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return kOk;
+}
+
+int alice_codec_dev_split_encode(const void* d_symbols, uint64_t n, const uint32_t hist[256], uint32_t lane_symbols, void* d_out,
+                                 uint64_t cap, uint64_t* out_len, void* hip_stream) {
+    clear_error();
+    if ((!d_symbols && n) || !hist || !out_len || (!d_out && cap)) return fail(kNullArgument, "null argument");
+    if (!lane_symbols) lane_symbols = kSplitDefaultLane;
+    if (!split_lane_ok(lane_symbols)) return fail(kInvalidDimensions, "lane_symbols must be a power of two in [64, 16384]");
+    if (n > 0xFFFFFFFFull) return fail(kDimensionOverflow, "more symbols than the header's u32 num_symbols counts");
+    uint64_t total = 0;
+    for (int i = 0; i < 256; ++i) total += hist[i];
+    if (total != n) return fail(kInvalidBufferSize, "the histogram counts " + std::to_string(total) + " symbols, n is " + std::to_string(n));
+    *out_len = 0;
+    if (!n) return kOk;
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);
+    DevBuf dh;
+    TRY(dh.alloc(256 * 4));
+    HIP_TRY(hipMemcpyAsync(dh.p, hist, 256 * 4, hipMemcpyHostToDevice, st));
+    SplitWork w;
+    TRY(split_work_alloc(w, 1, n, lane_symbols, true));
+    w.h[0].sym = (const uint8_t*)d_symbols;
+    std::vector<uint64_t> totals;
+    TRY(split_count(w, dh.as<uint32_t>(), st, totals, nullptr));
+    if (totals[0] > cap)
+        return fail(kInvalidBufferSize, "the stream needs " + std::to_string(totals[0]) + " bytes, capacity is " + std::to_string(cap) +
+                                            " (alice_codec_split_stream_bound gives the worst case)");
+    w.h[0].stream = (uint8_t*)d_out;
+    TRY(split_write(w, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *out_len = totals[0];
+    return kOk;
+}
+
+int alice_codec_dev_split_decode(const void* d_stream, uint64_t len, const uint16_t freq[256], uint32_t lane_symbols, void* d_symbols,
+                                 uint64_t n, void* hip_stream) {
+    clear_error();
+    if ((!d_stream && len) || !freq || (!d_symbols && n)) return fail(kNullArgument, "null argument");
+    if (!lane_symbols) lane_symbols = kSplitDefaultLane;
+    if (!split_lane_ok(lane_symbols)) return fail(kInvalidDimensions, "lane_symbols must be a power of two in [64, 16384]");
+    if (n > 0xFFFFFFFFull) return fail(kDimensionOverflow, "more symbols than the header's u32 num_symbols counts");
+    uint32_t sum = 0;
+    for (int i = 0; i < 256; ++i) sum += freq[i];
+    if (sum != (n ? kProbScale : 0u)) return fail(kInvalidBitstream, "frequencies sum to " + std::to_string(sum) + ", not " + std::to_string(n ? kProbScale : 0u));
+    if (!n) return len == 0 ? (int)kOk : fail(kInvalidBitstream, "an empty channel has no payload");
+    if (len < 132ull * split_blocks(n, lane_symbols)) return fail(kInvalidBitstream, "the payload cannot hold its directories");
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);
+    SplitWork w;
+    TRY(split_work_alloc(w, 1, n, lane_symbols, false));
+    w.h[0].sym = (const uint8_t*)d_symbols;
+    w.h[0].stream = (uint8_t*)d_stream;
+    w.h[0].len = len;
+    TRY(split_decode_launch(w, freq, st));
+    return split_decode_verdict(w, st);
+}
+
+int alice_codec_split_info(const uint8_t* data, uint64_t len, AliceSplitInfo* info) {
+    clear_error();
+    if (!data || !info) return fail(kNullArgument, "null argument");
+    SplitHeader h;
+    ChunkDims d{};
+    TRY(parse_split_header(data, len, h, &d));
+    TRY(check_split_directories(data, h));
+    memset(info, 0, sizeof(*info));
+    info->width = h.width; info->height = h.height; info->frames = h.frames;
+    info->lane_symbols = h.lane_symbols; info->wavelet = h.wavelet;
+    for (int c = 0; c < 3; ++c) {
+        info->quant_step[c] = h.step[c]; info->dead_zone[c] = h.dead_zone[c];
+        info->num_symbols[c] = h.num_symbols[c]; info->n_blocks[c] = h.n_blocks[c];
+        info->payload_len[c] = h.payload_len[c];
+    }
+    return kOk;
+}
+
+uint8_t* alice_codec_encode_split(const FrameEncoder* encoder, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
+                                  uint32_t frames, uint32_t lane_symbols, uint64_t* out_len) {
+    clear_error();
+    if (!encoder || !rgb || !out_len) { fail(kNullArgument, "null argument"); return nullptr; }
+    auto run = [&](uint8_t** out) -> int {
+        uint64_t n_pixels = 0;
+        TRY(checked_pixel_count(width, height, frames, &n_pixels));
+        if (n_pixels == 0 && rgb_len != 0) return fail(kInvalidBufferSize, "buffer size mismatch: expected 0, got " + std::to_string(rgb_len));
+        ChunkDims d{};
+        EncodedChunk* none = nullptr;
+        if (n_pixels) TRY(validate_encode_many(encoder, rgb, rgb_len, width, height, frames, 1, &none, &d));
+        const uint32_t L = lane_symbols ? lane_symbols : kSplitDefaultLane;
+        if (!split_lane_ok(L)) return fail(kInvalidDimensions, "lane_symbols must be a power of two in [64, 16384]");
+        if (n_pixels == 0) {
+            *out = host_result_alloc(kSplitHeaderBytes);
+            if (!*out) return fail(kOutOfMemory, "out of host memory");
+            write_empty_split(*out, encoder->wavelet, width, height, frames, L, quality_to_step(encoder->quality));
+            *out_len = kSplitHeaderBytes;
+            return kOk;
+        }
+        hipStream_t st;
+        TRY(get_stream(&st));
+        DevBuf d_rgb, d_out;
+        TRY(d_rgb.alloc(n_pixels * 3));
+        HIP_TRY(hipMemcpyAsync(d_rgb.p, rgb, n_pixels * 3, hipMemcpyHostToDevice, st));
+        const RgbLayout layout = packed_rgb(d_rgb.p, d);
+        std::vector<uint64_t> sizes;
+        TRY(split_encode_chunks(&layout, 1, d, encoder->wavelet, &encoder->quality, L, st, sizes,
+                                [&](const std::vector<uint64_t>& sz, std::vector<uint8_t*>& outs) -> int {
+                                    TRY(d_out.alloc(sz[0]));
+                                    outs[0] = d_out.as<uint8_t>();
+                                    return kOk;
+                                }));
+        *out = host_result_alloc(sizes[0]);
+        if (!*out) return fail(kOutOfMemory, "out of host memory");
+        const int rc = copy_to_host(*out, d_out.p, sizes[0], st);
+        if (rc != kOk) { free(*out); *out = nullptr; return rc; }
+        *out_len = sizes[0];
+        return kOk;
+    };
+    uint8_t* out = nullptr;
+    return run(&out) == kOk ? out : nullptr;
+}
+
+uint8_t* alice_codec_decode_split(const uint8_t* data, uint64_t len, uint64_t* out_len) {
+    clear_error();
+    if (!data || !out_len) { fail(kNullArgument, "null argument"); return nullptr; }
+    auto run = [&](uint8_t** out) -> int {
+        SplitHeader h;
+        ChunkDims d{};
+        TRY(parse_split_header(data, len, h, &d));
+        TRY(check_split_directories(data, h));
+        const uint64_t bytes = (uint64_t)h.width * h.height * h.frames * 3;
+        *out = host_result_alloc(bytes);
+        if (!*out) return fail(kOutOfMemory, "out of host memory");
+        *out_len = bytes;
+        if (!bytes) return kOk;
+        auto body = [&]() -> int {
+            hipStream_t st;
+            TRY(get_stream(&st));
+            DevBuf d_alc, d_rgb;
+            TRY(d_alc.alloc(len));
+            TRY(d_rgb.alloc(bytes));
+            HIP_TRY(hipMemcpyAsync(d_alc.p, data, len, hipMemcpyHostToDevice, st));
+            const uint8_t* p = d_alc.as<uint8_t>();
+            const RgbLayout layout = packed_rgb(d_rgb.p, d);
+            TRY(split_decode_chunks(&h, &p, 1, d, &layout, st));
+            return copy_to_host(*out, d_rgb.p, bytes, st);
+        };
+        const int rc = body();
+        if (rc != kOk) { free(*out); *out = nullptr; }
+        return rc;
+    };
+    uint8_t* out = nullptr;
+    return run(&out) == kOk ? out : nullptr;
+}
+
+int alice_codec_dev_encode_split(const void* d_rgb, uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks,
+                                 uint8_t wavelet_type, uint8_t quality, const uint8_t* qualities, uint32_t lane_symbols, void* d_out,
+                                 uint64_t out_stride, uint64_t* sizes, void* hip_stream) {
+    clear_error();
+    if (!d_rgb || !d_out || !sizes) return fail(kNullArgument, "null argument");
+    if (wavelet_type > 2) return fail(kInvalidBitstream, "unknown wavelet type");
+    ChunkDims d{};
+    TRY(chunk_dims(width, height, frames, &d, n_chunks));
+    const uint32_t L = lane_symbols ? lane_symbols : kSplitDefaultLane;
+    if (!split_lane_ok(L)) return fail(kInvalidDimensions, "lane_symbols must be a power of two in [64, 16384]");
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);
+    std::vector<RgbLayout> layouts(n_chunks);
+    std::vector<uint8_t> q(n_chunks);
+    for (uint32_t i = 0; i < n_chunks; ++i) {
+        layouts[i] = packed_rgb((const uint8_t*)d_rgb + (size_t)i * d.n_pixels * 3, d);
+        q[i] = qualities ? qualities[i] : quality;
+    }
+    const uint32_t group = split_group(d);
+    for (uint32_t first = 0; first < n_chunks; first += group) {
+        const uint32_t B = std::min(group, n_chunks - first);
+        std::vector<uint64_t> sz;
+        TRY(split_encode_chunks(layouts.data() + first, B, d, wavelet_type, q.data() + first, L, st, sz,
+                                [&](const std::vector<uint64_t>& s, std::vector<uint8_t*>& outs) -> int {
+                                    for (uint32_t i = 0; i < B; ++i) {
+                                        if (s[i] > out_stride)
+                                            return fail(kInvalidBufferSize, "chunk " + std::to_string(first + i) + " needs " + std::to_string(s[i]) +
+                                                                                " bytes, the output stride is " + std::to_string(out_stride));
+                                        outs[i] = (uint8_t*)d_out + (size_t)(first + i) * out_stride;
+                                    }
+                                    return kOk;
+                                }));
+        for (uint32_t i = 0; i < B; ++i) sizes[first + i] = sz[i];
+    }
+    return kOk;
+}
+
+int alice_codec_dev_decode_split(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks, void* d_rgb_out,
+                                 void* hip_stream) {
+    clear_error();
+    if (!d_alc || !sizes || !d_rgb_out) return fail(kNullArgument, "null argument");
+    if (n_chunks == 0) return fail(kInvalidDimensions, "empty batch");
+    for (uint32_t i = 0; i < n_chunks; ++i)
+        if (sizes[i] > alc_stride && n_chunks > 1) return fail(kInvalidBufferSize, "chunk " + std::to_string(i) + " is longer than the stride");
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);
+    std::vector<uint8_t> raw((size_t)n_chunks * kSplitHeaderBytes, 0);
+    for (uint32_t i = 0; i < n_chunks; ++i)
+        HIP_TRY(hipMemcpyAsync(raw.data() + (size_t)i * kSplitHeaderBytes, (const uint8_t*)d_alc + (size_t)i * alc_stride,
+                               std::min<uint64_t>(sizes[i], kSplitHeaderBytes), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    std::vector<SplitHeader> hdr(n_chunks);
+    std::vector<const uint8_t*> ptr(n_chunks);
+    std::vector<RgbLayout> layouts(n_chunks);
+    ChunkDims d{};
+    for (uint32_t i = 0; i < n_chunks; ++i) {
+        ChunkDims di{};
+        TRY(parse_split_header(raw.data() + (size_t)i * kSplitHeaderBytes, sizes[i], hdr[i], &di));
+        if (di.n_pixels == 0) return fail(kInvalidDimensions, "invalid dimensions");
+        if (i == 0) d = di;
+        else if (di.w != d.w || di.h != d.h || di.f != d.f || hdr[i].lane_symbols != hdr[0].lane_symbols)
+            return fail(kInvalidDimensions, "the chunks of one call must have the same shape and lane_symbols");
+        ptr[i] = (const uint8_t*)d_alc + (size_t)i * alc_stride;
+        layouts[i] = packed_rgb((uint8_t*)d_rgb_out + (size_t)i * d.n_pixels * 3, d);
+    }
+    const uint32_t group = split_group(d);
+    for (uint32_t first = 0; first < n_chunks; first += group)
+        TRY(split_decode_chunks(hdr.data() + first, ptr.data() + first, std::min(group, n_chunks - first), d, layouts.data() + first, st));
+    return kOk;
+}
+
+}  // extern "C"

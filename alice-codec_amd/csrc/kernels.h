@@ -241,4 +241,43 @@ void launch_rate_fold(const uint32_t* d_bins, const uint32_t* d_oor, uint32_t n_
 // d_log: the lo and hi arrays of rate_log_table() back to back on the device; out: [chunk][step - 1][channel]
 void launch_rate_cost(const uint32_t* d_step_hist, const uint32_t* d_log, uint32_t n_chunks, RateChannel* d_out, hipStream_t st);
 
+// ---- split.hip: the split-stream entropy stage of .alc v2 ----
+constexpr uint32_t kSplitFixedHeaderBytes = 22;      // magic, version, wavelet, width, height, frames, lane_symbols
+constexpr uint32_t kSplitChannelHeaderBytes = 536;   // step, dead zone, num_symbols, n_blocks, payload_len u64, 256 x u16
+constexpr uint32_t kSplitHeaderBytes = kSplitFixedHeaderBytes + 3 * kSplitChannelHeaderBytes;   // 1630
+constexpr uint32_t kSplitMinLane = 64, kSplitMaxLane = 16384, kSplitDefaultLane = 512;
+constexpr uint32_t kSplitBadDirectory = 1u;   // block table or lane directory does not add up to the payload
+constexpr uint32_t kSplitBadLane = 2u;        // a lane failed its end check
+// One channel: n symbols in blocks of 64 * lane_symbols, payload at `stream`.
+struct SplitJob {
+    const uint8_t* sym;        // encode: the symbols; decode: where they go (written)
+    unsigned long long n;
+    const RansTable* table;
+    uint8_t* stream;           // the channel's payload: u32 block lengths, then the blocks
+    unsigned long long len;    // decode: length of the payload
+    uint32_t n_blocks, lane_symbols;
+    uint32_t* blk_len;         // scratch, n_blocks
+    unsigned long long* blk_off;   // scratch, n_blocks + 1
+    uint16_t* lane_len;        // scratch, 64 * n_blocks (encode)
+    uint32_t* flags;           // decode: kSplitBad*, zeroed by the caller
+};
+struct SplitHeaderDesc {
+    uint8_t* out;
+    uint32_t width, height, frames, lane_symbols, num_symbols, n_blocks;
+    int32_t step[3], dead_zone[3];
+    unsigned long long payload_len[3];
+    const uint16_t* freq;      // device, 3 x 256
+    uint8_t wavelet;
+};
+// hist [n_tables][256] -> freq, cum [n_tables][256]
+void launch_split_table(const uint32_t* d_hist, uint16_t* d_freq, uint16_t* d_cum, int n_tables, hipStream_t st);
+// max_blocks: the largest n_blocks among the jobs.  count fills lane_len and blk_len; scan(from_stream = false) turns
+// blk_len into blk_off and the payload lengths d_totals[job]; write then needs `stream` to hold that many bytes.
+void launch_split_count(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, hipStream_t st);
+void launch_split_write(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, hipStream_t st);
+void launch_split_scan(const SplitJob* d_jobs, int n_jobs, bool from_stream, unsigned long long* d_totals, hipStream_t st);
+// after scan(from_stream = true); *flags != 0 afterwards: the payload is not a valid stream
+void launch_split_decode(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, hipStream_t st);
+void launch_split_headers(const SplitHeaderDesc* d_descs, int n_chunks, hipStream_t st);
+
 }  // namespace alice

@@ -1,0 +1,388 @@
+// Split-stream entropy stage (.alc v2) for gfx950.
+//
+// A channel's symbols are cut into blocks of 64 * L consecutive symbols; inside a block lane j owns symbols j, j + 64,
+// j + 128, ... and codes them as an independent rANS chain with the reference coder's parameters (32-bit state, lower
+// bound 2^23, byte renormalisation, 12-bit scale; src/rans.rs:269-308, 351-371 in the reference).  One wavefront per
+// block, one lane per chain: the opposite operating point to the v1 chain kernels of rans.hip -- tens of thousands of
+// short chains, several wavefronts per SIMD, latency hidden by occupancy instead of by a stripped dependency chain.
+//
+// Kernels:
+//   split_table_kernel    histogram -> normalised frequencies (sum exactly 4096) and their running sum
+//   split_encode_kernel   <false> counts every lane's stream length, <true> writes directory and streams in place
+//   split_scan_kernel     block lengths -> block offsets (encode: from the count pass; decode: from the stream, validated)
+//   split_decode_kernel   lane streams -> symbols, with the end check of every lane
+//   split_header_kernel   the 1630-byte container header of whole chunks
+// The output is sized by counting first and writing second: the chain arithmetic runs twice, but nothing is staged in
+// worst-case slots (2 bytes per symbol) and no compaction pass moves the payload again.
+//
+// Every store to memory is a vector store; the scalar unit only reads.
+#include "common.h"
+#include "kernels.h"
+
+namespace alice {
+
+namespace {
+
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t o = __shfl_up(v, d, 64);
+        if (lane >= d) v += o;
+    }
+    return v;
+}
+
+// max over the 256 threads of a block; red: 4 u32 of LDS
+__device__ __forceinline__ uint32_t block_max_256(uint32_t v, uint32_t* red) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint32_t o = __shfl_xor(v, d, 64);
+        v = o > v ? o : v;
+    }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const uint32_t a = red[0] > red[1] ? red[0] : red[1], b = red[2] > red[3] ? red[2] : red[3];
+    return a > b ? a : b;
+}
+
+__device__ __forceinline__ unsigned long long block_sum_256(unsigned long long v, unsigned long long* red) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return red[0] + red[1] + red[2] + red[3];
+}
+
+}  // namespace
+
+// ----------------------------------------------------------------------------------
+// Normalisation: freq = max(1, floor(count * 4096 / total)) for a present symbol, 0 for an absent one;
+// a short sum gives the whole deficit to the largest frequency (lowest symbol on ties); a sum that is over takes one at
+// a time from the currently largest frequency (lowest symbol on ties).  The excess is at most the number of symbols the
+// floor of 1 lifted, so the loop runs at most 255 rounds.  One 256-thread workgroup per table.
+// ----------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void split_table_kernel(const uint32_t* __restrict__ hist, uint16_t* __restrict__ freq,
+                                                          uint16_t* __restrict__ cum) {
+    __shared__ unsigned long long red64[4];
+    __shared__ uint32_t red32[4];
+    __shared__ uint32_t scan[256];
+    const int s = threadIdx.x;
+    const size_t t = blockIdx.x;
+    const uint32_t count = hist[t * 256 + s];
+    const unsigned long long total = block_sum_256(count, red64);
+    uint32_t f = 0u;
+    if (count) {
+        f = (uint32_t)(((unsigned long long)count << kProbBits) / total);
+        if (f < 1u) f = 1u;
+    }
+    if (total) {
+        uint32_t sum = (uint32_t)block_sum_256(f, red64);
+        // key: larger frequency first, then the lower symbol
+        uint32_t top = block_max_256((f << 8) | (255u - (uint32_t)s), red32);
+        if (sum < kProbScale) {
+            if (255u - (top & 255u) == (uint32_t)s) f += kProbScale - sum;
+        } else {
+            while (sum > kProbScale) {   // uniform across the block
+                if (255u - (top & 255u) == (uint32_t)s) f -= 1u;
+                sum -= 1u;
+                top = block_max_256((f << 8) | (255u - (uint32_t)s), red32);
+            }
+        }
+    }
+    scan[s] = f;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {
+        const uint32_t o = s >= d ? scan[s - d] : 0u;
+        __syncthreads();
+        scan[s] += o;
+        __syncthreads();
+    }
+    freq[t * 256 + s] = (uint16_t)f;
+    cum[t * 256 + s] = (uint16_t)(scan[s] - f);
+}
+
+// ----------------------------------------------------------------------------------
+// Encoder.  A workgroup is four wavefronts = four blocks of job blockIdx.y.  The table rows sit in LDS, 16 bytes each
+// (one ds_read_b128 per symbol): xmax = freq << 19, the exact reciprocal, cum bias, and 4096 - freq with the shift.
+// The chain walks a lane's symbols last to first and writes its bytes back to front, so the finished stream reads
+// forward: four state bytes, most significant first, then the renormalisation bytes in the order the decoder wants them.
+// ----------------------------------------------------------------------------------
+template <bool kWrite>
+__global__ __launch_bounds__(256) void split_encode_kernel(const SplitJob* __restrict__ jobs) {
+    __shared__ uint4 rows[256];
+    const SplitJob job = jobs[blockIdx.y];
+    {
+        const RansEncEntry e = job.table->enc[threadIdx.x];
+        rows[threadIdx.x] = make_uint4(e.xmax, e.rcp, e.cbias, (uint32_t)e.g | (e.rsh << 16));
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const unsigned long long b = (unsigned long long)blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (b >= job.n_blocks) return;
+    const unsigned long long base = b * 64ull * job.lane_symbols;
+    const unsigned long long left = job.n - base;
+    const uint32_t in_block = left < 64ull * job.lane_symbols ? (uint32_t)left : 64u * job.lane_symbols;
+    const uint32_t k = (uint32_t)lane < in_block ? (in_block - (uint32_t)lane + 63u) / 64u : 0u;
+    const uint32_t kmax = (in_block + 63u) / 64u;   // lane 0's count
+    const uint8_t* __restrict__ sym = job.sym + base + lane;
+
+    uint32_t len = 0u;              // bytes of this lane's stream
+    uint8_t* out = nullptr;         // kWrite: one past the lane's last byte
+    uint32_t acc = 0u, nacc = 0u;   // kWrite: bytes collected for the dword in progress (lowest address in the low byte)
+    if (kWrite) {
+        len = job.lane_len[b * 64u + lane];
+        const uint32_t incl = wave_incl_scan(len, lane);
+        uint8_t* blk = job.stream + job.blk_off[b];
+        blk[2 * lane] = (uint8_t)len;
+        blk[2 * lane + 1] = (uint8_t)(len >> 8);
+        if (lane < 4) job.stream[4ull * b + lane] = (uint8_t)(job.blk_len[b] >> (8 * lane));
+        out = blk + 128u + incl;
+    }
+    auto put = [&](uint32_t byte) {
+        if (kWrite) {
+            --out;
+            acc = (acc << 8) | byte;
+            ++nacc;
+            if (((uintptr_t)out & 3u) == 0u) {
+                if (nacc == 4u) *(uint32_t*)out = acc;
+                else for (uint32_t t = 0; t < nacc; ++t) out[t] = (uint8_t)(acc >> (8u * t));
+                nacc = 0u;
+            }
+        } else {
+            ++len;
+        }
+    };
+    uint32_t x = kRansL;
+    // eight symbols are loaded ahead of the chain that consumes them
+    for (uint32_t hi = kmax; hi > 0u; hi = hi > 8u ? hi - 8u : 0u) {
+        uint32_t s[8];
+#pragma unroll
+        for (uint32_t u = 0; u < 8u; ++u) {
+            const uint32_t i = hi - 1u - u;   // wraps past 0: then i >= k
+            s[u] = i < k ? sym[(size_t)i * 64u] : 0u;
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < 8u; ++u) {
+            const uint32_t i = hi - 1u - u;
+            if (i < k) {
+                const uint4 r = rows[s[u]];
+                if (x >= r.x) { put(x & 255u); x >>= 8; }
+                if (x >= r.x) { put(x & 255u); x >>= 8; }
+                const uint32_t q = __umulhi(x, r.y) >> (r.w >> 16);
+                x = x + q * (r.w & 0xFFFFu) + r.z;
+            }
+        }
+    }
+    if (k) {
+        put(x & 255u); put((x >> 8) & 255u); put((x >> 16) & 255u); put(x >> 24);
+    }
+    if (kWrite) {
+        for (uint32_t t = 0; t < nacc; ++t) out[t] = (uint8_t)(acc >> (8u * t));
+    } else {
+        job.lane_len[b * 64u + lane] = (uint16_t)len;
+        const uint32_t incl = wave_incl_scan(len, lane);
+        if (lane == 63) job.blk_len[b] = 128u + incl;
+    }
+}
+
+// ----------------------------------------------------------------------------------
+// Block offsets: blk_off[b] = 4 * n_blocks + sum of the lengths of the blocks before b; blk_off[n_blocks] = the payload's
+// length.  One workgroup per job.  kFromStream: the lengths are the u32 table at the head of the payload (any alignment),
+// and the scan is the directory check of the decoder: a table that does not fit, a block shorter than its lane directory
+// or a sum that is not the payload's length sets kSplitBadDirectory, and offsets are clamped so that no block reaches
+// outside the payload.
+// ----------------------------------------------------------------------------------
+template <bool kFromStream>
+__global__ __launch_bounds__(256) void split_scan_kernel(const SplitJob* __restrict__ jobs, unsigned long long* __restrict__ totals) {
+    __shared__ unsigned long long sc[256];
+    __shared__ uint32_t bad_sh;
+    const SplitJob job = jobs[blockIdx.x];
+    const int s = threadIdx.x;
+    if (s == 0) bad_sh = 0u;
+    __syncthreads();
+    const unsigned long long head = 4ull * job.n_blocks;
+    const bool table_fits = !kFromStream || head <= job.len;
+    unsigned long long carry = head;
+    for (unsigned long long b0 = 0; b0 < job.n_blocks; b0 += 256u) {
+        const unsigned long long b = b0 + s;
+        unsigned long long v = 0;
+        if (b < job.n_blocks) {
+            if (kFromStream) {
+                if (table_fits) {
+                    const uint8_t* p = job.stream + 4ull * b;
+                    v = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+                    job.blk_len[b] = (uint32_t)v;
+                }
+            } else {
+                v = job.blk_len[b];
+            }
+        }
+        sc[s] = v;
+        __syncthreads();
+        for (int d = 1; d < 256; d <<= 1) {
+            const unsigned long long o = s >= d ? sc[s - d] : 0ull;
+            __syncthreads();
+            sc[s] += o;
+            __syncthreads();
+        }
+        if (b < job.n_blocks) {
+            const unsigned long long off = carry + sc[s] - v;
+            if (kFromStream && (v < 128u || off + v > job.len)) {
+                bad_sh = 1u;
+                job.blk_len[b] = 0u;   // the decode kernel skips the block
+                job.blk_off[b] = 0ull;
+            } else {
+                job.blk_off[b] = off;
+            }
+        }
+        carry += sc[255];
+        __syncthreads();
+    }
+    if (s == 0) {
+        job.blk_off[job.n_blocks] = carry;
+        if (totals) totals[blockIdx.x] = carry;
+        if (kFromStream && (bad_sh || !table_fits || carry != job.len)) *job.flags = kSplitBadDirectory;
+    }
+}
+
+// ----------------------------------------------------------------------------------
+// Decoder: the geometry of the encoder.  LDS holds the slot -> symbol map (4096 x u8) and freq | cum << 16 per symbol.
+// A lane reads its stream four bytes at a time; a read never leaves [lane start, lane end): past the end the window
+// is zero-filled and the cursor keeps counting, so a damaged stream ends in a failed end check (state back at 2^23,
+// cursor at the end of the stream) and never in an access outside the payload.  Every symbol store lies inside the block.
+// ----------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void split_decode_kernel(const SplitJob* __restrict__ jobs) {
+    __shared__ uint32_t c2s_sh[kProbScale / 4];
+    __shared__ uint32_t symtab[256];
+    const SplitJob job = jobs[blockIdx.y];
+    {
+        const uint32_t* src = (const uint32_t*)job.table->dec.c2s;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) c2s_sh[threadIdx.x + 256 * t] = src[threadIdx.x + 256 * t];
+        symtab[threadIdx.x] = job.table->dec.symtab[threadIdx.x];
+    }
+    __syncthreads();
+    const uint8_t* c2s = (const uint8_t*)c2s_sh;
+    const int lane = threadIdx.x & 63;
+    const unsigned long long b = (unsigned long long)blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (b >= job.n_blocks) return;
+    const unsigned long long base = b * 64ull * job.lane_symbols;
+    const unsigned long long left = job.n - base;
+    const uint32_t in_block = left < 64ull * job.lane_symbols ? (uint32_t)left : 64u * job.lane_symbols;
+    const uint32_t k = (uint32_t)lane < in_block ? (in_block - (uint32_t)lane + 63u) / 64u : 0u;
+    uint8_t* __restrict__ sym = (uint8_t*)job.sym + base + lane;
+
+    const uint32_t blen = job.blk_len[b];
+    const unsigned long long boff = job.blk_off[b];
+    // (the scan left 0 for a block it refused; checked again here so that the bounds do not rest on another kernel)
+    if (blen < 128u || boff + blen > job.len) { if (lane == 0) *job.flags = kSplitBadDirectory; return; }
+    const uint8_t* blk = job.stream + boff;
+    const uint32_t len = (uint32_t)blk[2 * lane] | ((uint32_t)blk[2 * lane + 1] << 8);
+    const uint32_t incl = wave_incl_scan(len, lane);
+    const uint32_t all = __shfl(incl, 63, 64);
+    if (all + 128u != blen) { if (lane == 0) *job.flags = kSplitBadDirectory; return; }
+    const uint8_t* __restrict__ src = blk + 128u + (incl - len);   // [src, src + len) lies inside the block
+
+    uint32_t win = 0u, nwin = 0u, fpos = 0u, pos = 0u;
+    auto take = [&]() -> uint32_t {
+        if (nwin == 0u) {
+            uint32_t w = 0u;
+            if (fpos + 4u <= len) {
+                uint32_t t;
+                __builtin_memcpy(&t, src + fpos, 4);
+                w = __builtin_bswap32(t);
+            } else {
+#pragma unroll
+                for (uint32_t t = 0; t < 4u; ++t) w = (w << 8) | (fpos + t < len ? (uint32_t)src[fpos + t] : 0u);
+            }
+            fpos += 4u;
+            win = w;
+            nwin = 4u;
+        }
+        const uint32_t byte = win >> 24;
+        win <<= 8;
+        --nwin;
+        ++pos;
+        return byte;
+    };
+    bool ok = true;
+    if (k == 0u) {
+        ok = len == 0u;
+    } else {
+        uint32_t x = take() << 24;
+        x |= take() << 16;
+        x |= take() << 8;
+        x |= take();
+        for (uint32_t i = 0; i < k; ++i) {
+            const uint32_t slot = x & (kProbScale - 1u);
+            const uint32_t s = c2s[slot];
+            const uint32_t fc = symtab[s];
+            x = (fc & 0xFFFFu) * (x >> kProbBits) + slot - (fc >> 16);
+            if (x < kRansL) x = (x << 8) | take();
+            if (x < kRansL) x = (x << 8) | take();
+            sym[(size_t)i * 64u] = (uint8_t)s;
+        }
+        ok = x == kRansL && pos == len;
+    }
+    if (!ok) *job.flags = kSplitBadLane;
+}
+
+// ----------------------------------------------------------------------------------
+// Container header of whole chunks, one workgroup per chunk.
+// ----------------------------------------------------------------------------------
+__device__ __forceinline__ void put_le(uint8_t* p, unsigned long long v, int bytes) {
+    for (int i = 0; i < bytes; ++i) p[i] = (uint8_t)(v >> (8 * i));
+}
+
+__global__ __launch_bounds__(256) void split_header_kernel(const SplitHeaderDesc* __restrict__ descs) {
+    const SplitHeaderDesc h = descs[blockIdx.x];
+    uint8_t* p = h.out;
+    const int s = threadIdx.x;
+    if (s == 0) {
+        p[0] = 'A'; p[1] = 'L'; p[2] = 'C'; p[3] = 'C'; p[4] = 2; p[5] = h.wavelet;
+        put_le(p + 6, h.width, 4); put_le(p + 10, h.height, 4); put_le(p + 14, h.frames, 4);
+        put_le(p + 18, h.lane_symbols, 4);
+    }
+    for (int c = 0; c < 3; ++c) {
+        uint8_t* q = p + kSplitFixedHeaderBytes + c * kSplitChannelHeaderBytes;
+        if (s == 0) {
+            put_le(q, (uint32_t)h.step[c], 4); put_le(q + 4, (uint32_t)h.dead_zone[c], 4);
+            put_le(q + 8, h.num_symbols, 4); put_le(q + 12, h.n_blocks, 4);
+            put_le(q + 16, h.payload_len[c], 8);
+        }
+        const uint16_t f = h.freq[c * 256 + s];
+        q[24 + 2 * s] = (uint8_t)f;
+        q[25 + 2 * s] = (uint8_t)(f >> 8);
+    }
+}
+
+// ----------------------------------------------------------------------------------
+// launchers
+// ----------------------------------------------------------------------------------
+void launch_split_table(const uint32_t* d_hist, uint16_t* d_freq, uint16_t* d_cum, int n_tables, hipStream_t st) {
+    if (n_tables > 0) hipLaunchKernelGGL(split_table_kernel, dim3(n_tables), dim3(256), 0, st, d_hist, d_freq, d_cum);
+}
+
+static dim3 split_grid(uint32_t max_blocks, int n_jobs) { return dim3((max_blocks + 3u) / 4u, (unsigned)n_jobs); }
+
+void launch_split_count(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, hipStream_t st) {
+    if (n_jobs > 0 && max_blocks) hipLaunchKernelGGL(split_encode_kernel<false>, split_grid(max_blocks, n_jobs), dim3(256), 0, st, d_jobs);
+}
+void launch_split_write(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, hipStream_t st) {
+    if (n_jobs > 0 && max_blocks) hipLaunchKernelGGL(split_encode_kernel<true>, split_grid(max_blocks, n_jobs), dim3(256), 0, st, d_jobs);
+}
+void launch_split_scan(const SplitJob* d_jobs, int n_jobs, bool from_stream, unsigned long long* d_totals, hipStream_t st) {
+    if (n_jobs <= 0) return;
+    if (from_stream) hipLaunchKernelGGL(split_scan_kernel<true>, dim3(n_jobs), dim3(256), 0, st, d_jobs, d_totals);
+    else hipLaunchKernelGGL(split_scan_kernel<false>, dim3(n_jobs), dim3(256), 0, st, d_jobs, d_totals);
+}
+void launch_split_decode(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, hipStream_t st) {
+    if (n_jobs > 0 && max_blocks) hipLaunchKernelGGL(split_decode_kernel, split_grid(max_blocks, n_jobs), dim3(256), 0, st, d_jobs);
+}
+void launch_split_headers(const SplitHeaderDesc* d_descs, int n_chunks, hipStream_t st) {
+    if (n_chunks > 0) hipLaunchKernelGGL(split_header_kernel, dim3(n_chunks), dim3(256), 0, st, d_descs);
+}
+
+}  // namespace alice

@@ -618,3 +618,124 @@ pub fn paste_from_bbox(frame: &mut [u8], frame_width: u32, person_data: &[u8], b
     }
     Ok(())
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// split-stream format (.alc version 2).  An extension: version 1 (FrameEncoder::encode,
+// EncodedChunk) stays the reference's bitstream byte for byte; version 2 keeps transform, quantiser and symbols and
+// codes them as independent lanes with a table that sums to 4096 -- for video that comes back and for the latency of
+// one chunk.  EncodedChunk::from_bytes refuses version 2; alc_version tells the two apart.
+// ---------------------------------------------------------------------------------------------------------------
+
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
+struct RawSplitInfo {
+    width: u32, height: u32, frames: u32, lane_symbols: u32,
+    wavelet: u8, reserved: [u8; 3],
+    quant_step: [i32; 3], dead_zone: [i32; 3],
+    num_symbols: [u32; 3], n_blocks: [u32; 3],
+    payload_len: [u64; 3],
+}
+
+#[link(name = "alice_codec")]
+extern "C" {
+    fn alice_codec_split_stream_bound(n: u64, lane_symbols: u32) -> u64;
+    fn alice_codec_split_normalize(hist: *const u32, freq: *mut u16) -> c_int;
+    fn alice_codec_split_info(data: *const u8, len: u64, info: *mut RawSplitInfo) -> c_int;
+    fn alice_codec_encode_split(e: *const RawEncoder, rgb: *const u8, rgb_len: u64, w: u32, h: u32, f: u32, lane_symbols: u32,
+                                out_len: *mut u64) -> *mut u8;
+    fn alice_codec_decode_split(data: *const u8, len: u64, out_len: *mut u64) -> *mut u8;
+    fn alice_codec_dev_encode_split(d_rgb: *const std::ffi::c_void, w: u32, h: u32, f: u32, n_chunks: u32, wavelet: u8, quality: u8,
+                                    qualities: *const u8, lane_symbols: u32, d_out: *mut std::ffi::c_void, out_stride: u64,
+                                    sizes: *mut u64, hip_stream: *mut std::ffi::c_void) -> c_int;
+    fn alice_codec_dev_decode_split(d_alc: *const std::ffi::c_void, alc_stride: u64, sizes: *const u64, n_chunks: u32,
+                                    d_rgb_out: *mut std::ffi::c_void, hip_stream: *mut std::ffi::c_void) -> c_int;
+}
+
+pub const SPLIT_DEFAULT_LANE_SYMBOLS: u32 = 512;
+pub const SPLIT_HEADER_BYTES: usize = 1630;
+
+/// The validated header of a version 2 container.
+#[derive(Debug, Clone, PartialEq, Eq)]
+pub struct SplitInfo {
+    pub width: u32, pub height: u32, pub frames: u32, pub lane_symbols: u32,
+    pub wavelet_type: WaveletType,
+    pub quant_step: [i32; 3], pub dead_zone: [i32; 3],
+    pub num_symbols: [u32; 3], pub n_blocks: [u32; 3],
+    pub payload_len: [u64; 3],
+}
+
+/// Header parsing and validation: host code, no device needed; `InvalidBitstream` on a malformed field.
+pub fn split_info(data: &[u8]) -> Result<SplitInfo, CodecError> {
+    let mut c = RawSplitInfo::default();
+    let rc = unsafe { alice_codec_split_info(data.as_ptr(), data.len() as u64, &mut c) };
+    check(rc, 0, data.len())?;
+    Ok(SplitInfo {
+        width: c.width, height: c.height, frames: c.frames, lane_symbols: c.lane_symbols,
+        wavelet_type: match c.wavelet { 1 => WaveletType::Cdf97, 2 => WaveletType::Haar, _ => WaveletType::Cdf53 },
+        quant_step: c.quant_step, dead_zone: c.dead_zone, num_symbols: c.num_symbols, n_blocks: c.n_blocks,
+        payload_len: c.payload_len,
+    })
+}
+
+/// The version byte of a container (0 when the data is too short to have one).
+pub fn alc_version(data: &[u8]) -> u8 { if data.len() > 4 { data[4] } else { 0 } }
+
+/// One chunk as version 2 bytes, with the encoder's wavelet and quality (`lane_symbols` 0: the default).
+pub fn encode_split(encoder: &FrameEncoder, rgb_frames: &[u8], width: u32, height: u32, frames: u32, lane_symbols: u32)
+    -> Result<Vec<u8>, CodecError> {
+    let mut n = 0u64;
+    unsafe {
+        let e = alice_codec_encoder_create_ex(encoder.quality, encoder.wavelet_type as u8);
+        let p = alice_codec_encode_split(e, rgb_frames.as_ptr(), rgb_frames.len() as u64, width, height, frames, lane_symbols, &mut n);
+        alice_codec_encoder_destroy(e);
+        if p.is_null() {
+            let expected = (width as usize).saturating_mul(height as usize).saturating_mul(frames as usize).saturating_mul(3);
+            return Err(last_error(expected, rgb_frames.len(), width, height, 0));
+        }
+        Ok(take(p, n))
+    }
+}
+
+/// The RGB bytes of a version 2 container; `InvalidBitstream` when a directory does not add up or a lane fails its end check.
+pub fn decode_split(data: &[u8]) -> Result<Vec<u8>, CodecError> {
+    let mut n = 0u64;
+    unsafe {
+        let p = alice_codec_decode_split(data.as_ptr(), data.len() as u64, &mut n);
+        if p.is_null() { Err(last_error(0, data.len(), 0, 0, 0)) } else { Ok(take(p, n)) }
+    }
+}
+
+/// The 256 frequencies a version 2 header stores for this histogram (sum 4096), from the table kernel.
+pub fn normalized_frequencies(histogram: &[u32; 256]) -> Result<[u16; 256], CodecError> {
+    let mut f = [0u16; 256];
+    let rc = unsafe { alice_codec_split_normalize(histogram.as_ptr(), f.as_mut_ptr()) };
+    check(rc, 0, 0).map(|_| f)
+}
+
+pub fn split_stream_bound(n: u64, lane_symbols: u32) -> u64 { unsafe { alice_codec_split_stream_bound(n, lane_symbols) } }
+
+/// `n_chunks` packed device chunks -> version 2 bytes at `d_out + i * out_stride`; returns the sizes.  `qualities`: one
+/// per chunk, or `None` for `quality` everywhere.
+///
+/// # Safety
+/// `d_rgb` and `d_out` must be device pointers to `n_chunks * width*height*frames*3` and `n_chunks * out_stride` bytes.
+pub unsafe fn split_encode_device(d_rgb: *const std::ffi::c_void, width: u32, height: u32, frames: u32, n_chunks: u32,
+                                  wavelet_type: WaveletType, quality: u8, qualities: Option<&[u8]>, lane_symbols: u32,
+                                  d_out: *mut std::ffi::c_void, out_stride: u64, hip_stream: *mut std::ffi::c_void)
+    -> Result<Vec<u64>, CodecError> {
+    if let Some(q) = qualities {
+        if q.len() != n_chunks as usize { return Err(CodecError::InvalidBufferSize { expected: n_chunks as usize, got: q.len() }); }
+    }
+    let mut sizes = vec![0u64; n_chunks as usize];
+    let rc = alice_codec_dev_encode_split(d_rgb, width, height, frames, n_chunks, wavelet_type as u8, quality,
+                                          qualities.map_or(std::ptr::null(), |q| q.as_ptr()), lane_symbols, d_out, out_stride,
+                                          sizes.as_mut_ptr(), hip_stream);
+    check(rc, 0, 0).map(|_| sizes)
+}
+
+/// # Safety
+/// `d_alc` holds chunk i's `sizes[i]` bytes at `i * alc_stride`; `d_rgb_out` has room for every chunk's pixels.
+pub unsafe fn split_decode_device(d_alc: *const std::ffi::c_void, alc_stride: u64, sizes: &[u64], d_rgb_out: *mut std::ffi::c_void,
+                                  hip_stream: *mut std::ffi::c_void) -> Result<(), CodecError> {
+    check(alice_codec_dev_decode_split(d_alc, alc_stride, sizes.as_ptr(), sizes.len() as u32, d_rgb_out, hip_stream), 0, 0)
+}

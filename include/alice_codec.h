@@ -387,6 +387,60 @@ int alice_codec_dev_rle_encode_mask(const void *d_mask, uint64_t n, void *d_out,
 int alice_codec_dev_extract_person_rgb(const void *d_mask, uint32_t width, uint32_t height, const uint32_t bbox[4],
                                        const void *d_rgb, void *d_out, uint64_t cap, uint64_t *out_len, void *hip_stream);
 
+/* ---- split-stream format (.alc version 2) ----
+ * An opt-in second container.  Colour, padding, 3-D lifting, quantiser and symbol map are those of version 1 (the symbols
+ * are the ones alice_codec_dev_forward_symbols gives); the entropy stage is replaced: a frequency table that sums to
+ * exactly 4096, stored in the header, and one short independent rANS chain per lane -- blocks of 64 * lane_symbols
+ * symbols, lane j of a block owning symbols j, j + 64, ... -- so one chunk uses the whole device and
+ * decode(encode(x)) is the video the transform and quantiser define.  Version 1 stays the format for byte compatibility
+ * with the reference; alice_codec_chunk_from_bytes keeps refusing version 2.  lane_symbols: a power of two in
+ * [64, 16384], or 0 for the default (ALICE_SPLIT_DEFAULT_LANE_SYMBOLS).  A lane whose end check fails (state back at 2^23,
+ * cursor at the end of its stream) or a directory that does not add up makes a decode ALICE_ERR_INVALID_BITSTREAM. */
+enum { ALICE_SPLIT_DEFAULT_LANE_SYMBOLS = 512, ALICE_SPLIT_HEADER_BYTES = 1630 };
+typedef struct AliceSplitInfo {
+    uint32_t width, height, frames, lane_symbols;
+    uint8_t wavelet, reserved[3];
+    int32_t quant_step[3], dead_zone[3];
+    uint32_t num_symbols[3], n_blocks[3];
+    uint64_t payload_len[3];
+} AliceSplitInfo;
+/* stage level.  The most bytes a channel payload of n symbols takes (0: lane_symbols out of range or n above 2^32 - 1) */
+uint64_t alice_codec_split_stream_bound(uint64_t n, uint32_t lane_symbols);
+/* the normalised frequencies of a histogram (sum 4096, present >= 1, absent 0; all zero for an all-zero histogram),
+ * computed by the table kernel */
+int alice_codec_split_normalize(const uint32_t hist[256], uint16_t freq[256]);
+/* n device symbols with histogram hist (it must count exactly n symbols) -> the channel payload (block lengths, then per
+ * block the lane directory and the lane streams) at d_out[0 .. *out_len).  cap below what the stream needs is
+ * ALICE_ERR_INVALID_BUFFER_SIZE with nothing written.  Finished on return. */
+int alice_codec_dev_split_encode(const void *d_symbols, uint64_t n, const uint32_t hist[256], uint32_t lane_symbols,
+                                 void *d_out, uint64_t cap, uint64_t *out_len, void *hip_stream);
+/* a channel payload of len bytes at d_stream (any alignment) with the header's frequencies -> n device symbols */
+int alice_codec_dev_split_decode(const void *d_stream, uint64_t len, const uint16_t freq[256], uint32_t lane_symbols,
+                                 void *d_symbols, uint64_t n, void *hip_stream);
+/* whole chunk, host memory.  encode: the handle's wavelet and quality, alice_codec_encode64's validation in its order, then
+ * lane_symbols (ALICE_ERR_INVALID_DIMENSIONS); returns the version 2 bytes (free with alice_codec_data_free64), NULL on error.
+ * decode: returns width*height*frames*3 RGB bytes.  Header parsing and validation (alice_codec_split_info is only that) are
+ * host code and need no device; the checks run in a fixed order: length of the fixed part, magic, version, wavelet byte,
+ * lane_symbols, length of the header, then per channel the quantiser step (at least 1) and dead zone (at least 0),
+ * num_symbols (the padded volume, in 64 bits), n_blocks, the
+ * frequency sum, payload_len against its directories; then the total length; then each channel's block lengths. */
+uint8_t *alice_codec_encode_split(const FrameEncoder *encoder, const uint8_t *rgb, uint64_t rgb_len, uint32_t width,
+                                  uint32_t height, uint32_t frames, uint32_t lane_symbols, uint64_t *out_len);
+uint8_t *alice_codec_decode_split(const uint8_t *data, uint64_t len, uint64_t *out_len);
+int alice_codec_split_info(const uint8_t *data, uint64_t len, AliceSplitInfo *info);
+/* device-resident, n_chunks equal-shaped packed chunks per call.  Chunk i is encoded at qualities[i] (NULL: all at
+ * `quality`) into d_out + i * out_stride; sizes[i] receives its length.  Any number of chunks: the calls work through
+ * them in groups whose symbols take at most 4 GiB (ten 1080p x 64 chunks; one chunk already fills the device).  A chunk
+ * longer than out_stride is ALICE_ERR_INVALID_BUFFER_SIZE before anything of its group is written (earlier groups are
+ * complete; ALICE_SPLIT_HEADER_BYTES + 3 * alice_codec_split_stream_bound always suffices).  Finished on return. */
+int alice_codec_dev_encode_split(const void *d_rgb, uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks,
+                                 uint8_t wavelet_type, uint8_t quality, const uint8_t *qualities, uint32_t lane_symbols,
+                                 void *d_out, uint64_t out_stride, uint64_t *sizes, void *hip_stream);
+/* chunk i: sizes[i] bytes at d_alc + i * alc_stride -> pixels at d_rgb_out + i * width*height*frames*3 (shape from the
+ * headers; all chunks of a call must agree) */
+int alice_codec_dev_decode_split(const void *d_alc, uint64_t alc_stride, const uint64_t *sizes, uint32_t n_chunks,
+                                 void *d_rgb_out, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -519,6 +519,78 @@ inline SizedChunk encode_to_size(const std::vector<uint8_t>& rgb, uint32_t w, ui
     return SizedChunk{EncodedChunk::adopt(c), q, fits != 0};
 }
 
+// ---- split-stream format (.alc version 2) ----
+// v1 (FrameEncoder::encode, EncodedChunk) is the reference's bitstream byte for byte; v2 keeps transform, quantiser and
+// symbols and codes them as independent lanes with a table that sums to 4096: for video that comes back and for the
+// latency of one chunk.  EncodedChunk::from_bytes refuses v2; alc_version tells the two apart.
+constexpr uint32_t SPLIT_DEFAULT_LANE_SYMBOLS = ALICE_SPLIT_DEFAULT_LANE_SYMBOLS;
+constexpr uint32_t SPLIT_HEADER_BYTES = ALICE_SPLIT_HEADER_BYTES;
+struct SplitInfo {   // the validated header of a version 2 container
+    uint32_t width = 0, height = 0, frames = 0, lane_symbols = 0;
+    WaveletType wavelet_type = WaveletType::Cdf53;
+    std::array<int32_t, 3> quant_step{}, dead_zone{};
+    std::array<uint32_t, 3> num_symbols{}, n_blocks{};
+    std::array<uint64_t, 3> payload_len{};
+};
+// header parsing and validation: host code, no device needed; CodecError(InvalidBitstream) on a malformed field
+inline SplitInfo split_info(const uint8_t* data, size_t len) {
+    static const uint8_t empty = 0;
+    AliceSplitInfo c{};
+    detail::check(alice_codec_split_info(data ? data : &empty, len, &c));
+    SplitInfo i;
+    i.width = c.width; i.height = c.height; i.frames = c.frames; i.lane_symbols = c.lane_symbols;
+    i.wavelet_type = static_cast<WaveletType>(c.wavelet);
+    for (int k = 0; k < 3; ++k) {
+        i.quant_step[k] = c.quant_step[k]; i.dead_zone[k] = c.dead_zone[k];
+        i.num_symbols[k] = c.num_symbols[k]; i.n_blocks[k] = c.n_blocks[k]; i.payload_len[k] = c.payload_len[k];
+    }
+    return i;
+}
+inline SplitInfo split_info(const std::vector<uint8_t>& v) { return split_info(v.data(), v.size()); }
+inline int alc_version(const std::vector<uint8_t>& v) { return v.size() > 4 ? v[4] : 0; }
+// one chunk as version 2 bytes, with the encoder's wavelet and quality (lane_symbols 0: the default)
+inline std::vector<uint8_t> encode_split(const FrameEncoder& enc, const std::vector<uint8_t>& rgb, uint32_t w, uint32_t h, uint32_t f,
+                                         uint32_t lane_symbols = 0) {
+    static const uint8_t empty = 0;
+    uint64_t n = 0;
+    uint8_t* p = alice_codec_encode_split(enc.handle(), rgb.empty() ? &empty : rgb.data(), rgb.size(), w, h, f, lane_symbols, &n);
+    if (!p) detail::raise();
+    return detail::take(p, n);
+}
+inline std::vector<uint8_t> decode_split(const std::vector<uint8_t>& data) {
+    static const uint8_t empty = 0;
+    uint64_t n = 0;
+    uint8_t* p = alice_codec_decode_split(data.empty() ? &empty : data.data(), data.size(), &n);
+    if (!p) detail::raise(ALICE_ERR_INVALID_BITSTREAM);
+    return detail::take(p, n);
+}
+// the 256 frequencies a version 2 header stores for this histogram (sum 4096), from the table kernel
+inline std::array<uint16_t, 256> normalized_frequencies(const std::array<uint32_t, 256>& histogram) {
+    std::array<uint16_t, 256> f{};
+    detail::check(alice_codec_split_normalize(histogram.data(), f.data()));
+    return f;
+}
+inline uint64_t split_stream_bound(uint64_t n, uint32_t lane_symbols = SPLIT_DEFAULT_LANE_SYMBOLS) {
+    return alice_codec_split_stream_bound(n, lane_symbols);
+}
+// n_chunks packed device chunks -> version 2 bytes at d_out + i * out_stride; returns the sizes.  qualities empty: all at
+// `quality`, else one per chunk.
+inline std::vector<uint64_t> split_encode_device(const void* d_rgb, uint32_t w, uint32_t h, uint32_t f, uint32_t n_chunks, WaveletType wt,
+                                                 uint8_t quality, void* d_out, uint64_t out_stride,
+                                                 const std::vector<uint8_t>& qualities = {}, uint32_t lane_symbols = 0,
+                                                 void* hip_stream = nullptr) {
+    if (!qualities.empty() && qualities.size() != n_chunks) throw CodecError(ALICE_ERR_INVALID_BUFFER_SIZE, "one quality per chunk");
+    std::vector<uint64_t> sizes(n_chunks);
+    detail::check(alice_codec_dev_encode_split(d_rgb, w, h, f, n_chunks, static_cast<uint8_t>(wt), quality,
+                                               qualities.empty() ? nullptr : qualities.data(), lane_symbols, d_out, out_stride,
+                                               sizes.data(), hip_stream));
+    return sizes;
+}
+inline void split_decode_device(const void* d_alc, uint64_t alc_stride, const std::vector<uint64_t>& sizes, void* d_rgb_out,
+                                void* hip_stream = nullptr) {
+    detail::check(alice_codec_dev_decode_split(d_alc, alc_stride, sizes.data(), static_cast<uint32_t>(sizes.size()), d_rgb_out, hip_stream));
+}
+
 // The reference's buffer-model rate control (src/rate_control.rs:7-219), host only, with the Rust integer behaviour:
 // u32::midpoint start, buffer half full, 30-entry history, +-0.3 thresholds with +1 / -2 steps, saturating f64 casts
 // (NaN -> 0), wrapping integer casts.
