@@ -251,6 +251,19 @@ def load_library() -> C.CDLL:
         "alice_codec_dev_encode_split": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint8, _u8p,
                                                    C.c_uint32, vp, C.c_uint64, _u64p, vp]),
         "alice_codec_dev_decode_split": (C.c_int, [vp, C.c_uint64, _u64p, C.c_uint32, vp, vp]),
+        "alice_codec_predict_split_sizes": (C.c_int, [C.c_uint8, _u8p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                      _u64p, _u64p]),
+        "alice_codec_dev_predict_split_sizes": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint32,
+                                                          _u64p, _u64p, vp]),
+        "alice_codec_encode_split_to_size": (vp, [C.c_uint8, _u8p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                  C.c_uint64, C.c_uint8, C.c_uint8, _u8p, _u8p, _u64p]),
+        "alice_codec_dev_encode_split_regions": (C.c_int, [vp, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                           C.c_uint32, C.c_uint8, C.c_uint8, _u8p, C.c_uint32, vp, C.c_uint64, _u64p, vp]),
+        "alice_codec_dev_decode_split_regions": (C.c_int, [vp, C.c_uint64, _u64p, C.c_uint32, vp, C.c_uint32, C.c_uint32, _u32p, vp]),
+        "alice_codec_dev_encode_split_to_budget": (C.c_int, [vp, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                             C.c_uint32, C.c_uint8, C.c_uint32, _u64p, C.c_uint8, C.c_uint8, _u8p, _u8p,
+                                                             vp, C.c_uint64, _u64p, vp]),
+        "alice_codec_test_last_split_trials": (C.c_uint32, [_u32p, C.c_uint32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
@@ -1477,7 +1490,8 @@ def _runs(boxes) -> list:
 
 def encode_person_chunks(d_frames, d_background, width: int, height: int, frames: int, n_chunks: int, quality: int,
                          wavelet: WaveletType = WaveletType.Cdf53, config: SegmentConfig | None = None,
-                         green_threshold: int | None = None) -> list:
+                         green_threshold: int | None = None, format: str = "v1", lane_symbols: int = 0,
+                         max_bytes: int | None = None) -> list:
     """Hybrid encode of n_chunks chunks of `frames` frames each (d_frames: n_chunks * frames frames of width x height
     interleaved RGB in HBM) -> list of (bbox [x, y, w, h] in pixels, .alc bytes), one per chunk.
 
@@ -1487,7 +1501,16 @@ def encode_person_chunks(d_frames, d_background, width: int, height: int, frames
        chroma keying of the RGB frames instead (segment_chroma_rgb_device), d_background unused.
     2. Per chunk the union of its frames' boxes (only the stats come to the host), 3. person_chunk_boxes, 4. Batch region
        encodes of the chunks with foreground (one per run of consecutive such chunks).  A chunk without foreground gets
-       bbox [0, 0, 0, 0] and the reference's empty chunk, FrameEncoder.encode(b"", 0, 0, frames)."""
+       bbox [0, 0, 0, 0] and the reference's empty chunk, FrameEncoder.encode(b"", 0, 0, frames).
+
+    format="split" codes the boxes as version 2 (split_encode_regions_device; lane_symbols 0: the default), with the
+    version 2 empty chunk for chunks without foreground.  max_bytes (split only) is a byte budget per chunk: every box is
+    then coded at the quality split_encode_to_budget_device picks in [10, min(quality, 100)], and a chunk that cannot be
+    guaranteed to fit is coded at the low end of the range."""
+    if format not in ("v1", "split"):
+        raise CodecError(9, f"format must be 'v1' or 'split', got {format!r}")
+    if max_bytes is not None and format != "split":
+        raise CodecError(9, "max_bytes is a version 2 budget: it needs format='split'")
     W, H, f = _positive_u32(width, "width"), _positive_u32(height, "height"), _positive_u32(frames, "frames")
     n = _positive_u32(n_chunks, "n_chunks")
     if not 0 <= int(quality) <= 255:
@@ -1512,9 +1535,32 @@ def encode_person_chunks(d_frames, d_background, width: int, height: int, frames
         torch.cuda.synchronize()
         st = stats.cpu().numpy().view(np.uint32).reshape(-1, 5).astype(np.int64)
     boxes = person_chunk_boxes(st, W, H, f)
+    frame_bytes = W * H * 3
+    if format == "split":
+        enc = FrameEncoder(int(quality), wavelet)
+        empty = encode_split(enc, b"", 0, 0, f, lane_symbols)
+        out = [(b, empty) for b in boxes]
+        for i, j in _runs(boxes):
+            bw, bh = boxes[i][2], boxes[i][3]
+            stride = (SPLIT_HEADER_BYTES + 3 * split_stream_bound(_padded_pixels(bw, bh, f), lane_symbols or SPLIT_DEFAULT_LANE_SYMBOLS)
+                      + 255) & ~255
+            d_out = torch.empty((j - i) * stride, dtype=torch.uint8, device="cuda")
+            origins = [b[:2] for b in boxes[i:j]]
+            src = frames_ptr + i * f * frame_bytes
+            if max_bytes is None:
+                sizes = split_encode_regions_device(src, W, H, origins, bw, bh, f, wavelet, int(quality), d_out.data_ptr(), stride,
+                                                    lane_symbols=lane_symbols)
+            else:
+                hi_q = min(int(quality), 100)
+                _, _, sizes = split_encode_to_budget_device(src, bw, bh, f, j - i, wavelet, [int(max_bytes)] * (j - i),
+                                                            d_out.data_ptr(), stride, min_quality=min(10, hi_q), max_quality=hi_q,
+                                                            lane_symbols=lane_symbols, frame_width=W, frame_height=H, origins=origins)
+            host = d_out.cpu().numpy().reshape(j - i, stride)
+            for k in range(j - i):
+                out[i + k] = (boxes[i + k], host[k, :int(sizes[k])].tobytes())
+        return out
     empty = FrameEncoder(int(quality), wavelet).encode(b"", 0, 0, f).to_bytes()
     out = [(b, empty) for b in boxes]
-    frame_bytes = W * H * 3
     batches = {}
     for i, j in _runs(boxes):
         bw, bh = boxes[i][2], boxes[i][3]
@@ -1537,9 +1583,10 @@ def encode_person_chunks(d_frames, d_background, width: int, height: int, frames
 def decode_person_chunks(chunks, d_frames_out, width: int, height: int, frames: int) -> None:
     """Hybrid decode: chunk k of `chunks` (encode_person_chunks' list of (bbox, .alc bytes)) is decoded and pasted into
     its bbox of frames [k * frames, (k + 1) * frames) of d_frames_out (width x height RGB in HBM, typically holding the
-    background).  Empty chunks paste nothing; no byte outside the boxes is written."""
+    background).  Empty chunks paste nothing; no byte outside the boxes is written.  Each chunk is decoded by its own
+    container version (alc_version), so a list may mix version 1 and version 2 chunks."""
     W, H, f = _positive_u32(width, "width"), _positive_u32(height, "height"), _positive_u32(frames, "frames")
-    boxes, alcs = [], []
+    boxes, alcs, versions, lanes = [], [], [], {}
     for k, (bbox, alc) in enumerate(chunks):
         b = [_u32_arg(v, "bbox") for v in bbox]
         if len(b) != 4:
@@ -1547,13 +1594,24 @@ def decode_person_chunks(chunks, d_frames_out, width: int, height: int, frames: 
         if b[2] * b[3] and (b[0] + b[2] > W or b[1] + b[3] > H):
             raise CodecError(2, f"chunk {k}: bbox {b} does not lie inside the {W}x{H} frame")
         data = bytes(alc)
+        version = alc_version(data)
         if b[2] * b[3]:
-            c = EncodedChunk.from_bytes(data)
+            c = split_info(data) if version == 2 else EncodedChunk.from_bytes(data)
             if (c.width, c.height, c.frames) != (b[2], b[3], f):
                 raise CodecError(2, f"chunk {k}: .alc is {c.width}x{c.height}x{c.frames}, bbox says {b[2]}x{b[3]}x{f}")
+            if version == 2:
+                lanes[k] = c.lane_symbols
         boxes.append(b)
         alcs.append(data)
-    runs = _runs(boxes)
+        versions.append(version)
+    # one device call per run of consecutive chunks of one box size, one container version and one lane_symbols
+    runs = []
+    for i, j in _runs(boxes):
+        s0 = i
+        for k in range(i + 1, j + 1):
+            if k == j or (versions[k], lanes.get(k)) != (versions[s0], lanes.get(s0)):
+                runs.append((s0, k))
+                s0 = k
     if not runs:
         return
     import torch
@@ -1562,6 +1620,15 @@ def decode_person_chunks(chunks, d_frames_out, width: int, height: int, frames: 
     batches = {}
     for i, j in runs:
         bw, bh = boxes[i][2], boxes[i][3]
+        if versions[i] == 2:
+            stride = (max(len(a) for a in alcs[i:j]) + 255) & ~255
+            host = np.zeros((j - i, stride), np.uint8)
+            for k in range(i, j):
+                host[k - i, :len(alcs[k])] = np.frombuffer(alcs[k], np.uint8)
+            d_alc = torch.from_numpy(host).to("cuda")
+            split_decode_regions_device(d_alc.data_ptr(), stride, [len(a) for a in alcs[i:j]], out_ptr + i * f * frame_bytes, W, H,
+                                        [b[:2] for b in boxes[i:j]])
+            continue
         stride = (max(len(a) for a in alcs[i:j]) + 255) & ~255
         host = np.zeros((j - i, stride), np.uint8)
         for k in range(i, j):
@@ -1679,3 +1746,119 @@ def split_encode_device(d_rgb_ptr: int, width: int, height: int, frames: int, n_
 def split_decode_device(d_alc_ptr: int, alc_stride: int, sizes, d_rgb_out_ptr: int, stream: int = 0) -> None:
     s = np.ascontiguousarray(sizes, dtype=np.uint64).reshape(-1)
     _check(load_library().alice_codec_dev_decode_split(d_alc_ptr, alc_stride, _p(s, _u64p), s.size, d_rgb_out_ptr, stream or None))
+
+
+def _padded_pixels(width: int, height: int, frames: int) -> int:
+    """Symbols per channel of a width x height x frames chunk: every side padded to even, one frame to two."""
+    if width * height * frames == 0:
+        return 0
+    return (width + (width & 1)) * (height + (height & 1)) * (2 if frames == 1 else frames + (frames & 1))
+
+
+# ---- version 2: size prediction, byte budgets, regions of device frames (DESIGN.md section 10.8) ----
+
+def predict_split_sizes(rgb_frames, width: int, height: int, frames: int, wavelet_type: WaveletType = WaveletType.Cdf53,
+                        lane_symbols: int = 0) -> SizePrediction:
+    """The size bracket of encode_split at every quality, from one forward transform on the GPU (no entropy coding).
+    Every version 2 table is bounded: status is RATE_BOUNDED throughout."""
+    r = _as_u8(rgb_frames)
+    _dims_u32(width, height, frames, lane_symbols)
+    lo = np.zeros(101, np.uint64); hi = np.zeros(101, np.uint64)
+    ptr = _p(r, _u8p) if r.size else C.cast(C.c_char_p(b""), _u8p)
+    _check(load_library().alice_codec_predict_split_sizes(int(wavelet_type), ptr, r.size, width, height, frames, lane_symbols,
+                                                          _p(lo, _u64p), _p(hi, _u64p)))
+    return SizePrediction(lo, hi, np.zeros(101, np.uint8))
+
+
+def predict_split_sizes_device(d_rgb_ptr: int, width: int, height: int, frames: int, n_chunks: int,
+                               wavelet_type: WaveletType = WaveletType.Cdf53, lane_symbols: int = 0,
+                               stream: int = 0) -> SizePrediction:
+    """n_chunks packed chunks at a device pointer: arrays of shape (n_chunks, 101)."""
+    _dims_u32(width, height, frames, n_chunks, lane_symbols)
+    lo = np.zeros((max(n_chunks, 1), 101), np.uint64); hi = np.zeros_like(lo)
+    _check(load_library().alice_codec_dev_predict_split_sizes(d_rgb_ptr, width, height, frames, n_chunks, int(wavelet_type),
+                                                              lane_symbols, _p(lo, _u64p), _p(hi, _u64p), stream or None))
+    return SizePrediction(lo[:n_chunks], hi[:n_chunks], np.zeros((n_chunks, 101), np.uint8))
+
+
+def encode_split_to_size(rgb_frames, width: int, height: int, frames: int, max_bytes: int,
+                         wavelet_type: WaveletType = WaveletType.Cdf53, min_quality: int = 10, max_quality: int = 95,
+                         lane_symbols: int = 0) -> tuple:
+    """One chunk as version 2 bytes at the highest quality in [min_quality, max_quality] that fits max_bytes: the largest
+    whose predicted upper bound fits, refined by at most four exact size counts among the qualities whose bracket straddles
+    the budget.  Returns (bytes, quality, fits); fits is False when not even min_quality is guaranteed to fit (the chunk is
+    then encoded at min_quality).  The bytes are encode_split's at that quality."""
+    lib = load_library()
+    r = _as_u8(rgb_frames)
+    _dims_u32(width, height, frames, lane_symbols)
+    _check_budget_args([max_bytes], min_quality, max_quality)
+    chosen = C.c_uint8(0); fits = C.c_uint8(0); n = C.c_uint64(0)
+    src = _p(r, _u8p) if r.size else C.cast(C.c_char_p(b""), _u8p)
+    ptr = lib.alice_codec_encode_split_to_size(int(wavelet_type), src, r.size, width, height, frames, lane_symbols, int(max_bytes),
+                                               int(min_quality), int(max_quality), C.byref(chosen), C.byref(fits), C.byref(n))
+    if not ptr:
+        _raise_last()
+    try:
+        return _copy_out(ptr, n.value).tobytes(), int(chosen.value), bool(fits.value)
+    finally:
+        lib.alice_codec_data_free64(ptr, n.value)
+
+
+def _origins_u32(origins, n_chunks: int) -> np.ndarray:
+    o = np.ascontiguousarray(origins, dtype=np.int64).reshape(-1)
+    if o.size != 2 * n_chunks or (o < 0).any() or (o > 0xFFFFFFFF).any():
+        raise ValueError("origins: one (x, y) pair of u32 per chunk")
+    return o.astype(np.uint32)
+
+
+def split_encode_regions_device(d_frames_ptr: int, frame_width: int, frame_height: int, origins, width: int, height: int,
+                                frames: int, wavelet_type: WaveletType, quality: int, d_out_ptr: int, out_stride: int,
+                                qualities=None, lane_symbols: int = 0, stream: int = 0) -> np.ndarray:
+    """Chunk i = frames [i * frames, (i + 1) * frames) of the device frames, cropped to width x height at origins[i], as
+    version 2 bytes at d_out_ptr + i * out_stride (the bytes of encode_split of the crop); returns the sizes."""
+    n_chunks = len(origins)
+    o = _origins_u32(origins, n_chunks)
+    sizes = np.zeros(n_chunks, np.uint64)
+    q = None if qualities is None else np.ascontiguousarray(qualities, dtype=np.uint8).reshape(-1)
+    if q is not None and q.size != n_chunks:
+        raise ValueError("one quality per chunk")
+    _dims_u32(frame_width, frame_height, width, height, frames, lane_symbols)
+    _check(load_library().alice_codec_dev_encode_split_regions(d_frames_ptr, frame_width, frame_height, _p(o, _u32p), width, height,
+                                                               frames, n_chunks, int(wavelet_type), quality,
+                                                               None if q is None else _p(q, _u8p), lane_symbols, d_out_ptr,
+                                                               out_stride, _p(sizes, _u64p), stream or None))
+    return sizes
+
+
+def split_decode_regions_device(d_alc_ptr: int, alc_stride: int, sizes, d_frames_out_ptr: int, frame_width: int,
+                                frame_height: int, origins, stream: int = 0) -> None:
+    """Chunk i (sizes[i] bytes at d_alc_ptr + i * alc_stride) is decoded into its rectangle at origins[i] of its frames of
+    d_frames_out_ptr; no byte outside the rectangles is written."""
+    s = np.ascontiguousarray(sizes, dtype=np.uint64).reshape(-1)
+    o = _origins_u32(origins, s.size)
+    _dims_u32(frame_width, frame_height)
+    _check(load_library().alice_codec_dev_decode_split_regions(d_alc_ptr, alc_stride, _p(s, _u64p), s.size, d_frames_out_ptr,
+                                                               frame_width, frame_height, _p(o, _u32p), stream or None))
+
+
+def split_encode_to_budget_device(d_frames_ptr: int, width: int, height: int, frames: int, n_chunks: int,
+                                  wavelet_type: WaveletType, budgets, d_out_ptr: int, out_stride: int, min_quality: int = 10,
+                                  max_quality: int = 95, lane_symbols: int = 0, frame_width: int = 0, frame_height: int = 0,
+                                  origins=None, stream: int = 0) -> tuple:
+    """n_chunks device chunks (packed, or regions of frame_width x frame_height frames when origins is given), chunk i at
+    the quality encode_split_to_size's rule picks for budgets[i].  Returns (chosen, fits, sizes)."""
+    b = [int(v) for v in budgets]
+    if len(b) != n_chunks:
+        raise ValueError("one budget per chunk")
+    _check_budget_args(b, min_quality, max_quality)
+    _dims_u32(width, height, frames, n_chunks, lane_symbols, frame_width, frame_height)
+    bud = np.array(b, dtype=np.uint64)
+    o = None if origins is None else _origins_u32(origins, n_chunks)
+    chosen = np.zeros(n_chunks, np.uint8); fits = np.zeros(n_chunks, np.uint8); sizes = np.zeros(n_chunks, np.uint64)
+    _check(load_library().alice_codec_dev_encode_split_to_budget(d_frames_ptr, frame_width, frame_height,
+                                                                 None if o is None else _p(o, _u32p), width, height, frames,
+                                                                 n_chunks, int(wavelet_type), lane_symbols, _p(bud, _u64p),
+                                                                 int(min_quality), int(max_quality), _p(chosen, _u8p),
+                                                                 _p(fits, _u8p), d_out_ptr, out_stride, _p(sizes, _u64p),
+                                                                 stream or None))
+    return chosen, fits.astype(bool), sizes

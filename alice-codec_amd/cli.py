@@ -3,6 +3,7 @@
     python -m alice_codec_amd.cli decode INPUT.alc -o OUT.rgb
     python -m alice_codec_amd.cli info INPUT.alc
 `encode --format split [--lane-symbols N]` writes the split-stream container (.alc version 2, DESIGN.md section 10);
+`--max-bytes` and `encode-chunks --kbps` work in both formats;
 `decode` and `info` pick the format from the version byte.  The default of every subcommand is version 1.
 Like the reference it treats the whole input file as ONE chunk (src/bin/main.rs:117-122).  `encode-chunks`
 is the extension SURVEY.md section 8f asks for: it cuts a long raw-RGB file into 64-frame chunks
@@ -15,7 +16,7 @@ import sys
 import numpy as np
 
 from . import (DEFAULT_CHUNK_SIZE, CodecError, EncodedChunk, FrameDecoder, FrameEncoder, WaveletType, budget_bytes_per_chunk,
-               alc_version, decode_split, encode_many, encode_split, encode_to_size, split_info)
+               alc_version, decode_split, encode_many, encode_split, encode_split_to_size, encode_to_size, split_info)
 
 WAVELETS = {"cdf53": WaveletType.Cdf53, "cdf97": WaveletType.Cdf97, "haar": WaveletType.Haar}
 WAVELET_NAMES = {WaveletType.Cdf53: "CDF 5/3", WaveletType.Cdf97: "CDF 9/7", WaveletType.Haar: "Haar"}
@@ -33,8 +34,14 @@ def cmd_encode(a) -> None:
     quality = a.quality
     if a.format == "split":
         if a.max_bytes is not None:
-            raise ValueError("--max-bytes predicts version 1 sizes; it cannot be combined with --format split")
-        data = encode_split(FrameEncoder.with_wavelet(a.quality, wt), rgb, a.width, a.height, a.frames, a.lane_symbols)
+            data, quality, fits = encode_split_to_size(rgb, a.width, a.height, a.frames, a.max_bytes, wt, a.min_quality, a.max_quality,
+                                                       a.lane_symbols)
+            print(f"chosen quality: {quality}", file=sys.stderr)
+            if not fits:
+                print(f"warning: not even --min-quality {a.min_quality} is guaranteed to fit {a.max_bytes} bytes; "
+                      f"encoded at {quality}", file=sys.stderr)
+        else:
+            data = encode_split(FrameEncoder.with_wavelet(a.quality, wt), rgb, a.width, a.height, a.frames, a.lane_symbols)
         with open(a.output, "wb") as f:
             f.write(data)
         ratio = 0.0 if rgb.size == 0 else len(data) / rgb.size
@@ -65,8 +72,6 @@ def cmd_encode_chunks(a) -> None:
         raise ValueError("input size is not a whole number of frames")
     n_frames = rgb.size // frame_bytes
     if a.kbps is not None:
-        if a.format == "split":
-            raise ValueError("--kbps predicts version 1 sizes; it cannot be combined with --format split")
         _encode_chunks_to_rate(a, wt, rgb, frame_bytes, n_frames)
         return
     enc = FrameEncoder.with_wavelet(a.quality, wt)
@@ -98,7 +103,8 @@ def cmd_encode_chunks(a) -> None:
 
 def _encode_chunks_to_rate(a, wt, rgb, frame_bytes, n_frames) -> None:
     """--kbps / --fps: every chunk gets floor(target_bits_per_frame * frames / 8) bytes (RateController's per-frame target),
-    encoded by encode_to_size on --in-flight host threads, whose chains merge on the device."""
+    encoded by encode_to_size on --in-flight host threads, whose chains merge on the device.  --format split: chunk after
+    chunk through encode_split_to_size (one chunk uses the whole device)."""
     from concurrent.futures import ThreadPoolExecutor
     starts = list(range(0, n_frames, a.chunk))
 
@@ -107,13 +113,16 @@ def _encode_chunks_to_rate(a, wt, rgb, frame_bytes, n_frames) -> None:
         f = min(a.chunk, n_frames - s0)
         budget = budget_bytes_per_chunk(a.kbps, a.fps, f)
         part = np.ascontiguousarray(rgb[s0 * frame_bytes:(s0 + f) * frame_bytes])
-        chunk, q, fits = encode_to_size(part, a.width, a.height, f, budget, wt, a.min_quality, a.max_quality)
-        data = chunk.to_bytes()
+        if a.format == "split":
+            data, q, fits = encode_split_to_size(part, a.width, a.height, f, budget, wt, a.min_quality, a.max_quality, a.lane_symbols)
+        else:
+            chunk, q, fits = encode_to_size(part, a.width, a.height, f, budget, wt, a.min_quality, a.max_quality)
+            data = chunk.to_bytes()
         with open(f"{a.output}.{k:05d}.alc", "wb") as out:
             out.write(data)
         return s0, f, budget, q, fits, len(data)
 
-    with ThreadPoolExecutor(max_workers=max(1, a.in_flight)) as ex:
+    with ThreadPoolExecutor(max_workers=1 if a.format == "split" else max(1, a.in_flight)) as ex:
         for k, (s0, f, budget, q, fits, n) in enumerate(ex.map(one, range(len(starts)))):
             print(f"chunk {k}: frames {s0}..{s0 + f - 1} -> {n} bytes (budget {budget}), chosen quality: {q}", file=sys.stderr)
             if not fits:

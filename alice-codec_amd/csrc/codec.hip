@@ -853,9 +853,11 @@ int coef_hist_chunk(const RgbLayout& rgb, const ChunkDims& d, int wavelet, Encod
 // Stream-length brackets of n chunks at every step: out[(chunk * 64 + step - 1) * 3 + channel].  w: the chunk shape's
 // forward scratch (EncodeWork of one chunk).  d_step_hist: [chunk][step - 1][channel][256] u32 on the device, or null.
 // A chunk with coefficients outside the value table's range (never for 8-bit RGB at the default radius) gets its step
-// histograms from the real forward pass at each of the 64 steps instead of the fold.  Returns after the stream has drained.
+// histograms from the real forward pass at each of the 64 steps instead of the fold.  split_lane != 0: the brackets are
+// those of the split-stream channel payloads at that lane_symbols (rate.hip, split_cost_kernel) instead of the v1 streams.
+// Returns after the stream has drained.
 int predict_chunks(const RgbLayout* rgb, uint32_t n, const ChunkDims& d, int wavelet, EncodeWork& w, hipStream_t st,
-                   uint32_t* d_step_hist, std::vector<RateChannel>& out) {
+                   uint32_t* d_step_hist, std::vector<RateChannel>& out, uint32_t split_lane = 0) {
     const size_t per_chunk = (size_t)64 * 3;
     DevBuf bins, oor, own_hist, res, logt, fsym;
     TRY(bins.alloc((size_t)n * 3 * 4096 * sizeof(uint32_t)));
@@ -883,7 +885,8 @@ int predict_chunks(const RgbLayout* rgb, uint32_t n, const ChunkDims& d, int wav
             TRY(forward_chunk(rgb[b], d, wavelet, step, w, fsym.as<uint8_t>(), h, st));
         }
     }
-    launch_rate_cost(d_step_hist, logt.as<uint32_t>(), n, res.as<RateChannel>(), st);
+    if (split_lane) launch_split_rate_cost(d_step_hist, logt.as<uint32_t>(), n, split_lane, res.as<RateChannel>(), st);
+    else launch_rate_cost(d_step_hist, logt.as<uint32_t>(), n, res.as<RateChannel>(), st);
     HIP_TRY(hipGetLastError());
     out.resize((size_t)n * per_chunk);
     HIP_TRY(hipMemcpyAsync(out.data(), res.p, out.size() * sizeof(RateChannel), hipMemcpyDeviceToHost, st));
@@ -3315,12 +3318,26 @@ int split_decode_verdict(SplitWork& w, hipStream_t st) {
     return kOk;
 }
 
-// Whole chunks: B equal-shaped chunks at rgb[i] on the device, chunk i at quality q[i].  place(sizes, outs) is called once
-// the sizes are known and names where each chunk's bytes go (device).  Returns after the stream has drained.
-template <typename Place>
-int split_encode_chunks(const RgbLayout* rgb, uint32_t B, const ChunkDims& d, uint8_t wavelet, const uint8_t* q, uint32_t L,
-                        hipStream_t st, std::vector<uint64_t>& sizes, Place place) {
+// Whole chunks, in two halves: split_count_chunks runs the forward pass of B equal-shaped chunks at rgb[i] on the device
+// (chunk i at quality q[i]), the tables and the count pass, and returns the exact container sizes after the stream has
+// drained; split_write_chunks then writes chunk i at outs[i] (device, sizes[i] bytes) and returns after the stream has
+// drained.  A budget encode stops after the first half when a quality does not fit.
+struct SplitChunkEncode {
     EncodeWork ew;
+    std::vector<SplitHeaderDesc> hd;   // (declared before w: w's destructor drains the stream that reads them)
+    DevBuf d_hd;
+    SplitWork w;
+    std::vector<uint64_t> totals;
+    std::vector<uint8_t> q;
+    uint32_t B = 0, L = 0;
+    uint8_t wavelet = 0;
+};
+
+int split_count_chunks(SplitChunkEncode& e, const RgbLayout* rgb, uint32_t B, const ChunkDims& d, uint8_t wavelet, const uint8_t* q,
+                       uint32_t L, hipStream_t st, std::vector<uint64_t>& sizes) {
+    EncodeWork& ew = e.ew;
+    e.B = B; e.L = L; e.wavelet = wavelet;
+    e.q.assign(q, q + B);
     ew.d = d; ew.n_chunks = (int)B;
     if (transform_tiles_eligible(d)) TRY(ew.scratch.alloc(forward_scratch_bytes(d)));
     TRY(ew.sym.alloc((size_t)B * 3 * d.padded));
@@ -3329,38 +3346,52 @@ int split_encode_chunks(const RgbLayout* rgb, uint32_t B, const ChunkDims& d, ui
     for (uint32_t i = 0; i < B; ++i)
         TRY(forward_chunk(rgb[i], d, wavelet, quality_to_step(q[i]), ew, ew.sym.as<uint8_t>() + (size_t)i * 3 * d.padded,
                           ew.hist.as<uint32_t>() + (size_t)i * 3 * 256, st));
-    std::vector<SplitHeaderDesc> hd(B);   // (declared before w: w's destructor drains the stream that reads them)
-    DevBuf d_hd;
-    SplitWork w;
+    e.hd.assign(B, SplitHeaderDesc{});
+    SplitWork& w = e.w;
     TRY(split_work_alloc(w, (int)(3 * B), d.padded, L, true));
     for (size_t j = 0; j < 3 * (size_t)B; ++j) w.h[j].sym = ew.sym.as<uint8_t>() + j * d.padded;
-    std::vector<uint64_t> totals;
-    TRY(split_count(w, ew.hist.as<uint32_t>(), st, totals, nullptr));
+    TRY(split_count(w, ew.hist.as<uint32_t>(), st, e.totals, nullptr));
     sizes.resize(B);
-    for (uint32_t i = 0; i < B; ++i) sizes[i] = kSplitHeaderBytes + totals[3 * i] + totals[3 * i + 1] + totals[3 * i + 2];
-    std::vector<uint8_t*> outs(B, nullptr);
-    TRY(place(sizes, outs));
-    TRY(d_hd.alloc((size_t)B * sizeof(SplitHeaderDesc)));
+    for (uint32_t i = 0; i < B; ++i) sizes[i] = kSplitHeaderBytes + e.totals[3 * i] + e.totals[3 * i + 1] + e.totals[3 * i + 2];
+    return kOk;
+}
+
+int split_write_chunks(SplitChunkEncode& e, const std::vector<uint8_t*>& outs, hipStream_t st) {
+    const uint32_t B = e.B;
+    const ChunkDims& d = e.ew.d;
+    SplitWork& w = e.w;
+    TRY(e.d_hd.alloc((size_t)B * sizeof(SplitHeaderDesc)));
     for (uint32_t i = 0; i < B; ++i) {
-        SplitHeaderDesc& h = hd[i];
+        SplitHeaderDesc& h = e.hd[i];
         h.out = outs[i];
-        h.width = d.w; h.height = d.h; h.frames = d.f; h.lane_symbols = L;
-        h.num_symbols = (uint32_t)d.padded; h.n_blocks = w.n_blocks; h.wavelet = wavelet;
+        h.width = d.w; h.height = d.h; h.frames = d.f; h.lane_symbols = e.L;
+        h.num_symbols = (uint32_t)d.padded; h.n_blocks = w.n_blocks; h.wavelet = e.wavelet;
         h.freq = w.freq.as<uint16_t>() + (size_t)i * 3 * 256;
         uint64_t off = kSplitHeaderBytes;
         for (int c = 0; c < 3; ++c) {
-            h.step[c] = h.dead_zone[c] = quality_to_step(q[i]);
-            h.payload_len[c] = totals[3 * i + c];
+            h.step[c] = h.dead_zone[c] = quality_to_step(e.q[i]);
+            h.payload_len[c] = e.totals[3 * i + c];
             w.h[3 * (size_t)i + c].stream = outs[i] + off;
-            off += totals[3 * i + c];
+            off += e.totals[3 * i + c];
         }
     }
-    HIP_TRY(hipMemcpyAsync(d_hd.p, hd.data(), hd.size() * sizeof(SplitHeaderDesc), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(e.d_hd.p, e.hd.data(), e.hd.size() * sizeof(SplitHeaderDesc), hipMemcpyHostToDevice, st));
     TRY(split_write(w, st));
-    launch_split_headers(d_hd.as<SplitHeaderDesc>(), (int)B, st);
+    launch_split_headers(e.d_hd.as<SplitHeaderDesc>(), (int)B, st);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
     return kOk;
+}
+
+// Both halves: place(sizes, outs) is called once the sizes are known and names where each chunk's bytes go (device).
+template <typename Place>
+int split_encode_chunks(const RgbLayout* rgb, uint32_t B, const ChunkDims& d, uint8_t wavelet, const uint8_t* q, uint32_t L,
+                        hipStream_t st, std::vector<uint64_t>& sizes, Place place) {
+    SplitChunkEncode e;
+    TRY(split_count_chunks(e, rgb, B, d, wavelet, q, L, st, sizes));
+    std::vector<uint8_t*> outs(B, nullptr);
+    TRY(place(sizes, outs));
+    return split_write_chunks(e, outs, st);
 }
 
 // Decode of B equal-shaped chunks: hdr[i] validated, d_alc[i] the chunk's first byte on the device, pixels to rgb[i].
@@ -3412,6 +3443,164 @@ void write_empty_split(uint8_t* p, uint8_t wavelet, uint32_t w, uint32_t h, uint
         uint8_t* q = p + kSplitFixedHeaderBytes + (size_t)c * kSplitChannelHeaderBytes;
         put_u32(q, (uint32_t)step); put_u32(q + 4, (uint32_t)step);
     }
+}
+
+// ---- size prediction and budget encodes of version 2 ----
+constexpr uint32_t kSplitRefineTrials = 4;   // ALICE_SPLIT_REFINE_TRIALS
+
+// Whole-container brackets of one chunk at the 101 qualities from its 64 x 3 channel payload brackets.
+void split_rate_by_quality(const RateChannel* rc, uint64_t* lo, uint64_t* hi) {
+    for (int q = 0; q < kQualities; ++q) {
+        const RateChannel* c = rc + (size_t)(quality_to_step((uint8_t)q) - 1) * 3;
+        lo[q] = kSplitHeaderBytes + c[0].lo + c[1].lo + c[2].lo;
+        hi[q] = kSplitHeaderBytes + c[0].hi + c[1].hi + c[2].hi;
+    }
+}
+
+thread_local std::vector<uint32_t> tl_split_trials;   // alice_codec_test_last_split_trials
+
+// The budget rule of version 2.  q0 = the largest quality in [min_q, max_q] whose upper bound fits.  Above q0 (everywhere
+// when there is no q0) the qualities whose bracket straddles the budget are tried from the highest down, one exact size
+// (exact(q, &size): forward pass, table, count pass) per quantiser step not tried before, at most kSplitRefineTrials in all;
+// the first that fits is chosen.  Otherwise q0; without one, min_q with *fits = 0.  Qualities above 100 act as 100.
+template <typename Exact>
+int split_choose_quality(const uint64_t* lo, const uint64_t* hi, uint64_t budget, uint8_t min_q, uint8_t max_q, Exact exact,
+                         uint8_t* chosen, uint8_t* fits, uint32_t* trials) {
+    min_q = std::min<uint8_t>(min_q, 100); max_q = std::min<uint8_t>(max_q, 100);
+    int q0 = -1;
+    for (int q = max_q; q >= min_q && q0 < 0; --q)
+        if (hi[q] <= budget) q0 = q;
+    bool tried[65] = {};
+    *trials = 0;
+    for (int q = max_q; q > q0 && q >= min_q && *trials < kSplitRefineTrials; --q) {
+        if (!(lo[q] <= budget && budget < hi[q])) continue;
+        const int32_t step = quality_to_step((uint8_t)q);
+        if (tried[step]) continue;
+        tried[step] = true;
+        ++*trials;
+        uint64_t size = 0;
+        TRY(exact((uint8_t)q, &size));
+        if (size <= budget) { *chosen = (uint8_t)q; *fits = 1; return kOk; }
+    }
+    *chosen = (uint8_t)(q0 >= 0 ? q0 : min_q);
+    *fits = q0 >= 0 ? 1 : 0;
+    return kOk;
+}
+
+// The qualities of n equal-shaped chunks under their budgets: one prediction pass per group, then the refinement trials
+// chunk by chunk.  Returns after the stream has drained; nothing is written.
+int split_choose_chunks(const RgbLayout* rgb, uint32_t n, const ChunkDims& d, uint8_t wavelet, uint32_t L, const uint64_t* budgets,
+                        uint8_t min_q, uint8_t max_q, uint8_t* chosen, uint8_t* fits, hipStream_t st) {
+    tl_split_trials.assign(n, 0u);
+    const uint32_t group = split_group(d);
+    uint64_t lo[kQualities], hi[kQualities];
+    for (uint32_t first = 0; first < n; first += group) {
+        const uint32_t B = std::min(group, n - first);
+        std::vector<RateChannel> rc;
+        {
+            EncodeWork w;
+            w.d = d; w.n_chunks = 1;
+            if (transform_tiles_eligible(d)) TRY(w.scratch.alloc(forward_scratch_bytes(d)));
+            TRY(predict_chunks(rgb + first, B, d, wavelet, w, st, nullptr, rc, L));
+        }
+        for (uint32_t i = 0; i < B; ++i) {
+            const uint32_t k = first + i;
+            split_rate_by_quality(rc.data() + (size_t)i * 192, lo, hi);
+            TRY(split_choose_quality(lo, hi, budgets[k], min_q, max_q,
+                                     [&](uint8_t q, uint64_t* size) -> int {
+                                         SplitChunkEncode e;
+                                         std::vector<uint64_t> sz;
+                                         TRY(split_count_chunks(e, rgb + k, 1, d, wavelet, &q, L, st, sz));
+                                         *size = sz[0];
+                                         return kOk;
+                                     },
+                                     chosen + k, fits + k, &tl_split_trials[k]));
+        }
+    }
+    return kOk;
+}
+
+// n equal-shaped chunks at their layouts -> version 2 bytes at d_out + i * out_stride, in groups of split_group.
+int split_encode_layouts(const RgbLayout* rgb, uint32_t n, const ChunkDims& d, uint8_t wavelet, const uint8_t* q, uint32_t L, void* d_out,
+                         uint64_t out_stride, uint64_t* sizes, hipStream_t st) {
+    const uint32_t group = split_group(d);
+    for (uint32_t first = 0; first < n; first += group) {
+        const uint32_t B = std::min(group, n - first);
+        std::vector<uint64_t> sz;
+        TRY(split_encode_chunks(rgb + first, B, d, wavelet, q + first, L, st, sz,
+                                [&](const std::vector<uint64_t>& s, std::vector<uint8_t*>& outs) -> int {
+                                    for (uint32_t i = 0; i < B; ++i) {
+                                        if (s[i] > out_stride)
+                                            return fail(kInvalidBufferSize, "chunk " + std::to_string(first + i) + " needs " + std::to_string(s[i]) +
+                                                                                " bytes, the output stride is " + std::to_string(out_stride));
+                                        outs[i] = (uint8_t*)d_out + (size_t)(first + i) * out_stride;
+                                    }
+                                    return kOk;
+                                }));
+        for (uint32_t i = 0; i < B; ++i) sizes[first + i] = sz[i];
+    }
+    return kOk;
+}
+
+// Where the chunks of a device call live.  origins == NULL: n packed chunks back to back at d_frames.  Otherwise chunk i is
+// frames [i * f, (i + 1) * f) of the frame_width x frame_height frames at d_frames, cropped to w x h at origins[2i],
+// origins[2i + 1] (the rule of region_layouts: a rectangle that leaves the frame is an error before anything is queued).
+int split_layouts(const void* d_frames, uint32_t frame_width, uint32_t frame_height, const uint32_t* origins, const ChunkDims& d,
+                  uint32_t n, std::vector<RgbLayout>& out) {
+    out.resize(n);
+    if (!origins) {
+        for (uint32_t i = 0; i < n; ++i) out[i] = packed_rgb((const uint8_t*)d_frames + (size_t)i * d.n_pixels * 3, d);
+        return kOk;
+    }
+    uint64_t frame_px = 0;
+    TRY(checked_pixel_count(frame_width, frame_height, (uint64_t)d.f * n, &frame_px));
+    if (frame_px > UINT64_MAX / 3) return fail(kDimensionOverflow, "dimensions overflow usize");
+    const uint64_t row_pitch = 3ull * frame_width, frame_pitch = row_pitch * frame_height;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint64_t x0 = origins[2 * i], y0 = origins[2 * i + 1];
+        if (x0 + d.w > frame_width || y0 + d.h > frame_height)
+            return fail(kInvalidDimensions, "region " + std::to_string(i) + " at (" + std::to_string(x0) + ", " + std::to_string(y0) +
+                                                ") does not lie inside the " + std::to_string(frame_width) + "x" + std::to_string(frame_height) + " frame");
+        out[i] = RgbLayout{(uint8_t*)d_frames + (size_t)i * d.f * frame_pitch + y0 * row_pitch + x0 * 3, row_pitch, frame_pitch};
+    }
+    return kOk;
+}
+
+// wavelet, then lane_symbols (0: the default), in the order of the split calls
+int check_split_args(uint8_t wavelet_type, uint32_t lane_symbols, uint32_t* L) {
+    if (wavelet_type > 2) return fail(kInvalidBitstream, "unknown wavelet type");
+    *L = lane_symbols ? lane_symbols : kSplitDefaultLane;
+    if (!split_lane_ok(*L)) return fail(kInvalidDimensions, "lane_symbols must be a power of two in [64, 16384]");
+    return kOk;
+}
+
+// Decode of n device containers into the layouts that layouts_of(dims of the headers, out) names; the headers come to the
+// host first, and nothing is queued before they and the layouts have been accepted.
+template <typename LayoutsOf>
+int split_decode_device(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks, hipStream_t st, LayoutsOf layouts_of) {
+    std::vector<uint8_t> raw((size_t)n_chunks * kSplitHeaderBytes, 0);
+    for (uint32_t i = 0; i < n_chunks; ++i)
+        HIP_TRY(hipMemcpyAsync(raw.data() + (size_t)i * kSplitHeaderBytes, (const uint8_t*)d_alc + (size_t)i * alc_stride,
+                               std::min<uint64_t>(sizes[i], kSplitHeaderBytes), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    std::vector<SplitHeader> hdr(n_chunks);
+    std::vector<const uint8_t*> ptr(n_chunks);
+    ChunkDims d{};
+    for (uint32_t i = 0; i < n_chunks; ++i) {
+        ChunkDims di{};
+        TRY(parse_split_header(raw.data() + (size_t)i * kSplitHeaderBytes, sizes[i], hdr[i], &di));
+        if (di.n_pixels == 0) return fail(kInvalidDimensions, "invalid dimensions");
+        if (i == 0) d = di;
+        else if (di.w != d.w || di.h != d.h || di.f != d.f || hdr[i].lane_symbols != hdr[0].lane_symbols)
+            return fail(kInvalidDimensions, "the chunks of one call must have the same shape and lane_symbols");
+        ptr[i] = (const uint8_t*)d_alc + (size_t)i * alc_stride;
+    }
+    std::vector<RgbLayout> layouts;
+    TRY(layouts_of(d, layouts));
+    const uint32_t group = split_group(d);
+    for (uint32_t first = 0; first < n_chunks; first += group)
+        TRY(split_decode_chunks(hdr.data() + first, ptr.data() + first, std::min(group, n_chunks - first), d, layouts.data() + first, st));
+    return kOk;
 }
 
 }  // namespace
@@ -3609,23 +3798,7 @@ int alice_codec_dev_encode_split(const void* d_rgb, uint32_t width, uint32_t hei
         layouts[i] = packed_rgb((const uint8_t*)d_rgb + (size_t)i * d.n_pixels * 3, d);
         q[i] = qualities ? qualities[i] : quality;
     }
-    const uint32_t group = split_group(d);
-    for (uint32_t first = 0; first < n_chunks; first += group) {
-        const uint32_t B = std::min(group, n_chunks - first);
-        std::vector<uint64_t> sz;
-        TRY(split_encode_chunks(layouts.data() + first, B, d, wavelet_type, q.data() + first, L, st, sz,
-                                [&](const std::vector<uint64_t>& s, std::vector<uint8_t*>& outs) -> int {
-                                    for (uint32_t i = 0; i < B; ++i) {
-                                        if (s[i] > out_stride)
-                                            return fail(kInvalidBufferSize, "chunk " + std::to_string(first + i) + " needs " + std::to_string(s[i]) +
-                                                                                " bytes, the output stride is " + std::to_string(out_stride));
-                                        outs[i] = (uint8_t*)d_out + (size_t)(first + i) * out_stride;
-                                    }
-                                    return kOk;
-                                }));
-        for (uint32_t i = 0; i < B; ++i) sizes[first + i] = sz[i];
-    }
-    return kOk;
+    return split_encode_layouts(layouts.data(), n_chunks, d, wavelet_type, q.data(), L, d_out, out_stride, sizes, st);
 }
 
 int alice_codec_dev_decode_split(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks, void* d_rgb_out,
@@ -3638,29 +3811,194 @@ int alice_codec_dev_decode_split(const void* d_alc, uint64_t alc_stride, const u
     TRY(ensure_device());
     hipStream_t st = (hipStream_t)hip_stream;
     ScopeStream scope(st);
-    std::vector<uint8_t> raw((size_t)n_chunks * kSplitHeaderBytes, 0);
-    for (uint32_t i = 0; i < n_chunks; ++i)
-        HIP_TRY(hipMemcpyAsync(raw.data() + (size_t)i * kSplitHeaderBytes, (const uint8_t*)d_alc + (size_t)i * alc_stride,
-                               std::min<uint64_t>(sizes[i], kSplitHeaderBytes), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    std::vector<SplitHeader> hdr(n_chunks);
-    std::vector<const uint8_t*> ptr(n_chunks);
-    std::vector<RgbLayout> layouts(n_chunks);
+    return split_decode_device(d_alc, alc_stride, sizes, n_chunks, st, [&](const ChunkDims& d, std::vector<RgbLayout>& out) {
+        return split_layouts(d_rgb_out, 0, 0, nullptr, d, n_chunks, out);
+    });
+}
+
+// ---- version 2: size prediction, budget encodes, regions of device frames ----
+
+int alice_codec_predict_split_sizes(uint8_t wavelet_type, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
+                                    uint32_t frames, uint32_t lane_symbols, uint64_t lo[101], uint64_t hi[101]) {
+    clear_error();
+    if (!lo || !hi || (!rgb && rgb_len)) return fail(kNullArgument, "null argument");
+    uint64_t n_pixels = 0;
+    TRY(checked_pixel_count(width, height, frames, &n_pixels));
+    if (n_pixels == 0 && rgb_len != 0) return fail(kInvalidBufferSize, "buffer size mismatch: expected 0, got " + std::to_string(rgb_len));
+    const FrameEncoder enc{0, wavelet_type};
     ChunkDims d{};
-    for (uint32_t i = 0; i < n_chunks; ++i) {
-        ChunkDims di{};
-        TRY(parse_split_header(raw.data() + (size_t)i * kSplitHeaderBytes, sizes[i], hdr[i], &di));
-        if (di.n_pixels == 0) return fail(kInvalidDimensions, "invalid dimensions");
-        if (i == 0) d = di;
-        else if (di.w != d.w || di.h != d.h || di.f != d.f || hdr[i].lane_symbols != hdr[0].lane_symbols)
-            return fail(kInvalidDimensions, "the chunks of one call must have the same shape and lane_symbols");
-        ptr[i] = (const uint8_t*)d_alc + (size_t)i * alc_stride;
-        layouts[i] = packed_rgb((uint8_t*)d_rgb_out + (size_t)i * d.n_pixels * 3, d);
+    EncodedChunk* none = nullptr;
+    if (n_pixels) TRY(validate_encode_many(&enc, rgb, rgb_len, width, height, frames, 1, &none, &d));
+    uint32_t L = 0;
+    TRY(check_split_args(wavelet_type, lane_symbols, &L));
+    if (n_pixels == 0) {   // an empty chunk is its header at every quality
+        for (int q = 0; q < kQualities; ++q) lo[q] = hi[q] = kSplitHeaderBytes;
+        return kOk;
     }
-    const uint32_t group = split_group(d);
-    for (uint32_t first = 0; first < n_chunks; first += group)
-        TRY(split_decode_chunks(hdr.data() + first, ptr.data() + first, std::min(group, n_chunks - first), d, layouts.data() + first, st));
+    hipStream_t st;
+    TRY(get_stream(&st));
+    DevBuf d_rgb;
+    EncodeWork w;
+    w.d = d; w.n_chunks = 1;
+    if (transform_tiles_eligible(d)) TRY(w.scratch.alloc(forward_scratch_bytes(d)));
+    TRY(d_rgb.alloc(n_pixels * 3));
+    HIP_TRY(hipMemcpyAsync(d_rgb.p, rgb, n_pixels * 3, hipMemcpyHostToDevice, st));
+    const RgbLayout layout = packed_rgb(d_rgb.p, d);
+    std::vector<RateChannel> rc;
+    TRY(predict_chunks(&layout, 1, d, wavelet_type, w, st, nullptr, rc, L));
+    split_rate_by_quality(rc.data(), lo, hi);
     return kOk;
+}
+
+int alice_codec_dev_predict_split_sizes(const void* d_rgb, uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks,
+                                        uint8_t wavelet_type, uint32_t lane_symbols, uint64_t* lo, uint64_t* hi, void* hip_stream) {
+    clear_error();
+    if (!d_rgb || !lo || !hi) return fail(kNullArgument, "null argument");
+    ChunkDims d{};
+    TRY(chunk_dims(width, height, frames, &d, n_chunks));
+    uint32_t L = 0;
+    TRY(check_split_args(wavelet_type, lane_symbols, &L));
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);
+    EncodeWork w;
+    w.d = d; w.n_chunks = 1;
+    if (transform_tiles_eligible(d)) TRY(w.scratch.alloc(forward_scratch_bytes(d)));
+    std::vector<RgbLayout> layouts;
+    TRY(split_layouts(d_rgb, 0, 0, nullptr, d, n_chunks, layouts));
+    const uint32_t group = split_group(d);
+    for (uint32_t first = 0; first < n_chunks; first += group) {
+        const uint32_t B = std::min(group, n_chunks - first);
+        std::vector<RateChannel> rc;
+        TRY(predict_chunks(layouts.data() + first, B, d, wavelet_type, w, st, nullptr, rc, L));
+        for (uint32_t i = 0; i < B; ++i)
+            split_rate_by_quality(rc.data() + (size_t)i * 192, lo + (size_t)(first + i) * kQualities, hi + (size_t)(first + i) * kQualities);
+    }
+    return kOk;
+}
+
+uint8_t* alice_codec_encode_split_to_size(uint8_t wavelet_type, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
+                                          uint32_t frames, uint32_t lane_symbols, uint64_t max_bytes, uint8_t min_q, uint8_t max_q,
+                                          uint8_t* chosen_q, uint8_t* fits, uint64_t* out_len) {
+    clear_error();
+    if (!chosen_q || !fits || !out_len || (!rgb && rgb_len)) { fail(kNullArgument, "null argument"); return nullptr; }
+    auto run = [&](uint8_t** out) -> int {
+        uint64_t n_pixels = 0;
+        TRY(checked_pixel_count(width, height, frames, &n_pixels));
+        if (n_pixels == 0 && rgb_len != 0) return fail(kInvalidBufferSize, "buffer size mismatch: expected 0, got " + std::to_string(rgb_len));
+        const FrameEncoder enc{0, wavelet_type};
+        ChunkDims d{};
+        EncodedChunk* none = nullptr;
+        if (n_pixels) TRY(validate_encode_many(&enc, rgb, rgb_len, width, height, frames, 1, &none, &d));
+        uint32_t L = 0;
+        TRY(check_split_args(wavelet_type, lane_symbols, &L));
+        TRY(check_quality_range(min_q, max_q));
+        if (n_pixels == 0) {
+            uint64_t lo[kQualities], hi[kQualities];
+            for (int q = 0; q < kQualities; ++q) lo[q] = hi[q] = kSplitHeaderBytes;
+            tl_split_trials.assign(1, 0u);
+            TRY(split_choose_quality(lo, hi, max_bytes, min_q, max_q, [](uint8_t, uint64_t*) -> int { return kOk; }, chosen_q, fits,
+                                     &tl_split_trials[0]));
+            *out = host_result_alloc(kSplitHeaderBytes);
+            if (!*out) return fail(kOutOfMemory, "out of host memory");
+            write_empty_split(*out, wavelet_type, width, height, frames, L, quality_to_step(*chosen_q));
+            *out_len = kSplitHeaderBytes;
+            return kOk;
+        }
+        hipStream_t st;
+        TRY(get_stream(&st));
+        DevBuf d_rgb, d_out;
+        TRY(d_rgb.alloc(n_pixels * 3));
+        HIP_TRY(hipMemcpyAsync(d_rgb.p, rgb, n_pixels * 3, hipMemcpyHostToDevice, st));
+        const RgbLayout layout = packed_rgb(d_rgb.p, d);
+        TRY(split_choose_chunks(&layout, 1, d, wavelet_type, L, &max_bytes, min_q, max_q, chosen_q, fits, st));
+        std::vector<uint64_t> sizes;
+        TRY(split_encode_chunks(&layout, 1, d, wavelet_type, chosen_q, L, st, sizes,
+                                [&](const std::vector<uint64_t>& sz, std::vector<uint8_t*>& outs) -> int {
+                                    TRY(d_out.alloc(sz[0]));
+                                    outs[0] = d_out.as<uint8_t>();
+                                    return kOk;
+                                }));
+        *out = host_result_alloc(sizes[0]);
+        if (!*out) return fail(kOutOfMemory, "out of host memory");
+        const int rc = copy_to_host(*out, d_out.p, sizes[0], st);
+        if (rc != kOk) { free(*out); *out = nullptr; return rc; }
+        *out_len = sizes[0];
+        return kOk;
+    };
+    uint8_t* out = nullptr;
+    return run(&out) == kOk ? out : nullptr;
+}
+
+int alice_codec_dev_encode_split_regions(const void* d_frames, uint32_t frame_width, uint32_t frame_height, const uint32_t* origins,
+                                         uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks, uint8_t wavelet_type,
+                                         uint8_t quality, const uint8_t* qualities, uint32_t lane_symbols, void* d_out,
+                                         uint64_t out_stride, uint64_t* sizes, void* hip_stream) {
+    clear_error();
+    if (!d_frames || !origins || !d_out || !sizes) return fail(kNullArgument, "null argument");
+    ChunkDims d{};
+    TRY(chunk_dims(width, height, frames, &d, n_chunks));
+    std::vector<RgbLayout> layouts;
+    TRY(split_layouts(d_frames, frame_width, frame_height, origins, d, n_chunks, layouts));
+    uint32_t L = 0;
+    TRY(check_split_args(wavelet_type, lane_symbols, &L));
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);
+    std::vector<uint8_t> q(n_chunks);
+    for (uint32_t i = 0; i < n_chunks; ++i) q[i] = qualities ? qualities[i] : quality;
+    return split_encode_layouts(layouts.data(), n_chunks, d, wavelet_type, q.data(), L, d_out, out_stride, sizes, st);
+}
+
+int alice_codec_dev_decode_split_regions(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks,
+                                         void* d_frames_out, uint32_t frame_width, uint32_t frame_height, const uint32_t* origins,
+                                         void* hip_stream) {
+    clear_error();
+    if (!d_alc || !sizes || !d_frames_out || !origins) return fail(kNullArgument, "null argument");
+    if (n_chunks == 0) return fail(kInvalidDimensions, "empty batch");
+    for (uint32_t i = 0; i < n_chunks; ++i) {
+        if (sizes[i] > alc_stride && n_chunks > 1) return fail(kInvalidBufferSize, "chunk " + std::to_string(i) + " is longer than the stride");
+        if (origins[2 * i] >= frame_width || origins[2 * i + 1] >= frame_height)   // (the whole rectangle once the headers are read)
+            return fail(kInvalidDimensions, "region " + std::to_string(i) + " starts outside the " + std::to_string(frame_width) + "x" +
+                                                std::to_string(frame_height) + " frame");
+    }
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);
+    return split_decode_device(d_alc, alc_stride, sizes, n_chunks, st, [&](const ChunkDims& d, std::vector<RgbLayout>& out) {
+        return split_layouts(d_frames_out, frame_width, frame_height, origins, d, n_chunks, out);
+    });
+}
+
+int alice_codec_dev_encode_split_to_budget(const void* d_frames, uint32_t frame_width, uint32_t frame_height, const uint32_t* origins,
+                                           uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks, uint8_t wavelet_type,
+                                           uint32_t lane_symbols, const uint64_t* budgets, uint8_t min_q, uint8_t max_q, uint8_t* chosen,
+                                           uint8_t* fits, void* d_out, uint64_t out_stride, uint64_t* sizes, void* hip_stream) {
+    clear_error();
+    if (!d_frames || !budgets || !chosen || !fits || !d_out || !sizes) return fail(kNullArgument, "null argument");
+    ChunkDims d{};
+    TRY(chunk_dims(width, height, frames, &d, n_chunks));
+    std::vector<RgbLayout> layouts;
+    TRY(split_layouts(d_frames, frame_width, frame_height, origins, d, n_chunks, layouts));
+    uint32_t L = 0;
+    TRY(check_split_args(wavelet_type, lane_symbols, &L));
+    TRY(check_quality_range(min_q, max_q));
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);
+    // the choices reach the caller only with the bytes: a failed call leaves chosen / fits / sizes as they were
+    std::vector<uint8_t> q(n_chunks), ok(n_chunks);
+    std::vector<uint64_t> sz(n_chunks);
+    TRY(split_choose_chunks(layouts.data(), n_chunks, d, wavelet_type, L, budgets, min_q, max_q, q.data(), ok.data(), st));
+    TRY(split_encode_layouts(layouts.data(), n_chunks, d, wavelet_type, q.data(), L, d_out, out_stride, sz.data(), st));
+    for (uint32_t i = 0; i < n_chunks; ++i) { chosen[i] = q[i]; fits[i] = ok[i]; sizes[i] = sz[i]; }
+    return kOk;
+}
+
+uint32_t alice_codec_test_last_split_trials(uint32_t* per_chunk, uint32_t cap) {
+    const uint32_t n = (uint32_t)tl_split_trials.size();
+    for (uint32_t i = 0; i < n && i < cap && per_chunk; ++i) per_chunk[i] = tl_split_trials[i];
+    return n;
 }
 
 }  // extern "C"

@@ -5,7 +5,8 @@
 // (fwd_t_bins_kernel on the tile path, coef_hist_kernel on the generic path) determines the symbol histogram of every
 // step: fold_kernel relabels the bins through the encoder's own value -> symbol map (quant_sym1).  cost_kernel then
 // builds the reference table of each folded histogram (freq_table_256, the code the encoder's table kernel runs),
-// classifies it and brackets the stream length.
+// classifies it and brackets the stream length.  split_cost_kernel does the same for the split-stream container, with that
+// format's normalisation rule and per-lane overheads.
 //
 // The bracket (per channel; n = number of symbols, f = a symbol's table frequency, encoder of src/rans.rs:244-308):
 //   The state starts at x0 = 2^23.  Before a symbol it is renormalised (x >>= 8, one byte out, while x >= f * 2^19) and
@@ -35,6 +36,7 @@
 #include "common.h"
 #include "freq_table.h"
 #include "kernels.h"
+#include "split_norm.h"
 #include "symbols.h"
 
 namespace alice {
@@ -124,6 +126,40 @@ __global__ __launch_bounds__(256) void cost_kernel(const uint32_t* __restrict__ 
     }
 }
 
+// The same for the split-stream container (.alc v2): one workgroup per (chunk, channel, step - 1).  The table
+// is the one split_table_kernel stores (split_normalize_256): it sums to exactly 4096, so every lane of the payload is a chain
+// of the argument above with e = 0, starting at 2^23 and ending in four state bytes.  With n symbols in B blocks of 64 * L,
+// K lanes that own a symbol, M / u / g as above, the lane bounds add up to
+//   sum of lane bytes <= (M + n u) / 8 + 4 K        sum of lane bytes > (M - n g - 8 K) / (8 + g) + 4 K
+// and the payload adds 4 bytes of block length and a 128-byte lane directory per block.  No table is unbounded: a present
+// symbol has 1 <= f <= 4096.  K <= n <= 2^32: 8 K 2^24 and n g stay below 2^60.
+__global__ __launch_bounds__(256) void split_cost_kernel(const uint32_t* __restrict__ step_hist, const uint32_t* __restrict__ log_lo,
+                                                         const uint32_t* __restrict__ log_hi, uint32_t g_up, uint32_t g_dn,
+                                                         uint32_t lane_symbols, RateChannel* __restrict__ out) {
+    __shared__ unsigned long long red64[4];
+    __shared__ uint32_t red32[4];
+    const uint32_t count = step_hist[(size_t)blockIdx.x * 256 + threadIdx.x];
+    unsigned long long n;
+    const uint32_t f = split_normalize_256(count, red64, red32, n);
+    const unsigned long long s_lo = block_sum_256(count ? (unsigned long long)count * log_lo[f] : 0ull, red64);
+    const unsigned long long s_hi = block_sum_256(count ? (unsigned long long)count * log_hi[f] : 0ull, red64);
+    if (threadIdx.x == 0) {
+        RateChannel r{};
+        r.status = kRateBounded;
+        if (n) {
+            const unsigned long long one = 1ull << kRateFracBits, per_block = 64ull * lane_symbols;
+            const unsigned long long blocks = (n + per_block - 1ull) / per_block;
+            const unsigned long long last = n - (blocks - 1ull) * per_block;   // symbols of the last block, >= 1
+            const unsigned long long lanes = 64ull * (blocks - 1ull) + (last < 64ull ? last : 64ull);
+            const unsigned long long fixed = 132ull * blocks + 4ull * lanes;
+            r.hi = fixed + (s_hi + n * g_up) / (8ull * one);
+            const unsigned long long sub = n * g_dn + 8ull * lanes * one;
+            r.lo = fixed + (s_lo > sub ? (s_lo - sub + 8ull * one + g_dn - 1ull) / (8ull * one + g_dn) : 0ull);
+        }
+        out[blockIdx.x] = r;
+    }
+}
+
 void launch_rate_fold(const uint32_t* d_bins, const uint32_t* d_oor, uint32_t n_chunks, uint32_t* d_step_hist, hipStream_t st) {
     hipLaunchKernelGGL(fold_kernel, dim3(n_chunks * 192u), dim3(256), 0, st, d_bins, d_oor, (uint32_t)value_table_radius(), d_step_hist);
 }
@@ -132,6 +168,13 @@ void launch_rate_cost(const uint32_t* d_step_hist, const uint32_t* d_log, uint32
     const RateLogTable& t = rate_log_table();
     hipLaunchKernelGGL(cost_kernel, dim3(n_chunks * 192u), dim3(256), 0, st, d_step_hist, d_log, d_log + (kProbScale + 1),
                        t.g_up, t.g_dn, d_out);
+}
+
+void launch_split_rate_cost(const uint32_t* d_step_hist, const uint32_t* d_log, uint32_t n_chunks, uint32_t lane_symbols,
+                            RateChannel* d_out, hipStream_t st) {
+    const RateLogTable& t = rate_log_table();
+    hipLaunchKernelGGL(split_cost_kernel, dim3(n_chunks * 192u), dim3(256), 0, st, d_step_hist, d_log, d_log + (kProbScale + 1),
+                       t.g_up, t.g_dn, lane_symbols, d_out);
 }
 
 // floor / ceil of log2(4096 / f) * 2^24 for f = 0 .. 4096 (entry 0 unused), and the two log2(1 +- 2^-11) terms rounded

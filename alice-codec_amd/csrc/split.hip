@@ -18,6 +18,7 @@
 // Every store to memory is a vector store; the scalar unit only reads.
 #include "common.h"
 #include "kernels.h"
+#include "split_norm.h"
 
 namespace alice {
 
@@ -32,36 +33,11 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane) {
     return v;
 }
 
-// max over the 256 threads of a block; red: 4 u32 of LDS
-__device__ __forceinline__ uint32_t block_max_256(uint32_t v, uint32_t* red) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t o = __shfl_xor(v, d, 64);
-        v = o > v ? o : v;
-    }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const uint32_t a = red[0] > red[1] ? red[0] : red[1], b = red[2] > red[3] ? red[2] : red[3];
-    return a > b ? a : b;
-}
-
-__device__ __forceinline__ unsigned long long block_sum_256(unsigned long long v, unsigned long long* red) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
-
 }  // namespace
 
 // ----------------------------------------------------------------------------------
-// Normalisation: freq = max(1, floor(count * 4096 / total)) for a present symbol, 0 for an absent one;
-// a short sum gives the whole deficit to the largest frequency (lowest symbol on ties); a sum that is over takes one at
-// a time from the currently largest frequency (lowest symbol on ties).  The excess is at most the number of symbols the
-// floor of 1 lifted, so the loop runs at most 255 rounds.  One 256-thread workgroup per table.
+// Normalisation (the rule itself is split_normalize_256 of split_norm.h, which the size prediction of
+// rate.hip calls too) and the running sum of the frequencies.  One 256-thread workgroup per table.
 // ----------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void split_table_kernel(const uint32_t* __restrict__ hist, uint16_t* __restrict__ freq,
                                                           uint16_t* __restrict__ cum) {
@@ -70,27 +46,8 @@ __global__ __launch_bounds__(256) void split_table_kernel(const uint32_t* __rest
     __shared__ uint32_t scan[256];
     const int s = threadIdx.x;
     const size_t t = blockIdx.x;
-    const uint32_t count = hist[t * 256 + s];
-    const unsigned long long total = block_sum_256(count, red64);
-    uint32_t f = 0u;
-    if (count) {
-        f = (uint32_t)(((unsigned long long)count << kProbBits) / total);
-        if (f < 1u) f = 1u;
-    }
-    if (total) {
-        uint32_t sum = (uint32_t)block_sum_256(f, red64);
-        // key: larger frequency first, then the lower symbol
-        uint32_t top = block_max_256((f << 8) | (255u - (uint32_t)s), red32);
-        if (sum < kProbScale) {
-            if (255u - (top & 255u) == (uint32_t)s) f += kProbScale - sum;
-        } else {
-            while (sum > kProbScale) {   // uniform across the block
-                if (255u - (top & 255u) == (uint32_t)s) f -= 1u;
-                sum -= 1u;
-                top = block_max_256((f << 8) | (255u - (uint32_t)s), red32);
-            }
-        }
-    }
+    unsigned long long total;
+    const uint32_t f = split_normalize_256(hist[t * 256 + s], red64, red32, total);
     scan[s] = f;
     __syncthreads();
     for (int d = 1; d < 256; d <<= 1) {

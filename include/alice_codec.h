@@ -441,6 +441,53 @@ int alice_codec_dev_encode_split(const void *d_rgb, uint32_t width, uint32_t hei
 int alice_codec_dev_decode_split(const void *d_alc, uint64_t alc_stride, const uint64_t *sizes, uint32_t n_chunks,
                                  void *d_rgb_out, void *hip_stream);
 
+/* ---- version 2: size prediction, byte budgets, regions of device frames ----
+ * Validation of every call below is host code and runs in this order before a device is looked for: NULL arguments,
+ * dimensions (overflow, empty), buffer size / regions inside the frame, wavelet byte (ALICE_ERR_INVALID_BITSTREAM),
+ * lane_symbols (ALICE_ERR_INVALID_DIMENSIONS), then the quality range (min_q > max_q after qualities above 100 became 100:
+ * ALICE_ERR_INVALID_DIMENSIONS).  Memory comes from the library's pool; nothing goes through the chain hub. */
+enum { ALICE_SPLIT_REFINE_TRIALS = 4 };
+/* lo[q] <= length of alice_codec_encode_split at quality q <= hi[q] for q = 0 .. 100, from one forward transform (no
+ * entropy coding): the bracket of every channel payload (about one byte per lane wide) plus the 1630-byte header.  Every
+ * version 2 table is bounded, so there is no status array.  A chunk without pixels is 1630 / 1630. */
+int alice_codec_predict_split_sizes(uint8_t wavelet_type, const uint8_t *rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
+                                    uint32_t frames, uint32_t lane_symbols, uint64_t lo[101], uint64_t hi[101]);
+/* n_chunks packed device chunks; lo / hi: n_chunks * 101 */
+int alice_codec_dev_predict_split_sizes(const void *d_rgb, uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks,
+                                        uint8_t wavelet_type, uint32_t lane_symbols, uint64_t *lo, uint64_t *hi, void *hip_stream);
+/* One chunk as version 2 bytes at the quality the budget rule picks in [min_q, max_q] (qualities above 100 act as 100):
+ *  1. q0 = the largest quality whose hi fits max_bytes;
+ *  2. the qualities above q0 (all of them without a q0) whose bracket straddles max_bytes are tried from the highest down,
+ *     one exact size (forward pass, table, count pass: no byte written) per quantiser step not tried before, at most
+ *     ALICE_SPLIT_REFINE_TRIALS in all; the first that fits is chosen;
+ *  3. otherwise q0; without one, min_q with *fits = 0 (the chunk is still encoded).
+ * The bytes are exactly alice_codec_encode_split's at *chosen_q.  Free with alice_codec_data_free64; NULL on error. */
+uint8_t *alice_codec_encode_split_to_size(uint8_t wavelet_type, const uint8_t *rgb, uint64_t rgb_len, uint32_t width,
+                                          uint32_t height, uint32_t frames, uint32_t lane_symbols, uint64_t max_bytes,
+                                          uint8_t min_q, uint8_t max_q, uint8_t *chosen_q, uint8_t *fits, uint64_t *out_len);
+/* Regions of device frames, with the semantics of alice_codec_batch_encode_regions / _decode_regions: chunk i is frames
+ * [i * frames, (i + 1) * frames) of the frame_width x frame_height packed RGB frames at d_frames, cropped to width x height
+ * at origins[2i], origins[2i + 1] (2 * n_chunks u32, read before return).  A rectangle that does not lie inside the frame
+ * is ALICE_ERR_INVALID_DIMENSIONS with nothing queued or written.  The bytes of chunk i are alice_codec_encode_split's of
+ * the crop; otherwise as alice_codec_dev_encode_split. */
+int alice_codec_dev_encode_split_regions(const void *d_frames, uint32_t frame_width, uint32_t frame_height, const uint32_t *origins,
+                                         uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks, uint8_t wavelet_type,
+                                         uint8_t quality, const uint8_t *qualities, uint32_t lane_symbols, void *d_out,
+                                         uint64_t out_stride, uint64_t *sizes, void *hip_stream);
+/* alice_codec_dev_decode_split with chunk i pasted into its rectangle of frames [i * frames, (i + 1) * frames) of
+ * d_frames_out (shape from the headers): no byte outside the rectangles is written. */
+int alice_codec_dev_decode_split_regions(const void *d_alc, uint64_t alc_stride, const uint64_t *sizes, uint32_t n_chunks,
+                                         void *d_frames_out, uint32_t frame_width, uint32_t frame_height, const uint32_t *origins,
+                                         void *hip_stream);
+/* Budget encode of n_chunks device chunks, chunk i under budgets[i] by the rule of alice_codec_encode_split_to_size:
+ * chosen[i], fits[i], sizes[i] and the bytes at d_out + i * out_stride.  origins == NULL: packed chunks at d_frames
+ * (frame_width / frame_height unused); otherwise regions as above.  On error chosen, fits and sizes are left alone. */
+int alice_codec_dev_encode_split_to_budget(const void *d_frames, uint32_t frame_width, uint32_t frame_height, const uint32_t *origins,
+                                           uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks, uint8_t wavelet_type,
+                                           uint32_t lane_symbols, const uint64_t *budgets, uint8_t min_q, uint8_t max_q,
+                                           uint8_t *chosen, uint8_t *fits, void *d_out, uint64_t out_stride, uint64_t *sizes,
+                                           void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

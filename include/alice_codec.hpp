@@ -590,6 +590,29 @@ inline void split_decode_device(const void* d_alc, uint64_t alc_stride, const st
                                 void* hip_stream = nullptr) {
     detail::check(alice_codec_dev_decode_split(d_alc, alc_stride, sizes.data(), static_cast<uint32_t>(sizes.size()), d_rgb_out, hip_stream));
 }
+// version 2 rate control: the bracket of encode_split's length at the 101 qualities (every version 2 table
+// is bounded: status stays ALICE_RATE_BOUNDED) and one encode at the quality the budget rule picks -- the largest whose
+// upper bound fits, refined by at most ALICE_SPLIT_REFINE_TRIALS exact size counts among the straddling qualities
+inline SizePrediction predict_split_sizes(const std::vector<uint8_t>& rgb, uint32_t w, uint32_t h, uint32_t f,
+                                          WaveletType wt = WaveletType::Cdf53, uint32_t lane_symbols = 0) {
+    static const uint8_t empty = 0;
+    SizePrediction p;
+    detail::check(alice_codec_predict_split_sizes(static_cast<uint8_t>(wt), rgb.empty() ? &empty : rgb.data(), rgb.size(), w, h, f,
+                                                  lane_symbols, p.lo.data(), p.hi.data()));
+    return p;
+}
+struct SizedSplit { std::vector<uint8_t> data; uint8_t quality; bool fits; };
+inline SizedSplit encode_split_to_size(const std::vector<uint8_t>& rgb, uint32_t w, uint32_t h, uint32_t f, uint64_t max_bytes,
+                                       WaveletType wt = WaveletType::Cdf53, uint8_t min_quality = 10, uint8_t max_quality = 95,
+                                       uint32_t lane_symbols = 0) {
+    static const uint8_t empty = 0;
+    uint8_t q = 0, fits = 0;
+    uint64_t n = 0;
+    uint8_t* p = alice_codec_encode_split_to_size(static_cast<uint8_t>(wt), rgb.empty() ? &empty : rgb.data(), rgb.size(), w, h, f,
+                                                  lane_symbols, max_bytes, min_quality, max_quality, &q, &fits, &n);
+    if (!p) detail::raise();
+    return SizedSplit{detail::take(p, n), q, fits != 0};
+}
 
 // The reference's buffer-model rate control (src/rate_control.rs:7-219), host only, with the Rust integer behaviour:
 // u32::midpoint start, buffer half full, 30-entry history, +-0.3 thresholds with +1 / -2 steps, saturating f64 casts

@@ -60,6 +60,11 @@ int alice_codec_test_chain_occupancy(uint32_t out[6]);
  * be NULL.  No device needed. */
 void alice_codec_test_rate_log_table(uint32_t lo[4097], uint32_t hi[4097], uint32_t g[2]);
 
+/* The last version 2 budget call of the calling thread (alice_codec_encode_split_to_size,
+ * alice_codec_dev_encode_split_to_budget): returns its number of chunks and writes the refinement trials (exact sizes
+ * computed, at most ALICE_SPLIT_REFINE_TRIALS each) of the first min(that, cap) chunks to per_chunk (may be NULL). */
+uint32_t alice_codec_test_last_split_trials(uint32_t *per_chunk, uint32_t cap);
+
 #ifdef __cplusplus
 }
 #endif
