@@ -251,6 +251,16 @@ def load_library() -> C.CDLL:
         "alice_codec_dev_encode_split": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint8, _u8p,
                                                    C.c_uint32, vp, C.c_uint64, _u64p, vp]),
         "alice_codec_dev_decode_split": (C.c_int, [vp, C.c_uint64, _u64p, C.c_uint32, vp, vp]),
+        "alice_codec_wide_stream_bound": (C.c_uint64, [C.c_uint64, C.c_uint32]),
+        "alice_codec_dev_wide_encode": (C.c_int, [vp, C.c_uint64, _u32p, C.c_uint32, vp, C.c_uint64, _u64p, vp]),
+        "alice_codec_dev_wide_decode": (C.c_int, [vp, C.c_uint64, _u16p, C.c_uint32, vp, C.c_uint64, vp]),
+        "alice_codec_encode_wide": (vp, [vp, _u8p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _u64p]),
+        "alice_codec_decode_wide": (vp, [_u8p, C.c_uint64, _u64p]),
+        "alice_codec_wide_info": (C.c_int, [_u8p, C.c_uint64, vp]),
+        "alice_codec_dev_encode_wide": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint8, _u8p,
+                                                  C.c_uint32, vp, C.c_uint64, _u64p, vp]),
+        "alice_codec_dev_decode_wide": (C.c_int, [vp, C.c_uint64, _u64p, C.c_uint32, vp, vp]),
+        "alice_codec_dev_forward_symbols_wide": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint8, vp, vp, vp]),
         "alice_codec_predict_split_sizes": (C.c_int, [C.c_uint8, _u8p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                                       _u64p, _u64p]),
         "alice_codec_dev_predict_split_sizes": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint32,
@@ -1753,6 +1763,90 @@ def _padded_pixels(width: int, height: int, frames: int) -> int:
     if width * height * frames == 0:
         return 0
     return (width + (width & 1)) * (height + (height & 1)) * (2 if frames == 1 else frames + (frames & 1))
+
+
+# ---- wide format (.alc version 3) ----
+# Version 2 with an untruncated symbol: the format for the top of the quality scale, where versions 1 and 2 wrap large
+# coefficients modulo 256.  lane_symbols: a power of two in [64, 8192].  No size prediction, budgets or regions yet.
+
+WIDE_MAX_LANE_SYMBOLS = 8192
+
+
+def wide_info(data) -> SplitInfo:
+    """The header fields of a version 3 container (validated, no device needed); the fields are version 2's."""
+    buf = _as_u8(data)
+    c = _CSplitInfo()
+    _check(load_library().alice_codec_wide_info(_p(buf, _u8p), buf.size, C.byref(c)))
+    return SplitInfo(c)
+
+
+def encode_wide(encoder: "FrameEncoder", rgb_frames, width: int, height: int, frames: int, lane_symbols: int = 0) -> bytes:
+    """One chunk as version 3 bytes, with the encoder's wavelet and quality (lane_symbols 0: the default)."""
+    lib = load_library()
+    buf = _as_u8(rgb_frames)
+    _dims_u32(width, height, frames, lane_symbols)
+    n = C.c_uint64(0)
+    src = _p(buf, _u8p) if buf.size else C.cast(C.c_char_p(b""), _u8p)
+    ptr = lib.alice_codec_encode_wide(encoder._h, src, buf.size, width, height, frames, lane_symbols, C.byref(n))
+    if not ptr:
+        _raise_last()
+    try:
+        return _copy_out(ptr, n.value).tobytes()
+    finally:
+        lib.alice_codec_data_free64(ptr, n.value)
+
+
+def decode_wide(data) -> np.ndarray:
+    """The RGB bytes of a version 3 container."""
+    lib = load_library()
+    buf = _as_u8(data)
+    n = C.c_uint64(0)
+    ptr = lib.alice_codec_decode_wide(_p(buf, _u8p), buf.size, C.byref(n))
+    if not ptr:
+        _raise_last()
+    return _adopt(ptr, n.value, lib.alice_codec_data_free64)
+
+
+def wide_stream_bound(n: int, lane_symbols: int = SPLIT_DEFAULT_LANE_SYMBOLS) -> int:
+    return int(load_library().alice_codec_wide_stream_bound(n, lane_symbols))
+
+
+def wide_encode_device(d_rgb_ptr: int, width: int, height: int, frames: int, n_chunks: int, wavelet_type: WaveletType,
+                       quality: int, d_out_ptr: int, out_stride: int, qualities=None, lane_symbols: int = 0,
+                       stream: int = 0) -> np.ndarray:
+    """n_chunks packed device chunks -> version 3 bytes at d_out_ptr + i * out_stride; returns the sizes."""
+    sizes = np.zeros(n_chunks, np.uint64)
+    q = None if qualities is None else np.ascontiguousarray(qualities, dtype=np.uint8).reshape(-1)
+    if q is not None and q.size != n_chunks:
+        raise ValueError("one quality per chunk")
+    _dims_u32(width, height, frames, n_chunks, lane_symbols)
+    _check(load_library().alice_codec_dev_encode_wide(d_rgb_ptr, width, height, frames, n_chunks, int(wavelet_type), quality,
+                                                      None if q is None else _p(q, _u8p), lane_symbols, d_out_ptr, out_stride,
+                                                      _p(sizes, _u64p), stream or None))
+    return sizes
+
+
+def wide_decode_device(d_alc_ptr: int, alc_stride: int, sizes, d_rgb_out_ptr: int, stream: int = 0) -> None:
+    s = np.ascontiguousarray(sizes, dtype=np.uint64).reshape(-1)
+    _check(load_library().alice_codec_dev_decode_wide(d_alc_ptr, alc_stride, _p(s, _u64p), s.size, d_rgb_out_ptr, stream or None))
+
+
+def forward_symbols_wide_device(d_rgb_ptr: int, width: int, height: int, frames: int, wavelet_type: WaveletType, quality: int,
+                                d_symbols_ptr: int, d_hist_ptr: int = 0, stream: int = 0) -> None:
+    """The 3 * padded u16 symbols encode_wide codes (Y, Co, Cg), and optionally the 3 x 256 histogram of min(z, 255)."""
+    _dims_u32(width, height, frames)
+    _check(load_library().alice_codec_dev_forward_symbols_wide(d_rgb_ptr, width, height, frames, int(wavelet_type), quality,
+                                                               d_symbols_ptr, d_hist_ptr or None, stream or None))
+
+
+def decode_alc(data) -> np.ndarray:
+    """The RGB bytes of a container of any version: 1 (FrameDecoder), 2 (decode_split) or 3 (decode_wide)."""
+    version = alc_version(data)
+    if version == 2:
+        return decode_split(data)
+    if version == 3:
+        return decode_wide(data)
+    return FrameDecoder().decode(EncodedChunk.from_bytes(data))   # version 1, and every refusal the v1 parser words
 
 
 # ---- version 2: size prediction, byte budgets, regions of device frames (DESIGN.md section 10.8) ----

@@ -3,8 +3,10 @@
     python -m alice_codec_amd.cli decode INPUT.alc -o OUT.rgb
     python -m alice_codec_amd.cli info INPUT.alc
 `encode --format split [--lane-symbols N]` writes the split-stream container (.alc version 2, DESIGN.md section 10);
-`--max-bytes` and `encode-chunks --kbps` work in both formats;
-`decode` and `info` pick the format from the version byte.  The default of every subcommand is version 1.
+`--format wide` the wide container (.alc version 3, section 11: the one whose video comes back at the top of the quality
+scale); `--max-bytes` and `encode-chunks --kbps` work in v1 and split, and are refused with `--format wide`;
+`decode` and `info` pick the format from the version byte unless `--format` names one.  The default of every subcommand
+is version 1.
 Like the reference it treats the whole input file as ONE chunk (src/bin/main.rs:117-122).  `encode-chunks`
 is the extension SURVEY.md section 8f asks for: it cuts a long raw-RGB file into 64-frame chunks
 (DEFAULT_CHUNK_SIZE, src/lib.rs:110) and writes one .alc per chunk."""
@@ -16,7 +18,8 @@ import sys
 import numpy as np
 
 from . import (DEFAULT_CHUNK_SIZE, CodecError, EncodedChunk, FrameDecoder, FrameEncoder, WaveletType, budget_bytes_per_chunk,
-               alc_version, decode_split, encode_many, encode_split, encode_split_to_size, encode_to_size, split_info)
+               alc_version, decode_split, decode_wide, encode_many, encode_split, encode_split_to_size, encode_to_size, encode_wide,
+               split_info, wide_info)
 
 WAVELETS = {"cdf53": WaveletType.Cdf53, "cdf97": WaveletType.Cdf97, "haar": WaveletType.Haar}
 WAVELET_NAMES = {WaveletType.Cdf53: "CDF 5/3", WaveletType.Cdf97: "CDF 9/7", WaveletType.Haar: "Haar"}
@@ -28,10 +31,29 @@ def parse_wavelet(s: str) -> WaveletType:
     return WAVELETS[s]
 
 
+FORMAT_VERSION = {"v1": 1, "split": 2, "wide": 3}
+NO_WIDE_BUDGET = "--format wide has no size prediction yet: it cannot be combined with {}; use --format split or v1 for a byte budget"
+
+
+def _container_version(a, data) -> int:
+    """The version a decode / info run treats the file as: the version byte, or the one --format names."""
+    return alc_version(data) if a.format == "auto" else FORMAT_VERSION[a.format]
+
+
 def cmd_encode(a) -> None:
     wt = parse_wavelet(a.wavelet)
+    if a.format == "wide" and a.max_bytes is not None:
+        raise ValueError(NO_WIDE_BUDGET.format("--max-bytes"))
     rgb = np.fromfile(a.input, dtype=np.uint8)
     quality = a.quality
+    if a.format == "wide":
+        data = encode_wide(FrameEncoder.with_wavelet(a.quality, wt), rgb, a.width, a.height, a.frames, a.lane_symbols)
+        with open(a.output, "wb") as f:
+            f.write(data)
+        ratio = 0.0 if rgb.size == 0 else len(data) / rgb.size
+        print(f"encoded {a.width}x{a.height}x{a.frames} ({rgb.size} bytes) -> {len(data)} bytes "
+              f"({ratio * 100:.1f}% ratio, quality={quality}, wavelet={a.wavelet}, format=wide)", file=sys.stderr)
+        return
     if a.format == "split":
         if a.max_bytes is not None:
             data, quality, fits = encode_split_to_size(rgb, a.width, a.height, a.frames, a.max_bytes, wt, a.min_quality, a.max_quality,
@@ -66,6 +88,8 @@ def cmd_encode(a) -> None:
 
 def cmd_encode_chunks(a) -> None:
     wt = parse_wavelet(a.wavelet)
+    if a.format == "wide" and a.kbps is not None:
+        raise ValueError(NO_WIDE_BUDGET.format("--kbps"))
     frame_bytes = a.width * a.height * 3
     rgb = np.memmap(a.input, dtype=np.uint8, mode="r")
     if frame_bytes == 0 or rgb.size % frame_bytes:
@@ -76,10 +100,11 @@ def cmd_encode_chunks(a) -> None:
         return
     enc = FrameEncoder.with_wavelet(a.quality, wt)
     starts = list(range(0, n_frames, a.chunk))
-    if a.format == "split":   # one chunk uses the whole device: chunk after chunk
+    if a.format in ("split", "wide"):   # one chunk uses the whole device: chunk after chunk
+        encode_one = encode_wide if a.format == "wide" else encode_split
         for k, s0 in enumerate(starts):
             f = min(a.chunk, n_frames - s0)
-            data = encode_split(enc, np.ascontiguousarray(rgb[s0 * frame_bytes:(s0 + f) * frame_bytes]), a.width, a.height, f,
+            data = encode_one(enc, np.ascontiguousarray(rgb[s0 * frame_bytes:(s0 + f) * frame_bytes]), a.width, a.height, f,
                                 a.lane_symbols)
             with open(f"{a.output}.{k:05d}.alc", "wb") as out:
                 out.write(data)
@@ -132,9 +157,10 @@ def _encode_chunks_to_rate(a, wt, rgb, frame_bytes, n_frames) -> None:
 
 def cmd_decode(a) -> None:
     data = np.fromfile(a.input, dtype=np.uint8)
-    if alc_version(data) == 2:
-        i = split_info(data)
-        rgb = decode_split(data)
+    version = _container_version(a, data)
+    if version in (2, 3):
+        i = wide_info(data) if version == 3 else split_info(data)
+        rgb = decode_wide(data) if version == 3 else decode_split(data)
         rgb.tofile(a.output)
         print(f"decoded {i.width}x{i.height}x{i.frames} -> {rgb.size} bytes (raw RGB)", file=sys.stderr)
         return
@@ -146,14 +172,15 @@ def cmd_decode(a) -> None:
 
 def cmd_info(a) -> None:
     data = np.fromfile(a.input, dtype=np.uint8)
-    if alc_version(data) == 2:
-        i = split_info(data)
+    version = _container_version(a, data)
+    if version in (2, 3):
+        i = wide_info(data) if version == 3 else split_info(data)
         raw = i.width * i.height * i.frames * 3
         payload = sum(i.payload_len)
         print("ALICE-Codec Bitstream Info")
         print(f"  File:        {a.input}")
         print(f"  File size:   {data.size} bytes")
-        print("  Format:      split-stream (version 2)")
+        print("  Format:      " + ("wide split-stream (version 3)" if version == 3 else "split-stream (version 2)"))
         print(f"  Width:       {i.width}")
         print(f"  Height:      {i.height}")
         print(f"  Frames:      {i.frames}")
@@ -207,8 +234,10 @@ def main(argv=None) -> int:
         else:
             e.add_argument("--kbps", type=int, default=None, help="target bitrate: a byte budget per chunk (with --fps)")
             e.add_argument("--fps", type=float, default=30.0)
-        e.add_argument("--format", choices=("v1", "split"), default="v1", help="v1: the reference's bitstream; split: .alc version 2")
-        e.add_argument("--lane-symbols", type=int, default=0, help="--format split: symbols per lane (power of two in 64..16384; 0 = default)")
+        e.add_argument("--format", choices=("v1", "split", "wide"), default="v1",
+                       help="v1: the reference's bitstream; split: .alc version 2; wide: .alc version 3 (untruncated symbols, for the top qualities)")
+        e.add_argument("--lane-symbols", type=int, default=0,
+                       help="--format split / wide: symbols per lane (power of two in 64..16384, wide: 64..8192; 0 = default)")
         e.add_argument("--min-quality", type=_u8, default=10)
         e.add_argument("--max-quality", type=_u8, default=95)
     d = sub.add_parser("decode")
@@ -216,6 +245,9 @@ def main(argv=None) -> int:
     d.add_argument("-o", "--output", required=True)
     i = sub.add_parser("info")
     i.add_argument("input")
+    for x in (d, i):
+        x.add_argument("--format", choices=("auto", "v1", "split", "wide"), default="auto",
+                       help="auto: from the file's version byte; otherwise the file must be of that format")
     a = p.parse_args(argv)
     try:
         {"encode": cmd_encode, "encode-chunks": cmd_encode_chunks, "decode": cmd_decode, "info": cmd_info}[a.command](a)

@@ -713,16 +713,18 @@ int chunk_dims(uint32_t w, uint32_t h, uint32_t f, ChunkDims* d, uint32_t count 
 
 inline uint64_t round_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
 
-// Rigorous magnitude bound through the inverse 3-D lifting.  Symbols are u8, so |q| <= 128 and every
-// dequantised sample is at most 128 * |step|; each lifting step adds at most (2 * other * |c| + 4096) / 8192 + 1.
+// Rigorous magnitude bound through the inverse 3-D lifting.  max_q bounds |q|: symbols of versions 1 and 2 are u8, so
+// |q| <= 128 (kByteMaxQ); a version 3 stream decodes to z <= 255 + 4095, so |q| <= 2175 (kWideMaxQ).  Every
+// dequantised sample is at most max_q * |step|; each lifting step adds at most (2 * other * |c| + 4096) / 8192 + 1.
 // The flags of launch_inverse_transform: exact unless 32-bit (24 x 24-bit) products are exact everywhere; mid16 (never with
 // exact): every value after the temporal pass fits i16, so it can be stored in 16 bits; lds16: also after the column pass.
 struct InverseBounds { bool exact; bool mid16; bool lds16; };
-InverseBounds inverse_bounds(int wavelet, const int32_t step[3]) {
+constexpr int kByteMaxQ = 128;
+InverseBounds inverse_bounds(int wavelet, const int32_t step[3], int max_q = kByteMaxQ) {
     const LiftSteps ls = lift_steps(wavelet);
     long double worst = 0;
     for (int c = 0; c < 3; ++c) {
-        long double a = 128.0L * fabsl((long double)step[c]);
+        long double a = (long double)max_q * fabsl((long double)step[c]);
         if (a > worst) worst = a;
     }
     const InverseBounds exact{true, false, false};
@@ -829,8 +831,19 @@ int generic_forward(const RgbLayout& rgb, const ChunkDims& d, int wavelet, Encod
 
 // The forward transform of one chunk: the tile kernels where they cover the shape (w.scratch holds their band slots), else
 // the generic path.
+// wide: d_sym holds 3 * d.padded untruncated u16 symbols (.alc v3) and the histogram bins min(z, 255).
 int forward_chunk(const RgbLayout& rgb, const ChunkDims& d, int wavelet, int32_t step, EncodeWork& w,
-                  uint8_t* d_sym, uint32_t* d_hist, hipStream_t st) {
+                  uint8_t* d_sym, uint32_t* d_hist, hipStream_t st, bool wide = false) {
+    if (wide) {
+        uint16_t* zs = (uint16_t*)d_sym;
+        if (w.scratch.p && launch_forward_transform_wide(rgb, d, wavelet, step, w.scratch.p, zs, d_hist, st)) return kOk;
+        return generic_forward(rgb, d, wavelet, w, st, [&](int c, int32_t* vol) {
+            int32_t* qb = vol + d.padded;
+            launch_quantize(vol, qb, d.padded, step, step, st);
+            launch_to_symbols_wide(qb, zs + (size_t)c * d.padded, d.padded, st);
+            launch_histogram_wide(zs + (size_t)c * d.padded, d.padded, d_hist + c * 256, st);
+        });
+    }
     if (w.scratch.p && launch_forward_transform(rgb, d, wavelet, step, w.scratch.p, d_sym, d_hist, st)) return kOk;
     return generic_forward(rgb, d, wavelet, w, st, [&](int c, int32_t* vol) {
         int32_t* qb = vol + d.padded;
@@ -1083,10 +1096,14 @@ int decode_work_alloc(DecodeWork& w, const ChunkDims& d, int n_chunks, uint8_t* 
 
 // The inverse transform of one chunk: the tile kernels where they cover the shape (d_scratch: their band slots, null when
 // they do not), else exact reference arithmetic.
+// wide: d_sym holds u16 symbols (.alc v3), and the instance choice starts from |q| <= kWideMaxQ.
 int inverse_chunk(const uint8_t* d_sym, const ChunkDims& d, int wavelet, const int32_t step[3], void* d_scratch, DecodeWork& w,
-                  const RgbLayout& rgb, hipStream_t st) {
-    const InverseBounds ib = inverse_bounds(wavelet, step);
-    if (d_scratch && launch_inverse_transform(d_sym, d, wavelet, step, ib.exact, ib.mid16, ib.lds16, d_scratch, rgb, st)) return kOk;
+                  const RgbLayout& rgb, hipStream_t st, bool wide = false) {
+    const InverseBounds ib = inverse_bounds(wavelet, step, wide ? kWideMaxQ : kByteMaxQ);
+    if (wide) {
+        if (d_scratch && launch_inverse_transform_wide((const uint16_t*)d_sym, d, wavelet, step, ib.exact, ib.mid16, ib.lds16, d_scratch, rgb, st))
+            return kOk;
+    } else if (d_scratch && launch_inverse_transform(d_sym, d, wavelet, step, ib.exact, ib.mid16, ib.lds16, d_scratch, rgb, st)) return kOk;
     if (!w.planes.p) TRY(w.planes.alloc(3 * d.n_pixels * sizeof(int16_t)));
     if (!w.tmp.p) TRY(w.tmp.alloc(d.padded * sizeof(int32_t)));
     if (!w.gen.p) TRY(w.gen.alloc(2 * d.padded * sizeof(int32_t)));
@@ -1095,7 +1112,8 @@ int inverse_chunk(const uint8_t* d_sym, const ChunkDims& d, int wavelet, const i
     int32_t* vol = qb + d.padded;
     const uint64_t W = d.pw, H = d.ph, D = d.pf;
     for (int c = 0; c < 3; ++c) {
-        launch_from_symbols(d_sym + (size_t)c * d.padded, qb, d.padded, st);
+        if (wide) launch_from_symbols_wide((const uint16_t*)d_sym + (size_t)c * d.padded, qb, d.padded, st);
+        else launch_from_symbols(d_sym + (size_t)c * d.padded, qb, d.padded, st);
         launch_dequantize(qb, vol, d.padded, step[c], st);
         launch_wavelet_axis(vol, w.tmp.as<int32_t>(), D, W * H, 1, 0, W * H, 1, wavelet, true, st);
         launch_wavelet_axis(vol, w.tmp.as<int32_t>(), H, W, D, W * H, W, 1, wavelet, true, st);
@@ -2633,8 +2651,8 @@ int alice_codec_dev_predict_sizes(const void* d_rgb, uint32_t width, uint32_t he
 // Every pointer named d_* is a device pointer; launches go on `hip_stream` and the call returns after the
 // stream has drained (the rANS calls need their result on the host anyway).
 
-int alice_codec_dev_forward_symbols(const void* d_rgb, uint32_t width, uint32_t height, uint32_t frames, uint8_t wavelet_type,
-                                    uint8_t quality, void* d_symbols, void* d_hist, void* hip_stream) {
+static int dev_forward_symbols(const void* d_rgb, uint32_t width, uint32_t height, uint32_t frames, uint8_t wavelet_type,
+                               uint8_t quality, void* d_symbols, void* d_hist, void* hip_stream, bool wide) {
     clear_error();
     if (!d_rgb || !d_symbols) return fail(kNullArgument, "null argument");
     if (wavelet_type > 2) return fail(kInvalidBitstream, "unknown wavelet type");
@@ -2649,10 +2667,20 @@ int alice_codec_dev_forward_symbols(const void* d_rgb, uint32_t width, uint32_t 
     TRY(w.hist.alloc(3 * 256 * sizeof(uint32_t)));
     uint32_t* hist = d_hist ? (uint32_t*)d_hist : w.hist.as<uint32_t>();
     HIP_TRY(hipMemsetAsync(hist, 0, 3 * 256 * sizeof(uint32_t), st));
-    TRY(forward_chunk(packed_rgb(d_rgb, d), d, wavelet_type, quality_to_step(quality), w, (uint8_t*)d_symbols, hist, st));
+    TRY(forward_chunk(packed_rgb(d_rgb, d), d, wavelet_type, quality_to_step(quality), w, (uint8_t*)d_symbols, hist, st, wide));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
     return kOk;
+}
+
+int alice_codec_dev_forward_symbols(const void* d_rgb, uint32_t width, uint32_t height, uint32_t frames, uint8_t wavelet_type,
+                                    uint8_t quality, void* d_symbols, void* d_hist, void* hip_stream) {
+    return dev_forward_symbols(d_rgb, width, height, frames, wavelet_type, quality, d_symbols, d_hist, hip_stream, false);
+}
+
+int alice_codec_dev_forward_symbols_wide(const void* d_rgb, uint32_t width, uint32_t height, uint32_t frames, uint8_t wavelet_type,
+                                         uint8_t quality, void* d_symbols, void* d_hist, void* hip_stream) {
+    return dev_forward_symbols(d_rgb, width, height, frames, wavelet_type, quality, d_symbols, d_hist, hip_stream, true);
 }
 
 int alice_codec_dev_inverse_symbols(const void* d_symbols, uint32_t width, uint32_t height, uint32_t frames, uint8_t wavelet_type,
@@ -3124,7 +3152,14 @@ int alice_codec_dev_extract_person_rgb(const void* d_mask, uint32_t width, uint3
 
 namespace {
 
-bool split_lane_ok(uint32_t L) { return L >= kSplitMinLane && L <= kSplitMaxLane && (L & (L - 1u)) == 0u; }
+// wide: the u16-symbol container (.alc v3) -- the same orchestration with two bytes per symbol, the
+// wide kernels and lane lengths up to 8192
+bool split_lane_ok(uint32_t L, bool wide = false) {
+    return L >= kSplitMinLane && L <= (wide ? kSplitWideMaxLane : kSplitMaxLane) && (L & (L - 1u)) == 0u;
+}
+const char* split_lane_msg(bool wide) {
+    return wide ? "lane_symbols must be a power of two in [64, 8192]" : "lane_symbols must be a power of two in [64, 16384]";
+}
 uint32_t split_blocks(uint64_t n, uint32_t L) { return (uint32_t)((n + 64ull * L - 1) / (64ull * L)); }   // n <= 2^32: at most 2^20
 
 inline void put_u64(uint8_t* p, uint64_t v) { put_u32(p, (uint32_t)v); put_u32(p + 4, (uint32_t)(v >> 32)); }
@@ -3133,6 +3168,7 @@ inline uint64_t get_u64(const uint8_t* p) { return (uint64_t)get_u32(p) | ((uint
 struct SplitHeader {
     uint32_t width = 0, height = 0, frames = 0, lane_symbols = 0;
     uint8_t wavelet = 0;
+    bool wide = false;   // version 3
     int32_t step[3] = {1, 1, 1}, dead_zone[3] = {1, 1, 1};
     uint32_t num_symbols[3] = {0, 0, 0}, n_blocks[3] = {0, 0, 0};
     uint64_t payload_len[3] = {0, 0, 0};
@@ -3141,18 +3177,21 @@ struct SplitHeader {
 
 // Header checks in their fixed order; data: at least min(total_len, kSplitHeaderBytes) readable bytes of a
 // container of total_len bytes.
-int parse_split_header(const uint8_t* data, uint64_t total_len, SplitHeader& h, ChunkDims* d) {
+int parse_split_header(const uint8_t* data, uint64_t total_len, SplitHeader& h, ChunkDims* d, int version = 2) {
     if (total_len < kSplitFixedHeaderBytes)
         return fail(kInvalidBitstream, "data too short for the fixed fields: " + std::to_string(total_len) + " bytes (they take " +
                                            std::to_string(kSplitFixedHeaderBytes) + ")");
     if (memcmp(data, "ALCC", 4) != 0) return fail(kInvalidBitstream, "bad magic (expected ALCC)");
-    if (data[4] != 2) return fail(kInvalidBitstream, "unsupported version: " + std::to_string((int)data[4]) + " (expected 2)");
+    if (data[4] != version)
+        return fail(kInvalidBitstream, "unsupported version: " + std::to_string((int)data[4]) + " (expected " + std::to_string(version) + ")");
+    h.wide = version == 3;
     if (data[5] > 2) return fail(kInvalidBitstream, "unknown wavelet type byte: " + std::to_string((int)data[5]));
     h.wavelet = data[5];
     h.width = get_u32(data + 6); h.height = get_u32(data + 10); h.frames = get_u32(data + 14);
     h.lane_symbols = get_u32(data + 18);
-    if (!split_lane_ok(h.lane_symbols))
-        return fail(kInvalidBitstream, "lane_symbols " + std::to_string(h.lane_symbols) + " is not a power of two in [64, 16384]");
+    if (!split_lane_ok(h.lane_symbols, h.wide))
+        return fail(kInvalidBitstream, "lane_symbols " + std::to_string(h.lane_symbols) + " is not a power of two in [64, " +
+                                           std::to_string(h.wide ? kSplitWideMaxLane : kSplitMaxLane) + "]");
     if (total_len < kSplitHeaderBytes)
         return fail(kInvalidBitstream, "data too short for the header: " + std::to_string(total_len) + " bytes (minimum " + std::to_string(kSplitHeaderBytes) + ")");
     *d = make_dims(h.width, h.height, h.frames);
@@ -3209,6 +3248,7 @@ int check_split_directories(const uint8_t* data, const SplitHeader& h) {
 struct SplitWork {
     int n_jobs = 0;
     uint32_t n_blocks = 0;
+    bool wide = false;                // u16 symbols, the wide kernels
     DevBuf jobs, tables, freq, cum, blk_len, blk_off, lane_len, totals, flags;
     std::vector<SplitJob> h;          // edited by the caller between the passes
     // what the asynchronous uploads read: every upload gets a vector of its own that is never touched again, and the
@@ -3221,8 +3261,9 @@ struct SplitWork {
     ~SplitWork() { if (armed) (void)hipStreamSynchronize(st); }
 };
 
-int split_work_alloc(SplitWork& w, int n_jobs, uint64_t n, uint32_t L, bool encode) {
+int split_work_alloc(SplitWork& w, int n_jobs, uint64_t n, uint32_t L, bool encode, bool wide = false) {
     w.n_jobs = n_jobs;
+    w.wide = wide;
     w.n_blocks = split_blocks(n, L);
     const size_t nb = w.n_blocks;
     TRY(w.jobs.alloc((size_t)n_jobs * sizeof(SplitJob)));
@@ -3261,7 +3302,12 @@ int split_count(SplitWork& w, const uint32_t* d_hist, hipStream_t st, std::vecto
     for (int j = 0; j < w.n_jobs; ++j)
         launch_rans_table_from_arrays(w.cum.as<uint16_t>() + (size_t)j * 256, w.freq.as<uint16_t>() + (size_t)j * 256, w.tables.as<RansTable>() + j, st);
     TRY(split_upload_jobs(w, st));
-    launch_split_count(w.jobs.as<SplitJob>(), w.n_jobs, w.n_blocks, st);
+    if (w.wide) {
+        HIP_TRY(hipMemsetAsync(w.flags.p, 0, (size_t)w.n_jobs * sizeof(uint32_t), st));
+        launch_split_wide_count(w.jobs.as<SplitJob>(), w.n_jobs, w.n_blocks, st);
+    } else {
+        launch_split_count(w.jobs.as<SplitJob>(), w.n_jobs, w.n_blocks, st);
+    }
     launch_split_scan(w.jobs.as<SplitJob>(), w.n_jobs, false, w.totals.as<unsigned long long>(), st);
     HIP_TRY(hipGetLastError());
     totals.resize((size_t)w.n_jobs);
@@ -3271,14 +3317,24 @@ int split_count(SplitWork& w, const uint32_t* d_hist, hipStream_t st, std::vecto
         freq_out->resize((size_t)w.n_jobs * 256);
         HIP_TRY(hipMemcpyAsync(freq_out->data(), w.freq.p, freq_out->size() * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
     }
+    std::vector<uint32_t> flags;
+    if (w.wide) {
+        flags.resize((size_t)w.n_jobs);
+        HIP_TRY(hipMemcpyAsync(flags.data(), w.flags.p, flags.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    }
     HIP_TRY(hipStreamSynchronize(st));
+    // the residual guard of the wide format: nothing has been written yet, and nothing will be
+    for (size_t j = 0; j < flags.size(); ++j)
+        if (flags[j] & kSplitWideResidual)
+            return fail(kInternal, "stream " + std::to_string(j) + ": a symbol above 255 + 4095 has no version 3 code");
     return kOk;
 }
 
 // the write pass, after the caller has pointed every h[j].stream at totals[j] writable bytes
 int split_write(SplitWork& w, hipStream_t st) {
     TRY(split_upload_jobs(w, st));
-    launch_split_write(w.jobs.as<SplitJob>(), w.n_jobs, w.n_blocks, st);
+    if (w.wide) launch_split_wide_write(w.jobs.as<SplitJob>(), w.n_jobs, w.n_blocks, st);
+    else launch_split_write(w.jobs.as<SplitJob>(), w.n_jobs, w.n_blocks, st);
     HIP_TRY(hipGetLastError());
     return kOk;
 }
@@ -3302,7 +3358,8 @@ int split_decode_launch(SplitWork& w, const uint16_t* freq, hipStream_t st) {
     for (int j = 0; j < w.n_jobs; ++j)
         launch_rans_table_from_arrays(w.cum.as<uint16_t>() + (size_t)j * 256, w.freq.as<uint16_t>() + (size_t)j * 256, w.tables.as<RansTable>() + j, st);
     launch_split_scan(w.jobs.as<SplitJob>(), w.n_jobs, true, nullptr, st);
-    launch_split_decode(w.jobs.as<SplitJob>(), w.n_jobs, w.n_blocks, st);
+    if (w.wide) launch_split_wide_decode(w.jobs.as<SplitJob>(), w.n_jobs, w.n_blocks, st);
+    else launch_split_decode(w.jobs.as<SplitJob>(), w.n_jobs, w.n_blocks, st);
     HIP_TRY(hipGetLastError());
     return kOk;
 }
@@ -3331,25 +3388,27 @@ struct SplitChunkEncode {
     std::vector<uint8_t> q;
     uint32_t B = 0, L = 0;
     uint8_t wavelet = 0;
+    bool wide = false;
 };
 
 int split_count_chunks(SplitChunkEncode& e, const RgbLayout* rgb, uint32_t B, const ChunkDims& d, uint8_t wavelet, const uint8_t* q,
-                       uint32_t L, hipStream_t st, std::vector<uint64_t>& sizes) {
+                       uint32_t L, hipStream_t st, std::vector<uint64_t>& sizes, bool wide = false) {
     EncodeWork& ew = e.ew;
-    e.B = B; e.L = L; e.wavelet = wavelet;
+    e.B = B; e.L = L; e.wavelet = wavelet; e.wide = wide;
+    const size_t sb = wide ? 2 : 1;   // bytes per symbol
     e.q.assign(q, q + B);
     ew.d = d; ew.n_chunks = (int)B;
     if (transform_tiles_eligible(d)) TRY(ew.scratch.alloc(forward_scratch_bytes(d)));
-    TRY(ew.sym.alloc((size_t)B * 3 * d.padded));
+    TRY(ew.sym.alloc((size_t)B * 3 * d.padded * sb));
     TRY(ew.hist.alloc((size_t)B * 3 * 256 * sizeof(uint32_t)));
     HIP_TRY(hipMemsetAsync(ew.hist.p, 0, (size_t)B * 3 * 256 * sizeof(uint32_t), st));
     for (uint32_t i = 0; i < B; ++i)
-        TRY(forward_chunk(rgb[i], d, wavelet, quality_to_step(q[i]), ew, ew.sym.as<uint8_t>() + (size_t)i * 3 * d.padded,
-                          ew.hist.as<uint32_t>() + (size_t)i * 3 * 256, st));
+        TRY(forward_chunk(rgb[i], d, wavelet, quality_to_step(q[i]), ew, ew.sym.as<uint8_t>() + (size_t)i * 3 * d.padded * sb,
+                          ew.hist.as<uint32_t>() + (size_t)i * 3 * 256, st, wide));
     e.hd.assign(B, SplitHeaderDesc{});
     SplitWork& w = e.w;
-    TRY(split_work_alloc(w, (int)(3 * B), d.padded, L, true));
-    for (size_t j = 0; j < 3 * (size_t)B; ++j) w.h[j].sym = ew.sym.as<uint8_t>() + j * d.padded;
+    TRY(split_work_alloc(w, (int)(3 * B), d.padded, L, true, wide));
+    for (size_t j = 0; j < 3 * (size_t)B; ++j) w.h[j].sym = ew.sym.as<uint8_t>() + j * d.padded * sb;
     TRY(split_count(w, ew.hist.as<uint32_t>(), st, e.totals, nullptr));
     sizes.resize(B);
     for (uint32_t i = 0; i < B; ++i) sizes[i] = kSplitHeaderBytes + e.totals[3 * i] + e.totals[3 * i + 1] + e.totals[3 * i + 2];
@@ -3378,6 +3437,7 @@ int split_write_chunks(SplitChunkEncode& e, const std::vector<uint8_t*>& outs, h
     HIP_TRY(hipMemcpyAsync(e.d_hd.p, e.hd.data(), e.hd.size() * sizeof(SplitHeaderDesc), hipMemcpyHostToDevice, st));
     TRY(split_write(w, st));
     launch_split_headers(e.d_hd.as<SplitHeaderDesc>(), (int)B, st);
+    if (e.wide) launch_split_header_version(e.d_hd.as<SplitHeaderDesc>(), (int)B, 3, st);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
     return kOk;
@@ -3386,9 +3446,9 @@ int split_write_chunks(SplitChunkEncode& e, const std::vector<uint8_t*>& outs, h
 // Both halves: place(sizes, outs) is called once the sizes are known and names where each chunk's bytes go (device).
 template <typename Place>
 int split_encode_chunks(const RgbLayout* rgb, uint32_t B, const ChunkDims& d, uint8_t wavelet, const uint8_t* q, uint32_t L,
-                        hipStream_t st, std::vector<uint64_t>& sizes, Place place) {
+                        hipStream_t st, std::vector<uint64_t>& sizes, Place place, bool wide = false) {
     SplitChunkEncode e;
-    TRY(split_count_chunks(e, rgb, B, d, wavelet, q, L, st, sizes));
+    TRY(split_count_chunks(e, rgb, B, d, wavelet, q, L, st, sizes, wide));
     std::vector<uint8_t*> outs(B, nullptr);
     TRY(place(sizes, outs));
     return split_write_chunks(e, outs, st);
@@ -3400,27 +3460,29 @@ int split_decode_chunks(const SplitHeader* hdr, const uint8_t* const* d_alc, uin
                         hipStream_t st) {
     DecodeWork dw;
     dw.d = d; dw.n_chunks = (int)B;
-    TRY(dw.sym.alloc((size_t)B * 3 * d.padded));
+    const bool wide = hdr[0].wide;    // (one parser, one version per call)
+    const size_t sb = wide ? 2 : 1;   // bytes per symbol
+    TRY(dw.sym.alloc((size_t)B * 3 * d.padded * sb));
     SplitWork w;
-    TRY(split_work_alloc(w, (int)(3 * B), d.padded, hdr[0].lane_symbols, false));
+    TRY(split_work_alloc(w, (int)(3 * B), d.padded, hdr[0].lane_symbols, false, wide));
     std::vector<uint16_t> freq((size_t)B * 3 * 256);
     bool all16 = true;
     for (uint32_t i = 0; i < B; ++i) {
         uint64_t off = kSplitHeaderBytes;
         for (int c = 0; c < 3; ++c) {
             SplitJob& s = w.h[3 * (size_t)i + c];
-            s.sym = dw.sym.as<uint8_t>() + (3 * (size_t)i + c) * d.padded;
+            s.sym = dw.sym.as<uint8_t>() + (3 * (size_t)i + c) * d.padded * sb;
             s.stream = (uint8_t*)d_alc[i] + off;
             s.len = hdr[i].payload_len[c];
             off += s.len;
             memcpy(&freq[(3 * (size_t)i + c) * 256], hdr[i].freq[c], 256 * sizeof(uint16_t));
         }
-        all16 = all16 && inverse_bounds(hdr[i].wavelet, hdr[i].step).mid16;
+        all16 = all16 && inverse_bounds(hdr[i].wavelet, hdr[i].step, wide ? kWideMaxQ : kByteMaxQ).mid16;
     }
     if (transform_tiles_eligible(d)) TRY(dw.scratch_own.alloc(inverse_scratch_bytes(d, all16)));
     TRY(split_decode_launch(w, freq.data(), st));
     for (uint32_t i = 0; i < B; ++i)
-        TRY(inverse_chunk(dw.sym.as<uint8_t>() + (size_t)i * 3 * d.padded, d, hdr[i].wavelet, hdr[i].step, dw.scratch_own.p, dw, rgb[i], st));
+        TRY(inverse_chunk(dw.sym.as<uint8_t>() + (size_t)i * 3 * d.padded * sb, d, hdr[i].wavelet, hdr[i].step, dw.scratch_own.p, dw, rgb[i], st, wide));
     HIP_TRY(hipGetLastError());
     return split_decode_verdict(w, st);
 }
@@ -3428,16 +3490,16 @@ int split_decode_chunks(const SplitHeader* hdr, const uint8_t* const* d_alc, uin
 // Chunks a device-resident call works on at a time: as many as keep its symbol buffer at or below 4 GiB (ten 1080p x 64
 // chunks).  Every chunk already fills the device on its own, so larger groups gain nothing, and a 32-chunk group (12.7 GB
 // of symbols) was measured to DEcode eleven times slower per chunk than groups of eight.
-uint32_t split_group(const ChunkDims& d) {
-    const uint64_t per_chunk = 3 * d.padded;
+uint32_t split_group(const ChunkDims& d, bool wide = false) {
+    const uint64_t per_chunk = 3 * d.padded * (wide ? 2 : 1);
     const uint64_t g = (uint64_t(4) << 30) / (per_chunk ? per_chunk : 1);
     return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(g, 1), 21845);
 }
 
-void write_empty_split(uint8_t* p, uint8_t wavelet, uint32_t w, uint32_t h, uint32_t f, uint32_t L, int32_t step) {
+void write_empty_split(uint8_t* p, uint8_t wavelet, uint32_t w, uint32_t h, uint32_t f, uint32_t L, int32_t step, uint8_t version = 2) {
     memset(p, 0, kSplitHeaderBytes);
     memcpy(p, "ALCC", 4);
-    p[4] = 2; p[5] = wavelet;
+    p[4] = version; p[5] = wavelet;
     put_u32(p + 6, w); put_u32(p + 10, h); put_u32(p + 14, f); put_u32(p + 18, L);
     for (int c = 0; c < 3; ++c) {
         uint8_t* q = p + kSplitFixedHeaderBytes + (size_t)c * kSplitChannelHeaderBytes;
@@ -3522,8 +3584,8 @@ int split_choose_chunks(const RgbLayout* rgb, uint32_t n, const ChunkDims& d, ui
 
 // n equal-shaped chunks at their layouts -> version 2 bytes at d_out + i * out_stride, in groups of split_group.
 int split_encode_layouts(const RgbLayout* rgb, uint32_t n, const ChunkDims& d, uint8_t wavelet, const uint8_t* q, uint32_t L, void* d_out,
-                         uint64_t out_stride, uint64_t* sizes, hipStream_t st) {
-    const uint32_t group = split_group(d);
+                         uint64_t out_stride, uint64_t* sizes, hipStream_t st, bool wide = false) {
+    const uint32_t group = split_group(d, wide);
     for (uint32_t first = 0; first < n; first += group) {
         const uint32_t B = std::min(group, n - first);
         std::vector<uint64_t> sz;
@@ -3536,7 +3598,7 @@ int split_encode_layouts(const RgbLayout* rgb, uint32_t n, const ChunkDims& d, u
                                         outs[i] = (uint8_t*)d_out + (size_t)(first + i) * out_stride;
                                     }
                                     return kOk;
-                                }));
+                                }, wide));
         for (uint32_t i = 0; i < B; ++i) sizes[first + i] = sz[i];
     }
     return kOk;
@@ -3577,7 +3639,8 @@ int check_split_args(uint8_t wavelet_type, uint32_t lane_symbols, uint32_t* L) {
 // Decode of n device containers into the layouts that layouts_of(dims of the headers, out) names; the headers come to the
 // host first, and nothing is queued before they and the layouts have been accepted.
 template <typename LayoutsOf>
-int split_decode_device(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks, hipStream_t st, LayoutsOf layouts_of) {
+int split_decode_device(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks, hipStream_t st, LayoutsOf layouts_of,
+                        int version = 2) {
     std::vector<uint8_t> raw((size_t)n_chunks * kSplitHeaderBytes, 0);
     for (uint32_t i = 0; i < n_chunks; ++i)
         HIP_TRY(hipMemcpyAsync(raw.data() + (size_t)i * kSplitHeaderBytes, (const uint8_t*)d_alc + (size_t)i * alc_stride,
@@ -3588,7 +3651,7 @@ int split_decode_device(const void* d_alc, uint64_t alc_stride, const uint64_t* 
     ChunkDims d{};
     for (uint32_t i = 0; i < n_chunks; ++i) {
         ChunkDims di{};
-        TRY(parse_split_header(raw.data() + (size_t)i * kSplitHeaderBytes, sizes[i], hdr[i], &di));
+        TRY(parse_split_header(raw.data() + (size_t)i * kSplitHeaderBytes, sizes[i], hdr[i], &di, version));
         if (di.n_pixels == 0) return fail(kInvalidDimensions, "invalid dimensions");
         if (i == 0) d = di;
         else if (di.w != d.w || di.h != d.h || di.f != d.f || hdr[i].lane_symbols != hdr[0].lane_symbols)
@@ -3597,7 +3660,7 @@ int split_decode_device(const void* d_alc, uint64_t alc_stride, const uint64_t* 
     }
     std::vector<RgbLayout> layouts;
     TRY(layouts_of(d, layouts));
-    const uint32_t group = split_group(d);
+    const uint32_t group = split_group(d, version == 3);
     for (uint32_t first = 0; first < n_chunks; first += group)
         TRY(split_decode_chunks(hdr.data() + first, ptr.data() + first, std::min(group, n_chunks - first), d, layouts.data() + first, st));
     return kOk;
@@ -3627,12 +3690,12 @@ int alice_codec_split_normalize(const uint32_t hist[256], uint16_t freq[256]) {
     return kOk;
 }
 
-int alice_codec_dev_split_encode(const void* d_symbols, uint64_t n, const uint32_t hist[256], uint32_t lane_symbols, void* d_out,
-                                 uint64_t cap, uint64_t* out_len, void* hip_stream) {
+static int stage_split_encode(const void* d_symbols, uint64_t n, const uint32_t hist[256], uint32_t lane_symbols, void* d_out,
+                              uint64_t cap, uint64_t* out_len, void* hip_stream, bool wide) {
     clear_error();
     if ((!d_symbols && n) || !hist || !out_len || (!d_out && cap)) return fail(kNullArgument, "null argument");
     if (!lane_symbols) lane_symbols = kSplitDefaultLane;
-    if (!split_lane_ok(lane_symbols)) return fail(kInvalidDimensions, "lane_symbols must be a power of two in [64, 16384]");
+    if (!split_lane_ok(lane_symbols, wide)) return fail(kInvalidDimensions, split_lane_msg(wide));
     if (n > 0xFFFFFFFFull) return fail(kDimensionOverflow, "more symbols than the header's u32 num_symbols counts");
     uint64_t total = 0;
     for (int i = 0; i < 256; ++i) total += hist[i];
@@ -3646,13 +3709,14 @@ int alice_codec_dev_split_encode(const void* d_symbols, uint64_t n, const uint32
     TRY(dh.alloc(256 * 4));
     HIP_TRY(hipMemcpyAsync(dh.p, hist, 256 * 4, hipMemcpyHostToDevice, st));
     SplitWork w;
-    TRY(split_work_alloc(w, 1, n, lane_symbols, true));
+    TRY(split_work_alloc(w, 1, n, lane_symbols, true, wide));
     w.h[0].sym = (const uint8_t*)d_symbols;
     std::vector<uint64_t> totals;
     TRY(split_count(w, dh.as<uint32_t>(), st, totals, nullptr));
     if (totals[0] > cap)
         return fail(kInvalidBufferSize, "the stream needs " + std::to_string(totals[0]) + " bytes, capacity is " + std::to_string(cap) +
-                                            " (alice_codec_split_stream_bound gives the worst case)");
+                                            (wide ? " (alice_codec_wide_stream_bound gives the worst case)"
+                                                  : " (alice_codec_split_stream_bound gives the worst case)"));
     w.h[0].stream = (uint8_t*)d_out;
     TRY(split_write(w, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -3660,12 +3724,17 @@ int alice_codec_dev_split_encode(const void* d_symbols, uint64_t n, const uint32
     return kOk;
 }
 
-int alice_codec_dev_split_decode(const void* d_stream, uint64_t len, const uint16_t freq[256], uint32_t lane_symbols, void* d_symbols,
-                                 uint64_t n, void* hip_stream) {
+int alice_codec_dev_split_encode(const void* d_symbols, uint64_t n, const uint32_t hist[256], uint32_t lane_symbols, void* d_out,
+                                 uint64_t cap, uint64_t* out_len, void* hip_stream) {
+    return stage_split_encode(d_symbols, n, hist, lane_symbols, d_out, cap, out_len, hip_stream, false);
+}
+
+static int stage_split_decode(const void* d_stream, uint64_t len, const uint16_t freq[256], uint32_t lane_symbols, void* d_symbols,
+                              uint64_t n, void* hip_stream, bool wide) {
     clear_error();
     if ((!d_stream && len) || !freq || (!d_symbols && n)) return fail(kNullArgument, "null argument");
     if (!lane_symbols) lane_symbols = kSplitDefaultLane;
-    if (!split_lane_ok(lane_symbols)) return fail(kInvalidDimensions, "lane_symbols must be a power of two in [64, 16384]");
+    if (!split_lane_ok(lane_symbols, wide)) return fail(kInvalidDimensions, split_lane_msg(wide));
     if (n > 0xFFFFFFFFull) return fail(kDimensionOverflow, "more symbols than the header's u32 num_symbols counts");
     uint32_t sum = 0;
     for (int i = 0; i < 256; ++i) sum += freq[i];
@@ -3676,7 +3745,7 @@ int alice_codec_dev_split_decode(const void* d_stream, uint64_t len, const uint1
     hipStream_t st = (hipStream_t)hip_stream;
     ScopeStream scope(st);
     SplitWork w;
-    TRY(split_work_alloc(w, 1, n, lane_symbols, false));
+    TRY(split_work_alloc(w, 1, n, lane_symbols, false, wide));
     w.h[0].sym = (const uint8_t*)d_symbols;
     w.h[0].stream = (uint8_t*)d_stream;
     w.h[0].len = len;
@@ -3684,12 +3753,17 @@ int alice_codec_dev_split_decode(const void* d_stream, uint64_t len, const uint1
     return split_decode_verdict(w, st);
 }
 
-int alice_codec_split_info(const uint8_t* data, uint64_t len, AliceSplitInfo* info) {
+int alice_codec_dev_split_decode(const void* d_stream, uint64_t len, const uint16_t freq[256], uint32_t lane_symbols, void* d_symbols,
+                                 uint64_t n, void* hip_stream) {
+    return stage_split_decode(d_stream, len, freq, lane_symbols, d_symbols, n, hip_stream, false);
+}
+
+static int container_info(const uint8_t* data, uint64_t len, AliceSplitInfo* info, int version) {
     clear_error();
     if (!data || !info) return fail(kNullArgument, "null argument");
     SplitHeader h;
     ChunkDims d{};
-    TRY(parse_split_header(data, len, h, &d));
+    TRY(parse_split_header(data, len, h, &d, version));
     TRY(check_split_directories(data, h));
     memset(info, 0, sizeof(*info));
     info->width = h.width; info->height = h.height; info->frames = h.frames;
@@ -3702,8 +3776,10 @@ int alice_codec_split_info(const uint8_t* data, uint64_t len, AliceSplitInfo* in
     return kOk;
 }
 
-uint8_t* alice_codec_encode_split(const FrameEncoder* encoder, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
-                                  uint32_t frames, uint32_t lane_symbols, uint64_t* out_len) {
+int alice_codec_split_info(const uint8_t* data, uint64_t len, AliceSplitInfo* info) { return container_info(data, len, info, 2); }
+
+static uint8_t* container_encode(const FrameEncoder* encoder, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
+                                 uint32_t frames, uint32_t lane_symbols, uint64_t* out_len, bool wide) {
     clear_error();
     if (!encoder || !rgb || !out_len) { fail(kNullArgument, "null argument"); return nullptr; }
     auto run = [&](uint8_t** out) -> int {
@@ -3714,11 +3790,11 @@ uint8_t* alice_codec_encode_split(const FrameEncoder* encoder, const uint8_t* rg
         EncodedChunk* none = nullptr;
         if (n_pixels) TRY(validate_encode_many(encoder, rgb, rgb_len, width, height, frames, 1, &none, &d));
         const uint32_t L = lane_symbols ? lane_symbols : kSplitDefaultLane;
-        if (!split_lane_ok(L)) return fail(kInvalidDimensions, "lane_symbols must be a power of two in [64, 16384]");
+        if (!split_lane_ok(L, wide)) return fail(kInvalidDimensions, split_lane_msg(wide));
         if (n_pixels == 0) {
             *out = host_result_alloc(kSplitHeaderBytes);
             if (!*out) return fail(kOutOfMemory, "out of host memory");
-            write_empty_split(*out, encoder->wavelet, width, height, frames, L, quality_to_step(encoder->quality));
+            write_empty_split(*out, encoder->wavelet, width, height, frames, L, quality_to_step(encoder->quality), wide ? 3 : 2);
             *out_len = kSplitHeaderBytes;
             return kOk;
         }
@@ -3734,7 +3810,7 @@ uint8_t* alice_codec_encode_split(const FrameEncoder* encoder, const uint8_t* rg
                                     TRY(d_out.alloc(sz[0]));
                                     outs[0] = d_out.as<uint8_t>();
                                     return kOk;
-                                }));
+                                }, wide));
         *out = host_result_alloc(sizes[0]);
         if (!*out) return fail(kOutOfMemory, "out of host memory");
         const int rc = copy_to_host(*out, d_out.p, sizes[0], st);
@@ -3746,13 +3822,18 @@ uint8_t* alice_codec_encode_split(const FrameEncoder* encoder, const uint8_t* rg
     return run(&out) == kOk ? out : nullptr;
 }
 
-uint8_t* alice_codec_decode_split(const uint8_t* data, uint64_t len, uint64_t* out_len) {
+uint8_t* alice_codec_encode_split(const FrameEncoder* encoder, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
+                                  uint32_t frames, uint32_t lane_symbols, uint64_t* out_len) {
+    return container_encode(encoder, rgb, rgb_len, width, height, frames, lane_symbols, out_len, false);
+}
+
+static uint8_t* container_decode(const uint8_t* data, uint64_t len, uint64_t* out_len, int version) {
     clear_error();
     if (!data || !out_len) { fail(kNullArgument, "null argument"); return nullptr; }
     auto run = [&](uint8_t** out) -> int {
         SplitHeader h;
         ChunkDims d{};
-        TRY(parse_split_header(data, len, h, &d));
+        TRY(parse_split_header(data, len, h, &d, version));
         TRY(check_split_directories(data, h));
         const uint64_t bytes = (uint64_t)h.width * h.height * h.frames * 3;
         *out = host_result_alloc(bytes);
@@ -3779,16 +3860,18 @@ uint8_t* alice_codec_decode_split(const uint8_t* data, uint64_t len, uint64_t* o
     return run(&out) == kOk ? out : nullptr;
 }
 
-int alice_codec_dev_encode_split(const void* d_rgb, uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks,
-                                 uint8_t wavelet_type, uint8_t quality, const uint8_t* qualities, uint32_t lane_symbols, void* d_out,
-                                 uint64_t out_stride, uint64_t* sizes, void* hip_stream) {
+uint8_t* alice_codec_decode_split(const uint8_t* data, uint64_t len, uint64_t* out_len) { return container_decode(data, len, out_len, 2); }
+
+static int container_dev_encode(const void* d_rgb, uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks,
+                                uint8_t wavelet_type, uint8_t quality, const uint8_t* qualities, uint32_t lane_symbols, void* d_out,
+                                uint64_t out_stride, uint64_t* sizes, void* hip_stream, bool wide) {
     clear_error();
     if (!d_rgb || !d_out || !sizes) return fail(kNullArgument, "null argument");
     if (wavelet_type > 2) return fail(kInvalidBitstream, "unknown wavelet type");
     ChunkDims d{};
     TRY(chunk_dims(width, height, frames, &d, n_chunks));
     const uint32_t L = lane_symbols ? lane_symbols : kSplitDefaultLane;
-    if (!split_lane_ok(L)) return fail(kInvalidDimensions, "lane_symbols must be a power of two in [64, 16384]");
+    if (!split_lane_ok(L, wide)) return fail(kInvalidDimensions, split_lane_msg(wide));
     TRY(ensure_device());
     hipStream_t st = (hipStream_t)hip_stream;
     ScopeStream scope(st);
@@ -3798,11 +3881,18 @@ int alice_codec_dev_encode_split(const void* d_rgb, uint32_t width, uint32_t hei
         layouts[i] = packed_rgb((const uint8_t*)d_rgb + (size_t)i * d.n_pixels * 3, d);
         q[i] = qualities ? qualities[i] : quality;
     }
-    return split_encode_layouts(layouts.data(), n_chunks, d, wavelet_type, q.data(), L, d_out, out_stride, sizes, st);
+    return split_encode_layouts(layouts.data(), n_chunks, d, wavelet_type, q.data(), L, d_out, out_stride, sizes, st, wide);
 }
 
-int alice_codec_dev_decode_split(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks, void* d_rgb_out,
-                                 void* hip_stream) {
+int alice_codec_dev_encode_split(const void* d_rgb, uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks,
+                                 uint8_t wavelet_type, uint8_t quality, const uint8_t* qualities, uint32_t lane_symbols, void* d_out,
+                                 uint64_t out_stride, uint64_t* sizes, void* hip_stream) {
+    return container_dev_encode(d_rgb, width, height, frames, n_chunks, wavelet_type, quality, qualities, lane_symbols, d_out, out_stride,
+                                sizes, hip_stream, false);
+}
+
+static int container_dev_decode(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks, void* d_rgb_out,
+                                void* hip_stream, int version) {
     clear_error();
     if (!d_alc || !sizes || !d_rgb_out) return fail(kNullArgument, "null argument");
     if (n_chunks == 0) return fail(kInvalidDimensions, "empty batch");
@@ -3813,7 +3903,50 @@ int alice_codec_dev_decode_split(const void* d_alc, uint64_t alc_stride, const u
     ScopeStream scope(st);
     return split_decode_device(d_alc, alc_stride, sizes, n_chunks, st, [&](const ChunkDims& d, std::vector<RgbLayout>& out) {
         return split_layouts(d_rgb_out, 0, 0, nullptr, d, n_chunks, out);
-    });
+    }, version);
+}
+
+int alice_codec_dev_decode_split(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks, void* d_rgb_out,
+                                 void* hip_stream) {
+    return container_dev_decode(d_alc, alc_stride, sizes, n_chunks, d_rgb_out, hip_stream, 2);
+}
+
+// ---- version 3: the wide container.  The same paths with the wide flag set. ----
+
+uint64_t alice_codec_wide_stream_bound(uint64_t n, uint32_t lane_symbols) {
+    if (!split_lane_ok(lane_symbols, true) || n > 0xFFFFFFFFull) return 0;
+    return (uint64_t)split_blocks(n, lane_symbols) * (4 + 128 + 64 * 4) + 4 * n;
+}
+
+int alice_codec_dev_wide_encode(const void* d_symbols, uint64_t n, const uint32_t hist[256], uint32_t lane_symbols, void* d_out,
+                                uint64_t cap, uint64_t* out_len, void* hip_stream) {
+    return stage_split_encode(d_symbols, n, hist, lane_symbols, d_out, cap, out_len, hip_stream, true);
+}
+
+int alice_codec_dev_wide_decode(const void* d_stream, uint64_t len, const uint16_t freq[256], uint32_t lane_symbols, void* d_symbols,
+                                uint64_t n, void* hip_stream) {
+    return stage_split_decode(d_stream, len, freq, lane_symbols, d_symbols, n, hip_stream, true);
+}
+
+int alice_codec_wide_info(const uint8_t* data, uint64_t len, AliceSplitInfo* info) { return container_info(data, len, info, 3); }
+
+uint8_t* alice_codec_encode_wide(const FrameEncoder* encoder, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
+                                 uint32_t frames, uint32_t lane_symbols, uint64_t* out_len) {
+    return container_encode(encoder, rgb, rgb_len, width, height, frames, lane_symbols, out_len, true);
+}
+
+uint8_t* alice_codec_decode_wide(const uint8_t* data, uint64_t len, uint64_t* out_len) { return container_decode(data, len, out_len, 3); }
+
+int alice_codec_dev_encode_wide(const void* d_rgb, uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks,
+                                uint8_t wavelet_type, uint8_t quality, const uint8_t* qualities, uint32_t lane_symbols, void* d_out,
+                                uint64_t out_stride, uint64_t* sizes, void* hip_stream) {
+    return container_dev_encode(d_rgb, width, height, frames, n_chunks, wavelet_type, quality, qualities, lane_symbols, d_out, out_stride,
+                                sizes, hip_stream, true);
+}
+
+int alice_codec_dev_decode_wide(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks, void* d_rgb_out,
+                                void* hip_stream) {
+    return container_dev_decode(d_alc, alc_stride, sizes, n_chunks, d_rgb_out, hip_stream, 3);
 }
 
 // ---- version 2: size prediction, budget encodes, regions of device frames ----

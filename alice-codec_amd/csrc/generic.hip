@@ -313,6 +313,52 @@ __global__ __launch_bounds__(256) void from_symbols_kernel(const uint8_t* __rest
     }
 }
 
+// Wide twins for .alc v3: the symbol is not truncated.  z saturates at 65535 so that a coefficient
+// no 8-bit chunk produces still fails the lane coder's residual guard instead of wrapping.
+__global__ __launch_bounds__(256) void to_symbols_wide_kernel(const int32_t* __restrict__ in, uint16_t* __restrict__ out,
+                                                              unsigned long long n) {
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n;
+         i += (unsigned long long)gridDim.x * 256) {
+        const int c = in[i];
+        unsigned s = 0u;
+        if (c > 0) s = (unsigned)c * 2u - 1u;
+        else if (c < 0) s = (0u - (unsigned)c) * 2u;
+        if (c > 32768 || c < -32767) s = 65535u;
+        out[i] = (uint16_t)(s < 65535u ? s : 65535u);
+    }
+}
+
+__global__ __launch_bounds__(256) void from_symbols_wide_kernel(const uint16_t* __restrict__ in, int32_t* __restrict__ out,
+                                                                unsigned long long n) {
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n;
+         i += (unsigned long long)gridDim.x * 256) {
+        const int s = in[i];
+        out[i] = (s == 0) ? 0 : ((s & 1) ? (s + 1) / 2 : -(s / 2));
+    }
+}
+
+// bins min(z, 255); 8 LDS replicas of the bins, zero counted in a register
+__global__ __launch_bounds__(256) void histogram_wide_kernel(const uint16_t* __restrict__ sym, unsigned long long n,
+                                                             uint32_t* __restrict__ hist) {
+    __shared__ uint32_t lh[8 * 256];
+    const int tid = threadIdx.x;
+    for (int i = tid; i < 8 * 256; i += 256) lh[i] = 0u;
+    __syncthreads();
+    uint32_t* my = lh + (tid & 7) * 256;
+    uint32_t zeros = 0u;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + tid; i < n; i += (unsigned long long)gridDim.x * 256) {
+        const uint32_t z = sym[i];
+        if (z == 0u) ++zeros;
+        else atomicAdd(&my[z < 255u ? z : 255u], 1u);
+    }
+    if (zeros) atomicAdd(&my[0], zeros);
+    __syncthreads();
+    uint32_t cnt = 0u;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) cnt += lh[r * 256 + tid];
+    if (cnt) atomicAdd(&hist[tid], cnt);
+}
+
 // build_histogram (src/quant.rs:594-600).  16 symbols per thread per step; the dominant zero symbol is
 // counted in a register (byte-wise zero test), the others go to 8 LDS replicas of the bins.
 __global__ __launch_bounds__(256) void histogram_kernel(const uint8_t* __restrict__ sym, unsigned long long n,
@@ -500,6 +546,20 @@ void launch_histogram(const uint8_t* sym, uint64_t n, uint32_t* hist, hipStream_
     unsigned g = grid_for(n);
     if (g > 2048) g = 2048;
     hipLaunchKernelGGL(histogram_kernel, dim3(g), dim3(256), 0, st, sym, (unsigned long long)n, hist);
+}
+void launch_to_symbols_wide(const int32_t* in, uint16_t* out, uint64_t n, hipStream_t st) {
+    if (!n) return;
+    hipLaunchKernelGGL(to_symbols_wide_kernel, dim3(grid_for(n)), dim3(256), 0, st, in, out, (unsigned long long)n);
+}
+void launch_from_symbols_wide(const uint16_t* in, int32_t* out, uint64_t n, hipStream_t st) {
+    if (!n) return;
+    hipLaunchKernelGGL(from_symbols_wide_kernel, dim3(grid_for(n)), dim3(256), 0, st, in, out, (unsigned long long)n);
+}
+void launch_histogram_wide(const uint16_t* sym, uint64_t n, uint32_t* hist, hipStream_t st) {
+    if (!n) return;
+    unsigned g = grid_for(n);
+    if (g > 2048) g = 2048;
+    hipLaunchKernelGGL(histogram_wide_kernel, dim3(g), dim3(256), 0, st, sym, (unsigned long long)n, hist);
 }
 void launch_sq_diff_sum(const uint8_t* a, const uint8_t* b, uint64_t n, unsigned long long* d_sum, hipStream_t st) {
     if (!n) return;

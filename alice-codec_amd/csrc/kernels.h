@@ -148,6 +148,12 @@ bool launch_forward_coef_hist(const RgbLayout& rgb, const ChunkDims& d, int wave
 // pixels of `rgb` are written: no byte between or beside the rows of a region.
 bool launch_inverse_transform(const uint8_t* d_sym, const ChunkDims& d, int wavelet, const int32_t step[3],
                               bool exact, bool mid16, bool lds16, void* d_scratch, const RgbLayout& rgb, hipStream_t st);
+// The wide twins (.alc v3): the temporal passes write / read untruncated u16 symbols z (0, 2q - 1, -2q) and the histogram
+// bins min(z, 255); the tile passes, band plans and scratch sizes are those above.
+bool launch_forward_transform_wide(const RgbLayout& rgb, const ChunkDims& d, int wavelet, int32_t step,
+                                   void* d_scratch, uint16_t* d_sym, uint32_t* d_hist, hipStream_t st);
+bool launch_inverse_transform_wide(const uint16_t* d_sym, const ChunkDims& d, int wavelet, const int32_t step[3],
+                                   bool exact, bool mid16, bool lds16, void* d_scratch, const RgbLayout& rgb, hipStream_t st);
 
 // ---- transform.hip, stage level: Wavelet2D / Wavelet3D of caller-shaped i32 data on the tile kernels' exact instances ----
 // eligible: even width and height >= 6, even depth (or depth 1); otherwise the caller uses launch_wavelet_axis.
@@ -176,6 +182,10 @@ void launch_dequantize(const int32_t* in, int32_t* out, uint64_t n, int32_t step
 void launch_to_symbols(const int32_t* in, uint8_t* out, uint64_t n, hipStream_t st);
 void launch_from_symbols(const uint8_t* in, int32_t* out, uint64_t n, hipStream_t st);
 void launch_histogram(const uint8_t* sym, uint64_t n, uint32_t* hist /*zeroed*/, hipStream_t st);
+// wide twins: z untruncated as u16 (the caller guarantees |q| <= 32767); the histogram bins min(z, 255)
+void launch_to_symbols_wide(const int32_t* in, uint16_t* out, uint64_t n, hipStream_t st);
+void launch_from_symbols_wide(const uint16_t* in, int32_t* out, uint64_t n, hipStream_t st);
+void launch_histogram_wide(const uint16_t* sym, uint64_t n, uint32_t* hist /*zeroed*/, hipStream_t st);
 // ssim (src/ssim.rs): per-8x8-block values in raster order; f64 fold in element order; 2x2 truncating mean
 void launch_ssim_blocks(const uint8_t* d_a, const uint8_t* d_b, uint64_t width, uint64_t bw, uint64_t nblocks, double* d_out, hipStream_t st);
 void launch_ordered_sum_f64(const double* d_v, uint64_t n, double* d_out, hipStream_t st);
@@ -252,9 +262,14 @@ constexpr uint32_t kSplitHeaderBytes = kSplitFixedHeaderBytes + 3 * kSplitChanne
 constexpr uint32_t kSplitMinLane = 64, kSplitMaxLane = 16384, kSplitDefaultLane = 512;
 constexpr uint32_t kSplitBadDirectory = 1u;   // block table or lane directory does not add up to the payload
 constexpr uint32_t kSplitBadLane = 2u;        // a lane failed its end check
+// .alc v3: u16 symbols, coded symbol min(z, 255), escape 255 + a uniform 12-bit residual
+constexpr uint32_t kSplitWideMaxLane = 8192;          // 4 L + 4 bytes per lane stream must fit the u16 directory
+constexpr uint32_t kSplitWideMaxResidual = 4095u;     // z <= 255 + 4095
+constexpr uint32_t kSplitWideResidual = 4u;           // count pass: a symbol whose residual does not fit 12 bits
+constexpr int kWideMaxQ = 2175;                       // |q| of z = 4350, the largest symbol a (damaged) v3 stream decodes to
 // One channel: n symbols in blocks of 64 * lane_symbols, payload at `stream`.
 struct SplitJob {
-    const uint8_t* sym;        // encode: the symbols; decode: where they go (written)
+    const uint8_t* sym;        // encode: the symbols; decode: where they go (written).  The wide kernels: n x u16
     unsigned long long n;
     const RansTable* table;
     uint8_t* stream;           // the channel's payload: u32 block lengths, then the blocks
@@ -283,5 +298,12 @@ void launch_split_scan(const SplitJob* d_jobs, int n_jobs, bool from_stream, uns
 // after scan(from_stream = true); *flags != 0 afterwards: the payload is not a valid stream
 void launch_split_decode(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, hipStream_t st);
 void launch_split_headers(const SplitHeaderDesc* d_descs, int n_chunks, hipStream_t st);
+// the same three passes on u16 symbols with the escape step (.alc v3); the count pass sets kSplitWideResidual in *flags
+// (zeroed by the caller) when a symbol exceeds 255 + kSplitWideMaxResidual
+// overwrites the version byte of the headers launch_split_headers wrote (same stream, after it)
+void launch_split_header_version(const SplitHeaderDesc* d_descs, int n_chunks, uint8_t version, hipStream_t st);
+void launch_split_wide_count(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, hipStream_t st);
+void launch_split_wide_write(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, hipStream_t st);
+void launch_split_wide_decode(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, hipStream_t st);
 
 }  // namespace alice

@@ -12,6 +12,7 @@
 //   split_scan_kernel     block lengths -> block offsets (encode: from the count pass; decode: from the stream, validated)
 //   split_decode_kernel   lane streams -> symbols, with the end check of every lane
 //   split_header_kernel   the 1630-byte container header of whole chunks
+//   split_wide_encode_kernel / split_wide_decode_kernel   the same chains on u16 symbols with the escape step of .alc v3
 // The output is sized by counting first and writing second: the chain arithmetic runs twice, but nothing is staged in
 // worst-case slots (2 bytes per symbol) and no compaction pass moves the payload again.
 //
@@ -287,6 +288,186 @@ __global__ __launch_bounds__(256) void split_decode_kernel(const SplitJob* __res
 }
 
 // ----------------------------------------------------------------------------------
+// Wide lane coder (.alc v3): the geometry of the kernels above on u16 symbols (128 consecutive
+// bytes per wavefront step).  The coded symbol is s = min(z, 255); s = 255 is an escape followed in the same chain by the
+// residual r = z - 255 as one uniform 12-bit step (frequency 1, cum r: xmax = 2^19, x = (x << 12) + r).  The encoder
+// walks last to first, so it codes the residual BEFORE the step of symbol 255; the decoder meets them the other way round.
+// A residual above 4095 cannot be coded: the count pass records it in *job.flags (kSplitWideResidual) and the host
+// refuses the call before the write pass runs; the write pass masks r so that its byte count stays the counted one.
+// ----------------------------------------------------------------------------------
+template <bool kWrite>
+__global__ __launch_bounds__(256) void split_wide_encode_kernel(const SplitJob* __restrict__ jobs) {
+    __shared__ uint4 rows[256];
+    const SplitJob job = jobs[blockIdx.y];
+    {
+        const RansEncEntry e = job.table->enc[threadIdx.x];
+        rows[threadIdx.x] = make_uint4(e.xmax, e.rcp, e.cbias, (uint32_t)e.g | (e.rsh << 16));
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const unsigned long long b = (unsigned long long)blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (b >= job.n_blocks) return;
+    const unsigned long long base = b * 64ull * job.lane_symbols;
+    const unsigned long long left = job.n - base;
+    const uint32_t in_block = left < 64ull * job.lane_symbols ? (uint32_t)left : 64u * job.lane_symbols;
+    const uint32_t k = (uint32_t)lane < in_block ? (in_block - (uint32_t)lane + 63u) / 64u : 0u;
+    const uint32_t kmax = (in_block + 63u) / 64u;   // lane 0's count
+    const uint16_t* __restrict__ sym = (const uint16_t*)job.sym + base + lane;
+
+    uint32_t len = 0u;              // bytes of this lane's stream
+    uint8_t* out = nullptr;         // kWrite: one past the lane's last byte
+    uint32_t acc = 0u, nacc = 0u;   // kWrite: bytes collected for the dword in progress (lowest address in the low byte)
+    bool wide_bad = false;          // count pass: a residual above 4095
+    if (kWrite) {
+        len = job.lane_len[b * 64u + lane];
+        const uint32_t incl = wave_incl_scan(len, lane);
+        uint8_t* blk = job.stream + job.blk_off[b];
+        blk[2 * lane] = (uint8_t)len;
+        blk[2 * lane + 1] = (uint8_t)(len >> 8);
+        if (lane < 4) job.stream[4ull * b + lane] = (uint8_t)(job.blk_len[b] >> (8 * lane));
+        out = blk + 128u + incl;
+    }
+    auto put = [&](uint32_t byte) {
+        if (kWrite) {
+            --out;
+            acc = (acc << 8) | byte;
+            ++nacc;
+            if (((uintptr_t)out & 3u) == 0u) {
+                if (nacc == 4u) *(uint32_t*)out = acc;
+                else for (uint32_t t = 0; t < nacc; ++t) out[t] = (uint8_t)(acc >> (8u * t));
+                nacc = 0u;
+            }
+        } else {
+            ++len;
+        }
+    };
+    uint32_t x = kRansL;
+    // eight symbols are loaded ahead of the chain that consumes them
+    for (uint32_t hi = kmax; hi > 0u; hi = hi > 8u ? hi - 8u : 0u) {
+        uint32_t s[8];
+#pragma unroll
+        for (uint32_t u = 0; u < 8u; ++u) {
+            const uint32_t i = hi - 1u - u;   // wraps past 0: then i >= k
+            s[u] = i < k ? sym[(size_t)i * 64u] : 0u;
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < 8u; ++u) {
+            const uint32_t i = hi - 1u - u;
+            if (i < k) {
+                const uint32_t z = s[u];
+                if (z >= 255u) {
+                    const uint32_t r = z - 255u;
+                    if (r > kSplitWideMaxResidual) wide_bad = true;
+                    if (x >= (1u << 19)) { put(x & 255u); x >>= 8; }
+                    if (x >= (1u << 19)) { put(x & 255u); x >>= 8; }
+                    x = (x << 12) + (r & kSplitWideMaxResidual);
+                }
+                const uint4 row = rows[z < 255u ? z : 255u];
+                if (x >= row.x) { put(x & 255u); x >>= 8; }
+                if (x >= row.x) { put(x & 255u); x >>= 8; }
+                const uint32_t q = __umulhi(x, row.y) >> (row.w >> 16);
+                x = x + q * (row.w & 0xFFFFu) + row.z;
+            }
+        }
+    }
+    if (k) {
+        put(x & 255u); put((x >> 8) & 255u); put((x >> 16) & 255u); put(x >> 24);
+    }
+    if (kWrite) {
+        for (uint32_t t = 0; t < nacc; ++t) out[t] = (uint8_t)(acc >> (8u * t));
+    } else {
+        job.lane_len[b * 64u + lane] = (uint16_t)len;
+        const uint32_t incl = wave_incl_scan(len, lane);
+        if (lane == 63) job.blk_len[b] = 128u + incl;
+        if (wide_bad) *job.flags = kSplitWideResidual;
+    }
+}
+
+// The wide decoder: split_decode_kernel with the escape step.  A damaged stream can give any residual in 0..4095, so any
+// z up to 4350; it is stored like every other symbol, at the lane's own position inside the block.
+__global__ __launch_bounds__(256) void split_wide_decode_kernel(const SplitJob* __restrict__ jobs) {
+    __shared__ uint32_t c2s_sh[kProbScale / 4];
+    __shared__ uint32_t symtab[256];
+    const SplitJob job = jobs[blockIdx.y];
+    {
+        const uint32_t* src = (const uint32_t*)job.table->dec.c2s;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) c2s_sh[threadIdx.x + 256 * t] = src[threadIdx.x + 256 * t];
+        symtab[threadIdx.x] = job.table->dec.symtab[threadIdx.x];
+    }
+    __syncthreads();
+    const uint8_t* c2s = (const uint8_t*)c2s_sh;
+    const int lane = threadIdx.x & 63;
+    const unsigned long long b = (unsigned long long)blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (b >= job.n_blocks) return;
+    const unsigned long long base = b * 64ull * job.lane_symbols;
+    const unsigned long long left = job.n - base;
+    const uint32_t in_block = left < 64ull * job.lane_symbols ? (uint32_t)left : 64u * job.lane_symbols;
+    const uint32_t k = (uint32_t)lane < in_block ? (in_block - (uint32_t)lane + 63u) / 64u : 0u;
+    uint16_t* __restrict__ sym = (uint16_t*)job.sym + base + lane;   // symbol i of the lane: base + lane + 64 i < base + in_block
+
+    const uint32_t blen = job.blk_len[b];
+    const unsigned long long boff = job.blk_off[b];
+    // (the scan left 0 for a block it refused; checked again here so that the bounds do not rest on another kernel)
+    if (blen < 128u || boff + blen > job.len) { if (lane == 0) *job.flags = kSplitBadDirectory; return; }
+    const uint8_t* blk = job.stream + boff;
+    const uint32_t len = (uint32_t)blk[2 * lane] | ((uint32_t)blk[2 * lane + 1] << 8);
+    const uint32_t incl = wave_incl_scan(len, lane);
+    const uint32_t all = __shfl(incl, 63, 64);
+    if (all + 128u != blen) { if (lane == 0) *job.flags = kSplitBadDirectory; return; }
+    const uint8_t* __restrict__ src = blk + 128u + (incl - len);   // [src, src + len) lies inside the block
+
+    uint32_t win = 0u, nwin = 0u, fpos = 0u, pos = 0u;
+    auto take = [&]() -> uint32_t {
+        if (nwin == 0u) {
+            uint32_t w = 0u;
+            if (fpos + 4u <= len) {
+                uint32_t t;
+                __builtin_memcpy(&t, src + fpos, 4);
+                w = __builtin_bswap32(t);
+            } else {
+#pragma unroll
+                for (uint32_t t = 0; t < 4u; ++t) w = (w << 8) | (fpos + t < len ? (uint32_t)src[fpos + t] : 0u);
+            }
+            fpos += 4u;
+            win = w;
+            nwin = 4u;
+        }
+        const uint32_t byte = win >> 24;
+        win <<= 8;
+        --nwin;
+        ++pos;
+        return byte;
+    };
+    bool ok = true;
+    if (k == 0u) {
+        ok = len == 0u;
+    } else {
+        uint32_t x = take() << 24;
+        x |= take() << 16;
+        x |= take() << 8;
+        x |= take();
+        for (uint32_t i = 0; i < k; ++i) {
+            const uint32_t slot = x & (kProbScale - 1u);
+            uint32_t s = c2s[slot];
+            const uint32_t fc = symtab[s];
+            x = (fc & 0xFFFFu) * (x >> kProbBits) + slot - (fc >> 16);
+            if (x < kRansL) x = (x << 8) | take();
+            if (x < kRansL) x = (x << 8) | take();
+            if (s == 255u) {
+                s += x & kSplitWideMaxResidual;
+                x >>= 12;
+                if (x < kRansL) x = (x << 8) | take();
+                if (x < kRansL) x = (x << 8) | take();
+            }
+            sym[(size_t)i * 64u] = (uint16_t)s;
+        }
+        ok = x == kRansL && pos == len;
+    }
+    if (!ok) *job.flags = kSplitBadLane;
+}
+
+// ----------------------------------------------------------------------------------
 // Container header of whole chunks, one workgroup per chunk.
 // ----------------------------------------------------------------------------------
 __device__ __forceinline__ void put_le(uint8_t* p, unsigned long long v, int bytes) {
@@ -315,6 +496,12 @@ __global__ __launch_bounds__(256) void split_header_kernel(const SplitHeaderDesc
     }
 }
 
+// The version byte of containers whose headers split_header_kernel has written (.alc v3 differs from v2 in that byte).
+__global__ __launch_bounds__(64) void split_version_kernel(const SplitHeaderDesc* __restrict__ descs, int n, uint32_t version) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i < n) descs[i].out[4] = (uint8_t)version;
+}
+
 // ----------------------------------------------------------------------------------
 // launchers
 // ----------------------------------------------------------------------------------
@@ -337,6 +524,18 @@ void launch_split_scan(const SplitJob* d_jobs, int n_jobs, bool from_stream, uns
 }
 void launch_split_decode(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, hipStream_t st) {
     if (n_jobs > 0 && max_blocks) hipLaunchKernelGGL(split_decode_kernel, split_grid(max_blocks, n_jobs), dim3(256), 0, st, d_jobs);
+}
+void launch_split_header_version(const SplitHeaderDesc* d_descs, int n_chunks, uint8_t version, hipStream_t st) {
+    if (n_chunks > 0) hipLaunchKernelGGL(split_version_kernel, dim3((n_chunks + 63) / 64), dim3(64), 0, st, d_descs, n_chunks, (uint32_t)version);
+}
+void launch_split_wide_count(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, hipStream_t st) {
+    if (n_jobs > 0 && max_blocks) hipLaunchKernelGGL(split_wide_encode_kernel<false>, split_grid(max_blocks, n_jobs), dim3(256), 0, st, d_jobs);
+}
+void launch_split_wide_write(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, hipStream_t st) {
+    if (n_jobs > 0 && max_blocks) hipLaunchKernelGGL(split_wide_encode_kernel<true>, split_grid(max_blocks, n_jobs), dim3(256), 0, st, d_jobs);
+}
+void launch_split_wide_decode(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, hipStream_t st) {
+    if (n_jobs > 0 && max_blocks) hipLaunchKernelGGL(split_wide_decode_kernel, split_grid(max_blocks, n_jobs), dim3(256), 0, st, d_jobs);
 }
 void launch_split_headers(const SplitHeaderDesc* d_descs, int n_chunks, hipStream_t st) {
     if (n_chunks > 0) hipLaunchKernelGGL(split_header_kernel, dim3(n_chunks), dim3(256), 0, st, d_descs);

@@ -29,6 +29,8 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include <type_traits>
+
 #include "common.h"
 #include "kernels.h"
 #include "symbols.h"
@@ -330,6 +332,26 @@ __device__ __forceinline__ uint32_t quant_sym4(const I4& x, uint32_t hdz, uint32
     return s[0] | (s[1] << 8) | (s[2] << 16) | (s[3] << 24);
 }
 
+// The wide symbol of .alc v3: the same arithmetic without the mask, z as u16 (four of them in a
+// uint2); the histogram bins the coded symbol min(z, 255).  z <= 4080 for 8-bit RGB; the clamp to 65535 only keeps a value
+// no such chunk produces from wrapping into a valid symbol (the lane coder's residual guard then refuses it).
+template <bool STEP1>
+__device__ __forceinline__ uint2 quant_sym4_wide(const I4& x, uint32_t hdz, uint32_t magic, uint32_t* lh, uint32_t lane_rep) {
+    uint32_t s[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int val = x.v[i];
+        const int neg = -val;
+        const uint32_t mag = (uint32_t)max(val, neg);
+        const uint32_t adj = sat_sub_u32(mag, hdz);
+        const uint32_t q = STEP1 ? adj : __umulhi(adj, magic);
+        const uint32_t t = sat_sub_u32((q << 1) + ((uint32_t)val >> 31), 1u);
+        s[i] = min(t, 65535u);
+        atomicAdd(&lh[min(t, 255u) * kHistReplicas + lane_rep], 1u);
+    }
+    return make_uint2(s[0] | (s[1] << 16), s[2] | (s[3] << 16));
+}
+
 // quant_sym1 (symbols.h) is the same map for one value: the table below is filled with it, so table and arithmetic
 // cannot disagree.
 
@@ -367,7 +389,7 @@ __device__ __forceinline__ I4 unpack4_i16(const uint2 w) {
 #endif
 constexpr int kBinReplicas = ALICE_BIN_REPLICAS;
 
-template <int NS, bool STEP1, bool HIST, int PROBE = 0, bool BINS = false>
+template <int NS, bool STEP1, bool HIST, int PROBE = 0, bool BINS = false, bool WIDE = false>
 struct FwdT {
     const char* src;     // channel base inside the band slot (uniform)
     char* dst;           // channel base of the symbol volume (uniform)
@@ -412,6 +434,13 @@ struct FwdT {
     }
     __device__ __forceinline__ void emit(int frame, const I4& lo, const I4& hi) {
         if constexpr (BINS) { bin4(lo); bin4(hi); return; }
+        if constexpr (WIDE) {   // dst counts u16 symbols: 8 bytes per 4 pixels per half
+            const uint2 wa = quant_sym4_wide<STEP1>(lo, hdz, magic, lh, lane_rep);
+            const uint2 wb = quant_sym4_wide<STEP1>(hi, hdz, magic, lh, lane_rep);
+            *(uint2*)(dst + ((size_t)frame * plane_d + off8) * 2) = wa;
+            *(uint2*)(dst + ((size_t)(half + frame) * plane_d + off8) * 2) = wb;
+            return;
+        }
         uint32_t a, b;
         uint32_t ix[8], any = 0u;
 #pragma unroll
@@ -576,6 +605,33 @@ __global__ __launch_bounds__(256) void fwd_t_kernel(FwdTm a) {
     if (cnt) atomicAdd(&a.hist[ch * 256 + tid], cnt);
 }
 
+// The wide instance (.alc v3): the same stream, symbols by arithmetic (no value table: 16 KB of LDS instead of 20), a.sym
+// is the u16 symbol volume.
+template <int NS, bool STEP1>
+__global__ __launch_bounds__(256) void fwd_t_wide_kernel(FwdTm a) {
+    __shared__ uint32_t lh[kHistWords];
+    const int tid = threadIdx.x;
+    for (int i = tid; i < kHistWords; i += 256) lh[i] = 0u;
+    __syncthreads();
+    const int ch = (int)(blockIdx.x / a.b.units_per_ch);
+    const uint32_t blk = blockIdx.x % a.b.units_per_ch;
+    const uint32_t idx = (blk * 256u + (uint32_t)tid) * 4u;
+    if (idx < a.b.band_px) {
+        FwdT<NS, STEP1, true, 0, false, true> f;
+        f.src = (const char*)(a.mid + (size_t)ch * a.b.pf * a.b.band_px);
+        f.dst = (char*)((uint16_t*)a.sym + (size_t)ch * a.b.pf * a.b.plane);
+        f.plane_s = a.b.band_px; f.plane_d = a.b.plane;
+        f.off16 = idx * 2u; f.off8 = band_plane_index(a.b, idx);
+        f.half = (int)a.b.pf / 2; f.cf = a.cf; f.hdz = a.hdz; f.magic = a.magic; f.lane_rep = (uint32_t)tid & (kHistReplicas - 1); f.lh = lh; f.qlut = nullptr; f.qr = 0u;
+        f.run();
+    }
+    __syncthreads();
+    uint32_t cnt = 0u;
+#pragma unroll 8
+    for (int r = 0; r < kHistReplicas; ++r) cnt += lh[tid * kHistReplicas + ((r + tid) & (kHistReplicas - 1))];
+    if (cnt) atomicAdd(&a.hist[ch * 256 + tid], cnt);
+}
+
 // The temporal pass of the rate prediction: the same lifting, but every coefficient is counted into 4096 bins per channel
 // (value + qr for values in [-qr, qr), the radius of the value table) instead of being quantised; values outside go to the
 // chunk's out-of-range counter.  No symbol stores.  A workgroup walks several units of its channel so that the 2 * qr bins
@@ -659,8 +715,10 @@ __device__ __forceinline__ void store4<int16_t>(int16_t* p, const I4& x) {
 // Tick k consumes the symbols of frames k (low band) and half+k (high band), emits frame 2(k-1) and
 // frame 2(k-2)+1.  from_symbols + dequantize (src/quant.rs:104-110,581-587) is a 256-entry table in LDS:
 // one byte extract and one LDS read per sample instead of seven VALU operations.
-template <int NS, bool EXACT, typename MidT, int PROBE = 0>
+// WIDE (.alc v3): the symbols are u16 and are dequantised by arithmetic (z -> q -> q * step, wrapping), since z reaches 4350.
+template <int NS, bool EXACT, typename MidT, int PROBE = 0, bool WIDE = false>
 struct InvT {
+    using Sym4 = std::conditional_t<WIDE, uint2, uint32_t>;   // the symbols of 4 pixels
     const char* src;      // channel base of the symbol volume
     MidT* dst;            // channel base inside the band slot + this thread's slot pixel
     size_t plane_s;       // pixels per frame of the symbol volume
@@ -669,18 +727,33 @@ struct InvT {
     int half, nf;
     int c0, c1, c2, c3;   // already negated
     const int* lut;
+    int step;             // WIDE only
     I4 o2p, e1p, o1pp, e0pp;
     int acc;              // PROBE only
 
-    __device__ __forceinline__ void load_pair(int pair, uint32_t& lo, uint32_t& hi) const {
-        if (PROBE & 1) { lo = (off8 + (uint32_t)pair * 0x01030507u) & 0x0F070F07u; hi = lo ^ 0x01010101u; return; }
-        lo = *(const uint32_t*)(src + (size_t)pair * plane_s + off8);
-        hi = *(const uint32_t*)(src + (size_t)(half + pair) * plane_s + off8);
+    __device__ __forceinline__ void load_pair(int pair, Sym4& lo, Sym4& hi) const {
+        if constexpr (WIDE) {
+            lo = *(const uint2*)(src + ((size_t)pair * plane_s + off8) * 2);
+            hi = *(const uint2*)(src + ((size_t)(half + pair) * plane_s + off8) * 2);
+        } else {
+            if (PROBE & 1) { lo = (off8 + (uint32_t)pair * 0x01030507u) & 0x0F070F07u; hi = lo ^ 0x01010101u; return; }
+            lo = *(const uint32_t*)(src + (size_t)pair * plane_s + off8);
+            hi = *(const uint32_t*)(src + (size_t)(half + pair) * plane_s + off8);
+        }
     }
-    __device__ __forceinline__ I4 dq(uint32_t packed) const {
+    __device__ __forceinline__ I4 dq(Sym4 packed) const {
         I4 r;
+        if constexpr (WIDE) {
+            const uint32_t z[4] = {packed.x & 0xFFFFu, packed.x >> 16, packed.y & 0xFFFFu, packed.y >> 16};
 #pragma unroll
-        for (int i = 0; i < 4; ++i) r.v[i] = lut[(packed >> (8 * i)) & 0xFFu];
+            for (int i = 0; i < 4; ++i) {
+                const int q = (z[i] & 1u) ? (int)((z[i] + 1u) >> 1) : -(int)(z[i] >> 1);   // src/quant.rs:581-587
+                r.v[i] = (int)((unsigned)q * (unsigned)step);                               // src/quant.rs:104-110 (wrapping)
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) r.v[i] = lut[(packed >> (8 * i)) & 0xFFu];
+        }
         return r;
     }
     __device__ __forceinline__ void put(int frame, const I4& x) {
@@ -688,7 +761,7 @@ struct InvT {
         if (frame < nf) store4<MidT>(dst + (size_t)frame * plane_d, x);
     }
     template <bool FIRST, bool SECOND>
-    __device__ __forceinline__ void tick(int k, uint32_t lo, uint32_t hi) {
+    __device__ __forceinline__ void tick(int k, Sym4 lo, Sym4 hi) {
         const I4 hv = dq(hi), lv = dq(lo);
         if (NS == 4) {
             const I4 e1 = lift4<EXACT>(lv, FIRST ? hv : o2p, hv, c3);
@@ -721,7 +794,7 @@ struct InvT {
     __device__ __forceinline__ void run() {
         o2p = I4{}; e1p = I4{}; o1pp = I4{}; e0pp = I4{};
         acc = 0;
-        uint32_t rl[4] = {0u, 0u, 0u, 0u}, rh[4] = {0u, 0u, 0u, 0u};   // symbols in flight; slot = pair & 3 (static)
+        Sym4 rl[4] = {}, rh[4] = {};   // symbols in flight; slot = pair & 3 (static)
 #pragma unroll
         for (int i = 0; i < 3; ++i)
             if (i < half) load_pair(i, rl[i], rh[i]);
@@ -787,6 +860,25 @@ __global__ __launch_bounds__(256) void inv_t_kernel(InvTm a) {
     f.half = (int)a.b.pf / 2; f.nf = (int)a.nf;
     f.c0 = -a.cf.c[0]; f.c1 = -a.cf.c[1]; f.c2 = -a.cf.c[2]; f.c3 = -a.cf.c[3];
     f.lut = lut;
+    f.run();
+}
+
+// The wide instance (.alc v3): a.sym is the u16 symbol volume; no table.
+template <int NS, bool EXACT, typename MidT>
+__global__ __launch_bounds__(256) void inv_t_wide_kernel(InvTm a) {
+    const int tid = threadIdx.x;
+    const int ch = (int)(blockIdx.x / a.b.units_per_ch);
+    const uint32_t blk = blockIdx.x % a.b.units_per_ch;
+    const uint32_t idx = (blk * 256u + (uint32_t)tid) * 4u;
+    if (idx >= a.b.band_px) return;
+    InvT<NS, EXACT, MidT, 0, true> f;
+    f.src = (const char*)((const uint16_t*)a.sym + (size_t)ch * a.b.pf * a.b.plane);
+    f.dst = (MidT*)a.mid + (size_t)ch * a.b.pf * a.b.band_px + idx;
+    f.plane_s = a.b.plane; f.plane_d = a.b.band_px;
+    f.off8 = band_plane_index(a.b, idx);
+    f.half = (int)a.b.pf / 2; f.nf = (int)a.nf;
+    f.c0 = -a.cf.c[0]; f.c1 = -a.cf.c[1]; f.c2 = -a.cf.c[2]; f.c3 = -a.cf.c[3];
+    f.lut = nullptr; f.step = a.step[ch];
     f.run();
 }
 
@@ -1340,6 +1432,10 @@ template <int NS, bool STEP1, int PROBE = 0>
 static void fwd_t_launch(const FwdTm& ta, hipStream_t st) {
     hipLaunchKernelGGL((fwd_t_kernel<NS, STEP1, PROBE>), dim3(3u * ta.b.units_per_ch), dim3(256), 0, st, ta);
 }
+template <int NS, bool STEP1>
+static void fwd_t_wide_launch(const FwdTm& ta, hipStream_t st) {
+    hipLaunchKernelGGL((fwd_t_wide_kernel<NS, STEP1>), dim3(3u * ta.b.units_per_ch), dim3(256), 0, st, ta);
+}
 
 // The band loop of the forward launches: the tile pass of every band, each followed by `temporal(BandT)` on its slot.
 template <typename Fn>
@@ -1397,6 +1493,22 @@ bool launch_forward_transform(const RgbLayout& rgb, const ChunkDims& d, int wave
     });
 }
 
+bool launch_forward_transform_wide(const RgbLayout& rgb, const ChunkDims& d, int wavelet, int32_t step,
+                                   void* d_scratch, uint16_t* d_sym, uint32_t* d_hist, hipStream_t st) {
+    if (step < 1 || step > 64) return false;
+    const uint32_t magic = step == 1 ? 0u : (uint32_t)(((1ull << 32) + (uint32_t)step - 1u) / (uint32_t)step);
+    return forward_bands(rgb, d, wavelet, d_scratch, 0, st, [&](const BandT& b, const Coeffs& cf, int ns) {
+        FwdTm ta{};
+        ta.mid = (const int16_t*)d_scratch; ta.sym = (uint8_t*)d_sym; ta.hist = d_hist; ta.cf = cf; ta.hdz = (uint32_t)step / 2u; ta.magic = magic;
+        ta.b = b;
+        if (ns == 4) {
+            if (step == 1) fwd_t_wide_launch<4, true>(ta, st); else fwd_t_wide_launch<4, false>(ta, st);
+        } else {
+            if (step == 1) fwd_t_wide_launch<2, true>(ta, st); else fwd_t_wide_launch<2, false>(ta, st);
+        }
+    });
+}
+
 bool launch_forward_coef_hist(const RgbLayout& rgb, const ChunkDims& d, int wavelet, void* d_scratch, uint32_t* d_bins,
                               uint32_t* d_oor, hipStream_t st) {
     return forward_bands(rgb, d, wavelet, d_scratch, 0, st, [&](const BandT& b, const Coeffs& cf, int ns) {
@@ -1411,15 +1523,18 @@ bool launch_forward_coef_hist(const RgbLayout& rgb, const ChunkDims& d, int wave
 
 // ---- inverse ----
 
-template <int NS, bool EXACT, typename MidT, bool PACKED, int PROBE = 0>
+template <int NS, bool EXACT, typename MidT, bool PACKED, int PROBE = 0, bool WIDE = false>
 static void inv_band_launch(const InvTm& ta, const InvXy& xa, hipStream_t st) {
-    hipLaunchKernelGGL((inv_t_kernel<NS, EXACT, MidT, PROBE>), dim3(3u * ta.b.units_per_ch), dim3(256), 0, st, ta);
+    if constexpr (WIDE) hipLaunchKernelGGL((inv_t_wide_kernel<NS, EXACT, MidT>), dim3(3u * ta.b.units_per_ch), dim3(256), 0, st, ta);
+    else hipLaunchKernelGGL((inv_t_kernel<NS, EXACT, MidT, PROBE>), dim3(3u * ta.b.units_per_ch), dim3(256), 0, st, ta);
     const unsigned long long tiles = (unsigned long long)xa.bt.nx * xa.bt.nby * xa.d.f;
     hipLaunchKernelGGL((inv_xy_kernel<NS, EXACT, MidT, PACKED, PROBE>), dim3(xcd_grid(tiles)), dim3(InvTileShape<PACKED>::kThreads), 0, st, xa);
 }
 
-bool launch_inverse_transform(const uint8_t* d_sym, const ChunkDims& d, int wavelet, const int32_t step[3],
-                              bool exact, bool mid16, bool lds16, void* d_scratch, const RgbLayout& rgb, hipStream_t st) {
+// WIDE: d_sym is the u16 symbol volume of .alc v3 and the temporal role runs its wide instance; everything else is shared.
+template <bool WIDE>
+static bool inverse_launches(const void* d_sym, const ChunkDims& d, int wavelet, const int32_t step[3],
+                             bool exact, bool mid16, bool lds16, void* d_scratch, const RgbLayout& rgb, hipStream_t st) {
     if (!transform_tiles_eligible(d)) return false;
     const LiftSteps ls = lift_steps(wavelet);
     // mid16: the host proved every value after the inverse temporal pass fits i16 (then exact is false too);
@@ -1439,7 +1554,7 @@ bool launch_inverse_transform(const uint8_t* d_sym, const ChunkDims& d, int wave
     const int hh = (int)(d.ph / 2);
     const uint32_t pw = (uint32_t)d.pw;
     const int n_bands = bp.n_bands > 1 ? ((int)ny + bp.tpb - 1) / bp.tpb : 1;
-    const int probe = (ls.n == 4 && variant == 2) ? tl_valu_probe : 0;
+    const int probe = (!WIDE && ls.n == 4 && variant == 2) ? tl_valu_probe : 0;
     for (int band = 0; band < n_bands; ++band) {
         const int by0 = n_bands > 1 ? band * bp.tpb : 0, nby = n_bands > 1 ? std::min(bp.tpb, (int)ny - by0) : (int)ny;
         // slot rows: the band's own rows plus two halo rows of each half on either side, inside the frame
@@ -1450,7 +1565,7 @@ bool launch_inverse_transform(const uint8_t* d_sym, const ChunkDims& d, int wave
         }
         const int rows_l = L1 - L0;
         InvTm ta{};
-        ta.sym = d_sym; ta.mid = d_scratch; ta.cf = cf; ta.step[0] = step[0]; ta.step[1] = step[1]; ta.step[2] = step[2]; ta.nf = d.f;
+        ta.sym = (const uint8_t*)d_sym; ta.mid = d_scratch; ta.cf = cf; ta.step[0] = step[0]; ta.step[1] = step[1]; ta.step[2] = step[2]; ta.nf = d.f;
         ta.b = make_band_t(d, 2u * (uint32_t)rows_l * pw, (uint32_t)rows_l * pw, (uint32_t)L0 * pw, (uint32_t)(hh + L0) * pw);
         InvXy xa{};
         xa.mid = d_scratch; xa.rgb = rgb; xa.d = d; xa.cf = cf;
@@ -1465,15 +1580,24 @@ bool launch_inverse_transform(const uint8_t* d_sym, const ChunkDims& d, int wave
         }
 #define ALICE_INV(NS_) \
         switch (variant) { \
-        case 0: inv_band_launch<NS_, true, int32_t, false>(ta, xa, st); break; \
-        case 1: inv_band_launch<NS_, false, int32_t, false>(ta, xa, st); break; \
-        case 2: inv_band_launch<NS_, false, int16_t, false>(ta, xa, st); break; \
-        default: inv_band_launch<NS_, false, int16_t, true>(ta, xa, st); break; \
+        case 0: inv_band_launch<NS_, true, int32_t, false, 0, WIDE>(ta, xa, st); break; \
+        case 1: inv_band_launch<NS_, false, int32_t, false, 0, WIDE>(ta, xa, st); break; \
+        case 2: inv_band_launch<NS_, false, int16_t, false, 0, WIDE>(ta, xa, st); break; \
+        default: inv_band_launch<NS_, false, int16_t, true, 0, WIDE>(ta, xa, st); break; \
         }
         if (ls.n == 4) { ALICE_INV(4) } else { ALICE_INV(2) }
 #undef ALICE_INV
     }
     return true;
+}
+
+bool launch_inverse_transform(const uint8_t* d_sym, const ChunkDims& d, int wavelet, const int32_t step[3],
+                              bool exact, bool mid16, bool lds16, void* d_scratch, const RgbLayout& rgb, hipStream_t st) {
+    return inverse_launches<false>(d_sym, d, wavelet, step, exact, mid16, lds16, d_scratch, rgb, st);
+}
+bool launch_inverse_transform_wide(const uint16_t* d_sym, const ChunkDims& d, int wavelet, const int32_t step[3],
+                                   bool exact, bool mid16, bool lds16, void* d_scratch, const RgbLayout& rgb, hipStream_t st) {
+    return inverse_launches<true>(d_sym, d, wavelet, step, exact, mid16, lds16, d_scratch, rgb, st);
 }
 
 

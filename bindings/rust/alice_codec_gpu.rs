@@ -775,3 +775,98 @@ pub fn encode_split_to_size(rgb_frames: &[u8], width: u32, height: u32, frames: 
         Ok((take(p, n), q, fits != 0))
     }
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// wide format (.alc version 3).  Version 2 with an untruncated symbol: the coded symbol is
+// min(z, 255) and 255 is an escape followed by a 12-bit residual in the same lane chain.  The container for the top of
+// the quality scale, where versions 1 and 2 wrap large coefficients modulo 256.  `lane_symbols`: a power of two in
+// [64, 8192].  The header fields are version 2's (`SplitInfo`); each parser refuses the other versions.
+// ---------------------------------------------------------------------------------------------------------------
+
+#[link(name = "alice_codec")]
+extern "C" {
+    fn alice_codec_wide_stream_bound(n: u64, lane_symbols: u32) -> u64;
+    fn alice_codec_wide_info(data: *const u8, len: u64, info: *mut RawSplitInfo) -> c_int;
+    fn alice_codec_encode_wide(e: *const RawEncoder, rgb: *const u8, rgb_len: u64, w: u32, h: u32, f: u32, lane_symbols: u32,
+                               out_len: *mut u64) -> *mut u8;
+    fn alice_codec_decode_wide(data: *const u8, len: u64, out_len: *mut u64) -> *mut u8;
+    fn alice_codec_dev_encode_wide(d_rgb: *const std::ffi::c_void, w: u32, h: u32, f: u32, n_chunks: u32, wavelet: u8, quality: u8,
+                                   qualities: *const u8, lane_symbols: u32, d_out: *mut std::ffi::c_void, out_stride: u64,
+                                   sizes: *mut u64, hip_stream: *mut std::ffi::c_void) -> c_int;
+    fn alice_codec_dev_decode_wide(d_alc: *const std::ffi::c_void, alc_stride: u64, sizes: *const u64, n_chunks: u32,
+                                   d_rgb_out: *mut std::ffi::c_void, hip_stream: *mut std::ffi::c_void) -> c_int;
+}
+
+pub const WIDE_MAX_LANE_SYMBOLS: u32 = 8192;
+
+/// The validated header of a version 3 container (host code, no device needed).
+pub fn wide_info(data: &[u8]) -> Result<SplitInfo, CodecError> {
+    let mut c = RawSplitInfo::default();
+    let rc = unsafe { alice_codec_wide_info(data.as_ptr(), data.len() as u64, &mut c) };
+    check(rc, 0, data.len())?;
+    Ok(SplitInfo {
+        width: c.width, height: c.height, frames: c.frames, lane_symbols: c.lane_symbols,
+        wavelet_type: match c.wavelet { 1 => WaveletType::Cdf97, 2 => WaveletType::Haar, _ => WaveletType::Cdf53 },
+        quant_step: c.quant_step, dead_zone: c.dead_zone, num_symbols: c.num_symbols, n_blocks: c.n_blocks,
+        payload_len: c.payload_len,
+    })
+}
+
+/// One chunk as version 3 bytes, with the encoder's wavelet and quality (`lane_symbols` 0: the default).
+pub fn encode_wide(encoder: &FrameEncoder, rgb_frames: &[u8], width: u32, height: u32, frames: u32, lane_symbols: u32)
+    -> Result<Vec<u8>, CodecError> {
+    let mut n = 0u64;
+    unsafe {
+        let e = alice_codec_encoder_create_ex(encoder.quality, encoder.wavelet_type as u8);
+        let p = alice_codec_encode_wide(e, rgb_frames.as_ptr(), rgb_frames.len() as u64, width, height, frames, lane_symbols, &mut n);
+        alice_codec_encoder_destroy(e);
+        if p.is_null() {
+            let expected = (width as usize).saturating_mul(height as usize).saturating_mul(frames as usize).saturating_mul(3);
+            return Err(last_error(expected, rgb_frames.len(), width, height, 0));
+        }
+        Ok(take(p, n))
+    }
+}
+
+/// The RGB bytes of a version 3 container; `InvalidBitstream` when a directory does not add up or a lane fails its end check.
+pub fn decode_wide(data: &[u8]) -> Result<Vec<u8>, CodecError> {
+    let mut n = 0u64;
+    unsafe {
+        let p = alice_codec_decode_wide(data.as_ptr(), data.len() as u64, &mut n);
+        if p.is_null() { Err(last_error(0, data.len(), 0, 0, 0)) } else { Ok(take(p, n)) }
+    }
+}
+
+pub fn wide_stream_bound(n: u64, lane_symbols: u32) -> u64 { unsafe { alice_codec_wide_stream_bound(n, lane_symbols) } }
+
+/// The RGB bytes of a container of any version: 1 (`FrameDecoder`), 2 (`decode_split`) or 3 (`decode_wide`).
+pub fn decode_alc(data: &[u8]) -> Result<Vec<u8>, CodecError> {
+    match alc_version(data) {
+        2 => decode_split(data),
+        3 => decode_wide(data),
+        _ => FrameDecoder::new().decode(&EncodedChunk::from_bytes(data)?),
+    }
+}
+
+/// # Safety
+/// As `split_encode_device`.
+pub unsafe fn wide_encode_device(d_rgb: *const std::ffi::c_void, width: u32, height: u32, frames: u32, n_chunks: u32,
+                                 wavelet_type: WaveletType, quality: u8, qualities: Option<&[u8]>, lane_symbols: u32,
+                                 d_out: *mut std::ffi::c_void, out_stride: u64, hip_stream: *mut std::ffi::c_void)
+    -> Result<Vec<u64>, CodecError> {
+    if let Some(q) = qualities {
+        if q.len() != n_chunks as usize { return Err(CodecError::InvalidBufferSize { expected: n_chunks as usize, got: q.len() }); }
+    }
+    let mut sizes = vec![0u64; n_chunks as usize];
+    let rc = alice_codec_dev_encode_wide(d_rgb, width, height, frames, n_chunks, wavelet_type as u8, quality,
+                                         qualities.map_or(std::ptr::null(), |q| q.as_ptr()), lane_symbols, d_out, out_stride,
+                                         sizes.as_mut_ptr(), hip_stream);
+    check(rc, 0, 0).map(|_| sizes)
+}
+
+/// # Safety
+/// As `split_decode_device`.
+pub unsafe fn wide_decode_device(d_alc: *const std::ffi::c_void, alc_stride: u64, sizes: &[u64], d_rgb_out: *mut std::ffi::c_void,
+                                 hip_stream: *mut std::ffi::c_void) -> Result<(), CodecError> {
+    check(alice_codec_dev_decode_wide(d_alc, alc_stride, sizes.as_ptr(), sizes.len() as u32, d_rgb_out, hip_stream), 0, 0)
+}

@@ -441,6 +441,43 @@ int alice_codec_dev_encode_split(const void *d_rgb, uint32_t width, uint32_t hei
 int alice_codec_dev_decode_split(const void *d_alc, uint64_t alc_stride, const uint64_t *sizes, uint32_t n_chunks,
                                  void *d_rgb_out, void *hip_stream);
 
+/* ---- wide format (.alc version 3) ----
+ * Version 2 with an untruncated symbol.  Versions 1 and 2 end their symbol map in the reference's `as u8`, so a
+ * quantised coefficient q with |q| > 127 wraps: at the top of the quality scale (small quantiser steps; about q > 90)
+ * the decoded video is garbage.  Version 3 codes the wide symbol z = 0, 2q - 1 (q > 0), -2q (q < 0) as the coded symbol
+ * min(z, 255) and, behind an escape (255), the residual z - 255 as one uniform 12-bit step of the same lane chain.  Choose
+ * it for qualities whose step lets z reach 255; below that its pixels are version 2's and its bytes differ only where the
+ * symbol 255 occurs.  lane_symbols: a power of two in [64, 8192] (a symbol emits up to 4 bytes and a lane stream must fit
+ * its u16 directory entry), 0 for the default.  The version 2 calls refuse version 3 data and these refuse versions 1 and
+ * 2 ("unsupported version").  Size prediction, byte budgets and region calls exist for version 2 only.  Every call
+ * validates like its version 2 twin, in the same order. */
+/* the most bytes a channel payload of n wide symbols takes (0: lane_symbols out of range or n above 2^32 - 1) */
+uint64_t alice_codec_wide_stream_bound(uint64_t n, uint32_t lane_symbols);
+/* stage pair on one channel: n device symbols z as u16; hist is over min(z, 255) and must count exactly n.  A symbol above
+ * 255 + 4095 has no code: ALICE_ERR_INTERNAL with nothing written (8-bit RGB stays below 4081).  Otherwise as
+ * alice_codec_dev_split_encode / _decode. */
+int alice_codec_dev_wide_encode(const void *d_symbols, uint64_t n, const uint32_t hist[256], uint32_t lane_symbols,
+                                void *d_out, uint64_t cap, uint64_t *out_len, void *hip_stream);
+int alice_codec_dev_wide_decode(const void *d_stream, uint64_t len, const uint16_t freq[256], uint32_t lane_symbols,
+                                void *d_symbols, uint64_t n, void *hip_stream);
+/* whole chunk, host memory: alice_codec_encode_split / _decode_split / _split_info for version 3 */
+uint8_t *alice_codec_encode_wide(const FrameEncoder *encoder, const uint8_t *rgb, uint64_t rgb_len, uint32_t width,
+                                 uint32_t height, uint32_t frames, uint32_t lane_symbols, uint64_t *out_len);
+uint8_t *alice_codec_decode_wide(const uint8_t *data, uint64_t len, uint64_t *out_len);
+int alice_codec_wide_info(const uint8_t *data, uint64_t len, AliceSplitInfo *info);
+/* device-resident: alice_codec_dev_encode_split / _dev_decode_split for version 3 (groups are sized at 2 bytes per
+ * symbol; ALICE_SPLIT_HEADER_BYTES + 3 * alice_codec_wide_stream_bound always suffices as out_stride) */
+int alice_codec_dev_encode_wide(const void *d_rgb, uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks,
+                                uint8_t wavelet_type, uint8_t quality, const uint8_t *qualities, uint32_t lane_symbols,
+                                void *d_out, uint64_t out_stride, uint64_t *sizes, void *hip_stream);
+int alice_codec_dev_decode_wide(const void *d_alc, uint64_t alc_stride, const uint64_t *sizes, uint32_t n_chunks,
+                                void *d_rgb_out, void *hip_stream);
+/* alice_codec_dev_forward_symbols with the wide symbol map: 3 * padded u16 symbols z (what alice_codec_encode_wide codes);
+ * d_hist (3*256 u32 or NULL) counts min(z, 255) */
+int alice_codec_dev_forward_symbols_wide(const void *d_rgb, uint32_t width, uint32_t height, uint32_t frames,
+                                         uint8_t wavelet_type, uint8_t quality, void *d_symbols, void *d_hist,
+                                         void *hip_stream);
+
 /* ---- version 2: size prediction, byte budgets, regions of device frames ----
  * Validation of every call below is host code and runs in this order before a device is looked for: NULL arguments,
  * dimensions (overflow, empty), buffer size / regions inside the frame, wavelet byte (ALICE_ERR_INVALID_BITSTREAM),

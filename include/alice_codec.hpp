@@ -590,6 +590,66 @@ inline void split_decode_device(const void* d_alc, uint64_t alc_stride, const st
                                 void* hip_stream = nullptr) {
     detail::check(alice_codec_dev_decode_split(d_alc, alc_stride, sizes.data(), static_cast<uint32_t>(sizes.size()), d_rgb_out, hip_stream));
 }
+// ---- wide format (.alc version 3) ----
+// Version 2 with an untruncated symbol (coded symbol min(z, 255), escape 255 + a 12-bit residual in the same lane chain): the
+// container for the top of the quality scale, where versions 1 and 2 wrap large coefficients modulo 256.  lane_symbols: a
+// power of two in [64, 8192].  The header fields are version 2's (SplitInfo); each parser refuses the other versions.
+constexpr uint32_t WIDE_MAX_LANE_SYMBOLS = 8192;
+inline SplitInfo wide_info(const uint8_t* data, size_t len) {
+    static const uint8_t empty = 0;
+    AliceSplitInfo c{};
+    detail::check(alice_codec_wide_info(data ? data : &empty, len, &c));
+    SplitInfo i;
+    i.width = c.width; i.height = c.height; i.frames = c.frames; i.lane_symbols = c.lane_symbols;
+    i.wavelet_type = static_cast<WaveletType>(c.wavelet);
+    for (int k = 0; k < 3; ++k) {
+        i.quant_step[k] = c.quant_step[k]; i.dead_zone[k] = c.dead_zone[k];
+        i.num_symbols[k] = c.num_symbols[k]; i.n_blocks[k] = c.n_blocks[k]; i.payload_len[k] = c.payload_len[k];
+    }
+    return i;
+}
+inline SplitInfo wide_info(const std::vector<uint8_t>& v) { return wide_info(v.data(), v.size()); }
+inline std::vector<uint8_t> encode_wide(const FrameEncoder& enc, const std::vector<uint8_t>& rgb, uint32_t w, uint32_t h, uint32_t f,
+                                        uint32_t lane_symbols = 0) {
+    static const uint8_t empty = 0;
+    uint64_t n = 0;
+    uint8_t* p = alice_codec_encode_wide(enc.handle(), rgb.empty() ? &empty : rgb.data(), rgb.size(), w, h, f, lane_symbols, &n);
+    if (!p) detail::raise();
+    return detail::take(p, n);
+}
+inline std::vector<uint8_t> decode_wide(const std::vector<uint8_t>& data) {
+    static const uint8_t empty = 0;
+    uint64_t n = 0;
+    uint8_t* p = alice_codec_decode_wide(data.empty() ? &empty : data.data(), data.size(), &n);
+    if (!p) detail::raise(ALICE_ERR_INVALID_BITSTREAM);
+    return detail::take(p, n);
+}
+inline uint64_t wide_stream_bound(uint64_t n, uint32_t lane_symbols = SPLIT_DEFAULT_LANE_SYMBOLS) {
+    return alice_codec_wide_stream_bound(n, lane_symbols);
+}
+inline std::vector<uint64_t> wide_encode_device(const void* d_rgb, uint32_t w, uint32_t h, uint32_t f, uint32_t n_chunks, WaveletType wt,
+                                                uint8_t quality, void* d_out, uint64_t out_stride,
+                                                const std::vector<uint8_t>& qualities = {}, uint32_t lane_symbols = 0,
+                                                void* hip_stream = nullptr) {
+    if (!qualities.empty() && qualities.size() != n_chunks) throw CodecError(ALICE_ERR_INVALID_BUFFER_SIZE, "one quality per chunk");
+    std::vector<uint64_t> sizes(n_chunks);
+    detail::check(alice_codec_dev_encode_wide(d_rgb, w, h, f, n_chunks, static_cast<uint8_t>(wt), quality,
+                                              qualities.empty() ? nullptr : qualities.data(), lane_symbols, d_out, out_stride,
+                                              sizes.data(), hip_stream));
+    return sizes;
+}
+inline void wide_decode_device(const void* d_alc, uint64_t alc_stride, const std::vector<uint64_t>& sizes, void* d_rgb_out,
+                               void* hip_stream = nullptr) {
+    detail::check(alice_codec_dev_decode_wide(d_alc, alc_stride, sizes.data(), static_cast<uint32_t>(sizes.size()), d_rgb_out, hip_stream));
+}
+// the RGB bytes of a container of any version: 1 (FrameDecoder), 2 (decode_split) or 3 (decode_wide)
+inline std::vector<uint8_t> decode_alc(const std::vector<uint8_t>& data) {
+    const int version = alc_version(data);
+    if (version == 2) return decode_split(data);
+    if (version == 3) return decode_wide(data);
+    return FrameDecoder::new_().decode(EncodedChunk::from_bytes(data));
+}
+
 // version 2 rate control: the bracket of encode_split's length at the 101 qualities (every version 2 table
 // is bounded: status stays ALICE_RATE_BOUNDED) and one encode at the quality the budget rule picks -- the largest whose
 // upper bound fits, refined by at most ALICE_SPLIT_REFINE_TRIALS exact size counts among the straddling qualities
