@@ -274,6 +274,7 @@ def load_library() -> C.CDLL:
                                                              C.c_uint32, C.c_uint8, C.c_uint32, _u64p, C.c_uint8, C.c_uint8, _u8p, _u8p,
                                                              vp, C.c_uint64, _u64p, vp]),
         "alice_codec_test_last_split_trials": (C.c_uint32, [_u32p, C.c_uint32]),
+        "alice_codec_test_inverse_variant": (C.c_int, [C.c_uint8, _i32p, C.c_int]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported

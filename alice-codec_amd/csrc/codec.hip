@@ -2800,6 +2800,11 @@ void alice_codec_test_rate_log_table(uint32_t lo[4097], uint32_t hi[4097], uint3
     if (hi) memcpy(hi, t.hi, sizeof(t.hi));
     if (g) { g[0] = t.g_up; g[1] = t.g_dn; }
 }
+int alice_codec_test_inverse_variant(uint8_t wavelet_type, const int32_t step[3], int wide) {
+    if (wavelet_type > 2 || !step) return -1;
+    const InverseBounds ib = inverse_bounds(wavelet_type, step, wide ? kWideMaxQ : kByteMaxQ);   // as inverse_chunk does
+    return inverse_variant(ib.exact, ib.mid16, ib.lds16);
+}
 int alice_codec_test_set_admission_budget(uint64_t bytes) {
     clear_error();
     TRY(ensure_device());

@@ -146,6 +146,9 @@ bool launch_forward_coef_hist(const RgbLayout& rgb, const ChunkDims& d, int wave
 // When the chunk is cut into bands the pixels of the first band are written while the symbols of later bands are still
 // unread: the pixels must not overlap d_sym then (an uncut chunk may decode over its own symbols).  Only the w x h x f
 // pixels of `rgb` are written: no byte between or beside the rows of a region.
+// The instance the flags select: 0 exact (wrapping i32 sums, 64-bit products), 1 fast i32 (24-bit multiply-adds, i32 band
+// slot), 2 fast with an i16 band slot and the lane-exchange tile, 3 fast with an i16 band slot and the packed i16 LDS tile.
+inline int inverse_variant(bool exact, bool mid16, bool lds16) { return exact ? 0 : (mid16 ? (lds16 ? 3 : 2) : 1); }
 bool launch_inverse_transform(const uint8_t* d_sym, const ChunkDims& d, int wavelet, const int32_t step[3],
                               bool exact, bool mid16, bool lds16, void* d_scratch, const RgbLayout& rgb, hipStream_t st);
 // The wide twins (.alc v3): the temporal passes write / read untruncated u16 symbols z (0, 2q - 1, -2q) and the histogram

@@ -1540,7 +1540,7 @@ static bool inverse_launches(const void* d_sym, const ChunkDims& d, int wavelet,
     // mid16: the host proved every value after the inverse temporal pass fits i16 (then exact is false too);
     // lds16: also after the inverse column pass (packed tile).
     // variant: 0 exact (i32), 1 fast i32, 2 fast i16 lane-exchange tile, 3 fast i16 packed tile
-    const int variant = exact ? 0 : (mid16 ? (lds16 ? 3 : 2) : 1);
+    const int variant = inverse_variant(exact, mid16, lds16);
     const BandPlan bp = plan_bands(d, I_TH, variant >= 2 ? sizeof(int16_t) : sizeof(int32_t), 4);
     const Coeffs cf = to_coeffs(ls);
     const unsigned nx = (d.w + I_TW - 1) / I_TW, ny = (d.h + I_TH - 1) / I_TH;   // tiles over the REAL frame (every pixel written exists)

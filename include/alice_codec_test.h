@@ -60,6 +60,14 @@ int alice_codec_test_chain_occupancy(uint32_t out[6]);
  * be NULL.  No device needed. */
 void alice_codec_test_rate_log_table(uint32_t lo[4097], uint32_t hi[4097], uint32_t g[2]);
 
+/* The instance of the inverse transform a decode picks for these quantiser steps (csrc/codec.hip, inverse_bounds, through
+ * the mapping the launcher itself uses, csrc/kernels.h inverse_variant): 0 = exact (wrapping i32 sums, 64-bit products),
+ * 1 = fast i32 (24-bit multiply-adds, i32 band slot), 2 = fast with an i16 band slot and the lane-exchange tile, 3 = fast
+ * with an i16 band slot and the packed i16 LDS tile; -1 for an unknown wavelet.  wide != 0: the symbols are those of
+ * version 3 (|q| <= 2175), else the u8 symbols of versions 1 and 2 (|q| <= 128).  Shapes the tile kernels do not cover
+ * run exact reference arithmetic whatever this says.  No device needed. */
+int alice_codec_test_inverse_variant(uint8_t wavelet_type, const int32_t step[3], int wide);
+
 /* The last version 2 budget call of the calling thread (alice_codec_encode_split_to_size,
  * alice_codec_dev_encode_split_to_budget): returns its number of chunks and writes the refinement trials (exact sizes
  * computed, at most ALICE_SPLIT_REFINE_TRIALS each) of the first min(that, cap) chunks to per_chunk (may be NULL). */
