@@ -2812,6 +2812,41 @@ int alice_codec_test_set_admission_budget(uint64_t bytes) {
     return kOk;
 }
 
+int alice_codec_test_decode_chains(uint32_t n_chains, const void* const* d_streams, const uint64_t* lens, const uint16_t* cum_freq,
+                                   const uint16_t* freq, void* const* d_symbols, uint64_t n, uint32_t* out, void* hip_stream) {
+    clear_error();
+    if (!n_chains || !d_streams || !lens || !cum_freq || !freq || !d_symbols || !out || !n) return fail(kNullArgument, "null argument");
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);
+    DevBuf dt, ddesc, dres;
+    TRY(dt.alloc((size_t)n_chains * (1024 + sizeof(RansTable))));   // every chain's (cum, freq) arrays, then the tables
+    TRY(ddesc.alloc((size_t)n_chains * sizeof(RansDecodeDesc)));
+    TRY(dres.alloc((size_t)n_chains * sizeof(RansResult)));
+    uint16_t* const arrays = dt.as<uint16_t>();
+    RansTable* const tables = (RansTable*)(dt.as<uint8_t>() + (size_t)n_chains * 1024);
+    HIP_TRY(hipMemcpy2DAsync(arrays, 1024, cum_freq, 512, 512, n_chains, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpy2DAsync(arrays + 256, 1024, freq, 512, 512, n_chains, hipMemcpyHostToDevice, st));
+    std::vector<RansDecodeDesc> descs(n_chains);
+    for (uint32_t c = 0; c < n_chains; ++c) {
+        launch_rans_table_from_arrays(arrays + 512 * (size_t)c, arrays + 512 * (size_t)c + 256, tables + c, st);
+        descs[c] = RansDecodeDesc{(const uint8_t*)d_streams[c], lens[c], (uint8_t*)d_symbols[c], n, tables + c, 0u, 0u, 0ull, nullptr};
+    }
+    HIP_TRY(hipMemcpyAsync(ddesc.p, descs.data(), descs.size() * sizeof(RansDecodeDesc), hipMemcpyHostToDevice, st));
+    launch_rans_decode(ddesc.as<RansDecodeDesc>(), dres.as<RansResult>(), (int)n_chains, st);
+    std::vector<RansResult> res(n_chains);
+    HIP_TRY(hipMemcpyAsync(res.data(), dres.p, res.size() * sizeof(RansResult), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (uint32_t c = 0; c < n_chains; ++c) {
+        out[4 * c] = (uint32_t)(res[c].len > 0xFFFFFFFFull ? 0xFFFFFFFFull : res[c].len);
+        out[4 * c + 1] = res[c].final_state;
+        out[4 * c + 2] = res[c].paths;
+        out[4 * c + 3] = res[c].fast_tiles;
+        if (res[c].flags & kRansInternal) return fail(kInternal, "rANS decode kernel invariant violated");
+    }
+    return kOk;
+}
+
 int alice_codec_test_chain_occupancy(uint32_t out[6]) {
     clear_error();
     if (!out) return fail(kNullArgument, "null argument");

@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
 """Generates rans_decode_tile.inc: the inline-asm body of the rANS decode fast tile (gfx950).
 
+    python gen_rans_decode_asm.py        writes ../rans_decode_tile.inc
+
+fast_tile() and dry_tile() return the instruction lists, so the program can be checked without a GPU
+(tests/test_decode_tile_model.py interprets them); main() writes the file.
+
 Costs measured on MI355X with scripts/probes/latency_probe.hip (one wave alone on its SIMD):
   any SALU or VALU instruction ~4 cycles; the first SALU instruction after a VALU instruction that wrote
   an SGPR (v_readlane) stalls ~20 cycles whatever it reads, while further VALU instructions do not;
@@ -10,13 +15,31 @@ v_writelane right behind them, inside the stall), no branch in the per-symbol co
 indexed by the leading-zero count), and the window refill test once per two symbols with the refill
 itself out of line.
 
+Slot budget: 11 issue slots per symbol + 3 per symbol pair = 12.5 per symbol (13 before the window carried its own fill
+level: the odd symbol's wait-state slot was a no-op and the pair tail had an add that only fed a valid-bit counter).
+Measured at 1011 chains (profiles/r09_decode_sentinel_window_ab.json): 38.16 ns per symbol instead of 38.93 / 38.92 (two runs
+of the 13-slot tile), rans_decode 5064.6 ms per step instead of 5166.3 / 5165.0; loop phase 0 mod 8: 5072.6 ms.
+
+The window.  s[62:63] holds V valid stream bits, left-aligned; directly below them one 1 bit, the sentinel; below that
+zeros.  V is a multiple of 8 (symbols consume 0, 8 or 16 bits, refills add 32).  Invariant at the start of every symbol
+pair: 32 <= V <= 63, so the upper dword s63 is all stream.  A pair consumes at most 24 bits (a 16-bit shift leaves the
+state at 2^27 or above, and the next symbol's state is then at least 2^15: 8 bits at the most), so V never drops below 8
+inside the tile; the sequences are nevertheless right down to V = 0.  After the pair's shifts the sentinel has moved into s63 exactly
+when V <= 31, which is when 32 more bits fit: the refill test is "s62 == 0".
+The refill.  The window dwords sit in v[192:224] with their top bit flipped (one v_xor per row at tile load), and
+s64 = 0x80000000 for the whole tile.  With q = ff1(s63) the sentinel's bit in s63 (V = 31 - q):
+    s[62:63] ^= {s64 : flipped dword} >> V
+The flipped top bit of the new dword lands on the sentinel and leaves the true stream bit there; the other 31 bits fall on
+zeros; the constant lower half supplies the new sentinel 32 bits further down.  Nine slots with the branch back (ten before).
+
 Register plan (all literal, all listed as clobbers by the including statement):
   v[64:127]   F'[slot] = freq << 20 (row = slot[11:6], lane = slot[5:0])
   v[128:191]  B'[slot] = slot - cum - ((freq * slot) >> 12), so that x' = umulhi(F', x) + B' = freq * (x >> 12) + slot - cum
-  v[192:224]  stream window, big-endian dwords (dword d in row d >> 6, lane d & 63)
+  v[192:224]  stream window, big-endian dwords, top bit flipped (dword d in row d >> 6, lane d & 63)
   v225        record: pre-update state of the 64 symbols of the current block
-  s[60:61]    {window copy : x} shift pair      s[62:63] 64-bit big-endian byte window      s[64:65] refill pair
-  s67 F'   s69 B'   s70 product   s71 shift   s72 valid window bits - 33   s73 next window dword
+  s[60:61]    {window copy : x} shift pair      s[62:63] 64-bit big-endian byte window with its sentinel
+  s[64:65]    refill pair {0x80000000 : new dword}      s[66:67] refill scratch pair (s67 is F' inside a symbol)
+  s67 F'   s69 B'   s70 product   s71 shift   s73 next window dword
   s74 blocks left   s75 byte-swap selector   s76 row   s77 shift of the odd symbol   s78 scratch
   s79..s99    renormalisation shift (0, 8 or 16) by count-leading-zeros of the state (0 .. 20: the updated state is at
               least 2^11).  Not s100 and up: the compiler keeps those for itself and ignores them in a clobber list.
@@ -33,156 +56,179 @@ import os
 
 WIN_ROWS = 33   # stream window: 33 VGPRs x 64 lanes x 4 B = 8448 bytes >= 2 * 4096 symbols + refill look-ahead
 REC = 192 + WIN_ROWS
-
-L = []
-def e(s): L.append(s)
-
 M0_SAVE = "s59"
+# Code placement: the block loop is pinned to a 64-byte boundary + LOOP_PHASE bytes (0 or 4).  Measured
+# (scripts/chain_probe.py): loop starts at 4 mod 8 bytes decode faster than starts at 0 mod 8, and without the pin the phase
+# is whatever the compiler-generated code in front of the asm statement happens to leave.  (The assembler pads with s_nop.)
+LOOP_PHASE = 4
 
-def table_loads(emit):
+
+def table_loads():
     """F' then B' (contiguous in RansDecSlots): 128 rows of 256 bytes, row r into v[64 + r], lane l <- dword 64 r + l.
     global_load's immediate offset is 13 bits signed, so the scalar base moves on every 16 rows (the address is read
     when the load issues)."""
-    emit(f"s_mov_b32 {M0_SAVE}, m0")
-    emit("s_mov_b64 s[64:65], %[tp]")
+    L = [f"s_mov_b32 {M0_SAVE}, m0", "s_mov_b64 s[64:65], %[tp]"]
     for r in range(128):
-        emit(f"global_load_dword v{64 + r}, %[l4], s[64:65] offset:{256 * (r % 16)}")
+        L.append(f"global_load_dword v{64 + r}, %[l4], s[64:65] offset:{256 * (r % 16)}")
         if r % 16 == 15 and r != 127:
-            emit("s_add_u32 s64, s64, 0x1000")
-            emit("s_addc_u32 s65, s65, 0")
+            L.append("s_add_u32 s64, s64, 0x1000")
+            L.append("s_addc_u32 s65, s65, 0")
+    return L
 
-table_loads(e)
-for r in range(WIN_ROWS):
-    e(f"ds_read_b32 v{192 + r}, %[wa] offset:{256 * r}")
-e("s_mov_b32 s75, 0x00010203")
-e("s_waitcnt vmcnt(0) lgkmcnt(0)")
-for r in range(WIN_ROWS):
-    e(f"v_perm_b32 v{192 + r}, v{192 + r}, v{192 + r}, s75")
-for c in range(21):
-    sh = 0 if c <= 8 else (8 if c <= 16 else 16)
-    e(f"s_mov_b32 s{79 + c}, {sh}")
-# scalar state: x, 64-bit window primed with two dwords
-e("s_mov_b32 s61, %[xi]")
-e("s_mov_b32 s74, %[nb]")
-e("s_lshr_b32 s73, %[pi], 2")
-e("s_and_b32 s71, %[pi], 3")
-e("s_lshl_b32 s71, s71, 3")
-e("s_lshr_b32 s76, s73, 6")
-e("s_set_gpr_idx_on s76, 0x1")
-e("s_nop 1")
-e("v_readlane_b32 s63, v192, s73")
-e("s_add_u32 s73, s73, 1")
-e("s_lshr_b32 s76, s73, 6")
-e("s_set_gpr_idx_on s76, 0x1")
-e("s_nop 1")
-e("v_readlane_b32 s62, v192, s73")
-e("s_add_u32 s73, s73, 1")
-e("s_lshl_b64 s[62:63], s[62:63], s71")
-e("s_sub_u32 s72, 31, s71")   # 64 - shift - 33
-# Code placement: the block loop is pinned to a 64-byte boundary + 4 bytes.  Measured (scripts/chain_probe.py): loop
-# starts at 4 mod 8 bytes decode 1.3 % faster than starts at 0 mod 8, and without the pin the phase is whatever the
-# compiler-generated code in front of the asm statement happens to leave.  (The assembler pads with s_nop.)
-e(".p2align 6")
-e("s_nop 0")
-e("2:")
-# s72 holds (valid window bits - 33): the borrow of the one subtraction per symbol pair is the refill condition
-# Symbols go in pairs.  At the start of a pair the window holds at least 33 valid bits, so its upper dword s63 is all
-# stream.  s60 takes a copy of it ONCE per pair: the even symbol's shift of {s60:s61} feeds the state and leaves
-# s60 = s63 << sh with 32 - sh >= 16 valid bits on top, enough for the odd symbol (a symbol consumes at most 16 bits);
-# the window itself is shifted once per pair by the sum of the two shifts, which the refill test needs anyway.
-# (Half an issue slot per symbol less than copying and shifting the window for every symbol.)
-for lane in range(64):
-    sh = "s77" if lane & 1 else "s71"
-    e("s_bfe_u32 s76, s61, 0x60006")
-    e("s_set_gpr_idx_on s76, 0x1")
-    e("v_readlane_b32 s67, v64, s61")
-    e("v_readlane_b32 s69, v128, s61")
-    e(f"v_writelane_b32 v{REC}, s61, {lane}")   # VALU work issues during the VALU->SALU stall; SALU work would not
-    e("s_mul_hi_u32 s70, s67, s61")
-    e("s_add_u32 s61, s70, s69")
-    e("s_flbit_i32_b32 m0, s61")
-    # one instruction must sit between the SALU write of M0 and s_movrels (wait state): the copy for the even symbol,
-    # a no-op for the odd one
-    e("s_mov_b32 s60, s63" if not lane & 1 else "s_nop 0")
-    e(f"s_movrels_b32 {sh}, s79")
-    e(f"s_lshl_b64 s[60:61], s[60:61], {sh}")
-    if lane & 1:
-        e("s_add_u32 s78, s71, s77")
-        e("s_lshl_b64 s[62:63], s[62:63], s78")
-        e("s_sub_u32 s72, s72, s78")            # SCC = borrow <=> fewer than 33 valid bits left
-        e(f"s_cbranch_scc1 3{lane:02d}f")
-        e(f"4{lane:02d}:")
-e("s_set_gpr_idx_off")
-e(f"ds_write_b16 %[ra], v{REC}")
-e("v_add_u32_e32 %[ra], 0x80, %[ra]")
-e("s_sub_u32 s74, s74, 1")
-e("s_cmp_lg_u32 s74, 0")
-e("s_cbranch_scc1 2b")
-e("s_branch 5f")
-for lane in range(1, 64, 2):   # out-of-line refills
-    e(f"3{lane:02d}:")
-    e("s_lshr_b32 s76, s73, 6")
-    e("s_set_gpr_idx_on s76, 0x1")
-    e("s_mov_b32 s64, 0")
-    e("v_readlane_b32 s65, v192, s73")
-    e("s_add_u32 s73, s73, 1")
-    e("s_add_u32 s78, s72, 33")                 # true number of valid bits (s72 has wrapped below zero)
-    e("s_lshr_b64 s[64:65], s[64:65], s78")
-    e("s_or_b64 s[62:63], s[62:63], s[64:65]")
-    e("s_add_u32 s72, s72, 32")
-    e(f"s_branch 4{lane:02d}b")
-e("5:")
-e("s_lshl_b32 s70, s73, 2")
-e("s_add_u32 s71, s72, 33")
-e("s_lshr_b32 s71, s71, 3")
-e("s_sub_u32 %[po], s70, s71")
-e("s_mov_b32 %[xo], s61")
-e("s_waitcnt lgkmcnt(0)")
-e(f"s_mov_b32 m0, {M0_SAVE}")
 
-# ---- "dry" tile: the stream is exhausted (pos >= len), so the reference's refill loop reads nothing any more
-# (src/rans.rs:365-368) and the state simply evolves: the same lookup and update, no window, no shift.
-D = []
-def d(s): D.append(s)
-table_loads(d)
-d("s_mov_b32 s61, %[xi]")
-d("s_mov_b32 s74, %[nb]")
-d("s_waitcnt vmcnt(0)")
-d(".p2align 6")
-d("s_nop 0")
-d("2:")
-for lane in range(64):
-    d("s_bfe_u32 s76, s61, 0x60006")
-    d("s_set_gpr_idx_on s76, 0x1")
-    d("v_readlane_b32 s67, v64, s61")
-    d("v_readlane_b32 s69, v128, s61")
-    d(f"v_writelane_b32 v{REC}, s61, {lane}")
-    d("s_mul_hi_u32 s70, s67, s61")
-    d("s_add_u32 s61, s70, s69")
-d("s_set_gpr_idx_off")
-d(f"ds_write_b16 %[ra], v{REC}")
-d("v_add_u32_e32 %[ra], 0x80, %[ra]")
-d("s_sub_u32 s74, s74, 1")
-d("s_cmp_lg_u32 s74, 0")
-d("s_cbranch_scc1 2b")
-d("s_mov_b32 %[xo], s61")
-d("s_waitcnt lgkmcnt(0)")
-d(f"s_mov_b32 m0, {M0_SAVE}")
-dry_clob = ["memory", "scc", "s59", "s61", "s64", "s65", "s67", "s69", "s70", "s74", "s76"] + [f"v{r}" for r in range(64, 192)] + [f"v{REC}"]
+def lookup_update(lane):
+    """The part of a symbol that the fast and the dry tile share: table lookup, record, state update."""
+    return ["s_bfe_u32 s76, s61, 0x60006",
+            "s_set_gpr_idx_on s76, 0x1",
+            "v_readlane_b32 s67, v64, s61",
+            "v_readlane_b32 s69, v128, s61",
+            f"v_writelane_b32 v{REC}, s61, {lane}",   # VALU work issues during the VALU->SALU stall; SALU work would not
+            "s_mul_hi_u32 s70, s67, s61",
+            "s_add_u32 s61, s70, s69"]
 
-clob = ["memory", "scc"] + [f"s{i}" for i in range(59, 79)] + [f"s{79 + c}" for c in range(21)]
-clob += [f"v{r}" for r in range(64, REC + 1)]
-out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "rans_decode_tile.inc")
-with open(out, "w") as f:
-    f.write("// GENERATED by gen/gen_rans_decode_asm.py -- do not edit.\n")
-    f.write("#define ALICE_DEC_TILE_ASM \\\n")
-    for s in L:
-        f.write(f'    "{s}\\n\\t" \\\n')
-    f.write('    ""\n')
-    f.write("#define ALICE_DEC_TILE_CLOBBERS " + ", ".join(f'"{c}"' for c in clob) + "\n")
-    f.write("#define ALICE_DEC_DRY_TILE_ASM \\\n")
-    for s in D:
-        f.write(f'    "{s}\\n\\t" \\\n')
-    f.write('    ""\n')
-    f.write("#define ALICE_DEC_DRY_TILE_CLOBBERS " + ", ".join(f'"{c}"' for c in dry_clob) + "\n")
-print("wrote", out, len(L), "asm lines")
+
+def block_end():
+    return ["s_set_gpr_idx_off",
+            f"ds_write_b16 %[ra], v{REC}",
+            "v_add_u32_e32 %[ra], 0x80, %[ra]",
+            "s_sub_u32 s74, s74, 1",
+            "s_cmp_lg_u32 s74, 0",
+            "s_cbranch_scc1 2b"]
+
+
+def loop_pin(phase):
+    assert phase in (0, 4)
+    return [".p2align 6"] + ["s_nop 0"] * (phase // 4) + ["2:"]
+
+
+def refill():
+    """Appends the next window dword below the V <= 31 valid bits (the sentinel is in s63).  Needs s64 = 0x80000000."""
+    return ["s_lshr_b32 s76, s73, 6",
+            "s_set_gpr_idx_on s76, 0x1",
+            "s_ff1_i32_b32 s78, s63",                   # the sentinel's bit in s63: 31 - V
+            "s_sub_u32 s78, 31, s78",                   # V
+            "v_readlane_b32 s65, v192, s73",
+            "s_add_u32 s73, s73, 1",
+            "s_lshr_b64 s[66:67], s[64:65], s78",       # into a scratch pair: s64 stays
+            "s_xor_b64 s[62:63], s[62:63], s[66:67]"]
+
+
+def fast_tile(loop_phase=LOOP_PHASE):
+    L = table_loads()
+    for r in range(WIN_ROWS):
+        L.append(f"ds_read_b32 v{192 + r}, %[wa] offset:{256 * r}")
+    L.append("s_mov_b32 s75, 0x00010203")
+    L.append("s_waitcnt vmcnt(0) lgkmcnt(0)")
+    for r in range(WIN_ROWS):
+        L.append(f"v_perm_b32 v{192 + r}, v{192 + r}, v{192 + r}, s75")
+    for r in range(WIN_ROWS):
+        L.append(f"v_xor_b32_e32 v{192 + r}, 0x80000000, v{192 + r}")   # see "The refill" above
+    for c in range(21):
+        sh = 0 if c <= 8 else (8 if c <= 16 else 16)
+        L.append(f"s_mov_b32 s{79 + c}, {sh}")
+    # scalar state: x, and the window primed with {first dword : sentinel} << 8 * (pos & 3); unless pos & 3 == 0 that
+    # leaves V = 32 - shift < 32 and one refill brings it to 64 - shift
+    L += ["s_mov_b32 s61, %[xi]",
+          "s_mov_b32 s74, %[nb]",
+          "s_mov_b32 s64, 0x80000000",
+          "s_lshr_b32 s73, %[pi], 2",
+          "s_and_b32 s71, %[pi], 3",
+          "s_lshl_b32 s71, s71, 3",
+          "s_lshr_b32 s76, s73, 6",
+          "s_set_gpr_idx_on s76, 0x1",
+          "s_nop 1",
+          "v_readlane_b32 s63, v192, s73",
+          "s_add_u32 s73, s73, 1",
+          "s_xor_b32 s63, s63, s64",                    # the true first dword
+          "s_mov_b32 s62, s64",
+          "s_lshl_b64 s[62:63], s[62:63], s71",
+          "s_cmp_eq_u32 s62, 0",
+          "s_cbranch_scc0 6f"]
+    L += refill()
+    L.append("6:")
+    L += loop_pin(loop_phase)
+    # Symbols go in pairs.  At the start of a pair the window holds at least 32 valid bits, so its upper dword s63 is all
+    # stream.  s60 takes a copy of it ONCE per pair: the even symbol's shift of {s60:s61} feeds the state and leaves
+    # s60 = s63 << sh with 32 - sh >= 16 valid bits on top, enough for the odd symbol (a symbol consumes at most 16 bits).
+    # The window itself is shifted by the even symbol's amount in the odd symbol's wait-state slot and by the odd symbol's
+    # amount in the pair tail.
+    for lane in range(64):
+        sh = "s77" if lane & 1 else "s71"
+        L += lookup_update(lane)
+        L.append("s_flbit_i32_b32 m0, s61")
+        # one instruction must sit between the SALU write of M0 and s_movrels (wait state): the copy for the even symbol,
+        # the window shift that the even symbol owes for the odd one (it touches neither M0 nor the table)
+        L.append("s_mov_b32 s60, s63" if not lane & 1 else "s_lshl_b64 s[62:63], s[62:63], s71")
+        L.append(f"s_movrels_b32 {sh}, s79")
+        L.append(f"s_lshl_b64 s[60:61], s[60:61], {sh}")
+        if lane & 1:
+            L.append("s_lshl_b64 s[62:63], s[62:63], s77")
+            L.append("s_cmp_eq_u32 s62, 0")             # the sentinel has left the lower dword <=> V <= 31
+            L.append(f"s_cbranch_scc1 3{lane:02d}f")
+            L.append(f"4{lane:02d}:")
+    L += block_end()
+    L.append("s_branch 5f")
+    for lane in range(1, 64, 2):   # out-of-line refills
+        L.append(f"3{lane:02d}:")
+        L += refill()
+        L.append(f"s_branch 4{lane:02d}b")
+    L += ["5:",
+          "s_ff1_i32_b64 s71, s[62:63]",                # 63 - V
+          "s_sub_u32 s71, 63, s71",
+          "s_lshr_b32 s71, s71, 3",                     # bytes read ahead of the decoder's position
+          "s_lshl_b32 s70, s73, 2",
+          "s_sub_u32 %[po], s70, s71",
+          "s_mov_b32 %[xo], s61",
+          "s_waitcnt lgkmcnt(0)",
+          f"s_mov_b32 m0, {M0_SAVE}"]
+    return L
+
+
+def dry_tile():
+    """The stream is exhausted (pos >= len), so the reference's refill loop reads nothing any more
+    (src/rans.rs:365-368) and the state simply evolves: the same lookup and update, no window, no shift."""
+    D = table_loads()
+    D += ["s_mov_b32 s61, %[xi]",
+          "s_mov_b32 s74, %[nb]",
+          "s_waitcnt vmcnt(0)"]
+    D += loop_pin(4)
+    for lane in range(64):
+        D += lookup_update(lane)
+    D += block_end()
+    D += ["s_mov_b32 %[xo], s61",
+          "s_waitcnt lgkmcnt(0)",
+          f"s_mov_b32 m0, {M0_SAVE}"]
+    return D
+
+
+def fast_clobbers():
+    return (["memory", "scc"] + [f"s{i}" for i in range(59, 79) if i != 72] + [f"s{79 + c}" for c in range(21)] +
+            [f"v{r}" for r in range(64, REC + 1)])
+
+
+def dry_clobbers():
+    return (["memory", "scc", "s59", "s61", "s64", "s65", "s67", "s69", "s70", "s74", "s76"] +
+            [f"v{r}" for r in range(64, 192)] + [f"v{REC}"])
+
+
+def render(loop_phase=LOOP_PHASE):
+    def macro(name, lines):
+        return f"#define {name} \\\n" + "".join(f'    "{s}\\n\\t" \\\n' for s in lines) + '    ""\n'
+
+    def clobbers(name, regs):
+        return f"#define {name} " + ", ".join(f'"{c}"' for c in regs) + "\n"
+
+    return ("// GENERATED by gen/gen_rans_decode_asm.py -- do not edit.\n" +
+            macro("ALICE_DEC_TILE_ASM", fast_tile(loop_phase)) + clobbers("ALICE_DEC_TILE_CLOBBERS", fast_clobbers()) +
+            macro("ALICE_DEC_DRY_TILE_ASM", dry_tile()) + clobbers("ALICE_DEC_DRY_TILE_CLOBBERS", dry_clobbers()))
+
+
+def main():
+    out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "rans_decode_tile.inc")
+    with open(out, "w") as f:
+        f.write(render())
+    print("wrote", out, len(fast_tile()), "asm lines")
+
+
+if __name__ == "__main__":
+    main()

@@ -759,8 +759,10 @@ void launch_rans_table_from_arrays(const uint16_t* d_cum, const uint16_t* d_freq
 // SIMD while another SIMD idles run at 0.7 / 1.0 of their speed to the end (measured: with 900 chains, 4 single-wave
 // workgroups per CU, a tenth of the SIMDs hosted two encoder waves).  Up to 1024 chains the kernels therefore claim more
 // than half of a SIMD's register file, which leaves the dispatcher no choice but one chain per SIMD.  Beyond that two
-// chains per SIMD are wanted (together they run at about 1.5x the rate of one); dynamic LDS that the kernels never touch
-// then caps the workgroups per CU at 8 so that the surplus spreads over all CUs.
+// chains per SIMD cannot be avoided; they buy little (measured in round 3, see chain_take_turns above and DESIGN section
+// 4.3: encoders +7 %, decoders -2 % and worse, because eight decoders on a CU saturate its one scalar unit -- not the
+// "1.5x the rate of one" this comment used to promise).  Dynamic LDS that the kernels never touch then caps the workgroups
+// per CU at 8 so that the surplus spreads over all CUs.
 // ALICE_CHAIN_TURNS=1 switches the priority alternation of shared SIMDs on (developer A/B, scripts/chain_probe.py)
 static uint32_t chain_turns_enabled() {
     static const uint32_t on = [] { const char* v = getenv("ALICE_CHAIN_TURNS"); return (v && *v == '1') ? 1u : 0u; }();

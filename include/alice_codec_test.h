@@ -20,6 +20,14 @@ void alice_codec_test_force_first_cap(uint64_t cap);
  * consumed. */
 void alice_codec_test_last_decode_stats(uint32_t out[4]);
 
+/* ONE launch of n_chains decode chains on device buffers (csrc/rans.hip, launch_rans_decode), each with a table of its own
+ * given as arrays: chain c decodes n symbols from d_streams[c] (lens[c] bytes, any byte alignment) with
+ * cum_freq[256 c ..] / freq[256 c ..] into d_symbols[c].  out[4 c ..] = stream bytes consumed (RansResult.len, saturated
+ * to 32 bits), final state, mask of tile-loop branches (kDecPath*), tiles taken by the fast path. */
+int alice_codec_test_decode_chains(uint32_t n_chains, const void *const *d_streams, const uint64_t *lens,
+                                   const uint16_t *cum_freq, const uint16_t *freq, void *const *d_symbols, uint64_t n,
+                                   uint32_t *out, void *hip_stream);
+
 /* Times the transform launches alone (no chains) with HIP events on `hip_stream`: `reps` passes over `n_chunks` chunks
  * of w x h x f pixels, forward (RGB -> symbols + histograms) and inverse (symbols -> RGB), through the same pipes the
  * encode / decode of a batch use.  Device buffers: d_rgb and d_rgb_out hold n_buffers chunks of RGB, d_sym n_buffers

@@ -76,6 +76,7 @@ for B in counts:
                   f"cycles/sym median {np.median(cyc) * 1e6 / px:.1f}, on shared SIMDs {cyc[shared].mean() * 1e6 / px if shared.any() else 0:.1f}")
     print(f"chunks {B:4d} chains {3 * B:5d}: encode {ms_e['rans_encode'] / px * 1e6:6.2f} ns/sym  decode {ms['rans_decode'] / px * 1e6:6.2f} ns/sym | "
           f"encoder cycles/sym mean {mc.mean() * 1e6 / px:5.1f} max {mc.max() * 1e6 / px:5.1f}  clock mean {ghz.mean():.2f} min {ghz.min():.2f} GHz | "
+          f"decoder cycles/sym median {np.median(dmc) * 1e6 / px:6.2f} max {dmc.max() * 1e6 / px:6.2f} | "
           f"aggregate enc {3 * B * px / ms_e['rans_encode'] / 1e3:7.0f} dec {3 * B * px / ms['rans_decode'] / 1e3:7.0f} Msym/s", flush=True)
     del bt, rgb
     a.load_library().alice_codec_trim()
