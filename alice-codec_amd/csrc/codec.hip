@@ -2752,9 +2752,15 @@ int alice_codec_dev_rans_encode(const void* d_symbols, uint64_t n, const uint32_
     hipStream_t st = (hipStream_t)hip_stream;
     ScopeStream scope(st);   // temporaries drain the caller's stream before they return to the pool
     DevBuf dh, dt, dres;
-    TRY(dh.alloc(256 * 4)); TRY(dt.alloc(sizeof(RansTable))); TRY(dres.alloc(sizeof(RansResult)));
+    TRY(dh.alloc(2 * 256 * 4)); TRY(dt.alloc(sizeof(RansTable))); TRY(dres.alloc(sizeof(RansResult)));
     HIP_TRY(hipMemcpyAsync(dh.p, hist, 256 * 4, hipMemcpyHostToDevice, st));
-    launch_rans_table(dh.as<uint32_t>(), dt.as<RansTable>(), 1, st);
+    // `hist` is the caller's word: the table is built from it, but which of its entries the chain will meet is counted
+    // from the symbols themselves (one pass, nothing next to a serial chain).  A table flagged clean on the strength of a
+    // histogram that is not the data's would send a symbol of frequency 0 or above 4096 through the one-compare step.
+    uint32_t* const d_used = dh.as<uint32_t>() + 256;
+    HIP_TRY(hipMemsetAsync(d_used, 0, 256 * 4, st));
+    if (n) launch_histogram((const uint8_t*)d_symbols, n, d_used, st);
+    launch_rans_table(dh.as<uint32_t>(), dt.as<RansTable>(), 1, st, 256, d_used);
     launch_rans_encode((const uint8_t*)d_symbols, n, n, dt.as<RansTable>(), (uint8_t*)d_out, cap, dres.as<RansResult>(), 1, st);
     RansResult res{};
     HIP_TRY(hipMemcpyAsync(&res, dres.p, sizeof(res), hipMemcpyDeviceToHost, st));
@@ -2843,6 +2849,52 @@ int alice_codec_test_decode_chains(uint32_t n_chains, const void* const* d_strea
         out[4 * c + 2] = res[c].paths;
         out[4 * c + 3] = res[c].fast_tiles;
         if (res[c].flags & kRansInternal) return fail(kInternal, "rANS decode kernel invariant violated");
+    }
+    return kOk;
+}
+
+int alice_codec_test_encode_chains(uint32_t n_chains, const void* const* d_symbols, const uint64_t* ns, const uint32_t* hists,
+                                   const uint16_t* cum_freq, const uint16_t* freq, void* const* d_regions, const uint64_t* caps,
+                                   const uint32_t* x_init, const uint32_t* keep_open, uint32_t* out, void* hip_stream) {
+    clear_error();
+    if (!n_chains || !d_symbols || !ns || (!hists && (!cum_freq || !freq)) || !d_regions || !caps || !out) return fail(kNullArgument, "null argument");
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);
+    DevBuf dt, ddesc, dres;
+    TRY(dt.alloc((size_t)n_chains * (1024 + sizeof(RansTable))));   // every chain's histogram or (cum, freq) arrays, then the tables
+    TRY(ddesc.alloc((size_t)n_chains * sizeof(RansEncodeDesc)));
+    TRY(dres.alloc((size_t)n_chains * sizeof(RansResult)));
+    RansTable* const tables = (RansTable*)(dt.as<uint8_t>() + (size_t)n_chains * 1024);
+    if (hists) {
+        HIP_TRY(hipMemcpyAsync(dt.p, hists, (size_t)n_chains * 1024, hipMemcpyHostToDevice, st));
+        launch_rans_table(dt.as<uint32_t>(), tables, (int)n_chains, st);
+    } else {
+        uint16_t* const arrays = dt.as<uint16_t>();
+        HIP_TRY(hipMemcpy2DAsync(arrays, 1024, cum_freq, 512, 512, n_chains, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpy2DAsync(arrays + 256, 1024, freq, 512, 512, n_chains, hipMemcpyHostToDevice, st));
+        for (uint32_t c = 0; c < n_chains; ++c)
+            launch_rans_table_from_arrays(arrays + 512 * (size_t)c, arrays + 512 * (size_t)c + 256, tables + c, st);
+    }
+    std::vector<RansEncodeDesc> descs(n_chains);
+    for (uint32_t c = 0; c < n_chains; ++c) {
+        if ((!d_symbols[c] && ns[c]) || !d_regions[c]) return fail(kNullArgument, "null argument");
+        descs[c] = RansEncodeDesc{(const uint8_t*)d_symbols[c], ns[c], tables + c, (uint8_t*)d_regions[c], caps[c], dres.as<RansResult>() + c,
+                                  x_init ? x_init[c] : kRansL, keep_open ? keep_open[c] : 0u};
+    }
+    HIP_TRY(hipMemcpyAsync(ddesc.p, descs.data(), descs.size() * sizeof(RansEncodeDesc), hipMemcpyHostToDevice, st));
+    launch_rans_encode_descs(ddesc.as<RansEncodeDesc>(), (int)n_chains, st);
+    HIP_TRY(hipGetLastError());
+    std::vector<RansResult> res(n_chains);
+    HIP_TRY(hipMemcpyAsync(res.data(), dres.p, res.size() * sizeof(RansResult), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (uint32_t c = 0; c < n_chains; ++c) {
+        out[6 * c] = (uint32_t)(res[c].len > 0xFFFFFFFFull ? 0xFFFFFFFFull : res[c].len);
+        out[6 * c + 1] = res[c].final_state;
+        out[6 * c + 2] = res[c].flags;
+        out[6 * c + 3] = res[c].paths;
+        out[6 * c + 4] = res[c].fast_tiles;
+        out[6 * c + 5] = res[c].slow_tiles;
     }
     return kOk;
 }

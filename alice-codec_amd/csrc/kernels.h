@@ -13,12 +13,12 @@ struct RansResult {
     uint32_t flags;
     uint32_t final_state;
     uint32_t fast_tiles;      // decode: tiles taken by the scalar fast path / by the exact lane loop
-    uint32_t slow_tiles;
+    uint32_t slow_tiles;      // encode: tiles taken by the one-compare clean path / block by block
     // diagnostics (ALICE_CODEC_DEBUG): shader cycles and 100 MHz ticks the chain took (kibi-units), where it ran
     uint32_t cycles_k, ticks_k;
     uint32_t hw_id;           // HW_REG_HW_ID: wave [3:0], SIMD [5:4], pipe [7:6], CU [11:8], SH [12], SE [15:13]
     uint32_t xcc_id;          // HW_REG_XCC_ID [3:0]
-    uint32_t paths;           // decode: which branches of the tile loop ran (kDecPath*), for the test-suite's coverage check
+    uint32_t paths;           // which branches of the tile loop ran (decode: kDecPath*, encode: kEncPath*), for the test-suite's coverage check
     uint32_t pad_;
 };
 
@@ -33,6 +33,16 @@ constexpr uint32_t kDecPathTail = 128u;       // last tile of fewer than 4096 sy
 constexpr uint32_t kDecPathUnaligned = 256u;  // output not dword aligned
 constexpr uint32_t kDecPathBelowL = 512u;     // fast tile refused: state below 2^23 with no renormalisation owed
 constexpr uint32_t kDecPathStillStarved = 1024u;  // fast tile refused: the owed renormalisation could not reach 2^23
+
+constexpr uint32_t kEncPathClean = 1u;         // full tile through the one-compare step (ripple64_clean)
+constexpr uint32_t kEncPathCapRefused = 2u;    // full tile of a clean chain block by block: no room for a tile's worst case
+constexpr uint32_t kEncPathNotClean = 4u;      // full tile block by block: table not verified clean, or a start state other than 2^23
+constexpr uint32_t kEncPathTail = 8u;          // first tile of fewer than 1024 symbols (the chain runs back to front)
+constexpr uint32_t kEncPathExact = 16u;        // exact serial block: a frequency of 0 or above 4096 in use
+constexpr uint32_t kEncPathNoRoom = 32u;       // a block's bytes or the four state bytes refused for lack of room
+constexpr uint32_t kEncPathFunnel = 64u;       // symbols not dword aligned: five-dword funnel shift
+constexpr uint32_t kEncPathBytewiseEnd = 128u; // ... within 20 bytes of the end of the symbols: byte loads
+constexpr uint32_t kEncPathBytewiseHead = 256u;  // lane's 16 bytes start before symbol 0 (tail tile): byte loads
 
 struct RansDecodeDesc {
     const uint8_t* in;        // channel stream
@@ -65,7 +75,11 @@ struct RansEncodeDesc {
 // ---- rans.hip ----
 // n_symbols <= 256: length of the histogram slice (FrequencyTable::from_histogram(&[u32]), src/rans.rs:102-104); bins from
 // n_symbols on are ignored and the symbols do not exist in the table (freq 0)
-void launch_rans_table(const uint32_t* d_hist, RansTable* d_tables, int n_chains, hipStream_t st, uint32_t n_symbols = 256);
+// d_used (256 counts per chain, or null = d_hist): the histogram of the symbols the encoder will really see.  The table is
+// d_hist's; the flags that let the encode chain skip its per-block table check (kTableVerified and its two companions)
+// are d_used's.  For a histogram that is the caller's word, not a count of the data.
+void launch_rans_table(const uint32_t* d_hist, RansTable* d_tables, int n_chains, hipStream_t st, uint32_t n_symbols = 256,
+                       const uint32_t* d_used = nullptr);
 void launch_rans_table_from_arrays(const uint16_t* d_cum, const uint16_t* d_freq, RansTable* d_table,
                                    hipStream_t st);
 // chain c reads sym + c*sym_stride (n symbols) and writes its stream back-to-front into a cap-sized region;

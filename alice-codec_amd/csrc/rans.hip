@@ -108,8 +108,12 @@ __device__ inline uint32_t build_dec_slots(uint32_t f, uint32_t c, uint32_t* scr
     return fl;
 }
 
+// used (may be null): the histogram of the symbols that will be encoded, where that is not `hist` itself -- a caller's
+// histogram need not be its data's.  kTableVerified promises that the generic / diverges flags speak for the DATA, so
+// they are taken from `used`; the table comes from `hist` either way.
 __global__ __launch_bounds__(256) void rans_table_kernel(const uint32_t* __restrict__ hist,
-                                                         RansTable* __restrict__ tables, uint32_t n_sym) {
+                                                         RansTable* __restrict__ tables, uint32_t n_sym,
+                                                         const uint32_t* __restrict__ used) {
     __shared__ uint32_t scratch[768];
     const int chain = blockIdx.x;
     const int s = threadIdx.x;
@@ -118,8 +122,9 @@ __global__ __launch_bounds__(256) void rans_table_kernel(const uint32_t* __restr
     freq_table_256(count, n_sym, scratch, f, c);
     tables[chain].enc[s] = make_enc_entry(f, c);
     uint32_t fl = build_dec_slots(f, c, scratch, &tables[chain].dec);
-    if (count > 0u && f == 0u) fl |= kTableDiverges;
-    if (count > 0u && f > kProbScale) fl |= kTableNeedsGeneric;
+    const uint32_t occurs = used ? used[(size_t)chain * 256 + s] : count;
+    if (occurs > 0u && f == 0u) fl |= kTableDiverges;
+    if (occurs > 0u && f > kProbScale) fl |= kTableNeedsGeneric;
     __shared__ uint32_t flags_sh;
     if (s == 0) flags_sh = 0u;
     __syncthreads();
@@ -295,6 +300,10 @@ __global__ __launch_bounds__(64) void rans_encode_kernel(const uint8_t* __restri
     const unsigned long long clk0 = clock64(), rt0 = wall_clock64();
     unsigned long long written = 0ull;
     uint32_t flags = 0u;
+    // which branches ran (kEncPath*): counted and marked only off the clean tile and the aligned load; the clean tiles
+    // are what is left at the end.  load_paths is per lane (a tail tile's lanes take different load branches).
+    uint32_t paths = 0u, load_paths = 0u, slow_tiles = 0u;
+    asm volatile("" : "+v"(load_paths));   // zeroed here, once: otherwise every load branch of the first tile, the aligned one included, zeroes it
 
     const unsigned long long ntiles = (n + kEncTile - 1) / kEncTile;
     // tile j covers symbol indices [hi - 1024, hi), hi = n - j*1024 (clipped at 0)
@@ -312,12 +321,14 @@ __global__ __launch_bounds__(64) void rans_encode_kernel(const uint8_t* __restri
             } else if (lo + 20 <= (long long)n || mis == 0u) {
                 const uint32_t t0 = p4[0], t1 = p4[1], t2 = p4[2], t3 = p4[3], t4 = p4[4];
                 const uint32_t sh = mis * 8u;
+                load_paths |= kEncPathFunnel;
                 v = make_uint4((t0 >> sh) | (t1 << (32u - sh)), (t1 >> sh) | (t2 << (32u - sh)),
                                (t2 >> sh) | (t3 << (32u - sh)), (t3 >> sh) | (t4 << (32u - sh)));
             } else {
                 uint32_t w[4] = {0u, 0u, 0u, 0u};
                 for (int b = 0; b < 16; ++b) w[b >> 2] |= (uint32_t)p[b] << (8 * (b & 3));
                 v = make_uint4(w[0], w[1], w[2], w[3]);
+                load_paths |= kEncPathBytewiseEnd;
             }
         } else {
             uint32_t w[4] = {0u, 0u, 0u, 0u};
@@ -326,6 +337,7 @@ __global__ __launch_bounds__(64) void rans_encode_kernel(const uint8_t* __restri
                 if (idx >= 0) w[b >> 2] |= (uint32_t)sym[idx] << (8 * (b & 3));
             }
             v = make_uint4(w[0], w[1], w[2], w[3]);
+            load_paths |= kEncPathBytewiseHead;
         }
         return v;
     };
@@ -385,6 +397,8 @@ __global__ __launch_bounds__(64) void rans_encode_kernel(const uint8_t* __restri
             x = (uint32_t)__builtin_amdgcn_readlane((int)xin, 0);
             continue;
         }
+        slow_tiles += 1u;
+        paths |= valid < kEncTile ? kEncPathTail : (table_clean ? kEncPathCapRefused : kEncPathNotClean);
         for (int b = 0; b < nblocks; ++b) {
             const BlockParams curp = nxt;
             nxt = params_of(sym1);
@@ -409,6 +423,7 @@ __global__ __launch_bounds__(64) void rans_encode_kernel(const uint8_t* __restri
                     (uint32_t)__builtin_amdgcn_readlane((int)cbias, 63);
             } else {
                 // exact serial path (a table entry outside 1..4096 is in use): true division
+                paths |= kEncPathExact;
                 uint32_t xs = x;
                 for (int i = 0; i < 64; ++i) {
                     if (lane == i) xin = xs;
@@ -436,6 +451,7 @@ __global__ __launch_bounds__(64) void rans_encode_kernel(const uint8_t* __restri
             const uint32_t total = (uint32_t)__popcll(b1) + (uint32_t)__popcll(b2);
             const bool room = written + total + 4ull + 64ull <= cap;  // uniform
             flags |= room ? 0u : kRansOverflow;
+            paths |= room ? 0u : kEncPathNoRoom;
             uint8_t* p = out_end - 1 - (written + off);
             uint8_t* p0 = (c1 && room) ? p : dummy;
             uint8_t* p1 = (c2 && room) ? p - 1 : dummy;
@@ -452,15 +468,21 @@ __global__ __launch_bounds__(64) void rans_encode_kernel(const uint8_t* __restri
             if (lane < 4) out_end[-1 - (long long)(written + lane)] = (uint8_t)((x >> (8 * lane)) & 0xFFu);
         } else {
             flags |= kRansOverflow;
+            paths |= kEncPathNoRoom;
         }
         written += 4ull;
     }
+    for (uint32_t bit = kEncPathFunnel; bit <= kEncPathBytewiseHead; bit <<= 1)
+        paths |= __ballot((load_paths & bit) != 0u) ? bit : 0u;
+    const uint32_t clean_tiles = (uint32_t)ntiles - slow_tiles;
+    paths |= clean_tiles ? kEncPathClean : 0u;
     if (lane == 0) {
         res->len = written;
         res->flags = flags;
         res->final_state = x;
-        res->fast_tiles = 0u;
-        res->slow_tiles = 0u;
+        res->fast_tiles = clean_tiles;
+        res->slow_tiles = slow_tiles;
+        res->paths = paths;
         res->cycles_k = (uint32_t)((clock64() - clk0) >> 10);
         res->ticks_k = (uint32_t)((wall_clock64() - rt0) >> 10);
         res->hw_id = __builtin_amdgcn_s_getreg((31 << 11) | 4);
@@ -745,9 +767,10 @@ __global__ __launch_bounds__(64) void rans_decode_kernel(const RansDecodeDesc* _
 // launchers
 // ----------------------------------------------------------------------------------
 
-void launch_rans_table(const uint32_t* d_hist, RansTable* d_tables, int n_chains, hipStream_t st, uint32_t n_symbols) {
+void launch_rans_table(const uint32_t* d_hist, RansTable* d_tables, int n_chains, hipStream_t st, uint32_t n_symbols,
+                       const uint32_t* d_used) {
     if (n_chains <= 0) return;
-    hipLaunchKernelGGL(rans_table_kernel, dim3(n_chains), dim3(256), 0, st, d_hist, d_tables, n_symbols);
+    hipLaunchKernelGGL(rans_table_kernel, dim3(n_chains), dim3(256), 0, st, d_hist, d_tables, n_symbols, d_used);
 }
 
 void launch_rans_table_from_arrays(const uint16_t* d_cum, const uint16_t* d_freq, RansTable* d_table,

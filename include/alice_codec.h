@@ -335,10 +335,17 @@ int alice_codec_dev_wavelet3d_inverse(uint8_t wavelet_type, void *d_volume, void
                                       uint64_t depth, void *hip_stream);
 /* build_histogram (src/quant.rs:587-600) of n device symbols -> d_hist[256] (u32, device) */
 int alice_codec_dev_histogram(const void *d_symbols, uint64_t n, void *d_hist, void *hip_stream);
-/* capacity that alice_codec_dev_rans_encode needs for n symbols with this histogram (NULL: worst case) */
+/* capacity that alice_codec_dev_rans_encode needs for n symbols whose histogram this is (NULL: worst case, right for any
+ * symbols and any table): the stream's length plus 64 bytes the encode chain keeps free at the front of the region */
 uint64_t alice_codec_rans_stream_bound(const uint32_t hist[256], uint64_t n);
 /* FrequencyTable::from_histogram(hist) + RansEncoder over n device symbols (src/pipeline.rs:479-484): the
- * stream is written at the END of [d_out, d_out + cap): bytes [*out_offset, *out_offset + *out_len). */
+ * stream is written at the END of [d_out, d_out + cap): bytes [*out_offset, *out_offset + *out_len).  d_symbols and d_out
+ * may have any byte alignment.  `hist` need not be the histogram of these symbols: the table is from_histogram(hist)
+ * whatever the symbols are, and the call counts the symbols itself (32-bit counts: n < 2^32, or no symbol that occurs an
+ * exact multiple of 2^32 times) to learn which table entries they use.  A symbol whose
+ * frequency there is above 4096 (the wrapped freq[255] of src/rans.rs:125-131) is encoded exactly as the reference
+ * encodes it; one whose frequency is 0 has no encoding (the reference does not terminate): ReferenceDiverges.  A region
+ * that is too small returns InvalidBufferSize and leaves every byte outside [d_out, d_out + cap) alone. */
 int alice_codec_dev_rans_encode(const void *d_symbols, uint64_t n, const uint32_t hist[256], void *d_out,
                                 uint64_t cap, uint64_t *out_offset, uint64_t *out_len, void *hip_stream);
 /* RansDecoder::new(stream).decode_n(n, from_histogram(hist)) (src/pipeline.rs:585-594) into device memory */

@@ -28,6 +28,20 @@ int alice_codec_test_decode_chains(uint32_t n_chains, const void *const *d_strea
                                    const uint16_t *cum_freq, const uint16_t *freq, void *const *d_symbols, uint64_t n,
                                    uint32_t *out, void *hip_stream);
 
+/* ONE launch of n_chains encode chains on device buffers (csrc/rans.hip, launch_rans_encode_descs: up to 1024 chains run
+ * the one-chain-per-SIMD instance of the kernel, more run the plain one).  Chain c encodes the ns[c] symbols at d_symbols[c]
+ * (any byte alignment) back to front into [d_regions[c], d_regions[c] + caps[c]); its stream is the LAST len bytes of that
+ * region.  Tables: hists != NULL gives 256 counts per chain and the table the kernel builds from a histogram, flagged as
+ * verified against the data (so the counts must be the data's own, or at least cover it); hists == NULL takes
+ * cum_freq[256 c ..] / freq[256 c ..] as they are.  x_init / keep_open (NULL: 2^23 / 0 for every chain): the state a
+ * RansEncoder object brings along, and whether it stays open (the four state bytes of finish() are not written and do not
+ * count in len).  No retry and no error mapping: out[6 c ..] = len (saturated to 32 bits), final state, RansResult.flags
+ * (kRansOverflow, kTableDiverges, ...), mask of branches that ran (kEncPath* in csrc/kernels.h), tiles taken by the
+ * one-compare clean path, tiles taken block by block. */
+int alice_codec_test_encode_chains(uint32_t n_chains, const void *const *d_symbols, const uint64_t *ns, const uint32_t *hists,
+                                   const uint16_t *cum_freq, const uint16_t *freq, void *const *d_regions, const uint64_t *caps,
+                                   const uint32_t *x_init, const uint32_t *keep_open, uint32_t *out, void *hip_stream);
+
 /* Times the transform launches alone (no chains) with HIP events on `hip_stream`: `reps` passes over `n_chunks` chunks
  * of w x h x f pixels, forward (RGB -> symbols + histograms) and inverse (symbols -> RGB), through the same pipes the
  * encode / decode of a batch use.  Device buffers: d_rgb and d_rgb_out hold n_buffers chunks of RGB, d_sym n_buffers

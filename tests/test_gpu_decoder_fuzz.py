@@ -5,9 +5,14 @@ dry-stream tile, the exact scalar-lane loop (tail tiles, starved states, tables 
 unaligned buffers.  Every case has at least three 4096-symbol tiles.  The path mask the kernel reports
 (alice_codec_test_last_decode_stats) must show that every branch ran at least once."""
 import ctypes as C
+import os
+import sys
 
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from rans_tables import custom_oracle_table as _custom_oracle_table  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -86,22 +91,6 @@ def test_decoder_fuzz_histogram_tables(gpu_codec, oracle_mod):
     assert n_cases >= 300
     missing = [name for bit, name in PATHS.items() if bit != 256 and not seen & bit]
     assert not missing, f"tile-loop branches never taken by the fuzz set: {missing} (mask {seen:#x})"
-
-
-def _custom_oracle_table(oracle_mod, cum, freq):
-    """The oracle's table struct filled by hand the way FrequencyTable::from_histogram fills cum_to_sym
-    (src/rans.rs:135-144: zeroed, then symbol by symbol over [cum, min(cum + freq, 4096)), later symbols overwrite)."""
-    t = oracle_mod.FrequencyTable(np.ones(256, np.uint32))
-    c2s = np.zeros(4096, np.uint8)
-    for s in range(256):
-        t._t.cum_freq[s] = int(cum[s])
-        t._t.freq[s] = int(freq[s])
-        lo, hi = int(cum[s]), min(int(cum[s]) + int(freq[s]), 4096)
-        if lo < hi:
-            c2s[lo:hi] = s
-    for k in range(4096):
-        t._t.cum_to_sym[k] = int(c2s[k])
-    return t
 
 
 def test_decoder_fuzz_caller_tables(gpu_codec, oracle_mod):
