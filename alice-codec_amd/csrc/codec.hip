@@ -3798,8 +3798,25 @@ static int stage_split_encode(const void* d_symbols, uint64_t n, const uint32_t 
     hipStream_t st = (hipStream_t)hip_stream;
     ScopeStream scope(st);
     DevBuf dh;
-    TRY(dh.alloc(256 * 4));
+    TRY(dh.alloc(2 * 256 * 4));
     HIP_TRY(hipMemcpyAsync(dh.p, hist, 256 * 4, hipMemcpyHostToDevice, st));
+    // `hist` is the caller's word: the table is normalize(hist) whatever the symbols are, so which of its rows the lanes
+    // will meet is counted from the symbols themselves (one pass, nothing inside the lane loop).  A row of frequency 0
+    // is the identity step: the count pass and the write pass would both drop the symbol and agree on a payload that
+    // decodes to other data.  n < 2^32, so the u32 counts do not wrap.
+    uint32_t* const d_used = dh.as<uint32_t>() + 256;
+    HIP_TRY(hipMemsetAsync(d_used, 0, 256 * 4, st));
+    if (wide) launch_histogram_wide((const uint16_t*)d_symbols, n, d_used, st);
+    else launch_histogram((const uint8_t*)d_symbols, n, d_used, st);
+    HIP_TRY(hipGetLastError());
+    uint32_t used[256];
+    HIP_TRY(hipMemcpyAsync(used, d_used, sizeof(used), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int s = 0; s < 256; ++s)
+        if (used[s] && !hist[s])
+            return fail(kInvalidBufferSize, "hist[" + std::to_string(s) + "] is 0 but the data holds symbol " + std::to_string(s) +
+                                                " (count " + std::to_string(used[s]) + ")" +
+                                                (wide && s == 255 ? ": 255 is the escape, every z >= 255" : ""));
     SplitWork w;
     TRY(split_work_alloc(w, 1, n, lane_symbols, true, wide));
     w.h[0].sym = (const uint8_t*)d_symbols;

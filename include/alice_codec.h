@@ -417,8 +417,12 @@ uint64_t alice_codec_split_stream_bound(uint64_t n, uint32_t lane_symbols);
  * computed by the table kernel */
 int alice_codec_split_normalize(const uint32_t hist[256], uint16_t freq[256]);
 /* n device symbols with histogram hist (it must count exactly n symbols) -> the channel payload (block lengths, then per
- * block the lane directory and the lane streams) at d_out[0 .. *out_len).  cap below what the stream needs is
- * ALICE_ERR_INVALID_BUFFER_SIZE with nothing written.  Finished on return. */
+ * block the lane directory and the lane streams) at d_out[0 .. *out_len).  `hist` need not be the histogram of these
+ * symbols: the table is normalize(hist) whatever the symbols are, and the call counts the symbols itself to learn which
+ * table entries they use.  A symbol that occurs while hist[s] == 0 has frequency 0 and no encoding:
+ * ALICE_ERR_INVALID_BUFFER_SIZE (the message names the first such symbol and how often it occurs), *out_len = 0 and
+ * nothing written.  cap below what the stream needs is ALICE_ERR_INVALID_BUFFER_SIZE with nothing written.  Finished on
+ * return. */
 int alice_codec_dev_split_encode(const void *d_symbols, uint64_t n, const uint32_t hist[256], uint32_t lane_symbols,
                                  void *d_out, uint64_t cap, uint64_t *out_len, void *hip_stream);
 /* a channel payload of len bytes at d_stream (any alignment) with the header's frequencies -> n device symbols */
@@ -460,9 +464,12 @@ int alice_codec_dev_decode_split(const void *d_alc, uint64_t alc_stride, const u
  * validates like its version 2 twin, in the same order. */
 /* the most bytes a channel payload of n wide symbols takes (0: lane_symbols out of range or n above 2^32 - 1) */
 uint64_t alice_codec_wide_stream_bound(uint64_t n, uint32_t lane_symbols);
-/* stage pair on one channel: n device symbols z as u16; hist is over min(z, 255) and must count exactly n.  A symbol above
- * 255 + 4095 has no code: ALICE_ERR_INTERNAL with nothing written (8-bit RGB stays below 4081).  Otherwise as
- * alice_codec_dev_split_encode / _decode. */
+/* stage pair on one channel: n device symbols z as u16; hist is over min(z, 255) and must count exactly n.  As for
+ * version 2 it need not be the histogram of these symbols: the table is normalize(hist) whatever the symbols are, the call
+ * counts the coded symbols min(z, 255) itself, and one that occurs while hist[s] == 0 (255: any z >= 255) is
+ * ALICE_ERR_INVALID_BUFFER_SIZE with *out_len = 0 and nothing written.  A symbol above 255 + 4095 has no code:
+ * ALICE_ERR_INTERNAL with nothing written (8-bit RGB stays below 4081).  Otherwise as alice_codec_dev_split_encode /
+ * _decode. */
 int alice_codec_dev_wide_encode(const void *d_symbols, uint64_t n, const uint32_t hist[256], uint32_t lane_symbols,
                                 void *d_out, uint64_t cap, uint64_t *out_len, void *hip_stream);
 int alice_codec_dev_wide_decode(const void *d_stream, uint64_t len, const uint16_t freq[256], uint32_t lane_symbols,

@@ -11,6 +11,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import split_ref as R  # noqa: E402
+import wide_ref as RW  # noqa: E402
 
 
 def seeded_histograms():
@@ -61,6 +62,90 @@ def test_split_ref_round_trips_its_own_streams(n, L):
     dec, ok = R.decode_channel(pay, freq, L, n)
     assert ok and np.array_equal(dec, sym)
     assert not R.decode_channel(pay[:-1], freq, L, n)[1]
+
+
+def starved_full_block(version):
+    """(symbols, histogram, L): the longest lane stream a format can hold -- one full block plus 5 symbols at the largest
+    lane length, every coded step at frequency 1.  Version 2: 12 bits per symbol, 16384 symbols per lane; version 3: 24 bits
+    per symbol (escape and residual), 8192 per lane.  Either way a lane stream of 3 * 8192 + 4 = 24580 bytes."""
+    L = 16384 if version == 2 else 8192
+    n = 64 * L + 5
+    hist = np.zeros(256, np.uint32)
+    hist[3] = n - 1
+    if version == 2:
+        hist[7] = 1
+        return np.full(n, 7, np.uint8), hist, L
+    hist[255] = 1
+    return np.full(n, 255 + 4095, np.uint16), hist, L
+
+
+# version -> (largest lane directory entry, payload bytes, the stream bound)
+LONGEST = {2: (24580, 1_573_409, 2_097_938), 3: (24580, 1_573_419, 2_097_948)}
+
+
+def lane_directories(payload, n, L):
+    """(block lengths, [n_blocks, 64] lane lengths) of a channel payload"""
+    nb = R.n_blocks_of(n, L)
+    blen = np.frombuffer(payload, "<u4", nb).astype(np.int64)
+    boff = 4 * nb + np.cumsum(blen) - blen
+    return blen, np.stack([np.frombuffer(payload, "<u2", 64, int(o)).astype(np.int64) for o in boff])
+
+
+@pytest.mark.parametrize("version", [2, 3])
+def test_longest_lane_stream_fits_its_directory_entry_and_the_bound(codec, version):
+    """What tests/test_gpu_lane_fuzz.py runs on the device, pinned without one: with a histogram that starves the one symbol
+    of the data, a full-length lane takes 24580 bytes -- below the 65536 of its u16 directory entry -- and the payload stays
+    within the stream bound."""
+    ref = R if version == 2 else RW
+    sym, hist, L = starved_full_block(version)
+    n = sym.size
+    freq = ref.normalize(hist)
+    assert freq[3] == 4095 and int(freq.max(initial=0, where=np.arange(256) != 3)) == 1
+    pay = ref.encode_channel(sym, freq, L)
+    lane, length, bound = LONGEST[version]
+    got_bound = codec.split_stream_bound(n, L) if version == 2 else codec.wide_stream_bound(n, L)
+    assert len(pay) == length <= bound == got_bound
+    blen, dirs = lane_directories(pay, n, L)
+    assert dirs.shape == (2, 64) and (dirs[0] == lane).all() and int(dirs.max()) == lane < 65536
+    assert (dirs[1, :5] == (5 if version == 2 else 7)).all() and not dirs[1, 5:].any()
+    assert (blen == dirs.sum(axis=1) + 128).all() and 4 * 2 + int(blen.sum()) == len(pay)
+    dec, ok = ref.decode_channel(pay, freq, L, n)
+    assert ok and np.array_equal(dec, sym)
+
+
+def test_stage_encode_argument_checks_need_no_device(codec):
+    """alice_codec_dev_split_encode / _dev_wide_encode answer a null argument, a bad lane_symbols, too many symbols and a
+    histogram whose total is not n, in that order, before they look for a device (the pointers are never followed)."""
+    lib = codec.load_library()
+    somewhere = 0x1000
+    hist = np.zeros(256, np.uint32)
+    hist[5] = 100
+    hp = hist.ctypes.data_as(C.POINTER(C.c_uint32))
+
+    def call(fn, n, L, h=hp, sym=somewhere, out=somewhere, cap=1 << 20):
+        got = C.c_uint64(77)
+        rc = getattr(lib, fn)(sym, n, h, L, out, cap, C.byref(got), None)
+        return rc, (lib.alice_codec_last_error_message() or b"").decode(), lib.alice_codec_last_error()
+
+    for fn, top in (("alice_codec_dev_split_encode", 16384), ("alice_codec_dev_wide_encode", 8192)):
+        rc, msg, last = call(fn, 101, 64)
+        assert rc == last == 1 and msg == "the histogram counts 100 symbols, n is 101"
+        rc, msg, _ = call(fn, 99, top)
+        assert rc == 1 and msg == "the histogram counts 100 symbols, n is 99"
+        rc, msg, _ = call(fn, 0, 0)
+        assert rc == 1 and msg == "the histogram counts 100 symbols, n is 0"
+        for L in (32, 96, 2 * top, 1 << 31):
+            rc, msg, last = call(fn, 100, L)
+            assert rc == last == 2 and f"[64, {top}]" in msg, (fn, L, msg)
+        # the earlier check answers: lane_symbols before the total, too many symbols before the total, null before all
+        assert call(fn, 101, 100)[0] == 2
+        assert call(fn, 1 << 32, 64)[0] == 3 and call(fn, 1 << 32, 100)[0] == 2
+        assert call(fn, 101, 100, sym=None)[0] == 9 and call(fn, 101, 100, h=None)[0] == 9
+        assert call(fn, 101, 100, out=None)[0] == 9 and call(fn, 101, 100, out=None, cap=0)[0] == 2
+        # an empty channel with an empty histogram is no payload, without a device
+        empty = np.zeros(256, np.uint32)
+        got = C.c_uint64(77)
+        assert getattr(lib, fn)(None, 0, empty.ctypes.data_as(C.POINTER(C.c_uint32)), 64, None, 0, C.byref(got), None) == 0 and got.value == 0
 
 
 def container(w=6, h=4, f=2, L=64, wavelet=1, seed=0):
