@@ -207,6 +207,26 @@ def vec_bbox(m):
     return [int(cols[0]), int(rows[0]), int(cols[-1] - cols[0] + 1), int(rows[-1] - rows[0] + 1)], count
 
 
+def vec_stats(m):
+    """m: bool [n, h, w] -> int64 [n, 5] = x, y, w, h, count per frame (vec_bbox without the loop over frames)"""
+    m = np.asarray(m, bool)
+    n, h, w = m.shape
+    count = m.reshape(n, -1).sum(axis=1, dtype=np.int64)
+    rows, cols = m.any(axis=2), m.any(axis=1)
+    y0, y1 = rows.argmax(axis=1), h - 1 - rows[:, ::-1].argmax(axis=1)
+    x0, x1 = cols.argmax(axis=1), w - 1 - cols[:, ::-1].argmax(axis=1)
+    st = np.stack([x0, y0, x1 - x0 + 1, y1 - y0 + 1, count], axis=1).astype(np.int64)
+    st[count == 0] = 0
+    return st
+
+
+def vec_motion_batch(cur, ref, threshold, dilate, erode):
+    """vec_motion with vec_stats: for batches of many small frames"""
+    m = np.abs(np.asarray(cur, np.int16) - np.asarray(ref, np.int16)) > int(threshold)
+    m = vec_cleanup(m, dilate, erode)
+    return m.astype(np.uint8), vec_stats(m)
+
+
 def vec_motion(cur, ref, threshold, dilate, erode):
     """cur, ref: uint8 [f, h, w] (ref broadcastable) -> (mask uint8 [f, h, w], stats int64 [f, 5] = x, y, w, h, count)"""
     cur = np.asarray(cur, np.int16)
@@ -269,3 +289,83 @@ def vec_extract(mask, width, bbox, rgb):
     ok &= mi * 3 + 2 < rgb.size
     sel = mi[ok]
     return rgb[(sel[:, None] * 3 + np.arange(3)[None, :]).reshape(-1)].tobytes()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# (c) the launch geometry of csrc/segment.hip, restated from its conditions
+# ---------------------------------------------------------------------------------------------------------------------
+
+GRID_CAP = 1 << 20   # grid_cap, segment.hip:328
+
+# every class a case table has to reach; the text before " @" is the key of segment_geometry that reports it
+ALL_CLASSES = frozenset([
+    "chunks_per_row=1", "chunks_per_row>1", "row_of_64_words",
+    "block<64", "block>64", "block==64", "block==h-1", "block==h", "block>h clamped",   # (64 only through the clamp: 2r+1 is odd)
+    "block_starts_on_lane0", "block_starts_on_lane63", "block_ends_on_lane0",
+    "pick=0", "pick=1", "pick=2",
+    "last_step_partial", "last_step_full",
+    "smear<63", "smear>=63",
+    "row_grid_loops", "row_grid_loops_with_partial_group", "column_grid_loops"])
+
+
+def segment_geometry(w, h, n_frames, dilate, erode):
+    """What one segmentation call of w x h x n_frames with these radii reaches in csrc/segment.hip.  Keys are
+    "<name> @<line of segment.hip>"; `geometry_classes` flattens the result into members of ALL_CLASSES."""
+    w, h, n, radii = int(w), int(h), int(n_frames), [int(r) for r in (dilate, erode) if int(r)]
+    W64 = (w + 63) // 64
+    nch = (W64 + 63) // 64
+    g = {
+        "words_per_row @133": W64,
+        "chunks_per_row @133": nch,
+        # a radius takes :215 (one chunk) or :220 (two sweeps with ncarry); the final stage always takes :213
+        "row_path @213-220": ({"one_chunk" if nch == 1 else "many_chunks"} if radii else set()) | {"plain"},
+        "row_of_64_words @215": bool(radii) and W64 == 64,
+        "smear @90": {">=63" if r >= 63 else "<63" for r in radii},
+        "block @505": {}, "pick @146": set(),
+        "block_starts_on_lane0 @292": False, "block_starts_on_lane63 @294": False, "block_ends_on_lane0 @308": False,
+        "last_step_partial @286": None if not radii else h % 64 != 0,
+        "row_grid_loops @135": ((h + 3) // 4) * n > GRID_CAP,
+        "row_group_partial @138": h % 4 != 0,
+        "column_grid_loops @281": bool(radii) and (n * W64 + 3) // 4 > GRID_CAP,
+    }
+    for r in radii:
+        full = 2 * r + 1
+        B = full if full < h else h                                    # :505
+        cls = {"<64" if B < 64 else ("==64" if B == 64 else ">64")}   # block_of, :110
+        if full > h:
+            cls.add("clamped")
+        if full == h:
+            cls.add("==h")
+        if full == h - 1:
+            cls.add("==h-1")
+        g["block @505"][r] = (B, cls)
+        for y0 in range(B, h, B):                                      # first row of every block but the first
+            g["block_starts_on_lane0 @292"] |= y0 % 64 == 0             # the carry of the step before must be dropped
+            g["block_starts_on_lane63 @294"] |= y0 % 64 == 63           # the carry out is a block of one row
+            g["block_ends_on_lane0 @308"] |= y0 % 64 == 1               # the same for the reverse pass
+        for y in range(h):                                             # :144-146
+            lo = y - r if y > r else 0
+            hi = y + r if h - 1 - y > r else h - 1
+            g["pick @146"].add(0 if lo // B != hi // B else (1 if lo % B == 0 else 2))
+    return g
+
+
+def geometry_classes(g):
+    """the members of ALL_CLASSES that a segment_geometry result holds"""
+    out = {"chunks_per_row=1" if g["chunks_per_row @133"] == 1 else "chunks_per_row>1"}
+    if g["row_of_64_words @215"]:
+        out.add("row_of_64_words")
+    out |= {"smear" + s for s in g["smear @90"]}
+    for B, cls in g["block @505"].values():
+        for c in cls:
+            out.add({"clamped": "block>h clamped"}.get(c, "block" + c))
+    for k in ("block_starts_on_lane0 @292", "block_starts_on_lane63 @294", "block_ends_on_lane0 @308", "row_grid_loops @135",
+              "column_grid_loops @281"):
+        if g[k]:
+            out.add(k.split(" @")[0])
+    if g["row_grid_loops @135"] and g["row_group_partial @138"]:
+        out.add("row_grid_loops_with_partial_group")
+    out |= {"pick=%d" % p for p in g["pick @146"]}
+    if g["last_step_partial @286"] is not None:
+        out.add("last_step_partial" if g["last_step_partial @286"] else "last_step_full")
+    return out

@@ -9,6 +9,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import segment_ref as R  # noqa: E402
+import segment_cases as K  # noqa: E402
 
 BIG = 2 ** 32 - 1
 
@@ -196,6 +197,111 @@ def test_numpy_aliases_shapes(codec):
     g = np.zeros((4, 5), np.uint8)
     assert codec.paste_bbox_numpy(g, c.reshape(-1), [1, 1, 2, 2]) is None
     assert g[1:3, 1:3].tolist() == [[6, 7], [11, 12]]
+
+
+# ---- the references and case tables of tests/test_gpu_segment_geometry.py ----
+
+def test_vec_stats_is_vec_bbox_frame_by_frame():
+    rng = np.random.default_rng(77)
+    for _ in range(40):
+        h, w = int(rng.integers(1, 12)), int(rng.integers(1, 70))
+        m = rng.random((8, h, w)) < rng.choice([0.0, 0.01, 0.1, 0.6, 1.0], size=(8, 1, 1))
+        st = R.vec_stats(m)
+        assert st.shape == (8, 5) and st.dtype == np.int64
+        for f in range(8):
+            bbox, count = R.vec_bbox(m[f])
+            assert list(st[f]) == bbox + [count], (h, w, f)
+    assert R.vec_stats(np.zeros((3, 2, 2), bool)).tolist() == [[0] * 5] * 3
+
+
+def _box(h, w, y, x, r):
+    out = np.zeros((h, w), bool)
+    out[max(0, y - r):min(h, y + r + 1), max(0, x - r):min(w, x + r + 1)] = True
+    return out
+
+
+def _lit_of_pattern(m, rd, re):
+    """lit_motion of a 0/255 frame against zeros: bool [h, w] -> (bool [h, w], stats)"""
+    h, w = m.shape
+    mask, bbox, count = R.lit_motion(list(m.reshape(-1).astype(int) * 255), [0] * (w * h), w, h, 100, rd, re)
+    return np.array(mask, bool).reshape(h, w), bbox + [count]
+
+
+def test_single_pixel_and_single_hole_give_the_clipped_box():
+    """what the GPU sweep relies on: one set pixel dilates to exactly the (2r+1)^2 box clipped to the frame, one hole
+    erodes to its complement, in both restatements"""
+    for h, w in ((3, 70), (5, 130), (66, 2)):
+        for r in (1, 2, 62, 63, 64, w + 1, BIG):
+            for y, x in ((0, 0), (h - 1, w - 1), (h // 2, 63 % w), (min(h - 1, 64), 64 % w), (1, w // 2)):
+                m = np.zeros((h, w), bool)
+                m[y, x] = True
+                want = _box(h, w, y, x, min(r, h + w))
+                assert np.array_equal(R.vec_dilate(m, r), want), (h, w, r, y, x)
+                assert np.array_equal(R.vec_erode(~m, r), ~want), (h, w, r, y, x)
+                if r in (1, 63, BIG):
+                    got, st = _lit_of_pattern(m, r, 0)
+                    assert np.array_equal(got, want) and st == R.vec_bbox(want)[0] + [int(want.sum())]
+                    assert np.array_equal(_lit_of_pattern(~m, 0, r)[0], ~want)
+
+
+def test_pattern_families_literal_vs_vectorised():
+    """reduced versions of the GPU sweep's patterns (widths that still cross a 64-pixel word; one row that crosses a
+    4096-pixel chunk) through both restatements, every radius class of dilate_word"""
+    rng = np.random.default_rng(5)
+    cases = []
+    for w, h in ((65, 2), (130, 3), (129, 5)):
+        for r in (0, 1, 62, 63, 64, w, w + 5):
+            singles = [[p] for p in (0, 63, 64, w - 1)]
+            pairs = [[63 - d // 2, 63 - d // 2 + d] for d in (r - 1, r, r + 1) if d >= 1 and 63 - d // 2 >= 0 and 63 - d // 2 + d < w]
+            for f, xs in enumerate(singles + pairs + [[]]):
+                m = np.zeros((h, w), bool)
+                m[f % h, xs] = True
+                cases.append((m, r))
+    for r in (1, 62, 64):                       # a chunk edge: 64 words of 64 pixels
+        for p, q in K.row_pairs(4100, r):
+            m = np.zeros((1, 4100), bool)
+            m[0, [p, q]] = True
+            cases.append((m, r))
+    for h in (3, 5, 65):                        # the column pass's patterns at a width of one word
+        for c in K.column_cases(h)[::17]:
+            if c["w"] == 1 and max(c["rd"], c["re"]) < BIG:
+                cases.append((K.column_pattern(c, rng)[0], c["rd"], c["re"]))
+    assert len(cases) > 150
+    for case in cases:
+        m = case[0]
+        for rd, re, pat in ([(case[1], 0, m), (0, case[1], ~m)] if len(case) == 2 else [(case[1], case[2], m)]):
+            got, st = _lit_of_pattern(pat, rd, re)
+            vm, vst = R.vec_motion_batch(pat[None].astype(np.uint8) * 255, np.zeros((1,) + m.shape, np.uint8), 100, rd, re)
+            assert np.array_equal(vm[0].astype(bool), got), (m.shape, rd, re)
+            assert list(vst[0]) == st
+            om, ost = R.vec_motion(pat[None].astype(np.uint8) * 255, np.zeros((1,) + m.shape, np.uint8), 100, rd, re)
+            assert np.array_equal(om, vm) and np.array_equal(ost, vst)
+
+
+def test_segment_geometry_known_answers():
+    g = R.segment_geometry(4096, 5, 3, 1, 0)
+    assert g["words_per_row @133"] == 64 and g["chunks_per_row @133"] == 1 and g["row_of_64_words @215"]
+    assert g["block @505"] == {1: (3, {"<64"})} and g["pick @146"] == {0, 1} and g["last_step_partial @286"]
+    assert R.segment_geometry(4096, 6, 3, 1, 0)["pick @146"] == {0, 1, 2}     # row 5: window rows 4..5 inside block 3..5
+    g = R.segment_geometry(4097, 64, 1, BIG, 31)
+    assert g["chunks_per_row @133"] == 2 and g["row_path @213-220"] == {"many_chunks", "plain"}
+    assert g["block @505"] == {BIG: (64, {"==64", "clamped"}), 31: (63, {"<64", "==h-1"})}
+    assert g["block_starts_on_lane63 @294"] and not g["block_starts_on_lane0 @292"] and g["last_step_partial @286"] is False
+    assert g["smear @90"] == {"<63", ">=63"}
+    g = R.segment_geometry(1, 1, 4_300_000, 0, 0)
+    assert g["row_grid_loops @135"] and not g["column_grid_loops @281"] and g["block @505"] == {}
+    assert R.segment_geometry(1, 1, 4_300_000, 1, 1)["column_grid_loops @281"]
+    assert not R.segment_geometry(1, 1, 4 << 20, 1, 1)["column_grid_loops @281"]
+    assert R.segment_geometry(257, 257, 1, 1, 0)["block_starts_on_lane0 @292"]
+    assert R.segment_geometry(1, 129, 1, 32, 0)["block_ends_on_lane0 @308"]
+    for g in (R.segment_geometry(5, 6, 530_000, 1, 1), R.segment_geometry(70, 200, 2, 40, 0)):
+        assert R.geometry_classes(g) <= R.ALL_CLASSES
+
+
+def test_case_table_reaches_every_geometry_class():
+    """the closure that tests/test_gpu_segment_geometry.py asserts after its sweep: an edit of the tables fails here first"""
+    missing = R.ALL_CLASSES - K.reached_classes(K.all_segment_calls())
+    assert not missing, sorted(missing)
 
 
 # ---- the C ABI's validation, before any device work ----
