@@ -276,6 +276,18 @@ def load_library() -> C.CDLL:
         "alice_codec_dev_encode_split_to_budget": (C.c_int, [vp, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, C.c_uint32, C.c_uint32,
                                                              C.c_uint32, C.c_uint8, C.c_uint32, _u64p, C.c_uint8, C.c_uint8, _u8p, _u8p,
                                                              vp, C.c_uint64, _u64p, vp]),
+        "alice_codec_predict_wide_sizes": (C.c_int, [C.c_uint8, _u8p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                     _u64p, _u64p]),
+        "alice_codec_dev_predict_wide_sizes": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint32,
+                                                         _u64p, _u64p, vp, vp]),
+        "alice_codec_encode_wide_to_size": (vp, [C.c_uint8, _u8p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                 C.c_uint64, C.c_uint8, C.c_uint8, _u8p, _u8p, _u64p]),
+        "alice_codec_dev_encode_wide_regions": (C.c_int, [vp, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                          C.c_uint32, C.c_uint8, C.c_uint8, _u8p, C.c_uint32, vp, C.c_uint64, _u64p, vp]),
+        "alice_codec_dev_decode_wide_regions": (C.c_int, [vp, C.c_uint64, _u64p, C.c_uint32, vp, C.c_uint32, C.c_uint32, _u32p, vp]),
+        "alice_codec_dev_encode_wide_to_budget": (C.c_int, [vp, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                            C.c_uint32, C.c_uint8, C.c_uint32, _u64p, C.c_uint8, C.c_uint8, _u8p, _u8p,
+                                                            vp, C.c_uint64, _u64p, vp]),
         "alice_codec_test_last_split_trials": (C.c_uint32, [_u32p, C.c_uint32]),
         "alice_codec_test_inverse_variant": (C.c_int, [C.c_uint8, _i32p, C.c_int]),
     }
@@ -1518,13 +1530,15 @@ def encode_person_chunks(d_frames, d_background, width: int, height: int, frames
        bbox [0, 0, 0, 0] and the reference's empty chunk, FrameEncoder.encode(b"", 0, 0, frames).
 
     format="split" codes the boxes as version 2 (split_encode_regions_device; lane_symbols 0: the default), with the
-    version 2 empty chunk for chunks without foreground.  max_bytes (split only) is a byte budget per chunk: every box is
-    then coded at the quality split_encode_to_budget_device picks in [10, min(quality, 100)], and a chunk that cannot be
-    guaranteed to fit is coded at the low end of the range."""
-    if format not in ("v1", "split"):
-        raise CodecError(9, f"format must be 'v1' or 'split', got {format!r}")
-    if max_bytes is not None and format != "split":
-        raise CodecError(9, "max_bytes is a version 2 budget: it needs format='split'")
+    version 2 empty chunk for chunks without foreground; format="wide" does the same with version 3
+    (wide_encode_regions_device), the container to choose for qualities above about 90.  max_bytes (split and wide only) is
+    a byte budget per chunk: every box is then coded at the quality split_encode_to_budget_device /
+    wide_encode_to_budget_device picks in [min(10, hi), hi], hi = min(quality, 100), and a chunk that cannot be guaranteed
+    to fit is coded at the low end of the range."""
+    if format not in ("v1", "split", "wide"):
+        raise CodecError(9, f"format must be 'v1', 'split' or 'wide', got {format!r}")
+    if max_bytes is not None and format not in ("split", "wide"):
+        raise CodecError(9, "max_bytes is a version 2 / version 3 budget: it needs format='split' or format='wide'")
     W, H, f = _positive_u32(width, "width"), _positive_u32(height, "height"), _positive_u32(frames, "frames")
     n = _positive_u32(n_chunks, "n_chunks")
     if not 0 <= int(quality) <= 255:
@@ -1550,25 +1564,29 @@ def encode_person_chunks(d_frames, d_background, width: int, height: int, frames
         st = stats.cpu().numpy().view(np.uint32).reshape(-1, 5).astype(np.int64)
     boxes = person_chunk_boxes(st, W, H, f)
     frame_bytes = W * H * 3
-    if format == "split":
+    if format in ("split", "wide"):
+        wide = format == "wide"
         enc = FrameEncoder(int(quality), wavelet)
-        empty = encode_split(enc, b"", 0, 0, f, lane_symbols)
+        empty = (encode_wide if wide else encode_split)(enc, b"", 0, 0, f, lane_symbols)
+        bound = wide_stream_bound if wide else split_stream_bound
+        encode_regions = wide_encode_regions_device if wide else split_encode_regions_device
+        encode_to_budget = wide_encode_to_budget_device if wide else split_encode_to_budget_device
         out = [(b, empty) for b in boxes]
         for i, j in _runs(boxes):
             bw, bh = boxes[i][2], boxes[i][3]
-            stride = (SPLIT_HEADER_BYTES + 3 * split_stream_bound(_padded_pixels(bw, bh, f), lane_symbols or SPLIT_DEFAULT_LANE_SYMBOLS)
+            stride = (SPLIT_HEADER_BYTES + 3 * bound(_padded_pixels(bw, bh, f), lane_symbols or SPLIT_DEFAULT_LANE_SYMBOLS)
                       + 255) & ~255
             d_out = torch.empty((j - i) * stride, dtype=torch.uint8, device="cuda")
             origins = [b[:2] for b in boxes[i:j]]
             src = frames_ptr + i * f * frame_bytes
             if max_bytes is None:
-                sizes = split_encode_regions_device(src, W, H, origins, bw, bh, f, wavelet, int(quality), d_out.data_ptr(), stride,
-                                                    lane_symbols=lane_symbols)
+                sizes = encode_regions(src, W, H, origins, bw, bh, f, wavelet, int(quality), d_out.data_ptr(), stride,
+                                       lane_symbols=lane_symbols)
             else:
                 hi_q = min(int(quality), 100)
-                _, _, sizes = split_encode_to_budget_device(src, bw, bh, f, j - i, wavelet, [int(max_bytes)] * (j - i),
-                                                            d_out.data_ptr(), stride, min_quality=min(10, hi_q), max_quality=hi_q,
-                                                            lane_symbols=lane_symbols, frame_width=W, frame_height=H, origins=origins)
+                _, _, sizes = encode_to_budget(src, bw, bh, f, j - i, wavelet, [int(max_bytes)] * (j - i),
+                                               d_out.data_ptr(), stride, min_quality=min(10, hi_q), max_quality=hi_q,
+                                               lane_symbols=lane_symbols, frame_width=W, frame_height=H, origins=origins)
             host = d_out.cpu().numpy().reshape(j - i, stride)
             for k in range(j - i):
                 out[i + k] = (boxes[i + k], host[k, :int(sizes[k])].tobytes())
@@ -1598,7 +1616,7 @@ def decode_person_chunks(chunks, d_frames_out, width: int, height: int, frames: 
     """Hybrid decode: chunk k of `chunks` (encode_person_chunks' list of (bbox, .alc bytes)) is decoded and pasted into
     its bbox of frames [k * frames, (k + 1) * frames) of d_frames_out (width x height RGB in HBM, typically holding the
     background).  Empty chunks paste nothing; no byte outside the boxes is written.  Each chunk is decoded by its own
-    container version (alc_version), so a list may mix version 1 and version 2 chunks."""
+    container version (alc_version), so a list may mix version 1, version 2 and version 3 chunks."""
     W, H, f = _positive_u32(width, "width"), _positive_u32(height, "height"), _positive_u32(frames, "frames")
     boxes, alcs, versions, lanes = [], [], [], {}
     for k, (bbox, alc) in enumerate(chunks):
@@ -1610,10 +1628,10 @@ def decode_person_chunks(chunks, d_frames_out, width: int, height: int, frames: 
         data = bytes(alc)
         version = alc_version(data)
         if b[2] * b[3]:
-            c = split_info(data) if version == 2 else EncodedChunk.from_bytes(data)
+            c = split_info(data) if version == 2 else wide_info(data) if version == 3 else EncodedChunk.from_bytes(data)
             if (c.width, c.height, c.frames) != (b[2], b[3], f):
                 raise CodecError(2, f"chunk {k}: .alc is {c.width}x{c.height}x{c.frames}, bbox says {b[2]}x{b[3]}x{f}")
-            if version == 2:
+            if version in (2, 3):
                 lanes[k] = c.lane_symbols
         boxes.append(b)
         alcs.append(data)
@@ -1634,14 +1652,15 @@ def decode_person_chunks(chunks, d_frames_out, width: int, height: int, frames: 
     batches = {}
     for i, j in runs:
         bw, bh = boxes[i][2], boxes[i][3]
-        if versions[i] == 2:
+        if versions[i] in (2, 3):
+            decode_regions = wide_decode_regions_device if versions[i] == 3 else split_decode_regions_device
             stride = (max(len(a) for a in alcs[i:j]) + 255) & ~255
             host = np.zeros((j - i, stride), np.uint8)
             for k in range(i, j):
                 host[k - i, :len(alcs[k])] = np.frombuffer(alcs[k], np.uint8)
             d_alc = torch.from_numpy(host).to("cuda")
-            split_decode_regions_device(d_alc.data_ptr(), stride, [len(a) for a in alcs[i:j]], out_ptr + i * f * frame_bytes, W, H,
-                                        [b[:2] for b in boxes[i:j]])
+            decode_regions(d_alc.data_ptr(), stride, [len(a) for a in alcs[i:j]], out_ptr + i * f * frame_bytes, W, H,
+                           [b[:2] for b in boxes[i:j]])
             continue
         stride = (max(len(a) for a in alcs[i:j]) + 255) & ~255
         host = np.zeros((j - i, stride), np.uint8)
@@ -1853,19 +1872,96 @@ def decode_alc(data) -> np.ndarray:
     return FrameDecoder().decode(EncodedChunk.from_bytes(data))   # version 1, and every refusal the v1 parser words
 
 
-# ---- version 2: size prediction, byte budgets, regions of device frames ----
+# ---- versions 2 and 3: size prediction, byte budgets, regions of device frames (DESIGN.md sections 10.8, 11.6) ----
+# One body per call with the container as an argument, as in the library: `kind` is "split" (version 2) or "wide"
+# (version 3) and names the C entry point.
+
+def _predict_container_sizes(kind: str, rgb_frames, width: int, height: int, frames: int, wavelet_type, lane_symbols: int):
+    r = _as_u8(rgb_frames)
+    _dims_u32(width, height, frames, lane_symbols)
+    lo = np.zeros(101, np.uint64); hi = np.zeros(101, np.uint64)
+    ptr = _p(r, _u8p) if r.size else C.cast(C.c_char_p(b""), _u8p)
+    fn = getattr(load_library(), f"alice_codec_predict_{kind}_sizes")
+    _check(fn(int(wavelet_type), ptr, r.size, width, height, frames, lane_symbols, _p(lo, _u64p), _p(hi, _u64p)))
+    return SizePrediction(lo, hi, np.zeros(101, np.uint8))
+
+
+def _encode_container_to_size(kind: str, rgb_frames, width: int, height: int, frames: int, max_bytes: int, wavelet_type,
+                              min_quality: int, max_quality: int, lane_symbols: int) -> tuple:
+    lib = load_library()
+    r = _as_u8(rgb_frames)
+    _dims_u32(width, height, frames, lane_symbols)
+    _check_budget_args([max_bytes], min_quality, max_quality)
+    chosen = C.c_uint8(0); fits = C.c_uint8(0); n = C.c_uint64(0)
+    src = _p(r, _u8p) if r.size else C.cast(C.c_char_p(b""), _u8p)
+    ptr = getattr(lib, f"alice_codec_encode_{kind}_to_size")(int(wavelet_type), src, r.size, width, height, frames, lane_symbols,
+                                                             int(max_bytes), int(min_quality), int(max_quality), C.byref(chosen),
+                                                             C.byref(fits), C.byref(n))
+    if not ptr:
+        _raise_last()
+    try:
+        return _copy_out(ptr, n.value).tobytes(), int(chosen.value), bool(fits.value)
+    finally:
+        lib.alice_codec_data_free64(ptr, n.value)
+
+
+def _origins_u32(origins, n_chunks: int) -> np.ndarray:
+    o = np.ascontiguousarray(origins, dtype=np.int64).reshape(-1)
+    if o.size != 2 * n_chunks or (o < 0).any() or (o > 0xFFFFFFFF).any():
+        raise ValueError("origins: one (x, y) pair of u32 per chunk")
+    return o.astype(np.uint32)
+
+
+def _encode_container_regions(kind: str, d_frames_ptr: int, frame_width: int, frame_height: int, origins, width: int, height: int,
+                              frames: int, wavelet_type, quality: int, d_out_ptr: int, out_stride: int, qualities,
+                              lane_symbols: int, stream: int) -> np.ndarray:
+    n_chunks = len(origins)
+    o = _origins_u32(origins, n_chunks)
+    sizes = np.zeros(n_chunks, np.uint64)
+    q = None if qualities is None else np.ascontiguousarray(qualities, dtype=np.uint8).reshape(-1)
+    if q is not None and q.size != n_chunks:
+        raise ValueError("one quality per chunk")
+    _dims_u32(frame_width, frame_height, width, height, frames, lane_symbols)
+    fn = getattr(load_library(), f"alice_codec_dev_encode_{kind}_regions")
+    _check(fn(d_frames_ptr, frame_width, frame_height, _p(o, _u32p), width, height, frames, n_chunks, int(wavelet_type), quality,
+              None if q is None else _p(q, _u8p), lane_symbols, d_out_ptr, out_stride, _p(sizes, _u64p), stream or None))
+    return sizes
+
+
+def _decode_container_regions(kind: str, d_alc_ptr: int, alc_stride: int, sizes, d_frames_out_ptr: int, frame_width: int,
+                              frame_height: int, origins, stream: int) -> None:
+    s = np.ascontiguousarray(sizes, dtype=np.uint64).reshape(-1)
+    o = _origins_u32(origins, s.size)
+    _dims_u32(frame_width, frame_height)
+    fn = getattr(load_library(), f"alice_codec_dev_decode_{kind}_regions")
+    _check(fn(d_alc_ptr, alc_stride, _p(s, _u64p), s.size, d_frames_out_ptr, frame_width, frame_height, _p(o, _u32p), stream or None))
+
+
+def _encode_container_to_budget(kind: str, d_frames_ptr: int, width: int, height: int, frames: int, n_chunks: int, wavelet_type,
+                                budgets, d_out_ptr: int, out_stride: int, min_quality: int, max_quality: int, lane_symbols: int,
+                                frame_width: int, frame_height: int, origins, stream: int) -> tuple:
+    b = [int(v) for v in budgets]
+    if len(b) != n_chunks:
+        raise ValueError("one budget per chunk")
+    _check_budget_args(b, min_quality, max_quality)
+    _dims_u32(width, height, frames, n_chunks, lane_symbols, frame_width, frame_height)
+    bud = np.array(b, dtype=np.uint64)
+    o = None if origins is None else _origins_u32(origins, n_chunks)
+    chosen = np.zeros(n_chunks, np.uint8); fits = np.zeros(n_chunks, np.uint8); sizes = np.zeros(n_chunks, np.uint64)
+    fn = getattr(load_library(), f"alice_codec_dev_encode_{kind}_to_budget")
+    _check(fn(d_frames_ptr, frame_width, frame_height, None if o is None else _p(o, _u32p), width, height, frames, n_chunks,
+              int(wavelet_type), lane_symbols, _p(bud, _u64p), int(min_quality), int(max_quality), _p(chosen, _u8p), _p(fits, _u8p),
+              d_out_ptr, out_stride, _p(sizes, _u64p), stream or None))
+    return chosen, fits.astype(bool), sizes
+
+
+# ---- version 2 ----
 
 def predict_split_sizes(rgb_frames, width: int, height: int, frames: int, wavelet_type: WaveletType = WaveletType.Cdf53,
                         lane_symbols: int = 0) -> SizePrediction:
     """The size bracket of encode_split at every quality, from one forward transform on the GPU (no entropy coding).
     Every version 2 table is bounded: status is RATE_BOUNDED throughout."""
-    r = _as_u8(rgb_frames)
-    _dims_u32(width, height, frames, lane_symbols)
-    lo = np.zeros(101, np.uint64); hi = np.zeros(101, np.uint64)
-    ptr = _p(r, _u8p) if r.size else C.cast(C.c_char_p(b""), _u8p)
-    _check(load_library().alice_codec_predict_split_sizes(int(wavelet_type), ptr, r.size, width, height, frames, lane_symbols,
-                                                          _p(lo, _u64p), _p(hi, _u64p)))
-    return SizePrediction(lo, hi, np.zeros(101, np.uint8))
+    return _predict_container_sizes("split", rgb_frames, width, height, frames, wavelet_type, lane_symbols)
 
 
 def predict_split_sizes_device(d_rgb_ptr: int, width: int, height: int, frames: int, n_chunks: int,
@@ -1886,27 +1982,8 @@ def encode_split_to_size(rgb_frames, width: int, height: int, frames: int, max_b
     whose predicted upper bound fits, refined by at most four exact size counts among the qualities whose bracket straddles
     the budget.  Returns (bytes, quality, fits); fits is False when not even min_quality is guaranteed to fit (the chunk is
     then encoded at min_quality).  The bytes are encode_split's at that quality."""
-    lib = load_library()
-    r = _as_u8(rgb_frames)
-    _dims_u32(width, height, frames, lane_symbols)
-    _check_budget_args([max_bytes], min_quality, max_quality)
-    chosen = C.c_uint8(0); fits = C.c_uint8(0); n = C.c_uint64(0)
-    src = _p(r, _u8p) if r.size else C.cast(C.c_char_p(b""), _u8p)
-    ptr = lib.alice_codec_encode_split_to_size(int(wavelet_type), src, r.size, width, height, frames, lane_symbols, int(max_bytes),
-                                               int(min_quality), int(max_quality), C.byref(chosen), C.byref(fits), C.byref(n))
-    if not ptr:
-        _raise_last()
-    try:
-        return _copy_out(ptr, n.value).tobytes(), int(chosen.value), bool(fits.value)
-    finally:
-        lib.alice_codec_data_free64(ptr, n.value)
-
-
-def _origins_u32(origins, n_chunks: int) -> np.ndarray:
-    o = np.ascontiguousarray(origins, dtype=np.int64).reshape(-1)
-    if o.size != 2 * n_chunks or (o < 0).any() or (o > 0xFFFFFFFF).any():
-        raise ValueError("origins: one (x, y) pair of u32 per chunk")
-    return o.astype(np.uint32)
+    return _encode_container_to_size("split", rgb_frames, width, height, frames, max_bytes, wavelet_type, min_quality, max_quality,
+                                     lane_symbols)
 
 
 def split_encode_regions_device(d_frames_ptr: int, frame_width: int, frame_height: int, origins, width: int, height: int,
@@ -1914,29 +1991,15 @@ def split_encode_regions_device(d_frames_ptr: int, frame_width: int, frame_heigh
                                 qualities=None, lane_symbols: int = 0, stream: int = 0) -> np.ndarray:
     """Chunk i = frames [i * frames, (i + 1) * frames) of the device frames, cropped to width x height at origins[i], as
     version 2 bytes at d_out_ptr + i * out_stride (the bytes of encode_split of the crop); returns the sizes."""
-    n_chunks = len(origins)
-    o = _origins_u32(origins, n_chunks)
-    sizes = np.zeros(n_chunks, np.uint64)
-    q = None if qualities is None else np.ascontiguousarray(qualities, dtype=np.uint8).reshape(-1)
-    if q is not None and q.size != n_chunks:
-        raise ValueError("one quality per chunk")
-    _dims_u32(frame_width, frame_height, width, height, frames, lane_symbols)
-    _check(load_library().alice_codec_dev_encode_split_regions(d_frames_ptr, frame_width, frame_height, _p(o, _u32p), width, height,
-                                                               frames, n_chunks, int(wavelet_type), quality,
-                                                               None if q is None else _p(q, _u8p), lane_symbols, d_out_ptr,
-                                                               out_stride, _p(sizes, _u64p), stream or None))
-    return sizes
+    return _encode_container_regions("split", d_frames_ptr, frame_width, frame_height, origins, width, height, frames, wavelet_type,
+                                     quality, d_out_ptr, out_stride, qualities, lane_symbols, stream)
 
 
 def split_decode_regions_device(d_alc_ptr: int, alc_stride: int, sizes, d_frames_out_ptr: int, frame_width: int,
                                 frame_height: int, origins, stream: int = 0) -> None:
     """Chunk i (sizes[i] bytes at d_alc_ptr + i * alc_stride) is decoded into its rectangle at origins[i] of its frames of
     d_frames_out_ptr; no byte outside the rectangles is written."""
-    s = np.ascontiguousarray(sizes, dtype=np.uint64).reshape(-1)
-    o = _origins_u32(origins, s.size)
-    _dims_u32(frame_width, frame_height)
-    _check(load_library().alice_codec_dev_decode_split_regions(d_alc_ptr, alc_stride, _p(s, _u64p), s.size, d_frames_out_ptr,
-                                                               frame_width, frame_height, _p(o, _u32p), stream or None))
+    _decode_container_regions("split", d_alc_ptr, alc_stride, sizes, d_frames_out_ptr, frame_width, frame_height, origins, stream)
 
 
 def split_encode_to_budget_device(d_frames_ptr: int, width: int, height: int, frames: int, n_chunks: int,
@@ -1945,18 +2008,63 @@ def split_encode_to_budget_device(d_frames_ptr: int, width: int, height: int, fr
                                   origins=None, stream: int = 0) -> tuple:
     """n_chunks device chunks (packed, or regions of frame_width x frame_height frames when origins is given), chunk i at
     the quality encode_split_to_size's rule picks for budgets[i].  Returns (chosen, fits, sizes)."""
-    b = [int(v) for v in budgets]
-    if len(b) != n_chunks:
-        raise ValueError("one budget per chunk")
-    _check_budget_args(b, min_quality, max_quality)
-    _dims_u32(width, height, frames, n_chunks, lane_symbols, frame_width, frame_height)
-    bud = np.array(b, dtype=np.uint64)
-    o = None if origins is None else _origins_u32(origins, n_chunks)
-    chosen = np.zeros(n_chunks, np.uint8); fits = np.zeros(n_chunks, np.uint8); sizes = np.zeros(n_chunks, np.uint64)
-    _check(load_library().alice_codec_dev_encode_split_to_budget(d_frames_ptr, frame_width, frame_height,
-                                                                 None if o is None else _p(o, _u32p), width, height, frames,
-                                                                 n_chunks, int(wavelet_type), lane_symbols, _p(bud, _u64p),
-                                                                 int(min_quality), int(max_quality), _p(chosen, _u8p),
-                                                                 _p(fits, _u8p), d_out_ptr, out_stride, _p(sizes, _u64p),
-                                                                 stream or None))
-    return chosen, fits.astype(bool), sizes
+    return _encode_container_to_budget("split", d_frames_ptr, width, height, frames, n_chunks, wavelet_type, budgets, d_out_ptr,
+                                       out_stride, min_quality, max_quality, lane_symbols, frame_width, frame_height, origins, stream)
+
+
+# ---- version 3 (DESIGN.md section 11.6): the same calls for the wide container; lane_symbols is a power of two in
+# [64, 8192], and a trial of the budget rule is the wide forward pass, the table and the wide count pass ----
+
+def predict_wide_sizes(rgb_frames, width: int, height: int, frames: int, wavelet_type: WaveletType = WaveletType.Cdf53,
+                       lane_symbols: int = 0) -> SizePrediction:
+    """The size bracket of encode_wide at every quality, from one forward transform on the GPU (no entropy coding): the
+    histogram of the coded symbol min(z, 255) at every step, with the 12-bit residual of every escape priced in.  Every
+    version 3 table is bounded: status is RATE_BOUNDED throughout."""
+    return _predict_container_sizes("wide", rgb_frames, width, height, frames, wavelet_type, lane_symbols)
+
+
+def predict_wide_sizes_device(d_rgb_ptr: int, width: int, height: int, frames: int, n_chunks: int,
+                              wavelet_type: WaveletType = WaveletType.Cdf53, lane_symbols: int = 0,
+                              d_step_hist: int = 0, stream: int = 0) -> SizePrediction:
+    """n_chunks packed chunks at a device pointer: arrays of shape (n_chunks, 101).  d_step_hist: 0, or a device pointer to
+    n_chunks * 64 * 3 * 256 u32 that receives the histograms of the coded symbol min(z, 255) behind the prediction,
+    [chunk][step - 1][channel][symbol]."""
+    _dims_u32(width, height, frames, n_chunks, lane_symbols)
+    lo = np.zeros((max(n_chunks, 1), 101), np.uint64); hi = np.zeros_like(lo)
+    _check(load_library().alice_codec_dev_predict_wide_sizes(d_rgb_ptr, width, height, frames, n_chunks, int(wavelet_type),
+                                                             lane_symbols, _p(lo, _u64p), _p(hi, _u64p), d_step_hist or None,
+                                                             stream or None))
+    return SizePrediction(lo[:n_chunks], hi[:n_chunks], np.zeros((n_chunks, 101), np.uint8))
+
+
+def encode_wide_to_size(rgb_frames, width: int, height: int, frames: int, max_bytes: int,
+                        wavelet_type: WaveletType = WaveletType.Cdf53, min_quality: int = 10, max_quality: int = 95,
+                        lane_symbols: int = 0) -> tuple:
+    """encode_split_to_size for version 3 (pass max_quality=100 for the top of the scale, where this container is the one
+    to use).  Returns (bytes, quality, fits); the bytes are encode_wide's at that quality."""
+    return _encode_container_to_size("wide", rgb_frames, width, height, frames, max_bytes, wavelet_type, min_quality, max_quality,
+                                     lane_symbols)
+
+
+def wide_encode_regions_device(d_frames_ptr: int, frame_width: int, frame_height: int, origins, width: int, height: int,
+                               frames: int, wavelet_type: WaveletType, quality: int, d_out_ptr: int, out_stride: int,
+                               qualities=None, lane_symbols: int = 0, stream: int = 0) -> np.ndarray:
+    """split_encode_regions_device for version 3: the bytes of chunk i are encode_wide's of the crop; returns the sizes."""
+    return _encode_container_regions("wide", d_frames_ptr, frame_width, frame_height, origins, width, height, frames, wavelet_type,
+                                     quality, d_out_ptr, out_stride, qualities, lane_symbols, stream)
+
+
+def wide_decode_regions_device(d_alc_ptr: int, alc_stride: int, sizes, d_frames_out_ptr: int, frame_width: int,
+                               frame_height: int, origins, stream: int = 0) -> None:
+    """split_decode_regions_device for version 3 containers: no byte outside the rectangles is written."""
+    _decode_container_regions("wide", d_alc_ptr, alc_stride, sizes, d_frames_out_ptr, frame_width, frame_height, origins, stream)
+
+
+def wide_encode_to_budget_device(d_frames_ptr: int, width: int, height: int, frames: int, n_chunks: int,
+                                 wavelet_type: WaveletType, budgets, d_out_ptr: int, out_stride: int, min_quality: int = 10,
+                                 max_quality: int = 95, lane_symbols: int = 0, frame_width: int = 0, frame_height: int = 0,
+                                 origins=None, stream: int = 0) -> tuple:
+    """split_encode_to_budget_device for version 3: chunk i at the quality encode_wide_to_size's rule picks for budgets[i].
+    Returns (chosen, fits, sizes)."""
+    return _encode_container_to_budget("wide", d_frames_ptr, width, height, frames, n_chunks, wavelet_type, budgets, d_out_ptr,
+                                       out_stride, min_quality, max_quality, lane_symbols, frame_width, frame_height, origins, stream)

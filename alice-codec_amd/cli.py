@@ -4,7 +4,8 @@
     python -m alice_codec_amd.cli info INPUT.alc
 `encode --format split [--lane-symbols N]` writes the split-stream container (.alc version 2, DESIGN.md section 10);
 `--format wide` the wide container (.alc version 3, section 11: the one whose video comes back at the top of the quality
-scale); `--max-bytes` and `encode-chunks --kbps` work in v1 and split, and are refused with `--format wide`;
+scale); `--max-bytes` and `encode-chunks --kbps` work in v1 and split, and are still refused with `--format wide` here (the
+library has the version 3 budget encode, `encode_wide_to_size`; this front end does not call it yet);
 `decode` and `info` pick the format from the version byte unless `--format` names one.  The default of every subcommand
 is version 1.
 Like the reference it treats the whole input file as ONE chunk (src/bin/main.rs:117-122).  `encode-chunks`
@@ -32,7 +33,8 @@ def parse_wavelet(s: str) -> WaveletType:
 
 
 FORMAT_VERSION = {"v1": 1, "split": 2, "wide": 3}
-NO_WIDE_BUDGET = "--format wide has no size prediction yet: it cannot be combined with {}; use --format split or v1 for a byte budget"
+NO_WIDE_BUDGET = ("--format wide cannot be combined with {} on the command line yet: call encode_wide_to_size from the library for a "
+                  "version 3 byte budget, or use --format split or v1 here")
 
 
 def _container_version(a, data) -> int:

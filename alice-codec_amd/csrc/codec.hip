@@ -868,9 +868,11 @@ int coef_hist_chunk(const RgbLayout& rgb, const ChunkDims& d, int wavelet, Encod
 // A chunk with coefficients outside the value table's range (never for 8-bit RGB at the default radius) gets its step
 // histograms from the real forward pass at each of the 64 steps instead of the fold.  split_lane != 0: the brackets are
 // those of the split-stream channel payloads at that lane_symbols (rate.hip, split_cost_kernel) instead of the v1 streams.
+// wide (with split_lane): the wide container's -- the histograms are of the coded symbol min(z, 255) (fold_kernel<true>, and
+// the wide forward pass with its 2-byte symbols in the fallback) and the brackets are wide_cost_kernel's.
 // Returns after the stream has drained.
 int predict_chunks(const RgbLayout* rgb, uint32_t n, const ChunkDims& d, int wavelet, EncodeWork& w, hipStream_t st,
-                   uint32_t* d_step_hist, std::vector<RateChannel>& out, uint32_t split_lane = 0) {
+                   uint32_t* d_step_hist, std::vector<RateChannel>& out, uint32_t split_lane = 0, bool wide = false) {
     const size_t per_chunk = (size_t)64 * 3;
     DevBuf bins, oor, own_hist, res, logt, fsym;
     TRY(bins.alloc((size_t)n * 3 * 4096 * sizeof(uint32_t)));
@@ -885,20 +887,22 @@ int predict_chunks(const RgbLayout* rgb, uint32_t n, const ChunkDims& d, int wav
     HIP_TRY(hipMemsetAsync(oor.p, 0, (size_t)n * sizeof(uint32_t), st));
     for (uint32_t b = 0; b < n; ++b)
         TRY(coef_hist_chunk(rgb[b], d, wavelet, w, bins.as<uint32_t>() + (size_t)b * 3 * 4096, oor.as<uint32_t>() + b, st));
-    launch_rate_fold(bins.as<uint32_t>(), oor.as<uint32_t>(), n, d_step_hist, st);
+    if (wide) launch_rate_fold_wide(bins.as<uint32_t>(), oor.as<uint32_t>(), n, d_step_hist, st);
+    else launch_rate_fold(bins.as<uint32_t>(), oor.as<uint32_t>(), n, d_step_hist, st);
     std::vector<uint32_t> h_oor(n);
     HIP_TRY(hipMemcpyAsync(h_oor.data(), oor.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     for (uint32_t b = 0; b < n; ++b) {
         if (!h_oor[b]) continue;
-        if (!fsym.p) TRY(fsym.alloc(3 * d.padded));   // (not w.sym: a batch keeps its decoded pixels there)
+        if (!fsym.p) TRY(fsym.alloc(3 * d.padded * (wide ? 2 : 1)));   // (not w.sym: a batch keeps its decoded pixels there)
         for (int32_t step = 1; step <= 64; ++step) {
             uint32_t* h = d_step_hist + ((size_t)b * 64 + (size_t)(step - 1)) * 3 * 256;
             HIP_TRY(hipMemsetAsync(h, 0, 3 * 256 * sizeof(uint32_t), st));
-            TRY(forward_chunk(rgb[b], d, wavelet, step, w, fsym.as<uint8_t>(), h, st));
+            TRY(forward_chunk(rgb[b], d, wavelet, step, w, fsym.as<uint8_t>(), h, st, wide));
         }
     }
-    if (split_lane) launch_split_rate_cost(d_step_hist, logt.as<uint32_t>(), n, split_lane, res.as<RateChannel>(), st);
+    if (wide) launch_wide_rate_cost(d_step_hist, logt.as<uint32_t>(), n, split_lane, res.as<RateChannel>(), st);
+    else if (split_lane) launch_split_rate_cost(d_step_hist, logt.as<uint32_t>(), n, split_lane, res.as<RateChannel>(), st);
     else launch_rate_cost(d_step_hist, logt.as<uint32_t>(), n, res.as<RateChannel>(), st);
     HIP_TRY(hipGetLastError());
     out.resize((size_t)n * per_chunk);
@@ -3599,7 +3603,7 @@ void write_empty_split(uint8_t* p, uint8_t wavelet, uint32_t w, uint32_t h, uint
     }
 }
 
-// ---- size prediction and budget encodes of version 2 ----
+// ---- size prediction and budget encodes of versions 2 and 3 ----
 constexpr uint32_t kSplitRefineTrials = 4;   // ALICE_SPLIT_REFINE_TRIALS
 
 // Whole-container brackets of one chunk at the 101 qualities from its 64 x 3 channel payload brackets.
@@ -3642,11 +3646,12 @@ int split_choose_quality(const uint64_t* lo, const uint64_t* hi, uint64_t budget
 }
 
 // The qualities of n equal-shaped chunks under their budgets: one prediction pass per group, then the refinement trials
-// chunk by chunk.  Returns after the stream has drained; nothing is written.
+// chunk by chunk.  Returns after the stream has drained; nothing is written.  wide: version 3 -- a trial is the wide forward
+// pass, the table and the wide count pass, whose residual guard fails the call as it does in an encode.
 int split_choose_chunks(const RgbLayout* rgb, uint32_t n, const ChunkDims& d, uint8_t wavelet, uint32_t L, const uint64_t* budgets,
-                        uint8_t min_q, uint8_t max_q, uint8_t* chosen, uint8_t* fits, hipStream_t st) {
+                        uint8_t min_q, uint8_t max_q, uint8_t* chosen, uint8_t* fits, hipStream_t st, bool wide = false) {
     tl_split_trials.assign(n, 0u);
-    const uint32_t group = split_group(d);
+    const uint32_t group = split_group(d, wide);
     uint64_t lo[kQualities], hi[kQualities];
     for (uint32_t first = 0; first < n; first += group) {
         const uint32_t B = std::min(group, n - first);
@@ -3655,7 +3660,7 @@ int split_choose_chunks(const RgbLayout* rgb, uint32_t n, const ChunkDims& d, ui
             EncodeWork w;
             w.d = d; w.n_chunks = 1;
             if (transform_tiles_eligible(d)) TRY(w.scratch.alloc(forward_scratch_bytes(d)));
-            TRY(predict_chunks(rgb + first, B, d, wavelet, w, st, nullptr, rc, L));
+            TRY(predict_chunks(rgb + first, B, d, wavelet, w, st, nullptr, rc, L, wide));
         }
         for (uint32_t i = 0; i < B; ++i) {
             const uint32_t k = first + i;
@@ -3664,7 +3669,7 @@ int split_choose_chunks(const RgbLayout* rgb, uint32_t n, const ChunkDims& d, ui
                                      [&](uint8_t q, uint64_t* size) -> int {
                                          SplitChunkEncode e;
                                          std::vector<uint64_t> sz;
-                                         TRY(split_count_chunks(e, rgb + k, 1, d, wavelet, &q, L, st, sz));
+                                         TRY(split_count_chunks(e, rgb + k, 1, d, wavelet, &q, L, st, sz, wide));
                                          *size = sz[0];
                                          return kOk;
                                      },
@@ -3674,7 +3679,7 @@ int split_choose_chunks(const RgbLayout* rgb, uint32_t n, const ChunkDims& d, ui
     return kOk;
 }
 
-// n equal-shaped chunks at their layouts -> version 2 bytes at d_out + i * out_stride, in groups of split_group.
+// n equal-shaped chunks at their layouts -> version 2 (wide: version 3) bytes at d_out + i * out_stride, in groups of split_group.
 int split_encode_layouts(const RgbLayout* rgb, uint32_t n, const ChunkDims& d, uint8_t wavelet, const uint8_t* q, uint32_t L, void* d_out,
                          uint64_t out_stride, uint64_t* sizes, hipStream_t st, bool wide = false) {
     const uint32_t group = split_group(d, wide);
@@ -3721,10 +3726,10 @@ int split_layouts(const void* d_frames, uint32_t frame_width, uint32_t frame_hei
 }
 
 // wavelet, then lane_symbols (0: the default), in the order of the split calls
-int check_split_args(uint8_t wavelet_type, uint32_t lane_symbols, uint32_t* L) {
+int check_split_args(uint8_t wavelet_type, uint32_t lane_symbols, uint32_t* L, bool wide = false) {
     if (wavelet_type > 2) return fail(kInvalidBitstream, "unknown wavelet type");
     *L = lane_symbols ? lane_symbols : kSplitDefaultLane;
-    if (!split_lane_ok(*L)) return fail(kInvalidDimensions, "lane_symbols must be a power of two in [64, 16384]");
+    if (!split_lane_ok(*L, wide)) return fail(kInvalidDimensions, split_lane_msg(wide));
     return kOk;
 }
 
@@ -4058,10 +4063,11 @@ int alice_codec_dev_decode_wide(const void* d_alc, uint64_t alc_stride, const ui
     return container_dev_decode(d_alc, alc_stride, sizes, n_chunks, d_rgb_out, hip_stream, 3);
 }
 
-// ---- version 2: size prediction, budget encodes, regions of device frames ----
+// ---- versions 2 and 3: size prediction, budget encodes, regions of device frames.  One body per
+// call, the container as an argument (wide: version 3). ----
 
-int alice_codec_predict_split_sizes(uint8_t wavelet_type, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
-                                    uint32_t frames, uint32_t lane_symbols, uint64_t lo[101], uint64_t hi[101]) {
+static int container_predict_sizes(uint8_t wavelet_type, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
+                                   uint32_t frames, uint32_t lane_symbols, uint64_t lo[101], uint64_t hi[101], bool wide) {
     clear_error();
     if (!lo || !hi || (!rgb && rgb_len)) return fail(kNullArgument, "null argument");
     uint64_t n_pixels = 0;
@@ -4072,7 +4078,7 @@ int alice_codec_predict_split_sizes(uint8_t wavelet_type, const uint8_t* rgb, ui
     EncodedChunk* none = nullptr;
     if (n_pixels) TRY(validate_encode_many(&enc, rgb, rgb_len, width, height, frames, 1, &none, &d));
     uint32_t L = 0;
-    TRY(check_split_args(wavelet_type, lane_symbols, &L));
+    TRY(check_split_args(wavelet_type, lane_symbols, &L, wide));
     if (n_pixels == 0) {   // an empty chunk is its header at every quality
         for (int q = 0; q < kQualities; ++q) lo[q] = hi[q] = kSplitHeaderBytes;
         return kOk;
@@ -4087,19 +4093,31 @@ int alice_codec_predict_split_sizes(uint8_t wavelet_type, const uint8_t* rgb, ui
     HIP_TRY(hipMemcpyAsync(d_rgb.p, rgb, n_pixels * 3, hipMemcpyHostToDevice, st));
     const RgbLayout layout = packed_rgb(d_rgb.p, d);
     std::vector<RateChannel> rc;
-    TRY(predict_chunks(&layout, 1, d, wavelet_type, w, st, nullptr, rc, L));
+    TRY(predict_chunks(&layout, 1, d, wavelet_type, w, st, nullptr, rc, L, wide));
     split_rate_by_quality(rc.data(), lo, hi);
     return kOk;
 }
 
-int alice_codec_dev_predict_split_sizes(const void* d_rgb, uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks,
-                                        uint8_t wavelet_type, uint32_t lane_symbols, uint64_t* lo, uint64_t* hi, void* hip_stream) {
+int alice_codec_predict_split_sizes(uint8_t wavelet_type, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
+                                    uint32_t frames, uint32_t lane_symbols, uint64_t lo[101], uint64_t hi[101]) {
+    return container_predict_sizes(wavelet_type, rgb, rgb_len, width, height, frames, lane_symbols, lo, hi, false);
+}
+
+int alice_codec_predict_wide_sizes(uint8_t wavelet_type, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
+                                   uint32_t frames, uint32_t lane_symbols, uint64_t lo[101], uint64_t hi[101]) {
+    return container_predict_sizes(wavelet_type, rgb, rgb_len, width, height, frames, lane_symbols, lo, hi, true);
+}
+
+// d_step_hist: [chunk][step - 1][channel][256] u32 on the device, or null
+static int container_dev_predict_sizes(const void* d_rgb, uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks,
+                                       uint8_t wavelet_type, uint32_t lane_symbols, uint64_t* lo, uint64_t* hi, void* d_step_hist,
+                                       void* hip_stream, bool wide) {
     clear_error();
     if (!d_rgb || !lo || !hi) return fail(kNullArgument, "null argument");
     ChunkDims d{};
     TRY(chunk_dims(width, height, frames, &d, n_chunks));
     uint32_t L = 0;
-    TRY(check_split_args(wavelet_type, lane_symbols, &L));
+    TRY(check_split_args(wavelet_type, lane_symbols, &L, wide));
     TRY(ensure_device());
     hipStream_t st = (hipStream_t)hip_stream;
     ScopeStream scope(st);
@@ -4108,20 +4126,32 @@ int alice_codec_dev_predict_split_sizes(const void* d_rgb, uint32_t width, uint3
     if (transform_tiles_eligible(d)) TRY(w.scratch.alloc(forward_scratch_bytes(d)));
     std::vector<RgbLayout> layouts;
     TRY(split_layouts(d_rgb, 0, 0, nullptr, d, n_chunks, layouts));
-    const uint32_t group = split_group(d);
+    const uint32_t group = split_group(d, wide);
     for (uint32_t first = 0; first < n_chunks; first += group) {
         const uint32_t B = std::min(group, n_chunks - first);
         std::vector<RateChannel> rc;
-        TRY(predict_chunks(layouts.data() + first, B, d, wavelet_type, w, st, nullptr, rc, L));
+        uint32_t* sh = d_step_hist ? (uint32_t*)d_step_hist + (size_t)first * 64 * 3 * 256 : nullptr;
+        TRY(predict_chunks(layouts.data() + first, B, d, wavelet_type, w, st, sh, rc, L, wide));
         for (uint32_t i = 0; i < B; ++i)
             split_rate_by_quality(rc.data() + (size_t)i * 192, lo + (size_t)(first + i) * kQualities, hi + (size_t)(first + i) * kQualities);
     }
     return kOk;
 }
 
-uint8_t* alice_codec_encode_split_to_size(uint8_t wavelet_type, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
-                                          uint32_t frames, uint32_t lane_symbols, uint64_t max_bytes, uint8_t min_q, uint8_t max_q,
-                                          uint8_t* chosen_q, uint8_t* fits, uint64_t* out_len) {
+int alice_codec_dev_predict_split_sizes(const void* d_rgb, uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks,
+                                        uint8_t wavelet_type, uint32_t lane_symbols, uint64_t* lo, uint64_t* hi, void* hip_stream) {
+    return container_dev_predict_sizes(d_rgb, width, height, frames, n_chunks, wavelet_type, lane_symbols, lo, hi, nullptr, hip_stream, false);
+}
+
+int alice_codec_dev_predict_wide_sizes(const void* d_rgb, uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks,
+                                       uint8_t wavelet_type, uint32_t lane_symbols, uint64_t* lo, uint64_t* hi, void* d_step_hist,
+                                       void* hip_stream) {
+    return container_dev_predict_sizes(d_rgb, width, height, frames, n_chunks, wavelet_type, lane_symbols, lo, hi, d_step_hist, hip_stream, true);
+}
+
+static uint8_t* container_encode_to_size(uint8_t wavelet_type, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
+                                         uint32_t frames, uint32_t lane_symbols, uint64_t max_bytes, uint8_t min_q, uint8_t max_q,
+                                         uint8_t* chosen_q, uint8_t* fits, uint64_t* out_len, bool wide) {
     clear_error();
     if (!chosen_q || !fits || !out_len || (!rgb && rgb_len)) { fail(kNullArgument, "null argument"); return nullptr; }
     auto run = [&](uint8_t** out) -> int {
@@ -4133,7 +4163,7 @@ uint8_t* alice_codec_encode_split_to_size(uint8_t wavelet_type, const uint8_t* r
         EncodedChunk* none = nullptr;
         if (n_pixels) TRY(validate_encode_many(&enc, rgb, rgb_len, width, height, frames, 1, &none, &d));
         uint32_t L = 0;
-        TRY(check_split_args(wavelet_type, lane_symbols, &L));
+        TRY(check_split_args(wavelet_type, lane_symbols, &L, wide));
         TRY(check_quality_range(min_q, max_q));
         if (n_pixels == 0) {
             uint64_t lo[kQualities], hi[kQualities];
@@ -4143,7 +4173,7 @@ uint8_t* alice_codec_encode_split_to_size(uint8_t wavelet_type, const uint8_t* r
                                      &tl_split_trials[0]));
             *out = host_result_alloc(kSplitHeaderBytes);
             if (!*out) return fail(kOutOfMemory, "out of host memory");
-            write_empty_split(*out, wavelet_type, width, height, frames, L, quality_to_step(*chosen_q));
+            write_empty_split(*out, wavelet_type, width, height, frames, L, quality_to_step(*chosen_q), wide ? 3 : 2);
             *out_len = kSplitHeaderBytes;
             return kOk;
         }
@@ -4153,14 +4183,14 @@ uint8_t* alice_codec_encode_split_to_size(uint8_t wavelet_type, const uint8_t* r
         TRY(d_rgb.alloc(n_pixels * 3));
         HIP_TRY(hipMemcpyAsync(d_rgb.p, rgb, n_pixels * 3, hipMemcpyHostToDevice, st));
         const RgbLayout layout = packed_rgb(d_rgb.p, d);
-        TRY(split_choose_chunks(&layout, 1, d, wavelet_type, L, &max_bytes, min_q, max_q, chosen_q, fits, st));
+        TRY(split_choose_chunks(&layout, 1, d, wavelet_type, L, &max_bytes, min_q, max_q, chosen_q, fits, st, wide));
         std::vector<uint64_t> sizes;
         TRY(split_encode_chunks(&layout, 1, d, wavelet_type, chosen_q, L, st, sizes,
                                 [&](const std::vector<uint64_t>& sz, std::vector<uint8_t*>& outs) -> int {
                                     TRY(d_out.alloc(sz[0]));
                                     outs[0] = d_out.as<uint8_t>();
                                     return kOk;
-                                }));
+                                }, wide));
         *out = host_result_alloc(sizes[0]);
         if (!*out) return fail(kOutOfMemory, "out of host memory");
         const int rc = copy_to_host(*out, d_out.p, sizes[0], st);
@@ -4172,10 +4202,24 @@ uint8_t* alice_codec_encode_split_to_size(uint8_t wavelet_type, const uint8_t* r
     return run(&out) == kOk ? out : nullptr;
 }
 
-int alice_codec_dev_encode_split_regions(const void* d_frames, uint32_t frame_width, uint32_t frame_height, const uint32_t* origins,
-                                         uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks, uint8_t wavelet_type,
-                                         uint8_t quality, const uint8_t* qualities, uint32_t lane_symbols, void* d_out,
-                                         uint64_t out_stride, uint64_t* sizes, void* hip_stream) {
+uint8_t* alice_codec_encode_split_to_size(uint8_t wavelet_type, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
+                                          uint32_t frames, uint32_t lane_symbols, uint64_t max_bytes, uint8_t min_q, uint8_t max_q,
+                                          uint8_t* chosen_q, uint8_t* fits, uint64_t* out_len) {
+    return container_encode_to_size(wavelet_type, rgb, rgb_len, width, height, frames, lane_symbols, max_bytes, min_q, max_q, chosen_q,
+                                    fits, out_len, false);
+}
+
+uint8_t* alice_codec_encode_wide_to_size(uint8_t wavelet_type, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
+                                         uint32_t frames, uint32_t lane_symbols, uint64_t max_bytes, uint8_t min_q, uint8_t max_q,
+                                         uint8_t* chosen_q, uint8_t* fits, uint64_t* out_len) {
+    return container_encode_to_size(wavelet_type, rgb, rgb_len, width, height, frames, lane_symbols, max_bytes, min_q, max_q, chosen_q,
+                                    fits, out_len, true);
+}
+
+static int container_dev_encode_regions(const void* d_frames, uint32_t frame_width, uint32_t frame_height, const uint32_t* origins,
+                                        uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks, uint8_t wavelet_type,
+                                        uint8_t quality, const uint8_t* qualities, uint32_t lane_symbols, void* d_out,
+                                        uint64_t out_stride, uint64_t* sizes, void* hip_stream, bool wide) {
     clear_error();
     if (!d_frames || !origins || !d_out || !sizes) return fail(kNullArgument, "null argument");
     ChunkDims d{};
@@ -4183,18 +4227,34 @@ int alice_codec_dev_encode_split_regions(const void* d_frames, uint32_t frame_wi
     std::vector<RgbLayout> layouts;
     TRY(split_layouts(d_frames, frame_width, frame_height, origins, d, n_chunks, layouts));
     uint32_t L = 0;
-    TRY(check_split_args(wavelet_type, lane_symbols, &L));
+    TRY(check_split_args(wavelet_type, lane_symbols, &L, wide));
     TRY(ensure_device());
     hipStream_t st = (hipStream_t)hip_stream;
     ScopeStream scope(st);
     std::vector<uint8_t> q(n_chunks);
     for (uint32_t i = 0; i < n_chunks; ++i) q[i] = qualities ? qualities[i] : quality;
-    return split_encode_layouts(layouts.data(), n_chunks, d, wavelet_type, q.data(), L, d_out, out_stride, sizes, st);
+    return split_encode_layouts(layouts.data(), n_chunks, d, wavelet_type, q.data(), L, d_out, out_stride, sizes, st, wide);
 }
 
-int alice_codec_dev_decode_split_regions(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks,
-                                         void* d_frames_out, uint32_t frame_width, uint32_t frame_height, const uint32_t* origins,
-                                         void* hip_stream) {
+int alice_codec_dev_encode_split_regions(const void* d_frames, uint32_t frame_width, uint32_t frame_height, const uint32_t* origins,
+                                         uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks, uint8_t wavelet_type,
+                                         uint8_t quality, const uint8_t* qualities, uint32_t lane_symbols, void* d_out,
+                                         uint64_t out_stride, uint64_t* sizes, void* hip_stream) {
+    return container_dev_encode_regions(d_frames, frame_width, frame_height, origins, width, height, frames, n_chunks, wavelet_type, quality,
+                                        qualities, lane_symbols, d_out, out_stride, sizes, hip_stream, false);
+}
+
+int alice_codec_dev_encode_wide_regions(const void* d_frames, uint32_t frame_width, uint32_t frame_height, const uint32_t* origins,
+                                        uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks, uint8_t wavelet_type,
+                                        uint8_t quality, const uint8_t* qualities, uint32_t lane_symbols, void* d_out,
+                                        uint64_t out_stride, uint64_t* sizes, void* hip_stream) {
+    return container_dev_encode_regions(d_frames, frame_width, frame_height, origins, width, height, frames, n_chunks, wavelet_type, quality,
+                                        qualities, lane_symbols, d_out, out_stride, sizes, hip_stream, true);
+}
+
+static int container_dev_decode_regions(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks,
+                                        void* d_frames_out, uint32_t frame_width, uint32_t frame_height, const uint32_t* origins,
+                                        void* hip_stream, int version) {
     clear_error();
     if (!d_alc || !sizes || !d_frames_out || !origins) return fail(kNullArgument, "null argument");
     if (n_chunks == 0) return fail(kInvalidDimensions, "empty batch");
@@ -4209,13 +4269,25 @@ int alice_codec_dev_decode_split_regions(const void* d_alc, uint64_t alc_stride,
     ScopeStream scope(st);
     return split_decode_device(d_alc, alc_stride, sizes, n_chunks, st, [&](const ChunkDims& d, std::vector<RgbLayout>& out) {
         return split_layouts(d_frames_out, frame_width, frame_height, origins, d, n_chunks, out);
-    });
+    }, version);
 }
 
-int alice_codec_dev_encode_split_to_budget(const void* d_frames, uint32_t frame_width, uint32_t frame_height, const uint32_t* origins,
-                                           uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks, uint8_t wavelet_type,
-                                           uint32_t lane_symbols, const uint64_t* budgets, uint8_t min_q, uint8_t max_q, uint8_t* chosen,
-                                           uint8_t* fits, void* d_out, uint64_t out_stride, uint64_t* sizes, void* hip_stream) {
+int alice_codec_dev_decode_split_regions(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks,
+                                         void* d_frames_out, uint32_t frame_width, uint32_t frame_height, const uint32_t* origins,
+                                         void* hip_stream) {
+    return container_dev_decode_regions(d_alc, alc_stride, sizes, n_chunks, d_frames_out, frame_width, frame_height, origins, hip_stream, 2);
+}
+
+int alice_codec_dev_decode_wide_regions(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks,
+                                        void* d_frames_out, uint32_t frame_width, uint32_t frame_height, const uint32_t* origins,
+                                        void* hip_stream) {
+    return container_dev_decode_regions(d_alc, alc_stride, sizes, n_chunks, d_frames_out, frame_width, frame_height, origins, hip_stream, 3);
+}
+
+static int container_dev_encode_to_budget(const void* d_frames, uint32_t frame_width, uint32_t frame_height, const uint32_t* origins,
+                                          uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks, uint8_t wavelet_type,
+                                          uint32_t lane_symbols, const uint64_t* budgets, uint8_t min_q, uint8_t max_q, uint8_t* chosen,
+                                          uint8_t* fits, void* d_out, uint64_t out_stride, uint64_t* sizes, void* hip_stream, bool wide) {
     clear_error();
     if (!d_frames || !budgets || !chosen || !fits || !d_out || !sizes) return fail(kNullArgument, "null argument");
     ChunkDims d{};
@@ -4223,7 +4295,7 @@ int alice_codec_dev_encode_split_to_budget(const void* d_frames, uint32_t frame_
     std::vector<RgbLayout> layouts;
     TRY(split_layouts(d_frames, frame_width, frame_height, origins, d, n_chunks, layouts));
     uint32_t L = 0;
-    TRY(check_split_args(wavelet_type, lane_symbols, &L));
+    TRY(check_split_args(wavelet_type, lane_symbols, &L, wide));
     TRY(check_quality_range(min_q, max_q));
     TRY(ensure_device());
     hipStream_t st = (hipStream_t)hip_stream;
@@ -4231,10 +4303,26 @@ int alice_codec_dev_encode_split_to_budget(const void* d_frames, uint32_t frame_
     // the choices reach the caller only with the bytes: a failed call leaves chosen / fits / sizes as they were
     std::vector<uint8_t> q(n_chunks), ok(n_chunks);
     std::vector<uint64_t> sz(n_chunks);
-    TRY(split_choose_chunks(layouts.data(), n_chunks, d, wavelet_type, L, budgets, min_q, max_q, q.data(), ok.data(), st));
-    TRY(split_encode_layouts(layouts.data(), n_chunks, d, wavelet_type, q.data(), L, d_out, out_stride, sz.data(), st));
+    TRY(split_choose_chunks(layouts.data(), n_chunks, d, wavelet_type, L, budgets, min_q, max_q, q.data(), ok.data(), st, wide));
+    TRY(split_encode_layouts(layouts.data(), n_chunks, d, wavelet_type, q.data(), L, d_out, out_stride, sz.data(), st, wide));
     for (uint32_t i = 0; i < n_chunks; ++i) { chosen[i] = q[i]; fits[i] = ok[i]; sizes[i] = sz[i]; }
     return kOk;
+}
+
+int alice_codec_dev_encode_split_to_budget(const void* d_frames, uint32_t frame_width, uint32_t frame_height, const uint32_t* origins,
+                                           uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks, uint8_t wavelet_type,
+                                           uint32_t lane_symbols, const uint64_t* budgets, uint8_t min_q, uint8_t max_q, uint8_t* chosen,
+                                           uint8_t* fits, void* d_out, uint64_t out_stride, uint64_t* sizes, void* hip_stream) {
+    return container_dev_encode_to_budget(d_frames, frame_width, frame_height, origins, width, height, frames, n_chunks, wavelet_type,
+                                          lane_symbols, budgets, min_q, max_q, chosen, fits, d_out, out_stride, sizes, hip_stream, false);
+}
+
+int alice_codec_dev_encode_wide_to_budget(const void* d_frames, uint32_t frame_width, uint32_t frame_height, const uint32_t* origins,
+                                          uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks, uint8_t wavelet_type,
+                                          uint32_t lane_symbols, const uint64_t* budgets, uint8_t min_q, uint8_t max_q, uint8_t* chosen,
+                                          uint8_t* fits, void* d_out, uint64_t out_stride, uint64_t* sizes, void* hip_stream) {
+    return container_dev_encode_to_budget(d_frames, frame_width, frame_height, origins, width, height, frames, n_chunks, wavelet_type,
+                                          lane_symbols, budgets, min_q, max_q, chosen, fits, d_out, out_stride, sizes, hip_stream, true);
 }
 
 uint32_t alice_codec_test_last_split_trials(uint32_t* per_chunk, uint32_t cap) {

@@ -265,12 +265,17 @@ const RateLogTable& rate_log_table();
 void launch_coef_hist(const int32_t* d_vol, uint64_t n, uint32_t* d_bins, uint32_t* d_oor, hipStream_t st);
 // step_hist: [chunk][step - 1][channel][256]; chunks with a non-zero out-of-range counter are left alone
 void launch_rate_fold(const uint32_t* d_bins, const uint32_t* d_oor, uint32_t n_chunks, uint32_t* d_step_hist, hipStream_t st);
+// the same over the coded symbol of the wide container, min(z, 255): bin 255 is the number of escapes
+void launch_rate_fold_wide(const uint32_t* d_bins, const uint32_t* d_oor, uint32_t n_chunks, uint32_t* d_step_hist, hipStream_t st);
 // d_log: the lo and hi arrays of rate_log_table() back to back on the device; out: [chunk][step - 1][channel]
 void launch_rate_cost(const uint32_t* d_step_hist, const uint32_t* d_log, uint32_t n_chunks, RateChannel* d_out, hipStream_t st);
 // the same for the channel payloads of the split-stream container at `lane_symbols` (status is always kRateBounded; a
 // histogram without symbols gives 0 / 0)
 void launch_split_rate_cost(const uint32_t* d_step_hist, const uint32_t* d_log, uint32_t n_chunks, uint32_t lane_symbols,
                             RateChannel* d_out, hipStream_t st);
+// the same for the channel payloads of the wide container (.alc v3) over the histograms of launch_rate_fold_wide
+void launch_wide_rate_cost(const uint32_t* d_step_hist, const uint32_t* d_log, uint32_t n_chunks, uint32_t lane_symbols,
+                           RateChannel* d_out, hipStream_t st);
 
 // ---- split.hip: the split-stream entropy stage of .alc v2 ----
 constexpr uint32_t kSplitFixedHeaderBytes = 22;      // magic, version, wavelet, width, height, frames, lane_symbols

@@ -6,7 +6,8 @@
 // step: fold_kernel relabels the bins through the encoder's own value -> symbol map (quant_sym1).  cost_kernel then
 // builds the reference table of each folded histogram (freq_table_256, the code the encoder's table kernel runs),
 // classifies it and brackets the stream length.  split_cost_kernel does the same for the split-stream container, with that
-// format's normalisation rule and per-lane overheads.
+// format's normalisation rule and per-lane overheads, and wide_cost_kernel for the wide container (.alc v3) over the
+// histograms of fold_kernel<true>: the coded symbol min(z, 255), with the 12-bit residual of every escape priced in.
 //
 // The bracket (per channel; n = number of symbols, f = a symbol's table frequency, encoder of src/rans.rs:244-308):
 //   The state starts at x0 = 2^23.  Before a symbol it is renormalised (x >>= 8, one byte out, while x >= f * 2^19) and
@@ -67,6 +68,8 @@ void launch_coef_hist(const int32_t* d_vol, uint64_t n, uint32_t* d_bins, uint32
 
 // One workgroup per (chunk, channel, step - 1): step_hist[((chunk * 64 + step - 1) * 3 + ch) * 256 + symbol].  Chunks with
 // out-of-range coefficients are skipped (the host fills their histograms from real forward passes).
+// WIDE: the coded symbol of .alc v3, min(z, 255) with z the untruncated zigzag (quant_sym1_wide); bin 255 counts the escapes.
+template <bool WIDE>
 __global__ __launch_bounds__(256) void fold_kernel(const uint32_t* __restrict__ bins, const uint32_t* __restrict__ oor,
                                                    uint32_t qr, uint32_t* __restrict__ step_hist) {
     __shared__ uint32_t sh[256];
@@ -82,7 +85,9 @@ __global__ __launch_bounds__(256) void fold_kernel(const uint32_t* __restrict__ 
         const uint32_t c = b[i];
         if (!c) continue;
         const int val = (int)i - (int)qr;
-        const uint32_t s = step == 1u ? quant_sym1<true>(val, hdz, magic) : quant_sym1<false>(val, hdz, magic);
+        uint32_t s;
+        if (WIDE) s = min(step == 1u ? quant_sym1_wide<true>(val, hdz, magic) : quant_sym1_wide<false>(val, hdz, magic), 255u);
+        else s = step == 1u ? quant_sym1<true>(val, hdz, magic) : quant_sym1<false>(val, hdz, magic);
         atomicAdd(&sh[s], c);
     }
     __syncthreads();
@@ -160,8 +165,53 @@ __global__ __launch_bounds__(256) void split_cost_kernel(const uint32_t* __restr
     }
 }
 
+// The same for the wide container (.alc v3): one workgroup per (chunk, channel, step - 1) over the histogram
+// of the coded symbol min(z, 255).  E = hist[255] is the number of escapes, and each escape is followed in its lane chain by
+// the residual step: an ordinary step with frequency 1 and cum r (cum + f <= 4096, so e = 0) that renormalises against
+// 1 * 2^19 and then sets x' = 4096 x + r with 2^11 <= x < 2^19 (11.1) -- the per-step argument at the top of this file
+// with f = 1: growth (4096 / 1)(1 + d), 0 <= d < 2^-11, a byte out drops less than 2^-11 of the state.  A lane is a chain
+// of n_lane + E_lane steps with e = 0, and a residual costs exactly log2(4096 / 1) = 12 bits in both table sums:
+//   steps = n + E      T_lo = S_lo + 12 one E      T_hi = S_hi + 12 one E
+// in split_cost_kernel's formula with steps for n in the g terms.  With E = 0 it is that kernel's bracket integer for
+// integer.  Every table is bounded (1 <= f <= 4096), so there is no status array.  n <= 2^32 and E <= n give steps <= 2^33:
+// T <= 12 * 2^24 * 2^33 < 2^61, steps * g < 2^33 * 2^14 and 8 K 2^24 <= 2^59, so every product and sum stays below 2^62.
+__global__ __launch_bounds__(256) void wide_cost_kernel(const uint32_t* __restrict__ step_hist, const uint32_t* __restrict__ log_lo,
+                                                        const uint32_t* __restrict__ log_hi, uint32_t g_up, uint32_t g_dn,
+                                                        uint32_t lane_symbols, RateChannel* __restrict__ out) {
+    __shared__ unsigned long long red64[4];
+    __shared__ uint32_t red32[4];
+    __shared__ uint32_t escapes;
+    const uint32_t count = step_hist[(size_t)blockIdx.x * 256 + threadIdx.x];
+    if (threadIdx.x == 255u) escapes = count;   // (the barriers of the normalisation order it before thread 0 reads)
+    unsigned long long n;
+    const uint32_t f = split_normalize_256(count, red64, red32, n);
+    const unsigned long long s_lo = block_sum_256(count ? (unsigned long long)count * log_lo[f] : 0ull, red64);
+    const unsigned long long s_hi = block_sum_256(count ? (unsigned long long)count * log_hi[f] : 0ull, red64);
+    if (threadIdx.x == 0) {
+        RateChannel r{};
+        r.status = kRateBounded;
+        if (n) {
+            const unsigned long long one = 1ull << kRateFracBits, per_block = 64ull * lane_symbols;
+            const unsigned long long blocks = (n + per_block - 1ull) / per_block;
+            const unsigned long long last = n - (blocks - 1ull) * per_block;   // symbols of the last block, >= 1
+            const unsigned long long lanes = 64ull * (blocks - 1ull) + (last < 64ull ? last : 64ull);
+            const unsigned long long fixed = 132ull * blocks + 4ull * lanes;
+            const unsigned long long e = escapes, steps = n + e;
+            const unsigned long long t_lo = s_lo + 12ull * one * e, t_hi = s_hi + 12ull * one * e;
+            r.hi = fixed + (t_hi + steps * g_up) / (8ull * one);
+            const unsigned long long sub = steps * g_dn + 8ull * lanes * one;
+            r.lo = fixed + (t_lo > sub ? (t_lo - sub + 8ull * one + g_dn - 1ull) / (8ull * one + g_dn) : 0ull);
+        }
+        out[blockIdx.x] = r;
+    }
+}
+
 void launch_rate_fold(const uint32_t* d_bins, const uint32_t* d_oor, uint32_t n_chunks, uint32_t* d_step_hist, hipStream_t st) {
-    hipLaunchKernelGGL(fold_kernel, dim3(n_chunks * 192u), dim3(256), 0, st, d_bins, d_oor, (uint32_t)value_table_radius(), d_step_hist);
+    hipLaunchKernelGGL(fold_kernel<false>, dim3(n_chunks * 192u), dim3(256), 0, st, d_bins, d_oor, (uint32_t)value_table_radius(), d_step_hist);
+}
+
+void launch_rate_fold_wide(const uint32_t* d_bins, const uint32_t* d_oor, uint32_t n_chunks, uint32_t* d_step_hist, hipStream_t st) {
+    hipLaunchKernelGGL(fold_kernel<true>, dim3(n_chunks * 192u), dim3(256), 0, st, d_bins, d_oor, (uint32_t)value_table_radius(), d_step_hist);
 }
 
 void launch_rate_cost(const uint32_t* d_step_hist, const uint32_t* d_log, uint32_t n_chunks, RateChannel* d_out, hipStream_t st) {
@@ -174,6 +224,13 @@ void launch_split_rate_cost(const uint32_t* d_step_hist, const uint32_t* d_log, 
                             RateChannel* d_out, hipStream_t st) {
     const RateLogTable& t = rate_log_table();
     hipLaunchKernelGGL(split_cost_kernel, dim3(n_chunks * 192u), dim3(256), 0, st, d_step_hist, d_log, d_log + (kProbScale + 1),
+                       t.g_up, t.g_dn, lane_symbols, d_out);
+}
+
+void launch_wide_rate_cost(const uint32_t* d_step_hist, const uint32_t* d_log, uint32_t n_chunks, uint32_t lane_symbols,
+                           RateChannel* d_out, hipStream_t st) {
+    const RateLogTable& t = rate_log_table();
+    hipLaunchKernelGGL(wide_cost_kernel, dim3(n_chunks * 192u), dim3(256), 0, st, d_step_hist, d_log, d_log + (kProbScale + 1),
                        t.g_up, t.g_dn, lane_symbols, d_out);
 }
 

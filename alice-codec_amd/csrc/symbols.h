@@ -19,4 +19,15 @@ __device__ __forceinline__ uint32_t quant_sym1(int val, uint32_t hdz, uint32_t m
     return sat_sub_u32((q << 1) + ((uint32_t)val >> 31), 1u) & 0xFFu;
 }
 
+// The wide symbol of .alc v3: quant_sym1 without its `& 0xFF`, clamped at 65535 -- the untruncated
+// zigzag z.  Derived from quant_sym4_wide in transform.hip (the map the wide forward pass stores), one value at a time: the
+// same operations in the same order, so the fold of the rate prediction (rate.hip) and the encoder cannot disagree.
+template <bool STEP1>
+__device__ __forceinline__ uint32_t quant_sym1_wide(int val, uint32_t hdz, uint32_t magic) {
+    const uint32_t mag = (uint32_t)max(val, -val);
+    const uint32_t adj = sat_sub_u32(mag, hdz);
+    const uint32_t q = STEP1 ? adj : __umulhi(adj, magic);
+    return min(sat_sub_u32((q << 1) + ((uint32_t)val >> 31), 1u), 65535u);
+}
+
 }  // namespace alice

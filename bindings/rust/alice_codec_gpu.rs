@@ -654,6 +654,11 @@ extern "C" {
     fn alice_codec_encode_split_to_size(wavelet: u8, rgb: *const u8, rgb_len: u64, w: u32, h: u32, f: u32, lane_symbols: u32,
                                         max_bytes: u64, min_q: u8, max_q: u8, chosen_q: *mut u8, fits: *mut u8,
                                         out_len: *mut u64) -> *mut u8;
+    fn alice_codec_predict_wide_sizes(wavelet: u8, rgb: *const u8, rgb_len: u64, w: u32, h: u32, f: u32, lane_symbols: u32,
+                                      lo: *mut u64, hi: *mut u64) -> c_int;
+    fn alice_codec_encode_wide_to_size(wavelet: u8, rgb: *const u8, rgb_len: u64, w: u32, h: u32, f: u32, lane_symbols: u32,
+                                       max_bytes: u64, min_q: u8, max_q: u8, chosen_q: *mut u8, fits: *mut u8,
+                                       out_len: *mut u64) -> *mut u8;
 }
 
 pub const SPLIT_DEFAULT_LANE_SYMBOLS: u32 = 512;
@@ -869,4 +874,37 @@ pub unsafe fn wide_encode_device(d_rgb: *const std::ffi::c_void, width: u32, hei
 pub unsafe fn wide_decode_device(d_alc: *const std::ffi::c_void, alc_stride: u64, sizes: &[u64], d_rgb_out: *mut std::ffi::c_void,
                                  hip_stream: *mut std::ffi::c_void) -> Result<(), CodecError> {
     check(alice_codec_dev_decode_wide(d_alc, alc_stride, sizes.as_ptr(), sizes.len() as u32, d_rgb_out, hip_stream), 0, 0)
+}
+
+
+// version 3 rate control: the twins of `predict_split_sizes` / `encode_split_to_size`.
+
+/// The bracket of `encode_wide`'s length at the 101 qualities, from one forward transform on the GPU.  Every version 3
+/// table is bounded, so `status` stays 0 throughout.
+pub fn predict_wide_sizes(rgb_frames: &[u8], width: u32, height: u32, frames: u32, wavelet_type: WaveletType, lane_symbols: u32)
+    -> Result<SizePrediction, CodecError> {
+    let mut p = SizePrediction { lo: [0; 101], hi: [0; 101], status: [0; 101] };
+    let rc = unsafe {
+        alice_codec_predict_wide_sizes(wavelet_type as u8, rgb_frames.as_ptr(), rgb_frames.len() as u64, width, height, frames,
+                                        lane_symbols, p.lo.as_mut_ptr(), p.hi.as_mut_ptr())
+    };
+    let expected = (width as usize).saturating_mul(height as usize).saturating_mul(frames as usize).saturating_mul(3);
+    check(rc, expected, rgb_frames.len()).map(|_| p)
+}
+
+/// One chunk as version 3 bytes at the quality the budget rule picks in `[min_quality, max_quality]`: the largest whose
+/// predicted upper bound fits `max_bytes`, refined by at most four exact size counts among the qualities whose bracket
+/// straddles the budget (a trial is the wide forward pass, the table and the wide count pass).  Returns `(bytes, quality, fits)`; `fits` is false when not even `min_quality` is guaranteed to fit.
+pub fn encode_wide_to_size(rgb_frames: &[u8], width: u32, height: u32, frames: u32, max_bytes: u64, wavelet_type: WaveletType,
+                           min_quality: u8, max_quality: u8, lane_symbols: u32) -> Result<(Vec<u8>, u8, bool), CodecError> {
+    let (mut q, mut fits, mut n) = (0u8, 0u8, 0u64);
+    unsafe {
+        let p = alice_codec_encode_wide_to_size(wavelet_type as u8, rgb_frames.as_ptr(), rgb_frames.len() as u64, width, height,
+                                                 frames, lane_symbols, max_bytes, min_quality, max_quality, &mut q, &mut fits, &mut n);
+        if p.is_null() {
+            let expected = (width as usize).saturating_mul(height as usize).saturating_mul(frames as usize).saturating_mul(3);
+            return Err(last_error(expected, rgb_frames.len(), width, height, 0));
+        }
+        Ok((take(p, n), q, fits != 0))
+    }
 }

@@ -460,8 +460,8 @@ int alice_codec_dev_decode_split(const void *d_alc, uint64_t alc_stride, const u
  * it for qualities whose step lets z reach 255; below that its pixels are version 2's and its bytes differ only where the
  * symbol 255 occurs.  lane_symbols: a power of two in [64, 8192] (a symbol emits up to 4 bytes and a lane stream must fit
  * its u16 directory entry), 0 for the default.  The version 2 calls refuse version 3 data and these refuse versions 1 and
- * 2 ("unsupported version").  Size prediction, byte budgets and region calls exist for version 2 only.  Every call
- * validates like its version 2 twin, in the same order. */
+ * 2 ("unsupported version").  Size prediction, byte budgets and region calls of version 3 are declared at the end of this
+ * header, behind their version 2 twins.  Every call validates like its version 2 twin, in the same order. */
 /* the most bytes a channel payload of n wide symbols takes (0: lane_symbols out of range or n above 2^32 - 1) */
 uint64_t alice_codec_wide_stream_bound(uint64_t n, uint32_t lane_symbols);
 /* stage pair on one channel: n device symbols z as u16; hist is over min(z, 255) and must count exactly n.  As for
@@ -538,6 +538,43 @@ int alice_codec_dev_encode_split_to_budget(const void *d_frames, uint32_t frame_
                                            uint32_t lane_symbols, const uint64_t *budgets, uint8_t min_q, uint8_t max_q,
                                            uint8_t *chosen, uint8_t *fits, void *d_out, uint64_t out_stride, uint64_t *sizes,
                                            void *hip_stream);
+
+/* ---- version 3: size prediction, byte budgets, regions of device frames ----
+ * The calls above for the wide container: the same bodies with the version as an argument, the same validation in the
+ * same order before a device is looked for, with lane_symbols a power of two in [64, 8192] (16384 is refused), the same
+ * budget rule and ALICE_SPLIT_REFINE_TRIALS.  The histogram priced is of the coded symbol min(z, 255); its bin 255 is the
+ * number of escapes E, and each escape adds one chain step of exactly 12 bits (the residual), so the bracket is version 2's
+ * with n + E steps and 12 E more bits.  A trial is the wide forward pass, the table and the wide count pass; the residual
+ * guard applies to it as to an encode (ALICE_ERR_INTERNAL before a byte is written). */
+/* lo[q] <= length of alice_codec_encode_wide at quality q <= hi[q] for q = 0 .. 100.  A chunk without pixels is 1630 / 1630. */
+int alice_codec_predict_wide_sizes(uint8_t wavelet_type, const uint8_t *rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
+                                   uint32_t frames, uint32_t lane_symbols, uint64_t lo[101], uint64_t hi[101]);
+/* n_chunks packed device chunks; lo / hi: n_chunks * 101.  d_step_hist: NULL, or device memory for n_chunks * 64 * 3 * 256
+ * u32 that receives the histograms of the coded symbol behind the prediction, [chunk][step - 1][channel][symbol]. */
+int alice_codec_dev_predict_wide_sizes(const void *d_rgb, uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks,
+                                       uint8_t wavelet_type, uint32_t lane_symbols, uint64_t *lo, uint64_t *hi, void *d_step_hist,
+                                       void *hip_stream);
+/* alice_codec_encode_split_to_size for version 3: the bytes are exactly alice_codec_encode_wide's at *chosen_q. */
+uint8_t *alice_codec_encode_wide_to_size(uint8_t wavelet_type, const uint8_t *rgb, uint64_t rgb_len, uint32_t width,
+                                         uint32_t height, uint32_t frames, uint32_t lane_symbols, uint64_t max_bytes,
+                                         uint8_t min_q, uint8_t max_q, uint8_t *chosen_q, uint8_t *fits, uint64_t *out_len);
+/* alice_codec_dev_encode_split_regions / _dev_decode_split_regions for version 3: the bytes of chunk i are
+ * alice_codec_encode_wide's of the crop; a rectangle outside the frame is ALICE_ERR_INVALID_DIMENSIONS with nothing queued
+ * or written; a decode writes no byte outside the rectangles. */
+int alice_codec_dev_encode_wide_regions(const void *d_frames, uint32_t frame_width, uint32_t frame_height, const uint32_t *origins,
+                                        uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks, uint8_t wavelet_type,
+                                        uint8_t quality, const uint8_t *qualities, uint32_t lane_symbols, void *d_out,
+                                        uint64_t out_stride, uint64_t *sizes, void *hip_stream);
+int alice_codec_dev_decode_wide_regions(const void *d_alc, uint64_t alc_stride, const uint64_t *sizes, uint32_t n_chunks,
+                                        void *d_frames_out, uint32_t frame_width, uint32_t frame_height, const uint32_t *origins,
+                                        void *hip_stream);
+/* alice_codec_dev_encode_split_to_budget for version 3: packed chunks when origins == NULL, regions otherwise; the trials run
+ * chunk by chunk and the final encode in the groups of alice_codec_dev_encode_wide. */
+int alice_codec_dev_encode_wide_to_budget(const void *d_frames, uint32_t frame_width, uint32_t frame_height, const uint32_t *origins,
+                                          uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks, uint8_t wavelet_type,
+                                          uint32_t lane_symbols, const uint64_t *budgets, uint8_t min_q, uint8_t max_q,
+                                          uint8_t *chosen, uint8_t *fits, void *d_out, uint64_t out_stride, uint64_t *sizes,
+                                          void *hip_stream);
 
 #ifdef __cplusplus
 }

@@ -674,6 +674,29 @@ inline SizedSplit encode_split_to_size(const std::vector<uint8_t>& rgb, uint32_t
     return SizedSplit{detail::take(p, n), q, fits != 0};
 }
 
+// version 3 rate control: the same two calls for the wide container -- the bracket prices the 12-bit
+// residual of every escape, the budget rule and its trial cap are version 2's, the bytes are encode_wide's at the chosen
+// quality.  lane_symbols: a power of two in [64, 8192], 0 for the default.
+inline SizePrediction predict_wide_sizes(const std::vector<uint8_t>& rgb, uint32_t w, uint32_t h, uint32_t f,
+                                         WaveletType wt = WaveletType::Cdf53, uint32_t lane_symbols = 0) {
+    static const uint8_t empty = 0;
+    SizePrediction p;
+    detail::check(alice_codec_predict_wide_sizes(static_cast<uint8_t>(wt), rgb.empty() ? &empty : rgb.data(), rgb.size(), w, h, f,
+                                                 lane_symbols, p.lo.data(), p.hi.data()));
+    return p;
+}
+inline SizedSplit encode_wide_to_size(const std::vector<uint8_t>& rgb, uint32_t w, uint32_t h, uint32_t f, uint64_t max_bytes,
+                                      WaveletType wt = WaveletType::Cdf53, uint8_t min_quality = 10, uint8_t max_quality = 95,
+                                      uint32_t lane_symbols = 0) {
+    static const uint8_t empty = 0;
+    uint8_t q = 0, fits = 0;
+    uint64_t n = 0;
+    uint8_t* p = alice_codec_encode_wide_to_size(static_cast<uint8_t>(wt), rgb.empty() ? &empty : rgb.data(), rgb.size(), w, h, f,
+                                                 lane_symbols, max_bytes, min_quality, max_quality, &q, &fits, &n);
+    if (!p) detail::raise();
+    return SizedSplit{detail::take(p, n), q, fits != 0};
+}
+
 // The reference's buffer-model rate control (src/rate_control.rs:7-219), host only, with the Rust integer behaviour:
 // u32::midpoint start, buffer half full, 30-entry history, +-0.3 thresholds with +1 / -2 steps, saturating f64 casts
 // (NaN -> 0), wrapping integer casts.

@@ -90,8 +90,9 @@ void alice_codec_test_rate_log_table(uint32_t lo[4097], uint32_t hi[4097], uint3
  * run exact reference arithmetic whatever this says.  No device needed. */
 int alice_codec_test_inverse_variant(uint8_t wavelet_type, const int32_t step[3], int wide);
 
-/* The last version 2 budget call of the calling thread (alice_codec_encode_split_to_size,
- * alice_codec_dev_encode_split_to_budget): returns its number of chunks and writes the refinement trials (exact sizes
+/* The last version 2 or version 3 budget call of the calling thread (alice_codec_encode_split_to_size,
+ * alice_codec_dev_encode_split_to_budget, alice_codec_encode_wide_to_size, alice_codec_dev_encode_wide_to_budget),
+ * whichever came last: returns its number of chunks and writes the refinement trials (exact sizes
  * computed, at most ALICE_SPLIT_REFINE_TRIALS each) of the first min(that, cap) chunks to per_chunk (may be NULL). */
 uint32_t alice_codec_test_last_split_trials(uint32_t *per_chunk, uint32_t cap);
 

@@ -14,6 +14,12 @@ prediction timed next to the v1 prediction in the same run (they differ by the c
 encode_split at q = 50 / 80 / 95, and encode_split_to_size at the three budgets with its refinement trials and wall time.
 
   python scripts/rate_probe.py --format split --out profiles/r08_split_rate_probe_1080p64.json
+
+--format wide: the same for the wide container (.alc version 3): the v3 prediction timed next to the v2
+prediction in the same run (they differ by the fold and the cost kernel only), the bracket against encode_wide at
+q = 90 / 95 / 100, and encode_wide_to_size at those three sizes with its refinement trials and wall time.
+
+  python scripts/rate_probe.py --format wide --chunks 1 --out profiles/r11_wide_rate_probe_1080p64.json
 """
 import argparse
 import ctypes as C
@@ -81,13 +87,50 @@ def split_probe(args, lib, rgb, wt):
     print(json.dumps(res))
 
 
+def wide_probe(args, lib, rgb, wt):
+    L = args.lane_symbols
+    n = args.chunks
+    _, v2_ms = _timed_prediction(lambda: a.predict_split_sizes_device(rgb.data_ptr(), W, H, F, n, wt, L), args.reps, n)
+    p, v3_ms = _timed_prediction(lambda: a.predict_wide_sizes_device(rgb.data_ptr(), W, H, F, n, wt, L), args.reps, n)
+    _, v2_ms_again = _timed_prediction(lambda: a.predict_split_sizes_device(rgb.data_ptr(), W, H, F, n, wt, L), args.reps, n)
+    host = rgb[0].cpu().numpy()
+    actual = {}
+    for q in (90, 95, 100):
+        size = len(a.encode_wide(a.FrameEncoder.with_wavelet(q, wt), host, W, H, F, L))
+        lo, hi = int(p.lo[0][q]), int(p.hi[0][q])
+        actual[q] = {"lo": lo, "actual": size, "hi": hi, "rel_width": (hi - lo) / hi, "inside": lo <= size <= hi}
+    trials = np.zeros(1, np.uint32)
+    rows = []
+    for q in (90, 95, 100):
+        budget = actual[q]["actual"]
+        a.encode_wide_to_size(host, W, H, F, budget, wt, 10, 100, L)   # warm-up of the pool for this size
+        t = time.perf_counter()
+        data, cq, fits = a.encode_wide_to_size(host, W, H, F, budget, wt, 10, 100, L)
+        ms = (time.perf_counter() - t) * 1e3
+        lib.alice_codec_test_last_split_trials(trials.ctypes.data_as(C.POINTER(C.c_uint32)), 1)
+        rows.append({"budget": budget, "budget_is_the_size_at_quality": q, "chosen_quality": cq, "fits": fits, "bytes": len(data),
+                     "trials": int(trials[0]), "host_call_ms": round(ms, 2)})
+    res = {
+        "what": "version 3 rate prediction of 1920x1080x64 CDF 9/7 chunks (bench.synth_chunk content), MI355X",
+        "lane_symbols": L,
+        "predict_ms_per_chunk": {"v3": round(v3_ms, 3), "v2_before": round(v2_ms, 3), "v2_after": round(v2_ms_again, 3)},
+        "chunks_per_call": n, "reps": args.reps,
+        "bracket_vs_actual": {str(k): v for k, v in actual.items()},
+        "encode_wide_to_size": rows,
+    }
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        json.dump(res, fh, indent=1)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r06_rate_probe_1080p64.json"))
     ap.add_argument("--chunks", type=int, default=4)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--predict-only", action="store_true", help="time the prediction only (replica sweeps of the bin layout)")
-    ap.add_argument("--format", choices=("v1", "split"), default="v1")
+    ap.add_argument("--format", choices=("v1", "split", "wide"), default="v1")
     ap.add_argument("--lane-symbols", type=int, default=512)
     args = ap.parse_args()
     a.set_device(0)
@@ -98,6 +141,8 @@ def main():
     wt = a.WaveletType.Cdf97
     if args.format == "split":
         return split_probe(args, lib, rgb, wt)
+    if args.format == "wide":
+        return wide_probe(args, lib, rgb, wt)
     a.predict_sizes_device(rgb.data_ptr(), W, H, F, args.chunks, wt)   # warm-up
     torch.cuda.synchronize()
     t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
