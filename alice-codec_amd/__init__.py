@@ -151,6 +151,8 @@ def load_library() -> C.CDLL:
         "alice_codec_test_encode_chains": (C.c_int, [C.c_uint32, C.POINTER(vp), _u64p, _u32p, _u16p, _u16p, C.POINTER(vp), _u64p, _u32p, _u32p,
                                                      _u32p, vp]),
         "alice_codec_test_set_tuning": (None, [C.c_long]),
+        "alice_codec_test_set_grid_cap": (None, [C.c_uint32]),
+        "alice_codec_test_wide_symbols": (C.c_int, [_i32p, C.c_uint64, _u8p]),
         "alice_codec_test_transform_ms": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint8,
                                                     C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_float), vp]),
         "alice_codec_encoder_create_ex": (vp, [C.c_uint8, C.c_uint8]),

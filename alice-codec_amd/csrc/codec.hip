@@ -2804,6 +2804,20 @@ int alice_codec_dev_rans_decode(const void* d_stream, uint64_t len, const uint32
 
 void alice_codec_test_set_tuning(long band_kb) { set_transform_tuning(band_kb); }
 void alice_codec_test_set_value_table_radius(int r) { set_value_table_radius(r); }
+void alice_codec_test_set_grid_cap(uint32_t max_blocks) { set_generic_grid_cap(max_blocks); }
+int alice_codec_test_wide_symbols(const int32_t* coeffs, uint64_t n, uint8_t* out) {
+    clear_error();
+    if (!coeffs || !out) return fail(kNullArgument, "null argument");
+    return staged<int32_t, uint8_t>(coeffs, n, out, 1024 + 6 * n, [&](const int32_t* a, uint8_t* b, hipStream_t st) {
+        uint32_t* hist = (uint32_t*)b;
+        int32_t* back = (int32_t*)(b + 1024);
+        uint16_t* z = (uint16_t*)(b + 1024 + 4 * n);
+        (void)hipMemsetAsync(hist, 0, 1024, st);
+        launch_to_symbols_wide(a, z, n, st);
+        launch_from_symbols_wide(z, back, n, st);
+        launch_histogram_wide(z, n, hist, st);
+    });
+}
 void alice_codec_test_rate_log_table(uint32_t lo[4097], uint32_t hi[4097], uint32_t g[2]) {
     const RateLogTable& t = rate_log_table();
     if (lo) memcpy(lo, t.lo, sizeof(t.lo));

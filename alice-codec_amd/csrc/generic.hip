@@ -4,6 +4,7 @@
 // Quantizer/FastQuantizer, to_symbols/from_symbols/build_histogram and colour entry points,
 // and the pipeline when a chunk has more than 64 (padded) frames.
 #include <algorithm>
+#include <atomic>
 
 #include "common.h"
 #include "kernels.h"
@@ -87,10 +88,18 @@ __global__ __launch_bounds__(256) void axis_copy_kernel(const int32_t* __restric
     }
 }
 
+// Every launch below sizes its grid here: one workgroup per 256 items up to a cap, beyond which the kernels' grid-stride
+// loops take further trips.  The cap is 65535 * 4 workgroups (67 107 840 items per trip); the suite lowers it
+// (alice_codec_test_set_grid_cap) so that shapes of a few hundred items already wrap.  Read at launch time, host side only.
+constexpr unsigned kGridCap = 65535u * 4u;
+static std::atomic<unsigned> g_grid_cap{kGridCap};
+void set_generic_grid_cap(uint32_t max_blocks) { g_grid_cap.store(max_blocks ? std::min(max_blocks, kGridCap) : kGridCap, std::memory_order_relaxed); }
+
 static unsigned grid_for(unsigned long long items) {
+    const unsigned long long cap = g_grid_cap.load(std::memory_order_relaxed);
     unsigned long long g = (items + 255) / 256;
     if (g < 1) g = 1;
-    if (g > 65535ull * 4) g = 65535ull * 4;
+    if (g > cap) g = cap;
     return (unsigned)g;
 }
 
@@ -441,34 +450,35 @@ __global__ __launch_bounds__(256) void ordered_sqdev_sum_kernel(const int32_t* _
     }
     if (threadIdx.x == 0) *out = acc;
 }
-// ---- ssim (src/ssim.rs:18-115): one thread per 8x8 block.  All block sums are sums of multiples of 1/4096 below
+// ---- ssim (src/ssim.rs:18-115): one thread per 8x8 block, further blocks in further trips.  All block sums are sums of multiples of 1/4096 below
 // 2^22, hence exact in f64 in any order; the scalar tail uses fma exactly where the reference uses mul_add; the
 // mean over the blocks is an f64 fold in raster order, done by one lane (ordered_sum_f64_kernel).
 __global__ __launch_bounds__(256) void ssim_blocks_kernel(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
                                                           unsigned long long width, unsigned long long bw, unsigned long long nblocks,
                                                           double* __restrict__ out) {
-    const unsigned long long blk = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
-    if (blk >= nblocks) return;
-    const unsigned long long by = blk / bw, bx = blk % bw;
-    const uint8_t* pa = a + (by * 8) * width + bx * 8;
-    const uint8_t* pb = b + (by * 8) * width + bx * 8;
-    double sa = 0.0, sb = 0.0;
-    for (int dy = 0; dy < 8; ++dy)
-        for (int dx = 0; dx < 8; ++dx) { sa += (double)pa[dy * width + dx]; sb += (double)pb[dy * width + dx]; }
-    const double n = 64.0;
-    const double mu_a = sa / n, mu_b = sb / n;
-    double va = 0.0, vb = 0.0, vab = 0.0;
-    for (int dy = 0; dy < 8; ++dy)
-        for (int dx = 0; dx < 8; ++dx) {
-            const double da = (double)pa[dy * width + dx] - mu_a, db = (double)pb[dy * width + dx] - mu_b;
-            va += da * da; vb += db * db; vab += da * db;
-        }
-    const double denom = n - 1.0;
-    va /= denom; vb /= denom; vab /= denom;
-    const double C1 = 6.5025, C2 = 58.5225;
-    const double numerator = fma(2.0 * mu_a, mu_b, C1) * fma(2.0, vab, C2);
-    const double denominator = (fma(mu_a, mu_a, mu_b * mu_b) + C1) * (va + vb + C2);
-    out[blk] = numerator / denominator;
+    for (unsigned long long blk = (unsigned long long)blockIdx.x * 256 + threadIdx.x; blk < nblocks;
+         blk += (unsigned long long)gridDim.x * 256) {
+        const unsigned long long by = blk / bw, bx = blk % bw;
+        const uint8_t* pa = a + (by * 8) * width + bx * 8;
+        const uint8_t* pb = b + (by * 8) * width + bx * 8;
+        double sa = 0.0, sb = 0.0;
+        for (int dy = 0; dy < 8; ++dy)
+            for (int dx = 0; dx < 8; ++dx) { sa += (double)pa[dy * width + dx]; sb += (double)pb[dy * width + dx]; }
+        const double n = 64.0;
+        const double mu_a = sa / n, mu_b = sb / n;
+        double va = 0.0, vb = 0.0, vab = 0.0;
+        for (int dy = 0; dy < 8; ++dy)
+            for (int dx = 0; dx < 8; ++dx) {
+                const double da = (double)pa[dy * width + dx] - mu_a, db = (double)pb[dy * width + dx] - mu_b;
+                va += da * da; vb += db * db; vab += da * db;
+            }
+        const double denom = n - 1.0;
+        va /= denom; vb /= denom; vab /= denom;
+        const double C1 = 6.5025, C2 = 58.5225;
+        const double numerator = fma(2.0 * mu_a, mu_b, C1) * fma(2.0, vab, C2);
+        const double denominator = (fma(mu_a, mu_a, mu_b * mu_b) + C1) * (va + vb + C2);
+        out[blk] = numerator / denominator;
+    }
 }
 __global__ __launch_bounds__(256) void ordered_sum_f64_kernel(const double* __restrict__ v, unsigned long long n, double* __restrict__ out) {
     constexpr int T = 4096;
@@ -488,11 +498,12 @@ __global__ __launch_bounds__(256) void ordered_sum_f64_kernel(const double* __re
 // downsample_2x (src/ssim.rs:181-200): truncating mean of each 2x2 cell
 __global__ __launch_bounds__(256) void downsample2_kernel(const uint8_t* __restrict__ in, unsigned long long width, unsigned long long nw,
                                                           unsigned long long n_out, uint8_t* __restrict__ out) {
-    const unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_out) return;
-    const unsigned long long y = i / nw, x = i % nw;
-    const uint8_t* p = in + (2 * y) * width + 2 * x;
-    out[i] = (uint8_t)(((unsigned)p[0] + p[1] + p[width] + p[width + 1]) / 4u);
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n_out;
+         i += (unsigned long long)gridDim.x * 256) {
+        const unsigned long long y = i / nw, x = i % nw;
+        const uint8_t* p = in + (2 * y) * width + 2 * x;
+        out[i] = (uint8_t)(((unsigned)p[0] + p[1] + p[width] + p[width + 1]) / 4u);
+    }
 }
 #pragma clang fp contract(fast)
 void launch_ssim_blocks(const uint8_t* d_a, const uint8_t* d_b, uint64_t width, uint64_t bw, uint64_t nblocks, double* d_out, hipStream_t st) {

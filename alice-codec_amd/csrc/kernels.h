@@ -182,6 +182,9 @@ void launch_stage_wavelet(int32_t* d_data, int32_t* d_tmp, uint64_t w, uint64_t 
 // ---- generic.hip (stage-level API on arbitrary i32 data; exact reference arithmetic) ----
 // 1-D transform of n_lines lines: element k of line (a, b) is at data[a*stride_a + b*stride_b + k*stride_k],
 // a in [0, n_a), b in [0, n_b).  tmp: same size as data.
+// Cap on the workgroups of the launches sized per item (grid_for in generic.hip); 0 restores the default, 65535 * 4.  The
+// launches that clamp further (to 2048) still do.  Process-wide; tests only.
+void set_generic_grid_cap(uint32_t max_blocks);
 void launch_wavelet_axis(int32_t* d_data, int32_t* d_tmp, uint64_t n, uint64_t stride_k, uint64_t n_a,
                          uint64_t stride_a, uint64_t n_b, uint64_t stride_b, int wavelet, bool inverse,
                          hipStream_t st);

@@ -64,6 +64,20 @@ void alice_codec_test_set_tuning(long band_kb);
  * and the boundary; results never depend on it. */
 void alice_codec_test_set_value_table_radius(int r);
 
+/* Cap on the workgroups of the generic stage kernels' launches (csrc/generic.hip, grid_for), process-wide: the stage calls
+ * (wavelets, quantisers, symbol maps, colour, pad / strip, ssim / ms_ssim) and the chunks the tile kernels do not cover
+ * launch one workgroup per 256 items up to 262 140 workgroups and cover the rest in further trips of a grid-stride loop.
+ * 0 restores 262 140; larger values are clamped to it.  The launches that clamp further to 2048 workgroups (histograms,
+ * psnr, the RDO sum) keep doing so on top of it.  Read at launch time on the host; no kernel knows about it.  The suite
+ * lowers it so that a few hundred items already take several trips; results never depend on it. */
+void alice_codec_test_set_grid_cap(uint32_t max_blocks);
+
+/* The wide twins of the symbol kernels (csrc/generic.hip), which no stage call reaches on data of the caller's choice: n host
+ * coefficients through to_symbols_wide, its result through from_symbols_wide and histogram_wide.  out receives
+ * 1024 + 6 n bytes: the 256 u32 bins of min(z, 255), then n i32 (the coefficients from_symbols_wide gives back), then n
+ * u16 (z; 65535 for a coefficient above 32768 or below -32767). */
+int alice_codec_test_wide_symbols(const int32_t *coeffs, uint64_t n, uint8_t *out);
+
 /* Admission budget of the calling thread's device (csrc/codec.hip, ChainHub::admit): whole-chunk host calls state the
  * device memory they are about to allocate and wait while the calls already in flight hold more than the budget allows
  * (a call alone always enters).  Default: 90 % of what is free (device + the library's cache) whenever a call enters an
