@@ -2871,9 +2871,10 @@ int alice_codec_test_decode_chains(uint32_t n_chains, const void* const* d_strea
     return kOk;
 }
 
-int alice_codec_test_encode_chains(uint32_t n_chains, const void* const* d_symbols, const uint64_t* ns, const uint32_t* hists,
-                                   const uint16_t* cum_freq, const uint16_t* freq, void* const* d_regions, const uint64_t* caps,
-                                   const uint32_t* x_init, const uint32_t* keep_open, uint32_t* out, void* hip_stream) {
+// out_stride: 6 (alice_codec_test_encode_chains) or 7 (..._blocks: RansResult.comp_blocks behind the six)
+static int test_encode_chains(uint32_t n_chains, const void* const* d_symbols, const uint64_t* ns, const uint32_t* hists,
+                              const uint16_t* cum_freq, const uint16_t* freq, void* const* d_regions, const uint64_t* caps,
+                              const uint32_t* x_init, const uint32_t* keep_open, uint32_t* out, uint32_t out_stride, void* hip_stream) {
     clear_error();
     if (!n_chains || !d_symbols || !ns || (!hists && (!cum_freq || !freq)) || !d_regions || !caps || !out) return fail(kNullArgument, "null argument");
     TRY(ensure_device());
@@ -2907,14 +2908,29 @@ int alice_codec_test_encode_chains(uint32_t n_chains, const void* const* d_symbo
     HIP_TRY(hipMemcpyAsync(res.data(), dres.p, res.size() * sizeof(RansResult), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     for (uint32_t c = 0; c < n_chains; ++c) {
-        out[6 * c] = (uint32_t)(res[c].len > 0xFFFFFFFFull ? 0xFFFFFFFFull : res[c].len);
-        out[6 * c + 1] = res[c].final_state;
-        out[6 * c + 2] = res[c].flags;
-        out[6 * c + 3] = res[c].paths;
-        out[6 * c + 4] = res[c].fast_tiles;
-        out[6 * c + 5] = res[c].slow_tiles;
+        uint32_t* const o = out + (size_t)out_stride * c;
+        o[0] = (uint32_t)(res[c].len > 0xFFFFFFFFull ? 0xFFFFFFFFull : res[c].len);
+        o[1] = res[c].final_state;
+        o[2] = res[c].flags;
+        o[3] = res[c].paths;
+        o[4] = res[c].fast_tiles;
+        o[5] = res[c].slow_tiles;
+        if (out_stride > 6u) o[6] = res[c].comp_blocks;
     }
     return kOk;
+}
+
+int alice_codec_test_encode_chains(uint32_t n_chains, const void* const* d_symbols, const uint64_t* ns, const uint32_t* hists,
+                                   const uint16_t* cum_freq, const uint16_t* freq, void* const* d_regions, const uint64_t* caps,
+                                   const uint32_t* x_init, const uint32_t* keep_open, uint32_t* out, void* hip_stream) {
+    return test_encode_chains(n_chains, d_symbols, ns, hists, cum_freq, freq, d_regions, caps, x_init, keep_open, out, 6u, hip_stream);
+}
+
+int alice_codec_test_encode_chains_blocks(uint32_t n_chains, const void* const* d_symbols, const uint64_t* ns, const uint32_t* hists,
+                                          const uint16_t* cum_freq, const uint16_t* freq, void* const* d_regions,
+                                          const uint64_t* caps, const uint32_t* x_init, const uint32_t* keep_open, uint32_t* out,
+                                          void* hip_stream) {
+    return test_encode_chains(n_chains, d_symbols, ns, hists, cum_freq, freq, d_regions, caps, x_init, keep_open, out, 7u, hip_stream);
 }
 
 int alice_codec_test_chain_occupancy(uint32_t out[6]) {

@@ -20,8 +20,9 @@
 // 64 times.  Lanes 0..t hold their final values after step t and are fixed points
 // of the update from then on, so no masking is needed; after 64 steps every lane
 // holds the exact state before and after its own symbol.  The serial chain is 9
-// VALU instructions per symbol with no memory access and no cross-lane traffic
-// other than the DPP operand.  Byte emission (0-2 bytes per symbol, taken from the
+// VALU instructions per symbol (7 in blocks without a symbol of frequency <= 16,
+// which carry the complement of the state: ripple64_comp) with no memory access
+// and no cross-lane traffic other than the DPP operand.  Byte emission (0-2 bytes per symbol, taken from the
 // low bytes of the pre-renormalisation state) is then a wave-parallel ballot/popcount
 // compaction.  Bytes are written back to front so the stream comes out already
 // "reversed" as RansEncoder::finish leaves it.
@@ -173,6 +174,7 @@ __device__ __forceinline__ void chain_take_turns(uint32_t enabled) {
 // ----------------------------------------------------------------------------------
 
 constexpr int kEncTile = 1024;  // symbols staged per global load (16 B per lane)
+constexpr int kEncTilePad = 128;
 
 // 64 ripple steps.  On entry lane 0 of xin holds the carry-in state and xout is
 // don't-care; on exit every lane holds the state before (xin) and after (xout,
@@ -243,6 +245,49 @@ __device__ __forceinline__ void ripple64_clean(uint32_t& xin, uint32_t& xout, ui
 #undef ALICE_RIPPLE_STEP
 }
 
+// The step for a block whose 64 symbols are all in the big class (17 <= freq <= 4096), 7 issue slots: the chain carries the
+// COMPLEMENT of the state, u = T - 1 - x (mod 2^32) with T = freq << 19, so that the choice between x and x >> 8 becomes
+// an unsigned minimum and needs neither a compare nor VCC.  With x in [2^23, 2^31 + 2^17):
+//   x <  T: u = T - 1 - x lies in [0, T);  x >= T: u wraps to above 2^31 (x - T + 1 < 2^31 because T > 2^17).
+//   w = ashr(u, 8) + T'' with T'' = T - (T >> 8) is T - 1 - (x >> 8) in BOTH cases (256 divides T, so the floor of
+//   (T - 1 - x) / 256 is T / 256 - 1 - floor(x / 256)), and x >> 8 < 2^23 + 2^9 < T puts it in [0, T) too.
+//   x < T: w >= u (x >> 8 <= x), min = u; x >= T: w < T <= 2^31 < u, min = w.  So m = min_u32(u, w) = T - 1 - y.
+// The division stays in the complement domain: T = freq * 2^19, so floor(y / freq) = 2^19 - 1 - floor(m / freq), and
+// m < freq << 19 is the bound the reciprocal is exact for.  With qm = umulhi(m, rcp) >> rsh and z = qm * g + m
+// (qm < 2^19, g = 4096 - freq: both fit v_mad_i32_i24) the new state is
+//   x' = y + (2^19 - 1 - qm) * g + cum = C - z,   C = 2^31 - 4097 + freq + cum,
+// and the next lane's complement is u' = T' - 1 - x' = z + kc with kc = T' - 1 - C (its own T, the previous lane's C),
+// one v_add_u32_dpp as before.  On entry lane 0 of u holds T - 1 - x of the carry-in (the DPP read from an invalid lane
+// leaves it alone); on exit every lane holds its own u (before its symbol) and z (after: x' = C - z).
+__device__ __forceinline__ void ripple64_comp(uint32_t& u, uint32_t& z, uint32_t kc, uint32_t tpp, uint32_t rcp, uint32_t rsh,
+                                              int32_t g) {
+    uint32_t m, q;
+    // w = ashr(u, 8) + T'' in ONE instruction: v_mad_i64_i32 {w : lo} = u * 2^24 + {T'' : 0}.  The signed product's high
+    // dword is ashr(u, 8), the addend's low dword is 0, so nothing carries into the sum of the high dwords.  7 issue
+    // slots.  The two register pairs are named outright (inline asm has no operand modifier for one half of a pair):
+    // v[60:61] = {0, T''}, set up here in place of the leading s_nop 1, and v[62:63] = the product.
+#define ALICE_RIPPLE_STEP                                                            \
+    "v_add_u32_dpp %[u], %[z], %[kc] wave_shr:1 row_mask:0xf bank_mask:0xf\n\t"     \
+    "v_mad_i64_i32 v[62:63], vcc, %[u], %[two24], v[60:61]\n\t"                    \
+    "v_min_u32_e32 %[m], %[u], v63\n\t"                                           \
+    "v_mul_hi_u32 %[q], %[m], %[rcp]\n\t"                                          \
+    "v_lshrrev_b32_e32 %[q], %[rsh], %[q]\n\t"                                     \
+    "v_mad_i32_i24 %[z], %[q], %[g], %[m]\n\t"                                     \
+    "s_nop 1\n\t"
+#define ALICE_RIPPLE_STEP4 ALICE_RIPPLE_STEP ALICE_RIPPLE_STEP ALICE_RIPPLE_STEP ALICE_RIPPLE_STEP
+#define ALICE_RIPPLE_STEP16 ALICE_RIPPLE_STEP4 ALICE_RIPPLE_STEP4 ALICE_RIPPLE_STEP4 ALICE_RIPPLE_STEP4
+    asm volatile(
+        "v_mov_b32_e32 v60, 0\n\t"
+        "v_mov_b32_e32 v61, %[tpp]\n\t"
+        ALICE_RIPPLE_STEP16 ALICE_RIPPLE_STEP16 ALICE_RIPPLE_STEP16 ALICE_RIPPLE_STEP16
+        : [u] "+v"(u), [z] "=&v"(z), [m] "=&v"(m), [q] "=&v"(q)
+        : [kc] "v"(kc), [tpp] "v"(tpp), [rcp] "v"(rcp), [rsh] "v"(rsh), [g] "v"(g), [two24] "s"(1u << 24)
+        : "v60", "v61", "v62", "v63", "vcc");
+#undef ALICE_RIPPLE_STEP16
+#undef ALICE_RIPPLE_STEP4
+#undef ALICE_RIPPLE_STEP
+}
+
 // kExclusive: the kernel claims more than half of the SIMD's 512 registers (an AGPR clobber; nothing uses them), so
 // the dispatcher cannot put two chains on one SIMD -- see launch_rans_encode.
 template <bool kExclusive>
@@ -259,9 +304,14 @@ __global__ __launch_bounds__(64) void rans_encode_kernel(const uint8_t* __restri
                                                          unsigned long long cap1, unsigned long long cap2,
                                                          uint32_t x_init, uint32_t keep_open, uint32_t take_turns,
                                                          const RansEncodeDesc* __restrict__ descs) {
-    __shared__ uint4 tab_a[256];  // xmax, xmax8, rcp, rsh
-    __shared__ uint4 tab_b[256];  // g, cbias, freq, cum
-    __shared__ __attribute__((aligned(16))) uint8_t tile[kEncTile];
+    // what the clean tile reads per symbol is in tab_a and tab_b; T'' and C are the complement step's per-lane constants
+    // (ripple64_comp; meaningful for 17 <= freq <= 4096 only)
+    __shared__ uint4 tab_a[256];  // xmax, rcp, rsh, g
+    __shared__ uint4 tab_b[256];  // T'' = xmax - (xmax >> 8), C = 2^31 - 4097 + freq + cum, cbias, xmax8
+    __shared__ uint2 tab_c[256];  // freq, cum
+    // the tile's 1024 symbols sit behind kEncTilePad bytes that are never written: the block pipeline reads two blocks
+    // past the end of a tile (values it never uses), at plain descending addresses
+    __shared__ __attribute__((aligned(16))) uint8_t tile[kEncTilePad + kEncTile];
 
     if constexpr (kExclusive) asm volatile("" ::: "a255");
     const int chain = blockIdx.x;
@@ -290,19 +340,23 @@ __global__ __launch_bounds__(64) void rans_encode_kernel(const uint8_t* __restri
 
     for (int s = lane; s < 256; s += 64) {
         const RansEncEntry e = tbl->enc[s];
-        tab_a[s] = make_uint4(e.xmax, e.xmax8, e.rcp, e.rsh);
-        tab_b[s] = make_uint4((uint32_t)e.g, e.cbias, e.freq, e.cum);
+        tab_a[s] = make_uint4(e.xmax, e.rcp, e.rsh, (uint32_t)e.g);
+        tab_b[s] = make_uint4(e.xmax - (e.xmax >> 8), e.cbias + e.freq + ((1u << 31) - kProbScale - 1u), e.cbias, e.xmax8);
+        tab_c[s] = make_uint2(e.freq, e.cum);
     }
 
     // (a state carried in from an earlier call may lie outside the range the one-compare step assumes)
-    const bool table_clean = x_init == kRansL && (tbl->flags & (kTableVerified | kTableNeedsGeneric | kTableDiverges)) == kTableVerified;  // uniform
+    // (readfirstlane: the load goes through a generic pointer, which alone would make every branch on it, and with them
+    // `written`, look divergent to the compiler)
+    const uint32_t tbl_flags = (uint32_t)__builtin_amdgcn_readfirstlane((int)tbl->flags);
+    const bool table_clean = x_init == kRansL && (tbl_flags & (kTableVerified | kTableNeedsGeneric | kTableDiverges)) == kTableVerified;  // uniform
     uint32_t x = x_init;  // RansEncoder::new, src/rans.rs:249-254: 2^23; a continued encoder (:288-294) brings its state
     const unsigned long long clk0 = clock64(), rt0 = wall_clock64();
     unsigned long long written = 0ull;
     uint32_t flags = 0u;
     // which branches ran (kEncPath*): counted and marked only off the clean tile and the aligned load; the clean tiles
     // are what is left at the end.  load_paths is per lane (a tail tile's lanes take different load branches).
-    uint32_t paths = 0u, load_paths = 0u, slow_tiles = 0u;
+    uint32_t paths = 0u, load_paths = 0u, slow_tiles = 0u, comp_blocks = 0u;
     asm volatile("" : "+v"(load_paths));   // zeroed here, once: otherwise every load branch of the first tile, the aligned one included, zeroes it
 
     const unsigned long long ntiles = (n + kEncTile - 1) / kEncTile;
@@ -342,15 +396,15 @@ __global__ __launch_bounds__(64) void rans_encode_kernel(const uint8_t* __restri
         return v;
     };
 
-    struct BlockParams { uint4 ea, eb; };
-    auto sym_of = [&](int b) -> uint32_t { return tile[(kEncTile - 1 - (b * 64 + lane)) & (kEncTile - 1)]; };
-    auto params_of = [&](uint32_t s) -> BlockParams { BlockParams p; p.ea = tab_a[s]; p.eb = tab_b[s]; return p; };
+    struct BlockParams { uint4 ea, eb; uint2 ec; };
+    auto sym_of = [&](int b) -> uint32_t { return tile[kEncTilePad + kEncTile - 1 - lane - b * 64]; };   // b <= 17
+    auto params_of = [&](uint32_t s) -> BlockParams { BlockParams p; p.ea = tab_a[s]; p.eb = tab_b[s]; p.ec = tab_c[s]; return p; };
 
     uint4 cur = load_tile(0);
     for (unsigned long long j = 0; j < ntiles; ++j) {
         if (!kExclusive && (j & 7ull) == 0ull) chain_take_turns(take_turns);
         __syncthreads();
-        ((uint4*)tile)[lane] = cur;
+        ((uint4*)(tile + kEncTilePad))[lane] = cur;
         __syncthreads();
         cur = load_tile(j + 1);  // in flight while this tile's 16 blocks ripple
         const long long hi = (long long)(n - j * kEncTile);
@@ -367,33 +421,69 @@ __global__ __launch_bounds__(64) void rans_encode_kernel(const uint8_t* __restri
         // two readlanes and a scalar add.
         if (table_clean && valid == kEncTile && written + 2ull * kEncTile + 4ull + 320ull <= cap) {
             uint32_t xin = x;
+            // One uniform base for all stores of the tile, kTileSpan bytes below the write position (the tile emits at
+            // most 2 * 1024 bytes, the capacity test above keeps the base inside the region), and a 32-bit count of
+            // the tile's bytes: every store is base + a 32-bit lane offset.  Byte i of the tile
+            // goes to base[kTileSpan - 1 - i]; lanes with nothing to emit write their own byte of the 64 at the
+            // bottom (stream space not yet written).
+            constexpr uint32_t kTileSpan = 2u * kEncTile + 320u;
+            const uintptr_t tb_v = (uintptr_t)(out_end - written - kTileSpan);
+            // (global, not generic: the stores take the SGPR base and the lane's 32-bit offset as they are)
+            typedef __attribute__((address_space(1))) uint8_t GlobalByte;
+            GlobalByte* const tb = (GlobalByte*)(((uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(tb_v >> 32)) << 32) |
+                                                 (uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)tb_v));
+            // (kept in a VGPR, where mbcnt wants its start value: one v_add per block instead of s_add + v_mov)
+            uint32_t tw = 0u, rare_blocks = 0u;
+            asm volatile("" : "+v"(tw));
 #pragma unroll 2
             for (int b = 0; b < kEncTile / 64; ++b) {
                 const BlockParams curp = nxt;
                 nxt = params_of(sym1);
                 sym1 = sym_of(b + 2);
-                const uint32_t xmax = curp.ea.x, xmax8 = curp.ea.y, rcp = curp.ea.z, rsh = curp.ea.w;
-                const int32_t g = (int32_t)curp.eb.x;
-                const uint32_t cbias = curp.eb.y;
-                uint32_t xout = 0u;
-                const uint32_t cprev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)cbias, 0x138, 0xf, 0xf, true);
+                const uint32_t xmax = curp.ea.x, rcp = curp.ea.y, rsh = curp.ea.z;
+                const int32_t g = (int32_t)curp.ea.w;
                 const bool small_f = xmax <= kRansL;            // freq <= 16
-                const uint32_t k0 = small_f ? 8u : 0u;
-                ripple64_clean(xin, xout, small_f ? xmax8 : xmax, k0, k0 + 8u, rcp, rsh, g, cprev);
-                const bool c1 = xin >= xmax;
-                const bool c2 = xin >= xmax8;
-                const unsigned long long b1 = __ballot(c1), b2 = __ballot(c2);
-                const uint32_t off = __builtin_amdgcn_mbcnt_hi((uint32_t)(b1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b1, 0u)) +
-                                     __builtin_amdgcn_mbcnt_hi((uint32_t)(b2 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b2, 0u));
-                // one uniform base 320 bytes ahead of the write position; real bytes at 319 - off and 318 - off,
-                // lanes with nothing to emit write their own byte of the 64 at the bottom (not yet written stream space)
-                uint8_t* const base = out_end - written - 320ull;
-                base[c1 ? 319u - off : (uint32_t)lane] = (uint8_t)(xin & 0xFFu);
-                base[c2 ? 318u - off : (uint32_t)lane] = (uint8_t)((xin >> 8) & 0xFFu);
-                written += (unsigned long long)((uint32_t)__popcll(b1) + (uint32_t)__popcll(b2));
-                // wave_ror:1 -- lane 0 of the next block's xin receives xout[63] + cbias[63]
-                xin = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(xout + cbias), 0x13C, 0xf, 0xf, false);
+                if (__builtin_expect(__ballot(small_f) == 0ull, 1)) {
+                    // every lane in the big class (17 <= freq <= 4096, so cbias = cum): the complement step
+                    const uint32_t tm1 = xmax - 1u, tpp = curp.eb.x, cc = curp.eb.y;
+                    // C of the lane before, as a value of its own: left to the compiler, the move folds into the
+                    // subtraction as v_subrev_u32_dpp, and that instruction gave tm1[lane - 1] - C[lane] on the MI355X
+                    // (DESIGN.md section 4.3).  Only v_mov_b32_dpp and v_add_u32_dpp carry lane traffic here.
+                    uint32_t cc_prev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)cc, 0x138, 0xf, 0xf, true);
+                    asm volatile("" : "+v"(cc_prev));
+                    const uint32_t kc = tm1 - cc_prev;
+                    uint32_t u = tm1 - xin, z;                  // lane 0: the carry-in; the others are overwritten
+                    ripple64_comp(u, z, kc, tpp, rcp, rsh, g);
+                    // x >= T exactly when u wrapped; at most one byte, x & 0xFF = ~u & 0xFF (256 divides T)
+                    const bool c1 = (int32_t)u < 0;
+                    const unsigned long long b1 = __ballot(c1);
+                    const uint32_t off = __builtin_amdgcn_mbcnt_hi((uint32_t)(b1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b1, tw));
+                    tb[c1 ? kTileSpan - 1u - off : (uint32_t)lane] = (uint8_t)(~u & 0xFFu);
+                    tw += (uint32_t)__popcll(b1);
+                    // wave_ror:1 -- lane 0 of the next block's xin receives the plain state x' = C[63] - z[63]
+                    xin = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(cc - z), 0x13C, 0xf, 0xf, true);
+                } else {
+                    rare_blocks += 1u;
+                    const uint32_t cbias = curp.eb.z, xmax8 = curp.eb.w;
+                    uint32_t xout = 0u;
+                    const uint32_t cprev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)cbias, 0x138, 0xf, 0xf, true);
+                    const uint32_t k0 = small_f ? 8u : 0u;
+                    ripple64_clean(xin, xout, small_f ? xmax8 : xmax, k0, k0 + 8u, rcp, rsh, g, cprev);
+                    const bool c1 = xin >= xmax;
+                    const bool c2 = xin >= xmax8;
+                    const unsigned long long b1 = __ballot(c1), b2 = __ballot(c2);
+                    const uint32_t off = __builtin_amdgcn_mbcnt_hi((uint32_t)(b1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b1, tw)) +
+                                         __builtin_amdgcn_mbcnt_hi((uint32_t)(b2 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b2, 0u));
+                    tb[c1 ? kTileSpan - 1u - off : (uint32_t)lane] = (uint8_t)(xin & 0xFFu);
+                    tb[c2 ? kTileSpan - 2u - off : (uint32_t)lane] = (uint8_t)((xin >> 8) & 0xFFu);
+                    tw += (uint32_t)__popcll(b1) + (uint32_t)__popcll(b2);
+                    // wave_ror:1 -- lane 0 of the next block's xin receives xout[63] + cbias[63]
+                    xin = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(xout + cbias), 0x13C, 0xf, 0xf, false);
+                }
+                asm volatile("" : "+v"(tw));
             }
+            written += (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)tw);
+            comp_blocks += (uint32_t)(kEncTile / 64) - rare_blocks;
             x = (uint32_t)__builtin_amdgcn_readlane((int)xin, 0);
             continue;
         }
@@ -406,13 +496,15 @@ __global__ __launch_bounds__(64) void rans_encode_kernel(const uint8_t* __restri
             const bool active = (kEncTile - 1 - (b * 64 + lane)) >= kEncTile - valid;  // all lanes except in the last tile
             uint4 ea = curp.ea;
             uint4 eb = curp.eb;
+            uint2 ec = curp.ec;
             if (!active) {  // identity step
-                ea = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u);
-                eb = make_uint4(0u, 0u, 1u, 0u);
+                ea = make_uint4(0xFFFFFFFFu, 0u, 0u, 0u);
+                eb = make_uint4(0u, 0u, 0u, 0xFFFFFFFFu);
+                ec = make_uint2(1u, 0u);
             }
-            const uint32_t xmax = ea.x, xmax8 = ea.y, rcp = ea.z, rsh = ea.w;
-            const int32_t g = (int32_t)eb.x;
-            const uint32_t cbias = eb.y, freq = eb.z, cum = eb.w;
+            const uint32_t xmax = ea.x, xmax8 = eb.w, rcp = ea.y, rsh = ea.z;
+            const int32_t g = (int32_t)ea.w;
+            const uint32_t cbias = eb.z, freq = ec.x, cum = ec.y;
             const bool bad = (freq - 1u) >= kProbScale;  // freq == 0 or freq > 4096 (identity lanes carry freq 1)
 
             uint32_t xin = x, xout = 0u;
@@ -483,6 +575,7 @@ __global__ __launch_bounds__(64) void rans_encode_kernel(const uint8_t* __restri
         res->fast_tiles = clean_tiles;
         res->slow_tiles = slow_tiles;
         res->paths = paths;
+        res->comp_blocks = comp_blocks;
         res->cycles_k = (uint32_t)((clock64() - clk0) >> 10);
         res->ticks_k = (uint32_t)((wall_clock64() - rt0) >> 10);
         res->hw_id = __builtin_amdgcn_s_getreg((31 << 11) | 4);

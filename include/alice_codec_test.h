@@ -42,6 +42,14 @@ int alice_codec_test_encode_chains(uint32_t n_chains, const void *const *d_symbo
                                    const uint16_t *cum_freq, const uint16_t *freq, void *const *d_regions, const uint64_t *caps,
                                    const uint32_t *x_init, const uint32_t *keep_open, uint32_t *out, void *hip_stream);
 
+/* The same launch with one more result per chain: out[7 c ..] = the six values above, then the number of 64-symbol blocks of
+ * clean tiles that took the complement step (csrc/rans.hip, ripple64_comp: blocks in which every symbol has a table
+ * frequency of at least 17). */
+int alice_codec_test_encode_chains_blocks(uint32_t n_chains, const void *const *d_symbols, const uint64_t *ns,
+                                          const uint32_t *hists, const uint16_t *cum_freq, const uint16_t *freq,
+                                          void *const *d_regions, const uint64_t *caps, const uint32_t *x_init,
+                                          const uint32_t *keep_open, uint32_t *out, void *hip_stream);
+
 /* Times the transform launches alone (no chains) with HIP events on `hip_stream`: `reps` passes over `n_chunks` chunks
  * of w x h x f pixels, forward (RGB -> symbols + histograms) and inverse (symbols -> RGB), through the same pipes the
  * encode / decode of a batch use.  Device buffers: d_rgb and d_rgb_out hold n_buffers chunks of RGB, d_sym n_buffers

@@ -25,7 +25,7 @@ __global__ __launch_bounds__(64) void NAME(unsigned long long* out, uint32_t see
     "s_memtime %[t1]\n\t s_waitcnt lgkmcnt(0)\n\t"                                            \
     "s_set_gpr_idx_off\n\t"                                                                   \
     : [t0] "=&s"(t0), [t1] "=&s"(t1), [cnt] "=&s"(cnt) : [seed] "s"(seed)                     \
-    : "s40","s41","s42","s43","s44","s45","s46","s47","v40","v41","v42","v43","v44","v45","vcc","scc","m0","memory"); \
+    : "s40","s41","s42","s43","s44","s45","s46","s47","v40","v41","v42","v43","v44","v45","v46","v47","v48","v49","vcc","scc","m0","memory"); \
   if (threadIdx.x == 0) out[0] = t1 - t0;                                                     \
 }
 
@@ -67,6 +67,14 @@ PROBE_KERNEL(k_dec4_core, "s_lshr_b32 s45, s40, 12\n\t s_bfe_u32 s46, s40, 0x600
 PROBE_KERNEL(k_dec4_pair, "s_lshr_b32 s45, s40, 12\n\t s_bfe_u32 s46, s40, 0x60006\n\t s_set_gpr_idx_on s43, 0x1\n\t v_writelane_b32 v44, s40, 3\n\t v_readlane_b32 s47, v40, s40\n\t v_readlane_b32 s46, v41, s40\n\t s_mul_i32 s47, s47, s45\n\t s_add_u32 s40, s47, s46\n\t s_flbit_i32_b32 m0, s44\n\t s_mov_b32 s46, s41\n\t s_movrels_b32 s45, s42\n\t s_lshl_b64 s[40:41], s[40:41], s43\n\t s_lshl_b64 s[46:47], s[46:47], s43\n\t s_sub_u32 s45, s45, s43\n\ts_lshr_b32 s45, s40, 12\n\t s_bfe_u32 s46, s40, 0x60006\n\t s_set_gpr_idx_on s43, 0x1\n\t v_writelane_b32 v44, s40, 3\n\t v_readlane_b32 s47, v40, s40\n\t v_readlane_b32 s46, v41, s40\n\t s_mul_i32 s47, s47, s45\n\t s_add_u32 s40, s47, s46\n\t s_flbit_i32_b32 m0, s44\n\t s_mov_b32 s46, s41\n\t s_movrels_b32 s45, s42\n\t s_lshl_b64 s[40:41], s[40:41], s43\n\t s_lshl_b64 s[46:47], s[46:47], s43\n\t s_sub_u32 s45, s45, s43\n\ts_cmp_lt_u32 s42, s43\n\t s_cbranch_scc1 9f\n\t 9:\n\t")
 PROBE_KERNEL(k_enc_core, "v_add_u32_dpp v40, v44, v41 wave_shr:1 row_mask:0xf bank_mask:0xf\n\t v_cmp_ge_u32_e64 s[46:47], v40, v41\n\t v_cmp_ge_u32_e32 vcc, v40, v42\n\t s_nop 0\n\t v_cndmask_b32_e64 v45, 0, 8, s[46:47]\n\t v_cndmask_b32_e64 v45, v45, 16, vcc\n\t v_lshrrev_b32_e32 v45, v45, v40\n\t v_mul_hi_u32 v43, v45, v41\n\t v_lshrrev_b32_e32 v43, v42, v43\n\t v_mad_i32_i24 v44, v43, v42, v45\n\t s_nop 1\n\t")
 
+// the encode steps of clean tiles (csrc/rans.hip): ripple64_clean (9 slots), the complement step with an arithmetic shift and
+// an add (8 slots), and with the two as one v_mad_i64_i32 (u * 2^24 + (T'' << 32): the high dword is ashr(u, 8) + T''; 7 slots,
+// the one ripple64_comp uses).  Measured: DESIGN.md section 4.3.
+PROBE_KERNEL(k_enc_clean9, "v_add_u32_dpp v40, v44, v41 wave_shr:1 row_mask:0xf bank_mask:0xf\n\t v_cmp_ge_u32_e32 vcc, v40, v42\n\t s_nop 1\n\t v_cndmask_b32_e32 v45, v42, v43, vcc\n\t v_lshrrev_b32_e32 v45, v45, v40\n\t v_mul_hi_u32 v43, v45, v41\n\t v_lshrrev_b32_e32 v43, v42, v43\n\t v_mad_i32_i24 v44, v43, v42, v45\n\t s_nop 1\n\t")
+PROBE_KERNEL(k_enc_comp8, "v_add_u32_dpp v40, v44, v41 wave_shr:1 row_mask:0xf bank_mask:0xf\n\t v_ashrrev_i32_e32 v46, 8, v40\n\t v_add_u32_e32 v46, v46, v41\n\t v_min_u32_e32 v45, v40, v46\n\t v_mul_hi_u32 v43, v45, v41\n\t v_lshrrev_b32_e32 v43, v42, v43\n\t v_mad_i32_i24 v44, v43, v42, v45\n\t s_nop 1\n\t")
+PROBE_KERNEL(k_enc_comp7, "v_add_u32_dpp v40, v44, v41 wave_shr:1 row_mask:0xf bank_mask:0xf\n\t v_mad_i64_i32 v[46:47], s[46:47], v40, v41, v[48:49]\n\t v_min_u32_e32 v45, v40, v47\n\t v_mul_hi_u32 v43, v45, v41\n\t v_lshrrev_b32_e32 v43, v42, v43\n\t v_mad_i32_i24 v44, v43, v42, v45\n\t s_nop 1\n\t")
+PROBE_KERNEL(k_vmad_i64_i32, "v_mad_i64_i32 v[46:47], s[46:47], v47, v41, v[48:49]\n\t")
+
 struct T { const char* name; void (*fn)(unsigned long long*, uint32_t); };
 int main() {
   unsigned long long* d; hipMalloc(&d, 64);
@@ -79,7 +87,9 @@ int main() {
     {"set_idx;v_readlane;s_and chain", k_setidx_readlane}, {"v_writelane", k_writelane},
     {"cmp+branch not taken", k_branch_nt}, {"cmp+branch taken (skip 1)", k_branch_t}, {"cmp+branch taken (skip 16)", k_branch_t_far},
     {"s_nop 0", k_snop0}, {"s_nop 1", k_snop1}, {"s_cmp+s_cselect dep", k_cselect},
-    {"s_set_gpr_idx_on", k_setidx_on}, {"s_set_gpr_idx_idx", k_setidx_idx}, {"s_flbit", k_flbit}, {"s_flbit m0;nop;s_movrels", k_flbit_m0_movrels}, {"s_mov m0", k_m0_write}, {"decode v3 core (17 instr, idx_on+flbit)", k_dec2_core}, {"decode v3 core (18 instr, idx_idx+cmp/csel)", k_dec2_core_idx}, {"decode v4 symbol (14 instr)", k_dec4_core}, {"decode v4 pair (28 instr + cmp + untaken branch)", k_dec4_pair}, {"decode core (9 instr)", k_dec_core}, {"encode ripple step (11 instr)", k_enc_core}};
+    {"s_set_gpr_idx_on", k_setidx_on}, {"s_set_gpr_idx_idx", k_setidx_idx}, {"s_flbit", k_flbit}, {"s_flbit m0;nop;s_movrels", k_flbit_m0_movrels}, {"s_mov m0", k_m0_write}, {"decode v3 core (17 instr, idx_on+flbit)", k_dec2_core}, {"decode v3 core (18 instr, idx_idx+cmp/csel)", k_dec2_core_idx}, {"decode v4 symbol (14 instr)", k_dec4_core}, {"decode v4 pair (28 instr + cmp + untaken branch)", k_dec4_pair}, {"decode core (9 instr)", k_dec_core}, {"encode ripple step (11 instr)", k_enc_core},
+    {"encode clean step (9 slots)", k_enc_clean9}, {"encode complement step (8 slots)", k_enc_comp8},
+    {"encode complement step, v_mad_i64_i32 (7 slots)", k_enc_comp7}, {"v_mad_i64_i32 dep", k_vmad_i64_i32}};
   double base = 0;
   for (auto& t : tests) {
     unsigned long long best = ~0ull;
