@@ -278,6 +278,17 @@ def load_library() -> C.CDLL:
         "alice_codec_dev_encode_split_to_budget": (C.c_int, [vp, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, C.c_uint32, C.c_uint32,
                                                              C.c_uint32, C.c_uint8, C.c_uint32, _u64p, C.c_uint8, C.c_uint8, _u8p, _u8p,
                                                              vp, C.c_uint64, _u64p, vp]),
+        "alice_codec_encode_reversible": (vp, [vp, _u8p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _u64p]),
+        "alice_codec_decode_reversible": (vp, [_u8p, C.c_uint64, _u64p]),
+        "alice_codec_reversible_info": (C.c_int, [_u8p, C.c_uint64, vp]),
+        "alice_codec_dev_encode_reversible": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint8, _u8p,
+                                                        C.c_uint32, vp, C.c_uint64, _u64p, vp]),
+        "alice_codec_dev_decode_reversible": (C.c_int, [vp, C.c_uint64, _u64p, C.c_uint32, vp, vp]),
+        "alice_codec_dev_encode_reversible_regions": (C.c_int, [vp, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                                C.c_uint32, C.c_uint8, C.c_uint8, _u8p, C.c_uint32, vp, C.c_uint64,
+                                                                _u64p, vp]),
+        "alice_codec_dev_decode_reversible_regions": (C.c_int, [vp, C.c_uint64, _u64p, C.c_uint32, vp, C.c_uint32, C.c_uint32, _u32p,
+                                                                vp]),
         "alice_codec_predict_wide_sizes": (C.c_int, [C.c_uint8, _u8p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                                      _u64p, _u64p]),
         "alice_codec_dev_predict_wide_sizes": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint32,
@@ -1536,9 +1547,10 @@ def encode_person_chunks(d_frames, d_background, width: int, height: int, frames
     (wide_encode_regions_device), the container to choose for qualities above about 90.  max_bytes (split and wide only) is
     a byte budget per chunk: every box is then coded at the quality split_encode_to_budget_device /
     wide_encode_to_budget_device picks in [min(10, hi), hi], hi = min(quality, 100), and a chunk that cannot be guaranteed
-    to fit is coded at the low end of the range."""
-    if format not in ("v1", "split", "wide"):
-        raise CodecError(9, f"format must be 'v1', 'split' or 'wide', got {format!r}")
+    to fit is coded at the low end of the range.  format="reversible" codes the boxes as version 4
+    (reversible_encode_regions_device): at quality 100 the boxes come back exactly; it has no byte budget."""
+    if format not in ("v1", "split", "wide", "reversible"):
+        raise CodecError(9, f"format must be 'v1', 'split', 'wide' or 'reversible', got {format!r}")
     if max_bytes is not None and format not in ("split", "wide"):
         raise CodecError(9, "max_bytes is a version 2 / version 3 budget: it needs format='split' or format='wide'")
     W, H, f = _positive_u32(width, "width"), _positive_u32(height, "height"), _positive_u32(frames, "frames")
@@ -1566,13 +1578,14 @@ def encode_person_chunks(d_frames, d_background, width: int, height: int, frames
         st = stats.cpu().numpy().view(np.uint32).reshape(-1, 5).astype(np.int64)
     boxes = person_chunk_boxes(st, W, H, f)
     frame_bytes = W * H * 3
-    if format in ("split", "wide"):
-        wide = format == "wide"
+    if format in ("split", "wide", "reversible"):
+        wide = format != "split"
         enc = FrameEncoder(int(quality), wavelet)
-        empty = (encode_wide if wide else encode_split)(enc, b"", 0, 0, f, lane_symbols)
+        empty = {"split": encode_split, "wide": encode_wide, "reversible": encode_reversible}[format](enc, b"", 0, 0, f, lane_symbols)
         bound = wide_stream_bound if wide else split_stream_bound
-        encode_regions = wide_encode_regions_device if wide else split_encode_regions_device
-        encode_to_budget = wide_encode_to_budget_device if wide else split_encode_to_budget_device
+        encode_regions = {"split": split_encode_regions_device, "wide": wide_encode_regions_device,
+                          "reversible": reversible_encode_regions_device}[format]
+        encode_to_budget = wide_encode_to_budget_device if wide else split_encode_to_budget_device   # (max_bytes: split, wide)
         out = [(b, empty) for b in boxes]
         for i, j in _runs(boxes):
             bw, bh = boxes[i][2], boxes[i][3]
@@ -1618,7 +1631,7 @@ def decode_person_chunks(chunks, d_frames_out, width: int, height: int, frames: 
     """Hybrid decode: chunk k of `chunks` (encode_person_chunks' list of (bbox, .alc bytes)) is decoded and pasted into
     its bbox of frames [k * frames, (k + 1) * frames) of d_frames_out (width x height RGB in HBM, typically holding the
     background).  Empty chunks paste nothing; no byte outside the boxes is written.  Each chunk is decoded by its own
-    container version (alc_version), so a list may mix version 1, version 2 and version 3 chunks."""
+    container version (alc_version), so a list may mix chunks of versions 1 to 4."""
     W, H, f = _positive_u32(width, "width"), _positive_u32(height, "height"), _positive_u32(frames, "frames")
     boxes, alcs, versions, lanes = [], [], [], {}
     for k, (bbox, alc) in enumerate(chunks):
@@ -1630,10 +1643,11 @@ def decode_person_chunks(chunks, d_frames_out, width: int, height: int, frames: 
         data = bytes(alc)
         version = alc_version(data)
         if b[2] * b[3]:
-            c = split_info(data) if version == 2 else wide_info(data) if version == 3 else EncodedChunk.from_bytes(data)
+            c = (split_info(data) if version == 2 else wide_info(data) if version == 3 else reversible_info(data) if version == 4
+                 else EncodedChunk.from_bytes(data))
             if (c.width, c.height, c.frames) != (b[2], b[3], f):
                 raise CodecError(2, f"chunk {k}: .alc is {c.width}x{c.height}x{c.frames}, bbox says {b[2]}x{b[3]}x{f}")
-            if version in (2, 3):
+            if version in (2, 3, 4):
                 lanes[k] = c.lane_symbols
         boxes.append(b)
         alcs.append(data)
@@ -1654,8 +1668,9 @@ def decode_person_chunks(chunks, d_frames_out, width: int, height: int, frames: 
     batches = {}
     for i, j in runs:
         bw, bh = boxes[i][2], boxes[i][3]
-        if versions[i] in (2, 3):
-            decode_regions = wide_decode_regions_device if versions[i] == 3 else split_decode_regions_device
+        if versions[i] in (2, 3, 4):
+            decode_regions = {2: split_decode_regions_device, 3: wide_decode_regions_device,
+                              4: reversible_decode_regions_device}[versions[i]]
             stride = (max(len(a) for a in alcs[i:j]) + 255) & ~255
             host = np.zeros((j - i, stride), np.uint8)
             for k in range(i, j):
@@ -1865,12 +1880,15 @@ def forward_symbols_wide_device(d_rgb_ptr: int, width: int, height: int, frames:
 
 
 def decode_alc(data) -> np.ndarray:
-    """The RGB bytes of a container of any version: 1 (FrameDecoder), 2 (decode_split) or 3 (decode_wide)."""
+    """The RGB bytes of a container of any version: 1 (FrameDecoder), 2 (decode_split), 3 (decode_wide) or
+    4 (decode_reversible)."""
     version = alc_version(data)
     if version == 2:
         return decode_split(data)
     if version == 3:
         return decode_wide(data)
+    if version == 4:
+        return decode_reversible(data)
     return FrameDecoder().decode(EncodedChunk.from_bytes(data))   # version 1, and every refusal the v1 parser words
 
 
@@ -2070,3 +2088,96 @@ def wide_encode_to_budget_device(d_frames_ptr: int, width: int, height: int, fra
     Returns (chosen, fits, sizes)."""
     return _encode_container_to_budget("wide", d_frames_ptr, width, height, frames, n_chunks, wavelet_type, budgets, d_out_ptr,
                                        out_stride, min_quality, max_quality, lane_symbols, frame_width, frame_height, origins, stream)
+
+
+# ---- reversible format (.alc version 4, DESIGN.md section 12) ----
+# Version 3 whose decoder runs the forward lifting's mirror: at quality 100 (quantiser step 1) the pixels come back exactly.
+# The container for lossless archival and intermediate storage; below quality 100 prefer version 3 (or 2).  The encoder is
+# version 3's -- the bytes differ from encode_wide's in byte 4 only -- so predict_wide_sizes brackets a version 4 length
+# exactly as it does a version 3 one and wide_stream_bound is the stream bound; there are no byte-budget calls.
+
+LOSSLESS_QUALITY = 100
+
+
+def reversible_info(data) -> SplitInfo:
+    """The header fields of a version 4 container (validated, no device needed); the fields are version 2's."""
+    buf = _as_u8(data)
+    c = _CSplitInfo()
+    _check(load_library().alice_codec_reversible_info(_p(buf, _u8p), buf.size, C.byref(c)))
+    return SplitInfo(c)
+
+
+def encode_reversible(encoder: "FrameEncoder", rgb_frames, width: int, height: int, frames: int, lane_symbols: int = 0) -> bytes:
+    """One chunk as version 4 bytes, with the encoder's wavelet and quality (lane_symbols 0: the default)."""
+    lib = load_library()
+    buf = _as_u8(rgb_frames)
+    _dims_u32(width, height, frames, lane_symbols)
+    n = C.c_uint64(0)
+    src = _p(buf, _u8p) if buf.size else C.cast(C.c_char_p(b""), _u8p)
+    ptr = lib.alice_codec_encode_reversible(encoder._h, src, buf.size, width, height, frames, lane_symbols, C.byref(n))
+    if not ptr:
+        _raise_last()
+    try:
+        return _copy_out(ptr, n.value).tobytes()
+    finally:
+        lib.alice_codec_data_free64(ptr, n.value)
+
+
+def decode_reversible(data) -> np.ndarray:
+    """The RGB bytes of a version 4 container."""
+    lib = load_library()
+    buf = _as_u8(data)
+    n = C.c_uint64(0)
+    ptr = lib.alice_codec_decode_reversible(_p(buf, _u8p), buf.size, C.byref(n))
+    if not ptr:
+        _raise_last()
+    return _adopt(ptr, n.value, lib.alice_codec_data_free64)
+
+
+def encode_lossless(rgb_frames, width: int, height: int, frames: int, wavelet_type: WaveletType = WaveletType.Cdf53,
+                    lane_symbols: int = 0) -> bytes:
+    """One chunk as version 4 bytes at quality 100: decode_reversible (or decode_alc) returns rgb_frames exactly."""
+    return encode_reversible(FrameEncoder(LOSSLESS_QUALITY, WaveletType(wavelet_type)), rgb_frames, width, height, frames, lane_symbols)
+
+
+def reversible_encode_device(d_rgb_ptr: int, width: int, height: int, frames: int, n_chunks: int, wavelet_type: WaveletType,
+                             quality: int, d_out_ptr: int, out_stride: int, qualities=None, lane_symbols: int = 0,
+                             stream: int = 0) -> np.ndarray:
+    """n_chunks packed device chunks -> version 4 bytes at d_out_ptr + i * out_stride; returns the sizes."""
+    sizes = np.zeros(n_chunks, np.uint64)
+    q = None if qualities is None else np.ascontiguousarray(qualities, dtype=np.uint8).reshape(-1)
+    if q is not None and q.size != n_chunks:
+        raise ValueError("one quality per chunk")
+    _dims_u32(width, height, frames, n_chunks, lane_symbols)
+    _check(load_library().alice_codec_dev_encode_reversible(d_rgb_ptr, width, height, frames, n_chunks, int(wavelet_type), quality,
+                                                            None if q is None else _p(q, _u8p), lane_symbols, d_out_ptr,
+                                                            out_stride, _p(sizes, _u64p), stream or None))
+    return sizes
+
+
+def encode_lossless_device(d_rgb_ptr: int, width: int, height: int, frames: int, n_chunks: int, d_out_ptr: int, out_stride: int,
+                           wavelet_type: WaveletType = WaveletType.Cdf53, lane_symbols: int = 0, stream: int = 0) -> np.ndarray:
+    """reversible_encode_device at quality 100 for every chunk; returns the sizes."""
+    return reversible_encode_device(d_rgb_ptr, width, height, frames, n_chunks, wavelet_type, LOSSLESS_QUALITY, d_out_ptr, out_stride,
+                                    lane_symbols=lane_symbols, stream=stream)
+
+
+def reversible_decode_device(d_alc_ptr: int, alc_stride: int, sizes, d_rgb_out_ptr: int, stream: int = 0) -> None:
+    s = np.ascontiguousarray(sizes, dtype=np.uint64).reshape(-1)
+    _check(load_library().alice_codec_dev_decode_reversible(d_alc_ptr, alc_stride, _p(s, _u64p), s.size, d_rgb_out_ptr,
+                                                            stream or None))
+
+
+def reversible_encode_regions_device(d_frames_ptr: int, frame_width: int, frame_height: int, origins, width: int, height: int,
+                                     frames: int, wavelet_type: WaveletType, quality: int, d_out_ptr: int, out_stride: int,
+                                     qualities=None, lane_symbols: int = 0, stream: int = 0) -> np.ndarray:
+    """wide_encode_regions_device for version 4: the bytes of chunk i are encode_reversible's of the crop; returns the sizes."""
+    return _encode_container_regions("reversible", d_frames_ptr, frame_width, frame_height, origins, width, height, frames,
+                                     wavelet_type, quality, d_out_ptr, out_stride, qualities, lane_symbols, stream)
+
+
+def reversible_decode_regions_device(d_alc_ptr: int, alc_stride: int, sizes, d_frames_out_ptr: int, frame_width: int,
+                                     frame_height: int, origins, stream: int = 0) -> None:
+    """wide_decode_regions_device for version 4: no byte outside the rectangles is written."""
+    _decode_container_regions("reversible", d_alc_ptr, alc_stride, sizes, d_frames_out_ptr, frame_width, frame_height, origins,
+                              stream)

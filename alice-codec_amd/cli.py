@@ -6,6 +6,9 @@
 `--format wide` the wide container (.alc version 3, section 11: the one whose video comes back at the top of the quality
 scale); `--max-bytes` and `encode-chunks --kbps` work in v1 and split, and are still refused with `--format wide` here (the
 library has the version 3 budget encode, `encode_wide_to_size`; this front end does not call it yet);
+`--format reversible` the reversible container (.alc version 4, section 12: version 3 with the mirrored inverse, lossless at
+quality 100), and `--lossless` is short for `--format reversible --quality 100`; version 4 has no byte budget, so
+`--max-bytes` and `--kbps` are refused with it;
 `decode` and `info` pick the format from the version byte unless `--format` names one.  The default of every subcommand
 is version 1.
 Like the reference it treats the whole input file as ONE chunk (src/bin/main.rs:117-122).  `encode-chunks`
@@ -19,8 +22,8 @@ import sys
 import numpy as np
 
 from . import (DEFAULT_CHUNK_SIZE, CodecError, EncodedChunk, FrameDecoder, FrameEncoder, WaveletType, budget_bytes_per_chunk,
-               alc_version, decode_split, decode_wide, encode_many, encode_split, encode_split_to_size, encode_to_size, encode_wide,
-               split_info, wide_info)
+               alc_version, decode_reversible, decode_split, decode_wide, encode_many, encode_reversible, encode_split,
+               encode_split_to_size, encode_to_size, encode_wide, reversible_info, split_info, wide_info)
 
 WAVELETS = {"cdf53": WaveletType.Cdf53, "cdf97": WaveletType.Cdf97, "haar": WaveletType.Haar}
 WAVELET_NAMES = {WaveletType.Cdf53: "CDF 5/3", WaveletType.Cdf97: "CDF 9/7", WaveletType.Haar: "Haar"}
@@ -32,9 +35,30 @@ def parse_wavelet(s: str) -> WaveletType:
     return WAVELETS[s]
 
 
-FORMAT_VERSION = {"v1": 1, "split": 2, "wide": 3}
+FORMAT_VERSION = {"v1": 1, "split": 2, "wide": 3, "reversible": 4}
 NO_WIDE_BUDGET = ("--format wide cannot be combined with {} on the command line yet: call encode_wide_to_size from the library for a "
                   "version 3 byte budget, or use --format split or v1 here")
+
+
+NO_REVERSIBLE_BUDGET = ("--format reversible cannot be combined with {}: version 4 is the lossless container (quality 100 has no "
+                        "quality to search, and a lossy version 4 is not recommended); use --format wide, split or v1 for a byte budget")
+LOSSLESS_CONFLICT = "--lossless is --format reversible --quality 100: it cannot be combined with {}"
+CONTAINER_INFO = {2: split_info, 3: wide_info, 4: reversible_info}
+CONTAINER_DECODE = {2: decode_split, 3: decode_wide, 4: decode_reversible}
+CONTAINER_NAME = {2: "split-stream (version 2)", 3: "wide split-stream (version 3)", 4: "reversible split-stream (version 4)"}
+
+
+def _apply_lossless(a) -> None:
+    """--lossless: --format reversible --quality 100, refused together with another format or quality."""
+    if not a.lossless:
+        if a.quality is None:
+            a.quality = 90
+        return
+    if a.format not in (None, "reversible"):
+        raise ValueError(LOSSLESS_CONFLICT.format(f"--format {a.format}"))
+    if a.quality not in (None, 100):
+        raise ValueError(LOSSLESS_CONFLICT.format(f"--quality {a.quality}"))
+    a.format, a.quality = "reversible", 100
 
 
 def _container_version(a, data) -> int:
@@ -44,17 +68,22 @@ def _container_version(a, data) -> int:
 
 def cmd_encode(a) -> None:
     wt = parse_wavelet(a.wavelet)
+    _apply_lossless(a)
+    a.format = a.format or "v1"
     if a.format == "wide" and a.max_bytes is not None:
         raise ValueError(NO_WIDE_BUDGET.format("--max-bytes"))
+    if a.format == "reversible" and a.max_bytes is not None:
+        raise ValueError(NO_REVERSIBLE_BUDGET.format("--max-bytes"))
     rgb = np.fromfile(a.input, dtype=np.uint8)
     quality = a.quality
-    if a.format == "wide":
-        data = encode_wide(FrameEncoder.with_wavelet(a.quality, wt), rgb, a.width, a.height, a.frames, a.lane_symbols)
+    if a.format in ("wide", "reversible"):
+        encode_one = encode_reversible if a.format == "reversible" else encode_wide
+        data = encode_one(FrameEncoder.with_wavelet(a.quality, wt), rgb, a.width, a.height, a.frames, a.lane_symbols)
         with open(a.output, "wb") as f:
             f.write(data)
         ratio = 0.0 if rgb.size == 0 else len(data) / rgb.size
         print(f"encoded {a.width}x{a.height}x{a.frames} ({rgb.size} bytes) -> {len(data)} bytes "
-              f"({ratio * 100:.1f}% ratio, quality={quality}, wavelet={a.wavelet}, format=wide)", file=sys.stderr)
+              f"({ratio * 100:.1f}% ratio, quality={quality}, wavelet={a.wavelet}, format={a.format})", file=sys.stderr)
         return
     if a.format == "split":
         if a.max_bytes is not None:
@@ -90,8 +119,12 @@ def cmd_encode(a) -> None:
 
 def cmd_encode_chunks(a) -> None:
     wt = parse_wavelet(a.wavelet)
+    _apply_lossless(a)
+    a.format = a.format or "v1"
     if a.format == "wide" and a.kbps is not None:
         raise ValueError(NO_WIDE_BUDGET.format("--kbps"))
+    if a.format == "reversible" and a.kbps is not None:
+        raise ValueError(NO_REVERSIBLE_BUDGET.format("--kbps"))
     frame_bytes = a.width * a.height * 3
     rgb = np.memmap(a.input, dtype=np.uint8, mode="r")
     if frame_bytes == 0 or rgb.size % frame_bytes:
@@ -102,8 +135,8 @@ def cmd_encode_chunks(a) -> None:
         return
     enc = FrameEncoder.with_wavelet(a.quality, wt)
     starts = list(range(0, n_frames, a.chunk))
-    if a.format in ("split", "wide"):   # one chunk uses the whole device: chunk after chunk
-        encode_one = encode_wide if a.format == "wide" else encode_split
+    if a.format in ("split", "wide", "reversible"):   # one chunk uses the whole device: chunk after chunk
+        encode_one = {"split": encode_split, "wide": encode_wide, "reversible": encode_reversible}[a.format]
         for k, s0 in enumerate(starts):
             f = min(a.chunk, n_frames - s0)
             data = encode_one(enc, np.ascontiguousarray(rgb[s0 * frame_bytes:(s0 + f) * frame_bytes]), a.width, a.height, f,
@@ -160,9 +193,9 @@ def _encode_chunks_to_rate(a, wt, rgb, frame_bytes, n_frames) -> None:
 def cmd_decode(a) -> None:
     data = np.fromfile(a.input, dtype=np.uint8)
     version = _container_version(a, data)
-    if version in (2, 3):
-        i = wide_info(data) if version == 3 else split_info(data)
-        rgb = decode_wide(data) if version == 3 else decode_split(data)
+    if version in CONTAINER_INFO:
+        i = CONTAINER_INFO[version](data)
+        rgb = CONTAINER_DECODE[version](data)
         rgb.tofile(a.output)
         print(f"decoded {i.width}x{i.height}x{i.frames} -> {rgb.size} bytes (raw RGB)", file=sys.stderr)
         return
@@ -175,14 +208,14 @@ def cmd_decode(a) -> None:
 def cmd_info(a) -> None:
     data = np.fromfile(a.input, dtype=np.uint8)
     version = _container_version(a, data)
-    if version in (2, 3):
-        i = wide_info(data) if version == 3 else split_info(data)
+    if version in CONTAINER_INFO:
+        i = CONTAINER_INFO[version](data)
         raw = i.width * i.height * i.frames * 3
         payload = sum(i.payload_len)
         print("ALICE-Codec Bitstream Info")
         print(f"  File:        {a.input}")
         print(f"  File size:   {data.size} bytes")
-        print("  Format:      " + ("wide split-stream (version 3)" if version == 3 else "split-stream (version 2)"))
+        print("  Format:      " + CONTAINER_NAME[version])
         print(f"  Width:       {i.width}")
         print(f"  Height:      {i.height}")
         print(f"  Frames:      {i.frames}")
@@ -229,17 +262,19 @@ def main(argv=None) -> int:
         else:
             e.add_argument("-c", "--chunk", type=int, default=DEFAULT_CHUNK_SIZE)
             e.add_argument("--in-flight", type=int, default=16, help="chunks encoded per call (GPU memory: about 2.4x the raw size of a chunk each)")
-        e.add_argument("-q", "--quality", type=_u8, default=90)
+        e.add_argument("-q", "--quality", type=_u8, default=None, help="0..100 (default 90; 100 with --lossless)")
         e.add_argument("-w", "--wavelet", default="cdf53")
         if name == "encode":
             e.add_argument("--max-bytes", type=int, default=None, help="encode at the highest quality that fits this many bytes")
         else:
             e.add_argument("--kbps", type=int, default=None, help="target bitrate: a byte budget per chunk (with --fps)")
             e.add_argument("--fps", type=float, default=30.0)
-        e.add_argument("--format", choices=("v1", "split", "wide"), default="v1",
-                       help="v1: the reference's bitstream; split: .alc version 2; wide: .alc version 3 (untruncated symbols, for the top qualities)")
+        e.add_argument("--format", choices=("v1", "split", "wide", "reversible"), default=None,
+                       help="v1 (default): the reference's bitstream; split: .alc version 2; wide: .alc version 3 (untruncated symbols, for "
+                            "the top qualities); reversible: .alc version 4 (version 3 with the mirrored inverse: lossless at quality 100)")
+        e.add_argument("--lossless", action="store_true", help="short for --format reversible --quality 100")
         e.add_argument("--lane-symbols", type=int, default=0,
-                       help="--format split / wide: symbols per lane (power of two in 64..16384, wide: 64..8192; 0 = default)")
+                       help="--format split / wide / reversible: symbols per lane (power of two in 64..16384, wide and reversible: 64..8192; 0 = default)")
         e.add_argument("--min-quality", type=_u8, default=10)
         e.add_argument("--max-quality", type=_u8, default=95)
     d = sub.add_parser("decode")
@@ -248,7 +283,7 @@ def main(argv=None) -> int:
     i = sub.add_parser("info")
     i.add_argument("input")
     for x in (d, i):
-        x.add_argument("--format", choices=("auto", "v1", "split", "wide"), default="auto",
+        x.add_argument("--format", choices=("auto", "v1", "split", "wide", "reversible"), default="auto",
                        help="auto: from the file's version byte; otherwise the file must be of that format")
     a = p.parse_args(argv)
     try:

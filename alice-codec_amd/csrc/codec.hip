@@ -718,7 +718,18 @@ inline uint64_t round_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
 // dequantised sample is at most max_q * |step|; each lifting step adds at most (2 * other * |c| + 4096) / 8192 + 1.
 // The flags of launch_inverse_transform: exact unless 32-bit (24 x 24-bit) products are exact everywhere; mid16 (never with
 // exact): every value after the temporal pass fits i16, so it can be stored in 16 bits; lds16: also after the column pass.
+// The same bound covers the mirrored inverse of version 4: its step subtracts
+// floor((v + 4096) / 8192) with v = (a + b) * c, and |floor((v + 4096) / 8192)| <= (|v| + 4096) / 8192 + 1 is the increment
+// above; the operand and product conditions of the 24-bit multiply depend on |a + b| and |c| only.
 struct InverseBounds { bool exact; bool mid16; bool lds16; };
+
+// The container of the lane-parallel orchestration (PART 4): version 2 (u8 symbols), version 3 (u16 symbols, the
+// reference's inverse) or version 4 (version 3 with the mirrored inverse).  Wide and reversible size and launch alike
+// except for the version byte and the inverse launcher.
+enum SplitFormat : int { kFormatSplit = 0, kFormatWide = 1, kFormatReversible = 2 };
+inline bool is_wide(SplitFormat f) { return f != kFormatSplit; }
+inline uint8_t format_version(SplitFormat f) { return (uint8_t)(2 + (int)f); }
+inline SplitFormat format_of_version(int version) { return version == 4 ? kFormatReversible : version == 3 ? kFormatWide : kFormatSplit; }
 constexpr int kByteMaxQ = 128;
 InverseBounds inverse_bounds(int wavelet, const int32_t step[3], int max_q = kByteMaxQ) {
     const LiftSteps ls = lift_steps(wavelet);
@@ -1100,11 +1111,16 @@ int decode_work_alloc(DecodeWork& w, const ChunkDims& d, int n_chunks, uint8_t* 
 
 // The inverse transform of one chunk: the tile kernels where they cover the shape (d_scratch: their band slots, null when
 // they do not), else exact reference arithmetic.
-// wide: d_sym holds u16 symbols (.alc v3), and the instance choice starts from |q| <= kWideMaxQ.
+// fmt wide or reversible: d_sym holds u16 symbols (.alc v3, v4), and the instance choice starts from |q| <= kWideMaxQ;
+// reversible: every lifting step is the forward's mirror (the tile kernels' MIRROR instances, the generic path's mirror mode).
 int inverse_chunk(const uint8_t* d_sym, const ChunkDims& d, int wavelet, const int32_t step[3], void* d_scratch, DecodeWork& w,
-                  const RgbLayout& rgb, hipStream_t st, bool wide = false) {
+                  const RgbLayout& rgb, hipStream_t st, SplitFormat fmt = kFormatSplit) {
+    const bool wide = is_wide(fmt), mirror = fmt == kFormatReversible;
     const InverseBounds ib = inverse_bounds(wavelet, step, wide ? kWideMaxQ : kByteMaxQ);
-    if (wide) {
+    if (mirror) {
+        if (d_scratch && launch_inverse_transform_reversible((const uint16_t*)d_sym, d, wavelet, step, ib.exact, ib.mid16, ib.lds16, d_scratch, rgb, st))
+            return kOk;
+    } else if (wide) {
         if (d_scratch && launch_inverse_transform_wide((const uint16_t*)d_sym, d, wavelet, step, ib.exact, ib.mid16, ib.lds16, d_scratch, rgb, st))
             return kOk;
     } else if (d_scratch && launch_inverse_transform(d_sym, d, wavelet, step, ib.exact, ib.mid16, ib.lds16, d_scratch, rgb, st)) return kOk;
@@ -1119,9 +1135,9 @@ int inverse_chunk(const uint8_t* d_sym, const ChunkDims& d, int wavelet, const i
         if (wide) launch_from_symbols_wide((const uint16_t*)d_sym + (size_t)c * d.padded, qb, d.padded, st);
         else launch_from_symbols(d_sym + (size_t)c * d.padded, qb, d.padded, st);
         launch_dequantize(qb, vol, d.padded, step[c], st);
-        launch_wavelet_axis(vol, w.tmp.as<int32_t>(), D, W * H, 1, 0, W * H, 1, wavelet, true, st);
-        launch_wavelet_axis(vol, w.tmp.as<int32_t>(), H, W, D, W * H, W, 1, wavelet, true, st);
-        launch_wavelet_axis(vol, w.tmp.as<int32_t>(), W, 1, D * H, W, 1, 0, wavelet, true, st);
+        launch_wavelet_axis(vol, w.tmp.as<int32_t>(), D, W * H, 1, 0, W * H, 1, wavelet, true, st, mirror);
+        launch_wavelet_axis(vol, w.tmp.as<int32_t>(), H, W, D, W * H, W, 1, wavelet, true, st, mirror);
+        launch_wavelet_axis(vol, w.tmp.as<int32_t>(), W, 1, D * H, W, 1, 0, wavelet, true, st, mirror);
         launch_strip_channel(vol, d, pl + (size_t)c * d.n_pixels, st);
     }
     launch_ycocg_to_rgb(pl, pl + d.n_pixels, pl + 2 * d.n_pixels, d, rgb, st);
@@ -3278,13 +3294,14 @@ int alice_codec_dev_extract_person_rgb(const void* d_mask, uint32_t width, uint3
 
 namespace {
 
-// wide: the u16-symbol container (.alc v3) -- the same orchestration with two bytes per symbol, the
-// wide kernels and lane lengths up to 8192
-bool split_lane_ok(uint32_t L, bool wide = false) {
-    return L >= kSplitMinLane && L <= (wide ? kSplitWideMaxLane : kSplitMaxLane) && (L & (L - 1u)) == 0u;
+// fmt: the container (SplitFormat).  Wide (.alc v3) is the same orchestration with two bytes per
+// symbol, the wide kernels and lane lengths up to 8192; reversible (.alc v4, section 12) is wide with its own version byte
+// and the mirrored inverse.
+bool split_lane_ok(uint32_t L, SplitFormat fmt = kFormatSplit) {
+    return L >= kSplitMinLane && L <= (is_wide(fmt) ? kSplitWideMaxLane : kSplitMaxLane) && (L & (L - 1u)) == 0u;
 }
-const char* split_lane_msg(bool wide) {
-    return wide ? "lane_symbols must be a power of two in [64, 8192]" : "lane_symbols must be a power of two in [64, 16384]";
+const char* split_lane_msg(SplitFormat fmt) {
+    return is_wide(fmt) ? "lane_symbols must be a power of two in [64, 8192]" : "lane_symbols must be a power of two in [64, 16384]";
 }
 uint32_t split_blocks(uint64_t n, uint32_t L) { return (uint32_t)((n + 64ull * L - 1) / (64ull * L)); }   // n <= 2^32: at most 2^20
 
@@ -3294,7 +3311,7 @@ inline uint64_t get_u64(const uint8_t* p) { return (uint64_t)get_u32(p) | ((uint
 struct SplitHeader {
     uint32_t width = 0, height = 0, frames = 0, lane_symbols = 0;
     uint8_t wavelet = 0;
-    bool wide = false;   // version 3
+    SplitFormat fmt = kFormatSplit;   // from the version byte
     int32_t step[3] = {1, 1, 1}, dead_zone[3] = {1, 1, 1};
     uint32_t num_symbols[3] = {0, 0, 0}, n_blocks[3] = {0, 0, 0};
     uint64_t payload_len[3] = {0, 0, 0};
@@ -3310,14 +3327,14 @@ int parse_split_header(const uint8_t* data, uint64_t total_len, SplitHeader& h, 
     if (memcmp(data, "ALCC", 4) != 0) return fail(kInvalidBitstream, "bad magic (expected ALCC)");
     if (data[4] != version)
         return fail(kInvalidBitstream, "unsupported version: " + std::to_string((int)data[4]) + " (expected " + std::to_string(version) + ")");
-    h.wide = version == 3;
+    h.fmt = format_of_version(version);
     if (data[5] > 2) return fail(kInvalidBitstream, "unknown wavelet type byte: " + std::to_string((int)data[5]));
     h.wavelet = data[5];
     h.width = get_u32(data + 6); h.height = get_u32(data + 10); h.frames = get_u32(data + 14);
     h.lane_symbols = get_u32(data + 18);
-    if (!split_lane_ok(h.lane_symbols, h.wide))
+    if (!split_lane_ok(h.lane_symbols, h.fmt))
         return fail(kInvalidBitstream, "lane_symbols " + std::to_string(h.lane_symbols) + " is not a power of two in [64, " +
-                                           std::to_string(h.wide ? kSplitWideMaxLane : kSplitMaxLane) + "]");
+                                           std::to_string(is_wide(h.fmt) ? kSplitWideMaxLane : kSplitMaxLane) + "]");
     if (total_len < kSplitHeaderBytes)
         return fail(kInvalidBitstream, "data too short for the header: " + std::to_string(total_len) + " bytes (minimum " + std::to_string(kSplitHeaderBytes) + ")");
     *d = make_dims(h.width, h.height, h.frames);
@@ -3387,9 +3404,9 @@ struct SplitWork {
     ~SplitWork() { if (armed) (void)hipStreamSynchronize(st); }
 };
 
-int split_work_alloc(SplitWork& w, int n_jobs, uint64_t n, uint32_t L, bool encode, bool wide = false) {
+int split_work_alloc(SplitWork& w, int n_jobs, uint64_t n, uint32_t L, bool encode, SplitFormat fmt = kFormatSplit) {
     w.n_jobs = n_jobs;
-    w.wide = wide;
+    w.wide = is_wide(fmt);
     w.n_blocks = split_blocks(n, L);
     const size_t nb = w.n_blocks;
     TRY(w.jobs.alloc((size_t)n_jobs * sizeof(SplitJob)));
@@ -3514,13 +3531,14 @@ struct SplitChunkEncode {
     std::vector<uint8_t> q;
     uint32_t B = 0, L = 0;
     uint8_t wavelet = 0;
-    bool wide = false;
+    SplitFormat fmt = kFormatSplit;
 };
 
 int split_count_chunks(SplitChunkEncode& e, const RgbLayout* rgb, uint32_t B, const ChunkDims& d, uint8_t wavelet, const uint8_t* q,
-                       uint32_t L, hipStream_t st, std::vector<uint64_t>& sizes, bool wide = false) {
+                       uint32_t L, hipStream_t st, std::vector<uint64_t>& sizes, SplitFormat fmt = kFormatSplit) {
     EncodeWork& ew = e.ew;
-    e.B = B; e.L = L; e.wavelet = wavelet; e.wide = wide;
+    e.B = B; e.L = L; e.wavelet = wavelet; e.fmt = fmt;
+    const bool wide = is_wide(fmt);
     const size_t sb = wide ? 2 : 1;   // bytes per symbol
     e.q.assign(q, q + B);
     ew.d = d; ew.n_chunks = (int)B;
@@ -3533,7 +3551,7 @@ int split_count_chunks(SplitChunkEncode& e, const RgbLayout* rgb, uint32_t B, co
                           ew.hist.as<uint32_t>() + (size_t)i * 3 * 256, st, wide));
     e.hd.assign(B, SplitHeaderDesc{});
     SplitWork& w = e.w;
-    TRY(split_work_alloc(w, (int)(3 * B), d.padded, L, true, wide));
+    TRY(split_work_alloc(w, (int)(3 * B), d.padded, L, true, fmt));
     for (size_t j = 0; j < 3 * (size_t)B; ++j) w.h[j].sym = ew.sym.as<uint8_t>() + j * d.padded * sb;
     TRY(split_count(w, ew.hist.as<uint32_t>(), st, e.totals, nullptr));
     sizes.resize(B);
@@ -3563,7 +3581,7 @@ int split_write_chunks(SplitChunkEncode& e, const std::vector<uint8_t*>& outs, h
     HIP_TRY(hipMemcpyAsync(e.d_hd.p, e.hd.data(), e.hd.size() * sizeof(SplitHeaderDesc), hipMemcpyHostToDevice, st));
     TRY(split_write(w, st));
     launch_split_headers(e.d_hd.as<SplitHeaderDesc>(), (int)B, st);
-    if (e.wide) launch_split_header_version(e.d_hd.as<SplitHeaderDesc>(), (int)B, 3, st);
+    if (e.fmt != kFormatSplit) launch_split_header_version(e.d_hd.as<SplitHeaderDesc>(), (int)B, format_version(e.fmt), st);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
     return kOk;
@@ -3572,9 +3590,9 @@ int split_write_chunks(SplitChunkEncode& e, const std::vector<uint8_t*>& outs, h
 // Both halves: place(sizes, outs) is called once the sizes are known and names where each chunk's bytes go (device).
 template <typename Place>
 int split_encode_chunks(const RgbLayout* rgb, uint32_t B, const ChunkDims& d, uint8_t wavelet, const uint8_t* q, uint32_t L,
-                        hipStream_t st, std::vector<uint64_t>& sizes, Place place, bool wide = false) {
+                        hipStream_t st, std::vector<uint64_t>& sizes, Place place, SplitFormat fmt = kFormatSplit) {
     SplitChunkEncode e;
-    TRY(split_count_chunks(e, rgb, B, d, wavelet, q, L, st, sizes, wide));
+    TRY(split_count_chunks(e, rgb, B, d, wavelet, q, L, st, sizes, fmt));
     std::vector<uint8_t*> outs(B, nullptr);
     TRY(place(sizes, outs));
     return split_write_chunks(e, outs, st);
@@ -3586,11 +3604,12 @@ int split_decode_chunks(const SplitHeader* hdr, const uint8_t* const* d_alc, uin
                         hipStream_t st) {
     DecodeWork dw;
     dw.d = d; dw.n_chunks = (int)B;
-    const bool wide = hdr[0].wide;    // (one parser, one version per call)
+    const SplitFormat fmt = hdr[0].fmt;   // (one parser, one version per call)
+    const bool wide = is_wide(fmt);
     const size_t sb = wide ? 2 : 1;   // bytes per symbol
     TRY(dw.sym.alloc((size_t)B * 3 * d.padded * sb));
     SplitWork w;
-    TRY(split_work_alloc(w, (int)(3 * B), d.padded, hdr[0].lane_symbols, false, wide));
+    TRY(split_work_alloc(w, (int)(3 * B), d.padded, hdr[0].lane_symbols, false, fmt));
     std::vector<uint16_t> freq((size_t)B * 3 * 256);
     bool all16 = true;
     for (uint32_t i = 0; i < B; ++i) {
@@ -3608,7 +3627,7 @@ int split_decode_chunks(const SplitHeader* hdr, const uint8_t* const* d_alc, uin
     if (transform_tiles_eligible(d)) TRY(dw.scratch_own.alloc(inverse_scratch_bytes(d, all16)));
     TRY(split_decode_launch(w, freq.data(), st));
     for (uint32_t i = 0; i < B; ++i)
-        TRY(inverse_chunk(dw.sym.as<uint8_t>() + (size_t)i * 3 * d.padded * sb, d, hdr[i].wavelet, hdr[i].step, dw.scratch_own.p, dw, rgb[i], st, wide));
+        TRY(inverse_chunk(dw.sym.as<uint8_t>() + (size_t)i * 3 * d.padded * sb, d, hdr[i].wavelet, hdr[i].step, dw.scratch_own.p, dw, rgb[i], st, fmt));
     HIP_TRY(hipGetLastError());
     return split_decode_verdict(w, st);
 }
@@ -3616,8 +3635,8 @@ int split_decode_chunks(const SplitHeader* hdr, const uint8_t* const* d_alc, uin
 // Chunks a device-resident call works on at a time: as many as keep its symbol buffer at or below 4 GiB (ten 1080p x 64
 // chunks).  Every chunk already fills the device on its own, so larger groups gain nothing, and a 32-chunk group (12.7 GB
 // of symbols) was measured to DEcode eleven times slower per chunk than groups of eight.
-uint32_t split_group(const ChunkDims& d, bool wide = false) {
-    const uint64_t per_chunk = 3 * d.padded * (wide ? 2 : 1);
+uint32_t split_group(const ChunkDims& d, SplitFormat fmt = kFormatSplit) {
+    const uint64_t per_chunk = 3 * d.padded * (is_wide(fmt) ? 2 : 1);
     const uint64_t g = (uint64_t(4) << 30) / (per_chunk ? per_chunk : 1);
     return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(g, 1), 21845);
 }
@@ -3679,9 +3698,9 @@ int split_choose_quality(const uint64_t* lo, const uint64_t* hi, uint64_t budget
 // chunk by chunk.  Returns after the stream has drained; nothing is written.  wide: version 3 -- a trial is the wide forward
 // pass, the table and the wide count pass, whose residual guard fails the call as it does in an encode.
 int split_choose_chunks(const RgbLayout* rgb, uint32_t n, const ChunkDims& d, uint8_t wavelet, uint32_t L, const uint64_t* budgets,
-                        uint8_t min_q, uint8_t max_q, uint8_t* chosen, uint8_t* fits, hipStream_t st, bool wide = false) {
+                        uint8_t min_q, uint8_t max_q, uint8_t* chosen, uint8_t* fits, hipStream_t st, SplitFormat fmt = kFormatSplit) {
     tl_split_trials.assign(n, 0u);
-    const uint32_t group = split_group(d, wide);
+    const uint32_t group = split_group(d, fmt);
     uint64_t lo[kQualities], hi[kQualities];
     for (uint32_t first = 0; first < n; first += group) {
         const uint32_t B = std::min(group, n - first);
@@ -3690,7 +3709,7 @@ int split_choose_chunks(const RgbLayout* rgb, uint32_t n, const ChunkDims& d, ui
             EncodeWork w;
             w.d = d; w.n_chunks = 1;
             if (transform_tiles_eligible(d)) TRY(w.scratch.alloc(forward_scratch_bytes(d)));
-            TRY(predict_chunks(rgb + first, B, d, wavelet, w, st, nullptr, rc, L, wide));
+            TRY(predict_chunks(rgb + first, B, d, wavelet, w, st, nullptr, rc, L, is_wide(fmt)));
         }
         for (uint32_t i = 0; i < B; ++i) {
             const uint32_t k = first + i;
@@ -3699,7 +3718,7 @@ int split_choose_chunks(const RgbLayout* rgb, uint32_t n, const ChunkDims& d, ui
                                      [&](uint8_t q, uint64_t* size) -> int {
                                          SplitChunkEncode e;
                                          std::vector<uint64_t> sz;
-                                         TRY(split_count_chunks(e, rgb + k, 1, d, wavelet, &q, L, st, sz, wide));
+                                         TRY(split_count_chunks(e, rgb + k, 1, d, wavelet, &q, L, st, sz, fmt));
                                          *size = sz[0];
                                          return kOk;
                                      },
@@ -3709,10 +3728,10 @@ int split_choose_chunks(const RgbLayout* rgb, uint32_t n, const ChunkDims& d, ui
     return kOk;
 }
 
-// n equal-shaped chunks at their layouts -> version 2 (wide: version 3) bytes at d_out + i * out_stride, in groups of split_group.
+// n equal-shaped chunks at their layouts -> version 2 (wide: version 3, reversible: version 4) bytes at d_out + i * out_stride, in groups of split_group.
 int split_encode_layouts(const RgbLayout* rgb, uint32_t n, const ChunkDims& d, uint8_t wavelet, const uint8_t* q, uint32_t L, void* d_out,
-                         uint64_t out_stride, uint64_t* sizes, hipStream_t st, bool wide = false) {
-    const uint32_t group = split_group(d, wide);
+                         uint64_t out_stride, uint64_t* sizes, hipStream_t st, SplitFormat fmt = kFormatSplit) {
+    const uint32_t group = split_group(d, fmt);
     for (uint32_t first = 0; first < n; first += group) {
         const uint32_t B = std::min(group, n - first);
         std::vector<uint64_t> sz;
@@ -3725,7 +3744,7 @@ int split_encode_layouts(const RgbLayout* rgb, uint32_t n, const ChunkDims& d, u
                                         outs[i] = (uint8_t*)d_out + (size_t)(first + i) * out_stride;
                                     }
                                     return kOk;
-                                }, wide));
+                                }, fmt));
         for (uint32_t i = 0; i < B; ++i) sizes[first + i] = sz[i];
     }
     return kOk;
@@ -3756,10 +3775,10 @@ int split_layouts(const void* d_frames, uint32_t frame_width, uint32_t frame_hei
 }
 
 // wavelet, then lane_symbols (0: the default), in the order of the split calls
-int check_split_args(uint8_t wavelet_type, uint32_t lane_symbols, uint32_t* L, bool wide = false) {
+int check_split_args(uint8_t wavelet_type, uint32_t lane_symbols, uint32_t* L, SplitFormat fmt = kFormatSplit) {
     if (wavelet_type > 2) return fail(kInvalidBitstream, "unknown wavelet type");
     *L = lane_symbols ? lane_symbols : kSplitDefaultLane;
-    if (!split_lane_ok(*L, wide)) return fail(kInvalidDimensions, split_lane_msg(wide));
+    if (!split_lane_ok(*L, fmt)) return fail(kInvalidDimensions, split_lane_msg(fmt));
     return kOk;
 }
 
@@ -3787,7 +3806,7 @@ int split_decode_device(const void* d_alc, uint64_t alc_stride, const uint64_t* 
     }
     std::vector<RgbLayout> layouts;
     TRY(layouts_of(d, layouts));
-    const uint32_t group = split_group(d, version == 3);
+    const uint32_t group = split_group(d, format_of_version(version));
     for (uint32_t first = 0; first < n_chunks; first += group)
         TRY(split_decode_chunks(hdr.data() + first, ptr.data() + first, std::min(group, n_chunks - first), d, layouts.data() + first, st));
     return kOk;
@@ -3818,11 +3837,11 @@ int alice_codec_split_normalize(const uint32_t hist[256], uint16_t freq[256]) {
 }
 
 static int stage_split_encode(const void* d_symbols, uint64_t n, const uint32_t hist[256], uint32_t lane_symbols, void* d_out,
-                              uint64_t cap, uint64_t* out_len, void* hip_stream, bool wide) {
+                              uint64_t cap, uint64_t* out_len, void* hip_stream, SplitFormat fmt) {
     clear_error();
     if ((!d_symbols && n) || !hist || !out_len || (!d_out && cap)) return fail(kNullArgument, "null argument");
     if (!lane_symbols) lane_symbols = kSplitDefaultLane;
-    if (!split_lane_ok(lane_symbols, wide)) return fail(kInvalidDimensions, split_lane_msg(wide));
+    if (!split_lane_ok(lane_symbols, fmt)) return fail(kInvalidDimensions, split_lane_msg(fmt));
     if (n > 0xFFFFFFFFull) return fail(kDimensionOverflow, "more symbols than the header's u32 num_symbols counts");
     uint64_t total = 0;
     for (int i = 0; i < 256; ++i) total += hist[i];
@@ -3841,7 +3860,7 @@ static int stage_split_encode(const void* d_symbols, uint64_t n, const uint32_t 
     // decodes to other data.  n < 2^32, so the u32 counts do not wrap.
     uint32_t* const d_used = dh.as<uint32_t>() + 256;
     HIP_TRY(hipMemsetAsync(d_used, 0, 256 * 4, st));
-    if (wide) launch_histogram_wide((const uint16_t*)d_symbols, n, d_used, st);
+    if (is_wide(fmt)) launch_histogram_wide((const uint16_t*)d_symbols, n, d_used, st);
     else launch_histogram((const uint8_t*)d_symbols, n, d_used, st);
     HIP_TRY(hipGetLastError());
     uint32_t used[256];
@@ -3851,15 +3870,15 @@ static int stage_split_encode(const void* d_symbols, uint64_t n, const uint32_t 
         if (used[s] && !hist[s])
             return fail(kInvalidBufferSize, "hist[" + std::to_string(s) + "] is 0 but the data holds symbol " + std::to_string(s) +
                                                 " (count " + std::to_string(used[s]) + ")" +
-                                                (wide && s == 255 ? ": 255 is the escape, every z >= 255" : ""));
+                                                (is_wide(fmt) && s == 255 ? ": 255 is the escape, every z >= 255" : ""));
     SplitWork w;
-    TRY(split_work_alloc(w, 1, n, lane_symbols, true, wide));
+    TRY(split_work_alloc(w, 1, n, lane_symbols, true, fmt));
     w.h[0].sym = (const uint8_t*)d_symbols;
     std::vector<uint64_t> totals;
     TRY(split_count(w, dh.as<uint32_t>(), st, totals, nullptr));
     if (totals[0] > cap)
         return fail(kInvalidBufferSize, "the stream needs " + std::to_string(totals[0]) + " bytes, capacity is " + std::to_string(cap) +
-                                            (wide ? " (alice_codec_wide_stream_bound gives the worst case)"
+                                            (is_wide(fmt) ? " (alice_codec_wide_stream_bound gives the worst case)"
                                                   : " (alice_codec_split_stream_bound gives the worst case)"));
     w.h[0].stream = (uint8_t*)d_out;
     TRY(split_write(w, st));
@@ -3870,15 +3889,15 @@ static int stage_split_encode(const void* d_symbols, uint64_t n, const uint32_t 
 
 int alice_codec_dev_split_encode(const void* d_symbols, uint64_t n, const uint32_t hist[256], uint32_t lane_symbols, void* d_out,
                                  uint64_t cap, uint64_t* out_len, void* hip_stream) {
-    return stage_split_encode(d_symbols, n, hist, lane_symbols, d_out, cap, out_len, hip_stream, false);
+    return stage_split_encode(d_symbols, n, hist, lane_symbols, d_out, cap, out_len, hip_stream, kFormatSplit);
 }
 
 static int stage_split_decode(const void* d_stream, uint64_t len, const uint16_t freq[256], uint32_t lane_symbols, void* d_symbols,
-                              uint64_t n, void* hip_stream, bool wide) {
+                              uint64_t n, void* hip_stream, SplitFormat fmt) {
     clear_error();
     if ((!d_stream && len) || !freq || (!d_symbols && n)) return fail(kNullArgument, "null argument");
     if (!lane_symbols) lane_symbols = kSplitDefaultLane;
-    if (!split_lane_ok(lane_symbols, wide)) return fail(kInvalidDimensions, split_lane_msg(wide));
+    if (!split_lane_ok(lane_symbols, fmt)) return fail(kInvalidDimensions, split_lane_msg(fmt));
     if (n > 0xFFFFFFFFull) return fail(kDimensionOverflow, "more symbols than the header's u32 num_symbols counts");
     uint32_t sum = 0;
     for (int i = 0; i < 256; ++i) sum += freq[i];
@@ -3889,7 +3908,7 @@ static int stage_split_decode(const void* d_stream, uint64_t len, const uint16_t
     hipStream_t st = (hipStream_t)hip_stream;
     ScopeStream scope(st);
     SplitWork w;
-    TRY(split_work_alloc(w, 1, n, lane_symbols, false, wide));
+    TRY(split_work_alloc(w, 1, n, lane_symbols, false, fmt));
     w.h[0].sym = (const uint8_t*)d_symbols;
     w.h[0].stream = (uint8_t*)d_stream;
     w.h[0].len = len;
@@ -3899,7 +3918,7 @@ static int stage_split_decode(const void* d_stream, uint64_t len, const uint16_t
 
 int alice_codec_dev_split_decode(const void* d_stream, uint64_t len, const uint16_t freq[256], uint32_t lane_symbols, void* d_symbols,
                                  uint64_t n, void* hip_stream) {
-    return stage_split_decode(d_stream, len, freq, lane_symbols, d_symbols, n, hip_stream, false);
+    return stage_split_decode(d_stream, len, freq, lane_symbols, d_symbols, n, hip_stream, kFormatSplit);
 }
 
 static int container_info(const uint8_t* data, uint64_t len, AliceSplitInfo* info, int version) {
@@ -3923,7 +3942,7 @@ static int container_info(const uint8_t* data, uint64_t len, AliceSplitInfo* inf
 int alice_codec_split_info(const uint8_t* data, uint64_t len, AliceSplitInfo* info) { return container_info(data, len, info, 2); }
 
 static uint8_t* container_encode(const FrameEncoder* encoder, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
-                                 uint32_t frames, uint32_t lane_symbols, uint64_t* out_len, bool wide) {
+                                 uint32_t frames, uint32_t lane_symbols, uint64_t* out_len, SplitFormat fmt) {
     clear_error();
     if (!encoder || !rgb || !out_len) { fail(kNullArgument, "null argument"); return nullptr; }
     auto run = [&](uint8_t** out) -> int {
@@ -3934,11 +3953,11 @@ static uint8_t* container_encode(const FrameEncoder* encoder, const uint8_t* rgb
         EncodedChunk* none = nullptr;
         if (n_pixels) TRY(validate_encode_many(encoder, rgb, rgb_len, width, height, frames, 1, &none, &d));
         const uint32_t L = lane_symbols ? lane_symbols : kSplitDefaultLane;
-        if (!split_lane_ok(L, wide)) return fail(kInvalidDimensions, split_lane_msg(wide));
+        if (!split_lane_ok(L, fmt)) return fail(kInvalidDimensions, split_lane_msg(fmt));
         if (n_pixels == 0) {
             *out = host_result_alloc(kSplitHeaderBytes);
             if (!*out) return fail(kOutOfMemory, "out of host memory");
-            write_empty_split(*out, encoder->wavelet, width, height, frames, L, quality_to_step(encoder->quality), wide ? 3 : 2);
+            write_empty_split(*out, encoder->wavelet, width, height, frames, L, quality_to_step(encoder->quality), format_version(fmt));
             *out_len = kSplitHeaderBytes;
             return kOk;
         }
@@ -3954,7 +3973,7 @@ static uint8_t* container_encode(const FrameEncoder* encoder, const uint8_t* rgb
                                     TRY(d_out.alloc(sz[0]));
                                     outs[0] = d_out.as<uint8_t>();
                                     return kOk;
-                                }, wide));
+                                }, fmt));
         *out = host_result_alloc(sizes[0]);
         if (!*out) return fail(kOutOfMemory, "out of host memory");
         const int rc = copy_to_host(*out, d_out.p, sizes[0], st);
@@ -3968,7 +3987,7 @@ static uint8_t* container_encode(const FrameEncoder* encoder, const uint8_t* rgb
 
 uint8_t* alice_codec_encode_split(const FrameEncoder* encoder, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
                                   uint32_t frames, uint32_t lane_symbols, uint64_t* out_len) {
-    return container_encode(encoder, rgb, rgb_len, width, height, frames, lane_symbols, out_len, false);
+    return container_encode(encoder, rgb, rgb_len, width, height, frames, lane_symbols, out_len, kFormatSplit);
 }
 
 static uint8_t* container_decode(const uint8_t* data, uint64_t len, uint64_t* out_len, int version) {
@@ -4008,14 +4027,14 @@ uint8_t* alice_codec_decode_split(const uint8_t* data, uint64_t len, uint64_t* o
 
 static int container_dev_encode(const void* d_rgb, uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks,
                                 uint8_t wavelet_type, uint8_t quality, const uint8_t* qualities, uint32_t lane_symbols, void* d_out,
-                                uint64_t out_stride, uint64_t* sizes, void* hip_stream, bool wide) {
+                                uint64_t out_stride, uint64_t* sizes, void* hip_stream, SplitFormat fmt) {
     clear_error();
     if (!d_rgb || !d_out || !sizes) return fail(kNullArgument, "null argument");
     if (wavelet_type > 2) return fail(kInvalidBitstream, "unknown wavelet type");
     ChunkDims d{};
     TRY(chunk_dims(width, height, frames, &d, n_chunks));
     const uint32_t L = lane_symbols ? lane_symbols : kSplitDefaultLane;
-    if (!split_lane_ok(L, wide)) return fail(kInvalidDimensions, split_lane_msg(wide));
+    if (!split_lane_ok(L, fmt)) return fail(kInvalidDimensions, split_lane_msg(fmt));
     TRY(ensure_device());
     hipStream_t st = (hipStream_t)hip_stream;
     ScopeStream scope(st);
@@ -4025,14 +4044,14 @@ static int container_dev_encode(const void* d_rgb, uint32_t width, uint32_t heig
         layouts[i] = packed_rgb((const uint8_t*)d_rgb + (size_t)i * d.n_pixels * 3, d);
         q[i] = qualities ? qualities[i] : quality;
     }
-    return split_encode_layouts(layouts.data(), n_chunks, d, wavelet_type, q.data(), L, d_out, out_stride, sizes, st, wide);
+    return split_encode_layouts(layouts.data(), n_chunks, d, wavelet_type, q.data(), L, d_out, out_stride, sizes, st, fmt);
 }
 
 int alice_codec_dev_encode_split(const void* d_rgb, uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks,
                                  uint8_t wavelet_type, uint8_t quality, const uint8_t* qualities, uint32_t lane_symbols, void* d_out,
                                  uint64_t out_stride, uint64_t* sizes, void* hip_stream) {
     return container_dev_encode(d_rgb, width, height, frames, n_chunks, wavelet_type, quality, qualities, lane_symbols, d_out, out_stride,
-                                sizes, hip_stream, false);
+                                sizes, hip_stream, kFormatSplit);
 }
 
 static int container_dev_decode(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks, void* d_rgb_out,
@@ -4058,25 +4077,25 @@ int alice_codec_dev_decode_split(const void* d_alc, uint64_t alc_stride, const u
 // ---- version 3: the wide container.  The same paths with the wide flag set. ----
 
 uint64_t alice_codec_wide_stream_bound(uint64_t n, uint32_t lane_symbols) {
-    if (!split_lane_ok(lane_symbols, true) || n > 0xFFFFFFFFull) return 0;
+    if (!split_lane_ok(lane_symbols, kFormatWide) || n > 0xFFFFFFFFull) return 0;
     return (uint64_t)split_blocks(n, lane_symbols) * (4 + 128 + 64 * 4) + 4 * n;
 }
 
 int alice_codec_dev_wide_encode(const void* d_symbols, uint64_t n, const uint32_t hist[256], uint32_t lane_symbols, void* d_out,
                                 uint64_t cap, uint64_t* out_len, void* hip_stream) {
-    return stage_split_encode(d_symbols, n, hist, lane_symbols, d_out, cap, out_len, hip_stream, true);
+    return stage_split_encode(d_symbols, n, hist, lane_symbols, d_out, cap, out_len, hip_stream, kFormatWide);
 }
 
 int alice_codec_dev_wide_decode(const void* d_stream, uint64_t len, const uint16_t freq[256], uint32_t lane_symbols, void* d_symbols,
                                 uint64_t n, void* hip_stream) {
-    return stage_split_decode(d_stream, len, freq, lane_symbols, d_symbols, n, hip_stream, true);
+    return stage_split_decode(d_stream, len, freq, lane_symbols, d_symbols, n, hip_stream, kFormatWide);
 }
 
 int alice_codec_wide_info(const uint8_t* data, uint64_t len, AliceSplitInfo* info) { return container_info(data, len, info, 3); }
 
 uint8_t* alice_codec_encode_wide(const FrameEncoder* encoder, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
                                  uint32_t frames, uint32_t lane_symbols, uint64_t* out_len) {
-    return container_encode(encoder, rgb, rgb_len, width, height, frames, lane_symbols, out_len, true);
+    return container_encode(encoder, rgb, rgb_len, width, height, frames, lane_symbols, out_len, kFormatWide);
 }
 
 uint8_t* alice_codec_decode_wide(const uint8_t* data, uint64_t len, uint64_t* out_len) { return container_decode(data, len, out_len, 3); }
@@ -4085,7 +4104,7 @@ int alice_codec_dev_encode_wide(const void* d_rgb, uint32_t width, uint32_t heig
                                 uint8_t wavelet_type, uint8_t quality, const uint8_t* qualities, uint32_t lane_symbols, void* d_out,
                                 uint64_t out_stride, uint64_t* sizes, void* hip_stream) {
     return container_dev_encode(d_rgb, width, height, frames, n_chunks, wavelet_type, quality, qualities, lane_symbols, d_out, out_stride,
-                                sizes, hip_stream, true);
+                                sizes, hip_stream, kFormatWide);
 }
 
 int alice_codec_dev_decode_wide(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks, void* d_rgb_out,
@@ -4097,7 +4116,7 @@ int alice_codec_dev_decode_wide(const void* d_alc, uint64_t alc_stride, const ui
 // call, the container as an argument (wide: version 3). ----
 
 static int container_predict_sizes(uint8_t wavelet_type, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
-                                   uint32_t frames, uint32_t lane_symbols, uint64_t lo[101], uint64_t hi[101], bool wide) {
+                                   uint32_t frames, uint32_t lane_symbols, uint64_t lo[101], uint64_t hi[101], SplitFormat fmt) {
     clear_error();
     if (!lo || !hi || (!rgb && rgb_len)) return fail(kNullArgument, "null argument");
     uint64_t n_pixels = 0;
@@ -4108,7 +4127,7 @@ static int container_predict_sizes(uint8_t wavelet_type, const uint8_t* rgb, uin
     EncodedChunk* none = nullptr;
     if (n_pixels) TRY(validate_encode_many(&enc, rgb, rgb_len, width, height, frames, 1, &none, &d));
     uint32_t L = 0;
-    TRY(check_split_args(wavelet_type, lane_symbols, &L, wide));
+    TRY(check_split_args(wavelet_type, lane_symbols, &L, fmt));
     if (n_pixels == 0) {   // an empty chunk is its header at every quality
         for (int q = 0; q < kQualities; ++q) lo[q] = hi[q] = kSplitHeaderBytes;
         return kOk;
@@ -4123,31 +4142,31 @@ static int container_predict_sizes(uint8_t wavelet_type, const uint8_t* rgb, uin
     HIP_TRY(hipMemcpyAsync(d_rgb.p, rgb, n_pixels * 3, hipMemcpyHostToDevice, st));
     const RgbLayout layout = packed_rgb(d_rgb.p, d);
     std::vector<RateChannel> rc;
-    TRY(predict_chunks(&layout, 1, d, wavelet_type, w, st, nullptr, rc, L, wide));
+    TRY(predict_chunks(&layout, 1, d, wavelet_type, w, st, nullptr, rc, L, is_wide(fmt)));
     split_rate_by_quality(rc.data(), lo, hi);
     return kOk;
 }
 
 int alice_codec_predict_split_sizes(uint8_t wavelet_type, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
                                     uint32_t frames, uint32_t lane_symbols, uint64_t lo[101], uint64_t hi[101]) {
-    return container_predict_sizes(wavelet_type, rgb, rgb_len, width, height, frames, lane_symbols, lo, hi, false);
+    return container_predict_sizes(wavelet_type, rgb, rgb_len, width, height, frames, lane_symbols, lo, hi, kFormatSplit);
 }
 
 int alice_codec_predict_wide_sizes(uint8_t wavelet_type, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
                                    uint32_t frames, uint32_t lane_symbols, uint64_t lo[101], uint64_t hi[101]) {
-    return container_predict_sizes(wavelet_type, rgb, rgb_len, width, height, frames, lane_symbols, lo, hi, true);
+    return container_predict_sizes(wavelet_type, rgb, rgb_len, width, height, frames, lane_symbols, lo, hi, kFormatWide);
 }
 
 // d_step_hist: [chunk][step - 1][channel][256] u32 on the device, or null
 static int container_dev_predict_sizes(const void* d_rgb, uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks,
                                        uint8_t wavelet_type, uint32_t lane_symbols, uint64_t* lo, uint64_t* hi, void* d_step_hist,
-                                       void* hip_stream, bool wide) {
+                                       void* hip_stream, SplitFormat fmt) {
     clear_error();
     if (!d_rgb || !lo || !hi) return fail(kNullArgument, "null argument");
     ChunkDims d{};
     TRY(chunk_dims(width, height, frames, &d, n_chunks));
     uint32_t L = 0;
-    TRY(check_split_args(wavelet_type, lane_symbols, &L, wide));
+    TRY(check_split_args(wavelet_type, lane_symbols, &L, fmt));
     TRY(ensure_device());
     hipStream_t st = (hipStream_t)hip_stream;
     ScopeStream scope(st);
@@ -4156,12 +4175,12 @@ static int container_dev_predict_sizes(const void* d_rgb, uint32_t width, uint32
     if (transform_tiles_eligible(d)) TRY(w.scratch.alloc(forward_scratch_bytes(d)));
     std::vector<RgbLayout> layouts;
     TRY(split_layouts(d_rgb, 0, 0, nullptr, d, n_chunks, layouts));
-    const uint32_t group = split_group(d, wide);
+    const uint32_t group = split_group(d, fmt);
     for (uint32_t first = 0; first < n_chunks; first += group) {
         const uint32_t B = std::min(group, n_chunks - first);
         std::vector<RateChannel> rc;
         uint32_t* sh = d_step_hist ? (uint32_t*)d_step_hist + (size_t)first * 64 * 3 * 256 : nullptr;
-        TRY(predict_chunks(layouts.data() + first, B, d, wavelet_type, w, st, sh, rc, L, wide));
+        TRY(predict_chunks(layouts.data() + first, B, d, wavelet_type, w, st, sh, rc, L, is_wide(fmt)));
         for (uint32_t i = 0; i < B; ++i)
             split_rate_by_quality(rc.data() + (size_t)i * 192, lo + (size_t)(first + i) * kQualities, hi + (size_t)(first + i) * kQualities);
     }
@@ -4170,18 +4189,18 @@ static int container_dev_predict_sizes(const void* d_rgb, uint32_t width, uint32
 
 int alice_codec_dev_predict_split_sizes(const void* d_rgb, uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks,
                                         uint8_t wavelet_type, uint32_t lane_symbols, uint64_t* lo, uint64_t* hi, void* hip_stream) {
-    return container_dev_predict_sizes(d_rgb, width, height, frames, n_chunks, wavelet_type, lane_symbols, lo, hi, nullptr, hip_stream, false);
+    return container_dev_predict_sizes(d_rgb, width, height, frames, n_chunks, wavelet_type, lane_symbols, lo, hi, nullptr, hip_stream, kFormatSplit);
 }
 
 int alice_codec_dev_predict_wide_sizes(const void* d_rgb, uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks,
                                        uint8_t wavelet_type, uint32_t lane_symbols, uint64_t* lo, uint64_t* hi, void* d_step_hist,
                                        void* hip_stream) {
-    return container_dev_predict_sizes(d_rgb, width, height, frames, n_chunks, wavelet_type, lane_symbols, lo, hi, d_step_hist, hip_stream, true);
+    return container_dev_predict_sizes(d_rgb, width, height, frames, n_chunks, wavelet_type, lane_symbols, lo, hi, d_step_hist, hip_stream, kFormatWide);
 }
 
 static uint8_t* container_encode_to_size(uint8_t wavelet_type, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
                                          uint32_t frames, uint32_t lane_symbols, uint64_t max_bytes, uint8_t min_q, uint8_t max_q,
-                                         uint8_t* chosen_q, uint8_t* fits, uint64_t* out_len, bool wide) {
+                                         uint8_t* chosen_q, uint8_t* fits, uint64_t* out_len, SplitFormat fmt) {
     clear_error();
     if (!chosen_q || !fits || !out_len || (!rgb && rgb_len)) { fail(kNullArgument, "null argument"); return nullptr; }
     auto run = [&](uint8_t** out) -> int {
@@ -4193,7 +4212,7 @@ static uint8_t* container_encode_to_size(uint8_t wavelet_type, const uint8_t* rg
         EncodedChunk* none = nullptr;
         if (n_pixels) TRY(validate_encode_many(&enc, rgb, rgb_len, width, height, frames, 1, &none, &d));
         uint32_t L = 0;
-        TRY(check_split_args(wavelet_type, lane_symbols, &L, wide));
+        TRY(check_split_args(wavelet_type, lane_symbols, &L, fmt));
         TRY(check_quality_range(min_q, max_q));
         if (n_pixels == 0) {
             uint64_t lo[kQualities], hi[kQualities];
@@ -4203,7 +4222,7 @@ static uint8_t* container_encode_to_size(uint8_t wavelet_type, const uint8_t* rg
                                      &tl_split_trials[0]));
             *out = host_result_alloc(kSplitHeaderBytes);
             if (!*out) return fail(kOutOfMemory, "out of host memory");
-            write_empty_split(*out, wavelet_type, width, height, frames, L, quality_to_step(*chosen_q), wide ? 3 : 2);
+            write_empty_split(*out, wavelet_type, width, height, frames, L, quality_to_step(*chosen_q), format_version(fmt));
             *out_len = kSplitHeaderBytes;
             return kOk;
         }
@@ -4213,14 +4232,14 @@ static uint8_t* container_encode_to_size(uint8_t wavelet_type, const uint8_t* rg
         TRY(d_rgb.alloc(n_pixels * 3));
         HIP_TRY(hipMemcpyAsync(d_rgb.p, rgb, n_pixels * 3, hipMemcpyHostToDevice, st));
         const RgbLayout layout = packed_rgb(d_rgb.p, d);
-        TRY(split_choose_chunks(&layout, 1, d, wavelet_type, L, &max_bytes, min_q, max_q, chosen_q, fits, st, wide));
+        TRY(split_choose_chunks(&layout, 1, d, wavelet_type, L, &max_bytes, min_q, max_q, chosen_q, fits, st, fmt));
         std::vector<uint64_t> sizes;
         TRY(split_encode_chunks(&layout, 1, d, wavelet_type, chosen_q, L, st, sizes,
                                 [&](const std::vector<uint64_t>& sz, std::vector<uint8_t*>& outs) -> int {
                                     TRY(d_out.alloc(sz[0]));
                                     outs[0] = d_out.as<uint8_t>();
                                     return kOk;
-                                }, wide));
+                                }, fmt));
         *out = host_result_alloc(sizes[0]);
         if (!*out) return fail(kOutOfMemory, "out of host memory");
         const int rc = copy_to_host(*out, d_out.p, sizes[0], st);
@@ -4236,20 +4255,20 @@ uint8_t* alice_codec_encode_split_to_size(uint8_t wavelet_type, const uint8_t* r
                                           uint32_t frames, uint32_t lane_symbols, uint64_t max_bytes, uint8_t min_q, uint8_t max_q,
                                           uint8_t* chosen_q, uint8_t* fits, uint64_t* out_len) {
     return container_encode_to_size(wavelet_type, rgb, rgb_len, width, height, frames, lane_symbols, max_bytes, min_q, max_q, chosen_q,
-                                    fits, out_len, false);
+                                    fits, out_len, kFormatSplit);
 }
 
 uint8_t* alice_codec_encode_wide_to_size(uint8_t wavelet_type, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
                                          uint32_t frames, uint32_t lane_symbols, uint64_t max_bytes, uint8_t min_q, uint8_t max_q,
                                          uint8_t* chosen_q, uint8_t* fits, uint64_t* out_len) {
     return container_encode_to_size(wavelet_type, rgb, rgb_len, width, height, frames, lane_symbols, max_bytes, min_q, max_q, chosen_q,
-                                    fits, out_len, true);
+                                    fits, out_len, kFormatWide);
 }
 
 static int container_dev_encode_regions(const void* d_frames, uint32_t frame_width, uint32_t frame_height, const uint32_t* origins,
                                         uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks, uint8_t wavelet_type,
                                         uint8_t quality, const uint8_t* qualities, uint32_t lane_symbols, void* d_out,
-                                        uint64_t out_stride, uint64_t* sizes, void* hip_stream, bool wide) {
+                                        uint64_t out_stride, uint64_t* sizes, void* hip_stream, SplitFormat fmt) {
     clear_error();
     if (!d_frames || !origins || !d_out || !sizes) return fail(kNullArgument, "null argument");
     ChunkDims d{};
@@ -4257,13 +4276,13 @@ static int container_dev_encode_regions(const void* d_frames, uint32_t frame_wid
     std::vector<RgbLayout> layouts;
     TRY(split_layouts(d_frames, frame_width, frame_height, origins, d, n_chunks, layouts));
     uint32_t L = 0;
-    TRY(check_split_args(wavelet_type, lane_symbols, &L, wide));
+    TRY(check_split_args(wavelet_type, lane_symbols, &L, fmt));
     TRY(ensure_device());
     hipStream_t st = (hipStream_t)hip_stream;
     ScopeStream scope(st);
     std::vector<uint8_t> q(n_chunks);
     for (uint32_t i = 0; i < n_chunks; ++i) q[i] = qualities ? qualities[i] : quality;
-    return split_encode_layouts(layouts.data(), n_chunks, d, wavelet_type, q.data(), L, d_out, out_stride, sizes, st, wide);
+    return split_encode_layouts(layouts.data(), n_chunks, d, wavelet_type, q.data(), L, d_out, out_stride, sizes, st, fmt);
 }
 
 int alice_codec_dev_encode_split_regions(const void* d_frames, uint32_t frame_width, uint32_t frame_height, const uint32_t* origins,
@@ -4271,7 +4290,7 @@ int alice_codec_dev_encode_split_regions(const void* d_frames, uint32_t frame_wi
                                          uint8_t quality, const uint8_t* qualities, uint32_t lane_symbols, void* d_out,
                                          uint64_t out_stride, uint64_t* sizes, void* hip_stream) {
     return container_dev_encode_regions(d_frames, frame_width, frame_height, origins, width, height, frames, n_chunks, wavelet_type, quality,
-                                        qualities, lane_symbols, d_out, out_stride, sizes, hip_stream, false);
+                                        qualities, lane_symbols, d_out, out_stride, sizes, hip_stream, kFormatSplit);
 }
 
 int alice_codec_dev_encode_wide_regions(const void* d_frames, uint32_t frame_width, uint32_t frame_height, const uint32_t* origins,
@@ -4279,7 +4298,7 @@ int alice_codec_dev_encode_wide_regions(const void* d_frames, uint32_t frame_wid
                                         uint8_t quality, const uint8_t* qualities, uint32_t lane_symbols, void* d_out,
                                         uint64_t out_stride, uint64_t* sizes, void* hip_stream) {
     return container_dev_encode_regions(d_frames, frame_width, frame_height, origins, width, height, frames, n_chunks, wavelet_type, quality,
-                                        qualities, lane_symbols, d_out, out_stride, sizes, hip_stream, true);
+                                        qualities, lane_symbols, d_out, out_stride, sizes, hip_stream, kFormatWide);
 }
 
 static int container_dev_decode_regions(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks,
@@ -4317,7 +4336,7 @@ int alice_codec_dev_decode_wide_regions(const void* d_alc, uint64_t alc_stride, 
 static int container_dev_encode_to_budget(const void* d_frames, uint32_t frame_width, uint32_t frame_height, const uint32_t* origins,
                                           uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks, uint8_t wavelet_type,
                                           uint32_t lane_symbols, const uint64_t* budgets, uint8_t min_q, uint8_t max_q, uint8_t* chosen,
-                                          uint8_t* fits, void* d_out, uint64_t out_stride, uint64_t* sizes, void* hip_stream, bool wide) {
+                                          uint8_t* fits, void* d_out, uint64_t out_stride, uint64_t* sizes, void* hip_stream, SplitFormat fmt) {
     clear_error();
     if (!d_frames || !budgets || !chosen || !fits || !d_out || !sizes) return fail(kNullArgument, "null argument");
     ChunkDims d{};
@@ -4325,7 +4344,7 @@ static int container_dev_encode_to_budget(const void* d_frames, uint32_t frame_w
     std::vector<RgbLayout> layouts;
     TRY(split_layouts(d_frames, frame_width, frame_height, origins, d, n_chunks, layouts));
     uint32_t L = 0;
-    TRY(check_split_args(wavelet_type, lane_symbols, &L, wide));
+    TRY(check_split_args(wavelet_type, lane_symbols, &L, fmt));
     TRY(check_quality_range(min_q, max_q));
     TRY(ensure_device());
     hipStream_t st = (hipStream_t)hip_stream;
@@ -4333,8 +4352,8 @@ static int container_dev_encode_to_budget(const void* d_frames, uint32_t frame_w
     // the choices reach the caller only with the bytes: a failed call leaves chosen / fits / sizes as they were
     std::vector<uint8_t> q(n_chunks), ok(n_chunks);
     std::vector<uint64_t> sz(n_chunks);
-    TRY(split_choose_chunks(layouts.data(), n_chunks, d, wavelet_type, L, budgets, min_q, max_q, q.data(), ok.data(), st, wide));
-    TRY(split_encode_layouts(layouts.data(), n_chunks, d, wavelet_type, q.data(), L, d_out, out_stride, sz.data(), st, wide));
+    TRY(split_choose_chunks(layouts.data(), n_chunks, d, wavelet_type, L, budgets, min_q, max_q, q.data(), ok.data(), st, fmt));
+    TRY(split_encode_layouts(layouts.data(), n_chunks, d, wavelet_type, q.data(), L, d_out, out_stride, sz.data(), st, fmt));
     for (uint32_t i = 0; i < n_chunks; ++i) { chosen[i] = q[i]; fits[i] = ok[i]; sizes[i] = sz[i]; }
     return kOk;
 }
@@ -4344,7 +4363,7 @@ int alice_codec_dev_encode_split_to_budget(const void* d_frames, uint32_t frame_
                                            uint32_t lane_symbols, const uint64_t* budgets, uint8_t min_q, uint8_t max_q, uint8_t* chosen,
                                            uint8_t* fits, void* d_out, uint64_t out_stride, uint64_t* sizes, void* hip_stream) {
     return container_dev_encode_to_budget(d_frames, frame_width, frame_height, origins, width, height, frames, n_chunks, wavelet_type,
-                                          lane_symbols, budgets, min_q, max_q, chosen, fits, d_out, out_stride, sizes, hip_stream, false);
+                                          lane_symbols, budgets, min_q, max_q, chosen, fits, d_out, out_stride, sizes, hip_stream, kFormatSplit);
 }
 
 int alice_codec_dev_encode_wide_to_budget(const void* d_frames, uint32_t frame_width, uint32_t frame_height, const uint32_t* origins,
@@ -4352,7 +4371,45 @@ int alice_codec_dev_encode_wide_to_budget(const void* d_frames, uint32_t frame_w
                                           uint32_t lane_symbols, const uint64_t* budgets, uint8_t min_q, uint8_t max_q, uint8_t* chosen,
                                           uint8_t* fits, void* d_out, uint64_t out_stride, uint64_t* sizes, void* hip_stream) {
     return container_dev_encode_to_budget(d_frames, frame_width, frame_height, origins, width, height, frames, n_chunks, wavelet_type,
-                                          lane_symbols, budgets, min_q, max_q, chosen, fits, d_out, out_stride, sizes, hip_stream, true);
+                                          lane_symbols, budgets, min_q, max_q, chosen, fits, d_out, out_stride, sizes, hip_stream, kFormatWide);
+}
+
+// ---- version 4: the reversible container.  The wide paths with the format set to reversible: the
+// version byte and the inverse launcher are all that differ. ----
+
+uint8_t* alice_codec_encode_reversible(const FrameEncoder* encoder, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
+                                       uint32_t frames, uint32_t lane_symbols, uint64_t* out_len) {
+    return container_encode(encoder, rgb, rgb_len, width, height, frames, lane_symbols, out_len, kFormatReversible);
+}
+
+uint8_t* alice_codec_decode_reversible(const uint8_t* data, uint64_t len, uint64_t* out_len) { return container_decode(data, len, out_len, 4); }
+
+int alice_codec_reversible_info(const uint8_t* data, uint64_t len, AliceSplitInfo* info) { return container_info(data, len, info, 4); }
+
+int alice_codec_dev_encode_reversible(const void* d_rgb, uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks,
+                                      uint8_t wavelet_type, uint8_t quality, const uint8_t* qualities, uint32_t lane_symbols, void* d_out,
+                                      uint64_t out_stride, uint64_t* sizes, void* hip_stream) {
+    return container_dev_encode(d_rgb, width, height, frames, n_chunks, wavelet_type, quality, qualities, lane_symbols, d_out, out_stride,
+                                sizes, hip_stream, kFormatReversible);
+}
+
+int alice_codec_dev_decode_reversible(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks, void* d_rgb_out,
+                                      void* hip_stream) {
+    return container_dev_decode(d_alc, alc_stride, sizes, n_chunks, d_rgb_out, hip_stream, 4);
+}
+
+int alice_codec_dev_encode_reversible_regions(const void* d_frames, uint32_t frame_width, uint32_t frame_height, const uint32_t* origins,
+                                              uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks, uint8_t wavelet_type,
+                                              uint8_t quality, const uint8_t* qualities, uint32_t lane_symbols, void* d_out,
+                                              uint64_t out_stride, uint64_t* sizes, void* hip_stream) {
+    return container_dev_encode_regions(d_frames, frame_width, frame_height, origins, width, height, frames, n_chunks, wavelet_type, quality,
+                                        qualities, lane_symbols, d_out, out_stride, sizes, hip_stream, kFormatReversible);
+}
+
+int alice_codec_dev_decode_reversible_regions(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks,
+                                              void* d_frames_out, uint32_t frame_width, uint32_t frame_height, const uint32_t* origins,
+                                              void* hip_stream) {
+    return container_dev_decode_regions(d_alc, alc_stride, sizes, n_chunks, d_frames_out, frame_width, frame_height, origins, hip_stream, 4);
 }
 
 uint32_t alice_codec_test_last_split_trials(uint32_t* per_chunk, uint32_t cap) {

@@ -18,7 +18,9 @@ __device__ __forceinline__ int g_delta(int a, int b, int c) {
 }
 
 // One lifting step over every line.  work item = (line, pair); lines are (a, b) pairs.
-template <bool PREDICT>
+// MIRROR: the step of the mirrored inverse (.alc v4): the target loses the delta of `coeff` (the
+// forward's own coefficient) instead of gaining the delta of the coefficient it is given.
+template <bool PREDICT, bool MIRROR = false>
 __global__ __launch_bounds__(256) void axis_lift_kernel(int32_t* __restrict__ data, unsigned long long n,
                                                         unsigned long long stride_k, unsigned long long n_a,
                                                         unsigned long long stride_a, unsigned long long n_b,
@@ -35,12 +37,14 @@ __global__ __launch_bounds__(256) void axis_lift_kernel(int32_t* __restrict__ da
             const int el = s[(2 * i) * stride_k];
             const int er = (2 * i + 2 < n) ? s[(2 * i + 2) * stride_k] : el;
             int32_t* o = s + (2 * i + 1) * stride_k;
-            *o = (int)((unsigned)*o + (unsigned)g_delta(el, er, coeff));
+            const unsigned dl = (unsigned)g_delta(el, er, coeff);
+            *o = MIRROR ? (int)((unsigned)*o - dl) : (int)((unsigned)*o + dl);
         } else {        // src/wavelet.rs:205-216
             const int orr = s[(2 * i + 1) * stride_k];
             const int ol = (i > 0) ? s[(2 * i - 1) * stride_k] : s[stride_k];
             int32_t* e = s + (2 * i) * stride_k;
-            *e = (int)((unsigned)*e + (unsigned)g_delta(ol, orr, coeff));
+            const unsigned dl = (unsigned)g_delta(ol, orr, coeff);
+            *e = MIRROR ? (int)((unsigned)*e - dl) : (int)((unsigned)*e + dl);
         }
     }
 }
@@ -105,7 +109,7 @@ static unsigned grid_for(unsigned long long items) {
 
 void launch_wavelet_axis(int32_t* d_data, int32_t* d_tmp, uint64_t n, uint64_t stride_k, uint64_t n_a,
                          uint64_t stride_a, uint64_t n_b, uint64_t stride_b, int wavelet, bool inverse,
-                         hipStream_t st) {
+                         hipStream_t st, bool mirror) {
     if (n < 2 || n_a == 0 || n_b == 0) return;  // src/wavelet.rs:135,159
     const LiftSteps ls = lift_steps(wavelet);
     const int line_fast = stride_k != 1 ? 1 : 0;
@@ -125,6 +129,11 @@ void launch_wavelet_axis(int32_t* d_data, int32_t* d_tmp, uint64_t n, uint64_t s
         hipLaunchKernelGGL(axis_shuffle_kernel<true>, dim3(gs), block, 0, st, d_data, d_tmp, AX_ARGS, line_fast);
         hipLaunchKernelGGL(axis_copy_kernel, dim3(gs), block, 0, st, d_tmp, d_data, AX_ARGS, line_fast);
         for (int k = ls.n - 1; k >= 0; --k) {
+            if (mirror) {   // the same grid, the forward's coefficient, a subtracting step
+                if ((k & 1) == 0) hipLaunchKernelGGL((axis_lift_kernel<true, true>), dim3(gl), block, 0, st, d_data, AX_ARGS, ls.coeff[k], line_fast);
+                else hipLaunchKernelGGL((axis_lift_kernel<false, true>), dim3(gl), block, 0, st, d_data, AX_ARGS, ls.coeff[k], line_fast);
+                continue;
+            }
             if ((k & 1) == 0) hipLaunchKernelGGL(axis_lift_kernel<true>, dim3(gl), block, 0, st, d_data, AX_ARGS, -ls.coeff[k], line_fast);
             else hipLaunchKernelGGL(axis_lift_kernel<false>, dim3(gl), block, 0, st, d_data, AX_ARGS, -ls.coeff[k], line_fast);
         }

@@ -171,6 +171,10 @@ bool launch_forward_transform_wide(const RgbLayout& rgb, const ChunkDims& d, int
                                    void* d_scratch, uint16_t* d_sym, uint32_t* d_hist, hipStream_t st);
 bool launch_inverse_transform_wide(const uint16_t* d_sym, const ChunkDims& d, int wavelet, const int32_t step[3],
                                    bool exact, bool mid16, bool lds16, void* d_scratch, const RgbLayout& rgb, hipStream_t st);
+// The reversible twin (.alc v4): the wide launcher with the mirrored instances of both roles -- every
+// lifting step subtracts the forward's own delta.  Same symbols, bands, scratch and instance flags.
+bool launch_inverse_transform_reversible(const uint16_t* d_sym, const ChunkDims& d, int wavelet, const int32_t step[3],
+                                         bool exact, bool mid16, bool lds16, void* d_scratch, const RgbLayout& rgb, hipStream_t st);
 
 // ---- transform.hip, stage level: Wavelet2D / Wavelet3D of caller-shaped i32 data on the tile kernels' exact instances ----
 // eligible: even width and height >= 6, even depth (or depth 1); otherwise the caller uses launch_wavelet_axis.
@@ -187,7 +191,7 @@ void launch_stage_wavelet(int32_t* d_data, int32_t* d_tmp, uint64_t w, uint64_t 
 void set_generic_grid_cap(uint32_t max_blocks);
 void launch_wavelet_axis(int32_t* d_data, int32_t* d_tmp, uint64_t n, uint64_t stride_k, uint64_t n_a,
                          uint64_t stride_a, uint64_t n_b, uint64_t stride_b, int wavelet, bool inverse,
-                         hipStream_t st);
+                         hipStream_t st, bool mirror = false);   // mirror (inverse only): the mirrored inverse of .alc v4
 void launch_rgb_to_ycocg(const uint8_t* d_rgb, uint64_t n_pixels, int16_t* y, int16_t* co, int16_t* cg, hipStream_t st);
 void launch_ycocg_to_rgb(const int16_t* y, const int16_t* co, const int16_t* cg, uint64_t n_pixels, uint8_t* d_rgb, hipStream_t st);
 // the same for the w x h x f pixels of a chunk at any layout (planes packed [f][h][w]; a packed layout takes the calls above)

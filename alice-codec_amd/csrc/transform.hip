@@ -55,6 +55,13 @@ __device__ __forceinline__ int lift_delta(int a, int b, int c) {
     }
 }
 __device__ __forceinline__ int wadd(int a, int b) { return (int)((unsigned)a + (unsigned)b); }
+__device__ __forceinline__ int wsub(int a, int b) { return (int)((unsigned)a - (unsigned)b); }
+// How an inverse lifting step undoes its forward step.  The reference re-runs the step with the negated coefficient
+// (target += delta(-c), src/wavelet.rs:167-174); MIRROR (.alc v4) subtracts the forward's own delta
+// (target -= delta(+c)).  The two differ by one wherever (a + b) * c = 4096 (mod 8192); only the mirror gives the
+// forward's input back.  Same cost: one multiply-add, one shift, one add or subtract.
+template <bool MIRROR>
+__device__ __forceinline__ int lift_undo(int x, int delta) { return MIRROR ? wsub(x, delta) : wadd(x, delta); }
 
 struct Coeffs { int c[4]; };
 
@@ -91,22 +98,23 @@ __device__ __forceinline__ int reflect_idx(int i, int n) {
 // In-register 1-D lifting of N consecutive samples (v[0] has an even global index).  No boundary logic: the
 // tile kernels load through the symmetric extension (reflect_idx), and the two array ends simply reuse their
 // inner neighbour (that garbage stays inside the halo, which is never stored).  INVERSE applies the steps
-// reversed with -coeff (src/wavelet.rs:167-174).
+// reversed with -coeff (src/wavelet.rs:167-174); INVERSE with MIRROR applies them reversed with +coeff and subtracts.
 // ------------------------------------------------------------------------------------------------
-template <int N, int NS, bool EXACT, bool INVERSE>
+template <int N, int NS, bool EXACT, bool INVERSE, bool MIRROR = false>
 __device__ __forceinline__ void lift_regs(int (&v)[N], const Coeffs& cf) {
+    static_assert(INVERSE || !MIRROR, "MIRROR is a mode of the inverse");
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
         const int k_step = INVERSE ? (NS - 1 - s) : s;
-        const int c = INVERSE ? -cf.c[k_step] : cf.c[k_step];
+        const int c = (INVERSE && !MIRROR) ? -cf.c[k_step] : cf.c[k_step];
         if ((k_step & 1) == 0) {  // predict: odd += d(even_left, even_right), src/wavelet.rs:184-196
 #pragma unroll
-            for (int k = 1; k < N; k += 2) v[k] = wadd(v[k], lift_delta<EXACT>(v[k - 1], (k + 1 < N) ? v[k + 1] : v[k - 1], c));
+            for (int k = 1; k < N; k += 2) v[k] = lift_undo<MIRROR>(v[k], lift_delta<EXACT>(v[k - 1], (k + 1 < N) ? v[k + 1] : v[k - 1], c));
         } else {                  // update: even += d(odd_left, odd_right), src/wavelet.rs:205-216
 #pragma unroll
             for (int k = 0; k < N; k += 2) {
                 const int rgt = (k + 1 < N) ? v[k + 1] : v[k - 1];
-                v[k] = wadd(v[k], lift_delta<EXACT>((k >= 1) ? v[k - 1] : rgt, rgt, c));
+                v[k] = lift_undo<MIRROR>(v[k], lift_delta<EXACT>((k >= 1) ? v[k - 1] : rgt, rgt, c));
             }
         }
     }
@@ -290,11 +298,11 @@ __device__ __forceinline__ void fwd_xy_tile(const FwdXy& a, int bx, int by, int 
 // ------------------------------------------------------------------------------------------------
 struct I4 { int v[4]; };
 
-template <bool EXACT>
+template <bool EXACT, bool MIRROR = false>
 __device__ __forceinline__ I4 lift4(const I4& base, const I4& a, const I4& b, int c) {
     I4 r;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) r.v[i] = wadd(base.v[i], lift_delta<EXACT>(a.v[i], b.v[i], c));
+    for (int i = 0; i < 4; ++i) r.v[i] = lift_undo<MIRROR>(base.v[i], lift_delta<EXACT>(a.v[i], b.v[i], c));
     return r;
 }
 
@@ -716,7 +724,8 @@ __device__ __forceinline__ void store4<int16_t>(int16_t* p, const I4& x) {
 // frame 2(k-2)+1.  from_symbols + dequantize (src/quant.rs:104-110,581-587) is a 256-entry table in LDS:
 // one byte extract and one LDS read per sample instead of seven VALU operations.
 // WIDE (.alc v3): the symbols are u16 and are dequantised by arithmetic (z -> q -> q * step, wrapping), since z reaches 4350.
-template <int NS, bool EXACT, typename MidT, int PROBE = 0, bool WIDE = false>
+// MIRROR (.alc v4): c0 .. c3 are the forward's coefficients and every step subtracts (lift_undo).
+template <int NS, bool EXACT, typename MidT, int PROBE = 0, bool WIDE = false, bool MIRROR = false>
 struct InvT {
     using Sym4 = std::conditional_t<WIDE, uint2, uint32_t>;   // the symbols of 4 pixels
     const char* src;      // channel base of the symbol volume
@@ -725,7 +734,7 @@ struct InvT {
     size_t plane_d;       // pixels per frame of the band slot
     uint32_t off8;
     int half, nf;
-    int c0, c1, c2, c3;   // already negated
+    int c0, c1, c2, c3;   // already negated (MIRROR: as in the forward)
     const int* lut;
     int step;             // WIDE only
     I4 o2p, e1p, o1pp, e0pp;
@@ -764,31 +773,31 @@ struct InvT {
     __device__ __forceinline__ void tick(int k, Sym4 lo, Sym4 hi) {
         const I4 hv = dq(hi), lv = dq(lo);
         if (NS == 4) {
-            const I4 e1 = lift4<EXACT>(lv, FIRST ? hv : o2p, hv, c3);
+            const I4 e1 = lift4<EXACT, MIRROR>(lv, FIRST ? hv : o2p, hv, c3);
             if (!FIRST) {
-                const I4 o1 = lift4<EXACT>(o2p, e1p, e1, c2);
-                const I4 e0 = lift4<EXACT>(e1p, SECOND ? o1 : o1pp, o1, c1);
+                const I4 o1 = lift4<EXACT, MIRROR>(o2p, e1p, e1, c2);
+                const I4 e0 = lift4<EXACT, MIRROR>(e1p, SECOND ? o1 : o1pp, o1, c1);
                 put(2 * (k - 1), e0);
-                if (!SECOND) put(2 * (k - 2) + 1, lift4<EXACT>(o1pp, e0pp, e0, c0));
+                if (!SECOND) put(2 * (k - 2) + 1, lift4<EXACT, MIRROR>(o1pp, e0pp, e0, c0));
                 o1pp = o1; e0pp = e0;
             }
             o2p = hv; e1p = e1;
         } else {
-            const I4 e0 = lift4<EXACT>(lv, FIRST ? hv : o2p, hv, c1);
+            const I4 e0 = lift4<EXACT, MIRROR>(lv, FIRST ? hv : o2p, hv, c1);
             put(2 * k, e0);
-            if (!FIRST) put(2 * (k - 1) + 1, lift4<EXACT>(o2p, e1p, e0, c0));
+            if (!FIRST) put(2 * (k - 1) + 1, lift4<EXACT, MIRROR>(o2p, e1p, e0, c0));
             o2p = hv; e1p = e0;
         }
     }
     __device__ __forceinline__ void flush() {
         if (NS == 4) {
-            const I4 o1 = lift4<EXACT>(o2p, e1p, e1p, c2);
-            const I4 e0 = lift4<EXACT>(e1p, half == 1 ? o1 : o1pp, o1, c1);
+            const I4 o1 = lift4<EXACT, MIRROR>(o2p, e1p, e1p, c2);
+            const I4 e0 = lift4<EXACT, MIRROR>(e1p, half == 1 ? o1 : o1pp, o1, c1);
             put(2 * (half - 1), e0);
-            if (half >= 2) put(2 * (half - 2) + 1, lift4<EXACT>(o1pp, e0pp, e0, c0));
-            put(2 * (half - 1) + 1, lift4<EXACT>(o1, e0, e0, c0));
+            if (half >= 2) put(2 * (half - 2) + 1, lift4<EXACT, MIRROR>(o1pp, e0pp, e0, c0));
+            put(2 * (half - 1) + 1, lift4<EXACT, MIRROR>(o1, e0, e0, c0));
         } else {
-            put(2 * (half - 1) + 1, lift4<EXACT>(o2p, e1p, e1p, c0));
+            put(2 * (half - 1) + 1, lift4<EXACT, MIRROR>(o2p, e1p, e1p, c0));
         }
     }
     __device__ __forceinline__ void run() {
@@ -863,21 +872,22 @@ __global__ __launch_bounds__(256) void inv_t_kernel(InvTm a) {
     f.run();
 }
 
-// The wide instance (.alc v3): a.sym is the u16 symbol volume; no table.
-template <int NS, bool EXACT, typename MidT>
+// The wide instance (.alc v3): a.sym is the u16 symbol volume; no table.  MIRROR: the reversible container's (.alc v4).
+template <int NS, bool EXACT, typename MidT, bool MIRROR = false>
 __global__ __launch_bounds__(256) void inv_t_wide_kernel(InvTm a) {
     const int tid = threadIdx.x;
     const int ch = (int)(blockIdx.x / a.b.units_per_ch);
     const uint32_t blk = blockIdx.x % a.b.units_per_ch;
     const uint32_t idx = (blk * 256u + (uint32_t)tid) * 4u;
     if (idx >= a.b.band_px) return;
-    InvT<NS, EXACT, MidT, 0, true> f;
+    InvT<NS, EXACT, MidT, 0, true, MIRROR> f;
     f.src = (const char*)((const uint16_t*)a.sym + (size_t)ch * a.b.pf * a.b.plane);
     f.dst = (MidT*)a.mid + (size_t)ch * a.b.pf * a.b.band_px + idx;
     f.plane_s = a.b.plane; f.plane_d = a.b.band_px;
     f.off8 = band_plane_index(a.b, idx);
     f.half = (int)a.b.pf / 2; f.nf = (int)a.nf;
-    f.c0 = -a.cf.c[0]; f.c1 = -a.cf.c[1]; f.c2 = -a.cf.c[2]; f.c3 = -a.cf.c[3];
+    if (MIRROR) { f.c0 = a.cf.c[0]; f.c1 = a.cf.c[1]; f.c2 = a.cf.c[2]; f.c3 = a.cf.c[3]; }
+    else { f.c0 = -a.cf.c[0]; f.c1 = -a.cf.c[1]; f.c2 = -a.cf.c[2]; f.c3 = -a.cf.c[3]; }
     f.lut = nullptr; f.step = a.step[ch];
     f.run();
 }
@@ -910,7 +920,7 @@ struct InvXy {
 // rows that only feed never-stored outputs of overhanging tiles are clamped into the slot.
 // (Scalar row pointers plus a 32-bit lane offset here, as the forward tile's stores have them, measured no gain -- 435 vs
 // 431 us -- and giving every channel 128 threads so that the channel is wave-uniform too was 6 % slower: DESIGN.md 4.0.)
-template <int NS, int ER, bool EDGE, bool EXACT, typename MidT, int PROBE = 0>
+template <int NS, int ER, bool EDGE, bool EXACT, typename MidT, int PROBE = 0, bool MIRROR = false>
 __device__ __forceinline__ void inv_load_lift_column(const InvXy& a, int ch, int par, int px, int t, int gy_s, int (&v)[ER]) {
     const ChunkDims& d = a.d;
     const int pw = d.pw, ph = d.ph, hw = pw / 2;
@@ -932,7 +942,7 @@ __device__ __forceinline__ void inv_load_lift_column(const InvXy& a, int ch, int
 #pragma unroll
         for (int m = 0; m < ER / 2; ++m) { v[2 * m] = (int)lo[(size_t)m * pw]; v[2 * m + 1] = (int)hi[(size_t)m * pw]; }
     }
-    lift_regs<ER, NS, EXACT, true>(v, a.cf);
+    lift_regs<ER, NS, EXACT, true, MIRROR>(v, a.cf);
 }
 
 // `as i16` (src/pipeline.rs:608), wrapping i16 colour inverse (src/color.rs:266-273), 8 pixels -> 24 bytes, dword stores
@@ -974,7 +984,7 @@ __device__ __forceinline__ void store_rgb8(const InvXy& a, bool edge, const int*
 // Recompute variant with the packed tile: the host proved that every value after the inverse column lifting fits i16
 // (InverseBounds::lds16): two tile rows share a dword, which halves the tile (26 KB: the 32-wave limit, not LDS, then
 // bounds the workgroups per CU).  A stage-B thread lifts its 8 pixels plus NS halo samples on each side.
-template <int NS, bool EDGE, bool EXACT, typename MidT>
+template <int NS, bool EDGE, bool EXACT, typename MidT, bool MIRROR = false>
 __device__ __forceinline__ void inv_xy_tile_packed(const InvXy& a, int bx, int by, int t, int* lds) {
     constexpr int H = NS;
     constexpr int ER = I_TH + 2 * H;        // rows incl. halo
@@ -993,7 +1003,7 @@ __device__ __forceinline__ void inv_xy_tile_packed(const InvXy& a, int bx, int b
         const int par = xq / ECh, j = xq % ECh;
         const int px = EDGE ? reflect_idx(2 * (gpx0 + j) + par, pw) : 2 * (gpx0 + j) + par;   // parity is preserved
         int v[ER];
-        inv_load_lift_column<NS, ER, EDGE, EXACT, MidT>(a, ch, par, px, t, gy0 - H, v);
+        inv_load_lift_column<NS, ER, EDGE, EXACT, MidT, 0, MIRROR>(a, ch, par, px, t, gy0 - H, v);
         int* L = lds + (ch * LR) * I_LW + par * I_HO + j;
 #pragma unroll
         for (int m = 0; m < ER / 2; ++m) L[m * I_LW] = (v[2 * m] & 0xFFFF) | (v[2 * m + 1] << 16);
@@ -1027,9 +1037,9 @@ __device__ __forceinline__ void inv_xy_tile_packed(const InvXy& a, int bx, int b
                 }
             };
             fetch(0, y); fetch(1, co); fetch(2, cg);
-            lift_regs<NL, NS, EXACT, true>(y, a.cf);
-            lift_regs<NL, NS, EXACT, true>(co, a.cf);
-            lift_regs<NL, NS, EXACT, true>(cg, a.cf);
+            lift_regs<NL, NS, EXACT, true, MIRROR>(y, a.cf);
+            lift_regs<NL, NS, EXACT, true, MIRROR>(co, a.cf);
+            lift_regs<NL, NS, EXACT, true, MIRROR>(cg, a.cf);
             store_rgb8(a, EDGE, y + H, co + H, cg + H, t, gy, gxs);
         }
     }
@@ -1048,25 +1058,26 @@ constexpr int X_TH = 32, X_THREADS = X_TH * 16;   // stage B: X_TH rows x 16 lan
 constexpr int X_HO = 56, X_LW = 112;    // tile row: even samples at columns 2 .. 53 (+2 never-read columns each side), odd at 56 + ...
 
 // one inverse/forward lifting pass over the 8 samples of a lane (v[0] even), neighbours by DPP within the 16-lane row
-template <int NS, bool EXACT, bool INVERSE>
+template <int NS, bool EXACT, bool INVERSE, bool MIRROR = false>
 __device__ __forceinline__ void lift_seg8_dpp(int (&v)[8], const Coeffs& cf) {
+    static_assert(INVERSE || !MIRROR, "MIRROR is a mode of the inverse");
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
         const int k_step = INVERSE ? (NS - 1 - s) : s;
-        const int c = INVERSE ? -cf.c[k_step] : cf.c[k_step];
+        const int c = (INVERSE && !MIRROR) ? -cf.c[k_step] : cf.c[k_step];
         if ((k_step & 1) == 0) {  // predict: odd += d(even_left, even_right); v[7] needs the right neighbour's v[0]
             const int right0 = __builtin_amdgcn_update_dpp(0, v[0], 0x101 /* row_shl:1 */, 0xf, 0xf, false);
 #pragma unroll
-            for (int k = 1; k < 8; k += 2) v[k] = wadd(v[k], lift_delta<EXACT>(v[k - 1], k + 1 < 8 ? v[k + 1] : right0, c));
+            for (int k = 1; k < 8; k += 2) v[k] = lift_undo<MIRROR>(v[k], lift_delta<EXACT>(v[k - 1], k + 1 < 8 ? v[k + 1] : right0, c));
         } else {                  // update: even += d(odd_left, odd_right); v[0] needs the left neighbour's v[7]
             const int left7 = __builtin_amdgcn_update_dpp(0, v[7], 0x111 /* row_shr:1 */, 0xf, 0xf, false);
 #pragma unroll
-            for (int k = 0; k < 8; k += 2) v[k] = wadd(v[k], lift_delta<EXACT>(k >= 1 ? v[k - 1] : left7, v[k + 1], c));
+            for (int k = 0; k < 8; k += 2) v[k] = lift_undo<MIRROR>(v[k], lift_delta<EXACT>(k >= 1 ? v[k - 1] : left7, v[k + 1], c));
         }
     }
 }
 
-template <int NS, bool EDGE, bool EXACT, typename MidT, int PROBE = 0>
+template <int NS, bool EDGE, bool EXACT, typename MidT, int PROBE = 0, bool MIRROR = false>
 __device__ __forceinline__ void inv_xy_tile_dpp(const InvXy& a, int bx, int by, int t, int* lds) {
     constexpr int H = NS;
     constexpr int ER = X_TH + 2 * H;
@@ -1085,7 +1096,7 @@ __device__ __forceinline__ void inv_xy_tile_dpp(const InvXy& a, int bx, int by, 
         const int par = xq / ECh, j = xq % ECh;
         const int px = EDGE ? reflect_idx(2 * (gpx0 + j) + par, pw) : 2 * (gpx0 + j) + par;
         int v[ER];
-        inv_load_lift_column<NS, ER, EDGE, EXACT, MidT, PROBE>(a, ch, par, px, t, gy0 - H, v);
+        inv_load_lift_column<NS, ER, EDGE, EXACT, MidT, PROBE, MIRROR>(a, ch, par, px, t, gy0 - H, v);
         int* L = lds + (ch * ER) * X_LW + par * X_HO + (8 - H) / 2 + j;
 #pragma unroll
         for (int k = 0; k < ER; ++k) L[k * X_LW] = v[k];
@@ -1111,9 +1122,9 @@ __device__ __forceinline__ void inv_xy_tile_dpp(const InvXy& a, int bx, int by, 
             dst[1] = vb.x; dst[3] = vb.y; dst[5] = vb.z; dst[7] = vb.w;
         };
         fetch(0, y); fetch(1, co); fetch(2, cg);
-        lift_seg8_dpp<NS, EXACT, true>(y, a.cf);
-        lift_seg8_dpp<NS, EXACT, true>(co, a.cf);
-        lift_seg8_dpp<NS, EXACT, true>(cg, a.cf);
+        lift_seg8_dpp<NS, EXACT, true, MIRROR>(y, a.cf);
+        lift_seg8_dpp<NS, EXACT, true, MIRROR>(co, a.cf);
+        lift_seg8_dpp<NS, EXACT, true, MIRROR>(cg, a.cf);
         if (s >= 1 && s <= 12 && (!EDGE || (gy < (int)d.h && gxs < (int)d.w))) store_rgb8<PROBE>(a, EDGE, y, co, cg, t, gy, gxs);
     }
 }
@@ -1122,18 +1133,18 @@ __device__ __forceinline__ void inv_xy_tile_dpp(const InvXy& a, int bx, int by, 
 template <bool PACKED> struct InvTileShape { static constexpr int kThreads = PACKED ? I_THREADS : X_THREADS;
                                              static constexpr int kLdsInts = PACKED ? 3 * ((I_TH + 8) / 2) * I_LW : 3 * (X_TH + 8) * X_LW; };
 
-template <int NS, bool EXACT, typename MidT, bool PACKED, int PROBE = 0>
+template <int NS, bool EXACT, typename MidT, bool PACKED, int PROBE = 0, bool MIRROR = false>
 __global__ __launch_bounds__(InvTileShape<PACKED>::kThreads) void inv_xy_kernel(InvXy xa) {
     __shared__ __attribute__((aligned(16))) int lds[InvTileShape<PACKED>::kLdsInts];
     int bx, by, t;
     bool edge;
     if (!band_tile_of_block(xa.bt, xa.d.f, bx, by, t, edge)) return;
     if (PACKED) {
-        if (edge) inv_xy_tile_packed<NS, true, EXACT, MidT>(xa, bx, by, t, lds);
-        else inv_xy_tile_packed<NS, false, EXACT, MidT>(xa, bx, by, t, lds);
+        if (edge) inv_xy_tile_packed<NS, true, EXACT, MidT, MIRROR>(xa, bx, by, t, lds);
+        else inv_xy_tile_packed<NS, false, EXACT, MidT, MIRROR>(xa, bx, by, t, lds);
     } else {
-        if (edge && PROBE != 3) inv_xy_tile_dpp<NS, true, EXACT, MidT, PROBE>(xa, bx, by, t, lds);
-        else inv_xy_tile_dpp<NS, false, EXACT, MidT, PROBE>(xa, bx, by, t, lds);
+        if (edge && PROBE != 3) inv_xy_tile_dpp<NS, true, EXACT, MidT, PROBE, MIRROR>(xa, bx, by, t, lds);
+        else inv_xy_tile_dpp<NS, false, EXACT, MidT, PROBE, MIRROR>(xa, bx, by, t, lds);
     }
 }
 
@@ -1523,16 +1534,18 @@ bool launch_forward_coef_hist(const RgbLayout& rgb, const ChunkDims& d, int wave
 
 // ---- inverse ----
 
-template <int NS, bool EXACT, typename MidT, bool PACKED, int PROBE = 0, bool WIDE = false>
+template <int NS, bool EXACT, typename MidT, bool PACKED, int PROBE = 0, bool WIDE = false, bool MIRROR = false>
 static void inv_band_launch(const InvTm& ta, const InvXy& xa, hipStream_t st) {
-    if constexpr (WIDE) hipLaunchKernelGGL((inv_t_wide_kernel<NS, EXACT, MidT>), dim3(3u * ta.b.units_per_ch), dim3(256), 0, st, ta);
+    static_assert(WIDE || !MIRROR, "the mirrored inverse belongs to a wide container (.alc v4)");
+    if constexpr (WIDE) hipLaunchKernelGGL((inv_t_wide_kernel<NS, EXACT, MidT, MIRROR>), dim3(3u * ta.b.units_per_ch), dim3(256), 0, st, ta);
     else hipLaunchKernelGGL((inv_t_kernel<NS, EXACT, MidT, PROBE>), dim3(3u * ta.b.units_per_ch), dim3(256), 0, st, ta);
     const unsigned long long tiles = (unsigned long long)xa.bt.nx * xa.bt.nby * xa.d.f;
-    hipLaunchKernelGGL((inv_xy_kernel<NS, EXACT, MidT, PACKED, PROBE>), dim3(xcd_grid(tiles)), dim3(InvTileShape<PACKED>::kThreads), 0, st, xa);
+    hipLaunchKernelGGL((inv_xy_kernel<NS, EXACT, MidT, PACKED, PROBE, MIRROR>), dim3(xcd_grid(tiles)), dim3(InvTileShape<PACKED>::kThreads), 0, st, xa);
 }
 
 // WIDE: d_sym is the u16 symbol volume of .alc v3 and the temporal role runs its wide instance; everything else is shared.
-template <bool WIDE>
+// MIRROR: both roles run their mirrored instances (.alc v4); the geometry, the bands and the instance choice are the same.
+template <bool WIDE, bool MIRROR = false>
 static bool inverse_launches(const void* d_sym, const ChunkDims& d, int wavelet, const int32_t step[3],
                              bool exact, bool mid16, bool lds16, void* d_scratch, const RgbLayout& rgb, hipStream_t st) {
     if (!transform_tiles_eligible(d)) return false;
@@ -1580,10 +1593,10 @@ static bool inverse_launches(const void* d_sym, const ChunkDims& d, int wavelet,
         }
 #define ALICE_INV(NS_) \
         switch (variant) { \
-        case 0: inv_band_launch<NS_, true, int32_t, false, 0, WIDE>(ta, xa, st); break; \
-        case 1: inv_band_launch<NS_, false, int32_t, false, 0, WIDE>(ta, xa, st); break; \
-        case 2: inv_band_launch<NS_, false, int16_t, false, 0, WIDE>(ta, xa, st); break; \
-        default: inv_band_launch<NS_, false, int16_t, true, 0, WIDE>(ta, xa, st); break; \
+        case 0: inv_band_launch<NS_, true, int32_t, false, 0, WIDE, MIRROR>(ta, xa, st); break; \
+        case 1: inv_band_launch<NS_, false, int32_t, false, 0, WIDE, MIRROR>(ta, xa, st); break; \
+        case 2: inv_band_launch<NS_, false, int16_t, false, 0, WIDE, MIRROR>(ta, xa, st); break; \
+        default: inv_band_launch<NS_, false, int16_t, true, 0, WIDE, MIRROR>(ta, xa, st); break; \
         }
         if (ls.n == 4) { ALICE_INV(4) } else { ALICE_INV(2) }
 #undef ALICE_INV
@@ -1598,6 +1611,10 @@ bool launch_inverse_transform(const uint8_t* d_sym, const ChunkDims& d, int wave
 bool launch_inverse_transform_wide(const uint16_t* d_sym, const ChunkDims& d, int wavelet, const int32_t step[3],
                                    bool exact, bool mid16, bool lds16, void* d_scratch, const RgbLayout& rgb, hipStream_t st) {
     return inverse_launches<true>(d_sym, d, wavelet, step, exact, mid16, lds16, d_scratch, rgb, st);
+}
+bool launch_inverse_transform_reversible(const uint16_t* d_sym, const ChunkDims& d, int wavelet, const int32_t step[3],
+                                         bool exact, bool mid16, bool lds16, void* d_scratch, const RgbLayout& rgb, hipStream_t st) {
+    return inverse_launches<true, true>(d_sym, d, wavelet, step, exact, mid16, lds16, d_scratch, rgb, st);
 }
 
 

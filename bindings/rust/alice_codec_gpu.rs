@@ -844,11 +844,13 @@ pub fn decode_wide(data: &[u8]) -> Result<Vec<u8>, CodecError> {
 
 pub fn wide_stream_bound(n: u64, lane_symbols: u32) -> u64 { unsafe { alice_codec_wide_stream_bound(n, lane_symbols) } }
 
-/// The RGB bytes of a container of any version: 1 (`FrameDecoder`), 2 (`decode_split`) or 3 (`decode_wide`).
+/// The RGB bytes of a container of any version: 1 (`FrameDecoder`), 2 (`decode_split`), 3 (`decode_wide`) or
+/// 4 (`decode_reversible`).
 pub fn decode_alc(data: &[u8]) -> Result<Vec<u8>, CodecError> {
     match alc_version(data) {
         2 => decode_split(data),
         3 => decode_wide(data),
+        4 => decode_reversible(data),
         _ => FrameDecoder::new().decode(&EncodedChunk::from_bytes(data)?),
     }
 }
@@ -907,4 +909,152 @@ pub fn encode_wide_to_size(rgb_frames: &[u8], width: u32, height: u32, frames: u
         }
         Ok((take(p, n), q, fits != 0))
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// reversible format (.alc version 4).  Version 3 whose decoder runs the forward lifting's mirror:
+// at quality 100 (quantiser step 1) the pixels come back exactly.  The container for lossless archival and intermediate
+// storage; below quality 100 prefer version 3 (or 2).  The encoder is version 3's -- the bytes are `encode_wide`'s except
+// byte 4 -- so `predict_wide_sizes` brackets a version 4 length and `wide_stream_bound` is its stream bound; there are no
+// byte-budget calls.  Each parser refuses the other versions.
+// ---------------------------------------------------------------------------------------------------------------
+
+#[link(name = "alice_codec")]
+extern "C" {
+    fn alice_codec_reversible_info(data: *const u8, len: u64, info: *mut RawSplitInfo) -> c_int;
+    fn alice_codec_encode_reversible(e: *const RawEncoder, rgb: *const u8, rgb_len: u64, w: u32, h: u32, f: u32, lane_symbols: u32,
+                                     out_len: *mut u64) -> *mut u8;
+    fn alice_codec_decode_reversible(data: *const u8, len: u64, out_len: *mut u64) -> *mut u8;
+    fn alice_codec_dev_encode_reversible(d_rgb: *const std::ffi::c_void, w: u32, h: u32, f: u32, n_chunks: u32, wavelet: u8,
+                                         quality: u8, qualities: *const u8, lane_symbols: u32, d_out: *mut std::ffi::c_void,
+                                         out_stride: u64, sizes: *mut u64, hip_stream: *mut std::ffi::c_void) -> c_int;
+    fn alice_codec_dev_decode_reversible(d_alc: *const std::ffi::c_void, alc_stride: u64, sizes: *const u64, n_chunks: u32,
+                                         d_rgb_out: *mut std::ffi::c_void, hip_stream: *mut std::ffi::c_void) -> c_int;
+    fn alice_codec_dev_encode_reversible_regions(d_frames: *const std::ffi::c_void, frame_width: u32, frame_height: u32,
+                                                 origins: *const u32, w: u32, h: u32, f: u32, n_chunks: u32, wavelet: u8,
+                                                 quality: u8, qualities: *const u8, lane_symbols: u32,
+                                                 d_out: *mut std::ffi::c_void, out_stride: u64, sizes: *mut u64,
+                                                 hip_stream: *mut std::ffi::c_void) -> c_int;
+    fn alice_codec_dev_decode_reversible_regions(d_alc: *const std::ffi::c_void, alc_stride: u64, sizes: *const u64, n_chunks: u32,
+                                                 d_frames_out: *mut std::ffi::c_void, frame_width: u32, frame_height: u32,
+                                                 origins: *const u32, hip_stream: *mut std::ffi::c_void) -> c_int;
+}
+
+pub const LOSSLESS_QUALITY: u8 = 100;
+
+/// The validated header of a version 4 container (host code, no device needed).
+pub fn reversible_info(data: &[u8]) -> Result<SplitInfo, CodecError> {
+    let mut c = RawSplitInfo::default();
+    let rc = unsafe { alice_codec_reversible_info(data.as_ptr(), data.len() as u64, &mut c) };
+    check(rc, 0, data.len())?;
+    Ok(SplitInfo {
+        width: c.width, height: c.height, frames: c.frames, lane_symbols: c.lane_symbols,
+        wavelet_type: match c.wavelet { 1 => WaveletType::Cdf97, 2 => WaveletType::Haar, _ => WaveletType::Cdf53 },
+        quant_step: c.quant_step, dead_zone: c.dead_zone, num_symbols: c.num_symbols, n_blocks: c.n_blocks,
+        payload_len: c.payload_len,
+    })
+}
+
+/// One chunk as version 4 bytes, with the encoder's wavelet and quality (`lane_symbols` 0: the default).
+pub fn encode_reversible(encoder: &FrameEncoder, rgb_frames: &[u8], width: u32, height: u32, frames: u32, lane_symbols: u32)
+    -> Result<Vec<u8>, CodecError> {
+    let mut n = 0u64;
+    unsafe {
+        let e = alice_codec_encoder_create_ex(encoder.quality, encoder.wavelet_type as u8);
+        let p = alice_codec_encode_reversible(e, rgb_frames.as_ptr(), rgb_frames.len() as u64, width, height, frames, lane_symbols,
+                                              &mut n);
+        alice_codec_encoder_destroy(e);
+        if p.is_null() {
+            let expected = (width as usize).saturating_mul(height as usize).saturating_mul(frames as usize).saturating_mul(3);
+            return Err(last_error(expected, rgb_frames.len(), width, height, 0));
+        }
+        Ok(take(p, n))
+    }
+}
+
+/// `encode_reversible` at quality 100: `decode_reversible` (or `decode_alc`) returns `rgb_frames` exactly.
+pub fn encode_lossless(rgb_frames: &[u8], width: u32, height: u32, frames: u32, wavelet_type: WaveletType, lane_symbols: u32)
+    -> Result<Vec<u8>, CodecError> {
+    encode_reversible(&FrameEncoder::with_wavelet(LOSSLESS_QUALITY, wavelet_type), rgb_frames, width, height, frames, lane_symbols)
+}
+
+/// The RGB bytes of a version 4 container; `InvalidBitstream` when a directory does not add up or a lane fails its end check.
+pub fn decode_reversible(data: &[u8]) -> Result<Vec<u8>, CodecError> {
+    let mut n = 0u64;
+    unsafe {
+        let p = alice_codec_decode_reversible(data.as_ptr(), data.len() as u64, &mut n);
+        if p.is_null() { Err(last_error(0, data.len(), 0, 0, 0)) } else { Ok(take(p, n)) }
+    }
+}
+
+/// # Safety
+/// As `split_encode_device`.
+pub unsafe fn reversible_encode_device(d_rgb: *const std::ffi::c_void, width: u32, height: u32, frames: u32, n_chunks: u32,
+                                       wavelet_type: WaveletType, quality: u8, qualities: Option<&[u8]>, lane_symbols: u32,
+                                       d_out: *mut std::ffi::c_void, out_stride: u64, hip_stream: *mut std::ffi::c_void)
+    -> Result<Vec<u64>, CodecError> {
+    if let Some(q) = qualities {
+        if q.len() != n_chunks as usize { return Err(CodecError::InvalidBufferSize { expected: n_chunks as usize, got: q.len() }); }
+    }
+    let mut sizes = vec![0u64; n_chunks as usize];
+    let rc = alice_codec_dev_encode_reversible(d_rgb, width, height, frames, n_chunks, wavelet_type as u8, quality,
+                                               qualities.map_or(std::ptr::null(), |q| q.as_ptr()), lane_symbols, d_out, out_stride,
+                                               sizes.as_mut_ptr(), hip_stream);
+    check(rc, 0, 0).map(|_| sizes)
+}
+
+/// `reversible_encode_device` at quality 100 for every chunk.
+///
+/// # Safety
+/// As `split_encode_device`.
+pub unsafe fn encode_lossless_device(d_rgb: *const std::ffi::c_void, width: u32, height: u32, frames: u32, n_chunks: u32,
+                                     wavelet_type: WaveletType, lane_symbols: u32, d_out: *mut std::ffi::c_void, out_stride: u64,
+                                     hip_stream: *mut std::ffi::c_void) -> Result<Vec<u64>, CodecError> {
+    reversible_encode_device(d_rgb, width, height, frames, n_chunks, wavelet_type, LOSSLESS_QUALITY, None, lane_symbols, d_out,
+                             out_stride, hip_stream)
+}
+
+/// # Safety
+/// As `split_decode_device`.
+pub unsafe fn reversible_decode_device(d_alc: *const std::ffi::c_void, alc_stride: u64, sizes: &[u64],
+                                       d_rgb_out: *mut std::ffi::c_void, hip_stream: *mut std::ffi::c_void)
+    -> Result<(), CodecError> {
+    check(alice_codec_dev_decode_reversible(d_alc, alc_stride, sizes.as_ptr(), sizes.len() as u32, d_rgb_out, hip_stream), 0, 0)
+}
+
+/// Chunk i is frames `[i * frames, (i + 1) * frames)` of the `frame_width` x `frame_height` device frames, cropped to
+/// `width` x `height` at `origins[i]`; the bytes of chunk i are `encode_reversible`'s of the crop.
+///
+/// # Safety
+/// As `split_encode_device`; `d_frames` holds `origins.len() * frames` packed RGB frames.
+pub unsafe fn reversible_encode_regions_device(d_frames: *const std::ffi::c_void, frame_width: u32, frame_height: u32,
+                                               origins: &[(u32, u32)], width: u32, height: u32, frames: u32,
+                                               wavelet_type: WaveletType, quality: u8, qualities: Option<&[u8]>, lane_symbols: u32,
+                                               d_out: *mut std::ffi::c_void, out_stride: u64, hip_stream: *mut std::ffi::c_void)
+    -> Result<Vec<u64>, CodecError> {
+    let n_chunks = origins.len();
+    if let Some(q) = qualities {
+        if q.len() != n_chunks { return Err(CodecError::InvalidBufferSize { expected: n_chunks, got: q.len() }); }
+    }
+    let flat: Vec<u32> = origins.iter().flat_map(|&(x, y)| [x, y]).collect();
+    let mut sizes = vec![0u64; n_chunks];
+    let rc = alice_codec_dev_encode_reversible_regions(d_frames, frame_width, frame_height, flat.as_ptr(), width, height, frames,
+                                                       n_chunks as u32, wavelet_type as u8, quality,
+                                                       qualities.map_or(std::ptr::null(), |q| q.as_ptr()), lane_symbols, d_out,
+                                                       out_stride, sizes.as_mut_ptr(), hip_stream);
+    check(rc, 0, 0).map(|_| sizes)
+}
+
+/// Chunk i is decoded and pasted into its rectangle of frames `[i * frames, (i + 1) * frames)`; no byte outside the
+/// rectangles is written.
+///
+/// # Safety
+/// As `split_decode_device`; `d_frames_out` holds `sizes.len() * frames` packed RGB frames.
+pub unsafe fn reversible_decode_regions_device(d_alc: *const std::ffi::c_void, alc_stride: u64, sizes: &[u64],
+                                               d_frames_out: *mut std::ffi::c_void, frame_width: u32, frame_height: u32,
+                                               origins: &[(u32, u32)], hip_stream: *mut std::ffi::c_void) -> Result<(), CodecError> {
+    if origins.len() != sizes.len() { return Err(CodecError::InvalidBufferSize { expected: sizes.len(), got: origins.len() }); }
+    let flat: Vec<u32> = origins.iter().flat_map(|&(x, y)| [x, y]).collect();
+    check(alice_codec_dev_decode_reversible_regions(d_alc, alc_stride, sizes.as_ptr(), sizes.len() as u32, d_frames_out, frame_width,
+                                                    frame_height, flat.as_ptr(), hip_stream), 0, 0)
 }

@@ -576,6 +576,37 @@ int alice_codec_dev_encode_wide_to_budget(const void *d_frames, uint32_t frame_w
                                           uint8_t *chosen, uint8_t *fits, void *d_out, uint64_t out_stride, uint64_t *sizes,
                                           void *hip_stream);
 
+/* ---- reversible format (.alc version 4) ----
+ * Version 3 with a decoder whose inverse lifting is the forward's mirror: the steps in reverse order, each one
+ * target -= delta(neighbours, +c) with the forward's own delta, where the reference's inverse (versions 1 to 3) re-runs the
+ * step with the negated coefficient and is off by one wherever (a + b) * c = 4096 (mod 8192).  At quality 100 (quantiser
+ * step 1) the decoded pixels ARE the input: choose it for lossless archival or intermediate storage.  Any quality is
+ * legal (the header stores the step); below 100 its pixels are no better than version 3's and it is not recommended.
+ * The encoder is version 3's: the bytes equal alice_codec_encode_wide's of the same call except byte 4 (the version), so
+ * alice_codec_predict_wide_sizes / _dev_predict_wide_sizes are exact for version 4 and alice_codec_wide_stream_bound is
+ * its stream bound; there are no byte-budget calls.  These calls refuse versions 1 to 3 and the calls of those versions
+ * refuse version 4 ("unsupported version: 3 (expected 4)").  Every call validates like its version 3 twin, in the same
+ * order. */
+uint8_t *alice_codec_encode_reversible(const FrameEncoder *encoder, const uint8_t *rgb, uint64_t rgb_len, uint32_t width,
+                                       uint32_t height, uint32_t frames, uint32_t lane_symbols, uint64_t *out_len);
+uint8_t *alice_codec_decode_reversible(const uint8_t *data, uint64_t len, uint64_t *out_len);
+int alice_codec_reversible_info(const uint8_t *data, uint64_t len, AliceSplitInfo *info);
+/* device-resident: alice_codec_dev_encode_wide / _dev_decode_wide for version 4 */
+int alice_codec_dev_encode_reversible(const void *d_rgb, uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks,
+                                      uint8_t wavelet_type, uint8_t quality, const uint8_t *qualities, uint32_t lane_symbols,
+                                      void *d_out, uint64_t out_stride, uint64_t *sizes, void *hip_stream);
+int alice_codec_dev_decode_reversible(const void *d_alc, uint64_t alc_stride, const uint64_t *sizes, uint32_t n_chunks,
+                                      void *d_rgb_out, void *hip_stream);
+/* alice_codec_dev_encode_wide_regions / _dev_decode_wide_regions for version 4 */
+int alice_codec_dev_encode_reversible_regions(const void *d_frames, uint32_t frame_width, uint32_t frame_height,
+                                              const uint32_t *origins, uint32_t width, uint32_t height, uint32_t frames,
+                                              uint32_t n_chunks, uint8_t wavelet_type, uint8_t quality, const uint8_t *qualities,
+                                              uint32_t lane_symbols, void *d_out, uint64_t out_stride, uint64_t *sizes,
+                                              void *hip_stream);
+int alice_codec_dev_decode_reversible_regions(const void *d_alc, uint64_t alc_stride, const uint64_t *sizes, uint32_t n_chunks,
+                                              void *d_frames_out, uint32_t frame_width, uint32_t frame_height,
+                                              const uint32_t *origins, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -642,11 +642,97 @@ inline void wide_decode_device(const void* d_alc, uint64_t alc_stride, const std
                                void* hip_stream = nullptr) {
     detail::check(alice_codec_dev_decode_wide(d_alc, alc_stride, sizes.data(), static_cast<uint32_t>(sizes.size()), d_rgb_out, hip_stream));
 }
-// the RGB bytes of a container of any version: 1 (FrameDecoder), 2 (decode_split) or 3 (decode_wide)
+// ---- reversible format (.alc version 4) ----
+// Version 3 whose decoder runs the forward lifting's mirror: at quality 100 (quantiser step 1) the pixels come back exactly.
+// The container for lossless archival and intermediate storage; below quality 100 prefer version 3 (or 2).  The encoder is
+// version 3's -- the bytes are encode_wide's except byte 4 -- so predict_wide_sizes brackets a version 4 length and
+// wide_stream_bound is its stream bound; there are no byte-budget calls.  Each parser refuses the other versions.
+constexpr uint8_t LOSSLESS_QUALITY = 100;
+inline SplitInfo reversible_info(const uint8_t* data, size_t len) {
+    static const uint8_t empty = 0;
+    AliceSplitInfo c{};
+    detail::check(alice_codec_reversible_info(data ? data : &empty, len, &c));
+    SplitInfo i;
+    i.width = c.width; i.height = c.height; i.frames = c.frames; i.lane_symbols = c.lane_symbols;
+    i.wavelet_type = static_cast<WaveletType>(c.wavelet);
+    for (int k = 0; k < 3; ++k) {
+        i.quant_step[k] = c.quant_step[k]; i.dead_zone[k] = c.dead_zone[k];
+        i.num_symbols[k] = c.num_symbols[k]; i.n_blocks[k] = c.n_blocks[k]; i.payload_len[k] = c.payload_len[k];
+    }
+    return i;
+}
+inline SplitInfo reversible_info(const std::vector<uint8_t>& v) { return reversible_info(v.data(), v.size()); }
+inline std::vector<uint8_t> encode_reversible(const FrameEncoder& enc, const std::vector<uint8_t>& rgb, uint32_t w, uint32_t h, uint32_t f,
+                                              uint32_t lane_symbols = 0) {
+    static const uint8_t empty = 0;
+    uint64_t n = 0;
+    uint8_t* p = alice_codec_encode_reversible(enc.handle(), rgb.empty() ? &empty : rgb.data(), rgb.size(), w, h, f, lane_symbols, &n);
+    if (!p) detail::raise();
+    return detail::take(p, n);
+}
+inline std::vector<uint8_t> decode_reversible(const std::vector<uint8_t>& data) {
+    static const uint8_t empty = 0;
+    uint64_t n = 0;
+    uint8_t* p = alice_codec_decode_reversible(data.empty() ? &empty : data.data(), data.size(), &n);
+    if (!p) detail::raise(ALICE_ERR_INVALID_BITSTREAM);
+    return detail::take(p, n);
+}
+// encode_reversible at quality 100: decode_reversible (or decode_alc) returns rgb exactly
+inline std::vector<uint8_t> encode_lossless(const std::vector<uint8_t>& rgb, uint32_t w, uint32_t h, uint32_t f,
+                                            WaveletType wt = WaveletType::Cdf53, uint32_t lane_symbols = 0) {
+    return encode_reversible(FrameEncoder::with_wavelet(LOSSLESS_QUALITY, wt), rgb, w, h, f, lane_symbols);
+}
+inline std::vector<uint64_t> reversible_encode_device(const void* d_rgb, uint32_t w, uint32_t h, uint32_t f, uint32_t n_chunks,
+                                                      WaveletType wt, uint8_t quality, void* d_out, uint64_t out_stride,
+                                                      const std::vector<uint8_t>& qualities = {}, uint32_t lane_symbols = 0,
+                                                      void* hip_stream = nullptr) {
+    if (!qualities.empty() && qualities.size() != n_chunks) throw CodecError(ALICE_ERR_INVALID_BUFFER_SIZE, "one quality per chunk");
+    std::vector<uint64_t> sizes(n_chunks);
+    detail::check(alice_codec_dev_encode_reversible(d_rgb, w, h, f, n_chunks, static_cast<uint8_t>(wt), quality,
+                                                    qualities.empty() ? nullptr : qualities.data(), lane_symbols, d_out, out_stride,
+                                                    sizes.data(), hip_stream));
+    return sizes;
+}
+inline std::vector<uint64_t> encode_lossless_device(const void* d_rgb, uint32_t w, uint32_t h, uint32_t f, uint32_t n_chunks, void* d_out,
+                                                    uint64_t out_stride, WaveletType wt = WaveletType::Cdf53, uint32_t lane_symbols = 0,
+                                                    void* hip_stream = nullptr) {
+    return reversible_encode_device(d_rgb, w, h, f, n_chunks, wt, LOSSLESS_QUALITY, d_out, out_stride, {}, lane_symbols, hip_stream);
+}
+inline void reversible_decode_device(const void* d_alc, uint64_t alc_stride, const std::vector<uint64_t>& sizes, void* d_rgb_out,
+                                     void* hip_stream = nullptr) {
+    detail::check(alice_codec_dev_decode_reversible(d_alc, alc_stride, sizes.data(), static_cast<uint32_t>(sizes.size()), d_rgb_out,
+                                                    hip_stream));
+}
+// regions of device frames (alice_codec_dev_encode_reversible_regions / _dev_decode_reversible_regions): chunk i is frames
+// [i * f, (i + 1) * f) cropped to w x h at origins[2i], origins[2i + 1]; a decode writes no byte outside the rectangles
+inline std::vector<uint64_t> reversible_encode_regions_device(const void* d_frames, uint32_t frame_width, uint32_t frame_height,
+                                                              const std::vector<uint32_t>& origins, uint32_t w, uint32_t h, uint32_t f,
+                                                              WaveletType wt, uint8_t quality, void* d_out, uint64_t out_stride,
+                                                              const std::vector<uint8_t>& qualities = {}, uint32_t lane_symbols = 0,
+                                                              void* hip_stream = nullptr) {
+    const uint32_t n_chunks = static_cast<uint32_t>(origins.size() / 2);
+    if (origins.size() % 2) throw CodecError(ALICE_ERR_INVALID_BUFFER_SIZE, "origins: one (x, y) pair per chunk");
+    if (!qualities.empty() && qualities.size() != n_chunks) throw CodecError(ALICE_ERR_INVALID_BUFFER_SIZE, "one quality per chunk");
+    std::vector<uint64_t> sizes(n_chunks);
+    detail::check(alice_codec_dev_encode_reversible_regions(d_frames, frame_width, frame_height, origins.data(), w, h, f, n_chunks,
+                                                            static_cast<uint8_t>(wt), quality,
+                                                            qualities.empty() ? nullptr : qualities.data(), lane_symbols, d_out,
+                                                            out_stride, sizes.data(), hip_stream));
+    return sizes;
+}
+inline void reversible_decode_regions_device(const void* d_alc, uint64_t alc_stride, const std::vector<uint64_t>& sizes, void* d_frames_out,
+                                             uint32_t frame_width, uint32_t frame_height, const std::vector<uint32_t>& origins,
+                                             void* hip_stream = nullptr) {
+    if (origins.size() != 2 * sizes.size()) throw CodecError(ALICE_ERR_INVALID_BUFFER_SIZE, "origins: one (x, y) pair per chunk");
+    detail::check(alice_codec_dev_decode_reversible_regions(d_alc, alc_stride, sizes.data(), static_cast<uint32_t>(sizes.size()),
+                                                            d_frames_out, frame_width, frame_height, origins.data(), hip_stream));
+}
+// the RGB bytes of a container of any version: 1 (FrameDecoder), 2 (decode_split), 3 (decode_wide) or 4 (decode_reversible)
 inline std::vector<uint8_t> decode_alc(const std::vector<uint8_t>& data) {
     const int version = alc_version(data);
     if (version == 2) return decode_split(data);
     if (version == 3) return decode_wide(data);
+    if (version == 4) return decode_reversible(data);
     return FrameDecoder::new_().decode(EncodedChunk::from_bytes(data));
 }
 
