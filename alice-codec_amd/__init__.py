@@ -302,6 +302,19 @@ def load_library() -> C.CDLL:
                                                             C.c_uint32, C.c_uint8, C.c_uint32, _u64p, C.c_uint8, C.c_uint8, _u8p, _u8p,
                                                             vp, C.c_uint64, _u64p, vp]),
         "alice_codec_test_last_split_trials": (C.c_uint32, [_u32p, C.c_uint32]),
+        "alice_codec_dev_rgb_sse": (C.c_int, [vp, C.c_uint64, C.c_uint64, vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
+                                              C.c_uint64, vp, vp]),
+        "alice_codec_dev_trial_sse": (C.c_int, [C.c_uint8, vp, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                C.c_uint32, C.c_uint8, C.c_uint8, _u8p, _u64p, vp, vp]),
+        "alice_codec_psnr_from_sse": (C.c_double, [C.c_uint64, C.c_uint64]),
+        "alice_codec_dev_encode_to_psnr": (C.c_int, [C.c_uint8, vp, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                     C.c_uint32, C.c_uint8, C.c_uint32, C.c_double, C.c_uint8, C.c_uint8, _u8p, _u8p,
+                                                     C.POINTER(C.c_double), vp, C.c_uint64, _u64p, vp]),
+        "alice_codec_encode_to_psnr": (vp, [C.c_uint8, C.c_uint8, _u8p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                            C.c_double, C.c_uint8, C.c_uint8, _u8p, _u8p, C.POINTER(C.c_double), _u64p]),
+        "alice_codec_test_last_quality_trials": (C.c_uint32, [_u32p, C.c_uint32]),
+        "alice_codec_test_inverse_scratch_bytes": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]),
+        "alice_codec_test_sq_diff_sum": (C.c_int, [vp, vp, C.c_uint64, _u64p, vp]),
         "alice_codec_test_inverse_variant": (C.c_int, [C.c_uint8, _i32p, C.c_int]),
     }
     for name, (res, args) in sig.items():
@@ -1530,7 +1543,7 @@ def _runs(boxes) -> list:
 def encode_person_chunks(d_frames, d_background, width: int, height: int, frames: int, n_chunks: int, quality: int,
                          wavelet: WaveletType = WaveletType.Cdf53, config: SegmentConfig | None = None,
                          green_threshold: int | None = None, format: str = "v1", lane_symbols: int = 0,
-                         max_bytes: int | None = None) -> list:
+                         max_bytes: int | None = None, min_psnr: float | None = None) -> list:
     """Hybrid encode of n_chunks chunks of `frames` frames each (d_frames: n_chunks * frames frames of width x height
     interleaved RGB in HBM) -> list of (bbox [x, y, w, h] in pixels, .alc bytes), one per chunk.
 
@@ -1548,9 +1561,19 @@ def encode_person_chunks(d_frames, d_background, width: int, height: int, frames
     a byte budget per chunk: every box is then coded at the quality split_encode_to_budget_device /
     wide_encode_to_budget_device picks in [min(10, hi), hi], hi = min(quality, 100), and a chunk that cannot be guaranteed
     to fit is coded at the low end of the range.  format="reversible" codes the boxes as version 4
-    (reversible_encode_regions_device): at quality 100 the boxes come back exactly; it has no byte budget."""
+    (reversible_encode_regions_device): at quality 100 the boxes come back exactly; it has no byte budget.  min_psnr (split
+    and wide only, not together with max_bytes) is a PSNR floor in dB per chunk, measured on the box: every box is coded at
+    the lowest quality in [min(10, hi), hi] that split_encode_to_psnr_device / wide_encode_to_psnr_device finds to reach it,
+    and at hi when none does."""
     if format not in ("v1", "split", "wide", "reversible"):
         raise CodecError(9, f"format must be 'v1', 'split', 'wide' or 'reversible', got {format!r}")
+    if min_psnr is not None and max_bytes is not None:
+        raise CodecError(9, "min_psnr and max_bytes are two rate controls: give one of them")
+    if min_psnr is not None and format not in ("split", "wide"):
+        raise CodecError(9, "min_psnr is a version 2 / version 3 quality floor: it needs format='split' or format='wide' "
+                            "(version 1 has no quality to control, and a lossless encode has no quality to search)")
+    if min_psnr is not None:
+        min_psnr = _check_min_psnr(min_psnr)
     if max_bytes is not None and format not in ("split", "wide"):
         raise CodecError(9, "max_bytes is a version 2 / version 3 budget: it needs format='split' or format='wide'")
     W, H, f = _positive_u32(width, "width"), _positive_u32(height, "height"), _positive_u32(frames, "frames")
@@ -1586,6 +1609,7 @@ def encode_person_chunks(d_frames, d_background, width: int, height: int, frames
         encode_regions = {"split": split_encode_regions_device, "wide": wide_encode_regions_device,
                           "reversible": reversible_encode_regions_device}[format]
         encode_to_budget = wide_encode_to_budget_device if wide else split_encode_to_budget_device   # (max_bytes: split, wide)
+        encode_to_psnr = wide_encode_to_psnr_device if wide else split_encode_to_psnr_device         # (min_psnr: split, wide)
         out = [(b, empty) for b in boxes]
         for i, j in _runs(boxes):
             bw, bh = boxes[i][2], boxes[i][3]
@@ -1594,7 +1618,12 @@ def encode_person_chunks(d_frames, d_background, width: int, height: int, frames
             d_out = torch.empty((j - i) * stride, dtype=torch.uint8, device="cuda")
             origins = [b[:2] for b in boxes[i:j]]
             src = frames_ptr + i * f * frame_bytes
-            if max_bytes is None:
+            if min_psnr is not None:
+                hi_q = min(int(quality), 100)
+                _, _, _, sizes = encode_to_psnr(src, bw, bh, f, j - i, wavelet, min_psnr, d_out.data_ptr(), stride,
+                                                min_quality=min(10, hi_q), max_quality=hi_q, lane_symbols=lane_symbols,
+                                                frame_width=W, frame_height=H, origins=origins)
+            elif max_bytes is None:
                 sizes = encode_regions(src, W, H, origins, bw, bh, f, wavelet, int(quality), d_out.data_ptr(), stride,
                                        lane_symbols=lane_symbols)
             else:
@@ -2181,3 +2210,161 @@ def reversible_decode_regions_device(d_alc_ptr: int, alc_stride: int, sizes, d_f
     """wide_decode_regions_device for version 4: no byte outside the rectangles is written."""
     _decode_container_regions("reversible", d_alc_ptr, alc_stride, sizes, d_frames_out_ptr, frame_width, frame_height, origins,
                               stream)
+
+
+# ---- quality control: exact trial distortion and PSNR-floor encodes (DESIGN.md section 13) ----
+
+FORMAT_SPLIT, FORMAT_WIDE, FORMAT_REVERSIBLE = 2, 3, 4
+QUALITY_MAX_TRIALS = 8
+_FORMAT_BYTE = {"split": FORMAT_SPLIT, "wide": FORMAT_WIDE, "reversible": FORMAT_REVERSIBLE}
+
+
+def _format_byte(format) -> int:
+    """'split' / 'wide' / 'reversible' or the version byte itself (the library refuses the bytes it does not know)."""
+    if isinstance(format, str):
+        if format not in _FORMAT_BYTE:
+            raise CodecError(4, f"format must be 'split', 'wide' or 'reversible', got {format!r}")
+        return _FORMAT_BYTE[format]
+    v = int(format)
+    if not 0 <= v <= 255:
+        raise CodecError(4, f"format byte must fit a u8, got {format}")
+    return v
+
+
+def _check_min_psnr(min_psnr) -> float:
+    t = float(min_psnr)
+    if t != t or t < 0.0:
+        raise CodecError(2, "min_psnr must be a number >= 0 (or inf for exact)")
+    return t
+
+
+def psnr_from_sse(sse: int, n_bytes: int) -> float:
+    """The dB value of a squared error over n_bytes samples, by the expression psnr() uses: inf at 0."""
+    return float(load_library().alice_codec_psnr_from_sse(int(sse), int(n_bytes)))
+
+
+def rgb_sse_device(d_a_ptr: int, d_b_ptr: int, width: int, height: int, n_frames: int, a_pitches=None, b_pitches=None,
+                   d_frame_sse_ptr: int | None = None, stream: int = 0):
+    """Exact squared error per frame of two device volumes of n_frames frames of width x height interleaved RGB.  A side's
+    pitches are (row_pitch, frame_pitch) in bytes (None: packed); the pointers may have any byte alignment.  The n_frames
+    u64 sums go to d_frame_sse_ptr when given (returns None), else they are returned as an array."""
+    _dims_u32(width, height)
+    packed = (3 * width, 3 * width * height)
+    ap = tuple(int(v) for v in (a_pitches or packed)); bp = tuple(int(v) for v in (b_pitches or packed))
+    fn = load_library().alice_codec_dev_rgb_sse
+    if d_frame_sse_ptr is not None:
+        _check(fn(d_a_ptr, ap[0], ap[1], d_b_ptr, bp[0], bp[1], width, height, int(n_frames), d_frame_sse_ptr, stream or None))
+        return None
+    import torch
+    out = torch.empty(max(int(n_frames), 1), dtype=torch.int64, device="cuda")
+    _check(fn(d_a_ptr, ap[0], ap[1], d_b_ptr, bp[0], bp[1], width, height, int(n_frames), out.data_ptr(), stream or None))
+    return out.cpu().numpy().view(np.uint64)[:int(n_frames)]
+
+
+def trial_sse_device(format, d_frames_ptr: int, width: int, height: int, frames: int, n_chunks: int, wavelet_type: WaveletType,
+                     quality: int, qualities=None, frame_width: int = 0, frame_height: int = 0, origins=None,
+                     d_frame_sse_ptr: int | None = None, stream: int = 0) -> np.ndarray:
+    """The squared error, per chunk, between the source and what the format's decode returns for the format's encode at the
+    given quality (chunk i at qualities[i] when given): a forward and an inverse transform and one comparison pass, no
+    entropy coding.  Packed chunks, or regions of frame_width x frame_height frames when origins is given.
+    d_frame_sse_ptr: device memory for n_chunks * frames u64 that receives the per-frame sums."""
+    _dims_u32(width, height, frames, n_chunks, frame_width, frame_height)
+    q = None if qualities is None else np.ascontiguousarray(qualities, dtype=np.uint8).reshape(-1)
+    if q is not None and q.size != n_chunks:
+        raise ValueError("one quality per chunk")
+    o = None if origins is None else _origins_u32(origins, n_chunks)
+    sse = np.zeros(max(n_chunks, 1), np.uint64)
+    _check(load_library().alice_codec_dev_trial_sse(_format_byte(format), d_frames_ptr, frame_width, frame_height,
+                                                    None if o is None else _p(o, _u32p), width, height, frames, n_chunks,
+                                                    int(wavelet_type), int(quality), None if q is None else _p(q, _u8p),
+                                                    _p(sse, _u64p), d_frame_sse_ptr, stream or None))
+    return sse[:n_chunks]
+
+
+def trial_psnr_device(format, d_frames_ptr: int, width: int, height: int, frames: int, n_chunks: int, wavelet_type: WaveletType,
+                      quality: int, qualities=None, frame_width: int = 0, frame_height: int = 0, origins=None,
+                      stream: int = 0) -> np.ndarray:
+    """trial_sse_device as dB per chunk (psnr_from_sse over the chunk's width * height * frames * 3 samples)."""
+    sse = trial_sse_device(format, d_frames_ptr, width, height, frames, n_chunks, wavelet_type, quality, qualities, frame_width,
+                           frame_height, origins, None, stream)
+    n = int(width) * int(height) * int(frames) * 3
+    return np.array([psnr_from_sse(int(s), n) for s in sse], dtype=np.float64)
+
+
+def _encode_container_to_psnr(kind: str, rgb_frames, width: int, height: int, frames: int, min_psnr, wavelet_type,
+                              min_quality: int, max_quality: int, lane_symbols: int) -> tuple:
+    lib = load_library()
+    r = _as_u8(rgb_frames)
+    _dims_u32(width, height, frames, lane_symbols)
+    _check_budget_args([0], min_quality, max_quality)
+    t = _check_min_psnr(min_psnr)
+    chosen = C.c_uint8(0); reached = C.c_uint8(0); db = C.c_double(0.0); n = C.c_uint64(0)
+    src = _p(r, _u8p) if r.size else C.cast(C.c_char_p(b""), _u8p)
+    ptr = lib.alice_codec_encode_to_psnr(_format_byte(kind), int(wavelet_type), src, r.size, width, height, frames, lane_symbols, t,
+                                         int(min_quality), int(max_quality), C.byref(chosen), C.byref(reached), C.byref(db),
+                                         C.byref(n))
+    if not ptr:
+        _raise_last()
+    try:
+        return _copy_out(ptr, n.value).tobytes(), int(chosen.value), bool(reached.value), float(db.value)
+    finally:
+        lib.alice_codec_data_free64(ptr, n.value)
+
+
+def _encode_container_to_psnr_device(kind: str, d_frames_ptr: int, width: int, height: int, frames: int, n_chunks: int, wavelet_type,
+                                     min_psnr, d_out_ptr: int, out_stride: int, min_quality: int, max_quality: int,
+                                     lane_symbols: int, frame_width: int, frame_height: int, origins, stream: int) -> tuple:
+    _check_budget_args([0], min_quality, max_quality)
+    t = _check_min_psnr(min_psnr)
+    _dims_u32(width, height, frames, n_chunks, lane_symbols, frame_width, frame_height)
+    o = None if origins is None else _origins_u32(origins, n_chunks)
+    m = max(n_chunks, 1)
+    chosen = np.zeros(m, np.uint8); reached = np.zeros(m, np.uint8); db = np.zeros(m, np.float64); sizes = np.zeros(m, np.uint64)
+    _check(load_library().alice_codec_dev_encode_to_psnr(_format_byte(kind), d_frames_ptr, frame_width, frame_height,
+                                                         None if o is None else _p(o, _u32p), width, height, frames, n_chunks,
+                                                         int(wavelet_type), lane_symbols, t, int(min_quality), int(max_quality),
+                                                         _p(chosen, _u8p), _p(reached, _u8p), _p(db, C.POINTER(C.c_double)),
+                                                         d_out_ptr, out_stride, _p(sizes, _u64p), stream or None))
+    return chosen[:n_chunks], reached[:n_chunks].astype(bool), db[:n_chunks], sizes[:n_chunks]
+
+
+def encode_split_to_psnr(rgb_frames, width: int, height: int, frames: int, min_psnr: float,
+                         wavelet_type: WaveletType = WaveletType.Cdf53, min_quality: int = 10, max_quality: int = 95,
+                         lane_symbols: int = 0) -> tuple:
+    """One chunk as version 2 bytes at the lowest quality in [min_quality, max_quality] whose measured PSNR is at least
+    min_psnr dB: the finest and the coarsest quantiser step of the range are tried, then bisection, at most eight exact
+    trials (a transform pair and a comparison each, no entropy coding).  Returns (bytes, quality, reached, psnr): reached is
+    False when not even max_quality reaches the floor (the chunk is then encoded at max_quality), psnr is the measured value
+    of the point returned.  The bytes are encode_split's at that quality.  Version 2 wraps at qualities 97 and above: keep
+    max_quality <= 96 or use encode_wide_to_psnr."""
+    return _encode_container_to_psnr("split", rgb_frames, width, height, frames, min_psnr, wavelet_type, min_quality, max_quality,
+                                     lane_symbols)
+
+
+def encode_wide_to_psnr(rgb_frames, width: int, height: int, frames: int, min_psnr: float,
+                        wavelet_type: WaveletType = WaveletType.Cdf53, min_quality: int = 10, max_quality: int = 95,
+                        lane_symbols: int = 0) -> tuple:
+    """encode_split_to_psnr for version 3: the bytes are encode_wide's at the returned quality."""
+    return _encode_container_to_psnr("wide", rgb_frames, width, height, frames, min_psnr, wavelet_type, min_quality, max_quality,
+                                     lane_symbols)
+
+
+def split_encode_to_psnr_device(d_frames_ptr: int, width: int, height: int, frames: int, n_chunks: int,
+                                wavelet_type: WaveletType, min_psnr: float, d_out_ptr: int, out_stride: int, min_quality: int = 10,
+                                max_quality: int = 95, lane_symbols: int = 0, frame_width: int = 0, frame_height: int = 0,
+                                origins=None, stream: int = 0) -> tuple:
+    """n_chunks device chunks (packed, or regions of frame_width x frame_height frames when origins is given), chunk i at
+    the quality encode_split_to_psnr's rule picks for it.  Returns (chosen, reached, psnr, sizes)."""
+    return _encode_container_to_psnr_device("split", d_frames_ptr, width, height, frames, n_chunks, wavelet_type, min_psnr, d_out_ptr,
+                                            out_stride, min_quality, max_quality, lane_symbols, frame_width, frame_height, origins,
+                                            stream)
+
+
+def wide_encode_to_psnr_device(d_frames_ptr: int, width: int, height: int, frames: int, n_chunks: int,
+                               wavelet_type: WaveletType, min_psnr: float, d_out_ptr: int, out_stride: int, min_quality: int = 10,
+                               max_quality: int = 95, lane_symbols: int = 0, frame_width: int = 0, frame_height: int = 0,
+                               origins=None, stream: int = 0) -> tuple:
+    """split_encode_to_psnr_device for version 3."""
+    return _encode_container_to_psnr_device("wide", d_frames_ptr, width, height, frames, n_chunks, wavelet_type, min_psnr, d_out_ptr,
+                                            out_stride, min_quality, max_quality, lane_symbols, frame_width, frame_height, origins,
+                                            stream)

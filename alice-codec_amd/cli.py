@@ -9,6 +9,10 @@ library has the version 3 budget encode, `encode_wide_to_size`; this front end d
 `--format reversible` the reversible container (.alc version 4, section 12: version 3 with the mirrored inverse, lossless at
 quality 100), and `--lossless` is short for `--format reversible --quality 100`; version 4 has no byte budget, so
 `--max-bytes` and `--kbps` are refused with it;
+`--min-psnr DB` (encode and encode-chunks, `--format split` or `--format wide` only) codes each chunk at
+the lowest quality in [--min-quality, --max-quality] whose measured PSNR reaches DB, and prints the chosen quality, the
+measured dB and whether the floor was reached per chunk; it is refused for the default format, for `reversible` /
+`--lossless`, and together with `--max-bytes` / `--kbps`;
 `decode` and `info` pick the format from the version byte unless `--format` names one.  The default of every subcommand
 is version 1.
 Like the reference it treats the whole input file as ONE chunk (src/bin/main.rs:117-122).  `encode-chunks`
@@ -23,7 +27,8 @@ import numpy as np
 
 from . import (DEFAULT_CHUNK_SIZE, CodecError, EncodedChunk, FrameDecoder, FrameEncoder, WaveletType, budget_bytes_per_chunk,
                alc_version, decode_reversible, decode_split, decode_wide, encode_many, encode_reversible, encode_split,
-               encode_split_to_size, encode_to_size, encode_wide, reversible_info, split_info, wide_info)
+               encode_split_to_psnr, encode_split_to_size, encode_to_size, encode_wide, encode_wide_to_psnr, reversible_info,
+               split_info, wide_info)
 
 WAVELETS = {"cdf53": WaveletType.Cdf53, "cdf97": WaveletType.Cdf97, "haar": WaveletType.Haar}
 WAVELET_NAMES = {WaveletType.Cdf53: "CDF 5/3", WaveletType.Cdf97: "CDF 9/7", WaveletType.Haar: "Haar"}
@@ -61,6 +66,37 @@ def _apply_lossless(a) -> None:
     a.format, a.quality = "reversible", 100
 
 
+NO_PSNR_FORMAT = ("--min-psnr needs --format split or --format wide: version 1 has no quality to control (its decoder desynchronises on "
+                  "almost all content)")
+NO_REVERSIBLE_PSNR = ("--min-psnr cannot be combined with {}: version 4 is the lossless container (quality 100 has no quality to "
+                      "search, and a lossy version 4 is not recommended); use --format wide or split for a PSNR floor")
+PSNR_AND_BUDGET = "--min-psnr and {} are two rate controls: give one of them"
+
+
+def _check_min_psnr(a, budget_flag: str, budget) -> None:
+    """The refusals of --min-psnr, before --lossless is applied and before the input is read."""
+    if a.min_psnr is None:
+        return
+    if a.lossless:
+        raise ValueError(NO_REVERSIBLE_PSNR.format("--lossless"))
+    if a.format == "reversible":
+        raise ValueError(NO_REVERSIBLE_PSNR.format("--format reversible"))
+    if a.format not in ("split", "wide"):
+        raise ValueError(NO_PSNR_FORMAT)
+    if budget is not None:
+        raise ValueError(PSNR_AND_BUDGET.format(budget_flag))
+    if a.min_psnr != a.min_psnr or a.min_psnr < 0:
+        raise ValueError("--min-psnr must be a number of dB >= 0 (inf for exact)")
+
+
+def _encode_to_psnr(a, wt, rgb, frames):
+    """One chunk under --min-psnr -> (bytes, the line that reports it)."""
+    fn = encode_split_to_psnr if a.format == "split" else encode_wide_to_psnr
+    data, quality, reached, db = fn(rgb, a.width, a.height, frames, a.min_psnr, wt, a.min_quality, a.max_quality, a.lane_symbols)
+    line = f"chosen quality: {quality}, measured {db:.2f} dB, floor {a.min_psnr:g} dB {'reached' if reached else 'NOT reached'}"
+    return data, quality, reached, line
+
+
 def _container_version(a, data) -> int:
     """The version a decode / info run treats the file as: the version byte, or the one --format names."""
     return alc_version(data) if a.format == "auto" else FORMAT_VERSION[a.format]
@@ -68,6 +104,7 @@ def _container_version(a, data) -> int:
 
 def cmd_encode(a) -> None:
     wt = parse_wavelet(a.wavelet)
+    _check_min_psnr(a, "--max-bytes", a.max_bytes)
     _apply_lossless(a)
     a.format = a.format or "v1"
     if a.format == "wide" and a.max_bytes is not None:
@@ -76,6 +113,17 @@ def cmd_encode(a) -> None:
         raise ValueError(NO_REVERSIBLE_BUDGET.format("--max-bytes"))
     rgb = np.fromfile(a.input, dtype=np.uint8)
     quality = a.quality
+    if a.min_psnr is not None:
+        data, quality, reached, line = _encode_to_psnr(a, wt, rgb, a.frames)
+        print(line, file=sys.stderr)
+        if not reached:
+            print(f"warning: not even --max-quality {a.max_quality} reaches {a.min_psnr:g} dB; encoded at {quality}", file=sys.stderr)
+        with open(a.output, "wb") as f:
+            f.write(data)
+        ratio = 0.0 if rgb.size == 0 else len(data) / rgb.size
+        print(f"encoded {a.width}x{a.height}x{a.frames} ({rgb.size} bytes) -> {len(data)} bytes "
+              f"({ratio * 100:.1f}% ratio, quality={quality}, wavelet={a.wavelet}, format={a.format})", file=sys.stderr)
+        return
     if a.format in ("wide", "reversible"):
         encode_one = encode_reversible if a.format == "reversible" else encode_wide
         data = encode_one(FrameEncoder.with_wavelet(a.quality, wt), rgb, a.width, a.height, a.frames, a.lane_symbols)
@@ -119,6 +167,7 @@ def cmd_encode(a) -> None:
 
 def cmd_encode_chunks(a) -> None:
     wt = parse_wavelet(a.wavelet)
+    _check_min_psnr(a, "--kbps", a.kbps)
     _apply_lossless(a)
     a.format = a.format or "v1"
     if a.format == "wide" and a.kbps is not None:
@@ -135,6 +184,14 @@ def cmd_encode_chunks(a) -> None:
         return
     enc = FrameEncoder.with_wavelet(a.quality, wt)
     starts = list(range(0, n_frames, a.chunk))
+    if a.min_psnr is not None:   # one chunk uses the whole device: chunk after chunk
+        for k, s0 in enumerate(starts):
+            f = min(a.chunk, n_frames - s0)
+            data, _, _, line = _encode_to_psnr(a, wt, np.ascontiguousarray(rgb[s0 * frame_bytes:(s0 + f) * frame_bytes]), f)
+            with open(f"{a.output}.{k:05d}.alc", "wb") as out:
+                out.write(data)
+            print(f"chunk {k}: frames {s0}..{s0 + f - 1} -> {len(data)} bytes, {line}", file=sys.stderr)
+        return
     if a.format in ("split", "wide", "reversible"):   # one chunk uses the whole device: chunk after chunk
         encode_one = {"split": encode_split, "wide": encode_wide, "reversible": encode_reversible}[a.format]
         for k, s0 in enumerate(starts):
@@ -269,6 +326,8 @@ def main(argv=None) -> int:
         else:
             e.add_argument("--kbps", type=int, default=None, help="target bitrate: a byte budget per chunk (with --fps)")
             e.add_argument("--fps", type=float, default=30.0)
+        e.add_argument("--min-psnr", type=float, default=None, metavar="DB",
+                       help="--format split / wide: the lowest quality in [--min-quality, --max-quality] whose measured PSNR is at least DB")
         e.add_argument("--format", choices=("v1", "split", "wide", "reversible"), default=None,
                        help="v1 (default): the reference's bitstream; split: .alc version 2; wide: .alc version 3 (untruncated symbols, for "
                             "the top qualities); reversible: .alc version 4 (version 3 with the mirrored inverse: lossless at quality 100)")

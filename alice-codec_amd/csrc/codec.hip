@@ -1812,11 +1812,7 @@ double alice_codec_psnr(const uint8_t* a, const uint8_t* b, uint32_t len) {
     launch_sq_diff_sum(da.as<uint8_t>(), db.as<uint8_t>(), len, ds.as<unsigned long long>(), st);
     if (hipMemcpyAsync(&sum, ds.p, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess) { fail(kDeviceError, "psnr kernel failed"); return -1.0; }
-    // the reference sums squared differences in f64; every partial sum is an integer < 2^53, so the
-    // integer total converts to the same f64 (src/metrics.rs:26-34)
-    const double mse = (double)sum / (double)len;
-    if (mse == 0.0) return INFINITY;
-    return 10.0 * log10(255.0 * 255.0 / mse);
+    return alice_codec_psnr_from_sse(sum, len);   // one expression for every dB value the library reports
 }
 
 void alice_codec_data_free64(uint8_t* ptr, uint64_t len) { (void)len; if (ptr) free(ptr); }
@@ -4416,6 +4412,336 @@ uint32_t alice_codec_test_last_split_trials(uint32_t* per_chunk, uint32_t cap) {
     const uint32_t n = (uint32_t)tl_split_trials.size();
     for (uint32_t i = 0; i < n && i < cap && per_chunk; ++i) per_chunk[i] = tl_split_trials[i];
     return n;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// PART 5: quality control (kernel: quality.hip)
+//
+// The lane coders of versions 2 to 4 are lossless, so a decode returns inverse_chunk(forward_chunk(q)): a trial is that
+// transform pair into pool scratch plus launch_rgb_sse against the source.  Nothing here touches split.hip or the chain hub.
+// ------------------------------------------------------------------------------------------
+
+namespace {
+
+static_assert(ALICE_QUALITY_MAX_TRIALS == 8, "2 + ceil(log2(63)) trials for the 64 steps");
+thread_local std::vector<uint32_t> tl_quality_trials;   // alice_codec_test_last_quality_trials
+
+int check_format_byte(uint8_t format, SplitFormat* fmt) {
+    if (format < 2 || format > 4) return fail(kInvalidBitstream, "unknown format byte: " + std::to_string((int)format) + " (2, 3 or 4)");
+    *fmt = format_of_version(format);
+    return kOk;
+}
+
+int check_searchable_format(uint8_t format, SplitFormat* fmt) {
+    TRY(check_format_byte(format, fmt));
+    if (*fmt == kFormatReversible)
+        return fail(kInvalidBitstream, "version 4 is the lossless container (quality 100 has no quality to search, and a lossy version 4 is "
+                                       "not recommended); use version 3 or 2 for a PSNR floor");
+    return kOk;
+}
+
+int check_min_psnr(double t) {
+    if (std::isnan(t) || t < 0.0) return fail(kInvalidDimensions, "min_psnr_db must be a number >= 0 (or +inf for exact)");
+    return kOk;
+}
+
+// Buffers of the trials of up to B equal-shaped chunks; one set serves every trial of a call.
+struct TrialWork {
+    EncodeWork ew;
+    DecodeWork dw;
+    DevBuf recon, fs;   // one chunk of reconstructed pixels; [B][f] u64 when the caller lends none
+    uint32_t B = 0;
+    SplitFormat fmt = kFormatSplit;
+};
+
+int trial_alloc(TrialWork& t, const ChunkDims& d, uint32_t B, SplitFormat fmt, bool own_frame_sse) {
+    t.B = B; t.fmt = fmt;
+    const size_t sb = is_wide(fmt) ? 2 : 1;
+    t.ew.d = d; t.ew.n_chunks = (int)B;
+    t.dw.d = d; t.dw.n_chunks = 1;
+    if (transform_tiles_eligible(d)) {
+        TRY(t.ew.scratch.alloc(forward_scratch_bytes(d)));
+        // one set of buffers serves trials at any step, and the inverse plans its bands by the sample width the step allows
+        // (inverse_bounds().mid16): a chunk the i32 plan cuts into bands may stay whole in the i16 plan, whose slot is then
+        // the larger of the two.  The slot has to hold either.
+        TRY(t.dw.scratch_own.alloc(std::max(inverse_scratch_bytes(d, false), inverse_scratch_bytes(d, true))));
+    }
+    TRY(t.ew.sym.alloc((size_t)B * 3 * d.padded * sb));
+    TRY(t.ew.hist.alloc((size_t)B * 3 * 256 * sizeof(uint32_t)));
+    TRY(t.recon.alloc(d.n_pixels * 3));
+    if (own_frame_sse) TRY(t.fs.alloc((size_t)B * d.f * sizeof(unsigned long long)));
+    return kOk;
+}
+
+// n <= t.B chunks at rgb[i], chunk i at q[i]: sse[i] on the host; d_frame_sse (device, [n][f]; null: t.fs) receives the
+// per-frame sums.  Returns after the stream has drained.
+int trial_run(TrialWork& t, const RgbLayout* rgb, uint32_t n, uint8_t wavelet, const uint8_t* q, hipStream_t st, uint64_t* sse,
+              unsigned long long* d_frame_sse) {
+    const ChunkDims& d = t.ew.d;
+    const bool wide = is_wide(t.fmt);
+    const size_t sb = wide ? 2 : 1;
+    unsigned long long* fs = d_frame_sse ? d_frame_sse : t.fs.as<unsigned long long>();
+    HIP_TRY(hipMemsetAsync(t.ew.hist.p, 0, (size_t)n * 3 * 256 * sizeof(uint32_t), st));
+    for (uint32_t i = 0; i < n; ++i)
+        TRY(forward_chunk(rgb[i], d, wavelet, quality_to_step(q[i]), t.ew, t.ew.sym.as<uint8_t>() + (size_t)i * 3 * d.padded * sb,
+                          t.ew.hist.as<uint32_t>() + (size_t)i * 3 * 256, st, wide));
+    const RgbLayout recon = packed_rgb(t.recon.p, d);
+    for (uint32_t i = 0; i < n; ++i) {
+        const int32_t s = quality_to_step(q[i]);
+        const int32_t step[3] = {s, s, s};   // what the encoder writes into the three channel headers
+        TRY(inverse_chunk(t.ew.sym.as<uint8_t>() + (size_t)i * 3 * d.padded * sb, d, wavelet, step, t.dw.scratch_own.p, t.dw, recon, st, t.fmt));
+        HIP_TRY(launch_rgb_sse(rgb[i], recon, d.w, d.h, d.f, fs + (size_t)i * d.f, st));
+    }
+    HIP_TRY(hipGetLastError());
+    std::vector<unsigned long long> host((size_t)n * d.f);
+    TRY(copy_to_host(host.data(), fs, host.size() * sizeof(unsigned long long), st));
+    for (uint32_t i = 0; i < n; ++i) {
+        uint64_t tot = 0;
+        for (uint32_t k = 0; k < d.f; ++k) tot += host[(size_t)i * d.f + k];
+        sse[i] = tot;
+    }
+    return kOk;
+}
+
+// floor(65025 N / 10^(T / 10)) in f64; 0 for T = +inf (and wherever the power overflows to it)
+uint64_t quality_sse_max(double t, uint64_t n_bytes) {
+    const double v = floor(65025.0 * (double)n_bytes / pow(10.0, t / 10.0));
+    return v >= 18446744073709551615.0 ? UINT64_MAX : (uint64_t)v;
+}
+
+// The rule of alice_codec_encode_to_psnr for one chunk; trial(q, &sse) measures one step.
+template <typename Trial>
+int quality_choose(uint64_t n_bytes, double min_psnr, uint8_t min_q, uint8_t max_q, Trial trial, uint8_t* chosen, uint8_t* reached,
+                   uint64_t* chosen_sse, uint32_t* trials) {
+    min_q = std::min<uint8_t>(min_q, 100); max_q = std::min<uint8_t>(max_q, 100);
+    const uint64_t sse_max = quality_sse_max(min_psnr, n_bytes);
+    uint8_t cand[kQualities];   // coarsest first: the lowest quality of every distinct step in the range
+    int n = 0;
+    for (int q = min_q; q <= max_q; ++q)
+        if (!n || quality_to_step((uint8_t)q) != quality_to_step(cand[n - 1])) cand[n++] = (uint8_t)q;
+    *trials = 0;
+    auto run = [&](int k, uint64_t* sse) -> int { ++*trials; return trial(cand[k], sse); };
+    uint64_t s_fine = 0, s = 0;
+    TRY(run(n - 1, &s_fine));
+    if (s_fine > sse_max) { *chosen = max_q; *reached = 0; *chosen_sse = s_fine; return kOk; }
+    *reached = 1;
+    if (n == 1) { *chosen = cand[0]; *chosen_sse = s_fine; return kOk; }
+    TRY(run(0, &s));
+    if (s <= sse_max) { *chosen = cand[0]; *chosen_sse = s; return kOk; }
+    int lo = 0, hi = n - 1;   // lo fails, hi passes
+    uint64_t s_hi = s_fine;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi + 1) / 2;
+        TRY(run(mid, &s));
+        if (s <= sse_max) { hi = mid; s_hi = s; } else lo = mid;
+    }
+    *chosen = cand[hi]; *chosen_sse = s_hi;
+    return kOk;
+}
+
+int quality_choose_chunks(const RgbLayout* rgb, uint32_t n, const ChunkDims& d, uint8_t wavelet, double min_psnr, uint8_t min_q,
+                          uint8_t max_q, uint8_t* chosen, uint8_t* reached, double* psnr, hipStream_t st, SplitFormat fmt) {
+    tl_quality_trials.assign(n, 0u);
+    TrialWork t;
+    TRY(trial_alloc(t, d, 1, fmt, true));
+    for (uint32_t k = 0; k < n; ++k) {
+        uint64_t sse = 0;
+        TRY(quality_choose(d.n_pixels * 3, min_psnr, min_q, max_q,
+                           [&](uint8_t q, uint64_t* out) -> int { return trial_run(t, rgb + k, 1, wavelet, &q, st, out, nullptr); },
+                           chosen + k, reached + k, &sse, &tl_quality_trials[k]));
+        psnr[k] = alice_codec_psnr_from_sse(sse, d.n_pixels * 3);
+    }
+    return kOk;
+}
+
+}  // namespace
+
+extern "C" {
+
+double alice_codec_psnr_from_sse(uint64_t sse, uint64_t n_bytes) {
+    // the reference sums squared differences in f64; every partial sum is an integer < 2^53, so the
+    // integer total converts to the same f64 (src/metrics.rs:26-34)
+    if (n_bytes == 0) return INFINITY;  // mse 0.0 for empty buffers (src/metrics.rs:23-25)
+    const double mse = (double)sse / (double)n_bytes;
+    if (mse == 0.0) return INFINITY;
+    return 10.0 * log10(255.0 * 255.0 / mse);
+}
+
+int alice_codec_dev_rgb_sse(const void* d_a, uint64_t a_row_pitch, uint64_t a_frame_pitch, const void* d_b, uint64_t b_row_pitch,
+                            uint64_t b_frame_pitch, uint32_t width, uint32_t height, uint64_t n_frames, void* d_frame_sse,
+                            void* hip_stream) {
+    clear_error();
+    if (!d_a || !d_b || !d_frame_sse) return fail(kNullArgument, "null argument");
+    uint64_t n_pixels = 0;
+    TRY(checked_pixel_count(width, height, n_frames, &n_pixels));
+    if (n_pixels == 0) return fail(kInvalidDimensions, "invalid dimensions");
+    if (n_pixels > UINT64_MAX / 3) return fail(kDimensionOverflow, "dimensions overflow usize");
+    const uint64_t row = 3ull * width;
+    const uint64_t rp[2] = {a_row_pitch, b_row_pitch}, fp[2] = {a_frame_pitch, b_frame_pitch};
+    for (int s = 0; s < 2; ++s) {
+        const char* side = s ? "b" : "a";
+        if (rp[s] < row) return fail(kInvalidDimensions, std::string("row pitch of ") + side + " is below the " + std::to_string(row) + " bytes of a row");
+        const unsigned __int128 span = (unsigned __int128)(height - 1) * rp[s] + row;
+        if (fp[s] < span) return fail(kInvalidDimensions, std::string("frame pitch of ") + side + " is below the bytes its rows span");
+        if ((unsigned __int128)(n_frames - 1) * fp[s] + span > UINT64_MAX) return fail(kDimensionOverflow, "dimensions overflow usize");
+    }
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    HIP_TRY(launch_rgb_sse(RgbLayout{(uint8_t*)d_a, a_row_pitch, a_frame_pitch}, RgbLayout{(uint8_t*)d_b, b_row_pitch, b_frame_pitch}, width,
+                           height, n_frames, (unsigned long long*)d_frame_sse, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return kOk;
+}
+
+int alice_codec_dev_trial_sse(uint8_t format, const void* d_frames, uint32_t frame_width, uint32_t frame_height, const uint32_t* origins,
+                              uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks, uint8_t wavelet_type, uint8_t quality,
+                              const uint8_t* qualities, uint64_t* sse, void* d_frame_sse, void* hip_stream) {
+    clear_error();
+    if (!d_frames || !sse) return fail(kNullArgument, "null argument");
+    SplitFormat fmt;
+    TRY(check_format_byte(format, &fmt));
+    ChunkDims d{};
+    TRY(chunk_dims(width, height, frames, &d, n_chunks));
+    std::vector<RgbLayout> layouts;
+    TRY(split_layouts(d_frames, frame_width, frame_height, origins, d, n_chunks, layouts));
+    if (wavelet_type > 2) return fail(kInvalidBitstream, "unknown wavelet type");
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);
+    std::vector<uint8_t> q(n_chunks);
+    for (uint32_t i = 0; i < n_chunks; ++i) q[i] = qualities ? qualities[i] : quality;
+    std::vector<uint64_t> out(n_chunks);
+    const uint32_t group = split_group(d, fmt);
+    TrialWork t;
+    TRY(trial_alloc(t, d, std::min(group, n_chunks), fmt, d_frame_sse == nullptr));
+    for (uint32_t first = 0; first < n_chunks; first += group) {
+        const uint32_t B = std::min(group, n_chunks - first);
+        TRY(trial_run(t, layouts.data() + first, B, wavelet_type, q.data() + first, st, out.data() + first,
+                      d_frame_sse ? (unsigned long long*)d_frame_sse + (size_t)first * d.f : nullptr));
+    }
+    for (uint32_t i = 0; i < n_chunks; ++i) sse[i] = out[i];
+    return kOk;
+}
+
+int alice_codec_dev_encode_to_psnr(uint8_t format, const void* d_frames, uint32_t frame_width, uint32_t frame_height,
+                                   const uint32_t* origins, uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks,
+                                   uint8_t wavelet_type, uint32_t lane_symbols, double min_psnr_db, uint8_t min_q, uint8_t max_q,
+                                   uint8_t* chosen, uint8_t* reached, double* psnr, void* d_out, uint64_t out_stride, uint64_t* sizes,
+                                   void* hip_stream) {
+    clear_error();
+    if (!d_frames || !chosen || !reached || !psnr || !d_out || !sizes) return fail(kNullArgument, "null argument");
+    SplitFormat fmt;
+    TRY(check_searchable_format(format, &fmt));
+    ChunkDims d{};
+    TRY(chunk_dims(width, height, frames, &d, n_chunks));
+    std::vector<RgbLayout> layouts;
+    TRY(split_layouts(d_frames, frame_width, frame_height, origins, d, n_chunks, layouts));
+    uint32_t L = 0;
+    TRY(check_split_args(wavelet_type, lane_symbols, &L, fmt));
+    TRY(check_quality_range(min_q, max_q));
+    TRY(check_min_psnr(min_psnr_db));
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);
+    // the choices reach the caller only with the bytes: a failed call leaves the outputs as they were
+    std::vector<uint8_t> q(n_chunks), ok(n_chunks);
+    std::vector<double> db(n_chunks);
+    std::vector<uint64_t> sz(n_chunks);
+    TRY(quality_choose_chunks(layouts.data(), n_chunks, d, wavelet_type, min_psnr_db, min_q, max_q, q.data(), ok.data(), db.data(), st, fmt));
+    TRY(split_encode_layouts(layouts.data(), n_chunks, d, wavelet_type, q.data(), L, d_out, out_stride, sz.data(), st, fmt));
+    for (uint32_t i = 0; i < n_chunks; ++i) { chosen[i] = q[i]; reached[i] = ok[i]; psnr[i] = db[i]; sizes[i] = sz[i]; }
+    return kOk;
+}
+
+uint8_t* alice_codec_encode_to_psnr(uint8_t format, uint8_t wavelet_type, const uint8_t* rgb, uint64_t rgb_len, uint32_t width,
+                                    uint32_t height, uint32_t frames, uint32_t lane_symbols, double min_psnr_db, uint8_t min_q,
+                                    uint8_t max_q, uint8_t* chosen_q, uint8_t* reached, double* psnr, uint64_t* out_len) {
+    clear_error();
+    if (!chosen_q || !reached || !psnr || !out_len || (!rgb && rgb_len)) { fail(kNullArgument, "null argument"); return nullptr; }
+    auto run = [&](uint8_t** out) -> int {
+        SplitFormat fmt;
+        TRY(check_searchable_format(format, &fmt));
+        uint64_t n_pixels = 0;
+        TRY(checked_pixel_count(width, height, frames, &n_pixels));
+        if (n_pixels == 0 && rgb_len != 0) return fail(kInvalidBufferSize, "buffer size mismatch: expected 0, got " + std::to_string(rgb_len));
+        const FrameEncoder enc{0, wavelet_type};
+        ChunkDims d{};
+        EncodedChunk* none = nullptr;
+        if (n_pixels) TRY(validate_encode_many(&enc, rgb, rgb_len, width, height, frames, 1, &none, &d));
+        uint32_t L = 0;
+        TRY(check_split_args(wavelet_type, lane_symbols, &L, fmt));
+        TRY(check_quality_range(min_q, max_q));
+        TRY(check_min_psnr(min_psnr_db));
+        uint8_t q = 0, ok = 0;
+        if (n_pixels == 0) {   // no sample differs at any step
+            uint64_t sse = 0;
+            tl_quality_trials.assign(1, 0u);
+            TRY(quality_choose(0, min_psnr_db, min_q, max_q, [](uint8_t, uint64_t* s) -> int { *s = 0; return kOk; }, &q, &ok, &sse,
+                               &tl_quality_trials[0]));
+            *out = host_result_alloc(kSplitHeaderBytes);
+            if (!*out) return fail(kOutOfMemory, "out of host memory");
+            write_empty_split(*out, wavelet_type, width, height, frames, L, quality_to_step(q), format_version(fmt));
+            *out_len = kSplitHeaderBytes;
+            *chosen_q = q; *reached = ok; *psnr = alice_codec_psnr_from_sse(0, 0);
+            return kOk;
+        }
+        hipStream_t st;
+        TRY(get_stream(&st));
+        DevBuf d_rgb, d_out;
+        TRY(d_rgb.alloc(n_pixels * 3));
+        HIP_TRY(hipMemcpyAsync(d_rgb.p, rgb, n_pixels * 3, hipMemcpyHostToDevice, st));
+        const RgbLayout layout = packed_rgb(d_rgb.p, d);
+        double db = 0.0;
+        TRY(quality_choose_chunks(&layout, 1, d, wavelet_type, min_psnr_db, min_q, max_q, &q, &ok, &db, st, fmt));
+        std::vector<uint64_t> sizes;
+        TRY(split_encode_chunks(&layout, 1, d, wavelet_type, &q, L, st, sizes,
+                                [&](const std::vector<uint64_t>& sz, std::vector<uint8_t*>& outs) -> int {
+                                    TRY(d_out.alloc(sz[0]));
+                                    outs[0] = d_out.as<uint8_t>();
+                                    return kOk;
+                                }, fmt));
+        *out = host_result_alloc(sizes[0]);
+        if (!*out) return fail(kOutOfMemory, "out of host memory");
+        const int rc = copy_to_host(*out, d_out.p, sizes[0], st);
+        if (rc != kOk) { free(*out); *out = nullptr; return rc; }
+        *out_len = sizes[0];
+        *chosen_q = q; *reached = ok; *psnr = db;
+        return kOk;
+    };
+    uint8_t* out = nullptr;
+    return run(&out) == kOk ? out : nullptr;
+}
+
+uint32_t alice_codec_test_last_quality_trials(uint32_t* per_chunk, uint32_t cap) {
+    const uint32_t n = (uint32_t)tl_quality_trials.size();
+    for (uint32_t i = 0; i < n && i < cap && per_chunk; ++i) per_chunk[i] = tl_quality_trials[i];
+    return n;
+}
+
+uint64_t alice_codec_test_inverse_scratch_bytes(uint32_t width, uint32_t height, uint32_t frames, int mid16) {
+    clear_error();
+    ChunkDims d{};
+    if (chunk_dims(width, height, frames, &d) != kOk || !transform_tiles_eligible(d)) return 0;
+    return inverse_scratch_bytes(d, mid16 != 0);
+}
+
+int alice_codec_test_sq_diff_sum(const void* d_a, const void* d_b, uint64_t n, uint64_t* sse, void* hip_stream) {
+    clear_error();
+    if (!d_a || !d_b || !sse) return fail(kNullArgument, "null argument");
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);
+    DevBuf ds;
+    TRY(ds.alloc(8));
+    HIP_TRY(hipMemsetAsync(ds.p, 0, 8, st));
+    if (n) launch_sq_diff_sum((const uint8_t*)d_a, (const uint8_t*)d_b, n, ds.as<unsigned long long>(), st);
+    HIP_TRY(hipGetLastError());
+    unsigned long long v = 0;
+    TRY(copy_to_host(&v, ds.p, 8, st));
+    *sse = v;
+    return kOk;
 }
 
 }  // extern "C"

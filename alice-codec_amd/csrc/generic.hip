@@ -106,6 +106,7 @@ static unsigned grid_for(unsigned long long items) {
     if (g > cap) g = cap;
     return (unsigned)g;
 }
+unsigned generic_grid_for(unsigned long long items) { return grid_for(items); }
 
 void launch_wavelet_axis(int32_t* d_data, int32_t* d_tmp, uint64_t n, uint64_t stride_k, uint64_t n_a,
                          uint64_t stride_a, uint64_t n_b, uint64_t stride_b, int wavelet, bool inverse,

@@ -189,6 +189,8 @@ void launch_stage_wavelet(int32_t* d_data, int32_t* d_tmp, uint64_t w, uint64_t 
 // Cap on the workgroups of the launches sized per item (grid_for in generic.hip); 0 restores the default, 65535 * 4.  The
 // launches that clamp further (to 2048) still do.  Process-wide; tests only.
 void set_generic_grid_cap(uint32_t max_blocks);
+// grid_for for the launches outside generic.hip that are sized per item and obey the same cap (quality.hip)
+unsigned generic_grid_for(unsigned long long items);
 void launch_wavelet_axis(int32_t* d_data, int32_t* d_tmp, uint64_t n, uint64_t stride_k, uint64_t n_a,
                          uint64_t stride_a, uint64_t n_b, uint64_t stride_b, int wavelet, bool inverse,
                          hipStream_t st, bool mirror = false);   // mirror (inverse only): the mirrored inverse of .alc v4
@@ -334,5 +336,24 @@ void launch_split_header_version(const SplitHeaderDesc* d_descs, int n_chunks, u
 void launch_split_wide_count(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, hipStream_t st);
 void launch_split_wide_write(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, hipStream_t st);
 void launch_split_wide_decode(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, hipStream_t st);
+
+// ---- quality.hip: exact squared error of two RGB volumes ----
+constexpr uint32_t kSseBlock = 256;               // lanes of a workgroup
+constexpr uint32_t kSseVectorsPerLane = 8;        // 16-byte windows a lane takes per virtual block (256 * 8 windows = 32 KiB a side)
+// 16-byte windows a lane may hold in its u32 sums before it folds them into its u64: each byte adds at most 255^2 = 65 025
+// to a sum, and 4128 * 16 * 65 025 = 4 294 771 200 < 2^32, while the next multiple of kSseVectorsPerLane (4136 windows) would not.  A
+// multiple of kSseVectorsPerLane.
+constexpr uint32_t kSseLaneFlushVectors = 4128;
+constexpr uint32_t kSseMaxBlocks = 2048;          // workgroups of a launch at most (256 CUs x 8), below grid_for's cap
+static_assert(kSseLaneFlushVectors % kSseVectorsPerLane == 0, "the fold is checked once per virtual block");
+static_assert(16ull * 65025ull * kSseLaneFlushVectors < (1ull << 32), "a lane's u32 sums must hold kSseLaneFlushVectors windows");
+static_assert(16ull * 65025ull * (kSseLaneFlushVectors + kSseVectorsPerLane) >= (1ull << 32), "the limit is the last that fits: the tests rely on it");
+// one run of 3wh bytes per frame (both sides keep their rows back to back, or there is one row) instead of h runs of 3w
+bool rgb_sse_flat(const RgbLayout& a, const RgbLayout& b, uint64_t w, uint64_t h);
+// d_frame_sse[k] = sum over the w x h pixels of frame k of (a - b)^2, all three colours; zeroed here.  Bases of any byte
+// alignment, pitches >= the bytes they span (the caller checks); reads exactly the w x h x n_frames pixels of each side.
+// Returns the status of zeroing and launching; on an error nothing was launched.
+hipError_t launch_rgb_sse(const RgbLayout& a, const RgbLayout& b, uint64_t w, uint64_t h, uint64_t n_frames,
+                          unsigned long long* d_frame_sse, hipStream_t st);
 
 }  // namespace alice

@@ -1058,3 +1058,176 @@ pub unsafe fn reversible_decode_regions_device(d_alc: *const std::ffi::c_void, a
     check(alice_codec_dev_decode_reversible_regions(d_alc, alc_stride, sizes.as_ptr(), sizes.len() as u32, d_frames_out, frame_width,
                                                     frame_height, flat.as_ptr(), hip_stream), 0, 0)
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// quality control: exact trial distortion and PSNR-floor encodes.  The lane coders of versions 2 to 4
+// are lossless, so the distortion of an encode is that of a transform pair: a trial runs the format's forward pass and the
+// format's inverse on the device and compares the pixels with the source, without a byte of a container.
+// ---------------------------------------------------------------------------------------------------------------
+
+#[link(name = "alice_codec")]
+extern "C" {
+    fn alice_codec_dev_rgb_sse(d_a: *const std::ffi::c_void, a_row_pitch: u64, a_frame_pitch: u64, d_b: *const std::ffi::c_void,
+                               b_row_pitch: u64, b_frame_pitch: u64, w: u32, h: u32, n_frames: u64,
+                               d_frame_sse: *mut std::ffi::c_void, hip_stream: *mut std::ffi::c_void) -> c_int;
+    fn alice_codec_dev_trial_sse(format: u8, d_frames: *const std::ffi::c_void, frame_width: u32, frame_height: u32,
+                                 origins: *const u32, w: u32, h: u32, f: u32, n_chunks: u32, wavelet: u8, quality: u8,
+                                 qualities: *const u8, sse: *mut u64, d_frame_sse: *mut std::ffi::c_void,
+                                 hip_stream: *mut std::ffi::c_void) -> c_int;
+    fn alice_codec_psnr_from_sse(sse: u64, n_bytes: u64) -> f64;
+    fn alice_codec_dev_encode_to_psnr(format: u8, d_frames: *const std::ffi::c_void, frame_width: u32, frame_height: u32,
+                                      origins: *const u32, w: u32, h: u32, f: u32, n_chunks: u32, wavelet: u8, lane_symbols: u32,
+                                      min_psnr_db: f64, min_q: u8, max_q: u8, chosen: *mut u8, reached: *mut u8, psnr: *mut f64,
+                                      d_out: *mut std::ffi::c_void, out_stride: u64, sizes: *mut u64,
+                                      hip_stream: *mut std::ffi::c_void) -> c_int;
+    fn alice_codec_encode_to_psnr(format: u8, wavelet: u8, rgb: *const u8, rgb_len: u64, w: u32, h: u32, f: u32, lane_symbols: u32,
+                                  min_psnr_db: f64, min_q: u8, max_q: u8, chosen_q: *mut u8, reached: *mut u8, psnr: *mut f64,
+                                  out_len: *mut u64) -> *mut u8;
+}
+
+/// The container of a quality call, by its version byte.
+#[repr(u8)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum ContainerFormat { Split = 2, Wide = 3, Reversible = 4 }
+
+pub const QUALITY_MAX_TRIALS: u32 = 8;
+
+/// The dB value of a squared error over `n_bytes` samples, by the expression `psnr` uses: infinite at 0.
+pub fn psnr_from_sse(sse: u64, n_bytes: u64) -> f64 { unsafe { alice_codec_psnr_from_sse(sse, n_bytes) } }
+
+/// Exact squared error per frame of two device volumes of `n_frames` frames of `width` x `height` interleaved RGB; the
+/// `n_frames` u64 sums land at `d_frame_sse`.  A side's pitches are `(row_pitch, frame_pitch)` in bytes, `None` for packed.
+///
+/// # Safety
+/// `d_a` / `d_b` (any byte alignment) must hold the pixels their pitches name, `d_frame_sse` `n_frames` u64, all on the device.
+pub unsafe fn rgb_sse_device(d_a: *const std::ffi::c_void, a_pitches: Option<(u64, u64)>, d_b: *const std::ffi::c_void,
+                             b_pitches: Option<(u64, u64)>, width: u32, height: u32, n_frames: u64,
+                             d_frame_sse: *mut std::ffi::c_void, hip_stream: *mut std::ffi::c_void) -> Result<(), CodecError> {
+    let packed = (3 * width as u64, 3 * width as u64 * height as u64);
+    let (a, b) = (a_pitches.unwrap_or(packed), b_pitches.unwrap_or(packed));
+    check(alice_codec_dev_rgb_sse(d_a, a.0, a.1, d_b, b.0, b.1, width, height, n_frames, d_frame_sse, hip_stream), 0, 0)
+}
+
+/// The squared error, per chunk, between the source and what the format's decode returns for the format's encode (chunk i at
+/// `qualities[i]` when given, else all at `quality`).  Packed chunks when `origins` is `None`, else regions of the
+/// `frame_width` x `frame_height` frames.  `d_frame_sse`: null, or device memory for `n_chunks * frames` u64.
+///
+/// # Safety
+/// `d_frames` must hold the chunks (or the frames the regions lie in) on the device.
+pub unsafe fn trial_sse_device(format: ContainerFormat, d_frames: *const std::ffi::c_void, frame_width: u32, frame_height: u32,
+                               origins: Option<&[(u32, u32)]>, width: u32, height: u32, frames: u32, n_chunks: u32,
+                               wavelet_type: WaveletType, quality: u8, qualities: Option<&[u8]>,
+                               d_frame_sse: *mut std::ffi::c_void, hip_stream: *mut std::ffi::c_void)
+    -> Result<Vec<u64>, CodecError> {
+    let n = n_chunks as usize;
+    if let Some(q) = qualities {
+        if q.len() != n { return Err(CodecError::InvalidBufferSize { expected: n, got: q.len() }); }
+    }
+    if let Some(o) = origins {
+        if o.len() != n { return Err(CodecError::InvalidBufferSize { expected: n, got: o.len() }); }
+    }
+    let flat: Option<Vec<u32>> = origins.map(|o| o.iter().flat_map(|&(x, y)| [x, y]).collect());
+    let mut sse = vec![0u64; n.max(1)];
+    let rc = alice_codec_dev_trial_sse(format as u8, d_frames, frame_width, frame_height,
+                                       flat.as_ref().map_or(std::ptr::null(), |o| o.as_ptr()), width, height, frames, n_chunks,
+                                       wavelet_type as u8, quality, qualities.map_or(std::ptr::null(), |q| q.as_ptr()),
+                                       sse.as_mut_ptr(), d_frame_sse, hip_stream);
+    sse.truncate(n);
+    check(rc, 0, 0).map(|_| sse)
+}
+
+/// `trial_sse_device` as dB per chunk.
+///
+/// # Safety
+/// As `trial_sse_device`.
+pub unsafe fn trial_psnr_device(format: ContainerFormat, d_frames: *const std::ffi::c_void, frame_width: u32, frame_height: u32,
+                                origins: Option<&[(u32, u32)]>, width: u32, height: u32, frames: u32, n_chunks: u32,
+                                wavelet_type: WaveletType, quality: u8, qualities: Option<&[u8]>,
+                                hip_stream: *mut std::ffi::c_void) -> Result<Vec<f64>, CodecError> {
+    let n_bytes = 3 * width as u64 * height as u64 * frames as u64;
+    trial_sse_device(format, d_frames, frame_width, frame_height, origins, width, height, frames, n_chunks, wavelet_type, quality,
+                     qualities, std::ptr::null_mut(), hip_stream)
+        .map(|sse| sse.into_iter().map(|s| psnr_from_sse(s, n_bytes)).collect())
+}
+
+fn encode_to_psnr(format: ContainerFormat, rgb_frames: &[u8], width: u32, height: u32, frames: u32, min_psnr: f64,
+                  wavelet_type: WaveletType, min_quality: u8, max_quality: u8, lane_symbols: u32)
+    -> Result<(Vec<u8>, u8, bool, f64), CodecError> {
+    let (mut q, mut reached, mut db, mut n) = (0u8, 0u8, 0f64, 0u64);
+    unsafe {
+        let p = alice_codec_encode_to_psnr(format as u8, wavelet_type as u8, rgb_frames.as_ptr(), rgb_frames.len() as u64, width,
+                                           height, frames, lane_symbols, min_psnr, min_quality, max_quality, &mut q, &mut reached,
+                                           &mut db, &mut n);
+        if p.is_null() {
+            let expected = (width as usize).saturating_mul(height as usize).saturating_mul(frames as usize).saturating_mul(3);
+            return Err(last_error(expected, rgb_frames.len(), width, height, 0));
+        }
+        Ok((take(p, n), q, reached != 0, db))
+    }
+}
+
+/// One chunk as version 2 bytes at the lowest quality in `[min_quality, max_quality]` whose measured PSNR is at least
+/// `min_psnr` dB: the finest and the coarsest step of the range, then bisection, at most eight exact trials.  Returns
+/// `(bytes, quality, reached, psnr)`; `reached` is false when not even `max_quality` reaches the floor (the chunk is then
+/// coded at `max_quality`).  Version 2 wraps at qualities 97 and above: keep `max_quality <= 96` or use `encode_wide_to_psnr`.
+pub fn encode_split_to_psnr(rgb_frames: &[u8], width: u32, height: u32, frames: u32, min_psnr: f64, wavelet_type: WaveletType,
+                            min_quality: u8, max_quality: u8, lane_symbols: u32) -> Result<(Vec<u8>, u8, bool, f64), CodecError> {
+    encode_to_psnr(ContainerFormat::Split, rgb_frames, width, height, frames, min_psnr, wavelet_type, min_quality, max_quality,
+                   lane_symbols)
+}
+
+/// `encode_split_to_psnr` for version 3: the bytes are `encode_wide`'s at the returned quality.
+pub fn encode_wide_to_psnr(rgb_frames: &[u8], width: u32, height: u32, frames: u32, min_psnr: f64, wavelet_type: WaveletType,
+                           min_quality: u8, max_quality: u8, lane_symbols: u32) -> Result<(Vec<u8>, u8, bool, f64), CodecError> {
+    encode_to_psnr(ContainerFormat::Wide, rgb_frames, width, height, frames, min_psnr, wavelet_type, min_quality, max_quality,
+                   lane_symbols)
+}
+
+/// What a device PSNR-floor encode chose per chunk.
+pub struct PsnrChoices { pub chosen: Vec<u8>, pub reached: Vec<bool>, pub psnr: Vec<f64>, pub sizes: Vec<u64> }
+
+unsafe fn encode_to_psnr_device(format: ContainerFormat, d_frames: *const std::ffi::c_void, frame_width: u32, frame_height: u32,
+                                origins: Option<&[(u32, u32)]>, width: u32, height: u32, frames: u32, n_chunks: u32,
+                                wavelet_type: WaveletType, lane_symbols: u32, min_psnr: f64, min_quality: u8, max_quality: u8,
+                                d_out: *mut std::ffi::c_void, out_stride: u64, hip_stream: *mut std::ffi::c_void)
+    -> Result<PsnrChoices, CodecError> {
+    let n = n_chunks as usize;
+    if let Some(o) = origins {
+        if o.len() != n { return Err(CodecError::InvalidBufferSize { expected: n, got: o.len() }); }
+    }
+    let flat: Option<Vec<u32>> = origins.map(|o| o.iter().flat_map(|&(x, y)| [x, y]).collect());
+    let (mut chosen, mut reached, mut psnr, mut sizes) = (vec![0u8; n.max(1)], vec![0u8; n.max(1)], vec![0f64; n.max(1)], vec![0u64; n.max(1)]);
+    let rc = alice_codec_dev_encode_to_psnr(format as u8, d_frames, frame_width, frame_height,
+                                            flat.as_ref().map_or(std::ptr::null(), |o| o.as_ptr()), width, height, frames, n_chunks,
+                                            wavelet_type as u8, lane_symbols, min_psnr, min_quality, max_quality, chosen.as_mut_ptr(),
+                                            reached.as_mut_ptr(), psnr.as_mut_ptr(), d_out, out_stride, sizes.as_mut_ptr(), hip_stream);
+    chosen.truncate(n); reached.truncate(n); psnr.truncate(n); sizes.truncate(n);
+    check(rc, 0, 0).map(|_| PsnrChoices { chosen, reached: reached.into_iter().map(|r| r != 0).collect(), psnr, sizes })
+}
+
+/// `n_chunks` device chunks (packed, or regions when `origins` is given), chunk i at the quality `encode_split_to_psnr`'s
+/// rule picks for it, the bytes at `d_out + i * out_stride`.
+///
+/// # Safety
+/// As `split_encode_device`.
+pub unsafe fn split_encode_to_psnr_device(d_frames: *const std::ffi::c_void, frame_width: u32, frame_height: u32,
+                                          origins: Option<&[(u32, u32)]>, width: u32, height: u32, frames: u32, n_chunks: u32,
+                                          wavelet_type: WaveletType, lane_symbols: u32, min_psnr: f64, min_quality: u8,
+                                          max_quality: u8, d_out: *mut std::ffi::c_void, out_stride: u64,
+                                          hip_stream: *mut std::ffi::c_void) -> Result<PsnrChoices, CodecError> {
+    encode_to_psnr_device(ContainerFormat::Split, d_frames, frame_width, frame_height, origins, width, height, frames, n_chunks,
+                          wavelet_type, lane_symbols, min_psnr, min_quality, max_quality, d_out, out_stride, hip_stream)
+}
+
+/// `split_encode_to_psnr_device` for version 3.
+///
+/// # Safety
+/// As `split_encode_device`.
+pub unsafe fn wide_encode_to_psnr_device(d_frames: *const std::ffi::c_void, frame_width: u32, frame_height: u32,
+                                         origins: Option<&[(u32, u32)]>, width: u32, height: u32, frames: u32, n_chunks: u32,
+                                         wavelet_type: WaveletType, lane_symbols: u32, min_psnr: f64, min_quality: u8,
+                                         max_quality: u8, d_out: *mut std::ffi::c_void, out_stride: u64,
+                                         hip_stream: *mut std::ffi::c_void) -> Result<PsnrChoices, CodecError> {
+    encode_to_psnr_device(ContainerFormat::Wide, d_frames, frame_width, frame_height, origins, width, height, frames, n_chunks,
+                          wavelet_type, lane_symbols, min_psnr, min_quality, max_quality, d_out, out_stride, hip_stream)
+}

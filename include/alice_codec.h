@@ -607,6 +607,71 @@ int alice_codec_dev_decode_reversible_regions(const void *d_alc, uint64_t alc_st
                                               void *d_frames_out, uint32_t frame_width, uint32_t frame_height,
                                               const uint32_t *origins, void *hip_stream);
 
+/* ---- quality control: exact trial distortion and PSNR-floor encodes ----
+ * The lane coders of versions 2, 3 and 4 are lossless, so the pixels a decode returns are the format's inverse transform of
+ * the format's forward symbols: the distortion of an encode is known from a transform pair and one comparison pass, without
+ * a byte of a container.  The container is chosen by its version byte; any other value is ALICE_ERR_INVALID_BITSTREAM.
+ * Version 1 has no such calls (its decoder desynchronises on almost all content).  Validation is host code in this order
+ * before a device is looked for: null arguments, the format byte, dimensions (overflow, empty), pitches / regions inside
+ * the frame, wavelet byte (ALICE_ERR_INVALID_BITSTREAM), lane_symbols (ALICE_ERR_INVALID_DIMENSIONS), the quality range
+ * (as in the budget calls), then the target.  Memory comes from the library's pool; nothing goes through the chain hub. */
+enum { ALICE_FORMAT_SPLIT = 2, ALICE_FORMAT_WIDE = 3, ALICE_FORMAT_REVERSIBLE = 4 };
+enum { ALICE_QUALITY_MAX_TRIALS = 8 };
+/* d_frame_sse[k] (n_frames u64 on the device) = the exact sum over frame k of (a - b)^2, all three colours, of two volumes
+ * of n_frames frames of width x height interleaved 8-bit RGB on the device.  Pixel x of row y of frame k of a side is at
+ * base + k * frame_pitch + y * row_pitch + 3 x; the base may have any byte alignment; a packed volume has pitches 3 * width
+ * and 3 * width * height.  A row pitch below 3 * width or a frame pitch below (height - 1) * row_pitch + 3 * width is
+ * ALICE_ERR_INVALID_DIMENSIONS.  Only the pixels named are read.  Integer arithmetic throughout.  Finished on return. */
+int alice_codec_dev_rgb_sse(const void *d_a, uint64_t a_row_pitch, uint64_t a_frame_pitch, const void *d_b, uint64_t b_row_pitch,
+                            uint64_t b_frame_pitch, uint32_t width, uint32_t height, uint64_t n_frames, void *d_frame_sse,
+                            void *hip_stream);
+/* Trial distortion of n_chunks device chunks (packed when origins == NULL, regions otherwise, as in
+ * alice_codec_dev_encode_split_to_budget), chunk i at qualities[i] (NULL: all at `quality`): the format's forward pass to
+ * symbols, the format's inverse (the reference's for versions 2 and 3, the mirrored one for version 4) into scratch, and the
+ * comparison against the source.  sse[i] (host) = the chunk's total; d_frame_sse: NULL, or device memory for
+ * n_chunks * frames u64, [chunk][frame].  No lane coding, no table, no byte of a container; the chunks are worked on in
+ * the groups of alice_codec_dev_encode_split / _wide.  CONTRACT: sse[i] equals the squared error between the source and the
+ * pixels the format's decode returns for the format's encode at that quality, bit for bit.  On error sse is left alone. */
+int alice_codec_dev_trial_sse(uint8_t format, const void *d_frames, uint32_t frame_width, uint32_t frame_height,
+                              const uint32_t *origins, uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks,
+                              uint8_t wavelet_type, uint8_t quality, const uint8_t *qualities, uint64_t *sse, void *d_frame_sse,
+                              void *hip_stream);
+/* The dB value of a squared error over n_bytes samples, by the expression alice_codec_psnr uses (which calls this):
+ * +inf when the mean squared error is 0, else 10 * log10(255^2 / (sse / n_bytes)).  No device, no error state. */
+double alice_codec_psnr_from_sse(uint64_t sse, uint64_t n_bytes);
+/* PSNR-floor encode: the smallest quality whose trial reaches min_psnr_db, for versions 2 and 3 (version 4 is refused: a
+ * lossless encode has no quality to search).  min_psnr_db NaN or negative is ALICE_ERR_INVALID_DIMENSIONS; +inf means exact.
+ * The rule, per chunk (N = the unpadded chunk's bytes, T = min_psnr_db):
+ *   1. sse_max = floor(65025 * N / 10^(T / 10)) in f64 (0 for T = +inf).  A trial passes iff its integer sse <= sse_max:
+ *      integers decide, not the reported dB.
+ *   2. The candidates are the distinct quantiser steps of the qualities in [min_q, max_q] after qualities above 100 became
+ *      100; the step falls with quality, and each step is tried at the lowest quality that has it.
+ *   3. The finest step (max_q's) is tried.  If it fails: chosen = max_q, reached = 0.
+ *   4. The coarsest step (min_q's) is tried.  If it passes it is chosen.
+ *   5. Otherwise bisection between a passing finer step and a failing coarser one, the midpoint rounded towards the finer,
+ *      until they are adjacent; the coarsest passing step found is chosen.  At most ALICE_QUALITY_MAX_TRIALS = 2 + 6 trials
+ *      for the 64 steps.
+ *   6. chosen = the lowest quality in the range with the chosen step; the bytes are exactly alice_codec_encode_split's /
+ *      _wide's at chosen; psnr = alice_codec_psnr_from_sse of the chosen step's trial.
+ * Bisection assumes that distortion does not fall as the step grows.  The call PROMISES only: the returned point was
+ * measured, `reached` tells the truth about it, and no trial between the finest step and the chosen one was seen to fail.
+ * On 64x48x8 smooth-plus-noise content the CPU oracle finds version 3 monotone over all 64 steps for all three wavelets;
+ * version 2 is NOT among steps 1 to 3 (q >= 97), where the u8 symbol wraps (step 1 with every wavelet, steps 2 and 3 too
+ * with CDF 9/7): there the finest step fails and the call answers max_q with reached = 0.  Callers who want a floor near the top should use version 3, or max_q <= 96 with version 2.
+ * Device call: packed chunks when origins == NULL, regions otherwise; chosen / reached / psnr / sizes per chunk and the
+ * bytes at d_out + i * out_stride; the trials run chunk by chunk, the final encode in the groups of
+ * alice_codec_dev_encode_split / _wide.  On error the outputs are left alone. */
+int alice_codec_dev_encode_to_psnr(uint8_t format, const void *d_frames, uint32_t frame_width, uint32_t frame_height,
+                                   const uint32_t *origins, uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks,
+                                   uint8_t wavelet_type, uint32_t lane_symbols, double min_psnr_db, uint8_t min_q, uint8_t max_q,
+                                   uint8_t *chosen, uint8_t *reached, double *psnr, void *d_out, uint64_t out_stride,
+                                   uint64_t *sizes, void *hip_stream);
+/* The same for one chunk in host memory: returns the bytes (free with alice_codec_data_free64), NULL on error.  A chunk
+ * without pixels has squared error 0 at every step: min_q, reached, +inf, and the 1630-byte header. */
+uint8_t *alice_codec_encode_to_psnr(uint8_t format, uint8_t wavelet_type, const uint8_t *rgb, uint64_t rgb_len, uint32_t width,
+                                    uint32_t height, uint32_t frames, uint32_t lane_symbols, double min_psnr_db, uint8_t min_q,
+                                    uint8_t max_q, uint8_t *chosen_q, uint8_t *reached, double *psnr, uint64_t *out_len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -870,4 +870,100 @@ inline uint32_t estimate_quality(uint32_t target_bitrate_kbps, uint32_t width, u
     return detail::clamp_or_throw<uint32_t>(detail::f64_as_u32(q), 5u, 100u);
 }
 
+// quality control: exact trial distortion and PSNR-floor encodes.  `format` is the container's version
+// byte (ALICE_FORMAT_SPLIT / _WIDE / _REVERSIBLE); the device pointers may have any byte alignment.
+inline double psnr_from_sse(uint64_t sse, uint64_t n_bytes) { return alice_codec_psnr_from_sse(sse, n_bytes); }
+struct RgbPitches { uint64_t row = 0, frame = 0; };   // 0, 0: packed
+// the n_frames u64 sums land at d_frame_sse (device)
+inline void rgb_sse_device(const void* d_a, const void* d_b, uint32_t w, uint32_t h, uint64_t n_frames, void* d_frame_sse,
+                           RgbPitches a = {}, RgbPitches b = {}, void* hip_stream = nullptr) {
+    const uint64_t row = 3ull * w, frame = row * h;
+    detail::check(alice_codec_dev_rgb_sse(d_a, a.row ? a.row : row, a.frame ? a.frame : frame, d_b, b.row ? b.row : row,
+                                          b.frame ? b.frame : frame, w, h, n_frames, d_frame_sse, hip_stream));
+}
+// per-chunk squared error of the format's decode of the format's encode (chunk i at qualities[i] when given); packed chunks,
+// or regions of frame_width x frame_height frames when origins (one (x, y) pair per chunk) is not empty
+inline std::vector<uint64_t> trial_sse_device(uint8_t format, const void* d_frames, uint32_t w, uint32_t h, uint32_t f, uint32_t n_chunks,
+                                              WaveletType wt, uint8_t quality, const std::vector<uint8_t>& qualities = {},
+                                              uint32_t frame_width = 0, uint32_t frame_height = 0,
+                                              const std::vector<uint32_t>& origins = {}, void* d_frame_sse = nullptr,
+                                              void* hip_stream = nullptr) {
+    if (!qualities.empty() && qualities.size() != n_chunks) throw CodecError(ALICE_ERR_INVALID_BUFFER_SIZE, "one quality per chunk");
+    if (!origins.empty() && origins.size() != 2 * (size_t)n_chunks) throw CodecError(ALICE_ERR_INVALID_BUFFER_SIZE, "origins: one (x, y) pair per chunk");
+    std::vector<uint64_t> sse(n_chunks ? n_chunks : 1);
+    detail::check(alice_codec_dev_trial_sse(format, d_frames, frame_width, frame_height, origins.empty() ? nullptr : origins.data(), w, h, f,
+                                            n_chunks, static_cast<uint8_t>(wt), quality, qualities.empty() ? nullptr : qualities.data(),
+                                            sse.data(), d_frame_sse, hip_stream));
+    sse.resize(n_chunks);
+    return sse;
+}
+inline std::vector<double> trial_psnr_device(uint8_t format, const void* d_frames, uint32_t w, uint32_t h, uint32_t f, uint32_t n_chunks,
+                                             WaveletType wt, uint8_t quality, const std::vector<uint8_t>& qualities = {},
+                                             uint32_t frame_width = 0, uint32_t frame_height = 0,
+                                             const std::vector<uint32_t>& origins = {}, void* hip_stream = nullptr) {
+    const std::vector<uint64_t> sse = trial_sse_device(format, d_frames, w, h, f, n_chunks, wt, quality, qualities, frame_width,
+                                                       frame_height, origins, nullptr, hip_stream);
+    std::vector<double> db(sse.size());
+    for (size_t i = 0; i < sse.size(); ++i) db[i] = psnr_from_sse(sse[i], 3ull * w * h * f);
+    return db;
+}
+// the lowest quality in [min_quality, max_quality] whose measured PSNR reaches min_psnr (the rule: alice_codec.h); reached is
+// false when not even max_quality does (the chunk is then coded at max_quality); psnr is the measured value of the point
+struct PsnrEncode { std::vector<uint8_t> data; uint8_t quality; bool reached; double psnr; };
+namespace detail {
+inline PsnrEncode encode_to_psnr(uint8_t format, const std::vector<uint8_t>& rgb, uint32_t w, uint32_t h, uint32_t f, double min_psnr,
+                                 WaveletType wt, uint8_t min_quality, uint8_t max_quality, uint32_t lane_symbols) {
+    static const uint8_t empty = 0;
+    uint8_t q = 0, reached = 0;
+    double db = 0.0;
+    uint64_t n = 0;
+    uint8_t* p = alice_codec_encode_to_psnr(format, static_cast<uint8_t>(wt), rgb.empty() ? &empty : rgb.data(), rgb.size(), w, h, f,
+                                            lane_symbols, min_psnr, min_quality, max_quality, &q, &reached, &db, &n);
+    if (!p) raise();
+    return PsnrEncode{take(p, n), q, reached != 0, db};
+}
+}  // namespace detail
+inline PsnrEncode encode_split_to_psnr(const std::vector<uint8_t>& rgb, uint32_t w, uint32_t h, uint32_t f, double min_psnr,
+                                       WaveletType wt = WaveletType::Cdf53, uint8_t min_quality = 10, uint8_t max_quality = 95,
+                                       uint32_t lane_symbols = 0) {
+    return detail::encode_to_psnr(ALICE_FORMAT_SPLIT, rgb, w, h, f, min_psnr, wt, min_quality, max_quality, lane_symbols);
+}
+inline PsnrEncode encode_wide_to_psnr(const std::vector<uint8_t>& rgb, uint32_t w, uint32_t h, uint32_t f, double min_psnr,
+                                      WaveletType wt = WaveletType::Cdf53, uint8_t min_quality = 10, uint8_t max_quality = 95,
+                                      uint32_t lane_symbols = 0) {
+    return detail::encode_to_psnr(ALICE_FORMAT_WIDE, rgb, w, h, f, min_psnr, wt, min_quality, max_quality, lane_symbols);
+}
+struct PsnrChoices { std::vector<uint8_t> chosen, reached; std::vector<double> psnr; std::vector<uint64_t> sizes; };
+namespace detail {
+inline PsnrChoices encode_to_psnr_device(uint8_t format, const void* d_frames, uint32_t w, uint32_t h, uint32_t f, uint32_t n_chunks,
+                                         WaveletType wt, double min_psnr, void* d_out, uint64_t out_stride, uint8_t min_quality,
+                                         uint8_t max_quality, uint32_t lane_symbols, uint32_t frame_width, uint32_t frame_height,
+                                         const std::vector<uint32_t>& origins, void* hip_stream) {
+    if (!origins.empty() && origins.size() != 2 * (size_t)n_chunks) throw CodecError(ALICE_ERR_INVALID_BUFFER_SIZE, "origins: one (x, y) pair per chunk");
+    const size_t m = n_chunks ? n_chunks : 1;
+    PsnrChoices c{std::vector<uint8_t>(m), std::vector<uint8_t>(m), std::vector<double>(m), std::vector<uint64_t>(m)};
+    check(alice_codec_dev_encode_to_psnr(format, d_frames, frame_width, frame_height, origins.empty() ? nullptr : origins.data(), w, h, f,
+                                         n_chunks, static_cast<uint8_t>(wt), lane_symbols, min_psnr, min_quality, max_quality,
+                                         c.chosen.data(), c.reached.data(), c.psnr.data(), d_out, out_stride, c.sizes.data(), hip_stream));
+    c.chosen.resize(n_chunks); c.reached.resize(n_chunks); c.psnr.resize(n_chunks); c.sizes.resize(n_chunks);
+    return c;
+}
+}  // namespace detail
+inline PsnrChoices split_encode_to_psnr_device(const void* d_frames, uint32_t w, uint32_t h, uint32_t f, uint32_t n_chunks, WaveletType wt,
+                                               double min_psnr, void* d_out, uint64_t out_stride, uint8_t min_quality = 10,
+                                               uint8_t max_quality = 95, uint32_t lane_symbols = 0, uint32_t frame_width = 0,
+                                               uint32_t frame_height = 0, const std::vector<uint32_t>& origins = {},
+                                               void* hip_stream = nullptr) {
+    return detail::encode_to_psnr_device(ALICE_FORMAT_SPLIT, d_frames, w, h, f, n_chunks, wt, min_psnr, d_out, out_stride, min_quality,
+                                         max_quality, lane_symbols, frame_width, frame_height, origins, hip_stream);
+}
+inline PsnrChoices wide_encode_to_psnr_device(const void* d_frames, uint32_t w, uint32_t h, uint32_t f, uint32_t n_chunks, WaveletType wt,
+                                              double min_psnr, void* d_out, uint64_t out_stride, uint8_t min_quality = 10,
+                                              uint8_t max_quality = 95, uint32_t lane_symbols = 0, uint32_t frame_width = 0,
+                                              uint32_t frame_height = 0, const std::vector<uint32_t>& origins = {},
+                                              void* hip_stream = nullptr) {
+    return detail::encode_to_psnr_device(ALICE_FORMAT_WIDE, d_frames, w, h, f, n_chunks, wt, min_psnr, d_out, out_stride, min_quality,
+                                         max_quality, lane_symbols, frame_width, frame_height, origins, hip_stream);
+}
+
 }  // namespace alice_codec

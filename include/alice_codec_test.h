@@ -118,6 +118,21 @@ int alice_codec_test_inverse_variant(uint8_t wavelet_type, const int32_t step[3]
  * computed, at most ALICE_SPLIT_REFINE_TRIALS each) of the first min(that, cap) chunks to per_chunk (may be NULL). */
 uint32_t alice_codec_test_last_split_trials(uint32_t *per_chunk, uint32_t cap);
 
+/* The last alice_codec_dev_encode_to_psnr / alice_codec_encode_to_psnr of the calling thread: returns its number of chunks and
+ * writes the trials (transform pairs measured, at most ALICE_QUALITY_MAX_TRIALS each) of the first min(that, cap) chunks to
+ * per_chunk (may be NULL). */
+uint32_t alice_codec_test_last_quality_trials(uint32_t *per_chunk, uint32_t cap);
+
+/* Bytes of the band slot the inverse transform of a width x height x frames chunk needs under the current band target
+ * (alice_codec_test_set_tuning) when its intermediate is i16 (mid16 != 0: the steps alice_codec_test_inverse_variant maps to 2
+ * or 3) or i32; 0 for a shape the tile kernels do not cover.  The two plans cut a chunk differently, and either slot can be
+ * the larger.  No device needed. */
+uint64_t alice_codec_test_inverse_scratch_bytes(uint32_t width, uint32_t height, uint32_t frames, int mid16);
+
+/* The byte-at-a-time squared-error kernel behind alice_codec_psnr (csrc/generic.hip, sq_diff_sum_kernel) on two device
+ * buffers of n bytes: *sse (host) = the sum.  For the probes that time it beside alice_codec_dev_rgb_sse. */
+int alice_codec_test_sq_diff_sum(const void *d_a, const void *d_b, uint64_t n, uint64_t *sse, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
