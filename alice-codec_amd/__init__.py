@@ -316,6 +316,10 @@ def load_library() -> C.CDLL:
         "alice_codec_test_inverse_scratch_bytes": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]),
         "alice_codec_test_sq_diff_sum": (C.c_int, [vp, vp, C.c_uint64, _u64p, vp]),
         "alice_codec_test_inverse_variant": (C.c_int, [C.c_uint8, _i32p, C.c_int]),
+        "alice_codec_frames_window": (C.c_int, [C.c_uint8, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p]),
+        "alice_codec_decode_frames": (vp, [_u8p, C.c_uint64, C.c_uint32, C.c_uint32, _u64p]),
+        "alice_codec_dev_decode_frames": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp]),
+        "alice_codec_test_last_frames_stats": (None, [_u64p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
@@ -2210,6 +2214,45 @@ def reversible_decode_regions_device(d_alc_ptr: int, alc_stride: int, sizes, d_f
     """wide_decode_regions_device for version 4: no byte outside the rectangles is written."""
     _decode_container_regions("reversible", d_alc_ptr, alc_stride, sizes, d_frames_out_ptr, frame_width, frame_height, origins,
                               stream)
+
+
+# ---- frame ranges of a version 2, 3 or 4 chunk (DESIGN.md section 14) ----
+
+def frames_window(wavelet_type: WaveletType, frames: int, first: int, count: int) -> tuple:
+    """(a, b): frames [first, first + count) of a chunk of `frames` frames depend on the coefficient planes of the frame
+    pairs inside [a, b) only.  No device needed."""
+    _dims_u32(frames, first, count)
+    a, b = C.c_uint32(0), C.c_uint32(0)
+    _check(load_library().alice_codec_frames_window(int(wavelet_type), frames, first, count, C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
+def decode_frames(data, first: int, count: int) -> np.ndarray:
+    """The RGB bytes of frames [first, first + count) of a version 2, 3 or 4 container, from the blocks they need: only the
+    header, the block-length tables and those blocks are read and uploaded (data may be an np.memmap).  The end checks
+    cover the blocks that are read."""
+    lib = load_library()
+    buf = _as_u8(data)
+    _dims_u32(first, count)
+    n = C.c_uint64(0)
+    ptr = lib.alice_codec_decode_frames(_p(buf, _u8p), buf.size, first, count, C.byref(n))
+    if not ptr:
+        _raise_last()
+    return _adopt(ptr, n.value, lib.alice_codec_data_free64)
+
+
+def frames_decode_device(d_alc_ptr: int, length: int, first: int, count: int, d_rgb_out_ptr: int, stream: int = 0) -> None:
+    """decode_frames of a device-resident container of `length` bytes into count packed frames at d_rgb_out_ptr."""
+    _dims_u32(first, count)
+    _check(load_library().alice_codec_dev_decode_frames(d_alc_ptr, length, first, count, d_rgb_out_ptr, stream or None))
+
+
+def _test_last_frames_stats() -> tuple:
+    """(a, b, blocks decoded over the three channels, payload bytes the host call uploaded, frames of the spatial pass) of
+    the calling thread's last frame-range decode."""
+    out = np.zeros(5, np.uint64)
+    load_library().alice_codec_test_last_frames_stats(_p(out, _u64p))
+    return tuple(int(v) for v in out)
 
 
 # ---- quality control: exact trial distortion and PSNR-floor encodes (DESIGN.md section 13) ----

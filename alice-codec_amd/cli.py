@@ -15,6 +15,9 @@ measured dB and whether the floor was reached per chunk; it is refused for the d
 `--lossless`, and together with `--max-bytes` / `--kbps`;
 `decode` and `info` pick the format from the version byte unless `--format` names one.  The default of every subcommand
 is version 1.
+`decode --frames A:B` (A alone: one frame) writes frames [A, B) of a version 2, 3 or 4 file from the blocks they need
+(DESIGN.md section 14): the file is mapped, so only the header, the block-length tables and those blocks are read;
+version 1 is refused with the library's message.
 Like the reference it treats the whole input file as ONE chunk (src/bin/main.rs:117-122).  `encode-chunks`
 is the extension SURVEY.md section 8f asks for: it cuts a long raw-RGB file into 64-frame chunks
 (DEFAULT_CHUNK_SIZE, src/lib.rs:110) and writes one .alc per chunk."""
@@ -26,7 +29,7 @@ import sys
 import numpy as np
 
 from . import (DEFAULT_CHUNK_SIZE, CodecError, EncodedChunk, FrameDecoder, FrameEncoder, WaveletType, budget_bytes_per_chunk,
-               alc_version, decode_reversible, decode_split, decode_wide, encode_many, encode_reversible, encode_split,
+               alc_version, decode_frames, decode_reversible, decode_split, decode_wide, encode_many, encode_reversible, encode_split,
                encode_split_to_psnr, encode_split_to_size, encode_to_size, encode_wide, encode_wide_to_psnr, reversible_info,
                split_info, wide_info)
 
@@ -247,7 +250,36 @@ def _encode_chunks_to_rate(a, wt, rgb, frame_bytes, n_frames) -> None:
                       file=sys.stderr)
 
 
+def parse_frames(text: str):
+    """'A' -> (A, A + 1), 'A:B' -> (A, B), half-open; ValueError otherwise."""
+    parts = text.split(":")
+    try:
+        if len(parts) > 2 or not all(p.strip().isdigit() for p in parts):
+            raise ValueError
+        first = int(parts[0])
+        end = int(parts[1]) if len(parts) == 2 else first + 1
+        if end <= first or end > 0xFFFFFFFF:
+            raise ValueError
+    except ValueError:
+        raise ValueError(f"--frames wants A or A:B with 0 <= A < B (half-open), got '{text}'") from None
+    return first, end
+
+
+def cmd_decode_frames(a) -> None:
+    first, end = parse_frames(a.frames)
+    data = np.memmap(a.input, dtype=np.uint8, mode="r")
+    if a.format != "auto" and data.size > 4 and int(data[4]) != FORMAT_VERSION[a.format]:
+        raise ValueError(f"--format {a.format} names version {FORMAT_VERSION[a.format]}, the file's version byte is {int(data[4])}")
+    rgb = decode_frames(data, first, end - first)
+    rgb.tofile(a.output)
+    width, height, frames = (int(v) for v in np.frombuffer(bytes(data[6:18]), "<u4"))
+    print(f"decoded frames [{first}, {end}) of {width}x{height}x{frames} -> {rgb.size} bytes (raw RGB)", file=sys.stderr)
+
+
 def cmd_decode(a) -> None:
+    if a.frames is not None:
+        cmd_decode_frames(a)
+        return
     data = np.fromfile(a.input, dtype=np.uint8)
     version = _container_version(a, data)
     if version in CONTAINER_INFO:
@@ -339,6 +371,8 @@ def main(argv=None) -> int:
     d = sub.add_parser("decode")
     d.add_argument("input")
     d.add_argument("-o", "--output", required=True)
+    d.add_argument("--frames", default=None, metavar="A[:B]",
+                   help="write frames [A, B) only (A alone: one frame), decoded from the blocks they need; versions 2, 3 and 4")
     i = sub.add_parser("info")
     i.add_argument("input")
     for x in (d, i):

@@ -22,6 +22,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <exception>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -3480,7 +3481,8 @@ int split_write(SplitWork& w, hipStream_t st) {
 
 // Decode of the jobs' payloads (h[j].stream / len / sym set by the caller) with the tables of freq (n_jobs x 256, each
 // summing to 4096).  Queues the directory scan and the lane decode; split_decode_verdict reads the flags.
-int split_decode_launch(SplitWork& w, const uint16_t* freq, hipStream_t st) {
+// lane_decode: what runs instead of the decode of every block (frame ranges: the planned blocks).
+int split_decode_launch(SplitWork& w, const uint16_t* freq, hipStream_t st, const std::function<int()>* lane_decode = nullptr) {
     w.st = st; w.armed = true;
     w.h_freq.assign(freq, freq + (size_t)w.n_jobs * 256);
     freq = w.h_freq.data();
@@ -3497,7 +3499,8 @@ int split_decode_launch(SplitWork& w, const uint16_t* freq, hipStream_t st) {
     for (int j = 0; j < w.n_jobs; ++j)
         launch_rans_table_from_arrays(w.cum.as<uint16_t>() + (size_t)j * 256, w.freq.as<uint16_t>() + (size_t)j * 256, w.tables.as<RansTable>() + j, st);
     launch_split_scan(w.jobs.as<SplitJob>(), w.n_jobs, true, nullptr, st);
-    if (w.wide) launch_split_wide_decode(w.jobs.as<SplitJob>(), w.n_jobs, w.n_blocks, st);
+    if (lane_decode) TRY((*lane_decode)());
+    else if (w.wide) launch_split_wide_decode(w.jobs.as<SplitJob>(), w.n_jobs, w.n_blocks, st);
     else launch_split_decode(w.jobs.as<SplitJob>(), w.n_jobs, w.n_blocks, st);
     HIP_TRY(hipGetLastError());
     return kOk;
@@ -4742,6 +4745,260 @@ int alice_codec_test_sq_diff_sum(const void* d_a, const void* d_b, uint64_t n, u
     TRY(copy_to_host(&v, ds.p, 8, st));
     *sse = v;
     return kOk;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// PART 8: frame ranges of a version 2, 3 or 4 chunk (kernels: split_frames_decode_kernel of
+// split.hip, the window instances of transform.hip's temporal role)
+//
+// The temporal transform is one lifting level, so frames [t0, t1) depend on the coefficient planes of the frame pairs
+// inside [a, b) only (frames_window).  Those b - a planes, low band then high band, are the symbol volume of a virtual
+// chunk of b - a frames whose inverse temporal lifting equals the full chunk's at [t0 - a, t1 - a).  The lane decode runs
+// over the blocks that intersect the planes, the temporal role stores t1 - t0 frames, the spatial pass runs over those.
+// The end checks cover the blocks that are read: damage in a lane of another block is not seen.
+// ------------------------------------------------------------------------------------------
+
+namespace {
+
+uint32_t frames_halo(uint8_t wavelet) { return wavelet == 1 ? 4u : 2u; }   // lifting steps: CDF 9/7 four, CDF 5/3 and Haar two
+
+// frames > 0, first + count <= frames, count > 0
+void frames_window(uint8_t wavelet, uint32_t frames, uint32_t first, uint32_t count, uint32_t* a, uint32_t* b) {
+    const uint64_t ns = frames_halo(wavelet), pf = frames == 1 ? 2ull : (uint64_t)frames + (frames & 1u);
+    const uint64_t t0 = first, t1 = (uint64_t)first + count;
+    *a = t0 > ns ? (uint32_t)((t0 - ns) & ~1ull) : 0u;
+    *b = (uint32_t)std::min<uint64_t>(pf, (t1 + ns + 1) & ~1ull);
+}
+
+struct FramesPlan {
+    uint32_t a = 0, b = 0;
+    int n_ranges = 0;                       // 1 when the two bands' planes touch (a = 0 and b = pf)
+    uint64_t sym_lo[2] = {0, 0}, sym_hi[2] = {0, 0};
+    uint32_t blk_first[2] = {0, 0}, blk_count[2] = {0, 0};   // disjoint: a block both ranges touch belongs to the first
+    uint32_t blocks() const { return blk_count[0] + blk_count[1]; }
+};
+
+FramesPlan frames_plan(const SplitHeader& h, const ChunkDims& d, uint32_t first, uint32_t count) {
+    FramesPlan p;
+    frames_window(h.wavelet, h.frames, first, count, &p.a, &p.b);
+    const uint64_t P = d.pw * d.ph, half = d.pf / 2, B = 64ull * h.lane_symbols;
+    const uint64_t lo0 = p.a / 2 * P, hi0 = p.b / 2 * P, lo1 = (half + p.a / 2) * P, hi1 = (half + p.b / 2) * P;
+    if (hi0 == lo1) { p.n_ranges = 1; p.sym_lo[0] = lo0; p.sym_hi[0] = hi1; }
+    else { p.n_ranges = 2; p.sym_lo[0] = lo0; p.sym_hi[0] = hi0; p.sym_lo[1] = lo1; p.sym_hi[1] = hi1; }
+    uint64_t next = 0;   // first block no earlier range has taken
+    for (int r = 0; r < p.n_ranges; ++r) {
+        const uint64_t f = std::max(p.sym_lo[r] / B, next), e = (p.sym_hi[r] + B - 1) / B;
+        p.blk_first[r] = (uint32_t)f;
+        p.blk_count[r] = e > f ? (uint32_t)(e - f) : 0u;
+        next = std::max(next, e);
+    }
+    return p;
+}
+
+thread_local uint64_t tl_frames_stats[5] = {0, 0, 0, 0, 0};   // alice_codec_test_last_frames_stats
+
+// The checks both calls share, in their order (after the null checks): fixed fields and magic, the version byte, that
+// version's header checks, then the range.  data: min(len, kSplitHeaderBytes) readable bytes.
+int frames_validate(const uint8_t* data, uint64_t len, uint32_t first, uint32_t count, SplitHeader& h, ChunkDims& d) {
+    if (len < kSplitFixedHeaderBytes)
+        return fail(kInvalidBitstream, "data too short for the fixed fields: " + std::to_string(len) + " bytes (they take " +
+                                           std::to_string(kSplitFixedHeaderBytes) + ")");
+    if (memcmp(data, "ALCC", 4) != 0) return fail(kInvalidBitstream, "bad magic (expected ALCC)");
+    const int version = data[4];
+    if (version == 1) return fail(kInvalidBitstream, "version 1 has no random access (one serial chain per channel)");
+    if (version < 2 || version > 4)
+        return fail(kInvalidBitstream, "unsupported version: " + std::to_string(version) + " (a frame range needs version 2, 3 or 4)");
+    TRY(parse_split_header(data, len, h, &d, version));
+    if (count < 1 || (uint64_t)first + count > h.frames)
+        return fail(kInvalidDimensions, "frames [" + std::to_string(first) + ", " + std::to_string((uint64_t)first + count) +
+                                            ") are not a range of the chunk's " + std::to_string(h.frames) + " frames");
+    if (d.n_pixels == 0) return fail(kInvalidDimensions, "invalid dimensions");
+    return kOk;
+}
+
+// The inverse of the virtual chunk dv whose symbols are at d_sym, frames [lo, hi) of it to `rgb` (packed, hi - lo frames):
+// inverse_chunk with the window clip.  The instance is the one the full chunk's decode takes (wavelet and steps alone).
+int inverse_window(const uint8_t* d_sym, const ChunkDims& dv, uint32_t lo, uint32_t hi, int wavelet, const int32_t step[3], void* d_scratch,
+                   DecodeWork& w, const RgbLayout& rgb, hipStream_t st, SplitFormat fmt) {
+    const bool wide = is_wide(fmt), mirror = fmt == kFormatReversible;
+    const InverseBounds ib = inverse_bounds(wavelet, step, wide ? kWideMaxQ : kByteMaxQ);
+    if (d_scratch && launch_inverse_transform_window(d_sym, dv, FrameWindow{lo, hi}, (int)fmt, wavelet, step, ib.exact, ib.mid16, ib.lds16,
+                                                     d_scratch, rgb, st))
+        return kOk;
+    // generic path: the temporal axis over the whole virtual chunk, then the spatial axes, the strip and the colour
+    // step over the frames that are kept
+    const ChunkDims dx = make_dims(dv.w, dv.h, hi - lo);
+    if (!w.planes.p) TRY(w.planes.alloc(3 * dx.n_pixels * sizeof(int16_t)));
+    if (!w.tmp.p) TRY(w.tmp.alloc(dv.padded * sizeof(int32_t)));
+    if (!w.gen.p) TRY(w.gen.alloc(2 * dv.padded * sizeof(int32_t)));
+    int16_t* pl = w.planes.as<int16_t>();
+    int32_t* qb = w.gen.as<int32_t>();
+    int32_t* vol = qb + dv.padded;
+    const uint64_t W = dv.pw, H = dv.ph, D = dv.pf, K = hi - lo;
+    int32_t* kept = vol + (size_t)lo * W * H;
+    for (int c = 0; c < 3; ++c) {
+        if (wide) launch_from_symbols_wide((const uint16_t*)d_sym + (size_t)c * dv.padded, qb, dv.padded, st);
+        else launch_from_symbols(d_sym + (size_t)c * dv.padded, qb, dv.padded, st);
+        launch_dequantize(qb, vol, dv.padded, step[c], st);
+        launch_wavelet_axis(vol, w.tmp.as<int32_t>(), D, W * H, 1, 0, W * H, 1, wavelet, true, st, mirror);
+        launch_wavelet_axis(kept, w.tmp.as<int32_t>(), H, W, K, W * H, W, 1, wavelet, true, st, mirror);
+        launch_wavelet_axis(kept, w.tmp.as<int32_t>(), W, 1, K * H, W, 1, 0, wavelet, true, st, mirror);
+        launch_strip_channel(kept, dx, pl + (size_t)c * dx.n_pixels, st);
+    }
+    launch_ycocg_to_rgb(pl, pl + dx.n_pixels, pl + 2 * dx.n_pixels, dx, rgb, st);
+    return kOk;
+}
+
+// Frames [first, first + count) of the container at d_alc (device, h validated) to d_rgb (device, count packed frames).
+// Of the payloads only the block-length tables and the planned blocks are read.  Returns after the stream has drained.
+int frames_decode_device(const SplitHeader& h, const ChunkDims& d, const uint8_t* d_alc, uint32_t first, uint32_t count, void* d_rgb,
+                         hipStream_t st, uint64_t uploaded) {
+    const FramesPlan p = frames_plan(h, d, first, count);
+    const ChunkDims dv = make_dims(h.width, h.height, p.b - p.a);   // b - a is even and at least 2: no padding of its own
+    const ChunkDims dx = make_dims(h.width, h.height, count);
+    const SplitFormat fmt = h.fmt;
+    const bool wide = is_wide(fmt);
+    const size_t sb = wide ? 2 : 1;
+    DecodeWork dw;
+    dw.d = dv; dw.n_chunks = 1;
+    TRY(dw.sym.alloc(3 * dv.padded * sb));
+    DevBuf d_fj;                          // (declared before w: w's destructor drains the stream that reads them)
+    std::vector<SplitFramesJob> fj(3);
+    TRY(d_fj.alloc(3 * sizeof(SplitFramesJob)));
+    SplitWork w;
+    TRY(split_work_alloc(w, 3, d.padded, h.lane_symbols, false, fmt));
+    uint64_t off = kSplitHeaderBytes;
+    for (int c = 0; c < 3; ++c) {
+        SplitJob& s = w.h[(size_t)c];
+        s.sym = dw.sym.as<uint8_t>() + (size_t)c * dv.padded * sb;
+        s.stream = (uint8_t*)d_alc + off;
+        s.len = h.payload_len[c];
+        off += s.len;
+    }
+    for (int c = 0; c < 3; ++c) {
+        fj[(size_t)c].j = w.h[(size_t)c];
+        for (int r = 0; r < 2; ++r) {
+            fj[(size_t)c].blk_first[r] = p.blk_first[r]; fj[(size_t)c].blk_count[r] = p.blk_count[r];
+            fj[(size_t)c].sym_lo[r] = p.sym_lo[r]; fj[(size_t)c].sym_hi[r] = p.sym_hi[r];
+        }
+    }
+    if (transform_tiles_eligible(dv))
+        TRY(dw.scratch_own.alloc(inverse_scratch_bytes(dx, inverse_bounds(h.wavelet, h.step, wide ? kWideMaxQ : kByteMaxQ).mid16)));
+    // the uploads, the tables and the directory scan of every lane decode; the lane decode itself over the planned blocks
+    const std::function<int()> lane_decode = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(d_fj.p, fj.data(), fj.size() * sizeof(SplitFramesJob), hipMemcpyHostToDevice, st));
+        launch_split_frames_decode(d_fj.as<SplitFramesJob>(), 3, p.blocks(), wide, st);
+        return kOk;
+    };
+    TRY(split_decode_launch(w, &h.freq[0][0], st, &lane_decode));
+    TRY(inverse_window(dw.sym.as<uint8_t>(), dv, first - p.a, first - p.a + count, h.wavelet, h.step, dw.scratch_own.p, dw,
+                       packed_rgb(d_rgb, dx), st, fmt));
+    HIP_TRY(hipGetLastError());
+    const int rc = split_decode_verdict(w, st);
+    tl_frames_stats[0] = p.a; tl_frames_stats[1] = p.b; tl_frames_stats[2] = 3ull * p.blocks();
+    tl_frames_stats[3] = uploaded; tl_frames_stats[4] = count;
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int alice_codec_frames_window(uint8_t wavelet_type, uint32_t frames, uint32_t first, uint32_t count, uint32_t* a, uint32_t* b) {
+    clear_error();
+    if (!a || !b) return fail(kNullArgument, "null argument");
+    if (wavelet_type > 2) return fail(kInvalidBitstream, "unknown wavelet type");
+    if (frames == 0xFFFFFFFFu) return fail(kDimensionOverflow, "the padded frame count does not fit 32 bits");
+    if (count < 1 || (uint64_t)first + count > frames)
+        return fail(kInvalidDimensions, "frames [" + std::to_string(first) + ", " + std::to_string((uint64_t)first + count) +
+                                            ") are not a range of the chunk's " + std::to_string(frames) + " frames");
+    frames_window(wavelet_type, frames, first, count, a, b);
+    return kOk;
+}
+
+int alice_codec_dev_decode_frames(const void* d_alc, uint64_t len, uint32_t first, uint32_t count, void* d_rgb_out, void* hip_stream) {
+    clear_error();
+    if (!d_alc || !d_rgb_out) return fail(kNullArgument, "null argument");
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);
+    // the header comes to the host first; nothing is queued before it and the range have been accepted
+    uint8_t raw[kSplitHeaderBytes] = {};
+    if (len) {
+        HIP_TRY(hipMemcpyAsync(raw, d_alc, std::min<uint64_t>(len, kSplitHeaderBytes), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    SplitHeader h;
+    ChunkDims d{};
+    TRY(frames_validate(raw, len, first, count, h, d));
+    return frames_decode_device(h, d, (const uint8_t*)d_alc, first, count, d_rgb_out, st, 0);
+}
+
+uint8_t* alice_codec_decode_frames(const uint8_t* data, uint64_t len, uint32_t first, uint32_t count, uint64_t* out_len) {
+    clear_error();
+    if (!data || !out_len) { fail(kNullArgument, "null argument"); return nullptr; }
+    auto run = [&](uint8_t** out) -> int {
+        SplitHeader h;
+        ChunkDims d{};
+        TRY(frames_validate(data, len, first, count, h, d));
+        const FramesPlan p = frames_plan(h, d, first, count);
+        // Block offsets from the tables, on the host; the tables get check_split_directories' verdict on the way.  What
+        // goes up: the header, the three tables, the byte runs of the planned blocks -- at their own offsets of a pool
+        // buffer of the container's size, so that the device path runs on it unchanged.  The rest of it stays unwritten
+        // and unread.
+        struct Span { uint64_t off, len; };
+        std::vector<Span> spans;
+        spans.push_back({0, kSplitHeaderBytes});
+        uint64_t payload_bytes = 0, pos = kSplitHeaderBytes;
+        for (int c = 0; c < 3; ++c) {
+            const uint8_t* tab = data + pos;
+            const uint32_t nb = h.n_blocks[c];
+            spans.push_back({pos, 4ull * nb});
+            uint64_t run_off[2] = {0, 0}, run_len[2] = {0, 0};
+            uint64_t sum = 4ull * nb;
+            for (uint32_t blk = 0; blk < nb; ++blk) {
+                const uint32_t v = get_u32(tab + 4ull * blk);
+                if (v < 128u) return fail(kInvalidBitstream, "channel " + std::to_string(c) + ": block " + std::to_string(blk) + " is shorter than its lane directory");
+                for (int r = 0; r < p.n_ranges; ++r) {
+                    if (blk == p.blk_first[r]) run_off[r] = sum;
+                    if (blk >= p.blk_first[r] && blk - p.blk_first[r] < p.blk_count[r]) run_len[r] += v;
+                }
+                sum += v;
+                if (sum > h.payload_len[c]) break;   // (the sum below refuses it; no span may leave the payload)
+            }
+            if (sum != h.payload_len[c])
+                return fail(kInvalidBitstream, "channel " + std::to_string(c) + ": block lengths do not sum to payload_len " + std::to_string(h.payload_len[c]));
+            for (int r = 0; r < p.n_ranges; ++r)
+                if (run_len[r]) { spans.push_back({pos + run_off[r], run_len[r]}); payload_bytes += run_len[r]; }
+            pos += h.payload_len[c];
+        }
+        const uint64_t bytes = (uint64_t)h.width * h.height * count * 3;
+        *out = host_result_alloc(bytes);
+        if (!*out) return fail(kOutOfMemory, "out of host memory");
+        *out_len = bytes;
+        auto body = [&]() -> int {
+            hipStream_t st;
+            TRY(get_stream(&st));
+            DevBuf d_alc, d_rgb;
+            TRY(d_alc.alloc(len));
+            TRY(d_rgb.alloc(bytes));
+            for (const Span& s : spans)
+                HIP_TRY(hipMemcpyAsync(d_alc.as<uint8_t>() + s.off, data + s.off, s.len, hipMemcpyHostToDevice, st));
+            TRY(frames_decode_device(h, d, d_alc.as<uint8_t>(), first, count, d_rgb.p, st, payload_bytes));
+            return copy_to_host(*out, d_rgb.p, bytes, st);
+        };
+        const int rc = body();
+        if (rc != kOk) { free(*out); *out = nullptr; }
+        return rc;
+    };
+    uint8_t* out = nullptr;
+    return run(&out) == kOk ? out : nullptr;
+}
+
+void alice_codec_test_last_frames_stats(uint64_t out[5]) {
+    if (out) memcpy(out, tl_frames_stats, sizeof(tl_frames_stats));
 }
 
 }  // extern "C"

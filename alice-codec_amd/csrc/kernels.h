@@ -175,6 +175,14 @@ bool launch_inverse_transform_wide(const uint16_t* d_sym, const ChunkDims& d, in
 // lifting step subtracts the forward's own delta.  Same symbols, bands, scratch and instance flags.
 bool launch_inverse_transform_reversible(const uint16_t* d_sym, const ChunkDims& d, int wavelet, const int32_t step[3],
                                          bool exact, bool mid16, bool lds16, void* d_scratch, const RgbLayout& rgb, hipStream_t st);
+// Frame ranges: d_sym is the symbol volume of a virtual chunk dv (u8 for format 0 = .alc v2, u16 for
+// 1 = v3 and 2 = v4, mirrored); its inverse runs with the instance flags the full chunk takes, and only frames
+// [win.lo, win.hi) of it reach the spatial pass and `rgb` (a layout of win.hi - win.lo frames).  The scratch is
+// inverse_scratch_bytes(make_dims(w, h, win.hi - win.lo), mid16): the slot holds the frames that are kept.
+struct FrameWindow { uint32_t lo, hi; };
+bool launch_inverse_transform_window(const void* d_sym, const ChunkDims& dv, const FrameWindow& win, int format, int wavelet,
+                                     const int32_t step[3], bool exact, bool mid16, bool lds16, void* d_scratch, const RgbLayout& rgb,
+                                     hipStream_t st);
 
 // ---- transform.hip, stage level: Wavelet2D / Wavelet3D of caller-shaped i32 data on the tile kernels' exact instances ----
 // eligible: even width and height >= 6, even depth (or depth 1); otherwise the caller uses launch_wavelet_axis.
@@ -311,6 +319,14 @@ struct SplitJob {
     uint16_t* lane_len;        // scratch, 64 * n_blocks (encode)
     uint32_t* flags;           // decode: kSplitBad*, zeroed by the caller
 };
+// Frame ranges: the blocks [blk_first[r], blk_first[r] + blk_count[r]) of channel `j` are decoded,
+// and the symbols at positions [sym_lo[r], sym_hi[r]) of the channel are stored at j.sym, range 0 first and range 1
+// directly behind it (sym_hi[0] - sym_lo[0] + sym_hi[1] - sym_lo[1] symbols; an unused range is empty, count 0).
+struct SplitFramesJob {
+    SplitJob j;
+    uint32_t blk_first[2], blk_count[2];
+    unsigned long long sym_lo[2], sym_hi[2];
+};
 struct SplitHeaderDesc {
     uint8_t* out;
     uint32_t width, height, frames, lane_symbols, num_symbols, n_blocks;
@@ -329,6 +345,8 @@ void launch_split_scan(const SplitJob* d_jobs, int n_jobs, bool from_stream, uns
 // after scan(from_stream = true); *flags != 0 afterwards: the payload is not a valid stream
 void launch_split_decode(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, hipStream_t st);
 void launch_split_headers(const SplitHeaderDesc* d_descs, int n_chunks, hipStream_t st);
+// after scan(from_stream = true) over the same channels; max_blocks: the largest blk_count[0] + blk_count[1] among the jobs
+void launch_split_frames_decode(const SplitFramesJob* d_jobs, int n_jobs, uint32_t max_blocks, bool wide, hipStream_t st);
 // the same three passes on u16 symbols with the escape step (.alc v3); the count pass sets kSplitWideResidual in *flags
 // (zeroed by the caller) when a symbol exceeds 255 + kSplitWideMaxResidual
 // overwrites the version byte of the headers launch_split_headers wrote (same stream, after it)

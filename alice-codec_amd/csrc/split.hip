@@ -12,6 +12,7 @@
 //   split_scan_kernel     block lengths -> block offsets (encode: from the count pass; decode: from the stream, validated)
 //   split_decode_kernel   lane streams -> symbols, with the end check of every lane
 //   split_header_kernel   the 1630-byte container header of whole chunks
+//   split_frames_decode_kernel   the lane decode of the blocks a frame range needs, stored as a compact volume
 //   split_wide_encode_kernel / split_wide_decode_kernel   the same chains on u16 symbols with the escape step of .alc v3
 // The output is sized by counting first and writing second: the chain arithmetic runs twice, but nothing is staged in
 // worst-case slots (2 bytes per symbol) and no compaction pass moves the payload again.
@@ -20,6 +21,8 @@
 #include "common.h"
 #include "kernels.h"
 #include "split_norm.h"
+
+#include <type_traits>
 
 namespace alice {
 
@@ -468,6 +471,120 @@ __global__ __launch_bounds__(256) void split_wide_decode_kernel(const SplitJob* 
 }
 
 // ----------------------------------------------------------------------------------
+// Lane decode of a block subset (frame ranges): the geometry, tables and bounds re-checks of the two
+// decoders above over the one or two runs of blocks a SplitFramesJob names.  A block that straddles an edge of a symbol
+// range still runs its 64 chains to their end checks (a chain is serial, and its end check is the integrity check), but
+// stores only the symbols inside the ranges, relocated into the compact volume at job.j.sym: range 0 first, range 1
+// behind it.  The two symbol ranges become two per-lane iteration ranges before the chain loop, so the loop itself
+// carries two 32-bit compares.  End checks cover the decoded blocks only.
+// ----------------------------------------------------------------------------------
+template <bool WIDE>
+__global__ __launch_bounds__(256) void split_frames_decode_kernel(const SplitFramesJob* __restrict__ jobs) {
+    using SymT = std::conditional_t<WIDE, uint16_t, uint8_t>;
+    __shared__ uint32_t c2s_sh[kProbScale / 4];
+    __shared__ uint32_t symtab[256];
+    const SplitFramesJob fj = jobs[blockIdx.y];
+    const SplitJob& job = fj.j;
+    {
+        const uint32_t* src = (const uint32_t*)job.table->dec.c2s;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) c2s_sh[threadIdx.x + 256 * t] = src[threadIdx.x + 256 * t];
+        symtab[threadIdx.x] = job.table->dec.symtab[threadIdx.x];
+    }
+    __syncthreads();
+    const uint8_t* c2s = (const uint8_t*)c2s_sh;
+    const int lane = threadIdx.x & 63;
+    const unsigned long long slot = (unsigned long long)blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (slot >= (unsigned long long)fj.blk_count[0] + fj.blk_count[1]) return;
+    const unsigned long long b = slot < fj.blk_count[0] ? fj.blk_first[0] + slot : fj.blk_first[1] + (slot - fj.blk_count[0]);
+    if (b >= job.n_blocks) return;   // (the host plans inside the channel; the bounds below do not rest on it)
+    const unsigned long long base = b * 64ull * job.lane_symbols;
+    const unsigned long long left = job.n - base;
+    const uint32_t in_block = left < 64ull * job.lane_symbols ? (uint32_t)left : 64u * job.lane_symbols;
+    const uint32_t k = (uint32_t)lane < in_block ? (in_block - (uint32_t)lane + 63u) / 64u : 0u;
+
+    // Range r keeps the lane's symbols i in [lo[r], hi[r]): position base + lane + 64 i inside [sym_lo[r], sym_hi[r]).
+    // Symbol i of range r goes to out[off[r] + 64 i]; off[r] + 64 i is the position inside the compact volume, so it
+    // lies inside range r's part of it for every kept i.  (An inverted range keeps nothing.)
+    uint32_t lo[2], hi[2];
+    long long off[2];
+    const unsigned long long p0 = base + (unsigned)lane;
+    unsigned long long before = 0;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const unsigned long long s0 = fj.sym_lo[r], s1 = fj.sym_hi[r];
+        const unsigned long long a = s0 > p0 ? (s0 - p0 + 63u) / 64u : 0ull;
+        const unsigned long long e = s1 > p0 ? (s1 - p0 + 63u) / 64u : 0ull;
+        lo[r] = (uint32_t)(a < k ? a : k);
+        hi[r] = (uint32_t)(e < k ? e : k);
+        if (hi[r] < lo[r]) hi[r] = lo[r];
+        off[r] = (long long)before + (long long)p0 - (long long)s0;
+        before += s1 > s0 ? s1 - s0 : 0ull;
+    }
+    SymT* __restrict__ out = (SymT*)job.sym;
+
+    const uint32_t blen = job.blk_len[b];
+    const unsigned long long boff = job.blk_off[b];
+    if (blen < 128u || boff + blen > job.len) { if (lane == 0) *job.flags = kSplitBadDirectory; return; }
+    const uint8_t* blk = job.stream + boff;
+    const uint32_t len = (uint32_t)blk[2 * lane] | ((uint32_t)blk[2 * lane + 1] << 8);
+    const uint32_t incl = wave_incl_scan(len, lane);
+    const uint32_t all = __shfl(incl, 63, 64);
+    if (all + 128u != blen) { if (lane == 0) *job.flags = kSplitBadDirectory; return; }
+    const uint8_t* __restrict__ src = blk + 128u + (incl - len);   // [src, src + len) lies inside the block
+
+    uint32_t win = 0u, nwin = 0u, fpos = 0u, pos = 0u;
+    auto take = [&]() -> uint32_t {
+        if (nwin == 0u) {
+            uint32_t w = 0u;
+            if (fpos + 4u <= len) {
+                uint32_t t;
+                __builtin_memcpy(&t, src + fpos, 4);
+                w = __builtin_bswap32(t);
+            } else {
+#pragma unroll
+                for (uint32_t t = 0; t < 4u; ++t) w = (w << 8) | (fpos + t < len ? (uint32_t)src[fpos + t] : 0u);
+            }
+            fpos += 4u;
+            win = w;
+            nwin = 4u;
+        }
+        const uint32_t byte = win >> 24;
+        win <<= 8;
+        --nwin;
+        ++pos;
+        return byte;
+    };
+    bool ok = true;
+    if (k == 0u) {
+        ok = len == 0u;
+    } else {
+        uint32_t x = take() << 24;
+        x |= take() << 16;
+        x |= take() << 8;
+        x |= take();
+        for (uint32_t i = 0; i < k; ++i) {
+            const uint32_t slot12 = x & (kProbScale - 1u);
+            uint32_t s = c2s[slot12];
+            const uint32_t fc = symtab[s];
+            x = (fc & 0xFFFFu) * (x >> kProbBits) + slot12 - (fc >> 16);
+            if (x < kRansL) x = (x << 8) | take();
+            if (x < kRansL) x = (x << 8) | take();
+            if (WIDE && s == 255u) {
+                s += x & kSplitWideMaxResidual;
+                x >>= 12;
+                if (x < kRansL) x = (x << 8) | take();
+                if (x < kRansL) x = (x << 8) | take();
+            }
+            if (i - lo[0] < hi[0] - lo[0]) out[off[0] + (long long)i * 64] = (SymT)s;
+            else if (i - lo[1] < hi[1] - lo[1]) out[off[1] + (long long)i * 64] = (SymT)s;
+        }
+        ok = x == kRansL && pos == len;
+    }
+    if (!ok) *job.flags = kSplitBadLane;
+}
+
+// ----------------------------------------------------------------------------------
 // Container header of whole chunks, one workgroup per chunk.
 // ----------------------------------------------------------------------------------
 __device__ __forceinline__ void put_le(uint8_t* p, unsigned long long v, int bytes) {
@@ -536,6 +653,11 @@ void launch_split_wide_write(const SplitJob* d_jobs, int n_jobs, uint32_t max_bl
 }
 void launch_split_wide_decode(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, hipStream_t st) {
     if (n_jobs > 0 && max_blocks) hipLaunchKernelGGL(split_wide_decode_kernel, split_grid(max_blocks, n_jobs), dim3(256), 0, st, d_jobs);
+}
+void launch_split_frames_decode(const SplitFramesJob* d_jobs, int n_jobs, uint32_t max_blocks, bool wide, hipStream_t st) {
+    if (n_jobs <= 0 || !max_blocks) return;
+    if (wide) hipLaunchKernelGGL(split_frames_decode_kernel<true>, split_grid(max_blocks, n_jobs), dim3(256), 0, st, d_jobs);
+    else hipLaunchKernelGGL(split_frames_decode_kernel<false>, split_grid(max_blocks, n_jobs), dim3(256), 0, st, d_jobs);
 }
 void launch_split_headers(const SplitHeaderDesc* d_descs, int n_chunks, hipStream_t st) {
     if (n_chunks > 0) hipLaunchKernelGGL(split_header_kernel, dim3(n_chunks), dim3(256), 0, st, d_descs);

@@ -725,7 +725,8 @@ __device__ __forceinline__ void store4<int16_t>(int16_t* p, const I4& x) {
 // one byte extract and one LDS read per sample instead of seven VALU operations.
 // WIDE (.alc v3): the symbols are u16 and are dequantised by arithmetic (z -> q -> q * step, wrapping), since z reaches 4350.
 // MIRROR (.alc v4): c0 .. c3 are the forward's coefficients and every step subtracts (lift_undo).
-template <int NS, bool EXACT, typename MidT, int PROBE = 0, bool WIDE = false, bool MIRROR = false>
+// WIN (frame ranges): only frames lo <= t < nf are stored, frame t at slot frame t - lo.
+template <int NS, bool EXACT, typename MidT, int PROBE = 0, bool WIDE = false, bool MIRROR = false, bool WIN = false>
 struct InvT {
     using Sym4 = std::conditional_t<WIDE, uint2, uint32_t>;   // the symbols of 4 pixels
     const char* src;      // channel base of the symbol volume
@@ -737,6 +738,7 @@ struct InvT {
     int c0, c1, c2, c3;   // already negated (MIRROR: as in the forward)
     const int* lut;
     int step;             // WIDE only
+    int lo;               // WIN only
     I4 o2p, e1p, o1pp, e0pp;
     int acc;              // PROBE only
 
@@ -767,7 +769,11 @@ struct InvT {
     }
     __device__ __forceinline__ void put(int frame, const I4& x) {
         if (PROBE & 2) { acc ^= (x.v[0] + frame) ^ x.v[1] ^ x.v[2] ^ x.v[3]; return; }
-        if (frame < nf) store4<MidT>(dst + (size_t)frame * plane_d, x);
+        if constexpr (WIN) {
+            if (frame >= lo && frame < nf) store4<MidT>(dst + (size_t)(frame - lo) * plane_d, x);
+        } else {
+            if (frame < nf) store4<MidT>(dst + (size_t)frame * plane_d, x);
+        }
     }
     template <bool FIRST, bool SECOND>
     __device__ __forceinline__ void tick(int k, Sym4 lo, Sym4 hi) {
@@ -886,6 +892,62 @@ __global__ __launch_bounds__(256) void inv_t_wide_kernel(InvTm a) {
     f.plane_s = a.b.plane; f.plane_d = a.b.band_px;
     f.off8 = band_plane_index(a.b, idx);
     f.half = (int)a.b.pf / 2; f.nf = (int)a.nf;
+    if (MIRROR) { f.c0 = a.cf.c[0]; f.c1 = a.cf.c[1]; f.c2 = a.cf.c[2]; f.c3 = a.cf.c[3]; }
+    else { f.c0 = -a.cf.c[0]; f.c1 = -a.cf.c[1]; f.c2 = -a.cf.c[2]; f.c3 = -a.cf.c[3]; }
+    f.lut = nullptr; f.step = a.step[ch];
+    f.run();
+}
+
+// The window instances (frame ranges): a.m describes the virtual chunk (b.pf = its planes, sym = its
+// compact symbol volume); frames [lo, hi) of it are stored, frame t at slot frame t - lo of a slot that holds pf_out frames
+// per channel -- the slot the tile role then reads as a chunk of hi - lo frames.  The fields the window adds live here, so
+// the instances above keep their arguments.
+struct InvTw {
+    InvTm m;
+    uint32_t lo, hi;             // lo < hi <= m.b.pf
+    uint32_t pf_out;             // frames per channel of the slot, >= hi - lo
+};
+
+template <int NS, bool EXACT, typename MidT>
+__global__ __launch_bounds__(256) void inv_t_win_kernel(InvTw w) {
+    __shared__ int lut[256];
+    const InvTm& a = w.m;
+    const int tid = threadIdx.x;
+    const int ch = (int)(blockIdx.x / a.b.units_per_ch);
+    const uint32_t blk = blockIdx.x % a.b.units_per_ch;
+    {
+        const int s = tid;
+        const int q = (s == 0) ? 0 : ((s & 1) ? (s + 1) / 2 : -(s / 2));      // src/quant.rs:581-587
+        lut[s] = (int)((unsigned)q * (unsigned)a.step[ch]);                   // src/quant.rs:104-110 (wrapping)
+    }
+    __syncthreads();
+    const uint32_t idx = (blk * 256u + (uint32_t)tid) * 4u;
+    if (idx >= a.b.band_px) return;
+    InvT<NS, EXACT, MidT, 0, false, false, true> f;
+    f.src = (const char*)(a.sym + (size_t)ch * a.b.pf * a.b.plane);
+    f.dst = (MidT*)a.mid + (size_t)ch * w.pf_out * a.b.band_px + idx;
+    f.plane_s = a.b.plane; f.plane_d = a.b.band_px;
+    f.off8 = band_plane_index(a.b, idx);
+    f.half = (int)a.b.pf / 2; f.nf = (int)w.hi; f.lo = (int)w.lo;
+    f.c0 = -a.cf.c[0]; f.c1 = -a.cf.c[1]; f.c2 = -a.cf.c[2]; f.c3 = -a.cf.c[3];
+    f.lut = lut;
+    f.run();
+}
+
+template <int NS, bool EXACT, typename MidT, bool MIRROR>
+__global__ __launch_bounds__(256) void inv_t_wide_win_kernel(InvTw w) {
+    const InvTm& a = w.m;
+    const int tid = threadIdx.x;
+    const int ch = (int)(blockIdx.x / a.b.units_per_ch);
+    const uint32_t blk = blockIdx.x % a.b.units_per_ch;
+    const uint32_t idx = (blk * 256u + (uint32_t)tid) * 4u;
+    if (idx >= a.b.band_px) return;
+    InvT<NS, EXACT, MidT, 0, true, MIRROR, true> f;
+    f.src = (const char*)((const uint16_t*)a.sym + (size_t)ch * a.b.pf * a.b.plane);
+    f.dst = (MidT*)a.mid + (size_t)ch * w.pf_out * a.b.band_px + idx;
+    f.plane_s = a.b.plane; f.plane_d = a.b.band_px;
+    f.off8 = band_plane_index(a.b, idx);
+    f.half = (int)a.b.pf / 2; f.nf = (int)w.hi; f.lo = (int)w.lo;
     if (MIRROR) { f.c0 = a.cf.c[0]; f.c1 = a.cf.c[1]; f.c2 = a.cf.c[2]; f.c3 = a.cf.c[3]; }
     else { f.c0 = -a.cf.c[0]; f.c1 = -a.cf.c[1]; f.c2 = -a.cf.c[2]; f.c3 = -a.cf.c[3]; }
     f.lut = nullptr; f.step = a.step[ch];
@@ -1535,9 +1597,16 @@ bool launch_forward_coef_hist(const RgbLayout& rgb, const ChunkDims& d, int wave
 // ---- inverse ----
 
 template <int NS, bool EXACT, typename MidT, bool PACKED, int PROBE = 0, bool WIDE = false, bool MIRROR = false>
-static void inv_band_launch(const InvTm& ta, const InvXy& xa, hipStream_t st) {
+static void inv_band_launch(const InvTm& ta, const InvXy& xa, hipStream_t st, const FrameWindow* win = nullptr) {
     static_assert(WIDE || !MIRROR, "the mirrored inverse belongs to a wide container (.alc v4)");
-    if constexpr (WIDE) hipLaunchKernelGGL((inv_t_wide_kernel<NS, EXACT, MidT, MIRROR>), dim3(3u * ta.b.units_per_ch), dim3(256), 0, st, ta);
+    if (win) {   // frame range: the temporal role's window instance; the tile role is the one below, over xa.d's frames
+        if constexpr (PROBE == 0) {
+            InvTw tw{};
+            tw.m = ta; tw.lo = win->lo; tw.hi = win->hi; tw.pf_out = (uint32_t)xa.d.pf;
+            if constexpr (WIDE) hipLaunchKernelGGL((inv_t_wide_win_kernel<NS, EXACT, MidT, MIRROR>), dim3(3u * ta.b.units_per_ch), dim3(256), 0, st, tw);
+            else hipLaunchKernelGGL((inv_t_win_kernel<NS, EXACT, MidT>), dim3(3u * ta.b.units_per_ch), dim3(256), 0, st, tw);
+        }
+    } else if constexpr (WIDE) hipLaunchKernelGGL((inv_t_wide_kernel<NS, EXACT, MidT, MIRROR>), dim3(3u * ta.b.units_per_ch), dim3(256), 0, st, ta);
     else hipLaunchKernelGGL((inv_t_kernel<NS, EXACT, MidT, PROBE>), dim3(3u * ta.b.units_per_ch), dim3(256), 0, st, ta);
     const unsigned long long tiles = (unsigned long long)xa.bt.nx * xa.bt.nby * xa.d.f;
     hipLaunchKernelGGL((inv_xy_kernel<NS, EXACT, MidT, PACKED, PROBE, MIRROR>), dim3(xcd_grid(tiles)), dim3(InvTileShape<PACKED>::kThreads), 0, st, xa);
@@ -1545,10 +1614,15 @@ static void inv_band_launch(const InvTm& ta, const InvXy& xa, hipStream_t st) {
 
 // WIDE: d_sym is the u16 symbol volume of .alc v3 and the temporal role runs its wide instance; everything else is shared.
 // MIRROR: both roles run their mirrored instances (.alc v4); the geometry, the bands and the instance choice are the same.
+// win (frame ranges): dt is the virtual chunk the temporal role lifts, and only its frames [lo, hi) reach the slot, the
+// tile role and `rgb`, as a chunk of hi - lo frames (d below); the bands are that chunk's.
 template <bool WIDE, bool MIRROR = false>
-static bool inverse_launches(const void* d_sym, const ChunkDims& d, int wavelet, const int32_t step[3],
-                             bool exact, bool mid16, bool lds16, void* d_scratch, const RgbLayout& rgb, hipStream_t st) {
-    if (!transform_tiles_eligible(d)) return false;
+static bool inverse_launches(const void* d_sym, const ChunkDims& dt, int wavelet, const int32_t step[3],
+                             bool exact, bool mid16, bool lds16, void* d_scratch, const RgbLayout& rgb, hipStream_t st,
+                             const FrameWindow* win = nullptr) {
+    if (!transform_tiles_eligible(dt)) return false;
+    if (win && !(win->lo < win->hi && win->hi <= dt.pf)) return false;
+    const ChunkDims d = win ? make_dims(dt.w, dt.h, win->hi - win->lo) : dt;
     const LiftSteps ls = lift_steps(wavelet);
     // mid16: the host proved every value after the inverse temporal pass fits i16 (then exact is false too);
     // lds16: also after the inverse column pass (packed tile).
@@ -1579,13 +1653,13 @@ static bool inverse_launches(const void* d_sym, const ChunkDims& d, int wavelet,
         const int rows_l = L1 - L0;
         InvTm ta{};
         ta.sym = (const uint8_t*)d_sym; ta.mid = d_scratch; ta.cf = cf; ta.step[0] = step[0]; ta.step[1] = step[1]; ta.step[2] = step[2]; ta.nf = d.f;
-        ta.b = make_band_t(d, 2u * (uint32_t)rows_l * pw, (uint32_t)rows_l * pw, (uint32_t)L0 * pw, (uint32_t)(hh + L0) * pw);
+        ta.b = make_band_t(dt, 2u * (uint32_t)rows_l * pw, (uint32_t)rows_l * pw, (uint32_t)L0 * pw, (uint32_t)(hh + L0) * pw);
         InvXy xa{};
         xa.mid = d_scratch; xa.rgb = rgb; xa.d = d; xa.cf = cf;
         xa.aligned = rgb_dword_aligned(rgb);
         xa.bt = BandTiles{(int)nx, by0, nby, 1, (int)ix1, 1, (int)iy1};
         xa.L0 = L0; xa.rows_l = rows_l;
-        if (probe) {
+        if (probe && !win) {
             if (probe == 1) inv_band_launch<4, false, int16_t, false, 3>(ta, xa, st);
             else if (probe == 2) inv_band_launch<4, false, int16_t, false, 1>(ta, xa, st);
             else inv_band_launch<4, false, int16_t, false, 2>(ta, xa, st);
@@ -1593,10 +1667,10 @@ static bool inverse_launches(const void* d_sym, const ChunkDims& d, int wavelet,
         }
 #define ALICE_INV(NS_) \
         switch (variant) { \
-        case 0: inv_band_launch<NS_, true, int32_t, false, 0, WIDE, MIRROR>(ta, xa, st); break; \
-        case 1: inv_band_launch<NS_, false, int32_t, false, 0, WIDE, MIRROR>(ta, xa, st); break; \
-        case 2: inv_band_launch<NS_, false, int16_t, false, 0, WIDE, MIRROR>(ta, xa, st); break; \
-        default: inv_band_launch<NS_, false, int16_t, true, 0, WIDE, MIRROR>(ta, xa, st); break; \
+        case 0: inv_band_launch<NS_, true, int32_t, false, 0, WIDE, MIRROR>(ta, xa, st, win); break; \
+        case 1: inv_band_launch<NS_, false, int32_t, false, 0, WIDE, MIRROR>(ta, xa, st, win); break; \
+        case 2: inv_band_launch<NS_, false, int16_t, false, 0, WIDE, MIRROR>(ta, xa, st, win); break; \
+        default: inv_band_launch<NS_, false, int16_t, true, 0, WIDE, MIRROR>(ta, xa, st, win); break; \
         }
         if (ls.n == 4) { ALICE_INV(4) } else { ALICE_INV(2) }
 #undef ALICE_INV
@@ -1615,6 +1689,13 @@ bool launch_inverse_transform_wide(const uint16_t* d_sym, const ChunkDims& d, in
 bool launch_inverse_transform_reversible(const uint16_t* d_sym, const ChunkDims& d, int wavelet, const int32_t step[3],
                                          bool exact, bool mid16, bool lds16, void* d_scratch, const RgbLayout& rgb, hipStream_t st) {
     return inverse_launches<true, true>(d_sym, d, wavelet, step, exact, mid16, lds16, d_scratch, rgb, st);
+}
+bool launch_inverse_transform_window(const void* d_sym, const ChunkDims& dv, const FrameWindow& win, int format, int wavelet,
+                                     const int32_t step[3], bool exact, bool mid16, bool lds16, void* d_scratch, const RgbLayout& rgb,
+                                     hipStream_t st) {
+    if (format == 2) return inverse_launches<true, true>(d_sym, dv, wavelet, step, exact, mid16, lds16, d_scratch, rgb, st, &win);
+    if (format == 1) return inverse_launches<true>(d_sym, dv, wavelet, step, exact, mid16, lds16, d_scratch, rgb, st, &win);
+    return inverse_launches<false>(d_sym, dv, wavelet, step, exact, mid16, lds16, d_scratch, rgb, st, &win);
 }
 
 

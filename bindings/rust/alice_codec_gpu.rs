@@ -1231,3 +1231,41 @@ pub unsafe fn wide_encode_to_psnr_device(d_frames: *const std::ffi::c_void, fram
     encode_to_psnr_device(ContainerFormat::Wide, d_frames, frame_width, frame_height, origins, width, height, frames, n_chunks,
                           wavelet_type, lane_symbols, min_psnr, min_quality, max_quality, d_out, out_stride, hip_stream)
 }
+
+// ---- frame ranges of a version 2, 3 or 4 chunk ----
+
+extern "C" {
+    fn alice_codec_frames_window(wavelet_type: u8, frames: u32, first: u32, count: u32, a: *mut u32, b: *mut u32) -> c_int;
+    fn alice_codec_decode_frames(data: *const u8, len: u64, first: u32, count: u32, out_len: *mut u64) -> *mut u8;
+    fn alice_codec_dev_decode_frames(d_alc: *const std::ffi::c_void, len: u64, first: u32, count: u32,
+                                     d_rgb_out: *mut std::ffi::c_void, hip_stream: *mut std::ffi::c_void) -> c_int;
+}
+
+/// `(a, b)`: frames `[first, first + count)` of a chunk of `frames` frames depend on the coefficient planes of the frame
+/// pairs inside `[a, b)` only.  No device needed.
+pub fn frames_window(wavelet_type: WaveletType, frames: u32, first: u32, count: u32) -> Result<(u32, u32), CodecError> {
+    let (mut a, mut b) = (0u32, 0u32);
+    let rc = unsafe { alice_codec_frames_window(wavelet_type as u8, frames, first, count, &mut a, &mut b) };
+    check(rc, 0, 0).map(|_| (a, b))
+}
+
+/// The RGB bytes of frames `[first, first + count)` of a version 2, 3 or 4 container, from the blocks they need: only the
+/// header, the block-length tables and those blocks are read and uploaded.  The end checks cover the blocks that are read;
+/// version 1 is `InvalidBitstream` (it has no random access).
+pub fn decode_frames(data: &[u8], first: u32, count: u32) -> Result<Vec<u8>, CodecError> {
+    let mut n = 0u64;
+    unsafe {
+        let p = alice_codec_decode_frames(data.as_ptr(), data.len() as u64, first, count, &mut n);
+        if p.is_null() { Err(last_error(0, data.len(), 0, 0, 0)) } else { Ok(take(p, n)) }
+    }
+}
+
+/// `decode_frames` of a device-resident container of `length` bytes into `count` packed frames at `d_rgb_out`.
+///
+/// # Safety
+/// As `split_decode_device`: `d_alc` holds `length` bytes and `d_rgb_out` room for `count` frames on the current device.
+pub unsafe fn frames_decode_device(d_alc: *const std::ffi::c_void, length: u64, first: u32, count: u32,
+                                   d_rgb_out: *mut std::ffi::c_void, hip_stream: *mut std::ffi::c_void)
+    -> Result<(), CodecError> {
+    check(alice_codec_dev_decode_frames(d_alc, length, first, count, d_rgb_out, hip_stream), 0, 0)
+}

@@ -672,6 +672,38 @@ uint8_t *alice_codec_encode_to_psnr(uint8_t format, uint8_t wavelet_type, const 
                                     uint32_t height, uint32_t frames, uint32_t lane_symbols, double min_psnr_db, uint8_t min_q,
                                     uint8_t max_q, uint8_t *chosen_q, uint8_t *reached, double *psnr, uint64_t *out_len);
 
+/* ---- frame ranges of a version 2, 3 or 4 chunk ----
+ * The lane formats cut a channel's symbols, coded in [t'][y][x] order, into blocks of 64 * lane_symbols symbols behind a
+ * table of their byte lengths, and the temporal transform is one lifting level: frames [first, first + count) depend on
+ * the coefficient planes of the frame pairs inside a window [a, b) only.  With pf the padded frame count (frames rounded up
+ * to even; 2 for 1), NS the wavelet's lifting steps (4 for CDF 9/7; 2 for CDF 5/3 and for Haar, whose predict step
+ * averages both even neighbours) and t1 = first + count:
+ *     a = max(0, (first - NS) & ~1)        b = min(pf, (t1 + NS + 1) & ~1)
+ * The planes a/2 .. b/2 of the low band and of the high band are the symbol volume of a chunk of b - a frames whose inverse
+ * temporal lifting equals the full chunk's at [first - a, t1 - a), bit for bit.  These calls decode the blocks that
+ * intersect those planes, run the temporal pass over them, and the spatial pass over `count` frames.  The pixels are the
+ * full decode's, the inverse instance is the full decode's (it depends on the wavelet and the quantiser steps alone).
+ * INTEGRITY: the whole block-length tables are checked, so a damaged table is refused wherever the damage is; the lane end
+ * checks cover the blocks that are decoded.  Damage inside a lane of any other block is NOT seen: a range may decode from
+ * a file whose full decode is refused.
+ * Validation is host code in this order: null arguments; the fixed fields and the magic; the version byte (1 is
+ * ALICE_ERR_INVALID_BITSTREAM, "version 1 has no random access (one serial chain per channel)"; anything but 2, 3, 4 is
+ * refused as unsupported); that version's header checks in their order; count >= 1 and first + count <=
+ * frames, else ALICE_ERR_INVALID_DIMENSIONS (so a chunk without pixels refuses every range).  Nothing is queued or written
+ * on a refusal.  Memory comes from the library's pool; nothing goes through the chain hub. */
+/* The window of a range; no device needed.  wavelet_type above 2: ALICE_ERR_INVALID_BITSTREAM; frames = 2^32 - 1 (its
+ * padded count does not fit b): ALICE_ERR_DIMENSION_OVERFLOW; count 0 or first + count above frames:
+ * ALICE_ERR_INVALID_DIMENSIONS. */
+int alice_codec_frames_window(uint8_t wavelet_type, uint32_t frames, uint32_t first, uint32_t count, uint32_t *a, uint32_t *b);
+/* One container in host memory -> count * height * width * 3 packed RGB bytes (free with alice_codec_data_free64), NULL on
+ * error.  Reads and uploads the 1630-byte header, the three block-length tables and the byte runs of the planned blocks,
+ * nothing else of `data` (which may be a mapped file); downloads `count` frames. */
+uint8_t *alice_codec_decode_frames(const uint8_t *data, uint64_t len, uint32_t first, uint32_t count, uint64_t *out_len);
+/* The same for a container of `len` bytes on the device (any byte alignment) into count packed frames at d_rgb_out, which
+ * must not overlap it.  The header is read back first.  Finished on return. */
+int alice_codec_dev_decode_frames(const void *d_alc, uint64_t len, uint32_t first, uint32_t count, void *d_rgb_out,
+                                  void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -736,6 +736,29 @@ inline std::vector<uint8_t> decode_alc(const std::vector<uint8_t>& data) {
     return FrameDecoder::new_().decode(EncodedChunk::from_bytes(data));
 }
 
+// ---- frame ranges of a version 2, 3 or 4 chunk ----
+// frames [first, first + count) from the blocks they need; the end checks cover the blocks that are read
+struct FramesWindow { uint32_t a, b; };
+inline FramesWindow frames_window(WaveletType wt, uint32_t frames, uint32_t first, uint32_t count) {
+    FramesWindow w{0, 0};
+    detail::check(alice_codec_frames_window(static_cast<uint8_t>(wt), frames, first, count, &w.a, &w.b));
+    return w;
+}
+inline std::vector<uint8_t> decode_frames(const uint8_t* data, uint64_t len, uint32_t first, uint32_t count) {
+    static const uint8_t empty = 0;
+    uint64_t n = 0;
+    uint8_t* p = alice_codec_decode_frames(data ? data : &empty, data ? len : 0, first, count, &n);
+    if (!p) detail::raise(ALICE_ERR_INVALID_BITSTREAM);
+    return detail::take(p, n);
+}
+inline std::vector<uint8_t> decode_frames(const std::vector<uint8_t>& data, uint32_t first, uint32_t count) {
+    return decode_frames(data.empty() ? nullptr : data.data(), data.size(), first, count);
+}
+inline void frames_decode_device(const void* d_alc, uint64_t length, uint32_t first, uint32_t count, void* d_rgb_out,
+                                 void* hip_stream = nullptr) {
+    detail::check(alice_codec_dev_decode_frames(d_alc, length, first, count, d_rgb_out, hip_stream));
+}
+
 // version 2 rate control: the bracket of encode_split's length at the 101 qualities (every version 2 table
 // is bounded: status stays ALICE_RATE_BOUNDED) and one encode at the quality the budget rule picks -- the largest whose
 // upper bound fits, refined by at most ALICE_SPLIT_REFINE_TRIALS exact size counts among the straddling qualities

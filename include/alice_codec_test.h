@@ -133,6 +133,11 @@ uint64_t alice_codec_test_inverse_scratch_bytes(uint32_t width, uint32_t height,
  * buffers of n bytes: *sse (host) = the sum.  For the probes that time it beside alice_codec_dev_rgb_sse. */
 int alice_codec_test_sq_diff_sum(const void *d_a, const void *d_b, uint64_t n, uint64_t *sse, void *hip_stream);
 
+/* The last alice_codec_decode_frames / alice_codec_dev_decode_frames of the calling thread that reached the device:
+ * out = {a, b of the window, blocks decoded over the three channels, payload bytes the host call uploaded (the planned
+ * blocks; 0 for the device call), frames given to the spatial pass}. */
+void alice_codec_test_last_frames_stats(uint64_t out[5]);
+
 #ifdef __cplusplus
 }
 #endif
