@@ -4893,13 +4893,16 @@ int frames_decode_device(const SplitHeader& h, const ChunkDims& d, const uint8_t
         return kOk;
     };
     TRY(split_decode_launch(w, &h.freq[0][0], st, &lane_decode));
+    // The verdict of the end checks comes before anything is queued that writes d_rgb: a range that is refused for damage
+    // in a planned block leaves its output alone, as one that is refused by the validation does.
+    TRY(split_decode_verdict(w, st));
     TRY(inverse_window(dw.sym.as<uint8_t>(), dv, first - p.a, first - p.a + count, h.wavelet, h.step, dw.scratch_own.p, dw,
                        packed_rgb(d_rgb, dx), st, fmt));
     HIP_TRY(hipGetLastError());
-    const int rc = split_decode_verdict(w, st);
+    HIP_TRY(hipStreamSynchronize(st));
     tl_frames_stats[0] = p.a; tl_frames_stats[1] = p.b; tl_frames_stats[2] = 3ull * p.blocks();
     tl_frames_stats[3] = uploaded; tl_frames_stats[4] = count;
-    return rc;
+    return kOk;
 }
 
 }  // namespace

@@ -685,7 +685,8 @@ uint8_t *alice_codec_encode_to_psnr(uint8_t format, uint8_t wavelet_type, const 
  * full decode's, the inverse instance is the full decode's (it depends on the wavelet and the quantiser steps alone).
  * INTEGRITY: the whole block-length tables are checked, so a damaged table is refused wherever the damage is; the lane end
  * checks cover the blocks that are decoded.  Damage inside a lane of any other block is NOT seen: a range may decode from
- * a file whose full decode is refused.
+ * a file whose full decode is refused.  A range that is refused for damage in a decoded block writes nothing to d_rgb_out:
+ * the verdict of the end checks is read before the inverse is queued.
  * Validation is host code in this order: null arguments; the fixed fields and the magic; the version byte (1 is
  * ALICE_ERR_INVALID_BITSTREAM, "version 1 has no random access (one serial chain per channel)"; anything but 2, 3, 4 is
  * refused as unsupported); that version's header checks in their order; count >= 1 and first + count <=

@@ -42,9 +42,9 @@ def _guard_pattern(n):
     return torch.tensor([0, 255], dtype=torch.uint8, device=DEV).repeat((n + 1) // 2)[:n]
 
 
-def _encode(a, version, rgb, w, h, f, q, kind):
+def _encode(a, version, rgb, w, h, f, q, kind, lane=L):
     enc = a.FrameEncoder.with_wavelet(q, a.WaveletType(kind))
-    return {2: a.encode_split, 3: a.encode_wide, 4: a.encode_reversible}[version](enc, rgb, w, h, f, L)
+    return {2: a.encode_split, 3: a.encode_wide, 4: a.encode_reversible}[version](enc, rgb, w, h, f, lane)
 
 
 def _full_decode(a, version, blob):
@@ -59,14 +59,18 @@ class Chunk:
     """One encoded chunk, its full decode on the device, and the buffers of the calls: the container at an odd device
     address, the output between guard bytes of 0 and 255."""
 
-    def __init__(self, a, version, shape, kind, q=None, seed=None):
+    def __init__(self, a, version, shape, kind, q=None, seed=None, lane=L, blob=None):
+        """blob: a container made elsewhere (nothing is encoded or fully decoded here: full and full_dev stay None)"""
         self.a, self.version, self.shape, self.kind = a, version, tuple(shape), kind
         w, h, f = shape
-        self.q = quality_for(shape, kind, version) if q is None else q
-        self.rgb = WO.smooth_plus_noise(w, h, f, seed=(w * 7 + f) if seed is None else seed)
-        self.blob = _encode(a, version, self.rgb, w, h, f, self.q, kind)
-        self.full = np.asarray(_full_decode(a, version, self.blob))
-        self.full_dev = torch.from_numpy(self.full.copy()).to(DEV)
+        if blob is None:
+            self.q = quality_for(shape, kind, version) if q is None else q
+            self.rgb = WO.smooth_plus_noise(w, h, f, seed=(w * 7 + f) if seed is None else seed)
+            self.blob = _encode(a, version, self.rgb, w, h, f, self.q, kind, lane)
+            self.full = np.asarray(_full_decode(a, version, self.blob))
+            self.full_dev = torch.from_numpy(self.full.copy()).to(DEV)
+        else:
+            self.q, self.rgb, self.blob, self.full, self.full_dev = None, None, bytes(blob), None, None
         self.frame_bytes = w * h * 3
         self.out = torch.empty(2 * GUARD + f * self.frame_bytes, dtype=torch.uint8, device=DEV)
         self.pattern = _guard_pattern(self.out.numel())

@@ -13,6 +13,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import split_ref as R2  # noqa: E402
 import transform_extremes as X  # noqa: E402
+from transform_extremes import EXPECTED_VARIANTS, byte_step_cases, classes, edge_steps, variant  # noqa: E402
 import wide_oracle as WO  # noqa: E402
 import wide_ref as R3  # noqa: E402
 from slab_oracle_stages import OracleStages  # noqa: E402
@@ -25,43 +26,7 @@ DEV = "cuda:0"
 GUARD = 64
 CDF53, CDF97, HAAR = 0, 1, 2
 KINDS = (CDF53, CDF97, HAAR)
-EXPECTED_VARIANTS = {CDF53: {0, 1, 2, 3}, CDF97: {0, 2, 3}, HAAR: {0, 1, 2, 3}}     # CDF 9/7 has no fast i32 class
 _ran = {(k, wide): set() for k in KINDS for wide in (0, 1)}      # variants the tile kernels ran in this process
-
-
-def variant(lib, kind, steps, wide=0):
-    return lib.alice_codec_test_inverse_variant(kind, (C.c_int32 * 3)(*[int(s) for s in steps]), wide)
-
-
-def classes(lib, kind, wide):
-    """[(variant, first step, last step)] over steps 1 .. 400, in the order of the steps; the last class is still open"""
-    out = []
-    for s in range(1, 401):
-        v = variant(lib, kind, (s, s, s), wide)
-        if out and out[-1][0] == v:
-            out[-1][2] = s
-        else:
-            out.append([v, s, s])
-    return [tuple(c) for c in out]
-
-
-def edge_steps(lib, kind, wide):
-    """[(steps, variant)]: the first and the last step of every class (the open end of the exact class left out)"""
-    cl = classes(lib, kind, wide)
-    cases = []
-    for i, (v, first, last) in enumerate(cl):
-        for s in (first, last) if i + 1 < len(cl) else (first,):
-            if ((s, s, s), v) not in cases:
-                cases.append(((s, s, s), v))
-    return cases
-
-
-def byte_step_cases(lib, kind):
-    cl = classes(lib, kind, 0)
-    cases = edge_steps(lib, kind, 0) + [((70000,) * 3, 0), ((1 << 20,) * 3, 0)]
-    v, _, top = cl[-2]      # the last step of the last class before exact, in another channel each time
-    cases += [((top, 1, 2), v), ((2, top, 1), v), ((1, 2, top), v)]
-    return cases
 
 
 # (w, h, f) -> band target in KiB (None: the default) and the centres (t, y, x) of the two worst volumes.  Inverse tiles

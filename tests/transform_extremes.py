@@ -10,6 +10,8 @@ Measured with these functions (any length >= 4): inverse gain 2.0 for CDF 5/3 an
 (a single frame, padded) has 1.75 / 1.434 / 1.5.  The forward gains are the same three numbers."""
 from __future__ import annotations
 
+import ctypes as C
+
 import numpy as np
 
 import oracle.alice_oracle_np as o
@@ -127,3 +129,45 @@ def inverse_quantised_steps(qs, steps, dims, w: int, h: int, f: int, kind: int) 
         vol = o.wavelet3d(kind, dequantised(q, step), pw, ph, pf, inverse=True).reshape(pf, ph, pw)
         chans.append(o._wrap16(vol[:f, :h, :w].reshape(-1)))
     return o.ycocg_r_to_rgb(*chans)
+
+
+# ---- the quantiser steps at which the launcher changes the instance class, read from the library ----
+CDF53, CDF97, HAAR = 0, 1, 2
+EXPECTED_VARIANTS = {CDF53: {0, 1, 2, 3}, CDF97: {0, 2, 3}, HAAR: {0, 1, 2, 3}}     # u8 symbols; CDF 9/7 has no fast i32 class
+
+
+def variant(lib, kind, steps, wide=0):
+    return lib.alice_codec_test_inverse_variant(kind, (C.c_int32 * 3)(*[int(s) for s in steps]), wide)
+
+
+def classes(lib, kind, wide):
+    """[(variant, first step, last step)] over steps 1 .. 400, in the order of the steps; the last class is still open"""
+    out = []
+    for s in range(1, 401):
+        v = variant(lib, kind, (s, s, s), wide)
+        if out and out[-1][0] == v:
+            out[-1][2] = s
+        else:
+            out.append([v, s, s])
+    return [tuple(c) for c in out]
+
+
+def edge_steps(lib, kind, wide):
+    """[(steps, variant)]: the first and the last step of every class (the open end of the exact class left out)"""
+    cl = classes(lib, kind, wide)
+    cases = []
+    for i, (v, first, last) in enumerate(cl):
+        for s in (first, last) if i + 1 < len(cl) else (first,):
+            if ((s, s, s), v) not in cases:
+                cases.append(((s, s, s), v))
+    return cases
+
+
+def byte_step_cases(lib, kind):
+    """the step plan of the u8 symbols: edge_steps, two steps whose products wrap i32, and the last step of the last class
+    before exact in another channel each time"""
+    cl = classes(lib, kind, 0)
+    cases = edge_steps(lib, kind, 0) + [((70000,) * 3, 0), ((1 << 20,) * 3, 0)]
+    v, _, top = cl[-2]
+    cases += [((top, 1, 2), v), ((2, top, 1), v), ((1, 2, top), v)]
+    return cases
