@@ -320,6 +320,10 @@ def load_library() -> C.CDLL:
         "alice_codec_decode_frames": (vp, [_u8p, C.c_uint64, C.c_uint32, C.c_uint32, _u64p]),
         "alice_codec_dev_decode_frames": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp]),
         "alice_codec_test_last_frames_stats": (None, [_u64p]),
+        "alice_codec_preview_dims": (C.c_int, [C.c_uint32, C.c_uint32, _u32p, _u32p]),
+        "alice_codec_decode_preview": (vp, [_u8p, C.c_uint64, C.c_uint32, C.c_uint32, _u64p]),
+        "alice_codec_dev_decode_preview": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp]),
+        "alice_codec_test_last_preview_stats": (None, [_u64p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
@@ -2252,6 +2256,45 @@ def _test_last_frames_stats() -> tuple:
     the calling thread's last frame-range decode."""
     out = np.zeros(5, np.uint64)
     load_library().alice_codec_test_last_frames_stats(_p(out, _u64p))
+    return tuple(int(v) for v in out)
+
+
+# ---- half-resolution preview of a version 2, 3 or 4 chunk from the low band alone (DESIGN.md section 15) ----
+
+def preview_dims(width: int, height: int) -> tuple:
+    """(qw, qh) = (ceil(width / 2), ceil(height / 2)): the size of a preview frame.  No device needed."""
+    _dims_u32(width, height)
+    qw, qh = C.c_uint32(0), C.c_uint32(0)
+    _check(load_library().alice_codec_preview_dims(width, height, C.byref(qw), C.byref(qh)))
+    return qw.value, qh.value
+
+
+def decode_preview(data, first: int, count: int) -> np.ndarray:
+    """The half-resolution RGB bytes (count * qh * qw * 3) of frames [first, first + count) of a version 2, 3 or 4 container,
+    from the low-low quadrants of the coefficient planes the range needs: only the header, the block-length tables and the
+    blocks of the planes' top halves are read and uploaded (data may be an np.memmap), and no spatial inverse runs.  The end
+    checks cover the blocks that are read."""
+    lib = load_library()
+    buf = _as_u8(data)
+    _dims_u32(first, count)
+    n = C.c_uint64(0)
+    ptr = lib.alice_codec_decode_preview(_p(buf, _u8p), buf.size, first, count, C.byref(n))
+    if not ptr:
+        _raise_last()
+    return _adopt(ptr, n.value, lib.alice_codec_data_free64)
+
+
+def preview_decode_device(d_alc_ptr: int, length: int, first: int, count: int, d_rgb_out_ptr: int, stream: int = 0) -> None:
+    """decode_preview of a device-resident container of `length` bytes into count packed preview frames at d_rgb_out_ptr."""
+    _dims_u32(first, count)
+    _check(load_library().alice_codec_dev_decode_preview(d_alc_ptr, length, first, count, d_rgb_out_ptr, stream or None))
+
+
+def _test_last_preview_stats() -> tuple:
+    """(a, b, blocks decoded over the three channels, payload bytes the host call uploaded, frames written, symbols stored
+    over the three channels) of the calling thread's last preview decode."""
+    out = np.zeros(6, np.uint64)
+    load_library().alice_codec_test_last_preview_stats(_p(out, _u64p))
     return tuple(int(v) for v in out)
 
 

@@ -29,7 +29,7 @@ import sys
 import numpy as np
 
 from . import (DEFAULT_CHUNK_SIZE, CodecError, EncodedChunk, FrameDecoder, FrameEncoder, WaveletType, budget_bytes_per_chunk,
-               alc_version, decode_frames, decode_reversible, decode_split, decode_wide, encode_many, encode_reversible, encode_split,
+               alc_version, decode_frames, decode_preview, decode_reversible, decode_split, decode_wide, encode_many, encode_reversible, encode_split,
                encode_split_to_psnr, encode_split_to_size, encode_to_size, encode_wide, encode_wide_to_psnr, reversible_info,
                split_info, wide_info)
 
@@ -276,7 +276,25 @@ def cmd_decode_frames(a) -> None:
     print(f"decoded frames [{first}, {end}) of {width}x{height}x{frames} -> {rgb.size} bytes (raw RGB)", file=sys.stderr)
 
 
+def cmd_decode_preview(a) -> None:
+    """--preview alone: every frame; with --frames A[:B]: that range.  Half resolution, from the low band alone."""
+    data = np.memmap(a.input, dtype=np.uint8, mode="r")
+    if a.format != "auto" and data.size > 4 and int(data[4]) != FORMAT_VERSION[a.format]:
+        raise ValueError(f"--format {a.format} names version {FORMAT_VERSION[a.format]}, the file's version byte is {int(data[4])}")
+    if data.size < 18:
+        raise ValueError(f"{a.input}: too short for a container header")
+    width, height, frames = (int(v) for v in np.frombuffer(bytes(data[6:18]), "<u4"))
+    first, end = parse_frames(a.frames) if a.frames is not None else (0, frames)
+    rgb = decode_preview(data, first, end - first)
+    rgb.tofile(a.output)
+    qw, qh = (width + 1) // 2, (height + 1) // 2
+    print(f"decoded preview {qw}x{qh} of frames [{first}, {end}) of {width}x{height}x{frames} -> {rgb.size} bytes (raw RGB)", file=sys.stderr)
+
+
 def cmd_decode(a) -> None:
+    if a.preview:
+        cmd_decode_preview(a)
+        return
     if a.frames is not None:
         cmd_decode_frames(a)
         return
@@ -373,6 +391,9 @@ def main(argv=None) -> int:
     d.add_argument("-o", "--output", required=True)
     d.add_argument("--frames", default=None, metavar="A[:B]",
                    help="write frames [A, B) only (A alone: one frame), decoded from the blocks they need; versions 2, 3 and 4")
+    d.add_argument("--preview", action="store_true",
+                   help="write half-resolution frames (ceil(W/2) x ceil(H/2)) decoded from the low band alone: all frames, or those of "
+                        "--frames; versions 2, 3 and 4")
     i = sub.add_parser("info")
     i.add_argument("input")
     for x in (d, i):

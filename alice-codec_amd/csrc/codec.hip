@@ -5005,3 +5005,198 @@ void alice_codec_test_last_frames_stats(uint64_t out[5]) {
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// PART 9: half-resolution preview of a version 2, 3 or 4 chunk from the low band alone (kernels:
+// split_preview_decode_kernel of split.hip, preview_inv_kernel of transform.hip)
+//
+// The spatial transform is one lifting level, so the low-low quadrant [0, ph/2) x [0, pw/2) of every coefficient plane is a
+// half-size picture.  A frame range needs the quadrants of PART 8's window [a, b) (the temporal lifting runs per (y, x), so
+// the window rule carries over to a sub-rectangle of the planes); the top half of a plane is one contiguous symbol run, so
+// the blocks of the bottom half are never entropy-decoded, and no spatial inverse runs at all.
+// ------------------------------------------------------------------------------------------
+
+namespace {
+
+struct PreviewPlan {
+    uint32_t a = 0, b = 0;
+    uint64_t qw = 0, qh = 0, pitch = 0;       // quadrant, and the plane pitch of the compact volume (qw * qh rounded up to 4)
+    std::vector<uint32_t> blocks;             // ascending, no duplicates; the three channels are alike
+};
+
+// the union, over the window's planes t', of the blocks that intersect [t' P, t' P + (qh - 1) pw + qw)
+PreviewPlan preview_plan(const SplitHeader& h, const ChunkDims& d, uint32_t first, uint32_t count) {
+    PreviewPlan p;
+    frames_window(h.wavelet, h.frames, first, count, &p.a, &p.b);
+    p.qw = d.pw / 2; p.qh = d.ph / 2;
+    p.pitch = round_up(p.qw * p.qh, 4);
+    const uint64_t P = d.pw * d.ph, half = d.pf / 2, B = 64ull * h.lane_symbols, run = (p.qh - 1) * d.pw + p.qw;
+    for (int band = 0; band < 2; ++band)
+        for (uint64_t t = p.a / 2; t < p.b / 2; ++t) {
+            const uint64_t lo = (band * half + t) * P, hi = lo + run;
+            for (uint64_t blk = lo / B; blk <= (hi - 1) / B; ++blk)
+                if (p.blocks.empty() || blk > p.blocks.back()) p.blocks.push_back((uint32_t)blk);
+        }
+    return p;
+}
+
+thread_local uint64_t tl_preview_stats[6] = {0, 0, 0, 0, 0, 0};   // alice_codec_test_last_preview_stats
+
+// The preview of frames [first, first + count) of the container at d_alc (device, h validated) to d_rgb (device,
+// count * qh * qw * 3 bytes).  Of the payloads only the block-length tables and the planned blocks are read.  Returns after
+// the stream has drained.
+int preview_decode_device(const SplitHeader& h, const ChunkDims& d, const PreviewPlan& p, const uint8_t* d_alc, uint32_t first,
+                          uint32_t count, void* d_rgb, hipStream_t st, uint64_t uploaded) {
+    const SplitFormat fmt = h.fmt;
+    const bool wide = is_wide(fmt);
+    const size_t sb = wide ? 2 : 1;
+    const uint32_t planes = p.b - p.a;
+    DevBuf d_sym, d_pj;                      // (declared before w: w's destructor drains the stream that reads them)
+    std::vector<SplitPreviewJob> pj(3);
+    // one upload: the three jobs, then the block list they share
+    const size_t jobs_bytes = 3 * sizeof(SplitPreviewJob), list_bytes = p.blocks.size() * sizeof(uint32_t);
+    std::vector<uint8_t> up(jobs_bytes + list_bytes);
+    // the pad symbols of a plane (pitch - qw * qh < 4) are never stored; the finish loads them with a group's real ones
+    // and drops what it computes from them, so they need no value
+    TRY(d_sym.alloc(3 * (size_t)planes * p.pitch * sb));
+    TRY(d_pj.alloc(up.size()));
+    SplitWork w;
+    TRY(split_work_alloc(w, 3, d.padded, h.lane_symbols, false, fmt));
+    uint64_t off = kSplitHeaderBytes;
+    for (int c = 0; c < 3; ++c) {
+        SplitJob& s = w.h[(size_t)c];
+        s.sym = d_sym.as<uint8_t>() + (size_t)c * planes * p.pitch * sb;
+        s.stream = (uint8_t*)d_alc + off;
+        s.len = h.payload_len[c];
+        off += s.len;
+    }
+    for (int c = 0; c < 3; ++c) {
+        SplitPreviewJob& j = pj[(size_t)c];
+        j.j = w.h[(size_t)c];
+        j.blocks = (const uint32_t*)(d_pj.as<uint8_t>() + jobs_bytes); j.n_planned = (uint32_t)p.blocks.size();
+        j.pw = (uint32_t)d.pw; j.ph = (uint32_t)d.ph; j.qw = (uint32_t)p.qw; j.qh = (uint32_t)p.qh;
+        j.t_lo = p.a / 2; j.half = (uint32_t)(d.pf / 2); j.hw = planes / 2;
+        j.pitch = p.pitch;
+    }
+    // the jobs and the list go up first, while nothing of this call is queued yet
+    memcpy(up.data(), pj.data(), jobs_bytes);
+    memcpy(up.data() + jobs_bytes, p.blocks.data(), list_bytes);
+    w.st = st; w.armed = true;
+    HIP_TRY(hipMemcpyAsync(d_pj.p, up.data(), up.size(), hipMemcpyHostToDevice, st));
+    const std::function<int()> lane_decode = [&]() -> int {
+        launch_split_preview_decode(d_pj.as<SplitPreviewJob>(), 3, (uint32_t)p.blocks.size(), wide, st);
+        return kOk;
+    };
+    TRY(split_decode_launch(w, &h.freq[0][0], st, &lane_decode));
+    // as in PART 8: the verdict of the end checks comes before anything is queued that writes d_rgb
+    TRY(split_decode_verdict(w, st));
+    // EXACT is the full chunk's verdict: the first pass inverse_bounds looks at is the temporal one
+    const InverseBounds ib = inverse_bounds(h.wavelet, h.step, wide ? kWideMaxQ : kByteMaxQ);
+    if (!launch_preview_inverse(d_sym.p, p.pitch, p.qw * p.qh, planes, FrameWindow{first - p.a, first - p.a + count}, (int)fmt, h.wavelet,
+                                h.step, ib.exact, (uint8_t*)d_rgb, st))
+        return fail(kInternal, "preview: no finish kernel for this volume");
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    tl_preview_stats[0] = p.a; tl_preview_stats[1] = p.b; tl_preview_stats[2] = 3ull * p.blocks.size();
+    tl_preview_stats[3] = uploaded; tl_preview_stats[4] = count; tl_preview_stats[5] = 3ull * planes * p.qw * p.qh;
+    return kOk;
+}
+
+}  // namespace
+
+extern "C" {
+
+int alice_codec_preview_dims(uint32_t width, uint32_t height, uint32_t* qw, uint32_t* qh) {
+    clear_error();
+    if (!qw || !qh) return fail(kNullArgument, "null argument");
+    if (width == 0 || height == 0) return fail(kInvalidDimensions, "invalid dimensions");
+    *qw = (uint32_t)(((uint64_t)width + 1) / 2);
+    *qh = (uint32_t)(((uint64_t)height + 1) / 2);
+    return kOk;
+}
+
+int alice_codec_dev_decode_preview(const void* d_alc, uint64_t len, uint32_t first, uint32_t count, void* d_rgb_out, void* hip_stream) {
+    clear_error();
+    if (!d_alc || !d_rgb_out) return fail(kNullArgument, "null argument");
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);
+    // the header comes to the host first; nothing is queued before it and the range have been accepted
+    uint8_t raw[kSplitHeaderBytes] = {};
+    if (len) {
+        HIP_TRY(hipMemcpyAsync(raw, d_alc, std::min<uint64_t>(len, kSplitHeaderBytes), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    SplitHeader h;
+    ChunkDims d{};
+    TRY(frames_validate(raw, len, first, count, h, d));
+    return preview_decode_device(h, d, preview_plan(h, d, first, count), (const uint8_t*)d_alc, first, count, d_rgb_out, st, 0);
+}
+
+uint8_t* alice_codec_decode_preview(const uint8_t* data, uint64_t len, uint32_t first, uint32_t count, uint64_t* out_len) {
+    clear_error();
+    if (!data || !out_len) { fail(kNullArgument, "null argument"); return nullptr; }
+    auto run = [&](uint8_t** out) -> int {
+        SplitHeader h;
+        ChunkDims d{};
+        TRY(frames_validate(data, len, first, count, h, d));
+        const PreviewPlan p = preview_plan(h, d, first, count);
+        // As alice_codec_decode_frames does: block offsets from the tables, on the host, with the directory verdict on the
+        // way; the header, the three tables and the byte runs of consecutive planned blocks go up at their own offsets.
+        struct Span { uint64_t off, len; };
+        std::vector<Span> spans;
+        spans.push_back({0, kSplitHeaderBytes});
+        uint64_t payload_bytes = 0, pos = kSplitHeaderBytes;
+        for (int c = 0; c < 3; ++c) {
+            const uint8_t* tab = data + pos;
+            const uint32_t nb = h.n_blocks[c];
+            spans.push_back({pos, 4ull * nb});
+            uint64_t sum = 4ull * nb;
+            size_t next = 0;            // the next planned block
+            bool open = false;          // the last span ends where this block starts
+            for (uint32_t blk = 0; blk < nb; ++blk) {
+                const uint32_t v = get_u32(tab + 4ull * blk);
+                if (v < 128u) return fail(kInvalidBitstream, "channel " + std::to_string(c) + ": block " + std::to_string(blk) + " is shorter than its lane directory");
+                if (sum + v > h.payload_len[c]) { sum += v; break; }   // (the sum below refuses it; no span may leave the payload)
+                if (next < p.blocks.size() && p.blocks[next] == blk) {
+                    if (open) spans.back().len += v; else spans.push_back({pos + sum, v});
+                    payload_bytes += v;
+                    open = true;
+                    ++next;
+                } else {
+                    open = false;
+                }
+                sum += v;
+            }
+            if (sum != h.payload_len[c])
+                return fail(kInvalidBitstream, "channel " + std::to_string(c) + ": block lengths do not sum to payload_len " + std::to_string(h.payload_len[c]));
+            pos += h.payload_len[c];
+        }
+        const uint64_t bytes = p.qw * p.qh * count * 3;
+        *out = host_result_alloc(bytes);
+        if (!*out) return fail(kOutOfMemory, "out of host memory");
+        *out_len = bytes;
+        auto body = [&]() -> int {
+            hipStream_t st;
+            TRY(get_stream(&st));
+            DevBuf d_alc, d_rgb;
+            TRY(d_alc.alloc(len));
+            TRY(d_rgb.alloc(bytes));
+            for (const Span& s : spans)
+                HIP_TRY(hipMemcpyAsync(d_alc.as<uint8_t>() + s.off, data + s.off, s.len, hipMemcpyHostToDevice, st));
+            TRY(preview_decode_device(h, d, p, d_alc.as<uint8_t>(), first, count, d_rgb.p, st, payload_bytes));
+            return copy_to_host(*out, d_rgb.p, bytes, st);
+        };
+        const int rc = body();
+        if (rc != kOk) { free(*out); *out = nullptr; }
+        return rc;
+    };
+    uint8_t* out = nullptr;
+    return run(&out) == kOk ? out : nullptr;
+}
+
+void alice_codec_test_last_preview_stats(uint64_t out[6]) {
+    if (out) memcpy(out, tl_preview_stats, sizeof(tl_preview_stats));
+}
+
+}  // extern "C"

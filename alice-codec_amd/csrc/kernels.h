@@ -183,6 +183,15 @@ struct FrameWindow { uint32_t lo, hi; };
 bool launch_inverse_transform_window(const void* d_sym, const ChunkDims& dv, const FrameWindow& win, int format, int wavelet,
                                      const int32_t step[3], bool exact, bool mid16, bool lds16, void* d_scratch, const RgbLayout& rgb,
                                      hipStream_t st);
+// Half-resolution preview: d_sym is the compact volume [3][planes][pitch] of the low-low quadrants of a
+// virtual chunk's planes (u8 for format 0, u16 for 1 and 2; pitch a multiple of 4, q = qw * qh <= pitch quadrant pixels per
+// plane).  One fused launch: symbols -> dequantise -> inverse temporal lifting of the three channels in lock step -> DC
+// normalisation -> `as i16` -> colour; frames [win.lo, win.hi) of the virtual chunk go to d_rgb as (hi - lo) * q * 3 packed
+// bytes.  No tile geometry: every shape takes this path.  False (nothing launched): arguments that are no such volume.
+constexpr int kPreviewGainOne = 65536;    // CDF 5/3, Haar: the low band's DC gain is exactly 1
+constexpr int kPreviewGain97 = 47484;     // CDF 9/7: round(65536 / g^2), g = 1.17480326 per spatial axis
+bool launch_preview_inverse(const void* d_sym, uint64_t pitch, uint64_t q, uint32_t planes, const FrameWindow& win, int format,
+                            int wavelet, const int32_t step[3], bool exact, uint8_t* d_rgb, hipStream_t st);
 
 // ---- transform.hip, stage level: Wavelet2D / Wavelet3D of caller-shaped i32 data on the tile kernels' exact instances ----
 // eligible: even width and height >= 6, even depth (or depth 1); otherwise the caller uses launch_wavelet_axis.
@@ -327,6 +336,18 @@ struct SplitFramesJob {
     uint32_t blk_first[2], blk_count[2];
     unsigned long long sym_lo[2], sym_hi[2];
 };
+// Half-resolution preview: the n_planned blocks blocks[0 .. n_planned) of channel `j` (ascending, no
+// duplicates) are decoded.  A symbol at channel position p = (t' * ph + y) * pw + x is stored only when t' lies in
+// [t_lo, t_lo + hw) (low band, plane t' - t_lo of the compact volume) or in [half + t_lo, half + t_lo + hw) (high band,
+// plane hw + ...), y < qh and x < qw: at j.sym[plane * pitch + y * qw + x].  pitch >= qw * qh.
+struct SplitPreviewJob {
+    SplitJob j;
+    const uint32_t* blocks;
+    uint32_t n_planned;
+    uint32_t pw, ph, qw, qh;
+    uint32_t t_lo, half, hw;
+    unsigned long long pitch;
+};
 struct SplitHeaderDesc {
     uint8_t* out;
     uint32_t width, height, frames, lane_symbols, num_symbols, n_blocks;
@@ -347,6 +368,8 @@ void launch_split_decode(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks
 void launch_split_headers(const SplitHeaderDesc* d_descs, int n_chunks, hipStream_t st);
 // after scan(from_stream = true) over the same channels; max_blocks: the largest blk_count[0] + blk_count[1] among the jobs
 void launch_split_frames_decode(const SplitFramesJob* d_jobs, int n_jobs, uint32_t max_blocks, bool wide, hipStream_t st);
+// after scan(from_stream = true) over the same channels; max_planned: the largest n_planned among the jobs
+void launch_split_preview_decode(const SplitPreviewJob* d_jobs, int n_jobs, uint32_t max_planned, bool wide, hipStream_t st);
 // the same three passes on u16 symbols with the escape step (.alc v3); the count pass sets kSplitWideResidual in *flags
 // (zeroed by the caller) when a symbol exceeds 255 + kSplitWideMaxResidual
 // overwrites the version byte of the headers launch_split_headers wrote (same stream, after it)

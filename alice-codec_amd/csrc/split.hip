@@ -13,6 +13,7 @@
 //   split_decode_kernel   lane streams -> symbols, with the end check of every lane
 //   split_header_kernel   the 1630-byte container header of whole chunks
 //   split_frames_decode_kernel   the lane decode of the blocks a frame range needs, stored as a compact volume
+//   split_preview_decode_kernel  the lane decode of the blocks a half-resolution preview needs: low-low quadrants only
 //   split_wide_encode_kernel / split_wide_decode_kernel   the same chains on u16 symbols with the escape step of .alc v3
 // The output is sized by counting first and writing second: the chain arithmetic runs twice, but nothing is staged in
 // worst-case slots (2 bytes per symbol) and no compaction pass moves the payload again.
@@ -585,6 +586,130 @@ __global__ __launch_bounds__(256) void split_frames_decode_kernel(const SplitFra
 }
 
 // ----------------------------------------------------------------------------------
+// Lane decode for the half-resolution preview: the geometry, tables and bounds re-checks of the
+// decoders above over the blocks a SplitPreviewJob lists (slot -> block through the list).  Every chain runs to its end
+// check; a symbol is stored only when its plane lies in the low or the high window and its (y, x) in the low-low quadrant,
+// relocated into the compact volume [plane][pitch] at job.j.sym.  A lane's positions advance by 64 = dP * P + dy * pw + dx
+// (dy * pw + dx < P), so (x, y, t') are carried with three adds and at most one wrap each -- also for pw = 2 and P < 64
+// (then dP >= 1).  The 64-bit divisions happen once per lane, before the chain loop; the coordinates do not depend on
+// the chain's state, so the serial dependency is the decoders' own.
+// ----------------------------------------------------------------------------------
+template <bool WIDE>
+__global__ __launch_bounds__(256) void split_preview_decode_kernel(const SplitPreviewJob* __restrict__ jobs) {
+    using SymT = std::conditional_t<WIDE, uint16_t, uint8_t>;
+    __shared__ uint32_t c2s_sh[kProbScale / 4];
+    __shared__ uint32_t symtab[256];
+    const SplitPreviewJob pj = jobs[blockIdx.y];
+    const SplitJob& job = pj.j;
+    {
+        const uint32_t* src = (const uint32_t*)job.table->dec.c2s;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) c2s_sh[threadIdx.x + 256 * t] = src[threadIdx.x + 256 * t];
+        symtab[threadIdx.x] = job.table->dec.symtab[threadIdx.x];
+    }
+    __syncthreads();
+    const uint8_t* c2s = (const uint8_t*)c2s_sh;
+    const int lane = threadIdx.x & 63;
+    const unsigned long long slot = (unsigned long long)blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (slot >= pj.n_planned) return;
+    const unsigned long long b = pj.blocks[slot];
+    if (b >= job.n_blocks || !pj.pw || !pj.ph) return;   // (the host plans inside the channel; the bounds below do not rest on it)
+    const unsigned long long base = b * 64ull * job.lane_symbols;
+    const unsigned long long left = job.n - base;
+    const uint32_t in_block = left < 64ull * job.lane_symbols ? (uint32_t)left : 64u * job.lane_symbols;
+    const uint32_t k = (uint32_t)lane < in_block ? (in_block - (uint32_t)lane + 63u) / 64u : 0u;
+
+    // where the lane's first symbol lies, and what 64 positions further means
+    const uint32_t pw = pj.pw, ph = pj.ph, qw = pj.qw, qh = pj.qh, hw = pj.hw;
+    const unsigned long long P = (unsigned long long)pw * ph;
+    const unsigned long long p0 = base + (unsigned)lane;
+    const unsigned long long rem0 = p0 % P, step_rem = 64ull % P;
+    uint32_t tp = (uint32_t)(p0 / P), y = (uint32_t)(rem0 / pw), x = (uint32_t)(rem0 % pw);
+    const uint32_t dP = (uint32_t)(64ull / P), dy = (uint32_t)(step_rem / pw), dx = (uint32_t)(step_rem % pw);   // dy, dx < 64
+    const uint32_t t_hi = pj.half + pj.t_lo;
+    SymT* __restrict__ out = (SymT*)job.sym;
+    // off = (t' - t_lo) * pitch + y * qw + x is carried beside (x, y, t'), so the loop has no multiply: it is the symbol's
+    // place in the compact volume while t' lies in the low window, and off + high_off while it lies in the high one
+    const long long pitch = (long long)pj.pitch;
+    long long off = ((long long)tp - (long long)pj.t_lo) * pitch + (long long)y * qw + x;
+    const long long step_off = (long long)dP * pitch + (long long)dy * qw + dx;   // 64 positions on, nothing wraps
+    const long long xwrap_off = (long long)qw - (long long)pw;                    // x -= pw, ++y
+    const long long ywrap_off = pitch - (long long)ph * qw;                       // y -= ph, ++t'
+    const long long high_off = ((long long)hw - (long long)pj.half) * pitch;
+    const unsigned long long limit = 2ull * hw * pj.pitch;                        // symbols of the channel's compact volume
+
+    const uint32_t blen = job.blk_len[b];
+    const unsigned long long boff = job.blk_off[b];
+    if (blen < 128u || boff + blen > job.len) { if (lane == 0) *job.flags = kSplitBadDirectory; return; }
+    const uint8_t* blk = job.stream + boff;
+    const uint32_t len = (uint32_t)blk[2 * lane] | ((uint32_t)blk[2 * lane + 1] << 8);
+    const uint32_t incl = wave_incl_scan(len, lane);
+    const uint32_t all = __shfl(incl, 63, 64);
+    if (all + 128u != blen) { if (lane == 0) *job.flags = kSplitBadDirectory; return; }
+    const uint8_t* __restrict__ src = blk + 128u + (incl - len);   // [src, src + len) lies inside the block
+
+    uint32_t win = 0u, nwin = 0u, fpos = 0u, pos = 0u;
+    auto take = [&]() -> uint32_t {
+        if (nwin == 0u) {
+            uint32_t w = 0u;
+            if (fpos + 4u <= len) {
+                uint32_t t;
+                __builtin_memcpy(&t, src + fpos, 4);
+                w = __builtin_bswap32(t);
+            } else {
+#pragma unroll
+                for (uint32_t t = 0; t < 4u; ++t) w = (w << 8) | (fpos + t < len ? (uint32_t)src[fpos + t] : 0u);
+            }
+            fpos += 4u;
+            win = w;
+            nwin = 4u;
+        }
+        const uint32_t byte = win >> 24;
+        win <<= 8;
+        --nwin;
+        ++pos;
+        return byte;
+    };
+    bool ok = true;
+    if (k == 0u) {
+        ok = len == 0u;
+    } else {
+        uint32_t xs = take() << 24;
+        xs |= take() << 16;
+        xs |= take() << 8;
+        xs |= take();
+        for (uint32_t i = 0; i < k; ++i) {
+            const uint32_t slot12 = xs & (kProbScale - 1u);
+            uint32_t s = c2s[slot12];
+            const uint32_t fc = symtab[s];
+            xs = (fc & 0xFFFFu) * (xs >> kProbBits) + slot12 - (fc >> 16);
+            if (xs < kRansL) xs = (xs << 8) | take();
+            if (xs < kRansL) xs = (xs << 8) | take();
+            if (WIDE && s == 255u) {
+                s += xs & kSplitWideMaxResidual;
+                xs >>= 12;
+                if (xs < kRansL) xs = (xs << 8) | take();
+                if (xs < kRansL) xs = (xs << 8) | take();
+            }
+            // plane < 2 hw, y < qh and x < qw: the index is plane * pitch + y * qw + x, inside the channel's 2 hw * pitch
+            // symbols (pitch >= qw * qh); the compare with `limit` keeps the store there whatever the carried sum holds
+            const uint32_t u0 = tp - pj.t_lo, u1 = tp - t_hi;
+            if ((u0 < hw || u1 < hw) && y < qh && x < qw) {
+                const unsigned long long at = (unsigned long long)(off + (u0 < hw ? 0ll : high_off));
+                if (at < limit) out[at] = (SymT)s;
+            }
+            x += dx; off += step_off;
+            if (x >= pw) { x -= pw; ++y; off += xwrap_off; }
+            y += dy;
+            if (y >= ph) { y -= ph; ++tp; off += ywrap_off; }
+            tp += dP;
+        }
+        ok = xs == kRansL && pos == len;
+    }
+    if (!ok) *job.flags = kSplitBadLane;
+}
+
+// ----------------------------------------------------------------------------------
 // Container header of whole chunks, one workgroup per chunk.
 // ----------------------------------------------------------------------------------
 __device__ __forceinline__ void put_le(uint8_t* p, unsigned long long v, int bytes) {
@@ -658,6 +783,11 @@ void launch_split_frames_decode(const SplitFramesJob* d_jobs, int n_jobs, uint32
     if (n_jobs <= 0 || !max_blocks) return;
     if (wide) hipLaunchKernelGGL(split_frames_decode_kernel<true>, split_grid(max_blocks, n_jobs), dim3(256), 0, st, d_jobs);
     else hipLaunchKernelGGL(split_frames_decode_kernel<false>, split_grid(max_blocks, n_jobs), dim3(256), 0, st, d_jobs);
+}
+void launch_split_preview_decode(const SplitPreviewJob* d_jobs, int n_jobs, uint32_t max_planned, bool wide, hipStream_t st) {
+    if (n_jobs <= 0 || !max_planned) return;
+    if (wide) hipLaunchKernelGGL(split_preview_decode_kernel<true>, split_grid(max_planned, n_jobs), dim3(256), 0, st, d_jobs);
+    else hipLaunchKernelGGL(split_preview_decode_kernel<false>, split_grid(max_planned, n_jobs), dim3(256), 0, st, d_jobs);
 }
 void launch_split_headers(const SplitHeaderDesc* d_descs, int n_chunks, hipStream_t st) {
     if (n_chunks > 0) hipLaunchKernelGGL(split_header_kernel, dim3(n_chunks), dim3(256), 0, st, d_descs);

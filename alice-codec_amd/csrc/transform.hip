@@ -17,6 +17,8 @@
 //   tile role     : stage A inverse column lifting (registers) -> LDS -> stage B inverse row lifting,
 //                   `as i16`, ycocg_r_to_rgb_bytes.
 // How the roles of consecutive bands share launches: "Band-ordered, role-fused launches" below.
+// Half-resolution preview (preview_inv_kernel): the temporal role of the three channels in lock step
+// on the low-low quadrants, with the DC normalisation and the colour step fused behind it; no tile role.
 //
 // Lifting facts used: inside one lifting step every write depends only on samples of the other
 // parity, so a step is data-parallel; an output depends on inputs within +-n_steps samples;
@@ -955,6 +957,172 @@ __global__ __launch_bounds__(256) void inv_t_wide_win_kernel(InvTw w) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// Half-resolution preview: the fused finish.  The low-low quadrant of every coefficient plane is a
+// half-size picture, so there is no spatial pass: a thread owns four neighbouring quadrant pixels (linear index y * qw + x
+// of the compact volume) and runs InvT's stream -- symbols -> dequantise -> inverse temporal lifting, the same ticks, the
+// same lift4 -- for Y, Co and Cg in lock step.  When the three channels emit frame t of [lo, hi) the thread normalises the
+// low band's DC gain (n = (v * K + 32768) >> 16 with a 64-bit product; K = 65536 for CDF 5/3 and Haar is the identity and
+// is not computed), truncates `as i16`, converts the colour and stores 12 RGB bytes.  No intermediate volume.
+// PrevCh is one channel's state: InvT's o2p / e1p / o1pp / e0pp, with the frames handed back instead of stored.
+// ------------------------------------------------------------------------------------------------
+template <int NS, bool EXACT, bool MIRROR>
+struct PrevCh {
+    I4 o2p, e1p, o1pp, e0pp;
+    // tick k: ev = frame 2 (k - 1) (NS 4, k >= 1) or 2 k (NS 2); od = frame 2 (k - 2) + 1 (NS 4, k >= 2) or 2 (k - 1) + 1 (NS 2, k >= 1)
+    __device__ __forceinline__ void tick(int k, const I4& lv, const I4& hv, const int (&c)[4], I4& ev, I4& od) {
+        if (NS == 4) {
+            const I4 e1 = lift4<EXACT, MIRROR>(lv, k == 0 ? hv : o2p, hv, c[3]);
+            if (k > 0) {
+                const I4 o1 = lift4<EXACT, MIRROR>(o2p, e1p, e1, c[2]);
+                const I4 e0 = lift4<EXACT, MIRROR>(e1p, k == 1 ? o1 : o1pp, o1, c[1]);
+                ev = e0;
+                od = lift4<EXACT, MIRROR>(o1pp, e0pp, e0, c[0]);
+                o1pp = o1; e0pp = e0;
+            }
+            o2p = hv; e1p = e1;
+        } else {
+            const I4 e0 = lift4<EXACT, MIRROR>(lv, k == 0 ? hv : o2p, hv, c[1]);
+            ev = e0;
+            od = lift4<EXACT, MIRROR>(o2p, e1p, e0, c[0]);
+            o2p = hv; e1p = e0;
+        }
+    }
+    // NS 4: ev = frame 2 (half - 1), od = frame 2 (half - 2) + 1 (half >= 2), last = frame 2 (half - 1) + 1;  NS 2: last only
+    __device__ __forceinline__ void flush(int half, const int (&c)[4], I4& ev, I4& od, I4& last) {
+        if (NS == 4) {
+            const I4 o1 = lift4<EXACT, MIRROR>(o2p, e1p, e1p, c[2]);
+            const I4 e0 = lift4<EXACT, MIRROR>(e1p, half == 1 ? o1 : o1pp, o1, c[1]);
+            ev = e0;
+            od = lift4<EXACT, MIRROR>(o1pp, e0pp, e0, c[0]);
+            last = lift4<EXACT, MIRROR>(o1, e0, e0, c[0]);
+        } else {
+            last = lift4<EXACT, MIRROR>(o2p, e1p, e1p, c[0]);
+        }
+    }
+};
+
+struct PreviewInv {
+    const void* sym;             // compact volume [3][planes][pitch], u8 or u16
+    uint8_t* rgb;                // (hi - lo) frames of q packed RGB pixels
+    unsigned long long pitch;    // symbols per plane, a multiple of 4, >= q
+    unsigned long long q;        // quadrant pixels per plane (qw * qh)
+    uint32_t planes;             // b - a: low band planes, then as many high band planes
+    uint32_t lo, hi;             // frames of the virtual chunk that are written, lo < hi <= planes
+    Coeffs cf;
+    int step[3];
+    int gain;                    // K
+};
+
+template <int NS, bool EXACT, bool WIDE, bool MIRROR>
+__global__ __launch_bounds__(256) void preview_inv_kernel(PreviewInv a) {
+    static_assert(WIDE || !MIRROR, "the mirrored inverse belongs to a wide container (.alc v4)");
+    using Sym4 = std::conditional_t<WIDE, uint2, uint32_t>;
+    __shared__ int lut[WIDE ? 1 : 3 * 256];
+    const int tid = threadIdx.x;
+    if constexpr (!WIDE) {
+        const int s = tid;
+        const int q = (s == 0) ? 0 : ((s & 1) ? (s + 1) / 2 : -(s / 2));      // src/quant.rs:581-587
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) lut[ch * 256 + s] = (int)((unsigned)q * (unsigned)a.step[ch]);   // src/quant.rs:104-110 (wrapping)
+        __syncthreads();
+    }
+    const unsigned long long idx = ((unsigned long long)blockIdx.x * 256u + (unsigned)tid) * 4u;
+    if (idx >= a.q) return;
+    const int half = (int)(a.planes / 2u);
+    int c[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) c[i] = MIRROR ? a.cf.c[i] : -a.cf.c[i];
+
+    // plane p of channel ch: the thread's four symbols (pitch % 4 == 0, so the last group of a plane stays inside its pitch)
+    auto load = [&](int ch, int p) -> Sym4 {
+        const unsigned long long at = ((unsigned long long)ch * a.planes + (unsigned)p) * a.pitch + idx;
+        if constexpr (WIDE) return *(const uint2*)((const uint16_t*)a.sym + at);
+        else return *(const uint32_t*)((const uint8_t*)a.sym + at);
+    };
+    auto dq = [&](int ch, Sym4 packed) -> I4 {
+        I4 r;
+        if constexpr (WIDE) {
+            const uint32_t z[4] = {packed.x & 0xFFFFu, packed.x >> 16, packed.y & 0xFFFFu, packed.y >> 16};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int q = (z[i] & 1u) ? (int)((z[i] + 1u) >> 1) : -(int)(z[i] >> 1);   // src/quant.rs:581-587
+                r.v[i] = (int)((unsigned)q * (unsigned)a.step[ch]);                         // src/quant.rs:104-110 (wrapping)
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) r.v[i] = lut[ch * 256 + ((packed >> (8 * i)) & 0xFFu)];
+        }
+        return r;
+    };
+    // frame t of the three channels -> pixels
+    auto emit = [&](int t, const I4 (&v)[3]) {
+        if (t < (int)a.lo || t >= (int)a.hi) return;
+        uint8_t out[12];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            int n[3];
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch)
+                n[ch] = NS == 4 ? (int)(((long long)v[ch].v[i] * (long long)a.gain + 32768ll) >> 16) : v[ch].v[i];
+            // `as i16` (src/pipeline.rs:608), wrapping i16 colour inverse (src/color.rs:266-273)
+            const short yv = (short)n[0], c_o = (short)n[1], c_g = (short)n[2];
+            const short tt = (short)(yv - (short)(c_g >> 1));
+            const short g = (short)(c_g + tt);
+            const short b = (short)(tt - (short)(c_o >> 1));
+            const short rr = (short)(c_o + b);
+            out[3 * i] = (uint8_t)min(max((int)rr, 0), 255);
+            out[3 * i + 1] = (uint8_t)min(max((int)g, 0), 255);
+            out[3 * i + 2] = (uint8_t)min(max((int)b, 0), 255);
+        }
+        uint8_t* p = a.rgb + ((unsigned long long)(t - (int)a.lo) * a.q + idx) * 3u;   // pixels idx .. idx + 3 of frame t - lo
+        if (idx + 4u <= a.q && ((uintptr_t)p & 3u) == 0u) {
+            uint32_t* p4 = (uint32_t*)p;
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+                p4[i] = (uint32_t)out[4 * i] | ((uint32_t)out[4 * i + 1] << 8) | ((uint32_t)out[4 * i + 2] << 16) | ((uint32_t)out[4 * i + 3] << 24);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (idx + (unsigned)i < a.q) { p[3 * i] = out[3 * i]; p[3 * i + 1] = out[3 * i + 1]; p[3 * i + 2] = out[3 * i + 2]; }
+        }
+    };
+
+    PrevCh<NS, EXACT, MIRROR> st[3];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) { st[ch].o2p = I4{}; st[ch].e1p = I4{}; st[ch].o1pp = I4{}; st[ch].e0pp = I4{}; }
+    Sym4 nl[3], nh[3];   // the next pair's symbols, loaded one tick ahead
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) { nl[ch] = load(ch, 0); nh[ch] = load(ch, half); }
+    for (int k = 0; k < half; ++k) {
+        Sym4 cl[3], chh[3];
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) { cl[ch] = nl[ch]; chh[ch] = nh[ch]; }
+        if (k + 1 < half) {
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) { nl[ch] = load(ch, k + 1); nh[ch] = load(ch, half + k + 1); }
+        }
+        I4 ev[3] = {}, od[3] = {};
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) st[ch].tick(k, dq(ch, cl[ch]), dq(ch, chh[ch]), c, ev[ch], od[ch]);
+        if (NS == 4) {
+            if (k >= 1) emit(2 * (k - 1), ev);
+            if (k >= 2) emit(2 * (k - 2) + 1, od);
+        } else {
+            emit(2 * k, ev);
+            if (k >= 1) emit(2 * (k - 1) + 1, od);
+        }
+    }
+    I4 ev[3] = {}, od[3] = {}, last[3] = {};
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) st[ch].flush(half, c, ev[ch], od[ch], last[ch]);
+    if (NS == 4) {
+        emit(2 * (half - 1), ev);
+        if (half >= 2) emit(2 * (half - 2) + 1, od);
+    }
+    emit(2 * (half - 1) + 1, last);
+}
+
+// ------------------------------------------------------------------------------------------------
 // K4: inverse spatial transform of one frame tile + colour (tile role of the inverse launch)
 // ------------------------------------------------------------------------------------------------
 constexpr int I_TW = 96, I_TH = 32, I_SEG = 8, I_NSEG = 12, I_THREADS = 384;
@@ -1696,6 +1864,28 @@ bool launch_inverse_transform_window(const void* d_sym, const ChunkDims& dv, con
     if (format == 2) return inverse_launches<true, true>(d_sym, dv, wavelet, step, exact, mid16, lds16, d_scratch, rgb, st, &win);
     if (format == 1) return inverse_launches<true>(d_sym, dv, wavelet, step, exact, mid16, lds16, d_scratch, rgb, st, &win);
     return inverse_launches<false>(d_sym, dv, wavelet, step, exact, mid16, lds16, d_scratch, rgb, st, &win);
+}
+
+template <int NS, bool EXACT>
+static void preview_inv_launch(const PreviewInv& a, int format, hipStream_t st) {
+    const dim3 grid((unsigned)((a.q + 1023u) / 1024u));
+    if (format == 2) hipLaunchKernelGGL((preview_inv_kernel<NS, EXACT, true, true>), grid, dim3(256), 0, st, a);
+    else if (format == 1) hipLaunchKernelGGL((preview_inv_kernel<NS, EXACT, true, false>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((preview_inv_kernel<NS, EXACT, false, false>), grid, dim3(256), 0, st, a);
+}
+
+bool launch_preview_inverse(const void* d_sym, uint64_t pitch, uint64_t q, uint32_t planes, const FrameWindow& win, int format,
+                            int wavelet, const int32_t step[3], bool exact, uint8_t* d_rgb, hipStream_t st) {
+    if (!q || planes < 2 || (planes & 1u) || !(win.lo < win.hi && win.hi <= planes) || pitch < q || (pitch & 3u)) return false;
+    const LiftSteps ls = lift_steps(wavelet);
+    PreviewInv a{};
+    a.sym = d_sym; a.rgb = d_rgb; a.pitch = pitch; a.q = q; a.planes = planes; a.lo = win.lo; a.hi = win.hi;
+    a.cf = to_coeffs(ls);
+    a.step[0] = step[0]; a.step[1] = step[1]; a.step[2] = step[2];
+    a.gain = ls.n == 4 ? kPreviewGain97 : kPreviewGainOne;
+    if (ls.n == 4) { if (exact) preview_inv_launch<4, true>(a, format, st); else preview_inv_launch<4, false>(a, format, st); }
+    else { if (exact) preview_inv_launch<2, true>(a, format, st); else preview_inv_launch<2, false>(a, format, st); }
+    return true;
 }
 
 

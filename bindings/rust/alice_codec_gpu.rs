@@ -1269,3 +1269,41 @@ pub unsafe fn frames_decode_device(d_alc: *const std::ffi::c_void, length: u64, 
     -> Result<(), CodecError> {
     check(alice_codec_dev_decode_frames(d_alc, length, first, count, d_rgb_out, hip_stream), 0, 0)
 }
+
+// ---- half-resolution preview of a version 2, 3 or 4 chunk from the low band alone ----
+
+extern "C" {
+    fn alice_codec_preview_dims(width: u32, height: u32, qw: *mut u32, qh: *mut u32) -> c_int;
+    fn alice_codec_decode_preview(data: *const u8, len: u64, first: u32, count: u32, out_len: *mut u64) -> *mut u8;
+    fn alice_codec_dev_decode_preview(d_alc: *const std::ffi::c_void, len: u64, first: u32, count: u32,
+                                      d_rgb_out: *mut std::ffi::c_void, hip_stream: *mut std::ffi::c_void) -> c_int;
+}
+
+/// `(qw, qh)` = `(ceil(width / 2), ceil(height / 2))`: the size of a preview frame.  No device needed.
+pub fn preview_dims(width: u32, height: u32) -> Result<(u32, u32), CodecError> {
+    let (mut qw, mut qh) = (0u32, 0u32);
+    let rc = unsafe { alice_codec_preview_dims(width, height, &mut qw, &mut qh) };
+    check(rc, 0, 0).map(|_| (qw, qh))
+}
+
+/// The half-resolution RGB bytes (`count * qh * qw * 3`) of frames `[first, first + count)` of a version 2, 3 or 4
+/// container, from the low-low quadrants of the coefficient planes the range needs: the blocks of a plane's bottom half are
+/// never read.  The end checks cover the blocks that are read; version 1 is `InvalidBitstream`.
+pub fn decode_preview(data: &[u8], first: u32, count: u32) -> Result<Vec<u8>, CodecError> {
+    let mut n = 0u64;
+    unsafe {
+        let p = alice_codec_decode_preview(data.as_ptr(), data.len() as u64, first, count, &mut n);
+        if p.is_null() { Err(last_error(0, data.len(), 0, 0, 0)) } else { Ok(take(p, n)) }
+    }
+}
+
+/// `decode_preview` of a device-resident container of `length` bytes into `count` packed preview frames at `d_rgb_out`.
+///
+/// # Safety
+/// As `split_decode_device`: `d_alc` holds `length` bytes and `d_rgb_out` room for `count * qh * qw * 3` bytes on the
+/// current device.
+pub unsafe fn preview_decode_device(d_alc: *const std::ffi::c_void, length: u64, first: u32, count: u32,
+                                    d_rgb_out: *mut std::ffi::c_void, hip_stream: *mut std::ffi::c_void)
+    -> Result<(), CodecError> {
+    check(alice_codec_dev_decode_preview(d_alc, length, first, count, d_rgb_out, hip_stream), 0, 0)
+}

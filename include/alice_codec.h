@@ -705,6 +705,29 @@ uint8_t *alice_codec_decode_frames(const uint8_t *data, uint64_t len, uint32_t f
 int alice_codec_dev_decode_frames(const void *d_alc, uint64_t len, uint32_t first, uint32_t count, void *d_rgb_out,
                                   void *hip_stream);
 
+/* ---- Half-resolution preview of a version 2, 3 or 4 chunk from the low band alone ----
+ * The spatial transform is one lifting level, so the low-low quadrant of every coefficient plane is a half-size picture of
+ * qw x qh = ceil(width / 2) x ceil(height / 2) pixels.  For frames [first, first + count) these calls decode the blocks
+ * that intersect the quadrants of the planes inside the frame-range window [a, b) above -- the top half of a plane is one
+ * contiguous symbol run; the bottom half is never entropy-decoded -- and finish in one launch: dequantise, the container's
+ * inverse temporal lifting, n = (v * K + 32768) >> 16 (64-bit product, arithmetic shift; K = 65536 for CDF 5/3 and Haar,
+ * whose low band has DC gain 1, and 47484 = round(65536 / 1.17480326^2) for CDF 9/7), `as i16`, colour.  No spatial inverse
+ * runs.  The output is count * qh * qw * 3 packed RGB bytes; it approximates the 2x2 box average of the full decode (it is
+ * the wavelet's low-pass, not the box filter).
+ * Validation, its order and its codes are alice_codec_decode_frames' (version 1: "no random access").  INTEGRITY as above:
+ * the whole block-length tables are checked, the lane end checks cover the decoded blocks only, and a refusal for damage in
+ * a decoded block writes nothing to d_rgb_out.  Memory comes from the library's pool; nothing goes through the chain hub. */
+/* qw, qh of a width x height picture; no device needed.  width or height 0: ALICE_ERR_INVALID_DIMENSIONS. */
+int alice_codec_preview_dims(uint32_t width, uint32_t height, uint32_t *qw, uint32_t *qh);
+/* One container in host memory -> count * qh * qw * 3 packed RGB bytes (free with alice_codec_data_free64), NULL on error.
+ * Reads and uploads the 1630-byte header, the three block-length tables and the byte runs of consecutive planned blocks,
+ * nothing else of `data` (which may be a mapped file). */
+uint8_t *alice_codec_decode_preview(const uint8_t *data, uint64_t len, uint32_t first, uint32_t count, uint64_t *out_len);
+/* The same for a container of `len` bytes on the device (any byte alignment) into d_rgb_out, which must not overlap it.
+ * The header is read back first.  Finished on return. */
+int alice_codec_dev_decode_preview(const void *d_alc, uint64_t len, uint32_t first, uint32_t count, void *d_rgb_out,
+                                   void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -759,6 +759,29 @@ inline void frames_decode_device(const void* d_alc, uint64_t length, uint32_t fi
     detail::check(alice_codec_dev_decode_frames(d_alc, length, first, count, d_rgb_out, hip_stream));
 }
 
+// ---- half-resolution preview of a version 2, 3 or 4 chunk from the low band alone ----
+// count * qh * qw * 3 packed RGB bytes of frames [first, first + count), qw x qh = ceil(width / 2) x ceil(height / 2)
+struct PreviewDims { uint32_t qw, qh; };
+inline PreviewDims preview_dims(uint32_t width, uint32_t height) {
+    PreviewDims d{0, 0};
+    detail::check(alice_codec_preview_dims(width, height, &d.qw, &d.qh));
+    return d;
+}
+inline std::vector<uint8_t> decode_preview(const uint8_t* data, uint64_t len, uint32_t first, uint32_t count) {
+    static const uint8_t empty = 0;
+    uint64_t n = 0;
+    uint8_t* p = alice_codec_decode_preview(data ? data : &empty, data ? len : 0, first, count, &n);
+    if (!p) detail::raise(ALICE_ERR_INVALID_BITSTREAM);
+    return detail::take(p, n);
+}
+inline std::vector<uint8_t> decode_preview(const std::vector<uint8_t>& data, uint32_t first, uint32_t count) {
+    return decode_preview(data.empty() ? nullptr : data.data(), data.size(), first, count);
+}
+inline void preview_decode_device(const void* d_alc, uint64_t length, uint32_t first, uint32_t count, void* d_rgb_out,
+                                  void* hip_stream = nullptr) {
+    detail::check(alice_codec_dev_decode_preview(d_alc, length, first, count, d_rgb_out, hip_stream));
+}
+
 // version 2 rate control: the bracket of encode_split's length at the 101 qualities (every version 2 table
 // is bounded: status stays ALICE_RATE_BOUNDED) and one encode at the quality the budget rule picks -- the largest whose
 // upper bound fits, refined by at most ALICE_SPLIT_REFINE_TRIALS exact size counts among the straddling qualities

@@ -138,6 +138,11 @@ int alice_codec_test_sq_diff_sum(const void *d_a, const void *d_b, uint64_t n, u
  * blocks; 0 for the device call), frames given to the spatial pass}. */
 void alice_codec_test_last_frames_stats(uint64_t out[5]);
 
+/* The last alice_codec_decode_preview / alice_codec_dev_decode_preview of the calling thread that reached the device:
+ * out = {a, b of the window, blocks decoded over the three channels, payload bytes the host call uploaded (the planned
+ * blocks; 0 for the device call), frames written, symbols stored over the three channels (3 (b - a) qw qh)}. */
+void alice_codec_test_last_preview_stats(uint64_t out[6]);
+
 #ifdef __cplusplus
 }
 #endif
