@@ -3435,6 +3435,19 @@ int split_upload_jobs(SplitWork& w, hipStream_t st) {
     return kOk;
 }
 
+// The three channel jobs w.h[first .. first + 3) of the chunk at d_alc (device, h validated): where each payload lies, and
+// where its symbols go -- channel c at sym + c * sym_stride (bytes).
+void split_chunk_jobs(SplitWork& w, size_t first, const SplitHeader& h, const uint8_t* d_alc, uint8_t* sym, size_t sym_stride) {
+    uint64_t off = kSplitHeaderBytes;
+    for (int c = 0; c < 3; ++c) {
+        SplitJob& s = w.h[first + (size_t)c];
+        s.sym = sym + (size_t)c * sym_stride;
+        s.stream = (uint8_t*)d_alc + off;
+        s.len = h.payload_len[c];
+        off += s.len;
+    }
+}
+
 // Tables from the jobs' histograms (device, n_jobs x 256) and the count pass: totals[j] = payload length of job j.  The
 // jobs' symbols (h[j].sym) are set by the caller.  Returns after the stream has drained.
 int split_count(SplitWork& w, const uint32_t* d_hist, hipStream_t st, std::vector<uint64_t>& totals, std::vector<uint16_t>* freq_out) {
@@ -3442,12 +3455,8 @@ int split_count(SplitWork& w, const uint32_t* d_hist, hipStream_t st, std::vecto
     for (int j = 0; j < w.n_jobs; ++j)
         launch_rans_table_from_arrays(w.cum.as<uint16_t>() + (size_t)j * 256, w.freq.as<uint16_t>() + (size_t)j * 256, w.tables.as<RansTable>() + j, st);
     TRY(split_upload_jobs(w, st));
-    if (w.wide) {
-        HIP_TRY(hipMemsetAsync(w.flags.p, 0, (size_t)w.n_jobs * sizeof(uint32_t), st));
-        launch_split_wide_count(w.jobs.as<SplitJob>(), w.n_jobs, w.n_blocks, st);
-    } else {
-        launch_split_count(w.jobs.as<SplitJob>(), w.n_jobs, w.n_blocks, st);
-    }
+    if (w.wide) HIP_TRY(hipMemsetAsync(w.flags.p, 0, (size_t)w.n_jobs * sizeof(uint32_t), st));
+    launch_split_count(w.jobs.as<SplitJob>(), w.n_jobs, w.n_blocks, w.wide, st);
     launch_split_scan(w.jobs.as<SplitJob>(), w.n_jobs, false, w.totals.as<unsigned long long>(), st);
     HIP_TRY(hipGetLastError());
     totals.resize((size_t)w.n_jobs);
@@ -3473,8 +3482,7 @@ int split_count(SplitWork& w, const uint32_t* d_hist, hipStream_t st, std::vecto
 // the write pass, after the caller has pointed every h[j].stream at totals[j] writable bytes
 int split_write(SplitWork& w, hipStream_t st) {
     TRY(split_upload_jobs(w, st));
-    if (w.wide) launch_split_wide_write(w.jobs.as<SplitJob>(), w.n_jobs, w.n_blocks, st);
-    else launch_split_write(w.jobs.as<SplitJob>(), w.n_jobs, w.n_blocks, st);
+    launch_split_write(w.jobs.as<SplitJob>(), w.n_jobs, w.n_blocks, w.wide, st);
     HIP_TRY(hipGetLastError());
     return kOk;
 }
@@ -3500,8 +3508,7 @@ int split_decode_launch(SplitWork& w, const uint16_t* freq, hipStream_t st, cons
         launch_rans_table_from_arrays(w.cum.as<uint16_t>() + (size_t)j * 256, w.freq.as<uint16_t>() + (size_t)j * 256, w.tables.as<RansTable>() + j, st);
     launch_split_scan(w.jobs.as<SplitJob>(), w.n_jobs, true, nullptr, st);
     if (lane_decode) TRY((*lane_decode)());
-    else if (w.wide) launch_split_wide_decode(w.jobs.as<SplitJob>(), w.n_jobs, w.n_blocks, st);
-    else launch_split_decode(w.jobs.as<SplitJob>(), w.n_jobs, w.n_blocks, st);
+    else launch_split_decode(w.jobs.as<SplitJob>(), w.n_jobs, w.n_blocks, w.wide, st);
     HIP_TRY(hipGetLastError());
     return kOk;
 }
@@ -3612,15 +3619,8 @@ int split_decode_chunks(const SplitHeader* hdr, const uint8_t* const* d_alc, uin
     std::vector<uint16_t> freq((size_t)B * 3 * 256);
     bool all16 = true;
     for (uint32_t i = 0; i < B; ++i) {
-        uint64_t off = kSplitHeaderBytes;
-        for (int c = 0; c < 3; ++c) {
-            SplitJob& s = w.h[3 * (size_t)i + c];
-            s.sym = dw.sym.as<uint8_t>() + (3 * (size_t)i + c) * d.padded * sb;
-            s.stream = (uint8_t*)d_alc[i] + off;
-            s.len = hdr[i].payload_len[c];
-            off += s.len;
-            memcpy(&freq[(3 * (size_t)i + c) * 256], hdr[i].freq[c], 256 * sizeof(uint16_t));
-        }
+        split_chunk_jobs(w, 3 * (size_t)i, hdr[i], d_alc[i], dw.sym.as<uint8_t>() + 3 * (size_t)i * d.padded * sb, d.padded * sb);
+        memcpy(&freq[3 * (size_t)i * 256], hdr[i].freq, 3 * 256 * sizeof(uint16_t));
         all16 = all16 && inverse_bounds(hdr[i].wavelet, hdr[i].step, wide ? kWideMaxQ : kByteMaxQ).mid16;
     }
     if (transform_tiles_eligible(d)) TRY(dw.scratch_own.alloc(inverse_scratch_bytes(d, all16)));
@@ -4778,6 +4778,12 @@ struct FramesPlan {
     uint64_t sym_lo[2] = {0, 0}, sym_hi[2] = {0, 0};
     uint32_t blk_first[2] = {0, 0}, blk_count[2] = {0, 0};   // disjoint: a block both ranges touch belongs to the first
     uint32_t blocks() const { return blk_count[0] + blk_count[1]; }
+    std::vector<uint32_t> block_list() const {   // ascending, no duplicates
+        std::vector<uint32_t> v;
+        for (int r = 0; r < n_ranges; ++r)
+            for (uint32_t i = 0; i < blk_count[r]; ++i) v.push_back(blk_first[r] + i);
+        return v;
+    }
 };
 
 FramesPlan frames_plan(const SplitHeader& h, const ChunkDims& d, uint32_t first, uint32_t count) {
@@ -4815,6 +4821,79 @@ int frames_validate(const uint8_t* data, uint64_t len, uint32_t first, uint32_t 
         return fail(kInvalidDimensions, "frames [" + std::to_string(first) + ", " + std::to_string((uint64_t)first + count) +
                                             ") are not a range of the chunk's " + std::to_string(h.frames) + " frames");
     if (d.n_pixels == 0) return fail(kInvalidDimensions, "invalid dimensions");
+    return kOk;
+}
+
+// What the two device calls (frame range, preview) share: the null checks, the header fetched to the host and validated,
+// then decode(h, d, stream).  Nothing is queued before the header and the range have been accepted.
+template <typename Decode>
+int partial_decode_dev(const void* d_alc, uint64_t len, uint32_t first, uint32_t count, const void* d_rgb_out, void* hip_stream, Decode decode) {
+    clear_error();
+    if (!d_alc || !d_rgb_out) return fail(kNullArgument, "null argument");
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);
+    uint8_t raw[kSplitHeaderBytes] = {};
+    if (len) {
+        HIP_TRY(hipMemcpyAsync(raw, d_alc, std::min<uint64_t>(len, kSplitHeaderBytes), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    SplitHeader h;
+    ChunkDims d{};
+    TRY(frames_validate(raw, len, first, count, h, d));
+    return decode(h, d, st);
+}
+
+// What the two host calls share once h is validated and the blocks are planned (`blocks`: ascending, no duplicates, the
+// same for the three channels).  Block offsets come from the tables, on the host; the tables get check_split_directories'
+// verdict on the way.  What goes up: the header, the three tables, the byte runs of consecutive planned blocks -- at their
+// own offsets of a pool buffer of the container's size, so that the device path runs on it unchanged.  The rest of it
+// stays unwritten and unread.  device(d_alc, d_rgb, stream, uploaded payload bytes) decodes `bytes` bytes to d_rgb.
+template <typename Device>
+int partial_decode_host(const uint8_t* data, uint64_t len, const SplitHeader& h, const std::vector<uint32_t>& blocks, uint64_t bytes,
+                        uint8_t** result, uint64_t* out_len, Device device) {
+    struct Span { uint64_t off, len; };
+    std::vector<Span> spans;
+    spans.push_back({0, kSplitHeaderBytes});
+    uint64_t payload_bytes = 0, pos = kSplitHeaderBytes;
+    for (int c = 0; c < 3; ++c) {
+        const uint8_t* tab = data + pos;
+        const uint32_t nb = h.n_blocks[c];
+        spans.push_back({pos, 4ull * nb});
+        uint64_t sum = 4ull * nb;
+        size_t next = 0;            // the next planned block
+        bool open = false;          // the last span ends where this block starts
+        for (uint32_t blk = 0; blk < nb; ++blk) {
+            const uint32_t v = get_u32(tab + 4ull * blk);
+            if (v < 128u) return fail(kInvalidBitstream, "channel " + std::to_string(c) + ": block " + std::to_string(blk) + " is shorter than its lane directory");
+            if (sum + v > h.payload_len[c]) { sum += v; break; }   // (the sum below refuses it; no span may leave the payload)
+            if (next < blocks.size() && blocks[next] == blk) {
+                if (open) spans.back().len += v; else spans.push_back({pos + sum, v});
+                payload_bytes += v;
+                open = true;
+                ++next;
+            } else {
+                open = false;
+            }
+            sum += v;
+        }
+        if (sum != h.payload_len[c])
+            return fail(kInvalidBitstream, "channel " + std::to_string(c) + ": block lengths do not sum to payload_len " + std::to_string(h.payload_len[c]));
+        pos += h.payload_len[c];
+    }
+    std::unique_ptr<uint8_t, decltype(&free)> out(host_result_alloc(bytes), &free);   // freed on every failure below
+    if (!out) return fail(kOutOfMemory, "out of host memory");
+    *out_len = bytes;
+    hipStream_t st;
+    TRY(get_stream(&st));
+    DevBuf d_alc, d_rgb;
+    TRY(d_alc.alloc(len));
+    TRY(d_rgb.alloc(bytes));
+    for (const Span& s : spans)
+        HIP_TRY(hipMemcpyAsync(d_alc.as<uint8_t>() + s.off, data + s.off, s.len, hipMemcpyHostToDevice, st));
+    TRY(device(d_alc.as<uint8_t>(), d_rgb.p, st, payload_bytes));
+    TRY(copy_to_host(out.get(), d_rgb.p, bytes, st));
+    *result = out.release();
     return kOk;
 }
 
@@ -4869,14 +4948,7 @@ int frames_decode_device(const SplitHeader& h, const ChunkDims& d, const uint8_t
     TRY(d_fj.alloc(3 * sizeof(SplitFramesJob)));
     SplitWork w;
     TRY(split_work_alloc(w, 3, d.padded, h.lane_symbols, false, fmt));
-    uint64_t off = kSplitHeaderBytes;
-    for (int c = 0; c < 3; ++c) {
-        SplitJob& s = w.h[(size_t)c];
-        s.sym = dw.sym.as<uint8_t>() + (size_t)c * dv.padded * sb;
-        s.stream = (uint8_t*)d_alc + off;
-        s.len = h.payload_len[c];
-        off += s.len;
-    }
+    split_chunk_jobs(w, 0, h, d_alc, dw.sym.as<uint8_t>(), dv.padded * sb);
     for (int c = 0; c < 3; ++c) {
         fj[(size_t)c].j = w.h[(size_t)c];
         for (int r = 0; r < 2; ++r) {
@@ -4922,82 +4994,23 @@ int alice_codec_frames_window(uint8_t wavelet_type, uint32_t frames, uint32_t fi
 }
 
 int alice_codec_dev_decode_frames(const void* d_alc, uint64_t len, uint32_t first, uint32_t count, void* d_rgb_out, void* hip_stream) {
-    clear_error();
-    if (!d_alc || !d_rgb_out) return fail(kNullArgument, "null argument");
-    TRY(ensure_device());
-    hipStream_t st = (hipStream_t)hip_stream;
-    ScopeStream scope(st);
-    // the header comes to the host first; nothing is queued before it and the range have been accepted
-    uint8_t raw[kSplitHeaderBytes] = {};
-    if (len) {
-        HIP_TRY(hipMemcpyAsync(raw, d_alc, std::min<uint64_t>(len, kSplitHeaderBytes), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    SplitHeader h;
-    ChunkDims d{};
-    TRY(frames_validate(raw, len, first, count, h, d));
-    return frames_decode_device(h, d, (const uint8_t*)d_alc, first, count, d_rgb_out, st, 0);
+    return partial_decode_dev(d_alc, len, first, count, d_rgb_out, hip_stream, [&](const SplitHeader& h, const ChunkDims& d, hipStream_t st) {
+        return frames_decode_device(h, d, (const uint8_t*)d_alc, first, count, d_rgb_out, st, 0);
+    });
 }
 
 uint8_t* alice_codec_decode_frames(const uint8_t* data, uint64_t len, uint32_t first, uint32_t count, uint64_t* out_len) {
     clear_error();
     if (!data || !out_len) { fail(kNullArgument, "null argument"); return nullptr; }
-    auto run = [&](uint8_t** out) -> int {
-        SplitHeader h;
-        ChunkDims d{};
-        TRY(frames_validate(data, len, first, count, h, d));
-        const FramesPlan p = frames_plan(h, d, first, count);
-        // Block offsets from the tables, on the host; the tables get check_split_directories' verdict on the way.  What
-        // goes up: the header, the three tables, the byte runs of the planned blocks -- at their own offsets of a pool
-        // buffer of the container's size, so that the device path runs on it unchanged.  The rest of it stays unwritten
-        // and unread.
-        struct Span { uint64_t off, len; };
-        std::vector<Span> spans;
-        spans.push_back({0, kSplitHeaderBytes});
-        uint64_t payload_bytes = 0, pos = kSplitHeaderBytes;
-        for (int c = 0; c < 3; ++c) {
-            const uint8_t* tab = data + pos;
-            const uint32_t nb = h.n_blocks[c];
-            spans.push_back({pos, 4ull * nb});
-            uint64_t run_off[2] = {0, 0}, run_len[2] = {0, 0};
-            uint64_t sum = 4ull * nb;
-            for (uint32_t blk = 0; blk < nb; ++blk) {
-                const uint32_t v = get_u32(tab + 4ull * blk);
-                if (v < 128u) return fail(kInvalidBitstream, "channel " + std::to_string(c) + ": block " + std::to_string(blk) + " is shorter than its lane directory");
-                for (int r = 0; r < p.n_ranges; ++r) {
-                    if (blk == p.blk_first[r]) run_off[r] = sum;
-                    if (blk >= p.blk_first[r] && blk - p.blk_first[r] < p.blk_count[r]) run_len[r] += v;
-                }
-                sum += v;
-                if (sum > h.payload_len[c]) break;   // (the sum below refuses it; no span may leave the payload)
-            }
-            if (sum != h.payload_len[c])
-                return fail(kInvalidBitstream, "channel " + std::to_string(c) + ": block lengths do not sum to payload_len " + std::to_string(h.payload_len[c]));
-            for (int r = 0; r < p.n_ranges; ++r)
-                if (run_len[r]) { spans.push_back({pos + run_off[r], run_len[r]}); payload_bytes += run_len[r]; }
-            pos += h.payload_len[c];
-        }
-        const uint64_t bytes = (uint64_t)h.width * h.height * count * 3;
-        *out = host_result_alloc(bytes);
-        if (!*out) return fail(kOutOfMemory, "out of host memory");
-        *out_len = bytes;
-        auto body = [&]() -> int {
-            hipStream_t st;
-            TRY(get_stream(&st));
-            DevBuf d_alc, d_rgb;
-            TRY(d_alc.alloc(len));
-            TRY(d_rgb.alloc(bytes));
-            for (const Span& s : spans)
-                HIP_TRY(hipMemcpyAsync(d_alc.as<uint8_t>() + s.off, data + s.off, s.len, hipMemcpyHostToDevice, st));
-            TRY(frames_decode_device(h, d, d_alc.as<uint8_t>(), first, count, d_rgb.p, st, payload_bytes));
-            return copy_to_host(*out, d_rgb.p, bytes, st);
-        };
-        const int rc = body();
-        if (rc != kOk) { free(*out); *out = nullptr; }
-        return rc;
-    };
+    SplitHeader h;
+    ChunkDims d{};
     uint8_t* out = nullptr;
-    return run(&out) == kOk ? out : nullptr;
+    if (frames_validate(data, len, first, count, h, d) != kOk) return nullptr;
+    partial_decode_host(data, len, h, frames_plan(h, d, first, count).block_list(), (uint64_t)h.width * h.height * count * 3, &out, out_len,
+                        [&](const uint8_t* d_alc, void* d_rgb, hipStream_t st, uint64_t uploaded) {
+                            return frames_decode_device(h, d, d_alc, first, count, d_rgb, st, uploaded);
+                        });
+    return out;
 }
 
 void alice_codec_test_last_frames_stats(uint64_t out[5]) {
@@ -5062,14 +5075,7 @@ int preview_decode_device(const SplitHeader& h, const ChunkDims& d, const Previe
     TRY(d_pj.alloc(up.size()));
     SplitWork w;
     TRY(split_work_alloc(w, 3, d.padded, h.lane_symbols, false, fmt));
-    uint64_t off = kSplitHeaderBytes;
-    for (int c = 0; c < 3; ++c) {
-        SplitJob& s = w.h[(size_t)c];
-        s.sym = d_sym.as<uint8_t>() + (size_t)c * planes * p.pitch * sb;
-        s.stream = (uint8_t*)d_alc + off;
-        s.len = h.payload_len[c];
-        off += s.len;
-    }
+    split_chunk_jobs(w, 0, h, d_alc, d_sym.as<uint8_t>(), (size_t)planes * p.pitch * sb);
     for (int c = 0; c < 3; ++c) {
         SplitPreviewJob& j = pj[(size_t)c];
         j.j = w.h[(size_t)c];
@@ -5116,83 +5122,24 @@ int alice_codec_preview_dims(uint32_t width, uint32_t height, uint32_t* qw, uint
 }
 
 int alice_codec_dev_decode_preview(const void* d_alc, uint64_t len, uint32_t first, uint32_t count, void* d_rgb_out, void* hip_stream) {
-    clear_error();
-    if (!d_alc || !d_rgb_out) return fail(kNullArgument, "null argument");
-    TRY(ensure_device());
-    hipStream_t st = (hipStream_t)hip_stream;
-    ScopeStream scope(st);
-    // the header comes to the host first; nothing is queued before it and the range have been accepted
-    uint8_t raw[kSplitHeaderBytes] = {};
-    if (len) {
-        HIP_TRY(hipMemcpyAsync(raw, d_alc, std::min<uint64_t>(len, kSplitHeaderBytes), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    SplitHeader h;
-    ChunkDims d{};
-    TRY(frames_validate(raw, len, first, count, h, d));
-    return preview_decode_device(h, d, preview_plan(h, d, first, count), (const uint8_t*)d_alc, first, count, d_rgb_out, st, 0);
+    return partial_decode_dev(d_alc, len, first, count, d_rgb_out, hip_stream, [&](const SplitHeader& h, const ChunkDims& d, hipStream_t st) {
+        return preview_decode_device(h, d, preview_plan(h, d, first, count), (const uint8_t*)d_alc, first, count, d_rgb_out, st, 0);
+    });
 }
 
 uint8_t* alice_codec_decode_preview(const uint8_t* data, uint64_t len, uint32_t first, uint32_t count, uint64_t* out_len) {
     clear_error();
     if (!data || !out_len) { fail(kNullArgument, "null argument"); return nullptr; }
-    auto run = [&](uint8_t** out) -> int {
-        SplitHeader h;
-        ChunkDims d{};
-        TRY(frames_validate(data, len, first, count, h, d));
-        const PreviewPlan p = preview_plan(h, d, first, count);
-        // As alice_codec_decode_frames does: block offsets from the tables, on the host, with the directory verdict on the
-        // way; the header, the three tables and the byte runs of consecutive planned blocks go up at their own offsets.
-        struct Span { uint64_t off, len; };
-        std::vector<Span> spans;
-        spans.push_back({0, kSplitHeaderBytes});
-        uint64_t payload_bytes = 0, pos = kSplitHeaderBytes;
-        for (int c = 0; c < 3; ++c) {
-            const uint8_t* tab = data + pos;
-            const uint32_t nb = h.n_blocks[c];
-            spans.push_back({pos, 4ull * nb});
-            uint64_t sum = 4ull * nb;
-            size_t next = 0;            // the next planned block
-            bool open = false;          // the last span ends where this block starts
-            for (uint32_t blk = 0; blk < nb; ++blk) {
-                const uint32_t v = get_u32(tab + 4ull * blk);
-                if (v < 128u) return fail(kInvalidBitstream, "channel " + std::to_string(c) + ": block " + std::to_string(blk) + " is shorter than its lane directory");
-                if (sum + v > h.payload_len[c]) { sum += v; break; }   // (the sum below refuses it; no span may leave the payload)
-                if (next < p.blocks.size() && p.blocks[next] == blk) {
-                    if (open) spans.back().len += v; else spans.push_back({pos + sum, v});
-                    payload_bytes += v;
-                    open = true;
-                    ++next;
-                } else {
-                    open = false;
-                }
-                sum += v;
-            }
-            if (sum != h.payload_len[c])
-                return fail(kInvalidBitstream, "channel " + std::to_string(c) + ": block lengths do not sum to payload_len " + std::to_string(h.payload_len[c]));
-            pos += h.payload_len[c];
-        }
-        const uint64_t bytes = p.qw * p.qh * count * 3;
-        *out = host_result_alloc(bytes);
-        if (!*out) return fail(kOutOfMemory, "out of host memory");
-        *out_len = bytes;
-        auto body = [&]() -> int {
-            hipStream_t st;
-            TRY(get_stream(&st));
-            DevBuf d_alc, d_rgb;
-            TRY(d_alc.alloc(len));
-            TRY(d_rgb.alloc(bytes));
-            for (const Span& s : spans)
-                HIP_TRY(hipMemcpyAsync(d_alc.as<uint8_t>() + s.off, data + s.off, s.len, hipMemcpyHostToDevice, st));
-            TRY(preview_decode_device(h, d, p, d_alc.as<uint8_t>(), first, count, d_rgb.p, st, payload_bytes));
-            return copy_to_host(*out, d_rgb.p, bytes, st);
-        };
-        const int rc = body();
-        if (rc != kOk) { free(*out); *out = nullptr; }
-        return rc;
-    };
+    SplitHeader h;
+    ChunkDims d{};
+    if (frames_validate(data, len, first, count, h, d) != kOk) return nullptr;
+    const PreviewPlan p = preview_plan(h, d, first, count);
     uint8_t* out = nullptr;
-    return run(&out) == kOk ? out : nullptr;
+    partial_decode_host(data, len, h, p.blocks, p.qw * p.qh * count * 3, &out, out_len,
+                        [&](const uint8_t* d_alc, void* d_rgb, hipStream_t st, uint64_t uploaded) {
+                            return preview_decode_device(h, d, p, d_alc, first, count, d_rgb, st, uploaded);
+                        });
+    return out;
 }
 
 void alice_codec_test_last_preview_stats(uint64_t out[6]) {

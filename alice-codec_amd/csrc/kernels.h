@@ -360,23 +360,20 @@ struct SplitHeaderDesc {
 void launch_split_table(const uint32_t* d_hist, uint16_t* d_freq, uint16_t* d_cum, int n_tables, hipStream_t st);
 // max_blocks: the largest n_blocks among the jobs.  count fills lane_len and blk_len; scan(from_stream = false) turns
 // blk_len into blk_off and the payload lengths d_totals[job]; write then needs `stream` to hold that many bytes.
-void launch_split_count(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, hipStream_t st);
-void launch_split_write(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, hipStream_t st);
+// wide: the same passes on u16 symbols with the escape step (.alc v3); the count pass then sets kSplitWideResidual in
+// *flags (zeroed by the caller) when a symbol exceeds 255 + kSplitWideMaxResidual
+void launch_split_count(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, bool wide, hipStream_t st);
+void launch_split_write(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, bool wide, hipStream_t st);
 void launch_split_scan(const SplitJob* d_jobs, int n_jobs, bool from_stream, unsigned long long* d_totals, hipStream_t st);
 // after scan(from_stream = true); *flags != 0 afterwards: the payload is not a valid stream
-void launch_split_decode(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, hipStream_t st);
+void launch_split_decode(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, bool wide, hipStream_t st);
 void launch_split_headers(const SplitHeaderDesc* d_descs, int n_chunks, hipStream_t st);
 // after scan(from_stream = true) over the same channels; max_blocks: the largest blk_count[0] + blk_count[1] among the jobs
 void launch_split_frames_decode(const SplitFramesJob* d_jobs, int n_jobs, uint32_t max_blocks, bool wide, hipStream_t st);
 // after scan(from_stream = true) over the same channels; max_planned: the largest n_planned among the jobs
 void launch_split_preview_decode(const SplitPreviewJob* d_jobs, int n_jobs, uint32_t max_planned, bool wide, hipStream_t st);
-// the same three passes on u16 symbols with the escape step (.alc v3); the count pass sets kSplitWideResidual in *flags
-// (zeroed by the caller) when a symbol exceeds 255 + kSplitWideMaxResidual
 // overwrites the version byte of the headers launch_split_headers wrote (same stream, after it)
 void launch_split_header_version(const SplitHeaderDesc* d_descs, int n_chunks, uint8_t version, hipStream_t st);
-void launch_split_wide_count(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, hipStream_t st);
-void launch_split_wide_write(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, hipStream_t st);
-void launch_split_wide_decode(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, hipStream_t st);
 
 // ---- quality.hip: exact squared error of two RGB volumes ----
 constexpr uint32_t kSseBlock = 256;               // lanes of a workgroup

@@ -1,4 +1,4 @@
-// Split-stream entropy stage (.alc v2) for gfx950.
+// Split-stream entropy stage (.alc v2 to v4; DESIGN.md sections 10, 11, 14, 15) for gfx950.
 //
 // A channel's symbols are cut into blocks of 64 * L consecutive symbols; inside a block lane j owns symbols j, j + 64,
 // j + 128, ... and codes them as an independent rANS chain with the reference coder's parameters (32-bit state, lower
@@ -6,15 +6,18 @@
 // block, one lane per chain: the opposite operating point to the v1 chain kernels of rans.hip -- tens of thousands of
 // short chains, several wavefronts per SIMD, latency hidden by occupancy instead of by a stripped dependency chain.
 //
-// Kernels:
+// The chain stands once per direction: lane_encode<WIDE, kWrite> and lane_decode<WIDE>(..., store).  WIDE is the u16
+// symbol with the escape step of .alc v3.  The kernels are faces of the two: a kernel chooses the block its wavefront
+// takes and, when decoding, what happens to symbol i once it is known.  (split_frames_decode_kernel carries its own
+// copy of the decode chain: see there.)
 //   split_table_kernel    histogram -> normalised frequencies (sum exactly 4096) and their running sum
-//   split_encode_kernel   <false> counts every lane's stream length, <true> writes directory and streams in place
+//   split_encode_kernel / split_wide_encode_kernel   <false> counts every lane's stream length, <true> writes directory
+//                         and streams in place
 //   split_scan_kernel     block lengths -> block offsets (encode: from the count pass; decode: from the stream, validated)
-//   split_decode_kernel   lane streams -> symbols, with the end check of every lane
-//   split_header_kernel   the 1630-byte container header of whole chunks
-//   split_frames_decode_kernel   the lane decode of the blocks a frame range needs, stored as a compact volume
-//   split_preview_decode_kernel  the lane decode of the blocks a half-resolution preview needs: low-low quadrants only
-//   split_wide_encode_kernel / split_wide_decode_kernel   the same chains on u16 symbols with the escape step of .alc v3
+//   split_decode_kernel / split_wide_decode_kernel   every block; symbol i at the lane's own position
+//   split_frames_decode_kernel<WIDE>    the blocks a frame range needs, stored as a compact volume
+//   split_preview_decode_kernel<WIDE>   the blocks a half-resolution preview needs: low-low quadrants only
+//   split_header_kernel / split_version_kernel   the 1630-byte container header of whole chunks
 // The output is sized by counting first and writing second: the chain arithmetic runs twice, but nothing is staged in
 // worst-case slots (2 bytes per symbol) and no compaction pass moves the payload again.
 //
@@ -29,6 +32,8 @@ namespace alice {
 
 namespace {
 
+template <bool WIDE> using SplitSym = std::conditional_t<WIDE, uint16_t, uint8_t>;
+
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane) {
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
@@ -36,6 +41,28 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane) {
         if (lane >= d) v += o;
     }
     return v;
+}
+
+// Block b of a job (b < n_blocks): its first symbol, its symbol count, and how many of them lane `lane` owns.
+struct LaneGeometry {
+    unsigned long long base;
+    uint32_t in_block, k;
+    __device__ __forceinline__ LaneGeometry(const SplitJob& job, unsigned long long b, int lane) {
+        base = b * 64ull * job.lane_symbols;
+        const unsigned long long left = job.n - base;
+        in_block = left < 64ull * job.lane_symbols ? (uint32_t)left : 64u * job.lane_symbols;
+        k = (uint32_t)lane < in_block ? (in_block - (uint32_t)lane + 63u) / 64u : 0u;
+    }
+};
+
+// The decoders' LDS tables, loaded by the 256 threads of a workgroup: the slot -> symbol map (4096 x u8) and
+// freq | cum << 16 per symbol.
+__device__ __forceinline__ void load_decode_tables(const RansTable* table, uint32_t* c2s_sh, uint32_t* symtab) {
+    const uint32_t* src = (const uint32_t*)table->dec.c2s;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) c2s_sh[threadIdx.x + 256 * t] = src[threadIdx.x + 256 * t];
+    symtab[threadIdx.x] = table->dec.symtab[threadIdx.x];
+    __syncthreads();
 }
 
 }  // namespace
@@ -70,10 +97,16 @@ __global__ __launch_bounds__(256) void split_table_kernel(const uint32_t* __rest
 // (one ds_read_b128 per symbol): xmax = freq << 19, the exact reciprocal, cum bias, and 4096 - freq with the shift.
 // The chain walks a lane's symbols last to first and writes its bytes back to front, so the finished stream reads
 // forward: four state bytes, most significant first, then the renormalisation bytes in the order the decoder wants them.
+//
+// The escape rule of the wide coder (.alc v3; u16 symbols, 128 consecutive bytes per wavefront
+// step): the coded symbol is s = min(z, 255); s = 255 is an escape followed in the same chain by the residual r = z - 255
+// as one uniform 12-bit step (frequency 1, cum r: xmax = 2^19, x = (x << 12) + r).  The encoder walks last to first, so
+// it codes the residual BEFORE the step of symbol 255; the decoder meets them the other way round.  A residual above 4095
+// cannot be coded: the count pass records it in *job.flags (kSplitWideResidual) and the host refuses the call before the
+// write pass runs; the write pass masks r so that its byte count stays the counted one.
 // ----------------------------------------------------------------------------------
-template <bool kWrite>
-__global__ __launch_bounds__(256) void split_encode_kernel(const SplitJob* __restrict__ jobs) {
-    __shared__ uint4 rows[256];
+template <bool WIDE, bool kWrite>
+__device__ __forceinline__ void lane_encode(const SplitJob* jobs, uint4* rows) {
     const SplitJob job = jobs[blockIdx.y];
     {
         const RansEncEntry e = job.table->enc[threadIdx.x];
@@ -83,16 +116,14 @@ __global__ __launch_bounds__(256) void split_encode_kernel(const SplitJob* __res
     const int lane = threadIdx.x & 63;
     const unsigned long long b = (unsigned long long)blockIdx.x * 4u + (threadIdx.x >> 6);
     if (b >= job.n_blocks) return;
-    const unsigned long long base = b * 64ull * job.lane_symbols;
-    const unsigned long long left = job.n - base;
-    const uint32_t in_block = left < 64ull * job.lane_symbols ? (uint32_t)left : 64u * job.lane_symbols;
-    const uint32_t k = (uint32_t)lane < in_block ? (in_block - (uint32_t)lane + 63u) / 64u : 0u;
-    const uint32_t kmax = (in_block + 63u) / 64u;   // lane 0's count
-    const uint8_t* __restrict__ sym = job.sym + base + lane;
+    const LaneGeometry g(job, b, lane);
+    const uint32_t k = g.k, kmax = (g.in_block + 63u) / 64u;   // kmax: lane 0's count
+    const SplitSym<WIDE>* __restrict__ sym = (const SplitSym<WIDE>*)job.sym + g.base + lane;
 
     uint32_t len = 0u;              // bytes of this lane's stream
     uint8_t* out = nullptr;         // kWrite: one past the lane's last byte
     uint32_t acc = 0u, nacc = 0u;   // kWrite: bytes collected for the dword in progress (lowest address in the low byte)
+    bool wide_bad = false;          // WIDE count pass: a residual above 4095
     if (kWrite) {
         len = job.lane_len[b * 64u + lane];
         const uint32_t incl = wave_incl_scan(len, lane);
@@ -129,11 +160,19 @@ __global__ __launch_bounds__(256) void split_encode_kernel(const SplitJob* __res
         for (uint32_t u = 0; u < 8u; ++u) {
             const uint32_t i = hi - 1u - u;
             if (i < k) {
-                const uint4 r = rows[s[u]];
-                if (x >= r.x) { put(x & 255u); x >>= 8; }
-                if (x >= r.x) { put(x & 255u); x >>= 8; }
-                const uint32_t q = __umulhi(x, r.y) >> (r.w >> 16);
-                x = x + q * (r.w & 0xFFFFu) + r.z;
+                const uint32_t z = s[u];
+                if (WIDE && z >= 255u) {
+                    const uint32_t r = z - 255u;
+                    if (r > kSplitWideMaxResidual) wide_bad = true;
+                    if (x >= (1u << 19)) { put(x & 255u); x >>= 8; }
+                    if (x >= (1u << 19)) { put(x & 255u); x >>= 8; }
+                    x = (x << 12) + (r & kSplitWideMaxResidual);
+                }
+                const uint4 row = rows[WIDE && z >= 255u ? 255u : z];
+                if (x >= row.x) { put(x & 255u); x >>= 8; }
+                if (x >= row.x) { put(x & 255u); x >>= 8; }
+                const uint32_t q = __umulhi(x, row.y) >> (row.w >> 16);
+                x = x + q * (row.w & 0xFFFFu) + row.z;
             }
         }
     }
@@ -146,7 +185,19 @@ __global__ __launch_bounds__(256) void split_encode_kernel(const SplitJob* __res
         job.lane_len[b * 64u + lane] = (uint16_t)len;
         const uint32_t incl = wave_incl_scan(len, lane);
         if (lane == 63) job.blk_len[b] = 128u + incl;
+        if (WIDE && wide_bad) *job.flags = kSplitWideResidual;
     }
+}
+
+template <bool kWrite>
+__global__ __launch_bounds__(256) void split_encode_kernel(const SplitJob* __restrict__ jobs) {
+    __shared__ uint4 rows[256];
+    lane_encode<false, kWrite>(jobs, rows);
+}
+template <bool kWrite>
+__global__ __launch_bounds__(256) void split_wide_encode_kernel(const SplitJob* __restrict__ jobs) {
+    __shared__ uint4 rows[256];
+    lane_encode<true, kWrite>(jobs, rows);
 }
 
 // ----------------------------------------------------------------------------------
@@ -193,7 +244,7 @@ __global__ __launch_bounds__(256) void split_scan_kernel(const SplitJob* __restr
             const unsigned long long off = carry + sc[s] - v;
             if (kFromStream && (v < 128u || off + v > job.len)) {
                 bad_sh = 1u;
-                job.blk_len[b] = 0u;   // the decode kernel skips the block
+                job.blk_len[b] = 0u;   // the decoders skip the block
                 job.blk_off[b] = 0ull;
             } else {
                 job.blk_off[b] = off;
@@ -210,206 +261,16 @@ __global__ __launch_bounds__(256) void split_scan_kernel(const SplitJob* __restr
 }
 
 // ----------------------------------------------------------------------------------
-// Decoder: the geometry of the encoder.  LDS holds the slot -> symbol map (4096 x u8) and freq | cum << 16 per symbol.
+// Decoder: the geometry of the encoder.  lane_decode runs lane `lane` of block b (k symbols, tables in LDS) and hands
+// symbol i to store(i, s), once per symbol and in order; WIDE adds the escape step (see the encoder).
 // A lane reads its stream four bytes at a time; a read never leaves [lane start, lane end): past the end the window
 // is zero-filled and the cursor keeps counting, so a damaged stream ends in a failed end check (state back at 2^23,
-// cursor at the end of the stream) and never in an access outside the payload.  Every symbol store lies inside the block.
+// cursor at the end of the stream) and never in an access outside the payload.  A damaged wide stream can give any
+// residual in 0..4095, so any z up to 4350; it is handed to store like every other symbol.
 // ----------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void split_decode_kernel(const SplitJob* __restrict__ jobs) {
-    __shared__ uint32_t c2s_sh[kProbScale / 4];
-    __shared__ uint32_t symtab[256];
-    const SplitJob job = jobs[blockIdx.y];
-    {
-        const uint32_t* src = (const uint32_t*)job.table->dec.c2s;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) c2s_sh[threadIdx.x + 256 * t] = src[threadIdx.x + 256 * t];
-        symtab[threadIdx.x] = job.table->dec.symtab[threadIdx.x];
-    }
-    __syncthreads();
-    const uint8_t* c2s = (const uint8_t*)c2s_sh;
-    const int lane = threadIdx.x & 63;
-    const unsigned long long b = (unsigned long long)blockIdx.x * 4u + (threadIdx.x >> 6);
-    if (b >= job.n_blocks) return;
-    const unsigned long long base = b * 64ull * job.lane_symbols;
-    const unsigned long long left = job.n - base;
-    const uint32_t in_block = left < 64ull * job.lane_symbols ? (uint32_t)left : 64u * job.lane_symbols;
-    const uint32_t k = (uint32_t)lane < in_block ? (in_block - (uint32_t)lane + 63u) / 64u : 0u;
-    uint8_t* __restrict__ sym = (uint8_t*)job.sym + base + lane;
-
-    const uint32_t blen = job.blk_len[b];
-    const unsigned long long boff = job.blk_off[b];
-    // (the scan left 0 for a block it refused; checked again here so that the bounds do not rest on another kernel)
-    if (blen < 128u || boff + blen > job.len) { if (lane == 0) *job.flags = kSplitBadDirectory; return; }
-    const uint8_t* blk = job.stream + boff;
-    const uint32_t len = (uint32_t)blk[2 * lane] | ((uint32_t)blk[2 * lane + 1] << 8);
-    const uint32_t incl = wave_incl_scan(len, lane);
-    const uint32_t all = __shfl(incl, 63, 64);
-    if (all + 128u != blen) { if (lane == 0) *job.flags = kSplitBadDirectory; return; }
-    const uint8_t* __restrict__ src = blk + 128u + (incl - len);   // [src, src + len) lies inside the block
-
-    uint32_t win = 0u, nwin = 0u, fpos = 0u, pos = 0u;
-    auto take = [&]() -> uint32_t {
-        if (nwin == 0u) {
-            uint32_t w = 0u;
-            if (fpos + 4u <= len) {
-                uint32_t t;
-                __builtin_memcpy(&t, src + fpos, 4);
-                w = __builtin_bswap32(t);
-            } else {
-#pragma unroll
-                for (uint32_t t = 0; t < 4u; ++t) w = (w << 8) | (fpos + t < len ? (uint32_t)src[fpos + t] : 0u);
-            }
-            fpos += 4u;
-            win = w;
-            nwin = 4u;
-        }
-        const uint32_t byte = win >> 24;
-        win <<= 8;
-        --nwin;
-        ++pos;
-        return byte;
-    };
-    bool ok = true;
-    if (k == 0u) {
-        ok = len == 0u;
-    } else {
-        uint32_t x = take() << 24;
-        x |= take() << 16;
-        x |= take() << 8;
-        x |= take();
-        for (uint32_t i = 0; i < k; ++i) {
-            const uint32_t slot = x & (kProbScale - 1u);
-            const uint32_t s = c2s[slot];
-            const uint32_t fc = symtab[s];
-            x = (fc & 0xFFFFu) * (x >> kProbBits) + slot - (fc >> 16);
-            if (x < kRansL) x = (x << 8) | take();
-            if (x < kRansL) x = (x << 8) | take();
-            sym[(size_t)i * 64u] = (uint8_t)s;
-        }
-        ok = x == kRansL && pos == len;
-    }
-    if (!ok) *job.flags = kSplitBadLane;
-}
-
-// ----------------------------------------------------------------------------------
-// Wide lane coder (.alc v3): the geometry of the kernels above on u16 symbols (128 consecutive
-// bytes per wavefront step).  The coded symbol is s = min(z, 255); s = 255 is an escape followed in the same chain by the
-// residual r = z - 255 as one uniform 12-bit step (frequency 1, cum r: xmax = 2^19, x = (x << 12) + r).  The encoder
-// walks last to first, so it codes the residual BEFORE the step of symbol 255; the decoder meets them the other way round.
-// A residual above 4095 cannot be coded: the count pass records it in *job.flags (kSplitWideResidual) and the host
-// refuses the call before the write pass runs; the write pass masks r so that its byte count stays the counted one.
-// ----------------------------------------------------------------------------------
-template <bool kWrite>
-__global__ __launch_bounds__(256) void split_wide_encode_kernel(const SplitJob* __restrict__ jobs) {
-    __shared__ uint4 rows[256];
-    const SplitJob job = jobs[blockIdx.y];
-    {
-        const RansEncEntry e = job.table->enc[threadIdx.x];
-        rows[threadIdx.x] = make_uint4(e.xmax, e.rcp, e.cbias, (uint32_t)e.g | (e.rsh << 16));
-    }
-    __syncthreads();
-    const int lane = threadIdx.x & 63;
-    const unsigned long long b = (unsigned long long)blockIdx.x * 4u + (threadIdx.x >> 6);
-    if (b >= job.n_blocks) return;
-    const unsigned long long base = b * 64ull * job.lane_symbols;
-    const unsigned long long left = job.n - base;
-    const uint32_t in_block = left < 64ull * job.lane_symbols ? (uint32_t)left : 64u * job.lane_symbols;
-    const uint32_t k = (uint32_t)lane < in_block ? (in_block - (uint32_t)lane + 63u) / 64u : 0u;
-    const uint32_t kmax = (in_block + 63u) / 64u;   // lane 0's count
-    const uint16_t* __restrict__ sym = (const uint16_t*)job.sym + base + lane;
-
-    uint32_t len = 0u;              // bytes of this lane's stream
-    uint8_t* out = nullptr;         // kWrite: one past the lane's last byte
-    uint32_t acc = 0u, nacc = 0u;   // kWrite: bytes collected for the dword in progress (lowest address in the low byte)
-    bool wide_bad = false;          // count pass: a residual above 4095
-    if (kWrite) {
-        len = job.lane_len[b * 64u + lane];
-        const uint32_t incl = wave_incl_scan(len, lane);
-        uint8_t* blk = job.stream + job.blk_off[b];
-        blk[2 * lane] = (uint8_t)len;
-        blk[2 * lane + 1] = (uint8_t)(len >> 8);
-        if (lane < 4) job.stream[4ull * b + lane] = (uint8_t)(job.blk_len[b] >> (8 * lane));
-        out = blk + 128u + incl;
-    }
-    auto put = [&](uint32_t byte) {
-        if (kWrite) {
-            --out;
-            acc = (acc << 8) | byte;
-            ++nacc;
-            if (((uintptr_t)out & 3u) == 0u) {
-                if (nacc == 4u) *(uint32_t*)out = acc;
-                else for (uint32_t t = 0; t < nacc; ++t) out[t] = (uint8_t)(acc >> (8u * t));
-                nacc = 0u;
-            }
-        } else {
-            ++len;
-        }
-    };
-    uint32_t x = kRansL;
-    // eight symbols are loaded ahead of the chain that consumes them
-    for (uint32_t hi = kmax; hi > 0u; hi = hi > 8u ? hi - 8u : 0u) {
-        uint32_t s[8];
-#pragma unroll
-        for (uint32_t u = 0; u < 8u; ++u) {
-            const uint32_t i = hi - 1u - u;   // wraps past 0: then i >= k
-            s[u] = i < k ? sym[(size_t)i * 64u] : 0u;
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < 8u; ++u) {
-            const uint32_t i = hi - 1u - u;
-            if (i < k) {
-                const uint32_t z = s[u];
-                if (z >= 255u) {
-                    const uint32_t r = z - 255u;
-                    if (r > kSplitWideMaxResidual) wide_bad = true;
-                    if (x >= (1u << 19)) { put(x & 255u); x >>= 8; }
-                    if (x >= (1u << 19)) { put(x & 255u); x >>= 8; }
-                    x = (x << 12) + (r & kSplitWideMaxResidual);
-                }
-                const uint4 row = rows[z < 255u ? z : 255u];
-                if (x >= row.x) { put(x & 255u); x >>= 8; }
-                if (x >= row.x) { put(x & 255u); x >>= 8; }
-                const uint32_t q = __umulhi(x, row.y) >> (row.w >> 16);
-                x = x + q * (row.w & 0xFFFFu) + row.z;
-            }
-        }
-    }
-    if (k) {
-        put(x & 255u); put((x >> 8) & 255u); put((x >> 16) & 255u); put(x >> 24);
-    }
-    if (kWrite) {
-        for (uint32_t t = 0; t < nacc; ++t) out[t] = (uint8_t)(acc >> (8u * t));
-    } else {
-        job.lane_len[b * 64u + lane] = (uint16_t)len;
-        const uint32_t incl = wave_incl_scan(len, lane);
-        if (lane == 63) job.blk_len[b] = 128u + incl;
-        if (wide_bad) *job.flags = kSplitWideResidual;
-    }
-}
-
-// The wide decoder: split_decode_kernel with the escape step.  A damaged stream can give any residual in 0..4095, so any
-// z up to 4350; it is stored like every other symbol, at the lane's own position inside the block.
-__global__ __launch_bounds__(256) void split_wide_decode_kernel(const SplitJob* __restrict__ jobs) {
-    __shared__ uint32_t c2s_sh[kProbScale / 4];
-    __shared__ uint32_t symtab[256];
-    const SplitJob job = jobs[blockIdx.y];
-    {
-        const uint32_t* src = (const uint32_t*)job.table->dec.c2s;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) c2s_sh[threadIdx.x + 256 * t] = src[threadIdx.x + 256 * t];
-        symtab[threadIdx.x] = job.table->dec.symtab[threadIdx.x];
-    }
-    __syncthreads();
-    const uint8_t* c2s = (const uint8_t*)c2s_sh;
-    const int lane = threadIdx.x & 63;
-    const unsigned long long b = (unsigned long long)blockIdx.x * 4u + (threadIdx.x >> 6);
-    if (b >= job.n_blocks) return;
-    const unsigned long long base = b * 64ull * job.lane_symbols;
-    const unsigned long long left = job.n - base;
-    const uint32_t in_block = left < 64ull * job.lane_symbols ? (uint32_t)left : 64u * job.lane_symbols;
-    const uint32_t k = (uint32_t)lane < in_block ? (in_block - (uint32_t)lane + 63u) / 64u : 0u;
-    uint16_t* __restrict__ sym = (uint16_t*)job.sym + base + lane;   // symbol i of the lane: base + lane + 64 i < base + in_block
-
+template <bool WIDE, typename Store>
+__device__ __forceinline__ void lane_decode(const SplitJob& job, unsigned long long b, int lane, uint32_t k, const uint8_t* c2s,
+                                            const uint32_t* symtab, Store store) {
     const uint32_t blen = job.blk_len[b];
     const unsigned long long boff = job.blk_off[b];
     // (the scan left 0 for a block it refused; checked again here so that the bounds do not rest on another kernel)
@@ -458,58 +319,78 @@ __global__ __launch_bounds__(256) void split_wide_decode_kernel(const SplitJob* 
             x = (fc & 0xFFFFu) * (x >> kProbBits) + slot - (fc >> 16);
             if (x < kRansL) x = (x << 8) | take();
             if (x < kRansL) x = (x << 8) | take();
-            if (s == 255u) {
+            if (WIDE && s == 255u) {
                 s += x & kSplitWideMaxResidual;
                 x >>= 12;
                 if (x < kRansL) x = (x << 8) | take();
                 if (x < kRansL) x = (x << 8) | take();
             }
-            sym[(size_t)i * 64u] = (uint16_t)s;
+            store(i, s);
         }
         ok = x == kRansL && pos == len;
     }
     if (!ok) *job.flags = kSplitBadLane;
 }
 
+// Every block of job blockIdx.y, four per workgroup.  Symbol i of the lane goes to its own position inside the block:
+// base + lane + 64 i < base + in_block.
+template <bool WIDE>
+__device__ __forceinline__ void decode_every_block(const SplitJob* jobs, uint32_t* c2s_sh, uint32_t* symtab) {
+    const SplitJob job = jobs[blockIdx.y];
+    load_decode_tables(job.table, c2s_sh, symtab);
+    const int lane = threadIdx.x & 63;
+    const unsigned long long b = (unsigned long long)blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (b >= job.n_blocks) return;
+    const LaneGeometry g(job, b, lane);
+    SplitSym<WIDE>* __restrict__ sym = (SplitSym<WIDE>*)job.sym + g.base + lane;
+    lane_decode<WIDE>(job, b, lane, g.k, (const uint8_t*)c2s_sh, symtab,
+                      [&](uint32_t i, uint32_t s) { sym[(size_t)i * 64u] = (SplitSym<WIDE>)s; });
+}
+
+__global__ __launch_bounds__(256) void split_decode_kernel(const SplitJob* __restrict__ jobs) {
+    __shared__ uint32_t c2s_sh[kProbScale / 4];
+    __shared__ uint32_t symtab[256];
+    decode_every_block<false>(jobs, c2s_sh, symtab);
+}
+__global__ __launch_bounds__(256) void split_wide_decode_kernel(const SplitJob* __restrict__ jobs) {
+    __shared__ uint32_t c2s_sh[kProbScale / 4];
+    __shared__ uint32_t symtab[256];
+    decode_every_block<true>(jobs, c2s_sh, symtab);
+}
+
 // ----------------------------------------------------------------------------------
-// Lane decode of a block subset (frame ranges): the geometry, tables and bounds re-checks of the two
-// decoders above over the one or two runs of blocks a SplitFramesJob names.  A block that straddles an edge of a symbol
-// range still runs its 64 chains to their end checks (a chain is serial, and its end check is the integrity check), but
-// stores only the symbols inside the ranges, relocated into the compact volume at job.j.sym: range 0 first, range 1
-// behind it.  The two symbol ranges become two per-lane iteration ranges before the chain loop, so the loop itself
-// carries two 32-bit compares.  End checks cover the decoded blocks only.
+// Lane decode of a block subset (frame ranges): the one or two runs of blocks a SplitFramesJob
+// names.  A block that straddles an edge of a symbol range still runs its 64 chains to their end checks (a chain is
+// serial, and its end check is the integrity check), but stores only the symbols inside the ranges, relocated into the
+// compact volume at job.j.sym: range 0 first, range 1 behind it.  The two symbol ranges become two per-lane iteration
+// ranges before the chain loop, so the loop itself carries two 32-bit compares.  End checks cover the decoded blocks only.
+// This kernel alone keeps a copy of lane_decode's checks, window and chain: with the range store passed as a callback the
+// WIDE instance measured 0.6 to 1.1 % slower (the two stores fold into one behind a selected address), outside the
+// run-to-run spread.  A change to lane_decode is repeated below.
 // ----------------------------------------------------------------------------------
 template <bool WIDE>
 __global__ __launch_bounds__(256) void split_frames_decode_kernel(const SplitFramesJob* __restrict__ jobs) {
-    using SymT = std::conditional_t<WIDE, uint16_t, uint8_t>;
+    using SymT = SplitSym<WIDE>;
     __shared__ uint32_t c2s_sh[kProbScale / 4];
     __shared__ uint32_t symtab[256];
     const SplitFramesJob fj = jobs[blockIdx.y];
     const SplitJob& job = fj.j;
-    {
-        const uint32_t* src = (const uint32_t*)job.table->dec.c2s;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) c2s_sh[threadIdx.x + 256 * t] = src[threadIdx.x + 256 * t];
-        symtab[threadIdx.x] = job.table->dec.symtab[threadIdx.x];
-    }
-    __syncthreads();
+    load_decode_tables(job.table, c2s_sh, symtab);
     const uint8_t* c2s = (const uint8_t*)c2s_sh;
     const int lane = threadIdx.x & 63;
     const unsigned long long slot = (unsigned long long)blockIdx.x * 4u + (threadIdx.x >> 6);
     if (slot >= (unsigned long long)fj.blk_count[0] + fj.blk_count[1]) return;
     const unsigned long long b = slot < fj.blk_count[0] ? fj.blk_first[0] + slot : fj.blk_first[1] + (slot - fj.blk_count[0]);
     if (b >= job.n_blocks) return;   // (the host plans inside the channel; the bounds below do not rest on it)
-    const unsigned long long base = b * 64ull * job.lane_symbols;
-    const unsigned long long left = job.n - base;
-    const uint32_t in_block = left < 64ull * job.lane_symbols ? (uint32_t)left : 64u * job.lane_symbols;
-    const uint32_t k = (uint32_t)lane < in_block ? (in_block - (uint32_t)lane + 63u) / 64u : 0u;
+    const LaneGeometry g(job, b, lane);
+    const uint32_t k = g.k;
 
     // Range r keeps the lane's symbols i in [lo[r], hi[r]): position base + lane + 64 i inside [sym_lo[r], sym_hi[r]).
     // Symbol i of range r goes to out[off[r] + 64 i]; off[r] + 64 i is the position inside the compact volume, so it
     // lies inside range r's part of it for every kept i.  (An inverted range keeps nothing.)
     uint32_t lo[2], hi[2];
     long long off[2];
-    const unsigned long long p0 = base + (unsigned)lane;
+    const unsigned long long p0 = g.base + (unsigned)lane;
     unsigned long long before = 0;
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
@@ -586,43 +467,32 @@ __global__ __launch_bounds__(256) void split_frames_decode_kernel(const SplitFra
 }
 
 // ----------------------------------------------------------------------------------
-// Lane decode for the half-resolution preview: the geometry, tables and bounds re-checks of the
-// decoders above over the blocks a SplitPreviewJob lists (slot -> block through the list).  Every chain runs to its end
-// check; a symbol is stored only when its plane lies in the low or the high window and its (y, x) in the low-low quadrant,
-// relocated into the compact volume [plane][pitch] at job.j.sym.  A lane's positions advance by 64 = dP * P + dy * pw + dx
-// (dy * pw + dx < P), so (x, y, t') are carried with three adds and at most one wrap each -- also for pw = 2 and P < 64
-// (then dP >= 1).  The 64-bit divisions happen once per lane, before the chain loop; the coordinates do not depend on
-// the chain's state, so the serial dependency is the decoders' own.
+// Lane decode for the half-resolution preview: the blocks a SplitPreviewJob lists (slot -> block
+// through the list).  Every chain runs to its end check; a symbol is stored only when its plane lies in the low or the
+// high window and its (y, x) in the low-low quadrant, relocated into the compact volume [plane][pitch] at job.j.sym.  A
+// lane's positions advance by 64 = dP * P + dy * pw + dx (dy * pw + dx < P), so (x, y, t') are carried with three adds and
+// at most one wrap each -- also for pw = 2 and P < 64 (then dP >= 1).  The 64-bit divisions happen once per lane, before
+// the chain loop; the coordinates do not depend on the chain's state, so the serial dependency is lane_decode's own.
 // ----------------------------------------------------------------------------------
 template <bool WIDE>
 __global__ __launch_bounds__(256) void split_preview_decode_kernel(const SplitPreviewJob* __restrict__ jobs) {
-    using SymT = std::conditional_t<WIDE, uint16_t, uint8_t>;
+    using SymT = SplitSym<WIDE>;
     __shared__ uint32_t c2s_sh[kProbScale / 4];
     __shared__ uint32_t symtab[256];
     const SplitPreviewJob pj = jobs[blockIdx.y];
     const SplitJob& job = pj.j;
-    {
-        const uint32_t* src = (const uint32_t*)job.table->dec.c2s;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) c2s_sh[threadIdx.x + 256 * t] = src[threadIdx.x + 256 * t];
-        symtab[threadIdx.x] = job.table->dec.symtab[threadIdx.x];
-    }
-    __syncthreads();
-    const uint8_t* c2s = (const uint8_t*)c2s_sh;
+    load_decode_tables(job.table, c2s_sh, symtab);
     const int lane = threadIdx.x & 63;
     const unsigned long long slot = (unsigned long long)blockIdx.x * 4u + (threadIdx.x >> 6);
     if (slot >= pj.n_planned) return;
     const unsigned long long b = pj.blocks[slot];
-    if (b >= job.n_blocks || !pj.pw || !pj.ph) return;   // (the host plans inside the channel; the bounds below do not rest on it)
-    const unsigned long long base = b * 64ull * job.lane_symbols;
-    const unsigned long long left = job.n - base;
-    const uint32_t in_block = left < 64ull * job.lane_symbols ? (uint32_t)left : 64u * job.lane_symbols;
-    const uint32_t k = (uint32_t)lane < in_block ? (in_block - (uint32_t)lane + 63u) / 64u : 0u;
+    if (b >= job.n_blocks || !pj.pw || !pj.ph) return;   // (the host plans inside the channel; the bounds of lane_decode do not rest on it)
+    const LaneGeometry g(job, b, lane);
 
     // where the lane's first symbol lies, and what 64 positions further means
     const uint32_t pw = pj.pw, ph = pj.ph, qw = pj.qw, qh = pj.qh, hw = pj.hw;
     const unsigned long long P = (unsigned long long)pw * ph;
-    const unsigned long long p0 = base + (unsigned)lane;
+    const unsigned long long p0 = g.base + (unsigned)lane;
     const unsigned long long rem0 = p0 % P, step_rem = 64ull % P;
     uint32_t tp = (uint32_t)(p0 / P), y = (uint32_t)(rem0 / pw), x = (uint32_t)(rem0 % pw);
     const uint32_t dP = (uint32_t)(64ull / P), dy = (uint32_t)(step_rem / pw), dx = (uint32_t)(step_rem % pw);   // dy, dx < 64
@@ -637,76 +507,20 @@ __global__ __launch_bounds__(256) void split_preview_decode_kernel(const SplitPr
     const long long ywrap_off = pitch - (long long)ph * qw;                       // y -= ph, ++t'
     const long long high_off = ((long long)hw - (long long)pj.half) * pitch;
     const unsigned long long limit = 2ull * hw * pj.pitch;                        // symbols of the channel's compact volume
-
-    const uint32_t blen = job.blk_len[b];
-    const unsigned long long boff = job.blk_off[b];
-    if (blen < 128u || boff + blen > job.len) { if (lane == 0) *job.flags = kSplitBadDirectory; return; }
-    const uint8_t* blk = job.stream + boff;
-    const uint32_t len = (uint32_t)blk[2 * lane] | ((uint32_t)blk[2 * lane + 1] << 8);
-    const uint32_t incl = wave_incl_scan(len, lane);
-    const uint32_t all = __shfl(incl, 63, 64);
-    if (all + 128u != blen) { if (lane == 0) *job.flags = kSplitBadDirectory; return; }
-    const uint8_t* __restrict__ src = blk + 128u + (incl - len);   // [src, src + len) lies inside the block
-
-    uint32_t win = 0u, nwin = 0u, fpos = 0u, pos = 0u;
-    auto take = [&]() -> uint32_t {
-        if (nwin == 0u) {
-            uint32_t w = 0u;
-            if (fpos + 4u <= len) {
-                uint32_t t;
-                __builtin_memcpy(&t, src + fpos, 4);
-                w = __builtin_bswap32(t);
-            } else {
-#pragma unroll
-                for (uint32_t t = 0; t < 4u; ++t) w = (w << 8) | (fpos + t < len ? (uint32_t)src[fpos + t] : 0u);
-            }
-            fpos += 4u;
-            win = w;
-            nwin = 4u;
+    lane_decode<WIDE>(job, b, lane, g.k, (const uint8_t*)c2s_sh, symtab, [&](uint32_t, uint32_t s) {
+        // plane < 2 hw, y < qh and x < qw: the index is plane * pitch + y * qw + x, inside the channel's 2 hw * pitch
+        // symbols (pitch >= qw * qh); the compare with `limit` keeps the store there whatever the carried sum holds
+        const uint32_t u0 = tp - pj.t_lo, u1 = tp - t_hi;
+        if ((u0 < hw || u1 < hw) && y < qh && x < qw) {
+            const unsigned long long at = (unsigned long long)(off + (u0 < hw ? 0ll : high_off));
+            if (at < limit) out[at] = (SymT)s;
         }
-        const uint32_t byte = win >> 24;
-        win <<= 8;
-        --nwin;
-        ++pos;
-        return byte;
-    };
-    bool ok = true;
-    if (k == 0u) {
-        ok = len == 0u;
-    } else {
-        uint32_t xs = take() << 24;
-        xs |= take() << 16;
-        xs |= take() << 8;
-        xs |= take();
-        for (uint32_t i = 0; i < k; ++i) {
-            const uint32_t slot12 = xs & (kProbScale - 1u);
-            uint32_t s = c2s[slot12];
-            const uint32_t fc = symtab[s];
-            xs = (fc & 0xFFFFu) * (xs >> kProbBits) + slot12 - (fc >> 16);
-            if (xs < kRansL) xs = (xs << 8) | take();
-            if (xs < kRansL) xs = (xs << 8) | take();
-            if (WIDE && s == 255u) {
-                s += xs & kSplitWideMaxResidual;
-                xs >>= 12;
-                if (xs < kRansL) xs = (xs << 8) | take();
-                if (xs < kRansL) xs = (xs << 8) | take();
-            }
-            // plane < 2 hw, y < qh and x < qw: the index is plane * pitch + y * qw + x, inside the channel's 2 hw * pitch
-            // symbols (pitch >= qw * qh); the compare with `limit` keeps the store there whatever the carried sum holds
-            const uint32_t u0 = tp - pj.t_lo, u1 = tp - t_hi;
-            if ((u0 < hw || u1 < hw) && y < qh && x < qw) {
-                const unsigned long long at = (unsigned long long)(off + (u0 < hw ? 0ll : high_off));
-                if (at < limit) out[at] = (SymT)s;
-            }
-            x += dx; off += step_off;
-            if (x >= pw) { x -= pw; ++y; off += xwrap_off; }
-            y += dy;
-            if (y >= ph) { y -= ph; ++tp; off += ywrap_off; }
-            tp += dP;
-        }
-        ok = xs == kRansL && pos == len;
-    }
-    if (!ok) *job.flags = kSplitBadLane;
+        x += dx; off += step_off;
+        if (x >= pw) { x -= pw; ++y; off += xwrap_off; }
+        y += dy;
+        if (y >= ph) { y -= ph; ++tp; off += ywrap_off; }
+        tp += dP;
+    });
 }
 
 // ----------------------------------------------------------------------------------
@@ -751,46 +565,39 @@ void launch_split_table(const uint32_t* d_hist, uint16_t* d_freq, uint16_t* d_cu
     if (n_tables > 0) hipLaunchKernelGGL(split_table_kernel, dim3(n_tables), dim3(256), 0, st, d_hist, d_freq, d_cum);
 }
 
-static dim3 split_grid(uint32_t max_blocks, int n_jobs) { return dim3((max_blocks + 3u) / 4u, (unsigned)n_jobs); }
-
-void launch_split_count(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, hipStream_t st) {
-    if (n_jobs > 0 && max_blocks) hipLaunchKernelGGL(split_encode_kernel<false>, split_grid(max_blocks, n_jobs), dim3(256), 0, st, d_jobs);
+// one lane kernel over n_jobs jobs of at most max_blocks blocks: four blocks per workgroup
+template <typename Job>
+static void launch_lanes(void (*narrow)(const Job*), void (*wide_k)(const Job*), bool wide, const Job* d_jobs, int n_jobs,
+                         uint32_t max_blocks, hipStream_t st) {
+    if (n_jobs <= 0 || !max_blocks) return;
+    hipLaunchKernelGGL(wide ? wide_k : narrow, dim3((max_blocks + 3u) / 4u, (unsigned)n_jobs), dim3(256), 0, st, d_jobs);
 }
-void launch_split_write(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, hipStream_t st) {
-    if (n_jobs > 0 && max_blocks) hipLaunchKernelGGL(split_encode_kernel<true>, split_grid(max_blocks, n_jobs), dim3(256), 0, st, d_jobs);
+
+void launch_split_count(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, bool wide, hipStream_t st) {
+    launch_lanes(split_encode_kernel<false>, split_wide_encode_kernel<false>, wide, d_jobs, n_jobs, max_blocks, st);
+}
+void launch_split_write(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, bool wide, hipStream_t st) {
+    launch_lanes(split_encode_kernel<true>, split_wide_encode_kernel<true>, wide, d_jobs, n_jobs, max_blocks, st);
 }
 void launch_split_scan(const SplitJob* d_jobs, int n_jobs, bool from_stream, unsigned long long* d_totals, hipStream_t st) {
     if (n_jobs <= 0) return;
     if (from_stream) hipLaunchKernelGGL(split_scan_kernel<true>, dim3(n_jobs), dim3(256), 0, st, d_jobs, d_totals);
     else hipLaunchKernelGGL(split_scan_kernel<false>, dim3(n_jobs), dim3(256), 0, st, d_jobs, d_totals);
 }
-void launch_split_decode(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, hipStream_t st) {
-    if (n_jobs > 0 && max_blocks) hipLaunchKernelGGL(split_decode_kernel, split_grid(max_blocks, n_jobs), dim3(256), 0, st, d_jobs);
-}
-void launch_split_header_version(const SplitHeaderDesc* d_descs, int n_chunks, uint8_t version, hipStream_t st) {
-    if (n_chunks > 0) hipLaunchKernelGGL(split_version_kernel, dim3((n_chunks + 63) / 64), dim3(64), 0, st, d_descs, n_chunks, (uint32_t)version);
-}
-void launch_split_wide_count(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, hipStream_t st) {
-    if (n_jobs > 0 && max_blocks) hipLaunchKernelGGL(split_wide_encode_kernel<false>, split_grid(max_blocks, n_jobs), dim3(256), 0, st, d_jobs);
-}
-void launch_split_wide_write(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, hipStream_t st) {
-    if (n_jobs > 0 && max_blocks) hipLaunchKernelGGL(split_wide_encode_kernel<true>, split_grid(max_blocks, n_jobs), dim3(256), 0, st, d_jobs);
-}
-void launch_split_wide_decode(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, hipStream_t st) {
-    if (n_jobs > 0 && max_blocks) hipLaunchKernelGGL(split_wide_decode_kernel, split_grid(max_blocks, n_jobs), dim3(256), 0, st, d_jobs);
+void launch_split_decode(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks, bool wide, hipStream_t st) {
+    launch_lanes(split_decode_kernel, split_wide_decode_kernel, wide, d_jobs, n_jobs, max_blocks, st);
 }
 void launch_split_frames_decode(const SplitFramesJob* d_jobs, int n_jobs, uint32_t max_blocks, bool wide, hipStream_t st) {
-    if (n_jobs <= 0 || !max_blocks) return;
-    if (wide) hipLaunchKernelGGL(split_frames_decode_kernel<true>, split_grid(max_blocks, n_jobs), dim3(256), 0, st, d_jobs);
-    else hipLaunchKernelGGL(split_frames_decode_kernel<false>, split_grid(max_blocks, n_jobs), dim3(256), 0, st, d_jobs);
+    launch_lanes(split_frames_decode_kernel<false>, split_frames_decode_kernel<true>, wide, d_jobs, n_jobs, max_blocks, st);
 }
 void launch_split_preview_decode(const SplitPreviewJob* d_jobs, int n_jobs, uint32_t max_planned, bool wide, hipStream_t st) {
-    if (n_jobs <= 0 || !max_planned) return;
-    if (wide) hipLaunchKernelGGL(split_preview_decode_kernel<true>, split_grid(max_planned, n_jobs), dim3(256), 0, st, d_jobs);
-    else hipLaunchKernelGGL(split_preview_decode_kernel<false>, split_grid(max_planned, n_jobs), dim3(256), 0, st, d_jobs);
+    launch_lanes(split_preview_decode_kernel<false>, split_preview_decode_kernel<true>, wide, d_jobs, n_jobs, max_planned, st);
 }
 void launch_split_headers(const SplitHeaderDesc* d_descs, int n_chunks, hipStream_t st) {
     if (n_chunks > 0) hipLaunchKernelGGL(split_header_kernel, dim3(n_chunks), dim3(256), 0, st, d_descs);
+}
+void launch_split_header_version(const SplitHeaderDesc* d_descs, int n_chunks, uint8_t version, hipStream_t st) {
+    if (n_chunks > 0) hipLaunchKernelGGL(split_version_kernel, dim3((n_chunks + 63) / 64), dim3(64), 0, st, d_descs, n_chunks, (uint32_t)version);
 }
 
 }  // namespace alice
