@@ -324,6 +324,10 @@ def load_library() -> C.CDLL:
         "alice_codec_decode_preview": (vp, [_u8p, C.c_uint64, C.c_uint32, C.c_uint32, _u64p]),
         "alice_codec_dev_decode_preview": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp]),
         "alice_codec_test_last_preview_stats": (None, [_u64p]),
+        "alice_codec_rect_window": (C.c_int, [C.c_uint8] + [C.c_uint32] * 6 + [_u32p] * 4),
+        "alice_codec_decode_rect": (vp, [_u8p, C.c_uint64] + [C.c_uint32] * 6 + [_u64p]),
+        "alice_codec_dev_decode_rect": (C.c_int, [vp, C.c_uint64] + [C.c_uint32] * 6 + [vp, C.c_uint64, C.c_uint64, vp]),
+        "alice_codec_test_last_rect_stats": (None, [_u64p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
@@ -2295,6 +2299,49 @@ def _test_last_preview_stats() -> tuple:
     over the three channels) of the calling thread's last preview decode."""
     out = np.zeros(6, np.uint64)
     load_library().alice_codec_test_last_preview_stats(_p(out, _u64p))
+    return tuple(int(v) for v in out)
+
+
+# ---- a spatial rectangle of a frame range of a version 2, 3 or 4 chunk (DESIGN.md section 16) ----
+
+def rect_window(wavelet_type: WaveletType, width: int, height: int, x: int, y: int, w: int, h: int) -> tuple:
+    """(xa, xb, ya, yb): the w x h pixels at (x, y) of a width x height frame depend on the coefficient columns inside
+    [xa, xb) and rows inside [ya, yb) only.  No device needed."""
+    _dims_u32(width, height, x, y, w, h)
+    v = [C.c_uint32(0) for _ in range(4)]
+    _check(load_library().alice_codec_rect_window(int(wavelet_type), width, height, x, y, w, h, *[C.byref(c) for c in v]))
+    return tuple(c.value for c in v)
+
+
+def decode_rect(data, first: int, count: int, x: int, y: int, w: int, h: int) -> np.ndarray:
+    """The RGB bytes (count * h * w * 3, packed) of the w x h rectangle at (x, y) of frames [first, first + count) of a
+    version 2, 3 or 4 container, from the blocks they need: only the header, the block-length tables and those blocks are
+    read and uploaded (data may be an np.memmap).  The end checks cover the blocks that are read."""
+    lib = load_library()
+    buf = _as_u8(data)
+    _dims_u32(first, count, x, y, w, h)
+    n = C.c_uint64(0)
+    ptr = lib.alice_codec_decode_rect(_p(buf, _u8p), buf.size, first, count, x, y, w, h, C.byref(n))
+    if not ptr:
+        _raise_last()
+    return _adopt(ptr, n.value, lib.alice_codec_data_free64)
+
+
+def rect_decode_device(d_alc_ptr: int, length: int, first: int, count: int, x: int, y: int, w: int, h: int, d_rgb_out_ptr: int,
+                       row_pitch: int = 0, frame_pitch: int = 0, stream: int = 0) -> None:
+    """decode_rect of a device-resident container of `length` bytes to d_rgb_out_ptr: packed when both pitches are 0, else
+    row r of frame k at k * frame_pitch + r * row_pitch (bytes), so that the rectangle can be pasted into full-size frames.
+    Only the 3 w bytes of each of the h rows of each frame are written."""
+    _dims_u32(first, count, x, y, w, h)
+    _check(load_library().alice_codec_dev_decode_rect(d_alc_ptr, length, first, count, x, y, w, h, d_rgb_out_ptr, row_pitch, frame_pitch,
+                                                      stream or None))
+
+
+def _test_last_rect_stats() -> tuple:
+    """(ta, tb, xa, xb, ya, yb, blocks decoded over the three channels, payload bytes the host call uploaded, frames
+    written, symbols stored over the three channels) of the calling thread's last rectangle decode."""
+    out = np.zeros(10, np.uint64)
+    load_library().alice_codec_test_last_rect_stats(_p(out, _u64p))
     return tuple(int(v) for v in out)
 
 

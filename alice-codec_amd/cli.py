@@ -18,6 +18,8 @@ is version 1.
 `decode --frames A:B` (A alone: one frame) writes frames [A, B) of a version 2, 3 or 4 file from the blocks they need
 (DESIGN.md section 14): the file is mapped, so only the header, the block-length tables and those blocks are read;
 version 1 is refused with the library's message.
+`decode --rect X,Y,W,H` (alone: every frame; or with `--frames`) writes the W x H pixels at (X, Y) as packed W x H frames,
+from the blocks they need, through the same mapped file; with `--preview` it is refused.
 Like the reference it treats the whole input file as ONE chunk (src/bin/main.rs:117-122).  `encode-chunks`
 is the extension SURVEY.md section 8f asks for: it cuts a long raw-RGB file into 64-frame chunks
 (DEFAULT_CHUNK_SIZE, src/lib.rs:110) and writes one .alc per chunk."""
@@ -29,7 +31,7 @@ import sys
 import numpy as np
 
 from . import (DEFAULT_CHUNK_SIZE, CodecError, EncodedChunk, FrameDecoder, FrameEncoder, WaveletType, budget_bytes_per_chunk,
-               alc_version, decode_frames, decode_preview, decode_reversible, decode_split, decode_wide, encode_many, encode_reversible, encode_split,
+               alc_version, decode_frames, decode_preview, decode_rect, decode_reversible, decode_split, decode_wide, encode_many, encode_reversible, encode_split,
                encode_split_to_psnr, encode_split_to_size, encode_to_size, encode_wide, encode_wide_to_psnr, reversible_info,
                split_info, wide_info)
 
@@ -291,7 +293,42 @@ def cmd_decode_preview(a) -> None:
     print(f"decoded preview {qw}x{qh} of frames [{first}, {end}) of {width}x{height}x{frames} -> {rgb.size} bytes (raw RGB)", file=sys.stderr)
 
 
+def parse_rect(text: str):
+    """'X,Y,W,H' -> (X, Y, W, H); ValueError otherwise."""
+    parts = text.split(",")
+    try:
+        if len(parts) != 4 or not all(p.strip().isdigit() for p in parts):
+            raise ValueError
+        x, y, w, h = (int(p) for p in parts)
+        if w < 1 or h < 1 or max(x, y, w, h) > 0xFFFFFFFF:
+            raise ValueError
+    except ValueError:
+        raise ValueError(f"--rect wants X,Y,W,H with W >= 1 and H >= 1, got '{text}'") from None
+    return x, y, w, h
+
+
+def cmd_decode_rect(a) -> None:
+    """--rect alone: the rectangle of every frame; with --frames A[:B]: of that range.  Packed W x H frames."""
+    x, y, w, h = parse_rect(a.rect)
+    data = np.memmap(a.input, dtype=np.uint8, mode="r")
+    if a.format != "auto" and data.size > 4 and int(data[4]) != FORMAT_VERSION[a.format]:
+        raise ValueError(f"--format {a.format} names version {FORMAT_VERSION[a.format]}, the file's version byte is {int(data[4])}")
+    if data.size < 18:
+        raise ValueError(f"{a.input}: too short for a container header")
+    width, height, frames = (int(v) for v in np.frombuffer(bytes(data[6:18]), "<u4"))
+    first, end = parse_frames(a.frames) if a.frames is not None else (0, frames)
+    rgb = decode_rect(data, first, end - first, x, y, w, h)
+    rgb.tofile(a.output)
+    print(f"decoded rectangle {w}x{h} at ({x}, {y}) of frames [{first}, {end}) of {width}x{height}x{frames} -> {rgb.size} bytes (raw RGB)",
+          file=sys.stderr)
+
+
 def cmd_decode(a) -> None:
+    if a.rect is not None:
+        if a.preview:
+            raise ValueError("--rect and --preview cannot be combined: there is no rectangle of a preview (decode the preview and crop it)")
+        cmd_decode_rect(a)
+        return
     if a.preview:
         cmd_decode_preview(a)
         return
@@ -394,6 +431,9 @@ def main(argv=None) -> int:
     d.add_argument("--preview", action="store_true",
                    help="write half-resolution frames (ceil(W/2) x ceil(H/2)) decoded from the low band alone: all frames, or those of "
                         "--frames; versions 2, 3 and 4")
+    d.add_argument("--rect", default=None, metavar="X,Y,W,H",
+                   help="write the W x H pixels at (X, Y) only, as packed W x H frames decoded from the blocks they need: all frames, or "
+                        "those of --frames; versions 2, 3 and 4; not with --preview")
     i = sub.add_parser("info")
     i.add_argument("input")
     for x in (d, i):

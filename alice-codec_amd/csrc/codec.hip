@@ -5147,3 +5147,222 @@ void alice_codec_test_last_preview_stats(uint64_t out[6]) {
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// PART 10: a spatial rectangle of a frame range of a version 2, 3 or 4 chunk (kernels:
+// split_rect_decode_kernel of split.hip, rgb_rect_paste_kernel of generic.hip)
+//
+// The spatial transform is one lifting level per axis too, and every axis of a channel's [t'][y][x] symbol volume is
+// deinterleaved into [low | high], so PART 8's window rule holds on x and on y as it holds on t: the pixels of
+// [t0, t1) x [y0, y1) x [x0, x1) depend on the coefficients whose coordinate lies, on every axis, in the low or the high run
+// of that axis's window.  Cut out in that order they are the symbol volume of a virtual chunk of (xb - xa) x (yb - ya) x
+// (tb - ta), all even, whose inverse equals the full chunk's at the rectangle shifted by (xa, ya, ta).  The lane decode runs
+// over the blocks that hold a kept symbol, the unchanged window inverse over the virtual chunk, and a copy kernel drops the
+// halo.  The end checks cover the blocks that are read.
+// ------------------------------------------------------------------------------------------
+
+namespace {
+
+// PART 8's rule for an axis of padded length pn and the real positions [c0, c1), c0 < c1 <= pn
+void axis_window(uint64_t ns, uint64_t pn, uint64_t c0, uint64_t c1, uint32_t* a, uint32_t* b) {
+    *a = c0 > ns ? (uint32_t)((c0 - ns) & ~1ull) : 0u;
+    *b = (uint32_t)std::min<uint64_t>(pn, (c1 + ns + 1) & ~1ull);
+}
+
+struct RectPlan {
+    uint32_t ta = 0, tb = 0, xa = 0, xb = 0, ya = 0, yb = 0;
+    bool whole = false;                       // the rectangle is the frame: no halo to drop
+    uint64_t stored = 0;                      // symbols of a channel's virtual chunk
+    std::vector<uint32_t> blocks;             // ascending, no duplicates; the three channels are alike
+};
+
+// the blocks that intersect an x run of a kept row of a planned plane: planes, rows and runs in ascending position order
+RectPlan rect_plan(const SplitHeader& h, const ChunkDims& d, uint32_t first, uint32_t count, uint32_t x, uint32_t y, uint32_t w, uint32_t rh) {
+    RectPlan p;
+    const uint64_t ns = frames_halo(h.wavelet);
+    frames_window(h.wavelet, h.frames, first, count, &p.ta, &p.tb);
+    axis_window(ns, d.pw, x, (uint64_t)x + w, &p.xa, &p.xb);
+    axis_window(ns, d.ph, y, (uint64_t)y + rh, &p.ya, &p.yb);
+    p.whole = x == 0 && y == 0 && w == h.width && rh == h.height;
+    p.stored = (uint64_t)(p.tb - p.ta) * (p.yb - p.ya) * (p.xb - p.xa);
+    const uint64_t B = 64ull * h.lane_symbols, hx = d.pw / 2, hy = d.ph / 2, ht = d.pf / 2;
+    const bool merged = p.xa == 0 && p.xb == d.pw;
+    if (merged && p.ya == 0 && p.yb == d.ph) {   // whole planes: PART 8's plan
+        p.blocks = frames_plan(h, d, first, count).block_list();
+        return p;
+    }
+    // `covered`: where the last listed block ends.  A run that ends at or before it adds nothing, which is what most rows
+    // find (a block holds many rows), so the divisions are paid once per new block and not once per row.
+    uint64_t covered = 0;
+    auto add = [&](uint64_t lo, uint64_t hi) {
+        if (hi <= covered) return;
+        for (uint64_t blk = std::max(lo, covered) / B; blk <= (hi - 1) / B; ++blk) p.blocks.push_back((uint32_t)blk);
+        covered = ((uint64_t)p.blocks.back() + 1) * B;
+    };
+    const uint64_t rows = (p.yb - p.ya) / 2;
+    for (int bt = 0; bt < 2; ++bt)
+        for (uint64_t t = bt * ht + p.ta / 2; t < bt * ht + p.tb / 2; ++t)
+            for (int by = 0; by < 2; ++by) {
+                const uint64_t r0 = by * hy + p.ya / 2;
+                if (merged) {   // whole rows: the kept rows of this half of the plane are one run
+                    add((t * d.ph + r0) * d.pw, (t * d.ph + r0 + rows) * d.pw);
+                    continue;
+                }
+                for (uint64_t r = r0; r < r0 + rows; ++r) {
+                    const uint64_t row = (t * d.ph + r) * d.pw;
+                    add(row + p.xa / 2, row + p.xb / 2);
+                    add(row + hx + p.xa / 2, row + hx + p.xb / 2);
+                }
+            }
+    return p;
+}
+
+// after frames_validate: the rectangle against the frame
+int rect_validate(const SplitHeader& h, uint32_t x, uint32_t y, uint32_t w, uint32_t rh) {
+    if (w < 1 || rh < 1 || (uint64_t)x + w > h.width || (uint64_t)y + rh > h.height)
+        return fail(kInvalidDimensions, "rectangle " + std::to_string(w) + "x" + std::to_string(rh) + " at (" + std::to_string(x) + ", " +
+                                            std::to_string(y) + ") does not lie inside the " + std::to_string(h.width) + "x" +
+                                            std::to_string(h.height) + " frame");
+    return kOk;
+}
+
+thread_local uint64_t tl_rect_stats[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // alice_codec_test_last_rect_stats
+
+// The w x rh pixels at (x, y) of frames [first, first + count) of the container at d_alc (device, h and the rectangle
+// validated) to `out` (device; only the 3 w bytes of each of the rh rows of each frame are written).  Of the payloads only
+// the block-length tables and the planned blocks are read.  Returns after the stream has drained.
+int rect_decode_device(const SplitHeader& h, const ChunkDims& d, const RectPlan& p, const uint8_t* d_alc, uint32_t first, uint32_t count,
+                       uint32_t x, uint32_t y, uint32_t w, uint32_t rh, const RgbLayout& out, hipStream_t st, uint64_t uploaded) {
+    const SplitFormat fmt = h.fmt;
+    const bool wide = is_wide(fmt);
+    const size_t sb = wide ? 2 : 1;
+    // the virtual chunk: even on every axis unless it is the whole frame, whose pad column and row are the chunk's own
+    const uint32_t vw = p.whole ? h.width : p.xb - p.xa, vh = p.whole ? h.height : p.yb - p.ya;
+    const ChunkDims dv = make_dims(vw, vh, p.tb - p.ta);
+    const ChunkDims dx = make_dims(vw, vh, count);
+    DecodeWork dw;
+    dw.d = dv; dw.n_chunks = 1;
+    TRY(dw.sym.alloc(3 * dv.padded * sb));
+    // When both spatial windows are the whole axis the kept symbols are whole coefficient planes, in plane order: PART 8's
+    // symbol ranges and its lane kernel (whose store is two compares), with the same blocks and the same compact volume.
+    const bool planes = p.xa == 0 && p.xb == d.pw && p.ya == 0 && p.yb == d.ph;
+    const FramesPlan fp = frames_plan(h, d, first, count);
+    DevBuf d_rj, d_tmp;                      // (declared before w: w's destructor drains the stream that reads them)
+    // one upload: the three jobs, then (rectangle jobs) the block list they share
+    const size_t jobs_bytes = 3 * (planes ? sizeof(SplitFramesJob) : sizeof(SplitRectJob));
+    const size_t list_bytes = planes ? 0 : p.blocks.size() * sizeof(uint32_t);
+    std::vector<uint8_t> up(jobs_bytes + list_bytes);
+    TRY(d_rj.alloc(up.size()));
+    if (!p.whole) TRY(d_tmp.alloc(3 * dx.n_pixels));
+    SplitWork sw;
+    TRY(split_work_alloc(sw, 3, d.padded, h.lane_symbols, false, fmt));
+    split_chunk_jobs(sw, 0, h, d_alc, dw.sym.as<uint8_t>(), dv.padded * sb);
+    for (int c = 0; c < 3; ++c) {
+        if (planes) {
+            SplitFramesJob j{};
+            j.j = sw.h[(size_t)c];
+            for (int r = 0; r < 2; ++r) {
+                j.blk_first[r] = fp.blk_first[r]; j.blk_count[r] = fp.blk_count[r];
+                j.sym_lo[r] = fp.sym_lo[r]; j.sym_hi[r] = fp.sym_hi[r];
+            }
+            memcpy(up.data() + (size_t)c * sizeof(j), &j, sizeof(j));
+        } else {
+            SplitRectJob j{};
+            j.j = sw.h[(size_t)c];
+            j.blocks = (const uint32_t*)(d_rj.as<uint8_t>() + jobs_bytes); j.n_planned = (uint32_t)p.blocks.size();
+            j.pw = (uint32_t)d.pw; j.ph = (uint32_t)d.ph;
+            j.lo[0] = p.xa / 2; j.hl[0] = (p.xb - p.xa) / 2; j.half[0] = (uint32_t)(d.pw / 2);
+            j.lo[1] = p.ya / 2; j.hl[1] = (p.yb - p.ya) / 2; j.half[1] = (uint32_t)(d.ph / 2);
+            j.lo[2] = p.ta / 2; j.hl[2] = (p.tb - p.ta) / 2; j.half[2] = (uint32_t)(d.pf / 2);
+            memcpy(up.data() + (size_t)c * sizeof(j), &j, sizeof(j));
+        }
+    }
+    if (transform_tiles_eligible(dv))
+        TRY(dw.scratch_own.alloc(inverse_scratch_bytes(dx, inverse_bounds(h.wavelet, h.step, wide ? kWideMaxQ : kByteMaxQ).mid16)));
+    // the jobs and the list go up first, while nothing of this call is queued yet
+    memcpy(up.data() + jobs_bytes, p.blocks.data(), list_bytes);
+    sw.st = st; sw.armed = true;
+    HIP_TRY(hipMemcpyAsync(d_rj.p, up.data(), up.size(), hipMemcpyHostToDevice, st));
+    const std::function<int()> lane_decode = [&]() -> int {
+        if (planes) launch_split_frames_decode(d_rj.as<SplitFramesJob>(), 3, fp.blocks(), wide, st);
+        else launch_split_rect_decode(d_rj.as<SplitRectJob>(), 3, (uint32_t)p.blocks.size(), wide, st);
+        return kOk;
+    };
+    TRY(split_decode_launch(sw, &h.freq[0][0], st, &lane_decode));
+    // as in PART 8: the verdict of the end checks comes before anything is queued that writes `out`
+    TRY(split_decode_verdict(sw, st));
+    const uint32_t lo = first - p.ta;
+    if (p.whole) {
+        TRY(inverse_window(dw.sym.as<uint8_t>(), dv, lo, lo + count, h.wavelet, h.step, dw.scratch_own.p, dw, out, st, fmt));
+    } else {
+        const RgbLayout tmp = packed_rgb(d_tmp.p, dx);
+        TRY(inverse_window(dw.sym.as<uint8_t>(), dv, lo, lo + count, h.wavelet, h.step, dw.scratch_own.p, dw, tmp, st, fmt));
+        launch_rgb_rect_paste(tmp, x - p.xa, y - p.ya, w, rh, count, out, st);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    const uint64_t stats[10] = {p.ta, p.tb, p.xa, p.xb, p.ya, p.yb, 3ull * p.blocks.size(), uploaded, count, 3ull * p.stored};
+    memcpy(tl_rect_stats, stats, sizeof(stats));
+    return kOk;
+}
+
+}  // namespace
+
+extern "C" {
+
+int alice_codec_rect_window(uint8_t wavelet_type, uint32_t width, uint32_t height, uint32_t x, uint32_t y, uint32_t w, uint32_t h,
+                            uint32_t* xa, uint32_t* xb, uint32_t* ya, uint32_t* yb) {
+    clear_error();
+    if (!xa || !xb || !ya || !yb) return fail(kNullArgument, "null argument");
+    if (wavelet_type > 2) return fail(kInvalidBitstream, "unknown wavelet type");
+    if (width == 0xFFFFFFFFu || height == 0xFFFFFFFFu) return fail(kDimensionOverflow, "the padded frame size does not fit 32 bits");
+    SplitHeader hd;
+    hd.width = width; hd.height = height;
+    TRY(rect_validate(hd, x, y, w, h));
+    const uint64_t ns = frames_halo(wavelet_type);
+    axis_window(ns, (uint64_t)width + (width & 1u), x, (uint64_t)x + w, xa, xb);
+    axis_window(ns, (uint64_t)height + (height & 1u), y, (uint64_t)y + h, ya, yb);
+    return kOk;
+}
+
+int alice_codec_dev_decode_rect(const void* d_alc, uint64_t len, uint32_t first, uint32_t count, uint32_t x, uint32_t y, uint32_t w,
+                                uint32_t h, void* d_rgb_out, uint64_t row_pitch, uint64_t frame_pitch, void* hip_stream) {
+    return partial_decode_dev(d_alc, len, first, count, d_rgb_out, hip_stream, [&](const SplitHeader& hd, const ChunkDims& d, hipStream_t st) {
+        TRY(rect_validate(hd, x, y, w, h));
+        RgbLayout out{(uint8_t*)d_rgb_out, 3ull * w, 3ull * w * h};
+        if (row_pitch || frame_pitch) {
+            const uint64_t rp = row_pitch ? row_pitch : out.row_pitch;
+            const uint64_t fp = frame_pitch ? frame_pitch : rp * h;
+            if (rp < 3ull * w || (unsigned __int128)fp < (unsigned __int128)rp * h)
+                return fail(kInvalidDimensions, "pitches " + std::to_string(row_pitch) + " and " + std::to_string(frame_pitch) +
+                                                    " are too small for rows of " + std::to_string(3ull * w) + " bytes and frames of " +
+                                                    std::to_string(h) + " rows");
+            out.row_pitch = rp; out.frame_pitch = fp;
+        }
+        return rect_decode_device(hd, d, rect_plan(hd, d, first, count, x, y, w, h), (const uint8_t*)d_alc, first, count, x, y, w, h, out,
+                                  st, 0);
+    });
+}
+
+uint8_t* alice_codec_decode_rect(const uint8_t* data, uint64_t len, uint32_t first, uint32_t count, uint32_t x, uint32_t y, uint32_t w,
+                                 uint32_t h, uint64_t* out_len) {
+    clear_error();
+    if (!data || !out_len) { fail(kNullArgument, "null argument"); return nullptr; }
+    SplitHeader hd;
+    ChunkDims d{};
+    if (frames_validate(data, len, first, count, hd, d) != kOk || rect_validate(hd, x, y, w, h) != kOk) return nullptr;
+    const RectPlan p = rect_plan(hd, d, first, count, x, y, w, h);
+    uint8_t* out = nullptr;
+    partial_decode_host(data, len, hd, p.blocks, 3ull * w * h * count, &out, out_len,
+                        [&](const uint8_t* d_alc, void* d_rgb, hipStream_t st, uint64_t uploaded) {
+                            return rect_decode_device(hd, d, p, d_alc, first, count, x, y, w, h,
+                                                      RgbLayout{(uint8_t*)d_rgb, 3ull * w, 3ull * w * h}, st, uploaded);
+                        });
+    return out;
+}
+
+void alice_codec_test_last_rect_stats(uint64_t out[10]) {
+    if (out) memcpy(out, tl_rect_stats, sizeof(tl_rect_stats));
+}
+
+}  // extern "C"

@@ -241,6 +241,35 @@ void launch_ycocg_to_rgb(const int16_t* y, const int16_t* co, const int16_t* cg,
                        cg, rgb, d.w, d.h, rows);
 }
 
+// Rectangle paste: row_bytes bytes of each of `rows` rows (h per frame) from src to dst, both with
+// their base at the rectangle's first byte.  A workgroup takes whole rows, its threads the V-sized pieces of a row and one
+// of them the row's last row_bytes % sizeof(V) bytes; the launcher picks the widest V that every row start of both sides
+// is aligned to.  All offsets are 64-bit.
+template <typename V>
+__global__ __launch_bounds__(256) void rgb_rect_paste_kernel(RgbLayout src, RgbLayout dst, unsigned long long row_bytes, uint32_t h,
+                                                             unsigned long long rows) {
+    const unsigned long long nv = row_bytes / sizeof(V);
+    for (unsigned long long row = blockIdx.x; row < rows; row += gridDim.x) {
+        const unsigned long long t = row / h, y = row % h;
+        const uint8_t* __restrict__ s = src.base + t * src.frame_pitch + y * src.row_pitch;
+        uint8_t* __restrict__ d = dst.base + t * dst.frame_pitch + y * dst.row_pitch;
+        for (unsigned long long i = threadIdx.x; i < nv; i += 256) ((V*)d)[i] = ((const V*)s)[i];
+        for (unsigned long long i = nv * sizeof(V) + threadIdx.x; i < row_bytes; i += 256) d[i] = s[i];
+    }
+}
+
+void launch_rgb_rect_paste(const RgbLayout& src, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t n_frames, const RgbLayout& dst,
+                           hipStream_t st) {
+    const unsigned long long rows = (unsigned long long)h * n_frames, row_bytes = 3ull * w;
+    if (!rows || !w) return;
+    const RgbLayout s{src.base + y * src.row_pitch + 3ull * x, src.row_pitch, src.frame_pitch};
+    const uint64_t bits = (uintptr_t)s.base | (uintptr_t)dst.base | s.row_pitch | s.frame_pitch | dst.row_pitch | dst.frame_pitch;
+    const dim3 grid((unsigned)std::min<unsigned long long>(rows, std::min(g_grid_cap.load(std::memory_order_relaxed), 65536u)));
+    if (bits % 16 == 0 && row_bytes >= 16) hipLaunchKernelGGL(rgb_rect_paste_kernel<uint4>, grid, dim3(256), 0, st, s, dst, row_bytes, h, rows);
+    else if (bits % 4 == 0 && row_bytes >= 4) hipLaunchKernelGGL(rgb_rect_paste_kernel<uint32_t>, grid, dim3(256), 0, st, s, dst, row_bytes, h, rows);
+    else hipLaunchKernelGGL(rgb_rect_paste_kernel<uint8_t>, grid, dim3(256), 0, st, s, dst, row_bytes, h, rows);
+}
+
 // ---- pad / strip (src/pipeline.rs:77-114, 603-611) ---------------------------------------
 
 __global__ __launch_bounds__(256) void pad_channel_kernel(const int16_t* __restrict__ ch, ChunkDims d, int32_t* __restrict__ out) {

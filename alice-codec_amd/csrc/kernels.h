@@ -216,6 +216,10 @@ void launch_ycocg_to_rgb(const int16_t* y, const int16_t* co, const int16_t* cg,
 // the same for the w x h x f pixels of a chunk at any layout (planes packed [f][h][w]; a packed layout takes the calls above)
 void launch_rgb_to_ycocg(const RgbLayout& rgb, const ChunkDims& d, int16_t* y, int16_t* co, int16_t* cg, hipStream_t st);
 void launch_ycocg_to_rgb(const int16_t* y, const int16_t* co, const int16_t* cg, const ChunkDims& d, const RgbLayout& rgb, hipStream_t st);
+// Rectangle paste: the w x h pixels at (x, y) of each of n_frames frames of `src` go to pixels
+// (0, 0) .. of the frames of `dst`; nothing else of dst is written and nothing else of src is read.  Any alignment.
+void launch_rgb_rect_paste(const RgbLayout& src, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t n_frames, const RgbLayout& dst,
+                           hipStream_t st);
 void launch_pad_channel(const int16_t* ch, const ChunkDims& d, int32_t* out, hipStream_t st);
 void launch_strip_channel(const int32_t* in, const ChunkDims& d, int16_t* ch, hipStream_t st);
 void launch_quantize(const int32_t* in, int32_t* out, uint64_t n, int32_t step, int32_t dead_zone, hipStream_t st);
@@ -348,6 +352,18 @@ struct SplitPreviewJob {
     uint32_t t_lo, half, hw;
     unsigned long long pitch;
 };
+// Spatial rectangle of a frame range: the n_planned blocks blocks[0 .. n_planned) of channel `j`
+// (ascending, no duplicates) are decoded.  Axis k (0 = x of pw, 1 = y of ph, 2 = t' of 2 * half[2]) keeps the coordinates
+// [lo[k], lo[k] + hl[k]) (low run, place c - lo[k] of the virtual chunk) and [half[k] + lo[k], half[k] + lo[k] + hl[k])
+// (high run, place hl[k] + ...).  A symbol at channel position (t' * ph + y) * pw + x is stored only when all three
+// coordinates are kept: at j.sym[(vt * 2 hl[1] + vy) * 2 hl[0] + vx], the [2 hl[2]][2 hl[1]][2 hl[0]] volume of the virtual chunk.
+struct SplitRectJob {
+    SplitJob j;
+    const uint32_t* blocks;
+    uint32_t n_planned;
+    uint32_t pw, ph;
+    uint32_t lo[3], hl[3], half[3];
+};
 struct SplitHeaderDesc {
     uint8_t* out;
     uint32_t width, height, frames, lane_symbols, num_symbols, n_blocks;
@@ -372,6 +388,8 @@ void launch_split_headers(const SplitHeaderDesc* d_descs, int n_chunks, hipStrea
 void launch_split_frames_decode(const SplitFramesJob* d_jobs, int n_jobs, uint32_t max_blocks, bool wide, hipStream_t st);
 // after scan(from_stream = true) over the same channels; max_planned: the largest n_planned among the jobs
 void launch_split_preview_decode(const SplitPreviewJob* d_jobs, int n_jobs, uint32_t max_planned, bool wide, hipStream_t st);
+// after scan(from_stream = true) over the same channels; max_planned: the largest n_planned among the jobs
+void launch_split_rect_decode(const SplitRectJob* d_jobs, int n_jobs, uint32_t max_planned, bool wide, hipStream_t st);
 // overwrites the version byte of the headers launch_split_headers wrote (same stream, after it)
 void launch_split_header_version(const SplitHeaderDesc* d_descs, int n_chunks, uint8_t version, hipStream_t st);
 

@@ -1,4 +1,4 @@
-// Split-stream entropy stage (.alc v2 to v4; DESIGN.md sections 10, 11, 14, 15) for gfx950.
+// Split-stream entropy stage (.alc v2 to v4; DESIGN.md sections 10, 11, 14, 15, 16) for gfx950.
 //
 // A channel's symbols are cut into blocks of 64 * L consecutive symbols; inside a block lane j owns symbols j, j + 64,
 // j + 128, ... and codes them as an independent rANS chain with the reference coder's parameters (32-bit state, lower
@@ -17,6 +17,7 @@
 //   split_decode_kernel / split_wide_decode_kernel   every block; symbol i at the lane's own position
 //   split_frames_decode_kernel<WIDE>    the blocks a frame range needs, stored as a compact volume
 //   split_preview_decode_kernel<WIDE>   the blocks a half-resolution preview needs: low-low quadrants only
+//   split_rect_decode_kernel<WIDE>      the blocks a spatial rectangle of a frame range needs: the kept runs of three axes
 //   split_header_kernel / split_version_kernel   the 1630-byte container header of whole chunks
 // The output is sized by counting first and writing second: the chain arithmetic runs twice, but nothing is staged in
 // worst-case slots (2 bytes per symbol) and no compaction pass moves the payload again.
@@ -524,6 +525,60 @@ __global__ __launch_bounds__(256) void split_preview_decode_kernel(const SplitPr
 }
 
 // ----------------------------------------------------------------------------------
+// Lane decode for a spatial rectangle of a frame range: the blocks a SplitRectJob lists, chosen as
+// the preview kernel chooses its own (slot -> block through the list).  Every chain runs to its end check; a symbol is
+// stored only when each of (x, y, t') lies in the low or the high run of its axis, relocated into the compact volume of the
+// virtual chunk at job.j.sym.  (x, y, t') are carried as in split_preview_decode_kernel: the 64-bit divisions happen once
+// per lane, the loop has three adds and at most one wrap per axis, also for pw = 2 and P < 64.  The destination index is
+// two multiplies of values that do not depend on the chain's state, so the serial dependency stays lane_decode's own.
+// ----------------------------------------------------------------------------------
+template <bool WIDE>
+__global__ __launch_bounds__(256) void split_rect_decode_kernel(const SplitRectJob* __restrict__ jobs) {
+    using SymT = SplitSym<WIDE>;
+    __shared__ uint32_t c2s_sh[kProbScale / 4];
+    __shared__ uint32_t symtab[256];
+    const SplitRectJob rj = jobs[blockIdx.y];
+    const SplitJob& job = rj.j;
+    load_decode_tables(job.table, c2s_sh, symtab);
+    const int lane = threadIdx.x & 63;
+    const unsigned long long slot = (unsigned long long)blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (slot >= rj.n_planned) return;
+    const unsigned long long b = rj.blocks[slot];
+    if (b >= job.n_blocks || !rj.pw || !rj.ph) return;   // (the host plans inside the channel; the bounds of lane_decode do not rest on it)
+    const LaneGeometry g(job, b, lane);
+
+    // where the lane's first symbol lies, and what 64 positions further means
+    const uint32_t pw = rj.pw, ph = rj.ph;
+    const unsigned long long P = (unsigned long long)pw * ph;
+    const unsigned long long p0 = g.base + (unsigned)lane;
+    const unsigned long long rem0 = p0 % P, step_rem = 64ull % P;
+    uint32_t tp = (uint32_t)(p0 / P), y = (uint32_t)(rem0 / pw), x = (uint32_t)(rem0 % pw);
+    const uint32_t dP = (uint32_t)(64ull / P), dy = (uint32_t)(step_rem / pw), dx = (uint32_t)(step_rem % pw);   // dy, dx < 64
+    const uint32_t x_lo = rj.lo[0], y_lo = rj.lo[1], t_lo = rj.lo[2];
+    const uint32_t x_hi = rj.half[0] + x_lo, y_hi = rj.half[1] + y_lo, t_hi = rj.half[2] + t_lo;
+    const uint32_t hx = rj.hl[0], hy = rj.hl[1], ht = rj.hl[2];
+    const unsigned long long vw = 2ull * hx, vh = 2ull * hy;
+    const unsigned long long limit = 2ull * ht * vh * vw;    // symbols of the channel's compact volume
+    SymT* __restrict__ out = (SymT*)job.sym;
+    lane_decode<WIDE>(job, b, lane, g.k, (const uint8_t*)c2s_sh, symtab, [&](uint32_t, uint32_t s) {
+        // a kept coordinate c of an axis has c - lo < hl (place c - lo) or c - hi < hl (place hl + c - hi): vx < vw, vy < vh
+        // and vt < 2 ht, so the index lies inside the channel's volume; the compare with `limit` keeps the store there
+        // whatever the carried coordinates hold
+        const uint32_t x0 = x - x_lo, x1 = x - x_hi, y0 = y - y_lo, y1 = y - y_hi, t0 = tp - t_lo, t1 = tp - t_hi;
+        if ((x0 < hx || x1 < hx) && (y0 < hy || y1 < hy) && (t0 < ht || t1 < ht)) {
+            const uint32_t vx = x0 < hx ? x0 : hx + x1, vy = y0 < hy ? y0 : hy + y1, vt = t0 < ht ? t0 : ht + t1;
+            const unsigned long long at = (vt * vh + vy) * vw + vx;
+            if (at < limit) out[at] = (SymT)s;
+        }
+        x += dx;
+        if (x >= pw) { x -= pw; ++y; }
+        y += dy;
+        if (y >= ph) { y -= ph; ++tp; }
+        tp += dP;
+    });
+}
+
+// ----------------------------------------------------------------------------------
 // Container header of whole chunks, one workgroup per chunk.
 // ----------------------------------------------------------------------------------
 __device__ __forceinline__ void put_le(uint8_t* p, unsigned long long v, int bytes) {
@@ -592,6 +647,9 @@ void launch_split_frames_decode(const SplitFramesJob* d_jobs, int n_jobs, uint32
 }
 void launch_split_preview_decode(const SplitPreviewJob* d_jobs, int n_jobs, uint32_t max_planned, bool wide, hipStream_t st) {
     launch_lanes(split_preview_decode_kernel<false>, split_preview_decode_kernel<true>, wide, d_jobs, n_jobs, max_planned, st);
+}
+void launch_split_rect_decode(const SplitRectJob* d_jobs, int n_jobs, uint32_t max_planned, bool wide, hipStream_t st) {
+    launch_lanes(split_rect_decode_kernel<false>, split_rect_decode_kernel<true>, wide, d_jobs, n_jobs, max_planned, st);
 }
 void launch_split_headers(const SplitHeaderDesc* d_descs, int n_chunks, hipStream_t st) {
     if (n_chunks > 0) hipLaunchKernelGGL(split_header_kernel, dim3(n_chunks), dim3(256), 0, st, d_descs);

@@ -1307,3 +1307,50 @@ pub unsafe fn preview_decode_device(d_alc: *const std::ffi::c_void, length: u64,
     -> Result<(), CodecError> {
     check(alice_codec_dev_decode_preview(d_alc, length, first, count, d_rgb_out, hip_stream), 0, 0)
 }
+
+// ---- a spatial rectangle of a frame range of a version 2, 3 or 4 chunk ----
+
+extern "C" {
+    fn alice_codec_rect_window(wavelet_type: u8, width: u32, height: u32, x: u32, y: u32, w: u32, h: u32, xa: *mut u32,
+                               xb: *mut u32, ya: *mut u32, yb: *mut u32) -> c_int;
+    fn alice_codec_decode_rect(data: *const u8, len: u64, first: u32, count: u32, x: u32, y: u32, w: u32, h: u32,
+                               out_len: *mut u64) -> *mut u8;
+    fn alice_codec_dev_decode_rect(d_alc: *const std::ffi::c_void, len: u64, first: u32, count: u32, x: u32, y: u32, w: u32,
+                                   h: u32, d_rgb_out: *mut std::ffi::c_void, row_pitch: u64, frame_pitch: u64,
+                                   hip_stream: *mut std::ffi::c_void) -> c_int;
+}
+
+/// The `w x h` pixels at `(x, y)` of a frame.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct Rect { pub x: u32, pub y: u32, pub w: u32, pub h: u32 }
+
+/// `(xa, xb, ya, yb)`: the rectangle's pixels depend on the coefficient columns inside `[xa, xb)` and rows inside
+/// `[ya, yb)` only.  No device needed.
+pub fn rect_window(wavelet_type: WaveletType, width: u32, height: u32, r: Rect) -> Result<(u32, u32, u32, u32), CodecError> {
+    let (mut xa, mut xb, mut ya, mut yb) = (0u32, 0u32, 0u32, 0u32);
+    let rc = unsafe { alice_codec_rect_window(wavelet_type as u8, width, height, r.x, r.y, r.w, r.h, &mut xa, &mut xb, &mut ya, &mut yb) };
+    check(rc, 0, 0).map(|_| (xa, xb, ya, yb))
+}
+
+/// The RGB bytes (`count * h * w * 3`, packed) of the rectangle of frames `[first, first + count)` of a version 2, 3 or 4
+/// container, from the blocks they need: only the header, the block-length tables and those blocks are read and uploaded.
+/// The end checks cover the blocks that are read; version 1 is `InvalidBitstream`.
+pub fn decode_rect(data: &[u8], first: u32, count: u32, r: Rect) -> Result<Vec<u8>, CodecError> {
+    let mut n = 0u64;
+    unsafe {
+        let p = alice_codec_decode_rect(data.as_ptr(), data.len() as u64, first, count, r.x, r.y, r.w, r.h, &mut n);
+        if p.is_null() { Err(last_error(0, data.len(), 0, 0, 0)) } else { Ok(take(p, n)) }
+    }
+}
+
+/// `decode_rect` of a device-resident container of `length` bytes to `d_rgb_out`: packed when both pitches are 0, else row
+/// `r` of frame `k` at `k * frame_pitch + r * row_pitch` bytes, so that the rectangle can be pasted into full-size frames.
+///
+/// # Safety
+/// As `split_decode_device`: `d_alc` holds `length` bytes, and every byte `d_rgb_out + k * frame_pitch + r * row_pitch +
+/// [0, 3 w)` for `k < count`, `r < h` is writable on the current device.
+pub unsafe fn rect_decode_device(d_alc: *const std::ffi::c_void, length: u64, first: u32, count: u32, r: Rect,
+                                 d_rgb_out: *mut std::ffi::c_void, row_pitch: u64, frame_pitch: u64,
+                                 hip_stream: *mut std::ffi::c_void) -> Result<(), CodecError> {
+    check(alice_codec_dev_decode_rect(d_alc, length, first, count, r.x, r.y, r.w, r.h, d_rgb_out, row_pitch, frame_pitch, hip_stream), 0, 0)
+}

@@ -728,6 +728,41 @@ uint8_t *alice_codec_decode_preview(const uint8_t *data, uint64_t len, uint32_t 
 int alice_codec_dev_decode_preview(const void *d_alc, uint64_t len, uint32_t first, uint32_t count, void *d_rgb_out,
                                    void *hip_stream);
 
+/* ---- A spatial rectangle of a frame range of a version 2, 3 or 4 chunk ----
+ * The spatial transform is one lifting level per axis and every axis of a channel's [t'][y][x] symbol volume is stored as
+ * [low | high], so the frame-range rule above holds on x and on y as it holds on t.  With pw, ph the padded width and
+ * height, for an axis of padded length pn and the real positions [c0, c1):
+ *     a = 0 if c0 - NS <= 0 else (c0 - NS) & ~1        b = min(pn, (c1 + NS + 1) & ~1)
+ * gives [ta, tb), [ya, yb) and [xa, xb).  The coefficients whose coordinate lies, on every axis, in [a/2, b/2) or in
+ * pn/2 + [a/2, b/2) are, low run then high run, the symbol volume of a chunk of (xb - xa) x (yb - ya) x (tb - ta) whose
+ * inverse equals the full chunk's at the rectangle shifted by (xa, ya, ta), bit for bit.  These calls decode the blocks
+ * that hold such a coefficient, run the container's inverse over that virtual chunk (the instance is the full decode's) and
+ * copy the w x h pixels at (x, y) of frames [first, first + count) out of it; a rectangle that is the whole frame is
+ * written directly and costs what a frame range costs.  The pixels are the full decode's.
+ * Validation, its order and its codes are alice_codec_decode_frames' (version 1: "no random access"); then w >= 1, h >= 1,
+ * x + w <= width and y + h <= height, else ALICE_ERR_INVALID_DIMENSIONS; then the pitches.  INTEGRITY as above: the whole
+ * block-length tables are checked, the lane end checks cover the decoded blocks only, and a refusal for damage in a decoded
+ * block writes nothing to d_rgb_out.  Nothing is queued or written on a refusal.  Memory comes from the library's pool;
+ * nothing goes through the chain hub. */
+/* The spatial windows of a rectangle of a width x height frame; no device needed.  wavelet_type above 2:
+ * ALICE_ERR_INVALID_BITSTREAM; width or height = 2^32 - 1: ALICE_ERR_DIMENSION_OVERFLOW; a rectangle that is empty or
+ * does not lie inside the frame: ALICE_ERR_INVALID_DIMENSIONS. */
+int alice_codec_rect_window(uint8_t wavelet_type, uint32_t width, uint32_t height, uint32_t x, uint32_t y, uint32_t w, uint32_t h,
+                            uint32_t *xa, uint32_t *xb, uint32_t *ya, uint32_t *yb);
+/* One container in host memory -> count * h * w * 3 packed RGB bytes (free with alice_codec_data_free64), NULL on error.
+ * Reads and uploads the 1630-byte header, the three block-length tables and the byte runs of consecutive planned blocks,
+ * nothing else of `data` (which may be a mapped file); downloads the rectangles. */
+uint8_t *alice_codec_decode_rect(const uint8_t *data, uint64_t len, uint32_t first, uint32_t count, uint32_t x, uint32_t y,
+                                 uint32_t w, uint32_t h, uint64_t *out_len);
+/* The same for a container of `len` bytes on the device (any byte alignment).  Pixel i of row r of frame k of the rectangle
+ * goes to d_rgb_out + k * frame_pitch + r * row_pitch + 3 * i (pitches in bytes); row_pitch = frame_pitch = 0 means packed
+ * (3 w, 3 w h); one of them 0 takes its packed value from the other.  Non-zero pitches need row_pitch >= 3 w and
+ * frame_pitch >= row_pitch * h, else ALICE_ERR_INVALID_DIMENSIONS.  Only the 3 w bytes of each of the h rows of each frame
+ * are written, so d_rgb_out may point into full-size frames.  The output must not overlap the container.  The header is
+ * read back first.  Finished on return. */
+int alice_codec_dev_decode_rect(const void *d_alc, uint64_t len, uint32_t first, uint32_t count, uint32_t x, uint32_t y, uint32_t w,
+                                uint32_t h, void *d_rgb_out, uint64_t row_pitch, uint64_t frame_pitch, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -782,6 +782,32 @@ inline void preview_decode_device(const void* d_alc, uint64_t length, uint32_t f
     detail::check(alice_codec_dev_decode_preview(d_alc, length, first, count, d_rgb_out, hip_stream));
 }
 
+// ---- a spatial rectangle of a frame range of a version 2, 3 or 4 chunk ----
+// the w x h pixels at (x, y) of frames [first, first + count) from the blocks they need: count * h * w * 3 packed RGB bytes,
+// or (device call, non-zero pitches) pasted into a pitched surface such as full-size frames
+struct Rect { uint32_t x, y, w, h; };
+struct RectWindow { uint32_t xa, xb, ya, yb; };
+inline RectWindow rect_window(WaveletType wt, uint32_t width, uint32_t height, const Rect& r) {
+    RectWindow v{0, 0, 0, 0};
+    detail::check(alice_codec_rect_window(static_cast<uint8_t>(wt), width, height, r.x, r.y, r.w, r.h, &v.xa, &v.xb, &v.ya, &v.yb));
+    return v;
+}
+inline std::vector<uint8_t> decode_rect(const uint8_t* data, uint64_t len, uint32_t first, uint32_t count, const Rect& r) {
+    static const uint8_t empty = 0;
+    uint64_t n = 0;
+    uint8_t* p = alice_codec_decode_rect(data ? data : &empty, data ? len : 0, first, count, r.x, r.y, r.w, r.h, &n);
+    if (!p) detail::raise(ALICE_ERR_INVALID_BITSTREAM);
+    return detail::take(p, n);
+}
+inline std::vector<uint8_t> decode_rect(const std::vector<uint8_t>& data, uint32_t first, uint32_t count, const Rect& r) {
+    return decode_rect(data.empty() ? nullptr : data.data(), data.size(), first, count, r);
+}
+inline void rect_decode_device(const void* d_alc, uint64_t length, uint32_t first, uint32_t count, const Rect& r, void* d_rgb_out,
+                               uint64_t row_pitch = 0, uint64_t frame_pitch = 0, void* hip_stream = nullptr) {
+    detail::check(alice_codec_dev_decode_rect(d_alc, length, first, count, r.x, r.y, r.w, r.h, d_rgb_out, row_pitch, frame_pitch,
+                                              hip_stream));
+}
+
 // version 2 rate control: the bracket of encode_split's length at the 101 qualities (every version 2 table
 // is bounded: status stays ALICE_RATE_BOUNDED) and one encode at the quality the budget rule picks -- the largest whose
 // upper bound fits, refined by at most ALICE_SPLIT_REFINE_TRIALS exact size counts among the straddling qualities

@@ -143,6 +143,12 @@ void alice_codec_test_last_frames_stats(uint64_t out[5]);
  * blocks; 0 for the device call), frames written, symbols stored over the three channels (3 (b - a) qw qh)}. */
 void alice_codec_test_last_preview_stats(uint64_t out[6]);
 
+/* The last alice_codec_decode_rect / alice_codec_dev_decode_rect of the calling thread that reached the device:
+ * out = {ta, tb, xa, xb, ya, yb of the three windows, blocks decoded over the three channels, payload bytes the host call
+ * uploaded (the planned blocks; 0 for the device call), frames written, symbols stored over the three channels
+ * (3 (tb - ta) (yb - ya) (xb - xa))}. */
+void alice_codec_test_last_rect_stats(uint64_t out[10]);
+
 #ifdef __cplusplus
 }
 #endif
