@@ -19,7 +19,7 @@ struct RansResult {
     uint32_t hw_id;           // HW_REG_HW_ID: wave [3:0], SIMD [5:4], pipe [7:6], CU [11:8], SH [12], SE [15:13]
     uint32_t xcc_id;          // HW_REG_XCC_ID [3:0]
     uint32_t paths;           // which branches of the tile loop ran (decode: kDecPath*, encode: kEncPath*), for the test-suite's coverage check
-    uint32_t comp_blocks;     // encode: 64-symbol blocks of clean tiles that took the complement step (ripple64_comp)
+    uint32_t comp_blocks;     // encode: 64-symbol blocks of clean tiles that took the complement step (ripple64_comp_run)
 };
 
 constexpr uint32_t kDecPathDry = 1u;          // stream exhausted: no-window tile

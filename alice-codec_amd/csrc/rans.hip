@@ -21,7 +21,7 @@
 // of the update from then on, so no masking is needed; after 64 steps every lane
 // holds the exact state before and after its own symbol.  The serial chain is 9
 // VALU instructions per symbol (7 in blocks without a symbol of frequency <= 16,
-// which carry the complement of the state: ripple64_comp) with no memory access
+// which carry the complement of the state: ripple64_comp_run) with no memory access
 // and no cross-lane traffic other than the DPP operand.  Byte emission (0-2 bytes per symbol, taken from the
 // low bytes of the pre-renormalisation state) is then a wave-parallel ballot/popcount
 // compaction.  Bytes are written back to front so the stream comes out already
@@ -259,33 +259,126 @@ __device__ __forceinline__ void ripple64_clean(uint32_t& xin, uint32_t& xout, ui
 // and the next lane's complement is u' = T' - 1 - x' = z + kc with kc = T' - 1 - C (its own T, the previous lane's C),
 // one v_add_u32_dpp as before.  On entry lane 0 of u holds T - 1 - x of the carry-in (the DPP read from an invalid lane
 // leaves it alone); on exit every lane holds its own u (before its symbol) and z (after: x' = C - z).
-__device__ __forceinline__ void ripple64_comp(uint32_t& u, uint32_t& z, uint32_t kc, uint32_t tpp, uint32_t rcp, uint32_t rsh,
-                                              int32_t g) {
-    uint32_t m, q;
-    // w = ashr(u, 8) + T'' in ONE instruction: v_mad_i64_i32 {w : lo} = u * 2^24 + {T'' : 0}.  The signed product's high
-    // dword is ashr(u, 8), the addend's low dword is 0, so nothing carries into the sum of the high dwords.  7 issue
-    // slots.  The two register pairs are named outright (inline asm has no operand modifier for one half of a pair):
-    // v[60:61] = {0, T''}, set up here in place of the leading s_nop 1, and v[62:63] = the product.
-#define ALICE_RIPPLE_STEP                                                            \
-    "v_add_u32_dpp %[u], %[z], %[kc] wave_shr:1 row_mask:0xf bank_mask:0xf\n\t"     \
-    "v_mad_i64_i32 v[62:63], vcc, %[u], %[two24], v[60:61]\n\t"                    \
-    "v_min_u32_e32 %[m], %[u], v63\n\t"                                           \
-    "v_mul_hi_u32 %[q], %[m], %[rcp]\n\t"                                          \
-    "v_lshrrev_b32_e32 %[q], %[rsh], %[q]\n\t"                                     \
-    "v_mad_i32_i24 %[z], %[q], %[g], %[m]\n\t"                                     \
-    "s_nop 1\n\t"
-#define ALICE_RIPPLE_STEP4 ALICE_RIPPLE_STEP ALICE_RIPPLE_STEP ALICE_RIPPLE_STEP ALICE_RIPPLE_STEP
-#define ALICE_RIPPLE_STEP16 ALICE_RIPPLE_STEP4 ALICE_RIPPLE_STEP4 ALICE_RIPPLE_STEP4 ALICE_RIPPLE_STEP4
+// w = ashr(u, 8) + T'' is ONE instruction: v_mad_i64_i32 {w : lo} = u * 2^24 + {T'' : 0}.  The signed product's high dword is
+// ashr(u, 8), the addend's low dword is 0, so nothing carries into the sum of the high dwords.  The product pair is named
+// outright, v[62:63] (inline asm has no operand modifier for one half of a pair).  The step is used by ripple64_comp_run.
+
+// The constants of a complement block that its chain reads in every step, and the block's C (which the block after it wants
+// in lane 0 of its cc_prev).  A run keeps two of these sets and its blocks swap their roles, so nothing is copied.
+struct CompSet { uint32_t kc, rcp, rsh, cc; int32_t g; };
+// What a run hands on besides the next block's CompSet: the rest of that block's constants, which only the plain code after
+// the run reads.
+struct CompNext { uint32_t xmax, tpp, cbias, xmax8, tm1; };
+
+// A RUN of complement blocks as one statement: the 64 complement steps of each block b of the run, with the
+// state-independent work of its neighbours in the seventh slot of a step, which otherwise only provides the two wait states
+// between the VALU write of z and its DPP read, and the comp -> comp block edge as one instruction.  Measured on a lone wave
+// (scripts/probes/latency_probe.hip, profiles/r20_ripple_filler_probe.json): the step costs 32.0 cycles with s_nop 1, with one
+// VALU or SALU instruction + s_nop 0, and with two VALU instructions; an LDS read or a byte store in the slot costs 8 cycles
+// more.  So every slot holds two instructions (they are the two wait states) or one and s_nop 0: the ALU fillers for nothing,
+// the three LDS reads and the byte store of a block for their 8 cycles each, beside an ALU filler.
+//   for block b + 1: its table row (tab_ab, LDS address `ad` = tab + 16 * symbol) and this lane's symbol of block b + 2
+//     (LDS address `sa`) are read in steps 0, 2 and 3, the row into v[52:59]; after the wait in step 20 the fillers compute
+//     the small-frequency ballot, cc_prev (lane 0: THIS block's C[63] by wave_ror:1, the others by wave_shr:1 -- only
+//     v_mov_b32_dpp carries lane traffic, see the v_subrev_u32_dpp trap in DESIGN.md section 4.3), tm1, kc, the row address
+//     of block b + 2, copy the row out of the fixed registers into the OTHER CompSet, or the ballot with all ones when the
+//     tile has no block b + 1 (`left` counts the blocks after this one), and the last slot makes {0, T''} of block b + 1
+//     and compares the ballot with 0 for the branch that ends the run.
+//   for block b - 1 (every block but the run's first): the sign test of its saved u into VCC -- v_mad_i64_i32's carry goes
+//     to an SGPR pair of its own here -- the mbcnt pair on tw, the offset (span1 - off for lanes that emit, the lane's dummy
+//     byte for the others), the byte ~u and tw += popcount in steps 0..5; the store in step 6.
+// The edge: step 0 of every block but the first is u = wave_ror1(z) + kc: lane 0 gets z[63] + kc[0] =
+// T'[0] - 1 - (C[63] - z[63]) with kc[0] = T'[0] - 1 - C[63] as the block before made it; the other lanes are overwritten by
+// the later steps as always.  The first block enters with T - 1 - x in lane 0 of u0.
+// The run ends when `stop` is not 0 after a block (block b + 1 holds a symbol of frequency <= 16, or the tile is over).  Then
+// phase tells which set is which: 0 -- the last block ran on sa_ and u0, sb_ holds block b + 1's constants; 1 -- the reverse.
+// The last block's own byte is NOT stored: the caller emits it from u0 / u1.  z is the last block's z.
+__device__ __forceinline__ void ripple64_comp_run(uint32_t& u0, uint32_t& u1, uint32_t& z, uint32_t tpp, CompSet& sa_, CompSet& sb_,
+                                                  uint32_t tab, uint32_t& ad, uint32_t& sa, uint32_t& sym1, CompNext& nx,
+                                                  unsigned long long& stop, uint32_t& left, uint32_t& phase, uint32_t& tw,
+                                                  uint32_t lane, uint32_t span1, const void* tb) {
+    uint32_t m, q, ccp, cnt, off, byt;
+    unsigned long long cy, end, tp = (unsigned long long)tpp << 32;   // {0, T''}
+    // U: the block's u; S: the CompSet its chain reads; N: the one it fills; P: the u of the block before
+#define ALICE_RUN_CHAIN(CTRL, U, S)                                                          \
+    "v_add_u32_dpp %[" U "], %[z], %[kc" S "] " CTRL " row_mask:0xf bank_mask:0xf\n\t"      \
+    "v_mad_i64_i32 v[62:63], %[cy], %[" U "], %[two24], %[tp]\n\t"                          \
+    "v_min_u32_e32 %[m], %[" U "], v63\n\t"                                                 \
+    "v_mul_hi_u32 %[q], %[m], %[rcp" S "]\n\t"                                              \
+    "v_lshrrev_b32_e32 %[q], %[rsh" S "], %[q]\n\t"                                         \
+    "v_mad_i32_i24 %[z], %[q], %[g" S "], %[m]\n\t"
+#define ALICE_RUN_STEP(U, S, FILL) ALICE_RUN_CHAIN("wave_shr:1", U, S) FILL
+#define ALICE_RUN_IDLE(U, S) ALICE_RUN_STEP(U, S, "s_nop 1\n\t")
+#define ALICE_RUN_IDLE4(U, S) ALICE_RUN_IDLE(U, S) ALICE_RUN_IDLE(U, S) ALICE_RUN_IDLE(U, S) ALICE_RUN_IDLE(U, S)
+#define ALICE_RUN_IDLE13(U, S) ALICE_RUN_IDLE4(U, S) ALICE_RUN_IDLE4(U, S) ALICE_RUN_IDLE4(U, S) ALICE_RUN_IDLE(U, S)
+    // steps 7..63
+#define ALICE_RUN_REST(U, S, N)                                                                                                   \
+    ALICE_RUN_IDLE13(U, S)                                                                                                        \
+    ALICE_RUN_STEP(U, S, "s_waitcnt lgkmcnt(0)\n\t s_nop 1\n\t")                                                                 \
+    ALICE_RUN_STEP(U, S, "v_lshl_add_u32 %[ad], %[sy], 4, %[tab]\n\t v_cmp_ge_u32_e64 %[sm], %[rl], v52\n\t")                    \
+    ALICE_RUN_STEP(U, S, "v_mov_b32_dpp %[ccp], %[cc" S "] wave_ror:1 row_mask:0xf bank_mask:0xf\n\t s_nop 0\n\t")              \
+    ALICE_RUN_STEP(U, S, "v_mov_b32_dpp %[ccp], v57 wave_shr:1 row_mask:0xf bank_mask:0xf\n\t s_nop 0\n\t")                      \
+    ALICE_RUN_STEP(U, S, "v_add_u32_e32 %[tmn], -1, v52\n\t s_nop 0\n\t")                                                        \
+    ALICE_RUN_STEP(U, S, "v_sub_u32_e32 %[kc" N "], %[tmn], %[ccp]\n\t s_nop 0\n\t")                                             \
+    ALICE_RUN_STEP(U, S, "v_mov_b32_e32 %[rcp" N "], v53\n\t v_mov_b32_e32 %[rsh" N "], v54\n\t")                                \
+    ALICE_RUN_STEP(U, S, "v_mov_b32_e32 %[g" N "], v55\n\t v_mov_b32_e32 %[cc" N "], v57\n\t")                                   \
+    ALICE_RUN_STEP(U, S, "v_mov_b32_e32 %[xmn], v52\n\t v_mov_b32_e32 %[cbn], v58\n\t")                                          \
+    ALICE_RUN_STEP(U, S, "v_mov_b32_e32 %[x8n], v59\n\t v_mov_b32_e32 %[tpn], v56\n\t")                                          \
+    ALICE_RUN_STEP(U, S, "s_cmp_eq_u32 %[left], 0\n\t s_cselect_b64 %[end], -1, 0\n\t")                                          \
+    ALICE_RUN_STEP(U, S, "s_or_b64 %[sm], %[sm], %[end]\n\t s_sub_u32 %[left], %[left], 1\n\t")                                  \
+    ALICE_RUN_IDLE13(U, S) ALICE_RUN_IDLE13(U, S) ALICE_RUN_IDLE4(U, S) ALICE_RUN_IDLE(U, S)                                      \
+    ALICE_RUN_STEP(U, S, "v_lshlrev_b64 %[tp], 32, v[56:57]\n\t s_cmp_lg_u64 %[sm], 0\n\t")
+#define ALICE_RUN_READ_A "ds_read_b128 v[52:55], %[ad]\n\t"
+#define ALICE_RUN_READ_B "ds_read_b128 v[56:59], %[ad] offset:4096\n\t"
+#define ALICE_RUN_READ_S "ds_read_u8 %[sy], %[sa]\n\t"
+#define ALICE_RUN_FIRST(U, S, N)                                                                                                  \
+    ALICE_RUN_STEP(U, S, ALICE_RUN_READ_A " s_nop 0\n\t")                                                                         \
+    ALICE_RUN_IDLE(U, S)                                                                                                          \
+    ALICE_RUN_STEP(U, S, ALICE_RUN_READ_B " s_nop 0\n\t")                                                                         \
+    ALICE_RUN_STEP(U, S, ALICE_RUN_READ_S " s_nop 0\n\t")                                                                         \
+    ALICE_RUN_IDLE(U, S) ALICE_RUN_IDLE(U, S)                                                                                     \
+    ALICE_RUN_STEP(U, S, "v_subrev_u32_e32 %[sa], 64, %[sa]\n\t s_nop 0\n\t")                                                    \
+    ALICE_RUN_REST(U, S, N)
+#define ALICE_RUN_NEXT(U, P, S, N)                                                                                                \
+    ALICE_RUN_CHAIN("wave_ror:1", U, S) "v_cmp_gt_i32_e32 vcc, 0, %[" P "]\n\t" ALICE_RUN_READ_A                                  \
+    ALICE_RUN_STEP(U, S, "v_not_b32_e32 %[byt], %[" P "]\n\t s_bcnt1_i32_b64 %[cnt], vcc\n\t")                                   \
+    ALICE_RUN_STEP(U, S, "v_mbcnt_lo_u32_b32 %[off], vcc_lo, %[tw]\n\t" ALICE_RUN_READ_B)                                         \
+    ALICE_RUN_STEP(U, S, "v_mbcnt_hi_u32_b32 %[off], vcc_hi, %[off]\n\t" ALICE_RUN_READ_S)                                        \
+    ALICE_RUN_STEP(U, S, "v_sub_u32_e32 %[off], %[span1], %[off]\n\t v_add_u32_e32 %[tw], %[cnt], %[tw]\n\t")                    \
+    ALICE_RUN_STEP(U, S, "v_cndmask_b32_e32 %[off], %[lane], %[off], vcc\n\t s_nop 0\n\t")                                       \
+    ALICE_RUN_STEP(U, S, "global_store_byte %[off], %[byt], %[tb]\n\t v_subrev_u32_e32 %[sa], 64, %[sa]\n\t")                    \
+    ALICE_RUN_REST(U, S, N)
     asm volatile(
-        "v_mov_b32_e32 v60, 0\n\t"
-        "v_mov_b32_e32 v61, %[tpp]\n\t"
-        ALICE_RIPPLE_STEP16 ALICE_RIPPLE_STEP16 ALICE_RIPPLE_STEP16 ALICE_RIPPLE_STEP16
-        : [u] "+v"(u), [z] "=&v"(z), [m] "=&v"(m), [q] "=&v"(q)
-        : [kc] "v"(kc), [tpp] "v"(tpp), [rcp] "v"(rcp), [rsh] "v"(rsh), [g] "v"(g), [two24] "s"(1u << 24)
-        : "v60", "v61", "v62", "v63", "vcc");
-#undef ALICE_RIPPLE_STEP16
-#undef ALICE_RIPPLE_STEP4
-#undef ALICE_RIPPLE_STEP
+        "s_mov_b32 %[ph], 0\n\t"
+        ALICE_RUN_FIRST("u0", "a", "b")
+        "1:\n\t"
+        "s_cbranch_scc1 3f\n\t"      // (SCC: stop != 0, from the last slot of the block before)
+        ALICE_RUN_NEXT("u1", "u0", "b", "a")
+        "s_cbranch_scc1 2f\n\t"
+        ALICE_RUN_NEXT("u0", "u1", "a", "b")
+        "s_branch 1b\n\t"
+        "2:\n\t"
+        "s_mov_b32 %[ph], 1\n\t"
+        "3:\n\t"
+        : [u0] "+v"(u0), [u1] "=&v"(u1), [z] "=&v"(z), [tp] "+v"(tp), [ad] "+v"(ad), [sa] "+v"(sa), [sy] "=&v"(sym1), [tw] "+v"(tw),
+          [off] "=&v"(off), [byt] "=&v"(byt), [cnt] "=&s"(cnt), [m] "=&v"(m), [q] "=&v"(q), [ccp] "=&v"(ccp), [cy] "=&s"(cy),
+          [sm] "=&s"(stop), [end] "=&s"(end), [left] "+s"(left), [ph] "=&s"(phase), [tmn] "=&v"(nx.tm1), [xmn] "=&v"(nx.xmax),
+          [tpn] "=&v"(nx.tpp), [cbn] "=&v"(nx.cbias), [x8n] "=&v"(nx.xmax8),
+          [kca] "+v"(sa_.kc), [rcpa] "+v"(sa_.rcp), [rsha] "+v"(sa_.rsh), [ga] "+v"(sa_.g), [cca] "+v"(sa_.cc),
+          [kcb] "=&v"(sb_.kc), [rcpb] "=&v"(sb_.rcp), [rshb] "=&v"(sb_.rsh), [gb] "=&v"(sb_.g), [ccb] "=&v"(sb_.cc)
+        : [tab] "s"(tab), [lane] "v"(lane), [span1] "s"(span1), [two24] "s"(1u << 24), [rl] "s"(kRansL), [tb] "s"(tb)
+        : "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v62", "v63", "vcc", "scc", "memory");
+#undef ALICE_RUN_NEXT
+#undef ALICE_RUN_FIRST
+#undef ALICE_RUN_READ_S
+#undef ALICE_RUN_READ_B
+#undef ALICE_RUN_READ_A
+#undef ALICE_RUN_REST
+#undef ALICE_RUN_IDLE13
+#undef ALICE_RUN_IDLE4
+#undef ALICE_RUN_IDLE
+#undef ALICE_RUN_STEP
+#undef ALICE_RUN_CHAIN
 }
 
 // kExclusive: the kernel claims more than half of the SIMD's 512 registers (an AGPR clobber; nothing uses them), so
@@ -304,10 +397,10 @@ __global__ __launch_bounds__(64) void rans_encode_kernel(const uint8_t* __restri
                                                          unsigned long long cap1, unsigned long long cap2,
                                                          uint32_t x_init, uint32_t keep_open, uint32_t take_turns,
                                                          const RansEncodeDesc* __restrict__ descs) {
-    // what the clean tile reads per symbol is in tab_a and tab_b; T'' and C are the complement step's per-lane constants
-    // (ripple64_comp; meaningful for 17 <= freq <= 4096 only)
-    __shared__ uint4 tab_a[256];  // xmax, rcp, rsh, g
-    __shared__ uint4 tab_b[256];  // T'' = xmax - (xmax >> 8), C = 2^31 - 4097 + freq + cum, cbias, xmax8
+    // what the clean tile reads per symbol is in tab_ab; T'' and C are the complement step's per-lane constants
+    // (ripple64_comp_run; meaningful for 17 <= freq <= 4096 only)
+    // (one array: a run statement reads both rows of a symbol off one LDS address, the second at offset 4096)
+    __shared__ uint4 tab_ab[512];  // [s]: xmax, rcp, rsh, g;  [256 + s]: T'' = xmax - (xmax >> 8), C = 2^31 - 4097 + freq + cum, cbias, xmax8
     __shared__ uint2 tab_c[256];  // freq, cum
     // the tile's 1024 symbols sit behind kEncTilePad bytes that are never written: the block pipeline reads two blocks
     // past the end of a tile (values it never uses), at plain descending addresses
@@ -340,8 +433,8 @@ __global__ __launch_bounds__(64) void rans_encode_kernel(const uint8_t* __restri
 
     for (int s = lane; s < 256; s += 64) {
         const RansEncEntry e = tbl->enc[s];
-        tab_a[s] = make_uint4(e.xmax, e.rcp, e.rsh, (uint32_t)e.g);
-        tab_b[s] = make_uint4(e.xmax - (e.xmax >> 8), e.cbias + e.freq + ((1u << 31) - kProbScale - 1u), e.cbias, e.xmax8);
+        tab_ab[s] = make_uint4(e.xmax, e.rcp, e.rsh, (uint32_t)e.g);
+        tab_ab[256 + s] = make_uint4(e.xmax - (e.xmax >> 8), e.cbias + e.freq + ((1u << 31) - kProbScale - 1u), e.cbias, e.xmax8);
         tab_c[s] = make_uint2(e.freq, e.cum);
     }
 
@@ -398,7 +491,7 @@ __global__ __launch_bounds__(64) void rans_encode_kernel(const uint8_t* __restri
 
     struct BlockParams { uint4 ea, eb; uint2 ec; };
     auto sym_of = [&](int b) -> uint32_t { return tile[kEncTilePad + kEncTile - 1 - lane - b * 64]; };   // b <= 17
-    auto params_of = [&](uint32_t s) -> BlockParams { BlockParams p; p.ea = tab_a[s]; p.eb = tab_b[s]; p.ec = tab_c[s]; return p; };
+    auto params_of = [&](uint32_t s) -> BlockParams { BlockParams p; p.ea = tab_ab[s]; p.eb = tab_ab[256 + s]; p.ec = tab_c[s]; return p; };
 
     uint4 cur = load_tile(0);
     for (unsigned long long j = 0; j < ntiles; ++j) {
@@ -435,40 +528,62 @@ __global__ __launch_bounds__(64) void rans_encode_kernel(const uint8_t* __restri
             // (kept in a VGPR, where mbcnt wants its start value: one v_add per block instead of s_add + v_mov)
             uint32_t tw = 0u, rare_blocks = 0u;
             asm volatile("" : "+v"(tw));
-#pragma unroll 2
-            for (int b = 0; b < kEncTile / 64; ++b) {
-                const BlockParams curp = nxt;
-                nxt = params_of(sym1);
-                sym1 = sym_of(b + 2);
-                const uint32_t xmax = curp.ea.x, rcp = curp.ea.y, rsh = curp.ea.z;
-                const int32_t g = (int32_t)curp.ea.w;
-                const bool small_f = xmax <= kRansL;            // freq <= 16
-                if (__builtin_expect(__ballot(small_f) == 0ull, 1)) {
-                    // every lane in the big class (17 <= freq <= 4096, so cbias = cum): the complement step
-                    const uint32_t tm1 = xmax - 1u, tpp = curp.eb.x, cc = curp.eb.y;
-                    // C of the lane before, as a value of its own: left to the compiler, the move folds into the
-                    // subtraction as v_subrev_u32_dpp, and that instruction gave tm1[lane - 1] - C[lane] on the MI355X
-                    // (DESIGN.md section 4.3).  Only v_mov_b32_dpp and v_add_u32_dpp carry lane traffic here.
-                    uint32_t cc_prev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)cc, 0x138, 0xf, 0xf, true);
-                    asm volatile("" : "+v"(cc_prev));
-                    const uint32_t kc = tm1 - cc_prev;
-                    uint32_t u = tm1 - xin, z;                  // lane 0: the carry-in; the others are overwritten
-                    ripple64_comp(u, z, kc, tpp, rcp, rsh, g);
+            // Carried from block to block: block b's constants, its small-frequency ballot and (for a complement block) tm1
+            // and kc; the symbol of block b + 1 and the LDS address of its table row; the LDS address of this lane's symbol
+            // of block b + 2; the number of blocks after this one.  A run statement advances all of them in its wait-state
+            // slots, a rare block in plain code.
+            uint32_t xmax = nxt.ea.x, tpp = nxt.eb.x, cbias = nxt.eb.z, xmax8 = nxt.eb.w;
+            CompSet cs;
+            cs.rcp = nxt.ea.y; cs.rsh = nxt.ea.z; cs.g = (int32_t)nxt.ea.w; cs.cc = nxt.eb.y;
+            const uint32_t tab = (uint32_t)(uintptr_t)tab_ab;
+            uint32_t ad = tab + 16u * sym1;
+            uint32_t sa = (uint32_t)(uintptr_t)tile + (uint32_t)(kEncTilePad + kEncTile - 1 - 2 * 64) - (uint32_t)lane;
+            // C of the lane before, as a value of its own: left to the compiler, the move folds into the subtraction as
+            // v_subrev_u32_dpp, and that instruction gave tm1[lane - 1] - C[lane] on the MI355X.
+            // Only v_mov_b32_dpp and v_add_u32_dpp carry lane traffic here.  (Lane 0's kc is not used: a block that takes
+            // this kc enters with the plain state.)
+            auto kc_of = [](uint32_t tm1_, uint32_t cc_) -> uint32_t {
+                uint32_t cc_prev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)cc_, 0x138, 0xf, 0xf, true);
+                asm volatile("" : "+v"(cc_prev));
+                return tm1_ - cc_prev;
+            };
+            // stop: lanes of block b with freq <= 16; out of a run statement also all ones when the tile has no block b + 1
+            unsigned long long stop = __ballot(xmax <= kRansL);
+            uint32_t tm1 = xmax - 1u;
+            cs.kc = kc_of(tm1, cs.cc);
+            uint32_t left = (uint32_t)(kEncTile / 64 - 1);
+            while ((int32_t)left >= 0) {
+                if (__builtin_expect(stop == 0ull, 1)) {
+                    // A run of blocks whose lanes are all in the big class (17 <= freq <= 4096, so cbias = cum): the first
+                    // enters with the plain state, the others through the one-instruction edge; each block stores the
+                    // byte of the block before it, the last block's emission follows the run.
+                    CompSet sa_ = cs, sb_;
+                    CompNext nx;
+                    uint32_t u0 = tm1 - xin, u1, z, phase;                   // lane 0: the carry-in; the others are overwritten
+                    ripple64_comp_run(u0, u1, z, tpp, sa_, sb_, tab, ad, sa, sym1, nx, stop, left, phase, tw, (uint32_t)lane,
+                                      kTileSpan - 1u, (const void*)tb);
+                    const bool swapped = phase != 0u;                         // uniform
+                    const uint32_t u = swapped ? u1 : u0, cc_last = swapped ? sb_.cc : sa_.cc;
+                    cs.kc = swapped ? sa_.kc : sb_.kc; cs.rcp = swapped ? sa_.rcp : sb_.rcp; cs.rsh = swapped ? sa_.rsh : sb_.rsh;
+                    cs.g = swapped ? sa_.g : sb_.g; cs.cc = swapped ? sa_.cc : sb_.cc;
+                    xmax = nx.xmax; tpp = nx.tpp; cbias = nx.cbias; xmax8 = nx.xmax8; tm1 = nx.tm1;
                     // x >= T exactly when u wrapped; at most one byte, x & 0xFF = ~u & 0xFF (256 divides T)
                     const bool c1 = (int32_t)u < 0;
                     const unsigned long long b1 = __ballot(c1);
-                    const uint32_t off = __builtin_amdgcn_mbcnt_hi((uint32_t)(b1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b1, tw));
-                    tb[c1 ? kTileSpan - 1u - off : (uint32_t)lane] = (uint8_t)(~u & 0xFFu);
+                    const uint32_t o1 = __builtin_amdgcn_mbcnt_hi((uint32_t)(b1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b1, tw));
+                    tb[c1 ? kTileSpan - 1u - o1 : (uint32_t)lane] = (uint8_t)(~u & 0xFFu);
                     tw += (uint32_t)__popcll(b1);
                     // wave_ror:1 -- lane 0 of the next block's xin receives the plain state x' = C[63] - z[63]
-                    xin = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(cc - z), 0x13C, 0xf, 0xf, true);
+                    xin = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(cc_last - z), 0x13C, 0xf, 0xf, true);
                 } else {
                     rare_blocks += 1u;
-                    const uint32_t cbias = curp.eb.z, xmax8 = curp.eb.w;
+                    const BlockParams np = params_of(sym1);   // block b + 1's rows, in flight while this block ripples
+                    sym1 = sym_of(kEncTile / 64 + 1 - (int)left);   // block b + 2
+                    const bool small_f = xmax <= kRansL;            // freq <= 16
                     uint32_t xout = 0u;
                     const uint32_t cprev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)cbias, 0x138, 0xf, 0xf, true);
                     const uint32_t k0 = small_f ? 8u : 0u;
-                    ripple64_clean(xin, xout, small_f ? xmax8 : xmax, k0, k0 + 8u, rcp, rsh, g, cprev);
+                    ripple64_clean(xin, xout, small_f ? xmax8 : xmax, k0, k0 + 8u, cs.rcp, cs.rsh, cs.g, cprev);
                     const bool c1 = xin >= xmax;
                     const bool c2 = xin >= xmax8;
                     const unsigned long long b1 = __ballot(c1), b2 = __ballot(c2);
@@ -479,6 +594,12 @@ __global__ __launch_bounds__(64) void rans_encode_kernel(const uint8_t* __restri
                     tw += (uint32_t)__popcll(b1) + (uint32_t)__popcll(b2);
                     // wave_ror:1 -- lane 0 of the next block's xin receives xout[63] + cbias[63]
                     xin = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(xout + cbias), 0x13C, 0xf, 0xf, false);
+                    xmax = np.ea.x; cs.rcp = np.ea.y; cs.rsh = np.ea.z; cs.g = (int32_t)np.ea.w;
+                    tpp = np.eb.x; cs.cc = np.eb.y; cbias = np.eb.z; xmax8 = np.eb.w;
+                    stop = __ballot(xmax <= kRansL);
+                    tm1 = xmax - 1u; cs.kc = kc_of(tm1, cs.cc);
+                    ad = tab + 16u * sym1; sa -= 64u;
+                    left -= 1u;
                 }
                 asm volatile("" : "+v"(tw));
             }

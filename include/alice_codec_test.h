@@ -43,7 +43,7 @@ int alice_codec_test_encode_chains(uint32_t n_chains, const void *const *d_symbo
                                    const uint32_t *x_init, const uint32_t *keep_open, uint32_t *out, void *hip_stream);
 
 /* The same launch with one more result per chain: out[7 c ..] = the six values above, then the number of 64-symbol blocks of
- * clean tiles that took the complement step (csrc/rans.hip, ripple64_comp: blocks in which every symbol has a table
+ * clean tiles that took the complement step (csrc/rans.hip, ripple64_comp_run: blocks in which every symbol has a table
  * frequency of at least 17). */
 int alice_codec_test_encode_chains_blocks(uint32_t n_chains, const void *const *d_symbols, const uint64_t *ns,
                                           const uint32_t *hists, const uint16_t *cum_freq, const uint16_t *freq,

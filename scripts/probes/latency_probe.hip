@@ -75,9 +75,64 @@ PROBE_KERNEL(k_enc_comp8, "v_add_u32_dpp v40, v44, v41 wave_shr:1 row_mask:0xf b
 PROBE_KERNEL(k_enc_comp7, "v_add_u32_dpp v40, v44, v41 wave_shr:1 row_mask:0xf bank_mask:0xf\n\t v_mad_i64_i32 v[46:47], s[46:47], v40, v41, v[48:49]\n\t v_min_u32_e32 v45, v40, v47\n\t v_mul_hi_u32 v43, v45, v41\n\t v_lshrrev_b32_e32 v43, v42, v43\n\t v_mad_i32_i24 v44, v43, v42, v45\n\t s_nop 1\n\t")
 PROBE_KERNEL(k_vmad_i64_i32, "v_mad_i64_i32 v[46:47], s[46:47], v47, v41, v[48:49]\n\t")
 
+// What the seventh slot of the complement step (its closing s_nop 1: the two wait states between the VALU write of z
+// and the DPP read) can carry for nothing.  The same six chain instructions as k_enc_comp7, then the filler.  These
+// kernels own LDS (the ds_read's target; v50 = 16 * lane) and take a byte buffer (the store's target: out + 256 + lane,
+// as an SGPR base s[50:51] + the lane offset v51).  The ds_read variant is a 16-step group: one read per step, the
+// first into v[52:55] and the others into v[56:59], the wait (lgkmcnt(14): the first read is back) in the slot of step
+// 14 and the first read's v53 as the multiplier of step 15 -- a result consumed 16 steps after its read.
+#define FILL_CHAIN_M(MUL)                                                                                         \
+  "v_add_u32_dpp v40, v44, v41 wave_shr:1 row_mask:0xf bank_mask:0xf\n\t"                                          \
+  "v_mad_i64_i32 v[46:47], s[46:47], v40, v41, v[48:49]\n\t v_min_u32_e32 v45, v40, v47\n\t"                       \
+  "v_mul_hi_u32 v43, v45, " MUL "\n\t v_lshrrev_b32_e32 v43, v42, v43\n\t v_mad_i32_i24 v44, v43, v42, v45\n\t"
+#define FILL_CHAIN FILL_CHAIN_M("v41")
+#define FILL_KERNEL(NAME, BODY32)                                                                                  \
+__global__ __launch_bounds__(64) void NAME(unsigned long long* out, uint32_t seed) {                               \
+  __shared__ uint4 lds[64];                                                                                        \
+  lds[threadIdx.x] = make_uint4(seed, 0x10001u, 3u, 7u);                                                            \
+  __syncthreads();                                                                                                 \
+  unsigned long long t0, t1;                                                                                       \
+  uint32_t cnt;                                                                                                    \
+  asm volatile(                                                                                                    \
+    "s_mov_b32 s41, 0x10001\n\t s_mov_b32 s42, 3\n\t"                                                              \
+    "v_mov_b32 v40, %[seed]\n\t v_mov_b32 v41, 0x10001\n\t v_mov_b32 v42, 3\n\t v_mov_b32 v44, 7\n\t"              \
+    "v_mov_b32 v48, 0\n\t v_mov_b32 v49, 0x1000\n\t v_mov_b32 v50, %[la]\n\t v_mov_b32 v51, %[so]\n\t"             \
+    "v_mov_b32 v53, 0x10001\n\t s_mov_b64 s[50:51], %[sb]\n\t"                                                     \
+    "s_memtime %[t0]\n\t s_waitcnt lgkmcnt(0)\n\t"                                                                 \
+    "s_mov_b32 %[cnt], 256\n\t"                                                                                    \
+    "1:\n\t" BODY32                                                                                                \
+    "s_sub_u32 %[cnt], %[cnt], 1\n\t s_cmp_lg_u32 %[cnt], 0\n\t s_cbranch_scc1 1b\n\t"                             \
+    "s_waitcnt vmcnt(0) lgkmcnt(0)\n\t"                                                                            \
+    "s_memtime %[t1]\n\t s_waitcnt lgkmcnt(0)\n\t"                                                                 \
+    : [t0] "=&s"(t0), [t1] "=&s"(t1), [cnt] "=&s"(cnt)                                                             \
+    : [seed] "s"(seed), [la] "v"((uint32_t)(threadIdx.x * 16u)), [so] "v"((uint32_t)(256u + threadIdx.x)), [sb] "s"(out) \
+    : "s41","s42","s45","s46","s47","s50","s51","v40","v41","v42","v43","v44","v45","v46","v47","v48","v49",      \
+      "v50","v51","v52","v53","v54","v55","v56","v57","v58","v59","v60","v61","vcc","scc","memory");               \
+  if (threadIdx.x == 0) out[0] = t1 - t0;                                                                          \
+}
+#define FILL_DS_FIRST FILL_CHAIN "ds_read_b128 v[52:55], v50\n\t s_nop 0\n\t"
+#define FILL_DS_MID FILL_CHAIN "ds_read_b128 v[56:59], v50\n\t s_nop 0\n\t"
+#define FILL_DS_WAIT FILL_CHAIN "ds_read_b128 v[56:59], v50\n\t s_waitcnt lgkmcnt(14)\n\t"
+#define FILL_DS_USE FILL_CHAIN_M("v53") "ds_read_b128 v[56:59], v50\n\t s_nop 0\n\t"
+#define FILL_DS_GROUP16 FILL_DS_FIRST FILL_DS_MID FILL_DS_MID FILL_DS_MID FILL_DS_MID FILL_DS_MID FILL_DS_MID FILL_DS_MID \
+  FILL_DS_MID FILL_DS_MID FILL_DS_MID FILL_DS_MID FILL_DS_MID FILL_DS_MID FILL_DS_WAIT FILL_DS_USE
+FILL_KERNEL(k_fill_nop1, REP32(FILL_CHAIN "s_nop 1\n\t"))
+FILL_KERNEL(k_fill_valu_nop0, REP32(FILL_CHAIN "v_add_u32_e32 v60, v41, v42\n\t s_nop 0\n\t"))
+FILL_KERNEL(k_fill_valu2, REP32(FILL_CHAIN "v_add_u32_e32 v60, v41, v42\n\t v_xor_b32_e32 v61, v41, v42\n\t"))
+FILL_KERNEL(k_fill_ds_read, FILL_DS_GROUP16 FILL_DS_GROUP16)
+FILL_KERNEL(k_fill_store_byte, REP32(FILL_CHAIN "global_store_byte v51, v42, s[50:51]\n\t s_nop 0\n\t"))
+FILL_KERNEL(k_fill_salu_nop0, REP32(FILL_CHAIN "s_add_u32 s45, s41, s42\n\t s_nop 0\n\t"))
+// further slots a run of blocks would use: a VALU compare into an SGPR pair (the deferred sign test), a DPP move of a
+// value that is not on the chain (cc_prev), and a block's whole share of the work spread over its steps (one filler in
+// 27 of 32 steps, s_nop 1 in the others)
+FILL_KERNEL(k_fill_vcmp_sgpr, REP32(FILL_CHAIN "v_cmp_gt_i32_e64 s[46:47], 0, v41\n\t s_nop 0\n\t"))
+FILL_KERNEL(k_fill_dpp_mov, REP32(FILL_CHAIN "v_mov_b32_dpp v60, v41 wave_shr:1 row_mask:0xf bank_mask:0xf\n\t s_nop 0\n\t"))
+FILL_KERNEL(k_fill_valu_only, REP32(FILL_CHAIN "v_add_u32_e32 v60, v41, v42\n\t"))
+FILL_KERNEL(k_fill_nop0, REP32(FILL_CHAIN "s_nop 0\n\t"))
+
 struct T { const char* name; void (*fn)(unsigned long long*, uint32_t); };
-int main() {
-  unsigned long long* d; hipMalloc(&d, 64);
+int main(int argc, char** argv) {
+  unsigned long long* d; hipMalloc(&d, 4096);
   T tests[] = {{"empty loop", k_empty}, {"s_add dep", k_sadd}, {"s_add indep", k_sadd_indep}, {"s_mul_i32 dep", k_smul},
     {"s_mul_hi+s_or dep", k_smulhi}, {"s_bfe dep", k_sbfe}, {"s_lshl_b64 dep", k_slshl64}, {"v_add dep", k_vadd},
     {"v_add indep", k_vadd_indep}, {"v_mul_hi+v_or dep", k_vmulhi}, {"v_mul_lo dep", k_vmullo}, {"v_mad_u32_u24 dep", k_vmad24},
@@ -89,8 +144,15 @@ int main() {
     {"s_nop 0", k_snop0}, {"s_nop 1", k_snop1}, {"s_cmp+s_cselect dep", k_cselect},
     {"s_set_gpr_idx_on", k_setidx_on}, {"s_set_gpr_idx_idx", k_setidx_idx}, {"s_flbit", k_flbit}, {"s_flbit m0;nop;s_movrels", k_flbit_m0_movrels}, {"s_mov m0", k_m0_write}, {"decode v3 core (17 instr, idx_on+flbit)", k_dec2_core}, {"decode v3 core (18 instr, idx_idx+cmp/csel)", k_dec2_core_idx}, {"decode v4 symbol (14 instr)", k_dec4_core}, {"decode v4 pair (28 instr + cmp + untaken branch)", k_dec4_pair}, {"decode core (9 instr)", k_dec_core}, {"encode ripple step (11 instr)", k_enc_core},
     {"encode clean step (9 slots)", k_enc_clean9}, {"encode complement step (8 slots)", k_enc_comp8},
-    {"encode complement step, v_mad_i64_i32 (7 slots)", k_enc_comp7}, {"v_mad_i64_i32 dep", k_vmad_i64_i32}};
+    {"encode complement step, v_mad_i64_i32 (7 slots)", k_enc_comp7}, {"v_mad_i64_i32 dep", k_vmad_i64_i32},
+    {"comp step + s_nop 1", k_fill_nop1}, {"comp step + VALU + s_nop 0", k_fill_valu_nop0},
+    {"comp step + 2 VALU", k_fill_valu2}, {"comp step + ds_read_b128 (used 16 steps on) + s_nop 0", k_fill_ds_read},
+    {"comp step + global_store_byte + s_nop 0", k_fill_store_byte}, {"comp step + SALU + s_nop 0", k_fill_salu_nop0},
+    {"comp step + v_cmp to SGPR pair + s_nop 0", k_fill_vcmp_sgpr}, {"comp step + v_mov_dpp + s_nop 0", k_fill_dpp_mov},
+    {"comp step + VALU alone", k_fill_valu_only}, {"comp step + s_nop 0", k_fill_nop0}};
   double base = 0;
+  FILE* js = argc > 1 ? fopen(argv[1], "w") : nullptr;   // the "comp step + ..." rows as JSON (cycles per step)
+  if (js) fprintf(js, "{\n  \"what\": \"scripts/probes/latency_probe.hip: the 7-slot complement step on one wave alone, its closing s_nop 1 replaced by fillers; shader cycles per step, best of 5 launches, empty loop subtracted\"");
   for (auto& t : tests) {
     unsigned long long best = ~0ull;
     for (int r = 0; r < 5; ++r) {
@@ -101,6 +163,9 @@ int main() {
     double per = (double)best / (256.0 * 32.0);
     if (std::string(t.name) == "empty loop") base = (double)best;
     printf("%-40s %8.2f cycles/copy\n", t.name, ((double)best - base) / (256.0 * 32.0) + (std::string(t.name) == "empty loop" ? per : 0));
+    if (js && std::string(t.name).rfind("comp step + ", 0) == 0)
+      fprintf(js, ",\n  \"%s\": %.2f", t.name, ((double)best - base) / (256.0 * 32.0));
   }
+  if (js) { fprintf(js, "\n}\n"); fclose(js); }
   return 0;
 }
