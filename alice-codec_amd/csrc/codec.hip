@@ -4750,60 +4750,75 @@ int alice_codec_test_sq_diff_sum(const void* d_a, const void* d_b, uint64_t n, u
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------
-// PART 8: frame ranges of a version 2, 3 or 4 chunk (kernels: split_frames_decode_kernel of
-// split.hip, the window instances of transform.hip's temporal role)
+// PART 8: partial decode of a version 2, 3 or 4 chunk, and its first call, the frame range (kernels:
+// split_frames_decode_kernel and split_box_decode_kernel of split.hip, the window instances of transform.hip's temporal role)
 //
-// The temporal transform is one lifting level, so frames [t0, t1) depend on the coefficient planes of the frame pairs
-// inside [a, b) only (frames_window).  Those b - a planes, low band then high band, are the symbol volume of a virtual
-// chunk of b - a frames whose inverse temporal lifting equals the full chunk's at [t0 - a, t1 - a).  The lane decode runs
-// over the blocks that intersect the planes, the temporal role stores t1 - t0 frames, the spatial pass runs over those.
-// The end checks cover the blocks that are read: damage in a lane of another block is not seen.
+// Every transform is one lifting level per axis and every axis of a channel's [t'][y][x] symbol volume is deinterleaved into
+// [low | high], so the positions [c0, c1) of an axis depend on the coefficients of the pairs inside a window [a, b) only
+// (axis_window).  A partial call is one plan (the windows, the blocks that hold a kept symbol, where a kept symbol goes), the
+// lane stage over the planned blocks (partial_lane_decode) and a finish over the compact volume.  The end checks cover the
+// blocks that are read: damage in a lane of another block is not seen.
+//
+// A frame range is the rectangle of the whole frame: the b - a kept planes, low band then high band, are the symbol volume of
+// a virtual chunk of b - a frames whose inverse temporal lifting equals the full chunk's at [t0 - a, t1 - a); the temporal role
+// stores t1 - t0 frames and the spatial pass runs over those.
 // ------------------------------------------------------------------------------------------
 
 namespace {
 
 uint32_t frames_halo(uint8_t wavelet) { return wavelet == 1 ? 4u : 2u; }   // lifting steps: CDF 9/7 four, CDF 5/3 and Haar two
 
-// frames > 0, first + count <= frames, count > 0
-void frames_window(uint8_t wavelet, uint32_t frames, uint32_t first, uint32_t count, uint32_t* a, uint32_t* b) {
-    const uint64_t ns = frames_halo(wavelet), pf = frames == 1 ? 2ull : (uint64_t)frames + (frames & 1u);
-    const uint64_t t0 = first, t1 = (uint64_t)first + count;
-    *a = t0 > ns ? (uint32_t)((t0 - ns) & ~1ull) : 0u;
-    *b = (uint32_t)std::min<uint64_t>(pf, (t1 + ns + 1) & ~1ull);
+// the window of an axis of padded length pn and the real positions [c0, c1), c0 < c1 <= pn; ns: frames_halo
+void axis_window(uint64_t ns, uint64_t pn, uint64_t c0, uint64_t c1, uint32_t* a, uint32_t* b) {
+    *a = c0 > ns ? (uint32_t)((c0 - ns) & ~1ull) : 0u;
+    *b = (uint32_t)std::min<uint64_t>(pn, (c1 + ns + 1) & ~1ull);
 }
 
-struct FramesPlan {
-    uint32_t a = 0, b = 0;
-    int n_ranges = 0;                       // 1 when the two bands' planes touch (a = 0 and b = pf)
-    uint64_t sym_lo[2] = {0, 0}, sym_hi[2] = {0, 0};
-    uint32_t blk_first[2] = {0, 0}, blk_count[2] = {0, 0};   // disjoint: a block both ranges touch belongs to the first
-    uint32_t blocks() const { return blk_count[0] + blk_count[1]; }
-    std::vector<uint32_t> block_list() const {   // ascending, no duplicates
-        std::vector<uint32_t> v;
-        for (int r = 0; r < n_ranges; ++r)
-            for (uint32_t i = 0; i < blk_count[r]; ++i) v.push_back(blk_first[r] + i);
-        return v;
-    }
+// What a partial call decodes.  The three channels are alike.
+struct PartialPlan {
+    uint32_t ta = 0, tb = 0, xa = 0, xb = 0, ya = 0, yb = 0;   // the windows
+    std::vector<uint32_t> blocks;             // ascending, no duplicates
+    bool planes = false;                      // the kept symbols are whole coefficient planes: `ranges`; otherwise `box`
+    SplitFramesJob ranges{};                  // a channel's job less its SplitJob; a block both ranges touch belongs to the first
+    SplitBoxJob box{};                        // a channel's job less its SplitJob and the list
+    uint64_t stored = 0;                      // symbols of a channel that are stored
 };
 
-FramesPlan frames_plan(const SplitHeader& h, const ChunkDims& d, uint32_t first, uint32_t count) {
-    FramesPlan p;
-    frames_window(h.wavelet, h.frames, first, count, &p.a, &p.b);
+PartialPlan frames_plan(const SplitHeader& h, const ChunkDims& d, uint32_t first, uint32_t count) {
+    PartialPlan p;
+    axis_window(frames_halo(h.wavelet), d.pf, first, (uint64_t)first + count, &p.ta, &p.tb);
+    p.xb = (uint32_t)d.pw; p.yb = (uint32_t)d.ph;
+    p.planes = true;
+    SplitFramesJob& r = p.ranges;
     const uint64_t P = d.pw * d.ph, half = d.pf / 2, B = 64ull * h.lane_symbols;
-    const uint64_t lo0 = p.a / 2 * P, hi0 = p.b / 2 * P, lo1 = (half + p.a / 2) * P, hi1 = (half + p.b / 2) * P;
-    if (hi0 == lo1) { p.n_ranges = 1; p.sym_lo[0] = lo0; p.sym_hi[0] = hi1; }
-    else { p.n_ranges = 2; p.sym_lo[0] = lo0; p.sym_hi[0] = hi0; p.sym_lo[1] = lo1; p.sym_hi[1] = hi1; }
+    const uint64_t lo0 = p.ta / 2 * P, hi0 = p.tb / 2 * P, lo1 = (half + p.ta / 2) * P, hi1 = (half + p.tb / 2) * P;
+    p.stored = (p.tb - p.ta) * P;
+    int n_ranges;                             // 1 when the two bands' planes touch (a = 0 and b = pf)
+    if (hi0 == lo1) { n_ranges = 1; r.sym_lo[0] = lo0; r.sym_hi[0] = hi1; }
+    else { n_ranges = 2; r.sym_lo[0] = lo0; r.sym_hi[0] = hi0; r.sym_lo[1] = lo1; r.sym_hi[1] = hi1; }
     uint64_t next = 0;   // first block no earlier range has taken
-    for (int r = 0; r < p.n_ranges; ++r) {
-        const uint64_t f = std::max(p.sym_lo[r] / B, next), e = (p.sym_hi[r] + B - 1) / B;
-        p.blk_first[r] = (uint32_t)f;
-        p.blk_count[r] = e > f ? (uint32_t)(e - f) : 0u;
+    for (int k = 0; k < n_ranges; ++k) {
+        const uint64_t f = std::max<uint64_t>(r.sym_lo[k] / B, next), e = (r.sym_hi[k] + B - 1) / B;
+        r.blk_first[k] = (uint32_t)f;
+        r.blk_count[k] = e > f ? (uint32_t)(e - f) : 0u;
+        for (uint64_t blk = f; blk < e; ++blk) p.blocks.push_back((uint32_t)blk);
         next = std::max(next, e);
     }
     return p;
 }
 
-thread_local uint64_t tl_frames_stats[5] = {0, 0, 0, 0, 0};   // alice_codec_test_last_frames_stats
+// What the calling thread's last call of each kind planned: the test hooks of alice_codec_test.h read their columns
+enum PartialKind : int { kPartialFrames = 0, kPartialPreview = 1, kPartialRect = 2 };
+struct PartialStats { uint64_t ta, tb, xa, xb, ya, yb, blocks, uploaded, frames, stored; };
+thread_local PartialStats tl_partial_stats[3] = {};
+
+// The end of every partial call: the launch status, the drain, and the call's figures
+int partial_done(PartialKind kind, const PartialPlan& p, uint32_t count, uint64_t uploaded, hipStream_t st) {
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    tl_partial_stats[kind] = PartialStats{p.ta, p.tb, p.xa, p.xb, p.ya, p.yb, 3ull * p.blocks.size(), uploaded, count, 3 * p.stored};
+    return kOk;
+}
 
 // The checks both calls share, in their order (after the null checks): fixed fields and magic, the version byte, that
 // version's header checks, then the range.  data: min(len, kSplitHeaderBytes) readable bytes.
@@ -4930,51 +4945,78 @@ int inverse_window(const uint8_t* d_sym, const ChunkDims& dv, uint32_t lo, uint3
     return kOk;
 }
 
-// Frames [first, first + count) of the container at d_alc (device, h validated) to d_rgb (device, count packed frames).
-// Of the payloads only the block-length tables and the planned blocks are read.  Returns after the stream has drained.
-int frames_decode_device(const SplitHeader& h, const ChunkDims& d, const uint8_t* d_alc, uint32_t first, uint32_t count, void* d_rgb,
-                         hipStream_t st, uint64_t uploaded) {
-    const FramesPlan p = frames_plan(h, d, first, count);
-    const ChunkDims dv = make_dims(h.width, h.height, p.b - p.a);   // b - a is even and at least 2: no padding of its own
-    const ChunkDims dx = make_dims(h.width, h.height, count);
-    const SplitFormat fmt = h.fmt;
-    const bool wide = is_wide(fmt);
-    const size_t sb = wide ? 2 : 1;
-    DecodeWork dw;
-    dw.d = dv; dw.n_chunks = 1;
-    TRY(dw.sym.alloc(3 * dv.padded * sb));
-    DevBuf d_fj;                          // (declared before w: w's destructor drains the stream that reads them)
-    std::vector<SplitFramesJob> fj(3);
-    TRY(d_fj.alloc(3 * sizeof(SplitFramesJob)));
+// The lane stage of a partial call: the planned blocks of the container at d_alc (device, h validated) are decoded and the
+// kept symbols of channel c stored in the compact volume at d_sym + c * sym_stride (bytes).  The jobs and the list go up in
+// one copy while nothing of the call is queued yet; the verdict of the end checks comes before the caller queues anything
+// that writes its output, so a call that is refused for damage in a planned block leaves its output alone, as one that is
+// refused by the validation does.  Of the payloads only the block-length tables and the planned blocks are read.
+struct LaneStage {
+    DevBuf jobs;                 // (before w, as the caller's own buffers are before the LaneStage: w's destructor drains the
+    std::vector<uint8_t> up;     //  stream that reads them)
     SplitWork w;
-    TRY(split_work_alloc(w, 3, d.padded, h.lane_symbols, false, fmt));
-    split_chunk_jobs(w, 0, h, d_alc, dw.sym.as<uint8_t>(), dv.padded * sb);
-    for (int c = 0; c < 3; ++c) {
-        fj[(size_t)c].j = w.h[(size_t)c];
-        for (int r = 0; r < 2; ++r) {
-            fj[(size_t)c].blk_first[r] = p.blk_first[r]; fj[(size_t)c].blk_count[r] = p.blk_count[r];
-            fj[(size_t)c].sym_lo[r] = p.sym_lo[r]; fj[(size_t)c].sym_hi[r] = p.sym_hi[r];
+};
+
+int partial_lane_decode(LaneStage& ls, const SplitHeader& h, const ChunkDims& d, const PartialPlan& p, const uint8_t* d_alc, uint8_t* d_sym,
+                        size_t sym_stride, hipStream_t st) {
+    const bool wide = is_wide(h.fmt);
+    const size_t job_bytes = p.planes ? sizeof(SplitFramesJob) : sizeof(SplitBoxJob);
+    const size_t list_at = 3 * job_bytes, list_bytes = p.planes ? 0 : p.blocks.size() * sizeof(uint32_t);
+    const uint32_t n_planned = (uint32_t)p.blocks.size();
+    ls.up.resize(list_at + list_bytes);
+    TRY(ls.jobs.alloc(ls.up.size()));
+    TRY(split_work_alloc(ls.w, 3, d.padded, h.lane_symbols, false, h.fmt));
+    split_chunk_jobs(ls.w, 0, h, d_alc, d_sym, sym_stride);
+    for (size_t c = 0; c < 3; ++c) {
+        if (p.planes) {
+            SplitFramesJob j = p.ranges;
+            j.j = ls.w.h[c];
+            memcpy(ls.up.data() + c * job_bytes, &j, sizeof(j));
+        } else {
+            SplitBoxJob j = p.box;
+            j.j = ls.w.h[c];
+            j.blocks = (const uint32_t*)(ls.jobs.as<uint8_t>() + list_at); j.n_planned = n_planned;
+            memcpy(ls.up.data() + c * job_bytes, &j, sizeof(j));
         }
     }
-    if (transform_tiles_eligible(dv))
-        TRY(dw.scratch_own.alloc(inverse_scratch_bytes(dx, inverse_bounds(h.wavelet, h.step, wide ? kWideMaxQ : kByteMaxQ).mid16)));
-    // the uploads, the tables and the directory scan of every lane decode; the lane decode itself over the planned blocks
-    const std::function<int()> lane_decode = [&]() -> int {
-        HIP_TRY(hipMemcpyAsync(d_fj.p, fj.data(), fj.size() * sizeof(SplitFramesJob), hipMemcpyHostToDevice, st));
-        launch_split_frames_decode(d_fj.as<SplitFramesJob>(), 3, p.blocks(), wide, st);
+    memcpy(ls.up.data() + list_at, p.blocks.data(), list_bytes);
+    ls.w.st = st; ls.w.armed = true;
+    HIP_TRY(hipMemcpyAsync(ls.jobs.p, ls.up.data(), ls.up.size(), hipMemcpyHostToDevice, st));
+    const std::function<int()> lanes = [&]() -> int {
+        if (p.planes) launch_split_frames_decode(ls.jobs.as<SplitFramesJob>(), 3, n_planned, wide, st);
+        else launch_split_box_decode(ls.jobs.as<SplitBoxJob>(), 3, n_planned, wide, p.box.n_hi[0] || p.box.n_hi[1], st);
         return kOk;
     };
-    TRY(split_decode_launch(w, &h.freq[0][0], st, &lane_decode));
-    // The verdict of the end checks comes before anything is queued that writes d_rgb: a range that is refused for damage
-    // in a planned block leaves its output alone, as one that is refused by the validation does.
-    TRY(split_decode_verdict(w, st));
-    TRY(inverse_window(dw.sym.as<uint8_t>(), dv, first - p.a, first - p.a + count, h.wavelet, h.step, dw.scratch_own.p, dw,
-                       packed_rgb(d_rgb, dx), st, fmt));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-    tl_frames_stats[0] = p.a; tl_frames_stats[1] = p.b; tl_frames_stats[2] = 3ull * p.blocks();
-    tl_frames_stats[3] = uploaded; tl_frames_stats[4] = count;
-    return kOk;
+    TRY(split_decode_launch(ls.w, &h.freq[0][0], st, &lanes));
+    return split_decode_verdict(ls.w, st);
+}
+
+// The w x rh pixels at (x, y) of frames [first, first + count) of the container at d_alc (device; h, the range and the
+// rectangle validated, p their plan) to `out` (device; only the 3 w bytes of each of the rh rows of each frame are written).
+// The kept symbols, cut out in axis order, are the symbol volume of a virtual chunk of (xb - xa) x (yb - ya) x (tb - ta)
+// whose inverse equals the full chunk's at the rectangle shifted by (xa, ya, ta): the unchanged window inverse runs over it
+// and a copy kernel drops the halo.  Returns after the stream has drained.
+int rect_decode_device(PartialKind kind, const SplitHeader& h, const ChunkDims& d, const PartialPlan& p, const uint8_t* d_alc, uint32_t first,
+                       uint32_t count, uint32_t x, uint32_t y, uint32_t w, uint32_t rh, const RgbLayout& out, hipStream_t st, uint64_t uploaded) {
+    const bool wide = is_wide(h.fmt);
+    const size_t sb = wide ? 2 : 1;
+    // the virtual chunk: even on every axis unless it is the whole frame (no halo to drop), whose pad column and row are the
+    // chunk's own
+    const bool whole = x == 0 && y == 0 && w == h.width && rh == h.height;
+    const ChunkDims dv = make_dims(whole ? h.width : p.xb - p.xa, whole ? h.height : p.yb - p.ya, p.tb - p.ta);
+    const ChunkDims dx = make_dims(dv.w, dv.h, count);
+    DecodeWork dw;
+    dw.d = dv; dw.n_chunks = 1;
+    DevBuf d_tmp;
+    TRY(dw.sym.alloc(3 * dv.padded * sb));
+    if (!whole) TRY(d_tmp.alloc(3 * dx.n_pixels));
+    if (transform_tiles_eligible(dv))
+        TRY(dw.scratch_own.alloc(inverse_scratch_bytes(dx, inverse_bounds(h.wavelet, h.step, wide ? kWideMaxQ : kByteMaxQ).mid16)));
+    LaneStage ls;
+    TRY(partial_lane_decode(ls, h, d, p, d_alc, dw.sym.as<uint8_t>(), dv.padded * sb, st));
+    const RgbLayout full = whole ? out : packed_rgb(d_tmp.p, dx);
+    TRY(inverse_window(dw.sym.as<uint8_t>(), dv, first - p.ta, first - p.ta + count, h.wavelet, h.step, dw.scratch_own.p, dw, full, st, h.fmt));
+    if (!whole) launch_rgb_rect_paste(full, x - p.xa, y - p.ya, w, rh, count, out, st);
+    return partial_done(kind, p, count, uploaded, st);
 }
 
 }  // namespace
@@ -4989,13 +5031,14 @@ int alice_codec_frames_window(uint8_t wavelet_type, uint32_t frames, uint32_t fi
     if (count < 1 || (uint64_t)first + count > frames)
         return fail(kInvalidDimensions, "frames [" + std::to_string(first) + ", " + std::to_string((uint64_t)first + count) +
                                             ") are not a range of the chunk's " + std::to_string(frames) + " frames");
-    frames_window(wavelet_type, frames, first, count, a, b);
+    axis_window(frames_halo(wavelet_type), make_dims(1, 1, frames).pf, first, (uint64_t)first + count, a, b);
     return kOk;
 }
 
 int alice_codec_dev_decode_frames(const void* d_alc, uint64_t len, uint32_t first, uint32_t count, void* d_rgb_out, void* hip_stream) {
     return partial_decode_dev(d_alc, len, first, count, d_rgb_out, hip_stream, [&](const SplitHeader& h, const ChunkDims& d, hipStream_t st) {
-        return frames_decode_device(h, d, (const uint8_t*)d_alc, first, count, d_rgb_out, st, 0);
+        return rect_decode_device(kPartialFrames, h, d, frames_plan(h, d, first, count), (const uint8_t*)d_alc, first, count, 0, 0, h.width,
+                                  h.height, RgbLayout{(uint8_t*)d_rgb_out, 3ull * h.width, 3ull * h.width * h.height}, st, 0);
     });
 }
 
@@ -5006,46 +5049,51 @@ uint8_t* alice_codec_decode_frames(const uint8_t* data, uint64_t len, uint32_t f
     ChunkDims d{};
     uint8_t* out = nullptr;
     if (frames_validate(data, len, first, count, h, d) != kOk) return nullptr;
-    partial_decode_host(data, len, h, frames_plan(h, d, first, count).block_list(), (uint64_t)h.width * h.height * count * 3, &out, out_len,
+    const PartialPlan p = frames_plan(h, d, first, count);
+    partial_decode_host(data, len, h, p.blocks, (uint64_t)h.width * h.height * count * 3, &out, out_len,
                         [&](const uint8_t* d_alc, void* d_rgb, hipStream_t st, uint64_t uploaded) {
-                            return frames_decode_device(h, d, d_alc, first, count, d_rgb, st, uploaded);
+                            return rect_decode_device(kPartialFrames, h, d, p, d_alc, first, count, 0, 0, h.width, h.height,
+                                                      RgbLayout{(uint8_t*)d_rgb, 3ull * h.width, 3ull * h.width * h.height}, st, uploaded);
                         });
     return out;
 }
 
 void alice_codec_test_last_frames_stats(uint64_t out[5]) {
-    if (out) memcpy(out, tl_frames_stats, sizeof(tl_frames_stats));
+    const PartialStats& s = tl_partial_stats[kPartialFrames];
+    const uint64_t v[5] = {s.ta, s.tb, s.blocks, s.uploaded, s.frames};
+    if (out) memcpy(out, v, sizeof(v));
 }
 
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------
 // PART 9: half-resolution preview of a version 2, 3 or 4 chunk from the low band alone (kernels:
-// split_preview_decode_kernel of split.hip, preview_inv_kernel of transform.hip)
+// split_box_decode_kernel of split.hip, preview_inv_kernel of transform.hip)
 //
-// The spatial transform is one lifting level, so the low-low quadrant [0, ph/2) x [0, pw/2) of every coefficient plane is a
-// half-size picture.  A frame range needs the quadrants of PART 8's window [a, b) (the temporal lifting runs per (y, x), so
-// the window rule carries over to a sub-rectangle of the planes); the top half of a plane is one contiguous symbol run, so
-// the blocks of the bottom half are never entropy-decoded, and no spatial inverse runs at all.
+// The low-low quadrant [0, ph/2) x [0, pw/2) of every coefficient plane is a half-size picture.  A frame range needs the
+// quadrants of its window [a, b) (the temporal lifting runs per (y, x), so the window rule carries over to a sub-rectangle of
+// the planes): a box with both runs on t' and the low run alone on x and y.  The top half of a plane is one contiguous symbol
+// run, so the blocks of the bottom half are never entropy-decoded, and no spatial inverse runs at all.
 // ------------------------------------------------------------------------------------------
 
 namespace {
 
-struct PreviewPlan {
-    uint32_t a = 0, b = 0;
-    uint64_t qw = 0, qh = 0, pitch = 0;       // quadrant, and the plane pitch of the compact volume (qw * qh rounded up to 4)
-    std::vector<uint32_t> blocks;             // ascending, no duplicates; the three channels are alike
-};
-
 // the union, over the window's planes t', of the blocks that intersect [t' P, t' P + (qh - 1) pw + qw)
-PreviewPlan preview_plan(const SplitHeader& h, const ChunkDims& d, uint32_t first, uint32_t count) {
-    PreviewPlan p;
-    frames_window(h.wavelet, h.frames, first, count, &p.a, &p.b);
-    p.qw = d.pw / 2; p.qh = d.ph / 2;
-    p.pitch = round_up(p.qw * p.qh, 4);
-    const uint64_t P = d.pw * d.ph, half = d.pf / 2, B = 64ull * h.lane_symbols, run = (p.qh - 1) * d.pw + p.qw;
+PartialPlan preview_plan(const SplitHeader& h, const ChunkDims& d, uint32_t first, uint32_t count) {
+    PartialPlan p;
+    axis_window(frames_halo(h.wavelet), d.pf, first, (uint64_t)first + count, &p.ta, &p.tb);
+    p.xb = (uint32_t)d.pw; p.yb = (uint32_t)d.ph;
+    const uint64_t qw = d.pw / 2, qh = d.ph / 2;
+    SplitBoxJob& bx = p.box;
+    bx.pw = (uint32_t)d.pw; bx.ph = (uint32_t)d.ph;
+    bx.half[0] = (uint32_t)qw; bx.n_lo[0] = (uint32_t)qw;
+    bx.half[1] = (uint32_t)qh; bx.n_lo[1] = (uint32_t)qh;
+    bx.lo[2] = p.ta / 2; bx.half[2] = (uint32_t)(d.pf / 2); bx.n_lo[2] = bx.n_hi[2] = (p.tb - p.ta) / 2;
+    bx.pitch = round_up(qw * qh, 4);          // the plane pitch of the compact volume
+    p.stored = (p.tb - p.ta) * qw * qh;
+    const uint64_t P = d.pw * d.ph, half = d.pf / 2, B = 64ull * h.lane_symbols, run = (qh - 1) * d.pw + qw;
     for (int band = 0; band < 2; ++band)
-        for (uint64_t t = p.a / 2; t < p.b / 2; ++t) {
+        for (uint64_t t = p.ta / 2; t < p.tb / 2; ++t) {
             const uint64_t lo = (band * half + t) * P, hi = lo + run;
             for (uint64_t blk = lo / B; blk <= (hi - 1) / B; ++blk)
                 if (p.blocks.empty() || blk > p.blocks.back()) p.blocks.push_back((uint32_t)blk);
@@ -5053,59 +5101,26 @@ PreviewPlan preview_plan(const SplitHeader& h, const ChunkDims& d, uint32_t firs
     return p;
 }
 
-thread_local uint64_t tl_preview_stats[6] = {0, 0, 0, 0, 0, 0};   // alice_codec_test_last_preview_stats
-
 // The preview of frames [first, first + count) of the container at d_alc (device, h validated) to d_rgb (device,
-// count * qh * qw * 3 bytes).  Of the payloads only the block-length tables and the planned blocks are read.  Returns after
-// the stream has drained.
-int preview_decode_device(const SplitHeader& h, const ChunkDims& d, const PreviewPlan& p, const uint8_t* d_alc, uint32_t first,
+// count * qh * qw * 3 bytes).  Returns after the stream has drained.
+int preview_decode_device(const SplitHeader& h, const ChunkDims& d, const PartialPlan& p, const uint8_t* d_alc, uint32_t first,
                           uint32_t count, void* d_rgb, hipStream_t st, uint64_t uploaded) {
-    const SplitFormat fmt = h.fmt;
-    const bool wide = is_wide(fmt);
+    const bool wide = is_wide(h.fmt);
     const size_t sb = wide ? 2 : 1;
-    const uint32_t planes = p.b - p.a;
-    DevBuf d_sym, d_pj;                      // (declared before w: w's destructor drains the stream that reads them)
-    std::vector<SplitPreviewJob> pj(3);
-    // one upload: the three jobs, then the block list they share
-    const size_t jobs_bytes = 3 * sizeof(SplitPreviewJob), list_bytes = p.blocks.size() * sizeof(uint32_t);
-    std::vector<uint8_t> up(jobs_bytes + list_bytes);
+    const uint32_t planes = p.tb - p.ta;
+    const uint64_t pitch = p.box.pitch, quadrant = (uint64_t)p.box.n_lo[0] * p.box.n_lo[1];
     // the pad symbols of a plane (pitch - qw * qh < 4) are never stored; the finish loads them with a group's real ones
     // and drops what it computes from them, so they need no value
-    TRY(d_sym.alloc(3 * (size_t)planes * p.pitch * sb));
-    TRY(d_pj.alloc(up.size()));
-    SplitWork w;
-    TRY(split_work_alloc(w, 3, d.padded, h.lane_symbols, false, fmt));
-    split_chunk_jobs(w, 0, h, d_alc, d_sym.as<uint8_t>(), (size_t)planes * p.pitch * sb);
-    for (int c = 0; c < 3; ++c) {
-        SplitPreviewJob& j = pj[(size_t)c];
-        j.j = w.h[(size_t)c];
-        j.blocks = (const uint32_t*)(d_pj.as<uint8_t>() + jobs_bytes); j.n_planned = (uint32_t)p.blocks.size();
-        j.pw = (uint32_t)d.pw; j.ph = (uint32_t)d.ph; j.qw = (uint32_t)p.qw; j.qh = (uint32_t)p.qh;
-        j.t_lo = p.a / 2; j.half = (uint32_t)(d.pf / 2); j.hw = planes / 2;
-        j.pitch = p.pitch;
-    }
-    // the jobs and the list go up first, while nothing of this call is queued yet
-    memcpy(up.data(), pj.data(), jobs_bytes);
-    memcpy(up.data() + jobs_bytes, p.blocks.data(), list_bytes);
-    w.st = st; w.armed = true;
-    HIP_TRY(hipMemcpyAsync(d_pj.p, up.data(), up.size(), hipMemcpyHostToDevice, st));
-    const std::function<int()> lane_decode = [&]() -> int {
-        launch_split_preview_decode(d_pj.as<SplitPreviewJob>(), 3, (uint32_t)p.blocks.size(), wide, st);
-        return kOk;
-    };
-    TRY(split_decode_launch(w, &h.freq[0][0], st, &lane_decode));
-    // as in PART 8: the verdict of the end checks comes before anything is queued that writes d_rgb
-    TRY(split_decode_verdict(w, st));
+    DevBuf d_sym;
+    TRY(d_sym.alloc(3 * (size_t)planes * pitch * sb));
+    LaneStage ls;
+    TRY(partial_lane_decode(ls, h, d, p, d_alc, d_sym.as<uint8_t>(), (size_t)planes * pitch * sb, st));
     // EXACT is the full chunk's verdict: the first pass inverse_bounds looks at is the temporal one
     const InverseBounds ib = inverse_bounds(h.wavelet, h.step, wide ? kWideMaxQ : kByteMaxQ);
-    if (!launch_preview_inverse(d_sym.p, p.pitch, p.qw * p.qh, planes, FrameWindow{first - p.a, first - p.a + count}, (int)fmt, h.wavelet,
+    if (!launch_preview_inverse(d_sym.p, pitch, quadrant, planes, FrameWindow{first - p.ta, first - p.ta + count}, (int)h.fmt, h.wavelet,
                                 h.step, ib.exact, (uint8_t*)d_rgb, st))
         return fail(kInternal, "preview: no finish kernel for this volume");
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-    tl_preview_stats[0] = p.a; tl_preview_stats[1] = p.b; tl_preview_stats[2] = 3ull * p.blocks.size();
-    tl_preview_stats[3] = uploaded; tl_preview_stats[4] = count; tl_preview_stats[5] = 3ull * planes * p.qw * p.qh;
-    return kOk;
+    return partial_done(kPartialPreview, p, count, uploaded, st);
 }
 
 }  // namespace
@@ -5133,9 +5148,9 @@ uint8_t* alice_codec_decode_preview(const uint8_t* data, uint64_t len, uint32_t 
     SplitHeader h;
     ChunkDims d{};
     if (frames_validate(data, len, first, count, h, d) != kOk) return nullptr;
-    const PreviewPlan p = preview_plan(h, d, first, count);
+    const PartialPlan p = preview_plan(h, d, first, count);
     uint8_t* out = nullptr;
-    partial_decode_host(data, len, h, p.blocks, p.qw * p.qh * count * 3, &out, out_len,
+    partial_decode_host(data, len, h, p.blocks, (uint64_t)p.box.n_lo[0] * p.box.n_lo[1] * count * 3, &out, out_len,
                         [&](const uint8_t* d_alc, void* d_rgb, hipStream_t st, uint64_t uploaded) {
                             return preview_decode_device(h, d, p, d_alc, first, count, d_rgb, st, uploaded);
                         });
@@ -5143,54 +5158,43 @@ uint8_t* alice_codec_decode_preview(const uint8_t* data, uint64_t len, uint32_t 
 }
 
 void alice_codec_test_last_preview_stats(uint64_t out[6]) {
-    if (out) memcpy(out, tl_preview_stats, sizeof(tl_preview_stats));
+    const PartialStats& s = tl_partial_stats[kPartialPreview];
+    const uint64_t v[6] = {s.ta, s.tb, s.blocks, s.uploaded, s.frames, s.stored};
+    if (out) memcpy(out, v, sizeof(v));
 }
 
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------
 // PART 10: a spatial rectangle of a frame range of a version 2, 3 or 4 chunk (kernels:
-// split_rect_decode_kernel of split.hip, rgb_rect_paste_kernel of generic.hip)
+// split_box_decode_kernel of split.hip, rgb_rect_paste_kernel of generic.hip)
 //
-// The spatial transform is one lifting level per axis too, and every axis of a channel's [t'][y][x] symbol volume is
-// deinterleaved into [low | high], so PART 8's window rule holds on x and on y as it holds on t: the pixels of
-// [t0, t1) x [y0, y1) x [x0, x1) depend on the coefficients whose coordinate lies, on every axis, in the low or the high run
-// of that axis's window.  Cut out in that order they are the symbol volume of a virtual chunk of (xb - xa) x (yb - ya) x
-// (tb - ta), all even, whose inverse equals the full chunk's at the rectangle shifted by (xa, ya, ta).  The lane decode runs
-// over the blocks that hold a kept symbol, the unchanged window inverse over the virtual chunk, and a copy kernel drops the
-// halo.  The end checks cover the blocks that are read.
+// The window rule holds on x and on y as it holds on t: the pixels of [t0, t1) x [y0, y1) x [x0, x1) depend on the
+// coefficients whose coordinate lies, on every axis, in the low or the high run of that axis's window -- a box with both runs
+// on every axis.  The body is PART 8's rect_decode_device.
 // ------------------------------------------------------------------------------------------
 
 namespace {
 
-// PART 8's rule for an axis of padded length pn and the real positions [c0, c1), c0 < c1 <= pn
-void axis_window(uint64_t ns, uint64_t pn, uint64_t c0, uint64_t c1, uint32_t* a, uint32_t* b) {
-    *a = c0 > ns ? (uint32_t)((c0 - ns) & ~1ull) : 0u;
-    *b = (uint32_t)std::min<uint64_t>(pn, (c1 + ns + 1) & ~1ull);
-}
-
-struct RectPlan {
-    uint32_t ta = 0, tb = 0, xa = 0, xb = 0, ya = 0, yb = 0;
-    bool whole = false;                       // the rectangle is the frame: no halo to drop
-    uint64_t stored = 0;                      // symbols of a channel's virtual chunk
-    std::vector<uint32_t> blocks;             // ascending, no duplicates; the three channels are alike
-};
-
 // the blocks that intersect an x run of a kept row of a planned plane: planes, rows and runs in ascending position order
-RectPlan rect_plan(const SplitHeader& h, const ChunkDims& d, uint32_t first, uint32_t count, uint32_t x, uint32_t y, uint32_t w, uint32_t rh) {
-    RectPlan p;
+PartialPlan rect_plan(const SplitHeader& h, const ChunkDims& d, uint32_t first, uint32_t count, uint32_t x, uint32_t y, uint32_t w, uint32_t rh) {
+    PartialPlan p;
     const uint64_t ns = frames_halo(h.wavelet);
-    frames_window(h.wavelet, h.frames, first, count, &p.ta, &p.tb);
+    axis_window(ns, d.pf, first, (uint64_t)first + count, &p.ta, &p.tb);
     axis_window(ns, d.pw, x, (uint64_t)x + w, &p.xa, &p.xb);
     axis_window(ns, d.ph, y, (uint64_t)y + rh, &p.ya, &p.yb);
-    p.whole = x == 0 && y == 0 && w == h.width && rh == h.height;
-    p.stored = (uint64_t)(p.tb - p.ta) * (p.yb - p.ya) * (p.xb - p.xa);
     const uint64_t B = 64ull * h.lane_symbols, hx = d.pw / 2, hy = d.ph / 2, ht = d.pf / 2;
     const bool merged = p.xa == 0 && p.xb == d.pw;
-    if (merged && p.ya == 0 && p.yb == d.ph) {   // whole planes: PART 8's plan
-        p.blocks = frames_plan(h, d, first, count).block_list();
-        return p;
-    }
+    // both spatial windows are the whole axis: the kept symbols are whole coefficient planes, in plane order (PART 8's plan,
+    // whose lane kernel stores with two compares)
+    if (merged && p.ya == 0 && p.yb == d.ph) return frames_plan(h, d, first, count);
+    p.stored = (uint64_t)(p.tb - p.ta) * (p.yb - p.ya) * (p.xb - p.xa);
+    SplitBoxJob& bx = p.box;
+    bx.pw = (uint32_t)d.pw; bx.ph = (uint32_t)d.ph;
+    bx.lo[0] = p.xa / 2; bx.half[0] = (uint32_t)hx; bx.n_lo[0] = bx.n_hi[0] = (p.xb - p.xa) / 2;
+    bx.lo[1] = p.ya / 2; bx.half[1] = (uint32_t)hy; bx.n_lo[1] = bx.n_hi[1] = (p.yb - p.ya) / 2;
+    bx.lo[2] = p.ta / 2; bx.half[2] = (uint32_t)ht; bx.n_lo[2] = bx.n_hi[2] = (p.tb - p.ta) / 2;
+    bx.pitch = (uint64_t)(p.yb - p.ya) * (p.xb - p.xa);
     // `covered`: where the last listed block ends.  A run that ends at or before it adds nothing, which is what most rows
     // find (a block holds many rows), so the divisions are paid once per new block and not once per row.
     uint64_t covered = 0;
@@ -5223,86 +5227,6 @@ int rect_validate(const SplitHeader& h, uint32_t x, uint32_t y, uint32_t w, uint
         return fail(kInvalidDimensions, "rectangle " + std::to_string(w) + "x" + std::to_string(rh) + " at (" + std::to_string(x) + ", " +
                                             std::to_string(y) + ") does not lie inside the " + std::to_string(h.width) + "x" +
                                             std::to_string(h.height) + " frame");
-    return kOk;
-}
-
-thread_local uint64_t tl_rect_stats[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // alice_codec_test_last_rect_stats
-
-// The w x rh pixels at (x, y) of frames [first, first + count) of the container at d_alc (device, h and the rectangle
-// validated) to `out` (device; only the 3 w bytes of each of the rh rows of each frame are written).  Of the payloads only
-// the block-length tables and the planned blocks are read.  Returns after the stream has drained.
-int rect_decode_device(const SplitHeader& h, const ChunkDims& d, const RectPlan& p, const uint8_t* d_alc, uint32_t first, uint32_t count,
-                       uint32_t x, uint32_t y, uint32_t w, uint32_t rh, const RgbLayout& out, hipStream_t st, uint64_t uploaded) {
-    const SplitFormat fmt = h.fmt;
-    const bool wide = is_wide(fmt);
-    const size_t sb = wide ? 2 : 1;
-    // the virtual chunk: even on every axis unless it is the whole frame, whose pad column and row are the chunk's own
-    const uint32_t vw = p.whole ? h.width : p.xb - p.xa, vh = p.whole ? h.height : p.yb - p.ya;
-    const ChunkDims dv = make_dims(vw, vh, p.tb - p.ta);
-    const ChunkDims dx = make_dims(vw, vh, count);
-    DecodeWork dw;
-    dw.d = dv; dw.n_chunks = 1;
-    TRY(dw.sym.alloc(3 * dv.padded * sb));
-    // When both spatial windows are the whole axis the kept symbols are whole coefficient planes, in plane order: PART 8's
-    // symbol ranges and its lane kernel (whose store is two compares), with the same blocks and the same compact volume.
-    const bool planes = p.xa == 0 && p.xb == d.pw && p.ya == 0 && p.yb == d.ph;
-    const FramesPlan fp = frames_plan(h, d, first, count);
-    DevBuf d_rj, d_tmp;                      // (declared before w: w's destructor drains the stream that reads them)
-    // one upload: the three jobs, then (rectangle jobs) the block list they share
-    const size_t jobs_bytes = 3 * (planes ? sizeof(SplitFramesJob) : sizeof(SplitRectJob));
-    const size_t list_bytes = planes ? 0 : p.blocks.size() * sizeof(uint32_t);
-    std::vector<uint8_t> up(jobs_bytes + list_bytes);
-    TRY(d_rj.alloc(up.size()));
-    if (!p.whole) TRY(d_tmp.alloc(3 * dx.n_pixels));
-    SplitWork sw;
-    TRY(split_work_alloc(sw, 3, d.padded, h.lane_symbols, false, fmt));
-    split_chunk_jobs(sw, 0, h, d_alc, dw.sym.as<uint8_t>(), dv.padded * sb);
-    for (int c = 0; c < 3; ++c) {
-        if (planes) {
-            SplitFramesJob j{};
-            j.j = sw.h[(size_t)c];
-            for (int r = 0; r < 2; ++r) {
-                j.blk_first[r] = fp.blk_first[r]; j.blk_count[r] = fp.blk_count[r];
-                j.sym_lo[r] = fp.sym_lo[r]; j.sym_hi[r] = fp.sym_hi[r];
-            }
-            memcpy(up.data() + (size_t)c * sizeof(j), &j, sizeof(j));
-        } else {
-            SplitRectJob j{};
-            j.j = sw.h[(size_t)c];
-            j.blocks = (const uint32_t*)(d_rj.as<uint8_t>() + jobs_bytes); j.n_planned = (uint32_t)p.blocks.size();
-            j.pw = (uint32_t)d.pw; j.ph = (uint32_t)d.ph;
-            j.lo[0] = p.xa / 2; j.hl[0] = (p.xb - p.xa) / 2; j.half[0] = (uint32_t)(d.pw / 2);
-            j.lo[1] = p.ya / 2; j.hl[1] = (p.yb - p.ya) / 2; j.half[1] = (uint32_t)(d.ph / 2);
-            j.lo[2] = p.ta / 2; j.hl[2] = (p.tb - p.ta) / 2; j.half[2] = (uint32_t)(d.pf / 2);
-            memcpy(up.data() + (size_t)c * sizeof(j), &j, sizeof(j));
-        }
-    }
-    if (transform_tiles_eligible(dv))
-        TRY(dw.scratch_own.alloc(inverse_scratch_bytes(dx, inverse_bounds(h.wavelet, h.step, wide ? kWideMaxQ : kByteMaxQ).mid16)));
-    // the jobs and the list go up first, while nothing of this call is queued yet
-    memcpy(up.data() + jobs_bytes, p.blocks.data(), list_bytes);
-    sw.st = st; sw.armed = true;
-    HIP_TRY(hipMemcpyAsync(d_rj.p, up.data(), up.size(), hipMemcpyHostToDevice, st));
-    const std::function<int()> lane_decode = [&]() -> int {
-        if (planes) launch_split_frames_decode(d_rj.as<SplitFramesJob>(), 3, fp.blocks(), wide, st);
-        else launch_split_rect_decode(d_rj.as<SplitRectJob>(), 3, (uint32_t)p.blocks.size(), wide, st);
-        return kOk;
-    };
-    TRY(split_decode_launch(sw, &h.freq[0][0], st, &lane_decode));
-    // as in PART 8: the verdict of the end checks comes before anything is queued that writes `out`
-    TRY(split_decode_verdict(sw, st));
-    const uint32_t lo = first - p.ta;
-    if (p.whole) {
-        TRY(inverse_window(dw.sym.as<uint8_t>(), dv, lo, lo + count, h.wavelet, h.step, dw.scratch_own.p, dw, out, st, fmt));
-    } else {
-        const RgbLayout tmp = packed_rgb(d_tmp.p, dx);
-        TRY(inverse_window(dw.sym.as<uint8_t>(), dv, lo, lo + count, h.wavelet, h.step, dw.scratch_own.p, dw, tmp, st, fmt));
-        launch_rgb_rect_paste(tmp, x - p.xa, y - p.ya, w, rh, count, out, st);
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-    const uint64_t stats[10] = {p.ta, p.tb, p.xa, p.xb, p.ya, p.yb, 3ull * p.blocks.size(), uploaded, count, 3ull * p.stored};
-    memcpy(tl_rect_stats, stats, sizeof(stats));
     return kOk;
 }
 
@@ -5339,8 +5263,8 @@ int alice_codec_dev_decode_rect(const void* d_alc, uint64_t len, uint32_t first,
                                                     std::to_string(h) + " rows");
             out.row_pitch = rp; out.frame_pitch = fp;
         }
-        return rect_decode_device(hd, d, rect_plan(hd, d, first, count, x, y, w, h), (const uint8_t*)d_alc, first, count, x, y, w, h, out,
-                                  st, 0);
+        return rect_decode_device(kPartialRect, hd, d, rect_plan(hd, d, first, count, x, y, w, h), (const uint8_t*)d_alc, first, count, x, y, w, h,
+                                  out, st, 0);
     });
 }
 
@@ -5351,18 +5275,20 @@ uint8_t* alice_codec_decode_rect(const uint8_t* data, uint64_t len, uint32_t fir
     SplitHeader hd;
     ChunkDims d{};
     if (frames_validate(data, len, first, count, hd, d) != kOk || rect_validate(hd, x, y, w, h) != kOk) return nullptr;
-    const RectPlan p = rect_plan(hd, d, first, count, x, y, w, h);
+    const PartialPlan p = rect_plan(hd, d, first, count, x, y, w, h);
     uint8_t* out = nullptr;
     partial_decode_host(data, len, hd, p.blocks, 3ull * w * h * count, &out, out_len,
                         [&](const uint8_t* d_alc, void* d_rgb, hipStream_t st, uint64_t uploaded) {
-                            return rect_decode_device(hd, d, p, d_alc, first, count, x, y, w, h,
+                            return rect_decode_device(kPartialRect, hd, d, p, d_alc, first, count, x, y, w, h,
                                                       RgbLayout{(uint8_t*)d_rgb, 3ull * w, 3ull * w * h}, st, uploaded);
                         });
     return out;
 }
 
 void alice_codec_test_last_rect_stats(uint64_t out[10]) {
-    if (out) memcpy(out, tl_rect_stats, sizeof(tl_rect_stats));
+    const PartialStats& s = tl_partial_stats[kPartialRect];
+    const uint64_t v[10] = {s.ta, s.tb, s.xa, s.xb, s.ya, s.yb, s.blocks, s.uploaded, s.frames, s.stored};
+    if (out) memcpy(out, v, sizeof(v));
 }
 
 }  // extern "C"

@@ -340,29 +340,21 @@ struct SplitFramesJob {
     uint32_t blk_first[2], blk_count[2];
     unsigned long long sym_lo[2], sym_hi[2];
 };
-// Half-resolution preview: the n_planned blocks blocks[0 .. n_planned) of channel `j` (ascending, no
-// duplicates) are decoded.  A symbol at channel position p = (t' * ph + y) * pw + x is stored only when t' lies in
-// [t_lo, t_lo + hw) (low band, plane t' - t_lo of the compact volume) or in [half + t_lo, half + t_lo + hw) (high band,
-// plane hw + ...), y < qh and x < qw: at j.sym[plane * pitch + y * qw + x].  pitch >= qw * qh.
-struct SplitPreviewJob {
-    SplitJob j;
-    const uint32_t* blocks;
-    uint32_t n_planned;
-    uint32_t pw, ph, qw, qh;
-    uint32_t t_lo, half, hw;
-    unsigned long long pitch;
-};
-// Spatial rectangle of a frame range: the n_planned blocks blocks[0 .. n_planned) of channel `j`
-// (ascending, no duplicates) are decoded.  Axis k (0 = x of pw, 1 = y of ph, 2 = t' of 2 * half[2]) keeps the coordinates
-// [lo[k], lo[k] + hl[k]) (low run, place c - lo[k] of the virtual chunk) and [half[k] + lo[k], half[k] + lo[k] + hl[k])
-// (high run, place hl[k] + ...).  A symbol at channel position (t' * ph + y) * pw + x is stored only when all three
-// coordinates are kept: at j.sym[(vt * 2 hl[1] + vy) * 2 hl[0] + vx], the [2 hl[2]][2 hl[1]][2 hl[0]] volume of the virtual chunk.
-struct SplitRectJob {
+// A box of a channel's [t'][ph][pw] symbol volume (preview and rectangle, DESIGN.md sections 15 and 16): the n_planned
+// blocks blocks[0 .. n_planned) of channel `j` (ascending, no duplicates) are decoded.  Axis k (0 = x, 1 = y, 2 = t') keeps the
+// coordinates [lo[k], lo[k] + n_lo[k]) (low run, place c - lo[k]) and [half[k] + lo[k], half[k] + lo[k] + n_hi[k]) (high run,
+// place n_lo[k] + ...); n_hi[k] is n_lo[k] when both bands are kept and 0 when only the low band is.  A symbol at channel
+// position (t' * ph + y) * pw + x is stored only when all three coordinates are kept: at j.sym[vt * pitch + vy * (n_lo[0] +
+// n_hi[0]) + vx], v* the places.  pitch >= the rows times the row extent; the channel's compact volume is (n_lo[2] + n_hi[2]) *
+// pitch symbols.  The rectangle keeps both runs of every axis, pitch = rows * row extent (the virtual chunk); the preview keeps
+// both runs of t' only, lo = 0 on x and y, and pitch = qw * qh rounded up to 4.
+struct SplitBoxJob {
     SplitJob j;
     const uint32_t* blocks;
     uint32_t n_planned;
     uint32_t pw, ph;
-    uint32_t lo[3], hl[3], half[3];
+    uint32_t lo[3], half[3], n_lo[3], n_hi[3];
+    unsigned long long pitch;
 };
 struct SplitHeaderDesc {
     uint8_t* out;
@@ -386,10 +378,9 @@ void launch_split_decode(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks
 void launch_split_headers(const SplitHeaderDesc* d_descs, int n_chunks, hipStream_t st);
 // after scan(from_stream = true) over the same channels; max_blocks: the largest blk_count[0] + blk_count[1] among the jobs
 void launch_split_frames_decode(const SplitFramesJob* d_jobs, int n_jobs, uint32_t max_blocks, bool wide, hipStream_t st);
-// after scan(from_stream = true) over the same channels; max_planned: the largest n_planned among the jobs
-void launch_split_preview_decode(const SplitPreviewJob* d_jobs, int n_jobs, uint32_t max_planned, bool wide, hipStream_t st);
-// after scan(from_stream = true) over the same channels; max_planned: the largest n_planned among the jobs
-void launch_split_rect_decode(const SplitRectJob* d_jobs, int n_jobs, uint32_t max_planned, bool wide, hipStream_t st);
+// after scan(from_stream = true) over the same channels; max_planned: the largest n_planned among the jobs; xy_high: a job
+// has a high run on x or y (false: the instance without them, which stores nothing of such runs)
+void launch_split_box_decode(const SplitBoxJob* d_jobs, int n_jobs, uint32_t max_planned, bool wide, bool xy_high, hipStream_t st);
 // overwrites the version byte of the headers launch_split_headers wrote (same stream, after it)
 void launch_split_header_version(const SplitHeaderDesc* d_descs, int n_chunks, uint8_t version, hipStream_t st);
 

@@ -16,8 +16,7 @@
 //   split_scan_kernel     block lengths -> block offsets (encode: from the count pass; decode: from the stream, validated)
 //   split_decode_kernel / split_wide_decode_kernel   every block; symbol i at the lane's own position
 //   split_frames_decode_kernel<WIDE>    the blocks a frame range needs, stored as a compact volume
-//   split_preview_decode_kernel<WIDE>   the blocks a half-resolution preview needs: low-low quadrants only
-//   split_rect_decode_kernel<WIDE>      the blocks a spatial rectangle of a frame range needs: the kept runs of three axes
+//   split_box_decode_kernel<WIDE, XY_HIGH>   the blocks a preview or a spatial rectangle needs: the kept runs of three axes
 //   split_header_kernel / split_version_kernel   the 1630-byte container header of whole chunks
 // The output is sized by counting first and writing second: the chain arithmetic runs twice, but nothing is staged in
 // worst-case slots (2 bytes per symbol) and no compaction pass moves the payload again.
@@ -468,106 +467,57 @@ __global__ __launch_bounds__(256) void split_frames_decode_kernel(const SplitFra
 }
 
 // ----------------------------------------------------------------------------------
-// Lane decode for the half-resolution preview: the blocks a SplitPreviewJob lists (slot -> block
-// through the list).  Every chain runs to its end check; a symbol is stored only when its plane lies in the low or the
-// high window and its (y, x) in the low-low quadrant, relocated into the compact volume [plane][pitch] at job.j.sym.  A
-// lane's positions advance by 64 = dP * P + dy * pw + dx (dy * pw + dx < P), so (x, y, t') are carried with three adds and
-// at most one wrap each -- also for pw = 2 and P < 64 (then dP >= 1).  The 64-bit divisions happen once per lane, before
-// the chain loop; the coordinates do not depend on the chain's state, so the serial dependency is lane_decode's own.
+// Lane decode of a box (half-resolution preview and spatial rectangle, DESIGN.md sections 15 and 16): the blocks a
+// SplitBoxJob lists (slot -> block through the list).  Every chain runs to its end check; a symbol is stored only when each
+// of (x, y, t') lies in the low or the high run of its axis, relocated into the compact volume at job.j.sym.  A lane's
+// positions advance by 64 = dP * P + dy * pw + dx (dy * pw + dx < P), so (x, y, t') are carried with three adds and at most
+// one wrap each -- also for pw = 2 and P < 64 (then dP >= 1).  The 64-bit divisions happen once per lane, before the chain
+// loop; the box is wave-uniform, the coordinates and the destination (two multiplies) do not depend on the chain's state, so
+// the serial dependency is lane_decode's own.
+// XY_HIGH = false is the instance for jobs that keep the low run alone on x and y (n_hi[0] = n_hi[1] = 0, the preview): the
+// two high-run compares and selects are not compiled in.  A partial call runs about one wavefront per SIMD, so every
+// instruction of the store rule is paid in full: with the compares left in, the preview's launches measured 337.4 -> 344.8
+// us (u8) and 540.8 -> 550.5 us (u16), +2.2 and +1.8 % against a spread of 1.1 and 0.7 % (six rounds, one 1920x1080x64
+// chunk); carrying the destination additively instead of multiplying measured +1.0 to +8.6 % in all four roles.  On this
+// form the preview's launches are level or faster than the kernel they replace (326.3 and 538.4 us) and the rectangle's level
+// (profiles/r21_box_kernel_trace_vs_parent.json).
 // ----------------------------------------------------------------------------------
-template <bool WIDE>
-__global__ __launch_bounds__(256) void split_preview_decode_kernel(const SplitPreviewJob* __restrict__ jobs) {
+template <bool WIDE, bool XY_HIGH>
+__global__ __launch_bounds__(256) void split_box_decode_kernel(const SplitBoxJob* __restrict__ jobs) {
     using SymT = SplitSym<WIDE>;
     __shared__ uint32_t c2s_sh[kProbScale / 4];
     __shared__ uint32_t symtab[256];
-    const SplitPreviewJob pj = jobs[blockIdx.y];
-    const SplitJob& job = pj.j;
+    const SplitBoxJob bj = jobs[blockIdx.y];
+    const SplitJob& job = bj.j;
     load_decode_tables(job.table, c2s_sh, symtab);
     const int lane = threadIdx.x & 63;
     const unsigned long long slot = (unsigned long long)blockIdx.x * 4u + (threadIdx.x >> 6);
-    if (slot >= pj.n_planned) return;
-    const unsigned long long b = pj.blocks[slot];
-    if (b >= job.n_blocks || !pj.pw || !pj.ph) return;   // (the host plans inside the channel; the bounds of lane_decode do not rest on it)
+    if (slot >= bj.n_planned) return;
+    const unsigned long long b = bj.blocks[slot];
+    if (b >= job.n_blocks || !bj.pw || !bj.ph) return;   // (the host plans inside the channel; the bounds of lane_decode do not rest on it)
     const LaneGeometry g(job, b, lane);
 
     // where the lane's first symbol lies, and what 64 positions further means
-    const uint32_t pw = pj.pw, ph = pj.ph, qw = pj.qw, qh = pj.qh, hw = pj.hw;
+    const uint32_t pw = bj.pw, ph = bj.ph;
     const unsigned long long P = (unsigned long long)pw * ph;
     const unsigned long long p0 = g.base + (unsigned)lane;
     const unsigned long long rem0 = p0 % P, step_rem = 64ull % P;
     uint32_t tp = (uint32_t)(p0 / P), y = (uint32_t)(rem0 / pw), x = (uint32_t)(rem0 % pw);
     const uint32_t dP = (uint32_t)(64ull / P), dy = (uint32_t)(step_rem / pw), dx = (uint32_t)(step_rem % pw);   // dy, dx < 64
-    const uint32_t t_hi = pj.half + pj.t_lo;
-    SymT* __restrict__ out = (SymT*)job.sym;
-    // off = (t' - t_lo) * pitch + y * qw + x is carried beside (x, y, t'), so the loop has no multiply: it is the symbol's
-    // place in the compact volume while t' lies in the low window, and off + high_off while it lies in the high one
-    const long long pitch = (long long)pj.pitch;
-    long long off = ((long long)tp - (long long)pj.t_lo) * pitch + (long long)y * qw + x;
-    const long long step_off = (long long)dP * pitch + (long long)dy * qw + dx;   // 64 positions on, nothing wraps
-    const long long xwrap_off = (long long)qw - (long long)pw;                    // x -= pw, ++y
-    const long long ywrap_off = pitch - (long long)ph * qw;                       // y -= ph, ++t'
-    const long long high_off = ((long long)hw - (long long)pj.half) * pitch;
-    const unsigned long long limit = 2ull * hw * pj.pitch;                        // symbols of the channel's compact volume
-    lane_decode<WIDE>(job, b, lane, g.k, (const uint8_t*)c2s_sh, symtab, [&](uint32_t, uint32_t s) {
-        // plane < 2 hw, y < qh and x < qw: the index is plane * pitch + y * qw + x, inside the channel's 2 hw * pitch
-        // symbols (pitch >= qw * qh); the compare with `limit` keeps the store there whatever the carried sum holds
-        const uint32_t u0 = tp - pj.t_lo, u1 = tp - t_hi;
-        if ((u0 < hw || u1 < hw) && y < qh && x < qw) {
-            const unsigned long long at = (unsigned long long)(off + (u0 < hw ? 0ll : high_off));
-            if (at < limit) out[at] = (SymT)s;
-        }
-        x += dx; off += step_off;
-        if (x >= pw) { x -= pw; ++y; off += xwrap_off; }
-        y += dy;
-        if (y >= ph) { y -= ph; ++tp; off += ywrap_off; }
-        tp += dP;
-    });
-}
-
-// ----------------------------------------------------------------------------------
-// Lane decode for a spatial rectangle of a frame range: the blocks a SplitRectJob lists, chosen as
-// the preview kernel chooses its own (slot -> block through the list).  Every chain runs to its end check; a symbol is
-// stored only when each of (x, y, t') lies in the low or the high run of its axis, relocated into the compact volume of the
-// virtual chunk at job.j.sym.  (x, y, t') are carried as in split_preview_decode_kernel: the 64-bit divisions happen once
-// per lane, the loop has three adds and at most one wrap per axis, also for pw = 2 and P < 64.  The destination index is
-// two multiplies of values that do not depend on the chain's state, so the serial dependency stays lane_decode's own.
-// ----------------------------------------------------------------------------------
-template <bool WIDE>
-__global__ __launch_bounds__(256) void split_rect_decode_kernel(const SplitRectJob* __restrict__ jobs) {
-    using SymT = SplitSym<WIDE>;
-    __shared__ uint32_t c2s_sh[kProbScale / 4];
-    __shared__ uint32_t symtab[256];
-    const SplitRectJob rj = jobs[blockIdx.y];
-    const SplitJob& job = rj.j;
-    load_decode_tables(job.table, c2s_sh, symtab);
-    const int lane = threadIdx.x & 63;
-    const unsigned long long slot = (unsigned long long)blockIdx.x * 4u + (threadIdx.x >> 6);
-    if (slot >= rj.n_planned) return;
-    const unsigned long long b = rj.blocks[slot];
-    if (b >= job.n_blocks || !rj.pw || !rj.ph) return;   // (the host plans inside the channel; the bounds of lane_decode do not rest on it)
-    const LaneGeometry g(job, b, lane);
-
-    // where the lane's first symbol lies, and what 64 positions further means
-    const uint32_t pw = rj.pw, ph = rj.ph;
-    const unsigned long long P = (unsigned long long)pw * ph;
-    const unsigned long long p0 = g.base + (unsigned)lane;
-    const unsigned long long rem0 = p0 % P, step_rem = 64ull % P;
-    uint32_t tp = (uint32_t)(p0 / P), y = (uint32_t)(rem0 / pw), x = (uint32_t)(rem0 % pw);
-    const uint32_t dP = (uint32_t)(64ull / P), dy = (uint32_t)(step_rem / pw), dx = (uint32_t)(step_rem % pw);   // dy, dx < 64
-    const uint32_t x_lo = rj.lo[0], y_lo = rj.lo[1], t_lo = rj.lo[2];
-    const uint32_t x_hi = rj.half[0] + x_lo, y_hi = rj.half[1] + y_lo, t_hi = rj.half[2] + t_lo;
-    const uint32_t hx = rj.hl[0], hy = rj.hl[1], ht = rj.hl[2];
-    const unsigned long long vw = 2ull * hx, vh = 2ull * hy;
-    const unsigned long long limit = 2ull * ht * vh * vw;    // symbols of the channel's compact volume
+    const uint32_t x_lo = bj.lo[0], y_lo = bj.lo[1], t_lo = bj.lo[2];
+    const uint32_t x_hi = bj.half[0] + x_lo, y_hi = bj.half[1] + y_lo, t_hi = bj.half[2] + t_lo;
+    const uint32_t lx = bj.n_lo[0], ly = bj.n_lo[1], lt = bj.n_lo[2], hx = bj.n_hi[0], hy = bj.n_hi[1], ht = bj.n_hi[2];
+    const unsigned long long row = (unsigned long long)lx + hx, pitch = bj.pitch;
+    const unsigned long long limit = ((unsigned long long)lt + ht) * pitch;   // symbols of the channel's compact volume
     SymT* __restrict__ out = (SymT*)job.sym;
     lane_decode<WIDE>(job, b, lane, g.k, (const uint8_t*)c2s_sh, symtab, [&](uint32_t, uint32_t s) {
-        // a kept coordinate c of an axis has c - lo < hl (place c - lo) or c - hi < hl (place hl + c - hi): vx < vw, vy < vh
-        // and vt < 2 ht, so the index lies inside the channel's volume; the compare with `limit` keeps the store there
-        // whatever the carried coordinates hold
+        // a kept coordinate c of an axis has c - lo < n_lo (place c - lo) or c - hi < n_hi (place n_lo + c - hi): vx < row,
+        // vy < n_lo[1] + n_hi[1] and vt < n_lo[2] + n_hi[2], so with the job's pitch the index lies inside the channel's
+        // volume; the compare with `limit` keeps the store there whatever the job and the carried coordinates hold
         const uint32_t x0 = x - x_lo, x1 = x - x_hi, y0 = y - y_lo, y1 = y - y_hi, t0 = tp - t_lo, t1 = tp - t_hi;
-        if ((x0 < hx || x1 < hx) && (y0 < hy || y1 < hy) && (t0 < ht || t1 < ht)) {
-            const uint32_t vx = x0 < hx ? x0 : hx + x1, vy = y0 < hy ? y0 : hy + y1, vt = t0 < ht ? t0 : ht + t1;
-            const unsigned long long at = (vt * vh + vy) * vw + vx;
+        if ((x0 < lx || (XY_HIGH && x1 < hx)) && (y0 < ly || (XY_HIGH && y1 < hy)) && (t0 < lt || t1 < ht)) {
+            const uint32_t vx = !XY_HIGH || x0 < lx ? x0 : lx + x1, vy = !XY_HIGH || y0 < ly ? y0 : ly + y1, vt = t0 < lt ? t0 : lt + t1;
+            const unsigned long long at = vt * pitch + vy * row + vx;
             if (at < limit) out[at] = (SymT)s;
         }
         x += dx;
@@ -645,11 +595,9 @@ void launch_split_decode(const SplitJob* d_jobs, int n_jobs, uint32_t max_blocks
 void launch_split_frames_decode(const SplitFramesJob* d_jobs, int n_jobs, uint32_t max_blocks, bool wide, hipStream_t st) {
     launch_lanes(split_frames_decode_kernel<false>, split_frames_decode_kernel<true>, wide, d_jobs, n_jobs, max_blocks, st);
 }
-void launch_split_preview_decode(const SplitPreviewJob* d_jobs, int n_jobs, uint32_t max_planned, bool wide, hipStream_t st) {
-    launch_lanes(split_preview_decode_kernel<false>, split_preview_decode_kernel<true>, wide, d_jobs, n_jobs, max_planned, st);
-}
-void launch_split_rect_decode(const SplitRectJob* d_jobs, int n_jobs, uint32_t max_planned, bool wide, hipStream_t st) {
-    launch_lanes(split_rect_decode_kernel<false>, split_rect_decode_kernel<true>, wide, d_jobs, n_jobs, max_planned, st);
+void launch_split_box_decode(const SplitBoxJob* d_jobs, int n_jobs, uint32_t max_planned, bool wide, bool xy_high, hipStream_t st) {
+    if (xy_high) launch_lanes(split_box_decode_kernel<false, true>, split_box_decode_kernel<true, true>, wide, d_jobs, n_jobs, max_planned, st);
+    else launch_lanes(split_box_decode_kernel<false, false>, split_box_decode_kernel<true, false>, wide, d_jobs, n_jobs, max_planned, st);
 }
 void launch_split_headers(const SplitHeaderDesc* d_descs, int n_chunks, hipStream_t st) {
     if (n_chunks > 0) hipLaunchKernelGGL(split_header_kernel, dim3(n_chunks), dim3(256), 0, st, d_descs);

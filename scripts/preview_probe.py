@@ -81,7 +81,7 @@ def crop_reference(coefs, f, kind, step, version, t0, t1):
 
 TRACE_RANGE = (31, 32)
 TRACE_CALLS = 10
-TRACE_KERNELS = ("rans_table_from_arrays_kernel", "split_scan_kernel", "split_preview_decode_kernel", "split_frames_decode_kernel",
+TRACE_KERNELS = ("rans_table_from_arrays_kernel", "split_scan_kernel", "split_box_decode_kernel", "split_frames_decode_kernel",
                  "preview_inv_kernel", "inv_t_win_kernel", "inv_t_wide_win_kernel", "inv_xy_kernel")
 
 
