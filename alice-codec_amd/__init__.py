@@ -40,6 +40,15 @@ class WaveletType(enum.IntEnum):  # reference src/pipeline.rs:34-41
     Haar = 2
 
 
+PREVIEWS_MAX_ITEMS = 1024          # ALICE_PREVIEWS_MAX_ITEMS
+PREVIEWS_NO_ITEM = 0xFFFFFFFF      # *bad_item of a refusal that is no item's
+
+
+class PreviewItem(C.Structure):
+    """alice_codec_preview_item of include/alice_codec.h"""
+    _fields_ = [("alc", C.c_void_p), ("len", C.c_uint64), ("first", C.c_uint32), ("count", C.c_uint32), ("rgb_out", C.c_void_p)]
+
+
 class CodecError(Exception):
     """Mirror of the reference ``CodecError`` (src/error.rs:12-23)."""
 
@@ -324,6 +333,9 @@ def load_library() -> C.CDLL:
         "alice_codec_decode_preview": (vp, [_u8p, C.c_uint64, C.c_uint32, C.c_uint32, _u64p]),
         "alice_codec_dev_decode_preview": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp]),
         "alice_codec_test_last_preview_stats": (None, [_u64p]),
+        "alice_codec_decode_previews": (vp, [C.POINTER(PreviewItem), C.c_uint32, _u64p, _u32p]),
+        "alice_codec_dev_decode_previews": (C.c_int, [C.POINTER(PreviewItem), C.c_uint32, _u32p, vp]),
+        "alice_codec_test_last_previews_stats": (None, [_u64p]),
         "alice_codec_rect_window": (C.c_int, [C.c_uint8] + [C.c_uint32] * 6 + [_u32p] * 4),
         "alice_codec_decode_rect": (vp, [_u8p, C.c_uint64] + [C.c_uint32] * 6 + [_u64p]),
         "alice_codec_dev_decode_rect": (C.c_int, [vp, C.c_uint64] + [C.c_uint32] * 6 + [vp, C.c_uint64, C.c_uint64, vp]),
@@ -2299,6 +2311,68 @@ def _test_last_preview_stats() -> tuple:
     over the three channels) of the calling thread's last preview decode."""
     out = np.zeros(6, np.uint64)
     load_library().alice_codec_test_last_preview_stats(_p(out, _u64p))
+    return tuple(int(v) for v in out)
+
+
+# ---- many previews in one call (DESIGN.md section 17) ----
+
+def _previews_error(bad: int):
+    """Raises the library's last error with the index of the item that decided it (None: no item's) as .bad_item"""
+    try:
+        _raise_last()
+    except CodecError as e:
+        e.bad_item = None if bad == PREVIEWS_NO_ITEM else bad
+        raise
+
+
+def _preview_items(rows):
+    n = len(rows)
+    if n > 0xFFFFFFFF:
+        raise CodecError(3, "dimension out of u32 range")
+    arr = (PreviewItem * max(n, 1))()
+    for i, (alc, length, first, count, out) in enumerate(rows):
+        _dims_u32(first, count)
+        arr[i] = PreviewItem(alc, length, first, count, out)
+    return arr
+
+
+def decode_previews(items) -> list:
+    """decode_preview of many (data, first, count) items in one call: a list of arrays, one per item, in item order.  Items
+    may mix versions 2, 3 and 4, wavelets, sizes and lane sizes; items that pass the same object as data share its header,
+    tables, directory scan and upload (the union of their planned blocks goes up once).  All or nothing: the first item that
+    is refused or damaged decides the CodecError, whose .bad_item is its index and whose message starts with "item <index>"."""
+    lib = load_library()
+    items = list(items)
+    bufs, rows = {}, []
+    for data, first, count in items:
+        buf = bufs.setdefault(id(data), _as_u8(data))
+        rows.append((buf.ctypes.data, buf.size, first, count, None))
+    arr = _preview_items(rows)
+    offsets = np.zeros(len(rows) + 1, np.uint64)
+    bad = C.c_uint32(PREVIEWS_NO_ITEM)
+    ptr = lib.alice_codec_decode_previews(arr, len(rows), _p(offsets, _u64p), C.byref(bad))
+    if not ptr:
+        _previews_error(bad.value)
+    whole = _adopt(ptr, int(offsets[-1]), lib.alice_codec_data_free64)
+    return [whole[int(offsets[i]):int(offsets[i + 1])] for i in range(len(rows))]
+
+
+def previews_decode_device(items, stream: int = 0) -> None:
+    """preview_decode_device of many (d_alc_ptr, length, first, count, d_rgb_out_ptr) items in one call (containers and
+    outputs on the device; outputs must not overlap).  Items that name the same pointer and length share their header,
+    tables and directory scan.  All or nothing, errors as decode_previews."""
+    rows = [tuple(r) for r in items]
+    arr = _preview_items(rows)
+    bad = C.c_uint32(PREVIEWS_NO_ITEM)
+    if load_library().alice_codec_dev_decode_previews(arr, len(rows), C.byref(bad), stream or None) != 0:
+        _previews_error(bad.value)
+
+
+def _test_last_previews_stats() -> tuple:
+    """(items, distinct containers, table launches, lane launches, finish launches, stream drains, blocks decoded, payload
+    bytes the host call uploaded, symbols stored) of the calling thread's last batched preview that ran to its end."""
+    out = np.zeros(9, np.uint64)
+    load_library().alice_codec_test_last_previews_stats(_p(out, _u64p))
     return tuple(int(v) for v in out)
 
 

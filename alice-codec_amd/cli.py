@@ -20,6 +20,9 @@ is version 1.
 version 1 is refused with the library's message.
 `decode --rect X,Y,W,H` (alone: every frame; or with `--frames`) writes the W x H pixels at (X, Y) as packed W x H frames,
 from the blocks they need, through the same mapped file; with `--preview` it is refused.
+`thumbnails IN [IN ...] -o OUT [--frame K | --every N]` writes preview frame K (default 0) of every input, or every N-th
+frame of every input, back to back: one batched call per 1024 items over mapped files, such as the
+PREFIX.NNNNN.alc files of `encode-chunks`; inputs whose preview sizes differ, and version 1 inputs, are refused.
 Like the reference it treats the whole input file as ONE chunk (src/bin/main.rs:117-122).  `encode-chunks`
 is the extension SURVEY.md section 8f asks for: it cuts a long raw-RGB file into 64-frame chunks
 (DEFAULT_CHUNK_SIZE, src/lib.rs:110) and writes one .alc per chunk."""
@@ -30,8 +33,8 @@ import sys
 
 import numpy as np
 
-from . import (DEFAULT_CHUNK_SIZE, CodecError, EncodedChunk, FrameDecoder, FrameEncoder, WaveletType, budget_bytes_per_chunk,
-               alc_version, decode_frames, decode_preview, decode_rect, decode_reversible, decode_split, decode_wide, encode_many, encode_reversible, encode_split,
+from . import (DEFAULT_CHUNK_SIZE, PREVIEWS_MAX_ITEMS, CodecError, EncodedChunk, FrameDecoder, FrameEncoder, WaveletType, budget_bytes_per_chunk,
+               alc_version, decode_frames, decode_preview, decode_previews, decode_rect, decode_reversible, decode_split, decode_wide, encode_many, encode_reversible, encode_split,
                encode_split_to_psnr, encode_split_to_size, encode_to_size, encode_wide, encode_wide_to_psnr, reversible_info,
                split_info, wide_info)
 
@@ -293,6 +296,48 @@ def cmd_decode_preview(a) -> None:
     print(f"decoded preview {qw}x{qh} of frames [{first}, {end}) of {width}x{height}x{frames} -> {rgb.size} bytes (raw RGB)", file=sys.stderr)
 
 
+def cmd_thumbnails(a) -> None:
+    """Preview frame K of every input (--frame K, default 0), or every N-th frame of every input (--every N), through the
+    batched call in groups of at most PREVIEWS_MAX_ITEMS items, written back to back in input order."""
+    if a.frame is not None and a.every is not None:
+        raise ValueError("--frame and --every cannot be combined")
+    if a.every is not None and a.every < 1:
+        raise ValueError(f"--every wants N >= 1, got {a.every}")
+    if a.frame is not None and a.frame < 0:
+        raise ValueError(f"--frame wants K >= 0, got {a.frame}")
+    files, items, size = [], [], None
+    for path in a.inputs:
+        data = np.memmap(path, dtype=np.uint8, mode="r")
+        if data.size < 18 or bytes(data[:4]) != b"ALCC" or not 2 <= int(data[4]) <= 4:
+            decode_previews([(data, 0, 1)])       # refused by the library, with its message (version 1: no random access)
+            raise ValueError(f"{path}: not a version 2, 3 or 4 container")
+        width, height, frames = (int(v) for v in np.frombuffer(bytes(data[6:18]), "<u4"))
+        q = ((width + 1) // 2, (height + 1) // 2)
+        if size is None:
+            size, first_path = q, path
+        elif q != size:
+            raise ValueError(f"preview sizes differ: {first_path} gives {size[0]}x{size[1]}, {path} gives {q[0]}x{q[1]}")
+        picks = range(0, frames, a.every) if a.every is not None else [a.frame or 0]
+        for k in picks:
+            if k >= frames:
+                raise ValueError(f"{path}: frames [{k}, {k + 1}) are not a range of the chunk's {frames} frames")
+            items.append((data, k, 1))
+        files.append(data)
+    written = 0
+    try:
+        with open(a.output, "wb") as out:
+            for at in range(0, len(items), PREVIEWS_MAX_ITEMS):
+                for rgb in decode_previews(items[at:at + PREVIEWS_MAX_ITEMS]):
+                    rgb.tofile(out)
+                    written += rgb.size
+    except BaseException:
+        import os
+        if os.path.exists(a.output):
+            os.remove(a.output)
+        raise
+    print(f"wrote {len(items)} preview frames {size[0]}x{size[1]} of {len(files)} files -> {written} bytes (raw RGB)", file=sys.stderr)
+
+
 def parse_rect(text: str):
     """'X,Y,W,H' -> (X, Y, W, H); ValueError otherwise."""
     parts = text.split(",")
@@ -434,6 +479,11 @@ def main(argv=None) -> int:
     d.add_argument("--rect", default=None, metavar="X,Y,W,H",
                    help="write the W x H pixels at (X, Y) only, as packed W x H frames decoded from the blocks they need: all frames, or "
                         "those of --frames; versions 2, 3 and 4; not with --preview")
+    t = sub.add_parser("thumbnails", help="one call for many small previews: a contact sheet or a scrub bar")
+    t.add_argument("inputs", nargs="+", metavar="IN", help="version 2, 3 or 4 containers, such as the PREFIX.NNNNN.alc files of encode-chunks")
+    t.add_argument("-o", "--output", required=True)
+    t.add_argument("--frame", type=int, default=None, metavar="K", help="preview frame K of every input (default 0)")
+    t.add_argument("--every", type=int, default=None, metavar="N", help="every N-th frame of every input instead")
     i = sub.add_parser("info")
     i.add_argument("input")
     for x in (d, i):
@@ -441,7 +491,8 @@ def main(argv=None) -> int:
                        help="auto: from the file's version byte; otherwise the file must be of that format")
     a = p.parse_args(argv)
     try:
-        {"encode": cmd_encode, "encode-chunks": cmd_encode_chunks, "decode": cmd_decode, "info": cmd_info}[a.command](a)
+        {"encode": cmd_encode, "encode-chunks": cmd_encode_chunks, "decode": cmd_decode, "info": cmd_info,
+         "thumbnails": cmd_thumbnails}[a.command](a)
     except (CodecError, ValueError, OSError) as e:
         print(f"error: {e}", file=sys.stderr)
         return 1

@@ -23,6 +23,7 @@
 #include <cstring>
 #include <exception>
 #include <functional>
+#include <iterator>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -4822,7 +4823,8 @@ int partial_done(PartialKind kind, const PartialPlan& p, uint32_t count, uint64_
 
 // The checks both calls share, in their order (after the null checks): fixed fields and magic, the version byte, that
 // version's header checks, then the range.  data: min(len, kSplitHeaderBytes) readable bytes.
-int frames_validate(const uint8_t* data, uint64_t len, uint32_t first, uint32_t count, SplitHeader& h, ChunkDims& d) {
+// (in two halves, so that a batched call validates a container's header once for all the items that name it)
+int frames_validate_header(const uint8_t* data, uint64_t len, SplitHeader& h, ChunkDims& d) {
     if (len < kSplitFixedHeaderBytes)
         return fail(kInvalidBitstream, "data too short for the fixed fields: " + std::to_string(len) + " bytes (they take " +
                                            std::to_string(kSplitFixedHeaderBytes) + ")");
@@ -4831,12 +4833,18 @@ int frames_validate(const uint8_t* data, uint64_t len, uint32_t first, uint32_t 
     if (version == 1) return fail(kInvalidBitstream, "version 1 has no random access (one serial chain per channel)");
     if (version < 2 || version > 4)
         return fail(kInvalidBitstream, "unsupported version: " + std::to_string(version) + " (a frame range needs version 2, 3 or 4)");
-    TRY(parse_split_header(data, len, h, &d, version));
+    return parse_split_header(data, len, h, &d, version);
+}
+int frames_validate_range(const SplitHeader& h, const ChunkDims& d, uint32_t first, uint32_t count) {
     if (count < 1 || (uint64_t)first + count > h.frames)
         return fail(kInvalidDimensions, "frames [" + std::to_string(first) + ", " + std::to_string((uint64_t)first + count) +
                                             ") are not a range of the chunk's " + std::to_string(h.frames) + " frames");
     if (d.n_pixels == 0) return fail(kInvalidDimensions, "invalid dimensions");
     return kOk;
+}
+int frames_validate(const uint8_t* data, uint64_t len, uint32_t first, uint32_t count, SplitHeader& h, ChunkDims& d) {
+    TRY(frames_validate_header(data, len, h, d));
+    return frames_validate_range(h, d, first, count);
 }
 
 // What the two device calls (frame range, preview) share: the null checks, the header fetched to the host and validated,
@@ -4864,13 +4872,13 @@ int partial_decode_dev(const void* d_alc, uint64_t len, uint32_t first, uint32_t
 // verdict on the way.  What goes up: the header, the three tables, the byte runs of consecutive planned blocks -- at their
 // own offsets of a pool buffer of the container's size, so that the device path runs on it unchanged.  The rest of it
 // stays unwritten and unread.  device(d_alc, d_rgb, stream, uploaded payload bytes) decodes `bytes` bytes to d_rgb.
-template <typename Device>
-int partial_decode_host(const uint8_t* data, uint64_t len, const SplitHeader& h, const std::vector<uint32_t>& blocks, uint64_t bytes,
-                        uint8_t** result, uint64_t* out_len, Device device) {
-    struct Span { uint64_t off, len; };
-    std::vector<Span> spans;
+struct PartialSpan { uint64_t off, len; };
+// the spans of a container that go up for `blocks`, and the payload bytes among them
+int partial_spans(const uint8_t* data, const SplitHeader& h, const std::vector<uint32_t>& blocks, std::vector<PartialSpan>& spans,
+                  uint64_t& payload_bytes) {
     spans.push_back({0, kSplitHeaderBytes});
-    uint64_t payload_bytes = 0, pos = kSplitHeaderBytes;
+    uint64_t pos = kSplitHeaderBytes;
+    payload_bytes = 0;
     for (int c = 0; c < 3; ++c) {
         const uint8_t* tab = data + pos;
         const uint32_t nb = h.n_blocks[c];
@@ -4896,6 +4904,15 @@ int partial_decode_host(const uint8_t* data, uint64_t len, const SplitHeader& h,
             return fail(kInvalidBitstream, "channel " + std::to_string(c) + ": block lengths do not sum to payload_len " + std::to_string(h.payload_len[c]));
         pos += h.payload_len[c];
     }
+    return kOk;
+}
+
+template <typename Device>
+int partial_decode_host(const uint8_t* data, uint64_t len, const SplitHeader& h, const std::vector<uint32_t>& blocks, uint64_t bytes,
+                        uint8_t** result, uint64_t* out_len, Device device) {
+    std::vector<PartialSpan> spans;
+    uint64_t payload_bytes = 0;
+    TRY(partial_spans(data, h, blocks, spans, payload_bytes));
     std::unique_ptr<uint8_t, decltype(&free)> out(host_result_alloc(bytes), &free);   // freed on every failure below
     if (!out) return fail(kOutOfMemory, "out of host memory");
     *out_len = bytes;
@@ -4904,7 +4921,7 @@ int partial_decode_host(const uint8_t* data, uint64_t len, const SplitHeader& h,
     DevBuf d_alc, d_rgb;
     TRY(d_alc.alloc(len));
     TRY(d_rgb.alloc(bytes));
-    for (const Span& s : spans)
+    for (const PartialSpan& s : spans)
         HIP_TRY(hipMemcpyAsync(d_alc.as<uint8_t>() + s.off, data + s.off, s.len, hipMemcpyHostToDevice, st));
     TRY(device(d_alc.as<uint8_t>(), d_rgb.p, st, payload_bytes));
     TRY(copy_to_host(out.get(), d_rgb.p, bytes, st));
@@ -5161,6 +5178,352 @@ void alice_codec_test_last_preview_stats(uint64_t out[6]) {
     const PartialStats& s = tl_partial_stats[kPartialPreview];
     const uint64_t v[6] = {s.ta, s.tb, s.blocks, s.uploaded, s.frames, s.stored};
     if (out) memcpy(out, v, sizeof(v));
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// PART 9, batched: many previews in one call (kernels: rans_tables_from_arrays_kernel of rans.hip,
+// split_scan_kernel<true> and split_box_decode_kernel<WIDE, false> of split.hip, preview_inv_many_kernel of transform.hip)
+//
+// A thumbnail strip asks for one frame of each of N chunks, a scrub bar for every k-th frame of one chunk: N times PART 9's
+// fixed cost through the single call.  Here the items of a call share one queue: the headers of the distinct containers are
+// fetched together, every table of every container is built by one launch, one scan covers every channel, the planned
+// blocks of all items are decoded by one lane launch per symbol width (3 jobs per item on blockIdx.y, each with its own
+// list), the end checks of all items come back in one copy, and the finish runs once per instance class present.  Every item
+// means what PART 9's call means; the call is all or nothing.
+// ------------------------------------------------------------------------------------------
+
+namespace {
+
+constexpr uint32_t kPreviewsNoItem = 0xFFFFFFFFu;   // *bad_item of a refusal that is no item's
+
+struct PreviewsContainer {                 // a distinct (pointer, len) among the items
+    const uint8_t* src = nullptr;          // as the caller named it: device memory (dev call) or host memory (host call)
+    uint64_t len = 0;
+    const uint8_t* d_alc = nullptr;        // on the device
+    uint32_t first_item = 0;               // the first item that names it
+    uint8_t raw[kSplitHeaderBytes] = {};   // dev call: the header, fetched
+    SplitHeader h;
+    ChunkDims d{};
+    int rc = kOk;                          // the header's verdict, and its message
+    std::string msg;
+    std::vector<uint32_t> blocks;          // host call: the union of its items' planned blocks
+    std::vector<PartialSpan> spans;        // host call: what goes up
+};
+
+struct PreviewsItem {
+    uint32_t container = 0, first = 0, count = 0;
+    PartialPlan p;
+    uint8_t* d_rgb = nullptr;
+    uint64_t bytes = 0;                    // count * qh * qw * 3
+    size_t sym_at = 0;                     // its compact volume inside d_sym
+};
+
+// Everything a batched call owns.  The destructor drains the stream before any member goes: the host vectors that
+// asynchronous copies read (cs[].raw, up, flags) and the pool buffers outlive the work that touches them, also on an error
+// return with kernels still queued.
+struct PreviewsBatch {
+    std::vector<PreviewsContainer> cs;
+    std::vector<PreviewsItem> items;
+    std::vector<std::unique_ptr<DevBuf>> alcs;   // host call: one pool buffer of the container's size per distinct container
+    DevBuf d_rgb;                                // host call: the outputs, back to back
+    DevBuf d_up, d_work, d_sym;
+    std::vector<uint8_t> up;
+    std::vector<uint32_t> flags;
+    hipStream_t st = nullptr;
+    bool armed = false;
+    uint64_t drains = 0, table_launches = 0, lane_launches = 0, finish_launches = 0;
+    ~PreviewsBatch() { if (armed) (void)hipStreamSynchronize(st); }
+    int drain() { ++drains; HIP_TRY(hipStreamSynchronize(st)); return kOk; }
+};
+
+thread_local uint64_t tl_previews_stats[9] = {};
+
+int fail_item(uint32_t k, uint32_t* bad_item, int code, const std::string& msg) {
+    if (bad_item) *bad_item = k;
+    return fail(code, "item " + std::to_string(k) + ": " + msg);
+}
+
+// The checks that need neither a device nor a byte of a container, then the distinct containers and the items
+int previews_collect(const alice_codec_preview_item* items, uint32_t n_items, bool dev, uint32_t* bad_item, PreviewsBatch& b) {
+    if (bad_item) *bad_item = kPreviewsNoItem;
+    if (!items) return fail(kNullArgument, "null argument");
+    if (n_items == 0) return fail(kInvalidDimensions, "a batch holds at least one item");
+    if (n_items > ALICE_PREVIEWS_MAX_ITEMS)
+        return fail(kInvalidDimensions, std::to_string(n_items) + " items: a batch holds at most " + std::to_string(ALICE_PREVIEWS_MAX_ITEMS));
+    for (uint32_t k = 0; k < n_items; ++k)
+        if (!items[k].alc || (dev && !items[k].rgb_out)) return fail_item(k, bad_item, kNullArgument, "null argument");
+    std::map<std::pair<const void*, uint64_t>, uint32_t> seen;
+    b.items.resize(n_items);
+    for (uint32_t k = 0; k < n_items; ++k) {
+        const auto at = seen.emplace(std::make_pair(items[k].alc, items[k].len), (uint32_t)b.cs.size());
+        if (at.second) {
+            b.cs.emplace_back();
+            b.cs.back().src = (const uint8_t*)items[k].alc; b.cs.back().len = items[k].len; b.cs.back().first_item = k;
+        }
+        PreviewsItem& it = b.items[k];
+        it.container = at.first->second; it.first = items[k].first; it.count = items[k].count; it.d_rgb = (uint8_t*)items[k].rgb_out;
+    }
+    return kOk;
+}
+
+// frames_validate per item, in item order; a container's header is checked once.  header(c): min(len, kSplitHeaderBytes)
+// readable bytes of container c.  Then every item's plan.
+template <typename Header>
+int previews_validate(PreviewsBatch& b, uint32_t* bad_item, Header header) {
+    for (PreviewsContainer& c : b.cs) {
+        c.rc = frames_validate_header(header(c), c.len, c.h, c.d);
+        c.msg = tl_msg;
+    }
+    clear_error();
+    for (uint32_t k = 0; k < b.items.size(); ++k) {
+        PreviewsItem& it = b.items[k];
+        const PreviewsContainer& c = b.cs[it.container];
+        if (c.rc != kOk) return fail_item(k, bad_item, c.rc, c.msg);
+        if (frames_validate_range(c.h, c.d, it.first, it.count) != kOk) return fail_item(k, bad_item, tl_err, std::string(tl_msg));
+        it.p = preview_plan(c.h, c.d, it.first, it.count);
+        it.bytes = (uint64_t)it.p.box.n_lo[0] * it.p.box.n_lo[1] * it.count * 3;
+    }
+    return kOk;
+}
+
+// dev call: no two items' output byte ranges may overlap.  One sort finds whether any do; only a refusal pays for naming
+// the first item that overlaps an earlier one.
+int previews_outputs_disjoint(const PreviewsBatch& b, uint32_t* bad_item) {
+    const size_t n = b.items.size();
+    std::vector<std::pair<uintptr_t, uintptr_t>> r(n);
+    for (size_t k = 0; k < n; ++k) r[k] = {(uintptr_t)b.items[k].d_rgb, (uintptr_t)b.items[k].d_rgb + b.items[k].bytes};
+    std::vector<std::pair<uintptr_t, uintptr_t>> sorted = r;
+    std::sort(sorted.begin(), sorted.end());
+    bool any = false;
+    uintptr_t end = 0;
+    for (size_t k = 0; k < n && !any; ++k) {
+        any = k > 0 && sorted[k].first < end;
+        end = std::max(end, sorted[k].second);
+    }
+    if (!any) return kOk;
+    for (size_t k = 1; k < n; ++k)
+        for (size_t j = 0; j < k; ++j)
+            if (r[k].first < r[j].second && r[j].first < r[k].second)
+                return fail_item((uint32_t)k, bad_item, kInvalidDimensions, "its output overlaps the output of item " + std::to_string(j));
+    return fail(kInternal, "previews: overlap not found again");
+}
+
+// The queue of a batched call whose containers are on the device (c.d_alc) and whose items are planned: tables, scan, lanes,
+// the verdict of all end checks in one copy, then the finish launches.  Nothing that writes an output is queued before the
+// verdict.  drain_at_end: the stream has drained on return (false: the caller's copy to the host drains it).
+int previews_device(PreviewsBatch& b, uint32_t* bad_item, bool drain_at_end) {
+    hipStream_t st = b.st;
+    const size_t C = b.cs.size(), N = b.items.size();
+    auto take = [](size_t& at, size_t bytes) { const size_t r = at; at = round_up(at + bytes, 256); return r; };
+    // what goes up in one copy: frequencies and their prefix sums, the (zero) flags, the scan's jobs, the lane jobs with the
+    // narrow items first, their lists, the finish records
+    size_t up_n = 0, work_n = 0, sym_n = 0, n_listed = 0;
+    std::vector<uint32_t> order;   // lane-job order: items of u8 symbols, then items of u16 symbols
+    size_t n_narrow = 0;
+    for (int wide = 0; wide < 2; ++wide)
+        for (uint32_t k = 0; k < N; ++k)
+            if ((int)is_wide(b.cs[b.items[k].container].h.fmt) == wide) { order.push_back(k); if (!wide) ++n_narrow; }
+    for (const PreviewsItem& it : b.items) n_listed += it.p.blocks.size();
+    const size_t freq_at = take(up_n, 3 * C * 256 * sizeof(uint16_t)), cum_at = take(up_n, 3 * C * 256 * sizeof(uint16_t));
+    const size_t flags_at = take(up_n, (3 * C + 3 * N) * sizeof(uint32_t));
+    const size_t scan_at = take(up_n, 3 * C * sizeof(SplitJob)), box_at = take(up_n, 3 * N * sizeof(SplitBoxJob));
+    const size_t list_at = take(up_n, n_listed * sizeof(uint32_t)), rec_at = take(up_n, N * preview_record_bytes());
+    // device scratch: the tables, and every container's block lengths and offsets (per-job block counts: containers differ)
+    const size_t tables_at = take(work_n, 3 * C * sizeof(RansTable));
+    std::vector<size_t> len_at(C), off_at(C);
+    for (size_t i = 0; i < C; ++i) {
+        const size_t nb = b.cs[i].h.n_blocks[0];
+        len_at[i] = take(work_n, 3 * nb * sizeof(uint32_t));
+        off_at[i] = take(work_n, 3 * (nb + 1) * sizeof(unsigned long long));
+    }
+    // the pad symbols of a plane (pitch - qw * qh < 4) are never stored; the finish loads them with a group's real ones
+    // and drops what it computes from them, so they need no value
+    for (PreviewsItem& it : b.items) {
+        const size_t sb = is_wide(b.cs[it.container].h.fmt) ? 2 : 1;
+        it.sym_at = take(sym_n, 3 * (size_t)(it.p.tb - it.p.ta) * it.p.box.pitch * sb);
+    }
+    b.up.assign(up_n, 0);
+    TRY(b.d_up.alloc(up_n));
+    TRY(b.d_work.alloc(work_n));
+    TRY(b.d_sym.alloc(sym_n));
+    uint8_t* const d_up = b.d_up.as<uint8_t>();
+    uint8_t* const d_work = b.d_work.as<uint8_t>();
+    uint32_t* const d_flags = (uint32_t*)(d_up + flags_at);
+    RansTable* const d_tables = (RansTable*)(d_work + tables_at);
+
+    // a channel's job less its symbols and its flags
+    auto channel_job = [&](size_t ci, int c) {
+        const PreviewsContainer& pc = b.cs[ci];
+        const size_t nb = pc.h.n_blocks[0];
+        SplitJob j{};
+        uint64_t off = kSplitHeaderBytes;
+        for (int e = 0; e < c; ++e) off += pc.h.payload_len[e];
+        j.n = pc.d.padded; j.n_blocks = pc.h.n_blocks[c]; j.lane_symbols = pc.h.lane_symbols;
+        j.table = d_tables + 3 * ci + (size_t)c;
+        j.stream = (uint8_t*)pc.d_alc + off; j.len = pc.h.payload_len[c];
+        j.blk_len = (uint32_t*)(d_work + len_at[ci]) + (size_t)c * nb;
+        j.blk_off = (unsigned long long*)(d_work + off_at[ci]) + (size_t)c * (nb + 1);
+        return j;
+    };
+    uint16_t* freq = (uint16_t*)(b.up.data() + freq_at);
+    uint16_t* cum = (uint16_t*)(b.up.data() + cum_at);
+    for (size_t ci = 0; ci < C; ++ci)
+        for (int c = 0; c < 3; ++c) {
+            const size_t t = 3 * ci + (size_t)c;
+            uint32_t run = 0;
+            for (int i = 0; i < 256; ++i) { freq[t * 256 + i] = b.cs[ci].h.freq[c][i]; cum[t * 256 + i] = (uint16_t)run; run += b.cs[ci].h.freq[c][i]; }
+            SplitJob j = channel_job(ci, c);
+            j.flags = d_flags + t;
+            memcpy(b.up.data() + scan_at + t * sizeof(SplitJob), &j, sizeof(j));
+        }
+    std::vector<PreviewFinish> fin(N);
+    uint32_t max_planned[2] = {0, 0};
+    size_t listed = 0;
+    for (size_t slot = 0; slot < N; ++slot) {
+        const uint32_t k = order[slot];
+        const PreviewsItem& it = b.items[k];
+        const PreviewsContainer& pc = b.cs[it.container];
+        const bool wide = is_wide(pc.h.fmt);
+        const size_t sb = wide ? 2 : 1;
+        const uint32_t planes = it.p.tb - it.p.ta, n_planned = (uint32_t)it.p.blocks.size();
+        uint8_t* const sym = b.d_sym.as<uint8_t>() + it.sym_at;
+        memcpy(b.up.data() + list_at + listed * sizeof(uint32_t), it.p.blocks.data(), n_planned * sizeof(uint32_t));
+        for (int c = 0; c < 3; ++c) {
+            SplitBoxJob j = it.p.box;
+            j.j = channel_job(it.container, c);
+            j.j.sym = sym + (size_t)c * planes * it.p.box.pitch * sb;
+            j.j.flags = d_flags + 3 * C + 3 * (size_t)k + (size_t)c;
+            j.blocks = (const uint32_t*)(d_up + list_at) + listed; j.n_planned = n_planned;
+            memcpy(b.up.data() + box_at + (3 * slot + (size_t)c) * sizeof(SplitBoxJob), &j, sizeof(j));
+        }
+        listed += n_planned;
+        max_planned[wide] = std::max(max_planned[wide], n_planned);
+        // EXACT is the full chunk's verdict: the first pass inverse_bounds looks at is the temporal one
+        PreviewFinish& f = fin[k];
+        f.d_sym = sym; f.pitch = it.p.box.pitch; f.q = (uint64_t)it.p.box.n_lo[0] * it.p.box.n_lo[1]; f.planes = planes;
+        f.win = FrameWindow{it.first - it.p.ta, it.first - it.p.ta + it.count};
+        f.format = (int)pc.h.fmt; f.wavelet = pc.h.wavelet;
+        for (int c = 0; c < 3; ++c) f.step[c] = pc.h.step[c];
+        f.exact = inverse_bounds(pc.h.wavelet, pc.h.step, wide ? kWideMaxQ : kByteMaxQ).exact;
+        f.d_rgb = it.d_rgb;
+    }
+    std::vector<PreviewFinishLaunch> finishes;
+    if (!preview_records_plan(fin.data(), (uint32_t)N, b.up.data() + rec_at, finishes))
+        return fail(kInternal, "previews: no finish kernel for an item's volume");
+
+    b.armed = true;
+    HIP_TRY(hipMemcpyAsync(d_up, b.up.data(), up_n, hipMemcpyHostToDevice, st));
+    launch_rans_tables_from_arrays((const uint16_t*)(d_up + cum_at), (const uint16_t*)(d_up + freq_at), d_tables, (int)(3 * C), st);
+    b.table_launches = 1;
+    launch_split_scan((const SplitJob*)(d_up + scan_at), (int)(3 * C), true, nullptr, st);
+    const SplitBoxJob* d_box = (const SplitBoxJob*)(d_up + box_at);
+    if (n_narrow) { launch_split_box_decode(d_box, (int)(3 * n_narrow), max_planned[0], false, false, st); ++b.lane_launches; }
+    if (N > n_narrow) { launch_split_box_decode(d_box + 3 * n_narrow, (int)(3 * (N - n_narrow)), max_planned[1], true, false, st); ++b.lane_launches; }
+    HIP_TRY(hipGetLastError());
+    // the verdict: every container's and every item's end-check flags in one copy, before anything writes an output
+    b.flags.assign(3 * C + 3 * N, 0);
+    HIP_TRY(hipMemcpyAsync(b.flags.data(), d_flags, b.flags.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    TRY(b.drain());
+    for (uint32_t k = 0; k < N; ++k)
+        for (int c = 0; c < 3; ++c) {
+            const uint32_t scan = b.flags[3 * (size_t)b.items[k].container + (size_t)c], lanes = b.flags[3 * C + 3 * (size_t)k + (size_t)c];
+            if ((scan | lanes) & kSplitBadDirectory)
+                return fail_item(k, bad_item, kInvalidBitstream, "stream " + std::to_string(c) + ": block or lane directory does not add up");
+            if (scan | lanes) return fail_item(k, bad_item, kInvalidBitstream, "stream " + std::to_string(c) + ": a lane failed its end check");
+        }
+    for (const PreviewFinishLaunch& l : finishes) { launch_preview_inverse_many(d_up + rec_at, l, st); ++b.finish_launches; }
+    HIP_TRY(hipGetLastError());
+    if (drain_at_end) TRY(b.drain());
+    return kOk;
+}
+
+void previews_done(const PreviewsBatch& b, uint64_t uploaded) {
+    uint64_t blocks = 0, stored = 0;
+    for (const PreviewsItem& it : b.items) { blocks += 3ull * it.p.blocks.size(); stored += 3 * it.p.stored; }
+    const uint64_t v[9] = {b.items.size(), b.cs.size(), b.table_launches, b.lane_launches, b.finish_launches, b.drains, blocks, uploaded, stored};
+    memcpy(tl_previews_stats, v, sizeof(v));
+}
+
+}  // namespace
+
+extern "C" {
+
+int alice_codec_dev_decode_previews(const alice_codec_preview_item* items, uint32_t n_items, uint32_t* bad_item, void* hip_stream) {
+    clear_error();
+    PreviewsBatch b;
+    TRY(previews_collect(items, n_items, true, bad_item, b));
+    TRY(ensure_device());
+    b.st = (hipStream_t)hip_stream;
+    ScopeStream scope(b.st);
+    // every distinct container's header, queued before the first drain
+    b.armed = true;
+    bool fetched = false;
+    for (PreviewsContainer& c : b.cs) {
+        c.d_alc = c.src;
+        if (!c.len) continue;
+        HIP_TRY(hipMemcpyAsync(c.raw, c.src, std::min<uint64_t>(c.len, kSplitHeaderBytes), hipMemcpyDeviceToHost, b.st));
+        fetched = true;
+    }
+    if (fetched) TRY(b.drain());
+    TRY(previews_validate(b, bad_item, [](const PreviewsContainer& c) { return c.raw; }));
+    TRY(previews_outputs_disjoint(b, bad_item));
+    TRY(previews_device(b, bad_item, true));
+    previews_done(b, 0);
+    return kOk;
+}
+
+uint8_t* alice_codec_decode_previews(const alice_codec_preview_item* items, uint32_t n_items, uint64_t* offsets, uint32_t* bad_item) {
+    clear_error();
+    PreviewsBatch b;
+    if (previews_collect(items, n_items, false, bad_item, b) != kOk) return nullptr;
+    if (!offsets) { fail(kNullArgument, "null argument"); return nullptr; }
+    if (previews_validate(b, bad_item, [](const PreviewsContainer& c) { return c.src; }) != kOk) return nullptr;
+    // per distinct container: the union of its items' planned blocks, and the spans that hold them
+    for (const PreviewsItem& it : b.items) {
+        std::vector<uint32_t>& u = b.cs[it.container].blocks;
+        std::vector<uint32_t> merged;
+        std::set_union(u.begin(), u.end(), it.p.blocks.begin(), it.p.blocks.end(), std::back_inserter(merged));
+        u.swap(merged);
+    }
+    uint64_t uploaded = 0, total = 0;
+    for (PreviewsContainer& c : b.cs) {
+        uint64_t payload = 0;
+        if (partial_spans(c.src, c.h, c.blocks, c.spans, payload) != kOk) { fail_item(c.first_item, bad_item, tl_err, std::string(tl_msg)); return nullptr; }
+        uploaded += payload;
+    }
+    for (const PreviewsItem& it : b.items) total += it.bytes;
+    std::unique_ptr<uint8_t, decltype(&free)> out(host_result_alloc(total), &free);   // freed on every failure below
+    if (!out) { fail(kOutOfMemory, "out of host memory"); return nullptr; }
+    auto run = [&]() -> int {
+        TRY(get_stream(&b.st));
+        TRY(b.d_rgb.alloc(total));
+        for (PreviewsContainer& c : b.cs) {
+            b.alcs.emplace_back(new DevBuf());
+            TRY(b.alcs.back()->alloc(c.len));
+            c.d_alc = b.alcs.back()->as<uint8_t>();
+        }
+        uint64_t at = 0;
+        for (PreviewsItem& it : b.items) { it.d_rgb = b.d_rgb.as<uint8_t>() + at; at += it.bytes; }
+        b.armed = true;
+        for (const PreviewsContainer& c : b.cs)
+            for (const PartialSpan& s : c.spans)
+                HIP_TRY(hipMemcpyAsync((uint8_t*)c.d_alc + s.off, c.src + s.off, s.len, hipMemcpyHostToDevice, b.st));
+        TRY(previews_device(b, bad_item, false));
+        ++b.drains;
+        return copy_to_host(out.get(), b.d_rgb.p, total, b.st);
+    };
+    if (run() != kOk) return nullptr;
+    uint64_t at = 0;
+    for (size_t k = 0; k < b.items.size(); ++k) { offsets[k] = at; at += b.items[k].bytes; }
+    offsets[b.items.size()] = at;
+    previews_done(b, uploaded);
+    return out.release();
+}
+
+void alice_codec_test_last_previews_stats(uint64_t out[9]) {
+    if (out) memcpy(out, tl_previews_stats, sizeof(tl_previews_stats));
 }
 
 }  // extern "C"

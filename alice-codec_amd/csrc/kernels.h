@@ -1,6 +1,8 @@
 // Kernel launch interface (host side) for the gfx950 ALICE-Codec path.
 #pragma once
 
+#include <vector>
+
 #include "common.h"
 
 namespace alice {
@@ -82,6 +84,9 @@ void launch_rans_table(const uint32_t* d_hist, RansTable* d_tables, int n_chains
                        const uint32_t* d_used = nullptr);
 void launch_rans_table_from_arrays(const uint16_t* d_cum, const uint16_t* d_freq, RansTable* d_table,
                                    hipStream_t st);
+// n tables in one launch: cum and freq are [n][256], table i comes out byte for byte what the call above writes for row i
+void launch_rans_tables_from_arrays(const uint16_t* d_cum, const uint16_t* d_freq, RansTable* d_tables, int n,
+                                    hipStream_t st);
 // chain c reads sym + c*sym_stride (n symbols) and writes its stream back-to-front into a cap-sized region;
 // the stream is the last results[c].len bytes of that region.  group_stride == 0: region c starts at
 // out + c*cap.  Otherwise chains 3g, 3g+1, 3g+2 write into chunk g's .alc buffer: region start =
@@ -192,6 +197,26 @@ constexpr int kPreviewGainOne = 65536;    // CDF 5/3, Haar: the low band's DC ga
 constexpr int kPreviewGain97 = 47484;     // CDF 9/7: round(65536 / g^2), g = 1.17480326 per spatial axis
 bool launch_preview_inverse(const void* d_sym, uint64_t pitch, uint64_t q, uint32_t planes, const FrameWindow& win, int format,
                             int wavelet, const int32_t step[3], bool exact, uint8_t* d_rgb, hipStream_t st);
+// The same finish over many volumes in one queue (the batched preview).  preview_records_plan checks
+// every item as launch_preview_inverse checks its arguments, groups the items by instance class (format x lifting steps x
+// exact: at most 12), writes their device records, class after class, to h_records (n * preview_record_bytes() bytes) and
+// names one launch per class present; false: an item is no such volume, nothing was written that matters.  After the
+// records have been copied to d_records, launch_preview_inverse_many runs one class: a flattened work list, so the grid is
+// the sum of the items' own workgroups whatever their sizes.
+struct PreviewFinish {
+    const void* d_sym;
+    uint64_t pitch, q;
+    uint32_t planes;
+    FrameWindow win;
+    int format, wavelet;
+    int32_t step[3];
+    bool exact;
+    uint8_t* d_rgb;
+};
+struct PreviewFinishLaunch { int cls; uint32_t first, count, grid; };   // records [first, first + count), `grid` workgroups
+size_t preview_record_bytes();
+bool preview_records_plan(const PreviewFinish* items, uint32_t n, void* h_records, std::vector<PreviewFinishLaunch>& launches);
+void launch_preview_inverse_many(const void* d_records, const PreviewFinishLaunch& l, hipStream_t st);
 
 // ---- transform.hip, stage level: Wavelet2D / Wavelet3D of caller-shaped i32 data on the tile kernels' exact instances ----
 // eligible: even width and height >= 6, even depth (or depth 1); otherwise the caller uses launch_wavelet_axis.

@@ -149,6 +149,25 @@ __global__ __launch_bounds__(256) void rans_table_from_arrays_kernel(const uint1
     if (s == 0) table->flags = flags_sh;
 }
 
+// The same over n tables in one launch (the batched preview): workgroup blockIdx.x builds
+// tables[blockIdx.x] from row blockIdx.x of cum and freq ([n][256]), byte for byte what the kernel above writes.
+__global__ __launch_bounds__(256) void rans_tables_from_arrays_kernel(const uint16_t* __restrict__ cum,
+                                                                      const uint16_t* __restrict__ freq,
+                                                                      RansTable* __restrict__ tables) {
+    __shared__ uint32_t scratch[768];
+    __shared__ uint32_t flags_sh;
+    const int s = threadIdx.x;
+    const size_t t = blockIdx.x;
+    RansTable* __restrict__ table = tables + t;
+    const uint32_t f = freq[t * 256 + s], c = cum[t * 256 + s];
+    if (s == 0) flags_sh = 0u;
+    table->enc[s] = make_enc_entry(f, c);
+    const uint32_t fl = build_dec_slots(f, c, scratch, &table->dec);
+    if (fl) atomicOr(&flags_sh, fl);
+    __syncthreads();
+    if (s == 0) table->flags = flags_sh;
+}
+
 // Two chains on one SIMD (more than 1024 chains in flight): the SIMD's issue arbiter prefers the OLDER wave, so the older
 // chain runs almost undisturbed and the younger one gets what is left -- and the step waits for the slowest chain.  Taking
 // turns was the proposed cure (round 2): every wave derives its priority from a bit of the shader clock
@@ -990,6 +1009,12 @@ void launch_rans_table(const uint32_t* d_hist, RansTable* d_tables, int n_chains
 void launch_rans_table_from_arrays(const uint16_t* d_cum, const uint16_t* d_freq, RansTable* d_table,
                                    hipStream_t st) {
     hipLaunchKernelGGL(rans_table_from_arrays_kernel, dim3(1), dim3(256), 0, st, d_cum, d_freq, d_table);
+}
+
+void launch_rans_tables_from_arrays(const uint16_t* d_cum, const uint16_t* d_freq, RansTable* d_tables, int n,
+                                    hipStream_t st) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(rans_tables_from_arrays_kernel, dim3((unsigned)n), dim3(256), 0, st, d_cum, d_freq, d_tables);
 }
 
 // A chain is one wavefront that runs for seconds, and waves never migrate: two chains that the dispatcher puts on one

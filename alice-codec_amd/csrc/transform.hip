@@ -19,6 +19,7 @@
 // How the roles of consecutive bands share launches: "Band-ordered, role-fused launches" below.
 // Half-resolution preview (preview_inv_kernel): the temporal role of the three channels in lock step
 // on the low-low quadrants, with the DC normalisation and the colour step fused behind it; no tile role.
+// preview_inv_many_kernel (section 17) runs the same body over a work list of many such volumes.
 //
 // Lifting facts used: inside one lifting step every write depends only on samples of the other
 // parity, so a step is data-parallel; an output depends on inputs within +-n_steps samples;
@@ -1012,12 +1013,18 @@ struct PreviewInv {
     int step[3];
     int gain;                    // K
 };
+// a record of preview_inv_many_kernel's work list
+struct PreviewInvItem {
+    PreviewInv a;
+    uint32_t wg_first;           // the record's first workgroup of the launch
+};
 
+// The finish of one record: workgroup `group` of it takes quadrant pixels [1024 group, 1024 group + 1024).  lut: the
+// workgroup's dequantise table (3 x 256 entries; unused by the wide instances).  Both entry points below run this body.
 template <int NS, bool EXACT, bool WIDE, bool MIRROR>
-__global__ __launch_bounds__(256) void preview_inv_kernel(PreviewInv a) {
+__device__ __forceinline__ void preview_inv_body(const PreviewInv& a, uint32_t group, int (&lut)[WIDE ? 1 : 3 * 256]) {
     static_assert(WIDE || !MIRROR, "the mirrored inverse belongs to a wide container (.alc v4)");
     using Sym4 = std::conditional_t<WIDE, uint2, uint32_t>;
-    __shared__ int lut[WIDE ? 1 : 3 * 256];
     const int tid = threadIdx.x;
     if constexpr (!WIDE) {
         const int s = tid;
@@ -1026,7 +1033,7 @@ __global__ __launch_bounds__(256) void preview_inv_kernel(PreviewInv a) {
         for (int ch = 0; ch < 3; ++ch) lut[ch * 256 + s] = (int)((unsigned)q * (unsigned)a.step[ch]);   // src/quant.rs:104-110 (wrapping)
         __syncthreads();
     }
-    const unsigned long long idx = ((unsigned long long)blockIdx.x * 256u + (unsigned)tid) * 4u;
+    const unsigned long long idx = ((unsigned long long)group * 256u + (unsigned)tid) * 4u;
     if (idx >= a.q) return;
     const int half = (int)(a.planes / 2u);
     int c[4];
@@ -1120,6 +1127,30 @@ __global__ __launch_bounds__(256) void preview_inv_kernel(PreviewInv a) {
         if (half >= 2) emit(2 * (half - 2) + 1, od);
     }
     emit(2 * (half - 1) + 1, last);
+}
+
+template <int NS, bool EXACT, bool WIDE, bool MIRROR>
+__global__ __launch_bounds__(256) void preview_inv_kernel(PreviewInv a) {
+    __shared__ int lut[WIDE ? 1 : 3 * 256];
+    preview_inv_body<NS, EXACT, WIDE, MIRROR>(a, blockIdx.x, lut);
+}
+
+// The finish over many records of one instance class (the batched preview): a flattened work list.
+// Record r owns the workgroups [wg_first, wg_first + ceil(q / 1024)) of the launch, the records in ascending wg_first with
+// recs[0].wg_first = 0, so the grid is exactly the sum of the records' workgroups: a 2x2 item beside a 1920x1080 one costs
+// one workgroup, not a grid row of early exits.  A workgroup finds its record by bisection (at most 10 wave-uniform loads
+// for 1024 records) and runs the one-record body on it; every per-item value -- the dequantise table, gain, coefficients,
+// window, pitch, q, output -- comes from the record.
+template <int NS, bool EXACT, bool WIDE, bool MIRROR>
+__global__ __launch_bounds__(256) void preview_inv_many_kernel(const PreviewInvItem* __restrict__ recs, uint32_t n) {
+    __shared__ int lut[WIDE ? 1 : 3 * 256];
+    uint32_t lo = 0u, hi = n;      // recs[lo].wg_first <= blockIdx.x < recs[hi].wg_first (hi == n: the end of the grid)
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (recs[mid].wg_first <= blockIdx.x) lo = mid; else hi = mid;
+    }
+    const PreviewInv a = recs[lo].a;
+    preview_inv_body<NS, EXACT, WIDE, MIRROR>(a, blockIdx.x - recs[lo].wg_first, lut);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1888,6 +1919,59 @@ bool launch_preview_inverse(const void* d_sym, uint64_t pitch, uint64_t q, uint3
     return true;
 }
 
+size_t preview_record_bytes() { return sizeof(PreviewInvItem); }
+
+template <int NS, bool EXACT>
+static void preview_many_launch(const PreviewInvItem* d_recs, uint32_t n, unsigned grid, int format, hipStream_t st) {
+    if (format == 2) hipLaunchKernelGGL((preview_inv_many_kernel<NS, EXACT, true, true>), dim3(grid), dim3(256), 0, st, d_recs, n);
+    else if (format == 1) hipLaunchKernelGGL((preview_inv_many_kernel<NS, EXACT, true, false>), dim3(grid), dim3(256), 0, st, d_recs, n);
+    else hipLaunchKernelGGL((preview_inv_many_kernel<NS, EXACT, false, false>), dim3(grid), dim3(256), 0, st, d_recs, n);
+}
+
+// instance class of a finish: format (3) x lifting steps (2) x exact (2)
+static int preview_class(const PreviewFinish& f) { return (f.format * 2 + (lift_steps(f.wavelet).n == 4 ? 1 : 0)) * 2 + (f.exact ? 1 : 0); }
+
+bool preview_records_plan(const PreviewFinish* items, uint32_t n, void* h_records, std::vector<PreviewFinishLaunch>& launches) {
+    launches.clear();
+    std::vector<uint32_t> order(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const PreviewFinish& f = items[i];
+        if (f.format < 0 || f.format > 2 || !f.q || f.planes < 2 || (f.planes & 1u) || !(f.win.lo < f.win.hi && f.win.hi <= f.planes) ||
+            f.pitch < f.q || (f.pitch & 3u))
+            return false;
+        order[i] = i;
+    }
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return preview_class(items[x]) < preview_class(items[y]); });
+    PreviewInvItem* recs = (PreviewInvItem*)h_records;
+    for (uint32_t k = 0; k < n; ++k) {
+        const PreviewFinish& f = items[order[k]];
+        const int cls = preview_class(f);
+        if (launches.empty() || launches.back().cls != cls) launches.push_back(PreviewFinishLaunch{cls, k, 0u, 0u});
+        PreviewFinishLaunch& l = launches.back();
+        const uint64_t wgs = (f.q + 1023u) / 1024u;
+        if (wgs > 0x7FFFFFFFull - l.grid) return false;
+        const LiftSteps ls = lift_steps(f.wavelet);
+        PreviewInvItem r{};
+        r.a.sym = f.d_sym; r.a.rgb = f.d_rgb; r.a.pitch = f.pitch; r.a.q = f.q; r.a.planes = f.planes; r.a.lo = f.win.lo; r.a.hi = f.win.hi;
+        r.a.cf = to_coeffs(ls);
+        r.a.step[0] = f.step[0]; r.a.step[1] = f.step[1]; r.a.step[2] = f.step[2];
+        r.a.gain = ls.n == 4 ? kPreviewGain97 : kPreviewGainOne;
+        r.wg_first = l.grid;
+        recs[k] = r;
+        l.grid += (uint32_t)wgs;
+        ++l.count;
+    }
+    return true;
+}
+
+void launch_preview_inverse_many(const void* d_records, const PreviewFinishLaunch& l, hipStream_t st) {
+    if (!l.count || !l.grid) return;
+    const PreviewInvItem* recs = (const PreviewInvItem*)d_records + l.first;
+    const int format = l.cls / 4;
+    const bool ns4 = (l.cls / 2) & 1, exact = l.cls & 1;
+    if (ns4) { if (exact) preview_many_launch<4, true>(recs, l.count, l.grid, format, st); else preview_many_launch<4, false>(recs, l.count, l.grid, format, st); }
+    else { if (exact) preview_many_launch<2, true>(recs, l.count, l.grid, format, st); else preview_many_launch<2, false>(recs, l.count, l.grid, format, st); }
+}
 
 bool stage_tiles_eligible(uint64_t w, uint64_t h, uint64_t depth, int ndim) {
     if (ndim < 2 || (w & 1) || (h & 1) || w < 6 || h < 6) return false;

@@ -1308,6 +1308,54 @@ pub unsafe fn preview_decode_device(d_alc: *const std::ffi::c_void, length: u64,
     check(alice_codec_dev_decode_preview(d_alc, length, first, count, d_rgb_out, hip_stream), 0, 0)
 }
 
+// ---- many previews in one call ----
+
+/// `alice_codec_preview_item` of include/alice_codec.h
+#[repr(C)]
+#[derive(Debug, Clone, Copy)]
+pub struct PreviewItem {
+    pub alc: *const std::ffi::c_void,
+    pub len: u64,
+    pub first: u32,
+    pub count: u32,
+    pub rgb_out: *mut std::ffi::c_void,
+}
+
+pub const PREVIEWS_MAX_ITEMS: u32 = 1024;
+
+extern "C" {
+    fn alice_codec_decode_previews(items: *const PreviewItem, n_items: u32, offsets: *mut u64, bad_item: *mut u32) -> *mut u8;
+    fn alice_codec_dev_decode_previews(items: *const PreviewItem, n_items: u32, bad_item: *mut u32,
+                                       hip_stream: *mut std::ffi::c_void) -> c_int;
+}
+
+/// `decode_preview` of many `(data, first, count)` items in one call, one `Vec` per item in item order.  Items that pass the
+/// same slice share its header, tables, directory scan and upload.  All or nothing: the message of the error of a refused
+/// or damaged call starts with `item <index>: `.
+pub fn decode_previews(items: &[(&[u8], u32, u32)]) -> Result<Vec<Vec<u8>>, CodecError> {
+    let raw: Vec<PreviewItem> = items.iter().map(|(d, first, count)| PreviewItem {
+        alc: d.as_ptr() as *const std::ffi::c_void, len: d.len() as u64, first: *first, count: *count, rgb_out: std::ptr::null_mut(),
+    }).collect();
+    let mut offsets = vec![0u64; items.len() + 1];
+    let n = u32::try_from(items.len()).unwrap_or(u32::MAX);
+    unsafe {
+        let p = alice_codec_decode_previews(raw.as_ptr(), n, offsets.as_mut_ptr(), std::ptr::null_mut());
+        if p.is_null() { return Err(last_error(0, 0, 0, 0, 0)); }
+        let whole = take(p, offsets[items.len()]);
+        Ok((0..items.len()).map(|i| whole[offsets[i] as usize..offsets[i + 1] as usize].to_vec()).collect())
+    }
+}
+
+/// `preview_decode_device` of many items in one call; returns the index of the item that decided a refusal with the error.
+///
+/// # Safety
+/// As `preview_decode_device` for every item; the outputs must not overlap.
+pub unsafe fn previews_decode_device(items: &[PreviewItem], hip_stream: *mut std::ffi::c_void) -> Result<(), (CodecError, u32)> {
+    let mut bad = u32::MAX;
+    let n = u32::try_from(items.len()).unwrap_or(u32::MAX);
+    check(alice_codec_dev_decode_previews(items.as_ptr(), n, &mut bad, hip_stream), 0, 0).map_err(|e| (e, bad))
+}
+
 // ---- a spatial rectangle of a frame range of a version 2, 3 or 4 chunk ----
 
 extern "C" {

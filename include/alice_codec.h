@@ -728,6 +728,42 @@ uint8_t *alice_codec_decode_preview(const uint8_t *data, uint64_t len, uint32_t 
 int alice_codec_dev_decode_preview(const void *d_alc, uint64_t len, uint32_t first, uint32_t count, void *d_rgb_out,
                                    void *hip_stream);
 
+/* ---- Many previews in one call ----
+ * A contact sheet wants one frame of each of N chunks, a scrub bar every k-th frame of one chunk.  These calls take an array
+ * of items; every item alone means exactly what alice_codec_dev_decode_preview(alc, len, first, count, rgb_out, stream)
+ * means, bit for bit.  Items may mix versions 2, 3 and 4, the wavelets, dimensions and lane sizes, and any number of items
+ * may name the same container (the same pointer and the same len): such items share one header fetch, one validation, one
+ * set of tables and one directory scan.  One launch builds every table, one covers every directory, one lane launch per
+ * symbol width decodes the planned blocks of all items, and the finish runs once per instance class present.
+ * ALL OR NOTHING.  Validation: items NULL (ALICE_ERR_NULL_ARGUMENT), n_items 0 or above ALICE_PREVIEWS_MAX_ITEMS
+ * (ALICE_ERR_INVALID_DIMENSIONS), a NULL alc -- or, dev call, rgb_out -- in an item (ALICE_ERR_NULL_ARGUMENT), then
+ * alice_codec_decode_frames' checks, in its order and with its codes, item after item; the dev call then refuses two items
+ * whose output byte ranges overlap (ALICE_ERR_INVALID_DIMENSIONS, the later item of the pair).  The first item that fails
+ * decides the code, *bad_item (when not NULL) receives its index and the message starts with "item <index>: "; a refusal
+ * that is no item's leaves *bad_item = 0xFFFFFFFF.  A refused call queues nothing and writes nothing.  INTEGRITY: the end
+ * checks of all items are read in one copy before anything that writes an output is queued; a directory that does not add
+ * up or a failed lane in a planned block of any item is ALICE_ERR_INVALID_BITSTREAM for the whole call with *bad_item the
+ * first such item, and no output is written, the clean items' included.  Damage in a block no item plans is not seen.
+ * Memory comes from the library's pool; nothing goes through the chain hub. */
+typedef struct alice_codec_preview_item {
+    const void *alc;       /* the container: device memory for the dev call, host memory for the host call */
+    uint64_t    len;
+    uint32_t    first, count;
+    void       *rgb_out;   /* dev call: count * qh * qw * 3 packed bytes go here; host call: ignored */
+} alice_codec_preview_item;
+
+#define ALICE_PREVIEWS_MAX_ITEMS 1024u
+
+/* Containers on the device (any byte alignment), outputs on the device (any byte alignment, disjoint, not overlapping a
+ * container).  The stream is drained at most three times: after the header fetches of all distinct containers, at the
+ * verdict, and at the end.  Finished on return. */
+int alice_codec_dev_decode_previews(const alice_codec_preview_item *items, uint32_t n_items, uint32_t *bad_item, void *hip_stream);
+/* Containers in host memory (they may be mapped files) -> one buffer (free with alice_codec_data_free64(ptr,
+ * offsets[n_items])), NULL on error; item i is at [offsets[i], offsets[i + 1]), in item order.  Per distinct container the
+ * 1630-byte header, the three block-length tables and the byte runs of the union of its items' planned blocks go up, once.
+ * offsets (n_items + 1 entries) is left alone on a refusal. */
+uint8_t *alice_codec_decode_previews(const alice_codec_preview_item *items, uint32_t n_items, uint64_t *offsets, uint32_t *bad_item);
+
 /* ---- A spatial rectangle of a frame range of a version 2, 3 or 4 chunk ----
  * The spatial transform is one lifting level per axis and every axis of a channel's [t'][y][x] symbol volume is stored as
  * [low | high], so the frame-range rule above holds on x and on y as it holds on t.  With pw, ph the padded width and

@@ -782,6 +782,29 @@ inline void preview_decode_device(const void* d_alc, uint64_t length, uint32_t f
     detail::check(alice_codec_dev_decode_preview(d_alc, length, first, count, d_rgb_out, hip_stream));
 }
 
+// ---- many previews in one call ----
+// All or nothing: the CodecError of a refused or damaged call starts with "item <index>: " when an item decided it.
+struct PreviewRequest { const uint8_t* data; uint64_t len; uint32_t first, count; };   // host call: one item
+inline std::vector<std::vector<uint8_t>> decode_previews(const std::vector<PreviewRequest>& requests) {
+    std::vector<alice_codec_preview_item> items(requests.size());
+    for (size_t i = 0; i < requests.size(); ++i) items[i] = alice_codec_preview_item{requests[i].data, requests[i].len, requests[i].first, requests[i].count, nullptr};
+    std::vector<uint64_t> offsets(requests.size() + 1, 0);
+    static const alice_codec_preview_item none{};   // (an empty vector has no data(): the count is what the library refuses)
+    uint8_t* p = alice_codec_decode_previews(items.empty() ? &none : items.data(), (uint32_t)std::min<size_t>(items.size(), 0xFFFFFFFFu),
+                                             offsets.data(), nullptr);
+    if (!p) detail::raise(ALICE_ERR_INVALID_BITSTREAM);
+    std::vector<std::vector<uint8_t>> out(requests.size());
+    for (size_t i = 0; i < requests.size(); ++i) out[i].assign(p + offsets[i], p + offsets[i + 1]);
+    alice_codec_data_free64(p, offsets.back());
+    return out;
+}
+// device call: containers and outputs on the device, the items as the C ABI declares them; *bad_item as there
+inline void previews_decode_device(const std::vector<alice_codec_preview_item>& items, void* hip_stream = nullptr, uint32_t* bad_item = nullptr) {
+    static const alice_codec_preview_item none{};
+    detail::check(alice_codec_dev_decode_previews(items.empty() ? &none : items.data(), (uint32_t)std::min<size_t>(items.size(), 0xFFFFFFFFu),
+                                                  bad_item, hip_stream));
+}
+
 // ---- a spatial rectangle of a frame range of a version 2, 3 or 4 chunk ----
 // the w x h pixels at (x, y) of frames [first, first + count) from the blocks they need: count * h * w * 3 packed RGB bytes,
 // or (device call, non-zero pitches) pasted into a pitched surface such as full-size frames

@@ -143,6 +143,13 @@ void alice_codec_test_last_frames_stats(uint64_t out[5]);
  * blocks; 0 for the device call), frames written, symbols stored over the three channels (3 (b - a) qw qh)}. */
 void alice_codec_test_last_preview_stats(uint64_t out[6]);
 
+/* The last alice_codec_decode_previews / alice_codec_dev_decode_previews of the calling thread that ran to its end (a
+ * refused call leaves it alone; the single-item calls above never touch it): out = {items, distinct containers, table
+ * launches, lane launches, finish launches, stream drains, blocks decoded over all items and channels, payload bytes the
+ * host call uploaded (the union of the planned blocks per distinct container; 0 for the device call), symbols stored over
+ * all items and channels}. */
+void alice_codec_test_last_previews_stats(uint64_t out[9]);
+
 /* The last alice_codec_decode_rect / alice_codec_dev_decode_rect of the calling thread that reached the device:
  * out = {ta, tb, xa, xb, ya, yb of the three windows, blocks decoded over the three channels, payload bytes the host call
  * uploaded (the planned blocks; 0 for the device call), frames written, symbols stored over the three channels
