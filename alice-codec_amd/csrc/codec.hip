@@ -2850,10 +2850,13 @@ int alice_codec_test_set_admission_budget(uint64_t bytes) {
     return kOk;
 }
 
-int alice_codec_test_decode_chains(uint32_t n_chains, const void* const* d_streams, const uint64_t* lens, const uint16_t* cum_freq,
-                                   const uint16_t* freq, void* const* d_symbols, uint64_t n, uint32_t* out, void* hip_stream) {
+// ns != nullptr: chain c decodes ns[c] symbols (alice_codec_test_decode_chains_n); else every chain decodes n
+static int test_decode_chains(uint32_t n_chains, const void* const* d_streams, const uint64_t* lens, const uint16_t* cum_freq,
+                              const uint16_t* freq, void* const* d_symbols, uint64_t n, const uint64_t* ns, uint32_t* out, void* hip_stream) {
     clear_error();
-    if (!n_chains || !d_streams || !lens || !cum_freq || !freq || !d_symbols || !out || !n) return fail(kNullArgument, "null argument");
+    if (!n_chains || !d_streams || !lens || !cum_freq || !freq || !d_symbols || !out || (!ns && !n)) return fail(kNullArgument, "null argument");
+    for (uint32_t c = 0; ns && c < n_chains; ++c)
+        if (!ns[c]) return fail(kNullArgument, "null argument");
     TRY(ensure_device());
     hipStream_t st = (hipStream_t)hip_stream;
     ScopeStream scope(st);
@@ -2868,7 +2871,7 @@ int alice_codec_test_decode_chains(uint32_t n_chains, const void* const* d_strea
     std::vector<RansDecodeDesc> descs(n_chains);
     for (uint32_t c = 0; c < n_chains; ++c) {
         launch_rans_table_from_arrays(arrays + 512 * (size_t)c, arrays + 512 * (size_t)c + 256, tables + c, st);
-        descs[c] = RansDecodeDesc{(const uint8_t*)d_streams[c], lens[c], (uint8_t*)d_symbols[c], n, tables + c, 0u, 0u, 0ull, nullptr};
+        descs[c] = RansDecodeDesc{(const uint8_t*)d_streams[c], lens[c], (uint8_t*)d_symbols[c], ns ? ns[c] : n, tables + c, 0u, 0u, 0ull, nullptr};
     }
     HIP_TRY(hipMemcpyAsync(ddesc.p, descs.data(), descs.size() * sizeof(RansDecodeDesc), hipMemcpyHostToDevice, st));
     launch_rans_decode(ddesc.as<RansDecodeDesc>(), dres.as<RansResult>(), (int)n_chains, st);
@@ -2883,6 +2886,15 @@ int alice_codec_test_decode_chains(uint32_t n_chains, const void* const* d_strea
         if (res[c].flags & kRansInternal) return fail(kInternal, "rANS decode kernel invariant violated");
     }
     return kOk;
+}
+int alice_codec_test_decode_chains(uint32_t n_chains, const void* const* d_streams, const uint64_t* lens, const uint16_t* cum_freq,
+                                   const uint16_t* freq, void* const* d_symbols, uint64_t n, uint32_t* out, void* hip_stream) {
+    return test_decode_chains(n_chains, d_streams, lens, cum_freq, freq, d_symbols, n, nullptr, out, hip_stream);
+}
+int alice_codec_test_decode_chains_n(uint32_t n_chains, const void* const* d_streams, const uint64_t* lens, const uint16_t* cum_freq,
+                                     const uint16_t* freq, void* const* d_symbols, const uint64_t* ns, uint32_t* out, void* hip_stream) {
+    if (!ns) return fail(kNullArgument, "null argument");
+    return test_decode_chains(n_chains, d_streams, lens, cum_freq, freq, d_symbols, 0ull, ns, out, hip_stream);
 }
 
 // out_stride: 6 (alice_codec_test_encode_chains) or 7 (..._blocks: RansResult.comp_blocks behind the six)

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
-"""Generates rans_decode_tile.inc: the inline-asm body of the rANS decode fast tile (gfx950).
+"""Generates rans_decode_tile.inc and rans_decode_tile_vec.inc: the inline-asm bodies of the rANS decode fast tile (gfx950).
 
-    python gen_rans_decode_asm.py        writes ../rans_decode_tile.inc
+    python gen_rans_decode_asm.py        writes ../rans_decode_tile.inc (classic and dry tile) and ../rans_decode_tile_vec.inc
 
-fast_tile() and dry_tile() return the instruction lists, so the program can be checked without a GPU
-(tests/test_decode_tile_model.py interprets them); main() writes the file.
+fast_tile(), vector_tile() and dry_tile() return the instruction lists, so the programs can be checked without a GPU
+(tests/test_decode_tile_model.py and tests/test_decode_tile_vec_model.py interpret them); main() writes the files.
+The vector tile (state update on the vector side, ten slots per symbol) is described where it is defined, below render().
 
 Costs measured on MI355X with scripts/probes/latency_probe.hip (one wave alone on its SIMD):
   any SALU or VALU instruction ~4 cycles; the first SALU instruction after a VALU instruction that wrote
@@ -113,7 +114,7 @@ def refill():
             "s_xor_b64 s[62:63], s[62:63], s[66:67]"]
 
 
-def fast_tile(loop_phase=LOOP_PHASE):
+def fast_tile(loop_phase=LOOP_PHASE, symbol=lookup_update):
     L = table_loads()
     for r in range(WIN_ROWS):
         L.append(f"ds_read_b32 v{192 + r}, %[wa] offset:{256 * r}")
@@ -154,7 +155,7 @@ def fast_tile(loop_phase=LOOP_PHASE):
     # amount in the pair tail.
     for lane in range(64):
         sh = "s77" if lane & 1 else "s71"
-        L += lookup_update(lane)
+        L += symbol(lane)
         L.append("s_flbit_i32_b32 m0, s61")
         # one instruction must sit between the SALU write of M0 and s_movrels (wait state): the copy for the even symbol,
         # the window shift that the even symbol owes for the odd one (it touches neither M0 nor the table)
@@ -223,11 +224,60 @@ def render(loop_phase=LOOP_PHASE):
             macro("ALICE_DEC_DRY_TILE_ASM", dry_tile()) + clobbers("ALICE_DEC_DRY_TILE_CLOBBERS", dry_clobbers()))
 
 
+# ---- the vector tile: the state update on the vector side, one lane read per symbol ------------------------------------
+# The classic symbol carries F' and B' across to the scalar unit with one v_readlane each and combines them there
+# (s_mul_hi, s_add).  The vector unit can do umulhi(F', x) + B' for the whole table row at once -- x is an SGPR operand,
+# every lane computes the update its slot would give -- and one v_readlane of lane x[5:0] brings back the finished x':
+#     s_bfe / s_set_gpr_idx_on row, 0x6 / v_mul_hi_u32 / v_add_u32 / v_writelane (record) / v_readlane / s_flbit ...
+# ten slots instead of eleven.  Mode 0x6 is SRC1_REL | SRC2_REL (M0 bits 13 and 14): the table rows are the src1 operands
+# of the multiply and the add, while src0 (x, the scratch row, the source of v_readlane) and every destination stay where
+# they are named, and v_readlane's src1 is an SGPR, which the mode does not touch (scripts/probes/gpr_idx_probe.hip).
+# The record takes the pre-update state, so its v_writelane sits in front of the v_readlane that overwrites s61; it is
+# independent of the multiply-add and stands as the one wait state that gfx940 and later want between a VALU write of a
+# VGPR (the add) and a v_readlane of it.  Everything else -- pair structure, sentinel
+# window, refill, shift table, block end, M0 save / restore -- is the classic tile's, and so are the tables: a
+# frequency-4096 entry is F' = 2^32 - 1 and right for x >= 1 here as there.
+VT = REC + 1    # scratch row: the updated state of every slot of the current table row
+
+
+def lookup_update_vector(lane):
+    return ["s_bfe_u32 s76, s61, 0x60006",
+            "s_set_gpr_idx_on s76, 0x6",
+            f"v_mul_hi_u32 v{VT}, s61, v64",               # src1 relative: the F' row
+            f"v_add_u32_e64 v{VT}, v{VT}, v128",           # src1 relative: the B' row
+            f"v_writelane_b32 v{REC}, s61, {lane}",        # the pre-update state, before s61 goes
+            f"v_readlane_b32 s61, v{VT}, s61"]             # src0 not relative; the hardware masks the lane select to 6 bits
+
+
+def vector_tile(loop_phase=LOOP_PHASE):
+    """fast_tile() with lookup_update_vector() as the symbol body.  The refills and the window priming read the window rows
+    as src0 of a v_readlane and switch to mode 0x1 for that, as the classic tile does; the next symbol sets 0x6 again."""
+    return fast_tile(loop_phase, lookup_update_vector)
+
+
+def vector_clobbers():
+    return fast_clobbers() + [f"v{VT}"]
+
+
+def render_vector(loop_phase=LOOP_PHASE):
+    def macro(name, lines):
+        return f"#define {name} \\\n" + "".join(f'    "{s}\\n\\t" \\\n' for s in lines) + '    ""\n'
+
+    return ("// GENERATED by gen/gen_rans_decode_asm.py -- do not edit.\n" +
+            macro("ALICE_DEC_TILE_VEC_ASM", vector_tile(loop_phase)) +
+            "#define ALICE_DEC_TILE_VEC_CLOBBERS " + ", ".join(f'"{c}"' for c in vector_clobbers()) + "\n")
+
+
 def main():
-    out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "rans_decode_tile.inc")
+    here = os.path.dirname(os.path.abspath(__file__))
+    out = os.path.join(here, "..", "rans_decode_tile.inc")
     with open(out, "w") as f:
         f.write(render())
     print("wrote", out, len(fast_tile()), "asm lines")
+    out = os.path.join(here, "..", "rans_decode_tile_vec.inc")
+    with open(out, "w") as f:
+        f.write(render_vector())
+    print("wrote", out, len(vector_tile()), "asm lines")
 
 
 if __name__ == "__main__":

@@ -28,6 +28,11 @@ int alice_codec_test_decode_chains(uint32_t n_chains, const void *const *d_strea
                                    const uint16_t *cum_freq, const uint16_t *freq, void *const *d_symbols, uint64_t n,
                                    uint32_t *out, void *hip_stream);
 
+/* The same launch with a symbol count per chain: chain c decodes ns[c] symbols. */
+int alice_codec_test_decode_chains_n(uint32_t n_chains, const void *const *d_streams, const uint64_t *lens,
+                                     const uint16_t *cum_freq, const uint16_t *freq, void *const *d_symbols,
+                                     const uint64_t *ns, uint32_t *out, void *hip_stream);
+
 /* ONE launch of n_chains encode chains on device buffers (csrc/rans.hip, launch_rans_encode_descs: up to 1024 chains run
  * the one-chain-per-SIMD instance of the kernel, more run the plain one).  Chain c encodes the ns[c] symbols at d_symbols[c]
  * (any byte alignment) back to front into [d_regions[c], d_regions[c] + caps[c]); its stream is the LAST len bytes of that

@@ -25,7 +25,7 @@ __global__ __launch_bounds__(64) void NAME(unsigned long long* out, uint32_t see
     "s_memtime %[t1]\n\t s_waitcnt lgkmcnt(0)\n\t"                                            \
     "s_set_gpr_idx_off\n\t"                                                                   \
     : [t0] "=&s"(t0), [t1] "=&s"(t1), [cnt] "=&s"(cnt) : [seed] "s"(seed)                     \
-    : "s40","s41","s42","s43","s44","s45","s46","s47","v40","v41","v42","v43","v44","v45","v46","v47","v48","v49","vcc","scc","m0","memory"); \
+    : "s40","s41","s42","s43","s44","s45","s46","s47","s48","s49","s50","s51","v40","v41","v42","v43","v44","v45","v46","v47","v48","v49","vcc","scc","m0","memory"); \
   if (threadIdx.x == 0) out[0] = t1 - t0;                                                     \
 }
 
@@ -74,6 +74,35 @@ PROBE_KERNEL(k_enc_clean9, "v_add_u32_dpp v40, v44, v41 wave_shr:1 row_mask:0xf 
 PROBE_KERNEL(k_enc_comp8, "v_add_u32_dpp v40, v44, v41 wave_shr:1 row_mask:0xf bank_mask:0xf\n\t v_ashrrev_i32_e32 v46, 8, v40\n\t v_add_u32_e32 v46, v46, v41\n\t v_min_u32_e32 v45, v40, v46\n\t v_mul_hi_u32 v43, v45, v41\n\t v_lshrrev_b32_e32 v43, v42, v43\n\t v_mad_i32_i24 v44, v43, v42, v45\n\t s_nop 1\n\t")
 PROBE_KERNEL(k_enc_comp7, "v_add_u32_dpp v40, v44, v41 wave_shr:1 row_mask:0xf bank_mask:0xf\n\t v_mad_i64_i32 v[46:47], s[46:47], v40, v41, v[48:49]\n\t v_min_u32_e32 v45, v40, v47\n\t v_mul_hi_u32 v43, v45, v41\n\t v_lshrrev_b32_e32 v43, v42, v43\n\t v_mad_i32_i24 v44, v43, v42, v45\n\t s_nop 1\n\t")
 PROBE_KERNEL(k_vmad_i64_i32, "v_mad_i64_i32 v[46:47], s[46:47], v47, v41, v[48:49]\n\t")
+
+// The decode symbol with the state update on the vector side (csrc/gen/gen_rans_decode_asm.py: vector_tile).  All rows are
+// dependent chains on the state (s40, or s41 / s47 in turn for candidate B); the index register s43 is 0 and v40 / v41 stand
+// in for the F' / B' rows, so every relative operand stays inside the registers this kernel owns.  M0 = 8 after the s_flbit
+// (s44 = 2^23), so s_movrels reads s50.
+//   dec: classic   today's even symbol: two table readlanes, the record, s_mul_hi + s_add (11 slots)
+//   dec: A         rows as src1 of v_mul_hi / v_add (mode 0x6), record, ONE readlane (10 slots)
+//   dec: B pair    A plus the shift on the vector side ((clz - 1, saturated) & 24 per lane, a second readlane by the old
+//                  state), no s_flbit / filler / s_movrels; the window copy and the two window shifts take slots of their
+//                  own; two symbols, states in s41 and s47 in turn; no compare / branch
+// gfx940 and later want one wait state between a VALU write of a VGPR and a v_readlane of it: the record's v_writelane (A)
+// and the v_ffbh / v_writelane (B) stand there.
+PROBE_KERNEL(k_dec_classic, "s_bfe_u32 s45, s40, 0x60006\n\t s_set_gpr_idx_on s43, 0x1\n\t v_readlane_b32 s47, v40, s40\n\t v_readlane_b32 s46, v41, s40\n\t v_writelane_b32 v44, s40, 3\n\t s_mul_hi_u32 s45, s47, s40\n\t s_add_u32 s40, s45, s46\n\t s_flbit_i32_b32 m0, s44\n\t s_mov_b32 s46, s41\n\t s_movrels_b32 s45, s42\n\t s_lshl_b64 s[40:41], s[40:41], s43\n\t")
+PROBE_KERNEL(k_dec_vec_a, "s_bfe_u32 s45, s40, 0x60006\n\t s_set_gpr_idx_on s43, 0x6\n\t v_mul_hi_u32 v45, s40, v40\n\t v_add_u32_e64 v45, v45, v41\n\t v_writelane_b32 v44, s40, 3\n\t v_readlane_b32 s40, v45, s40\n\t s_flbit_i32_b32 m0, s44\n\t s_mov_b32 s46, s41\n\t s_movrels_b32 s45, s42\n\t s_lshl_b64 s[40:41], s[40:41], s43\n\t")
+#define DEC_B_SYM(X, XN, COPY) "s_bfe_u32 s48, " X ", 0x60006\n\t s_set_gpr_idx_on s43, 0x6\n\t v_mul_hi_u32 v45, " X ", v40\n\t v_add_u32_e64 v45, v45, v41\n\t v_ffbh_u32_e32 v46, v45\n\t v_readlane_b32 " XN ", v45, " X "\n\t v_sub_u32_e64 v46, v46, 1 clamp\n\t v_and_b32_e32 v46, 24, v46\n\t v_writelane_b32 v44, " X ", 3\n\t v_readlane_b32 s42, v46, " X "\n\t" COPY
+PROBE_KERNEL(k_dec_vec_b, DEC_B_SYM("s41", "s47", "s_mov_b32 s46, s45\n\t s_lshl_b64 s[46:47], s[46:47], s42\n\t s_lshl_b64 s[44:45], s[44:45], s42\n\t")
+                          DEC_B_SYM("s47", "s41", "s_mov_b32 s40, s46\n\t s_lshl_b64 s[40:41], s[40:41], s42\n\t s_lshl_b64 s[44:45], s[44:45], s42\n\t"))
+// the VALU -> SALU crossing: does the stall count from the first or from the last VALU write of an SGPR, and do VALU
+// instructions between the lane read and the first SALU instruction ride in it for nothing?
+#define VALU4 "v_add_u32_e32 v44, v41, v42\n\t v_xor_b32_e32 v46, v41, v42\n\t v_add_u32_e32 v47, v41, v42\n\t v_xor_b32_e32 v48, v41, v42\n\t"
+#define VALU3 "v_add_u32_e32 v44, v41, v42\n\t v_xor_b32_e32 v46, v41, v42\n\t v_add_u32_e32 v47, v41, v42\n\t"
+PROBE_KERNEL(k_cross_0, "v_readlane_b32 s45, v40, s42\n\t s_add_u32 s40, s45, s40\n\t")
+PROBE_KERNEL(k_cross_4valu, "v_readlane_b32 s45, v40, s42\n\t" VALU4 "s_add_u32 s40, s45, s40\n\t")
+PROBE_KERNEL(k_cross_3valu_readlane, "v_readlane_b32 s45, v40, s42\n\t" VALU3 "v_readlane_b32 s46, v41, s42\n\t s_add_u32 s40, s45, s40\n\t")
+PROBE_KERNEL(k_valu4, VALU4)
+// the multiply of candidate A (a table row as relative src1, the state as an SGPR) against the 24-bit multiply-add;
+// both rows carry an s_set_gpr_idx_on, whose own row is above
+PROBE_KERNEL(k_vmulhi_rel, "s_set_gpr_idx_on s43, 0x6\n\t v_mul_hi_u32 v45, s41, v45\n\t")
+PROBE_KERNEL(k_vmad24_rel, "s_set_gpr_idx_on s43, 0x6\n\t v_mad_u32_u24 v45, s41, v45, v41\n\t")
 
 // What the seventh slot of the complement step (its closing s_nop 1: the two wait states between the VALU write of z
 // and the DPP read) can carry for nothing.  The same six chain instructions as k_enc_comp7, then the filler.  These
@@ -149,9 +178,17 @@ int main(int argc, char** argv) {
     {"comp step + 2 VALU", k_fill_valu2}, {"comp step + ds_read_b128 (used 16 steps on) + s_nop 0", k_fill_ds_read},
     {"comp step + global_store_byte + s_nop 0", k_fill_store_byte}, {"comp step + SALU + s_nop 0", k_fill_salu_nop0},
     {"comp step + v_cmp to SGPR pair + s_nop 0", k_fill_vcmp_sgpr}, {"comp step + v_mov_dpp + s_nop 0", k_fill_dpp_mov},
-    {"comp step + VALU alone", k_fill_valu_only}, {"comp step + s_nop 0", k_fill_nop0}};
+    {"comp step + VALU alone", k_fill_valu_only}, {"comp step + s_nop 0", k_fill_nop0},
+    {"dec: classic symbol (11 slots)", k_dec_classic}, {"dec: A symbol (10 slots)", k_dec_vec_a},
+    {"dec: B symbol pair (2 x 13 slots)", k_dec_vec_b},
+    {"dec: v_readlane; SALU", k_cross_0}, {"dec: v_readlane; 4 x VALU; SALU", k_cross_4valu},
+    {"dec: v_readlane; 3 x VALU; v_readlane; SALU", k_cross_3valu_readlane}, {"dec: 4 x VALU", k_valu4},
+    {"dec: s_set_gpr_idx_on 0x6; v_mul_hi_u32 s, v(rel)", k_vmulhi_rel},
+    {"dec: s_set_gpr_idx_on 0x6; v_mad_u32_u24 s, v(rel), v(rel)", k_vmad24_rel}};
   double base = 0;
   FILE* js = argc > 1 ? fopen(argv[1], "w") : nullptr;   // the "comp step + ..." rows as JSON (cycles per step)
+  FILE* jd = argc > 2 ? fopen(argv[2], "w") : nullptr;   // the "dec: ..." rows as JSON (cycles per copy)
+  if (jd) fprintf(jd, "{\n  \"what\": \"scripts/probes/latency_probe.hip: the decode symbol with the state update on the vector side, one wave alone; shader cycles per copy of the row's snippet, best of 5 launches, empty loop subtracted\"");
   if (js) fprintf(js, "{\n  \"what\": \"scripts/probes/latency_probe.hip: the 7-slot complement step on one wave alone, its closing s_nop 1 replaced by fillers; shader cycles per step, best of 5 launches, empty loop subtracted\"");
   for (auto& t : tests) {
     unsigned long long best = ~0ull;
@@ -165,7 +202,10 @@ int main(int argc, char** argv) {
     printf("%-40s %8.2f cycles/copy\n", t.name, ((double)best - base) / (256.0 * 32.0) + (std::string(t.name) == "empty loop" ? per : 0));
     if (js && std::string(t.name).rfind("comp step + ", 0) == 0)
       fprintf(js, ",\n  \"%s\": %.2f", t.name, ((double)best - base) / (256.0 * 32.0));
+    if (jd && std::string(t.name).rfind("dec: ", 0) == 0)
+      fprintf(jd, ",\n  \"%s\": %.2f", t.name + 5, ((double)best - base) / (256.0 * 32.0));
   }
   if (js) { fprintf(js, "\n}\n"); fclose(js); }
+  if (jd) { fprintf(jd, "\n}\n"); fclose(jd); }
   return 0;
 }
