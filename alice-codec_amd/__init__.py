@@ -158,6 +158,8 @@ def load_library() -> C.CDLL:
         "alice_codec_test_chain_occupancy": (C.c_int, [_u32p]),
         "alice_codec_test_decode_chains": (C.c_int, [C.c_uint32, C.POINTER(vp), _u64p, _u16p, _u16p, C.POINTER(vp), C.c_uint64, _u32p, vp]),
         "alice_codec_test_decode_chains_n": (C.c_int, [C.c_uint32, C.POINTER(vp), _u64p, _u16p, _u16p, C.POINTER(vp), _u64p, _u32p, vp]),
+        "alice_codec_test_decode_chains_ex": (C.c_int, [C.c_uint32, C.POINTER(vp), _u64p, C.POINTER(vp), _u64p, _u32p, _u16p, _u16p, _u32p,
+                                                        _u32p, _u32p, _u64p, _u32p, _u32p, vp]),
         "alice_codec_test_encode_chains": (C.c_int, [C.c_uint32, C.POINTER(vp), _u64p, _u32p, _u16p, _u16p, C.POINTER(vp), _u64p, _u32p, _u32p,
                                                      _u32p, vp]),
         "alice_codec_test_set_tuning": (None, [C.c_long]),

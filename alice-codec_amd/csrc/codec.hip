@@ -2897,6 +2897,81 @@ int alice_codec_test_decode_chains_n(uint32_t n_chains, const void* const* d_str
     return test_decode_chains(n_chains, d_streams, lens, cum_freq, freq, d_symbols, 0ull, ns, out, hip_stream);
 }
 
+int alice_codec_test_decode_chains_ex(uint32_t n_chains, const void* const* d_streams, const uint64_t* lens, void* const* d_symbols,
+                                      const uint64_t* ns, const uint32_t* hists, const uint16_t* cum_freq, const uint16_t* freq,
+                                      const uint32_t* from_arrays, const uint32_t* resume, const uint32_t* x0, const uint64_t* pos0,
+                                      const uint32_t* own_result, uint32_t* out, void* hip_stream) {
+    clear_error();
+    const bool arrays_given = cum_freq && freq;
+    if (!n_chains || !d_streams || !lens || !d_symbols || !ns || !out || (!hists && !arrays_given) || (from_arrays && (!hists || !arrays_given)) ||
+        (resume && (!x0 || !pos0)))
+        return fail(kNullArgument, "null argument");
+    for (uint32_t c = 0; c < n_chains; ++c)
+        if ((!d_streams[c] && lens[c]) || (!d_symbols[c] && ns[c])) return fail(kNullArgument, "null argument");
+    // no decoder object stands behind the end of its stream, and the kernel's window arithmetic relies on it
+    for (uint32_t c = 0; resume && c < n_chains; ++c)
+        if (resume[c] && pos0[c] > lens[c]) return fail(kInvalidBufferSize, "resume position behind the end of the stream");
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);
+    // per kind of table: every chain's histogram or (cum, freq) arrays, then the tables
+    DevBuf dth, dta, ddesc, dres;
+    RansTable *tables_h = nullptr, *tables_a = nullptr;
+    if (hists) {
+        TRY(dth.alloc((size_t)n_chains * (1024 + sizeof(RansTable))));
+        tables_h = (RansTable*)(dth.as<uint8_t>() + (size_t)n_chains * 1024);
+        HIP_TRY(hipMemcpyAsync(dth.p, hists, (size_t)n_chains * 1024, hipMemcpyHostToDevice, st));
+        launch_rans_table(dth.as<uint32_t>(), tables_h, (int)n_chains, st);
+    }
+    if (arrays_given) {
+        TRY(dta.alloc((size_t)n_chains * (1024 + sizeof(RansTable))));
+        tables_a = (RansTable*)(dta.as<uint8_t>() + (size_t)n_chains * 1024);
+        uint16_t* const d_cum = dta.as<uint16_t>();
+        uint16_t* const d_freq = d_cum + (size_t)n_chains * 256;
+        HIP_TRY(hipMemcpyAsync(d_cum, cum_freq, (size_t)n_chains * 512, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_freq, freq, (size_t)n_chains * 512, hipMemcpyHostToDevice, st));
+        launch_rans_tables_from_arrays(d_cum, d_freq, tables_a, (int)n_chains, st);
+    }
+    // results[c] of the launch, then a RansResult of its own per chain; both filled with a pattern no chain writes, so that a
+    // chain that reports into the wrong one (or into both) is seen
+    TRY(ddesc.alloc((size_t)n_chains * sizeof(RansDecodeDesc)));
+    TRY(dres.alloc(2 * (size_t)n_chains * sizeof(RansResult)));
+    HIP_TRY(hipMemsetAsync(dres.p, 0xA5, 2 * (size_t)n_chains * sizeof(RansResult), st));
+    RansResult* const shared = dres.as<RansResult>();
+    RansResult* const own = shared + n_chains;
+    std::vector<RansDecodeDesc> descs(n_chains);
+    for (uint32_t c = 0; c < n_chains; ++c) {
+        const bool arr = from_arrays ? from_arrays[c] != 0u : !hists;
+        const bool res = resume && resume[c];
+        descs[c] = RansDecodeDesc{(const uint8_t*)d_streams[c], lens[c], (uint8_t*)d_symbols[c], ns[c], (arr ? tables_a : tables_h) + c,
+                                  res ? 1u : 0u, res ? x0[c] : 0u, res ? pos0[c] : 0ull, own_result && own_result[c] ? own + c : nullptr};
+    }
+    HIP_TRY(hipMemcpyAsync(ddesc.p, descs.data(), descs.size() * sizeof(RansDecodeDesc), hipMemcpyHostToDevice, st));
+    launch_rans_decode(ddesc.as<RansDecodeDesc>(), shared, (int)n_chains, st);
+    HIP_TRY(hipGetLastError());
+    std::vector<RansResult> res(2 * (size_t)n_chains);
+    HIP_TRY(hipMemcpyAsync(res.data(), dres.p, res.size() * sizeof(RansResult), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    bool internal = false, misplaced = false;
+    for (uint32_t c = 0; c < n_chains; ++c) {
+        const bool mine = own_result && own_result[c];
+        const RansResult& r = res[(mine ? n_chains : 0u) + c];
+        const uint8_t* const other = (const uint8_t*)&res[(mine ? 0u : n_chains) + c];
+        for (size_t b = 0; b < sizeof(RansResult); ++b) misplaced |= other[b] != 0xA5u;
+        uint32_t* const o = out + 6 * (size_t)c;
+        o[0] = (uint32_t)(r.len > 0xFFFFFFFFull ? 0xFFFFFFFFull : r.len);
+        o[1] = r.final_state;
+        o[2] = r.paths;
+        o[3] = r.fast_tiles;
+        o[4] = r.slow_tiles;
+        o[5] = r.flags;
+        internal |= (r.flags & kRansInternal) != 0u;
+    }
+    if (misplaced) return fail(kInternal, "a decode chain wrote a RansResult that is not its own");
+    if (internal) return fail(kInternal, "rANS decode kernel invariant violated");
+    return kOk;
+}
+
 // out_stride: 6 (alice_codec_test_encode_chains) or 7 (..._blocks: RansResult.comp_blocks behind the six)
 static int test_encode_chains(uint32_t n_chains, const void* const* d_symbols, const uint64_t* ns, const uint32_t* hists,
                               const uint16_t* cum_freq, const uint16_t* freq, void* const* d_regions, const uint64_t* caps,

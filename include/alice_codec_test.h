@@ -33,6 +33,27 @@ int alice_codec_test_decode_chains_n(uint32_t n_chains, const void *const *d_str
                                      const uint16_t *cum_freq, const uint16_t *freq, void *const *d_symbols,
                                      const uint64_t *ns, uint32_t *out, void *hip_stream);
 
+/* ONE launch_rans_decode of n_chains descriptors spelled out per chain, the way the chain hub and the stateful decoder
+ * objects fill them (up to 1024 chains run the one-chain-per-SIMD instance of the kernel, more run the plain one).  Chain c
+ * decodes ns[c] symbols (0 is allowed: nothing is written, the chain still reports) from d_streams[c] (lens[c] bytes) into
+ * d_symbols[c], both at any byte alignment.
+ * Tables: hists gives 256 counts per chain and the table the kernel builds from a histogram (the production path, with its
+ * kTableDec* flags); cum_freq[256 c ..] / freq[256 c ..] are taken as they are, all of them built in one launch.  One of the
+ * two may be NULL.  With both given, from_arrays[c] != 0 picks chain c's arrays and 0 its histogram (every row of both is
+ * built, so every row must be a table); from_arrays == NULL picks the histograms when they are given.
+ * resume / x0 / pos0 (NULL: a fresh decoder for every chain): resume[c] != 0 starts chain c from state x0[c] at stream
+ * position pos0[c] (at most lens[c]) instead of from the four head bytes.
+ * own_result (NULL: 0 for every chain): own_result[c] != 0 gives chain c a RansResult of its own through its descriptor, 0
+ * leaves it results[c] of the launch; a chain that writes the one it was not given is an error.
+ * hipGetLastError() is checked behind the launch.  out[6 c ..] = stream bytes consumed (RansResult.len, saturated to 32
+ * bits), final state, mask of tile-loop branches (kDecPath*), tiles taken by the fast path, tiles taken by the exact loop,
+ * RansResult.flags. */
+int alice_codec_test_decode_chains_ex(uint32_t n_chains, const void *const *d_streams, const uint64_t *lens,
+                                      void *const *d_symbols, const uint64_t *ns, const uint32_t *hists,
+                                      const uint16_t *cum_freq, const uint16_t *freq, const uint32_t *from_arrays,
+                                      const uint32_t *resume, const uint32_t *x0, const uint64_t *pos0,
+                                      const uint32_t *own_result, uint32_t *out, void *hip_stream);
+
 /* ONE launch of n_chains encode chains on device buffers (csrc/rans.hip, launch_rans_encode_descs: up to 1024 chains run
  * the one-chain-per-SIMD instance of the kernel, more run the plain one).  Chain c encodes the ns[c] symbols at d_symbols[c]
  * (any byte alignment) back to front into [d_regions[c], d_regions[c] + caps[c]); its stream is the LAST len bytes of that
