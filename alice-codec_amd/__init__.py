@@ -49,6 +49,16 @@ class PreviewItem(C.Structure):
     _fields_ = [("alc", C.c_void_p), ("len", C.c_uint64), ("first", C.c_uint32), ("count", C.c_uint32), ("rgb_out", C.c_void_p)]
 
 
+RECTS_MAX_ITEMS = 1024             # ALICE_RECTS_MAX_ITEMS
+
+
+class RectItem(C.Structure):
+    """alice_codec_rect_item of include/alice_codec.h (64 bytes)"""
+    _fields_ = [("alc", C.c_void_p), ("len", C.c_uint64), ("first", C.c_uint32), ("count", C.c_uint32), ("x", C.c_uint32),
+                ("y", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32), ("rgb_out", C.c_void_p), ("row_pitch", C.c_uint64),
+                ("frame_pitch", C.c_uint64)]
+
+
 class CodecError(Exception):
     """Mirror of the reference ``CodecError`` (src/error.rs:12-23)."""
 
@@ -343,6 +353,10 @@ def load_library() -> C.CDLL:
         "alice_codec_decode_rect": (vp, [_u8p, C.c_uint64] + [C.c_uint32] * 6 + [_u64p]),
         "alice_codec_dev_decode_rect": (C.c_int, [vp, C.c_uint64] + [C.c_uint32] * 6 + [vp, C.c_uint64, C.c_uint64, vp]),
         "alice_codec_test_last_rect_stats": (None, [_u64p]),
+        "alice_codec_decode_rects": (vp, [C.POINTER(RectItem), C.c_uint32, _u64p, _u32p]),
+        "alice_codec_dev_decode_rects": (C.c_int, [C.POINTER(RectItem), C.c_uint32, _u32p, vp]),
+        "alice_codec_test_last_rects_stats": (None, [_u64p]),
+        "alice_codec_test_rects_outputs_disjoint": (C.c_int, [C.POINTER(RectItem), C.c_uint32, _u32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
@@ -2420,6 +2434,75 @@ def _test_last_rect_stats() -> tuple:
     out = np.zeros(10, np.uint64)
     load_library().alice_codec_test_last_rect_stats(_p(out, _u64p))
     return tuple(int(v) for v in out)
+
+
+# ---- many frame ranges and rectangles in one call ----
+
+def _rect_items(rows):
+    n = len(rows)
+    if n > 0xFFFFFFFF:
+        raise CodecError(3, "dimension out of u32 range")
+    arr = (RectItem * max(n, 1))()
+    for i, (alc, length, first, count, x, y, w, h, out, row_pitch, frame_pitch) in enumerate(rows):
+        _dims_u32(first, count, x, y, w, h)
+        arr[i] = RectItem(alc, length, first, count, x, y, w, h, out, row_pitch, frame_pitch)
+    return arr
+
+
+def decode_rects(items) -> list:
+    """decode_frames / decode_rect of many items in one call: (data, first, count) is the whole frames, (data, first, count,
+    x, y, w, h) the w x h rectangle at (x, y).  A list of arrays, one per item (count * h * w * 3 packed bytes), in item
+    order.  Items may mix versions 2, 3 and 4, wavelets, sizes, lane sizes, ranges and rectangles; items that pass the same
+    object as data share its header, tables, directory scan and upload (the union of their planned blocks goes up once).
+    All or nothing: the first item that is refused or damaged decides the CodecError, whose .bad_item is its index and whose
+    message starts with "item <index>"."""
+    lib = load_library()
+    bufs, rows = {}, []
+    for item in list(items):
+        data, first, count = item[:3]
+        x, y, w, h = item[3:] if len(item) > 3 else (0, 0, 0, 0)
+        buf = bufs.setdefault(id(data), _as_u8(data))
+        rows.append((buf.ctypes.data, buf.size, first, count, x, y, w, h, None, 0, 0))
+    arr = _rect_items(rows)
+    offsets = np.zeros(len(rows) + 1, np.uint64)
+    bad = C.c_uint32(PREVIEWS_NO_ITEM)
+    ptr = lib.alice_codec_decode_rects(arr, len(rows), _p(offsets, _u64p), C.byref(bad))
+    if not ptr:
+        _previews_error(bad.value)
+    whole = _adopt(ptr, int(offsets[-1]), lib.alice_codec_data_free64)
+    return [whole[int(offsets[i]):int(offsets[i + 1])] for i in range(len(rows))]
+
+
+def rects_decode_device(items, stream: int = 0) -> None:
+    """rect_decode_device of many (d_alc_ptr, length, first, count, x, y, w, h, d_rgb_out_ptr, row_pitch, frame_pitch) items
+    in one call (containers and outputs on the device; x = y = w = h = 0 is the whole frame).  Outputs must be disjoint:
+    byte ranges that do not intersect, or boxes of one pitched surface that do not (a mosaic).  Items that name the same
+    pointer and length share their header, tables and directory scan.  All or nothing, errors as decode_rects."""
+    rows = [tuple(r) for r in items]
+    arr = _rect_items(rows)
+    bad = C.c_uint32(PREVIEWS_NO_ITEM)
+    if load_library().alice_codec_dev_decode_rects(arr, len(rows), C.byref(bad), stream or None) != 0:
+        _previews_error(bad.value)
+
+
+def _test_last_rects_stats() -> tuple:
+    """(items, distinct containers, table launches, lane launches, batched finish launches, items finished through the
+    per-item path, stream drains, blocks decoded, payload bytes the host call uploaded, symbols stored, frames written) of
+    the calling thread's last batched frame-range / rectangle decode that ran to its end."""
+    out = np.zeros(11, np.uint64)
+    load_library().alice_codec_test_last_rects_stats(_p(out, _u64p))
+    return tuple(int(v) for v in out)
+
+
+def _test_rects_outputs_disjoint(items):
+    """The output-disjointness rule of rects_decode_device on (d_rgb_out_ptr, count, w, h, row_pitch, frame_pitch) rows; no
+    device.  None when no two conflict, else the index of the later item of the first conflicting pair."""
+    rows = [(1, 0, 0, count, 0, 0, w, h, out, rp, fp) for out, count, w, h, rp, fp in items]
+    arr = _rect_items(rows)
+    bad = C.c_uint32(PREVIEWS_NO_ITEM)
+    if load_library().alice_codec_test_rects_outputs_disjoint(arr, len(rows), C.byref(bad)) != 0:
+        return bad.value
+    return None
 
 
 # ---- quality control: exact trial distortion and PSNR-floor encodes (DESIGN.md section 13) ----

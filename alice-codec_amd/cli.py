@@ -23,6 +23,9 @@ from the blocks they need (DESIGN.md section 16), through the same mapped file; 
 `thumbnails IN [IN ...] -o OUT [--frame K | --every N]` writes preview frame K (default 0) of every input, or every N-th
 frame of every input, back to back: one batched call per 1024 items over mapped files, such as the
 PREFIX.NNNNN.alc files of `encode-chunks`; inputs whose preview sizes differ, and version 1 inputs, are refused.
+`extract IN [IN ...] -o OUT [--rect X,Y,W,H] [--frame K | --every N]` is its full-resolution twin: whole frames, or the W x H
+pixels at (X, Y), of frame K (default 0) or of every N-th frame of every input, back to back, one batched call per 1024
+items over mapped files; inputs whose output sizes differ, and version 1 inputs, are refused.
 Like the reference it treats the whole input file as ONE chunk (src/bin/main.rs:117-122).  `encode-chunks`
 is the extension SURVEY.md section 8f asks for: it cuts a long raw-RGB file into 64-frame chunks
 (DEFAULT_CHUNK_SIZE, src/lib.rs:110) and writes one .alc per chunk."""
@@ -33,8 +36,8 @@ import sys
 
 import numpy as np
 
-from . import (DEFAULT_CHUNK_SIZE, PREVIEWS_MAX_ITEMS, CodecError, EncodedChunk, FrameDecoder, FrameEncoder, WaveletType, budget_bytes_per_chunk,
-               alc_version, decode_frames, decode_preview, decode_previews, decode_rect, decode_reversible, decode_split, decode_wide, encode_many, encode_reversible, encode_split,
+from . import (DEFAULT_CHUNK_SIZE, PREVIEWS_MAX_ITEMS, RECTS_MAX_ITEMS, CodecError, EncodedChunk, FrameDecoder, FrameEncoder, WaveletType, budget_bytes_per_chunk,
+               alc_version, decode_frames, decode_preview, decode_previews, decode_rect, decode_rects, decode_reversible, decode_split, decode_wide, encode_many, encode_reversible, encode_split,
                encode_split_to_psnr, encode_split_to_size, encode_to_size, encode_wide, encode_wide_to_psnr, reversible_info,
                split_info, wide_info)
 
@@ -352,6 +355,53 @@ def parse_rect(text: str):
     return x, y, w, h
 
 
+def cmd_extract(a) -> None:
+    """Full-resolution frame K of every input (--frame K, default 0), or every N-th frame of every input (--every N): whole
+    frames, or the rectangle of --rect, through the batched call in groups of at most RECTS_MAX_ITEMS items, written back to
+    back in input order."""
+    if a.frame is not None and a.every is not None:
+        raise ValueError("--frame and --every cannot be combined")
+    if a.every is not None and a.every < 1:
+        raise ValueError(f"--every wants N >= 1, got {a.every}")
+    if a.frame is not None and a.frame < 0:
+        raise ValueError(f"--frame wants K >= 0, got {a.frame}")
+    rect = parse_rect(a.rect) if a.rect is not None else None
+    files, items, size = [], [], None
+    for path in a.inputs:
+        data = np.memmap(path, dtype=np.uint8, mode="r")
+        if data.size < 18 or bytes(data[:4]) != b"ALCC" or not 2 <= int(data[4]) <= 4:
+            decode_rects([(data, 0, 1)])          # refused by the library, with its message (version 1: no random access)
+            raise ValueError(f"{path}: not a version 2, 3 or 4 container")
+        width, height, frames = (int(v) for v in np.frombuffer(bytes(data[6:18]), "<u4"))
+        if rect is not None and (rect[0] + rect[2] > width or rect[1] + rect[3] > height):
+            raise ValueError(f"{path}: rectangle {rect[2]}x{rect[3]} at ({rect[0]}, {rect[1]}) does not lie inside the {width}x{height} frame")
+        out_size = (rect[2], rect[3]) if rect is not None else (width, height)
+        if size is None:
+            size, first_path = out_size, path
+        elif out_size != size:
+            raise ValueError(f"output sizes differ: {first_path} gives {size[0]}x{size[1]}, {path} gives {out_size[0]}x{out_size[1]}")
+        picks = range(0, frames, a.every) if a.every is not None else [a.frame or 0]
+        for k in picks:
+            if k >= frames:
+                raise ValueError(f"{path}: frames [{k}, {k + 1}) are not a range of the chunk's {frames} frames")
+            items.append((data, k, 1) if rect is None else (data, k, 1, *rect))
+        files.append(data)
+    written = 0
+    try:
+        with open(a.output, "wb") as out:
+            for at in range(0, len(items), RECTS_MAX_ITEMS):
+                for rgb in decode_rects(items[at:at + RECTS_MAX_ITEMS]):
+                    rgb.tofile(out)
+                    written += rgb.size
+    except BaseException:
+        import os
+        if os.path.exists(a.output):
+            os.remove(a.output)
+        raise
+    what = "frames" if rect is None else f"rectangles at ({rect[0]}, {rect[1]})"
+    print(f"wrote {len(items)} {what} {size[0]}x{size[1]} of {len(files)} files -> {written} bytes (raw RGB)", file=sys.stderr)
+
+
 def cmd_decode_rect(a) -> None:
     """--rect alone: the rectangle of every frame; with --frames A[:B]: of that range.  Packed W x H frames."""
     x, y, w, h = parse_rect(a.rect)
@@ -484,6 +534,12 @@ def main(argv=None) -> int:
     t.add_argument("-o", "--output", required=True)
     t.add_argument("--frame", type=int, default=None, metavar="K", help="preview frame K of every input (default 0)")
     t.add_argument("--every", type=int, default=None, metavar="N", help="every N-th frame of every input instead")
+    x = sub.add_parser("extract", help="one call for many full-resolution frames or crops: frame K, or every N-th frame, of every input")
+    x.add_argument("inputs", nargs="+", metavar="IN", help="version 2, 3 or 4 containers, such as the PREFIX.NNNNN.alc files of encode-chunks")
+    x.add_argument("-o", "--output", required=True)
+    x.add_argument("--rect", default=None, metavar="X,Y,W,H", help="the W x H pixels at (X, Y) of every picked frame instead of the whole frame")
+    x.add_argument("--frame", type=int, default=None, metavar="K", help="frame K of every input (default 0)")
+    x.add_argument("--every", type=int, default=None, metavar="N", help="every N-th frame of every input instead")
     i = sub.add_parser("info")
     i.add_argument("input")
     for x in (d, i):
@@ -492,7 +548,7 @@ def main(argv=None) -> int:
     a = p.parse_args(argv)
     try:
         {"encode": cmd_encode, "encode-chunks": cmd_encode_chunks, "decode": cmd_decode, "info": cmd_info,
-         "thumbnails": cmd_thumbnails}[a.command](a)
+         "thumbnails": cmd_thumbnails, "extract": cmd_extract}[a.command](a)
     except (CodecError, ValueError, OSError) as e:
         print(f"error: {e}", file=sys.stderr)
         return 1

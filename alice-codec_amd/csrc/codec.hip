@@ -5285,7 +5285,10 @@ namespace {
 
 constexpr uint32_t kPreviewsNoItem = 0xFFFFFFFFu;   // *bad_item of a refusal that is no item's
 
-struct PreviewsContainer {                 // a distinct (pointer, len) among the items
+// What the batched calls share (the previews here, the frame ranges and rectangles of PART 10's batched call): the distinct
+// containers, the queue's buffers and counters, and the front of the queue -- headers, tables, scan, the one upload and the
+// one verdict.  The lane jobs, the finish and the hook are each call's own.
+struct BatchContainer {                    // a distinct (pointer, len) among the items
     const uint8_t* src = nullptr;          // as the caller named it: device memory (dev call) or host memory (host call)
     uint64_t len = 0;
     const uint8_t* d_alc = nullptr;        // on the device
@@ -5307,12 +5310,11 @@ struct PreviewsItem {
     size_t sym_at = 0;                     // its compact volume inside d_sym
 };
 
-// Everything a batched call owns.  The destructor drains the stream before any member goes: the host vectors that
-// asynchronous copies read (cs[].raw, up, flags) and the pool buffers outlive the work that touches them, also on an error
-// return with kernels still queued.
-struct PreviewsBatch {
-    std::vector<PreviewsContainer> cs;
-    std::vector<PreviewsItem> items;
+// Everything a batched call owns but its items.  settle() drains the stream; the owning struct's destructor calls it
+// before any member goes: the host vectors that asynchronous copies read (cs[].raw, up, flags) and the pool buffers
+// outlive the work that touches them, also on an error return with kernels still queued.
+struct BatchQueue {
+    std::vector<BatchContainer> cs;
     std::vector<std::unique_ptr<DevBuf>> alcs;   // host call: one pool buffer of the container's size per distinct container
     DevBuf d_rgb;                                // host call: the outputs, back to back
     DevBuf d_up, d_work, d_sym;
@@ -5321,8 +5323,13 @@ struct PreviewsBatch {
     hipStream_t st = nullptr;
     bool armed = false;
     uint64_t drains = 0, table_launches = 0, lane_launches = 0, finish_launches = 0;
-    ~PreviewsBatch() { if (armed) (void)hipStreamSynchronize(st); }
+    void settle() { if (armed) (void)hipStreamSynchronize(st); armed = false; }
+    ~BatchQueue() { settle(); }
     int drain() { ++drains; HIP_TRY(hipStreamSynchronize(st)); return kOk; }
+};
+struct PreviewsBatch : BatchQueue {
+    std::vector<PreviewsItem> items;
+    ~PreviewsBatch() { settle(); }
 };
 
 thread_local uint64_t tl_previews_stats[9] = {};
@@ -5333,12 +5340,14 @@ int fail_item(uint32_t k, uint32_t* bad_item, int code, const std::string& msg) 
 }
 
 // The checks that need neither a device nor a byte of a container, then the distinct containers and the items
-int previews_collect(const alice_codec_preview_item* items, uint32_t n_items, bool dev, uint32_t* bad_item, PreviewsBatch& b) {
+// (container, first, count, d_rgb of each)
+template <typename Item, typename Batch>
+int batch_collect(const Item* items, uint32_t n_items, uint32_t max_items, bool dev, uint32_t* bad_item, Batch& b) {
     if (bad_item) *bad_item = kPreviewsNoItem;
     if (!items) return fail(kNullArgument, "null argument");
     if (n_items == 0) return fail(kInvalidDimensions, "a batch holds at least one item");
-    if (n_items > ALICE_PREVIEWS_MAX_ITEMS)
-        return fail(kInvalidDimensions, std::to_string(n_items) + " items: a batch holds at most " + std::to_string(ALICE_PREVIEWS_MAX_ITEMS));
+    if (n_items > max_items)
+        return fail(kInvalidDimensions, std::to_string(n_items) + " items: a batch holds at most " + std::to_string(max_items));
     for (uint32_t k = 0; k < n_items; ++k)
         if (!items[k].alc || (dev && !items[k].rgb_out)) return fail_item(k, bad_item, kNullArgument, "null argument");
     std::map<std::pair<const void*, uint64_t>, uint32_t> seen;
@@ -5349,24 +5358,46 @@ int previews_collect(const alice_codec_preview_item* items, uint32_t n_items, bo
             b.cs.emplace_back();
             b.cs.back().src = (const uint8_t*)items[k].alc; b.cs.back().len = items[k].len; b.cs.back().first_item = k;
         }
-        PreviewsItem& it = b.items[k];
+        auto& it = b.items[k];
         it.container = at.first->second; it.first = items[k].first; it.count = items[k].count; it.d_rgb = (uint8_t*)items[k].rgb_out;
     }
     return kOk;
 }
+int previews_collect(const alice_codec_preview_item* items, uint32_t n_items, bool dev, uint32_t* bad_item, PreviewsBatch& b) {
+    return batch_collect(items, n_items, ALICE_PREVIEWS_MAX_ITEMS, dev, bad_item, b);
+}
 
-// frames_validate per item, in item order; a container's header is checked once.  header(c): min(len, kSplitHeaderBytes)
-// readable bytes of container c.  Then every item's plan.
+// dev call: every distinct container's header, queued before the first drain
+int batch_fetch_headers(BatchQueue& b) {
+    b.armed = true;
+    bool fetched = false;
+    for (BatchContainer& c : b.cs) {
+        c.d_alc = c.src;
+        if (!c.len) continue;
+        HIP_TRY(hipMemcpyAsync(c.raw, c.src, std::min<uint64_t>(c.len, kSplitHeaderBytes), hipMemcpyDeviceToHost, b.st));
+        fetched = true;
+    }
+    if (fetched) TRY(b.drain());
+    return kOk;
+}
+
+// a container's header is checked once.  header(c): min(len, kSplitHeaderBytes) readable bytes of container c
 template <typename Header>
-int previews_validate(PreviewsBatch& b, uint32_t* bad_item, Header header) {
-    for (PreviewsContainer& c : b.cs) {
+void batch_validate_headers(BatchQueue& b, Header header) {
+    for (BatchContainer& c : b.cs) {
         c.rc = frames_validate_header(header(c), c.len, c.h, c.d);
         c.msg = tl_msg;
     }
     clear_error();
+}
+
+// frames_validate per item, in item order, with the container's header verdict.  Then every item's plan.
+template <typename Header>
+int previews_validate(PreviewsBatch& b, uint32_t* bad_item, Header header) {
+    batch_validate_headers(b, header);
     for (uint32_t k = 0; k < b.items.size(); ++k) {
         PreviewsItem& it = b.items[k];
-        const PreviewsContainer& c = b.cs[it.container];
+        const BatchContainer& c = b.cs[it.container];
         if (c.rc != kOk) return fail_item(k, bad_item, c.rc, c.msg);
         if (frames_validate_range(c.h, c.d, it.first, it.count) != kOk) return fail_item(k, bad_item, tl_err, std::string(tl_msg));
         it.p = preview_plan(c.h, c.d, it.first, it.count);
@@ -5397,121 +5428,77 @@ int previews_outputs_disjoint(const PreviewsBatch& b, uint32_t* bad_item) {
     return fail(kInternal, "previews: overlap not found again");
 }
 
-// The queue of a batched call whose containers are on the device (c.d_alc) and whose items are planned: tables, scan, lanes,
-// the verdict of all end checks in one copy, then the finish launches.  Nothing that writes an output is queued before the
-// verdict.  drain_at_end: the stream has drained on return (false: the caller's copy to the host drains it).
-int previews_device(PreviewsBatch& b, uint32_t* bad_item, bool drain_at_end) {
-    hipStream_t st = b.st;
-    const size_t C = b.cs.size(), N = b.items.size();
-    auto take = [](size_t& at, size_t bytes) { const size_t r = at; at = round_up(at + bytes, 256); return r; };
-    // what goes up in one copy: frequencies and their prefix sums, the (zero) flags, the scan's jobs, the lane jobs with the
-    // narrow items first, their lists, the finish records
-    size_t up_n = 0, work_n = 0, sym_n = 0, n_listed = 0;
-    std::vector<uint32_t> order;   // lane-job order: items of u8 symbols, then items of u16 symbols
-    size_t n_narrow = 0;
-    for (int wide = 0; wide < 2; ++wide)
-        for (uint32_t k = 0; k < N; ++k)
-            if ((int)is_wide(b.cs[b.items[k].container].h.fmt) == wide) { order.push_back(k); if (!wide) ++n_narrow; }
-    for (const PreviewsItem& it : b.items) n_listed += it.p.blocks.size();
-    const size_t freq_at = take(up_n, 3 * C * 256 * sizeof(uint16_t)), cum_at = take(up_n, 3 * C * 256 * sizeof(uint16_t));
-    const size_t flags_at = take(up_n, (3 * C + 3 * N) * sizeof(uint32_t));
-    const size_t scan_at = take(up_n, 3 * C * sizeof(SplitJob)), box_at = take(up_n, 3 * N * sizeof(SplitBoxJob));
-    const size_t list_at = take(up_n, n_listed * sizeof(uint32_t)), rec_at = take(up_n, N * preview_record_bytes());
-    // device scratch: the tables, and every container's block lengths and offsets (per-job block counts: containers differ)
-    const size_t tables_at = take(work_n, 3 * C * sizeof(RansTable));
-    std::vector<size_t> len_at(C), off_at(C);
+// The front of a batched queue.  What goes up in one copy starts with: frequencies and their prefix sums, the (zero) flags
+// (3 per container for the scan, then 3 per item for the lanes), the scan's jobs; the call's own lane jobs, lists and finish
+// records follow.  Device scratch: the tables, and every container's block lengths and offsets (per-job block counts:
+// containers differ).
+inline size_t batch_take(size_t& at, size_t bytes) { const size_t r = at; at = round_up(at + bytes, 256); return r; }
+struct BatchFront {
+    size_t freq_at = 0, cum_at = 0, flags_at = 0, scan_at = 0, tables_at = 0;
+    std::vector<size_t> len_at, off_at;
+};
+void batch_front_layout(const BatchQueue& b, size_t n_items, size_t& up_n, size_t& work_n, BatchFront& f) {
+    const size_t C = b.cs.size();
+    f.freq_at = batch_take(up_n, 3 * C * 256 * sizeof(uint16_t)); f.cum_at = batch_take(up_n, 3 * C * 256 * sizeof(uint16_t));
+    f.flags_at = batch_take(up_n, (3 * C + 3 * n_items) * sizeof(uint32_t));
+    f.scan_at = batch_take(up_n, 3 * C * sizeof(SplitJob));
+    f.tables_at = batch_take(work_n, 3 * C * sizeof(RansTable));
+    f.len_at.resize(C); f.off_at.resize(C);
     for (size_t i = 0; i < C; ++i) {
         const size_t nb = b.cs[i].h.n_blocks[0];
-        len_at[i] = take(work_n, 3 * nb * sizeof(uint32_t));
-        off_at[i] = take(work_n, 3 * (nb + 1) * sizeof(unsigned long long));
+        f.len_at[i] = batch_take(work_n, 3 * nb * sizeof(uint32_t));
+        f.off_at[i] = batch_take(work_n, 3 * (nb + 1) * sizeof(unsigned long long));
     }
-    // the pad symbols of a plane (pitch - qw * qh < 4) are never stored; the finish loads them with a group's real ones
-    // and drops what it computes from them, so they need no value
-    for (PreviewsItem& it : b.items) {
-        const size_t sb = is_wide(b.cs[it.container].h.fmt) ? 2 : 1;
-        it.sym_at = take(sym_n, 3 * (size_t)(it.p.tb - it.p.ta) * it.p.box.pitch * sb);
-    }
-    b.up.assign(up_n, 0);
-    TRY(b.d_up.alloc(up_n));
-    TRY(b.d_work.alloc(work_n));
-    TRY(b.d_sym.alloc(sym_n));
-    uint8_t* const d_up = b.d_up.as<uint8_t>();
+}
+uint32_t* batch_flags(const BatchQueue& b, const BatchFront& f) { return (uint32_t*)(b.d_up.as<uint8_t>() + f.flags_at); }
+// a channel's job less its symbols and its flags (d_up and d_work allocated)
+SplitJob batch_channel_job(const BatchQueue& b, const BatchFront& f, size_t ci, int c) {
+    const BatchContainer& pc = b.cs[ci];
+    const size_t nb = pc.h.n_blocks[0];
     uint8_t* const d_work = b.d_work.as<uint8_t>();
-    uint32_t* const d_flags = (uint32_t*)(d_up + flags_at);
-    RansTable* const d_tables = (RansTable*)(d_work + tables_at);
-
-    // a channel's job less its symbols and its flags
-    auto channel_job = [&](size_t ci, int c) {
-        const PreviewsContainer& pc = b.cs[ci];
-        const size_t nb = pc.h.n_blocks[0];
-        SplitJob j{};
-        uint64_t off = kSplitHeaderBytes;
-        for (int e = 0; e < c; ++e) off += pc.h.payload_len[e];
-        j.n = pc.d.padded; j.n_blocks = pc.h.n_blocks[c]; j.lane_symbols = pc.h.lane_symbols;
-        j.table = d_tables + 3 * ci + (size_t)c;
-        j.stream = (uint8_t*)pc.d_alc + off; j.len = pc.h.payload_len[c];
-        j.blk_len = (uint32_t*)(d_work + len_at[ci]) + (size_t)c * nb;
-        j.blk_off = (unsigned long long*)(d_work + off_at[ci]) + (size_t)c * (nb + 1);
-        return j;
-    };
-    uint16_t* freq = (uint16_t*)(b.up.data() + freq_at);
-    uint16_t* cum = (uint16_t*)(b.up.data() + cum_at);
-    for (size_t ci = 0; ci < C; ++ci)
+    SplitJob j{};
+    uint64_t off = kSplitHeaderBytes;
+    for (int e = 0; e < c; ++e) off += pc.h.payload_len[e];
+    j.n = pc.d.padded; j.n_blocks = pc.h.n_blocks[c]; j.lane_symbols = pc.h.lane_symbols;
+    j.table = (RansTable*)(d_work + f.tables_at) + 3 * ci + (size_t)c;
+    j.stream = (uint8_t*)pc.d_alc + off; j.len = pc.h.payload_len[c];
+    j.blk_len = (uint32_t*)(d_work + f.len_at[ci]) + (size_t)c * nb;
+    j.blk_off = (unsigned long long*)(d_work + f.off_at[ci]) + (size_t)c * (nb + 1);
+    return j;
+}
+// the frequencies, their prefix sums and the scan's jobs into b.up (sized, zeroed)
+void batch_front_fill(BatchQueue& b, const BatchFront& f) {
+    uint16_t* freq = (uint16_t*)(b.up.data() + f.freq_at);
+    uint16_t* cum = (uint16_t*)(b.up.data() + f.cum_at);
+    for (size_t ci = 0; ci < b.cs.size(); ++ci)
         for (int c = 0; c < 3; ++c) {
             const size_t t = 3 * ci + (size_t)c;
             uint32_t run = 0;
             for (int i = 0; i < 256; ++i) { freq[t * 256 + i] = b.cs[ci].h.freq[c][i]; cum[t * 256 + i] = (uint16_t)run; run += b.cs[ci].h.freq[c][i]; }
-            SplitJob j = channel_job(ci, c);
-            j.flags = d_flags + t;
-            memcpy(b.up.data() + scan_at + t * sizeof(SplitJob), &j, sizeof(j));
+            SplitJob j = batch_channel_job(b, f, ci, c);
+            j.flags = batch_flags(b, f) + t;
+            memcpy(b.up.data() + f.scan_at + t * sizeof(SplitJob), &j, sizeof(j));
         }
-    std::vector<PreviewFinish> fin(N);
-    uint32_t max_planned[2] = {0, 0};
-    size_t listed = 0;
-    for (size_t slot = 0; slot < N; ++slot) {
-        const uint32_t k = order[slot];
-        const PreviewsItem& it = b.items[k];
-        const PreviewsContainer& pc = b.cs[it.container];
-        const bool wide = is_wide(pc.h.fmt);
-        const size_t sb = wide ? 2 : 1;
-        const uint32_t planes = it.p.tb - it.p.ta, n_planned = (uint32_t)it.p.blocks.size();
-        uint8_t* const sym = b.d_sym.as<uint8_t>() + it.sym_at;
-        memcpy(b.up.data() + list_at + listed * sizeof(uint32_t), it.p.blocks.data(), n_planned * sizeof(uint32_t));
-        for (int c = 0; c < 3; ++c) {
-            SplitBoxJob j = it.p.box;
-            j.j = channel_job(it.container, c);
-            j.j.sym = sym + (size_t)c * planes * it.p.box.pitch * sb;
-            j.j.flags = d_flags + 3 * C + 3 * (size_t)k + (size_t)c;
-            j.blocks = (const uint32_t*)(d_up + list_at) + listed; j.n_planned = n_planned;
-            memcpy(b.up.data() + box_at + (3 * slot + (size_t)c) * sizeof(SplitBoxJob), &j, sizeof(j));
-        }
-        listed += n_planned;
-        max_planned[wide] = std::max(max_planned[wide], n_planned);
-        // EXACT is the full chunk's verdict: the first pass inverse_bounds looks at is the temporal one
-        PreviewFinish& f = fin[k];
-        f.d_sym = sym; f.pitch = it.p.box.pitch; f.q = (uint64_t)it.p.box.n_lo[0] * it.p.box.n_lo[1]; f.planes = planes;
-        f.win = FrameWindow{it.first - it.p.ta, it.first - it.p.ta + it.count};
-        f.format = (int)pc.h.fmt; f.wavelet = pc.h.wavelet;
-        for (int c = 0; c < 3; ++c) f.step[c] = pc.h.step[c];
-        f.exact = inverse_bounds(pc.h.wavelet, pc.h.step, wide ? kWideMaxQ : kByteMaxQ).exact;
-        f.d_rgb = it.d_rgb;
-    }
-    std::vector<PreviewFinishLaunch> finishes;
-    if (!preview_records_plan(fin.data(), (uint32_t)N, b.up.data() + rec_at, finishes))
-        return fail(kInternal, "previews: no finish kernel for an item's volume");
-
+}
+// the one upload, every table of every container in one launch, one scan over every channel
+int batch_front_launch(BatchQueue& b, const BatchFront& f) {
+    const size_t C = b.cs.size();
+    uint8_t* const d_up = b.d_up.as<uint8_t>();
     b.armed = true;
-    HIP_TRY(hipMemcpyAsync(d_up, b.up.data(), up_n, hipMemcpyHostToDevice, st));
-    launch_rans_tables_from_arrays((const uint16_t*)(d_up + cum_at), (const uint16_t*)(d_up + freq_at), d_tables, (int)(3 * C), st);
+    HIP_TRY(hipMemcpyAsync(d_up, b.up.data(), b.up.size(), hipMemcpyHostToDevice, b.st));
+    launch_rans_tables_from_arrays((const uint16_t*)(d_up + f.cum_at), (const uint16_t*)(d_up + f.freq_at),
+                                   (RansTable*)(b.d_work.as<uint8_t>() + f.tables_at), (int)(3 * C), b.st);
     b.table_launches = 1;
-    launch_split_scan((const SplitJob*)(d_up + scan_at), (int)(3 * C), true, nullptr, st);
-    const SplitBoxJob* d_box = (const SplitBoxJob*)(d_up + box_at);
-    if (n_narrow) { launch_split_box_decode(d_box, (int)(3 * n_narrow), max_planned[0], false, false, st); ++b.lane_launches; }
-    if (N > n_narrow) { launch_split_box_decode(d_box + 3 * n_narrow, (int)(3 * (N - n_narrow)), max_planned[1], true, false, st); ++b.lane_launches; }
+    launch_split_scan((const SplitJob*)(d_up + f.scan_at), (int)(3 * C), true, nullptr, b.st);
+    return kOk;
+}
+// the verdict: every container's and every item's end-check flags in one copy, before anything writes an output
+template <typename Batch>
+int batch_verdict(Batch& b, const BatchFront& f, uint32_t* bad_item) {
+    const size_t C = b.cs.size(), N = b.items.size();
     HIP_TRY(hipGetLastError());
-    // the verdict: every container's and every item's end-check flags in one copy, before anything writes an output
     b.flags.assign(3 * C + 3 * N, 0);
-    HIP_TRY(hipMemcpyAsync(b.flags.data(), d_flags, b.flags.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(b.flags.data(), batch_flags(b, f), b.flags.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, b.st));
     TRY(b.drain());
     for (uint32_t k = 0; k < N; ++k)
         for (int c = 0; c < 3; ++c) {
@@ -5520,6 +5507,112 @@ int previews_device(PreviewsBatch& b, uint32_t* bad_item, bool drain_at_end) {
                 return fail_item(k, bad_item, kInvalidBitstream, "stream " + std::to_string(c) + ": block or lane directory does not add up");
             if (scan | lanes) return fail_item(k, bad_item, kInvalidBitstream, "stream " + std::to_string(c) + ": a lane failed its end check");
         }
+    return kOk;
+}
+
+// host call, per distinct container: the union of its items' planned blocks, and the spans that hold them
+template <typename Batch>
+int batch_host_spans(Batch& b, uint32_t* bad_item, uint64_t& uploaded) {
+    for (const auto& it : b.items) {
+        std::vector<uint32_t>& u = b.cs[it.container].blocks;
+        std::vector<uint32_t> merged;
+        std::set_union(u.begin(), u.end(), it.p.blocks.begin(), it.p.blocks.end(), std::back_inserter(merged));
+        u.swap(merged);
+    }
+    uploaded = 0;
+    for (BatchContainer& c : b.cs) {
+        uint64_t payload = 0;
+        if (partial_spans(c.src, c.h, c.blocks, c.spans, payload) != kOk) return fail_item(c.first_item, bad_item, tl_err, std::string(tl_msg));
+        uploaded += payload;
+    }
+    return kOk;
+}
+// host call: the outputs' buffer, the containers' buffers, and the spans queued
+int batch_host_upload(BatchQueue& b, uint64_t total) {
+    TRY(b.d_rgb.alloc(total));
+    for (BatchContainer& c : b.cs) {
+        b.alcs.emplace_back(new DevBuf());
+        TRY(b.alcs.back()->alloc(c.len));
+        c.d_alc = b.alcs.back()->as<uint8_t>();
+    }
+    b.armed = true;
+    for (const BatchContainer& c : b.cs)
+        for (const PartialSpan& s : c.spans)
+            HIP_TRY(hipMemcpyAsync((uint8_t*)c.d_alc + s.off, c.src + s.off, s.len, hipMemcpyHostToDevice, b.st));
+    return kOk;
+}
+
+// The queue of a batched call whose containers are on the device (c.d_alc) and whose items are planned: tables, scan, lanes,
+// the verdict of all end checks in one copy, then the finish launches.  Nothing that writes an output is queued before the
+// verdict.  drain_at_end: the stream has drained on return (false: the caller's copy to the host drains it).
+int previews_device(PreviewsBatch& b, uint32_t* bad_item, bool drain_at_end) {
+    hipStream_t st = b.st;
+    const size_t C = b.cs.size(), N = b.items.size();
+    // after the front: the lane jobs with the narrow items first, their lists, the finish records
+    size_t up_n = 0, work_n = 0, sym_n = 0, n_listed = 0;
+    std::vector<uint32_t> order;   // lane-job order: items of u8 symbols, then items of u16 symbols
+    size_t n_narrow = 0;
+    for (int wide = 0; wide < 2; ++wide)
+        for (uint32_t k = 0; k < N; ++k)
+            if ((int)is_wide(b.cs[b.items[k].container].h.fmt) == wide) { order.push_back(k); if (!wide) ++n_narrow; }
+    for (const PreviewsItem& it : b.items) n_listed += it.p.blocks.size();
+    BatchFront f;
+    batch_front_layout(b, N, up_n, work_n, f);
+    const size_t box_at = batch_take(up_n, 3 * N * sizeof(SplitBoxJob));
+    const size_t list_at = batch_take(up_n, n_listed * sizeof(uint32_t)), rec_at = batch_take(up_n, N * preview_record_bytes());
+    // the pad symbols of a plane (pitch - qw * qh < 4) are never stored; the finish loads them with a group's real ones
+    // and drops what it computes from them, so they need no value
+    for (PreviewsItem& it : b.items) {
+        const size_t sb = is_wide(b.cs[it.container].h.fmt) ? 2 : 1;
+        it.sym_at = batch_take(sym_n, 3 * (size_t)(it.p.tb - it.p.ta) * it.p.box.pitch * sb);
+    }
+    b.up.assign(up_n, 0);
+    TRY(b.d_up.alloc(up_n));
+    TRY(b.d_work.alloc(work_n));
+    TRY(b.d_sym.alloc(sym_n));
+    uint8_t* const d_up = b.d_up.as<uint8_t>();
+    uint32_t* const d_flags = batch_flags(b, f);
+    batch_front_fill(b, f);
+    std::vector<PreviewFinish> fin(N);
+    uint32_t max_planned[2] = {0, 0};
+    size_t listed = 0;
+    for (size_t slot = 0; slot < N; ++slot) {
+        const uint32_t k = order[slot];
+        const PreviewsItem& it = b.items[k];
+        const BatchContainer& pc = b.cs[it.container];
+        const bool wide = is_wide(pc.h.fmt);
+        const size_t sb = wide ? 2 : 1;
+        const uint32_t planes = it.p.tb - it.p.ta, n_planned = (uint32_t)it.p.blocks.size();
+        uint8_t* const sym = b.d_sym.as<uint8_t>() + it.sym_at;
+        memcpy(b.up.data() + list_at + listed * sizeof(uint32_t), it.p.blocks.data(), n_planned * sizeof(uint32_t));
+        for (int c = 0; c < 3; ++c) {
+            SplitBoxJob j = it.p.box;
+            j.j = batch_channel_job(b, f, it.container, c);
+            j.j.sym = sym + (size_t)c * planes * it.p.box.pitch * sb;
+            j.j.flags = d_flags + 3 * C + 3 * (size_t)k + (size_t)c;
+            j.blocks = (const uint32_t*)(d_up + list_at) + listed; j.n_planned = n_planned;
+            memcpy(b.up.data() + box_at + (3 * slot + (size_t)c) * sizeof(SplitBoxJob), &j, sizeof(j));
+        }
+        listed += n_planned;
+        max_planned[wide] = std::max(max_planned[wide], n_planned);
+        // EXACT is the full chunk's verdict: the first pass inverse_bounds looks at is the temporal one
+        PreviewFinish& pf = fin[k];
+        pf.d_sym = sym; pf.pitch = it.p.box.pitch; pf.q = (uint64_t)it.p.box.n_lo[0] * it.p.box.n_lo[1]; pf.planes = planes;
+        pf.win = FrameWindow{it.first - it.p.ta, it.first - it.p.ta + it.count};
+        pf.format = (int)pc.h.fmt; pf.wavelet = pc.h.wavelet;
+        for (int c = 0; c < 3; ++c) pf.step[c] = pc.h.step[c];
+        pf.exact = inverse_bounds(pc.h.wavelet, pc.h.step, wide ? kWideMaxQ : kByteMaxQ).exact;
+        pf.d_rgb = it.d_rgb;
+    }
+    std::vector<PreviewFinishLaunch> finishes;
+    if (!preview_records_plan(fin.data(), (uint32_t)N, b.up.data() + rec_at, finishes))
+        return fail(kInternal, "previews: no finish kernel for an item's volume");
+
+    TRY(batch_front_launch(b, f));
+    const SplitBoxJob* d_box = (const SplitBoxJob*)(d_up + box_at);
+    if (n_narrow) { launch_split_box_decode(d_box, (int)(3 * n_narrow), max_planned[0], false, false, st); ++b.lane_launches; }
+    if (N > n_narrow) { launch_split_box_decode(d_box + 3 * n_narrow, (int)(3 * (N - n_narrow)), max_planned[1], true, false, st); ++b.lane_launches; }
+    TRY(batch_verdict(b, f, bad_item));
     for (const PreviewFinishLaunch& l : finishes) { launch_preview_inverse_many(d_up + rec_at, l, st); ++b.finish_launches; }
     HIP_TRY(hipGetLastError());
     if (drain_at_end) TRY(b.drain());
@@ -5544,17 +5637,8 @@ int alice_codec_dev_decode_previews(const alice_codec_preview_item* items, uint3
     TRY(ensure_device());
     b.st = (hipStream_t)hip_stream;
     ScopeStream scope(b.st);
-    // every distinct container's header, queued before the first drain
-    b.armed = true;
-    bool fetched = false;
-    for (PreviewsContainer& c : b.cs) {
-        c.d_alc = c.src;
-        if (!c.len) continue;
-        HIP_TRY(hipMemcpyAsync(c.raw, c.src, std::min<uint64_t>(c.len, kSplitHeaderBytes), hipMemcpyDeviceToHost, b.st));
-        fetched = true;
-    }
-    if (fetched) TRY(b.drain());
-    TRY(previews_validate(b, bad_item, [](const PreviewsContainer& c) { return c.raw; }));
+    TRY(batch_fetch_headers(b));
+    TRY(previews_validate(b, bad_item, [](const BatchContainer& c) { return c.raw; }));
     TRY(previews_outputs_disjoint(b, bad_item));
     TRY(previews_device(b, bad_item, true));
     previews_done(b, 0);
@@ -5566,37 +5650,17 @@ uint8_t* alice_codec_decode_previews(const alice_codec_preview_item* items, uint
     PreviewsBatch b;
     if (previews_collect(items, n_items, false, bad_item, b) != kOk) return nullptr;
     if (!offsets) { fail(kNullArgument, "null argument"); return nullptr; }
-    if (previews_validate(b, bad_item, [](const PreviewsContainer& c) { return c.src; }) != kOk) return nullptr;
-    // per distinct container: the union of its items' planned blocks, and the spans that hold them
-    for (const PreviewsItem& it : b.items) {
-        std::vector<uint32_t>& u = b.cs[it.container].blocks;
-        std::vector<uint32_t> merged;
-        std::set_union(u.begin(), u.end(), it.p.blocks.begin(), it.p.blocks.end(), std::back_inserter(merged));
-        u.swap(merged);
-    }
+    if (previews_validate(b, bad_item, [](const BatchContainer& c) { return c.src; }) != kOk) return nullptr;
     uint64_t uploaded = 0, total = 0;
-    for (PreviewsContainer& c : b.cs) {
-        uint64_t payload = 0;
-        if (partial_spans(c.src, c.h, c.blocks, c.spans, payload) != kOk) { fail_item(c.first_item, bad_item, tl_err, std::string(tl_msg)); return nullptr; }
-        uploaded += payload;
-    }
+    if (batch_host_spans(b, bad_item, uploaded) != kOk) return nullptr;
     for (const PreviewsItem& it : b.items) total += it.bytes;
     std::unique_ptr<uint8_t, decltype(&free)> out(host_result_alloc(total), &free);   // freed on every failure below
     if (!out) { fail(kOutOfMemory, "out of host memory"); return nullptr; }
     auto run = [&]() -> int {
         TRY(get_stream(&b.st));
-        TRY(b.d_rgb.alloc(total));
-        for (PreviewsContainer& c : b.cs) {
-            b.alcs.emplace_back(new DevBuf());
-            TRY(b.alcs.back()->alloc(c.len));
-            c.d_alc = b.alcs.back()->as<uint8_t>();
-        }
+        TRY(batch_host_upload(b, total));
         uint64_t at = 0;
         for (PreviewsItem& it : b.items) { it.d_rgb = b.d_rgb.as<uint8_t>() + at; at += it.bytes; }
-        b.armed = true;
-        for (const PreviewsContainer& c : b.cs)
-            for (const PartialSpan& s : c.spans)
-                HIP_TRY(hipMemcpyAsync((uint8_t*)c.d_alc + s.off, c.src + s.off, s.len, hipMemcpyHostToDevice, b.st));
         TRY(previews_device(b, bad_item, false));
         ++b.drains;
         return copy_to_host(out.get(), b.d_rgb.p, total, b.st);
@@ -5680,6 +5744,21 @@ int rect_validate(const SplitHeader& h, uint32_t x, uint32_t y, uint32_t w, uint
     return kOk;
 }
 
+// the layout of a rectangle's output: packed (both pitches 0), or the caller's pitches, checked
+int rect_output_layout(void* d_rgb_out, uint32_t w, uint32_t h, uint64_t row_pitch, uint64_t frame_pitch, RgbLayout& out) {
+    out = RgbLayout{(uint8_t*)d_rgb_out, 3ull * w, 3ull * w * h};
+    if (row_pitch || frame_pitch) {
+        const uint64_t rp = row_pitch ? row_pitch : out.row_pitch;
+        const uint64_t fp = frame_pitch ? frame_pitch : rp * h;
+        if (rp < 3ull * w || (unsigned __int128)fp < (unsigned __int128)rp * h)
+            return fail(kInvalidDimensions, "pitches " + std::to_string(row_pitch) + " and " + std::to_string(frame_pitch) +
+                                                " are too small for rows of " + std::to_string(3ull * w) + " bytes and frames of " +
+                                                std::to_string(h) + " rows");
+        out.row_pitch = rp; out.frame_pitch = fp;
+    }
+    return kOk;
+}
+
 }  // namespace
 
 extern "C" {
@@ -5703,16 +5782,8 @@ int alice_codec_dev_decode_rect(const void* d_alc, uint64_t len, uint32_t first,
                                 uint32_t h, void* d_rgb_out, uint64_t row_pitch, uint64_t frame_pitch, void* hip_stream) {
     return partial_decode_dev(d_alc, len, first, count, d_rgb_out, hip_stream, [&](const SplitHeader& hd, const ChunkDims& d, hipStream_t st) {
         TRY(rect_validate(hd, x, y, w, h));
-        RgbLayout out{(uint8_t*)d_rgb_out, 3ull * w, 3ull * w * h};
-        if (row_pitch || frame_pitch) {
-            const uint64_t rp = row_pitch ? row_pitch : out.row_pitch;
-            const uint64_t fp = frame_pitch ? frame_pitch : rp * h;
-            if (rp < 3ull * w || (unsigned __int128)fp < (unsigned __int128)rp * h)
-                return fail(kInvalidDimensions, "pitches " + std::to_string(row_pitch) + " and " + std::to_string(frame_pitch) +
-                                                    " are too small for rows of " + std::to_string(3ull * w) + " bytes and frames of " +
-                                                    std::to_string(h) + " rows");
-            out.row_pitch = rp; out.frame_pitch = fp;
-        }
+        RgbLayout out;
+        TRY(rect_output_layout(d_rgb_out, w, h, row_pitch, frame_pitch, out));
         return rect_decode_device(kPartialRect, hd, d, rect_plan(hd, d, first, count, x, y, w, h), (const uint8_t*)d_alc, first, count, x, y, w, h,
                                   out, st, 0);
     });
@@ -5739,6 +5810,362 @@ void alice_codec_test_last_rect_stats(uint64_t out[10]) {
     const PartialStats& s = tl_partial_stats[kPartialRect];
     const uint64_t v[10] = {s.ta, s.tb, s.xa, s.xb, s.ya, s.yb, s.blocks, s.uploaded, s.frames, s.stored};
     if (out) memcpy(out, v, sizeof(v));
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// PART 10, batched: many frame ranges and rectangles in one call (kernels: rans_tables_from_arrays_kernel
+// of rans.hip, split_scan_kernel<true>, split_frames_decode_kernel and split_box_decode_kernel<WIDE, true> of split.hip,
+// inv_t_win_many_kernel, inv_t_wide_win_many_kernel and inv_xy_many_kernel of transform.hip, rgb_rect_paste_many_kernel of
+// generic.hip)
+//
+// A detector asks for the same crop of frame k of every chunk, a viewer for a mosaic of crops in one surface: N times PART
+// 8's and PART 10's fixed cost through the single calls.  Here the items share the batched preview's queue up to the verdict
+// (one table launch, one scan, the lane jobs of all items on blockIdx.y of at most four launches, one copy of all end
+// checks) and a finish that runs once per instance class present: the window inverse and the paste over flattened work
+// lists.  Every item's virtual chunk, kept-frames slot, compact symbol volume and packed temporary are sub-ranges of pooled
+// buffers.  Every item means what the single call means; the call is all or nothing.
+// ------------------------------------------------------------------------------------------
+
+namespace {
+
+struct RectsItem {
+    uint32_t container = 0, first = 0, count = 0;
+    uint32_t x = 0, y = 0, w = 0, h = 0;       // as validated: the whole frame spelled out
+    uint64_t row_pitch = 0, frame_pitch = 0;   // as the caller gave them
+    PartialPlan p;
+    uint8_t* d_rgb = nullptr;
+    RgbLayout out{};
+    uint64_t bytes = 0;                        // count * h * w * 3
+    bool whole = false;                        // the whole frame: the inverse writes the output itself
+    bool batched = false;                      // finished by the work-list kernels
+    ChunkDims dv{}, dx{};                      // the virtual chunk; its kept frames
+    size_t sym_at = 0, slot_at = 0, tmp_at = 0;
+    bool has_slot = false;
+};
+
+struct RectsBatch : BatchQueue {
+    std::vector<RectsItem> items;
+    DevBuf d_slot, d_tmp;                               // the band slots; the packed temporaries of the items that paste
+    std::vector<std::unique_ptr<DecodeWork>> works;     // per item: the generic path's buffers (null: the item has a band slot)
+    uint64_t fallback_items = 0;
+    ~RectsBatch() { settle(); }
+};
+
+thread_local uint64_t tl_rects_stats[11] = {};
+
+// An output as the disjointness rule sees it
+struct RectsOut { uintptr_t base; uint64_t count, h, row_bytes, rp, fp; };
+unsigned __int128 rects_out_end(const RectsOut& o) {
+    return (unsigned __int128)o.base + (unsigned __int128)(o.count - 1) * o.fp + (unsigned __int128)(o.h - 1) * o.rp + o.row_bytes;
+}
+// Two outputs conflict when their enclosing byte ranges intersect -- unless both have the same pitches and are disjoint boxes
+// of that surface: in coordinates (t, y, x_byte) from the lower base (off = t * fp + y * rp + x_byte, y * rp + x_byte < fp,
+// x_byte < rp) each stays a box (x_byte + row_bytes <= rp, (y + h) * rp <= fp), so a byte has one coordinate triple, and the
+// boxes are separated on an axis.
+bool rects_outputs_conflict(const RectsOut& a, const RectsOut& b) {
+    if (!((unsigned __int128)a.base < rects_out_end(b) && (unsigned __int128)b.base < rects_out_end(a))) return false;
+    if (a.rp != b.rp || a.fp != b.fp) return true;
+    const uintptr_t lower = std::min(a.base, b.base);
+    uint64_t t[2], y[2], x[2];
+    const RectsOut* o[2] = {&a, &b};
+    for (int i = 0; i < 2; ++i) {
+        const uint64_t off = o[i]->base - lower, in_frame = off % a.fp;
+        t[i] = off / a.fp; y[i] = in_frame / a.rp; x[i] = in_frame % a.rp;
+        if (x[i] + o[i]->row_bytes > a.rp || (unsigned __int128)(y[i] + o[i]->h) * a.rp > a.fp) return true;
+    }
+    const bool apart = t[0] + a.count <= t[1] || t[1] + b.count <= t[0] || y[0] + a.h <= y[1] || y[1] + b.h <= y[0] ||
+                       x[0] + a.row_bytes <= x[1] || x[1] + b.row_bytes <= x[0];
+    return !apart;
+}
+// One sweep over the outputs in base order finds whether any two conflict; only a refusal pays for naming the first item, in
+// item order, that conflicts with an earlier one.
+int rects_outputs_disjoint(const std::vector<RectsOut>& r, uint32_t* bad_item) {
+    const size_t n = r.size();
+    std::vector<uint32_t> by_base(n), open;
+    for (size_t k = 0; k < n; ++k) by_base[k] = (uint32_t)k;
+    std::sort(by_base.begin(), by_base.end(), [&](uint32_t a, uint32_t b) { return r[a].base < r[b].base; });
+    bool any = false;
+    for (size_t i = 0; i < n && !any; ++i) {
+        const RectsOut& cur = r[by_base[i]];
+        size_t kept = 0;
+        for (size_t e = 0; e < open.size(); ++e) {
+            if (rects_out_end(r[open[e]]) <= (unsigned __int128)cur.base) continue;   // ends before every later base
+            any = any || rects_outputs_conflict(r[open[e]], cur);
+            open[kept++] = open[e];
+        }
+        open.resize(kept);
+        open.push_back(by_base[i]);
+    }
+    if (!any) return kOk;
+    for (size_t k = 1; k < n; ++k)
+        for (size_t j = 0; j < k; ++j)
+            if (rects_outputs_conflict(r[j], r[k]))
+                return fail_item((uint32_t)k, bad_item, kInvalidDimensions, "its output overlaps the output of item " + std::to_string(j));
+    return fail(kInternal, "rects: overlap not found again");
+}
+
+int rects_collect(const alice_codec_rect_item* items, uint32_t n_items, bool dev, uint32_t* bad_item, RectsBatch& b) {
+    TRY(batch_collect(items, n_items, ALICE_RECTS_MAX_ITEMS, dev, bad_item, b));
+    for (uint32_t k = 0; k < n_items; ++k) {
+        RectsItem& it = b.items[k];
+        it.x = items[k].x; it.y = items[k].y; it.w = items[k].w; it.h = items[k].h;
+        it.row_pitch = dev ? items[k].row_pitch : 0; it.frame_pitch = dev ? items[k].frame_pitch : 0;
+    }
+    return kOk;
+}
+
+// Per item, in item order: frames_validate with the container's header verdict, the rectangle, the pitches.  Then every
+// item's plan, as the single call picks it, and its virtual chunk.
+template <typename Header>
+int rects_validate(RectsBatch& b, uint32_t* bad_item, Header header) {
+    batch_validate_headers(b, header);
+    for (uint32_t k = 0; k < b.items.size(); ++k) {
+        RectsItem& it = b.items[k];
+        const BatchContainer& c = b.cs[it.container];
+        if (c.rc != kOk) return fail_item(k, bad_item, c.rc, c.msg);
+        if (frames_validate_range(c.h, c.d, it.first, it.count) != kOk) return fail_item(k, bad_item, tl_err, std::string(tl_msg));
+        const bool range = !it.x && !it.y && !it.w && !it.h;   // a frame range: the whole frame
+        if (range) { it.w = c.h.width; it.h = c.h.height; }
+        else if (rect_validate(c.h, it.x, it.y, it.w, it.h) != kOk) return fail_item(k, bad_item, tl_err, std::string(tl_msg));
+        if (rect_output_layout(it.d_rgb, it.w, it.h, it.row_pitch, it.frame_pitch, it.out) != kOk)
+            return fail_item(k, bad_item, tl_err, std::string(tl_msg));
+        it.p = range ? frames_plan(c.h, c.d, it.first, it.count) : rect_plan(c.h, c.d, it.first, it.count, it.x, it.y, it.w, it.h);
+        it.bytes = 3ull * it.w * it.h * it.count;
+        // the virtual chunk, as rect_decode_device derives it
+        it.whole = it.x == 0 && it.y == 0 && it.w == c.h.width && it.h == c.h.height;
+        it.dv = make_dims(it.whole ? c.h.width : it.p.xb - it.p.xa, it.whole ? c.h.height : it.p.yb - it.p.ya, it.p.tb - it.p.ta);
+        it.dx = make_dims(it.dv.w, it.dv.h, it.count);
+    }
+    return kOk;
+}
+
+std::vector<RectsOut> rects_outs(const RectsBatch& b) {
+    std::vector<RectsOut> r(b.items.size());
+    for (size_t k = 0; k < r.size(); ++k) {
+        const RectsItem& it = b.items[k];
+        r[k] = RectsOut{(uintptr_t)it.out.base, it.count, it.h, 3ull * it.w, it.out.row_pitch, it.out.frame_pitch};
+    }
+    return r;
+}
+
+// The queue of a batched call whose containers are on the device and whose items are planned (it.out set): the front, at
+// most four lane launches, the verdict, the finish.  Nothing that writes an output is queued before the verdict.
+int rects_device(RectsBatch& b, uint32_t* bad_item, bool drain_at_end) {
+    hipStream_t st = b.st;
+    const size_t C = b.cs.size(), N = b.items.size();
+    // lane-job order: whole planes before boxes, u8 symbols before u16 symbols in each
+    std::vector<uint32_t> order[4];   // [2 * box + wide]
+    size_t n_listed = 0, n_batched = 0, n_paste = 0;
+    for (uint32_t k = 0; k < N; ++k) {
+        RectsItem& it = b.items[k];
+        const SplitHeader& h = b.cs[it.container].h;
+        order[2 * (it.p.planes ? 0 : 1) + (is_wide(h.fmt) ? 1 : 0)].push_back(k);
+        if (!it.p.planes) n_listed += it.p.blocks.size();
+        const InverseBounds ib = inverse_bounds(h.wavelet, h.step, is_wide(h.fmt) ? kWideMaxQ : kByteMaxQ);
+        it.batched = rects_finish_batchable(it.dv, it.count, ib.exact, ib.mid16);
+        if (it.batched) { ++n_batched; if (!it.whole) ++n_paste; }
+    }
+    const size_t n_frames_jobs = order[0].size() + order[1].size(), n_box_jobs = order[2].size() + order[3].size();
+    size_t up_n = 0, work_n = 0, sym_n = 0, slot_n = 0, tmp_n = 0;
+    BatchFront f;
+    batch_front_layout(b, N, up_n, work_n, f);
+    const size_t frames_at = batch_take(up_n, 3 * n_frames_jobs * sizeof(SplitFramesJob));
+    const size_t box_at = batch_take(up_n, 3 * n_box_jobs * sizeof(SplitBoxJob));
+    const size_t list_at = batch_take(up_n, n_listed * sizeof(uint32_t));
+    const size_t t_rec_at = batch_take(up_n, n_batched * rects_record_bytes(0)), xy_rec_at = batch_take(up_n, n_batched * rects_record_bytes(1));
+    const size_t paste_rec_at = batch_take(up_n, n_paste * rect_paste_record_bytes());
+    for (RectsItem& it : b.items) {
+        const SplitHeader& h = b.cs[it.container].h;
+        const size_t sb = is_wide(h.fmt) ? 2 : 1;
+        it.sym_at = batch_take(sym_n, 3 * it.dv.padded * sb);
+        it.has_slot = transform_tiles_eligible(it.dv);
+        if (it.has_slot)
+            it.slot_at = batch_take(slot_n, inverse_scratch_bytes(it.dx, inverse_bounds(h.wavelet, h.step, is_wide(h.fmt) ? kWideMaxQ : kByteMaxQ).mid16));
+        if (!it.whole) it.tmp_at = batch_take(tmp_n, 3 * it.dx.n_pixels);
+    }
+    b.up.assign(up_n, 0);
+    TRY(b.d_up.alloc(up_n));
+    TRY(b.d_work.alloc(work_n));
+    TRY(b.d_sym.alloc(sym_n));
+    TRY(b.d_slot.alloc(slot_n));
+    TRY(b.d_tmp.alloc(tmp_n));
+    // the generic path's buffers, as inverse_window would allocate them: here, so that no allocation can fail after an
+    // output has been written
+    for (const RectsItem& it : b.items) {
+        b.works.emplace_back(it.has_slot ? nullptr : new DecodeWork());
+        if (it.has_slot) continue;
+        DecodeWork& dw = *b.works.back();
+        dw.d = it.dv; dw.n_chunks = 1;
+        TRY(dw.planes.alloc(3 * it.dx.n_pixels * sizeof(int16_t)));
+        TRY(dw.tmp.alloc(it.dv.padded * sizeof(int32_t)));
+        TRY(dw.gen.alloc(2 * it.dv.padded * sizeof(int32_t)));
+    }
+    uint8_t* const d_up = b.d_up.as<uint8_t>();
+    uint32_t* const d_flags = batch_flags(b, f);
+    batch_front_fill(b, f);
+
+    uint32_t max_blocks[4] = {0, 0, 0, 0};
+    size_t listed = 0;
+    for (int g = 0; g < 4; ++g) {
+        const size_t slot0 = (g & 1) ? order[g - 1].size() : 0;   // the wide jobs follow the narrow ones of their kind
+        for (size_t s = 0; s < order[g].size(); ++s) {
+            const uint32_t k = order[g][s];
+            const RectsItem& it = b.items[k];
+            const size_t sb = (g & 1) ? 2 : 1, slot = slot0 + s;
+            const uint32_t n_planned = (uint32_t)it.p.blocks.size();
+            uint8_t* const sym = b.d_sym.as<uint8_t>() + it.sym_at;
+            if (g >= 2) memcpy(b.up.data() + list_at + listed * sizeof(uint32_t), it.p.blocks.data(), n_planned * sizeof(uint32_t));
+            for (int c = 0; c < 3; ++c) {
+                SplitJob sj = batch_channel_job(b, f, it.container, c);
+                sj.sym = sym + (size_t)c * it.dv.padded * sb;
+                sj.flags = d_flags + 3 * C + 3 * (size_t)k + (size_t)c;
+                if (g < 2) {
+                    SplitFramesJob j = it.p.ranges;
+                    j.j = sj;
+                    memcpy(b.up.data() + frames_at + (3 * slot + (size_t)c) * sizeof(SplitFramesJob), &j, sizeof(j));
+                } else {
+                    SplitBoxJob j = it.p.box;
+                    j.j = sj;
+                    j.blocks = (const uint32_t*)(d_up + list_at) + listed; j.n_planned = n_planned;
+                    memcpy(b.up.data() + box_at + (3 * slot + (size_t)c) * sizeof(SplitBoxJob), &j, sizeof(j));
+                }
+            }
+            if (g >= 2) listed += n_planned;
+            max_blocks[g] = std::max(max_blocks[g], n_planned);
+        }
+    }
+
+    // the finish of the batched items: the window inverse's records, then the pastes'
+    std::vector<RectFinish> fin;
+    std::vector<RectPaste> pastes;
+    for (const RectsItem& it : b.items) {
+        if (!it.batched) continue;
+        const SplitHeader& h = b.cs[it.container].h;
+        const InverseBounds ib = inverse_bounds(h.wavelet, h.step, is_wide(h.fmt) ? kWideMaxQ : kByteMaxQ);
+        const RgbLayout full = it.whole ? it.out : packed_rgb(b.d_tmp.as<uint8_t>() + it.tmp_at, it.dx);
+        RectFinish r{};
+        r.d_sym = b.d_sym.as<uint8_t>() + it.sym_at; r.dv = it.dv;
+        r.win = FrameWindow{it.first - it.p.ta, it.first - it.p.ta + it.count};
+        r.format = (int)h.fmt; r.wavelet = h.wavelet;
+        for (int c = 0; c < 3; ++c) r.step[c] = h.step[c];
+        r.exact = ib.exact; r.mid16 = ib.mid16; r.lds16 = ib.lds16;
+        r.d_slot = b.d_slot.as<uint8_t>() + it.slot_at; r.rgb = full;
+        fin.push_back(r);
+        if (!it.whole) pastes.push_back(RectPaste{full, it.x - it.p.xa, it.y - it.p.ya, it.w, it.h, it.count, it.out});
+    }
+    std::vector<RectFinishLaunch> finishes;
+    std::vector<RectPasteLaunch> paste_launches;
+    if (!rects_records_plan(fin.data(), (uint32_t)fin.size(), b.up.data() + t_rec_at, b.up.data() + xy_rec_at, finishes) ||
+        !rect_paste_records_plan(pastes.data(), (uint32_t)pastes.size(), b.up.data() + paste_rec_at, paste_launches))
+        return fail(kInternal, "rects: no finish kernel for an item's volume");
+
+    TRY(batch_front_launch(b, f));
+    const SplitFramesJob* d_frames = (const SplitFramesJob*)(d_up + frames_at);
+    const SplitBoxJob* d_box = (const SplitBoxJob*)(d_up + box_at);
+    if (!order[0].empty()) { launch_split_frames_decode(d_frames, (int)(3 * order[0].size()), max_blocks[0], false, st); ++b.lane_launches; }
+    if (!order[1].empty()) { launch_split_frames_decode(d_frames + 3 * order[0].size(), (int)(3 * order[1].size()), max_blocks[1], true, st); ++b.lane_launches; }
+    if (!order[2].empty()) { launch_split_box_decode(d_box, (int)(3 * order[2].size()), max_blocks[2], false, true, st); ++b.lane_launches; }
+    if (!order[3].empty()) { launch_split_box_decode(d_box + 3 * order[2].size(), (int)(3 * order[3].size()), max_blocks[3], true, true, st); ++b.lane_launches; }
+    TRY(batch_verdict(b, f, bad_item));
+
+    for (const RectFinishLaunch& l : finishes) { launch_rects_inverse_many(d_up + t_rec_at, d_up + xy_rec_at, l, st); ++b.finish_launches; }
+    for (const RectPasteLaunch& l : paste_launches) { launch_rgb_rect_paste_many(d_up + paste_rec_at, l, st); ++b.finish_launches; }
+    // the items the work lists do not take (the generic path; an inverse cut into bands), one after another
+    DecodeWork none;   // (an item with a band slot allocates nothing in inverse_window)
+    for (size_t k = 0; k < N; ++k) {
+        const RectsItem& it = b.items[k];
+        if (it.batched) continue;
+        const SplitHeader& h = b.cs[it.container].h;
+        DecodeWork& dw = b.works[k] ? *b.works[k] : none;
+        const RgbLayout full = it.whole ? it.out : packed_rgb(b.d_tmp.as<uint8_t>() + it.tmp_at, it.dx);
+        TRY(inverse_window(b.d_sym.as<uint8_t>() + it.sym_at, it.dv, it.first - it.p.ta, it.first - it.p.ta + it.count, h.wavelet, h.step,
+                           it.has_slot ? (void*)(b.d_slot.as<uint8_t>() + it.slot_at) : nullptr, dw, full, st, h.fmt));
+        if (!it.whole) launch_rgb_rect_paste(full, it.x - it.p.xa, it.y - it.p.ya, it.w, it.h, it.count, it.out, st);
+        ++b.fallback_items;
+    }
+    HIP_TRY(hipGetLastError());
+    if (drain_at_end) TRY(b.drain());
+    return kOk;
+}
+
+void rects_done(const RectsBatch& b, uint64_t uploaded) {
+    uint64_t blocks = 0, stored = 0, frames = 0;
+    for (const RectsItem& it : b.items) { blocks += 3ull * it.p.blocks.size(); stored += 3 * it.p.stored; frames += it.count; }
+    const uint64_t v[11] = {b.items.size(), b.cs.size(), b.table_launches, b.lane_launches, b.finish_launches, b.fallback_items, b.drains,
+                            blocks, uploaded, stored, frames};
+    memcpy(tl_rects_stats, v, sizeof(v));
+}
+
+}  // namespace
+
+extern "C" {
+
+int alice_codec_dev_decode_rects(const alice_codec_rect_item* items, uint32_t n_items, uint32_t* bad_item, void* hip_stream) {
+    clear_error();
+    RectsBatch b;
+    TRY(rects_collect(items, n_items, true, bad_item, b));
+    TRY(ensure_device());
+    b.st = (hipStream_t)hip_stream;
+    ScopeStream scope(b.st);
+    TRY(batch_fetch_headers(b));
+    TRY(rects_validate(b, bad_item, [](const BatchContainer& c) { return c.raw; }));
+    TRY(rects_outputs_disjoint(rects_outs(b), bad_item));
+    TRY(rects_device(b, bad_item, true));
+    rects_done(b, 0);
+    return kOk;
+}
+
+uint8_t* alice_codec_decode_rects(const alice_codec_rect_item* items, uint32_t n_items, uint64_t* offsets, uint32_t* bad_item) {
+    clear_error();
+    RectsBatch b;
+    if (rects_collect(items, n_items, false, bad_item, b) != kOk) return nullptr;
+    if (!offsets) { fail(kNullArgument, "null argument"); return nullptr; }
+    if (rects_validate(b, bad_item, [](const BatchContainer& c) { return c.src; }) != kOk) return nullptr;
+    uint64_t uploaded = 0, total = 0;
+    if (batch_host_spans(b, bad_item, uploaded) != kOk) return nullptr;
+    for (const RectsItem& it : b.items) total += it.bytes;
+    std::unique_ptr<uint8_t, decltype(&free)> out(host_result_alloc(total), &free);   // freed on every failure below
+    if (!out) { fail(kOutOfMemory, "out of host memory"); return nullptr; }
+    auto run = [&]() -> int {
+        TRY(get_stream(&b.st));
+        TRY(batch_host_upload(b, total));
+        uint64_t at = 0;
+        for (RectsItem& it : b.items) {
+            it.d_rgb = b.d_rgb.as<uint8_t>() + at;
+            it.out = RgbLayout{it.d_rgb, 3ull * it.w, 3ull * it.w * it.h};
+            at += it.bytes;
+        }
+        TRY(rects_device(b, bad_item, false));
+        ++b.drains;
+        return copy_to_host(out.get(), b.d_rgb.p, total, b.st);
+    };
+    if (run() != kOk) return nullptr;
+    uint64_t at = 0;
+    for (size_t k = 0; k < b.items.size(); ++k) { offsets[k] = at; at += b.items[k].bytes; }
+    offsets[b.items.size()] = at;
+    rects_done(b, uploaded);
+    return out.release();
+}
+
+void alice_codec_test_last_rects_stats(uint64_t out[11]) {
+    if (out) memcpy(out, tl_rects_stats, sizeof(tl_rects_stats));
+}
+
+int alice_codec_test_rects_outputs_disjoint(const alice_codec_rect_item* items, uint32_t n_items, uint32_t* bad_item) {
+    clear_error();
+    if (bad_item) *bad_item = kPreviewsNoItem;
+    if (!items) return fail(kNullArgument, "null argument");
+    std::vector<RectsOut> r(n_items);
+    for (uint32_t k = 0; k < n_items; ++k) {
+        const alice_codec_rect_item& it = items[k];
+        RgbLayout out;
+        if (!it.w || !it.h || !it.count) return fail_item(k, bad_item, kInvalidDimensions, "the rule needs an explicit rectangle and a frame count");
+        if (rect_output_layout(it.rgb_out, it.w, it.h, it.row_pitch, it.frame_pitch, out) != kOk) return fail_item(k, bad_item, tl_err, std::string(tl_msg));
+        r[k] = RectsOut{(uintptr_t)out.base, it.count, it.h, 3ull * it.w, out.row_pitch, out.frame_pitch};
+    }
+    return rects_outputs_disjoint(r, bad_item);
 }
 
 }  // extern "C"

@@ -245,11 +245,12 @@ void launch_ycocg_to_rgb(const int16_t* y, const int16_t* co, const int16_t* cg,
 // their base at the rectangle's first byte.  A workgroup takes whole rows, its threads the V-sized pieces of a row and one
 // of them the row's last row_bytes % sizeof(V) bytes; the launcher picks the widest V that every row start of both sides
 // is aligned to.  All offsets are 64-bit.
+// (the row body, shared with the work-list kernel below: rows first, first + stride, ... of one rectangle)
 template <typename V>
-__global__ __launch_bounds__(256) void rgb_rect_paste_kernel(RgbLayout src, RgbLayout dst, unsigned long long row_bytes, uint32_t h,
-                                                             unsigned long long rows) {
+__device__ __forceinline__ void rgb_rect_paste_rows(const RgbLayout& src, const RgbLayout& dst, unsigned long long row_bytes, uint32_t h,
+                                                    unsigned long long rows, unsigned long long first, unsigned long long stride) {
     const unsigned long long nv = row_bytes / sizeof(V);
-    for (unsigned long long row = blockIdx.x; row < rows; row += gridDim.x) {
+    for (unsigned long long row = first; row < rows; row += stride) {
         const unsigned long long t = row / h, y = row % h;
         const uint8_t* __restrict__ s = src.base + t * src.frame_pitch + y * src.row_pitch;
         uint8_t* __restrict__ d = dst.base + t * dst.frame_pitch + y * dst.row_pitch;
@@ -258,16 +259,97 @@ __global__ __launch_bounds__(256) void rgb_rect_paste_kernel(RgbLayout src, RgbL
     }
 }
 
+template <typename V>
+__global__ __launch_bounds__(256) void rgb_rect_paste_kernel(RgbLayout src, RgbLayout dst, unsigned long long row_bytes, uint32_t h,
+                                                             unsigned long long rows) {
+    rgb_rect_paste_rows<V>(src, dst, row_bytes, h, rows, blockIdx.x, gridDim.x);
+}
+
+// The rectangle of launch_rgb_rect_paste's arguments, and the piece width its launcher picks: 16, 4 or 1
+static RgbLayout rect_paste_source(const RgbLayout& src, uint32_t x, uint32_t y) {
+    return RgbLayout{src.base + y * src.row_pitch + 3ull * x, src.row_pitch, src.frame_pitch};
+}
+static int rect_paste_piece(const RgbLayout& s, const RgbLayout& dst, unsigned long long row_bytes) {
+    const uint64_t bits = (uintptr_t)s.base | (uintptr_t)dst.base | s.row_pitch | s.frame_pitch | dst.row_pitch | dst.frame_pitch;
+    if (bits % 16 == 0 && row_bytes >= 16) return 16;
+    if (bits % 4 == 0 && row_bytes >= 4) return 4;
+    return 1;
+}
+static unsigned rect_paste_grid(unsigned long long rows) {
+    return (unsigned)std::min<unsigned long long>(rows, std::min(g_grid_cap.load(std::memory_order_relaxed), 65536u));
+}
+
 void launch_rgb_rect_paste(const RgbLayout& src, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t n_frames, const RgbLayout& dst,
                            hipStream_t st) {
     const unsigned long long rows = (unsigned long long)h * n_frames, row_bytes = 3ull * w;
     if (!rows || !w) return;
-    const RgbLayout s{src.base + y * src.row_pitch + 3ull * x, src.row_pitch, src.frame_pitch};
-    const uint64_t bits = (uintptr_t)s.base | (uintptr_t)dst.base | s.row_pitch | s.frame_pitch | dst.row_pitch | dst.frame_pitch;
-    const dim3 grid((unsigned)std::min<unsigned long long>(rows, std::min(g_grid_cap.load(std::memory_order_relaxed), 65536u)));
-    if (bits % 16 == 0 && row_bytes >= 16) hipLaunchKernelGGL(rgb_rect_paste_kernel<uint4>, grid, dim3(256), 0, st, s, dst, row_bytes, h, rows);
-    else if (bits % 4 == 0 && row_bytes >= 4) hipLaunchKernelGGL(rgb_rect_paste_kernel<uint32_t>, grid, dim3(256), 0, st, s, dst, row_bytes, h, rows);
+    const RgbLayout s = rect_paste_source(src, x, y);
+    const dim3 grid(rect_paste_grid(rows));
+    const int piece = rect_paste_piece(s, dst, row_bytes);
+    if (piece == 16) hipLaunchKernelGGL(rgb_rect_paste_kernel<uint4>, grid, dim3(256), 0, st, s, dst, row_bytes, h, rows);
+    else if (piece == 4) hipLaunchKernelGGL(rgb_rect_paste_kernel<uint32_t>, grid, dim3(256), 0, st, s, dst, row_bytes, h, rows);
     else hipLaunchKernelGGL(rgb_rect_paste_kernel<uint8_t>, grid, dim3(256), 0, st, s, dst, row_bytes, h, rows);
+}
+
+// Many rectangle pastes of one piece width in one launch (batched rectangles): a flattened work list.
+// Record r owns the workgroups [wg_first, next record's wg_first) of the launch -- as many as launch_rgb_rect_paste would
+// launch for it -- which stride over its own rows; records in ascending wg_first with recs[0].wg_first = 0, the grid their sum.
+struct RectPasteItem {
+    RgbLayout src, dst;
+    unsigned long long row_bytes;
+    uint32_t h;
+    unsigned long long rows;
+    uint32_t wg_first;
+};
+template <typename V>
+__global__ __launch_bounds__(256) void rgb_rect_paste_many_kernel(const RectPasteItem* __restrict__ recs, uint32_t n) {
+    uint32_t lo = 0u, hi = n;      // recs[lo].wg_first <= blockIdx.x < recs[hi].wg_first (hi == n: the end of the grid)
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (recs[mid].wg_first <= blockIdx.x) lo = mid; else hi = mid;
+    }
+    const RectPasteItem r = recs[lo];
+    const uint32_t end = lo + 1u < n ? recs[lo + 1u].wg_first : gridDim.x;
+    rgb_rect_paste_rows<V>(r.src, r.dst, r.row_bytes, r.h, r.rows, blockIdx.x - r.wg_first, end - r.wg_first);
+}
+
+size_t rect_paste_record_bytes() { return sizeof(RectPasteItem); }
+
+bool rect_paste_records_plan(const RectPaste* items, uint32_t n, void* h_records, std::vector<RectPasteLaunch>& launches) {
+    launches.clear();
+    std::vector<uint32_t> order(n);
+    std::vector<int> piece(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const RectPaste& it = items[i];
+        if (!it.w || !it.h || !it.n_frames) return false;
+        piece[i] = rect_paste_piece(rect_paste_source(it.src, it.x, it.y), it.dst, 3ull * it.w);
+        order[i] = i;
+    }
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return piece[x] > piece[y]; });
+    RectPasteItem* recs = (RectPasteItem*)h_records;
+    for (uint32_t k = 0; k < n; ++k) {
+        const RectPaste& it = items[order[k]];
+        if (launches.empty() || launches.back().piece != piece[order[k]]) launches.push_back(RectPasteLaunch{piece[order[k]], k, 0u, 0u});
+        RectPasteLaunch& l = launches.back();
+        RectPasteItem r{};
+        r.src = rect_paste_source(it.src, it.x, it.y); r.dst = it.dst;
+        r.row_bytes = 3ull * it.w; r.h = it.h; r.rows = (unsigned long long)it.h * it.n_frames;
+        const unsigned wgs = rect_paste_grid(r.rows);
+        if (wgs > 0x7FFFFFFFu - l.grid) return false;
+        r.wg_first = l.grid;
+        recs[k] = r;
+        l.grid += wgs;
+        ++l.count;
+    }
+    return true;
+}
+
+void launch_rgb_rect_paste_many(const void* d_records, const RectPasteLaunch& l, hipStream_t st) {
+    if (!l.count || !l.grid) return;
+    const RectPasteItem* recs = (const RectPasteItem*)d_records + l.first;
+    if (l.piece == 16) hipLaunchKernelGGL(rgb_rect_paste_many_kernel<uint4>, dim3(l.grid), dim3(256), 0, st, recs, l.count);
+    else if (l.piece == 4) hipLaunchKernelGGL(rgb_rect_paste_many_kernel<uint32_t>, dim3(l.grid), dim3(256), 0, st, recs, l.count);
+    else hipLaunchKernelGGL(rgb_rect_paste_many_kernel<uint8_t>, dim3(l.grid), dim3(256), 0, st, recs, l.count);
 }
 
 // ---- pad / strip (src/pipeline.rs:77-114, 603-611) ---------------------------------------

@@ -217,6 +217,32 @@ struct PreviewFinishLaunch { int cls; uint32_t first, count, grid; };   // recor
 size_t preview_record_bytes();
 bool preview_records_plan(const PreviewFinish* items, uint32_t n, void* h_records, std::vector<PreviewFinishLaunch>& launches);
 void launch_preview_inverse_many(const void* d_records, const PreviewFinishLaunch& l, hipStream_t st);
+// The window inverse over many virtual chunks in one queue (batched frame ranges and rectangles).  An
+// item is what launch_inverse_transform_window takes, with a band slot of its own (d_slot: inverse_scratch_bytes of the kept
+// frames' chunk).  rects_finish_batchable: the tile kernels take dv and the kept frames' inverse is one band; every other
+// item runs through launch_inverse_transform_window (or the generic path) on its own.  rects_records_plan checks every item
+// as the single launcher checks its arguments, derives the two roles' arguments with the single launcher's code, groups the
+// items by instance class with a stable sort -- temporal role: lifting steps x {exact i32, fast i32, i16} x {u8, wide, wide
+// mirrored}, 18; tile role: lifting steps x inverse_variant x mirrored, 16 -- writes the records of each role, class after
+// class, to h_t_records / h_xy_records (n * rects_record_bytes(role) bytes each) and names the launches: every temporal
+// launch, then every tile launch.  false: an item is no such volume.  launch_rects_inverse_many runs one of them over the
+// records' device copies: a flattened work list whose grid is the sum of the items' own workgroups (tile role: padded to a
+// multiple of 8, the XCD order over the whole list).
+struct RectFinish {
+    const void* d_sym;
+    ChunkDims dv;
+    FrameWindow win;
+    int format, wavelet;
+    int32_t step[3];
+    bool exact, mid16, lds16;
+    void* d_slot;
+    RgbLayout rgb;               // win.hi - win.lo frames of dv.w x dv.h
+};
+struct RectFinishLaunch { int role, cls; uint32_t first, count, grid; };   // role 0 temporal, 1 tile; records [first, first + count)
+size_t rects_record_bytes(int role);
+bool rects_finish_batchable(const ChunkDims& dv, uint32_t frames_kept, bool exact, bool mid16);
+bool rects_records_plan(const RectFinish* items, uint32_t n, void* h_t_records, void* h_xy_records, std::vector<RectFinishLaunch>& launches);
+void launch_rects_inverse_many(const void* d_t_records, const void* d_xy_records, const RectFinishLaunch& l, hipStream_t st);
 
 // ---- transform.hip, stage level: Wavelet2D / Wavelet3D of caller-shaped i32 data on the tile kernels' exact instances ----
 // eligible: even width and height >= 6, even depth (or depth 1); otherwise the caller uses launch_wavelet_axis.
@@ -245,6 +271,19 @@ void launch_ycocg_to_rgb(const int16_t* y, const int16_t* co, const int16_t* cg,
 // (0, 0) .. of the frames of `dst`; nothing else of dst is written and nothing else of src is read.  Any alignment.
 void launch_rgb_rect_paste(const RgbLayout& src, uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t n_frames, const RgbLayout& dst,
                            hipStream_t st);
+// Many such pastes in one queue (batched rectangles).  rect_paste_records_plan groups the items by the
+// piece width the single launcher would pick (16, 4 or 1 bytes: the same alignment test on both sides) with a stable sort,
+// writes their device records, widest group first, to h_records (n * rect_paste_record_bytes() bytes) and names one launch
+// per width present; an item's workgroups are what the single launcher's grid would be.  false: an empty rectangle.
+struct RectPaste {
+    RgbLayout src;
+    uint32_t x, y, w, h, n_frames;
+    RgbLayout dst;
+};
+struct RectPasteLaunch { int piece; uint32_t first, count, grid; };   // records [first, first + count), `grid` workgroups
+size_t rect_paste_record_bytes();
+bool rect_paste_records_plan(const RectPaste* items, uint32_t n, void* h_records, std::vector<RectPasteLaunch>& launches);
+void launch_rgb_rect_paste_many(const void* d_records, const RectPasteLaunch& l, hipStream_t st);
 void launch_pad_channel(const int16_t* ch, const ChunkDims& d, int32_t* out, hipStream_t st);
 void launch_strip_channel(const int32_t* in, const ChunkDims& d, int16_t* ch, hipStream_t st);
 void launch_quantize(const int32_t* in, int32_t* out, uint64_t n, int32_t step, int32_t dead_zone, hipStream_t st);

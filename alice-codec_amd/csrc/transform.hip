@@ -151,14 +151,19 @@ struct BandTiles {
 
 // workgroup -> tile.  XCD-aware order (xcd_logical_block): XCD k takes the k-th contiguous eighth of the sequence
 // (frame-major, then tile row, then tile), so a tile's neighbours hit in the same L2.
-__device__ __forceinline__ bool band_tile_of_block(const BandTiles& bt, unsigned frames, int& bx, int& by, int& t, bool& edge) {
-    const unsigned per_frame = (unsigned)(bt.nx * bt.nby);
-    const unsigned l = xcd_logical_block(per_frame * frames);
-    if (l == 0xFFFFFFFFu) return false;
+// In two halves: the function of the logical index (the flattened work lists of section 18 run it on an index into one
+// record's tiles), and the head that reads blockIdx.
+__device__ __forceinline__ void band_tile_of_logical(const BandTiles& bt, unsigned per_frame, unsigned l, int& bx, int& by, int& t, bool& edge) {
     t = (int)(l / per_frame);
     const int i = (int)(l % per_frame);
     bx = i % bt.nx; by = bt.by0 + i / bt.nx;
     edge = !(bx >= bt.ix0 && bx < bt.ix1 && by >= bt.iy0 && by < bt.iy1);
+}
+__device__ __forceinline__ bool band_tile_of_block(const BandTiles& bt, unsigned frames, int& bx, int& by, int& t, bool& edge) {
+    const unsigned per_frame = (unsigned)(bt.nx * bt.nby);
+    const unsigned l = xcd_logical_block(per_frame * frames);
+    if (l == 0xFFFFFFFFu) return false;
+    band_tile_of_logical(bt, per_frame, l, bx, by, t, edge);
     return true;
 }
 
@@ -911,17 +916,20 @@ struct InvTw {
     uint32_t pf_out;             // frames per channel of the slot, >= hi - lo
 };
 
+// The two window bodies: workgroup `group` of the 3 * units_per_ch a volume owns.  lut: the workgroup's dequantise table
+// (u8 instance).  The one-volume kernels and the work-list kernels of section 18 below both run them.  step: w.m.step where
+// it lives -- the kernel arguments, or the record in memory: it is indexed by the channel, and a copy of the record that is
+// indexed at run time would go to scratch instead of SGPRs.
 template <int NS, bool EXACT, typename MidT>
-__global__ __launch_bounds__(256) void inv_t_win_kernel(InvTw w) {
-    __shared__ int lut[256];
+__device__ __forceinline__ void inv_t_win_body(const InvTw& w, const int* __restrict__ step, uint32_t group, int (&lut)[256]) {
     const InvTm& a = w.m;
     const int tid = threadIdx.x;
-    const int ch = (int)(blockIdx.x / a.b.units_per_ch);
-    const uint32_t blk = blockIdx.x % a.b.units_per_ch;
+    const int ch = (int)(group / a.b.units_per_ch);
+    const uint32_t blk = group % a.b.units_per_ch;
     {
         const int s = tid;
         const int q = (s == 0) ? 0 : ((s & 1) ? (s + 1) / 2 : -(s / 2));      // src/quant.rs:581-587
-        lut[s] = (int)((unsigned)q * (unsigned)a.step[ch]);                   // src/quant.rs:104-110 (wrapping)
+        lut[s] = (int)((unsigned)q * (unsigned)step[ch]);                     // src/quant.rs:104-110 (wrapping)
     }
     __syncthreads();
     const uint32_t idx = (blk * 256u + (uint32_t)tid) * 4u;
@@ -938,11 +946,11 @@ __global__ __launch_bounds__(256) void inv_t_win_kernel(InvTw w) {
 }
 
 template <int NS, bool EXACT, typename MidT, bool MIRROR>
-__global__ __launch_bounds__(256) void inv_t_wide_win_kernel(InvTw w) {
+__device__ __forceinline__ void inv_t_wide_win_body(const InvTw& w, const int* __restrict__ step, uint32_t group) {
     const InvTm& a = w.m;
     const int tid = threadIdx.x;
-    const int ch = (int)(blockIdx.x / a.b.units_per_ch);
-    const uint32_t blk = blockIdx.x % a.b.units_per_ch;
+    const int ch = (int)(group / a.b.units_per_ch);
+    const uint32_t blk = group % a.b.units_per_ch;
     const uint32_t idx = (blk * 256u + (uint32_t)tid) * 4u;
     if (idx >= a.b.band_px) return;
     InvT<NS, EXACT, MidT, 0, true, MIRROR, true> f;
@@ -953,8 +961,53 @@ __global__ __launch_bounds__(256) void inv_t_wide_win_kernel(InvTw w) {
     f.half = (int)a.b.pf / 2; f.nf = (int)w.hi; f.lo = (int)w.lo;
     if (MIRROR) { f.c0 = a.cf.c[0]; f.c1 = a.cf.c[1]; f.c2 = a.cf.c[2]; f.c3 = a.cf.c[3]; }
     else { f.c0 = -a.cf.c[0]; f.c1 = -a.cf.c[1]; f.c2 = -a.cf.c[2]; f.c3 = -a.cf.c[3]; }
-    f.lut = nullptr; f.step = a.step[ch];
+    f.lut = nullptr; f.step = step[ch];
     f.run();
+}
+
+template <int NS, bool EXACT, typename MidT>
+__global__ __launch_bounds__(256) void inv_t_win_kernel(InvTw w) {
+    __shared__ int lut[256];
+    inv_t_win_body<NS, EXACT, MidT>(w, w.m.step, blockIdx.x, lut);
+}
+
+template <int NS, bool EXACT, typename MidT, bool MIRROR>
+__global__ __launch_bounds__(256) void inv_t_wide_win_kernel(InvTw w) {
+    inv_t_wide_win_body<NS, EXACT, MidT, MIRROR>(w, w.m.step, blockIdx.x);
+}
+
+// The window role over many volumes of one instance class (batched frame ranges and rectangles): the
+// flattened work list of preview_inv_many_kernel.  Record r owns the workgroups [wg_first, wg_first + 3 * units_per_ch) of
+// the launch, the records in ascending wg_first with recs[0].wg_first = 0, and the grid is the sum.  A workgroup finds its
+// record by bisection (wave-uniform loads) and runs the one-volume body on a copy of it; the u8 instance fills its table
+// from the record's steps (read where the record lies).
+struct InvTwItem {
+    InvTw w;
+    uint32_t wg_first;           // the record's first workgroup of the launch
+};
+template <typename Rec>
+__device__ __forceinline__ uint32_t work_list_record(const Rec* __restrict__ recs, uint32_t n, uint32_t l) {
+    uint32_t lo = 0u, hi = n;      // recs[lo].wg_first <= l < recs[hi].wg_first (hi == n: the end of the list)
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (recs[mid].wg_first <= l) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+template <int NS, bool EXACT, typename MidT>
+__global__ __launch_bounds__(256) void inv_t_win_many_kernel(const InvTwItem* __restrict__ recs, uint32_t n) {
+    __shared__ int lut[256];
+    const uint32_t r = work_list_record(recs, n, blockIdx.x);
+    const InvTw w = recs[r].w;
+    inv_t_win_body<NS, EXACT, MidT>(w, recs[r].w.m.step, blockIdx.x - recs[r].wg_first, lut);
+}
+
+template <int NS, bool EXACT, typename MidT, bool MIRROR>
+__global__ __launch_bounds__(256) void inv_t_wide_win_many_kernel(const InvTwItem* __restrict__ recs, uint32_t n) {
+    const uint32_t r = work_list_record(recs, n, blockIdx.x);
+    const InvTw w = recs[r].w;
+    inv_t_wide_win_body<NS, EXACT, MidT, MIRROR>(w, recs[r].w.m.step, blockIdx.x - recs[r].wg_first);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1409,6 +1462,37 @@ __global__ __launch_bounds__(InvTileShape<PACKED>::kThreads) void inv_xy_kernel(
     }
 }
 
+// The tile role over many chunks of one instance class (batched frame ranges and rectangles).  Record r
+// owns the tiles [wg_first, wg_first + nx * nby * d.f) of the flattened tile sequence, the records in ascending wg_first with
+// recs[0].wg_first = 0; `total` is the sum.  The XCD order runs over the WHOLE list: the grid is xcd_grid(total), a workgroup
+// maps to a logical index of the list, the padding workgroups leave, and the bisection runs on the logical index -- XCD k
+// takes a contiguous eighth of the tile sequence, so a tile's neighbours (the same record's, but for the record edges)
+// share an L2.  The record is copied once (a wave-uniform address: scalar loads) and the tile functions run on the copy as
+// they run on inv_xy_kernel's argument; no pointer into the list stays live across the tile body.
+struct InvXyItem {
+    InvXy xa;
+    uint32_t wg_first;           // the record's first tile of the list
+};
+template <int NS, bool EXACT, typename MidT, bool PACKED, bool MIRROR>
+__global__ __launch_bounds__(InvTileShape<PACKED>::kThreads) void inv_xy_many_kernel(const InvXyItem* __restrict__ recs, uint32_t n, uint32_t total) {
+    __shared__ __attribute__((aligned(16))) int lds[InvTileShape<PACKED>::kLdsInts];
+    const unsigned l = xcd_logical_block(total);
+    if (l == 0xFFFFFFFFu) return;
+    const uint32_t r = work_list_record(recs, n, l);
+    const unsigned in_rec = l - recs[r].wg_first;
+    const InvXy xa = recs[r].xa;
+    int bx, by, t;
+    bool edge;
+    band_tile_of_logical(xa.bt, (unsigned)(xa.bt.nx * xa.bt.nby), in_rec, bx, by, t, edge);
+    if (PACKED) {
+        if (edge) inv_xy_tile_packed<NS, true, EXACT, MidT, MIRROR>(xa, bx, by, t, lds);
+        else inv_xy_tile_packed<NS, false, EXACT, MidT, MIRROR>(xa, bx, by, t, lds);
+    } else {
+        if (edge) inv_xy_tile_dpp<NS, true, EXACT, MidT, 0, MIRROR>(xa, bx, by, t, lds);
+        else inv_xy_tile_dpp<NS, false, EXACT, MidT, 0, MIRROR>(xa, bx, by, t, lds);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Stage-level Wavelet2D / Wavelet3D on caller-shaped i32 data (src/wavelet.rs:292-340, 392-484): the same tile
 // structure as the pipeline kernels with the reference's exact arithmetic (wrapping i32 sums, 64-bit products), so any
@@ -1811,53 +1895,81 @@ static void inv_band_launch(const InvTm& ta, const InvXy& xa, hipStream_t st, co
     hipLaunchKernelGGL((inv_xy_kernel<NS, EXACT, MidT, PACKED, PROBE, MIRROR>), dim3(xcd_grid(tiles)), dim3(InvTileShape<PACKED>::kThreads), 0, st, xa);
 }
 
-// WIDE: d_sym is the u16 symbol volume of .alc v3 and the temporal role runs its wide instance; everything else is shared.
-// MIRROR: both roles run their mirrored instances (.alc v4); the geometry, the bands and the instance choice are the same.
-// win (frame ranges): dt is the virtual chunk the temporal role lifts, and only its frames [lo, hi) reach the slot, the
-// tile role and `rgb`, as a chunk of hi - lo frames (d below); the bands are that chunk's.
-template <bool WIDE, bool MIRROR = false>
-static bool inverse_launches(const void* d_sym, const ChunkDims& dt, int wavelet, const int32_t step[3],
-                             bool exact, bool mid16, bool lds16, void* d_scratch, const RgbLayout& rgb, hipStream_t st,
-                             const FrameWindow* win = nullptr) {
+// What the inverse launches of a chunk share: the chunk the tile role sees, the instance, the bands and the interior
+// rectangle.  inverse_geometry checks the arguments (false: the generic path, or no such window) and inverse_band_args
+// builds the two roles' arguments of one band; inverse_launches and the batched planner (rects_records_plan) both go
+// through them.
+struct InvGeometry {
+    ChunkDims d;                 // the chunk of the tile role: dt, or its window's frames
+    int ns, variant;             // lifting steps; inverse_variant
+    Coeffs cf;
+    BandPlan bp;
+    unsigned nx, ny, ix1, iy1;   // tiles over the REAL frame (every pixel written exists); the interior rectangle's end
+    int n_bands;
+};
+static bool inverse_geometry(const ChunkDims& dt, int wavelet, bool exact, bool mid16, bool lds16, const FrameWindow* win, InvGeometry& g) {
     if (!transform_tiles_eligible(dt)) return false;
     if (win && !(win->lo < win->hi && win->hi <= dt.pf)) return false;
-    const ChunkDims d = win ? make_dims(dt.w, dt.h, win->hi - win->lo) : dt;
+    g.d = win ? make_dims(dt.w, dt.h, win->hi - win->lo) : dt;
+    const ChunkDims& d = g.d;
     const LiftSteps ls = lift_steps(wavelet);
+    g.ns = ls.n;
     // mid16: the host proved every value after the inverse temporal pass fits i16 (then exact is false too);
     // lds16: also after the inverse column pass (packed tile).
     // variant: 0 exact (i32), 1 fast i32, 2 fast i16 lane-exchange tile, 3 fast i16 packed tile
-    const int variant = inverse_variant(exact, mid16, lds16);
-    const BandPlan bp = plan_bands(d, I_TH, variant >= 2 ? sizeof(int16_t) : sizeof(int32_t), 4);
-    const Coeffs cf = to_coeffs(ls);
-    const unsigned nx = (d.w + I_TW - 1) / I_TW, ny = (d.h + I_TH - 1) / I_TH;   // tiles over the REAL frame (every pixel written exists)
+    g.variant = inverse_variant(exact, mid16, lds16);
+    g.bp = plan_bands(d, I_TH, g.variant >= 2 ? sizeof(int16_t) : sizeof(int32_t), 4);
+    g.cf = to_coeffs(ls);
+    g.nx = (d.w + I_TW - 1) / I_TW; g.ny = (d.h + I_TH - 1) / I_TH;
     // a tile is interior when the range it reads, [gx0 - 4, gx0 + 96 + 4) x [gy0 - 4, gy0 + 32 + 4), lies inside w x h
     // (then inside the padded frame too)
     auto interior_x = [&](unsigned bx) { return bx >= 1 && (bx * I_TW + I_TW + 4) <= d.w; };
     auto interior_y = [&](unsigned by) { return by >= 1 && (by * I_TH + I_TH + 4) <= d.h; };
-    unsigned ix1 = 1, iy1 = 1;
-    while (ix1 < nx && interior_x(ix1)) ++ix1;
-    while (iy1 < ny && interior_y(iy1)) ++iy1;
+    g.ix1 = 1; g.iy1 = 1;
+    while (g.ix1 < g.nx && interior_x(g.ix1)) ++g.ix1;
+    while (g.iy1 < g.ny && interior_y(g.iy1)) ++g.iy1;
+    g.n_bands = g.bp.n_bands > 1 ? ((int)g.ny + g.bp.tpb - 1) / g.bp.tpb : 1;
+    return true;
+}
+static void inverse_band_args(const InvGeometry& g, int band, const void* d_sym, const ChunkDims& dt, const int32_t step[3], void* d_scratch,
+                              const RgbLayout& rgb, InvTm& ta, InvXy& xa) {
+    const ChunkDims& d = g.d;
     const int hh = (int)(d.ph / 2);
     const uint32_t pw = (uint32_t)d.pw;
-    const int n_bands = bp.n_bands > 1 ? ((int)ny + bp.tpb - 1) / bp.tpb : 1;
-    const int probe = (!WIDE && ls.n == 4 && variant == 2) ? tl_valu_probe : 0;
-    for (int band = 0; band < n_bands; ++band) {
-        const int by0 = n_bands > 1 ? band * bp.tpb : 0, nby = n_bands > 1 ? std::min(bp.tpb, (int)ny - by0) : (int)ny;
-        // slot rows: the band's own rows plus two halo rows of each half on either side, inside the frame
-        int L0 = 0, L1 = hh;
-        if (n_bands > 1) {
-            const int Y0 = by0 * I_TH, Y1 = (int)std::min<uint64_t>((uint64_t)(by0 + nby) * I_TH, d.ph);
-            L0 = std::max(0, Y0 / 2 - 2); L1 = std::min(hh, Y1 / 2 + 2);
-        }
-        const int rows_l = L1 - L0;
-        InvTm ta{};
-        ta.sym = (const uint8_t*)d_sym; ta.mid = d_scratch; ta.cf = cf; ta.step[0] = step[0]; ta.step[1] = step[1]; ta.step[2] = step[2]; ta.nf = d.f;
-        ta.b = make_band_t(dt, 2u * (uint32_t)rows_l * pw, (uint32_t)rows_l * pw, (uint32_t)L0 * pw, (uint32_t)(hh + L0) * pw);
-        InvXy xa{};
-        xa.mid = d_scratch; xa.rgb = rgb; xa.d = d; xa.cf = cf;
-        xa.aligned = rgb_dword_aligned(rgb);
-        xa.bt = BandTiles{(int)nx, by0, nby, 1, (int)ix1, 1, (int)iy1};
-        xa.L0 = L0; xa.rows_l = rows_l;
+    const int by0 = g.n_bands > 1 ? band * g.bp.tpb : 0, nby = g.n_bands > 1 ? std::min(g.bp.tpb, (int)g.ny - by0) : (int)g.ny;
+    // slot rows: the band's own rows plus two halo rows of each half on either side, inside the frame
+    int L0 = 0, L1 = hh;
+    if (g.n_bands > 1) {
+        const int Y0 = by0 * I_TH, Y1 = (int)std::min<uint64_t>((uint64_t)(by0 + nby) * I_TH, d.ph);
+        L0 = std::max(0, Y0 / 2 - 2); L1 = std::min(hh, Y1 / 2 + 2);
+    }
+    const int rows_l = L1 - L0;
+    ta = InvTm{};
+    ta.sym = (const uint8_t*)d_sym; ta.mid = d_scratch; ta.cf = g.cf; ta.step[0] = step[0]; ta.step[1] = step[1]; ta.step[2] = step[2]; ta.nf = d.f;
+    ta.b = make_band_t(dt, 2u * (uint32_t)rows_l * pw, (uint32_t)rows_l * pw, (uint32_t)L0 * pw, (uint32_t)(hh + L0) * pw);
+    xa = InvXy{};
+    xa.mid = d_scratch; xa.rgb = rgb; xa.d = d; xa.cf = g.cf;
+    xa.aligned = rgb_dword_aligned(rgb);
+    xa.bt = BandTiles{(int)g.nx, by0, nby, 1, (int)g.ix1, 1, (int)g.iy1};
+    xa.L0 = L0; xa.rows_l = rows_l;
+}
+
+// WIDE: d_sym is the u16 symbol volume of .alc v3 and the temporal role runs its wide instance; everything else is shared.
+// MIRROR: both roles run their mirrored instances (.alc v4); the geometry, the bands and the instance choice are the same.
+// win (frame ranges): dt is the virtual chunk the temporal role lifts, and only its frames [lo, hi) reach the slot, the
+// tile role and `rgb`, as a chunk of hi - lo frames (g.d below); the bands are that chunk's.
+template <bool WIDE, bool MIRROR = false>
+static bool inverse_launches(const void* d_sym, const ChunkDims& dt, int wavelet, const int32_t step[3],
+                             bool exact, bool mid16, bool lds16, void* d_scratch, const RgbLayout& rgb, hipStream_t st,
+                             const FrameWindow* win = nullptr) {
+    InvGeometry g;
+    if (!inverse_geometry(dt, wavelet, exact, mid16, lds16, win, g)) return false;
+    const int variant = g.variant;
+    const int probe = (!WIDE && g.ns == 4 && variant == 2) ? tl_valu_probe : 0;
+    for (int band = 0; band < g.n_bands; ++band) {
+        InvTm ta;
+        InvXy xa;
+        inverse_band_args(g, band, d_sym, dt, step, d_scratch, rgb, ta, xa);
         if (probe && !win) {
             if (probe == 1) inv_band_launch<4, false, int16_t, false, 3>(ta, xa, st);
             else if (probe == 2) inv_band_launch<4, false, int16_t, false, 1>(ta, xa, st);
@@ -1871,10 +1983,106 @@ static bool inverse_launches(const void* d_sym, const ChunkDims& dt, int wavelet
         case 2: inv_band_launch<NS_, false, int16_t, false, 0, WIDE, MIRROR>(ta, xa, st, win); break; \
         default: inv_band_launch<NS_, false, int16_t, true, 0, WIDE, MIRROR>(ta, xa, st, win); break; \
         }
-        if (ls.n == 4) { ALICE_INV(4) } else { ALICE_INV(2) }
+        if (g.ns == 4) { ALICE_INV(4) } else { ALICE_INV(2) }
 #undef ALICE_INV
     }
     return true;
+}
+
+// ---- the batched finish of frame ranges and rectangles ----
+
+size_t rects_record_bytes(int role) { return role == 0 ? sizeof(InvTwItem) : sizeof(InvXyItem); }
+
+bool rects_finish_batchable(const ChunkDims& dv, uint32_t frames_kept, bool exact, bool mid16) {
+    if (!transform_tiles_eligible(dv) || !frames_kept) return false;
+    const int variant = inverse_variant(exact, mid16, false);
+    return plan_bands(make_dims(dv.w, dv.h, frames_kept), I_TH, variant >= 2 ? sizeof(int16_t) : sizeof(int32_t), 4).n_bands == 1;
+}
+
+// temporal class: lifting steps (2) x {exact i32, fast i32, i16} (3) x {u8, wide, wide mirrored} (3)
+static int rects_t_class(int ns, int variant, int format) { return ((ns == 4 ? 1 : 0) * 3 + std::min(variant, 2)) * 3 + format; }
+// tile class: lifting steps (2) x inverse_variant (4) x mirrored (2); the wide container's tile role is the narrow one's
+static int rects_xy_class(int ns, int variant, int format) { return ((ns == 4 ? 1 : 0) * 4 + variant) * 2 + (format == 2 ? 1 : 0); }
+
+bool rects_records_plan(const RectFinish* items, uint32_t n, void* h_t_records, void* h_xy_records, std::vector<RectFinishLaunch>& launches) {
+    launches.clear();
+    struct Planned { InvTwItem t; InvXyItem xy; int t_cls, xy_cls; };
+    std::vector<Planned> pl(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const RectFinish& f = items[i];
+        if (f.format < 0 || f.format > 2) return false;
+        InvGeometry g;
+        if (!inverse_geometry(f.dv, f.wavelet, f.exact, f.mid16, f.lds16, &f.win, g) || g.n_bands != 1) return false;
+        InvTm ta;
+        Planned& p = pl[i];
+        inverse_band_args(g, 0, f.d_sym, f.dv, f.step, f.d_slot, f.rgb, ta, p.xy.xa);
+        p.t.w = InvTw{};
+        p.t.w.m = ta; p.t.w.lo = f.win.lo; p.t.w.hi = f.win.hi; p.t.w.pf_out = (uint32_t)g.d.pf;
+        p.t_cls = rects_t_class(g.ns, g.variant, f.format);
+        p.xy_cls = rects_xy_class(g.ns, g.variant, f.format);
+    }
+    std::vector<uint32_t> order(n);
+    InvTwItem* t_recs = (InvTwItem*)h_t_records;
+    InvXyItem* xy_recs = (InvXyItem*)h_xy_records;
+    for (int role = 0; role < 2; ++role) {
+        for (uint32_t i = 0; i < n; ++i) order[i] = i;
+        auto cls_of = [&](uint32_t i) { return role == 0 ? pl[i].t_cls : pl[i].xy_cls; };
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return cls_of(x) < cls_of(y); });
+        const size_t first_of_role = launches.size();
+        for (uint32_t k = 0; k < n; ++k) {
+            Planned& p = pl[order[k]];
+            const int cls = cls_of(order[k]);
+            if (launches.size() == first_of_role || launches.back().cls != cls) launches.push_back(RectFinishLaunch{role, cls, k, 0u, 0u});
+            RectFinishLaunch& l = launches.back();
+            const uint64_t wgs = role == 0 ? 3ull * p.t.w.m.b.units_per_ch
+                                           : (uint64_t)p.xy.xa.bt.nx * (uint64_t)p.xy.xa.bt.nby * p.xy.xa.d.f;
+            if (wgs > 0x7FFFFFF0ull - l.grid) return false;
+            if (role == 0) { p.t.wg_first = l.grid; t_recs[k] = p.t; }
+            else { p.xy.wg_first = l.grid; xy_recs[k] = p.xy; }
+            l.grid += (uint32_t)wgs;
+            ++l.count;
+        }
+    }
+    return true;
+}
+
+template <int NS>
+static void rects_t_many_launch(const InvTwItem* recs, const RectFinishLaunch& l, hipStream_t st) {
+    const int kind = (l.cls / 3) % 3, format = l.cls % 3;
+    const dim3 grid(l.grid), block(256);
+#define ALICE_T_MANY(EXACT_, MID_) \
+    if (format == 2) hipLaunchKernelGGL((inv_t_wide_win_many_kernel<NS, EXACT_, MID_, true>), grid, block, 0, st, recs, l.count); \
+    else if (format == 1) hipLaunchKernelGGL((inv_t_wide_win_many_kernel<NS, EXACT_, MID_, false>), grid, block, 0, st, recs, l.count); \
+    else hipLaunchKernelGGL((inv_t_win_many_kernel<NS, EXACT_, MID_>), grid, block, 0, st, recs, l.count);
+    if (kind == 0) { ALICE_T_MANY(true, int32_t) }
+    else if (kind == 1) { ALICE_T_MANY(false, int32_t) }
+    else { ALICE_T_MANY(false, int16_t) }
+#undef ALICE_T_MANY
+}
+
+template <int NS, bool MIRROR>
+static void rects_xy_many_launch(const InvXyItem* recs, const RectFinishLaunch& l, hipStream_t st) {
+    const int variant = (l.cls / 2) % 4;
+    const dim3 grid(xcd_grid(l.grid));
+    switch (variant) {
+    case 0: hipLaunchKernelGGL((inv_xy_many_kernel<NS, true, int32_t, false, MIRROR>), grid, dim3(InvTileShape<false>::kThreads), 0, st, recs, l.count, l.grid); break;
+    case 1: hipLaunchKernelGGL((inv_xy_many_kernel<NS, false, int32_t, false, MIRROR>), grid, dim3(InvTileShape<false>::kThreads), 0, st, recs, l.count, l.grid); break;
+    case 2: hipLaunchKernelGGL((inv_xy_many_kernel<NS, false, int16_t, false, MIRROR>), grid, dim3(InvTileShape<false>::kThreads), 0, st, recs, l.count, l.grid); break;
+    default: hipLaunchKernelGGL((inv_xy_many_kernel<NS, false, int16_t, true, MIRROR>), grid, dim3(InvTileShape<true>::kThreads), 0, st, recs, l.count, l.grid); break;
+    }
+}
+
+void launch_rects_inverse_many(const void* d_t_records, const void* d_xy_records, const RectFinishLaunch& l, hipStream_t st) {
+    if (!l.count || !l.grid) return;
+    if (l.role == 0) {
+        const InvTwItem* recs = (const InvTwItem*)d_t_records + l.first;
+        if (l.cls / 9) rects_t_many_launch<4>(recs, l, st); else rects_t_many_launch<2>(recs, l, st);
+        return;
+    }
+    const InvXyItem* recs = (const InvXyItem*)d_xy_records + l.first;
+    const bool ns4 = l.cls / 8, mirror = l.cls & 1;
+    if (ns4) { if (mirror) rects_xy_many_launch<4, true>(recs, l, st); else rects_xy_many_launch<4, false>(recs, l, st); }
+    else { if (mirror) rects_xy_many_launch<2, true>(recs, l, st); else rects_xy_many_launch<2, false>(recs, l, st); }
 }
 
 bool launch_inverse_transform(const uint8_t* d_sym, const ChunkDims& d, int wavelet, const int32_t step[3],

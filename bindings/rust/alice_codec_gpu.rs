@@ -1402,3 +1402,60 @@ pub unsafe fn rect_decode_device(d_alc: *const std::ffi::c_void, length: u64, fi
                                  hip_stream: *mut std::ffi::c_void) -> Result<(), CodecError> {
     check(alice_codec_dev_decode_rect(d_alc, length, first, count, r.x, r.y, r.w, r.h, d_rgb_out, row_pitch, frame_pitch, hip_stream), 0, 0)
 }
+
+// ---- many frame ranges and rectangles in one call ----
+
+/// `alice_codec_rect_item` of include/alice_codec.h (64 bytes); `x = y = w = h = 0` is the whole frame
+#[repr(C)]
+#[derive(Debug, Clone, Copy)]
+pub struct RectItem {
+    pub alc: *const std::ffi::c_void,
+    pub len: u64,
+    pub first: u32,
+    pub count: u32,
+    pub x: u32,
+    pub y: u32,
+    pub w: u32,
+    pub h: u32,
+    pub rgb_out: *mut std::ffi::c_void,
+    pub row_pitch: u64,
+    pub frame_pitch: u64,
+}
+
+pub const RECTS_MAX_ITEMS: u32 = 1024;
+
+extern "C" {
+    fn alice_codec_decode_rects(items: *const RectItem, n_items: u32, offsets: *mut u64, bad_item: *mut u32) -> *mut u8;
+    fn alice_codec_dev_decode_rects(items: *const RectItem, n_items: u32, bad_item: *mut u32,
+                                    hip_stream: *mut std::ffi::c_void) -> c_int;
+}
+
+/// `decode_rect` (or, with `None`, `decode_frames`) of many `(data, first, count, rectangle)` items in one call, one `Vec`
+/// per item in item order.  Items that pass the same slice share its header, tables, directory scan and upload.  All or
+/// nothing: the message of the error of a refused or damaged call starts with `item <index>: `.
+pub fn decode_rects(items: &[(&[u8], u32, u32, Option<Rect>)]) -> Result<Vec<Vec<u8>>, CodecError> {
+    let raw: Vec<RectItem> = items.iter().map(|(d, first, count, r)| {
+        let r = r.unwrap_or(Rect { x: 0, y: 0, w: 0, h: 0 });
+        RectItem { alc: d.as_ptr() as *const std::ffi::c_void, len: d.len() as u64, first: *first, count: *count, x: r.x, y: r.y,
+                   w: r.w, h: r.h, rgb_out: std::ptr::null_mut(), row_pitch: 0, frame_pitch: 0 }
+    }).collect();
+    let mut offsets = vec![0u64; items.len() + 1];
+    let n = u32::try_from(items.len()).unwrap_or(u32::MAX);
+    unsafe {
+        let p = alice_codec_decode_rects(raw.as_ptr(), n, offsets.as_mut_ptr(), std::ptr::null_mut());
+        if p.is_null() { return Err(last_error(0, 0, 0, 0, 0)); }
+        let whole = take(p, offsets[items.len()]);
+        Ok((0..items.len()).map(|i| whole[offsets[i] as usize..offsets[i + 1] as usize].to_vec()).collect())
+    }
+}
+
+/// `rect_decode_device` of many items in one call; returns the index of the item that decided a refusal with the error.
+///
+/// # Safety
+/// As `rect_decode_device` for every item; the outputs must be disjoint (byte ranges apart, or boxes of one pitched surface
+/// that are).
+pub unsafe fn rects_decode_device(items: &[RectItem], hip_stream: *mut std::ffi::c_void) -> Result<(), (CodecError, u32)> {
+    let mut bad = u32::MAX;
+    let n = u32::try_from(items.len()).unwrap_or(u32::MAX);
+    check(alice_codec_dev_decode_rects(items.as_ptr(), n, &mut bad, hip_stream), 0, 0).map_err(|e| (e, bad))
+}

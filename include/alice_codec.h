@@ -799,6 +799,60 @@ uint8_t *alice_codec_decode_rect(const uint8_t *data, uint64_t len, uint32_t fir
 int alice_codec_dev_decode_rect(const void *d_alc, uint64_t len, uint32_t first, uint32_t count, uint32_t x, uint32_t y, uint32_t w,
                                 uint32_t h, void *d_rgb_out, uint64_t row_pitch, uint64_t frame_pitch, void *hip_stream);
 
+/* ---- Many frame ranges and rectangles in one call ----
+ * A detector wants the same crop of frame k of every chunk, a viewer a mosaic of crops pasted into one surface, a sheet
+ * frame 0 of each of N chunks at full resolution.  These calls take an array of items, as the batched preview does; every
+ * item alone means exactly what alice_codec_dev_decode_rect(alc, len, first, count, x, y, w, h, rgb_out, row_pitch,
+ * frame_pitch, stream) means, bit for bit, and an item with x = y = w = h = 0 is the whole frame: what
+ * alice_codec_dev_decode_frames means (its pitches, when given, are those of a rectangle that is the whole frame).  Items
+ * may mix versions 2, 3 and 4, the wavelets, dimensions, lane sizes, ranges and rectangles, and any number of items may name
+ * the same container (the same pointer and the same len): such items share one header fetch, one validation, one set of
+ * tables and one directory scan.  One launch builds every table, one covers every directory, at most four lane launches
+ * (whole planes or boxes, u8 or u16 symbols) decode the planned blocks of all items, and the finish -- the window inverse's
+ * two roles and the paste -- runs once per instance class present over all items; an item whose virtual chunk the tile
+ * kernels do not take, or whose inverse is cut into bands, is finished on its own after those, on the same stream.
+ * ALL OR NOTHING.  Validation: items NULL (ALICE_ERR_NULL_ARGUMENT), n_items 0 or above ALICE_RECTS_MAX_ITEMS
+ * (ALICE_ERR_INVALID_DIMENSIONS), a NULL alc -- or, dev call, rgb_out -- in an item (ALICE_ERR_NULL_ARGUMENT), all without a
+ * device; then, item after item, alice_codec_decode_frames' checks in its order and with its codes (a container's header
+ * is checked once), the rectangle's and the pitches' of alice_codec_dev_decode_rect; the dev call then refuses two items
+ * whose outputs conflict (ALICE_ERR_INVALID_DIMENSIONS, the later item of the first such pair in item order).  The first
+ * item that fails decides the code, *bad_item (when not NULL) receives its index and the message starts with
+ * "item <index>: "; a refusal that is no item's leaves *bad_item = 0xFFFFFFFF.  A refused call queues nothing and writes
+ * nothing.
+ * DISJOINT OUTPUTS.  An item's enclosing byte range is [rgb_out, rgb_out + (count - 1) frame_pitch + (h - 1) row_pitch +
+ * 3 w) with its effective pitches.  Two items conflict when these ranges intersect -- unless both have the same effective
+ * row_pitch and frame_pitch and are disjoint boxes of that surface: with off the distance of an item's base from the lower
+ * of the two bases, t = off / frame_pitch, y = (off % frame_pitch) / row_pitch, x_byte = (off % frame_pitch) % row_pitch,
+ * each item stays a box (x_byte + 3 w <= row_pitch, (y + h) row_pitch <= frame_pitch) and the boxes [t, t + count) x [y,
+ * y + h) x [x_byte, x_byte + 3 w) are apart on at least one axis.  This is exact for items pasted into a common surface
+ * (a mosaic, whose ranges interleave) and conservative elsewhere: interleaved ranges with different pitches, or a row that
+ * wraps past row_pitch, are refused although their bytes may be disjoint.
+ * INTEGRITY: the end checks of all items are read in one copy before anything that writes an output is queued; a directory
+ * that does not add up or a failed lane in a planned block of any item is ALICE_ERR_INVALID_BITSTREAM for the whole call
+ * with *bad_item the first such item, and no output is written, the clean items' included.  Damage in a block no item plans
+ * is not seen.  Memory comes from the library's pool (every item's volumes are sub-ranges of pooled buffers; a failed
+ * allocation is ALICE_ERR_OUT_OF_MEMORY before any output is written); nothing goes through the chain hub. */
+typedef struct alice_codec_rect_item {
+    const void *alc;       /* the container: device memory for the dev call, host memory for the host call */
+    uint64_t    len;
+    uint32_t    first, count;              /* frames [first, first + count) */
+    uint32_t    x, y, w, h;                /* x = y = w = h = 0: the whole frame (a frame range) */
+    void       *rgb_out;                   /* dev call: the rectangle's first byte; host call: ignored */
+    uint64_t    row_pitch, frame_pitch;    /* dev call: as alice_codec_dev_decode_rect's, 0, 0 = packed; host call: ignored */
+} alice_codec_rect_item;                   /* 64 bytes */
+
+#define ALICE_RECTS_MAX_ITEMS 1024u
+
+/* Containers on the device (any byte alignment), outputs on the device (any byte alignment, disjoint by the rule above, not
+ * overlapping a container).  The stream is drained at most three times: after the header fetches of all distinct
+ * containers, at the verdict, and at the end.  Finished on return. */
+int alice_codec_dev_decode_rects(const alice_codec_rect_item *items, uint32_t n_items, uint32_t *bad_item, void *hip_stream);
+/* Containers in host memory (they may be mapped files) -> one buffer (free with alice_codec_data_free64(ptr,
+ * offsets[n_items])), NULL on error; item i is count * h * w * 3 packed bytes at [offsets[i], offsets[i + 1]), in item
+ * order.  Per distinct container the 1630-byte header, the three block-length tables and the byte runs of the union of its
+ * items' planned blocks go up, once.  offsets (n_items + 1 entries) is left alone on a refusal. */
+uint8_t *alice_codec_decode_rects(const alice_codec_rect_item *items, uint32_t n_items, uint64_t *offsets, uint32_t *bad_item);
+
 #ifdef __cplusplus
 }
 #endif

@@ -831,6 +831,34 @@ inline void rect_decode_device(const void* d_alc, uint64_t length, uint32_t firs
                                               hip_stream));
 }
 
+// ---- many frame ranges and rectangles in one call ----
+// All or nothing: the CodecError of a refused or damaged call starts with "item <index>: " when an item decided it.
+// host call: one item; rect {0, 0, 0, 0} is the whole frame (a frame range)
+struct RectRequest { const uint8_t* data; uint64_t len; uint32_t first, count; Rect rect; };
+inline std::vector<std::vector<uint8_t>> decode_rects(const std::vector<RectRequest>& requests) {
+    std::vector<alice_codec_rect_item> items(requests.size());
+    for (size_t i = 0; i < requests.size(); ++i) {
+        const RectRequest& r = requests[i];
+        items[i] = alice_codec_rect_item{r.data, r.len, r.first, r.count, r.rect.x, r.rect.y, r.rect.w, r.rect.h, nullptr, 0, 0};
+    }
+    std::vector<uint64_t> offsets(requests.size() + 1, 0);
+    static const alice_codec_rect_item none{};   // (an empty vector has no data(): the count is what the library refuses)
+    uint8_t* p = alice_codec_decode_rects(items.empty() ? &none : items.data(), (uint32_t)std::min<size_t>(items.size(), 0xFFFFFFFFu),
+                                          offsets.data(), nullptr);
+    if (!p) detail::raise(ALICE_ERR_INVALID_BITSTREAM);
+    std::vector<std::vector<uint8_t>> out(requests.size());
+    for (size_t i = 0; i < requests.size(); ++i) out[i].assign(p + offsets[i], p + offsets[i + 1]);
+    alice_codec_data_free64(p, offsets.back());
+    return out;
+}
+// device call: containers and outputs on the device, the items as the C ABI declares them (outputs disjoint: byte ranges
+// apart, or boxes of one pitched surface that are); *bad_item as there
+inline void rects_decode_device(const std::vector<alice_codec_rect_item>& items, void* hip_stream = nullptr, uint32_t* bad_item = nullptr) {
+    static const alice_codec_rect_item none{};
+    detail::check(alice_codec_dev_decode_rects(items.empty() ? &none : items.data(), (uint32_t)std::min<size_t>(items.size(), 0xFFFFFFFFu),
+                                               bad_item, hip_stream));
+}
+
 // version 2 rate control: the bracket of encode_split's length at the 101 qualities (every version 2 table
 // is bounded: status stays ALICE_RATE_BOUNDED) and one encode at the quality the budget rule picks -- the largest whose
 // upper bound fits, refined by at most ALICE_SPLIT_REFINE_TRIALS exact size counts among the straddling qualities

@@ -182,6 +182,20 @@ void alice_codec_test_last_previews_stats(uint64_t out[9]);
  * (3 (tb - ta) (yb - ya) (xb - xa))}. */
 void alice_codec_test_last_rect_stats(uint64_t out[10]);
 
+/* The last alice_codec_decode_rects / alice_codec_dev_decode_rects of the calling thread that ran to its end (a refused call
+ * leaves it alone; the single calls and the previews never touch it, nor it their hooks): out = {items, distinct
+ * containers, table launches, lane launches, batched finish launches (temporal, tile and paste work lists), items finished
+ * through the per-item path, stream drains, blocks decoded over all items and channels, payload bytes the host call
+ * uploaded (the union of the planned blocks per distinct container; 0 for the device call), symbols stored over all items
+ * and channels, frames written over all items}. */
+void alice_codec_test_last_rects_stats(uint64_t out[11]);
+
+/* The disjointness rule of alice_codec_dev_decode_rects alone, on items with explicit w, h and count (alc, len, first, x, y
+ * are not looked at; rgb_out is only compared); no device needed.  0: no two outputs conflict.  ALICE_ERR_INVALID_DIMENSIONS
+ * with *bad_item the later item of the first conflicting pair; an item without w, h or count, or with bad pitches, is
+ * refused with its index too. */
+int alice_codec_test_rects_outputs_disjoint(const alice_codec_rect_item *items, uint32_t n_items, uint32_t *bad_item);
+
 #ifdef __cplusplus
 }
 #endif
