@@ -1,16 +1,22 @@
 #!/usr/bin/env python3
-"""Generates rans_decode_tile.inc and rans_decode_tile_vec.inc: the inline-asm bodies of the rANS decode fast tile (gfx950).
+"""Generates rans_decode_tile.inc, rans_decode_tile_vec.inc and rans_decode_tile_sh.inc: the inline-asm bodies of the rANS
+decode fast tile (gfx950).
 
-    python gen_rans_decode_asm.py        writes ../rans_decode_tile.inc (classic and dry tile) and ../rans_decode_tile_vec.inc
+    python gen_rans_decode_asm.py        writes ../rans_decode_tile.inc (classic and dry tile), ../rans_decode_tile_vec.inc
+                                         and ../rans_decode_tile_sh.inc
 
-fast_tile(), vector_tile() and dry_tile() return the instruction lists, so the programs can be checked without a GPU
-(tests/test_decode_tile_model.py and tests/test_decode_tile_vec_model.py interpret them); main() writes the files.
-The vector tile (state update on the vector side, ten slots per symbol) is described where it is defined, below render().
+fast_tile(), vector_tile(), shadow_tile() and dry_tile() return the instruction lists, so the programs can be checked without
+a GPU (tests/test_decode_tile_model.py, tests/test_decode_tile_vec_model.py and tests/test_decode_tile_shadow_model.py
+interpret them); main() writes the files.
+The vector tile (state update on the vector side, ten slots per symbol) is described where it is defined, below render();
+the shadow tile (the kernel's default: the record in the stall behind the lane read, both window shifts in wait-state slots,
+22 paid slots per symbol pair, the refill branch inside the stall) below the vector tile.
 
 Costs measured on MI355X with scripts/probes/latency_probe.hip (one wave alone on its SIMD):
   any SALU or VALU instruction ~4 cycles; the first SALU instruction after a VALU instruction that wrote
   an SGPR (v_readlane) stalls ~20 cycles whatever it reads, while further VALU instructions do not;
-  an untaken branch ~10 cycles, a taken one ~25.
+  an untaken branch ~10 cycles, a taken one ~25 -- but an untaken branch directly behind a v_readlane (and the VALU
+  instructions that follow it) overlaps the stall and costs next to nothing (profiles/r25_decode_shadow_probe.json).
 Hence: exactly one VALU->SALU crossing per symbol (both table readlanes back to back, the record
 v_writelane right behind them, inside the stall), no branch in the per-symbol code (renormalisation shift from an SGPR table
 indexed by the leading-zero count), and the window refill test once per two symbols with the refill
@@ -27,6 +33,8 @@ pair: 32 <= V <= 63, so the upper dword s63 is all stream.  A pair consumes at m
 state at 2^27 or above, and the next symbol's state is then at least 2^15: 8 bits at the most), so V never drops below 8
 inside the tile; the sequences are nevertheless right down to V = 0.  After the pair's shifts the sentinel has moved into s63 exactly
 when V <= 31, which is when 32 more bits fit: the refill test is "s62 == 0".
+In the shadow tile the odd symbol's shift is applied, and the test made, in the NEXT pair's even symbol, in front of that
+pair's copy of s63; the invariant 32 <= V <= 63 holds where the copy is taken, which is the only place that relies on it.
 The refill.  The window dwords sit in v[192:224] with their top bit flipped (one v_xor per row at tile load), and
 s64 = 0x80000000 for the whole tile.  With q = ff1(s63) the sentinel's bit in s63 (V = 31 - q):
     s[62:63] ^= {s64 : flipped dword} >> V
@@ -39,9 +47,11 @@ Register plan (all literal, all listed as clobbers by the including statement):
   v[192:224]  stream window, big-endian dwords, top bit flipped (dword d in row d >> 6, lane d & 63)
   v225        record: pre-update state of the 64 symbols of the current block
   s[60:61]    {window copy : x} shift pair      s[62:63] 64-bit big-endian byte window with its sentinel
+  s[56:57]    shadow tile only: the odd symbols' {window copy : x} shift pair (even symbols read x' into s57, odd into s61)
   s[64:65]    refill pair {0x80000000 : new dword}      s[66:67] refill scratch pair (s67 is F' inside a symbol)
   s67 F'   s69 B'   s70 product   s71 shift   s73 next window dword
   s74 blocks left   s75 byte-swap selector   s76 row   s77 shift of the odd symbol   s78 scratch
+              (shadow tile: s77 stays pending until hole 1 of the next pair's even symbol, or the tile exit; 0 on entry)
   s79..s99    renormalisation shift (0, 8 or 16) by count-leading-zeros of the state (0 .. 20: the updated state is at
               least 2^11).  Not s100 and up: the compiler keeps those for itself and ignores them in a clobber list.
   s59         M0 of the surrounding code.  M0 is written by every s_set_gpr_idx_on (the row) and by s_flbit (the index of
@@ -114,7 +124,8 @@ def refill():
             "s_xor_b64 s[62:63], s[62:63], s[66:67]"]
 
 
-def fast_tile(loop_phase=LOOP_PHASE, symbol=lookup_update):
+def tile_entry():
+    """Tables and window rows into VGPRs, the shift table, the scalar state and the primed window (shared by all fast tiles)."""
     L = table_loads()
     for r in range(WIN_ROWS):
         L.append(f"ds_read_b32 v{192 + r}, %[wa] offset:{256 * r}")
@@ -147,6 +158,23 @@ def fast_tile(loop_phase=LOOP_PHASE, symbol=lookup_update):
           "s_cbranch_scc0 6f"]
     L += refill()
     L.append("6:")
+    return L
+
+
+def tile_exit():
+    """The position from the window's fill level and the dwords taken, the state, M0 back."""
+    return ["s_ff1_i32_b64 s71, s[62:63]",                # 63 - V
+            "s_sub_u32 s71, 63, s71",
+            "s_lshr_b32 s71, s71, 3",                     # bytes read ahead of the decoder's position
+            "s_lshl_b32 s70, s73, 2",
+            "s_sub_u32 %[po], s70, s71",
+            "s_mov_b32 %[xo], s61",
+            "s_waitcnt lgkmcnt(0)",
+            f"s_mov_b32 m0, {M0_SAVE}"]
+
+
+def fast_tile(loop_phase=LOOP_PHASE, symbol=lookup_update):
+    L = tile_entry()
     L += loop_pin(loop_phase)
     # Symbols go in pairs.  At the start of a pair the window holds at least 32 valid bits, so its upper dword s63 is all
     # stream.  s60 takes a copy of it ONCE per pair: the even symbol's shift of {s60:s61} feeds the state and leaves
@@ -173,15 +201,8 @@ def fast_tile(loop_phase=LOOP_PHASE, symbol=lookup_update):
         L.append(f"3{lane:02d}:")
         L += refill()
         L.append(f"s_branch 4{lane:02d}b")
-    L += ["5:",
-          "s_ff1_i32_b64 s71, s[62:63]",                # 63 - V
-          "s_sub_u32 s71, 63, s71",
-          "s_lshr_b32 s71, s71, 3",                     # bytes read ahead of the decoder's position
-          "s_lshl_b32 s70, s73, 2",
-          "s_sub_u32 %[po], s70, s71",
-          "s_mov_b32 %[xo], s61",
-          "s_waitcnt lgkmcnt(0)",
-          f"s_mov_b32 m0, {M0_SAVE}"]
+    L.append("5:")
+    L += tile_exit()
     return L
 
 
@@ -268,6 +289,87 @@ def render_vector(loop_phase=LOOP_PHASE):
             "#define ALICE_DEC_TILE_VEC_CLOBBERS " + ", ".join(f'"{c}"' for c in vector_clobbers()) + "\n")
 
 
+# ---- the shadow tile: the record in the stall shadow, the pair tail in the wait-state holes ------------------------------
+# The vector symbol pays for its record: the v_writelane stands in front of the v_readlane because the lane read overwrites
+# s61.  Here the state alternates between two shift pairs -- even symbols have x in s61 (pair s[60:61]) and read x' into s57,
+# odd symbols have x in s57 (pair s[56:57]) and read x' into s61 -- so the record follows the lane read and rides in the
+# VALU -> SALU stall, as the classic tile's does.  The wait state between the v_add and the v_readlane of its result then
+# becomes a free hole in every symbol, next to the M0 hole between s_flbit and s_movrels: four holes per pair, which carry
+# the pair's copy, the hand-over of the shifted copy to the other pair, and BOTH window shifts.  Of the pair tail only the
+# sentinel compare and the branch remain; the compare stands in front of the lane read (SCC survives VALU instructions) and
+# the branch directly behind lane read and record:
+#     even  s_bfe / s_set_gpr_idx_on 0x6 / v_mul_hi / v_add / s_lshl_b64 window, s77 (hole 1: the PREVIOUS pair's odd shift) /
+#           s_cmp_eq_u32 s62, 0 / v_readlane s57 / v_writelane (record) / s_cbranch_scc1 refill / s_flbit m0, s57 /
+#           s_mov_b32 s56, s63 (hole 2: the copy) / s_movrels s71 / s_lshl_b64 s[56:57], s71
+#     odd   s_bfe / s_set_gpr_idx_on 0x6 / v_mul_hi / v_add / s_lshl_b64 window, s71 (hole 1: the even symbol's shift) /
+#           v_readlane s61 / v_writelane (record) / s_flbit m0, s61 / s_mov_b32 s60, s56 (hole 2: the shifted copy changes
+#           pairs) / s_movrels s77 / s_lshl_b64 s[60:61], s77
+# Slot budget: 13 + 11 instructions per pair of which the two records ride in the stall: 22 paid slots per pair, 11 per
+# symbol (the vector tile: 10 per symbol + 3 per pair = 11.5).  The untaken branch behind the lane read overlaps the stall
+# too.  Lone wave: 125.0 cycles per pair against 144.5 (136.0 with compare and branch together in front of the lane read).
+# Measured at 1011 chains (profiles/r25_decode_shadow_ab.json): 31.25 ns per symbol instead of 36.93 / 36.95, rans_decode
+# 4146.5 / 4147.6 ms per step instead of 4899.6 / 4903.3; loop phase 0 mod 8: 4173.3 ms.
+# The window invariant is the sentinel window's, at a new place: when the copy is taken (hole 2 of the even symbol) all
+# shifts of the symbols before it have been applied -- the last of them in hole 1 of this very symbol -- the test "s62 == 0"
+# has seen that window, and the refill, if taken, has run: 32 <= V <= 63 at the copy.  What moves is where the odd symbol's
+# shift is applied: s77 stays pending from the end of a pair to hole 1 of the next pair's even symbol, across the block end
+# (nothing there reads the window) and, after the last pair, to the tile exit, which applies it before it derives the
+# position.  s77 is therefore 0 on tile entry.  The refill is refill() as it is; it now runs between the lane read and the
+# s_flbit, leaves M0 to the s_flbit as before, and neither s56 nor s57 is among its registers (s65 .. s67, s73, s76, s78).
+# Register plan: the vector tile's plus s[56:57], the odd symbols' {window copy : x} shift pair.
+def shadow_symbol(lane):
+    x, xn, owed, sh = ("s61", "s57", "s77", "s71") if not lane & 1 else ("s57", "s61", "s71", "s77")
+    L = [f"s_bfe_u32 s76, {x}, 0x60006",
+         "s_set_gpr_idx_on s76, 0x6",
+         f"v_mul_hi_u32 v{VT}, {x}, v64",
+         f"v_add_u32_e64 v{VT}, v{VT}, v128",
+         f"s_lshl_b64 s[62:63], s[62:63], {owed}"]         # hole 1: the shift the symbol before this one chose
+    if not lane & 1:
+        L.append("s_cmp_eq_u32 s62, 0")                    # the sentinel has left the lower dword <=> V <= 31
+    L += [f"v_readlane_b32 {xn}, v{VT}, {x}",
+          f"v_writelane_b32 v{REC}, {x}, {lane}"]          # x is still there: the record rides in the stall
+    if not lane & 1:
+        L += [f"s_cbranch_scc1 3{lane:02d}f",
+              f"4{lane:02d}:"]
+    pair = "s[56:57]" if not lane & 1 else "s[60:61]"
+    L += [f"s_flbit_i32_b32 m0, {xn}",
+          "s_mov_b32 s56, s63" if not lane & 1 else "s_mov_b32 s60, s56",   # hole 2
+          f"s_movrels_b32 {sh}, s79",
+          f"s_lshl_b64 {pair}, {pair}, {sh}"]
+    return L
+
+
+def shadow_tile(loop_phase=LOOP_PHASE):
+    L = tile_entry()
+    L.append("s_mov_b32 s77, 0")                           # no shift is pending
+    L += loop_pin(loop_phase)
+    for lane in range(64):
+        L += shadow_symbol(lane)
+    L += block_end()
+    L.append("s_branch 5f")
+    for lane in range(0, 64, 2):   # out-of-line refills
+        L.append(f"3{lane:02d}:")
+        L += refill()
+        L.append(f"s_branch 4{lane:02d}b")
+    L += ["5:",
+          "s_lshl_b64 s[62:63], s[62:63], s77"]            # the last odd symbol's shift is still pending
+    L += tile_exit()
+    return L
+
+
+def shadow_clobbers():
+    return vector_clobbers() + ["s56", "s57"]
+
+
+def render_shadow(loop_phase=LOOP_PHASE):
+    def macro(name, lines):
+        return f"#define {name} \\\n" + "".join(f'    "{s}\\n\\t" \\\n' for s in lines) + '    ""\n'
+
+    return ("// GENERATED by gen/gen_rans_decode_asm.py -- do not edit.\n" +
+            macro("ALICE_DEC_TILE_SH_ASM", shadow_tile(loop_phase)) +
+            "#define ALICE_DEC_TILE_SH_CLOBBERS " + ", ".join(f'"{c}"' for c in shadow_clobbers()) + "\n")
+
+
 def main():
     here = os.path.dirname(os.path.abspath(__file__))
     out = os.path.join(here, "..", "rans_decode_tile.inc")
@@ -278,6 +380,10 @@ def main():
     with open(out, "w") as f:
         f.write(render_vector())
     print("wrote", out, len(vector_tile()), "asm lines")
+    out = os.path.join(here, "..", "rans_decode_tile_sh.inc")
+    with open(out, "w") as f:
+        f.write(render_shadow())
+    print("wrote", out, len(shadow_tile()), "asm lines")
 
 
 if __name__ == "__main__":

@@ -756,17 +756,28 @@ constexpr int kDecWinLds = kDecWinBytes;
 // The vector tile (rans_decode_tile_vec.inc) evaluates umulhi(F', x) + B' on the vector unit for the whole table row
 // (VGPR-index mode with the rows as src1) and brings the finished state back with ONE v_readlane per symbol: ten issue
 // slots per symbol instead of eleven.  Same tables, same window, same record.
+// The shadow tile (rans_decode_tile_sh.inc) is the vector tile with the state alternating between two SGPR shift pairs, so
+// that the record follows the lane read and rides in the VALU -> SALU stall, with both window shifts in wait-state slots and
+// the refill branch in the same stall: 22 paid slots per symbol pair instead of 23, and the branch for nothing.
 #include "rans_decode_tile.inc"
 #include "rans_decode_tile_vec.inc"
+#include "rans_decode_tile_sh.inc"
+
+enum DecTile : int { kDecTileClassic = 0, kDecTileVector = 1, kDecTileShadow = 2 };
 
 // Decodes nblk*64 symbols on the fast path.  slots = the chain's RansDecSlots (F' at byte 0, B' at byte 16384, read with
 // 128 global loads per lane: lane4 = 4 * lane); win_addr / rec_addr are this lane's LDS byte addresses (base + 4*lane;
 // the record is 2 bytes per lane).  pos = byte offset of the next stream byte inside the window.
-template <bool kVector>
+template <int kTile>
 __device__ __forceinline__ void dec_tile_fast(uint32_t& x, uint32_t& pos, const RansDecSlots* slots, uint32_t lane4,
                                               uint32_t win_addr, uint32_t rec_addr, uint32_t nblk) {
     uint32_t xo, po;
-    if constexpr (kVector)
+    if constexpr (kTile == kDecTileShadow)
+        asm volatile(ALICE_DEC_TILE_SH_ASM
+                     : [xo] "=&s"(xo), [po] "=&s"(po), [ra] "+v"(rec_addr)
+                     : [xi] "s"(x), [pi] "s"(pos), [nb] "s"(nblk), [tp] "s"(slots), [l4] "v"(lane4), [wa] "v"(win_addr)
+                     : ALICE_DEC_TILE_SH_CLOBBERS);
+    else if constexpr (kTile == kDecTileVector)
         asm volatile(ALICE_DEC_TILE_VEC_ASM
                      : [xo] "=&s"(xo), [po] "=&s"(po), [ra] "+v"(rec_addr)
                      : [xi] "s"(x), [pi] "s"(pos), [nb] "s"(nblk), [tp] "s"(slots), [l4] "v"(lane4), [wa] "v"(win_addr)
@@ -795,12 +806,12 @@ __device__ __forceinline__ void dec_tile_dry(uint32_t& x, const RansDecSlots* sl
 // LDS per chain: cum_to_sym 4 KB + exact-loop symbol table 1 KB + stream window 8.25 KB + state record 8 KB
 // (the exact loop's output bytes share the record's space) = 21.3 KB.  The launcher adds dynamic LDS so that at most
 // four (up to 1024 chains: one per SIMD) or seven chains share a CU.
-// kVector: the fast tile is the vector tile; everything around it (window staging, speculation, symbol recovery, the
-// exact loop, the dry tile) is the same code.
-template <bool kExclusive, bool kVector>
+// kTile: which fast tile (classic, vector, shadow); everything around it (window staging, speculation, symbol recovery,
+// the exact loop, the dry tile) is the same code.
+template <bool kExclusive, int kTile>
 __global__ __launch_bounds__(64) void rans_decode_kernel(const RansDecodeDesc* __restrict__ descs,
                                                          RansResult* __restrict__ results, uint32_t take_turns) {
-    if constexpr (kExclusive) asm volatile("" ::: "a63");   // 226 (vector tile: 227) VGPRs + 64 AGPRs > 256: one chain per SIMD
+    if constexpr (kExclusive) asm volatile("" ::: "a63");   // 226 (vector and shadow tile: 227) VGPRs + 64 AGPRs > 256: one chain per SIMD
     __shared__ __attribute__((aligned(16))) uint8_t c2s[kProbScale];                  // cum_to_sym
     __shared__ uint32_t symtab[256];                                                    // freq | cum << 16 (exact loop)
     __shared__ __attribute__((aligned(16))) uint8_t win[kDecWinLds];
@@ -922,8 +933,8 @@ __global__ __launch_bounds__(64) void rans_decode_kernel(const RansDecodeDesc* _
             uint32_t prel = (uint32_t)(pos - wbase);
             uint32_t xs = (uint32_t)__builtin_amdgcn_readfirstlane((int)x);
             prel = (uint32_t)__builtin_amdgcn_readfirstlane((int)prel);
-            dec_tile_fast<kVector>(xs, prel, slots, 4u * lane, (uint32_t)(uintptr_t)win + 4u * lane,
-                                   (uint32_t)(uintptr_t)rec + 2u * lane, (uint32_t)kDecBlocks);
+            dec_tile_fast<kTile>(xs, prel, slots, 4u * lane, (uint32_t)(uintptr_t)win + 4u * lane,
+                                 (uint32_t)(uintptr_t)rec + 2u * lane, (uint32_t)kDecBlocks);
             x = xs;
             pos = wbase + prel;
             pending = false;  // the fast path renormalises right after each update
@@ -1045,10 +1056,23 @@ static uint32_t chain_turns_enabled() {
     return on;
 }
 
-// ALICE_DEC_TILE=classic selects the scalar-side decode tile instead of the vector tile (developer A/B, read once)
-static bool dec_tile_vector() {
-    static const bool vec = [] { const char* v = getenv("ALICE_DEC_TILE"); return !(v && strcmp(v, "classic") == 0); }();
-    return vec;
+// ALICE_DEC_TILE=classic / vector selects an earlier decode tile instead of the shadow tile (developer A/B, read once)
+static int dec_tile_choice() {
+    static const int tile = [] {
+        const char* v = getenv("ALICE_DEC_TILE");
+        if (v && strcmp(v, "classic") == 0) return (int)kDecTileClassic;
+        if (v && strcmp(v, "vector") == 0) return (int)kDecTileVector;
+        return (int)kDecTileShadow;
+    }();
+    return tile;
+}
+using DecKernel = void (*)(const RansDecodeDesc*, RansResult*, uint32_t);
+static DecKernel dec_kernel(bool exclusive) {
+    switch (dec_tile_choice()) {
+        case kDecTileClassic: return exclusive ? rans_decode_kernel<true, kDecTileClassic> : rans_decode_kernel<false, kDecTileClassic>;
+        case kDecTileVector: return exclusive ? rans_decode_kernel<true, kDecTileVector> : rans_decode_kernel<false, kDecTileVector>;
+        default: return exclusive ? rans_decode_kernel<true, kDecTileShadow> : rans_decode_kernel<false, kDecTileShadow>;
+    }
 }
 
 static unsigned chain_lds_pad(int n_chains, unsigned static_lds) {
@@ -1077,11 +1101,9 @@ static const ChainKernelFacts& chain_kernel_facts() {
         };
         unsigned dummy = 0;
         q((const void*)rans_encode_kernel<true>, r.enc_regs, r.enc_lds, &r.enc_wg_per_cu);
-        q(dec_tile_vector() ? (const void*)rans_decode_kernel<true, true> : (const void*)rans_decode_kernel<true, false>, r.dec_regs,
-          r.dec_lds, &r.dec_wg_per_cu);
+        q((const void*)dec_kernel(true), r.dec_regs, r.dec_lds, &r.dec_wg_per_cu);
         q((const void*)rans_encode_kernel<false>, dummy, r.enc_lds_plain, nullptr);
-        q(dec_tile_vector() ? (const void*)rans_decode_kernel<false, true> : (const void*)rans_decode_kernel<false, false>, dummy,
-          r.dec_lds_plain, nullptr);
+        q((const void*)dec_kernel(false), dummy, r.dec_lds_plain, nullptr);
         return r;
     }();
     return f;
@@ -1118,8 +1140,7 @@ void launch_rans_encode_descs(const RansEncodeDesc* d_descs, int n_chains, hipSt
 
 void launch_rans_decode(const RansDecodeDesc* d_descs, RansResult* d_results, int n_chains, hipStream_t st) {
     if (n_chains <= 0) return;
-    auto kern = dec_tile_vector() ? (n_chains <= 1024 ? rans_decode_kernel<true, true> : rans_decode_kernel<false, true>)
-                                  : (n_chains <= 1024 ? rans_decode_kernel<true, false> : rans_decode_kernel<false, false>);
+    auto kern = dec_kernel(n_chains <= 1024);
     const ChainKernelFacts& facts = chain_kernel_facts();
     hipLaunchKernelGGL(kern, dim3(n_chains), dim3(64), chain_lds_pad(n_chains, facts.ok ? facts.dec_lds_plain : 21776u + 256u), st, d_descs, d_results,
                        chain_turns_enabled());

@@ -17,6 +17,7 @@ __global__ __launch_bounds__(64) void NAME(unsigned long long* out, uint32_t see
     "s_mov_b32 s40, %[seed]\n\t s_mov_b32 s41, 0x10001\n\t s_mov_b32 s42, 3\n\t s_mov_b32 s43, 0\n\t" \
     "v_mov_b32 v40, %[seed]\n\t v_mov_b32 v41, 0x10001\n\t v_mov_b32 v42, 3\n\t v_mov_b32 v43, 7\n\t" \
     "s_mov_b32 s44, 0x00800000\n\t s_mov_b32 s46, 0\n\t s_mov_b32 s47, 1\n\t"                 \
+    "s_mov_b32 s48, 1\n\t s_mov_b32 s49, 0\n\t"                                               \
     "s_set_gpr_idx_on s43, 0x1\n\t"                                                           \
     "s_memtime %[t0]\n\t s_waitcnt lgkmcnt(0)\n\t"                                            \
     "s_mov_b32 %[cnt], 256\n\t"                                                               \
@@ -104,6 +105,36 @@ PROBE_KERNEL(k_valu4, VALU4)
 PROBE_KERNEL(k_vmulhi_rel, "s_set_gpr_idx_on s43, 0x6\n\t v_mul_hi_u32 v45, s41, v45\n\t")
 PROBE_KERNEL(k_vmad24_rel, "s_set_gpr_idx_on s43, 0x6\n\t v_mad_u32_u24 v45, s41, v45, v41\n\t")
 
+// The shadow pair (csrc/gen/gen_rans_decode_asm.py: shadow_tile): the lane read writes the OTHER shift pair's state register,
+// so the record's v_writelane can follow it and ride in the VALU -> SALU stall, and the wait state between the v_add and the
+// lane read becomes a hole that carries a window shift.  The states are s41 (pair s[40:41]) and s47 (pair s[46:47]) in turn,
+// the window stands in s[48:49] = {1 : 0} (shifted by s43 = 0, so "s48 == 0" is never true and the branch is never taken),
+// the rest as in the rows above.  Rows, all per copy of the whole snippet:
+//   shadow: (a)    today's vector symbol (the kernel of "dec: A symbol")
+//   shadow: (a2)   today's pair: two vector symbols with their fillers, then the tail (window shift, compare, untaken branch)
+//   shadow: (b)    the shadow pair, compare in front of the lane read and the branch behind lane read and record
+//   shadow: (c)    the shadow pair, compare and branch together in front of the lane read
+//   shadow: (d0/d1)  v_readlane; SALU   against   v_readlane; v_writelane (reading an SGPR); SALU
+//   shadow: (e0/e1/e2)  s_cmp; v_readlane; SALU   against the same with an untaken s_cbranch_scc1 in front of / behind the SALU
+#define SH_HEAD(X) "s_bfe_u32 s45, " X ", 0x60006\n\t s_set_gpr_idx_on s43, 0x6\n\t v_mul_hi_u32 v45, " X ", v40\n\t v_add_u32_e64 v45, v45, v41\n\t"
+#define SH_SHIFT(PAIR, FILL) "s_flbit_i32_b32 m0, s44\n\t" FILL "s_movrels_b32 s45, s42\n\t s_lshl_b64 " PAIR ", " PAIR ", s43\n\t"
+#define SH_WSHIFT "s_lshl_b64 s[48:49], s[48:49], s43\n\t"
+#define VEC_SYM(FILL) SH_HEAD("s41") "v_writelane_b32 v44, s41, 3\n\t v_readlane_b32 s41, v45, s41\n\t" SH_SHIFT("s[40:41]", FILL)
+PROBE_KERNEL(k_sh_pair_today, VEC_SYM("s_mov_b32 s40, s49\n\t") VEC_SYM(SH_WSHIFT)
+                              SH_WSHIFT "s_cmp_eq_u32 s48, 0\n\t s_cbranch_scc1 9f\n\t 9:\n\t")
+#define SH_ODD SH_HEAD("s47") SH_WSHIFT "v_readlane_b32 s41, v45, s47\n\t v_writelane_b32 v44, s47, 3\n\t"       \
+               SH_SHIFT("s[40:41]", "s_mov_b32 s40, s46\n\t")
+PROBE_KERNEL(k_sh_pair_v1, SH_HEAD("s41") SH_WSHIFT "s_cmp_eq_u32 s48, 0\n\t"
+                           "v_readlane_b32 s47, v45, s41\n\t v_writelane_b32 v44, s41, 3\n\t s_cbranch_scc1 9f\n\t 9:\n\t"
+                           SH_SHIFT("s[46:47]", "s_mov_b32 s46, s49\n\t") SH_ODD)
+PROBE_KERNEL(k_sh_pair_v2, SH_HEAD("s41") SH_WSHIFT "s_cmp_eq_u32 s48, 0\n\t s_cbranch_scc1 9f\n\t 9:\n\t"
+                           "v_readlane_b32 s47, v45, s41\n\t v_writelane_b32 v44, s41, 3\n\t"
+                           SH_SHIFT("s[46:47]", "s_mov_b32 s46, s49\n\t") SH_ODD)
+PROBE_KERNEL(k_sh_record, "v_readlane_b32 s45, v40, s42\n\t v_writelane_b32 v44, s40, 5\n\t s_add_u32 s40, s45, s40\n\t")
+PROBE_KERNEL(k_sh_cmp_salu, "s_cmp_eq_u32 s48, 0\n\t v_readlane_b32 s45, v40, s42\n\t s_flbit_i32_b32 s46, s45\n\t")
+PROBE_KERNEL(k_sh_branch_salu, "s_cmp_eq_u32 s48, 0\n\t v_readlane_b32 s45, v40, s42\n\t s_cbranch_scc1 9f\n\t 9:\n\t s_flbit_i32_b32 s46, s45\n\t")
+PROBE_KERNEL(k_sh_salu_branch, "s_cmp_eq_u32 s48, 0\n\t v_readlane_b32 s45, v40, s42\n\t s_flbit_i32_b32 s46, s45\n\t s_cbranch_scc1 9f\n\t 9:\n\t")
+
 // What the seventh slot of the complement step (its closing s_nop 1: the two wait states between the VALU write of z
 // and the DPP read) can carry for nothing.  The same six chain instructions as k_enc_comp7, then the filler.  These
 // kernels own LDS (the ds_read's target; v50 = 16 * lane) and take a byte buffer (the store's target: out + 256 + lane,
@@ -184,10 +215,20 @@ int main(int argc, char** argv) {
     {"dec: v_readlane; SALU", k_cross_0}, {"dec: v_readlane; 4 x VALU; SALU", k_cross_4valu},
     {"dec: v_readlane; 3 x VALU; v_readlane; SALU", k_cross_3valu_readlane}, {"dec: 4 x VALU", k_valu4},
     {"dec: s_set_gpr_idx_on 0x6; v_mul_hi_u32 s, v(rel)", k_vmulhi_rel},
-    {"dec: s_set_gpr_idx_on 0x6; v_mad_u32_u24 s, v(rel), v(rel)", k_vmad24_rel}};
+    {"dec: s_set_gpr_idx_on 0x6; v_mad_u32_u24 s, v(rel), v(rel)", k_vmad24_rel},
+    {"shadow: (a) vector symbol today (10 slots)", k_dec_vec_a},
+    {"shadow: (a2) vector pair today with its tail (23 slots)", k_sh_pair_today},
+    {"shadow: (b) shadow pair, branch behind lane read and record", k_sh_pair_v1},
+    {"shadow: (c) shadow pair, compare and branch in front of the lane read", k_sh_pair_v2},
+    {"shadow: (d0) v_readlane; SALU", k_cross_0}, {"shadow: (d1) v_readlane; v_writelane of an SGPR; SALU", k_sh_record},
+    {"shadow: (e0) s_cmp; v_readlane; SALU", k_sh_cmp_salu},
+    {"shadow: (e1) s_cmp; v_readlane; untaken s_cbranch_scc1; SALU", k_sh_branch_salu},
+    {"shadow: (e2) s_cmp; v_readlane; SALU; untaken s_cbranch_scc1", k_sh_salu_branch}};
   double base = 0;
   FILE* js = argc > 1 ? fopen(argv[1], "w") : nullptr;   // the "comp step + ..." rows as JSON (cycles per step)
   FILE* jd = argc > 2 ? fopen(argv[2], "w") : nullptr;   // the "dec: ..." rows as JSON (cycles per copy)
+  FILE* jh = argc > 3 ? fopen(argv[3], "w") : nullptr;   // the "shadow: ..." rows as JSON (cycles per copy)
+  if (jh) fprintf(jh, "{\n  \"what\": \"scripts/probes/latency_probe.hip: the shadow pair of the decode tile (record behind the lane read, window shifts in the wait-state holes) against today's vector pair, one wave alone; shader cycles per copy of the row's snippet, best of 5 launches, empty loop subtracted\"");
   if (jd) fprintf(jd, "{\n  \"what\": \"scripts/probes/latency_probe.hip: the decode symbol with the state update on the vector side, one wave alone; shader cycles per copy of the row's snippet, best of 5 launches, empty loop subtracted\"");
   if (js) fprintf(js, "{\n  \"what\": \"scripts/probes/latency_probe.hip: the 7-slot complement step on one wave alone, its closing s_nop 1 replaced by fillers; shader cycles per step, best of 5 launches, empty loop subtracted\"");
   for (auto& t : tests) {
@@ -204,7 +245,10 @@ int main(int argc, char** argv) {
       fprintf(js, ",\n  \"%s\": %.2f", t.name, ((double)best - base) / (256.0 * 32.0));
     if (jd && std::string(t.name).rfind("dec: ", 0) == 0)
       fprintf(jd, ",\n  \"%s\": %.2f", t.name + 5, ((double)best - base) / (256.0 * 32.0));
+    if (jh && std::string(t.name).rfind("shadow: ", 0) == 0)
+      fprintf(jh, ",\n  \"%s\": %.2f", t.name + 8, ((double)best - base) / (256.0 * 32.0));
   }
+  if (jh) { fprintf(jh, "\n}\n"); fclose(jh); }
   if (js) { fprintf(js, "\n}\n"); fclose(js); }
   if (jd) { fprintf(jd, "\n}\n"); fclose(jd); }
   return 0;
