@@ -1,16 +1,19 @@
 #!/usr/bin/env python3
-"""Generates rans_decode_tile.inc, rans_decode_tile_vec.inc and rans_decode_tile_sh.inc: the inline-asm bodies of the rANS
-decode fast tile (gfx950).
+"""Generates rans_decode_tile.inc, rans_decode_tile_vec.inc, rans_decode_tile_sh.inc and rans_decode_tile_ih.inc: the
+inline-asm bodies of the rANS decode fast tile (gfx950).
 
-    python gen_rans_decode_asm.py        writes ../rans_decode_tile.inc (classic and dry tile), ../rans_decode_tile_vec.inc
-                                         and ../rans_decode_tile_sh.inc
+    python gen_rans_decode_asm.py        writes ../rans_decode_tile.inc (classic and dry tile), ../rans_decode_tile_vec.inc,
+                                         ../rans_decode_tile_sh.inc and ../rans_decode_tile_ih.inc
 
-fast_tile(), vector_tile(), shadow_tile() and dry_tile() return the instruction lists, so the programs can be checked without
-a GPU (tests/test_decode_tile_model.py, tests/test_decode_tile_vec_model.py and tests/test_decode_tile_shadow_model.py
-interpret them); main() writes the files.
+fast_tile(), vector_tile(), shadow_tile(), inhand_tile() and dry_tile() return the instruction lists, so the programs can be
+checked without a GPU (tests/test_decode_tile_model.py, tests/test_decode_tile_vec_model.py,
+tests/test_decode_tile_shadow_model.py and tests/test_decode_tile_inhand_model.py interpret them); main() writes the files.
 The vector tile (state update on the vector side, ten slots per symbol) is described where it is defined, below render();
-the shadow tile (the kernel's default: the record in the stall behind the lane read, both window shifts in wait-state slots,
-22 paid slots per symbol pair, the refill branch inside the stall) below the vector tile.
+the shadow tile (the record in the stall behind the lane read, both window shifts in wait-state slots, 22 paid slots per
+symbol pair, the refill branch inside the stall) below the vector tile; the in-hand tile (the shadow tile's main line; the next
+window dword always in s65, so the refill is five scalar instructions, and its out-of-line path runs on to the odd symbol's
+lane read, where the dword after it is read in the same stall) below the shadow tile.  Which of them is the kernel's default:
+dec_tile_choice() in rans.hip.
 
 Costs measured on MI355X with scripts/probes/latency_probe.hip (one wave alone on its SIMD):
   any SALU or VALU instruction ~4 cycles; the first SALU instruction after a VALU instruction that wrote
@@ -48,7 +51,11 @@ Register plan (all literal, all listed as clobbers by the including statement):
   v225        record: pre-update state of the 64 symbols of the current block
   s[60:61]    {window copy : x} shift pair      s[62:63] 64-bit big-endian byte window with its sentinel
   s[56:57]    shadow tile only: the odd symbols' {window copy : x} shift pair (even symbols read x' into s57, odd into s61)
+  v226        vector, shadow and in-hand tile: the updated state of every slot of the current table row
+  v227        in-hand tile only: staging row, the 64 window dwords from s73 on (lane d & 63 <- dword d)
+  s[54:55]    in-hand tile only: EXEC of the surrounding code (the staging narrows EXEC for one v_mov)
   s[64:65]    refill pair {0x80000000 : new dword}      s[66:67] refill scratch pair (s67 is F' inside a symbol)
+              (in-hand tile: s65 is ALWAYS the dword with index s73, top bit flipped)
   s67 F'   s69 B'   s70 product   s71 shift   s73 next window dword
   s74 blocks left   s75 byte-swap selector   s76 row   s77 shift of the odd symbol   s78 scratch
               (shadow tile: s77 stays pending until hole 1 of the next pair's even symbol, or the tile exit; 0 on entry)
@@ -370,6 +377,105 @@ def render_shadow(loop_phase=LOOP_PHASE):
             "#define ALICE_DEC_TILE_SH_CLOBBERS " + ", ".join(f'"{c}"' for c in shadow_clobbers()) + "\n")
 
 
+# ---- the in-hand tile: the refill takes a dword that is already in an SGPR -----------------------------------------------
+# The shadow tile's refill switches the index mode and reads the window dword with a lane read of its own: a second
+# VALU -> SALU crossing, then the taken branch back.  Here s65 ALWAYS holds the window dword with index s73 (the next one
+# that is not yet in the window, top bit flipped), so the refill is SALU work on registers that are already there:
+#     s_ff1_i32_b32 s78, s63 / s_sub_u32 s78, 31, s78 / s_lshr_b64 s[66:67], s[64:65], s78 /
+#     s_xor_b64 s[62:63], s[62:63], s[66:67] / s_add_u32 s73, s73, 1
+# The dword after it is fetched by a v_readlane that stands directly behind the ODD symbol's own lane read, so both pay one
+# crossing.  That read must not switch the index mode (the odd symbol's multiply-add needs 0x6 and src0 is not relative in
+# 0x6), so it reads a staging row v227 that holds the 64 window dwords from s73 on, lane d & 63 <- dword d (the hardware masks
+# the lane select to 6 bits).  v227 is rebuilt in tile_entry() and at every block end from rows s73 >> 6 (all lanes) and
+# (s73 >> 6) + 1 (the lanes below s73 & 63, through EXEC); a block consumes at most 24 dwords and reads one ahead, well inside
+# the 64.  Row 33 is the record row: those lanes stand for dwords behind the 33-row window, which no tile reaches.
+# The out-of-line path of an even symbol does not return at once: behind the refill it carries the even symbol's tail and the
+# odd symbol's head, copied from the main line, up to the odd symbol's lane read, the prefetch and the record, and only then
+# branches back, to the odd symbol's s_flbit (label 6xx):
+#     3xx: refill (5) / s_flbit m0, s57 / s_mov_b32 s56, s63 / s_movrels s71 / s_lshl_b64 s[56:57], s71 /
+#          s_bfe / s_set_gpr_idx_on 0x6 / v_mul_hi / v_add / s_lshl_b64 window, s71 /
+#          v_readlane s61 / v_readlane s65, v227, s73 / v_writelane (record) / s_branch 6xx
+# The main line is the shadow tile's, instruction for instruction; only the label 6xx in the odd symbol is new.  Two refills in
+# consecutive pairs work: the next even symbol tests the refilled window, and s65 is the next dword by then.
+# Register plan: the shadow tile's plus v227 (staging row) and s[54:55] (EXEC of the surrounding code).
+VW = VT + 1     # staging row: the 64 window dwords from s73 on
+EXEC_SAVE = "s[54:55]"
+
+
+def stage():
+    """v227[d & 63] = window dword d for s73 <= d < s73 + 64.  Leaves index mode 0x1 on and EXEC as it was."""
+    return ["s_lshr_b32 s76, s73, 6",
+            "s_set_gpr_idx_on s76, 0x1",
+            f"v_mov_b32_e32 v{VW}, v192",                  # src0 relative: row s73 >> 6
+            "s_bfm_b64 exec, s73, 0",                      # the lanes below s73 & 63 (the width is S0[5:0])
+            f"v_mov_b32_e32 v{VW}, v193",                  # ... take the row after it
+            f"s_mov_b64 exec, {EXEC_SAVE}"]
+
+
+def inhand_refill():
+    """refill() without its lane read: the dword is in s65.  Needs s64 = 0x80000000; the caller reads the next s65."""
+    return ["s_ff1_i32_b32 s78, s63",                      # the sentinel's bit in s63: 31 - V
+            "s_sub_u32 s78, 31, s78",                      # V
+            "s_lshr_b64 s[66:67], s[64:65], s78",
+            "s_xor_b64 s[62:63], s[62:63], s[66:67]",
+            "s_add_u32 s73, s73, 1"]
+
+
+def inhand_entry():
+    L = tile_entry()
+    at = L.index(f"s_mov_b32 {M0_SAVE}, m0")
+    L.insert(at + 1, f"s_mov_b64 {EXEC_SAVE}, exec")
+    L += ["s_lshr_b32 s76, s73, 6",                        # prime s65: the dword with index s73
+          "s_set_gpr_idx_on s76, 0x1",
+          "s_nop 1",
+          "v_readlane_b32 s65, v192, s73"]
+    L += stage()
+    L.append("s_mov_b32 s77, 0")                           # no shift is pending
+    return L
+
+
+def inhand_path(lane):
+    """The out-of-line path of the even symbol `lane`: refill, the rest of the pair up to the odd symbol's record."""
+    even, odd = shadow_symbol(lane), shadow_symbol(lane + 1)
+    rd = odd.index(f"v_readlane_b32 s61, v{VT}, s57")
+    return ([f"3{lane:02d}:"] + inhand_refill() + even[even.index(f"4{lane:02d}:") + 1:] + odd[:rd + 1] +
+            [f"v_readlane_b32 s65, v{VW}, s73",            # shares the odd symbol's crossing; src0 is not relative in 0x6
+             odd[rd + 1],                                  # the record
+             f"s_branch 6{lane:02d}b"])
+
+
+def inhand_tile(loop_phase=LOOP_PHASE):
+    L = inhand_entry()
+    L += loop_pin(loop_phase)
+    for lane in range(64):
+        body = shadow_symbol(lane)
+        if lane & 1:
+            body.insert(body.index("s_flbit_i32_b32 m0, s61"), f"6{lane - 1:02d}:")
+        L += body
+    L += stage()
+    L += block_end()
+    L.append("s_branch 5f")
+    for lane in range(0, 64, 2):
+        L += inhand_path(lane)
+    L += ["5:",
+          "s_lshl_b64 s[62:63], s[62:63], s77"]            # the last odd symbol's shift is still pending
+    L += tile_exit()
+    return L
+
+
+def inhand_clobbers():
+    return shadow_clobbers() + ["s54", "s55", f"v{VW}"]
+
+
+def render_inhand(loop_phase=LOOP_PHASE):
+    def macro(name, lines):
+        return f"#define {name} \\\n" + "".join(f'    "{s}\\n\\t" \\\n' for s in lines) + '    ""\n'
+
+    return ("// GENERATED by gen/gen_rans_decode_asm.py -- do not edit.\n" +
+            macro("ALICE_DEC_TILE_IH_ASM", inhand_tile(loop_phase)) +
+            "#define ALICE_DEC_TILE_IH_CLOBBERS " + ", ".join(f'"{c}"' for c in inhand_clobbers()) + "\n")
+
+
 def main():
     here = os.path.dirname(os.path.abspath(__file__))
     out = os.path.join(here, "..", "rans_decode_tile.inc")
@@ -384,6 +490,10 @@ def main():
     with open(out, "w") as f:
         f.write(render_shadow())
     print("wrote", out, len(shadow_tile()), "asm lines")
+    out = os.path.join(here, "..", "rans_decode_tile_ih.inc")
+    with open(out, "w") as f:
+        f.write(render_inhand())
+    print("wrote", out, len(inhand_tile()), "asm lines")
 
 
 if __name__ == "__main__":

@@ -761,9 +761,13 @@ constexpr int kDecWinLds = kDecWinBytes;
 // the refill branch in the same stall: 22 paid slots per symbol pair instead of 23, and the branch for nothing.
 #include "rans_decode_tile.inc"
 #include "rans_decode_tile_vec.inc"
+// The in-hand tile (rans_decode_tile_ih.inc) is the shadow tile with the next window dword always in an SGPR: the refill is
+// five scalar instructions without a lane read, and its out-of-line path runs on through the pair to the odd symbol's lane
+// read, where the dword after it is read from a staging row in the same stall.
 #include "rans_decode_tile_sh.inc"
+#include "rans_decode_tile_ih.inc"
 
-enum DecTile : int { kDecTileClassic = 0, kDecTileVector = 1, kDecTileShadow = 2 };
+enum DecTile : int { kDecTileClassic = 0, kDecTileVector = 1, kDecTileShadow = 2, kDecTileInhand = 3 };
 
 // Decodes nblk*64 symbols on the fast path.  slots = the chain's RansDecSlots (F' at byte 0, B' at byte 16384, read with
 // 128 global loads per lane: lane4 = 4 * lane); win_addr / rec_addr are this lane's LDS byte addresses (base + 4*lane;
@@ -772,7 +776,12 @@ template <int kTile>
 __device__ __forceinline__ void dec_tile_fast(uint32_t& x, uint32_t& pos, const RansDecSlots* slots, uint32_t lane4,
                                               uint32_t win_addr, uint32_t rec_addr, uint32_t nblk) {
     uint32_t xo, po;
-    if constexpr (kTile == kDecTileShadow)
+    if constexpr (kTile == kDecTileInhand)
+        asm volatile(ALICE_DEC_TILE_IH_ASM
+                     : [xo] "=&s"(xo), [po] "=&s"(po), [ra] "+v"(rec_addr)
+                     : [xi] "s"(x), [pi] "s"(pos), [nb] "s"(nblk), [tp] "s"(slots), [l4] "v"(lane4), [wa] "v"(win_addr)
+                     : ALICE_DEC_TILE_IH_CLOBBERS);
+    else if constexpr (kTile == kDecTileShadow)
         asm volatile(ALICE_DEC_TILE_SH_ASM
                      : [xo] "=&s"(xo), [po] "=&s"(po), [ra] "+v"(rec_addr)
                      : [xi] "s"(x), [pi] "s"(pos), [nb] "s"(nblk), [tp] "s"(slots), [l4] "v"(lane4), [wa] "v"(win_addr)
@@ -806,12 +815,12 @@ __device__ __forceinline__ void dec_tile_dry(uint32_t& x, const RansDecSlots* sl
 // LDS per chain: cum_to_sym 4 KB + exact-loop symbol table 1 KB + stream window 8.25 KB + state record 8 KB
 // (the exact loop's output bytes share the record's space) = 21.3 KB.  The launcher adds dynamic LDS so that at most
 // four (up to 1024 chains: one per SIMD) or seven chains share a CU.
-// kTile: which fast tile (classic, vector, shadow); everything around it (window staging, speculation, symbol recovery,
+// kTile: which fast tile (classic, vector, shadow, in-hand); everything around it (window staging, speculation, symbol recovery,
 // the exact loop, the dry tile) is the same code.
 template <bool kExclusive, int kTile>
 __global__ __launch_bounds__(64) void rans_decode_kernel(const RansDecodeDesc* __restrict__ descs,
                                                          RansResult* __restrict__ results, uint32_t take_turns) {
-    if constexpr (kExclusive) asm volatile("" ::: "a63");   // 226 (vector and shadow tile: 227) VGPRs + 64 AGPRs > 256: one chain per SIMD
+    if constexpr (kExclusive) asm volatile("" ::: "a63");   // 226 (vector and shadow tile: 227, in-hand tile: 228) VGPRs + 64 AGPRs > 256: one chain per SIMD
     __shared__ __attribute__((aligned(16))) uint8_t c2s[kProbScale];                  // cum_to_sym
     __shared__ uint32_t symtab[256];                                                    // freq | cum << 16 (exact loop)
     __shared__ __attribute__((aligned(16))) uint8_t win[kDecWinLds];
@@ -1056,13 +1065,16 @@ static uint32_t chain_turns_enabled() {
     return on;
 }
 
-// ALICE_DEC_TILE=classic / vector selects an earlier decode tile instead of the shadow tile (developer A/B, read once)
+// ALICE_DEC_TILE=classic / vector / shadow selects an earlier decode tile instead of the in-hand tile, inhand names the
+// default (developer A/B, read once)
 static int dec_tile_choice() {
     static const int tile = [] {
         const char* v = getenv("ALICE_DEC_TILE");
         if (v && strcmp(v, "classic") == 0) return (int)kDecTileClassic;
         if (v && strcmp(v, "vector") == 0) return (int)kDecTileVector;
-        return (int)kDecTileShadow;
+        if (v && strcmp(v, "shadow") == 0) return (int)kDecTileShadow;
+        if (v && strcmp(v, "inhand") == 0) return (int)kDecTileInhand;
+        return (int)kDecTileInhand;
     }();
     return tile;
 }
@@ -1071,7 +1083,8 @@ static DecKernel dec_kernel(bool exclusive) {
     switch (dec_tile_choice()) {
         case kDecTileClassic: return exclusive ? rans_decode_kernel<true, kDecTileClassic> : rans_decode_kernel<false, kDecTileClassic>;
         case kDecTileVector: return exclusive ? rans_decode_kernel<true, kDecTileVector> : rans_decode_kernel<false, kDecTileVector>;
-        default: return exclusive ? rans_decode_kernel<true, kDecTileShadow> : rans_decode_kernel<false, kDecTileShadow>;
+        case kDecTileShadow: return exclusive ? rans_decode_kernel<true, kDecTileShadow> : rans_decode_kernel<false, kDecTileShadow>;
+        default: return exclusive ? rans_decode_kernel<true, kDecTileInhand> : rans_decode_kernel<false, kDecTileInhand>;
     }
 }
 

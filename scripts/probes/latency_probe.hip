@@ -135,6 +135,46 @@ PROBE_KERNEL(k_sh_cmp_salu, "s_cmp_eq_u32 s48, 0\n\t v_readlane_b32 s45, v40, s4
 PROBE_KERNEL(k_sh_branch_salu, "s_cmp_eq_u32 s48, 0\n\t v_readlane_b32 s45, v40, s42\n\t s_cbranch_scc1 9f\n\t 9:\n\t s_flbit_i32_b32 s46, s45\n\t")
 PROBE_KERNEL(k_sh_salu_branch, "s_cmp_eq_u32 s48, 0\n\t v_readlane_b32 s45, v40, s42\n\t s_flbit_i32_b32 s46, s45\n\t s_cbranch_scc1 9f\n\t 9:\n\t")
 
+// The window refill (csrc/gen/gen_rans_decode_asm.py: refill() in the shadow tile, inhand_tile()).  The pairs are the shadow
+// pair above with the compare always true ("s43 == 0"), so the even symbol leaves the main line every time; the window's
+// content does not matter to the timing (it is shifted by s43 = 0 and only copied).  The out-of-line code of a copy stands
+// behind the copy's main line, which ends in an s_branch over it: rows (c), (d) and (d1) all carry that one extra taken
+// branch, their differences do not.  Scratch: s45, s50, s51.  Rows, per copy of the snippet:
+//   refill: (a0/a1/a2)  v_readlane; taken s_branch; SALU   against   v_readlane; SALU; taken s_branch   and the branch-in:
+//                       s_cmp; v_readlane; TAKEN s_cbranch_scc1; SALU (untaken: shadow (e1))
+//   refill: (b1/b2)     v_readlane; SALU   against   two v_readlane back to back; SALU
+//   refill: (c0)        the shadow pair, branch never taken, with the s_branch over an (empty) path: the base of c, d, d1
+//   refill: (c)         the shadow pair whose even symbol takes refill() every time (mode switch, lane read, branch back)
+//   refill: (d)         the in-hand pair: five SALU, the pair's rest up to the odd lane read + prefetch + record, branch back
+//   refill: (d1)        the same with the odd symbol's s_flbit in the path, in front of the return branch
+//   refill: (e)         the staging of the row v227 at a block end, alone
+#define RF_EVEN_HEAD SH_HEAD("s41") SH_WSHIFT "s_cmp_eq_u32 s43, 0\n\t v_readlane_b32 s47, v45, s41\n\t v_writelane_b32 v44, s41, 3\n\t"
+#define RF_EVEN_TAIL SH_SHIFT("s[46:47]", "s_mov_b32 s46, s49\n\t")
+#define RF_ODD_HEAD SH_HEAD("s47") SH_WSHIFT "v_readlane_b32 s41, v45, s47\n\t"
+#define RF_ODD_REC "v_writelane_b32 v44, s47, 3\n\t"
+#define RF_TODAY "s_lshr_b32 s50, s42, 6\n\t s_set_gpr_idx_on s43, 0x1\n\t s_ff1_i32_b32 s45, s49\n\t s_sub_u32 s45, 31, s45\n\t" \
+                 "v_readlane_b32 s51, v40, s42\n\t s_add_u32 s50, s50, 1\n\t s_lshr_b64 s[50:51], s[50:51], s45\n\t"        \
+                 "s_xor_b64 s[48:49], s[48:49], s[50:51]\n\t"
+#define RF_INHAND "s_ff1_i32_b32 s45, s49\n\t s_sub_u32 s45, 31, s45\n\t s_lshr_b64 s[50:51], s[50:51], s45\n\t"               \
+                  "s_xor_b64 s[48:49], s[48:49], s[50:51]\n\t s_add_u32 s45, s45, 1\n\t"
+PROBE_KERNEL(k_rf_branch_salu, "v_readlane_b32 s45, v40, s42\n\t s_branch 9f\n\t s_nop 0\n\t 9:\n\t s_add_u32 s40, s45, s40\n\t")
+PROBE_KERNEL(k_rf_salu_branch, "v_readlane_b32 s45, v40, s42\n\t s_add_u32 s40, s45, s40\n\t s_branch 9f\n\t s_nop 0\n\t 9:\n\t")
+PROBE_KERNEL(k_rf_cbranch_taken, "s_cmp_eq_u32 s43, 0\n\t v_readlane_b32 s45, v40, s42\n\t s_cbranch_scc1 9f\n\t s_nop 0\n\t 9:\n\t s_flbit_i32_b32 s46, s45\n\t")
+PROBE_KERNEL(k_rf_two_reads, "v_readlane_b32 s45, v40, s42\n\t v_readlane_b32 s46, v41, s42\n\t s_add_u32 s40, s45, s40\n\t")
+PROBE_KERNEL(k_rf_pair_base, SH_HEAD("s41") SH_WSHIFT "s_cmp_eq_u32 s48, 0\n\t v_readlane_b32 s47, v45, s41\n\t v_writelane_b32 v44, s41, 3\n\t"
+                             "s_cbranch_scc1 3f\n\t 4:\n\t" RF_EVEN_TAIL SH_ODD "s_branch 5f\n\t 3:\n\t s_branch 4b\n\t 5:\n\t")
+PROBE_KERNEL(k_rf_pair_today, RF_EVEN_HEAD "s_cbranch_scc1 3f\n\t 4:\n\t" RF_EVEN_TAIL SH_ODD "s_branch 5f\n\t"
+                              "3:\n\t" RF_TODAY "s_branch 4b\n\t 5:\n\t")
+PROBE_KERNEL(k_rf_pair_inhand, RF_EVEN_HEAD "s_cbranch_scc1 3f\n\t" RF_EVEN_TAIL RF_ODD_HEAD RF_ODD_REC
+                               "6:\n\t" SH_SHIFT("s[40:41]", "s_mov_b32 s40, s46\n\t") "s_branch 5f\n\t"
+                               "3:\n\t" RF_INHAND RF_EVEN_TAIL RF_ODD_HEAD "v_readlane_b32 s51, v40, s42\n\t" RF_ODD_REC "s_branch 6b\n\t 5:\n\t")
+PROBE_KERNEL(k_rf_pair_inhand_flbit, RF_EVEN_HEAD "s_cbranch_scc1 3f\n\t" RF_EVEN_TAIL RF_ODD_HEAD RF_ODD_REC
+                               "s_flbit_i32_b32 m0, s44\n\t 6:\n\t s_mov_b32 s40, s46\n\t s_movrels_b32 s45, s42\n\t s_lshl_b64 s[40:41], s[40:41], s43\n\t s_branch 5f\n\t"
+                               "3:\n\t" RF_INHAND RF_EVEN_TAIL RF_ODD_HEAD "v_readlane_b32 s51, v40, s42\n\t" RF_ODD_REC
+                               "s_flbit_i32_b32 m0, s44\n\t s_branch 6b\n\t 5:\n\t")
+PROBE_KERNEL(k_rf_stage, "s_lshr_b32 s45, s42, 6\n\t s_set_gpr_idx_on s43, 0x1\n\t v_mov_b32_e32 v46, v40\n\t s_bfm_b64 exec, s42, 0\n\t"
+                         "v_mov_b32_e32 v46, v41\n\t s_mov_b64 exec, -1\n\t")
+
 // What the seventh slot of the complement step (its closing s_nop 1: the two wait states between the VALU write of z
 // and the DPP read) can carry for nothing.  The same six chain instructions as k_enc_comp7, then the filler.  These
 // kernels own LDS (the ds_read's target; v50 = 16 * lane) and take a byte buffer (the store's target: out + 256 + lane,
@@ -223,11 +263,23 @@ int main(int argc, char** argv) {
     {"shadow: (d0) v_readlane; SALU", k_cross_0}, {"shadow: (d1) v_readlane; v_writelane of an SGPR; SALU", k_sh_record},
     {"shadow: (e0) s_cmp; v_readlane; SALU", k_sh_cmp_salu},
     {"shadow: (e1) s_cmp; v_readlane; untaken s_cbranch_scc1; SALU", k_sh_branch_salu},
-    {"shadow: (e2) s_cmp; v_readlane; SALU; untaken s_cbranch_scc1", k_sh_salu_branch}};
+    {"shadow: (e2) s_cmp; v_readlane; SALU; untaken s_cbranch_scc1", k_sh_salu_branch},
+    {"refill: (a0) v_readlane; taken s_branch; SALU", k_rf_branch_salu},
+    {"refill: (a1) v_readlane; SALU; taken s_branch", k_rf_salu_branch},
+    {"refill: (a2) s_cmp; v_readlane; taken s_cbranch_scc1; SALU", k_rf_cbranch_taken},
+    {"refill: (a3) s_cmp; v_readlane; untaken s_cbranch_scc1; SALU", k_sh_branch_salu},
+    {"refill: (b1) v_readlane; SALU", k_cross_0}, {"refill: (b2) two v_readlane; SALU", k_rf_two_reads},
+    {"refill: (c0) shadow pair, no refill, s_branch over the path", k_rf_pair_base},
+    {"refill: (c) shadow pair, refill() in every pair", k_rf_pair_today},
+    {"refill: (d) in-hand pair, refill in every pair", k_rf_pair_inhand},
+    {"refill: (d1) in-hand pair, s_flbit in front of the return branch", k_rf_pair_inhand_flbit},
+    {"refill: (e) staging of the window row at a block end", k_rf_stage}};
   double base = 0;
   FILE* js = argc > 1 ? fopen(argv[1], "w") : nullptr;   // the "comp step + ..." rows as JSON (cycles per step)
   FILE* jd = argc > 2 ? fopen(argv[2], "w") : nullptr;   // the "dec: ..." rows as JSON (cycles per copy)
   FILE* jh = argc > 3 ? fopen(argv[3], "w") : nullptr;   // the "shadow: ..." rows as JSON (cycles per copy)
+  FILE* jr = argc > 4 ? fopen(argv[4], "w") : nullptr;   // the "refill: ..." rows as JSON (cycles per copy)
+  if (jr) fprintf(jr, "{\n  \"what\": \"scripts/probes/latency_probe.hip: the window refill of the decode tile, today's (mode switch and lane read of its own, branch back at once) against the in-hand one (dword already in an SGPR, the path runs on to the odd symbol's lane read), one wave alone; shader cycles per copy of the row's snippet, best of 5 launches, empty loop subtracted; rows c0, c, d and d1 each contain one taken s_branch over the out-of-line code that the tile does not have\"");
   if (jh) fprintf(jh, "{\n  \"what\": \"scripts/probes/latency_probe.hip: the shadow pair of the decode tile (record behind the lane read, window shifts in the wait-state holes) against today's vector pair, one wave alone; shader cycles per copy of the row's snippet, best of 5 launches, empty loop subtracted\"");
   if (jd) fprintf(jd, "{\n  \"what\": \"scripts/probes/latency_probe.hip: the decode symbol with the state update on the vector side, one wave alone; shader cycles per copy of the row's snippet, best of 5 launches, empty loop subtracted\"");
   if (js) fprintf(js, "{\n  \"what\": \"scripts/probes/latency_probe.hip: the 7-slot complement step on one wave alone, its closing s_nop 1 replaced by fillers; shader cycles per step, best of 5 launches, empty loop subtracted\"");
@@ -247,7 +299,10 @@ int main(int argc, char** argv) {
       fprintf(jd, ",\n  \"%s\": %.2f", t.name + 5, ((double)best - base) / (256.0 * 32.0));
     if (jh && std::string(t.name).rfind("shadow: ", 0) == 0)
       fprintf(jh, ",\n  \"%s\": %.2f", t.name + 8, ((double)best - base) / (256.0 * 32.0));
+    if (jr && std::string(t.name).rfind("refill: ", 0) == 0)
+      fprintf(jr, ",\n  \"%s\": %.2f", t.name + 8, ((double)best - base) / (256.0 * 32.0));
   }
+  if (jr) { fprintf(jr, "\n}\n"); fclose(jr); }
   if (jh) { fprintf(jh, "\n}\n"); fclose(jh); }
   if (js) { fprintf(js, "\n}\n"); fclose(js); }
   if (jd) { fprintf(jd, "\n}\n"); fclose(jd); }
