@@ -357,6 +357,15 @@ def load_library() -> C.CDLL:
         "alice_codec_dev_decode_rects": (C.c_int, [C.POINTER(RectItem), C.c_uint32, _u32p, vp]),
         "alice_codec_test_last_rects_stats": (None, [_u64p]),
         "alice_codec_test_rects_outputs_disjoint": (C.c_int, [C.POINTER(RectItem), C.c_uint32, _u32p]),
+        "alice_codec_transcode": (vp, [_u8p, C.c_uint64, C.c_uint8, C.c_uint32, C.c_uint8, _u64p]),
+        "alice_codec_transcode_to_size": (vp, [_u8p, C.c_uint64, C.c_uint32, C.c_uint8, C.c_uint64, C.c_uint8, C.c_uint8, _u8p, _u8p, _u64p]),
+        "alice_codec_predict_transcode_sizes": (C.c_int, [_u8p, C.c_uint64, C.c_uint32, _u64p, _u64p]),
+        "alice_codec_dev_transcode": (C.c_int, [vp, C.c_uint64, _u64p, C.c_uint32, C.c_uint8, _u8p, C.c_uint32, C.c_uint8, vp, C.c_uint64,
+                                                _u64p, vp]),
+        "alice_codec_dev_transcode_to_budget": (C.c_int, [vp, C.c_uint64, _u64p, C.c_uint32, C.c_uint32, C.c_uint8, _u64p, C.c_uint8, C.c_uint8,
+                                                          _u8p, _u8p, vp, C.c_uint64, _u64p, vp]),
+        "alice_codec_dev_requant_symbols": (C.c_int, [vp, vp, C.c_uint64, C.c_int, C.c_int32, C.c_int32, vp, vp]),
+        "alice_codec_test_symbol_bins": (C.c_int, [vp, C.c_uint64, C.c_int, C.c_int32, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
@@ -2661,3 +2670,108 @@ def wide_encode_to_psnr_device(d_frames_ptr: int, width: int, height: int, frame
     return _encode_container_to_psnr_device("wide", d_frames_ptr, width, height, frames, n_chunks, wavelet_type, min_psnr, d_out_ptr,
                                             out_stride, min_quality, max_quality, lane_symbols, frame_width, frame_height, origins,
                                             stream)
+
+
+# ---- transcode of a version 2, 3 or 4 chunk to a lower quality or a byte budget, without pixels ----
+
+def _u8_arg(v, what: str) -> int:
+    if not 0 <= int(v) <= 255:
+        raise ValueError(f"{what} must fit a u8 (0..255), got {v}")
+    return int(v)
+
+
+def transcode(data, quality: int, lane_symbols: int = 0, out_version: int = 0) -> bytes:
+    """A version 2, 3 or 4 container at `quality`, made from its symbols alone: lane decode, a map of every symbol to the
+    coarser quantiser step, table, lane encode.  A channel whose step is already at or above the target's is left as it is,
+    so a quality at or above the source's returns the source's bytes.  From a quality-100 source the result is byte for
+    byte the direct encode at `quality`.  lane_symbols 0 keeps the source's; out_version 0 keeps the version (3 and 4 may be
+    exchanged).  The result is read by the ordinary decode calls (decode_alc)."""
+    lib = load_library()
+    buf = _as_u8(data)
+    _dims_u32(lane_symbols)
+    n = C.c_uint64(0)
+    ptr = lib.alice_codec_transcode(_p(buf, _u8p), buf.size, _u8_arg(quality, "quality"), lane_symbols, _u8_arg(out_version, "out_version"),
+                                    C.byref(n))
+    if not ptr:
+        _raise_last()
+    try:
+        return _copy_out(ptr, n.value).tobytes()
+    finally:
+        lib.alice_codec_data_free64(ptr, n.value)
+
+
+def transcode_to_size(data, max_bytes: int, min_quality: int = 10, max_quality: int = 95, lane_symbols: int = 0,
+                      out_version: int = 0) -> tuple:
+    """transcode at the highest quality in [min_quality, max_quality] that the byte-budget rule of encode_split_to_size finds
+    to fit max_bytes (brackets from predict_transcode_sizes, at most four exact trials from the decoded symbols).  Returns
+    (bytes, quality, fits); the bytes are transcode's at that quality.  A version 4 result has no budget: out_version=3."""
+    lib = load_library()
+    buf = _as_u8(data)
+    _dims_u32(lane_symbols)
+    _check_budget_args([max_bytes], min_quality, max_quality)
+    chosen = C.c_uint8(0); fits = C.c_uint8(0); n = C.c_uint64(0)
+    ptr = lib.alice_codec_transcode_to_size(_p(buf, _u8p), buf.size, lane_symbols, _u8_arg(out_version, "out_version"), int(max_bytes),
+                                            int(min_quality), int(max_quality), C.byref(chosen), C.byref(fits), C.byref(n))
+    if not ptr:
+        _raise_last()
+    try:
+        return _copy_out(ptr, n.value).tobytes(), int(chosen.value), bool(fits.value)
+    finally:
+        lib.alice_codec_data_free64(ptr, n.value)
+
+
+def predict_transcode_sizes(data, lane_symbols: int = 0) -> SizePrediction:
+    """lo[q] <= len(transcode(data, q, lane_symbols)) <= hi[q] for the 101 qualities (status is always bounded)."""
+    buf = _as_u8(data)
+    _dims_u32(lane_symbols)
+    lo = np.zeros(101, np.uint64); hi = np.zeros(101, np.uint64)
+    _check(load_library().alice_codec_predict_transcode_sizes(_p(buf, _u8p), buf.size, lane_symbols, _p(lo, _u64p), _p(hi, _u64p)))
+    return SizePrediction(lo, hi, np.zeros(101, np.uint8))
+
+
+def transcode_device(d_alc_ptr: int, alc_stride: int, sizes, quality: int, d_out_ptr: int, out_stride: int, qualities=None,
+                     lane_symbols: int = 0, out_version: int = 0, stream: int = 0) -> np.ndarray:
+    """len(sizes) device containers of one version, wavelet, shape and lane_symbols (chunk i of sizes[i] bytes at
+    d_alc_ptr + i * alc_stride) -> chunk i transcoded to qualities[i] (None: `quality`) at d_out_ptr + i * out_stride;
+    returns the sizes."""
+    s = np.ascontiguousarray(sizes, dtype=np.uint64).reshape(-1)
+    q = None if qualities is None else np.ascontiguousarray(qualities, dtype=np.uint8).reshape(-1)
+    if q is not None and q.size != s.size:
+        raise ValueError("one quality per chunk")
+    _dims_u32(lane_symbols)
+    out = np.zeros(s.size, np.uint64)
+    _check(load_library().alice_codec_dev_transcode(d_alc_ptr, alc_stride, _p(s, _u64p), s.size, _u8_arg(quality, "quality"),
+                                                    None if q is None else _p(q, _u8p), lane_symbols, _u8_arg(out_version, "out_version"),
+                                                    d_out_ptr, out_stride, _p(out, _u64p), stream or None))
+    return out
+
+
+def transcode_to_budget_device(d_alc_ptr: int, alc_stride: int, sizes, budgets, d_out_ptr: int, out_stride: int, min_quality: int = 10,
+                               max_quality: int = 95, lane_symbols: int = 0, out_version: int = 0, stream: int = 0) -> tuple:
+    """transcode_device with chunk i under budgets[i] bytes by transcode_to_size's rule.  Returns (chosen, fits, sizes)."""
+    s = np.ascontiguousarray(sizes, dtype=np.uint64).reshape(-1)
+    b = [int(v) for v in budgets]
+    if len(b) != s.size:
+        raise ValueError("one budget per chunk")
+    _check_budget_args(b, min_quality, max_quality)
+    _dims_u32(lane_symbols)
+    bud = np.array(b, dtype=np.uint64)
+    chosen = np.zeros(s.size, np.uint8); fits = np.zeros(s.size, np.uint8); out = np.zeros(s.size, np.uint64)
+    _check(load_library().alice_codec_dev_transcode_to_budget(d_alc_ptr, alc_stride, _p(s, _u64p), s.size, lane_symbols,
+                                                              _u8_arg(out_version, "out_version"), _p(bud, _u64p), int(min_quality),
+                                                              int(max_quality), _p(chosen, _u8p), _p(fits, _u8p), d_out_ptr, out_stride,
+                                                              _p(out, _u64p), stream or None))
+    return chosen, fits.astype(bool), out
+
+
+def requant_symbols_device(d_src_ptr: int, d_dst_ptr: int, n: int, wide: bool, step_from: int, step_to: int, d_hist_ptr: int = 0,
+                           stream: int = 0) -> None:
+    """Stage call: n device symbols (u8; wide: u16) from d_src_ptr to d_dst_ptr (the same address, or no overlap) through the
+    transcode map of quantiser steps (step_from, step_to); the histogram of the coded symbols is added to the 256 u32 at
+    d_hist_ptr when given."""
+    if not 0 <= n < (1 << 64):
+        raise CodecError(3, "symbol count out of u64 range")
+    if not (-(1 << 31) <= step_from < (1 << 31) and -(1 << 31) <= step_to < (1 << 31)):
+        raise CodecError(5, "quantiser step out of i32 range")
+    _check(load_library().alice_codec_dev_requant_symbols(d_src_ptr or None, d_dst_ptr or None, n, 1 if wide else 0, step_from, step_to,
+                                                          d_hist_ptr or None, stream or None))

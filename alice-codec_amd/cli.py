@@ -26,6 +26,10 @@ PREFIX.NNNNN.alc files of `encode-chunks`; inputs whose preview sizes differ, an
 `extract IN [IN ...] -o OUT [--rect X,Y,W,H] [--frame K | --every N]` is its full-resolution twin: whole frames, or the W x H
 pixels at (X, Y), of frame K (default 0) or of every N-th frame of every input, back to back, one batched call per 1024
 items over mapped files; inputs whose output sizes differ, and version 1 inputs, are refused.
+`transcode IN -o OUT (--quality Q | --max-bytes N [--min-quality A --max-quality B]) [--lane-symbols L] [--to-version V]`
+writes a version 2, 3 or 4 file again at a lower quality or under a byte budget, from its symbols alone (DESIGN.md section
+19): no pixels, no transform.  A quality at or above the file's returns its bytes; `--to-version` 3 or 4 exchanges the two
+wide versions; a version 4 result has no byte budget (ask for `--to-version 3`); version 1 is refused.
 Like the reference it treats the whole input file as ONE chunk (src/bin/main.rs:117-122).  `encode-chunks`
 is the extension SURVEY.md section 8f asks for: it cuts a long raw-RGB file into 64-frame chunks
 (DEFAULT_CHUNK_SIZE, src/lib.rs:110) and writes one .alc per chunk."""
@@ -39,7 +43,7 @@ import numpy as np
 from . import (DEFAULT_CHUNK_SIZE, PREVIEWS_MAX_ITEMS, RECTS_MAX_ITEMS, CodecError, EncodedChunk, FrameDecoder, FrameEncoder, WaveletType, budget_bytes_per_chunk,
                alc_version, decode_frames, decode_preview, decode_previews, decode_rect, decode_rects, decode_reversible, decode_split, decode_wide, encode_many, encode_reversible, encode_split,
                encode_split_to_psnr, encode_split_to_size, encode_to_size, encode_wide, encode_wide_to_psnr, reversible_info,
-               split_info, wide_info)
+               split_info, transcode, transcode_to_size, wide_info)
 
 WAVELETS = {"cdf53": WaveletType.Cdf53, "cdf97": WaveletType.Cdf97, "haar": WaveletType.Haar}
 WAVELET_NAMES = {WaveletType.Cdf53: "CDF 5/3", WaveletType.Cdf97: "CDF 9/7", WaveletType.Haar: "Haar"}
@@ -444,6 +448,26 @@ def cmd_decode(a) -> None:
     print(f"decoded {chunk.width}x{chunk.height}x{chunk.frames} -> {rgb.size} bytes (raw RGB)", file=sys.stderr)
 
 
+def cmd_transcode(a) -> None:
+    """IN at --quality Q, or under --max-bytes N at the best quality in [--min-quality, --max-quality], from its symbols."""
+    if (a.quality is None) == (a.max_bytes is None):
+        raise ValueError("transcode wants exactly one of --quality Q and --max-bytes N")
+    if a.max_bytes is not None and a.max_bytes < 0:
+        raise ValueError(f"--max-bytes wants a byte count >= 0, got {a.max_bytes}")
+    data = np.fromfile(a.input, dtype=np.uint8)
+    if a.max_bytes is None:
+        out = transcode(data, a.quality, a.lane_symbols, a.to_version)
+        line = f"quality {a.quality}"
+    else:
+        out, quality, fits = transcode_to_size(data, a.max_bytes, a.min_quality, a.max_quality, a.lane_symbols, a.to_version)
+        line = f"chosen quality: {quality}, budget {a.max_bytes} bytes {'met' if fits else 'NOT met'}"
+    with open(a.output, "wb") as f:
+        f.write(out)
+    info = CONTAINER_INFO[out[4]](out)
+    print(f"transcoded {data.size} -> {len(out)} bytes ({CONTAINER_NAME[out[4]]}, {line}, quantiser steps {list(info.quant_step)}, "
+          f"lane_symbols {info.lane_symbols})", file=sys.stderr)
+
+
 def cmd_info(a) -> None:
     data = np.fromfile(a.input, dtype=np.uint8)
     version = _container_version(a, data)
@@ -540,6 +564,15 @@ def main(argv=None) -> int:
     x.add_argument("--rect", default=None, metavar="X,Y,W,H", help="the W x H pixels at (X, Y) of every picked frame instead of the whole frame")
     x.add_argument("--frame", type=int, default=None, metavar="K", help="frame K of every input (default 0)")
     x.add_argument("--every", type=int, default=None, metavar="N", help="every N-th frame of every input instead")
+    tr = sub.add_parser("transcode", help="a version 2, 3 or 4 file at a lower quality or under a byte budget, from its symbols alone")
+    tr.add_argument("input")
+    tr.add_argument("-o", "--output", required=True)
+    tr.add_argument("-q", "--quality", type=_u8, default=None, help="target quality 0..100; at or above the file's: its bytes come back")
+    tr.add_argument("--max-bytes", type=int, default=None, help="instead of --quality: the highest quality that fits this many bytes")
+    tr.add_argument("--min-quality", type=_u8, default=10)
+    tr.add_argument("--max-quality", type=_u8, default=95)
+    tr.add_argument("--lane-symbols", type=int, default=0, help="lane the chunk again (power of two in the version's range; 0 = keep)")
+    tr.add_argument("--to-version", type=_u8, default=0, metavar="V", help="3 or 4 for a version 3 or 4 file (0 = keep)")
     i = sub.add_parser("info")
     i.add_argument("input")
     for x in (d, i):
@@ -548,7 +581,7 @@ def main(argv=None) -> int:
     a = p.parse_args(argv)
     try:
         {"encode": cmd_encode, "encode-chunks": cmd_encode_chunks, "decode": cmd_decode, "info": cmd_info,
-         "thumbnails": cmd_thumbnails, "extract": cmd_extract}[a.command](a)
+         "thumbnails": cmd_thumbnails, "extract": cmd_extract, "transcode": cmd_transcode}[a.command](a)
     except (CodecError, ValueError, OSError) as e:
         print(f"error: {e}", file=sys.stderr)
         return 1

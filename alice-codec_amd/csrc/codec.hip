@@ -3623,6 +3623,7 @@ struct SplitChunkEncode {
     SplitWork w;
     std::vector<uint64_t> totals;
     std::vector<uint8_t> q;
+    std::vector<int32_t> steps, dead_zones;   // a transcode: 3 per chunk, written instead of quality_to_step(q[i])
     uint32_t B = 0, L = 0;
     uint8_t wavelet = 0;
     SplitFormat fmt = kFormatSplit;
@@ -3666,7 +3667,8 @@ int split_write_chunks(SplitChunkEncode& e, const std::vector<uint8_t*>& outs, h
         h.freq = w.freq.as<uint16_t>() + (size_t)i * 3 * 256;
         uint64_t off = kSplitHeaderBytes;
         for (int c = 0; c < 3; ++c) {
-            h.step[c] = h.dead_zone[c] = quality_to_step(e.q[i]);
+            if (e.steps.empty()) h.step[c] = h.dead_zone[c] = quality_to_step(e.q[i]);
+            else { h.step[c] = e.steps[3 * (size_t)i + c]; h.dead_zone[c] = e.dead_zones[3 * (size_t)i + c]; }
             h.payload_len[c] = e.totals[3 * i + c];
             w.h[3 * (size_t)i + c].stream = outs[i] + off;
             off += e.totals[3 * i + c];
@@ -6166,6 +6168,457 @@ int alice_codec_test_rects_outputs_disjoint(const alice_codec_rect_item* items, 
         r[k] = RectsOut{(uintptr_t)out.base, it.count, it.h, 3ull * it.w, out.row_pitch, out.frame_pitch};
     }
     return rects_outputs_disjoint(r, bad_item);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// PART 11: transcode of version 2, 3 and 4 chunks to a coarser step or a byte budget (kernels:
+// transcode.hip)
+//
+// A symbol is a function of the quantised coefficient alone and the step is stored per channel, so a coarser chunk is made
+// from the symbols: lane decode, the map, histogram and table, lane encode.  No transform runs and no pixel exists.  One
+// body carries the container (SplitFormat); the lane coders, the table, count and cost kernels are the encoders' own.
+// ------------------------------------------------------------------------------------------
+
+namespace {
+
+// drains the stream before the buffers declared ahead of it go back to the pool, on every return
+struct StreamDrain {
+    hipStream_t st;
+    explicit StreamDrain(hipStream_t s) : st(s) {}
+    ~StreamDrain() { (void)hipStreamSynchronize(st); }
+    StreamDrain(const StreamDrain&) = delete;
+    StreamDrain& operator=(const StreamDrain&) = delete;
+};
+
+// The arguments every transcode call shares, after the header has been accepted: lane_symbols (0 keeps the source's),
+// then out_version (0 keeps the version; 3 and 4 are interchangeable, only the version byte differs).
+int transcode_check_args(const SplitHeader& h, uint32_t lane_symbols, uint8_t out_version, uint32_t* L, SplitFormat* fmt_out) {
+    *L = lane_symbols ? lane_symbols : h.lane_symbols;
+    if (!split_lane_ok(*L, h.fmt)) return fail(kInvalidDimensions, split_lane_msg(h.fmt));
+    const bool ok = out_version == 0 || (is_wide(h.fmt) && (out_version == 3 || out_version == 4));
+    if (!ok)
+        return fail(kInvalidDimensions, "out_version " + std::to_string((int)out_version) + " of a version " + std::to_string((int)format_version(h.fmt)) +
+                                            " chunk (0 keeps the version; 3 and 4 for a version 3 or 4 chunk)");
+    *fmt_out = out_version ? format_of_version(out_version) : h.fmt;
+    return kOk;
+}
+
+int transcode_check_budget_format(SplitFormat fmt_out) {
+    if (fmt_out == kFormatReversible)
+        return fail(kInvalidBitstream, "version 4 is the lossless container (a byte budget searches the quality, and a lossy version 4 is "
+                                       "not recommended); ask for out_version = 3");
+    return kOk;
+}
+
+// step and dead zone channel c of a chunk gets at target step s2: untouched unless the target is coarser
+inline void transcode_channel_steps(const SplitHeader& h, int c, int32_t s2, int32_t* step, int32_t* dead_zone) {
+    const bool coarser = s2 > h.step[c];
+    *step = coarser ? s2 : h.step[c];
+    *dead_zone = coarser ? s2 : h.dead_zone[c];
+}
+
+// The decoded symbols of B equal-shaped chunks of one version, resident for the whole call: chunk i, channel c at
+// sym + (3 i + c) * padded * sb.
+struct TranscodeSource {
+    DevBuf sym;
+    SplitWork dw;
+    size_t sb = 1;
+};
+
+// Queues the directory scan and the lane decode of the chunks at d_alc[i] (hdr[i] validated) and returns with their verdict:
+// nothing of a damaged source is mapped or written.
+int transcode_decode(TranscodeSource& s, const SplitHeader* hdr, const uint8_t* const* d_alc, uint32_t B, const ChunkDims& d, hipStream_t st) {
+    const SplitFormat fmt = hdr[0].fmt;
+    s.sb = is_wide(fmt) ? 2 : 1;
+    TRY(s.sym.alloc((size_t)B * 3 * d.padded * s.sb));
+    TRY(split_work_alloc(s.dw, (int)(3 * B), d.padded, hdr[0].lane_symbols, false, fmt));
+    std::vector<uint16_t> freq((size_t)B * 3 * 256);
+    for (uint32_t i = 0; i < B; ++i) {
+        split_chunk_jobs(s.dw, 3 * (size_t)i, hdr[i], d_alc[i], s.sym.as<uint8_t>() + 3 * (size_t)i * d.padded * s.sb, d.padded * s.sb);
+        memcpy(&freq[3 * (size_t)i * 256], hdr[i].freq, 3 * 256 * sizeof(uint16_t));
+    }
+    TRY(split_decode_launch(s.dw, freq.data(), st));
+    return split_decode_verdict(s.dw, st);
+}
+
+// The first half of an encode from symbols: B chunks whose source symbols lie at `in` (chunk stride 3 * padded * sb) are
+// mapped to target step s2[i] into `out` (in == out: in place, untouched channels are only counted), then the tables and
+// the count pass.  Returns the exact container sizes after the stream has drained; split_write_chunks(e, ...) writes them.
+int transcode_count_chunks(SplitChunkEncode& e, const uint8_t* in, uint8_t* out, const SplitHeader* hdr, uint32_t B, const ChunkDims& d,
+                           const int32_t* s2, uint32_t L, SplitFormat fmt_out, hipStream_t st, std::vector<uint64_t>& sizes) {
+    const bool wide = is_wide(fmt_out);
+    const size_t sb = wide ? 2 : 1;
+    e.B = B; e.L = L; e.wavelet = hdr[0].wavelet; e.fmt = fmt_out;
+    e.q.assign(B, 0);
+    e.steps.assign(3 * (size_t)B, 1); e.dead_zones.assign(3 * (size_t)B, 1);
+    e.ew.d = d; e.ew.n_chunks = (int)B;
+    TRY(e.ew.hist.alloc((size_t)B * 3 * 256 * sizeof(uint32_t)));
+    HIP_TRY(hipMemsetAsync(e.ew.hist.p, 0, (size_t)B * 3 * 256 * sizeof(uint32_t), st));
+    for (uint32_t i = 0; i < B; ++i)
+        for (int c = 0; c < 3; ++c) {
+            const size_t j = 3 * (size_t)i + c;
+            transcode_channel_steps(hdr[i], c, s2[i], &e.steps[j], &e.dead_zones[j]);
+            const uint8_t* src = in + j * d.padded * sb;
+            uint8_t* dst = out + j * d.padded * sb;
+            uint32_t* hist = e.ew.hist.as<uint32_t>() + j * 256;
+            if (src != dst || s2[i] > hdr[i].step[c]) launch_requant_symbols(src, dst, d.padded, wide, hdr[i].step[c], s2[i], hist, st);
+            else if (wide) launch_histogram_wide((const uint16_t*)src, d.padded, hist, st);
+            else launch_histogram(src, d.padded, hist, st);
+        }
+    HIP_TRY(hipGetLastError());
+    e.hd.assign(B, SplitHeaderDesc{});
+    TRY(split_work_alloc(e.w, (int)(3 * B), d.padded, L, true, fmt_out));
+    for (size_t j = 0; j < 3 * (size_t)B; ++j) e.w.h[j].sym = out + j * d.padded * sb;
+    TRY(split_count(e.w, e.ew.hist.as<uint32_t>(), st, e.totals, nullptr));
+    sizes.resize(B);
+    for (uint32_t i = 0; i < B; ++i) sizes[i] = kSplitHeaderBytes + e.totals[3 * i] + e.totals[3 * i + 1] + e.totals[3 * i + 2];
+    return kOk;
+}
+
+// Payload brackets of B resident chunks at every target step: out[(chunk * 64 + step - 1) * 3 + channel], as predict_chunks
+// gives them for an encode.  The bins are of the value the map quantises (launch_symbol_bins), folded by the encoders' fold;
+// the rows of steps at or below a channel's own step are its own coded histogram (the channel is left untouched there).  A
+// chunk with values outside the bins' range gets its rows from real maps at each coarser step.  Returns after the stream
+// has drained.
+int transcode_predict_chunks(const TranscodeSource& s, const SplitHeader* hdr, uint32_t B, const ChunkDims& d, uint32_t L, hipStream_t st,
+                             std::vector<RateChannel>& out) {
+    const bool wide = is_wide(hdr[0].fmt);
+    const size_t per_chunk = (size_t)64 * 3;
+    DevBuf bins, oor, src_hist, step_hist, res, logt, scratch;
+    StreamDrain drain(st);
+    TRY(bins.alloc((size_t)B * 3 * 4096 * sizeof(uint32_t)));
+    TRY(oor.alloc((size_t)B * sizeof(uint32_t)));
+    TRY(src_hist.alloc((size_t)B * 3 * 256 * sizeof(uint32_t)));
+    TRY(step_hist.alloc((size_t)B * per_chunk * 256 * sizeof(uint32_t)));
+    TRY(res.alloc((size_t)B * per_chunk * sizeof(RateChannel)));
+    TRY(logt.alloc(2 * (kProbScale + 1) * sizeof(uint32_t)));
+    const RateLogTable& t = rate_log_table();
+    HIP_TRY(hipMemcpyAsync(logt.p, t.lo, sizeof(t.lo), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(logt.as<uint32_t>() + (kProbScale + 1), t.hi, sizeof(t.hi), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(bins.p, 0, (size_t)B * 3 * 4096 * sizeof(uint32_t), st));
+    HIP_TRY(hipMemsetAsync(oor.p, 0, (size_t)B * sizeof(uint32_t), st));
+    HIP_TRY(hipMemsetAsync(src_hist.p, 0, (size_t)B * 3 * 256 * sizeof(uint32_t), st));
+    auto sym_of = [&](uint32_t i, int c) { return s.sym.as<uint8_t>() + (3 * (size_t)i + c) * d.padded * s.sb; };
+    for (uint32_t i = 0; i < B; ++i)
+        for (int c = 0; c < 3; ++c) {
+            launch_symbol_bins(sym_of(i, c), d.padded, wide, hdr[i].step[c], bins.as<uint32_t>() + (3 * (size_t)i + c) * 4096, oor.as<uint32_t>() + i, st);
+            uint32_t* h = src_hist.as<uint32_t>() + (3 * (size_t)i + c) * 256;
+            if (wide) launch_histogram_wide((const uint16_t*)sym_of(i, c), d.padded, h, st);
+            else launch_histogram(sym_of(i, c), d.padded, h, st);
+        }
+    if (wide) launch_rate_fold_wide(bins.as<uint32_t>(), oor.as<uint32_t>(), B, step_hist.as<uint32_t>(), st);
+    else launch_rate_fold(bins.as<uint32_t>(), oor.as<uint32_t>(), B, step_hist.as<uint32_t>(), st);
+    std::vector<uint32_t> h_oor(B);
+    HIP_TRY(hipMemcpyAsync(h_oor.data(), oor.p, B * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (uint32_t i = 0; i < B; ++i) {
+        uint32_t* rows = step_hist.as<uint32_t>() + (size_t)i * per_chunk * 256;
+        if (h_oor[i]) {
+            if (!scratch.p) TRY(scratch.alloc(d.padded * s.sb));
+            HIP_TRY(hipMemsetAsync(rows, 0, per_chunk * 256 * sizeof(uint32_t), st));
+            for (int c = 0; c < 3; ++c)
+                for (int32_t step = hdr[i].step[c] + 1; step <= 64; ++step)
+                    launch_requant_symbols(sym_of(i, c), scratch.p, d.padded, wide, hdr[i].step[c], step, rows + ((size_t)(step - 1) * 3 + c) * 256, st);
+        }
+        launch_kept_rows(src_hist.as<uint32_t>() + 3 * (size_t)i * 256, hdr[i].step, rows, st);
+    }
+    if (wide) launch_wide_rate_cost(step_hist.as<uint32_t>(), logt.as<uint32_t>(), B, L, res.as<RateChannel>(), st);
+    else launch_split_rate_cost(step_hist.as<uint32_t>(), logt.as<uint32_t>(), B, L, res.as<RateChannel>(), st);
+    HIP_TRY(hipGetLastError());
+    out.resize((size_t)B * per_chunk);
+    HIP_TRY(hipMemcpyAsync(out.data(), res.p, out.size() * sizeof(RateChannel), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return kOk;
+}
+
+// The qualities of the B resident chunks under their budgets: split_choose_quality unchanged.  A trial maps the chunk's
+// resident symbols into a scratch copy, then the table and the count pass; nothing is decoded again.
+int transcode_choose_chunks(const TranscodeSource& s, const SplitHeader* hdr, uint32_t B, const ChunkDims& d, uint32_t L, SplitFormat fmt_out,
+                            const uint64_t* budgets, uint8_t min_q, uint8_t max_q, uint8_t* chosen, uint8_t* fits, uint32_t* trials, hipStream_t st) {
+    std::vector<RateChannel> rc;
+    TRY(transcode_predict_chunks(s, hdr, B, d, L, st, rc));
+    DevBuf scratch;
+    StreamDrain drain(st);
+    uint64_t lo[kQualities], hi[kQualities];
+    for (uint32_t i = 0; i < B; ++i) {
+        split_rate_by_quality(rc.data() + (size_t)i * 192, lo, hi);
+        TRY(split_choose_quality(lo, hi, budgets[i], min_q, max_q,
+                                 [&](uint8_t q, uint64_t* size) -> int {
+                                     if (!scratch.p) TRY(scratch.alloc(3 * d.padded * s.sb));
+                                     SplitChunkEncode e;
+                                     std::vector<uint64_t> sz;
+                                     const int32_t s2 = quality_to_step(q);
+                                     TRY(transcode_count_chunks(e, s.sym.as<uint8_t>() + 3 * (size_t)i * d.padded * s.sb, scratch.as<uint8_t>(), hdr + i, 1, d,
+                                                                &s2, L, fmt_out, st, sz));
+                                     *size = sz[0];
+                                     return kOk;
+                                 },
+                                 chosen + i, fits + i, trials + i));
+    }
+    return kOk;
+}
+
+// One group of a transcode: decode, (budgets: choose the qualities,) map in place and count, place(sizes, outs), write.
+// q: the target quality per chunk; with budgets it is written (and fits) before the map.
+template <typename Place>
+int transcode_group(const SplitHeader* hdr, const uint8_t* const* d_alc, uint32_t B, const ChunkDims& d, uint8_t* q, uint32_t L,
+                    SplitFormat fmt_out, const uint64_t* budgets, uint8_t min_q, uint8_t max_q, uint8_t* fits, uint32_t* trials,
+                    hipStream_t st, std::vector<uint64_t>& sizes, Place place) {
+    TranscodeSource s;
+    SplitChunkEncode e;     // (after s: its destructor drains the stream that reads s.sym)
+    TRY(transcode_decode(s, hdr, d_alc, B, d, st));
+    if (budgets) TRY(transcode_choose_chunks(s, hdr, B, d, L, fmt_out, budgets, min_q, max_q, q, fits, trials, st));
+    std::vector<int32_t> s2(B);
+    for (uint32_t i = 0; i < B; ++i) s2[i] = quality_to_step(q[i]);
+    TRY(transcode_count_chunks(e, s.sym.as<uint8_t>(), s.sym.as<uint8_t>(), hdr, B, d, s2.data(), L, fmt_out, st, sizes));
+    std::vector<uint8_t*> outs(B, nullptr);
+    TRY(place(sizes, outs));
+    return split_write_chunks(e, outs, st);
+}
+
+// A chunk without pixels is its header: the steps, lane_symbols and the version byte change in place.
+void transcode_empty(uint8_t* p, const SplitHeader& h, int32_t s2, uint32_t L, SplitFormat fmt_out) {
+    p[4] = format_version(fmt_out);
+    put_u32(p + 18, L);
+    for (int c = 0; c < 3; ++c) {
+        int32_t step, dz;
+        transcode_channel_steps(h, c, s2, &step, &dz);
+        uint8_t* qh = p + kSplitFixedHeaderBytes + (size_t)c * kSplitChannelHeaderBytes;
+        put_u32(qh, (uint32_t)step); put_u32(qh + 4, (uint32_t)dz);
+    }
+}
+
+// The host calls: data validated on the host (header, arguments, directories) before a device is looked for.
+uint8_t* transcode_host(const uint8_t* data, uint64_t len, uint8_t quality, uint32_t lane_symbols, uint8_t out_version, const uint64_t* max_bytes,
+                        uint8_t min_q, uint8_t max_q, uint8_t* chosen_q, uint8_t* fits, uint64_t* out_len) {
+    auto run = [&](uint8_t** out) -> int {
+        SplitHeader h;
+        ChunkDims d{};
+        TRY(frames_validate_header(data, len, h, d));
+        uint32_t L = 0;
+        SplitFormat fmt_out;
+        TRY(transcode_check_args(h, lane_symbols, out_version, &L, &fmt_out));
+        if (max_bytes) {
+            TRY(check_quality_range(min_q, max_q));
+            TRY(transcode_check_budget_format(fmt_out));
+        }
+        TRY(check_split_directories(data, h));
+        uint8_t q = quality, ok = 1;
+        uint32_t trials = 0;
+        if (d.n_pixels == 0) {
+            if (max_bytes) {
+                uint64_t lo[kQualities], hi[kQualities];
+                for (int k = 0; k < kQualities; ++k) lo[k] = hi[k] = kSplitHeaderBytes;
+                TRY(split_choose_quality(lo, hi, *max_bytes, min_q, max_q, [](uint8_t, uint64_t*) -> int { return kOk; }, &q, &ok, &trials));
+                tl_split_trials.assign(1, trials);
+            }
+            *out = host_result_alloc(kSplitHeaderBytes);
+            if (!*out) return fail(kOutOfMemory, "out of host memory");
+            memcpy(*out, data, kSplitHeaderBytes);
+            transcode_empty(*out, h, quality_to_step(q), L, fmt_out);
+            *out_len = kSplitHeaderBytes;
+            if (max_bytes) { *chosen_q = q; *fits = ok; }
+            return kOk;
+        }
+        hipStream_t st;
+        TRY(get_stream(&st));
+        DevBuf d_alc, d_out;
+        StreamDrain drain(st);
+        TRY(d_alc.alloc(len));
+        HIP_TRY(hipMemcpyAsync(d_alc.p, data, len, hipMemcpyHostToDevice, st));
+        const uint8_t* p = d_alc.as<uint8_t>();
+        std::vector<uint64_t> sizes;
+        TRY(transcode_group(&h, &p, 1, d, &q, L, fmt_out, max_bytes, min_q, max_q, &ok, &trials, st, sizes,
+                            [&](const std::vector<uint64_t>& sz, std::vector<uint8_t*>& outs) -> int {
+                                TRY(d_out.alloc(sz[0]));
+                                outs[0] = d_out.as<uint8_t>();
+                                return kOk;
+                            }));
+        if (max_bytes) tl_split_trials.assign(1, trials);
+        *out = host_result_alloc(sizes[0]);
+        if (!*out) return fail(kOutOfMemory, "out of host memory");
+        const int rc = copy_to_host(*out, d_out.p, sizes[0], st);
+        if (rc != kOk) { free(*out); *out = nullptr; return rc; }
+        *out_len = sizes[0];
+        if (max_bytes) { *chosen_q = q; *fits = ok; }
+        return kOk;
+    };
+    uint8_t* out = nullptr;
+    return run(&out) == kOk ? out : nullptr;
+}
+
+// The device calls: the headers come to the host first, and nothing is queued before they and the arguments have been
+// accepted.  The chunks agree in version, wavelet, shape and lane_symbols.  budgets == NULL: chunk i at q[i].
+int transcode_device(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks, uint8_t* q, uint32_t lane_symbols,
+                     uint8_t out_version, const uint64_t* budgets, uint8_t min_q, uint8_t max_q, uint8_t* fits, void* d_out,
+                     uint64_t out_stride, uint64_t* out_sizes, hipStream_t st) {
+    std::vector<uint8_t> raw((size_t)n_chunks * kSplitHeaderBytes, 0);
+    for (uint32_t i = 0; i < n_chunks; ++i)
+        if (sizes[i])
+            HIP_TRY(hipMemcpyAsync(raw.data() + (size_t)i * kSplitHeaderBytes, (const uint8_t*)d_alc + (size_t)i * alc_stride,
+                                   std::min<uint64_t>(sizes[i], kSplitHeaderBytes), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    std::vector<SplitHeader> hdr(n_chunks);
+    std::vector<const uint8_t*> ptr(n_chunks);
+    ChunkDims d{};
+    for (uint32_t i = 0; i < n_chunks; ++i) {
+        ChunkDims di{};
+        TRY(frames_validate_header(raw.data() + (size_t)i * kSplitHeaderBytes, sizes[i], hdr[i], di));
+        if (di.n_pixels == 0) return fail(kInvalidDimensions, "invalid dimensions");
+        if (i == 0) d = di;
+        else if (hdr[i].fmt != hdr[0].fmt || hdr[i].wavelet != hdr[0].wavelet || di.w != d.w || di.h != d.h || di.f != d.f ||
+                 hdr[i].lane_symbols != hdr[0].lane_symbols)
+            return fail(kInvalidDimensions, "the chunks of one call must have the same version, wavelet, shape and lane_symbols");
+        ptr[i] = (const uint8_t*)d_alc + (size_t)i * alc_stride;
+    }
+    uint32_t L = 0;
+    SplitFormat fmt_out;
+    TRY(transcode_check_args(hdr[0], lane_symbols, out_version, &L, &fmt_out));
+    if (budgets) TRY(transcode_check_budget_format(fmt_out));
+    std::vector<uint32_t> trials(n_chunks, 0u);
+    const uint32_t group = split_group(d, hdr[0].fmt);
+    for (uint32_t first = 0; first < n_chunks; first += group) {
+        const uint32_t B = std::min(group, n_chunks - first);
+        std::vector<uint64_t> sz;
+        TRY(transcode_group(hdr.data() + first, ptr.data() + first, B, d, q + first, L, fmt_out, budgets ? budgets + first : nullptr, min_q, max_q,
+                            fits ? fits + first : nullptr, trials.data() + first, st, sz,
+                            [&](const std::vector<uint64_t>& s, std::vector<uint8_t*>& outs) -> int {
+                                for (uint32_t i = 0; i < B; ++i) {
+                                    if (s[i] > out_stride)
+                                        return fail(kInvalidBufferSize, "chunk " + std::to_string(first + i) + " needs " + std::to_string(s[i]) +
+                                                                            " bytes, the output stride is " + std::to_string(out_stride));
+                                    outs[i] = (uint8_t*)d_out + (size_t)(first + i) * out_stride;
+                                }
+                                return kOk;
+                            }));
+        for (uint32_t i = 0; i < B; ++i) out_sizes[first + i] = sz[i];
+    }
+    if (budgets) tl_split_trials = trials;
+    return kOk;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint8_t* alice_codec_transcode(const uint8_t* data, uint64_t len, uint8_t quality, uint32_t lane_symbols, uint8_t out_version, uint64_t* out_len) {
+    clear_error();
+    if (!data || !out_len) { fail(kNullArgument, "null argument"); return nullptr; }
+    return transcode_host(data, len, quality, lane_symbols, out_version, nullptr, 0, 0, nullptr, nullptr, out_len);
+}
+
+uint8_t* alice_codec_transcode_to_size(const uint8_t* data, uint64_t len, uint32_t lane_symbols, uint8_t out_version, uint64_t max_bytes,
+                                       uint8_t min_q, uint8_t max_q, uint8_t* chosen_q, uint8_t* fits, uint64_t* out_len) {
+    clear_error();
+    if (!data || !chosen_q || !fits || !out_len) { fail(kNullArgument, "null argument"); return nullptr; }
+    return transcode_host(data, len, 0, lane_symbols, out_version, &max_bytes, min_q, max_q, chosen_q, fits, out_len);
+}
+
+int alice_codec_predict_transcode_sizes(const uint8_t* data, uint64_t len, uint32_t lane_symbols, uint64_t lo[101], uint64_t hi[101]) {
+    clear_error();
+    if (!data || !lo || !hi) return fail(kNullArgument, "null argument");
+    SplitHeader h;
+    ChunkDims d{};
+    TRY(frames_validate_header(data, len, h, d));
+    uint32_t L = 0;
+    SplitFormat fmt_out;
+    TRY(transcode_check_args(h, lane_symbols, 0, &L, &fmt_out));
+    TRY(check_split_directories(data, h));
+    if (d.n_pixels == 0) {   // an empty chunk is its header at every quality
+        for (int q = 0; q < kQualities; ++q) lo[q] = hi[q] = kSplitHeaderBytes;
+        return kOk;
+    }
+    hipStream_t st;
+    TRY(get_stream(&st));
+    DevBuf d_alc;
+    TranscodeSource s;
+    StreamDrain drain(st);
+    TRY(d_alc.alloc(len));
+    HIP_TRY(hipMemcpyAsync(d_alc.p, data, len, hipMemcpyHostToDevice, st));
+    const uint8_t* p = d_alc.as<uint8_t>();
+    TRY(transcode_decode(s, &h, &p, 1, d, st));
+    std::vector<RateChannel> rc;
+    TRY(transcode_predict_chunks(s, &h, 1, d, L, st, rc));
+    split_rate_by_quality(rc.data(), lo, hi);
+    return kOk;
+}
+
+static int dev_transcode_checks(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks, void* d_out, uint64_t* out_sizes) {
+    if (!d_alc || !sizes || !d_out || !out_sizes) return fail(kNullArgument, "null argument");
+    if (n_chunks == 0) return fail(kInvalidDimensions, "empty batch");
+    for (uint32_t i = 0; i < n_chunks; ++i)
+        if (sizes[i] > alc_stride && n_chunks > 1) return fail(kInvalidBufferSize, "chunk " + std::to_string(i) + " is longer than the stride");
+    return kOk;
+}
+
+int alice_codec_dev_transcode(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks, uint8_t quality,
+                              const uint8_t* qualities, uint32_t lane_symbols, uint8_t out_version, void* d_out, uint64_t out_stride,
+                              uint64_t* out_sizes, void* hip_stream) {
+    clear_error();
+    TRY(dev_transcode_checks(d_alc, alc_stride, sizes, n_chunks, d_out, out_sizes));
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);
+    std::vector<uint8_t> q(n_chunks);
+    for (uint32_t i = 0; i < n_chunks; ++i) q[i] = qualities ? qualities[i] : quality;
+    return transcode_device(d_alc, alc_stride, sizes, n_chunks, q.data(), lane_symbols, out_version, nullptr, 0, 0, nullptr, d_out, out_stride,
+                            out_sizes, st);
+}
+
+int alice_codec_dev_transcode_to_budget(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks, uint32_t lane_symbols,
+                                        uint8_t out_version, const uint64_t* budgets, uint8_t min_q, uint8_t max_q, uint8_t* chosen,
+                                        uint8_t* fits, void* d_out, uint64_t out_stride, uint64_t* out_sizes, void* hip_stream) {
+    clear_error();
+    TRY(dev_transcode_checks(d_alc, alc_stride, sizes, n_chunks, d_out, out_sizes));
+    if (!budgets || !chosen || !fits) return fail(kNullArgument, "null argument");
+    TRY(check_quality_range(min_q, max_q));
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);
+    // the choices reach the caller only with the bytes: a failed call leaves chosen / fits / out_sizes as they were
+    std::vector<uint8_t> q(n_chunks), ok(n_chunks);
+    std::vector<uint64_t> sz(n_chunks);
+    TRY(transcode_device(d_alc, alc_stride, sizes, n_chunks, q.data(), lane_symbols, out_version, budgets, min_q, max_q, ok.data(), d_out,
+                         out_stride, sz.data(), st));
+    for (uint32_t i = 0; i < n_chunks; ++i) { chosen[i] = q[i]; fits[i] = ok[i]; out_sizes[i] = sz[i]; }
+    return kOk;
+}
+
+int alice_codec_dev_requant_symbols(const void* d_src, void* d_dst, uint64_t n, int wide, int32_t step_from, int32_t step_to, void* d_hist,
+                                    void* hip_stream) {
+    clear_error();
+    if ((!d_src || !d_dst) && n) return fail(kNullArgument, "null argument");
+    if (step_from < 1 || step_from > 64 || step_to < 1 || step_to > 64)
+        return fail(kInvalidQuantStep, "quantiser steps " + std::to_string(step_from) + " -> " + std::to_string(step_to) + " (both are 1..64)");
+    const uint64_t sb = wide ? 2 : 1;
+    if (n > UINT64_MAX / 2) return fail(kDimensionOverflow, "more symbols than memory holds");
+    if (wide && (((uintptr_t)d_src | (uintptr_t)d_dst) & 1u)) return fail(kInvalidDimensions, "u16 symbols lie at even addresses");
+    const uintptr_t a = (uintptr_t)d_src, b = (uintptr_t)d_dst;
+    if (a != b && a < b + n * sb && b < a + n * sb) return fail(kInvalidDimensions, "source and destination overlap (in place: the same address)");
+    if (!n) return kOk;
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);
+    launch_requant_symbols(d_src, d_dst, n, wide != 0, step_from, step_to, (uint32_t*)d_hist, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    return kOk;
+}
+
+int alice_codec_test_symbol_bins(const void* d_symbols, uint64_t n, int wide, int32_t step_from, void* d_bins, void* d_oor, void* hip_stream) {
+    clear_error();
+    if (!d_symbols || !d_bins || !d_oor) return fail(kNullArgument, "null argument");
+    if (step_from < 1 || step_from > 64) return fail(kInvalidQuantStep, "quantiser step " + std::to_string(step_from) + " (1..64)");
+    if (wide && ((uintptr_t)d_symbols & 1u)) return fail(kInvalidDimensions, "u16 symbols lie at even addresses");
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);
+    launch_symbol_bins(d_symbols, n, wide != 0, step_from, (uint32_t*)d_bins, (uint32_t*)d_oor, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    return kOk;
 }
 
 }  // extern "C"

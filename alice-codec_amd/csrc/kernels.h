@@ -467,4 +467,17 @@ bool rgb_sse_flat(const RgbLayout& a, const RgbLayout& b, uint64_t w, uint64_t h
 hipError_t launch_rgb_sse(const RgbLayout& a, const RgbLayout& b, uint64_t w, uint64_t h, uint64_t n_frames,
                           unsigned long long* d_frame_sse, hipStream_t st);
 
+// ---- transcode.hip: symbols of .alc v2-v4 to a coarser quantiser step ----
+// n symbols (u8; wide: u16 at an even address) from d_src to d_dst -- the same address, or buffers that do not overlap --
+// through the map of steps (step_from, step_to), both in 1..64; step_to <= step_from is the identity.  d_hist (256 u32, or
+// null): the histogram of the coded symbols written (wide: min(z, 255)) is ADDED to it.
+void launch_requant_symbols(const void* d_src, void* d_dst, uint64_t n, bool wide, int32_t step_from, int32_t step_to,
+                            uint32_t* d_hist, hipStream_t st);
+// the bins of the value the map quantises, layout and counter of launch_coef_hist (d_bins: 4096 u32 of one channel, zeroed
+// by the caller): what launch_rate_fold / launch_rate_fold_wide turn into the histogram of every target step
+void launch_symbol_bins(const void* d_sym, uint64_t n, bool wide, int32_t step_from, uint32_t* d_bins, uint32_t* d_oor, hipStream_t st);
+// rows (step - 1, channel) of one chunk's step_hist [64][3][256] with step <= step_from[channel]: d_src_hist [3][256], the
+// coded histogram of the channel's own symbols (a transcode leaves the channel untouched there)
+void launch_kept_rows(const uint32_t* d_src_hist, const int32_t step_from[3], uint32_t* d_step_hist, hipStream_t st);
+
 }  // namespace alice

@@ -1459,3 +1459,96 @@ pub unsafe fn rects_decode_device(items: &[RectItem], hip_stream: *mut std::ffi:
     let n = u32::try_from(items.len()).unwrap_or(u32::MAX);
     check(alice_codec_dev_decode_rects(items.as_ptr(), n, &mut bad, hip_stream), 0, 0).map_err(|e| (e, bad))
 }
+
+// ---- transcode of a version 2, 3 or 4 chunk to a lower quality or a byte budget, without pixels ----
+
+extern "C" {
+    fn alice_codec_transcode(data: *const u8, len: u64, quality: u8, lane_symbols: u32, out_version: u8, out_len: *mut u64) -> *mut u8;
+    fn alice_codec_transcode_to_size(data: *const u8, len: u64, lane_symbols: u32, out_version: u8, max_bytes: u64, min_q: u8, max_q: u8,
+                                     chosen_q: *mut u8, fits: *mut u8, out_len: *mut u64) -> *mut u8;
+    fn alice_codec_predict_transcode_sizes(data: *const u8, len: u64, lane_symbols: u32, lo: *mut u64, hi: *mut u64) -> c_int;
+    fn alice_codec_dev_transcode(d_alc: *const std::ffi::c_void, alc_stride: u64, sizes: *const u64, n_chunks: u32, quality: u8,
+                                 qualities: *const u8, lane_symbols: u32, out_version: u8, d_out: *mut std::ffi::c_void, out_stride: u64,
+                                 out_sizes: *mut u64, hip_stream: *mut std::ffi::c_void) -> c_int;
+    fn alice_codec_dev_transcode_to_budget(d_alc: *const std::ffi::c_void, alc_stride: u64, sizes: *const u64, n_chunks: u32,
+                                           lane_symbols: u32, out_version: u8, budgets: *const u64, min_q: u8, max_q: u8, chosen: *mut u8,
+                                           fits: *mut u8, d_out: *mut std::ffi::c_void, out_stride: u64, out_sizes: *mut u64,
+                                           hip_stream: *mut std::ffi::c_void) -> c_int;
+    fn alice_codec_dev_requant_symbols(d_src: *const std::ffi::c_void, d_dst: *mut std::ffi::c_void, n: u64, wide: c_int, step_from: i32,
+                                       step_to: i32, d_hist: *mut std::ffi::c_void, hip_stream: *mut std::ffi::c_void) -> c_int;
+}
+
+/// A version 2, 3 or 4 container at `quality`, made from its symbols alone.  A channel whose quantiser step is already at or
+/// above the target's is left as it is, so a quality at or above the source's returns the source's bytes; from a quality-100
+/// source the result is byte for byte the direct encode at `quality`.  `lane_symbols` 0 keeps the source's; `out_version` 0
+/// keeps the version, 3 and 4 may be exchanged.  Version 1 is `InvalidBitstream`.
+pub fn transcode(data: &[u8], quality: u8, lane_symbols: u32, out_version: u8) -> Result<Vec<u8>, CodecError> {
+    let mut n = 0u64;
+    unsafe {
+        let p = alice_codec_transcode(data.as_ptr(), data.len() as u64, quality, lane_symbols, out_version, &mut n);
+        if p.is_null() { Err(last_error(0, data.len(), 0, 0, 0)) } else { Ok(take(p, n)) }
+    }
+}
+
+/// `transcode` at the highest quality in `[min_quality, max_quality]` the byte-budget rule of `encode_split_to_size` finds to
+/// fit `max_bytes`: `(bytes, quality, fits)`.  A version 4 result has no budget: pass `out_version` 3.
+pub fn transcode_to_size(data: &[u8], max_bytes: u64, min_quality: u8, max_quality: u8, lane_symbols: u32, out_version: u8)
+    -> Result<(Vec<u8>, u8, bool), CodecError> {
+    let (mut q, mut fits, mut n) = (0u8, 0u8, 0u64);
+    unsafe {
+        let p = alice_codec_transcode_to_size(data.as_ptr(), data.len() as u64, lane_symbols, out_version, max_bytes, min_quality,
+                                              max_quality, &mut q, &mut fits, &mut n);
+        if p.is_null() { return Err(last_error(0, data.len(), 0, 0, 0)); }
+        Ok((take(p, n), q, fits != 0))
+    }
+}
+
+/// `(lo, hi)`: `lo[q] <= transcode(data, q, lane_symbols, 0).len() <= hi[q]` for the 101 qualities.
+pub fn predict_transcode_sizes(data: &[u8], lane_symbols: u32) -> Result<([u64; 101], [u64; 101]), CodecError> {
+    let (mut lo, mut hi) = ([0u64; 101], [0u64; 101]);
+    let rc = unsafe { alice_codec_predict_transcode_sizes(data.as_ptr(), data.len() as u64, lane_symbols, lo.as_mut_ptr(), hi.as_mut_ptr()) };
+    check(rc, 0, data.len()).map(|_| (lo, hi))
+}
+
+/// `sizes.len()` device containers of one version, wavelet, shape and lane_symbols, chunk `i` at `d_alc + i * alc_stride`, to
+/// `qualities[i]` (`None`: `quality`) at `d_out + i * out_stride`; returns the sizes.
+///
+/// # Safety
+/// `d_alc` holds the chunks and `d_out` room for `sizes.len() * out_stride` bytes on the current device; they do not overlap.
+pub unsafe fn transcode_device(d_alc: *const std::ffi::c_void, alc_stride: u64, sizes: &[u64], quality: u8, qualities: Option<&[u8]>,
+                               lane_symbols: u32, out_version: u8, d_out: *mut std::ffi::c_void, out_stride: u64,
+                               hip_stream: *mut std::ffi::c_void) -> Result<Vec<u64>, CodecError> {
+    if let Some(q) = qualities { if q.len() != sizes.len() { return Err(CodecError::InvalidDimensions { width: 0, height: 0 }); } }
+    let mut out = vec![0u64; sizes.len()];
+    let n = u32::try_from(sizes.len()).unwrap_or(u32::MAX);
+    check(alice_codec_dev_transcode(d_alc, alc_stride, sizes.as_ptr(), n, quality, qualities.map_or(std::ptr::null(), |q| q.as_ptr()),
+                                    lane_symbols, out_version, d_out, out_stride, out.as_mut_ptr(), hip_stream), 0, 0).map(|_| out)
+}
+
+/// `transcode_device` with chunk `i` under `budgets[i]` bytes: `(chosen, fits, sizes)`.
+///
+/// # Safety
+/// As `transcode_device`.
+pub unsafe fn transcode_to_budget_device(d_alc: *const std::ffi::c_void, alc_stride: u64, sizes: &[u64], budgets: &[u64], min_quality: u8,
+                                         max_quality: u8, lane_symbols: u32, out_version: u8, d_out: *mut std::ffi::c_void,
+                                         out_stride: u64, hip_stream: *mut std::ffi::c_void)
+    -> Result<(Vec<u8>, Vec<bool>, Vec<u64>), CodecError> {
+    if budgets.len() != sizes.len() { return Err(CodecError::InvalidDimensions { width: 0, height: 0 }); }
+    let (mut chosen, mut fits, mut out) = (vec![0u8; sizes.len()], vec![0u8; sizes.len()], vec![0u64; sizes.len()]);
+    let n = u32::try_from(sizes.len()).unwrap_or(u32::MAX);
+    check(alice_codec_dev_transcode_to_budget(d_alc, alc_stride, sizes.as_ptr(), n, lane_symbols, out_version, budgets.as_ptr(), min_quality,
+                                              max_quality, chosen.as_mut_ptr(), fits.as_mut_ptr(), d_out, out_stride, out.as_mut_ptr(),
+                                              hip_stream), 0, 0)?;
+    Ok((chosen, fits.into_iter().map(|v| v != 0).collect(), out))
+}
+
+/// Stage call: the map alone.  `n` device symbols (u8; `wide`: u16) from `d_src` to `d_dst` through the transcode map of the
+/// quantiser steps `(step_from, step_to)`; the histogram of the coded symbols is added to the 256 u32 at `d_hist` when not null.
+///
+/// # Safety
+/// `d_src` and `d_dst` hold `n` symbols on the current device and are the same address or do not overlap.
+pub unsafe fn requant_symbols_device(d_src: *const std::ffi::c_void, d_dst: *mut std::ffi::c_void, n: u64, wide: bool, step_from: i32,
+                                     step_to: i32, d_hist: *mut std::ffi::c_void, hip_stream: *mut std::ffi::c_void)
+    -> Result<(), CodecError> {
+    check(alice_codec_dev_requant_symbols(d_src, d_dst, n, wide as c_int, step_from, step_to, d_hist, hip_stream), 0, 0)
+}

@@ -853,6 +853,65 @@ int alice_codec_dev_decode_rects(const alice_codec_rect_item *items, uint32_t n_
  * items' planned blocks go up, once.  offsets (n_items + 1 entries) is left alone on a refusal. */
 uint8_t *alice_codec_decode_rects(const alice_codec_rect_item *items, uint32_t n_items, uint64_t *offsets, uint32_t *bad_item);
 
+/* ---- Transcode of a version 2, 3 or 4 chunk to a lower quality or a byte budget, without pixels ----
+ * The header stores the quantiser step per channel, a symbol is a function of the quantised coefficient alone and the
+ * transform does not depend on the quality, so a chunk at a coarser step is made from the symbols: lane decode, a map of
+ * every symbol, histogram and table, lane encode.  No transform runs.  Per channel, with s1 the step in the header and
+ * s2 = the step of `quality` (64 - quality * 63 / 100, at least 1; qualities above 100 act as 100):
+ *   s2 <= s1: the channel is untouched -- its symbols, its step and its dead zone stay.  A transcode never refuses because the
+ *             target is not coarser; (90 -> 89), which share a step, and (60 -> 90) give the source's bytes back.
+ *   s2 >  s1: q1 = the coefficient the container's decoder makes of the symbol; m = 0 for q1 = 0, else
+ *             sign(q1) * (|q1| * s1 + s1 / 2 + s1 / 2) (integer divisions: the centre of the values the encoder's quantiser
+ *             sends to q1; the stored dead zone is not consulted); q2 = the encoder's quantiser of m at step and dead zone
+ *             s2; the symbol is the container's of q2, and the channel's step and dead zone become s2.
+ * |q2| <= |q1|: no escape appears that was not there.  From a step-1 source (quality 100) m is the coefficient itself, so the
+ * result is byte for byte the direct encode at `quality`; otherwise it is close to it, not equal.  The
+ * output is an ordinary container: the table is the normalised histogram of the new symbols, as every encoder writes it,
+ * and the existing decode calls read it.
+ * lane_symbols: 0 keeps the source's; otherwise a power of two in the version's range (the chunk is laned again), else
+ * ALICE_ERR_INVALID_DIMENSIONS.  out_version: 0 keeps the version; 3 or 4 for a version 3 or 4 source (only the version byte
+ * differs, hence which inverse a decoder runs); every other combination is ALICE_ERR_INVALID_DIMENSIONS.
+ * Validation, its order and its codes are alice_codec_decode_frames' for the container (version 1: "no random access"),
+ * then lane_symbols, out_version, (budget calls) min_q > max_q and a version 4 result -- a byte budget searches the
+ * quality, which version 4 does not have: ALICE_ERR_INVALID_BITSTREAM, ask for out_version = 3 -- all on the host, before a
+ * device is looked for.  INTEGRITY: every block is decoded, so every lane end check runs; a directory that does not add up
+ * or a failed lane is ALICE_ERR_INVALID_BITSTREAM and nothing is written.  Memory comes from the library's pool; nothing
+ * goes through the chain hub. */
+/* One container in host memory -> the transcoded container (free with alice_codec_data_free64), NULL on error. */
+uint8_t *alice_codec_transcode(const uint8_t *data, uint64_t len, uint8_t quality, uint32_t lane_symbols, uint8_t out_version,
+                               uint64_t *out_len);
+/* The same at the quality the version 2 / 3 budget rule chooses for max_bytes (alice_codec_encode_split_to_size: q0 from
+ * the brackets below, at most ALICE_SPLIT_REFINE_TRIALS exact trials; a trial maps the decoded symbols, which stay on the
+ * device, into a scratch copy and runs the table and the count pass).  The bytes are exactly alice_codec_transcode's at
+ * *chosen_q; *fits = 0: not even min_q fits, the chunk at min_q is returned. */
+uint8_t *alice_codec_transcode_to_size(const uint8_t *data, uint64_t len, uint32_t lane_symbols, uint8_t out_version, uint64_t max_bytes,
+                                       uint8_t min_q, uint8_t max_q, uint8_t *chosen_q, uint8_t *fits, uint64_t *out_len);
+/* lo[q] <= the size of alice_codec_transcode(data, len, q, lane_symbols, 0) <= hi[q] for the 101 qualities, from one decode,
+ * one pass over the symbols and the encoders' fold and cost kernels.  At a step that leaves a channel untouched the
+ * channel's bracket is that of its own histogram. */
+int alice_codec_predict_transcode_sizes(const uint8_t *data, uint64_t len, uint32_t lane_symbols, uint64_t lo[101], uint64_t hi[101]);
+/* n_chunks containers on the device, chunk i of sizes[i] bytes at d_alc + i * alc_stride (any byte alignment), that agree
+ * in version, wavelet, shape and lane_symbols (else ALICE_ERR_INVALID_DIMENSIONS; a chunk without pixels likewise) -> chunk
+ * i at qualities[i] (NULL: `quality` for all) at d_out + i * out_stride, its size in out_sizes[i].  The output must not
+ * overlap the input.  The headers are read back first.  The chunks are worked on in groups (at most 4 GiB of symbols); a
+ * chunk that needs more than out_stride bytes is ALICE_ERR_INVALID_BUFFER_SIZE before anything of its group is written, and
+ * damage likewise.  Finished on return. */
+int alice_codec_dev_transcode(const void *d_alc, uint64_t alc_stride, const uint64_t *sizes, uint32_t n_chunks, uint8_t quality,
+                              const uint8_t *qualities, uint32_t lane_symbols, uint8_t out_version, void *d_out, uint64_t out_stride,
+                              uint64_t *out_sizes, void *hip_stream);
+/* The budget form: chunk i under budgets[i] bytes, by the rule of alice_codec_transcode_to_size.  chosen, fits and out_sizes
+ * are written only when the call succeeds. */
+int alice_codec_dev_transcode_to_budget(const void *d_alc, uint64_t alc_stride, const uint64_t *sizes, uint32_t n_chunks,
+                                        uint32_t lane_symbols, uint8_t out_version, const uint64_t *budgets, uint8_t min_q, uint8_t max_q,
+                                        uint8_t *chosen, uint8_t *fits, void *d_out, uint64_t out_stride, uint64_t *out_sizes,
+                                        void *hip_stream);
+/* Stage call: the map alone.  n symbols (u8; wide != 0: u16 at even addresses) from d_src to d_dst on the device -- the same
+ * address (in place) or buffers that do not overlap, any alignment of the element type -- through the map of (step_from,
+ * step_to), both in 1..64 (else ALICE_ERR_INVALID_QUANT_STEP); step_to <= step_from copies.  d_hist (256 u32 on the device,
+ * or NULL): the histogram of the coded symbols written (wide: min(z, 255)) is ADDED to it.  Finished on return. */
+int alice_codec_dev_requant_symbols(const void *d_src, void *d_dst, uint64_t n, int wide, int32_t step_from, int32_t step_to,
+                                    void *d_hist, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1089,4 +1089,70 @@ inline PsnrChoices wide_encode_to_psnr_device(const void* d_frames, uint32_t w, 
                                          max_quality, lane_symbols, frame_width, frame_height, origins, hip_stream);
 }
 
+// ---- transcode of a version 2, 3 or 4 chunk to a lower quality or a byte budget, without pixels ----
+// The chunk at `quality` from its symbols alone: a channel whose step is already at or above the target's is untouched, so a
+// quality at or above the source's returns the source's bytes; from a quality-100 source the result is the direct encode's.
+// lane_symbols 0 keeps the source's; out_version 0 keeps the version, 3 and 4 may be exchanged.
+inline std::vector<uint8_t> transcode(const uint8_t* data, uint64_t len, uint8_t quality, uint32_t lane_symbols = 0, uint8_t out_version = 0) {
+    static const uint8_t empty = 0;
+    uint64_t n = 0;
+    uint8_t* p = alice_codec_transcode(data ? data : &empty, data ? len : 0, quality, lane_symbols, out_version, &n);
+    if (!p) detail::raise(ALICE_ERR_INVALID_BITSTREAM);
+    return detail::take(p, n);
+}
+inline std::vector<uint8_t> transcode(const std::vector<uint8_t>& data, uint8_t quality, uint32_t lane_symbols = 0, uint8_t out_version = 0) {
+    return transcode(data.empty() ? nullptr : data.data(), data.size(), quality, lane_symbols, out_version);
+}
+// at the quality the version 2 / 3 budget rule picks for max_bytes; the bytes are transcode's at that quality
+inline SizedSplit transcode_to_size(const std::vector<uint8_t>& data, uint64_t max_bytes, uint8_t min_quality = 10, uint8_t max_quality = 95,
+                                    uint32_t lane_symbols = 0, uint8_t out_version = 0) {
+    static const uint8_t empty = 0;
+    uint8_t q = 0, fits = 0;
+    uint64_t n = 0;
+    uint8_t* p = alice_codec_transcode_to_size(data.empty() ? &empty : data.data(), data.size(), lane_symbols, out_version, max_bytes,
+                                               min_quality, max_quality, &q, &fits, &n);
+    if (!p) detail::raise(ALICE_ERR_INVALID_BITSTREAM);
+    return SizedSplit{detail::take(p, n), q, fits != 0};
+}
+// lo[q] <= transcode(data, q, lane_symbols).size() <= hi[q]; status is always bounded
+inline SizePrediction predict_transcode_sizes(const std::vector<uint8_t>& data, uint32_t lane_symbols = 0) {
+    static const uint8_t empty = 0;
+    SizePrediction p;
+    detail::check(alice_codec_predict_transcode_sizes(data.empty() ? &empty : data.data(), data.size(), lane_symbols, p.lo.data(), p.hi.data()));
+    return p;
+}
+// sizes.size() device containers of one version, wavelet, shape and lane_symbols, chunk i at d_alc + i * alc_stride -> chunk i at
+// qualities[i] (empty: `quality`) at d_out + i * out_stride; returns the sizes
+inline std::vector<uint64_t> transcode_device(const void* d_alc, uint64_t alc_stride, const std::vector<uint64_t>& sizes, uint8_t quality,
+                                              void* d_out, uint64_t out_stride, const std::vector<uint8_t>& qualities = {},
+                                              uint32_t lane_symbols = 0, uint8_t out_version = 0, void* hip_stream = nullptr) {
+    if (!qualities.empty() && qualities.size() != sizes.size()) throw std::invalid_argument("one quality per chunk");
+    std::vector<uint64_t> out(sizes.size(), 0);
+    static const uint64_t none = 0;
+    detail::check(alice_codec_dev_transcode(d_alc, alc_stride, sizes.empty() ? &none : sizes.data(), (uint32_t)std::min<size_t>(sizes.size(), 0xFFFFFFFFu),
+                                            quality, qualities.empty() ? nullptr : qualities.data(), lane_symbols, out_version, d_out, out_stride,
+                                            out.empty() ? nullptr : out.data(), hip_stream));
+    return out;
+}
+struct TranscodeChoices { std::vector<uint8_t> chosen, fits; std::vector<uint64_t> sizes; };
+inline TranscodeChoices transcode_to_budget_device(const void* d_alc, uint64_t alc_stride, const std::vector<uint64_t>& sizes,
+                                                   const std::vector<uint64_t>& budgets, void* d_out, uint64_t out_stride, uint8_t min_quality = 10,
+                                                   uint8_t max_quality = 95, uint32_t lane_symbols = 0, uint8_t out_version = 0,
+                                                   void* hip_stream = nullptr) {
+    if (budgets.size() != sizes.size()) throw std::invalid_argument("one budget per chunk");
+    TranscodeChoices c{std::vector<uint8_t>(sizes.size(), 0), std::vector<uint8_t>(sizes.size(), 0), std::vector<uint64_t>(sizes.size(), 0)};
+    static const uint64_t none = 0;
+    detail::check(alice_codec_dev_transcode_to_budget(d_alc, alc_stride, sizes.empty() ? &none : sizes.data(),
+                                                      (uint32_t)std::min<size_t>(sizes.size(), 0xFFFFFFFFu), lane_symbols, out_version,
+                                                      budgets.empty() ? &none : budgets.data(), min_quality, max_quality,
+                                                      c.chosen.empty() ? nullptr : c.chosen.data(), c.fits.empty() ? nullptr : c.fits.data(), d_out,
+                                                      out_stride, c.sizes.empty() ? nullptr : c.sizes.data(), hip_stream));
+    return c;
+}
+// stage call: the map alone, n device symbols (u8; wide: u16) from d_src to d_dst (the same address, or no overlap)
+inline void requant_symbols_device(const void* d_src, void* d_dst, uint64_t n, bool wide, int32_t step_from, int32_t step_to,
+                                   void* d_hist = nullptr, void* hip_stream = nullptr) {
+    detail::check(alice_codec_dev_requant_symbols(d_src, d_dst, n, wide ? 1 : 0, step_from, step_to, d_hist, hip_stream));
+}
+
 }  // namespace alice_codec

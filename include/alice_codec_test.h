@@ -196,6 +196,14 @@ void alice_codec_test_last_rects_stats(uint64_t out[11]);
  * refused with its index too. */
 int alice_codec_test_rects_outputs_disjoint(const alice_codec_rect_item *items, uint32_t n_items, uint32_t *bad_item);
 
+/* The bins kernel of the transcode's size prediction (csrc/transcode.hip, symbol_bins_kernel), which no public call reaches
+ * on data of the caller's choice: n device symbols (u8; wide != 0: u16 at an even address) of a channel whose step is
+ * step_from (1..64) -> the value m the map quantises is counted into d_bins[m + r] (4096 u32 on the device,
+ * ADDED to) for m in [-r, r), r the value table's radius, and every other symbol into *d_oor (one u32, added to).
+ * Finished on return.  The budget transcodes report their trials through alice_codec_test_last_split_trials. */
+int alice_codec_test_symbol_bins(const void *d_symbols, uint64_t n, int wide, int32_t step_from, void *d_bins, void *d_oor,
+                                 void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
