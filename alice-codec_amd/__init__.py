@@ -336,6 +336,9 @@ def load_library() -> C.CDLL:
                                             C.c_double, C.c_uint8, C.c_uint8, _u8p, _u8p, C.POINTER(C.c_double), _u64p]),
         "alice_codec_test_last_quality_trials": (C.c_uint32, [_u32p, C.c_uint32]),
         "alice_codec_test_inverse_scratch_bytes": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]),
+        "alice_codec_test_group_scratch_bytes": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int]),
+        "alice_codec_test_set_group_chunks": (None, [C.c_uint32]),
+        "alice_codec_test_group_chunks": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]),
         "alice_codec_test_sq_diff_sum": (C.c_int, [vp, vp, C.c_uint64, _u64p, vp]),
         "alice_codec_test_inverse_variant": (C.c_int, [C.c_uint8, _i32p, C.c_int]),
         "alice_codec_frames_window": (C.c_int, [C.c_uint8, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, _u32p]),

@@ -479,8 +479,24 @@ struct HubTicket {
 // device memory of an encode / a decode of n chunks of shape d (inputs or pixels, symbols, .alc at a byte per symbol, the
 // transform scratch): the figure admission works with
 size_t encode_device_bytes(const ChunkDims& d, uint64_t n) { return (size_t)(n * (d.n_pixels * 3 + d.padded * 6) + forward_scratch_bytes(d)); }
+// Band slot of a decode group whose chunks share one ring: every chunk's inverse plans its bands by its OWN sample width
+// (launch_inverse_transform*: plan_bands at 2 or 4 bytes), the two plans cut a chunk differently, and either slot can be the
+// larger (256 x 256 x 16 at a 4 MiB target: i16 6 291 712, i32 3 539 200).  any16 / any32: which widths occur in the group.
+// A group of one width gets exactly that width's slot.
+size_t group_scratch_bytes(const ChunkDims& d, bool any16, bool any32) {
+    if (any16 && any32) return std::max(inverse_scratch_bytes(d, true), inverse_scratch_bytes(d, false));
+    return inverse_scratch_bytes(d, !any32);
+}
 size_t decode_device_bytes(const ChunkDims& d, uint64_t n, uint64_t payload) {
-    return (size_t)(n * (d.n_pixels * 3 + d.padded * 3) + payload + inverse_scratch_bytes(d, false));
+    return (size_t)(n * (d.n_pixels * 3 + d.padded * 3) + payload + group_scratch_bytes(d, true, true));
+}
+
+// alice_codec_test_set_group_chunks: cap on the chunks a call works on at a time (split_group, chunks_that_fit); 0 = none.
+// Host side only, read at call time.
+static std::atomic<uint32_t> g_group_chunks_cap{0};
+inline uint32_t cap_group(uint32_t n) {
+    const uint32_t cap = g_group_chunks_cap.load(std::memory_order_relaxed);
+    return cap && cap < n ? cap : n;
 }
 
 // Large device-to-host copies into the caller's pageable memory.  hipMemcpyAsync to pageable memory goes through the
@@ -1155,12 +1171,12 @@ int decode_launch(const EncodedChunk* const* headers, const std::vector<const ui
     if (transform_tiles_eligible(d)) {
         // band slots: i16 when every chunk's bound allows it, else i32 (sized before anything is queued: the chunks of
         // a batch share the ring, and growing it must not wait for the chains)
-        bool all16 = true;
+        bool any16 = false, any32 = false;
         for (int b = 0; b < B; ++b) {
             const int32_t step[3] = {headers[b]->ch[0].quant_step, headers[b]->ch[1].quant_step, headers[b]->ch[2].quant_step};
-            all16 = all16 && inverse_bounds(headers[b]->wavelet, step).mid16;
+            (inverse_bounds(headers[b]->wavelet, step).mid16 ? any16 : any32) = true;
         }
-        const size_t need = inverse_scratch_bytes(d, all16);
+        const size_t need = group_scratch_bytes(d, any16, any32);
         if (!w.scratch->p || w.scratch->n < need) {
             HIP_TRY(hipStreamSynchronize(st));   // an earlier call's tail may still use the old ring
             TRY(w.scratch->alloc(need));
@@ -1240,13 +1256,13 @@ int validate_for_decode(const EncodedChunk& c, ChunkDims* dims, uint64_t payload
 uint32_t chunks_that_fit(const ChunkDims& d, uint32_t want) {
     if (want <= 1) return want;
     size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return want; }
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return cap_group(want); }
     const long double per_chunk = (long double)d.n_pixels * 3 + (long double)d.padded * 3 * 2 + 3.0L * sizeof(RansTable) * 2 + 65536;
-    const long double fixed = (long double)std::max(forward_scratch_bytes(d), inverse_scratch_bytes(d, false)) + (64u << 20);
+    const long double fixed = (long double)std::max(forward_scratch_bytes(d), group_scratch_bytes(d, true, true)) + (64u << 20);
     const long double room = (long double)free_b * 0.8L - fixed;
     if (room < per_chunk) return 1;
     const long double n = room / per_chunk;
-    return n >= (long double)want ? want : (uint32_t)n;
+    return cap_group(n >= (long double)want ? want : (uint32_t)n);
 }
 
 // The n_chunks encoded chunks of w (chain results res) as chunk objects: chunk i's object goes to slot(i) (left for the
@@ -3707,13 +3723,13 @@ int split_decode_chunks(const SplitHeader* hdr, const uint8_t* const* d_alc, uin
     SplitWork w;
     TRY(split_work_alloc(w, (int)(3 * B), d.padded, hdr[0].lane_symbols, false, fmt));
     std::vector<uint16_t> freq((size_t)B * 3 * 256);
-    bool all16 = true;
+    bool any16 = false, any32 = false;
     for (uint32_t i = 0; i < B; ++i) {
         split_chunk_jobs(w, 3 * (size_t)i, hdr[i], d_alc[i], dw.sym.as<uint8_t>() + 3 * (size_t)i * d.padded * sb, d.padded * sb);
         memcpy(&freq[3 * (size_t)i * 256], hdr[i].freq, 3 * 256 * sizeof(uint16_t));
-        all16 = all16 && inverse_bounds(hdr[i].wavelet, hdr[i].step, wide ? kWideMaxQ : kByteMaxQ).mid16;
+        (inverse_bounds(hdr[i].wavelet, hdr[i].step, wide ? kWideMaxQ : kByteMaxQ).mid16 ? any16 : any32) = true;
     }
-    if (transform_tiles_eligible(d)) TRY(dw.scratch_own.alloc(inverse_scratch_bytes(d, all16)));
+    if (transform_tiles_eligible(d)) TRY(dw.scratch_own.alloc(group_scratch_bytes(d, any16, any32)));
     TRY(split_decode_launch(w, freq.data(), st));
     for (uint32_t i = 0; i < B; ++i)
         TRY(inverse_chunk(dw.sym.as<uint8_t>() + (size_t)i * 3 * d.padded * sb, d, hdr[i].wavelet, hdr[i].step, dw.scratch_own.p, dw, rgb[i], st, fmt));
@@ -3727,7 +3743,7 @@ int split_decode_chunks(const SplitHeader* hdr, const uint8_t* const* d_alc, uin
 uint32_t split_group(const ChunkDims& d, SplitFormat fmt = kFormatSplit) {
     const uint64_t per_chunk = 3 * d.padded * (is_wide(fmt) ? 2 : 1);
     const uint64_t g = (uint64_t(4) << 30) / (per_chunk ? per_chunk : 1);
-    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(g, 1), 21845);
+    return cap_group((uint32_t)std::min<uint64_t>(std::max<uint64_t>(g, 1), 21845));
 }
 
 void write_empty_split(uint8_t* p, uint8_t wavelet, uint32_t w, uint32_t h, uint32_t f, uint32_t L, int32_t step, uint8_t version = 2) {
@@ -4818,6 +4834,22 @@ uint64_t alice_codec_test_inverse_scratch_bytes(uint32_t width, uint32_t height,
     ChunkDims d{};
     if (chunk_dims(width, height, frames, &d) != kOk || !transform_tiles_eligible(d)) return 0;
     return inverse_scratch_bytes(d, mid16 != 0);
+}
+
+uint64_t alice_codec_test_group_scratch_bytes(uint32_t width, uint32_t height, uint32_t frames, int any16, int any32) {
+    clear_error();
+    ChunkDims d{};
+    if (chunk_dims(width, height, frames, &d) != kOk || !transform_tiles_eligible(d)) return 0;
+    return group_scratch_bytes(d, any16 != 0, any32 != 0);
+}
+
+void alice_codec_test_set_group_chunks(uint32_t max_chunks) { g_group_chunks_cap.store(max_chunks, std::memory_order_relaxed); }
+
+uint32_t alice_codec_test_group_chunks(uint32_t width, uint32_t height, uint32_t frames, int format) {
+    clear_error();
+    ChunkDims d{};
+    if (format < 2 || format > 4 || chunk_dims(width, height, frames, &d) != kOk) return 0;
+    return split_group(d, format_of_version(format));
 }
 
 int alice_codec_test_sq_diff_sum(const void* d_a, const void* d_b, uint64_t n, uint64_t* sse, void* hip_stream) {

@@ -155,6 +155,24 @@ uint32_t alice_codec_test_last_quality_trials(uint32_t *per_chunk, uint32_t cap)
  * the larger.  No device needed. */
 uint64_t alice_codec_test_inverse_scratch_bytes(uint32_t width, uint32_t height, uint32_t frames, int mid16);
 
+/* Bytes of the band slot one decode group allocates for chunks of this shape under the current band target (csrc/codec.hip,
+ * group_scratch_bytes): every chunk of the group plans its bands by its own sample width into the one slot, so a group that
+ * holds both widths (any16 != 0 and any32 != 0) gets the larger of the two plans' slots, a group of one width exactly
+ * alice_codec_test_inverse_scratch_bytes of that width (neither flag: the i16 slot, as for an empty group); 0 for a shape the
+ * tile kernels do not cover.  No device needed. */
+uint64_t alice_codec_test_group_scratch_bytes(uint32_t width, uint32_t height, uint32_t frames, int any16, int any32);
+
+/* Cap on the chunks a call works on at a time, process-wide: the groups of the device-resident calls of versions 2-4
+ * (csrc/codec.hip, split_group: 4 GiB of symbols) and the passes of the version 1 host calls (chunks_that_fit) hold at most
+ * max_chunks chunks; never fewer than 1, never more than they compute themselves.  0 restores the default.  Read at call time
+ * on the host; no kernel knows about it.  The suite lowers it so that a call of seven small chunks already takes several
+ * groups with a ragged last one; results never depend on it. */
+void alice_codec_test_set_group_chunks(uint32_t max_chunks);
+
+/* The group size a device-resident call of this shape in this format (2, 3 or 4) would use under the current cap; 0 for
+ * another format or a shape no call accepts.  No device needed. */
+uint32_t alice_codec_test_group_chunks(uint32_t width, uint32_t height, uint32_t frames, int format);
+
 /* The byte-at-a-time squared-error kernel behind alice_codec_psnr (csrc/generic.hip, sq_diff_sum_kernel) on two device
  * buffers of n bytes: *sse (host) = the sum.  For the probes that time it beside alice_codec_dev_rgb_sse. */
 int alice_codec_test_sq_diff_sum(const void *d_a, const void *d_b, uint64_t n, uint64_t *sse, void *hip_stream);
