@@ -369,6 +369,18 @@ def load_library() -> C.CDLL:
                                                           _u8p, _u8p, vp, C.c_uint64, _u64p, vp]),
         "alice_codec_dev_requant_symbols": (C.c_int, [vp, vp, C.c_uint64, C.c_int, C.c_int32, C.c_int32, vp, vp]),
         "alice_codec_test_symbol_bins": (C.c_int, [vp, C.c_uint64, C.c_int, C.c_int32, vp, vp, vp]),
+        "alice_codec_banded_stream_bound": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint8]),
+        "alice_codec_banded_info": (C.c_int, [_u8p, C.c_uint64, vp]),
+        "alice_codec_encode_banded": (vp, [vp, _u8p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint8, _u64p]),
+        "alice_codec_decode_banded": (vp, [_u8p, C.c_uint64, _u64p]),
+        "alice_codec_dev_encode_banded": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint8, _u8p,
+                                                    C.c_uint32, C.c_uint8, vp, C.c_uint64, _u64p, vp]),
+        "alice_codec_dev_decode_banded": (C.c_int, [vp, C.c_uint64, _u64p, C.c_uint32, vp, vp]),
+        "alice_codec_to_banded": (vp, [_u8p, C.c_uint64, C.c_uint32, _u64p]),
+        "alice_codec_from_banded": (vp, [_u8p, C.c_uint64, C.c_uint32, _u64p]),
+        "alice_codec_dev_to_banded": (C.c_int, [vp, C.c_uint64, _u64p, C.c_uint32, C.c_uint32, vp, C.c_uint64, _u64p, vp]),
+        "alice_codec_dev_from_banded": (C.c_int, [vp, C.c_uint64, _u64p, C.c_uint32, C.c_uint32, vp, C.c_uint64, _u64p, vp]),
+        "alice_codec_dev_band_histograms": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
@@ -1962,8 +1974,8 @@ def forward_symbols_wide_device(d_rgb_ptr: int, width: int, height: int, frames:
 
 
 def decode_alc(data) -> np.ndarray:
-    """The RGB bytes of a container of any version: 1 (FrameDecoder), 2 (decode_split), 3 (decode_wide) or
-    4 (decode_reversible)."""
+    """The RGB bytes of a container of any version: 1 (FrameDecoder), 2 (decode_split), 3 (decode_wide),
+    4 (decode_reversible) or 5 (decode_banded)."""
     version = alc_version(data)
     if version == 2:
         return decode_split(data)
@@ -1971,6 +1983,8 @@ def decode_alc(data) -> np.ndarray:
         return decode_wide(data)
     if version == 4:
         return decode_reversible(data)
+    if version == 5:
+        return decode_banded(data)
     return FrameDecoder().decode(EncodedChunk.from_bytes(data))   # version 1, and every refusal the v1 parser words
 
 
@@ -2777,4 +2791,149 @@ def requant_symbols_device(d_src_ptr: int, d_dst_ptr: int, n: int, wide: bool, s
     if not (-(1 << 31) <= step_from < (1 << 31) and -(1 << 31) <= step_to < (1 << 31)):
         raise CodecError(5, "quantiser step out of i32 range")
     _check(load_library().alice_codec_dev_requant_symbols(d_src_ptr or None, d_dst_ptr or None, n, 1 if wide else 0, step_from, step_to,
+                                                          d_hist_ptr or None, stream or None))
+
+
+# ---- banded format (.alc version 5) ----
+# One frequency table per wavelet subband instead of one per channel: the pixels of the base version (2, 3 or 4) in fewer
+# bytes at chunk sizes (the 12 636-byte header makes thumbnails larger).  Frame ranges, previews, rectangles, budgets and
+# transcodes stay with the base versions: from_banded gives the base chunk back byte for byte.
+
+BANDED_HEADER_BYTES = 12636
+
+
+class _CBandedInfo(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("frames", C.c_uint32), ("lane_symbols", C.c_uint32),
+                ("wavelet", C.c_uint8), ("base", C.c_uint8), ("reserved", C.c_uint8 * 2),
+                ("quant_step", C.c_int32 * 3), ("dead_zone", C.c_int32 * 3), ("num_symbols", C.c_uint32 * 3),
+                ("n_blocks", C.c_uint32 * 24), ("payload_len", C.c_uint64 * 24)]
+
+
+class BandedInfo:
+    """The header fields of a version 5 container (alice_codec_banded_info: validated, no device needed).  n_blocks and
+    payload_len have 24 entries: channel-major, band k = 4 bt + 2 by + bx ascending inside a channel."""
+
+    def __init__(self, c: _CBandedInfo):
+        self.width, self.height, self.frames = int(c.width), int(c.height), int(c.frames)
+        self.lane_symbols = int(c.lane_symbols)
+        self.wavelet_type = WaveletType(int(c.wavelet))
+        self.base = int(c.base)
+        self.quant_step = [int(v) for v in c.quant_step]
+        self.dead_zone = [int(v) for v in c.dead_zone]
+        self.num_symbols = [int(v) for v in c.num_symbols]
+        self.n_blocks = [int(v) for v in c.n_blocks]
+        self.payload_len = [int(v) for v in c.payload_len]
+
+    def __repr__(self):
+        return (f"BandedInfo({self.width}x{self.height}x{self.frames}, {self.wavelet_type.name}, base={self.base}, "
+                f"lane_symbols={self.lane_symbols}, steps={self.quant_step}, payload={self.payload_len})")
+
+
+def banded_info(data) -> BandedInfo:
+    buf = _as_u8(data)
+    c = _CBandedInfo()
+    _check(load_library().alice_codec_banded_info(_p(buf, _u8p), buf.size, C.byref(c)))
+    return BandedInfo(c)
+
+
+def banded_stream_bound(n_band: int, lane_symbols: int = SPLIT_DEFAULT_LANE_SYMBOLS, base: int = 2) -> int:
+    return int(load_library().alice_codec_banded_stream_bound(n_band, lane_symbols, _u8_arg(base, "base")))
+
+
+def _banded_bytes(ptr, n) -> bytes:
+    lib = load_library()
+    if not ptr:
+        _raise_last()
+    try:
+        return _copy_out(ptr, n.value).tobytes()
+    finally:
+        lib.alice_codec_data_free64(ptr, n.value)
+
+
+def encode_banded(encoder: "FrameEncoder", rgb_frames, width: int, height: int, frames: int, lane_symbols: int = 0, base: int = 2) -> bytes:
+    """One chunk as version 5 bytes of `base` (2: u8 symbols, 3: wide symbols, 4: wide symbols and the mirrored inverse), with
+    the encoder's wavelet and quality.  It decodes to the pixels of the base version's chunk."""
+    lib = load_library()
+    buf = _as_u8(rgb_frames)
+    _dims_u32(width, height, frames, lane_symbols)
+    n = C.c_uint64(0)
+    src = _p(buf, _u8p) if buf.size else C.cast(C.c_char_p(b""), _u8p)
+    return _banded_bytes(lib.alice_codec_encode_banded(encoder._h, src, buf.size, width, height, frames, lane_symbols, _u8_arg(base, "base"),
+                                                       C.byref(n)), n)
+
+
+def decode_banded(data) -> np.ndarray:
+    """The RGB bytes of a version 5 container."""
+    lib = load_library()
+    buf = _as_u8(data)
+    n = C.c_uint64(0)
+    ptr = lib.alice_codec_decode_banded(_p(buf, _u8p), buf.size, C.byref(n))
+    if not ptr:
+        _raise_last()
+    return _adopt(ptr, n.value, lib.alice_codec_data_free64)
+
+
+def to_banded(data, lane_symbols: int = 0) -> bytes:
+    """A version 2, 3 or 4 container as the version 5 container of that base, from its symbols alone (no transform runs):
+    byte for byte what encode_banded makes of the same input.  lane_symbols 0 keeps the source's."""
+    buf = _as_u8(data)
+    _dims_u32(lane_symbols)
+    n = C.c_uint64(0)
+    return _banded_bytes(load_library().alice_codec_to_banded(_p(buf, _u8p), buf.size, lane_symbols, C.byref(n)), n)
+
+
+def from_banded(data, lane_symbols: int = 0) -> bytes:
+    """A version 5 container as the container of its base version: from_banded(to_banded(x)) == x."""
+    buf = _as_u8(data)
+    _dims_u32(lane_symbols)
+    n = C.c_uint64(0)
+    return _banded_bytes(load_library().alice_codec_from_banded(_p(buf, _u8p), buf.size, lane_symbols, C.byref(n)), n)
+
+
+def banded_encode_device(d_rgb_ptr: int, width: int, height: int, frames: int, n_chunks: int, wavelet_type: WaveletType,
+                         quality: int, d_out_ptr: int, out_stride: int, qualities=None, lane_symbols: int = 0, base: int = 2,
+                         stream: int = 0) -> np.ndarray:
+    """n_chunks packed device chunks -> version 5 bytes of `base` at d_out_ptr + i * out_stride; returns the sizes."""
+    sizes = np.zeros(n_chunks, np.uint64)
+    q = None if qualities is None else np.ascontiguousarray(qualities, dtype=np.uint8).reshape(-1)
+    if q is not None and q.size != n_chunks:
+        raise ValueError("one quality per chunk")
+    _dims_u32(width, height, frames, n_chunks, lane_symbols)
+    _check(load_library().alice_codec_dev_encode_banded(d_rgb_ptr, width, height, frames, n_chunks, int(wavelet_type), quality,
+                                                        None if q is None else _p(q, _u8p), lane_symbols, _u8_arg(base, "base"),
+                                                        d_out_ptr, out_stride, _p(sizes, _u64p), stream or None))
+    return sizes
+
+
+def banded_decode_device(d_alc_ptr: int, alc_stride: int, sizes, d_rgb_out_ptr: int, stream: int = 0) -> None:
+    s = np.ascontiguousarray(sizes, dtype=np.uint64).reshape(-1)
+    _check(load_library().alice_codec_dev_decode_banded(d_alc_ptr, alc_stride, _p(s, _u64p), s.size, d_rgb_out_ptr, stream or None))
+
+
+def _repack_device(fn: str, d_alc_ptr: int, alc_stride: int, sizes, d_out_ptr: int, out_stride: int, lane_symbols: int, stream: int):
+    s = np.ascontiguousarray(sizes, dtype=np.uint64).reshape(-1)
+    _dims_u32(lane_symbols)
+    out = np.zeros(s.size, np.uint64)
+    _check(getattr(load_library(), fn)(d_alc_ptr, alc_stride, _p(s, _u64p), s.size, lane_symbols, d_out_ptr, out_stride, _p(out, _u64p),
+                                       stream or None))
+    return out
+
+
+def to_banded_device(d_alc_ptr: int, alc_stride: int, sizes, d_out_ptr: int, out_stride: int, lane_symbols: int = 0,
+                     stream: int = 0) -> np.ndarray:
+    """len(sizes) device containers of one version (2, 3 or 4), wavelet, shape and lane_symbols -> their version 5 twins at
+    d_out_ptr + i * out_stride; returns the sizes."""
+    return _repack_device("alice_codec_dev_to_banded", d_alc_ptr, alc_stride, sizes, d_out_ptr, out_stride, lane_symbols, stream)
+
+
+def from_banded_device(d_alc_ptr: int, alc_stride: int, sizes, d_out_ptr: int, out_stride: int, lane_symbols: int = 0,
+                       stream: int = 0) -> np.ndarray:
+    """len(sizes) version 5 device containers of one base, wavelet, shape and lane_symbols -> their base chunks."""
+    return _repack_device("alice_codec_dev_from_banded", d_alc_ptr, alc_stride, sizes, d_out_ptr, out_stride, lane_symbols, stream)
+
+
+def band_histograms_device(d_symbols_ptr: int, width: int, height: int, frames: int, wide: bool, d_hist_ptr: int, stream: int = 0) -> None:
+    """Stage call: the 3 x 8 x 256 u32 band histograms (wide: of min(z, 255)) of one chunk's 3 * padded device symbols."""
+    _dims_u32(width, height, frames)
+    _check(load_library().alice_codec_dev_band_histograms(d_symbols_ptr or None, width, height, frames, 1 if wide else 0,
                                                           d_hist_ptr or None, stream or None))

@@ -30,6 +30,13 @@ items over mapped files; inputs whose output sizes differ
 writes a version 2, 3 or 4 file again at a lower quality or under a byte budget, from its symbols alone (DESIGN.md section
 19): no pixels, no transform.  A quality at or above the file's returns its bytes; `--to-version` 3 or 4 exchanges the two
 wide versions; a version 4 result has no byte budget (ask for `--to-version 3`); version 1 is refused.
+`--banded` (encode and encode-chunks, beside `--format split|wide|reversible` or `--lossless`) writes the banded container
+(.alc version 5, DESIGN.md section 20: one frequency table per wavelet subband, the pixels of the named format in fewer bytes
+at chunk sizes); it is refused with the default format, `--max-bytes`, `--kbps` and `--min-psnr`, which version 5 does not
+have: encode the base format and `repack` it.
+`repack IN -o OUT (--banded | --plain) [--lane-symbols L]` turns a version 2, 3 or 4 file into its version 5 twin or back,
+byte for byte what the encoders write, from the symbols alone.  `decode --frames / --rect / --preview`, `thumbnails`,
+`extract` and `transcode` refuse a version 5 file with the library's message: `repack --plain` it first.
 Like the reference it treats the whole input file as ONE chunk (src/bin/main.rs:117-122).  `encode-chunks`
 is the extension SURVEY.md section 8f asks for: it cuts a long raw-RGB file into 64-frame chunks
 (DEFAULT_CHUNK_SIZE, src/lib.rs:110) and writes one .alc per chunk."""
@@ -41,7 +48,7 @@ import sys
 import numpy as np
 
 from . import (DEFAULT_CHUNK_SIZE, PREVIEWS_MAX_ITEMS, RECTS_MAX_ITEMS, CodecError, EncodedChunk, FrameDecoder, FrameEncoder, WaveletType, budget_bytes_per_chunk,
-               alc_version, decode_frames, decode_preview, decode_previews, decode_rect, decode_rects, decode_reversible, decode_split, decode_wide, encode_many, encode_reversible, encode_split,
+               alc_version, banded_info, decode_banded, encode_banded, from_banded, to_banded, decode_frames, decode_preview, decode_previews, decode_rect, decode_rects, decode_reversible, decode_split, decode_wide, encode_many, encode_reversible, encode_split,
                encode_split_to_psnr, encode_split_to_size, encode_to_size, encode_wide, encode_wide_to_psnr, reversible_info,
                split_info, transcode, transcode_to_size, wide_info)
 
@@ -63,9 +70,25 @@ NO_WIDE_BUDGET = ("--format wide cannot be combined with {} on the command line 
 NO_REVERSIBLE_BUDGET = ("--format reversible cannot be combined with {}: version 4 is the lossless container (quality 100 has no "
                         "quality to search, and a lossy version 4 is not recommended); use --format wide, split or v1 for a byte budget")
 LOSSLESS_CONFLICT = "--lossless is --format reversible --quality 100: it cannot be combined with {}"
-CONTAINER_INFO = {2: split_info, 3: wide_info, 4: reversible_info}
-CONTAINER_DECODE = {2: decode_split, 3: decode_wide, 4: decode_reversible}
-CONTAINER_NAME = {2: "split-stream (version 2)", 3: "wide split-stream (version 3)", 4: "reversible split-stream (version 4)"}
+CONTAINER_INFO = {2: split_info, 3: wide_info, 4: reversible_info, 5: banded_info}
+CONTAINER_DECODE = {2: decode_split, 3: decode_wide, 4: decode_reversible, 5: decode_banded}
+CONTAINER_NAME = {2: "split-stream (version 2)", 3: "wide split-stream (version 3)", 4: "reversible split-stream (version 4)",
+                  5: "banded split-stream (version 5)"}
+NO_BANDED_V1 = ("--banded needs --format split, wide or reversible (or --lossless): version 5 keeps the symbols of one of them; "
+                "an existing file of those formats becomes banded with `repack --banded`")
+NO_BANDED_RATE = ("--banded cannot be combined with {}: version 5 has no size prediction, byte budget or PSNR floor; encode without "
+                  "--banded and run `repack --banded` on the result")
+
+
+def _check_banded(a, budget_flag: str, budget) -> None:
+    """The refusals of --banded, before the input is read (a.format: after --lossless has been applied; --min-psnr is
+    refused ahead of its own checks, by the callers)."""
+    if not a.banded:
+        return
+    if a.format not in ("split", "wide", "reversible"):
+        raise ValueError(NO_BANDED_V1)
+    if budget is not None:
+        raise ValueError(NO_BANDED_RATE.format(budget_flag))
 
 
 def _apply_lossless(a) -> None:
@@ -119,8 +142,11 @@ def _container_version(a, data) -> int:
 
 def cmd_encode(a) -> None:
     wt = parse_wavelet(a.wavelet)
+    if a.banded and a.min_psnr is not None:
+        raise ValueError(NO_BANDED_RATE.format("--min-psnr"))
     _check_min_psnr(a, "--max-bytes", a.max_bytes)
     _apply_lossless(a)
+    _check_banded(a, "--max-bytes", a.max_bytes)
     a.format = a.format or "v1"
     if a.format == "wide" and a.max_bytes is not None:
         raise ValueError(NO_WIDE_BUDGET.format("--max-bytes"))
@@ -128,6 +154,14 @@ def cmd_encode(a) -> None:
         raise ValueError(NO_REVERSIBLE_BUDGET.format("--max-bytes"))
     rgb = np.fromfile(a.input, dtype=np.uint8)
     quality = a.quality
+    if a.banded:
+        data = encode_banded(FrameEncoder.with_wavelet(a.quality, wt), rgb, a.width, a.height, a.frames, a.lane_symbols, FORMAT_VERSION[a.format])
+        with open(a.output, "wb") as f:
+            f.write(data)
+        ratio = 0.0 if rgb.size == 0 else len(data) / rgb.size
+        print(f"encoded {a.width}x{a.height}x{a.frames} ({rgb.size} bytes) -> {len(data)} bytes "
+              f"({ratio * 100:.1f}% ratio, quality={quality}, wavelet={a.wavelet}, format=banded {a.format})", file=sys.stderr)
+        return
     if a.min_psnr is not None:
         data, quality, reached, line = _encode_to_psnr(a, wt, rgb, a.frames)
         print(line, file=sys.stderr)
@@ -182,8 +216,11 @@ def cmd_encode(a) -> None:
 
 def cmd_encode_chunks(a) -> None:
     wt = parse_wavelet(a.wavelet)
+    if a.banded and a.min_psnr is not None:
+        raise ValueError(NO_BANDED_RATE.format("--min-psnr"))
     _check_min_psnr(a, "--kbps", a.kbps)
     _apply_lossless(a)
+    _check_banded(a, "--kbps", a.kbps)
     a.format = a.format or "v1"
     if a.format == "wide" and a.kbps is not None:
         raise ValueError(NO_WIDE_BUDGET.format("--kbps"))
@@ -209,6 +246,11 @@ def cmd_encode_chunks(a) -> None:
         return
     if a.format in ("split", "wide", "reversible"):   # one chunk uses the whole device: chunk after chunk
         encode_one = {"split": encode_split, "wide": encode_wide, "reversible": encode_reversible}[a.format]
+        if a.banded:
+            base = FORMAT_VERSION[a.format]
+
+            def encode_one(enc, part, width, height, f, lane_symbols):
+                return encode_banded(enc, part, width, height, f, lane_symbols, base)
         for k, s0 in enumerate(starts):
             f = min(a.chunk, n_frames - s0)
             data = encode_one(enc, np.ascontiguousarray(rgb[s0 * frame_bytes:(s0 + f) * frame_bytes]), a.width, a.height, f,
@@ -468,6 +510,18 @@ def cmd_transcode(a) -> None:
           f"lane_symbols {info.lane_symbols})", file=sys.stderr)
 
 
+def cmd_repack(a) -> None:
+    """IN as its version 5 twin (--banded) or a version 5 IN as its base version (--plain), from the symbols alone."""
+    if a.banded == a.plain:
+        raise ValueError("repack wants exactly one of --banded and --plain")
+    data = np.fromfile(a.input, dtype=np.uint8)
+    out = to_banded(data, a.lane_symbols) if a.banded else from_banded(data, a.lane_symbols)
+    with open(a.output, "wb") as f:
+        f.write(out)
+    info = CONTAINER_INFO[out[4]](out)
+    print(f"repacked {data.size} -> {len(out)} bytes ({CONTAINER_NAME[out[4]]}, lane_symbols {info.lane_symbols})", file=sys.stderr)
+
+
 def cmd_info(a) -> None:
     data = np.fromfile(a.input, dtype=np.uint8)
     version = _container_version(a, data)
@@ -484,6 +538,10 @@ def cmd_info(a) -> None:
         print(f"  Frames:      {i.frames}")
         print(f"  Wavelet:     {WAVELET_NAMES[i.wavelet_type]}")
         print(f"  Lane length: {i.lane_symbols} symbols, {sum(i.n_blocks)} blocks")
+        if version == 5:
+            print(f"  Base:        version {i.base}")
+            for c, name in enumerate(("Y", "Co", "Cg")):
+                print(f"  Bands {name + ':':4s}   " + " ".join(str(v) for v in i.payload_len[8 * c:8 * c + 8]) + " bytes")
         print(f"  Payload:     {payload} bytes")
         print(f"  Raw size:    {raw} bytes (uncompressed RGB)")
         print(f"  Ratio:       {0.0 if raw == 0 else payload / raw * 100:.1f}%")
@@ -538,6 +596,9 @@ def main(argv=None) -> int:
                        help="v1 (default): the reference's bitstream; split: .alc version 2; wide: .alc version 3 (untruncated symbols, for "
                             "the top qualities); reversible: .alc version 4 (version 3 with the mirrored inverse: lossless at quality 100)")
         e.add_argument("--lossless", action="store_true", help="short for --format reversible --quality 100")
+        e.add_argument("--banded", action="store_true",
+                       help="with --format split / wide / reversible or --lossless: .alc version 5 of that format (one frequency table per "
+                            "wavelet subband; for chunks, not thumbnails)")
         e.add_argument("--lane-symbols", type=int, default=0,
                        help="--format split / wide / reversible: symbols per lane (power of two in 64..16384, wide and reversible: 64..8192; 0 = default)")
         e.add_argument("--min-quality", type=_u8, default=10)
@@ -573,6 +634,12 @@ def main(argv=None) -> int:
     tr.add_argument("--max-quality", type=_u8, default=95)
     tr.add_argument("--lane-symbols", type=int, default=0, help="lane the chunk again (power of two in the version's range; 0 = keep)")
     tr.add_argument("--to-version", type=_u8, default=0, metavar="V", help="3 or 4 for a version 3 or 4 file (0 = keep)")
+    rp = sub.add_parser("repack", help="a version 2, 3 or 4 file as its banded (version 5) twin, or back, from its symbols alone")
+    rp.add_argument("input")
+    rp.add_argument("-o", "--output", required=True)
+    rp.add_argument("--banded", action="store_true", help="version 2, 3 or 4 -> version 5 of that base")
+    rp.add_argument("--plain", action="store_true", help="version 5 -> its base version, byte for byte")
+    rp.add_argument("--lane-symbols", type=int, default=0, help="lane the chunk again (power of two in the base's range; 0 = keep)")
     i = sub.add_parser("info")
     i.add_argument("input")
     for x in (d, i):
@@ -581,7 +648,7 @@ def main(argv=None) -> int:
     a = p.parse_args(argv)
     try:
         {"encode": cmd_encode, "encode-chunks": cmd_encode_chunks, "decode": cmd_decode, "info": cmd_info,
-         "thumbnails": cmd_thumbnails, "extract": cmd_extract, "transcode": cmd_transcode}[a.command](a)
+         "thumbnails": cmd_thumbnails, "extract": cmd_extract, "transcode": cmd_transcode, "repack": cmd_repack}[a.command](a)
     except (CodecError, ValueError, OSError) as e:
         print(f"error: {e}", file=sys.stderr)
         return 1

@@ -6654,3 +6654,730 @@ int alice_codec_test_symbol_bins(const void* d_symbols, uint64_t n, int wide, in
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// PART 12: banded container (.alc v5; kernels: band.hip)
+//
+// A version 5 chunk names a base version (2, 3 or 4) whose front end, symbols and inverse it keeps; only the entropy stage
+// differs: each of a channel's eight subbands is coded as a channel of the base is, with its own table.  A job is one
+// (chunk, channel, band), so a call of B chunks runs 24 B jobs through one table launch, one count or decode launch and one
+// scan.  The repack goes between a base chunk and its banded twin through the symbols alone.
+// ------------------------------------------------------------------------------------------
+
+namespace {
+
+constexpr uint32_t kBandMaxGroup = 2730;   // 24 jobs per chunk under the grid's 65 535
+
+struct BandHeader {
+    uint32_t width = 0, height = 0, frames = 0, lane_symbols = 0;
+    uint8_t wavelet = 0, base = 2;
+    SplitFormat fmt = kFormatSplit;   // of the base
+    int32_t step[3] = {1, 1, 1}, dead_zone[3] = {1, 1, 1};
+    uint32_t num_symbols[3] = {0, 0, 0}, n_blocks[24] = {};
+    uint64_t payload_len[24] = {};
+    uint16_t freq[24][256] = {};
+};
+
+inline const uint8_t* band_field(const uint8_t* data, int c, int k) {
+    return data + kBandFixedHeaderBytes + (size_t)c * kBandChannelHeaderBytes + 12 + (size_t)k * kBandBandHeaderBytes;
+}
+
+// Header checks in their fixed order; data: at least min(total_len, kBandHeaderBytes) readable bytes of a
+// container of total_len bytes.
+int parse_band_header(const uint8_t* data, uint64_t total_len, BandHeader& h, ChunkDims* d) {
+    if (total_len < kBandFixedHeaderBytes)
+        return fail(kInvalidBitstream, "data too short for the fixed fields: " + std::to_string(total_len) + " bytes (they take " +
+                                           std::to_string(kBandFixedHeaderBytes) + ")");
+    if (memcmp(data, "ALCC", 4) != 0) return fail(kInvalidBitstream, "bad magic (expected ALCC)");
+    if (data[4] != 5) return fail(kInvalidBitstream, "unsupported version: " + std::to_string((int)data[4]) + " (expected 5)");
+    if (data[5] > 2) return fail(kInvalidBitstream, "unknown wavelet type byte: " + std::to_string((int)data[5]));
+    h.wavelet = data[5];
+    h.width = get_u32(data + 6); h.height = get_u32(data + 10); h.frames = get_u32(data + 14);
+    h.lane_symbols = get_u32(data + 18);
+    if (data[22] < 2 || data[22] > 4) return fail(kInvalidBitstream, "unknown base version: " + std::to_string((int)data[22]) + " (2, 3 or 4)");
+    h.base = data[22];
+    h.fmt = format_of_version(h.base);
+    if (data[23] != 0) return fail(kInvalidBitstream, "reserved byte is " + std::to_string((int)data[23]) + ", not 0");
+    if (!split_lane_ok(h.lane_symbols, h.fmt))
+        return fail(kInvalidBitstream, "lane_symbols " + std::to_string(h.lane_symbols) + " is not a power of two in [64, " +
+                                           std::to_string(is_wide(h.fmt) ? kSplitWideMaxLane : kSplitMaxLane) + "]");
+    if (total_len < kBandHeaderBytes)
+        return fail(kInvalidBitstream, "data too short for the header: " + std::to_string(total_len) + " bytes (minimum " + std::to_string(kBandHeaderBytes) + ")");
+    *d = make_dims(h.width, h.height, h.frames);
+    const unsigned __int128 pix = (unsigned __int128)h.width * h.height * h.frames;
+    if (pix > UINT64_MAX / 3) return fail(kInvalidBitstream, "dimensions overflow");
+    const uint64_t padded = pix == 0 ? 0 : d->padded;
+    const uint64_t n_band = padded / 8;
+    uint64_t total = kBandHeaderBytes;
+    for (int c = 0; c < 3; ++c) {
+        const uint8_t* q = data + kBandFixedHeaderBytes + (size_t)c * kBandChannelHeaderBytes;
+        const std::string ch = "channel " + std::to_string(c) + ": ";
+        h.step[c] = (int32_t)get_u32(q); h.dead_zone[c] = (int32_t)get_u32(q + 4);
+        h.num_symbols[c] = get_u32(q + 8);
+        if (h.step[c] < 1 || h.dead_zone[c] < 0)
+            return fail(kInvalidBitstream, ch + "quantiser step " + std::to_string(h.step[c]) + " / dead zone " + std::to_string(h.dead_zone[c]) +
+                                               " (a step is at least 1, a dead zone at least 0)");
+        if ((uint64_t)h.num_symbols[c] != padded)
+            return fail(kInvalidBitstream, ch + "num_symbols " + std::to_string(h.num_symbols[c]) + " != padded_pixels " + std::to_string(padded));
+        for (int k = 0; k < 8; ++k) {
+            const int j = 8 * c + k;
+            const uint8_t* b = band_field(data, c, k);
+            const std::string bk = "channel " + std::to_string(c) + " band " + std::to_string(k) + ": ";
+            h.n_blocks[j] = get_u32(b);
+            h.payload_len[j] = get_u64(b + 4);
+            if (h.n_blocks[j] != split_blocks(n_band, h.lane_symbols))
+                return fail(kInvalidBitstream, bk + "n_blocks " + std::to_string(h.n_blocks[j]) + " does not match num_symbols and lane_symbols");
+            uint32_t sum = 0;
+            for (int i = 0; i < 256; ++i) { h.freq[j][i] = (uint16_t)(b[12 + 2 * i] | (b[13 + 2 * i] << 8)); sum += h.freq[j][i]; }
+            if (sum != (padded ? kProbScale : 0u))
+                return fail(kInvalidBitstream, bk + "frequencies sum to " + std::to_string(sum) + ", not " + std::to_string(padded ? kProbScale : 0u));
+            if (h.payload_len[j] < 132ull * h.n_blocks[j] || h.payload_len[j] > UINT64_MAX / 32)
+                return fail(kInvalidBitstream, bk + "payload_len " + std::to_string(h.payload_len[j]) + " cannot hold its directories");
+            total += h.payload_len[j];
+        }
+    }
+    if (total != total_len)
+        return fail(kInvalidBitstream, "length mismatch: header and payloads are " + std::to_string(total) + " bytes, data is " + std::to_string(total_len));
+    return kOk;
+}
+
+// the block tables of a whole container in host memory
+int check_band_directories(const uint8_t* data, const BandHeader& h) {
+    const uint8_t* p = data + kBandHeaderBytes;
+    for (int j = 0; j < 24; ++j) {
+        const std::string bk = "channel " + std::to_string(j / 8) + " band " + std::to_string(j % 8) + ": ";
+        uint64_t sum = 4ull * h.n_blocks[j];
+        for (uint32_t b = 0; b < h.n_blocks[j]; ++b) {
+            const uint32_t v = get_u32(p + 4ull * b);
+            if (v < 128u) return fail(kInvalidBitstream, bk + "block " + std::to_string(b) + " is shorter than its lane directory");
+            sum += v;
+        }
+        if (sum != h.payload_len[j])
+            return fail(kInvalidBitstream, bk + "block lengths sum to " + std::to_string(sum) + ", payload_len is " + std::to_string(h.payload_len[j]));
+        p += h.payload_len[j];
+    }
+    return kOk;
+}
+
+bool band_base_ok(uint8_t base) { return base >= 2 && base <= 4; }
+
+uint32_t band_group(const ChunkDims& d, SplitFormat fmt) { return std::min(split_group(d, fmt), kBandMaxGroup); }
+
+// 24 B band jobs: the channel scratch of SplitWork (one job per band) and the jobs with their geometry.  (bjobs and sent are
+// declared ahead of w: w's destructor drains the stream that reads them.)
+struct BandWork {
+    DevBuf bjobs;
+    std::vector<std::vector<SplitBandJob>> sent;
+    SplitWork w;
+    uint32_t pw = 0, ph = 0, hw = 0, hh = 0;
+};
+
+int band_work_alloc(BandWork& bw, uint32_t B, const ChunkDims& d, uint32_t L, bool encode, SplitFormat fmt) {
+    bw.pw = (uint32_t)d.pw; bw.ph = (uint32_t)d.ph; bw.hw = bw.pw / 2; bw.hh = bw.ph / 2;
+    TRY(split_work_alloc(bw.w, (int)(24 * B), d.padded / 8, L, encode, fmt));
+    TRY(bw.bjobs.alloc((size_t)24 * B * sizeof(SplitBandJob)));
+    return kOk;
+}
+
+// Where the bands' symbols live: chunk i, channel c at sym + (3 i + c) * padded * sb, band k at its box's origin inside.
+void band_set_symbols(BandWork& bw, const uint8_t* sym, uint32_t B, const ChunkDims& d, size_t sb) {
+    const uint64_t ht = d.pf / 2;
+    for (uint32_t i = 0; i < B; ++i)
+        for (int c = 0; c < 3; ++c)
+            for (int k = 0; k < 8; ++k) {
+                const uint64_t origin = ((uint64_t)((k >> 2) & 1) * ht * d.ph + (uint64_t)((k >> 1) & 1) * bw.hh) * d.pw + (uint64_t)(k & 1) * bw.hw;
+                bw.w.h[(size_t)24 * i + 8 * c + k].sym = sym + ((3 * (size_t)i + c) * d.padded + origin) * sb;
+            }
+}
+
+int band_upload_jobs(BandWork& bw, hipStream_t st) {
+    TRY(split_upload_jobs(bw.w, st));
+    std::vector<SplitBandJob> v(bw.w.h.size());
+    for (size_t j = 0; j < v.size(); ++j) v[j] = SplitBandJob{bw.w.h[j], bw.pw, bw.ph, bw.hw, bw.hh};
+    bw.sent.push_back(std::move(v));
+    HIP_TRY(hipMemcpyAsync(bw.bjobs.p, bw.sent.back().data(), bw.sent.back().size() * sizeof(SplitBandJob), hipMemcpyHostToDevice, st));
+    return kOk;
+}
+
+// Whole chunks from their symbols, in two halves (as split_count_chunks / split_write_chunks): band histograms, tables (one
+// launch for all 24 B), count pass and scan, sizes to the host; then the write pass and the headers.
+struct BandChunkEncode {
+    std::vector<BandHeaderDesc> hd;   // (declared before bw: its destructor drains the stream that reads them)
+    DevBuf d_hd, hist;
+    BandWork bw;
+    std::vector<uint64_t> totals;
+    std::vector<int32_t> steps, dead_zones;   // 3 per chunk
+    ChunkDims d{};
+    uint32_t B = 0, L = 0;
+    uint8_t wavelet = 0, base = 2;
+};
+
+int band_count_chunks(BandChunkEncode& e, const uint8_t* sym, uint32_t B, const ChunkDims& d, uint8_t wavelet, uint32_t L, SplitFormat fmt,
+                      hipStream_t st, std::vector<uint64_t>& sizes) {
+    const bool wide = is_wide(fmt);
+    const size_t sb = wide ? 2 : 1;
+    e.B = B; e.L = L; e.d = d; e.wavelet = wavelet; e.base = format_version(fmt);
+    TRY(e.hist.alloc((size_t)B * 24 * 256 * sizeof(uint32_t)));
+    HIP_TRY(hipMemsetAsync(e.hist.p, 0, (size_t)B * 24 * 256 * sizeof(uint32_t), st));
+    for (uint32_t i = 0; i < B; ++i)
+        launch_band_hist(sym + (size_t)i * 3 * d.padded * sb, d, wide, e.hist.as<uint32_t>() + (size_t)i * 24 * 256, st);
+    e.hd.assign(B, BandHeaderDesc{});
+    BandWork& bw = e.bw;
+    SplitWork& w = bw.w;
+    TRY(band_work_alloc(bw, B, d, L, true, fmt));
+    band_set_symbols(bw, sym, B, d, sb);
+    launch_split_table(e.hist.as<uint32_t>(), w.freq.as<uint16_t>(), w.cum.as<uint16_t>(), w.n_jobs, st);
+    launch_rans_tables_from_arrays(w.cum.as<uint16_t>(), w.freq.as<uint16_t>(), w.tables.as<RansTable>(), w.n_jobs, st);
+    TRY(band_upload_jobs(bw, st));
+    if (wide) HIP_TRY(hipMemsetAsync(w.flags.p, 0, (size_t)w.n_jobs * sizeof(uint32_t), st));
+    launch_band_count(bw.bjobs.as<SplitBandJob>(), w.n_jobs, w.n_blocks, wide, st);
+    launch_split_scan(w.jobs.as<SplitJob>(), w.n_jobs, false, w.totals.as<unsigned long long>(), st);
+    HIP_TRY(hipGetLastError());
+    e.totals.resize((size_t)w.n_jobs);
+    HIP_TRY(hipMemcpyAsync(e.totals.data(), w.totals.p, e.totals.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    std::vector<uint32_t> flags;
+    if (wide) {
+        flags.resize((size_t)w.n_jobs);
+        HIP_TRY(hipMemcpyAsync(flags.data(), w.flags.p, flags.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    for (size_t j = 0; j < flags.size(); ++j)
+        if (flags[j] & kSplitWideResidual)
+            return fail(kInternal, "stream " + std::to_string(j) + ": a symbol above 255 + 4095 has no version 3 code");
+    sizes.assign(B, kBandHeaderBytes);
+    for (uint32_t i = 0; i < B; ++i)
+        for (int j = 0; j < 24; ++j) sizes[i] += e.totals[(size_t)24 * i + j];
+    return kOk;
+}
+
+int band_write_chunks(BandChunkEncode& e, const std::vector<uint8_t*>& outs, hipStream_t st) {
+    const uint32_t B = e.B;
+    SplitWork& w = e.bw.w;
+    TRY(e.d_hd.alloc((size_t)B * sizeof(BandHeaderDesc)));
+    for (uint32_t i = 0; i < B; ++i) {
+        BandHeaderDesc& h = e.hd[i];
+        h.out = outs[i];
+        h.width = e.d.w; h.height = e.d.h; h.frames = e.d.f; h.lane_symbols = e.L;
+        h.num_symbols = (uint32_t)e.d.padded; h.n_blocks = w.n_blocks; h.wavelet = e.wavelet; h.base = e.base;
+        h.freq = w.freq.as<uint16_t>() + (size_t)i * 24 * 256;
+        for (int c = 0; c < 3; ++c) { h.step[c] = e.steps[3 * (size_t)i + c]; h.dead_zone[c] = e.dead_zones[3 * (size_t)i + c]; }
+        uint64_t off = kBandHeaderBytes;
+        for (int j = 0; j < 24; ++j) {
+            h.payload_len[j] = e.totals[(size_t)24 * i + j];
+            w.h[(size_t)24 * i + j].stream = outs[i] + off;
+            off += h.payload_len[j];
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(e.d_hd.p, e.hd.data(), e.hd.size() * sizeof(BandHeaderDesc), hipMemcpyHostToDevice, st));
+    TRY(band_upload_jobs(e.bw, st));
+    launch_band_write(e.bw.bjobs.as<SplitBandJob>(), w.n_jobs, w.n_blocks, w.wide, st);
+    launch_band_headers(e.d_hd.as<BandHeaderDesc>(), (int)B, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    return kOk;
+}
+
+// B equal-shaped chunks from pixels: the base's forward pass (its fused channel histogram is not used), then the halves above.
+template <typename Place>
+int band_encode_chunks(const RgbLayout* rgb, uint32_t B, const ChunkDims& d, uint8_t wavelet, const uint8_t* q, uint32_t L, SplitFormat fmt,
+                       hipStream_t st, std::vector<uint64_t>& sizes, Place place) {
+    const bool wide = is_wide(fmt);
+    const size_t sb = wide ? 2 : 1;
+    EncodeWork ew;
+    BandChunkEncode e;     // (after ew: its destructor drains the stream that reads ew.sym)
+    ew.d = d; ew.n_chunks = (int)B;
+    if (transform_tiles_eligible(d)) TRY(ew.scratch.alloc(forward_scratch_bytes(d)));
+    TRY(ew.sym.alloc((size_t)B * 3 * d.padded * sb));
+    TRY(ew.hist.alloc((size_t)B * 3 * 256 * sizeof(uint32_t)));
+    HIP_TRY(hipMemsetAsync(ew.hist.p, 0, (size_t)B * 3 * 256 * sizeof(uint32_t), st));
+    StreamDrain drain(st);
+    e.steps.resize(3 * (size_t)B); e.dead_zones.resize(3 * (size_t)B);
+    for (uint32_t i = 0; i < B; ++i) {
+        const int32_t step = quality_to_step(q[i]);
+        for (int c = 0; c < 3; ++c) e.steps[3 * (size_t)i + c] = e.dead_zones[3 * (size_t)i + c] = step;
+        TRY(forward_chunk(rgb[i], d, wavelet, step, ew, ew.sym.as<uint8_t>() + (size_t)i * 3 * d.padded * sb,
+                          ew.hist.as<uint32_t>() + (size_t)i * 3 * 256, st, wide));
+    }
+    TRY(band_count_chunks(e, ew.sym.as<uint8_t>(), B, d, wavelet, L, fmt, st, sizes));
+    std::vector<uint8_t*> outs(B, nullptr);
+    TRY(place(sizes, outs));
+    return band_write_chunks(e, outs, st);
+}
+
+// Queues the tables, the directory scan and the band decode of B chunks (hdr[i] validated, d_alc[i] the chunk's first byte on
+// the device) into the symbol volumes at sym (chunk stride 3 * padded * sb); split_decode_verdict(bw.w, st) reads the flags.
+int band_decode_launch(BandWork& bw, const BandHeader* hdr, const uint8_t* const* d_alc, uint32_t B, const ChunkDims& d, uint8_t* sym,
+                       hipStream_t st) {
+    const SplitFormat fmt = hdr[0].fmt;
+    const size_t sb = is_wide(fmt) ? 2 : 1;
+    TRY(band_work_alloc(bw, B, d, hdr[0].lane_symbols, false, fmt));
+    SplitWork& w = bw.w;
+    w.st = st; w.armed = true;
+    band_set_symbols(bw, sym, B, d, sb);
+    w.h_freq.resize((size_t)w.n_jobs * 256);
+    w.h_cum.assign((size_t)w.n_jobs * 256, 0);
+    for (uint32_t i = 0; i < B; ++i) {
+        uint64_t off = kBandHeaderBytes;
+        for (int j = 0; j < 24; ++j) {
+            const size_t t = (size_t)24 * i + j;
+            memcpy(&w.h_freq[t * 256], hdr[i].freq[j], 256 * sizeof(uint16_t));
+            uint32_t run = 0;
+            for (int s = 0; s < 256; ++s) { w.h_cum[t * 256 + s] = (uint16_t)run; run += hdr[i].freq[j][s]; }
+            w.h[t].stream = (uint8_t*)d_alc[i] + off;
+            w.h[t].len = hdr[i].payload_len[j];
+            off += hdr[i].payload_len[j];
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(w.freq.p, w.h_freq.data(), w.h_freq.size() * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(w.cum.p, w.h_cum.data(), w.h_cum.size() * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(w.flags.p, 0, (size_t)w.n_jobs * sizeof(uint32_t), st));
+    TRY(band_upload_jobs(bw, st));
+    launch_rans_tables_from_arrays(w.cum.as<uint16_t>(), w.freq.as<uint16_t>(), w.tables.as<RansTable>(), w.n_jobs, st);
+    launch_split_scan(w.jobs.as<SplitJob>(), w.n_jobs, true, nullptr, st);
+    launch_band_decode(bw.bjobs.as<SplitBandJob>(), w.n_jobs, w.n_blocks, w.wide, st);
+    HIP_TRY(hipGetLastError());
+    return kOk;
+}
+
+// Decode of B equal-shaped chunks of one base to pixels at rgb[i]: straight into the volume the base's inverse reads.
+// Returns after the stream has drained, with the verdict of the end checks.
+int band_decode_chunks(const BandHeader* hdr, const uint8_t* const* d_alc, uint32_t B, const ChunkDims& d, const RgbLayout* rgb, hipStream_t st) {
+    DecodeWork dw;
+    dw.d = d; dw.n_chunks = (int)B;
+    const SplitFormat fmt = hdr[0].fmt;
+    const bool wide = is_wide(fmt);
+    const size_t sb = wide ? 2 : 1;
+    TRY(dw.sym.alloc((size_t)B * 3 * d.padded * sb));
+    bool any16 = false, any32 = false;
+    for (uint32_t i = 0; i < B; ++i) (inverse_bounds(hdr[i].wavelet, hdr[i].step, wide ? kWideMaxQ : kByteMaxQ).mid16 ? any16 : any32) = true;
+    if (transform_tiles_eligible(d)) TRY(dw.scratch_own.alloc(group_scratch_bytes(d, any16, any32)));
+    BandWork bw;   // (after dw: its destructor drains the stream)
+    TRY(band_decode_launch(bw, hdr, d_alc, B, d, dw.sym.as<uint8_t>(), st));
+    for (uint32_t i = 0; i < B; ++i)
+        TRY(inverse_chunk(dw.sym.as<uint8_t>() + (size_t)i * 3 * d.padded * sb, d, hdr[i].wavelet, hdr[i].step, dw.scratch_own.p, dw, rgb[i], st, fmt));
+    HIP_TRY(hipGetLastError());
+    return split_decode_verdict(bw.w, st);
+}
+
+// The headers of n device containers, read back and validated; the chunks agree in base, wavelet, shape and lane_symbols.
+int band_device_headers(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks, hipStream_t st,
+                        std::vector<BandHeader>& hdr, std::vector<const uint8_t*>& ptr, ChunkDims& d) {
+    std::vector<uint8_t> raw((size_t)n_chunks * kBandHeaderBytes, 0);
+    for (uint32_t i = 0; i < n_chunks; ++i)
+        if (sizes[i])
+            HIP_TRY(hipMemcpyAsync(raw.data() + (size_t)i * kBandHeaderBytes, (const uint8_t*)d_alc + (size_t)i * alc_stride,
+                                   std::min<uint64_t>(sizes[i], kBandHeaderBytes), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    hdr.resize(n_chunks); ptr.resize(n_chunks);
+    for (uint32_t i = 0; i < n_chunks; ++i) {
+        ChunkDims di{};
+        TRY(parse_band_header(raw.data() + (size_t)i * kBandHeaderBytes, sizes[i], hdr[i], &di));
+        if (di.n_pixels == 0) return fail(kInvalidDimensions, "invalid dimensions");
+        if (i == 0) d = di;
+        else if (hdr[i].base != hdr[0].base || hdr[i].wavelet != hdr[0].wavelet || di.w != d.w || di.h != d.h || di.f != d.f ||
+                 hdr[i].lane_symbols != hdr[0].lane_symbols)
+            return fail(kInvalidDimensions, "the chunks of one call must have the same base, wavelet, shape and lane_symbols");
+        ptr[i] = (const uint8_t*)d_alc + (size_t)i * alc_stride;
+    }
+    return kOk;
+}
+
+// where the chunks of a device call go: chunk first + i at d_out + (first + i) * out_stride, refused before anything is written
+auto band_place_strided(void* d_out, uint64_t out_stride, uint32_t first, uint32_t B) {
+    return [=](const std::vector<uint64_t>& s, std::vector<uint8_t*>& outs) -> int {
+        for (uint32_t i = 0; i < B; ++i) {
+            if (s[i] > out_stride)
+                return fail(kInvalidBufferSize, "chunk " + std::to_string(first + i) + " needs " + std::to_string(s[i]) +
+                                                    " bytes, the output stride is " + std::to_string(out_stride));
+            outs[i] = (uint8_t*)d_out + (size_t)(first + i) * out_stride;
+        }
+        return kOk;
+    };
+}
+
+// ---- repack: between a base chunk and its banded twin through the symbols, no transform ----
+
+// One group base -> banded: lane decode of every block into the symbol volume (its verdict first: nothing of a damaged
+// source is coded), then the encode from symbols.
+template <typename Place>
+int to_banded_group(const SplitHeader* hdr, const uint8_t* const* d_alc, uint32_t B, const ChunkDims& d, uint32_t L, hipStream_t st,
+                    std::vector<uint64_t>& sizes, Place place) {
+    TranscodeSource s;
+    BandChunkEncode e;     // (after s: its destructor drains the stream that reads s.sym)
+    TRY(transcode_decode(s, hdr, d_alc, B, d, st));
+    e.steps.resize(3 * (size_t)B); e.dead_zones.resize(3 * (size_t)B);
+    for (uint32_t i = 0; i < B; ++i)
+        for (int c = 0; c < 3; ++c) { e.steps[3 * (size_t)i + c] = hdr[i].step[c]; e.dead_zones[3 * (size_t)i + c] = hdr[i].dead_zone[c]; }
+    TRY(band_count_chunks(e, s.sym.as<uint8_t>(), B, d, hdr[0].wavelet, L, hdr[0].fmt, st, sizes));
+    std::vector<uint8_t*> outs(B, nullptr);
+    TRY(place(sizes, outs));
+    return band_write_chunks(e, outs, st);
+}
+
+// One group banded -> base: band decode into the symbol volume, a 256-bin count of each channel, then the base's own table,
+// count and write passes (the first half of an encode from symbols at a target step that leaves every channel untouched).
+template <typename Place>
+int from_banded_group(const BandHeader* hdr, const uint8_t* const* d_alc, uint32_t B, const ChunkDims& d, uint32_t L, hipStream_t st,
+                      std::vector<uint64_t>& sizes, Place place) {
+    const SplitFormat fmt = hdr[0].fmt;
+    const size_t sb = is_wide(fmt) ? 2 : 1;
+    DevBuf sym;
+    StreamDrain drain(st);
+    SplitChunkEncode e;
+    TRY(sym.alloc((size_t)B * 3 * d.padded * sb));
+    {
+        BandWork bw;
+        TRY(band_decode_launch(bw, hdr, d_alc, B, d, sym.as<uint8_t>(), st));
+        TRY(split_decode_verdict(bw.w, st));
+    }
+    std::vector<SplitHeader> sh(B);
+    std::vector<int32_t> keep(B, 1);
+    for (uint32_t i = 0; i < B; ++i) {
+        sh[i].fmt = fmt; sh[i].wavelet = hdr[i].wavelet;
+        for (int c = 0; c < 3; ++c) { sh[i].step[c] = hdr[i].step[c]; sh[i].dead_zone[c] = hdr[i].dead_zone[c]; }
+    }
+    TRY(transcode_count_chunks(e, sym.as<uint8_t>(), sym.as<uint8_t>(), sh.data(), B, d, keep.data(), L, fmt, st, sizes));
+    std::vector<uint8_t*> outs(B, nullptr);
+    TRY(place(sizes, outs));
+    return split_write_chunks(e, outs, st);
+}
+
+void write_empty_banded(uint8_t* p, uint8_t wavelet, uint32_t w, uint32_t h, uint32_t f, uint32_t L, uint8_t base, const int32_t* step,
+                        const int32_t* dead_zone) {
+    memset(p, 0, kBandHeaderBytes);
+    memcpy(p, "ALCC", 4);
+    p[4] = 5; p[5] = wavelet;
+    put_u32(p + 6, w); put_u32(p + 10, h); put_u32(p + 14, f); put_u32(p + 18, L);
+    p[22] = base;
+    for (int c = 0; c < 3; ++c) {
+        uint8_t* q = p + kBandFixedHeaderBytes + (size_t)c * kBandChannelHeaderBytes;
+        put_u32(q, (uint32_t)step[c]); put_u32(q + 4, (uint32_t)dead_zone[c]);
+    }
+}
+
+int band_check_base_lane(uint8_t base, uint32_t lane_symbols, uint32_t* L, SplitFormat* fmt) {
+    if (!band_base_ok(base)) return fail(kInvalidDimensions, "base " + std::to_string((int)base) + " (a banded chunk has base 2, 3 or 4)");
+    *fmt = format_of_version(base);
+    *L = lane_symbols ? lane_symbols : kSplitDefaultLane;
+    if (!split_lane_ok(*L, *fmt)) return fail(kInvalidDimensions, split_lane_msg(*fmt));
+    return kOk;
+}
+
+// a host result from a device buffer of `size` bytes
+int band_host_result(uint8_t** out, uint64_t* out_len, const DevBuf& d_out, uint64_t size, hipStream_t st) {
+    *out = host_result_alloc(size);
+    if (!*out) return fail(kOutOfMemory, "out of host memory");
+    const int rc = copy_to_host(*out, d_out.p, size, st);
+    if (rc != kOk) { free(*out); *out = nullptr; return rc; }
+    *out_len = size;
+    return kOk;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t alice_codec_banded_stream_bound(uint64_t n_band, uint32_t lane_symbols, uint8_t base) {
+    if (!band_base_ok(base) || !split_lane_ok(lane_symbols, format_of_version(base)) || n_band > 0xFFFFFFFFull / 8) return 0;
+    return (uint64_t)split_blocks(n_band, lane_symbols) * (4 + 128 + 64 * 4) + (base == 2 ? 2 : 4) * n_band;
+}
+
+int alice_codec_banded_info(const uint8_t* data, uint64_t len, AliceBandedInfo* info) {
+    clear_error();
+    if (!data || !info) return fail(kNullArgument, "null argument");
+    BandHeader h;
+    ChunkDims d{};
+    TRY(parse_band_header(data, len, h, &d));
+    TRY(check_band_directories(data, h));
+    memset(info, 0, sizeof(*info));
+    info->width = h.width; info->height = h.height; info->frames = h.frames;
+    info->lane_symbols = h.lane_symbols; info->wavelet = h.wavelet; info->base = h.base;
+    for (int c = 0; c < 3; ++c) { info->quant_step[c] = h.step[c]; info->dead_zone[c] = h.dead_zone[c]; info->num_symbols[c] = h.num_symbols[c]; }
+    for (int j = 0; j < 24; ++j) { info->n_blocks[j] = h.n_blocks[j]; info->payload_len[j] = h.payload_len[j]; }
+    return kOk;
+}
+
+uint8_t* alice_codec_encode_banded(const FrameEncoder* encoder, const uint8_t* rgb, uint64_t rgb_len, uint32_t width, uint32_t height,
+                                   uint32_t frames, uint32_t lane_symbols, uint8_t base, uint64_t* out_len) {
+    clear_error();
+    if (!encoder || !rgb || !out_len) { fail(kNullArgument, "null argument"); return nullptr; }
+    auto run = [&](uint8_t** out) -> int {
+        uint64_t n_pixels = 0;
+        TRY(checked_pixel_count(width, height, frames, &n_pixels));
+        if (n_pixels == 0 && rgb_len != 0) return fail(kInvalidBufferSize, "buffer size mismatch: expected 0, got " + std::to_string(rgb_len));
+        ChunkDims d{};
+        EncodedChunk* none = nullptr;
+        if (n_pixels) TRY(validate_encode_many(encoder, rgb, rgb_len, width, height, frames, 1, &none, &d));
+        uint32_t L = 0;
+        SplitFormat fmt;
+        TRY(band_check_base_lane(base, lane_symbols, &L, &fmt));
+        if (n_pixels == 0) {
+            *out = host_result_alloc(kBandHeaderBytes);
+            if (!*out) return fail(kOutOfMemory, "out of host memory");
+            const int32_t s = quality_to_step(encoder->quality), steps[3] = {s, s, s};
+            write_empty_banded(*out, encoder->wavelet, width, height, frames, L, base, steps, steps);
+            *out_len = kBandHeaderBytes;
+            return kOk;
+        }
+        hipStream_t st;
+        TRY(get_stream(&st));
+        DevBuf d_rgb, d_out;
+        StreamDrain drain(st);
+        TRY(d_rgb.alloc(n_pixels * 3));
+        HIP_TRY(hipMemcpyAsync(d_rgb.p, rgb, n_pixels * 3, hipMemcpyHostToDevice, st));
+        const RgbLayout layout = packed_rgb(d_rgb.p, d);
+        std::vector<uint64_t> sizes;
+        TRY(band_encode_chunks(&layout, 1, d, encoder->wavelet, &encoder->quality, L, fmt, st, sizes,
+                               [&](const std::vector<uint64_t>& sz, std::vector<uint8_t*>& outs) -> int {
+                                   TRY(d_out.alloc(sz[0]));
+                                   outs[0] = d_out.as<uint8_t>();
+                                   return kOk;
+                               }));
+        return band_host_result(out, out_len, d_out, sizes[0], st);
+    };
+    uint8_t* out = nullptr;
+    return run(&out) == kOk ? out : nullptr;
+}
+
+uint8_t* alice_codec_decode_banded(const uint8_t* data, uint64_t len, uint64_t* out_len) {
+    clear_error();
+    if (!data || !out_len) { fail(kNullArgument, "null argument"); return nullptr; }
+    auto run = [&](uint8_t** out) -> int {
+        BandHeader h;
+        ChunkDims d{};
+        TRY(parse_band_header(data, len, h, &d));
+        TRY(check_band_directories(data, h));
+        const uint64_t bytes = (uint64_t)h.width * h.height * h.frames * 3;
+        *out = host_result_alloc(bytes);
+        if (!*out) return fail(kOutOfMemory, "out of host memory");
+        *out_len = bytes;
+        if (!bytes) return kOk;
+        auto body = [&]() -> int {
+            hipStream_t st;
+            TRY(get_stream(&st));
+            DevBuf d_alc, d_rgb;
+            StreamDrain drain(st);
+            TRY(d_alc.alloc(len));
+            TRY(d_rgb.alloc(bytes));
+            HIP_TRY(hipMemcpyAsync(d_alc.p, data, len, hipMemcpyHostToDevice, st));
+            const uint8_t* p = d_alc.as<uint8_t>();
+            const RgbLayout layout = packed_rgb(d_rgb.p, d);
+            TRY(band_decode_chunks(&h, &p, 1, d, &layout, st));
+            return copy_to_host(*out, d_rgb.p, bytes, st);
+        };
+        const int rc = body();
+        if (rc != kOk) { free(*out); *out = nullptr; }
+        return rc;
+    };
+    uint8_t* out = nullptr;
+    return run(&out) == kOk ? out : nullptr;
+}
+
+int alice_codec_dev_encode_banded(const void* d_rgb, uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks,
+                                  uint8_t wavelet_type, uint8_t quality, const uint8_t* qualities, uint32_t lane_symbols, uint8_t base,
+                                  void* d_out, uint64_t out_stride, uint64_t* sizes, void* hip_stream) {
+    clear_error();
+    if (!d_rgb || !d_out || !sizes) return fail(kNullArgument, "null argument");
+    if (wavelet_type > 2) return fail(kInvalidBitstream, "unknown wavelet type");
+    ChunkDims d{};
+    TRY(chunk_dims(width, height, frames, &d, n_chunks));
+    uint32_t L = 0;
+    SplitFormat fmt;
+    TRY(band_check_base_lane(base, lane_symbols, &L, &fmt));
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);
+    std::vector<RgbLayout> layouts(n_chunks);
+    std::vector<uint8_t> q(n_chunks);
+    for (uint32_t i = 0; i < n_chunks; ++i) {
+        layouts[i] = packed_rgb((const uint8_t*)d_rgb + (size_t)i * d.n_pixels * 3, d);
+        q[i] = qualities ? qualities[i] : quality;
+    }
+    const uint32_t group = band_group(d, fmt);
+    for (uint32_t first = 0; first < n_chunks; first += group) {
+        const uint32_t B = std::min(group, n_chunks - first);
+        std::vector<uint64_t> sz;
+        TRY(band_encode_chunks(layouts.data() + first, B, d, wavelet_type, q.data() + first, L, fmt, st, sz, band_place_strided(d_out, out_stride, first, B)));
+        for (uint32_t i = 0; i < B; ++i) sizes[first + i] = sz[i];
+    }
+    return kOk;
+}
+
+int alice_codec_dev_decode_banded(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks, void* d_rgb_out,
+                                  void* hip_stream) {
+    clear_error();
+    if (!d_alc || !sizes || !d_rgb_out) return fail(kNullArgument, "null argument");
+    if (n_chunks == 0) return fail(kInvalidDimensions, "empty batch");
+    for (uint32_t i = 0; i < n_chunks; ++i)
+        if (sizes[i] > alc_stride && n_chunks > 1) return fail(kInvalidBufferSize, "chunk " + std::to_string(i) + " is longer than the stride");
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);
+    std::vector<BandHeader> hdr;
+    std::vector<const uint8_t*> ptr;
+    ChunkDims d{};
+    TRY(band_device_headers(d_alc, alc_stride, sizes, n_chunks, st, hdr, ptr, d));
+    std::vector<RgbLayout> layouts;
+    TRY(split_layouts(d_rgb_out, 0, 0, nullptr, d, n_chunks, layouts));
+    const uint32_t group = band_group(d, hdr[0].fmt);
+    for (uint32_t first = 0; first < n_chunks; first += group)
+        TRY(band_decode_chunks(hdr.data() + first, ptr.data() + first, std::min(group, n_chunks - first), d, layouts.data() + first, st));
+    return kOk;
+}
+
+uint8_t* alice_codec_to_banded(const uint8_t* data, uint64_t len, uint32_t lane_symbols, uint64_t* out_len) {
+    clear_error();
+    if (!data || !out_len) { fail(kNullArgument, "null argument"); return nullptr; }
+    auto run = [&](uint8_t** out) -> int {
+        SplitHeader h;
+        ChunkDims d{};
+        TRY(frames_validate_header(data, len, h, d));
+        const uint32_t L = lane_symbols ? lane_symbols : h.lane_symbols;
+        if (!split_lane_ok(L, h.fmt)) return fail(kInvalidDimensions, split_lane_msg(h.fmt));
+        TRY(check_split_directories(data, h));
+        if (d.n_pixels == 0) {
+            *out = host_result_alloc(kBandHeaderBytes);
+            if (!*out) return fail(kOutOfMemory, "out of host memory");
+            write_empty_banded(*out, h.wavelet, h.width, h.height, h.frames, L, format_version(h.fmt), h.step, h.dead_zone);
+            *out_len = kBandHeaderBytes;
+            return kOk;
+        }
+        hipStream_t st;
+        TRY(get_stream(&st));
+        DevBuf d_alc, d_out;
+        StreamDrain drain(st);
+        TRY(d_alc.alloc(len));
+        HIP_TRY(hipMemcpyAsync(d_alc.p, data, len, hipMemcpyHostToDevice, st));
+        const uint8_t* p = d_alc.as<uint8_t>();
+        std::vector<uint64_t> sizes;
+        TRY(to_banded_group(&h, &p, 1, d, L, st, sizes, [&](const std::vector<uint64_t>& sz, std::vector<uint8_t*>& outs) -> int {
+            TRY(d_out.alloc(sz[0]));
+            outs[0] = d_out.as<uint8_t>();
+            return kOk;
+        }));
+        return band_host_result(out, out_len, d_out, sizes[0], st);
+    };
+    uint8_t* out = nullptr;
+    return run(&out) == kOk ? out : nullptr;
+}
+
+uint8_t* alice_codec_from_banded(const uint8_t* data, uint64_t len, uint32_t lane_symbols, uint64_t* out_len) {
+    clear_error();
+    if (!data || !out_len) { fail(kNullArgument, "null argument"); return nullptr; }
+    auto run = [&](uint8_t** out) -> int {
+        BandHeader h;
+        ChunkDims d{};
+        TRY(parse_band_header(data, len, h, &d));
+        const uint32_t L = lane_symbols ? lane_symbols : h.lane_symbols;
+        if (!split_lane_ok(L, h.fmt)) return fail(kInvalidDimensions, split_lane_msg(h.fmt));
+        TRY(check_band_directories(data, h));
+        if (d.n_pixels == 0) {
+            *out = host_result_alloc(kSplitHeaderBytes);
+            if (!*out) return fail(kOutOfMemory, "out of host memory");
+            write_empty_split(*out, h.wavelet, h.width, h.height, h.frames, L, h.step[0], h.base);
+            for (int c = 0; c < 3; ++c) {
+                uint8_t* q = *out + kSplitFixedHeaderBytes + (size_t)c * kSplitChannelHeaderBytes;
+                put_u32(q, (uint32_t)h.step[c]); put_u32(q + 4, (uint32_t)h.dead_zone[c]);
+            }
+            *out_len = kSplitHeaderBytes;
+            return kOk;
+        }
+        hipStream_t st;
+        TRY(get_stream(&st));
+        DevBuf d_alc, d_out;
+        StreamDrain drain(st);
+        TRY(d_alc.alloc(len));
+        HIP_TRY(hipMemcpyAsync(d_alc.p, data, len, hipMemcpyHostToDevice, st));
+        const uint8_t* p = d_alc.as<uint8_t>();
+        std::vector<uint64_t> sizes;
+        TRY(from_banded_group(&h, &p, 1, d, L, st, sizes, [&](const std::vector<uint64_t>& sz, std::vector<uint8_t*>& outs) -> int {
+            TRY(d_out.alloc(sz[0]));
+            outs[0] = d_out.as<uint8_t>();
+            return kOk;
+        }));
+        return band_host_result(out, out_len, d_out, sizes[0], st);
+    };
+    uint8_t* out = nullptr;
+    return run(&out) == kOk ? out : nullptr;
+}
+
+int alice_codec_dev_to_banded(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks, uint32_t lane_symbols,
+                              void* d_out, uint64_t out_stride, uint64_t* out_sizes, void* hip_stream) {
+    clear_error();
+    TRY(dev_transcode_checks(d_alc, alc_stride, sizes, n_chunks, d_out, out_sizes));
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);
+    std::vector<uint8_t> raw((size_t)n_chunks * kSplitHeaderBytes, 0);
+    for (uint32_t i = 0; i < n_chunks; ++i)
+        if (sizes[i])
+            HIP_TRY(hipMemcpyAsync(raw.data() + (size_t)i * kSplitHeaderBytes, (const uint8_t*)d_alc + (size_t)i * alc_stride,
+                                   std::min<uint64_t>(sizes[i], kSplitHeaderBytes), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    std::vector<SplitHeader> hdr(n_chunks);
+    std::vector<const uint8_t*> ptr(n_chunks);
+    ChunkDims d{};
+    for (uint32_t i = 0; i < n_chunks; ++i) {
+        ChunkDims di{};
+        TRY(frames_validate_header(raw.data() + (size_t)i * kSplitHeaderBytes, sizes[i], hdr[i], di));
+        if (di.n_pixels == 0) return fail(kInvalidDimensions, "invalid dimensions");
+        if (i == 0) d = di;
+        else if (hdr[i].fmt != hdr[0].fmt || hdr[i].wavelet != hdr[0].wavelet || di.w != d.w || di.h != d.h || di.f != d.f ||
+                 hdr[i].lane_symbols != hdr[0].lane_symbols)
+            return fail(kInvalidDimensions, "the chunks of one call must have the same version, wavelet, shape and lane_symbols");
+        ptr[i] = (const uint8_t*)d_alc + (size_t)i * alc_stride;
+    }
+    const uint32_t L = lane_symbols ? lane_symbols : hdr[0].lane_symbols;
+    if (!split_lane_ok(L, hdr[0].fmt)) return fail(kInvalidDimensions, split_lane_msg(hdr[0].fmt));
+    const uint32_t group = band_group(d, hdr[0].fmt);
+    for (uint32_t first = 0; first < n_chunks; first += group) {
+        const uint32_t B = std::min(group, n_chunks - first);
+        std::vector<uint64_t> sz;
+        TRY(to_banded_group(hdr.data() + first, ptr.data() + first, B, d, L, st, sz, band_place_strided(d_out, out_stride, first, B)));
+        for (uint32_t i = 0; i < B; ++i) out_sizes[first + i] = sz[i];
+    }
+    return kOk;
+}
+
+int alice_codec_dev_from_banded(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks, uint32_t lane_symbols,
+                                void* d_out, uint64_t out_stride, uint64_t* out_sizes, void* hip_stream) {
+    clear_error();
+    TRY(dev_transcode_checks(d_alc, alc_stride, sizes, n_chunks, d_out, out_sizes));
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);
+    std::vector<BandHeader> hdr;
+    std::vector<const uint8_t*> ptr;
+    ChunkDims d{};
+    TRY(band_device_headers(d_alc, alc_stride, sizes, n_chunks, st, hdr, ptr, d));
+    const uint32_t L = lane_symbols ? lane_symbols : hdr[0].lane_symbols;
+    if (!split_lane_ok(L, hdr[0].fmt)) return fail(kInvalidDimensions, split_lane_msg(hdr[0].fmt));
+    const uint32_t group = band_group(d, hdr[0].fmt);
+    for (uint32_t first = 0; first < n_chunks; first += group) {
+        const uint32_t B = std::min(group, n_chunks - first);
+        std::vector<uint64_t> sz;
+        TRY(from_banded_group(hdr.data() + first, ptr.data() + first, B, d, L, st, sz, band_place_strided(d_out, out_stride, first, B)));
+        for (uint32_t i = 0; i < B; ++i) out_sizes[first + i] = sz[i];
+    }
+    return kOk;
+}
+
+int alice_codec_dev_band_histograms(const void* d_symbols, uint32_t width, uint32_t height, uint32_t frames, int wide, void* d_hist,
+                                    void* hip_stream) {
+    clear_error();
+    if (!d_symbols || !d_hist) return fail(kNullArgument, "null argument");
+    ChunkDims d{};
+    TRY(chunk_dims(width, height, frames, &d));
+    if (wide && ((uintptr_t)d_symbols & 1u)) return fail(kInvalidDimensions, "u16 symbols lie at even addresses");
+    if ((uintptr_t)d_hist & 3u) return fail(kInvalidDimensions, "the histograms lie at a multiple of 4 bytes");
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);
+    HIP_TRY(hipMemsetAsync(d_hist, 0, 3 * 8 * 256 * sizeof(uint32_t), st));
+    launch_band_hist(d_symbols, d, wide != 0, (uint32_t*)d_hist, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    return kOk;
+}
+
+}  // extern "C"

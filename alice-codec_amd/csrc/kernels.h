@@ -420,6 +420,13 @@ struct SplitBoxJob {
     uint32_t lo[3], half[3], n_lo[3], n_hi[3];
     unsigned long long pitch;
 };
+// One band of a channel (.alc v5): `j` is a channel job whose n symbols are the band's, in band order
+// (the raster of an hw x hh x (n / (hw hh)) box), and j.sym is the band's origin inside the channel's [t'][ph][pw] volume:
+// band-order index idx lives at j.sym[((idx / (hw hh)) * ph + (idx / hw) % hh) * pw + idx % hw].
+struct SplitBandJob {
+    SplitJob j;
+    uint32_t pw, ph, hw, hh;
+};
 struct SplitHeaderDesc {
     uint8_t* out;
     uint32_t width, height, frames, lane_symbols, num_symbols, n_blocks;
@@ -447,6 +454,29 @@ void launch_split_frames_decode(const SplitFramesJob* d_jobs, int n_jobs, uint32
 void launch_split_box_decode(const SplitBoxJob* d_jobs, int n_jobs, uint32_t max_planned, bool wide, bool xy_high, hipStream_t st);
 // overwrites the version byte of the headers launch_split_headers wrote (same stream, after it)
 void launch_split_header_version(const SplitHeaderDesc* d_descs, int n_chunks, uint8_t version, hipStream_t st);
+
+// ---- band.hip: the banded entropy stage of .alc v5 ----
+constexpr uint32_t kBandFixedHeaderBytes = 24;       // the fixed fields of version 2, then base and a reserved byte
+constexpr uint32_t kBandBandHeaderBytes = 524;       // n_blocks, payload_len u64, 256 x u16
+constexpr uint32_t kBandChannelHeaderBytes = 12 + 8 * kBandBandHeaderBytes;   // step, dead zone, num_symbols, eight bands: 4204
+constexpr uint32_t kBandHeaderBytes = kBandFixedHeaderBytes + 3 * kBandChannelHeaderBytes;   // 12636
+struct BandHeaderDesc {
+    uint8_t* out;
+    uint32_t width, height, frames, lane_symbols, num_symbols, n_blocks;   // n_blocks: of every band
+    int32_t step[3], dead_zone[3];
+    unsigned long long payload_len[24];   // channel-major, band ascending
+    const uint16_t* freq;      // device, 24 x 256
+    uint8_t wavelet, base;
+};
+// symbols [3][pf][ph][pw] of one chunk (u8; wide: u16 at an even address) -> d_hist u32 [3][8][256], ADDED (the caller
+// zeroes); wide bins min(z, 255).  One read pass; the grid obeys generic_grid_for's cap.
+void launch_band_hist(const void* d_sym, const ChunkDims& d, bool wide, uint32_t* d_hist, hipStream_t st);
+// the passes of launch_split_count / _write / _decode over band jobs; the scan between them is launch_split_scan over the
+// same jobs' SplitJob parts
+void launch_band_count(const SplitBandJob* d_jobs, int n_jobs, uint32_t max_blocks, bool wide, hipStream_t st);
+void launch_band_write(const SplitBandJob* d_jobs, int n_jobs, uint32_t max_blocks, bool wide, hipStream_t st);
+void launch_band_decode(const SplitBandJob* d_jobs, int n_jobs, uint32_t max_blocks, bool wide, hipStream_t st);
+void launch_band_headers(const BandHeaderDesc* d_descs, int n_chunks, hipStream_t st);
 
 // ---- quality.hip: exact squared error of two RGB volumes ----
 constexpr uint32_t kSseBlock = 256;               // lanes of a workgroup

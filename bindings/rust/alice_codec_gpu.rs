@@ -844,13 +844,14 @@ pub fn decode_wide(data: &[u8]) -> Result<Vec<u8>, CodecError> {
 
 pub fn wide_stream_bound(n: u64, lane_symbols: u32) -> u64 { unsafe { alice_codec_wide_stream_bound(n, lane_symbols) } }
 
-/// The RGB bytes of a container of any version: 1 (`FrameDecoder`), 2 (`decode_split`), 3 (`decode_wide`) or
-/// 4 (`decode_reversible`).
+/// The RGB bytes of a container of any version: 1 (`FrameDecoder`), 2 (`decode_split`), 3 (`decode_wide`),
+/// 4 (`decode_reversible`) or 5 (`decode_banded`).
 pub fn decode_alc(data: &[u8]) -> Result<Vec<u8>, CodecError> {
     match alc_version(data) {
         2 => decode_split(data),
         3 => decode_wide(data),
         4 => decode_reversible(data),
+        5 => decode_banded(data),
         _ => FrameDecoder::new().decode(&EncodedChunk::from_bytes(data)?),
     }
 }
@@ -1551,4 +1552,153 @@ pub unsafe fn requant_symbols_device(d_src: *const std::ffi::c_void, d_dst: *mut
                                      step_to: i32, d_hist: *mut std::ffi::c_void, hip_stream: *mut std::ffi::c_void)
     -> Result<(), CodecError> {
     check(alice_codec_dev_requant_symbols(d_src, d_dst, n, wide as c_int, step_from, step_to, d_hist, hip_stream), 0, 0)
+}
+
+// ---- banded format (.alc version 5): one frequency table per wavelet subband ----
+pub const BANDED_HEADER_BYTES: usize = 12636;
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+struct RawBandedInfo {
+    width: u32, height: u32, frames: u32, lane_symbols: u32,
+    wavelet: u8, base: u8, reserved: [u8; 2],
+    quant_step: [i32; 3], dead_zone: [i32; 3],
+    num_symbols: [u32; 3], n_blocks: [u32; 24], payload_len: [u64; 24],
+}
+
+extern "C" {
+    fn alice_codec_banded_stream_bound(n_band: u64, lane_symbols: u32, base: u8) -> u64;
+    fn alice_codec_banded_info(data: *const u8, len: u64, info: *mut RawBandedInfo) -> c_int;
+    fn alice_codec_encode_banded(encoder: *const RawEncoder, rgb: *const u8, rgb_len: u64, width: u32, height: u32, frames: u32,
+                                 lane_symbols: u32, base: u8, out_len: *mut u64) -> *mut u8;
+    fn alice_codec_decode_banded(data: *const u8, len: u64, out_len: *mut u64) -> *mut u8;
+    fn alice_codec_to_banded(data: *const u8, len: u64, lane_symbols: u32, out_len: *mut u64) -> *mut u8;
+    fn alice_codec_from_banded(data: *const u8, len: u64, lane_symbols: u32, out_len: *mut u64) -> *mut u8;
+    fn alice_codec_dev_encode_banded(d_rgb: *const std::ffi::c_void, width: u32, height: u32, frames: u32, n_chunks: u32, wavelet_type: u8,
+                                     quality: u8, qualities: *const u8, lane_symbols: u32, base: u8, d_out: *mut std::ffi::c_void,
+                                     out_stride: u64, sizes: *mut u64, hip_stream: *mut std::ffi::c_void) -> c_int;
+    fn alice_codec_dev_decode_banded(d_alc: *const std::ffi::c_void, alc_stride: u64, sizes: *const u64, n_chunks: u32,
+                                     d_rgb_out: *mut std::ffi::c_void, hip_stream: *mut std::ffi::c_void) -> c_int;
+    fn alice_codec_dev_to_banded(d_alc: *const std::ffi::c_void, alc_stride: u64, sizes: *const u64, n_chunks: u32, lane_symbols: u32,
+                                 d_out: *mut std::ffi::c_void, out_stride: u64, out_sizes: *mut u64, hip_stream: *mut std::ffi::c_void) -> c_int;
+    fn alice_codec_dev_from_banded(d_alc: *const std::ffi::c_void, alc_stride: u64, sizes: *const u64, n_chunks: u32, lane_symbols: u32,
+                                   d_out: *mut std::ffi::c_void, out_stride: u64, out_sizes: *mut u64, hip_stream: *mut std::ffi::c_void) -> c_int;
+    fn alice_codec_dev_band_histograms(d_symbols: *const std::ffi::c_void, width: u32, height: u32, frames: u32, wide: c_int,
+                                       d_hist: *mut std::ffi::c_void, hip_stream: *mut std::ffi::c_void) -> c_int;
+}
+
+/// The validated header of a version 5 container; `n_blocks` and `payload_len` are channel-major, band ascending.
+#[derive(Debug, Clone, PartialEq, Eq)]
+pub struct BandedInfo {
+    pub width: u32, pub height: u32, pub frames: u32, pub lane_symbols: u32,
+    pub wavelet_type: WaveletType, pub base: u8,
+    pub quant_step: [i32; 3], pub dead_zone: [i32; 3], pub num_symbols: [u32; 3],
+    pub n_blocks: [u32; 24], pub payload_len: [u64; 24],
+}
+
+pub fn banded_info(data: &[u8]) -> Result<BandedInfo, CodecError> {
+    let mut c = RawBandedInfo { width: 0, height: 0, frames: 0, lane_symbols: 0, wavelet: 0, base: 0, reserved: [0; 2], quant_step: [0; 3],
+                                dead_zone: [0; 3], num_symbols: [0; 3], n_blocks: [0; 24], payload_len: [0; 24] };
+    let rc = unsafe { alice_codec_banded_info(data.as_ptr(), data.len() as u64, &mut c) };
+    check(rc, 0, data.len())?;
+    Ok(BandedInfo {
+        width: c.width, height: c.height, frames: c.frames, lane_symbols: c.lane_symbols,
+        wavelet_type: match c.wavelet { 1 => WaveletType::Cdf97, 2 => WaveletType::Haar, _ => WaveletType::Cdf53 }, base: c.base,
+        quant_step: c.quant_step, dead_zone: c.dead_zone, num_symbols: c.num_symbols, n_blocks: c.n_blocks, payload_len: c.payload_len,
+    })
+}
+
+pub fn banded_stream_bound(n_band: u64, lane_symbols: u32, base: u8) -> u64 { unsafe { alice_codec_banded_stream_bound(n_band, lane_symbols, base) } }
+
+/// One chunk as version 5 bytes of `base` (2, 3 or 4), with the encoder's wavelet and quality (`lane_symbols` 0: the default).
+pub fn encode_banded(encoder: &FrameEncoder, rgb_frames: &[u8], width: u32, height: u32, frames: u32, lane_symbols: u32, base: u8)
+    -> Result<Vec<u8>, CodecError> {
+    let mut n = 0u64;
+    unsafe {
+        let e = alice_codec_encoder_create_ex(encoder.quality, encoder.wavelet_type as u8);
+        let p = alice_codec_encode_banded(e, rgb_frames.as_ptr(), rgb_frames.len() as u64, width, height, frames, lane_symbols, base, &mut n);
+        alice_codec_encoder_destroy(e);
+        if p.is_null() {
+            let expected = (width as usize).saturating_mul(height as usize).saturating_mul(frames as usize).saturating_mul(3);
+            return Err(last_error(expected, rgb_frames.len(), width, height, 0));
+        }
+        Ok(take(p, n))
+    }
+}
+
+/// The RGB bytes of a version 5 container: the pixels of its base version's chunk.
+pub fn decode_banded(data: &[u8]) -> Result<Vec<u8>, CodecError> {
+    let mut n = 0u64;
+    unsafe {
+        let p = alice_codec_decode_banded(data.as_ptr(), data.len() as u64, &mut n);
+        if p.is_null() { Err(last_error(0, data.len(), 0, 0, 0)) } else { Ok(take(p, n)) }
+    }
+}
+
+/// A version 2, 3 or 4 container as the version 5 container of that base, from its symbols alone (`lane_symbols` 0 keeps it).
+pub fn to_banded(data: &[u8], lane_symbols: u32) -> Result<Vec<u8>, CodecError> {
+    let mut n = 0u64;
+    unsafe {
+        let p = alice_codec_to_banded(data.as_ptr(), data.len() as u64, lane_symbols, &mut n);
+        if p.is_null() { Err(last_error(0, data.len(), 0, 0, 0)) } else { Ok(take(p, n)) }
+    }
+}
+
+/// A version 5 container as the container of its base version: `from_banded(to_banded(x)) == x`.
+pub fn from_banded(data: &[u8], lane_symbols: u32) -> Result<Vec<u8>, CodecError> {
+    let mut n = 0u64;
+    unsafe {
+        let p = alice_codec_from_banded(data.as_ptr(), data.len() as u64, lane_symbols, &mut n);
+        if p.is_null() { Err(last_error(0, data.len(), 0, 0, 0)) } else { Ok(take(p, n)) }
+    }
+}
+
+/// # Safety
+/// As `split_encode_device`.
+pub unsafe fn banded_encode_device(d_rgb: *const std::ffi::c_void, width: u32, height: u32, frames: u32, n_chunks: u32,
+                                   wavelet_type: WaveletType, quality: u8, qualities: Option<&[u8]>, lane_symbols: u32, base: u8,
+                                   d_out: *mut std::ffi::c_void, out_stride: u64, hip_stream: *mut std::ffi::c_void)
+    -> Result<Vec<u64>, CodecError> {
+    if let Some(q) = qualities { if q.len() != n_chunks as usize { return Err(CodecError::InvalidDimensions { width, height }); } }
+    let mut sizes = vec![0u64; n_chunks as usize];
+    check(alice_codec_dev_encode_banded(d_rgb, width, height, frames, n_chunks, wavelet_type as u8, quality,
+                                        qualities.map_or(std::ptr::null(), |q| q.as_ptr()), lane_symbols, base, d_out, out_stride,
+                                        sizes.as_mut_ptr(), hip_stream), 0, 0).map(|_| sizes)
+}
+
+/// # Safety
+/// As `split_decode_device`.
+pub unsafe fn banded_decode_device(d_alc: *const std::ffi::c_void, alc_stride: u64, sizes: &[u64], d_rgb_out: *mut std::ffi::c_void,
+                                   hip_stream: *mut std::ffi::c_void) -> Result<(), CodecError> {
+    let n = u32::try_from(sizes.len()).unwrap_or(u32::MAX);
+    check(alice_codec_dev_decode_banded(d_alc, alc_stride, sizes.as_ptr(), n, d_rgb_out, hip_stream), 0, 0)
+}
+
+/// # Safety
+/// As `transcode_device`.
+pub unsafe fn to_banded_device(d_alc: *const std::ffi::c_void, alc_stride: u64, sizes: &[u64], lane_symbols: u32, d_out: *mut std::ffi::c_void,
+                               out_stride: u64, hip_stream: *mut std::ffi::c_void) -> Result<Vec<u64>, CodecError> {
+    let mut out = vec![0u64; sizes.len()];
+    let n = u32::try_from(sizes.len()).unwrap_or(u32::MAX);
+    check(alice_codec_dev_to_banded(d_alc, alc_stride, sizes.as_ptr(), n, lane_symbols, d_out, out_stride, out.as_mut_ptr(), hip_stream), 0, 0)
+        .map(|_| out)
+}
+
+/// # Safety
+/// As `transcode_device`.
+pub unsafe fn from_banded_device(d_alc: *const std::ffi::c_void, alc_stride: u64, sizes: &[u64], lane_symbols: u32, d_out: *mut std::ffi::c_void,
+                                 out_stride: u64, hip_stream: *mut std::ffi::c_void) -> Result<Vec<u64>, CodecError> {
+    let mut out = vec![0u64; sizes.len()];
+    let n = u32::try_from(sizes.len()).unwrap_or(u32::MAX);
+    check(alice_codec_dev_from_banded(d_alc, alc_stride, sizes.as_ptr(), n, lane_symbols, d_out, out_stride, out.as_mut_ptr(), hip_stream), 0, 0)
+        .map(|_| out)
+}
+
+/// Stage call: the 3 x 8 x 256 u32 band histograms (`wide`: of min(z, 255)) of one chunk's 3 * padded device symbols.
+///
+/// # Safety
+/// `d_symbols` holds the chunk's symbols and `d_hist` room for 6144 u32 on the current device.
+pub unsafe fn band_histograms_device(d_symbols: *const std::ffi::c_void, width: u32, height: u32, frames: u32, wide: bool,
+                                     d_hist: *mut std::ffi::c_void, hip_stream: *mut std::ffi::c_void) -> Result<(), CodecError> {
+    check(alice_codec_dev_band_histograms(d_symbols, width, height, frames, wide as c_int, d_hist, hip_stream), 0, 0)
 }

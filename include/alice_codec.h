@@ -912,6 +912,62 @@ int alice_codec_dev_transcode_to_budget(const void *d_alc, uint64_t alc_stride, 
 int alice_codec_dev_requant_symbols(const void *d_src, void *d_dst, uint64_t n, int wide, int32_t step_from, int32_t step_to,
                                     void *d_hist, void *hip_stream);
 
+/* ---- banded format (.alc version 5) ----
+ * Versions 2 to 4 code a channel with one frequency table; version 5 codes each of the channel's eight wavelet subbands (the
+ * octants of its [t'][yy][xx] symbol volume) with a table of its own.  A version 5 chunk names a BASE version 2, 3 or 4 and
+ * decodes to exactly the pixels of the base chunk made from the same input, wavelet and quality: colour, padding, lifting,
+ * quantiser, symbols and inverse are the base's, and so are the lanes, directories, end checks and (base >= 3) the escape
+ * step, applied to every band's symbols in band order.  At the sizes people store (160x96x16 and up) the same pixels take
+ * 10 to 45 % fewer bytes; the header is 12 636 bytes and every band carries its own directories, so a thumbnail-sized chunk
+ * grows instead: the format is for chunks.
+ * lane_symbols: a power of two in [64, 16384] (base 2) or [64, 8192] (bases 3 and 4), 0 for the default.
+ * Version 5 has no frame-range, preview, rectangle, batched, budget or transcode call: those keep refusing it with
+ * "unsupported version: 5".  The way to them is the repack below, back to the base version byte for byte.
+ * Validation of a container is host code, every failure ALICE_ERR_INVALID_BITSTREAM, in the order of DESIGN.md 20.3; lane
+ * directories and end checks belong to the decode kernel ("stream j", j = 24 * chunk + 8 * channel + band). */
+enum { ALICE_BANDED_HEADER_BYTES = 12636 };
+typedef struct AliceBandedInfo {
+    uint32_t width, height, frames, lane_symbols;
+    uint8_t wavelet, base, reserved[2];
+    int32_t quant_step[3], dead_zone[3];
+    uint32_t num_symbols[3];
+    uint32_t n_blocks[24];      /* channel-major, band k = 4 bt + 2 by + bx ascending inside a channel */
+    uint64_t payload_len[24];
+} AliceBandedInfo;
+/* The most bytes a band payload of n_band symbols takes (0: base, lane_symbols or n_band out of range) */
+uint64_t alice_codec_banded_stream_bound(uint64_t n_band, uint32_t lane_symbols, uint8_t base);
+/* One chunk in host memory (free the result with alice_codec_data_free64), NULL on error.  Validation order of the encode
+ * is alice_codec_encode_split's up to lane_symbols, then base (ALICE_ERR_INVALID_DIMENSIONS), then lane_symbols against the
+ * base's range. */
+uint8_t *alice_codec_encode_banded(const FrameEncoder *encoder, const uint8_t *rgb, uint64_t rgb_len, uint32_t width,
+                                   uint32_t height, uint32_t frames, uint32_t lane_symbols, uint8_t base, uint64_t *out_len);
+uint8_t *alice_codec_decode_banded(const uint8_t *data, uint64_t len, uint64_t *out_len);
+int alice_codec_banded_info(const uint8_t *data, uint64_t len, AliceBandedInfo *info);
+/* device-resident: alice_codec_dev_encode_wide / _dev_decode_wide for version 5 of `base`.  Groups hold at most 2730 chunks
+ * (24 jobs each); ALICE_BANDED_HEADER_BYTES + 24 * alice_codec_banded_stream_bound always suffices as out_stride.  The
+ * chunks of a decode agree in base, wavelet, shape and lane_symbols; d_alc may have any byte alignment. */
+int alice_codec_dev_encode_banded(const void *d_rgb, uint32_t width, uint32_t height, uint32_t frames, uint32_t n_chunks,
+                                  uint8_t wavelet_type, uint8_t quality, const uint8_t *qualities, uint32_t lane_symbols,
+                                  uint8_t base, void *d_out, uint64_t out_stride, uint64_t *sizes, void *hip_stream);
+int alice_codec_dev_decode_banded(const void *d_alc, uint64_t alc_stride, const uint64_t *sizes, uint32_t n_chunks,
+                                  void *d_rgb_out, void *hip_stream);
+/* Repack without pixels: a version 2, 3 or 4 chunk -> the version 5 chunk of that base (lane decode of every block, band
+ * histograms, band encode), and back (band decode, a 256-bin count of each channel, the base's encode).  No transform runs.
+ * lane_symbols: 0 keeps the source's.  alice_codec_from_banded(alice_codec_to_banded(x)) == x and alice_codec_to_banded of a
+ * base encode == alice_codec_encode_banded of the same input, byte for byte.  Every end check of the source runs; damage is
+ * ALICE_ERR_INVALID_BITSTREAM and nothing is written. */
+uint8_t *alice_codec_to_banded(const uint8_t *data, uint64_t len, uint32_t lane_symbols, uint64_t *out_len);
+uint8_t *alice_codec_from_banded(const uint8_t *data, uint64_t len, uint32_t lane_symbols, uint64_t *out_len);
+/* The same on the device, shaped as alice_codec_dev_transcode without the quality and version arguments. */
+int alice_codec_dev_to_banded(const void *d_alc, uint64_t alc_stride, const uint64_t *sizes, uint32_t n_chunks, uint32_t lane_symbols,
+                              void *d_out, uint64_t out_stride, uint64_t *out_sizes, void *hip_stream);
+int alice_codec_dev_from_banded(const void *d_alc, uint64_t alc_stride, const uint64_t *sizes, uint32_t n_chunks, uint32_t lane_symbols,
+                                void *d_out, uint64_t out_stride, uint64_t *out_sizes, void *hip_stream);
+/* Stage call: the symbols [3][pf][ph][pw] of one chunk's padded volume (u8; wide != 0: u16 at an even address) -> d_hist,
+ * 3 x 8 x 256 u32 on the device (overwritten): the histogram of every band, wide: of min(z, 255).  Finished on return. */
+int alice_codec_dev_band_histograms(const void *d_symbols, uint32_t width, uint32_t height, uint32_t frames, int wide,
+                                    void *d_hist, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

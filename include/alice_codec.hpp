@@ -728,11 +728,13 @@ inline void reversible_decode_regions_device(const void* d_alc, uint64_t alc_str
                                                             d_frames_out, frame_width, frame_height, origins.data(), hip_stream));
 }
 // the RGB bytes of a container of any version: 1 (FrameDecoder), 2 (decode_split), 3 (decode_wide) or 4 (decode_reversible)
+inline std::vector<uint8_t> decode_banded(const std::vector<uint8_t>& data);   // version 5, below
 inline std::vector<uint8_t> decode_alc(const std::vector<uint8_t>& data) {
     const int version = alc_version(data);
     if (version == 2) return decode_split(data);
     if (version == 3) return decode_wide(data);
     if (version == 4) return decode_reversible(data);
+    if (version == 5) return decode_banded(data);
     return FrameDecoder::new_().decode(EncodedChunk::from_bytes(data));
 }
 
@@ -1153,6 +1155,99 @@ inline TranscodeChoices transcode_to_budget_device(const void* d_alc, uint64_t a
 inline void requant_symbols_device(const void* d_src, void* d_dst, uint64_t n, bool wide, int32_t step_from, int32_t step_to,
                                    void* d_hist = nullptr, void* hip_stream = nullptr) {
     detail::check(alice_codec_dev_requant_symbols(d_src, d_dst, n, wide ? 1 : 0, step_from, step_to, d_hist, hip_stream));
+}
+
+// ---- banded format (.alc version 5) ----
+// One frequency table per wavelet subband: the pixels of the base version (2, 3 or 4) in fewer bytes at chunk sizes (the
+// 12 636-byte header makes thumbnails larger).  Frame ranges, previews, rectangles, budgets and transcodes stay with the base
+// versions; from_banded returns the base chunk byte for byte.
+constexpr size_t BANDED_HEADER_BYTES = ALICE_BANDED_HEADER_BYTES;
+struct BandedInfo {   // the validated header of a version 5 container; n_blocks / payload_len: channel-major, band ascending
+    uint32_t width = 0, height = 0, frames = 0, lane_symbols = 0;
+    WaveletType wavelet_type = WaveletType::Cdf53;
+    uint8_t base = 2;
+    int32_t quant_step[3] = {0, 0, 0}, dead_zone[3] = {0, 0, 0};
+    uint32_t num_symbols[3] = {0, 0, 0}, n_blocks[24] = {};
+    uint64_t payload_len[24] = {};
+};
+inline BandedInfo banded_info(const uint8_t* data, size_t len) {
+    static const uint8_t empty = 0;
+    AliceBandedInfo c{};
+    detail::check(alice_codec_banded_info(data ? data : &empty, len, &c));
+    BandedInfo i;
+    i.width = c.width; i.height = c.height; i.frames = c.frames; i.lane_symbols = c.lane_symbols;
+    i.wavelet_type = static_cast<WaveletType>(c.wavelet); i.base = c.base;
+    for (int k = 0; k < 3; ++k) { i.quant_step[k] = c.quant_step[k]; i.dead_zone[k] = c.dead_zone[k]; i.num_symbols[k] = c.num_symbols[k]; }
+    for (int k = 0; k < 24; ++k) { i.n_blocks[k] = c.n_blocks[k]; i.payload_len[k] = c.payload_len[k]; }
+    return i;
+}
+inline BandedInfo banded_info(const std::vector<uint8_t>& v) { return banded_info(v.data(), v.size()); }
+inline uint64_t banded_stream_bound(uint64_t n_band, uint32_t lane_symbols = 512, uint8_t base = 2) {
+    return alice_codec_banded_stream_bound(n_band, lane_symbols, base);
+}
+inline std::vector<uint8_t> encode_banded(const FrameEncoder& enc, const std::vector<uint8_t>& rgb, uint32_t w, uint32_t h, uint32_t f,
+                                          uint32_t lane_symbols = 0, uint8_t base = 2) {
+    static const uint8_t empty = 0;
+    uint64_t n = 0;
+    uint8_t* p = alice_codec_encode_banded(enc.handle(), rgb.empty() ? &empty : rgb.data(), rgb.size(), w, h, f, lane_symbols, base, &n);
+    if (!p) detail::raise();
+    return detail::take(p, n);
+}
+inline std::vector<uint8_t> decode_banded(const std::vector<uint8_t>& data) {
+    static const uint8_t empty = 0;
+    uint64_t n = 0;
+    uint8_t* p = alice_codec_decode_banded(data.empty() ? &empty : data.data(), data.size(), &n);
+    if (!p) detail::raise(ALICE_ERR_INVALID_BITSTREAM);
+    return detail::take(p, n);
+}
+// repack without pixels: version 2, 3 or 4 -> version 5 of that base, and back, byte for byte what the encoders write
+inline std::vector<uint8_t> to_banded(const std::vector<uint8_t>& data, uint32_t lane_symbols = 0) {
+    static const uint8_t empty = 0;
+    uint64_t n = 0;
+    uint8_t* p = alice_codec_to_banded(data.empty() ? &empty : data.data(), data.size(), lane_symbols, &n);
+    if (!p) detail::raise(ALICE_ERR_INVALID_BITSTREAM);
+    return detail::take(p, n);
+}
+inline std::vector<uint8_t> from_banded(const std::vector<uint8_t>& data, uint32_t lane_symbols = 0) {
+    static const uint8_t empty = 0;
+    uint64_t n = 0;
+    uint8_t* p = alice_codec_from_banded(data.empty() ? &empty : data.data(), data.size(), lane_symbols, &n);
+    if (!p) detail::raise(ALICE_ERR_INVALID_BITSTREAM);
+    return detail::take(p, n);
+}
+inline std::vector<uint64_t> banded_encode_device(const void* d_rgb, uint32_t w, uint32_t h, uint32_t f, uint32_t n_chunks, WaveletType wt,
+                                                  uint8_t quality, void* d_out, uint64_t out_stride, const std::vector<uint8_t>& qualities = {},
+                                                  uint32_t lane_symbols = 0, uint8_t base = 2, void* hip_stream = nullptr) {
+    if (!qualities.empty() && qualities.size() != n_chunks) throw CodecError(ALICE_ERR_INVALID_BUFFER_SIZE, "one quality per chunk");
+    std::vector<uint64_t> sizes(n_chunks);
+    detail::check(alice_codec_dev_encode_banded(d_rgb, w, h, f, n_chunks, static_cast<uint8_t>(wt), quality,
+                                                qualities.empty() ? nullptr : qualities.data(), lane_symbols, base, d_out, out_stride,
+                                                sizes.data(), hip_stream));
+    return sizes;
+}
+inline void banded_decode_device(const void* d_alc, uint64_t alc_stride, const std::vector<uint64_t>& sizes, void* d_rgb_out,
+                                 void* hip_stream = nullptr) {
+    detail::check(alice_codec_dev_decode_banded(d_alc, alc_stride, sizes.data(), static_cast<uint32_t>(sizes.size()), d_rgb_out, hip_stream));
+}
+inline std::vector<uint64_t> to_banded_device(const void* d_alc, uint64_t alc_stride, const std::vector<uint64_t>& sizes, void* d_out,
+                                              uint64_t out_stride, uint32_t lane_symbols = 0, void* hip_stream = nullptr) {
+    std::vector<uint64_t> out(sizes.size(), 0);
+    static const uint64_t none = 0;
+    detail::check(alice_codec_dev_to_banded(d_alc, alc_stride, sizes.empty() ? &none : sizes.data(), (uint32_t)std::min<size_t>(sizes.size(), 0xFFFFFFFFu),
+                                            lane_symbols, d_out, out_stride, out.empty() ? nullptr : out.data(), hip_stream));
+    return out;
+}
+inline std::vector<uint64_t> from_banded_device(const void* d_alc, uint64_t alc_stride, const std::vector<uint64_t>& sizes, void* d_out,
+                                                uint64_t out_stride, uint32_t lane_symbols = 0, void* hip_stream = nullptr) {
+    std::vector<uint64_t> out(sizes.size(), 0);
+    static const uint64_t none = 0;
+    detail::check(alice_codec_dev_from_banded(d_alc, alc_stride, sizes.empty() ? &none : sizes.data(), (uint32_t)std::min<size_t>(sizes.size(), 0xFFFFFFFFu),
+                                              lane_symbols, d_out, out_stride, out.empty() ? nullptr : out.data(), hip_stream));
+    return out;
+}
+// stage call: the 3 x 8 x 256 u32 band histograms (wide: of min(z, 255)) of one chunk's 3 * padded device symbols
+inline void band_histograms_device(const void* d_symbols, uint32_t w, uint32_t h, uint32_t f, bool wide, void* d_hist, void* hip_stream = nullptr) {
+    detail::check(alice_codec_dev_band_histograms(d_symbols, w, h, f, wide ? 1 : 0, d_hist, hip_stream));
 }
 
 }  // namespace alice_codec
