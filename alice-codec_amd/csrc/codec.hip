@@ -3746,6 +3746,139 @@ uint32_t split_group(const ChunkDims& d, SplitFormat fmt = kFormatSplit) {
     return cap_group((uint32_t)std::min<uint64_t>(std::max<uint64_t>(g, 1), 21845));
 }
 
+// ---- the call skeleton of the container entry points of versions 2 to 5: what a call does around its
+// groups, written once.  The group bodies (split_encode_chunks, transcode_group, band_encode_chunks, ...) and every check
+// of the arguments stay with the entry points. ----
+
+// drains the stream before the buffers declared ahead of it go back to the pool, on every return
+struct StreamDrain {
+    hipStream_t st;
+    explicit StreamDrain(hipStream_t s) : st(s) {}
+    ~StreamDrain() { (void)hipStreamSynchronize(st); }
+    StreamDrain(const StreamDrain&) = delete;
+    StreamDrain& operator=(const StreamDrain&) = delete;
+};
+
+// One host buffer in, one host result out.  body(d_src, st, sizes, place) runs one group of one chunk on the uploaded
+// input; place(sizes, outs) is the single slot the group writes to.  *out and *out_len are written on success alone, and
+// the stream has drained before the device buffers go back to the pool, whichever way the call ends.
+template <typename Body>
+int host_one_result(const void* src, uint64_t src_len, uint8_t** out, uint64_t* out_len, Body body) {
+    hipStream_t st;
+    TRY(get_stream(&st));
+    DevBuf d_src, d_out;
+    StreamDrain drain(st);
+    TRY(d_src.alloc(src_len));
+    HIP_TRY(hipMemcpyAsync(d_src.p, src, src_len, hipMemcpyHostToDevice, st));
+    std::vector<uint64_t> sizes;
+    TRY(body(d_src.as<uint8_t>(), st, sizes, [&](const std::vector<uint64_t>& sz, std::vector<uint8_t*>& outs) -> int {
+        TRY(d_out.alloc(sz[0]));
+        outs[0] = d_out.as<uint8_t>();
+        return kOk;
+    }));
+    std::unique_ptr<uint8_t, decltype(&free)> host(host_result_alloc(sizes[0]), &free);   // freed on every failure below
+    if (!host) return fail(kOutOfMemory, "out of host memory");
+    TRY(copy_to_host(host.get(), d_out.p, sizes[0], st));
+    *out = host.release();
+    *out_len = sizes[0];
+    return kOk;
+}
+
+// The result of a chunk without pixels: fill(p) writes its `bytes` header bytes.  No device is looked for.
+template <typename Fill>
+int host_header_result(uint64_t bytes, uint8_t** out, uint64_t* out_len, Fill fill) {
+    *out = host_result_alloc(bytes);
+    if (!*out) return fail(kOutOfMemory, "out of host memory");
+    fill(*out);
+    *out_len = bytes;
+    return kOk;
+}
+
+// A validated host container of len bytes to `bytes` of pixels: decode(d_alc, d_rgb, st) runs on the uploaded container.
+// *out_len is written once the result has been allocated; a chunk without pixels needs no device.
+template <typename Decode>
+int host_decode_pixels(const uint8_t* data, uint64_t len, uint64_t bytes, uint8_t** out, uint64_t* out_len, Decode decode) {
+    std::unique_ptr<uint8_t, decltype(&free)> host(host_result_alloc(bytes), &free);   // freed on every failure below
+    if (!host) return fail(kOutOfMemory, "out of host memory");
+    *out_len = bytes;
+    if (bytes) {
+        hipStream_t st;
+        TRY(get_stream(&st));
+        DevBuf d_alc, d_rgb;
+        StreamDrain drain(st);
+        TRY(d_alc.alloc(len));
+        TRY(d_rgb.alloc(bytes));
+        HIP_TRY(hipMemcpyAsync(d_alc.p, data, len, hipMemcpyHostToDevice, st));
+        TRY(decode(d_alc.as<uint8_t>(), d_rgb.p, st));
+        TRY(copy_to_host(host.get(), d_rgb.p, bytes, st));
+    }
+    *out = host.release();
+    return kOk;
+}
+
+// The headers of n device containers at d_alc + i * alc_stride, read back and validated; nothing else has been queued by
+// then.  parse(raw, size, hdr[i], dims) is the format's parser on min(size, header_bytes) bytes (a shorter container leaves
+// the rest of its row zero); a chunk without pixels is refused; agree(hdr[0], hdr[i]) compares what the format adds to the
+// shape.  d: the shape of all of them; ptr[i]: chunk i's first byte on the device.
+template <typename Header, typename Parse, typename Agree>
+int read_device_headers(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks, size_t header_bytes, hipStream_t st,
+                        Parse parse, Agree agree, const char* agree_msg, std::vector<Header>& hdr, std::vector<const uint8_t*>& ptr,
+                        ChunkDims& d) {
+    std::vector<uint8_t> raw((size_t)n_chunks * header_bytes, 0);
+    for (uint32_t i = 0; i < n_chunks; ++i)
+        if (sizes[i])
+            HIP_TRY(hipMemcpyAsync(raw.data() + (size_t)i * header_bytes, (const uint8_t*)d_alc + (size_t)i * alc_stride,
+                                   std::min<uint64_t>(sizes[i], header_bytes), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    hdr.resize(n_chunks); ptr.resize(n_chunks);
+    for (uint32_t i = 0; i < n_chunks; ++i) {
+        ChunkDims di{};
+        TRY(parse(raw.data() + (size_t)i * header_bytes, sizes[i], hdr[i], di));
+        if (di.n_pixels == 0) return fail(kInvalidDimensions, "invalid dimensions");
+        if (i == 0) d = di;
+        else if (di.w != d.w || di.h != d.h || di.f != d.f || !agree(hdr[0], hdr[i])) return fail(kInvalidDimensions, agree_msg);
+        ptr[i] = (const uint8_t*)d_alc + (size_t)i * alc_stride;
+    }
+    return kOk;
+}
+
+// where the chunks of a device call go: chunk first + i at d_out + (first + i) * out_stride, refused before anything of
+// the group is written
+auto place_strided(void* d_out, uint64_t out_stride, uint32_t first, uint32_t B) {
+    return [=](const std::vector<uint64_t>& s, std::vector<uint8_t*>& outs) -> int {
+        for (uint32_t i = 0; i < B; ++i) {
+            if (s[i] > out_stride)
+                return fail(kInvalidBufferSize, "chunk " + std::to_string(first + i) + " needs " + std::to_string(s[i]) +
+                                                    " bytes, the output stride is " + std::to_string(out_stride));
+            outs[i] = (uint8_t*)d_out + (size_t)(first + i) * out_stride;
+        }
+        return kOk;
+    };
+}
+
+// fn(first, B, sz) on chunks [first, first + B) of n_chunks, `group` at a time; a group that succeeds leaves its sizes sz
+// in out_sizes (may be null: a decode), so a failure in group k leaves those of the groups before k written.
+template <typename Fn>
+int for_each_group(uint32_t n_chunks, uint32_t group, uint64_t* out_sizes, Fn fn) {
+    for (uint32_t first = 0; first < n_chunks; first += group) {
+        const uint32_t B = std::min(group, n_chunks - first);
+        std::vector<uint64_t> sz;
+        TRY(fn(first, B, sz));
+        for (uint32_t i = 0; out_sizes && i < B; ++i) out_sizes[first + i] = sz[i];
+    }
+    return kOk;
+}
+
+// The containers of a device call, after the entry point's own pointers: null argument, empty batch, then a chunk that
+// is longer than the stride (a single chunk has no stride to keep).
+int check_dev_containers(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks) {
+    if (!d_alc || !sizes) return fail(kNullArgument, "null argument");
+    if (n_chunks == 0) return fail(kInvalidDimensions, "empty batch");
+    for (uint32_t i = 0; i < n_chunks; ++i)
+        if (sizes[i] > alc_stride && n_chunks > 1) return fail(kInvalidBufferSize, "chunk " + std::to_string(i) + " is longer than the stride");
+    return kOk;
+}
+
 void write_empty_split(uint8_t* p, uint8_t wavelet, uint32_t w, uint32_t h, uint32_t f, uint32_t L, int32_t step, uint8_t version = 2) {
     memset(p, 0, kSplitHeaderBytes);
     memcpy(p, "ALCC", 4);
@@ -3836,23 +3969,9 @@ int split_choose_chunks(const RgbLayout* rgb, uint32_t n, const ChunkDims& d, ui
 // n equal-shaped chunks at their layouts -> version 2 (wide: version 3, reversible: version 4) bytes at d_out + i * out_stride, in groups of split_group.
 int split_encode_layouts(const RgbLayout* rgb, uint32_t n, const ChunkDims& d, uint8_t wavelet, const uint8_t* q, uint32_t L, void* d_out,
                          uint64_t out_stride, uint64_t* sizes, hipStream_t st, SplitFormat fmt = kFormatSplit) {
-    const uint32_t group = split_group(d, fmt);
-    for (uint32_t first = 0; first < n; first += group) {
-        const uint32_t B = std::min(group, n - first);
-        std::vector<uint64_t> sz;
-        TRY(split_encode_chunks(rgb + first, B, d, wavelet, q + first, L, st, sz,
-                                [&](const std::vector<uint64_t>& s, std::vector<uint8_t*>& outs) -> int {
-                                    for (uint32_t i = 0; i < B; ++i) {
-                                        if (s[i] > out_stride)
-                                            return fail(kInvalidBufferSize, "chunk " + std::to_string(first + i) + " needs " + std::to_string(s[i]) +
-                                                                                " bytes, the output stride is " + std::to_string(out_stride));
-                                        outs[i] = (uint8_t*)d_out + (size_t)(first + i) * out_stride;
-                                    }
-                                    return kOk;
-                                }, fmt));
-        for (uint32_t i = 0; i < B; ++i) sizes[first + i] = sz[i];
-    }
-    return kOk;
+    return for_each_group(n, split_group(d, fmt), sizes, [&](uint32_t first, uint32_t B, std::vector<uint64_t>& sz) {
+        return split_encode_chunks(rgb + first, B, d, wavelet, q + first, L, st, sz, place_strided(d_out, out_stride, first, B), fmt);
+    });
 }
 
 // Where the chunks of a device call live.  origins == NULL: n packed chunks back to back at d_frames.  Otherwise chunk i is
@@ -3892,29 +4011,18 @@ int check_split_args(uint8_t wavelet_type, uint32_t lane_symbols, uint32_t* L, S
 template <typename LayoutsOf>
 int split_decode_device(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks, hipStream_t st, LayoutsOf layouts_of,
                         int version = 2) {
-    std::vector<uint8_t> raw((size_t)n_chunks * kSplitHeaderBytes, 0);
-    for (uint32_t i = 0; i < n_chunks; ++i)
-        HIP_TRY(hipMemcpyAsync(raw.data() + (size_t)i * kSplitHeaderBytes, (const uint8_t*)d_alc + (size_t)i * alc_stride,
-                               std::min<uint64_t>(sizes[i], kSplitHeaderBytes), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    std::vector<SplitHeader> hdr(n_chunks);
-    std::vector<const uint8_t*> ptr(n_chunks);
+    std::vector<SplitHeader> hdr;
+    std::vector<const uint8_t*> ptr;
     ChunkDims d{};
-    for (uint32_t i = 0; i < n_chunks; ++i) {
-        ChunkDims di{};
-        TRY(parse_split_header(raw.data() + (size_t)i * kSplitHeaderBytes, sizes[i], hdr[i], &di, version));
-        if (di.n_pixels == 0) return fail(kInvalidDimensions, "invalid dimensions");
-        if (i == 0) d = di;
-        else if (di.w != d.w || di.h != d.h || di.f != d.f || hdr[i].lane_symbols != hdr[0].lane_symbols)
-            return fail(kInvalidDimensions, "the chunks of one call must have the same shape and lane_symbols");
-        ptr[i] = (const uint8_t*)d_alc + (size_t)i * alc_stride;
-    }
+    TRY(read_device_headers(d_alc, alc_stride, sizes, n_chunks, kSplitHeaderBytes, st,
+                            [&](const uint8_t* raw, uint64_t size, SplitHeader& h, ChunkDims& di) { return parse_split_header(raw, size, h, &di, version); },
+                            [](const SplitHeader& h0, const SplitHeader& hi) { return hi.lane_symbols == h0.lane_symbols; },
+                            "the chunks of one call must have the same shape and lane_symbols", hdr, ptr, d));
     std::vector<RgbLayout> layouts;
     TRY(layouts_of(d, layouts));
-    const uint32_t group = split_group(d, format_of_version(version));
-    for (uint32_t first = 0; first < n_chunks; first += group)
-        TRY(split_decode_chunks(hdr.data() + first, ptr.data() + first, std::min(group, n_chunks - first), d, layouts.data() + first, st));
-    return kOk;
+    return for_each_group(n_chunks, split_group(d, format_of_version(version)), nullptr, [&](uint32_t first, uint32_t B, std::vector<uint64_t>&) {
+        return split_decode_chunks(hdr.data() + first, ptr.data() + first, B, d, layouts.data() + first, st);
+    });
 }
 
 }  // namespace
@@ -4059,32 +4167,14 @@ static uint8_t* container_encode(const FrameEncoder* encoder, const uint8_t* rgb
         if (n_pixels) TRY(validate_encode_many(encoder, rgb, rgb_len, width, height, frames, 1, &none, &d));
         const uint32_t L = lane_symbols ? lane_symbols : kSplitDefaultLane;
         if (!split_lane_ok(L, fmt)) return fail(kInvalidDimensions, split_lane_msg(fmt));
-        if (n_pixels == 0) {
-            *out = host_result_alloc(kSplitHeaderBytes);
-            if (!*out) return fail(kOutOfMemory, "out of host memory");
-            write_empty_split(*out, encoder->wavelet, width, height, frames, L, quality_to_step(encoder->quality), format_version(fmt));
-            *out_len = kSplitHeaderBytes;
-            return kOk;
-        }
-        hipStream_t st;
-        TRY(get_stream(&st));
-        DevBuf d_rgb, d_out;
-        TRY(d_rgb.alloc(n_pixels * 3));
-        HIP_TRY(hipMemcpyAsync(d_rgb.p, rgb, n_pixels * 3, hipMemcpyHostToDevice, st));
-        const RgbLayout layout = packed_rgb(d_rgb.p, d);
-        std::vector<uint64_t> sizes;
-        TRY(split_encode_chunks(&layout, 1, d, encoder->wavelet, &encoder->quality, L, st, sizes,
-                                [&](const std::vector<uint64_t>& sz, std::vector<uint8_t*>& outs) -> int {
-                                    TRY(d_out.alloc(sz[0]));
-                                    outs[0] = d_out.as<uint8_t>();
-                                    return kOk;
-                                }, fmt));
-        *out = host_result_alloc(sizes[0]);
-        if (!*out) return fail(kOutOfMemory, "out of host memory");
-        const int rc = copy_to_host(*out, d_out.p, sizes[0], st);
-        if (rc != kOk) { free(*out); *out = nullptr; return rc; }
-        *out_len = sizes[0];
-        return kOk;
+        if (n_pixels == 0)
+            return host_header_result(kSplitHeaderBytes, out, out_len, [&](uint8_t* p) {
+                write_empty_split(p, encoder->wavelet, width, height, frames, L, quality_to_step(encoder->quality), format_version(fmt));
+            });
+        return host_one_result(rgb, n_pixels * 3, out, out_len, [&](const uint8_t* d_rgb, hipStream_t st, std::vector<uint64_t>& sizes, auto place) {
+            const RgbLayout layout = packed_rgb(d_rgb, d);
+            return split_encode_chunks(&layout, 1, d, encoder->wavelet, &encoder->quality, L, st, sizes, place, fmt);
+        });
     };
     uint8_t* out = nullptr;
     return run(&out) == kOk ? out : nullptr;
@@ -4103,26 +4193,11 @@ static uint8_t* container_decode(const uint8_t* data, uint64_t len, uint64_t* ou
         ChunkDims d{};
         TRY(parse_split_header(data, len, h, &d, version));
         TRY(check_split_directories(data, h));
-        const uint64_t bytes = (uint64_t)h.width * h.height * h.frames * 3;
-        *out = host_result_alloc(bytes);
-        if (!*out) return fail(kOutOfMemory, "out of host memory");
-        *out_len = bytes;
-        if (!bytes) return kOk;
-        auto body = [&]() -> int {
-            hipStream_t st;
-            TRY(get_stream(&st));
-            DevBuf d_alc, d_rgb;
-            TRY(d_alc.alloc(len));
-            TRY(d_rgb.alloc(bytes));
-            HIP_TRY(hipMemcpyAsync(d_alc.p, data, len, hipMemcpyHostToDevice, st));
-            const uint8_t* p = d_alc.as<uint8_t>();
-            const RgbLayout layout = packed_rgb(d_rgb.p, d);
-            TRY(split_decode_chunks(&h, &p, 1, d, &layout, st));
-            return copy_to_host(*out, d_rgb.p, bytes, st);
-        };
-        const int rc = body();
-        if (rc != kOk) { free(*out); *out = nullptr; }
-        return rc;
+        return host_decode_pixels(data, len, (uint64_t)h.width * h.height * h.frames * 3, out, out_len,
+                                  [&](const uint8_t* d_alc, void* d_rgb, hipStream_t st) {
+                                      const RgbLayout layout = packed_rgb(d_rgb, d);
+                                      return split_decode_chunks(&h, &d_alc, 1, d, &layout, st);
+                                  });
     };
     uint8_t* out = nullptr;
     return run(&out) == kOk ? out : nullptr;
@@ -4162,10 +4237,8 @@ int alice_codec_dev_encode_split(const void* d_rgb, uint32_t width, uint32_t hei
 static int container_dev_decode(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks, void* d_rgb_out,
                                 void* hip_stream, int version) {
     clear_error();
-    if (!d_alc || !sizes || !d_rgb_out) return fail(kNullArgument, "null argument");
-    if (n_chunks == 0) return fail(kInvalidDimensions, "empty batch");
-    for (uint32_t i = 0; i < n_chunks; ++i)
-        if (sizes[i] > alc_stride && n_chunks > 1) return fail(kInvalidBufferSize, "chunk " + std::to_string(i) + " is longer than the stride");
+    if (!d_rgb_out) return fail(kNullArgument, "null argument");
+    TRY(check_dev_containers(d_alc, alc_stride, sizes, n_chunks));
     TRY(ensure_device());
     hipStream_t st = (hipStream_t)hip_stream;
     ScopeStream scope(st);
@@ -4325,32 +4398,16 @@ static uint8_t* container_encode_to_size(uint8_t wavelet_type, const uint8_t* rg
             tl_split_trials.assign(1, 0u);
             TRY(split_choose_quality(lo, hi, max_bytes, min_q, max_q, [](uint8_t, uint64_t*) -> int { return kOk; }, chosen_q, fits,
                                      &tl_split_trials[0]));
-            *out = host_result_alloc(kSplitHeaderBytes);
-            if (!*out) return fail(kOutOfMemory, "out of host memory");
-            write_empty_split(*out, wavelet_type, width, height, frames, L, quality_to_step(*chosen_q), format_version(fmt));
-            *out_len = kSplitHeaderBytes;
-            return kOk;
+            return host_header_result(kSplitHeaderBytes, out, out_len, [&](uint8_t* p) {
+                write_empty_split(p, wavelet_type, width, height, frames, L, quality_to_step(*chosen_q), format_version(fmt));
+            });
         }
-        hipStream_t st;
-        TRY(get_stream(&st));
-        DevBuf d_rgb, d_out;
-        TRY(d_rgb.alloc(n_pixels * 3));
-        HIP_TRY(hipMemcpyAsync(d_rgb.p, rgb, n_pixels * 3, hipMemcpyHostToDevice, st));
-        const RgbLayout layout = packed_rgb(d_rgb.p, d);
-        TRY(split_choose_chunks(&layout, 1, d, wavelet_type, L, &max_bytes, min_q, max_q, chosen_q, fits, st, fmt));
-        std::vector<uint64_t> sizes;
-        TRY(split_encode_chunks(&layout, 1, d, wavelet_type, chosen_q, L, st, sizes,
-                                [&](const std::vector<uint64_t>& sz, std::vector<uint8_t*>& outs) -> int {
-                                    TRY(d_out.alloc(sz[0]));
-                                    outs[0] = d_out.as<uint8_t>();
-                                    return kOk;
-                                }, fmt));
-        *out = host_result_alloc(sizes[0]);
-        if (!*out) return fail(kOutOfMemory, "out of host memory");
-        const int rc = copy_to_host(*out, d_out.p, sizes[0], st);
-        if (rc != kOk) { free(*out); *out = nullptr; return rc; }
-        *out_len = sizes[0];
-        return kOk;
+        // (*chosen_q and *fits are the chooser's own outputs, here as in the branch above: written before the encode)
+        return host_one_result(rgb, n_pixels * 3, out, out_len, [&](const uint8_t* d_rgb, hipStream_t st, std::vector<uint64_t>& sizes, auto place) -> int {
+            const RgbLayout layout = packed_rgb(d_rgb, d);
+            TRY(split_choose_chunks(&layout, 1, d, wavelet_type, L, &max_bytes, min_q, max_q, chosen_q, fits, st, fmt));
+            return split_encode_chunks(&layout, 1, d, wavelet_type, chosen_q, L, st, sizes, place, fmt);
+        });
     };
     uint8_t* out = nullptr;
     return run(&out) == kOk ? out : nullptr;
@@ -4789,33 +4846,18 @@ uint8_t* alice_codec_encode_to_psnr(uint8_t format, uint8_t wavelet_type, const 
             tl_quality_trials.assign(1, 0u);
             TRY(quality_choose(0, min_psnr_db, min_q, max_q, [](uint8_t, uint64_t* s) -> int { *s = 0; return kOk; }, &q, &ok, &sse,
                                &tl_quality_trials[0]));
-            *out = host_result_alloc(kSplitHeaderBytes);
-            if (!*out) return fail(kOutOfMemory, "out of host memory");
-            write_empty_split(*out, wavelet_type, width, height, frames, L, quality_to_step(q), format_version(fmt));
-            *out_len = kSplitHeaderBytes;
+            TRY(host_header_result(kSplitHeaderBytes, out, out_len, [&](uint8_t* p) {
+                write_empty_split(p, wavelet_type, width, height, frames, L, quality_to_step(q), format_version(fmt));
+            }));
             *chosen_q = q; *reached = ok; *psnr = alice_codec_psnr_from_sse(0, 0);
             return kOk;
         }
-        hipStream_t st;
-        TRY(get_stream(&st));
-        DevBuf d_rgb, d_out;
-        TRY(d_rgb.alloc(n_pixels * 3));
-        HIP_TRY(hipMemcpyAsync(d_rgb.p, rgb, n_pixels * 3, hipMemcpyHostToDevice, st));
-        const RgbLayout layout = packed_rgb(d_rgb.p, d);
         double db = 0.0;
-        TRY(quality_choose_chunks(&layout, 1, d, wavelet_type, min_psnr_db, min_q, max_q, &q, &ok, &db, st, fmt));
-        std::vector<uint64_t> sizes;
-        TRY(split_encode_chunks(&layout, 1, d, wavelet_type, &q, L, st, sizes,
-                                [&](const std::vector<uint64_t>& sz, std::vector<uint8_t*>& outs) -> int {
-                                    TRY(d_out.alloc(sz[0]));
-                                    outs[0] = d_out.as<uint8_t>();
-                                    return kOk;
-                                }, fmt));
-        *out = host_result_alloc(sizes[0]);
-        if (!*out) return fail(kOutOfMemory, "out of host memory");
-        const int rc = copy_to_host(*out, d_out.p, sizes[0], st);
-        if (rc != kOk) { free(*out); *out = nullptr; return rc; }
-        *out_len = sizes[0];
+        TRY(host_one_result(rgb, n_pixels * 3, out, out_len, [&](const uint8_t* d_rgb, hipStream_t st, std::vector<uint64_t>& sizes, auto place) -> int {
+            const RgbLayout layout = packed_rgb(d_rgb, d);
+            TRY(quality_choose_chunks(&layout, 1, d, wavelet_type, min_psnr_db, min_q, max_q, &q, &ok, &db, st, fmt));
+            return split_encode_chunks(&layout, 1, d, wavelet_type, &q, L, st, sizes, place, fmt);
+        }));
         *chosen_q = q; *reached = ok; *psnr = db;
         return kOk;
     };
@@ -6215,15 +6257,6 @@ int alice_codec_test_rects_outputs_disjoint(const alice_codec_rect_item* items, 
 
 namespace {
 
-// drains the stream before the buffers declared ahead of it go back to the pool, on every return
-struct StreamDrain {
-    hipStream_t st;
-    explicit StreamDrain(hipStream_t s) : st(s) {}
-    ~StreamDrain() { (void)hipStreamSynchronize(st); }
-    StreamDrain(const StreamDrain&) = delete;
-    StreamDrain& operator=(const StreamDrain&) = delete;
-};
-
 // The arguments every transcode call shares, after the header has been accepted: lane_symbols (0 keeps the source's),
 // then out_version (0 keeps the version; 3 and 4 are interchangeable, only the version byte differs).
 int transcode_check_args(const SplitHeader& h, uint32_t lane_symbols, uint8_t out_version, uint32_t* L, SplitFormat* fmt_out) {
@@ -6446,34 +6479,17 @@ uint8_t* transcode_host(const uint8_t* data, uint64_t len, uint8_t quality, uint
                 TRY(split_choose_quality(lo, hi, *max_bytes, min_q, max_q, [](uint8_t, uint64_t*) -> int { return kOk; }, &q, &ok, &trials));
                 tl_split_trials.assign(1, trials);
             }
-            *out = host_result_alloc(kSplitHeaderBytes);
-            if (!*out) return fail(kOutOfMemory, "out of host memory");
-            memcpy(*out, data, kSplitHeaderBytes);
-            transcode_empty(*out, h, quality_to_step(q), L, fmt_out);
-            *out_len = kSplitHeaderBytes;
-            if (max_bytes) { *chosen_q = q; *fits = ok; }
-            return kOk;
+            TRY(host_header_result(kSplitHeaderBytes, out, out_len, [&](uint8_t* p) {
+                memcpy(p, data, kSplitHeaderBytes);
+                transcode_empty(p, h, quality_to_step(q), L, fmt_out);
+            }));
+        } else {
+            TRY(host_one_result(data, len, out, out_len, [&](const uint8_t* d_alc, hipStream_t st, std::vector<uint64_t>& sizes, auto place) -> int {
+                TRY(transcode_group(&h, &d_alc, 1, d, &q, L, fmt_out, max_bytes, min_q, max_q, &ok, &trials, st, sizes, place));
+                if (max_bytes) tl_split_trials.assign(1, trials);   // (the trials of a group that ran, whatever becomes of the download)
+                return kOk;
+            }));
         }
-        hipStream_t st;
-        TRY(get_stream(&st));
-        DevBuf d_alc, d_out;
-        StreamDrain drain(st);
-        TRY(d_alc.alloc(len));
-        HIP_TRY(hipMemcpyAsync(d_alc.p, data, len, hipMemcpyHostToDevice, st));
-        const uint8_t* p = d_alc.as<uint8_t>();
-        std::vector<uint64_t> sizes;
-        TRY(transcode_group(&h, &p, 1, d, &q, L, fmt_out, max_bytes, min_q, max_q, &ok, &trials, st, sizes,
-                            [&](const std::vector<uint64_t>& sz, std::vector<uint8_t*>& outs) -> int {
-                                TRY(d_out.alloc(sz[0]));
-                                outs[0] = d_out.as<uint8_t>();
-                                return kOk;
-                            }));
-        if (max_bytes) tl_split_trials.assign(1, trials);
-        *out = host_result_alloc(sizes[0]);
-        if (!*out) return fail(kOutOfMemory, "out of host memory");
-        const int rc = copy_to_host(*out, d_out.p, sizes[0], st);
-        if (rc != kOk) { free(*out); *out = nullptr; return rc; }
-        *out_len = sizes[0];
         if (max_bytes) { *chosen_q = q; *fits = ok; }
         return kOk;
     };
@@ -6481,52 +6497,35 @@ uint8_t* transcode_host(const uint8_t* data, uint64_t len, uint8_t quality, uint
     return run(&out) == kOk ? out : nullptr;
 }
 
+// The headers of n device containers of any of the versions 2 to 4 (the transcodes, the repack to version 5): the chunks
+// agree in version, wavelet, shape and lane_symbols.
+int source_device_headers(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks, hipStream_t st,
+                          std::vector<SplitHeader>& hdr, std::vector<const uint8_t*>& ptr, ChunkDims& d) {
+    return read_device_headers(d_alc, alc_stride, sizes, n_chunks, kSplitHeaderBytes, st, frames_validate_header,
+                               [](const SplitHeader& h0, const SplitHeader& hi) {
+                                   return hi.fmt == h0.fmt && hi.wavelet == h0.wavelet && hi.lane_symbols == h0.lane_symbols;
+                               },
+                               "the chunks of one call must have the same version, wavelet, shape and lane_symbols", hdr, ptr, d);
+}
+
 // The device calls: the headers come to the host first, and nothing is queued before they and the arguments have been
-// accepted.  The chunks agree in version, wavelet, shape and lane_symbols.  budgets == NULL: chunk i at q[i].
+// accepted.  budgets == NULL: chunk i at q[i].
 int transcode_device(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks, uint8_t* q, uint32_t lane_symbols,
                      uint8_t out_version, const uint64_t* budgets, uint8_t min_q, uint8_t max_q, uint8_t* fits, void* d_out,
                      uint64_t out_stride, uint64_t* out_sizes, hipStream_t st) {
-    std::vector<uint8_t> raw((size_t)n_chunks * kSplitHeaderBytes, 0);
-    for (uint32_t i = 0; i < n_chunks; ++i)
-        if (sizes[i])
-            HIP_TRY(hipMemcpyAsync(raw.data() + (size_t)i * kSplitHeaderBytes, (const uint8_t*)d_alc + (size_t)i * alc_stride,
-                                   std::min<uint64_t>(sizes[i], kSplitHeaderBytes), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    std::vector<SplitHeader> hdr(n_chunks);
-    std::vector<const uint8_t*> ptr(n_chunks);
+    std::vector<SplitHeader> hdr;
+    std::vector<const uint8_t*> ptr;
     ChunkDims d{};
-    for (uint32_t i = 0; i < n_chunks; ++i) {
-        ChunkDims di{};
-        TRY(frames_validate_header(raw.data() + (size_t)i * kSplitHeaderBytes, sizes[i], hdr[i], di));
-        if (di.n_pixels == 0) return fail(kInvalidDimensions, "invalid dimensions");
-        if (i == 0) d = di;
-        else if (hdr[i].fmt != hdr[0].fmt || hdr[i].wavelet != hdr[0].wavelet || di.w != d.w || di.h != d.h || di.f != d.f ||
-                 hdr[i].lane_symbols != hdr[0].lane_symbols)
-            return fail(kInvalidDimensions, "the chunks of one call must have the same version, wavelet, shape and lane_symbols");
-        ptr[i] = (const uint8_t*)d_alc + (size_t)i * alc_stride;
-    }
+    TRY(source_device_headers(d_alc, alc_stride, sizes, n_chunks, st, hdr, ptr, d));
     uint32_t L = 0;
     SplitFormat fmt_out;
     TRY(transcode_check_args(hdr[0], lane_symbols, out_version, &L, &fmt_out));
     if (budgets) TRY(transcode_check_budget_format(fmt_out));
     std::vector<uint32_t> trials(n_chunks, 0u);
-    const uint32_t group = split_group(d, hdr[0].fmt);
-    for (uint32_t first = 0; first < n_chunks; first += group) {
-        const uint32_t B = std::min(group, n_chunks - first);
-        std::vector<uint64_t> sz;
-        TRY(transcode_group(hdr.data() + first, ptr.data() + first, B, d, q + first, L, fmt_out, budgets ? budgets + first : nullptr, min_q, max_q,
-                            fits ? fits + first : nullptr, trials.data() + first, st, sz,
-                            [&](const std::vector<uint64_t>& s, std::vector<uint8_t*>& outs) -> int {
-                                for (uint32_t i = 0; i < B; ++i) {
-                                    if (s[i] > out_stride)
-                                        return fail(kInvalidBufferSize, "chunk " + std::to_string(first + i) + " needs " + std::to_string(s[i]) +
-                                                                            " bytes, the output stride is " + std::to_string(out_stride));
-                                    outs[i] = (uint8_t*)d_out + (size_t)(first + i) * out_stride;
-                                }
-                                return kOk;
-                            }));
-        for (uint32_t i = 0; i < B; ++i) out_sizes[first + i] = sz[i];
-    }
+    TRY(for_each_group(n_chunks, split_group(d, hdr[0].fmt), out_sizes, [&](uint32_t first, uint32_t B, std::vector<uint64_t>& sz) {
+        return transcode_group(hdr.data() + first, ptr.data() + first, B, d, q + first, L, fmt_out, budgets ? budgets + first : nullptr, min_q, max_q,
+                               fits ? fits + first : nullptr, trials.data() + first, st, sz, place_strided(d_out, out_stride, first, B));
+    }));
     if (budgets) tl_split_trials = trials;
     return kOk;
 }
@@ -6577,19 +6576,12 @@ int alice_codec_predict_transcode_sizes(const uint8_t* data, uint64_t len, uint3
     return kOk;
 }
 
-static int dev_transcode_checks(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks, void* d_out, uint64_t* out_sizes) {
-    if (!d_alc || !sizes || !d_out || !out_sizes) return fail(kNullArgument, "null argument");
-    if (n_chunks == 0) return fail(kInvalidDimensions, "empty batch");
-    for (uint32_t i = 0; i < n_chunks; ++i)
-        if (sizes[i] > alc_stride && n_chunks > 1) return fail(kInvalidBufferSize, "chunk " + std::to_string(i) + " is longer than the stride");
-    return kOk;
-}
-
 int alice_codec_dev_transcode(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks, uint8_t quality,
                               const uint8_t* qualities, uint32_t lane_symbols, uint8_t out_version, void* d_out, uint64_t out_stride,
                               uint64_t* out_sizes, void* hip_stream) {
     clear_error();
-    TRY(dev_transcode_checks(d_alc, alc_stride, sizes, n_chunks, d_out, out_sizes));
+    if (!d_out || !out_sizes) return fail(kNullArgument, "null argument");
+    TRY(check_dev_containers(d_alc, alc_stride, sizes, n_chunks));
     TRY(ensure_device());
     hipStream_t st = (hipStream_t)hip_stream;
     ScopeStream scope(st);
@@ -6603,7 +6595,8 @@ int alice_codec_dev_transcode_to_budget(const void* d_alc, uint64_t alc_stride, 
                                         uint8_t out_version, const uint64_t* budgets, uint8_t min_q, uint8_t max_q, uint8_t* chosen,
                                         uint8_t* fits, void* d_out, uint64_t out_stride, uint64_t* out_sizes, void* hip_stream) {
     clear_error();
-    TRY(dev_transcode_checks(d_alc, alc_stride, sizes, n_chunks, d_out, out_sizes));
+    if (!d_out || !out_sizes) return fail(kNullArgument, "null argument");
+    TRY(check_dev_containers(d_alc, alc_stride, sizes, n_chunks));
     if (!budgets || !chosen || !fits) return fail(kNullArgument, "null argument");
     TRY(check_quality_range(min_q, max_q));
     TRY(ensure_device());
@@ -6662,6 +6655,11 @@ int alice_codec_test_symbol_bins(const void* d_symbols, uint64_t n, int wide, in
 // differs: each of a channel's eight subbands is coded as a channel of the base is, with its own table.  A job is one
 // (chunk, channel, band), so a call of B chunks runs 24 B jobs through one table launch, one count or decode launch and one
 // scan.  The repack goes between a base chunk and its banded twin through the symbols alone.
+//
+// This part holds the format (header, parser, directories), the band jobs and the group bodies (band_encode_chunks,
+// band_decode_chunks, to_banded_group, from_banded_group).  What a call does around its groups -- upload and download, the
+// header read-back, the group loop, placement at a stride, the container checks -- is the call skeleton ahead of the
+// version 2 entry points, shared with versions 2 to 4.
 // ------------------------------------------------------------------------------------------
 
 namespace {
@@ -6962,37 +6960,12 @@ int band_decode_chunks(const BandHeader* hdr, const uint8_t* const* d_alc, uint3
 // The headers of n device containers, read back and validated; the chunks agree in base, wavelet, shape and lane_symbols.
 int band_device_headers(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks, hipStream_t st,
                         std::vector<BandHeader>& hdr, std::vector<const uint8_t*>& ptr, ChunkDims& d) {
-    std::vector<uint8_t> raw((size_t)n_chunks * kBandHeaderBytes, 0);
-    for (uint32_t i = 0; i < n_chunks; ++i)
-        if (sizes[i])
-            HIP_TRY(hipMemcpyAsync(raw.data() + (size_t)i * kBandHeaderBytes, (const uint8_t*)d_alc + (size_t)i * alc_stride,
-                                   std::min<uint64_t>(sizes[i], kBandHeaderBytes), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    hdr.resize(n_chunks); ptr.resize(n_chunks);
-    for (uint32_t i = 0; i < n_chunks; ++i) {
-        ChunkDims di{};
-        TRY(parse_band_header(raw.data() + (size_t)i * kBandHeaderBytes, sizes[i], hdr[i], &di));
-        if (di.n_pixels == 0) return fail(kInvalidDimensions, "invalid dimensions");
-        if (i == 0) d = di;
-        else if (hdr[i].base != hdr[0].base || hdr[i].wavelet != hdr[0].wavelet || di.w != d.w || di.h != d.h || di.f != d.f ||
-                 hdr[i].lane_symbols != hdr[0].lane_symbols)
-            return fail(kInvalidDimensions, "the chunks of one call must have the same base, wavelet, shape and lane_symbols");
-        ptr[i] = (const uint8_t*)d_alc + (size_t)i * alc_stride;
-    }
-    return kOk;
-}
-
-// where the chunks of a device call go: chunk first + i at d_out + (first + i) * out_stride, refused before anything is written
-auto band_place_strided(void* d_out, uint64_t out_stride, uint32_t first, uint32_t B) {
-    return [=](const std::vector<uint64_t>& s, std::vector<uint8_t*>& outs) -> int {
-        for (uint32_t i = 0; i < B; ++i) {
-            if (s[i] > out_stride)
-                return fail(kInvalidBufferSize, "chunk " + std::to_string(first + i) + " needs " + std::to_string(s[i]) +
-                                                    " bytes, the output stride is " + std::to_string(out_stride));
-            outs[i] = (uint8_t*)d_out + (size_t)(first + i) * out_stride;
-        }
-        return kOk;
-    };
+    return read_device_headers(d_alc, alc_stride, sizes, n_chunks, kBandHeaderBytes, st,
+                               [](const uint8_t* raw, uint64_t size, BandHeader& h, ChunkDims& di) { return parse_band_header(raw, size, h, &di); },
+                               [](const BandHeader& h0, const BandHeader& hi) {
+                                   return hi.base == h0.base && hi.wavelet == h0.wavelet && hi.lane_symbols == h0.lane_symbols;
+                               },
+                               "the chunks of one call must have the same base, wavelet, shape and lane_symbols", hdr, ptr, d);
 }
 
 // ---- repack: between a base chunk and its banded twin through the symbols, no transform ----
@@ -7063,16 +7036,6 @@ int band_check_base_lane(uint8_t base, uint32_t lane_symbols, uint32_t* L, Split
     return kOk;
 }
 
-// a host result from a device buffer of `size` bytes
-int band_host_result(uint8_t** out, uint64_t* out_len, const DevBuf& d_out, uint64_t size, hipStream_t st) {
-    *out = host_result_alloc(size);
-    if (!*out) return fail(kOutOfMemory, "out of host memory");
-    const int rc = copy_to_host(*out, d_out.p, size, st);
-    if (rc != kOk) { free(*out); *out = nullptr; return rc; }
-    *out_len = size;
-    return kOk;
-}
-
 }  // namespace
 
 extern "C" {
@@ -7111,29 +7074,15 @@ uint8_t* alice_codec_encode_banded(const FrameEncoder* encoder, const uint8_t* r
         uint32_t L = 0;
         SplitFormat fmt;
         TRY(band_check_base_lane(base, lane_symbols, &L, &fmt));
-        if (n_pixels == 0) {
-            *out = host_result_alloc(kBandHeaderBytes);
-            if (!*out) return fail(kOutOfMemory, "out of host memory");
-            const int32_t s = quality_to_step(encoder->quality), steps[3] = {s, s, s};
-            write_empty_banded(*out, encoder->wavelet, width, height, frames, L, base, steps, steps);
-            *out_len = kBandHeaderBytes;
-            return kOk;
-        }
-        hipStream_t st;
-        TRY(get_stream(&st));
-        DevBuf d_rgb, d_out;
-        StreamDrain drain(st);
-        TRY(d_rgb.alloc(n_pixels * 3));
-        HIP_TRY(hipMemcpyAsync(d_rgb.p, rgb, n_pixels * 3, hipMemcpyHostToDevice, st));
-        const RgbLayout layout = packed_rgb(d_rgb.p, d);
-        std::vector<uint64_t> sizes;
-        TRY(band_encode_chunks(&layout, 1, d, encoder->wavelet, &encoder->quality, L, fmt, st, sizes,
-                               [&](const std::vector<uint64_t>& sz, std::vector<uint8_t*>& outs) -> int {
-                                   TRY(d_out.alloc(sz[0]));
-                                   outs[0] = d_out.as<uint8_t>();
-                                   return kOk;
-                               }));
-        return band_host_result(out, out_len, d_out, sizes[0], st);
+        if (n_pixels == 0)
+            return host_header_result(kBandHeaderBytes, out, out_len, [&](uint8_t* p) {
+                const int32_t s = quality_to_step(encoder->quality), steps[3] = {s, s, s};
+                write_empty_banded(p, encoder->wavelet, width, height, frames, L, base, steps, steps);
+            });
+        return host_one_result(rgb, n_pixels * 3, out, out_len, [&](const uint8_t* d_rgb, hipStream_t st, std::vector<uint64_t>& sizes, auto place) {
+            const RgbLayout layout = packed_rgb(d_rgb, d);
+            return band_encode_chunks(&layout, 1, d, encoder->wavelet, &encoder->quality, L, fmt, st, sizes, place);
+        });
     };
     uint8_t* out = nullptr;
     return run(&out) == kOk ? out : nullptr;
@@ -7147,27 +7096,11 @@ uint8_t* alice_codec_decode_banded(const uint8_t* data, uint64_t len, uint64_t* 
         ChunkDims d{};
         TRY(parse_band_header(data, len, h, &d));
         TRY(check_band_directories(data, h));
-        const uint64_t bytes = (uint64_t)h.width * h.height * h.frames * 3;
-        *out = host_result_alloc(bytes);
-        if (!*out) return fail(kOutOfMemory, "out of host memory");
-        *out_len = bytes;
-        if (!bytes) return kOk;
-        auto body = [&]() -> int {
-            hipStream_t st;
-            TRY(get_stream(&st));
-            DevBuf d_alc, d_rgb;
-            StreamDrain drain(st);
-            TRY(d_alc.alloc(len));
-            TRY(d_rgb.alloc(bytes));
-            HIP_TRY(hipMemcpyAsync(d_alc.p, data, len, hipMemcpyHostToDevice, st));
-            const uint8_t* p = d_alc.as<uint8_t>();
-            const RgbLayout layout = packed_rgb(d_rgb.p, d);
-            TRY(band_decode_chunks(&h, &p, 1, d, &layout, st));
-            return copy_to_host(*out, d_rgb.p, bytes, st);
-        };
-        const int rc = body();
-        if (rc != kOk) { free(*out); *out = nullptr; }
-        return rc;
+        return host_decode_pixels(data, len, (uint64_t)h.width * h.height * h.frames * 3, out, out_len,
+                                  [&](const uint8_t* d_alc, void* d_rgb, hipStream_t st) {
+                                      const RgbLayout layout = packed_rgb(d_rgb, d);
+                                      return band_decode_chunks(&h, &d_alc, 1, d, &layout, st);
+                                  });
     };
     uint8_t* out = nullptr;
     return run(&out) == kOk ? out : nullptr;
@@ -7193,23 +7126,16 @@ int alice_codec_dev_encode_banded(const void* d_rgb, uint32_t width, uint32_t he
         layouts[i] = packed_rgb((const uint8_t*)d_rgb + (size_t)i * d.n_pixels * 3, d);
         q[i] = qualities ? qualities[i] : quality;
     }
-    const uint32_t group = band_group(d, fmt);
-    for (uint32_t first = 0; first < n_chunks; first += group) {
-        const uint32_t B = std::min(group, n_chunks - first);
-        std::vector<uint64_t> sz;
-        TRY(band_encode_chunks(layouts.data() + first, B, d, wavelet_type, q.data() + first, L, fmt, st, sz, band_place_strided(d_out, out_stride, first, B)));
-        for (uint32_t i = 0; i < B; ++i) sizes[first + i] = sz[i];
-    }
-    return kOk;
+    return for_each_group(n_chunks, band_group(d, fmt), sizes, [&](uint32_t first, uint32_t B, std::vector<uint64_t>& sz) {
+        return band_encode_chunks(layouts.data() + first, B, d, wavelet_type, q.data() + first, L, fmt, st, sz, place_strided(d_out, out_stride, first, B));
+    });
 }
 
 int alice_codec_dev_decode_banded(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks, void* d_rgb_out,
                                   void* hip_stream) {
     clear_error();
-    if (!d_alc || !sizes || !d_rgb_out) return fail(kNullArgument, "null argument");
-    if (n_chunks == 0) return fail(kInvalidDimensions, "empty batch");
-    for (uint32_t i = 0; i < n_chunks; ++i)
-        if (sizes[i] > alc_stride && n_chunks > 1) return fail(kInvalidBufferSize, "chunk " + std::to_string(i) + " is longer than the stride");
+    if (!d_rgb_out) return fail(kNullArgument, "null argument");
+    TRY(check_dev_containers(d_alc, alc_stride, sizes, n_chunks));
     TRY(ensure_device());
     hipStream_t st = (hipStream_t)hip_stream;
     ScopeStream scope(st);
@@ -7219,10 +7145,9 @@ int alice_codec_dev_decode_banded(const void* d_alc, uint64_t alc_stride, const 
     TRY(band_device_headers(d_alc, alc_stride, sizes, n_chunks, st, hdr, ptr, d));
     std::vector<RgbLayout> layouts;
     TRY(split_layouts(d_rgb_out, 0, 0, nullptr, d, n_chunks, layouts));
-    const uint32_t group = band_group(d, hdr[0].fmt);
-    for (uint32_t first = 0; first < n_chunks; first += group)
-        TRY(band_decode_chunks(hdr.data() + first, ptr.data() + first, std::min(group, n_chunks - first), d, layouts.data() + first, st));
-    return kOk;
+    return for_each_group(n_chunks, band_group(d, hdr[0].fmt), nullptr, [&](uint32_t first, uint32_t B, std::vector<uint64_t>&) {
+        return band_decode_chunks(hdr.data() + first, ptr.data() + first, B, d, layouts.data() + first, st);
+    });
 }
 
 uint8_t* alice_codec_to_banded(const uint8_t* data, uint64_t len, uint32_t lane_symbols, uint64_t* out_len) {
@@ -7235,27 +7160,13 @@ uint8_t* alice_codec_to_banded(const uint8_t* data, uint64_t len, uint32_t lane_
         const uint32_t L = lane_symbols ? lane_symbols : h.lane_symbols;
         if (!split_lane_ok(L, h.fmt)) return fail(kInvalidDimensions, split_lane_msg(h.fmt));
         TRY(check_split_directories(data, h));
-        if (d.n_pixels == 0) {
-            *out = host_result_alloc(kBandHeaderBytes);
-            if (!*out) return fail(kOutOfMemory, "out of host memory");
-            write_empty_banded(*out, h.wavelet, h.width, h.height, h.frames, L, format_version(h.fmt), h.step, h.dead_zone);
-            *out_len = kBandHeaderBytes;
-            return kOk;
-        }
-        hipStream_t st;
-        TRY(get_stream(&st));
-        DevBuf d_alc, d_out;
-        StreamDrain drain(st);
-        TRY(d_alc.alloc(len));
-        HIP_TRY(hipMemcpyAsync(d_alc.p, data, len, hipMemcpyHostToDevice, st));
-        const uint8_t* p = d_alc.as<uint8_t>();
-        std::vector<uint64_t> sizes;
-        TRY(to_banded_group(&h, &p, 1, d, L, st, sizes, [&](const std::vector<uint64_t>& sz, std::vector<uint8_t*>& outs) -> int {
-            TRY(d_out.alloc(sz[0]));
-            outs[0] = d_out.as<uint8_t>();
-            return kOk;
-        }));
-        return band_host_result(out, out_len, d_out, sizes[0], st);
+        if (d.n_pixels == 0)
+            return host_header_result(kBandHeaderBytes, out, out_len, [&](uint8_t* p) {
+                write_empty_banded(p, h.wavelet, h.width, h.height, h.frames, L, format_version(h.fmt), h.step, h.dead_zone);
+            });
+        return host_one_result(data, len, out, out_len, [&](const uint8_t* d_alc, hipStream_t st, std::vector<uint64_t>& sizes, auto place) {
+            return to_banded_group(&h, &d_alc, 1, d, L, st, sizes, place);
+        });
     };
     uint8_t* out = nullptr;
     return run(&out) == kOk ? out : nullptr;
@@ -7271,31 +7182,17 @@ uint8_t* alice_codec_from_banded(const uint8_t* data, uint64_t len, uint32_t lan
         const uint32_t L = lane_symbols ? lane_symbols : h.lane_symbols;
         if (!split_lane_ok(L, h.fmt)) return fail(kInvalidDimensions, split_lane_msg(h.fmt));
         TRY(check_band_directories(data, h));
-        if (d.n_pixels == 0) {
-            *out = host_result_alloc(kSplitHeaderBytes);
-            if (!*out) return fail(kOutOfMemory, "out of host memory");
-            write_empty_split(*out, h.wavelet, h.width, h.height, h.frames, L, h.step[0], h.base);
-            for (int c = 0; c < 3; ++c) {
-                uint8_t* q = *out + kSplitFixedHeaderBytes + (size_t)c * kSplitChannelHeaderBytes;
-                put_u32(q, (uint32_t)h.step[c]); put_u32(q + 4, (uint32_t)h.dead_zone[c]);
-            }
-            *out_len = kSplitHeaderBytes;
-            return kOk;
-        }
-        hipStream_t st;
-        TRY(get_stream(&st));
-        DevBuf d_alc, d_out;
-        StreamDrain drain(st);
-        TRY(d_alc.alloc(len));
-        HIP_TRY(hipMemcpyAsync(d_alc.p, data, len, hipMemcpyHostToDevice, st));
-        const uint8_t* p = d_alc.as<uint8_t>();
-        std::vector<uint64_t> sizes;
-        TRY(from_banded_group(&h, &p, 1, d, L, st, sizes, [&](const std::vector<uint64_t>& sz, std::vector<uint8_t*>& outs) -> int {
-            TRY(d_out.alloc(sz[0]));
-            outs[0] = d_out.as<uint8_t>();
-            return kOk;
-        }));
-        return band_host_result(out, out_len, d_out, sizes[0], st);
+        if (d.n_pixels == 0)
+            return host_header_result(kSplitHeaderBytes, out, out_len, [&](uint8_t* p) {
+                write_empty_split(p, h.wavelet, h.width, h.height, h.frames, L, h.step[0], h.base);
+                for (int c = 0; c < 3; ++c) {
+                    uint8_t* q = p + kSplitFixedHeaderBytes + (size_t)c * kSplitChannelHeaderBytes;
+                    put_u32(q, (uint32_t)h.step[c]); put_u32(q + 4, (uint32_t)h.dead_zone[c]);
+                }
+            });
+        return host_one_result(data, len, out, out_len, [&](const uint8_t* d_alc, hipStream_t st, std::vector<uint64_t>& sizes, auto place) {
+            return from_banded_group(&h, &d_alc, 1, d, L, st, sizes, place);
+        });
     };
     uint8_t* out = nullptr;
     return run(&out) == kOk ? out : nullptr;
@@ -7304,45 +7201,27 @@ uint8_t* alice_codec_from_banded(const uint8_t* data, uint64_t len, uint32_t lan
 int alice_codec_dev_to_banded(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks, uint32_t lane_symbols,
                               void* d_out, uint64_t out_stride, uint64_t* out_sizes, void* hip_stream) {
     clear_error();
-    TRY(dev_transcode_checks(d_alc, alc_stride, sizes, n_chunks, d_out, out_sizes));
+    if (!d_out || !out_sizes) return fail(kNullArgument, "null argument");
+    TRY(check_dev_containers(d_alc, alc_stride, sizes, n_chunks));
     TRY(ensure_device());
     hipStream_t st = (hipStream_t)hip_stream;
     ScopeStream scope(st);
-    std::vector<uint8_t> raw((size_t)n_chunks * kSplitHeaderBytes, 0);
-    for (uint32_t i = 0; i < n_chunks; ++i)
-        if (sizes[i])
-            HIP_TRY(hipMemcpyAsync(raw.data() + (size_t)i * kSplitHeaderBytes, (const uint8_t*)d_alc + (size_t)i * alc_stride,
-                                   std::min<uint64_t>(sizes[i], kSplitHeaderBytes), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    std::vector<SplitHeader> hdr(n_chunks);
-    std::vector<const uint8_t*> ptr(n_chunks);
+    std::vector<SplitHeader> hdr;
+    std::vector<const uint8_t*> ptr;
     ChunkDims d{};
-    for (uint32_t i = 0; i < n_chunks; ++i) {
-        ChunkDims di{};
-        TRY(frames_validate_header(raw.data() + (size_t)i * kSplitHeaderBytes, sizes[i], hdr[i], di));
-        if (di.n_pixels == 0) return fail(kInvalidDimensions, "invalid dimensions");
-        if (i == 0) d = di;
-        else if (hdr[i].fmt != hdr[0].fmt || hdr[i].wavelet != hdr[0].wavelet || di.w != d.w || di.h != d.h || di.f != d.f ||
-                 hdr[i].lane_symbols != hdr[0].lane_symbols)
-            return fail(kInvalidDimensions, "the chunks of one call must have the same version, wavelet, shape and lane_symbols");
-        ptr[i] = (const uint8_t*)d_alc + (size_t)i * alc_stride;
-    }
+    TRY(source_device_headers(d_alc, alc_stride, sizes, n_chunks, st, hdr, ptr, d));
     const uint32_t L = lane_symbols ? lane_symbols : hdr[0].lane_symbols;
     if (!split_lane_ok(L, hdr[0].fmt)) return fail(kInvalidDimensions, split_lane_msg(hdr[0].fmt));
-    const uint32_t group = band_group(d, hdr[0].fmt);
-    for (uint32_t first = 0; first < n_chunks; first += group) {
-        const uint32_t B = std::min(group, n_chunks - first);
-        std::vector<uint64_t> sz;
-        TRY(to_banded_group(hdr.data() + first, ptr.data() + first, B, d, L, st, sz, band_place_strided(d_out, out_stride, first, B)));
-        for (uint32_t i = 0; i < B; ++i) out_sizes[first + i] = sz[i];
-    }
-    return kOk;
+    return for_each_group(n_chunks, band_group(d, hdr[0].fmt), out_sizes, [&](uint32_t first, uint32_t B, std::vector<uint64_t>& sz) {
+        return to_banded_group(hdr.data() + first, ptr.data() + first, B, d, L, st, sz, place_strided(d_out, out_stride, first, B));
+    });
 }
 
 int alice_codec_dev_from_banded(const void* d_alc, uint64_t alc_stride, const uint64_t* sizes, uint32_t n_chunks, uint32_t lane_symbols,
                                 void* d_out, uint64_t out_stride, uint64_t* out_sizes, void* hip_stream) {
     clear_error();
-    TRY(dev_transcode_checks(d_alc, alc_stride, sizes, n_chunks, d_out, out_sizes));
+    if (!d_out || !out_sizes) return fail(kNullArgument, "null argument");
+    TRY(check_dev_containers(d_alc, alc_stride, sizes, n_chunks));
     TRY(ensure_device());
     hipStream_t st = (hipStream_t)hip_stream;
     ScopeStream scope(st);
@@ -7352,14 +7231,9 @@ int alice_codec_dev_from_banded(const void* d_alc, uint64_t alc_stride, const ui
     TRY(band_device_headers(d_alc, alc_stride, sizes, n_chunks, st, hdr, ptr, d));
     const uint32_t L = lane_symbols ? lane_symbols : hdr[0].lane_symbols;
     if (!split_lane_ok(L, hdr[0].fmt)) return fail(kInvalidDimensions, split_lane_msg(hdr[0].fmt));
-    const uint32_t group = band_group(d, hdr[0].fmt);
-    for (uint32_t first = 0; first < n_chunks; first += group) {
-        const uint32_t B = std::min(group, n_chunks - first);
-        std::vector<uint64_t> sz;
-        TRY(from_banded_group(hdr.data() + first, ptr.data() + first, B, d, L, st, sz, band_place_strided(d_out, out_stride, first, B)));
-        for (uint32_t i = 0; i < B; ++i) out_sizes[first + i] = sz[i];
-    }
-    return kOk;
+    return for_each_group(n_chunks, band_group(d, hdr[0].fmt), out_sizes, [&](uint32_t first, uint32_t B, std::vector<uint64_t>& sz) {
+        return from_banded_group(hdr.data() + first, ptr.data() + first, B, d, L, st, sz, place_strided(d_out, out_stride, first, B));
+    });
 }
 
 int alice_codec_dev_band_histograms(const void* d_symbols, uint32_t width, uint32_t height, uint32_t frames, int wide, void* d_hist,

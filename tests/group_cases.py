@@ -5,13 +5,14 @@ Every chunk of a call differs from every other in content (a seeded smooth-plus-
 own), in quality and in budget, so that a result written to, or read from, another chunk's row or slot cannot pass.  Every
 expected value comes from the CPU references, chunk by chunk, each built once: the oracle's transform and quantiser, the
 containers of split_ref / wide_ref / reversible_ref, the brackets and the chooser of split_rate_ref / wide_rate_ref, the
-squared errors and the search of quality_ref, the maps of transcode_ref."""
+squared errors and the search of quality_ref, the maps of transcode_ref, the version 5 containers and repacks of banded_ref."""
 from __future__ import annotations
 
 import functools
 
 import numpy as np
 
+import banded_ref as B5
 import oracle.alice_oracle_np as o
 import quality_ref as Q
 import reversible_ref as R4
@@ -234,6 +235,67 @@ def transcode_budget_plan(version: int, shape: str):
         budget = _budget(TRANSCODE_BUDGETS[i], lo, hi, exact)
         out.append((budget,) + T.choose_transcode(src, budget, min_q, max_q))
     return out
+
+
+# ---- version 5: the banded twins of the containers above, one table per subband (banded_ref) ----
+
+BASES = (2, 3, 4)
+
+
+@functools.lru_cache(maxsize=None)
+def banded(base: int, shape: str, i: int, quality: int) -> bytes:
+    """what the banded encoder of this base writes for chunk i at this quality"""
+    w, h, f = SHAPES[shape]
+    step = SR.quality_to_step(quality)
+    return B5.write_container(base, KIND[base], w, h, f, L, (step,) * 3, (step,) * 3, symbols(base, shape, i, step))
+
+
+def bandeds(base: int, shape: str):
+    """the seven version 5 containers of a call at QUALITIES[base]"""
+    return [banded(base, shape, i, QUALITIES[base][i]) for i in range(N)]
+
+
+@functools.lru_cache(maxsize=None)
+def to_banded_plan(base: int, shape: str):
+    """-> [bytes] of containers(base, shape) repacked to version 5"""
+    return [B5.to_banded(b) for b in containers(base, shape)]
+
+
+@functools.lru_cache(maxsize=None)
+def from_banded_plan(base: int, shape: str):
+    """-> [bytes] of bandeds(base, shape) repacked to their base version"""
+    return [B5.from_banded(b) for b in bandeds(base, shape)]
+
+
+# ---- an output stride that is one byte short (cap 2) ----
+
+# The chunks of such a call in this order: BIG, whose output is the largest in every family, is chunk STRIDE_AT, the second
+# of the second group of two.  Its index in the call (3) is not its index in the group (1), and groups 2 and 3 are never run.
+STRIDE_CAP = 2
+STRIDE_ORDER = (0, 1, 2, BIG, 3, 5, 6)
+STRIDE_AT = 3
+STRIDE_FAMILIES = ("split", "wide", "reversible", "banded", "transcode", "to_banded", "from_banded")
+STRIDE_BANDED_BASE = 3                     # of the banded encode; the repacks take the two other bases
+STRIDE_VERSION = {"split": 2, "wide": 3, "reversible": 4, "banded": STRIDE_BANDED_BASE, "transcode": 3, "to_banded": 2, "from_banded": 4}
+
+
+def in_stride_order(items):
+    return [items[i] for i in STRIDE_ORDER]
+
+
+@functools.lru_cache(maxsize=None)
+def stride_plan(family: str, shape: str = "tile"):
+    """-> (inputs or None for the encodes from pixels, outputs) of the family's call, both in STRIDE_ORDER"""
+    v = STRIDE_VERSION[family]
+    if family in ("split", "wide", "reversible"):
+        return None, in_stride_order(containers(v, shape))
+    if family == "banded":
+        return None, in_stride_order(bandeds(v, shape))
+    if family == "transcode":
+        return in_stride_order(sources(v, shape)), in_stride_order(transcode_plan(v, shape))
+    if family == "to_banded":
+        return in_stride_order(containers(v, shape)), in_stride_order(to_banded_plan(v, shape))
+    return in_stride_order(bandeds(v, shape)), in_stride_order(from_banded_plan(v, shape))
 
 
 def damaged(blob: bytes) -> bytes:

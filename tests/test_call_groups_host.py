@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import banded_ref as B5  # noqa: E402
 import group_cases as G  # noqa: E402
 import split_rate_ref as SR  # noqa: E402
 import split_ref as R2  # noqa: E402
@@ -204,6 +205,32 @@ def test_transcode_plan(version, shape):
     assert [p[2] for p in plan].count(False) == 1
     assert plan[G.TRANSCODE_BUDGETS.index("nothing")][1:3] == (G.TRANSCODE_RANGE[0], False)
     assert plan[G.TRANSCODE_BUDGETS.index("everything")][1:4] == (G.TRANSCODE_RANGE[1], True, 0)
+
+
+@pytest.mark.parametrize("shape", list(G.SHAPES))
+@pytest.mark.parametrize("base", G.BASES)
+def test_banded_plan(base, shape):
+    blobs, plain = G.bandeds(base, shape), G.containers(base, shape)
+    assert _distinct(blobs) and all(b[4] == 5 and b[22] == base for b in blobs)
+    assert all(len(blobs[G.BIG]) > len(b) for i, b in enumerate(blobs) if i != G.BIG)
+    # the repacks are each other's inverse and meet the encoders' own bytes
+    assert G.to_banded_plan(base, shape) == blobs and G.from_banded_plan(base, shape) == plain
+    # a banded chunk decodes to its base chunk's pixels
+    i = G.BIG
+    assert np.array_equal(B5.decode(blobs[i]), G.pixels(base, shape, i, G.QUALITIES[base][i]))
+
+
+def test_stride_plan_is_one_byte_short_for_one_chunk_of_the_second_group():
+    assert sorted(G.STRIDE_ORDER) == list(range(G.N)) and G.STRIDE_ORDER[G.STRIDE_AT] == G.BIG
+    assert G.STRIDE_AT // G.STRIDE_CAP == 1 and G.STRIDE_AT % G.STRIDE_CAP == 1       # second chunk of the second group
+    assert G.STRIDE_ORDER[:G.STRIDE_CAP] == tuple(range(G.STRIDE_CAP))                # group 0 is chunks 0 and 1
+    assert {G.STRIDE_VERSION[f] for f in ("banded", "to_banded", "from_banded")} == set(G.BASES)
+    for family in G.STRIDE_FAMILIES:
+        inputs, want = G.stride_plan(family)
+        assert inputs is None or len(inputs) == G.N
+        short = len(want[G.STRIDE_AT]) - 1
+        assert [len(b) > short for b in want] == [i == G.STRIDE_AT for i in range(G.N)], family
+        assert _distinct(want[:G.STRIDE_CAP])
 
 
 def test_the_references_refuse_the_damaged_chunks():

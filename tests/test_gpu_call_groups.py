@@ -1,9 +1,10 @@
 """Calls of more than one group on the MI355X.  At the suite's shapes split_group() is 21845 chunks and chunks_that_fit()
-the whole call, so the group loops of the device-resident calls of versions 2-4 and of encode_many / decode_many make one
+the whole call, so the group loops of the device-resident calls of versions 2-5 and of encode_many / decode_many make one
 trip; the hook alice_codec_test_set_group_chunks makes groups of 1, 2 and 3 out of calls of seven chunks (7 x 1, 2 + 2 + 2 + 1,
 3 + 3 + 1).  Every chunk differs from every other in content, quality and budget (tests/group_cases.py, held to that by
 tests/test_call_groups_host.py), every expected value is the CPU reference's for that chunk, and every output lies between
-guard bytes.  Then the verdicts of a call whose second group fails, and decode groups that hold both band-slot widths."""
+guard bytes.  Then the verdicts of a call whose second group fails (every call that places its output at a stride refuses
+one that is a byte short), and decode groups that hold both band-slot widths."""
 import contextlib
 import ctypes as C
 import os
@@ -297,6 +298,36 @@ def test_version_1_host_calls(gpu_codec, oracle_mod, shape):
         assert np.array_equal(pixels[i], oracle_mod.decode(stored[i])), i
 
 
+# ---- 8. version 5: the banded encode and decode, the repack in both directions ----
+
+@pytest.mark.parametrize("shape,cap", CASES)
+@pytest.mark.parametrize("base", G.BASES)
+def test_banded_calls(gpu_codec, base, shape, cap):
+    a = gpu_codec
+    w, h, f = G.SHAPES[shape]
+    qs = G.QUALITIES[base]
+    plain, blobs = G.containers(base, shape), G.bandeds(base, shape)
+    stride = stride_of(blobs + plain)
+    d_rgb = torch.from_numpy(G.clips(shape)).to(DEV)
+    d_plain, d_v5 = upload(plain, stride), upload(blobs, stride)
+    out, there, back = Guarded(N * stride), Guarded(N * stride), Guarded(N * stride)
+    px = Guarded(N * w * h * f * 3, 0xEE)
+    with groups_of(a, cap):
+        sizes = a.banded_encode_device(d_rgb.data_ptr(), w, h, f, N, a.WaveletType(G.KIND[base]), 0, out.ptr, stride, qualities=qs,
+                                       lane_symbols=G.L, base=base)
+        a.banded_decode_device(d_v5.data_ptr(), stride, [len(b) for b in blobs], px.ptr)
+        sizes_there = a.to_banded_device(d_plain.data_ptr(), stride, [len(b) for b in plain], there.ptr, stride)
+        sizes_back = a.from_banded_device(d_v5.data_ptr(), stride, [len(b) for b in blobs], back.ptr, stride)
+    check_slots(out, stride, blobs, sizes)
+    got = px.host().reshape(N, -1)
+    for i in range(N):
+        assert np.array_equal(got[i], G.pixels(base, shape, i, qs[i])), i
+    check_slots(there, stride, G.to_banded_plan(base, shape), sizes_there)
+    check_slots(back, stride, G.from_banded_plan(base, shape), sizes_back)
+    assert torch.equal(d_rgb.cpu(), torch.from_numpy(G.clips(shape)))       # the inputs are only read
+    assert torch.equal(d_plain.cpu(), upload(plain, stride).cpu()) and torch.equal(d_v5.cpu(), upload(blobs, stride).cpu())
+
+
 # ---- verdicts of a call whose second group fails (3 + 3 + 1: chunks 0-2 have been written by then) ----
 
 def refused(a, code, fn):
@@ -335,6 +366,60 @@ def test_output_stride_one_byte_short_of_the_largest_chunk(gpu_codec):
                                                            qualities=G.TARGETS[version]))
         assert f"chunk {G.BIG} " in msg, msg
         check_slots(out, short, want, written={0, 1, 2})
+
+
+UNTOUCHED = 0xA5A5A5A5A5A5A5A5
+
+
+def _strided_call(a, family, shape, d_in, in_stride, in_lens, d_out, out_stride, sizes):
+    """the family's C entry point on chunks in G.STRIDE_ORDER, with the caller's own sizes array -> its return code"""
+    lib = a.load_library()
+    w, h, f = G.SHAPES[shape]
+    v = G.STRIDE_VERSION[family]
+    u8 = lambda values: np.array(G.in_stride_order(values), np.uint8)      # noqa: E731
+    p_sizes = sizes.ctypes.data_as(C.POINTER(C.c_uint64))
+    if d_in is None:
+        q = u8(G.QUALITIES[v])
+        d_rgb = torch.from_numpy(np.concatenate(G.in_stride_order([G.clip(shape, i) for i in range(N)]))).to(DEV)
+        head = (d_rgb.data_ptr(), w, h, f, N, G.KIND[v], 0, q.ctypes.data_as(C.POINTER(C.c_uint8)), G.L)
+        if family == "banded":
+            return lib.alice_codec_dev_encode_banded(*head, v, d_out, out_stride, p_sizes, None)
+        return getattr(lib, f"alice_codec_dev_encode_{family}")(*head, d_out, out_stride, p_sizes, None)
+    lens = np.array(in_lens, np.uint64)
+    p_lens = lens.ctypes.data_as(C.POINTER(C.c_uint64))
+    if family == "transcode":
+        q = u8(G.TARGETS[v])
+        return lib.alice_codec_dev_transcode(d_in.data_ptr(), in_stride, p_lens, N, 0, q.ctypes.data_as(C.POINTER(C.c_uint8)), 0, 0, d_out,
+                                             out_stride, p_sizes, None)
+    return getattr(lib, f"alice_codec_dev_{family}")(d_in.data_ptr(), in_stride, p_lens, N, 0, d_out, out_stride, p_sizes, None)
+
+
+@pytest.mark.parametrize("family", G.STRIDE_FAMILIES)
+def test_output_stride_refused_in_the_second_group(gpu_codec, family):
+    """Groups of two; the stride is one byte short of chunk 3 alone, the second chunk of the second group.  The call names
+    that chunk by its index in the call, group 0 has been written, nothing else has, and sizes holds group 0's entries."""
+    a = gpu_codec
+    shape = "tile"
+    inputs, want = G.stride_plan(family, shape)
+    short = len(want[G.STRIDE_AT]) - 1
+    assert all(len(b) <= short for i, b in enumerate(want) if i != G.STRIDE_AT)
+    d_in = in_stride = in_lens = None
+    if inputs is not None:
+        in_stride, in_lens = stride_of(inputs), [len(b) for b in inputs]
+        d_in = upload(inputs, in_stride)
+    out = Guarded(N * short)
+    sizes = np.full(N, UNTOUCHED, np.uint64)
+    lib = a.load_library()
+    with groups_of(a, G.STRIDE_CAP):
+        rc = _strided_call(a, family, shape, d_in, in_stride, in_lens, out.ptr, short, sizes)
+        code, msg = lib.alice_codec_last_error(), lib.alice_codec_last_error_message().decode()
+    print(f"{family}: rc {rc} code {code}: {msg}; sizes {[hex(int(s)) for s in sizes]}")
+    assert rc == 1 and code == 1, (rc, code, msg)                       # kInvalidBufferSize
+    assert f"chunk {G.STRIDE_AT} needs {len(want[G.STRIDE_AT])} bytes" in msg and f"stride is {short}" in msg, msg
+    first = set(range(G.STRIDE_CAP))
+    check_slots(out, short, want, written=first)
+    assert [int(s) for s in sizes[:G.STRIDE_CAP]] == [len(want[i]) for i in sorted(first)]
+    assert (sizes[G.STRIDE_CAP:] == UNTOUCHED).all()
 
 
 @pytest.mark.parametrize("version", [2, 3])
