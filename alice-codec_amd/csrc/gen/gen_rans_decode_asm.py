@@ -1,18 +1,21 @@
 #!/usr/bin/env python3
-"""Generates rans_decode_tile.inc, rans_decode_tile_vec.inc, rans_decode_tile_sh.inc and rans_decode_tile_ih.inc: the
-inline-asm bodies of the rANS decode fast tile (gfx950).
+"""Generates rans_decode_tile.inc, rans_decode_tile_vec.inc, rans_decode_tile_sh.inc, rans_decode_tile_ih.inc and
+rans_decode_tile_rs.inc: the inline-asm bodies of the rANS decode fast tile (gfx950).
 
     python gen_rans_decode_asm.py        writes ../rans_decode_tile.inc (classic and dry tile), ../rans_decode_tile_vec.inc,
-                                         ../rans_decode_tile_sh.inc and ../rans_decode_tile_ih.inc
+                                         ../rans_decode_tile_sh.inc, ../rans_decode_tile_ih.inc and ../rans_decode_tile_rs.inc
 
-fast_tile(), vector_tile(), shadow_tile(), inhand_tile() and dry_tile() return the instruction lists, so the programs can be
-checked without a GPU (tests/test_decode_tile_model.py, tests/test_decode_tile_vec_model.py,
-tests/test_decode_tile_shadow_model.py and tests/test_decode_tile_inhand_model.py interpret them); main() writes the files.
+fast_tile(), vector_tile(), shadow_tile(), inhand_tile(), resident_tile() and dry_tile() return the instruction lists, so the
+programs can be checked without a GPU (tests/test_decode_tile_model.py, tests/test_decode_tile_vec_model.py,
+tests/test_decode_tile_shadow_model.py, tests/test_decode_tile_inhand_model.py and tests/test_decode_tile_resident_model.py
+interpret them); main() writes the files.
 The vector tile (state update on the vector side, ten slots per symbol) is described where it is defined, below render();
 the shadow tile (the record in the stall behind the lane read, both window shifts in wait-state slots, 22 paid slots per
 symbol pair, the refill branch inside the stall) below the vector tile; the in-hand tile (the shadow tile's main line; the next
 window dword always in s65, so the refill is five scalar instructions, and its out-of-line path runs on to the odd symbol's
-lane read, where the dword after it is read in the same stall) below the shadow tile.  Which of them is the kernel's default:
+lane read, where the dword after it is read in the same stall) below the shadow tile; the resident tile (the in-hand block
+loop in one statement that decodes a run of full tiles: tables loaded once, window rows straight from global memory, a tile's
+symbols recovered while the next tile's window loads fly) below the in-hand tile.  Which of them is the kernel's default:
 dec_tile_choice() in rans.hip.
 
 Costs measured on MI355X with scripts/probes/latency_probe.hip (one wave alone on its SIMD):
@@ -67,8 +70,10 @@ Register plan (all literal, all listed as clobbers by the including statement):
 Operands: %[tp] (SGPR pair: the chain's RansDecSlots in global memory, F' then B'), %[l4] (VGPR: 4 * lane),
           %[wa] (VGPR: per-lane LDS byte address of the window), %[ra] (VGPR in/out: record address, 2 B per lane),
           %[xi] %[pi] %[nb] (SGPR in), %[xo] %[po] (SGPR out).
-The tables are re-read from global memory (L2) at the top of every tile: 128 loads per 4096 symbols, well under 1 % of a
-tile's time, and nothing of them lives in LDS, which is what bounds the number of chains a CU can host.
+Every tile but the resident one is a statement of its own and re-reads the tables from global memory (L2) at its top: 128
+loads per 4096 symbols, because the compiled code between two statements may use v64 and up.  The resident tile loads them
+once per statement, which runs over all consecutive full tiles with a whole window.  Nothing of the tables lives in LDS,
+which is what bounds the number of chains a CU can host.
 """
 import os
 
@@ -131,6 +136,46 @@ def refill():
             "s_xor_b64 s[62:63], s[62:63], s[66:67]"]
 
 
+def window_fixups():
+    """The window rows as the refill wants them: big-endian dwords (s75 = the byte-swap selector), top bit flipped."""
+    L = []
+    for r in range(WIN_ROWS):
+        L.append(f"v_perm_b32 v{192 + r}, v{192 + r}, v{192 + r}, s75")
+    for r in range(WIN_ROWS):
+        L.append(f"v_xor_b32_e32 v{192 + r}, 0x80000000, v{192 + r}")   # see "The refill" above
+    return L
+
+
+def shift_table():
+    L = []
+    for c in range(21):
+        sh = 0 if c <= 8 else (8 if c <= 16 else 16)
+        L.append(f"s_mov_b32 s{79 + c}, {sh}")
+    return L
+
+
+def prime(pi="%[pi]"):
+    """The window primed with {first dword : sentinel} << 8 * (pos & 3); unless pos & 3 == 0 that leaves V = 32 - shift < 32
+    and one refill brings it to 64 - shift.  pi: the position's byte offset inside the window rows."""
+    L = ["s_mov_b32 s64, 0x80000000",
+         f"s_lshr_b32 s73, {pi}, 2",
+         f"s_and_b32 s71, {pi}, 3",
+         "s_lshl_b32 s71, s71, 3",
+         "s_lshr_b32 s76, s73, 6",
+         "s_set_gpr_idx_on s76, 0x1",
+         "s_nop 1",
+         "v_readlane_b32 s63, v192, s73",
+         "s_add_u32 s73, s73, 1",
+         "s_xor_b32 s63, s63, s64",                    # the true first dword
+         "s_mov_b32 s62, s64",
+         "s_lshl_b64 s[62:63], s[62:63], s71",
+         "s_cmp_eq_u32 s62, 0",
+         "s_cbranch_scc0 6f"]
+    L += refill()
+    L.append("6:")
+    return L
+
+
 def tile_entry():
     """Tables and window rows into VGPRs, the shift table, the scalar state and the primed window (shared by all fast tiles)."""
     L = table_loads()
@@ -138,33 +183,11 @@ def tile_entry():
         L.append(f"ds_read_b32 v{192 + r}, %[wa] offset:{256 * r}")
     L.append("s_mov_b32 s75, 0x00010203")
     L.append("s_waitcnt vmcnt(0) lgkmcnt(0)")
-    for r in range(WIN_ROWS):
-        L.append(f"v_perm_b32 v{192 + r}, v{192 + r}, v{192 + r}, s75")
-    for r in range(WIN_ROWS):
-        L.append(f"v_xor_b32_e32 v{192 + r}, 0x80000000, v{192 + r}")   # see "The refill" above
-    for c in range(21):
-        sh = 0 if c <= 8 else (8 if c <= 16 else 16)
-        L.append(f"s_mov_b32 s{79 + c}, {sh}")
-    # scalar state: x, and the window primed with {first dword : sentinel} << 8 * (pos & 3); unless pos & 3 == 0 that
-    # leaves V = 32 - shift < 32 and one refill brings it to 64 - shift
+    L += window_fixups()
+    L += shift_table()
     L += ["s_mov_b32 s61, %[xi]",
-          "s_mov_b32 s74, %[nb]",
-          "s_mov_b32 s64, 0x80000000",
-          "s_lshr_b32 s73, %[pi], 2",
-          "s_and_b32 s71, %[pi], 3",
-          "s_lshl_b32 s71, s71, 3",
-          "s_lshr_b32 s76, s73, 6",
-          "s_set_gpr_idx_on s76, 0x1",
-          "s_nop 1",
-          "v_readlane_b32 s63, v192, s73",
-          "s_add_u32 s73, s73, 1",
-          "s_xor_b32 s63, s63, s64",                    # the true first dword
-          "s_mov_b32 s62, s64",
-          "s_lshl_b64 s[62:63], s[62:63], s71",
-          "s_cmp_eq_u32 s62, 0",
-          "s_cbranch_scc0 6f"]
-    L += refill()
-    L.append("6:")
+          "s_mov_b32 s74, %[nb]"]
+    L += prime()
     return L
 
 
@@ -476,6 +499,192 @@ def render_inhand(loop_phase=LOOP_PHASE):
             "#define ALICE_DEC_TILE_IH_CLOBBERS " + ", ".join(f'"{c}"' for c in inhand_clobbers()) + "\n")
 
 
+# ---- the resident tile: one statement decodes a run of full tiles, the tables stay in their registers ---------------------
+# The tiles above are one asm statement per 4096 symbols, and compiled code runs between two statements: the window goes
+# global -> VGPR -> LDS -> VGPR, the tables are loaded again because the compiler may use v64 and up, and the symbols are
+# recovered from the record only after the statement.  Measured in the chain (profiles/r30_decode_edge_probe.json): 9.5 k
+# cycles per tile outside the block loop -- 1.8 k window fetch and staging, 2.3 k statement entry, 5.2 k recovery.
+# This statement keeps going while the kernel's own conditions for the next fast `whole` tile hold, evaluated on the scalar
+# side at the end of every tile (tile_conditions()).  Per statement: M0 and EXEC saved, the 128 table loads, the shift table.
+# Per tile: the 33 window loads straight from global memory into v[192:224] (lane l of row r <- dword 64 r + l of the window
+# base, which is the position rounded down to a dword: the statement's stream pointer is dword aligned); while they fly
+# the PREVIOUS tile's symbols are recovered from the record through cum_to_sym and stored (recover()); then the wait, the
+# byte swap and the flipped top bits, the priming, and the in-hand block loop instruction for instruction.  On leaving the
+# last tile is recovered.  All positions inside the statement are 32-bit offsets from the statement's stream pointer; the
+# kernel bounds the tile count so that they cannot wrap, and clamps the stream length it passes in accordingly.
+# Register plan: the in-hand tile's plus v228 (the block loop's moving record address), v229 (record read address,
+# 8 B per lane), v[230:233] (two pairs of record words), v[234:241] (two sets of four slot addresses / symbols), v242 / v243
+# (packed symbols), s[40:41] (window load address), s[42:43] (output address of the tile being recovered), s44 (window base),
+# s45 (tiles left), s46 (tiles done), s48 (position).
+# Operands: %[ip] (SGPR pair: stream pointer, dword aligned), %[ln] (stream bytes from there, clamped to 32 bits), %[pi]
+# (position, 0 .. 3), %[nt] (most tiles to decode, at least 1), %[op] (SGPR pair: output of the first tile, dword aligned),
+# %[cs] (SGPR: LDS address of cum_to_sym), %[ra] (VGPR in: record address, 2 B per lane), %[xi], %[tp], %[l4]; out: %[xo],
+# %[po], %[to] (tiles decoded).
+RS_RA, RS_RB, RS_A, RS_B, RS_P = VW + 1, VW + 2, (VW + 3, VW + 5), (VW + 7, VW + 11), (VW + 15, VW + 16)
+RECOVER_TRIPS = 16
+WIN_BYTES = WIN_ROWS * 256
+
+
+def window_loads():
+    """Lane l of row r reads dword 64 r + l of the stream from s44 on; the scalar base moves every 16 rows (13-bit offset)."""
+    L = ["s_and_b32 s44, s48, 0xfffffffc",
+         "s_mov_b64 s[40:41], %[ip]",
+         "s_add_u32 s40, s40, s44",
+         "s_addc_u32 s41, s41, 0"]
+    for r in range(WIN_ROWS):
+        L.append(f"global_load_dword v{192 + r}, %[l4], s[40:41] offset:{256 * (r % 16)}")
+        if r % 16 == 15:
+            L.append("s_add_u32 s40, s40, 0x1000")
+            L.append("s_addc_u32 s41, s41, 0")
+    return L
+
+
+def recover():
+    """Symbols of the tile in the record, four per lane and trip: lane l of trip t reads states 256 t + 4 l .. + 3 (one
+    ds_read_b64), looks their slots up in cum_to_sym (four ds_read_u8) and stores the packed dword at s[42:43] + 256 t + 4 l.
+    Software pipeline: the record words are read two trips ahead, the symbols are packed and stored one trip after their
+    lookups were issued; LDS returns in order, so every wait is a count of the LDS instructions issued since.  Then the
+    output address moves on by a tile."""
+    L, issued = [], []
+
+    def issue(tag, line):
+        issued.append(tag)
+        L.append(line)
+
+    def wait(tag):
+        after = len(issued) - 1 - max(i for i, t in enumerate(issued) if t == tag)
+        L.append(f"s_waitcnt lgkmcnt({after})")
+
+    def read(t):
+        issue(("a", t), f"ds_read_b64 v[{RS_A[t % 2]}:{RS_A[t % 2] + 1}], v{RS_RB} offset:{512 * t}")
+
+    def finish(t):
+        b, p = RS_B[t % 2], RS_P[t % 2]
+        wait(("b", t))
+        L.extend([f"v_lshl_or_b32 v{p}, v{b + 1}, 8, v{b}",
+                  f"v_lshl_or_b32 v{p}, v{b + 2}, 16, v{p}",
+                  f"v_lshl_or_b32 v{p}, v{b + 3}, 24, v{p}",
+                  f"global_store_dword %[l4], v{p}, s[42:43] offset:{256 * t}"])
+
+    read(0)
+    read(1)
+    for t in range(RECOVER_TRIPS):
+        a, b = RS_A[t % 2], RS_B[t % 2]
+        wait(("a", t))
+        L.extend([f"v_and_b32_e32 v{b}, 0xfff, v{a}",
+                  f"v_bfe_u32 v{b + 1}, v{a}, 16, 12",
+                  f"v_and_b32_e32 v{b + 2}, 0xfff, v{a + 1}",
+                  f"v_bfe_u32 v{b + 3}, v{a + 1}, 16, 12"])
+        for k in range(4):
+            L.append(f"v_add_u32_e32 v{b + k}, %[cs], v{b + k}")
+        for k in range(4):
+            issue(("b", t), f"ds_read_u8 v{b + k}, v{b + k}")
+        if t + 2 < RECOVER_TRIPS:
+            read(t + 2)
+        if t:
+            finish(t - 1)
+    finish(RECOVER_TRIPS - 1)
+    L += ["s_add_u32 s42, s42, 0x1000",
+          "s_addc_u32 s43, s43, 0"]
+    return L
+
+
+def tile_conditions():
+    """What lets rans_decode_kernel take the fast `whole` path for the next tile, in its order: a full tile is left to
+    decode, the stream is not exhausted, the state is renormalised, and the whole window lies inside the stream (its base
+    is dword aligned because the statement's stream pointer is).  Leaves to 9 unless all hold."""
+    return ["s_add_u32 s46, s46, 1",
+            "s_sub_u32 s45, s45, 1",
+            "s_cmp_eq_u32 s45, 0",
+            "s_cbranch_scc1 9f",
+            "s_cmp_ge_u32 s48, %[ln]",
+            "s_cbranch_scc1 9f",
+            "s_cmp_lt_u32 s61, 0x800000",
+            "s_cbranch_scc1 9f",
+            "s_and_b32 s70, s48, 0xfffffffc",
+            "s_sub_u32 s70, %[ln], s70",
+            f"s_cmp_lt_u32 s70, {WIN_BYTES}",
+            "s_cbranch_scc1 9f"]
+
+
+def resident_tile(loop_phase=LOOP_PHASE):
+    ra = lambda lines: [s.replace("%[ra]", f"v{RS_RA}") for s in lines]
+    L = table_loads()
+    L.insert(1, f"s_mov_b64 {EXEC_SAVE}, exec")
+    L += shift_table()
+    L += ["s_mov_b32 s75, 0x00010203",
+          "s_mov_b32 s61, %[xi]",
+          "s_mov_b32 s48, %[pi]",
+          "s_mov_b32 s45, %[nt]",
+          "s_mov_b32 s46, 0",
+          "s_mov_b64 s[42:43], %[op]",
+          f"v_lshrrev_b32_e32 v{RS_RB}, 1, %[l4]",         # record read address: 8 B per lane = ra + 6 * lane
+          f"v_add_u32_e32 v{RS_RB}, %[l4], v{RS_RB}",
+          f"v_add_u32_e32 v{RS_RB}, %[ra], v{RS_RB}",
+          "7:"]
+    L += window_loads()
+    L += ["s_cmp_eq_u32 s46, 0",                           # the first tile has no tile in front of it to recover
+          "s_cbranch_scc1 8f"]
+    L += recover()
+    L += ["8:",
+          f"v_mov_b32_e32 v{RS_RA}, %[ra]",
+          "s_waitcnt vmcnt(0)"]
+    L += window_fixups()
+    L += ["s_mov_b32 s74, 64",
+          "s_sub_u32 s70, s48, s44"]                       # the position inside the window rows: pos & 3
+    L += prime("s70")
+    L += ["s_lshr_b32 s76, s73, 6",                        # prime s65: the dword with index s73
+          "s_set_gpr_idx_on s76, 0x1",
+          "s_nop 1",
+          "v_readlane_b32 s65, v192, s73"]
+    L += stage()
+    L.append("s_mov_b32 s77, 0")                           # no shift is pending
+    L += loop_pin(loop_phase)
+    for lane in range(64):
+        body = shadow_symbol(lane)
+        if lane & 1:
+            body.insert(body.index("s_flbit_i32_b32 m0, s61"), f"6{lane - 1:02d}:")
+        L += body
+    L += stage()
+    L += ra(block_end())
+    L.append("s_branch 5f")
+    for lane in range(0, 64, 2):
+        L += inhand_path(lane)
+    L += ["5:",
+          "s_lshl_b64 s[62:63], s[62:63], s77",            # the last odd symbol's shift is still pending
+          "s_ff1_i32_b64 s71, s[62:63]",                   # 63 - V
+          "s_sub_u32 s71, 63, s71",
+          "s_lshr_b32 s71, s71, 3",                        # bytes read ahead of the decoder's position
+          "s_lshl_b32 s70, s73, 2",
+          "s_sub_u32 s70, s70, s71",
+          "s_add_u32 s48, s44, s70",
+          "s_waitcnt lgkmcnt(0)"]
+    L += tile_conditions()
+    L += ["s_branch 7b",
+          "9:"]
+    L += recover()
+    L += ["s_waitcnt vmcnt(0)",
+          "s_mov_b32 %[xo], s61",
+          "s_mov_b32 %[po], s48",
+          "s_mov_b32 %[to], s46",
+          f"s_mov_b32 m0, {M0_SAVE}"]
+    return L
+
+
+def resident_clobbers():
+    return (inhand_clobbers() + [f"v{r}" for r in range(RS_RA, RS_P[1] + 1)] +
+            ["s40", "s41", "s42", "s43", "s44", "s45", "s46", "s48"])
+
+
+def render_resident(loop_phase=LOOP_PHASE):
+    def macro(name, lines):
+        return f"#define {name} \\\n" + "".join(f'    "{s}\\n\\t" \\\n' for s in lines) + '    ""\n'
+
+    return ("// GENERATED by gen/gen_rans_decode_asm.py -- do not edit.\n" +
+            macro("ALICE_DEC_TILE_RS_ASM", resident_tile(loop_phase)) +
+            "#define ALICE_DEC_TILE_RS_CLOBBERS " + ", ".join(f'"{c}"' for c in resident_clobbers()) + "\n")
+
+
 def main():
     here = os.path.dirname(os.path.abspath(__file__))
     out = os.path.join(here, "..", "rans_decode_tile.inc")
@@ -494,6 +703,10 @@ def main():
     with open(out, "w") as f:
         f.write(render_inhand())
     print("wrote", out, len(inhand_tile()), "asm lines")
+    out = os.path.join(here, "..", "rans_decode_tile_rs.inc")
+    with open(out, "w") as f:
+        f.write(render_resident())
+    print("wrote", out, len(resident_tile()), "asm lines")
 
 
 if __name__ == "__main__":

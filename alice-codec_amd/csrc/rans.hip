@@ -745,6 +745,7 @@ constexpr int kDecBlocks = 64;                 // 64-symbol blocks per fast tile
 constexpr int kDecTile = kDecBlocks * 64;      // 4096 symbols
 constexpr int kDecWinBytes = 33 * 64 * 4;       // stream window held in 33 VGPRs (big-endian dwords): 2 B/symbol + slack
 constexpr int kDecWinLds = kDecWinBytes;
+constexpr int kDecResidentRun = 65536;          // most tiles of one resident statement: 65536 * kDecWinBytes < 2^30 stream bytes
 
 // The tile body is generated (gen/gen_rans_decode_asm.py -> rans_decode_tile.inc, which documents the
 // register plan and the measured instruction costs behind its shape); per symbol, all on the scalar side:
@@ -766,8 +767,13 @@ constexpr int kDecWinLds = kDecWinBytes;
 // read, where the dword after it is read from a staging row in the same stall.
 #include "rans_decode_tile_sh.inc"
 #include "rans_decode_tile_ih.inc"
+// The resident tile (rans_decode_tile_rs.inc) is the in-hand block loop inside one statement that decodes a run of full tiles:
+// the tables stay in their registers, the window rows come straight from global memory, and the symbols of a tile are
+// recovered and stored while the next tile's window loads are in flight.  A kernel instance of its own (kDecTileResident);
+// every tile that the statement does not take runs the in-hand tile and the code around it, as in the in-hand instance.
+#include "rans_decode_tile_rs.inc"
 
-enum DecTile : int { kDecTileClassic = 0, kDecTileVector = 1, kDecTileShadow = 2, kDecTileInhand = 3 };
+enum DecTile : int { kDecTileClassic = 0, kDecTileVector = 1, kDecTileShadow = 2, kDecTileInhand = 3, kDecTileResident = 4 };
 
 // Decodes nblk*64 symbols on the fast path.  slots = the chain's RansDecSlots (F' at byte 0, B' at byte 16384, read with
 // 128 global loads per lane: lane4 = 4 * lane); win_addr / rec_addr are this lane's LDS byte addresses (base + 4*lane;
@@ -776,7 +782,7 @@ template <int kTile>
 __device__ __forceinline__ void dec_tile_fast(uint32_t& x, uint32_t& pos, const RansDecSlots* slots, uint32_t lane4,
                                               uint32_t win_addr, uint32_t rec_addr, uint32_t nblk) {
     uint32_t xo, po;
-    if constexpr (kTile == kDecTileInhand)
+    if constexpr (kTile == kDecTileInhand || kTile == kDecTileResident)
         asm volatile(ALICE_DEC_TILE_IH_ASM
                      : [xo] "=&s"(xo), [po] "=&s"(po), [ra] "+v"(rec_addr)
                      : [xi] "s"(x), [pi] "s"(pos), [nb] "s"(nblk), [tp] "s"(slots), [l4] "v"(lane4), [wa] "v"(win_addr)
@@ -800,6 +806,34 @@ __device__ __forceinline__ void dec_tile_fast(uint32_t& x, uint32_t& pos, const 
     pos = po;
 }
 
+// Decodes up to max_tiles full tiles in one statement (rans_decode_tile_rs.inc) and stores their symbols at out.  in_win
+// = the stream at the first tile's window base, dword aligned, with at least kDecWinBytes of the stream behind it; len_rel
+// = stream bytes from there on; pos = the position's offset from it (0 .. 3), on return the position after the last tile
+// decoded.  The statement goes on to the next tile exactly when rans_decode_kernel would take the fast path on a whole
+// window for it.  Returns the number of tiles decoded (at least 1).
+__device__ __forceinline__ uint32_t dec_tiles_resident(uint32_t& x, uint32_t& pos, const uint8_t* in_win, uint32_t len_rel,
+                                                       uint32_t max_tiles, uint8_t* out, const RansDecSlots* slots,
+                                                       uint32_t lane4, uint32_t c2s_addr, uint32_t rec_addr) {
+    // the scalar operands are uniform, but the compiler cannot always see it
+    const auto uni = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
+    const auto uni64 = [&](unsigned long long v) { return (unsigned long long)uni((uint32_t)v) | ((unsigned long long)uni((uint32_t)(v >> 32)) << 32); };
+    in_win = (const uint8_t*)uni64((unsigned long long)(uintptr_t)in_win);
+    out = (uint8_t*)uni64((unsigned long long)(uintptr_t)out);
+    len_rel = uni(len_rel);
+    max_tiles = uni(max_tiles);
+    x = uni(x);
+    pos = uni(pos);
+    uint32_t xo, po, to;
+    asm volatile(ALICE_DEC_TILE_RS_ASM
+                 : [xo] "=&s"(xo), [po] "=&s"(po), [to] "=&s"(to)
+                 : [xi] "s"(x), [pi] "s"(pos), [nt] "s"(max_tiles), [ln] "s"(len_rel), [ip] "s"(in_win), [op] "s"(out),
+                   [tp] "s"(slots), [cs] "s"(c2s_addr), [l4] "v"(lane4), [ra] "v"(rec_addr)
+                 : ALICE_DEC_TILE_RS_CLOBBERS);
+    x = xo;
+    pos = po;
+    return to;
+}
+
 // The same lookup and update with the stream exhausted: nothing is shifted in any more (src/rans.rs:365-368 reads
 // no byte once pos == len), the state just evolves.  A frequency-4096 entry is only right for x >= 1 (see
 // build_dec_slots); the caller checks that.
@@ -815,12 +849,12 @@ __device__ __forceinline__ void dec_tile_dry(uint32_t& x, const RansDecSlots* sl
 // LDS per chain: cum_to_sym 4 KB + exact-loop symbol table 1 KB + stream window 8.25 KB + state record 8 KB
 // (the exact loop's output bytes share the record's space) = 21.3 KB.  The launcher adds dynamic LDS so that at most
 // four (up to 1024 chains: one per SIMD) or seven chains share a CU.
-// kTile: which fast tile (classic, vector, shadow, in-hand); everything around it (window staging, speculation, symbol recovery,
+// kTile: which fast tile (classic, vector, shadow, in-hand, resident); everything around it (window staging, speculation, symbol recovery,
 // the exact loop, the dry tile) is the same code.
 template <bool kExclusive, int kTile>
 __global__ __launch_bounds__(64) void rans_decode_kernel(const RansDecodeDesc* __restrict__ descs,
                                                          RansResult* __restrict__ results, uint32_t take_turns) {
-    if constexpr (kExclusive) asm volatile("" ::: "a63");   // 226 (vector and shadow tile: 227, in-hand tile: 228) VGPRs + 64 AGPRs > 256: one chain per SIMD
+    if constexpr (kExclusive) asm volatile("" ::: "a63");   // 226 (vector and shadow tile: 227, in-hand tile: 228, resident tile: 245) VGPRs + 64 AGPRs > 256: one chain per SIMD
     __shared__ __attribute__((aligned(16))) uint8_t c2s[kProbScale];                  // cum_to_sym
     __shared__ uint32_t symtab[256];                                                    // freq | cum << 16 (exact loop)
     __shared__ __attribute__((aligned(16))) uint8_t win[kDecWinLds];
@@ -900,6 +934,26 @@ __global__ __launch_bounds__(64) void rans_decode_kernel(const RansDecodeDesc* _
         }
         const bool whole = (len - wbase >= (unsigned long long)kDecWinLds) && ((((uintptr_t)(d.in + wbase)) & 3u) == 0u);
         __syncthreads();
+        if constexpr (kTile == kDecTileResident) {
+            // A run of full tiles in one statement: the fast path on a whole window with nothing owed, and an aligned output.
+            // The statement works with 32-bit offsets from the window base: kDecResidentRun tiles move it by less than 2^30.
+            if (whole && want == (uint32_t)kDecTile && pos < len && !exact_only && !pending && x >= kRansL &&
+                ((((uintptr_t)(d.out + done)) & 3u) == 0u)) {
+                const unsigned long long left = remain / (unsigned long long)kDecTile, rel = len - wbase;
+                uint32_t nt = left < (unsigned long long)kDecResidentRun ? (uint32_t)left : (uint32_t)kDecResidentRun;
+                if (!kExclusive && take_turns) nt = 1u;   // the turn is taken once per tile
+                uint32_t prel = (uint32_t)(pos - wbase), xs = x;
+                const uint32_t got_tiles = dec_tiles_resident(xs, prel, d.in + wbase, rel < 0xFFFFFFFFull ? (uint32_t)rel : 0xFFFFFFFFu,
+                                                              nt, d.out + done, slots, 4u * lane, (uint32_t)(uintptr_t)c2s,
+                                                              (uint32_t)(uintptr_t)rec + 2u * lane);
+                x = xs;
+                pos = wbase + prel;
+                done += (unsigned long long)got_tiles * (unsigned long long)kDecTile;
+                n_fast += got_tiles;
+                paths |= kDecPathWhole;
+                continue;
+            }
+        }
         if (whole) {
             const uint32_t* g = (const uint32_t*)(d.in + wbase) + lane;
             uint32_t wv[kDecWinLds / 256];
@@ -1065,8 +1119,8 @@ static uint32_t chain_turns_enabled() {
     return on;
 }
 
-// ALICE_DEC_TILE=classic / vector / shadow selects an earlier decode tile instead of the in-hand tile, inhand names the
-// default (developer A/B, read once)
+// ALICE_DEC_TILE=classic / vector / shadow / inhand selects an earlier decode tile instead of the resident tile, resident names
+// the default (developer A/B, read once)
 static int dec_tile_choice() {
     static const int tile = [] {
         const char* v = getenv("ALICE_DEC_TILE");
@@ -1074,7 +1128,8 @@ static int dec_tile_choice() {
         if (v && strcmp(v, "vector") == 0) return (int)kDecTileVector;
         if (v && strcmp(v, "shadow") == 0) return (int)kDecTileShadow;
         if (v && strcmp(v, "inhand") == 0) return (int)kDecTileInhand;
-        return (int)kDecTileInhand;
+        if (v && strcmp(v, "resident") == 0) return (int)kDecTileResident;
+        return (int)kDecTileResident;
     }();
     return tile;
 }
@@ -1084,7 +1139,8 @@ static DecKernel dec_kernel(bool exclusive) {
         case kDecTileClassic: return exclusive ? rans_decode_kernel<true, kDecTileClassic> : rans_decode_kernel<false, kDecTileClassic>;
         case kDecTileVector: return exclusive ? rans_decode_kernel<true, kDecTileVector> : rans_decode_kernel<false, kDecTileVector>;
         case kDecTileShadow: return exclusive ? rans_decode_kernel<true, kDecTileShadow> : rans_decode_kernel<false, kDecTileShadow>;
-        default: return exclusive ? rans_decode_kernel<true, kDecTileInhand> : rans_decode_kernel<false, kDecTileInhand>;
+        case kDecTileInhand: return exclusive ? rans_decode_kernel<true, kDecTileInhand> : rans_decode_kernel<false, kDecTileInhand>;
+        default: return exclusive ? rans_decode_kernel<true, kDecTileResident> : rans_decode_kernel<false, kDecTileResident>;
     }
 }
 
