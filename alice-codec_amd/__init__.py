@@ -381,6 +381,12 @@ def load_library() -> C.CDLL:
         "alice_codec_dev_to_banded": (C.c_int, [vp, C.c_uint64, _u64p, C.c_uint32, C.c_uint32, vp, C.c_uint64, _u64p, vp]),
         "alice_codec_dev_from_banded": (C.c_int, [vp, C.c_uint64, _u64p, C.c_uint32, C.c_uint32, vp, C.c_uint64, _u64p, vp]),
         "alice_codec_dev_band_histograms": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, vp, vp]),
+        "alice_codec_decode_banded_frames": (vp, [_u8p, C.c_uint64, C.c_uint32, C.c_uint32, _u64p]),
+        "alice_codec_dev_decode_banded_frames": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp]),
+        "alice_codec_decode_banded_preview": (vp, [_u8p, C.c_uint64, C.c_uint32, C.c_uint32, _u64p]),
+        "alice_codec_dev_decode_banded_preview": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp]),
+        "alice_codec_test_last_banded_frames_stats": (None, [_u64p]),
+        "alice_codec_test_last_banded_preview_stats": (None, [_u64p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
@@ -2937,3 +2943,50 @@ def band_histograms_device(d_symbols_ptr: int, width: int, height: int, frames: 
     _dims_u32(width, height, frames)
     _check(load_library().alice_codec_dev_band_histograms(d_symbols_ptr or None, width, height, frames, 1 if wide else 0,
                                                           d_hist_ptr or None, stream or None))
+
+
+# ---- frame ranges and half-size previews of a version 5 chunk ----
+
+def _banded_partial_host(fn: str, data, first: int, count: int) -> np.ndarray:
+    lib = load_library()
+    buf = _as_u8(data)
+    _dims_u32(first, count)
+    n = C.c_uint64(0)
+    ptr = getattr(lib, fn)(_p(buf, _u8p), buf.size, first, count, C.byref(n))
+    if not ptr:
+        _raise_last()
+    return _adopt(ptr, n.value, lib.alice_codec_data_free64)
+
+
+def decode_banded_frames(data, first: int, count: int) -> np.ndarray:
+    """The RGB bytes of frames [first, first + count) of a version 5 container, bit for bit decode_frames(from_banded(data),
+    first, count): of every band only the blocks that hold coefficient planes of the range's window are read, uploaded (data
+    may be an np.memmap) and entropy-decoded.  The end checks cover the blocks that are read."""
+    return _banded_partial_host("alice_codec_decode_banded_frames", data, first, count)
+
+
+def banded_frames_decode_device(d_alc_ptr: int, length: int, first: int, count: int, d_rgb_out_ptr: int, stream: int = 0) -> None:
+    """decode_banded_frames of a device-resident container of `length` bytes into count packed frames at d_rgb_out_ptr."""
+    _dims_u32(first, count)
+    _check(load_library().alice_codec_dev_decode_banded_frames(d_alc_ptr, length, first, count, d_rgb_out_ptr, stream or None))
+
+
+def decode_banded_preview(data, first: int, count: int) -> np.ndarray:
+    """The half-resolution RGB bytes (count * qh * qw * 3, preview_dims) of frames [first, first + count) of a version 5
+    container, bit for bit decode_preview(from_banded(data), first, count): bands 0 and 4 are the low-low quadrants, so only
+    their blocks inside the window are read, uploaded and entropy-decoded, and no spatial inverse runs."""
+    return _banded_partial_host("alice_codec_decode_banded_preview", data, first, count)
+
+
+def banded_preview_decode_device(d_alc_ptr: int, length: int, first: int, count: int, d_rgb_out_ptr: int, stream: int = 0) -> None:
+    """decode_banded_preview of a device-resident container of `length` bytes into count packed preview frames."""
+    _dims_u32(first, count)
+    _check(load_library().alice_codec_dev_decode_banded_preview(d_alc_ptr, length, first, count, d_rgb_out_ptr, stream or None))
+
+
+def _test_last_banded_partial_stats(kind: str) -> tuple:
+    """(a, b, blocks decoded over the channels and kept bands, payload bytes the host call uploaded, frames written, symbols
+    stored over the three channels) of the calling thread's last banded frame-range (kind "frames") or preview decode."""
+    out = np.zeros(6, np.uint64)
+    getattr(load_library(), f"alice_codec_test_last_banded_{kind}_stats")(_p(out, _u64p))
+    return tuple(int(v) for v in out)

@@ -17,6 +17,7 @@
 //   band_hist_kernel<WIDE>            symbols [3][pf][ph][pw] -> u32 [3][8][256], min(z, 255) when WIDE
 //   band_encode_kernel<WIDE, kWrite>  <false> counts every lane's stream length, <true> writes directory and streams
 //   band_decode_kernel<WIDE>          every block of a band; symbol i at its place in the channel volume
+//   band_range_decode_kernel<WIDE>    a block run of a band; the symbols of a plane range alone, into a compact volume
 //   band_header_kernel                the 12 636-byte container header
 // Tables, block offsets and the decoder's directory check are split_table_kernel, rans_tables_from_arrays_kernel and
 // split_scan_kernel, unchanged.
@@ -60,6 +61,13 @@ struct BandLaneGeometry {
 struct BandWalk {
     uint32_t x, y, hw, hh, dx, dy;
     int32_t t, dP;
+    __device__ __forceinline__ BandWalk(uint32_t hw_, uint32_t hh_, uint32_t idx) {   // (band_range_decode_kernel's)
+        hw = hw_; hh = hh_;
+        const uint32_t P = hw * hh;
+        const uint32_t rem = idx % P, srem = 64u % P;
+        t = (int32_t)(idx / P); y = rem / hw; x = rem % hw;
+        dP = (int32_t)(64u / P); dy = srem / hw; dx = srem % hw;
+    }
     __device__ __forceinline__ BandWalk(const SplitBandJob& bj, uint32_t idx) {
         hw = bj.hw; hh = bj.hh;
         const uint32_t P = hw * hh;        // hw hh ht = n < 2^29
@@ -90,6 +98,10 @@ struct BandWalk {
 __device__ __forceinline__ bool band_job_ok(const SplitBandJob& bj) {
     // (the host plans the box; nothing below divides by zero or leaves 32 bits whatever the job holds)
     return bj.hw && bj.hh && (unsigned long long)bj.hw * bj.hh <= bj.j.n && bj.j.n < (1ull << 30);
+}
+__device__ __forceinline__ bool band_range_job_ok(const SplitBandRangeJob& rj) {
+    return rj.hw && rj.hh && (unsigned long long)rj.hw * rj.hh <= rj.j.n && rj.j.n < (1ull << 30) && rj.idx_lo <= rj.idx_hi &&
+           rj.idx_hi <= rj.j.n;
 }
 
 }  // namespace
@@ -395,6 +407,113 @@ __global__ __launch_bounds__(256) void band_decode_kernel(const SplitBandJob* __
 }
 
 // ----------------------------------------------------------------------------------
+// Lane decode of a plane range of a band (frame ranges and previews of a banded chunk): the blocks
+// [blk_first, blk_first + blk_count) of a SplitBandRangeJob, four consecutive ones per workgroup.  A block that straddles an
+// edge of [idx_lo, idx_hi) still runs its 64 chains to their end checks (a chain is serial, and its end check is the
+// integrity check) but stores only the symbols inside, at (t'' - idx_lo / (hw hh)) plane_pitch + y'' row_pitch + x'' of the
+// destination.  The index range becomes a per-lane iteration range before the chain loop (as in
+// split_frames_decode_kernel), so the loop carries one 32-bit compare and BandWalk's three adds, also for hw hh < 64.  For a
+// kept symbol idx >= idx_lo, so t'' - idx_lo / (hw hh) >= 0.  End checks cover the decoded blocks only.  The chain is a copy
+// of band_decode_kernel's, kept apart so that no existing instance is compiled differently; a change to either is repeated.
+// ----------------------------------------------------------------------------------
+template <bool WIDE>
+__global__ __launch_bounds__(256) void band_range_decode_kernel(const SplitBandRangeJob* __restrict__ jobs) {
+    __shared__ uint32_t c2s_sh[kProbScale / 4];
+    __shared__ uint32_t symtab[256];
+    const SplitBandRangeJob rj = jobs[blockIdx.y];
+    const SplitJob& job = rj.j;
+    {
+        const uint32_t* src = (const uint32_t*)job.table->dec.c2s;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) c2s_sh[threadIdx.x + 256 * t] = src[threadIdx.x + 256 * t];
+        symtab[threadIdx.x] = job.table->dec.symtab[threadIdx.x];
+        __syncthreads();
+    }
+    const uint8_t* c2s = (const uint8_t*)c2s_sh;
+    const int lane = threadIdx.x & 63;
+    const unsigned long long slot = (unsigned long long)blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (slot >= rj.blk_count || !band_range_job_ok(rj)) return;
+    const unsigned long long b64 = (unsigned long long)rj.blk_first + slot;
+    if (b64 >= job.n_blocks) return;   // (the host plans inside the band; the bounds below do not rest on it)
+    const uint32_t b = (uint32_t)b64;
+    const BandLaneGeometry g(job, b, lane);
+    const uint32_t k = g.k;
+    BandSym<WIDE>* __restrict__ sym = (BandSym<WIDE>*)job.sym;
+    const uint32_t p0 = g.base + (uint32_t)lane;   // below n + 64 < 2^31
+    BandWalk walk(rj.hw, rj.hh, p0);
+    // the lane's symbols i in [i_lo, i_hi) have their index p0 + 64 i inside [idx_lo, idx_hi)
+    uint32_t i_lo = rj.idx_lo > p0 ? (rj.idx_lo - p0 + 63u) / 64u : 0u;
+    uint32_t i_hi = rj.idx_hi > p0 ? (rj.idx_hi - p0 + 63u) / 64u : 0u;
+    if (i_lo > k) i_lo = k;
+    if (i_hi > k) i_hi = k;
+    if (i_hi < i_lo) i_hi = i_lo;
+    const uint32_t kept = i_hi - i_lo;
+    const int32_t t_lo = (int32_t)(rj.idx_lo / (rj.hw * rj.hh));
+
+    const uint32_t blen = job.blk_len[b];
+    const unsigned long long boff = job.blk_off[b];
+    // (the scan left 0 for a block it refused; checked again here so that the bounds do not rest on another kernel)
+    if (blen < 128u || boff + blen > job.len) { if (lane == 0) *job.flags = kSplitBadDirectory; return; }
+    const uint8_t* blk = job.stream + boff;
+    const uint32_t len = (uint32_t)blk[2 * lane] | ((uint32_t)blk[2 * lane + 1] << 8);
+    const uint32_t incl = band_wave_incl_scan(len, lane);
+    const uint32_t all = __shfl(incl, 63, 64);
+    if (all + 128u != blen) { if (lane == 0) *job.flags = kSplitBadDirectory; return; }
+    const uint8_t* __restrict__ src = blk + 128u + (incl - len);   // [src, src + len) lies inside the block
+
+    uint32_t win = 0u, nwin = 0u, fpos = 0u, pos = 0u;
+    auto take = [&]() -> uint32_t {
+        if (nwin == 0u) {
+            uint32_t w = 0u;
+            if (fpos + 4u <= len) {
+                uint32_t t;
+                __builtin_memcpy(&t, src + fpos, 4);
+                w = __builtin_bswap32(t);
+            } else {
+#pragma unroll
+                for (uint32_t t = 0; t < 4u; ++t) w = (w << 8) | (fpos + t < len ? (uint32_t)src[fpos + t] : 0u);
+            }
+            fpos += 4u;
+            win = w;
+            nwin = 4u;
+        }
+        const uint32_t byte = win >> 24;
+        win <<= 8;
+        --nwin;
+        ++pos;
+        return byte;
+    };
+    bool ok = true;
+    if (k == 0u) {
+        ok = len == 0u;
+    } else {
+        uint32_t x = take() << 24;
+        x |= take() << 16;
+        x |= take() << 8;
+        x |= take();
+        for (uint32_t i = 0; i < k; ++i) {
+            const uint32_t slot12 = x & (kProbScale - 1u);
+            uint32_t s = c2s[slot12];
+            const uint32_t fc = symtab[s];
+            x = (fc & 0xFFFFu) * (x >> kProbBits) + slot12 - (fc >> 16);
+            if (x < kRansL) x = (x << 8) | take();
+            if (x < kRansL) x = (x << 8) | take();
+            if (WIDE && s == 255u) {
+                s += x & kSplitWideMaxResidual;
+                x >>= 12;
+                if (x < kRansL) x = (x << 8) | take();
+                if (x < kRansL) x = (x << 8) | take();
+            }
+            if (i - i_lo < kept)
+                sym[(size_t)(uint32_t)(walk.t - t_lo) * rj.plane_pitch + (size_t)walk.y * rj.row_pitch + walk.x] = (BandSym<WIDE>)s;
+            walk.forward();
+        }
+        ok = x == kRansL && pos == len;
+    }
+    if (!ok) *job.flags = kSplitBadLane;
+}
+
+// ----------------------------------------------------------------------------------
 // Container header, one workgroup per chunk; any alignment, byte stores.
 // ----------------------------------------------------------------------------------
 namespace {
@@ -469,6 +588,12 @@ void launch_band_write(const SplitBandJob* d_jobs, int n_jobs, uint32_t max_bloc
 }
 void launch_band_decode(const SplitBandJob* d_jobs, int n_jobs, uint32_t max_blocks, bool wide, hipStream_t st) {
     launch_band_lanes(band_decode_kernel<false>, band_decode_kernel<true>, wide, d_jobs, n_jobs, max_blocks, st);
+}
+void launch_band_range_decode(const SplitBandRangeJob* d_jobs, int n_jobs, uint32_t max_blocks, bool wide, hipStream_t st) {
+    if (n_jobs <= 0 || !max_blocks) return;
+    const dim3 grid((max_blocks + 3u) / 4u, (unsigned)n_jobs);
+    if (wide) hipLaunchKernelGGL(band_range_decode_kernel<true>, grid, dim3(256), 0, st, d_jobs);
+    else hipLaunchKernelGGL(band_range_decode_kernel<false>, grid, dim3(256), 0, st, d_jobs);
 }
 void launch_band_headers(const BandHeaderDesc* d_descs, int n_chunks, hipStream_t st) {
     if (n_chunks > 0) hipLaunchKernelGGL(band_header_kernel, dim3(n_chunks), dim3(256), 0, st, d_descs);

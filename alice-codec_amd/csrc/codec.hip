@@ -7255,3 +7255,307 @@ int alice_codec_dev_band_histograms(const void* d_symbols, uint32_t width, uint3
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// PART 13: frame ranges and half-size previews of a banded chunk (kernels: band_range_decode_kernel of
+// band.hip, the finishes of PART 8 and PART 9 unchanged)
+//
+// A band's symbols are the raster [t''][y''][x''] of its octant, so the coefficient planes t'' in [a/2, b/2) of a band are ONE
+// run of band-order symbols, [a/2 Q, b/2 Q) with Q = hw hh, and that run and the blocks that hold it are the same for every
+// band and channel.  A frame range keeps the run of all eight bands and stores it where the virtual chunk of b - a frames has
+// that band (the volume inverse_window reads); a preview keeps bands 0 and 4 alone, which ARE the low-low quadrants of the
+// window's planes, and stores them as the compact volume launch_preview_inverse reads.  The windows, the output sizes, the
+// range checks and both finishes are PART 8's and PART 9's.
+// ------------------------------------------------------------------------------------------
+
+namespace {
+
+enum BandPartialKind : int { kBandFrames = 0, kBandPreview = 1 };
+
+struct BandPartialPlan {
+    uint32_t a = 0, b = 0;                   // section 14.1's window
+    uint32_t idx_lo = 0, idx_hi = 0;         // the kept band-order indices of every kept band
+    uint32_t blk_first = 0, blk_count = 0;   // the planned blocks of every kept band
+    bool kept[8] = {};
+    uint32_t n_kept = 0;                     // bands per channel
+    uint64_t stored = 0;                     // symbols of a channel that are stored
+};
+
+BandPartialPlan band_partial_plan(BandPartialKind kind, const BandHeader& h, const ChunkDims& d, uint32_t first, uint32_t count) {
+    BandPartialPlan p;
+    axis_window(frames_halo(h.wavelet), d.pf, first, (uint64_t)first + count, &p.a, &p.b);
+    const uint64_t Q = (d.pw / 2) * (d.ph / 2), B = 64ull * h.lane_symbols;
+    p.idx_lo = (uint32_t)(p.a / 2 * Q); p.idx_hi = (uint32_t)(p.b / 2 * Q);    // at most n_band < 2^29
+    p.blk_first = (uint32_t)(p.idx_lo / B);
+    p.blk_count = (uint32_t)((p.idx_hi + B - 1) / B) - p.blk_first;
+    for (int k = 0; k < 8; ++k) p.kept[k] = kind == kBandFrames || (k & 3) == 0;
+    p.n_kept = kind == kBandFrames ? 8u : 2u;
+    p.stored = (uint64_t)(p.b - p.a) * (kind == kBandFrames ? d.pw * d.ph : Q);
+    return p;
+}
+
+// What the calling thread's last call of each kind planned and did: the test hooks of alice_codec_test.h read these
+struct BandPartialStats { uint64_t a, b, blocks, uploaded, frames, stored; };
+thread_local BandPartialStats tl_band_partial_stats[2] = {};
+
+int band_partial_done(BandPartialKind kind, const BandPartialPlan& p, uint32_t count, uint64_t uploaded, hipStream_t st) {
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    tl_band_partial_stats[kind] = BandPartialStats{p.a, p.b, 3ull * p.n_kept * p.blk_count, uploaded, count, 3 * p.stored};
+    return kOk;
+}
+
+// The checks of the four calls after the null checks: the header in section 20.3's order, then the range as PART 8 has it
+int band_partial_validate(const uint8_t* data, uint64_t len, uint32_t first, uint32_t count, BandHeader& h, ChunkDims& d) {
+    TRY(parse_band_header(data, len, h, &d));
+    SplitHeader range;
+    range.frames = h.frames;
+    return frames_validate_range(range, d, first, count);
+}
+
+// The lane stage: the planned blocks of the kept bands of the container at d_alc (device, h validated) are decoded and the
+// kept run of channel c, band k stored at d_sym + (c * chan_stride + origin[k]) symbols with the pitches given.  All jobs
+// (the 24 scan jobs and the range jobs behind them) go up in one copy while nothing of the call is queued yet; the scan runs
+// over all 24 block-length tables, so a corrupt entry is refused wherever it is; the verdict of the end checks comes before
+// the caller queues anything that writes its output.  Stream numbers in a verdict are 8 channel + band.
+struct BandLaneStage {
+    DevBuf jobs;                 // (before w: w's destructor drains the stream that reads them)
+    std::vector<uint8_t> up;
+    SplitWork w;
+};
+
+int band_partial_lane_decode(BandLaneStage& ls, const BandHeader& h, const ChunkDims& d, const BandPartialPlan& p, const uint8_t* d_alc,
+                             uint8_t* d_sym, uint64_t chan_stride, const uint64_t origin[8], uint64_t row_pitch, uint64_t plane_pitch,
+                             hipStream_t st) {
+    const bool wide = is_wide(h.fmt);
+    const size_t sb = wide ? 2 : 1;
+    const uint32_t n_range = 3 * p.n_kept;
+    SplitWork& w = ls.w;
+    TRY(split_work_alloc(w, 24, d.padded / 8, h.lane_symbols, false, h.fmt));
+    const size_t range_at = 24 * sizeof(SplitJob);
+    static_assert(sizeof(SplitJob) % alignof(SplitBandRangeJob) == 0, "the range jobs lie behind the scan jobs");
+    ls.up.resize(range_at + n_range * sizeof(SplitBandRangeJob));
+    TRY(ls.jobs.alloc(ls.up.size()));
+    // the kept bands' tables are w.tables[0 .. n_range), in job order
+    w.h_freq.assign((size_t)n_range * 256, 0);
+    w.h_cum.assign((size_t)n_range * 256, 0);
+    uint64_t off = kBandHeaderBytes;
+    uint32_t r = 0;
+    for (int j = 0; j < 24; ++j) {
+        SplitJob& s = w.h[(size_t)j];
+        const int c = j / 8, k = j % 8;
+        s.stream = (uint8_t*)d_alc + off;
+        s.len = h.payload_len[j];
+        off += h.payload_len[j];
+        s.sym = nullptr;
+        if (!p.kept[k]) continue;
+        memcpy(&w.h_freq[(size_t)r * 256], h.freq[j], 256 * sizeof(uint16_t));
+        uint32_t run = 0;
+        for (int i = 0; i < 256; ++i) { w.h_cum[(size_t)r * 256 + i] = (uint16_t)run; run += h.freq[j][i]; }
+        SplitBandRangeJob rj{};
+        rj.j = s;
+        rj.j.table = w.tables.as<RansTable>() + r;
+        rj.j.sym = d_sym + ((size_t)c * chan_stride + origin[k]) * sb;
+        rj.hw = (uint32_t)(d.pw / 2); rj.hh = (uint32_t)(d.ph / 2);
+        rj.row_pitch = row_pitch; rj.plane_pitch = plane_pitch;
+        rj.blk_first = p.blk_first; rj.blk_count = p.blk_count;
+        rj.idx_lo = p.idx_lo; rj.idx_hi = p.idx_hi;
+        memcpy(ls.up.data() + range_at + (size_t)r * sizeof(rj), &rj, sizeof(rj));
+        ++r;
+    }
+    memcpy(ls.up.data(), w.h.data(), range_at);
+    w.st = st; w.armed = true;
+    HIP_TRY(hipMemcpyAsync(ls.jobs.p, ls.up.data(), ls.up.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(w.freq.p, w.h_freq.data(), w.h_freq.size() * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(w.cum.p, w.h_cum.data(), w.h_cum.size() * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(w.flags.p, 0, 24 * sizeof(uint32_t), st));
+    launch_rans_tables_from_arrays(w.cum.as<uint16_t>(), w.freq.as<uint16_t>(), w.tables.as<RansTable>(), (int)n_range, st);
+    launch_split_scan(ls.jobs.as<SplitJob>(), 24, true, nullptr, st);
+    launch_band_range_decode((const SplitBandRangeJob*)(ls.jobs.as<uint8_t>() + range_at), (int)n_range, p.blk_count, wide, st);
+    HIP_TRY(hipGetLastError());
+    return split_decode_verdict(w, st);
+}
+
+// Frames [first, first + count) of the banded container at d_alc (device; h and the range validated) to `out`.  The kept runs
+// are the symbol volume of the virtual chunk of b - a frames (rect_decode_device's whole-frame case); returns after the
+// stream has drained.
+int band_frames_decode_device(const BandHeader& h, const ChunkDims& d, const BandPartialPlan& p, const uint8_t* d_alc, uint32_t first,
+                              uint32_t count, const RgbLayout& out, hipStream_t st, uint64_t uploaded) {
+    const bool wide = is_wide(h.fmt);
+    const size_t sb = wide ? 2 : 1;
+    const ChunkDims dv = make_dims(h.width, h.height, p.b - p.a);
+    const ChunkDims dx = make_dims(dv.w, dv.h, count);
+    DecodeWork dw;
+    dw.d = dv; dw.n_chunks = 1;
+    TRY(dw.sym.alloc(3 * dv.padded * sb));
+    if (transform_tiles_eligible(dv))
+        TRY(dw.scratch_own.alloc(inverse_scratch_bytes(dx, inverse_bounds(h.wavelet, h.step, wide ? kWideMaxQ : kByteMaxQ).mid16)));
+    const uint64_t hw = d.pw / 2, hh = d.ph / 2, half = (p.b - p.a) / 2;
+    uint64_t origin[8];
+    for (int k = 0; k < 8; ++k) origin[k] = ((uint64_t)((k >> 2) & 1) * half * d.ph + (uint64_t)((k >> 1) & 1) * hh) * d.pw + (uint64_t)(k & 1) * hw;
+    BandLaneStage ls;
+    TRY(band_partial_lane_decode(ls, h, d, p, d_alc, dw.sym.as<uint8_t>(), dv.padded, origin, d.pw, d.pw * d.ph, st));
+    TRY(inverse_window(dw.sym.as<uint8_t>(), dv, first - p.a, first - p.a + count, h.wavelet, h.step, dw.scratch_own.p, dw, out, st, h.fmt));
+    return band_partial_done(kBandFrames, p, count, uploaded, st);
+}
+
+// The preview of frames [first, first + count) of the banded container at d_alc to d_rgb (count * hh * hw * 3 bytes): bands 0
+// and 4 as the compact volume [ch][b - a][pitch] of PART 9.  Returns after the stream has drained.
+int band_preview_decode_device(const BandHeader& h, const ChunkDims& d, const BandPartialPlan& p, const uint8_t* d_alc, uint32_t first,
+                               uint32_t count, void* d_rgb, hipStream_t st, uint64_t uploaded) {
+    const bool wide = is_wide(h.fmt);
+    const size_t sb = wide ? 2 : 1;
+    const uint32_t planes = p.b - p.a;
+    const uint64_t hw = d.pw / 2, quadrant = hw * (d.ph / 2), pitch = round_up(quadrant, 4);
+    // (the pad symbols of a plane are never stored and need no value: preview_decode_device)
+    DevBuf d_sym;
+    TRY(d_sym.alloc(3 * (size_t)planes * pitch * sb));
+    uint64_t origin[8] = {};
+    origin[4] = (uint64_t)(planes / 2) * pitch;
+    BandLaneStage ls;
+    TRY(band_partial_lane_decode(ls, h, d, p, d_alc, d_sym.as<uint8_t>(), (uint64_t)planes * pitch, origin, hw, pitch, st));
+    const InverseBounds ib = inverse_bounds(h.wavelet, h.step, wide ? kWideMaxQ : kByteMaxQ);
+    if (!launch_preview_inverse(d_sym.p, pitch, quadrant, planes, FrameWindow{first - p.a, first - p.a + count}, (int)h.fmt, h.wavelet, h.step,
+                                ib.exact, (uint8_t*)d_rgb, st))
+        return fail(kInternal, "preview: no finish kernel for this volume");
+    return band_partial_done(kBandPreview, p, count, uploaded, st);
+}
+
+// The spans of a banded container in host memory that go up for a plan: the header, the 24 block-length tables (with
+// section 20.3's directory checks applied to all of them on the way) and, per kept band, the one byte run of its planned blocks.
+int band_partial_spans(const uint8_t* data, const BandHeader& h, const BandPartialPlan& p, std::vector<PartialSpan>& spans,
+                       uint64_t& payload_bytes) {
+    spans.push_back({0, kBandHeaderBytes});
+    uint64_t pos = kBandHeaderBytes;
+    payload_bytes = 0;
+    for (int j = 0; j < 24; ++j) {
+        const std::string bk = "channel " + std::to_string(j / 8) + " band " + std::to_string(j % 8) + ": ";
+        const uint8_t* tab = data + pos;
+        const uint32_t nb = h.n_blocks[j];
+        uint64_t sum = 4ull * nb, run_off = 0, run_len = 0;
+        for (uint32_t blk = 0; blk < nb; ++blk) {
+            const uint32_t v = get_u32(tab + 4ull * blk);
+            if (v < 128u) return fail(kInvalidBitstream, bk + "block " + std::to_string(blk) + " is shorter than its lane directory");
+            if (blk == p.blk_first) run_off = sum;
+            if (blk - p.blk_first < p.blk_count) run_len += v;
+            sum += v;
+        }
+        if (sum != h.payload_len[j])
+            return fail(kInvalidBitstream, bk + "block lengths sum to " + std::to_string(sum) + ", payload_len is " + std::to_string(h.payload_len[j]));
+        spans.push_back({pos, 4ull * nb});
+        if (p.kept[j % 8] && run_len) {      // (inside the payload: the lengths sum to it)
+            spans.push_back({pos + run_off, run_len});
+            payload_bytes += run_len;
+        }
+        pos += h.payload_len[j];
+    }
+    return kOk;
+}
+
+// The host calls: validated header and plan, the spans to their own offsets of a pool buffer of the container's size, the
+// device path on it, the result down.  device(d_alc, d_rgb, stream, uploaded payload bytes) decodes `bytes` bytes to d_rgb.
+template <typename Device>
+int band_partial_decode_host(const uint8_t* data, uint64_t len, const BandHeader& h, const BandPartialPlan& p, uint64_t bytes, uint8_t** result,
+                             uint64_t* out_len, Device device) {
+    std::vector<PartialSpan> spans;
+    uint64_t payload_bytes = 0;
+    TRY(band_partial_spans(data, h, p, spans, payload_bytes));
+    std::unique_ptr<uint8_t, decltype(&free)> out(host_result_alloc(bytes), &free);   // freed on every failure below
+    if (!out) return fail(kOutOfMemory, "out of host memory");
+    hipStream_t st;
+    TRY(get_stream(&st));
+    DevBuf d_alc, d_rgb;
+    StreamDrain drain(st);
+    TRY(d_alc.alloc(len));
+    TRY(d_rgb.alloc(bytes));
+    for (const PartialSpan& s : spans)
+        if (s.len) HIP_TRY(hipMemcpyAsync(d_alc.as<uint8_t>() + s.off, data + s.off, s.len, hipMemcpyHostToDevice, st));
+    TRY(device(d_alc.as<uint8_t>(), d_rgb.p, st, payload_bytes));
+    TRY(copy_to_host(out.get(), d_rgb.p, bytes, st));
+    *out_len = bytes;
+    *result = out.release();
+    return kOk;
+}
+
+// The device calls: the null checks, the header read back and validated with the range, then decode(h, d, stream).  Nothing
+// is queued before the header and the range have been accepted.
+template <typename Decode>
+int band_partial_decode_dev(const void* d_alc, uint64_t len, uint32_t first, uint32_t count, const void* d_rgb_out, void* hip_stream, Decode decode) {
+    clear_error();
+    if (!d_alc || !d_rgb_out) return fail(kNullArgument, "null argument");
+    TRY(ensure_device());
+    hipStream_t st = (hipStream_t)hip_stream;
+    ScopeStream scope(st);
+    std::vector<uint8_t> raw(kBandHeaderBytes, 0);
+    if (len) {
+        HIP_TRY(hipMemcpyAsync(raw.data(), d_alc, std::min<uint64_t>(len, kBandHeaderBytes), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    BandHeader h;
+    ChunkDims d{};
+    TRY(band_partial_validate(raw.data(), len, first, count, h, d));
+    return decode(h, d, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+int alice_codec_dev_decode_banded_frames(const void* d_alc, uint64_t len, uint32_t first, uint32_t count, void* d_rgb_out, void* hip_stream) {
+    return band_partial_decode_dev(d_alc, len, first, count, d_rgb_out, hip_stream, [&](const BandHeader& h, const ChunkDims& d, hipStream_t st) {
+        return band_frames_decode_device(h, d, band_partial_plan(kBandFrames, h, d, first, count), (const uint8_t*)d_alc, first, count,
+                                         RgbLayout{(uint8_t*)d_rgb_out, 3ull * h.width, 3ull * h.width * h.height}, st, 0);
+    });
+}
+
+uint8_t* alice_codec_decode_banded_frames(const uint8_t* data, uint64_t len, uint32_t first, uint32_t count, uint64_t* out_len) {
+    clear_error();
+    if (!data || !out_len) { fail(kNullArgument, "null argument"); return nullptr; }
+    BandHeader h;
+    ChunkDims d{};
+    if (band_partial_validate(data, len, first, count, h, d) != kOk) return nullptr;
+    const BandPartialPlan p = band_partial_plan(kBandFrames, h, d, first, count);
+    uint8_t* out = nullptr;
+    band_partial_decode_host(data, len, h, p, (uint64_t)h.width * h.height * count * 3, &out, out_len,
+                             [&](const uint8_t* d_alc, void* d_rgb, hipStream_t st, uint64_t uploaded) {
+                                 return band_frames_decode_device(h, d, p, d_alc, first, count,
+                                                                  RgbLayout{(uint8_t*)d_rgb, 3ull * h.width, 3ull * h.width * h.height}, st, uploaded);
+                             });
+    return out;
+}
+
+int alice_codec_dev_decode_banded_preview(const void* d_alc, uint64_t len, uint32_t first, uint32_t count, void* d_rgb_out, void* hip_stream) {
+    return band_partial_decode_dev(d_alc, len, first, count, d_rgb_out, hip_stream, [&](const BandHeader& h, const ChunkDims& d, hipStream_t st) {
+        return band_preview_decode_device(h, d, band_partial_plan(kBandPreview, h, d, first, count), (const uint8_t*)d_alc, first, count,
+                                          d_rgb_out, st, 0);
+    });
+}
+
+uint8_t* alice_codec_decode_banded_preview(const uint8_t* data, uint64_t len, uint32_t first, uint32_t count, uint64_t* out_len) {
+    clear_error();
+    if (!data || !out_len) { fail(kNullArgument, "null argument"); return nullptr; }
+    BandHeader h;
+    ChunkDims d{};
+    if (band_partial_validate(data, len, first, count, h, d) != kOk) return nullptr;
+    const BandPartialPlan p = band_partial_plan(kBandPreview, h, d, first, count);
+    uint8_t* out = nullptr;
+    band_partial_decode_host(data, len, h, p, (d.pw / 2) * (d.ph / 2) * count * 3, &out, out_len,
+                             [&](const uint8_t* d_alc, void* d_rgb, hipStream_t st, uint64_t uploaded) {
+                                 return band_preview_decode_device(h, d, p, d_alc, first, count, d_rgb, st, uploaded);
+                             });
+    return out;
+}
+
+void alice_codec_test_last_banded_frames_stats(uint64_t out[6]) {
+    const BandPartialStats& s = tl_band_partial_stats[kBandFrames];
+    const uint64_t v[6] = {s.a, s.b, s.blocks, s.uploaded, s.frames, s.stored};
+    if (out) memcpy(out, v, sizeof(v));
+}
+
+void alice_codec_test_last_banded_preview_stats(uint64_t out[6]) {
+    const BandPartialStats& s = tl_band_partial_stats[kBandPreview];
+    const uint64_t v[6] = {s.a, s.b, s.blocks, s.uploaded, s.frames, s.stored};
+    if (out) memcpy(out, v, sizeof(v));
+}
+
+}  // extern "C"

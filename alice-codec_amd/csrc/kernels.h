@@ -427,6 +427,17 @@ struct SplitBandJob {
     SplitJob j;
     uint32_t pw, ph, hw, hh;
 };
+// A plane range of one band (frame ranges and previews of .alc v5): `j` is the band's job as in
+// SplitBandJob, but the blocks [blk_first, blk_first + blk_count) alone are decoded, and the symbol of band-order index idx =
+// (t'' hh + y'') hw + x'' is stored only for idx in [idx_lo, idx_hi), at j.sym[(t'' - idx_lo / (hw hh)) * plane_pitch +
+// y'' * row_pitch + x'']: j.sym is where the symbol of index idx_lo goes (idx_lo a multiple of hw hh).
+struct SplitBandRangeJob {
+    SplitJob j;
+    uint32_t hw, hh;
+    unsigned long long row_pitch, plane_pitch;   // of the destination, in symbols
+    uint32_t blk_first, blk_count;
+    uint32_t idx_lo, idx_hi;
+};
 struct SplitHeaderDesc {
     uint8_t* out;
     uint32_t width, height, frames, lane_symbols, num_symbols, n_blocks;
@@ -477,6 +488,8 @@ void launch_band_count(const SplitBandJob* d_jobs, int n_jobs, uint32_t max_bloc
 void launch_band_write(const SplitBandJob* d_jobs, int n_jobs, uint32_t max_blocks, bool wide, hipStream_t st);
 void launch_band_decode(const SplitBandJob* d_jobs, int n_jobs, uint32_t max_blocks, bool wide, hipStream_t st);
 void launch_band_headers(const BandHeaderDesc* d_descs, int n_chunks, hipStream_t st);
+// after scan(from_stream = true) over the same bands' SplitJob parts; max_blocks: the largest blk_count among the jobs
+void launch_band_range_decode(const SplitBandRangeJob* d_jobs, int n_jobs, uint32_t max_blocks, bool wide, hipStream_t st);
 
 // ---- quality.hip: exact squared error of two RGB volumes ----
 constexpr uint32_t kSseBlock = 256;               // lanes of a workgroup

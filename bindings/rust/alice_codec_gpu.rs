@@ -1702,3 +1702,56 @@ pub unsafe fn band_histograms_device(d_symbols: *const std::ffi::c_void, width: 
                                      d_hist: *mut std::ffi::c_void, hip_stream: *mut std::ffi::c_void) -> Result<(), CodecError> {
     check(alice_codec_dev_band_histograms(d_symbols, width, height, frames, wide as c_int, d_hist, hip_stream), 0, 0)
 }
+
+// ---- frame ranges and half-size previews of a version 5 chunk ----
+
+extern "C" {
+    fn alice_codec_decode_banded_frames(data: *const u8, len: u64, first: u32, count: u32, out_len: *mut u64) -> *mut u8;
+    fn alice_codec_dev_decode_banded_frames(d_alc: *const std::ffi::c_void, len: u64, first: u32, count: u32,
+                                            d_rgb_out: *mut std::ffi::c_void, hip_stream: *mut std::ffi::c_void) -> c_int;
+    fn alice_codec_decode_banded_preview(data: *const u8, len: u64, first: u32, count: u32, out_len: *mut u64) -> *mut u8;
+    fn alice_codec_dev_decode_banded_preview(d_alc: *const std::ffi::c_void, len: u64, first: u32, count: u32,
+                                             d_rgb_out: *mut std::ffi::c_void, hip_stream: *mut std::ffi::c_void) -> c_int;
+}
+
+/// The RGB bytes of frames `[first, first + count)` of a version 5 container, bit for bit
+/// `decode_frames(&from_banded(data, 0)?, first, count)`: of every band only the blocks that hold coefficient planes of the
+/// range's window are read.  The end checks cover the blocks that are read.
+pub fn decode_banded_frames(data: &[u8], first: u32, count: u32) -> Result<Vec<u8>, CodecError> {
+    let mut n = 0u64;
+    unsafe {
+        let p = alice_codec_decode_banded_frames(data.as_ptr(), data.len() as u64, first, count, &mut n);
+        if p.is_null() { Err(last_error(0, data.len(), 0, 0, 0)) } else { Ok(take(p, n)) }
+    }
+}
+
+/// `decode_banded_frames` of a device-resident container of `length` bytes into `count` packed frames at `d_rgb_out`.
+///
+/// # Safety
+/// As `frames_decode_device`.
+pub unsafe fn banded_frames_decode_device(d_alc: *const std::ffi::c_void, length: u64, first: u32, count: u32,
+                                          d_rgb_out: *mut std::ffi::c_void, hip_stream: *mut std::ffi::c_void)
+    -> Result<(), CodecError> {
+    check(alice_codec_dev_decode_banded_frames(d_alc, length, first, count, d_rgb_out, hip_stream), 0, 0)
+}
+
+/// The half-resolution RGB bytes (`count * qh * qw * 3`, `preview_dims`) of frames `[first, first + count)` of a version 5
+/// container, bit for bit `decode_preview(&from_banded(data, 0)?, first, count)`: bands 0 and 4 are the low-low quadrants,
+/// so only their blocks inside the window are read.
+pub fn decode_banded_preview(data: &[u8], first: u32, count: u32) -> Result<Vec<u8>, CodecError> {
+    let mut n = 0u64;
+    unsafe {
+        let p = alice_codec_decode_banded_preview(data.as_ptr(), data.len() as u64, first, count, &mut n);
+        if p.is_null() { Err(last_error(0, data.len(), 0, 0, 0)) } else { Ok(take(p, n)) }
+    }
+}
+
+/// `decode_banded_preview` of a device-resident container of `length` bytes into `count` packed preview frames.
+///
+/// # Safety
+/// As `preview_decode_device`.
+pub unsafe fn banded_preview_decode_device(d_alc: *const std::ffi::c_void, length: u64, first: u32, count: u32,
+                                           d_rgb_out: *mut std::ffi::c_void, hip_stream: *mut std::ffi::c_void)
+    -> Result<(), CodecError> {
+    check(alice_codec_dev_decode_banded_preview(d_alc, length, first, count, d_rgb_out, hip_stream), 0, 0)
+}

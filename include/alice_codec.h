@@ -967,6 +967,22 @@ int alice_codec_dev_from_banded(const void *d_alc, uint64_t alc_stride, const ui
  * 3 x 8 x 256 u32 on the device (overwritten): the histogram of every band, wide: of min(z, 255).  Finished on return. */
 int alice_codec_dev_band_histograms(const void *d_symbols, uint32_t width, uint32_t height, uint32_t frames, int wide,
                                     void *d_hist, void *hip_stream);
+/* Random access into a version 5 chunk: frames [first, first + count) at full size, and their
+ * half-size preview, bit for bit what alice_codec_decode_frames / alice_codec_decode_preview give on
+ * alice_codec_from_banded(data).  Only the blocks that hold coefficient planes of the window (alice_codec_frames_window) are
+ * entropy-decoded: of all eight bands for the frames, of bands 0 and 4 alone for the preview; the host calls upload the
+ * header, the 24 block-length tables and those blocks (data may be a mapped file).  Output sizes: width * height * count * 3
+ * bytes, and qw * qh * count * 3 bytes with alice_codec_preview_dims' qw and qh.  Validation: null arguments, the header in
+ * the order of DESIGN.md 20.3 (another version: "unsupported version: N (expected 5)"), then the range as
+ * alice_codec_decode_frames has it; a chunk without pixels refuses every range.  Every block-length table is checked, the end
+ * checks cover the decoded blocks ("stream j", j = 8 * channel + band); a refused call writes nothing of its output.  The
+ * device calls read the header back first, take d_alc at any byte alignment and return after their work has drained. */
+uint8_t *alice_codec_decode_banded_frames(const uint8_t *data, uint64_t len, uint32_t first, uint32_t count, uint64_t *out_len);
+int alice_codec_dev_decode_banded_frames(const void *d_alc, uint64_t len, uint32_t first, uint32_t count, void *d_rgb_out,
+                                         void *hip_stream);
+uint8_t *alice_codec_decode_banded_preview(const uint8_t *data, uint64_t len, uint32_t first, uint32_t count, uint64_t *out_len);
+int alice_codec_dev_decode_banded_preview(const void *d_alc, uint64_t len, uint32_t first, uint32_t count, void *d_rgb_out,
+                                          void *hip_stream);
 
 #ifdef __cplusplus
 }

@@ -1249,5 +1249,35 @@ inline std::vector<uint64_t> from_banded_device(const void* d_alc, uint64_t alc_
 inline void band_histograms_device(const void* d_symbols, uint32_t w, uint32_t h, uint32_t f, bool wide, void* d_hist, void* hip_stream = nullptr) {
     detail::check(alice_codec_dev_band_histograms(d_symbols, w, h, f, wide ? 1 : 0, d_hist, hip_stream));
 }
+// random access into a version 5 chunk: frames [first, first + count) and their half-size preview from the blocks of the
+// range's window alone, bit for bit decode_frames / decode_preview of from_banded(data)
+inline std::vector<uint8_t> decode_banded_frames(const uint8_t* data, uint64_t len, uint32_t first, uint32_t count) {
+    static const uint8_t empty = 0;
+    uint64_t n = 0;
+    uint8_t* p = alice_codec_decode_banded_frames(data ? data : &empty, data ? len : 0, first, count, &n);
+    if (!p) detail::raise(ALICE_ERR_INVALID_BITSTREAM);
+    return detail::take(p, n);
+}
+inline std::vector<uint8_t> decode_banded_frames(const std::vector<uint8_t>& data, uint32_t first, uint32_t count) {
+    return decode_banded_frames(data.empty() ? nullptr : data.data(), data.size(), first, count);
+}
+inline void banded_frames_decode_device(const void* d_alc, uint64_t length, uint32_t first, uint32_t count, void* d_rgb_out,
+                                        void* hip_stream = nullptr) {
+    detail::check(alice_codec_dev_decode_banded_frames(d_alc, length, first, count, d_rgb_out, hip_stream));
+}
+inline std::vector<uint8_t> decode_banded_preview(const uint8_t* data, uint64_t len, uint32_t first, uint32_t count) {
+    static const uint8_t empty = 0;
+    uint64_t n = 0;
+    uint8_t* p = alice_codec_decode_banded_preview(data ? data : &empty, data ? len : 0, first, count, &n);
+    if (!p) detail::raise(ALICE_ERR_INVALID_BITSTREAM);
+    return detail::take(p, n);
+}
+inline std::vector<uint8_t> decode_banded_preview(const std::vector<uint8_t>& data, uint32_t first, uint32_t count) {
+    return decode_banded_preview(data.empty() ? nullptr : data.data(), data.size(), first, count);
+}
+inline void banded_preview_decode_device(const void* d_alc, uint64_t length, uint32_t first, uint32_t count, void* d_rgb_out,
+                                         void* hip_stream = nullptr) {
+    detail::check(alice_codec_dev_decode_banded_preview(d_alc, length, first, count, d_rgb_out, hip_stream));
+}
 
 }  // namespace alice_codec

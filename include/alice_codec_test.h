@@ -222,6 +222,13 @@ int alice_codec_test_rects_outputs_disjoint(const alice_codec_rect_item *items, 
 int alice_codec_test_symbol_bins(const void *d_symbols, uint64_t n, int wide, int32_t step_from, void *d_bins, void *d_oor,
                                  void *hip_stream);
 
+/* The last alice_codec_decode_banded_frames / alice_codec_dev_decode_banded_frames (and the same for the preview) of the
+ * calling thread that ran to its end: out = {a, b of the window, blocks decoded summed over the three channels and the kept
+ * bands (8 for frames, 2 for a preview), payload bytes the host call uploaded (the planned blocks of the kept bands; 0 for
+ * the device call), frames written, symbols stored over the three channels (3 (b - a) pw ph, preview: 3 (b - a) hw hh)}. */
+void alice_codec_test_last_banded_frames_stats(uint64_t out[6]);
+void alice_codec_test_last_banded_preview_stats(uint64_t out[6]);
+
 #ifdef __cplusplus
 }
 #endif
